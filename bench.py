@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W                        one process drives N GPUs (bf_group)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   one rank per GPU (bf_comm)
+    python bench.py ... --dump-outputs DIR                               + what the last timed step computed, as DIR/<name>.npy
 
 One "step" = one complete fit of every GPU's frames, as SURVEY.md 8(d) defines the metric ("includes per-frame input upload
 and result download"): the NEXT frame's keypoints and initial estimate go from host memory to the device
@@ -76,7 +77,41 @@ def parse():
     ap.add_argument("--force-ranks", action="store_true", help="run the one-process-per-GPU code path (bf_comm: file rendezvous, ncclCommInitRank, barrier, gather) even with WORLD_SIZE 1")
     ap.add_argument("--force-group", action="store_true", help="drive even ONE GPU through bf_group (the N-GPU code path, incl. its RCCL all-gather with one rank): a 1-GPU box's check of what --gpus N runs")
     ap.add_argument("--frame-sets", type=int, default=16, help="distinct frame sets resident on the host that the steps cycle over")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32, "
+                                                          "at most 64 MB in all: a fixed, seeded sample of each array beyond that)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BYTES = 64_000_000
+
+
+def job_outputs(batches, gathered=None, displacement=False):
+    """What a caller of the timed path receives from its last step, over the job's batches in frame order: the fitted parameters
+    (`gathered`: the job's all-gather of them, when it has one), the final mesh, the joints, the full pose, the loss terms, and for
+    config 5 the SMPL+D displacements."""
+    res = [b.get_result() for b in batches]
+    out = {"params": gathered if gathered is not None else np.concatenate([b.get_params() for b in batches]),
+           "vertices": np.concatenate([r[0] for r in res]), "joints": np.concatenate([r[1] for r in res]),
+           "full_pose": np.concatenate([r[2] for r in res]), "loss_terms": np.concatenate([r[3] for r in res])}
+    if displacement:
+        out["displacement"] = np.concatenate([b.get_displacement() for b in batches])
+    return out
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy per array.  Beyond DUMP_BYTES in all, every array keeps the same share of its elements, picked by a fixed seed
+    (flattened, in index order): two runs with the same arguments write the same elements."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for k, v in arrays.items():
+        if total > DUMP_BYTES:
+            idx = np.random.default_rng(0).choice(v.size, v.size * DUMP_BYTES // total, replace=False)
+            v = v.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 _PROBLEMS = {}
@@ -369,7 +404,7 @@ def main_dense(a):
         job.sync()
         return None
 
-    steps, warmup, repeats = min(a.steps, 5 if cfg == 3 else 3), min(a.warmup, 1), min(a.repeats, 3)
+    steps, warmup, repeats = a.steps, min(a.warmup, 1), min(a.repeats, 3)
     run(max(1, warmup))
     walls, gathered = [], None
     for _ in range(repeats):
@@ -384,6 +419,8 @@ def main_dense(a):
     if gathered is not None:
         assert gathered.shape == (n_total, dev.n_params) and np.isfinite(gathered).all()
         assert len(np.unique(gathered[:, 4:14], axis=0)) == n_total
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, job_outputs(group.batches if group else [batch], gathered, displacement=cfg == 5))
     for _ in range(2):
         step(timed_parts=True)
     per = {k: parts[k] / parts["n"] * 1e3 for k in ("upload_s", "fit_s", "disp_s")}
@@ -528,6 +565,9 @@ def main():
         est = reduce_max(est)                              # (ranks mode: every rank must take the same decision - the brackets hold barriers)
         if est * a.steps < 0.05:
             repeats = 11
+    if feed is not None:
+        # the last timed step fits the feed's last frame set whatever the estimate above chose: the same inputs in every run
+        feed.at = -(a.warmup + repeats * a.steps) % len(feed.sets)
     walls, gathered = timed_brackets(job, a.steps, a.warmup, a.iters, flags, repeats, barrier, finish, reduce_max, feed)
     wall = statistics.median(walls)
 
@@ -550,6 +590,8 @@ def main():
         lo, hi = (group.shards[0][1], group.shards[0][1] + group.shards[0][2]) if group else shard.shard_range(n_total, rank, n_gpus)
         assert gathered.shape == (n_total, dev.n_params) and np.array_equal(gathered[lo:hi], mine)
         assert np.isfinite(gathered).all() and len(np.unique(gathered[:, 4:14], axis=0)) == n_total     # every frame is a different fit
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, job_outputs(group.batches if group else [batch], gathered))
 
     per_step = [w / a.steps * 1e3 for w in walls]
     value = n_total * a.steps / wall

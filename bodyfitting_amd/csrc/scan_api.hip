@@ -681,9 +681,8 @@ static int ensure_fit_stream(bf_batch *b, const FrameIO &io, const HyperDev &hd)
         if (!told.exchange(true))
             std::fprintf(stderr, "libbodyfit: the resident fit launch is off - its stream shares a hardware queue with the batch stream (self-test "
                                  "verdict %d).  The dense loops (use_mask / use_mesh / SMPL-X) fall back to one fit launch per iteration: same "
-                                 "results, ~3x slower.  HIP multiplexes a process's streams over GPU_MAX_HW_QUEUES hardware queues (default 4; the "
-                                 "library asks for 8 when it is loaded BEFORE HIP initialises): export GPU_MAX_HW_QUEUES=8 before the first HIP "
-                                 "call of the process, or load libbodyfit first.\n", verdict);
+                                 "results, ~3x slower.  HIP multiplexes a process's streams over the hardware queues GPU_MAX_HW_QUEUES allows; "
+                                 "fewer streams elsewhere in the process leave more of them to the batch.\n", verdict);
     }
     return BF_OK;
 }

@@ -1,6 +1,6 @@
 """Dense fits in FRESH processes whose HOST is not the tidy one the library hopes for (tests/test_gpu_hostile_host.py):
-  `hip_first`      the process initialises HIP, allocates and creates streams BEFORE libbodyfit is loaded - so the library's request for
-                   8 hardware queues comes too late - optionally with GPU_MAX_HW_QUEUES pinned to a small value by the 'user';
+  `hip_first`      the process initialises HIP, allocates and creates streams BEFORE libbodyfit is loaded (its streams
+                   then share the queues HIP has already handed out) - optionally with GPU_MAX_HW_QUEUES pinned to a small value by the 'user';
   `busy_neighbour` other streams of the same process keep the device busy (memsets over 256 MB, back to back, from a thread)
                    while the dense loops run.
 Each child fits the same two small jobs - a silhouette loop and a scan loop + SMPL+D, both with the resident fit launch if the

@@ -1,7 +1,7 @@
 """The dense loops on hosts that do not behave: the resident fit launch and the dense kernels talk through doorbells
-across streams, forks and joins ride on dispatch completion signals, and the library asks for more hardware queues when it is loaded -
-all of which assume things about the process around them.  Here the process initialises HIP first (the queue request comes too late,
-or the 'user' has pinned GPU_MAX_HW_QUEUES to 2), or hammers the device from two other streams while the loops run.  Whatever schedule
+across streams, forks and joins ride on dispatch completion signals, and the streams share the process's hardware queues - all of
+which assume things about the process around them.  Here the process initialises HIP first (with GPU_MAX_HW_QUEUES unset, or pinned
+to 2 by the 'user'), or hammers the device from two other streams while the loops run.  Whatever schedule
 the self-tests then choose, the results must be the bits of an undisturbed run - and a fit must never hang or fail."""
 import numpy as np
 import pytest
