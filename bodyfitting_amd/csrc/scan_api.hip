@@ -374,10 +374,12 @@ int bf_batch_set_scans(bf_batch *b, bf_scan *const *scans) {
     if (!b) return fail(BF_ERR_INVALID, "bf_batch_set_scans: null batch");
     HIP_TRY(hipSetDevice(b->m->device));
     { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
-    b->scans_lost = false;                         // (either way the caller has said what this batch's scans are now)
+    // (`scans_lost` is cleared only where the caller has said what this batch's scans are now: on a detach, or once the new scans
+    //  are linked - a rejected array leaves a batch that lost its scans failing its fits)
     if (!scans) {                                  // detach
         std::lock_guard<std::mutex> lk(bf_scan_links());
         bf_batch_unlink_scans(b);
+        b->scans_lost = false;
         return BF_OK;
     }
     std::vector<ScanDev> dev(b->F);
@@ -395,6 +397,7 @@ int bf_batch_set_scans(bf_batch *b, bf_scan *const *scans) {
         }
         b->scans.assign(scans, scans + b->F);
         for (bf_scan *sc : b->scans) sc->holders.push_back(b);
+        b->scans_lost = false;
     }
     b->cface_valid = false;
     // (a capture attaches new scans every frame: the two small tables are written in place - a hipFree waits for the whole device)

@@ -397,6 +397,14 @@ def model_digest(model):
     return h.hexdigest()[:16]
 
 
+def scan_digest(verts, faces):
+    """Short content hash of a scan mesh (float32 vertices, int32 faces), stored next to goldens instead of the scan itself."""
+    h = hashlib.sha256()
+    h.update(np.ascontiguousarray(verts, np.float32).tobytes())
+    h.update(np.ascontiguousarray(faces, np.int32).tobytes())
+    return h.hexdigest()[:16]
+
+
 # ----------------------------------------------------------------------------------------------
 # cameras and per-frame problems
 # ----------------------------------------------------------------------------------------------

@@ -209,8 +209,8 @@ int bf_batch_export_params_dev(bf_batch *b, void *dst_dev);
  * thirdparty/mesh_grid/mesh_grid.cpp:31-52): verts[n_verts,3], faces[n_faces,3] int32. */
 /* ORDER OF DESTRUCTION: a scan may be destroyed while batches still hold it (bf_batch_set_scans): bf_scan_destroy then waits for
  * the device and DETACHES every scan from those batches, which are marked: their next bf_fit / bf_fit_displacement returns
- * BF_ERR_INVALID ("a scan this batch held was destroyed") until bf_batch_set_scans is called again - with NULL to go on without
- * scans (rounds 4-5 let the fit run silently without the closest-point loss).  A batch may be destroyed before its scans.
+ * BF_ERR_INVALID ("a scan this batch held was destroyed") until a bf_batch_set_scans call succeeds - with NULL to go on without
+ * scans; a call that is rejected leaves the mark (rounds 4-5 let the fit run silently without the closest-point loss).  A batch may be destroyed before its scans.
  * Not thread-safe against a bf_fit / bf_batch_set_scans of a holding batch running at the same moment on another thread.
  * bf_scan_create builds the grid on the NULL stream and waits for that stream only (the library's streams are non-blocking):
  * a fit in flight on a batch's stream keeps running. */

@@ -162,15 +162,24 @@ class StandInMeshGridSearcher:
         return torch.from_numpy(pts), torch.from_numpy(ids)
 
 
-def run_reference_scan_fit(problem, meshfile, num_iters, snapshots=(), displacement=False):
-    """reference SMPLify.__call__ with use_mesh=True (smplify.py:146-156,205-210,228-247)."""
+SMPL_PARAMS = ("global_transl", "scale", "pose", "betas", "global_orient")
+SMPLX_PARAMS = SMPL_PARAMS + ("leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose")
+
+
+def run_reference_scan_fit(problem, meshfile, num_iters, snapshots=(), displacement=False, smpl_type="smpl", names=SMPL_PARAMS,
+                           disp_snapshots=None, losses=None):
+    """reference SMPLify.__call__ with use_mesh=True (smplify.py:146-156,205-210,228-247).  Snapshots of the optimiser's parameter
+    groups (`names`, in opt_params order) after the fit's Adam steps in `snapshots`, of the displacement after the SMPL+D steps in
+    `disp_snapshots` (default: `snapshots`); with a dict `losses`, the loss values the fit computed in the iterations of `snapshots`
+    (multiview_keypoint_loss's total + dict, point_cloud_loss_mesh_grid's value) - all recorded by wrapping what the loop calls."""
     import torch
     import smplify.smplify as RS
 
     RS.MeshGridSearcher = StandInMeshGridSearcher
     snaps, disp_snaps = {}, {}
-    orig_step = torch.optim.Adam.step
-    counter = {"n": 0}
+    disp_snapshots = snapshots if disp_snapshots is None else disp_snapshots
+    orig_step, orig_kp, orig_pc = torch.optim.Adam.step, RS.multiview_keypoint_loss, RS.point_cloud_loss_mesh_grid
+    counter = {"n": 0, "d": 0}
 
     def step(self, *a, **k):
         r = orig_step(self, *a, **k)
@@ -178,23 +187,38 @@ def run_reference_scan_fit(problem, meshfile, num_iters, snapshots=(), displacem
         if len(g) > 1:
             counter["n"] += 1
             if counter["n"] in snapshots:
-                snaps[counter["n"]] = {n: g[i]["params"][0].detach().numpy()[0].copy() for i, n in
-                                       enumerate(("global_transl", "scale", "pose", "betas", "global_orient"))}
+                snaps[counter["n"]] = {n: g[i]["params"][0].detach().numpy().reshape(-1).copy() for i, n in enumerate(names)}
         else:
-            counter["d"] = counter.get("d", 0) + 1
-            if counter["d"] in snapshots:
+            counter["d"] += 1
+            if counter["d"] in disp_snapshots:
                 disp_snaps[counter["d"]] = g[0]["params"][0].detach().numpy()[0].copy()
         return r
 
+    def kp_loss(*a, **k):
+        total, d = orig_kp(*a, **k)
+        it = counter["n"] + 1                          # (the iteration whose step comes next)
+        if it in snapshots:
+            losses[it] = {"total": float(total), **{kk: float(np.asarray(v).reshape(-1)[0]) for kk, v in d.items()}}
+        return total, d
+
+    def pc_loss(*a, **k):
+        v = orig_pc(*a, **k)
+        it = counter["n"] + 1
+        if counter["d"] == 0 and it in snapshots:       # (the fit's calls only; the SMPL+D stage calls it too)
+            losses[it]["pc_loss"] = float(v)
+        return v
+
     torch.optim.Adam.step = step
+    if losses is not None:
+        RS.multiview_keypoint_loss, RS.point_cloud_loss_mesh_grid = kp_loss, pc_loss
     try:
-        fitter = RS.SMPLify(smpl_type="smpl", num_iters=num_iters, gender="neutral", device=torch.device("cpu"), debug=False)
+        fitter = RS.SMPLify(smpl_type=smpl_type, num_iters=num_iters, gender="neutral", device=torch.device("cpu"), debug=False)
         net_output = (torch.from_numpy(problem["init_betas"].copy()), torch.from_numpy(problem["init_pose"].copy()))
         res = fitter(net_output, problem["c2ws"], problem["Ks"], problem["keypoints"], None,
                      use_frames=problem["use_frames"], imsize=problem["imsize"], use_mesh=True, meshfile=meshfile,
                      displacement=displacement)
     finally:
-        torch.optim.Adam.step = orig_step
+        torch.optim.Adam.step, RS.multiview_keypoint_loss, RS.point_cloud_loss_mesh_grid = orig_step, orig_kp, orig_pc
     return res, snaps, disp_snaps
 
 
@@ -643,6 +667,55 @@ def cfg3_goldens(variants=(("base", 1, None),) + PERTURBATIONS):
     torch.set_num_threads(1)
 
 
+CFG5_VARIANTS = (("base", 1, None, False),) + tuple((tag, threads, what, False) for tag, threads, what in PERTURBATIONS) + \
+    (("fused", 1, None, True),)
+
+
+def cfg5_goldens(variants=CFG5_VARIANTS, num_iters=300, out_dir=GOLDEN):
+    """BASELINE config 5 AS STATED for one frame, run by the imported reference: SMPL-X (10,475 vertices), 48 views, the frame-0 scan
+    (~84k triangles), 300 fit iterations (the closest-point loss is active for i > 300 // 3, smplify.py:205: steps 1..101 are
+    keypoint-only, 102 is the first with the scan) and 300 SMPL+D iterations, through StandInMeshGridSearcher.  Snapshots of the
+    parameters after fit steps 1 / 100 / 101 / 102 / 103 / 300, of the displacement after SMPL+D steps 1 / 10 / 300 (every 53rd vertex:
+    the files stay small; the end state holds all of it), the loss values of
+    those fit iterations, the end state (all vertices, joints, full_pose, the whole displacement), and digests of the model and of the
+    scan (which is regenerated, not stored).  One file per variant: `base` and the perturbations of tests/ref_drift.py SCAN_VARIANTS."""
+    import torch
+    import smplx
+    from bodyfitting_amd import synthetic as S
+    from bodyfitting_amd.io import save_obj_mesh
+
+    model = S.make_model("smplx", seed=0)
+    gmm = S.make_gmm(seed=0)
+    smplx.MODEL_REGISTRY["smplx"] = model
+    tmp = tempfile.mkdtemp(prefix="bf_golden_cfg5_")
+    os.makedirs(os.path.join(tmp, "data"), exist_ok=True)
+    with open(os.path.join(tmp, "data", "gmm_08.pkl"), "wb") as f:
+        pickle.dump(gmm, f)
+    os.chdir(tmp)
+    base, sv, sf = S.make_scan_problem_smplx(model, frame=0, n_views=48)
+    meshfile = os.path.join(tmp, "scan.obj")
+    save_obj_mesh(meshfile, sv, sf)
+    third = num_iters // 3
+    want = (1, third, third + 1, third + 2, third + 3, num_iters)
+    dwant = (1, 10, num_iters)
+    for tag, threads, what, fused in variants:
+        torch.set_num_threads(threads)
+        StandInMeshGridSearcher.FUSED = fused
+        losses = {}
+        t0 = time.perf_counter()
+        res, snaps, dsn = run_reference_scan_fit(_nudge(base, what), meshfile, num_iters, snapshots=want, displacement=True,
+                                                 smpl_type="smplx", names=SMPLX_PARAMS, disp_snapshots=dwant, losses=losses)
+        wall = time.perf_counter() - t0
+        extra = {f"it{it}_loss_{kk}": v for it, d in losses.items() for kk, v in d.items()}
+        np.savez_compressed(os.path.join(out_dir, f"cfg5_smplx_48view_scan_{num_iters}it_{tag}.npz"), frame=0, n_views=48,
+                            num_iters=num_iters, wall_s=wall, threads=threads, vertices=res["vertices"], joints=res["joints"],
+                            full_pose=res["full_pose"], displacement=res["displacement"], model_digest=S.model_digest(model),
+                            scan_digest=S.scan_digest(sv, sf), **flat_snaps(snaps), **{f"disp{k}_sample": v[::53] for k, v in dsn.items()}, **extra)
+        print("cfg5", tag, wall, "s", {it: d.get("pc_loss") for it, d in losses.items()}, flush=True)
+    torch.set_num_threads(1)
+    StandInMeshGridSearcher.FUSED = False
+
+
 def reference_timing(frames=(0, 1, 2)):
     """Wall time of the UNMODIFIED reference loop (SMPLify.__call__, smplify.py:84-250: 48 views, 100 iterations, torch CPU,
     1 thread = its faster setting) on this build container, per frame, without the snapshot hook: the reference-side CPU figure
@@ -836,6 +909,15 @@ if __name__ == "__main__":
     elif "--cfg3-new-only" in sys.argv:                      # only the perturbations round 6 added (the other files stay as committed)
         install_reference_imports()
         cfg3_goldens(variants=NEW_PERTURBATIONS)
+    elif "--cfg5-only" in sys.argv:                         # [--variants base,ulp,...] [--iters N --out DIR: a shorter dry run]
+        install_reference_imports()
+        arg = lambda name, default: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default      # noqa: E731
+        tags = arg("--variants", ",".join(v[0] for v in CFG5_VARIANTS)).split(",")
+        unknown = set(tags) - {v[0] for v in CFG5_VARIANTS}
+        if unknown:
+            sys.exit(f"unknown variants: {sorted(unknown)}")
+        cfg5_goldens(variants=tuple(v for v in CFG5_VARIANTS if v[0] in tags), num_iters=int(arg("--iters", 300)),
+                     out_dir=os.path.abspath(arg("--out", GOLDEN)))
     elif "--timing-only" in sys.argv:
         install_reference_imports()
         reference_timing()
@@ -852,4 +934,5 @@ if __name__ == "__main__":
         sensitivity_goldens()
         sensitivity_cfg2_goldens()
         cfg3_goldens()
+        cfg5_goldens()
         reference_timing()

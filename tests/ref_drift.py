@@ -56,3 +56,23 @@ def position(err, own):
 def cfg3_drifts(keys):
     base, var = cfg3_variants()
     return sorted(max(float(np.abs(np.asarray(var[v][k], np.float64) - np.asarray(base[k], np.float64)).max()) for k in keys) for v in VARIANTS)
+
+
+CFG5 = "cfg5_smplx_48view_scan_300it_%s.npz"
+
+
+def cfg5_variants():
+    """config 5 as stated, frame 0 (oracle/gen_golden.py cfg5_goldens): the reference's base run and its SCAN_VARIANTS"""
+    base = load_golden(CFG5 % "base")
+    return base, {v: load_golden(CFG5 % v) for v in SCAN_VARIANTS}
+
+
+def cfg5_drift(keys):
+    base, var = cfg5_variants()
+    return max(float(np.abs(np.asarray(var[v][k], np.float64) - np.asarray(base[k], np.float64)).max()) for v in SCAN_VARIANTS for k in keys)
+
+
+def cfg5_drifts(keys):
+    base, var = cfg5_variants()
+    return sorted(max(float(np.abs(np.asarray(var[v][k], np.float64) - np.asarray(base[k], np.float64)).max()) for k in keys)
+                  for v in SCAN_VARIANTS)

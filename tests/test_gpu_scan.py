@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from scan_metrics import disp_metrics
 from bodyfitting_amd import native as N
 from bodyfitting_amd import synthetic as S
 from oracle import mesh_oracle as MO
@@ -466,22 +467,6 @@ def test_scan_fit_matches_reference_golden(small):
     scan.close()
 
 
-def _disp_metrics(model, sv, sf, base, disp):
-    """end-state metrics of the SMPL+D stage (smplify.py:228-247) for `base + disp` against the scan, by the oracle's
-    pieces: distribution of point-to-scan distances, the icp term, normal and laplacian energies"""
-    import torch
-    P = (base + disp).astype(np.float32)
-    ids, cp, _ = MO.ReferenceSearcher(sv, sf).nearest(P)
-    d = np.linalg.norm(P - cp, axis=1)
-    faces_t = torch.as_tensor(np.asarray(model["faces"]), dtype=torch.long)
-    norms = MO.compute_normal_torch(torch.tensor(P, dtype=torch.float64), faces_t)
-    tris = sv.astype(np.float64)[sf]
-    fn = torch.tensor(np.cross(tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0]).astype(np.float32), dtype=torch.float64)
-    return {"mean": float(d.mean()), "median": float(np.median(d)), "p95": float(np.percentile(d, 95)), "icp": float(np.linalg.norm(P - cp)),
-            "normal": float(MO.normal_loss(fn[torch.as_tensor(ids, dtype=torch.long)], norms)),
-            "laplacian": float(MO.normal_laplacian_smoothness(norms, faces_t))}
-
-
 def test_config5_iteration_counts_end_state_against_the_reference(small):
     """config 5's loop lengths on the reduced model: 300 iterations with the scan loss after 100, then 300 SMPL+D iterations,
     against the imported reference's run (scan_nv690_300it.npz).  First loop: parameters after 100 / 101 / 300 iterations.
@@ -521,13 +506,13 @@ def test_config5_iteration_counts_end_state_against_the_reference(small):
     verts, joints, _, _ = b.get_result()
     np.testing.assert_allclose(verts[0], g["vertices"], atol=RD.band(g, sens, ["vertices"], variants=RD.SCAN_VARIANTS))
     np.testing.assert_allclose(joints[0], g["joints"], atol=RD.band(g, sens, ["joints"], variants=RD.SCAN_VARIANTS))
-    fit_ref = _disp_metrics(model, sv, sf, g["vertices"], 0 * g["vertices"])
-    fit_got = _disp_metrics(model, sv, sf, verts[0], 0 * verts[0])
+    fit_ref = disp_metrics(model, sv, sf, g["vertices"], 0 * g["vertices"])
+    fit_got = disp_metrics(model, sv, sf, verts[0], 0 * verts[0])
     print("scan loop end state  reference:", fit_ref, "\n                     HIP:      ", fit_got)
     # the closest-point term is ~10 % of the objective (keypoint terms ~2,400, 5 * imsize / height * icp ~270), so the distance
     # distribution is a soft quantity of the end state (held within a factor of two: rebuilds of the kernels that only changed an
     # fma contraction moved the mean between +16 % and +30 % of the reference's); the objective itself is held within 5 %
-    fit_var = {v: _disp_metrics(model, sv, sf, sens[f"{v}_vertices"], 0 * sens[f"{v}_vertices"]) for v in RD.SCAN_VARIANTS}
+    fit_var = {v: disp_metrics(model, sv, sf, sens[f"{v}_vertices"], 0 * sens[f"{v}_vertices"]) for v in RD.SCAN_VARIANTS}
     print("                     reference, perturbed:", fit_var)
     for key in ("mean", "median", "p95", "icp"):
         tol = rel_band(lambda v: fit_var[v][key], fit_ref[key])
@@ -549,11 +534,11 @@ def test_config5_iteration_counts_end_state_against_the_reference(small):
     assert obj["HIP"] == pytest.approx(obj["reference"], rel=rel_band(lambda v: obj[v], obj["reference"], floor=0.02))
     b.fit_displacement(300)
     disp = b.get_displacement()[0]
-    want = _disp_metrics(model, sv, sf, g["vertices"], g["displacement"])
-    before = _disp_metrics(model, sv, sf, g["vertices"], 0 * g["displacement"])
-    got = _disp_metrics(model, sv, sf, verts[0], disp)
+    want = disp_metrics(model, sv, sf, g["vertices"], g["displacement"])
+    before = disp_metrics(model, sv, sf, g["vertices"], 0 * g["displacement"])
+    got = disp_metrics(model, sv, sf, verts[0], disp)
     print("SMPL+D end state  reference:", want, "\n                  HIP:      ", got, "\n                  before:   ", before)
-    disp_var = {v: _disp_metrics(model, sv, sf, sens[f"{v}_vertices"], sens[f"{v}_displacement"]) for v in RD.SCAN_VARIANTS}
+    disp_var = {v: disp_metrics(model, sv, sf, sens[f"{v}_vertices"], sens[f"{v}_displacement"]) for v in RD.SCAN_VARIANTS}
     print("                  reference, perturbed:", disp_var)
     for key in ("mean", "median", "p95", "icp", "laplacian", "normal"):
         tol = rel_band(lambda v: disp_var[v][key], want[key], floor=0.1)
@@ -660,6 +645,16 @@ def test_scan_and_batch_may_be_destroyed_in_any_order(small):
     scans[0].close()                           # destroy-then-detach: waits for the device, detaches BOTH frames' scans
     b.reset()
     with pytest.raises(_lib.BodyfitError, match="was destroyed"):      # ... and the batch says so instead of fitting without them
+        b.fit(12)
+    with pytest.raises(_lib.BodyfitError, match="was destroyed"):
+        b.fit_displacement(2)
+    # a re-attach that is REJECTED (a NULL entry) leaves the batch as it was: its fits still fail instead of running without the
+    # closest-point loss (FrameBatch.set_scans asserts Scan objects, so the C ABI is called directly)
+    import ctypes as C
+    bad = (C.c_void_p * 2)(None, scans[1]._h)
+    assert _lib.load().bf_batch_set_scans(b._h, bad) == -1                # BF_ERR_INVALID
+    b.reset()
+    with pytest.raises(_lib.BodyfitError, match="was destroyed"):
         b.fit(12)
     with pytest.raises(_lib.BodyfitError, match="was destroyed"):
         b.fit_displacement(2)

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+import ref_drift as RD
 from conftest import load_golden
 from bodyfitting_amd import synthetic as S
 from oracle import smplify_oracle as O
@@ -87,3 +88,26 @@ def test_known_answers(smpl_model):
     K = torch.tensor([[500.0, 0, 256], [0, 500, 256], [0, 0, 1]], dtype=torch.float64)
     uv = O.perspective_projection(pts, torch.eye(3, dtype=torch.float64)[None], torch.zeros(1, 3, dtype=torch.float64), K)
     np.testing.assert_allclose(uv[0, 0].numpy(), [256 + 500 * 0.05, 256 - 500 * 0.1], atol=1e-9)
+
+
+@pytest.mark.parametrize("variant", ("base",) + RD.SCAN_VARIANTS)
+def test_cfg5_goldens_match_todays_generator(variant):
+    """config 5 as stated (oracle/gen_golden.py cfg5_goldens) is held on the GPU against these files, whose scan is not stored but
+    regenerated: each one must still describe today's model and frame-0 scan, and hold every snapshot the GPU test reads"""
+    g = load_golden(RD.CFG5 % variant)
+    model = S.make_model("smplx", seed=0)
+    _, sv, sf = S.make_scan_problem_smplx(model, frame=0, n_views=48)
+    assert str(g["model_digest"]) == S.model_digest(model)
+    assert str(g["scan_digest"]) == S.scan_digest(sv, sf)
+    assert int(g["num_iters"]) == 300 and int(g["n_views"]) == 48 and int(g["frame"]) == 0
+    want = {f"it{k}_{n}" for k in (1, 100, 101, 102, 103, 300) for n in O.SMPLX_PARAMS}
+    want |= {f"it{k}_loss_{n}" for k in (1, 100, 101, 102, 103, 300)
+             for n in ("total", "reprojection_loss", "pose_prior_loss", "angle_prior_loss", "shape_prior_loss")}
+    want |= {f"it{k}_loss_pc_loss" for k in (102, 103, 300)}               # (the scan loss is active from step 102 on)
+    want |= {f"disp{k}_sample" for k in (1, 10, 300)} | {"vertices", "joints", "full_pose", "displacement", "wall_s", "threads"}
+    assert want <= set(g.files), sorted(want - set(g.files))
+    assert not {f"it{k}_loss_pc_loss" for k in (1, 100, 101)} & set(g.files)
+    nv = model["v_template"].shape[0]
+    assert g["vertices"].shape == (nv, 3) and g["displacement"].shape == (nv, 3) and g["joints"].shape == (135, 3)
+    for k in O.SMPLX_PARAMS:
+        assert np.isfinite(g[f"it300_{k}"]).all()
