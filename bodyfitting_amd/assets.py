@@ -10,6 +10,10 @@ per *frame*.  Here a model is resolved once per process and cached per (type, ge
      (`model_files`),
   3. an `.npz` already in this package's tensor layout under `data/` (`{type}_{gender}.npz`),
   4. otherwise a clear error - nothing is downloaded and nothing is silently replaced.
+
+age='kid' (SMPL only) is the adult model with the kid template's 11th shape direction (`model_files.kid_model`); the template is
+the one registered with `register_kid_template(...)`, else the file at `kid_template_path` (default `data/smil/smil_web.pkl`,
+config.SMIL_MODEL_DIR).  Kid models are cached under (type, gender, 'kid'); the adult keys are those of before.
 """
 from __future__ import annotations
 
@@ -23,12 +27,38 @@ from . import model_files
 _MODELS = {}
 _GMM = {}
 _DEVICE_MODELS = {}
+_KID_TEMPLATE = {}
+
+
+def _drop_kid(model_type=None, gender=None):
+    """forget the kid models (and their device models) built from the given adult model (None: from any)"""
+    for cache in (_MODELS, _DEVICE_MODELS):
+        for k in [k for k in cache if k[-1] == "kid" and (model_type is None or k[:2] == (model_type, gender))]:
+            v = cache.pop(k)
+            if cache is _DEVICE_MODELS:
+                v.close()
 
 
 def register_model(model, model_type="smpl", gender="neutral"):
     _MODELS[(model_type, gender)] = model
     for k in [k for k in _DEVICE_MODELS if k[:2] == (model_type, gender)]:
         _DEVICE_MODELS.pop(k).close()
+    _drop_kid(model_type, gender)
+
+
+def register_kid_template(template):
+    """the kid template [NV, 3] to use instead of the file (tests, synthetic benchmarks); None forgets it"""
+    if template is None:
+        _KID_TEMPLATE.clear()
+    else:
+        _KID_TEMPLATE["template"] = np.asarray(template, np.float32).copy()
+    _drop_kid()
+
+
+def get_kid_template(path=None):
+    if "template" in _KID_TEMPLATE:
+        return _KID_TEMPLATE["template"]
+    return model_files.load_kid_template(model_files.KID_TEMPLATE_PATH if path is None else path)
 
 
 def register_gmm(gmm):
@@ -51,7 +81,21 @@ def _load_npz_model(model_type, gender, folder="data"):
     return None
 
 
-def get_model(model_type="smpl", gender="neutral"):
+def _check_age(model_type, age):
+    if age not in ("adult", "kid"):
+        raise ValueError(f"unknown age {age!r}: 'adult' or 'kid'")
+    if age == "kid" and model_type != "smpl":
+        raise ValueError("age='kid' is SMPL only: the reference builds SMPL-X without a kid template (smplx.create gets no age) "
+                         "and then feeds 11 betas to a 10-direction model, so there is no SMPL-X kid behaviour to reproduce")
+
+
+def get_model(model_type="smpl", gender="neutral", age="adult", kid_template_path=None):
+    _check_age(model_type, age)
+    if age == "kid":
+        key = (model_type, gender, "kid")
+        if key not in _MODELS:
+            _MODELS[key] = model_files.kid_model(get_model(model_type, gender), get_kid_template(kid_template_path))
+        return _MODELS[key]
     for key in ((model_type, gender), (model_type, "neutral")):
         if key in _MODELS:
             return _MODELS[key]
@@ -94,10 +138,11 @@ def gmm_buffers(gmm):
     return means, precisions, nll_weights.astype(np.float32)
 
 
-def get_device_model(model_type="smpl", gender="neutral", device=0):
-    """The HIP-resident model, created once per (type, gender, device)."""
+def get_device_model(model_type="smpl", gender="neutral", device=0, age="adult", kid_template_path=None):
+    """The HIP-resident model, created once per (type, gender, device) - (type, gender, device, 'kid') for a kid."""
     from .native import DeviceModel
-    key = (model_type, gender, int(device))
+    _check_age(model_type, age)
+    key = (model_type, gender, int(device)) + (("kid",) if age == "kid" else ())
     if key not in _DEVICE_MODELS:
-        _DEVICE_MODELS[key] = DeviceModel(get_model(model_type, gender), get_gmm(), device=device)
+        _DEVICE_MODELS[key] = DeviceModel(get_model(model_type, gender, age, kid_template_path), get_gmm(), device=device)
     return _DEVICE_MODELS[key]

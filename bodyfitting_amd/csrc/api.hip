@@ -12,7 +12,7 @@ extern "C" __global__ void bf_mesh_epilogue_kernel(MeshTab, const float *, const
 extern "C" hipError_t bf_poseblend_launch(const MeshTab *M, const float *state, int n, float *featT, int kpad, int fpad, float *pose_off, hipStream_t stream);
 extern "C" bool bf_mesh_batch32_fits(const MeshTab *M);
 extern "C" hipError_t bf_mesh_batch32_launch(const MeshTab *M, const float *state, int n, float *vraw, float *vout, float *xpart, hipStream_t stream);
-extern "C" __global__ void bf_mesh_epilogue_batch_kernel(MeshTab M, const float *state, const float *pose_off, int n_frames, float *vraw, float *vout, float *xpart);
+extern "C" void bf_mesh_epilogue_batch_launch(const MeshTab *M, const float *state, const float *pose_off, int n, float *vraw, float *vout, float *xpart, hipStream_t stream);
 extern "C" __global__ void bf_joints_kernel(MeshTab, const float *, const float *, const float *, float *, float *, float *, int *, float *);
 extern "C" size_t bf_fit_smem_bytes(int, int, int, int, int, int, int);
 extern "C" size_t bf_mesh_smem_bytes(int, int, int);
@@ -546,10 +546,8 @@ int bf_launch_mesh(bf_model *m, MeshScratch *scr, int n, const float *state_dev,
         }
         HIP_TRY(bf_poseblend_launch(&m->mesh, state_dev, n, scr->featT.p, kpad, fpad, scr->pose_off.p, stream));
         pose_off = scr->pose_off.p;
-        if (m->mesh.v_nnz == 4 && m->nb <= 10 && !vposed) {
-            hipLaunchKernelGGL(bf_mesh_epilogue_batch_kernel, dim3((m->nv + 127) / 128, (n + BF_EPI_FRAMES - 1) / BF_EPI_FRAMES), dim3(128),
-                               (size_t)BF_EPI_FRAMES * (m->nj * 12 + 128 * 3) * sizeof(float), stream, m->mesh, state_dev, pose_off, n, vraw, vout,
-                               need_x ? xpart : (float *)nullptr);
+        if (m->mesh.v_nnz == 4 && m->nb <= 12 && !vposed) {
+            bf_mesh_epilogue_batch_launch(&m->mesh, state_dev, pose_off, n, vraw, vout, need_x ? xpart : (float *)nullptr, stream);
         } else
         hipLaunchKernelGGL(bf_mesh_epilogue_kernel, grid, dim3(128), 0, stream, m->mesh, state_dev, pose_off, vraw, vout,
                            need_x ? xpart : (float *)nullptr, vposed);

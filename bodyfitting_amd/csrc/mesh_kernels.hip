@@ -20,6 +20,7 @@
 #include "joints_body.h"
 #include "loss_bodies.h"
 #include <cstring>
+#include <type_traits>
 
 namespace {
 __device__ inline float m_wave_sum(float v) {
@@ -233,7 +234,9 @@ bf_mesh_span_kernel(MeshTab M, const float *__restrict__ state, float *__restric
 #define BF_MM_OCC8 6
 #endif
 #define BF_MM_CH (FPW == 8 ? BF_MM_CH8 : 64)
-template <int FPW>
+// PNB: the shape directions the one-frame `pre` path holds in registers - 10 (SMPL) or 12 (the kid model's 11 and a 12th; the one-frame
+// instance is compiled twice, the 10-direction one exactly as before)
+template <int FPW, int PNB = 10>
 __global__ void __launch_bounds__(BF_MESH_TILE * 3 * BF_MESH_RG, FPW == 8 ? BF_MM_OCC8 : 1)
 bf_mesh_multi_kernel(MeshTab M, const float *__restrict__ state, int n_frames, float *__restrict__ vraw, float *__restrict__ vout,
                      float *__restrict__ xpart, float *__restrict__ vposed, float *__restrict__ dvzero, MaskProj mp, int *door, int door_target) {
@@ -269,13 +272,13 @@ bf_mesh_multi_kernel(MeshTab M, const float *__restrict__ state, int n_frames, f
     // before the pose blend is (they used to start behind it, on the 96 threads that do the epilogue of a frame)
     // (one frame per workgroup only: with eight, the 28 registers of the rows take the kernel from 3 to 2 waves per SIMD - config 5's
     //  iteration went from 0.202 to 0.214 ms)
-    const bool pre = FPW == 1 && rg < nf && ok && nb <= 10 && (M.v_nnz == 4 || M.v_nnz == 8);
-    float pre_sd[10], pre_vt = 0.f, pre_w[8];
+    const bool pre = FPW == 1 && rg < nf && ok && nb <= PNB && (M.v_nnz == 4 || M.v_nnz == 8);
+    float pre_sd[PNB], pre_vt = 0.f, pre_w[8];
     int pre_j[8];
     if (pre) {
         const float *sd = M.shapedirs + (size_t)gcol * nb;
 #pragma unroll
-        for (int l = 0; l < 10; ++l) pre_sd[l] = l < nb ? sd[l] : 0.f;
+        for (int l = 0; l < PNB; ++l) pre_sd[l] = l < nb ? sd[l] : 0.f;
         pre_vt = M.v_template[gcol];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -373,7 +376,7 @@ bf_mesh_multi_kernel(MeshTab M, const float *__restrict__ state, int n_frames, f
         if (pre) {
             vt = pre_vt;
 #pragma unroll
-            for (int l = 0; l < 10; ++l) if (l < nb) a2 += pre_sd[l] * s_beta[f * 32 + l];
+            for (int l = 0; l < PNB; ++l) if (l < nb) a2 += pre_sd[l] * s_beta[f * 32 + l];
         } else {
             const float *sd = M.shapedirs + (size_t)gcol * nb;
             vt = M.v_template[gcol];
@@ -488,7 +491,10 @@ extern "C" int bf_mesh_multi_launch(const MeshTab *M, const float *state, int n,
         if (e != hipSuccess) return (int)e;
     }
     switch (fpw) {
-    case 1: if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<1>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
+    case 1: if (M->nb > 10) {          // (11 or 12 shape directions: the `pre` path's rows sized for 12)
+                if (done) hipExtLaunchKernelGGL((bf_mesh_multi_kernel<1, 12>), grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
+                else hipLaunchKernelGGL((bf_mesh_multi_kernel<1, 12>), grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
+             } else if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<1>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
              else hipLaunchKernelGGL(bf_mesh_multi_kernel<1>, grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
              break;
     case 2: if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<2>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
@@ -630,12 +636,13 @@ extern "C" hipError_t bf_poseblend_launch(const MeshTab *M, const float *state, 
     return hipGetLastError();
 }
 
-// Batched epilogue (4-sparse skinning rows, nb <= 10): one THREAD per vertex, 128 vertices per workgroup, walking
+// Batched epilogue (4-sparse skinning rows, nb <= MAXNB: 10, or 12 for the kid model's 11): one THREAD per vertex, 128 vertices per workgroup, walking
 // BF_EPI_FRAMES frames.  The vertex's tables stay in registers (three shapedirs rows, template, four bones + weights);
 // the frames' bone transforms and (beta | t | s) records are staged in LDS once.  Per vertex and frame: shaped vertex +
 // pose offset (from the GEMM) -> T = sum_4 w A_j -> skinning -> similarity: ~100 VALU instructions, 16 b128 LDS reads,
 // nothing of the model re-read.  The extra-joint partial sums keep the 32-vertex tiling the joints kernel expects.
-extern "C" __global__ void __launch_bounds__(128)
+template <int MAXNB>
+__global__ void __launch_bounds__(128)
 bf_mesh_epilogue_batch_kernel(MeshTab M, const float *__restrict__ state, const float *__restrict__ pose_off, int n_frames,
                               float *__restrict__ vraw, float *__restrict__ vout, float *__restrict__ xpart) {
     constexpr int FE = BF_EPI_FRAMES, VT = 128;
@@ -672,13 +679,14 @@ bf_mesh_epilogue_batch_kernel(MeshTab M, const float *__restrict__ state, const 
     const int v = blockIdx.x * VT + tid;
     const bool ok = v < nv;
     const int vc = ok ? v : nv - 1;
-    float sd[3][10], vt[3], w4[4];
+    static_assert(MAXNB == 10 || MAXNB == 12, "the records carry 12 beta slots");
+    float sd[3][MAXNB], vt[3], w4[4];
     int j4[4];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float *sp = M.shapedirs + (size_t)(vc * 3 + c) * nb;
 #pragma unroll
-        for (int l = 0; l < 10; ++l) sd[c][l] = l < nb ? sp[l] : 0.f;
+        for (int l = 0; l < MAXNB; ++l) sd[c][l] = l < nb ? sp[l] : 0.f;
         vt[c] = M.v_template[vc * 3 + c];
     }
 #pragma unroll
@@ -695,13 +703,13 @@ bf_mesh_epilogue_batch_kernel(MeshTab M, const float *__restrict__ state, const 
     for (int f = 0; f < FE; ++f) {
         if (f < nf) {
             const float4 bq0 = *(const float4 *)&s_beta[f][0], bq1 = *(const float4 *)&s_beta[f][4], bq2 = *(const float4 *)&s_beta[f][8];
-            const float be[10] = {bq0.x, bq0.y, bq0.z, bq0.w, bq1.x, bq1.y, bq1.z, bq1.w, bq2.x, bq2.y};
+            const float be[12] = {bq0.x, bq0.y, bq0.z, bq0.w, bq1.x, bq1.y, bq1.z, bq1.w, bq2.x, bq2.y, bq2.z, bq2.w};
             float vp[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 float a2 = 0.f;
 #pragma unroll
-                for (int l = 0; l < 10; ++l) a2 += sd[c][l] * be[l];
+                for (int l = 0; l < MAXNB; ++l) a2 += sd[c][l] * be[l];
                 vp[c] = vt[c] + a2 + ofs[f][c];
             }
             float T[12];
@@ -764,6 +772,14 @@ bf_mesh_epilogue_batch_kernel(MeshTab M, const float *__restrict__ state, const 
     }
 }
 
+extern "C" void bf_mesh_epilogue_batch_launch(const MeshTab *M, const float *state, const float *pose_off, int n, float *vraw, float *vout,
+                                              float *xpart, hipStream_t stream) {
+    const dim3 grid((M->nv + 127) / 128, (n + BF_EPI_FRAMES - 1) / BF_EPI_FRAMES);
+    const size_t smem = (size_t)BF_EPI_FRAMES * (M->nj * 12 + 128 * 3) * sizeof(float);
+    if (M->nb > 10) hipLaunchKernelGGL(bf_mesh_epilogue_batch_kernel<12>, grid, dim3(128), smem, stream, *M, state, pose_off, n, vraw, vout, xpart);
+    else hipLaunchKernelGGL(bf_mesh_epilogue_batch_kernel<10>, grid, dim3(128), smem, stream, *M, state, pose_off, n, vraw, vout, xpart);
+}
+
 // Final mesh of a 32-frame block in ONE launch (config 4's per-GPU shard is exactly one block): pose blend on the
 // matrix cores with the shape blend, skinning and similarity BEHIND THE ACCUMULATORS - no featT, no pose_off round trip.
 // grid (n_tiles, ceil(F / 32)), 512 threads; SMPL-sized models (bf_mesh_batch32_fits).
@@ -776,15 +792,22 @@ bf_mesh_epilogue_batch_kernel(MeshTab M, const float *__restrict__ state, const 
 // Then 13 x 3 v_mfma_f32_32x32x2_f32 per wave (A operand: pose features frame-minor in LDS, conflict free), the eight
 // partial tiles meet in LDS (over the pose features) and are added in wave order; thread (vertex, frame pair) does what
 // bf_mesh_epilogue_batch_kernel does per vertex and frame.  Stores leave through LDS, 384 consecutive bytes per frame.
+// NB: 10 - SMPL's ten shape directions, every state record and its pose-feature block on an 8-byte boundary (bf_mesh_batch32_fits);
+// 12 - any nb of 11..12 (the kid model's 11): the shape rows held for 12 with the columns past nb zero, and the float2 reads along
+// the records only 4-byte aligned, since an odd nb makes the record stride odd
 typedef float bf_f3u __attribute__((ext_vector_type(3), aligned(4)));
 typedef float bf_f2u __attribute__((ext_vector_type(2), aligned(8)));
-extern "C" __global__ void __launch_bounds__(512)
+typedef float bf_f2u4 __attribute__((ext_vector_type(2), aligned(4)));
+template <int NB>
+__global__ void __launch_bounds__(512)
 bf_mesh_batch32_kernel(MeshTab M, const float *__restrict__ state, int n_frames, float *__restrict__ vraw, float *__restrict__ vout,
                        float *__restrict__ xpart) {
     constexpr int FB = 32, COLS = BF_MESH_TILE * 3, NW = 8, KS = 13, KROWS = 2 * NW * KS, FLD = FB + 1, ALD = COLS + 1, XLD = BF_MESH_TILE + 1;
     constexpr int NF2 = FB / 4;                             // 8 float2 of pose features per thread (threads 0..415: four frames a step)
     constexpr int NA2 = (FB + 2) / 3;                       // 11 float2 of bone transforms per thread (threads 0..3 nj6 - 1: three frames a step)
     constexpr int NX = (24 * BF_MESH_TILE + 511) / 512;     // 2 extra-joint regressor values per thread (n_extra <= 24)
+    static_assert(NB == 10 || NB == 12, "beta count");
+    typedef typename std::conditional<NB == 10, bf_f2u, bf_f2u4>::type f2r;     // (a float2 along a state record)
     extern __shared__ __align__(16) float s_dyn[];
     float *s_feat = s_dyn;                                  // [KROWS][FLD]   pose features, frame-minor (dead after the K loop, under s_acc)
     float *s_acc = s_dyn;                                   // [NW][FB][ALD]  the waves' partial tiles; [0] becomes the raw vertices
@@ -797,7 +820,7 @@ bf_mesh_batch32_kernel(MeshTab M, const float *__restrict__ state, int n_frames,
     const size_t stride = bf_state_stride(nj, npf, nb);
     const int feat_off = nj * 15;
     // ---- the loads, in the order of use
-    bf_f2u tfe[NF2], tA[NA2];
+    f2r tfe[NF2], tA[NA2];
     float tbe, tbs, tx[NX];
     const float *sblk = state + (size_t)fbase * stride;      // (the block's records: 32-bit offsets from here on)
     const int istride = (int)stride;
@@ -806,12 +829,12 @@ bf_mesh_batch32_kernel(MeshTab M, const float *__restrict__ state, int n_frames,
     if (tid < 4 * HP) {
         // (unconditional: frames past the block repeat its last one, rows past npf read on into the record - zeroed when stored)
 #pragma unroll
-        for (int r = 0; r < NF2; ++r) tfe[r] = *(const bf_f2u *)(sblk + min(4 * r + fe_hi, nf - 1) * istride + feat_off + fe_p);
+        for (int r = 0; r < NF2; ++r) tfe[r] = *(const f2r *)(sblk + min(4 * r + fe_hi, nf - 1) * istride + feat_off + fe_p);
     }
     const int fa = (tid >= nj6 ? 1 : 0) + (tid >= 2 * nj6 ? 1 : 0) + (tid >= 3 * nj6 ? 1 : 0), ea = tid - fa * nj6;      // frame mod 3, pair
     if (fa < 3) {
 #pragma unroll
-        for (int r = 0; r < NA2; ++r) tA[r] = *(const bf_f2u *)(sblk + min(3 * r + fa, nf - 1) * istride + 2 * ea);
+        for (int r = 0; r < NA2; ++r) tA[r] = *(const f2r *)(sblk + min(3 * r + fa, nf - 1) * istride + 2 * ea);
     }
     {
         // (beta | t | s cscale) records: plain loads, no branches - a wait inside this stream would serialise everything behind it
@@ -836,12 +859,18 @@ bf_mesh_batch32_kernel(MeshTab M, const float *__restrict__ state, int n_frames,
     const int vl = tid & 31, fo = tid >> 5, v = v0 + vl;
     const bool ok = v < nv;
     const int vc = ok ? v : nv - 1;
-    float sd[30], w4[4];
+    float sd[3 * NB], w4[4];
     int j4[4];
-    {
+    if constexpr (NB == 10) {
         const bf_f2u *sp = (const bf_f2u *)(M.shapedirs + (size_t)vc * 30);       // (nb == 10: three rows of ten, 8-byte aligned)
 #pragma unroll
         for (int l = 0; l < 15; ++l) { const bf_f2u x = sp[l]; sd[2 * l] = x.x; sd[2 * l + 1] = x.y; }
+    } else {
+        const float *sp = M.shapedirs + (size_t)vc * 3 * nb;                      // (three rows of nb, read as they lie)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int l = 0; l < NB; ++l) sd[c * NB + l] = l < nb ? sp[c * nb + l] : 0.f;
     }
     const bf_f3u vt = *(const bf_f3u *)(M.v_template + (size_t)vc * 3);
     {
@@ -918,7 +947,7 @@ bf_mesh_batch32_kernel(MeshTab M, const float *__restrict__ state, int n_frames,
         const int f = fo * 2 + i;
         const float *bp = s_beta + f * 16;
         const float4 bq0 = *(const float4 *)bp, bq1 = *(const float4 *)(bp + 4), bq2 = *(const float4 *)(bp + 8);
-        const float be[10] = {bq0.x, bq0.y, bq0.z, bq0.w, bq1.x, bq1.y, bq1.z, bq1.w, bq2.x, bq2.y};
+        const float be[12] = {bq0.x, bq0.y, bq0.z, bq0.w, bq1.x, bq1.y, bq1.z, bq1.w, bq2.x, bq2.y, bq2.z, bq2.w};
         float vp[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -928,7 +957,7 @@ bf_mesh_batch32_kernel(MeshTab M, const float *__restrict__ state, int n_frames,
             for (int w2 = 1; w2 < NW; ++w2) po += s_acc[w2 * FB * ALD + o];       // (wave order)
             float a2 = 0.f;
 #pragma unroll
-            for (int l = 0; l < 10; ++l) a2 += sd[c * 10 + l] * be[l];
+            for (int l = 0; l < NB; ++l) a2 += sd[c * NB + l] * be[l];
             vp[c] = (c == 0 ? vt.x : (c == 1 ? vt.y : vt.z)) + a2 + po;
         }
         float T[12];
@@ -991,22 +1020,25 @@ bf_mesh_batch32_kernel(MeshTab M, const float *__restrict__ state, int n_frames,
 }
 
 extern "C" bool bf_mesh_batch32_fits(const MeshTab *M) {
-    // (float2 reads along a frame's record: the record and its pose-feature block have to start on 8-byte boundaries)
-    if (bf_state_stride(M->nj, M->npf, M->nb) % 2 != 0 || (M->nj * 15) % 2 != 0) return false;
+    // (the 10-beta instance's float2 reads along a frame's record: the record and its pose-feature block have to start on 8-byte
+    //  boundaries; the 12-beta instance reads them 4-byte aligned)
+    if (M->nb == 10 && (bf_state_stride(M->nj, M->npf, M->nb) % 2 != 0 || (M->nj * 15) % 2 != 0)) return false;
     // npf >= 2 NW (KS - 1) + 1 = 193: only the LAST of a wave's 13 row pairs is clamped to the table's end (bq[KS - 1]); with fewer
     // rows an earlier pair would read past posedirs (nj = 22: npf = 189 - the operand it meets is zero, but 0 x garbage may be NaN)
     return M->npf <= 208 && M->npf >= 193 && M->nj <= 24 && M->nj >= 22 /* three frames' bone transforms per 512-thread step */ && M->v_nnz == 4 &&
-           M->nb == 10 && M->n_extra <= 24;
+           (M->nb == 10 || M->nb == 11 || M->nb == 12) && M->n_extra <= 24;
 }
 extern "C" hipError_t bf_mesh_batch32_launch(const MeshTab *M, const float *state, int n, float *vraw, float *vout, float *xpart,
                                              hipStream_t stream) {
     constexpr int FB = 32, COLS = BF_MESH_TILE * 3;
     const size_t smem = sizeof(float) * (8 * (size_t)FB * (COLS + 1) + (size_t)FB * 16 + (size_t)FB * 24 * 12 + 24 * (size_t)(BF_MESH_TILE + 1));
     {   // (every launch: the attribute belongs to the current device, and a group drives several from one process)
-        hipError_t e = hipFuncSetAttribute((const void *)bf_mesh_batch32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipError_t e = hipFuncSetAttribute(M->nb == 10 ? (const void *)bf_mesh_batch32_kernel<10> : (const void *)bf_mesh_batch32_kernel<12>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(bf_mesh_batch32_kernel, dim3(M->n_tiles, (n + FB - 1) / FB), dim3(512), smem, stream, *M, state, n, vraw, vout, xpart);
+    if (M->nb == 10) hipLaunchKernelGGL(bf_mesh_batch32_kernel<10>, dim3(M->n_tiles, (n + FB - 1) / FB), dim3(512), smem, stream, *M, state, n, vraw, vout, xpart);
+    else hipLaunchKernelGGL(bf_mesh_batch32_kernel<12>, dim3(M->n_tiles, (n + FB - 1) / FB), dim3(512), smem, stream, *M, state, n, vraw, vout, xpart);
     return hipGetLastError();
 }
 

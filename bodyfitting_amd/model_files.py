@@ -149,6 +149,51 @@ def load_smplx(path, vertex_ids=None, use_face_contour=True):
     return m
 
 
+KID_TEMPLATE_PATH = "data/smil/smil_web.pkl"     # config.SMIL_MODEL_DIR, relative to the working directory like every model file
+
+
+def load_kid_template(path=KID_TEMPLATE_PATH):
+    """The kid template the smplx `SMPL(age='kid', kid_template_path=...)` branch reads -> float32 [NV, 3].
+
+    `.npy`: the array itself (what smplx `np.load`s).  Anything else: a pickle holding `v_template` (the SMIL file of config.py),
+    read through the chumpy-free unpickler."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"kid template {path!r} not found: place the SMIL template there (config.SMIL_MODEL_DIR), pass "
+                                f"kid_template_path=, or register one with bodyfitting_amd.assets.register_kid_template()")
+    if path.endswith(".npy"):
+        t = np.load(path, allow_pickle=False)
+    else:
+        with open(path, "rb") as f:
+            d = _ModelUnpickler(f, encoding="latin1").load()
+        if not isinstance(d, dict) or "v_template" not in d:
+            raise ValueError(f"{path}: a kid template pickle must hold a dict with 'v_template'")
+        t = d["v_template"]
+    t = _dense(t)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError(f"{path}: kid template of shape {t.shape}, need [NV, 3]")
+    return t
+
+
+def kid_model(adult, template):
+    """The smplx `SMPL.__init__` kid branch on a model dict: the centred kid template minus the adult template becomes an 11th
+    shape direction behind the first ten; nothing else changes (the joints follow through J_regressor on the shaped mesh).
+
+        t = template - mean(template, axis=0)                          (float64, cast to float32 once)
+        shapedirs = concat(shapedirs[:, :, :10], (t - v_template)[:, :, None], axis=2)     -> [NV, 3, 11]
+    """
+    if adult.get("model_type", "smpl") != "smpl":
+        raise ValueError("age='kid' exists for SMPL only: the reference gives SMPL-X no kid template (it passes no age to smplx.create)")
+    vt = np.asarray(adult["v_template"], np.float32)
+    t64 = np.asarray(template, np.float64)
+    if t64.shape != vt.shape:
+        raise ValueError(f"kid template of shape {t64.shape} does not match the adult model's template {vt.shape}")
+    t = (t64 - t64.mean(axis=0)).astype(np.float32)
+    kid_dir = (t - vt)[:, :, None]
+    out = dict(adult)
+    out["shapedirs"] = np.ascontiguousarray(np.concatenate([np.asarray(adult["shapedirs"], np.float32)[:, :, :N_BETAS], kid_dir], axis=2))
+    return out
+
+
 def find(model_type, gender, folder="data"):
     """The path the reference's smplx call resolves: `data/smpl/SMPL_MALE.pkl` (config.py:4) / `data/smplx/SMPLX_MALE.npz`."""
     g = gender.upper()

@@ -34,12 +34,11 @@ class ModelOutput:                       # models/smpl.py:38-54 (whose __getitem
 class SMPL:
     def __init__(self, model_path=None, batch_size=1, gender="neutral", age="adult", create_transl=True,
                  kid_template_path=None, device=0, **kwargs):
-        if age != "adult":
-            raise NotImplementedError("age='kid' needs a newer smplx than the reference pins (SURVEY.md 8c); out of scope")
+        # age='kid': the 11-direction model of smplx's kid branch (model_files.kid_model), betas[B, 11]
         self.batch_size = batch_size
-        self.gender = gender
-        self._dev = assets.get_device_model("smpl", gender, device)
-        model = assets.get_model("smpl", gender)
+        self.gender, self.age = gender, age
+        self._dev = assets.get_device_model("smpl", gender, device, age=age, kid_template_path=kid_template_path)
+        model = assets.get_model("smpl", gender, age, kid_template_path)
         self.faces = np.asarray(model["faces"]) if "faces" in model else None
         self.J_regressor_extra = np.asarray(model["J_regressor_extra"], dtype=np.float32)
         self.J_regressor_h36m = np.asarray(model["J_regressor_h36m"], dtype=np.float32) if "J_regressor_h36m" in model else None

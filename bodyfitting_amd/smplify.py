@@ -3,6 +3,8 @@
 Same constructor arguments, same `__call__` signature, same result dict (numpy arrays, batch
 dimension squeezed): vertices[NV,3], joints[49,3], pose[69], betas[10], global_orient[3], faces,
 global_transl[3] (= t*s, without the constant scale), scale[1], full_pose[72].
+age='kid' (SMPL only, smplify.py:51-56,112-115): the model gets the kid template's 11th shape direction, the fit starts from
+betas = 0 whatever `init_betas` say (width 10 or 11) and the result's betas are [11].
 
 Differences, all at the edges: the model / GMM are resolved once per process through
 `bodyfitting_amd.assets` instead of being re-read per frame; `net_output` may hold numpy arrays or
@@ -41,8 +43,11 @@ class SMPLify:
                  use_mask=False, device=0, debug=True):
         if smpl_type not in ("smpl", "smplx"):
             raise ValueError(f"unknown smpl_type {smpl_type!r}")
-        if age != "adult":
-            raise NotImplementedError("age='kid' is out of scope (SURVEY.md 8c)")
+        if age not in ("adult", "kid"):
+            raise ValueError(f"unknown age {age!r}: 'adult' or 'kid'")
+        if age == "kid" and smpl_type == "smplx":
+            raise ValueError("SMPLify(smpl_type='smplx', age='kid') is not supported: the reference builds SMPL-X without a kid "
+                             "template (no age reaches smplx.create) and then optimises 11 betas against its 10 shape directions")
         self.smpl_type, self.age, self.gender = smpl_type, age, gender
         self.use_hand_face = smpl_type == "smplx"
         self.use_mask = use_mask
@@ -50,10 +55,22 @@ class SMPLify:
         self.num_iters = num_iters          # step_size is ignored by the reference too (smplify.py:24,174)
         self.debug = debug
         self.device = _device_index(device)
-        self._dev = assets.get_device_model(smpl_type, gender, self.device)
-        model = assets.get_model(smpl_type, gender)
+        # (kid: smplify.py:51-56 builds SMPL with kid_template_path=config.SMIL_MODEL_DIR - the 11-direction model; the template is
+        #  the registered one or that file, assets.get_kid_template)
+        self._dev = assets.get_device_model(smpl_type, gender, self.device, age=age)
+        model = assets.get_model(smpl_type, gender, age)
         self.smpl_faces = np.asarray(model["faces"]).astype(np.int32).reshape(1, -1, 3)    # smplify.py:82
         self._batches = {}                  # (frames, views) -> FrameBatch: device buffers, stream and pinned mirrors are kept between calls
+
+    def _init_betas(self, init_betas):
+        """[F, n_betas] float32: the caller's estimate, or - kid, smplify.py:112-115 - zeros of the model's 11 betas (the estimate,
+        10 or 11 wide, is ignored)"""
+        b = np.asarray(init_betas, np.float32)
+        if self.age == "kid":
+            if b.ndim == 0 or b.shape[-1] not in (10, self._dev.n_betas):
+                raise ValueError(f"init_betas of shape {b.shape}: a kid fit takes 10 or {self._dev.n_betas} per frame (and ignores them)")
+            return np.zeros((b.reshape(-1, b.shape[-1]).shape[0], self._dev.n_betas), np.float32)
+        return b.reshape(-1, self._dev.n_betas)
 
     def _batch(self, F, V):
         """The reference builds everything anew per frame (body_fitting.py:82); creating and destroying the device side of a
@@ -81,13 +98,13 @@ class SMPLify:
                    mask_view_index=None):
         """Fit F independent frames in one launch.
 
-        init_betas[F,10], init_poses[F,72], c2ws[F,V,4,4], Ks[F,V,3,3], keypoints[F,V,25,3]
+        init_betas[F,10] (kid: ignored, the fit starts from zeros[F,11]), init_poses[F,72], c2ws[F,V,4,4], Ks[F,V,3,3], keypoints[F,V,25,3]
         (confidence 0 = no detection); scans: optional list of F (verts, faces) scan meshes (use_mesh=True:
         the point-cloud loss switches on after num_iters // 3 and the constant scale becomes
         scan_height / 1.7, smplify.py:146-156,205-210); displacement: run the SMPL+D stage afterwards
         (smplify.py:228-247); masks: uint8[F,M,H,W] silhouettes of the views mask_view_index[M] (use_mask=True:
         5 * multview_mask_loss after num_iters // 3, smplify.py:138-144,197-199).  Returns a list of F result dicts."""
-        init_betas = np.asarray(init_betas, np.float32).reshape(-1, self._dev.n_betas)
+        init_betas = self._init_betas(init_betas)
         F = init_betas.shape[0]
         c2ws = np.asarray(c2ws, np.float32).reshape(F, -1, 4, 4)
         V = c2ws.shape[1]
@@ -212,7 +229,7 @@ class SMPLify:
             issued = 0
             for net_output, keypoints in frames:
                 betas, poses = (_np(x) for x in net_output)
-                batch.stage_inputs(pack(keypoints), [V], betas[:1], poses[:1])
+                batch.stage_inputs(pack(keypoints), [V], self._init_betas(betas[:1]), poses[:1])
                 batch.fit(self.num_iters, hyper, flags)
                 issued += 1
                 if issued > 1:
@@ -274,7 +291,7 @@ class SMPLify:
                     batch.clear_masks(); batch._had_masks = False
                 hyper = make_hyper(imsize=imsize, constant_scale=0.3)
                 state_hyper[0] = hyper
-                batch.stage_inputs(kp, [V], betas[:1], poses[:1])
+                batch.stage_inputs(kp, [V], self._init_betas(betas[:1]), poses[:1])
                 batch.fit(self.num_iters, hyper, _lib.FIT_RESET | _lib.FIT_FETCH)
                 in_flight = (scan, bool(displacement and scan is not None))
             if in_flight is not None:
@@ -305,8 +322,9 @@ class SMPLify:
         for i in range(V):
             if keypoints[i] is not None:                                               # loss.py:157
                 kp[i] = pack_keypoints_smplx(keypoints[i]) if self.use_hand_face else np.asarray(keypoints[i]["pose"], np.float32)[:nl]
+        init_betas = self._init_betas(init_betas[:1])                             # (kid: zeros[1, 11], smplify.py:115)
         if mk is None and scans is None and not self.use_hand_face:
-            return self._call_staged(init_betas[:1], init_poses[:1], c2w, K, kp, imsize)
+            return self._call_staged(init_betas, init_poses[:1], c2w, K, kp, imsize)
         res = self.fit_frames(init_betas[:1], init_poses[:1], c2w[None], K[None], kp[None], n_use_frames=[V],
                               imsize=imsize, scans=scans, displacement=displacement, masks=mk,
                               mask_view_index=mk_idx)[0]                               # divisor loss.py:197

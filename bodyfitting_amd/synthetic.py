@@ -539,6 +539,35 @@ def make_problem(model, frame=0, n_views=48, imsize=512, constant_scale=0.3, pos
     }
 
 
+def make_kid_template(model, seed=0):
+    """A synthetic stand-in for the SMIL kid template (no licensed file ships): the adult template shrunk about its centre, the
+    height more than the width, with a few millimetres of smooth relief so that the kid direction is not a pure scaling.
+    float32 [NV, 3], not centred (model_files.kid_model centres it)."""
+    rng = np.random.default_rng(7000 + seed)
+    vt = np.asarray(model["v_template"], np.float64)
+    c = vt.mean(0)
+    kid = (vt - c) * np.array([0.66, 0.58, 0.66]) + c + np.array([0.01, -0.02, 0.005])
+    kid += 0.003 * np.sin(vt * 9.0 + rng.uniform(0, 6.28, size=3))
+    return kid.astype(np.float32)
+
+
+def kid_problem_model(kid_model, kid_beta):
+    """The kid model with its 11th beta folded into the template: make_problem / make_scan_problem draw 10 ground-truth betas, so a
+    problem made from this model is the kid model's problem with betas_gt[10] = kid_beta (same random draws otherwise)."""
+    out = dict(kid_model)
+    sd = np.asarray(kid_model["shapedirs"], np.float64)
+    out["v_template"] = (np.asarray(kid_model["v_template"], np.float64) + kid_beta * sd[:, :, 10]).astype(np.float32)
+    out["shapedirs"] = np.ascontiguousarray(np.asarray(kid_model["shapedirs"])[:, :, :10])
+    return out
+
+
+def as_kid_problem(prob, kid_beta):
+    """a problem of `kid_problem_model`'s -> the kid problem: betas start at zeros[1, 11] (smplify.py:115), the GT gets its 11th beta"""
+    out = dict(prob, init_betas=np.zeros((1, 11), np.float32))
+    out["gt"] = dict(prob["gt"], betas=np.concatenate([np.asarray(prob["gt"]["betas"], np.float64), [kid_beta]]))
+    return out
+
+
 def _scan_noise(points, rng):
     """what separates a scan from the body under it, in units of `noise` (3 mm): smooth low-frequency relief (wavelengths of 25
     and 16 cm, SURVEY.md 8d: "GT posed mesh + smooth noise") plus a tenth of that as white sensor noise"""
