@@ -144,6 +144,13 @@ SIGNATURES = {
     "bf_texfit_step": (C.c_int, [_VP, _FP, _FP, _FP, C.c_float, C.c_float, C.POINTER(C.c_double)]),
     "bf_texfit_loss_grad": (C.c_int, [_VP, _FP, _FP, _FP, C.c_float, C.POINTER(C.c_double), _FP]),
     "bf_texfit_get_textures": (C.c_int, [_VP, _FP]),
+    "bf_hmr_n_weights": (C.c_int64, []),
+    "bf_hmr_create": (C.c_int, [C.c_int, _FP, C.c_int64, _FP, C.c_int, C.POINTER(_VP)]),
+    "bf_hmr_destroy": (None, [_VP]),
+    "bf_hmr_predict": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), _FP, _FP, _FP]),
+    "bf_hmr_features": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), _FP]),
+    "bf_hmr_preprocess": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _FP]),
+    "bf_hmr_selftest_conv": (C.c_int, [C.c_int] * 9 + [_FP, _FP, _FP, _FP, C.c_int, _FP]),
     "bf_batch_debug_dump": (C.c_int, [_VP, _FP, C.c_int]),
     "bf_batch_debug_disp_moment": (C.c_int, [_VP, _FP]),
 }

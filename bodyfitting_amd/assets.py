@@ -14,6 +14,9 @@ per *frame*.  Here a model is resolved once per process and cached per (type, ge
 age='kid' (SMPL only) is the adult model with the kid template's 11th shape direction (`model_files.kid_model`); the template is
 the one registered with `register_kid_template(...)`, else the file at `kid_template_path` (default `data/smil/smil_web.pkl`,
 config.SMIL_MODEL_DIR).  Kid models are cached under (type, gender, 'kid'); the adult keys are those of before.
+
+The HMR weights of the initial estimate (`hmr.HMR`) are the state dict registered with `register_hmr(...)`, else the reference's
+`data/model_checkpoint.pt` + `data/smpl_mean_params.npz` (config.HMR_CHECKPOINT, config.SMPL_MEAN_PARAMS), folded and packed once.
 """
 from __future__ import annotations
 
@@ -28,6 +31,9 @@ _MODELS = {}
 _GMM = {}
 _DEVICE_MODELS = {}
 _KID_TEMPLATE = {}
+_HMR = {}
+HMR_CHECKPOINT = "model_checkpoint.pt"          # config.HMR_CHECKPOINT / SMPL_MEAN_PARAMS, in the data folder of the model files
+SMPL_MEAN_PARAMS = "smpl_mean_params.npz"
 
 
 def _drop_kid(model_type=None, gender=None):
@@ -146,3 +152,34 @@ def get_device_model(model_type="smpl", gender="neutral", device=0, age="adult",
     if key not in _DEVICE_MODELS:
         _DEVICE_MODELS[key] = DeviceModel(get_model(model_type, gender, age, kid_template_path), get_gmm(), device=device)
     return _DEVICE_MODELS[key]
+
+
+def register_hmr(state_dict, mean_params=None):
+    """HMR weights held in memory (tests, callers that load them themselves): a state dict as the checkpoint's 'model' entry and,
+    when it lacks init_pose / init_shape / init_cam, the mean parameters (dict with pose[144], shape[10], cam[3]).  None forgets
+    them.  Matched as the reference matches `model_checkpoint.pt` (unexpected keys ignored)."""
+    _HMR.clear()
+    if state_dict is not None:
+        from . import hmr
+        _HMR["packed"] = hmr.fold_and_pack(hmr.match_state(state_dict, HMR_CHECKPOINT, mean_params))
+
+
+def hmr_paths(folder="data"):
+    return os.path.join(folder, HMR_CHECKPOINT), os.path.join(folder, SMPL_MEAN_PARAMS)
+
+
+def get_hmr(folder="data"):
+    """-> (packed float32 weights, mean state float32[157]) for hmr.HMR, read once per process"""
+    if "packed" in _HMR:
+        return _HMR["packed"]
+    from . import hmr
+    ckpt, npz = hmr_paths(folder)
+    if not (os.path.exists(ckpt) and os.path.exists(npz)):
+        raise ValueError(f"no initial estimate: HMR needs {ckpt} and {npz} (the reference's config.HMR_CHECKPOINT and "
+                         f"config.SMPL_MEAN_PARAMS), or weights registered with assets.register_hmr(); alternatively pass "
+                         f"net_output=(betas[1,10], pose[1,72]) or set options.init_estimator")
+    z = np.load(npz)
+    mean = {k: z[k] for k in ("pose", "shape", "cam")}
+    state = hmr.load_checkpoint(ckpt)["model"]
+    _HMR["packed"] = hmr.fold_and_pack(hmr.match_state(state, ckpt, mean))
+    return _HMR["packed"]

@@ -3,9 +3,9 @@
 Keeps `__init__(options)` / `__call__(images, c2ws, Ks, keypoints, gender=..., keyframe=..., use_frames=...,
 use_mask=..., masks=..., mask_frames=..., render_skip=..., output_folder=..., use_mesh=..., meshfile=...,
 disp=...)` and the files it writes (`{smpl_type}_parameter.npy` = pickled result dict, `{smpl_type}.obj`).
-The HMR initialisation (a ResNet-50 needing weights that do not ship, body_fitting.py:57-75) is out
-of scope: the initial (betas, pose) come from `options.init_estimator(image, c2w)` or from the
-`net_output=` keyword.
+The initial (betas, pose) come from the `net_output=` keyword, else from `options.init_estimator(image, c2w)`, else - as in
+the reference (body_fitting.py:57-75,86) - from HMR on `images[keyframe]` / `c2ws[keyframe]` (`hmr.HMR`, on the GPU; weights from
+`assets.get_hmr()`, one network per BodyFitting).
 """
 from __future__ import annotations
 
@@ -28,6 +28,7 @@ class BodyFitting:
         self.init_estimator = getattr(options, "init_estimator", None)
         self.num_iters = getattr(options, "num_iters", 600)            # smplify.py:26 default
         self._fitters = {}
+        self._hmr = None
 
     def _fitter(self, gender):
         if gender not in self._fitters:      # the reference rebuilds this per call (body_fitting.py:82)
@@ -36,14 +37,21 @@ class BodyFitting:
                                             device=getattr(self.options, "device", 0), debug=False)
         return self._fitters[gender]
 
+    def run_hmr(self, image, c2w):
+        """body_fitting.py:57-75: (pred_betas [1, 10], pred_poses [1, 72]) of one image, root rotation taken to world by c2w"""
+        if self._hmr is None:                 # (no weights registered and no files: ValueError naming the two files)
+            from .hmr import HMR
+            self._hmr = HMR(device=getattr(self.options, "device", 0), max_batch=1)
+        return self._hmr.predict([image], None if c2w is None else np.asarray(c2w)[None])
+
     def __call__(self, images, c2ws, Ks, keypoints, gender="male", keyframe=25, use_frames=list(range(48)),
                  use_mask=False, masks=None, mask_frames=None, render_skip=12, output_folder=None,
                  use_mesh=False, meshfile=None, disp=False, net_output=None):
         if net_output is None:
-            if self.init_estimator is None:
-                raise ValueError("no initial estimate: pass net_output=(betas[1,10], pose[1,72]) or set "
-                                 "options.init_estimator (the HMR network of the reference is out of scope)")
-            net_output = self.init_estimator(images[keyframe], c2ws[keyframe])
+            if self.init_estimator is not None:
+                net_output = self.init_estimator(images[keyframe], c2ws[keyframe])
+            else:
+                net_output = self.run_hmr(images[keyframe], c2ws[keyframe])
         imsize = images[0].shape[0] if images is not None else self.loadsize
         result = self._fitter(gender)(net_output, c2ws, Ks, keypoints, output_folder, use_mask=use_mask, masks=masks,
                                       use_frames=use_frames, mask_frames=mask_frames, keyframe=keyframe, imsize=imsize,

@@ -728,3 +728,45 @@ def make_scan_problem_smplx(model, frame=0, n_views=8, imsize=512, noise=0.003, 
             "init_betas": np.zeros((1, 10), np.float32),
             "init_pose": np.concatenate([init_pose, np.zeros(6)]).astype(np.float32)[None], "gt": gt, "constant_scale": cscale}
     return prob, sv, sf
+
+
+def make_hmr_weights(seed=0):
+    """A synthetic HMR state dict (numpy RNG, so anyone can recreate it) and mean parameters: He-normal convolutions (std
+    sqrt(2 / (k * k * cout)) as models/hmr.py initialises them), BatchNorm running statistics, gamma and beta away from the
+    identity so the fold is exercised, a small gamma on each block's bn3 so activations stay O(1), and small regressor weights.
+    -> (state dict with num_batches_tracked but WITHOUT init_pose / init_shape / init_cam, mean params {pose, shape, cam})."""
+    from . import hmr
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for conv, bn, cin, cout, k, _, _ in hmr.conv_layers():
+        sd[conv + ".weight"] = (rng.standard_normal((cout, cin, k, k)) * np.sqrt(2.0 / (k * k * cout))).astype(np.float32)
+        small = bn.endswith("bn3") or bn.endswith("downsample.1")
+        sd[bn + ".weight"] = (rng.uniform(0.1, 0.3, cout) if small else rng.uniform(0.6, 1.4, cout)).astype(np.float32)
+        sd[bn + ".bias"] = rng.normal(0.0, 0.1, cout).astype(np.float32)
+        sd[bn + ".running_mean"] = rng.normal(0.0, 0.2, cout).astype(np.float32)
+        sd[bn + ".running_var"] = rng.uniform(0.5, 2.0, cout).astype(np.float32)
+        sd[bn + ".num_batches_tracked"] = np.array(1000, np.int64)
+    for name, fin, fout in hmr.FC_LAYERS:
+        std = 0.01 if name.startswith("dec") else 1.0 / np.sqrt(fin)
+        sd[name + ".weight"] = (rng.standard_normal((fout, fin)) * std).astype(np.float32)
+        sd[name + ".bias"] = rng.normal(0.0, 0.01, fout).astype(np.float32)
+    rot = np.tile(np.array([1, 0, 0, 1, 0, 0], np.float32), 24) + rng.normal(0, 0.1, 144).astype(np.float32)
+    mean = {"pose": rot, "shape": rng.normal(0, 0.3, 10).astype(np.float32), "cam": np.array([0.9, 0.0, 0.0], np.float32)}
+    return sd, mean
+
+
+def make_hmr_images(seed=0, sizes=((512, 512), (480, 640), (224, 224))):
+    """smooth synthetic RGB uint8 images (a gradient, blobs and noise) of the given (H, W)"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for H, W in sizes:
+        y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+        img = np.zeros((H, W, 3))
+        for c in range(3):
+            img[..., c] = 128 + 60 * np.sin(x / W * rng.uniform(2, 9) + rng.uniform(0, 6)) * np.cos(y / H * rng.uniform(2, 9))
+            for _ in range(4):
+                cx, cy, r = rng.uniform(0, W), rng.uniform(0, H), rng.uniform(0.05, 0.3) * min(H, W)
+                img[..., c] += rng.uniform(-80, 80) * np.exp(-((x - cx) ** 2 + (y - cy) ** 2) / (2 * r * r))
+        img += rng.normal(0, 6, img.shape)
+        out.append(np.clip(np.rint(img), 0, 255).astype(np.uint8))
+    return out

@@ -409,6 +409,27 @@ int bf_texfit_step(bf_texfit *x, const float *R, const float *t, const float *K,
 int bf_texfit_loss_grad(bf_texfit *x, const float *R, const float *t, const float *K, float orig_size, double *loss, float *grad);
 int bf_texfit_get_textures(bf_texfit *x, float *textures);
 
+/* ---- HMR initial estimate (smplify/body_fitting.py:17-75, models/hmr.py) ----------------------------------------------------------
+ * The reference's run_hmr on the GPU in fp32: cv2.resize to 224 x 224 (INTER_LINEAR, OpenCV's 8-bit fixed-point arithmetic), /255,
+ * Normalize(IMG_NORM_MEAN, IMG_NORM_STD), ResNet-50 v1.5 in eval() and the iterative regressor (n_iter = 3).  Weights are packed by
+ * bodyfitting_amd/hmr.py in the order hmr_api.hip lists them, BatchNorm folded into each convolution (bf_hmr_n_weights floats);
+ * mean_params[157] = init_pose[144] | init_shape[10] | init_cam[3].  images[n][H][W][3] uint8 RGB, 1 <= n <= max_batch.
+ * rot6d_to_rotmat, the caller's root rotation and the rotation-matrix -> axis-angle conversion run on the host (hmr.py). */
+typedef struct bf_hmr bf_hmr;
+int64_t bf_hmr_n_weights(void);
+int bf_hmr_create(int device, const float *weights, int64_t n_weights, const float *mean_params, int max_batch, bf_hmr **out);
+void bf_hmr_destroy(bf_hmr *h);
+/* the regressor's final state: pose6d[n][144] (24 x the 6D rotation), betas[n][10], cam[n][3] */
+int bf_hmr_predict(bf_hmr *h, int n, int H, int W, const uint8_t *images, float *pose6d, float *betas, float *cam);
+/* the pooled backbone features xf[n][2048] */
+int bf_hmr_features(bf_hmr *h, int n, int H, int W, const uint8_t *images, float *xf);
+/* the image pipeline alone: resized[n][224][224][3] uint8 and / or normalized[n][224][224][3] fp32 (either may be NULL) */
+int bf_hmr_preprocess(bf_hmr *h, int n, int H, int W, const uint8_t *images, uint8_t *resized, float *normalized);
+/* test hook: one convolution of the HMR kernel on host arrays - x[n][H][W][cin] NHWC, w[k*k*cin][cout] in (ky, kx, ci) order,
+ * bias[cout], res[n][Ho][Wo][cout] or NULL, relu 0/1 -> y[n][Ho][Wo][cout] */
+int bf_hmr_selftest_conv(int device, int n, int H, int W, int cin, int cout, int k, int stride, int pad, const float *x, const float *w,
+                         const float *bias, const float *res, int relu, float *y);
+
 /* Device time of the kernels of the last bf_fit on this batch, from HIP events on the batch's
  * stream: ms[0] = fit loop kernel(s), ms[1] = final full-mesh forward kernel, ms[2] = joints kernel +
  * result fetch, ms[3] = whole call.  (With BF_FIT_DENSE every iteration's mesh pass is inside ms[0].) */
