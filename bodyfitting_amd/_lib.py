@@ -144,6 +144,9 @@ SIGNATURES = {
     "bf_texfit_step": (C.c_int, [_VP, _FP, _FP, _FP, C.c_float, C.c_float, C.POINTER(C.c_double)]),
     "bf_texfit_loss_grad": (C.c_int, [_VP, _FP, _FP, _FP, C.c_float, C.POINTER(C.c_double), _FP]),
     "bf_texfit_get_textures": (C.c_int, [_VP, _FP]),
+    "bf_texfit_render_depth": (C.c_int, [_VP, C.c_int, _FP, _FP, _FP, C.c_float, _FP, _FP]),
+    "bf_texfit_load_textures": (C.c_int, [C.c_int, C.c_int, _FP, _IP, _FP, C.c_int, C.POINTER(C.c_void_p), _IP, _IP, C.c_int, C.c_int,
+                                          C.c_int, _FP, _FP]),
     "bf_hmr_n_weights": (C.c_int64, []),
     "bf_hmr_create": (C.c_int, [C.c_int, _FP, C.c_int64, _FP, C.c_int, C.POINTER(_VP)]),
     "bf_hmr_destroy": (None, [_VP]),

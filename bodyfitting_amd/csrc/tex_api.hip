@@ -1,6 +1,8 @@
 // Host side of the texture-fitting loop (reference smplify/texture_fitting.py:240-275; kernels: tex_kernels.hip).
 #include "bf_host.h"
 
+#include <memory>
+
 struct TexView { float R[9], t[3], K[9], orig; };
 extern "C" __global__ void bf_tex_project_kernel(int, const float *, TexView, float *);
 extern "C" __global__ void bf_tex_face_kernel(int, const int *, const float *, int, int, float *, int *, int *, int *, int, int);
@@ -13,6 +15,9 @@ extern "C" __global__ void bf_tex_backward_kernel(int, int, int, int, const floa
 extern "C" __global__ void bf_tex_backward_large_kernel(int, int, int, const float *, const float *, int, const float *, float *);
 extern "C" __global__ void bf_tex_adam_kernel(size_t, float *, float *, float *, const float *, float, float, float, float, float, float);
 extern "C" __global__ void bf_grid_scan_kernel(int *, int *, int);
+struct TexImage { const unsigned char *p; int h, w; };
+extern "C" __global__ void bf_tex_load_kernel(long long, int, const float *, const int *, const float *, const TexImage *, const float *, int, int,
+                                              float *);
 
 #define BF_TEX_TILE 8
 #define BF_TEX_REC 20
@@ -241,6 +246,28 @@ int bf_texfit_render(bf_texfit *x, int which, const float *R, const float *t, co
     return fail(BF_ERR_HIP, "bf_texfit_render: the tile lists keep overflowing");
 }
 
+// Renderer.render (neural_renderer/renderer.py:234-292 -> rasterize_rgbad) as utils/renderer.py:50-55 calls it: bf_texfit_render's rgb
+// and the depth map pooled like the colours (far where no face was drawn); either output may be NULL
+int bf_texfit_render_depth(bf_texfit *x, int which, const float *R, const float *t, const float *K, float orig_size, float *rgb, float *depth) {
+    if (!x || which < 0 || which > 1 || !R || !t || !K) return fail(BF_ERR_INVALID, "bf_texfit_render_depth: bad argument");
+    HIP_TRY(hipSetDevice(x->device));
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        int rc = tex_render(x, which, make_view(R, t, K, orig_size));
+        if (rc) return rc;
+        hipLaunchKernelGGL(bf_tex_depth_kernel, dim3((x->out * x->out + 255) / 256), dim3(256), 0, x->stream, x->out, x->aa,
+                           (const float *)x->mesh[which].pix.p, x->depth_image.p);
+        HIP_TRY(hipGetLastError());
+        if (rgb) HIP_TRY(hipMemcpyAsync(rgb, x->image[which].p, x->image[which].n * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+        if (depth) HIP_TRY(hipMemcpyAsync(depth, x->depth_image.p, x->depth_image.n * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+        HIP_TRY(hipStreamSynchronize(x->stream));
+        bool fit = true;
+        rc = tex_lists_fit(x, which, &fit);
+        if (rc) return rc;
+        if (fit) return BF_OK;
+    }
+    return fail(BF_ERR_HIP, "bf_texfit_render_depth: the tile lists keep overflowing");
+}
+
 // One iteration of texture_fitting.py:262-270: render both meshes from the view, loss = sum |scan_img - smpl_img|, backward to
 // the fitted mesh's textures, one Adam step (lr; torch defaults otherwise).  *loss receives the loss of THIS view before the step.
 int bf_texfit_step(bf_texfit *x, const float *R, const float *t, const float *K, float orig_size, float lr, double *loss) {
@@ -281,6 +308,77 @@ int bf_texfit_get_textures(bf_texfit *x, float *textures) {
     HIP_TRY(hipStreamSynchronize(x->stream));
     HIP_TRY(hipMemcpy(textures, x->mesh[1].tex.p, x->mesh[1].tex.n * sizeof(float), hipMemcpyDeviceToHost));
     return BF_OK;
+}
+
+// nr.load_obj's per-face texture cubes (load_obj.py:31-95 + load_textures_cuda_kernel.cu) from the arrays bodyfitting_amd/obj_textures.py
+// reads: one bf_tex_load_kernel launch over every face.  Images no face uses are not uploaded.
+int bf_texfit_load_textures(int device, int n_faces, const float *face_uv, const int32_t *face_image, const float *face_fill, int n_images,
+                            const uint8_t *const *images, const int32_t *heights, const int32_t *widths, int texture_size, int wrapping,
+                            int bilinear, float *textures, float *ms) {
+    if (n_faces <= 0 || !face_uv || !face_image || !face_fill || !textures || n_images < 0 || (n_images && (!images || !heights || !widths)))
+        return fail(BF_ERR_INVALID, "bf_texfit_load_textures: bad argument");
+    if (texture_size < 2 || texture_size > 256) return fail(BF_ERR_INVALID, "bf_texfit_load_textures: texture_size must be in [2, 256]");
+    if (wrapping < 0 || wrapping > 3) return fail(BF_ERR_INVALID, "bf_texfit_load_textures: wrapping must be 0..3");
+    std::vector<char> used(n_images, 0);
+    for (int f = 0; f < n_faces; ++f) {
+        if (face_image[f] < -1 || face_image[f] >= n_images) return fail(BF_ERR_INVALID, "bf_texfit_load_textures: face_image out of range");
+        if (face_image[f] >= 0) used[face_image[f]] = 1;
+    }
+    for (int j = 0; j < n_images; ++j)
+        if (used[j] && (!images[j] || heights[j] <= 0 || widths[j] <= 0))
+            return fail(BF_ERR_INVALID, "bf_texfit_load_textures: bad image");
+    if (device < 0 || device >= bf_device_count()) return fail(BF_ERR_NO_DEVICE, "bf_texfit_load_textures: no such HIP device");
+    HIP_TRY(hipSetDevice(device));
+    // the byte -> float table of the reference's imread(...).astype(np.float32) / 255. (a correctly rounded float32 division)
+    std::vector<float> lut(256);
+    for (int b = 0; b < 256; ++b) lut[b] = (float)b / 255.0f;
+    const long long t3 = (long long)texture_size * texture_size * texture_size, n_texels = (long long)n_faces * t3;
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    auto cleanup = [&] {
+        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        if (s) (void)hipStreamDestroy(s);
+    };
+    std::unique_ptr<DevBuf<unsigned char>[]> img(new DevBuf<unsigned char>[std::max(n_images, 1)]);
+    DevBuf<float> uv, fill, tex, lut_d;
+    DevBuf<int> fimg;
+    DevBuf<TexImage> desc;
+    int rc = BF_OK;
+    auto run = [&]() -> int {
+        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(uv.alloc((size_t)n_faces * 6)); HIP_TRY(fill.alloc((size_t)n_faces * 3)); HIP_TRY(fimg.alloc(n_faces));
+        HIP_TRY(lut_d.alloc(256)); HIP_TRY(tex.alloc((size_t)n_texels * 3)); HIP_TRY(desc.alloc(std::max(n_images, 1)));
+        std::vector<TexImage> d(std::max(n_images, 1), TexImage{nullptr, 0, 0});
+        for (int j = 0; j < n_images; ++j)
+            if (used[j]) {
+                HIP_TRY(img[j].alloc((size_t)heights[j] * widths[j] * 3));
+                d[j] = TexImage{img[j].p, heights[j], widths[j]};
+            }
+        HIP_TRY(hipEventRecord(ev[0], s));
+        HIP_TRY(hipMemcpyAsync(uv.p, face_uv, uv.n * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(fill.p, face_fill, fill.n * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(fimg.p, face_image, fimg.n * sizeof(int), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(lut_d.p, lut.data(), 256 * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(desc.p, d.data(), d.size() * sizeof(TexImage), hipMemcpyHostToDevice, s));
+        for (int j = 0; j < n_images; ++j)
+            if (used[j]) HIP_TRY(hipMemcpyAsync(img[j].p, images[j], img[j].n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(ev[1], s));
+        hipLaunchKernelGGL(bf_tex_load_kernel, dim3((unsigned)((n_texels + 255) / 256)), dim3(256), 0, s, n_texels, texture_size,
+                           (const float *)uv.p, (const int *)fimg.p, (const float *)fill.p, (const TexImage *)desc.p, (const float *)lut_d.p,
+                           wrapping, bilinear ? 1 : 0, tex.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[2], s));
+        HIP_TRY(hipMemcpyAsync(textures, tex.p, tex.n * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(ev[3], s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (ms)
+            for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(ms + k, ev[k], ev[k + 1]));
+        return BF_OK;
+    };
+    rc = run();
+    cleanup();
+    return rc;
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 //                           sampling weight x dL/drgb into the face's texture cube (sampling indices / weights recomputed from
 //                           the stored weights and depth: 20 bytes per pixel kept instead of 64)
 //   bf_tex_adam_kernel      torch.optim.Adam (defaults) on every texel
+//   bf_tex_load_kernel      load_textures_cuda_kernel (cuda/load_textures_cuda_kernel.cu): the per-face texture cubes of nr.load_obj
 #include "bf_internal.h"
 
 #define BF_TEX_TILE 8
@@ -345,4 +346,91 @@ bf_tex_adam_kernel(size_t n, float *__restrict__ p, float *__restrict__ m, float
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     p[i] = p[i] - step_size * (mi / denom);
     m[i] = mi; v[i] = vi;
+}
+
+// ---- texture loading: load_textures_cuda_kernel (thirdparty/neural_renderer/neural_renderer/cuda/load_textures_cuda_kernel.cu), which
+// nr.load_obj(..., load_texture=True) runs once per material with a texture image.  Here ONE launch covers every face: face_image[fn]
+// names the face's image (-1: none - the face keeps face_fill, the 0.5 default or its material's Kd).  Thread = texel (i over
+// n_faces * ts^3, as in the reference), each writes its whole texel: a wave stores 64 consecutive 12-byte texels.
+// The image is the decoded file as uint8 [h][w][3], top row first; the reference's image[::-1] and / 255. happen here (the row
+// index is mirrored, the byte goes through lut[256] = float32(b) / 255, the division numpy does).
+// Wrapping is applied ONCE per face, to the face's own copy of its UV corners.  (The reference wraps the shared `faces` array in
+// place from every thread of the face; where mod() is not idempotent - exact integers, MIRRORED_REPEAT at integer boundaries - its
+// result depends on how many threads got there first.  DESIGN.md section 2.)
+struct TexImage { const unsigned char *p; int h, w; };
+
+#define BF_TEX_REPEAT 0
+#define BF_TEX_MIRRORED_REPEAT 1
+#define BF_TEX_CLAMP_TO_EDGE 2
+#define BF_TEX_CLAMP_TO_BORDER 3
+
+__device__ __forceinline__ float tex_mod(float x, float y) { return x > 0.f ? fmodf(x, y) : y + fmodf(x, y); }
+
+// one channel of the flipped, normalised image at (row y, column x) of the flipped image; indices kept inside the image (a no-op
+// for every finite UV: the wrapped corners lie in [0, 1])
+__device__ __forceinline__ float tex_texel(const TexImage &I, const float *lut, int y, int x, int k) {
+    y = min(max(y, 0), I.h - 1);
+    x = min(max(x, 0), I.w - 1);
+    return lut[I.p[((size_t)(I.h - 1 - y) * I.w + x) * 3 + k]];
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+bf_tex_load_kernel(long long n_texels, int ts, const float *__restrict__ face_uv, const int *__restrict__ face_image,
+                   const float *__restrict__ face_fill, const TexImage *__restrict__ images, const float *__restrict__ lut_g,
+                   int wrapping, int bilinear, float *__restrict__ textures) {
+    __shared__ float lut[256];
+    lut[threadIdx.x] = lut_g[threadIdx.x];
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_texels) return;
+    const int t3 = ts * ts * ts;
+    const long long fn = i / t3;
+    const int r = (int)(i - fn * t3);
+    float *out = textures + i * 3;
+    const int img = face_image[fn];
+    if (img < 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[k] = face_fill[fn * 3 + k];
+        return;
+    }
+    if (wrapping == BF_TEX_CLAMP_TO_BORDER) {             // (the reference samples nothing and writes 0)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[k] = 0.f;
+        return;
+    }
+    // the barycentric position of the texel: computed in double, stored as float, renormalised by the float sum
+    float dim0 = (float)((r / (ts * ts)) / (ts - 1.)), dim1 = (float)(((r / ts) % ts) / (ts - 1.)), dim2 = (float)((r % ts) / (ts - 1.));
+    if (0 < dim0 + dim1 + dim2) {
+        const float sum = dim0 + dim1 + dim2;
+        dim0 /= sum; dim1 /= sum; dim2 /= sum;
+    }
+    float f[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const float x = face_uv[fn * 6 + k];
+        if (wrapping == BF_TEX_REPEAT) f[k] = tex_mod(x, 1.f);
+        else if (wrapping == BF_TEX_MIRRORED_REPEAT) f[k] = tex_mod(x, 2.f) < 1 ? tex_mod(x, 1.f) : 1 - tex_mod(x, 1.f);
+        else f[k] = fmaxf(fminf(x, 1.f), 0.f);
+    }
+    const TexImage I = images[img];
+    const float pos_x = ((f[0] * dim0 + f[2] * dim1) + f[4] * dim2) * (float)(I.w - 1);
+    const float pos_y = ((f[1] * dim0 + f[3] * dim1) + f[5] * dim2) * (float)(I.h - 1);
+    if (bilinear) {
+        const float weight_x1 = pos_x - (int)pos_x, weight_x0 = 1 - weight_x1;
+        const float weight_y1 = pos_y - (int)pos_y, weight_y0 = 1 - weight_y1;
+        const int x0 = (int)pos_x, y0 = (int)pos_y, x1 = min((int)pos_x + 1, I.w - 1), y1 = min((int)(pos_y + 1), I.h - 1);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            float c = 0;
+            c += tex_texel(I, lut, y0, x0, k) * (weight_x0 * weight_y0);
+            c += tex_texel(I, lut, y1, x0, k) * (weight_x0 * weight_y1);
+            c += tex_texel(I, lut, y0, x1, k) * (weight_x1 * weight_y0);
+            c += tex_texel(I, lut, y1, x1, k) * (weight_x1 * weight_y1);
+            out[k] = c;
+        }
+    } else {
+        const int xi = (int)roundf(pos_x), yi = (int)roundf(pos_y);          // (roundf: half away from zero, as CUDA's round)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[k] = tex_texel(I, lut, yi, xi, k);
+    }
 }

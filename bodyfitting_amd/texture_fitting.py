@@ -4,7 +4,8 @@
 as arrays - (vertices[NV,3], faces[NF,3], textures[NF,ts,ts,ts,3]), what `nr.load_obj(..., load_texture=True)` returns - in
 place of OBJ directories: ring views first (`gen_cam_views`, 18 views x 5 rounds), random views on the sphere after, one
 render of each mesh + L1 loss + Adam step on the SMPL+D textures per iteration, all inside libbodyfit (bf_texfit_*).
-OBJ / MTL / image files, the UV texture image and the inpainting CNN (:276-289) stay with the caller.
+The OBJ / MTL / image files are read by `obj_textures.load_obj`; `texture_dropin.TextureFitting` is the reference's class with
+its file-level `__call__` on top of this loop.  The inpainting CNN (:276-289) is out of scope.
 """
 from __future__ import annotations
 
@@ -124,6 +125,16 @@ class Renderer:
                                               self.orig_size, _lib.fptr(out)), "bf_texfit_render")
         return out
 
+    def render_rgbd(self, which, pose):
+        """`Renderer.render(vertices, faces, textures)` of neural_renderer (renderer.py:234-292, rasterize_rgbad) for the mesh in slot
+        `which` -> (rgb[3, image_size, image_size] = render_rgb's, depth[image_size, image_size] pooled like it, far where empty)"""
+        R, t = self._view(pose)
+        rgb = np.empty((3, self.image_size, self.image_size), np.float32)
+        depth = np.empty((self.image_size, self.image_size), np.float32)
+        _lib.check(self._lib.bf_texfit_render_depth(self._h, int(which), _lib.fptr(R), _lib.fptr(t), _lib.fptr(self.K), self.orig_size,
+                                                    _lib.fptr(rgb), _lib.fptr(depth)), "bf_texfit_render_depth")
+        return rgb, depth
+
     def render_texture(self, uv, uv_faces, textures=None):
         """`Renderer.render_texture(filename_obj, textures)` of neural_renderer (renderer.py:294-346) with the OBJ's contents as
         arrays: uv[n,2] = its `vt` lines, uv_faces[NF,3] = the 0-based vt indices of its faces (same face order as the fitted
@@ -193,11 +204,12 @@ class TextureFitting:
             return round_poses[i % len(round_poses)]
         return np.linalg.inv(sphere2rot(dist, self.rng.uniform(0, np.pi), self.rng.uniform(0, np.pi * 2), t=center))
 
-    def fit(self, smpld_mesh, scan_mesh, poses=None):
-        """-> (fitted textures [NF,ts,ts,ts,3], losses[iter_num]); `poses` overrides the view schedule (tests)"""
+    def fit(self, smpld_mesh, scan_mesh, poses=None, far=None, before_step=None, after_fit=None):
+        """-> (fitted textures [NF,ts,ts,ts,3], losses[iter_num]); `poses` overrides the view schedule (tests), `far` the far plane
+        2 x dist; before_step(i, pose, renderer) runs before each step, after_fit(renderer) after the last (the drop-in's images)"""
         smpld_mesh, scan_mesh = _mesh(smpld_mesh), _mesh(scan_mesh)
         center, dist = scene_bound(scan_mesh[0])
-        r = Renderer(self.img_size, smpld_mesh[2].shape[1], near=0.0, far=2.0 * dist, device=self.device)
+        r = Renderer(self.img_size, smpld_mesh[2].shape[1], near=0.0, far=2.0 * dist if far is None else far, device=self.device)
         try:
             r.set_mesh(Renderer.TARGET, scan_mesh)
             r.set_mesh(Renderer.FITTED, smpld_mesh)
@@ -205,9 +217,13 @@ class TextureFitting:
             losses = []
             for i in range(self.iter_num):
                 pose = poses[i] if poses is not None else self.view(i, ring, center, dist)
+                if before_step is not None:
+                    before_step(i, pose, r)
                 losses.append(r.step(pose, self.lrate))
                 if self.logging:
                     print(f"texture fitting iter {i}, loss {losses[-1]}")
+            if after_fit is not None:
+                after_fit(r)
             return r.textures(), np.asarray(losses)
         finally:
             r.close()
