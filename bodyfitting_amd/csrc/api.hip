@@ -15,7 +15,6 @@ extern "C" hipError_t bf_mesh_batch32_launch(const MeshTab *M, const float *stat
 extern "C" void bf_mesh_epilogue_batch_launch(const MeshTab *M, const float *state, const float *pose_off, int n, float *vraw, float *vout, float *xpart, hipStream_t stream);
 extern "C" __global__ void bf_joints_kernel(MeshTab, const float *, const float *, const float *, float *, float *, float *, int *, float *);
 extern "C" size_t bf_fit_smem_bytes(int, int, int, int, int, int, int);
-extern "C" size_t bf_mesh_smem_bytes(int, int, int);
 
 // The HIP runtime multiplexes all streams of a process over its hardware queues, and streams that share a queue run in order.  A batch
 // uses up to three streams that must run side by side (batch stream; second stream for a call's mesh tail / the side kernels of a dense
@@ -54,464 +53,6 @@ void bf_hyper_default(bf_hyper *h) {
     h->mask_cdist_form = 1.f;
     h->dense_after = -1.f;
 }
-
-int bf_model_create(const bf_model_desc *d, int device, bf_model **out) {
-    if (!d || !out) return fail(BF_ERR_INVALID, "bf_model_create: null argument");
-    *out = nullptr;
-    if (bf_device_count() <= device || device < 0) return fail(BF_ERR_NO_DEVICE, "bf_model_create: no such HIP device");
-    if (d->n_verts <= 0 || d->n_joints < 2 || d->n_joints > 64 || d->n_betas <= 0 || d->n_betas > 12)
-        return fail(BF_ERR_UNSUPPORTED, "bf_model_create: need 2..64 joints and 1..12 betas");
-    if (d->gmm_components != BF_GMM_M || d->gmm_dim != BF_GMM_D)
-        return fail(BF_ERR_UNSUPPORTED, "bf_model_create: the GMM prior must be 8 components x 69 dims");
-    if (d->n_loss_joints <= 0 || d->n_loss_joints > 192 || d->n_loss_joints > d->n_joint_map)
-        return fail(BF_ERR_UNSUPPORTED, "bf_model_create: 1..192 loss joints supported");
-    const bool smplx = d->model_kind == 1;
-    const int n_lmk = smplx ? d->n_lmk_static + d->n_lmk_dynamic : 0;
-    if (d->n_extra > 32 || d->n_joints + d->n_selector + d->n_extra + n_lmk > 256)
-        return fail(BF_ERR_UNSUPPORTED, "bf_model_create: too many auxiliary joints");
-    if (smplx) {
-        if (d->n_joints != 55 || d->n_hand_pca <= 0 || d->n_hand_pca > 6 || !d->pose_mean || !d->left_hand_components ||
-            !d->right_hand_components || !d->faces || d->n_faces <= 0 || !d->lmk_faces_idx || !d->lmk_bary_coords ||
-            (d->n_lmk_dynamic > 0 && (!d->dynamic_lmk_faces_idx || !d->dynamic_lmk_bary_coords || d->n_dyn_rows < 79)) ||
-            d->neck_joint < 0 || d->neck_joint >= 55)
-            return fail(BF_ERR_INVALID, "bf_model_create: incomplete SMPL-X description");
-    }
-    const int nv = d->n_verts, nj = d->n_joints, nb = d->n_betas, npf = 9 * (nj - 1);
-    if (d->parents[0] != -1) return fail(BF_ERR_INVALID, "bf_model_create: parents[0] must be -1");
-    for (int j = 1; j < nj; ++j)
-        if (d->parents[j] < 0 || d->parents[j] >= j) return fail(BF_ERR_INVALID, "bf_model_create: parents[i] must be in [0,i)");
-    for (int i = 0; i < d->n_selector; ++i)
-        if (d->selector_ids[i] < 0 || d->selector_ids[i] >= nv) return fail(BF_ERR_INVALID, "bf_model_create: selector id out of range");
-    const int n_all = nj + d->n_selector + d->n_extra + ((d->model_kind == 1) ? d->n_lmk_static + d->n_lmk_dynamic : 0);
-    for (int i = 0; i < d->n_joint_map; ++i)
-        if (d->joint_map[i] < 0 || d->joint_map[i] >= n_all) return fail(BF_ERR_INVALID, "bf_model_create: joint_map entry out of range");
-    HIP_TRY(hipSetDevice(device));
-
-    auto *m = new bf_model();
-    m->device = device;
-    m->nv = nv; m->nj = nj; m->nb = nb; m->npf = npf;
-    m->n_selector = d->n_selector; m->n_extra = d->n_extra; m->n_joint_map = d->n_joint_map;
-    m->nl = d->n_loss_joints;
-    m->nl_loss = d->n_loss_joints;
-    m->kind = d->model_kind; m->n_lmk = n_lmk; m->n_all = n_all;
-    m->kp_dense = d->n_loss_joints > 32;
-    const int n_body = smplx ? 21 : nj - 1, n_pca = smplx ? d->n_hand_pca : 0;
-    m->np = smplx ? 3 + 1 + 63 + nb + 3 + 3 + 3 + 2 * n_pca : 3 + 1 + 3 * (nj - 1) + nb + 3;
-
-    // ---- kinematic tree: depth levels and children lists ----------------------------------
-    std::vector<int> parents(d->parents, d->parents + nj), depth(nj, 0);
-    int n_levels = 1;
-    for (int j = 1; j < nj; ++j) { depth[j] = depth[parents[j]] + 1; n_levels = std::max(n_levels, depth[j] + 1); }
-    std::vector<int> level_start(n_levels + 1, 0), level_joints;
-    for (int l = 0; l < n_levels; ++l) {
-        level_start[l] = (int)level_joints.size();
-        for (int j = 0; j < nj; ++j) if (depth[j] == l) level_joints.push_back(j);
-    }
-    level_start[n_levels] = (int)level_joints.size();
-    std::vector<int> child_start(nj + 1, 0), child_list;
-    for (int p = 0; p < nj; ++p) {
-        child_start[p] = (int)child_list.size();
-        for (int j = 1; j < nj; ++j) if (parents[j] == p) child_list.push_back(j);
-    }
-    child_start[nj] = (int)child_list.size();
-    m->n_levels = n_levels;
-
-    // ---- loss joints -> chain joint or selector-vertex slot (loss.py:163, models/smpl.py:75) ----
-    if (m->kp_dense) m->nl = 0;                   // the keypoint loss goes through the dense path (bf_kp_loss_kernel)
-    std::vector<int> lj_kind(m->nl), lj_index(m->nl), sel;
-    for (int k = 0; k < m->nl; ++k) {
-        int s = d->joint_map[k];
-        if (s < nj) { lj_kind[k] = 0; lj_index[k] = s; }
-        else if (s < nj + d->n_selector) {
-            int vid = d->selector_ids[s - nj];
-            auto it = std::find(sel.begin(), sel.end(), vid);
-            if (it == sel.end()) { sel.push_back(vid); it = sel.end() - 1; }
-            lj_kind[k] = 1; lj_index[k] = (int)(it - sel.begin());
-        } else {
-            delete m;
-            return fail(BF_ERR_UNSUPPORTED, "bf_model_create: a loss joint maps to an extra-regressor joint");
-        }
-    }
-    const int ns = (int)sel.size();
-    m->ns = ns;
-
-    // ---- pre-contracted joint regressor (float64 accumulate, rounded once) --------------------
-    std::vector<float> Jt(nj * 3), Jd((size_t)nj * 3 * nb), Jdrel((size_t)nj * 3 * nb), Jtrel(nj * 3);
-    {
-        std::vector<double> acc((size_t)3 + 3 * nb);
-        std::vector<double> Jd64((size_t)nj * 3 * nb), Jt64((size_t)nj * 3);
-        for (int j = 0; j < nj; ++j) {
-            std::fill(acc.begin(), acc.end(), 0.0);
-            const float *row = d->j_regressor + (size_t)j * nv;
-            for (int v = 0; v < nv; ++v) {
-                double w = row[v];
-                if (w == 0.0) continue;
-                for (int k = 0; k < 3; ++k) {
-                    acc[k] += w * d->v_template[(size_t)v * 3 + k];
-                    const float *sd = d->shapedirs + ((size_t)v * 3 + k) * nb;
-                    for (int l = 0; l < nb; ++l) acc[3 + k * nb + l] += w * sd[l];
-                }
-            }
-            for (int k = 0; k < 3; ++k) {
-                Jt[j * 3 + k] = (float)acc[k];
-                Jt64[j * 3 + k] = acc[k];
-                for (int l = 0; l < nb; ++l) {
-                    Jd64[((size_t)j * 3 + k) * nb + l] = acc[3 + k * nb + l];
-                    Jd[((size_t)j * 3 + k) * nb + l] = (float)acc[3 + k * nb + l];
-                }
-            }
-        }
-        for (int j = 0; j < nj; ++j)
-            for (int k = 0; k < 3; ++k) Jtrel[j * 3 + k] = (float)(Jt64[j * 3 + k] - (j > 0 ? Jt64[parents[j] * 3 + k] : 0.0));
-        for (int j = 0; j < nj; ++j)
-            for (int e = 0; e < 3 * nb; ++e) {
-                double v = Jd64[(size_t)j * 3 * nb + e];
-                if (j > 0) v -= Jd64[(size_t)parents[j] * 3 * nb + e];
-                Jdrel[(size_t)j * 3 * nb + e] = (float)v;
-            }
-    }
-    // ---- selector-vertex slices of the model ----------------------------------------------------
-    std::vector<float> sel_vt(ns * 3), sel_sd((size_t)ns * 3 * nb), sel_pd((size_t)npf * ns * 3), sel_w((size_t)ns * nj);
-    for (int s = 0; s < ns; ++s) {
-        int v = sel[s];
-        for (int k = 0; k < 3; ++k) {
-            sel_vt[s * 3 + k] = d->v_template[(size_t)v * 3 + k];
-            for (int l = 0; l < nb; ++l) sel_sd[((size_t)s * 3 + k) * nb + l] = d->shapedirs[((size_t)v * 3 + k) * nb + l];
-            for (int p = 0; p < npf; ++p) sel_pd[(size_t)p * ns * 3 + s * 3 + k] = d->posedirs[(size_t)p * 3 * nv + 3 * v + k];
-        }
-        for (int j = 0; j < nj; ++j) sel_w[(size_t)s * nj + j] = d->lbs_weights[(size_t)v * nj + j];
-    }
-    std::vector<float> nzw((size_t)ns * BF_SEL_NNZ, 0.f);
-    std::vector<int> nzj((size_t)ns * BF_SEL_NNZ, 0);
-    int sel_nnz = 0;
-    for (int s = 0; s < ns; ++s) {
-        int c = 0;
-        for (int j = 0; j < nj; ++j) {
-            float w = sel_w[(size_t)s * nj + j];
-            if (w == 0.f) continue;
-            if (c < BF_SEL_NNZ) { nzw[(size_t)s * BF_SEL_NNZ + c] = w; nzj[(size_t)s * BF_SEL_NNZ + c] = j; }
-            ++c;
-        }
-        sel_nnz = std::max(sel_nnz, c);
-    }
-    if (sel_nnz > BF_SEL_NNZ) sel_nnz = 0;
-    // ---- GMM: symmetrised precisions and -log of the merged weights (prior.py:188-189) ---------
-    const int M = BF_GMM_M, D = BF_GMM_D;
-    std::vector<float> psym((size_t)M * D * D), logw(M), means(d->gmm_means, d->gmm_means + (size_t)M * D);
-    for (int c = 0; c < M; ++c) {
-        for (int i = 0; i < D; ++i)
-            for (int j = 0; j < D; ++j)
-                psym[((size_t)c * D + i) * D + j] = (float)(0.5 * ((double)d->gmm_precisions[((size_t)c * D + i) * D + j] +
-                                                                   (double)d->gmm_precisions[((size_t)c * D + j) * D + i]));
-        logw[c] = (float)(-std::log((double)d->gmm_nll_weights[c]));
-    }
-
-    // lane-major register images of Psym for the fit kernel (coalesced one-off load)
-    std::vector<float> plane((size_t)M * BF_GMM_LD * 64, 0.f), ptail((size_t)4 * 12 * 64, 0.f);
-    for (int c = 0; c < M; ++c)
-        for (int j = 0; j < D; ++j)
-            for (int l = 0; l < 64; ++l) plane[((size_t)c * BF_GMM_LD + j) * 64 + l] = psym[((size_t)c * D + l) * D + j];
-    for (int w = 0; w < 4; ++w)
-        for (int l = 0; l < 60; ++l) {
-            int comp = l < 30 ? 2 * w : 2 * w + 1, row = 64 + (l % 30) / 6, col = 12 * (l % 6);
-            for (int e = 0; e < 12; ++e)
-                if (col + e < D) ptail[((size_t)w * 12 + e) * 64 + l] = psym[((size_t)comp * D + row) * D + col + e];
-        }
-    int max_children = 0;
-    for (int p = 0; p < nj; ++p) max_children = std::max(max_children, child_start[p + 1] - child_start[p]);
-    if (max_children > 6) { delete m; return fail(BF_ERR_UNSUPPORTED, "bf_model_create: a joint has more than 6 children"); }
-
-    bool okay = true;
-    auto up_f = [&](DevBuf<float> &b, const float *src, size_t n) {
-        std::vector<float> h(src, src + n);
-        okay = okay && b.upload(h) == hipSuccess;
-    };
-    auto up_vf = [&](DevBuf<float> &b, const std::vector<float> &h) { okay = okay && b.upload(h) == hipSuccess; };
-    auto up_vi = [&](DevBuf<int> &b, const std::vector<int> &h) { okay = okay && b.upload(h) == hipSuccess; };
-    up_f(m->v_template, d->v_template, (size_t)nv * 3);
-    up_f(m->shapedirs, d->shapedirs, (size_t)nv * 3 * nb);
-    // posedirs rows are padded to a multiple of 128 bytes: a tile's 96 columns are 384 bytes, and with the natural pitch (SMPL: 82,680 B)
-    // every slice straddled a fourth line that the neighbouring tile's workgroup - usually on another XCD - fetched again (counter
-    // traffic 1.30 x the algorithmic bytes in rounds 2-4)
-    auto pd_pitch_of = [](int cols) { return (cols + 31) & ~31; };
-    auto up_rows = [&](DevBuf<float> &b, const float *src, int rows, int cols, int pitch) {
-        std::vector<float> h((size_t)rows * pitch, 0.f);
-        for (int r = 0; r < rows; ++r) memcpy(h.data() + (size_t)r * pitch, src + (size_t)r * cols, (size_t)cols * sizeof(float));
-        okay = okay && b.upload(h) == hipSuccess;
-    };
-    up_rows(m->posedirs, d->posedirs, npf, 3 * nv, pd_pitch_of(3 * nv));
-    if (d->n_faces > 0 && d->faces) {
-        for (int i = 0; i < d->n_faces * 3; ++i)
-            if (d->faces[i] < 0 || d->faces[i] >= nv) { delete m; return fail(BF_ERR_INVALID, "bf_model_create: face index out of range"); }
-        m->faces_host.assign(d->faces, d->faces + (size_t)d->n_faces * 3);
-    }
-    up_f(m->lbs_weights, d->lbs_weights, (size_t)nv * nj);
-    int v_nnz = 0;
-    {   // sparse skinning rows: exact (the dropped entries are zeros)
-        int mx = 0;
-        for (int v = 0; v < nv; ++v) { int c = 0; for (int j = 0; j < nj; ++j) c += d->lbs_weights[(size_t)v * nj + j] != 0.f; mx = std::max(mx, c); }
-        v_nnz = mx <= 4 ? 4 : (mx <= 8 ? 8 : 0);
-        std::vector<int> zj((size_t)nv * std::max(v_nnz, 1), 0);
-        std::vector<float> zw((size_t)nv * std::max(v_nnz, 1), 0.f);
-        for (int v = 0; v < nv && v_nnz; ++v) {
-            int c = 0;
-            for (int j = 0; j < nj; ++j) {
-                float w = d->lbs_weights[(size_t)v * nj + j];
-                if (w != 0.f) { zj[(size_t)v * v_nnz + c] = j; zw[(size_t)v * v_nnz + c] = w; ++c; }
-            }
-        }
-        up_vi(m->v_nzj, zj); up_vf(m->v_nzw, zw);
-    }
-    up_f(m->j_extra, d->j_regressor_extra, (size_t)d->n_extra * nv);
-    up_vi(m->selector_ids, std::vector<int>(d->selector_ids, d->selector_ids + d->n_selector));
-    up_vi(m->joint_map, std::vector<int>(d->joint_map, d->joint_map + d->n_joint_map));
-    {
-        std::vector<unsigned long long> desc(nj, 0ull);
-        for (int j = nj - 1; j >= 1; --j) desc[parents[j]] |= desc[j] | (1ull << j);
-        okay = okay && m->desc_d.upload(desc) == hipSuccess;
-        // depth-first order (children in index order): a subtree is a contiguous run of positions, so subtree sums are
-        // differences of a prefix sum
-        std::vector<int> order, last(nj, 0), pos(nj, 0);
-        std::vector<int> stack{0};
-        while (!stack.empty()) {
-            int j = stack.back(); stack.pop_back();
-            pos[j] = (int)order.size(); order.push_back(j);
-            for (int c = nj - 1; c >= 1; --c) if (parents[c] == j) stack.push_back(c);
-        }
-        for (int i = 0; i < nj; ++i) {
-            int j = order[i], cnt = 1;
-            for (int k = 0; k < nj; ++k) if ((desc[j] >> k) & 1ull) ++cnt;
-            last[i] = i + cnt - 1;
-        }
-        okay = okay && m->dfs_order.upload(order) == hipSuccess && m->dfs_last.upload(last) == hipSuccess;
-    }
-    up_vi(m->depth_d, depth); up_vf(m->sel_nzw, nzw); up_vi(m->sel_nzj, nzj); up_vf(m->g_plane, plane); up_vf(m->g_ptail, ptail);
-    up_vi(m->parents, parents); up_vi(m->level_start, level_start); up_vi(m->level_joints, level_joints);
-    up_vi(m->child_start, child_start); up_vi(m->child_list, child_list);
-    up_vi(m->lj_kind, lj_kind); up_vi(m->lj_index, lj_index);
-    up_vf(m->Jt, Jt); up_vf(m->Jd, Jd); up_vf(m->Jdrel, Jdrel); up_vf(m->Jtrel, Jtrel);
-    up_vf(m->sel_vt, sel_vt); up_vf(m->sel_sd, sel_sd); up_vf(m->sel_pd, sel_pd); up_vf(m->sel_w, sel_w);
-    up_vf(m->g_means, means); up_vf(m->g_psym, psym); up_vf(m->g_logw, logw);
-    if (!okay) { delete m; return fail(BF_ERR_HIP, "bf_model_create: device allocation / upload failed"); }
-
-    FitTab &T = m->fit;
-    T.nj = nj; T.nb = nb; T.npf = npf; T.ns = ns; T.nl = m->nl; T.np = m->np; T.n_levels = n_levels;
-    T.nbp = 3 * n_body;
-    T.off_pose = 4; T.off_beta = 4 + 3 * n_body; T.off_orient = T.off_beta + nb;
-    T.n_pca = n_pca; T.off_lh = T.off_orient + 9; T.off_rh = T.off_lh + n_pca;
-    T.kp_dense = m->kp_dense;
-    {
-        const int off_leye = T.off_orient + 3, off_reye = T.off_orient + 6;
-        std::vector<int> thk(nj, 0), tho(nj, 0), pk(m->np, 0), pa(m->np, 0), pb(m->np, -1);
-        for (int j = 0; j < nj; ++j) {
-            if (j == 0) { thk[j] = 0; tho[j] = T.off_orient; }
-            else if (j <= n_body) { thk[j] = 0; tho[j] = T.off_pose + 3 * (j - 1); }
-            else if (j == 22) { thk[j] = 1; }
-            else if (j == 23) { thk[j] = 0; tho[j] = off_leye; }
-            else if (j == 24) { thk[j] = 0; tho[j] = off_reye; }
-            else if (j < 40) { thk[j] = 2; tho[j] = j - 25; }
-            else { thk[j] = 3; tho[j] = j - 40; }
-        }
-        for (int i = 0; i < m->np; ++i) {
-            if (i < 4) pk[i] = 0;
-            else if (i < T.off_beta) { int ip = i - T.off_pose; pk[i] = 1; pa[i] = 3 + ip; pb[i] = ip; }
-            else if (i < T.off_orient) pk[i] = 2;
-            else if (i < T.off_orient + 3) { pk[i] = 1; pa[i] = i - T.off_orient; }
-            else if (i < off_reye) { pk[i] = 1; pa[i] = 23 * 3 + (i - off_leye); }
-            else if (i < T.off_lh) { pk[i] = 1; pa[i] = 24 * 3 + (i - off_reye); }
-            else if (i < T.off_rh) { pk[i] = 3; pa[i] = 0; pb[i] = i - T.off_lh; }
-            else { pk[i] = 3; pa[i] = 1; pb[i] = i - T.off_rh; }
-        }
-        bool up = m->th_kind.upload(thk) == hipSuccess && m->th_off.upload(tho) == hipSuccess && m->p_kind.upload(pk) == hipSuccess &&
-                  m->p_a.upload(pa) == hipSuccess && m->p_b.upload(pb) == hipSuccess;
-        if (smplx) {
-            std::vector<float> hc((size_t)2 * n_pca * 45);
-            std::memcpy(hc.data(), d->left_hand_components, sizeof(float) * n_pca * 45);
-            std::memcpy(hc.data() + (size_t)n_pca * 45, d->right_hand_components, sizeof(float) * n_pca * 45);
-            up = up && m->hand_comp.upload(hc) == hipSuccess &&
-                 m->pose_mean.upload(std::vector<float>(d->pose_mean, d->pose_mean + (size_t)nj * 3)) == hipSuccess;
-        }
-        if (!up) { delete m; return fail(BF_ERR_HIP, "bf_model_create: device allocation failed (pose tables)"); }
-        T.th_kind = m->th_kind.p; T.th_off = m->th_off.p; T.p_kind = m->p_kind.p; T.p_a = m->p_a.p; T.p_b = m->p_b.p;
-        T.pose_mean = smplx ? m->pose_mean.p : nullptr; T.hand_comp = smplx ? m->hand_comp.p : nullptr;
-    }
-    T.sel_nnz = sel_nnz; T.sel_nzw = m->sel_nzw.p; T.sel_nzj = m->sel_nzj.p;
-    T.depth = m->depth_d.p; T.desc = m->desc_d.p; T.dfs_order = m->dfs_order.p; T.dfs_last = m->dfs_last.p; T.g_plane = m->g_plane.p; T.g_ptail = m->g_ptail.p;
-    T.parents = m->parents.p; T.level_start = m->level_start.p; T.level_joints = m->level_joints.p;
-    T.child_start = m->child_start.p; T.child_list = m->child_list.p;
-    T.lj_kind = m->lj_kind.p; T.lj_index = m->lj_index.p;
-    {   // deal pairs and selector vertices to the four geometry waves (FitTab::pair_slot): pairs with the most selector vertices
-        // first, each to the wave that already owns its vertices, else to the wave with the fewest vertices, then the fewest pairs
-        const int npairs = (m->nl + 1) / 2;
-        for (int &x : T.pair_slot) x = -1;
-        for (int &x : T.skin_vert) x = -1;
-        T.bd_ok = (npairs >= 1 && npairs <= 16 && ns <= 4 * BF_SKIN_PER_WAVE) ? 1 : 0;
-        std::vector<int> owner(ns, -1), order(std::max(npairs, 0)), nverts(4, 0), npw(4, 0);
-        auto verts_of = [&](int p) {
-            std::vector<int> v;
-            for (int l = 2 * p; l < std::min(2 * p + 2, m->nl); ++l)
-                if (lj_kind[l] == 1 && std::find(v.begin(), v.end(), lj_index[l]) == v.end()) v.push_back(lj_index[l]);
-            return v;
-        };
-        for (int p = 0; p < npairs; ++p) order[p] = p;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return verts_of(a).size() > verts_of(b).size(); });
-        for (int p : order) {
-            if (!T.bd_ok) break;
-            const std::vector<int> v = verts_of(p);
-            int w = -1;
-            for (int x : v) if (owner[x] >= 0) { if (w >= 0 && w != owner[x]) T.bd_ok = 0; w = owner[x]; }
-            int fresh = 0;
-            for (int x : v) if (owner[x] < 0) ++fresh;
-            if (w < 0) {
-                for (int c = 0; c < 4; ++c) {
-                    if (npw[c] >= 4 || nverts[c] + fresh > BF_SKIN_PER_WAVE) continue;
-                    if (w < 0 || nverts[c] < nverts[w] || (nverts[c] == nverts[w] && npw[c] < npw[w])) w = c;
-                }
-            }
-            if (w < 0 || npw[w] >= 4 || nverts[w] + fresh > BF_SKIN_PER_WAVE) { T.bd_ok = 0; break; }
-            T.pair_slot[4 * w + npw[w]++] = p;
-            for (int x : v) if (owner[x] < 0) { owner[x] = w; T.skin_vert[BF_SKIN_PER_WAVE * w + nverts[w]++] = x; }
-        }
-        for (int x = 0; x < ns && T.bd_ok; ++x) if (owner[x] < 0) T.bd_ok = 0;       // (a selector vertex no pair reads: cannot happen, sel is built from the loss joints)
-    }
-    T.Jt = m->Jt.p; T.Jd = m->Jd.p; T.Jdrel = m->Jdrel.p; T.Jtrel = m->Jtrel.p;
-    T.sel_vt = m->sel_vt.p; T.sel_sd = m->sel_sd.p; T.sel_pd = m->sel_pd.p; T.sel_w = m->sel_w.p;
-    T.g_means = m->g_means.p; T.g_psym = m->g_psym.p; T.g_logw = m->g_logw.p;
-    MeshTab &Q = m->mesh;
-    Q.nv = nv; Q.nj = nj; Q.nb = nb; Q.npf = npf;
-    Q.n_selector = d->n_selector; Q.n_extra = d->n_extra; Q.n_joint_map = d->n_joint_map;
-    Q.v_template = m->v_template.p; Q.shapedirs = m->shapedirs.p; Q.posedirs = m->posedirs.p; Q.pd_pitch = pd_pitch_of(3 * nv);
-    Q.lbs_weights = m->lbs_weights.p; Q.j_extra = m->j_extra.p;
-    Q.selector_ids = m->selector_ids.p; Q.joint_map = m->joint_map.p;
-    Q.n_tiles = (nv + BF_MESH_TILE - 1) / BF_MESH_TILE;
-    Q.v_nnz = v_nnz; Q.v_nzj = m->v_nzj.p; Q.v_nzw = m->v_nzw.p;
-    Q.n_lmk_static = smplx ? d->n_lmk_static : 0; Q.n_lmk_dyn = smplx ? d->n_lmk_dynamic : 0;
-    Q.n_dyn_rows = smplx ? d->n_dyn_rows : 0; Q.neck_joint = smplx ? d->neck_joint : 0;
-    if (smplx) {
-        bool up = m->faces_lm.upload(std::vector<int>(d->faces, d->faces + (size_t)d->n_faces * 3)) == hipSuccess &&
-                  m->lmk_faces.upload(std::vector<int>(d->lmk_faces_idx, d->lmk_faces_idx + d->n_lmk_static)) == hipSuccess &&
-                  m->lmk_bary.upload(std::vector<float>(d->lmk_bary_coords, d->lmk_bary_coords + (size_t)d->n_lmk_static * 3)) == hipSuccess &&
-                  m->dyn_faces.upload(std::vector<int>(d->dynamic_lmk_faces_idx, d->dynamic_lmk_faces_idx + (size_t)d->n_dyn_rows * d->n_lmk_dynamic)) == hipSuccess &&
-                  m->dyn_bary.upload(std::vector<float>(d->dynamic_lmk_bary_coords, d->dynamic_lmk_bary_coords + (size_t)d->n_dyn_rows * d->n_lmk_dynamic * 3)) == hipSuccess;
-        if (!up) { delete m; return fail(BF_ERR_HIP, "bf_model_create: device allocation failed (landmarks)"); }
-        for (int i = 0; i < d->n_lmk_static; ++i)
-            if (d->lmk_faces_idx[i] < 0 || d->lmk_faces_idx[i] >= d->n_faces) { delete m; return fail(BF_ERR_INVALID, "bf_model_create: landmark face out of range"); }
-        for (size_t i = 0; i < (size_t)d->n_dyn_rows * d->n_lmk_dynamic; ++i)
-            if (d->dynamic_lmk_faces_idx[i] < 0 || d->dynamic_lmk_faces_idx[i] >= d->n_faces) { delete m; return fail(BF_ERR_INVALID, "bf_model_create: dynamic landmark face out of range"); }
-        Q.faces = m->faces_lm.p; Q.lmk_faces = m->lmk_faces.p; Q.lmk_bary = m->lmk_bary.p; Q.dyn_faces = m->dyn_faces.p; Q.dyn_bary = m->dyn_bary.p;
-        // the landmarks' corner vertices, looked up once (MeshTab::lmk_fv / dyn_fv)
-        std::vector<int> sfv((size_t)d->n_lmk_static * 3), dfv((size_t)d->n_dyn_rows * d->n_lmk_dynamic * 3);
-        for (int i = 0; i < d->n_lmk_static; ++i)
-            for (int c = 0; c < 3; ++c) sfv[(size_t)i * 3 + c] = d->faces[(size_t)d->lmk_faces_idx[i] * 3 + c];
-        for (size_t i = 0; i < (size_t)d->n_dyn_rows * d->n_lmk_dynamic; ++i)
-            for (int c = 0; c < 3; ++c) dfv[i * 3 + c] = d->faces[(size_t)d->dynamic_lmk_faces_idx[i] * 3 + c];
-        if (dfv.empty()) dfv.push_back(0);
-        if (m->lmk_fv.upload(sfv) != hipSuccess || m->dyn_fv.upload(dfv) != hipSuccess) { delete m; return fail(BF_ERR_HIP, "bf_model_create: device allocation failed (landmark corners)"); }
-        Q.lmk_fv = m->lmk_fv.p; Q.dyn_fv = m->dyn_fv.p;
-    }
-    if (m->kp_dense) {
-        // dense keypoint loss tables: loss joints -> all-joints index; per chain joint the loss joints that use it
-        std::vector<int> jm(d->joint_map, d->joint_map + m->nl_loss), cs(nj + 1, 0), cl;
-        for (int j = 0; j < nj; ++j) {
-            cs[j] = (int)cl.size();
-            for (int q = 0; q < m->nl_loss; ++q) if (jm[q] == j) cl.push_back(q);
-        }
-        cs[nj] = (int)cl.size();
-        if (cl.empty()) cl.push_back(0);
-        bool up = m->kp_jm.upload(jm) == hipSuccess && m->cj_start.upload(cs) == hipSuccess && m->cj_list.upload(cl) == hipSuccess;
-        if (!up) { delete m; return fail(BF_ERR_HIP, "bf_model_create: device allocation failed (keypoint tables)"); }
-        KpIO &K = m->kp;
-        K.nl = m->nl_loss; K.nj = nj; K.npf = npf; K.nb = nb; K.nv = nv; K.n_all = n_all; K.n_selector = d->n_selector;
-        K.n_extra = d->n_extra; K.n_lmk = n_lmk;
-        K.joint_map = m->kp_jm.p; K.selector_ids = m->selector_ids.p; K.cj_start = m->cj_start.p; K.cj_list = m->cj_list.p;
-        K.n_cj_list = (int)cl.size();
-        K.j_extra = m->j_extra.p;
-    }
-    m->mesh_smem = bf_mesh_smem_bytes(nj, npf, nb);
-    {
-        // ---- sub-models (bf_model::Sub): the model's tables gathered for a subset of its vertices --------------------------
-        //   sub     "sampled first": every 4th vertex (the silhouette loss, loss.py:99) first, then what the dense keypoint loss reads;
-        //   sub_kp  (round 5) only what the dense keypoint loss reads - selector vertices, the landmark faces' corners, the support of
-        //           the extra regressor: the iterations BEFORE the silhouette / scan losses switch on (i <= num_iters // 3,
-        //           smplify.py:197,205) touch nothing else, with or without a scan attached.
-        std::vector<char> extra(nv, 0);
-        for (int i = 0; i < d->n_selector; ++i) extra[d->selector_ids[i]] = 1;
-        if (smplx) {
-            auto face = [&](int fidx) { if (fidx >= 0 && fidx < d->n_faces) for (int c = 0; c < 3; ++c) extra[d->faces[(size_t)fidx * 3 + c]] = 1; };
-            for (int i = 0; i < d->n_lmk_static; ++i) face(d->lmk_faces_idx[i]);
-            for (size_t i = 0; i < (size_t)d->n_dyn_rows * d->n_lmk_dynamic; ++i) face(d->dynamic_lmk_faces_idx[i]);
-        }
-        // (the extra-joint regressor rows are gathered for the sub-model's vertices: every vertex that carries regressor weight
-        //  must be one of them, or the extra joints of the dense loop would be partial sums)
-        for (int e = 0; e < d->n_extra; ++e)
-            for (int v = 0; v < nv; ++v) if (d->j_regressor_extra[(size_t)e * nv + v] != 0.f) extra[v] = 1;
-        auto build_sub = [&](bf_model::Sub &U, bool sampled_first, int max_tenths) -> int {
-            std::vector<int> pos(nv, -1), S;
-            if (sampled_first) for (int v = 0; v < nv; v += 4) { pos[v] = (int)S.size(); S.push_back(v); }
-            const int n_samp = (int)S.size();
-            for (int v = 0; v < nv; ++v) if (extra[v] && pos[v] < 0) { pos[v] = (int)S.size(); S.push_back(v); }
-            const int sv = (int)S.size();
-            if (sv == 0 || sv * 10 > nv * max_tenths) return BF_OK;          // (not worth it: the full model serves)
-            std::vector<float> vt((size_t)sv * 3), sd((size_t)sv * 3 * nb), pd((size_t)npf * pd_pitch_of(3 * sv), 0.f), lw((size_t)sv * nj), jx((size_t)std::max(d->n_extra, 0) * sv);
-            const int nnz = m->mesh.v_nnz;
-            std::vector<int> zj((size_t)sv * std::max(nnz, 1), 0), sel(d->n_selector), fc;
-            std::vector<float> zw((size_t)sv * std::max(nnz, 1), 0.f);
-            for (int i = 0; i < sv; ++i) {
-                const int v = S[i];
-                for (int k = 0; k < 3; ++k) {
-                    vt[(size_t)i * 3 + k] = d->v_template[(size_t)v * 3 + k];
-                    for (int l = 0; l < nb; ++l) sd[((size_t)i * 3 + k) * nb + l] = d->shapedirs[((size_t)v * 3 + k) * nb + l];
-                    for (int p = 0; p < npf; ++p) pd[(size_t)p * pd_pitch_of(3 * sv) + (size_t)i * 3 + k] = d->posedirs[(size_t)p * 3 * nv + (size_t)v * 3 + k];
-                }
-                int c = 0;
-                for (int j = 0; j < nj; ++j) {
-                    const float w = d->lbs_weights[(size_t)v * nj + j];
-                    lw[(size_t)i * nj + j] = w;
-                    if (nnz && w != 0.f) { zj[(size_t)i * nnz + c] = j; zw[(size_t)i * nnz + c] = w; ++c; }
-                }
-                for (int e = 0; e < d->n_extra; ++e) jx[(size_t)e * sv + i] = d->j_regressor_extra[(size_t)e * nv + v];
-            }
-            for (int i = 0; i < d->n_selector; ++i) sel[i] = pos[d->selector_ids[i]];
-            if (smplx) {            // faces re-indexed; a corner outside the sub-model belongs to a face no landmark uses
-                fc.resize((size_t)d->n_faces * 3);
-                for (size_t i = 0; i < fc.size(); ++i) fc[i] = std::max(pos[d->faces[i]], 0);
-            }
-            bool up = U.v_template.upload(vt) == hipSuccess && U.shapedirs.upload(sd) == hipSuccess && U.posedirs.upload(pd) == hipSuccess &&
-                      U.lbs_weights.upload(lw) == hipSuccess && U.j_extra.upload(jx) == hipSuccess && U.v_nzj.upload(zj) == hipSuccess &&
-                      U.v_nzw.upload(zw) == hipSuccess && U.selector_ids.upload(sel) == hipSuccess && U.faces.upload(fc) == hipSuccess;
-            if (!up) return fail(BF_ERR_HIP, "bf_model_create: device allocation failed (sub-model)");
-            U.mesh = m->mesh;
-            U.mesh.nv = sv; U.mesh.n_tiles = (sv + BF_MESH_TILE - 1) / BF_MESH_TILE;
-            U.mesh.v_template = U.v_template.p; U.mesh.shapedirs = U.shapedirs.p; U.mesh.posedirs = U.posedirs.p; U.mesh.pd_pitch = pd_pitch_of(3 * sv);
-            U.mesh.lbs_weights = U.lbs_weights.p; U.mesh.j_extra = U.j_extra.p; U.mesh.selector_ids = U.selector_ids.p;
-            U.mesh.v_nzj = U.v_nzj.p; U.mesh.v_nzw = U.v_nzw.p;
-            if (smplx) {
-                U.mesh.faces = U.faces.p;
-                std::vector<int> sfv((size_t)d->n_lmk_static * 3), dfv((size_t)d->n_dyn_rows * d->n_lmk_dynamic * 3);
-                for (int i = 0; i < d->n_lmk_static; ++i)
-                    for (int c = 0; c < 3; ++c) sfv[(size_t)i * 3 + c] = fc[(size_t)d->lmk_faces_idx[i] * 3 + c];
-                for (size_t i = 0; i < (size_t)d->n_dyn_rows * d->n_lmk_dynamic; ++i)
-                    for (int c = 0; c < 3; ++c) dfv[i * 3 + c] = fc[(size_t)d->dynamic_lmk_faces_idx[i] * 3 + c];
-                if (dfv.empty()) dfv.push_back(0);
-                if (U.lmk_fv.upload(sfv) != hipSuccess || U.dyn_fv.upload(dfv) != hipSuccess) return fail(BF_ERR_HIP, "bf_model_create: device allocation failed (sub-model landmark corners)");
-                U.mesh.lmk_fv = U.lmk_fv.p; U.mesh.dyn_fv = U.dyn_fv.p;
-            }
-            U.kp = m->kp; U.kp.nv = sv; U.kp.selector_ids = U.selector_ids.p; U.kp.j_extra = U.j_extra.p;
-            U.ns = n_samp;
-            U.on = true;
-            return BF_OK;
-        };
-        int rs = build_sub(m->sub, true, 6);
-        if (rs == BF_OK && m->kp_dense) rs = build_sub(m->sub_kp, false, 5);      // (only models whose keypoint loss is dense have keypoint-only dense iterations)
-        if (rs != BF_OK) { delete m; return rs; }
-    }
-    *out = m;
-    return BF_OK;
-}
-
-void bf_model_destroy(bf_model *m) { delete m; }
-int bf_model_n_params(const bf_model *m) { return m ? m->np : 0; }
-int bf_model_fit_instance(const bf_model *m) { return (m && bf_fit_is_sized_smpl(&m->fit)) ? 1 : 0; }
 
 int bf_launch_mesh(bf_model *m, MeshScratch *scr, int n, const float *state_dev, float *vraw, float *vout, float *xpart, float *joints,
                    float *joints_ori, hipStream_t stream, hipEvent_t after_mesh, float *vposed, float *jraw, int *lmk_vid,
