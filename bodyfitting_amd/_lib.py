@@ -49,6 +49,7 @@ FIT_DEFAULT, FIT_DENSE, FIT_NO_VERTICES, FIT_FETCH, FIT_RESET, FIT_GRAPH, FIT_NO
 # every entry point include/bodyfit.h declares: name -> (restype, argtypes)
 _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int32)
+_DP = C.POINTER(C.c_double)
 _VP = C.c_void_p
 SIGNATURES = {
     "bf_last_error": (C.c_char_p, []),
@@ -154,6 +155,16 @@ SIGNATURES = {
     "bf_hmr_features": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), _FP]),
     "bf_hmr_preprocess": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _FP]),
     "bf_hmr_selftest_conv": (C.c_int, [C.c_int] * 9 + [_FP, _FP, _FP, _FP, C.c_int, _FP]),
+    "bf_openpose_n_weights": (C.c_int64, []),
+    "bf_openpose_create": (C.c_int, [C.c_int, _FP, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "bf_openpose_destroy": (None, [_VP]),
+    "bf_openpose_maps": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), _DP, _DP]),
+    "bf_openpose_network": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), _FP, _FP]),
+    "bf_openpose_inject": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _FP, C.c_int64, _DP, _DP]),
+    "bf_openpose_map_size": (C.c_int, [_VP, _IP]),
+    "bf_openpose_peaks": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _IP, _IP, _DP]),
+    "bf_openpose_pairs": (C.c_int, [_VP, C.c_int, C.c_int, _IP, _DP, _IP]),
+    "bf_openpose_selftest_conv": (C.c_int, [C.c_int] * 8 + [_FP, _FP, _FP, _FP]),
     "bf_batch_debug_dump": (C.c_int, [_VP, _FP, C.c_int]),
     "bf_batch_debug_disp_moment": (C.c_int, [_VP, _FP]),
 }

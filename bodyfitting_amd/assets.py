@@ -17,6 +17,9 @@ config.SMIL_MODEL_DIR).  Kid models are cached under (type, gender, 'kid'); the 
 
 The HMR weights of the initial estimate (`hmr.HMR`) are the state dict registered with `register_hmr(...)`, else the reference's
 `data/model_checkpoint.pt` + `data/smpl_mean_params.npz` (config.HMR_CHECKPOINT, config.SMPL_MEAN_PARAMS), folded and packed once.
+
+The OpenPose body weights (`openpose.OpenPose`) are the state dict registered with `register_openpose(...)`, else the reference's
+`models/body_pose_model.pth` (openpose/infer_openpose.py:53), packed once.
 """
 from __future__ import annotations
 
@@ -34,6 +37,8 @@ _KID_TEMPLATE = {}
 _HMR = {}
 HMR_CHECKPOINT = "model_checkpoint.pt"          # config.HMR_CHECKPOINT / SMPL_MEAN_PARAMS, in the data folder of the model files
 SMPL_MEAN_PARAMS = "smpl_mean_params.npz"
+_OPENPOSE = {}
+OPENPOSE_WEIGHTS = os.path.join("models", "body_pose_model.pth")      # infer_openpose.py:53, relative to the working directory
 
 
 def _drop_kid(model_type=None, gender=None):
@@ -183,3 +188,25 @@ def get_hmr(folder="data"):
     state = hmr.load_checkpoint(ckpt)["model"]
     _HMR["packed"] = hmr.fold_and_pack(hmr.match_state(state, ckpt, mean))
     return _HMR["packed"]
+
+
+def register_openpose(state_dict):
+    """OpenPose body weights held in memory (tests, callers that load them themselves): a state dict with the caffe keys of
+    body_pose_model.pth (`conv1_1.weight`, ..., `Mconv7_stage6_L2.bias`).  None forgets them.  A missing key raises ValueError."""
+    _OPENPOSE.clear()
+    if state_dict is not None:
+        from . import openpose
+        _OPENPOSE["packed"] = openpose.pack(openpose.match_state(state_dict))
+
+
+def get_openpose(path=None):
+    """-> the packed float32 weights for openpose.OpenPose, read once per process"""
+    if "packed" in _OPENPOSE:
+        return _OPENPOSE["packed"]
+    from . import openpose
+    path = path or OPENPOSE_WEIGHTS
+    if not os.path.exists(path):
+        raise ValueError(f"no body keypoint estimator: OpenPose needs {path} (the reference's body_pose_model.pth) or weights "
+                         f"registered with assets.register_openpose(); alternatively pass keypoints=")
+    _OPENPOSE["packed"] = openpose.pack(openpose.load_weights(path))
+    return _OPENPOSE["packed"]

@@ -6,6 +6,10 @@ disp=...)` and the files it writes (`{smpl_type}_parameter.npy` = pickled result
 The initial (betas, pose) come from the `net_output=` keyword, else from `options.init_estimator(image, c2w)`, else - as in
 the reference (body_fitting.py:57-75,86) - from HMR on `images[keyframe]` / `c2ws[keyframe]` (`hmr.HMR`, on the GPU; weights from
 `assets.get_hmr()`, one network per BodyFitting).
+Without `keypoints` (None) the 2-D keypoints come from the reference's OpenPose body estimator on the GPU (`openpose.OpenPose`,
+weights from `assets.get_openpose()`), in place of apps/genebody_fitting.py's openpose.bin run: each view's image (RGB, as the
+runner loads it) is flipped to BGR - what openpose.bin reads from the written PNG - detected, laid out as BODY_25 as
+openpose/infer_openpose.py lays it out, and the person io.load_openpose would pick is kept.
 """
 from __future__ import annotations
 
@@ -29,6 +33,7 @@ class BodyFitting:
         self.num_iters = getattr(options, "num_iters", 600)            # smplify.py:26 default
         self._fitters = {}
         self._hmr = None
+        self._openpose = None
 
     def _fitter(self, gender):
         if gender not in self._fitters:      # the reference rebuilds this per call (body_fitting.py:82)
@@ -44,7 +49,18 @@ class BodyFitting:
             self._hmr = HMR(device=getattr(self.options, "device", 0), max_batch=1)
         return self._hmr.predict([image], None if c2w is None else np.asarray(c2w)[None])
 
-    def __call__(self, images, c2ws, Ks, keypoints, gender="male", keyframe=25, use_frames=list(range(48)),
+    def detect_keypoints(self, images):
+        """per view {'pose': [25, 3]} of the person io.load_openpose would choose from infer_openpose.py's JSON, or None"""
+        from . import openpose as O
+        if images is None:
+            raise ValueError("BodyFitting: keypoints=None detects them on the images, and images is None")
+        bgr = [np.ascontiguousarray(np.asarray(im)[:, :, ::-1]) for im in images]
+        if self._openpose is None:            # (no weights registered and no file: ValueError naming models/body_pose_model.pth)
+            H, W = bgr[0].shape[:2]
+            self._openpose = O.OpenPose(device=getattr(self.options, "device", 0), max_batch=4, max_h=max(H, 1024), max_w=max(W, 1024))
+        return [O.select_person(p) for p in self._openpose.pose25(bgr)]
+
+    def __call__(self, images, c2ws, Ks, keypoints=None, gender="male", keyframe=25, use_frames=list(range(48)),
                  use_mask=False, masks=None, mask_frames=None, render_skip=12, output_folder=None,
                  use_mesh=False, meshfile=None, disp=False, net_output=None):
         if net_output is None:
@@ -52,6 +68,8 @@ class BodyFitting:
                 net_output = self.init_estimator(images[keyframe], c2ws[keyframe])
             else:
                 net_output = self.run_hmr(images[keyframe], c2ws[keyframe])
+        if keypoints is None:
+            keypoints = self.detect_keypoints(images)
         imsize = images[0].shape[0] if images is not None else self.loadsize
         result = self._fitter(gender)(net_output, c2ws, Ks, keypoints, output_folder, use_mask=use_mask, masks=masks,
                                       use_frames=use_frames, mask_frames=mask_frames, keyframe=keyframe, imsize=imsize,

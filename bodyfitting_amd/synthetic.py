@@ -770,3 +770,19 @@ def make_hmr_images(seed=0, sizes=((512, 512), (480, 640), (224, 224))):
         img += rng.normal(0, 6, img.shape)
         out.append(np.clip(np.rint(img), 0, 255).astype(np.uint8))
     return out
+
+
+def make_openpose_weights(seed=0):
+    """A synthetic body_pose_model.pth state dict (numpy RNG; caffe keys, torch layout [cout][cin][k][k]): He-normal convolutions
+    (std sqrt(2 / (k * k * cin))) so activations stay O(1) through the ReLU stack, biases around 0.05, and each stage's output
+    layers scaled down so the maps stay in the range the real network produces (heatmaps about 0 .. 1)."""
+    from . import openpose
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for name, (cout, cin, k) in openpose.conv_shapes().items():
+        std = np.sqrt(2.0 / (k * k * cin))
+        if name.startswith("Mconv7") or name.startswith("conv5_5"):
+            std *= 0.25
+        sd[name + ".weight"] = (rng.standard_normal((cout, cin, k, k)) * std).astype(np.float32)
+        sd[name + ".bias"] = rng.normal(0.05, 0.05, cout).astype(np.float32)
+    return sd

@@ -442,6 +442,39 @@ int bf_hmr_preprocess(bf_hmr *h, int n, int H, int W, const uint8_t *images, uin
 int bf_hmr_selftest_conv(int device, int n, int H, int W, int cin, int cout, int k, int stride, int pad, const float *x, const float *w,
                          const float *bias, const float *res, int relu, float *y);
 
+/* ---- OpenPose body estimator (openpose/body.py Body.__call__, openpose/model.py bodypose_model) -------------------------------------
+ * The COCO-18 body CPM on the GPU in fp32 at body.py's four scales: cv2.resize INTER_CUBIC (OpenCV's 11-bit fixed-point path),
+ * padRightDownCorner, /256 - 0.5, the VGG front and six two-branch stages; then per scale the float cubic x8 resize, the crop and the
+ * cubic resize to the original, accumulated into float64 heatmap_avg[n][H][W][19] / paf_avg[n][H][W][38] in body.py's operation
+ * order (heatmap_avg += heatmap_avg + heatmap / 4).  Weights are packed by bodyfitting_amd/openpose.py in the order openpose_api.hip
+ * lists them (bf_openpose_n_weights floats).  bgr[n][H][W][3] uint8, 1 <= n <= max_batch, 13 <= H <= max_h, 13 <= W <= max_w; one
+ * call takes images of one size.  Each maps / inject call leaves its maps resident for bf_openpose_peaks and bf_openpose_pairs; the
+ * greedy connection pick and the subset assembly run on the host (openpose.py). */
+typedef struct bf_openpose bf_openpose;
+int64_t bf_openpose_n_weights(void);
+int bf_openpose_create(int device, const float *weights, int64_t n_weights, int max_batch, int max_h, int max_w, bf_openpose **out);
+void bf_openpose_destroy(bf_openpose *op);
+/* the accumulated maps; heat / paf may be NULL (the maps stay resident either way) */
+int bf_openpose_maps(bf_openpose *op, int n, int H, int W, const uint8_t *bgr, double *heat, double *paf);
+/* the network alone: per scale (0.5, 1, 1.5, 2 x 368 / H), concatenated, inputs[n][Hp][Wp][4] (channel 3 zero; may be NULL) and
+ * outputs[n][Hp/8][Wp/8][57] (Mconv7_stage6_L1 0:38, Mconv7_stage6_L2 38:57) */
+int bf_openpose_network(bf_openpose *op, int n, int H, int W, const uint8_t *bgr, float *inputs, float *outputs);
+/* test hook: everything after the network on injected per-scale outputs (bf_openpose_network's layout, n_outputs floats) */
+int bf_openpose_inject(bf_openpose *op, int n, int H, int W, const float *outputs, int64_t n_outputs, double *heat, double *paf);
+/* hw[2] = (H, W) of the resident maps */
+int bf_openpose_map_size(bf_openpose *op, int *hw);
+/* on the resident maps of the first n views: gaussian_filter(sigma=3) of parts 0..17 (blurred[n][H][W][18], may be NULL) and the
+ * peaks (> 0.1 and >= the four neighbours): counts[n], peaks[n][cap][3] = (x, y, part), scores[n][cap] = heatmap_avg there, in no
+ * particular order.  More than cap peaks in a view: BF_ERR_UNSUPPORTED. */
+int bf_openpose_peaks(bf_openpose *op, int n, int cap, double *blurred, int *counts, int *peaks, double *scores);
+/* limb scores on the resident paf_avg of one view: jobs[npairs][5] = (limb 0..18, ax, ay, bx, by) -> score[npairs]
+ * (score_with_dist_prior) and above[npairs] (samples of the 100 > 0.05) */
+int bf_openpose_pairs(bf_openpose *op, int view, int npairs, const int *jobs, double *score, int *above);
+/* test hook: one convolution of the OpenPose kernel (stride 1, padding k / 2, k = 1, 3 or 7) on host arrays - x[n][H][W][cin],
+ * w[k*k*cin][cout] in (ky, kx, ci) order, bias[cout], relu 0/1 -> y[n][H][W][cout] */
+int bf_openpose_selftest_conv(int device, int n, int H, int W, int cin, int cout, int k, int relu, const float *x, const float *w,
+                              const float *bias, float *y);
+
 /* Device time of the kernels of the last bf_fit on this batch, from HIP events on the batch's
  * stream: ms[0] = fit loop kernel(s), ms[1] = final full-mesh forward kernel, ms[2] = joints kernel +
  * result fetch, ms[3] = whole call.  (With BF_FIT_DENSE every iteration's mesh pass is inside ms[0].) */
