@@ -165,6 +165,14 @@ SIGNATURES = {
     "bf_openpose_peaks": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _IP, _IP, _DP]),
     "bf_openpose_pairs": (C.c_int, [_VP, C.c_int, C.c_int, _IP, _DP, _IP]),
     "bf_openpose_selftest_conv": (C.c_int, [C.c_int] * 8 + [_FP, _FP, _FP, _FP]),
+    "bf_openpose_hand_n_weights": (C.c_int64, []),
+    "bf_openpose_hand_create": (C.c_int, [C.c_int, _FP, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "bf_openpose_hand_destroy": (None, [_VP]),
+    "bf_openpose_hand_maps": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, _IP, _DP]),
+    "bf_openpose_hand_network": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, _IP, _FP, _FP]),
+    "bf_openpose_hand_inject": (C.c_int, [_VP, C.c_int, _IP, _FP, C.c_int64, _DP]),
+    "bf_openpose_hand_peaks": (C.c_int, [_VP, C.c_int, _DP, _IP, _DP, _IP]),
+    "bf_openpose_hand_selftest_label": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_uint8), _IP, _IP]),
     "bf_batch_debug_dump": (C.c_int, [_VP, _FP, C.c_int]),
     "bf_batch_debug_disp_moment": (C.c_int, [_VP, _FP]),
 }

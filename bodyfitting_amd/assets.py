@@ -19,7 +19,8 @@ The HMR weights of the initial estimate (`hmr.HMR`) are the state dict registere
 `data/model_checkpoint.pt` + `data/smpl_mean_params.npz` (config.HMR_CHECKPOINT, config.SMPL_MEAN_PARAMS), folded and packed once.
 
 The OpenPose body weights (`openpose.OpenPose`) are the state dict registered with `register_openpose(...)`, else the reference's
-`models/body_pose_model.pth` (openpose/infer_openpose.py:53), packed once.
+`models/body_pose_model.pth` (openpose/infer_openpose.py:53), packed once; the hand weights (`openpose_hand.OpenPoseHand`) likewise
+`register_openpose_hand(...)`, else `models/hand_pose_model.pth`.
 """
 from __future__ import annotations
 
@@ -39,6 +40,8 @@ HMR_CHECKPOINT = "model_checkpoint.pt"          # config.HMR_CHECKPOINT / SMPL_M
 SMPL_MEAN_PARAMS = "smpl_mean_params.npz"
 _OPENPOSE = {}
 OPENPOSE_WEIGHTS = os.path.join("models", "body_pose_model.pth")      # infer_openpose.py:53, relative to the working directory
+_OPENPOSE_HAND = {}
+OPENPOSE_HAND_WEIGHTS = os.path.join("models", "hand_pose_model.pth")  # next to the body weights
 
 
 def _drop_kid(model_type=None, gender=None):
@@ -210,3 +213,25 @@ def get_openpose(path=None):
                          f"registered with assets.register_openpose(); alternatively pass keypoints=")
     _OPENPOSE["packed"] = openpose.pack(openpose.load_weights(path))
     return _OPENPOSE["packed"]
+
+
+def register_openpose_hand(state_dict):
+    """OpenPose hand weights held in memory: a state dict with the caffe keys of hand_pose_model.pth (`conv1_1.weight`, ...,
+    `Mconv7_stage6.bias`).  None forgets them.  A missing key raises ValueError."""
+    _OPENPOSE_HAND.clear()
+    if state_dict is not None:
+        from . import openpose_hand
+        _OPENPOSE_HAND["packed"] = openpose_hand.pack_hand(openpose_hand.match_hand_state(state_dict))
+
+
+def get_openpose_hand(path=None):
+    """-> the packed float32 weights for openpose_hand.OpenPoseHand, read once per process"""
+    if "packed" in _OPENPOSE_HAND:
+        return _OPENPOSE_HAND["packed"]
+    from . import openpose_hand
+    path = path or OPENPOSE_HAND_WEIGHTS
+    if not os.path.exists(path):
+        raise ValueError(f"no hand keypoint estimator: OpenPose hands need {path} (the reference's hand_pose_model.pth) or weights "
+                         f"registered with assets.register_openpose_hand(); alternatively pass keypoints=")
+    _OPENPOSE_HAND["packed"] = openpose_hand.pack_hand(openpose_hand.load_hand_weights(path))
+    return _OPENPOSE_HAND["packed"]

@@ -10,6 +10,10 @@ Without `keypoints` (None) the 2-D keypoints come from the reference's OpenPose 
 weights from `assets.get_openpose()`), in place of apps/genebody_fitting.py's openpose.bin run: each view's image (RGB, as the
 runner loads it) is flipped to BGR - what openpose.bin reads from the written PNG - detected, laid out as BODY_25 as
 openpose/infer_openpose.py lays it out, and the person io.load_openpose would pick is kept.
+With `options.detect_hands` (default False) and smpl_type 'smplx', the hands come too, as `openpose.bin --hand` gives them
+(apps/genebody_fitting.py:144-155): the reference's hand estimator (`openpose_hand.OpenPoseHand`, weights from
+`assets.get_openpose_hand()`) on every box util.handDetect accepts, all views of the frame in one batched call; each person gets
+`hand_left` / `hand_right` [21, 3] in image coordinates, and the person is picked by the confidence sum over all its arrays.
 """
 from __future__ import annotations
 
@@ -34,6 +38,8 @@ class BodyFitting:
         self._fitters = {}
         self._hmr = None
         self._openpose = None
+        self._openpose_hand = None
+        self.detect_hands = bool(getattr(options, "detect_hands", False)) and self.smpl_type == "smplx"
 
     def _fitter(self, gender):
         if gender not in self._fitters:      # the reference rebuilds this per call (body_fitting.py:82)
@@ -55,10 +61,16 @@ class BodyFitting:
         if images is None:
             raise ValueError("BodyFitting: keypoints=None detects them on the images, and images is None")
         bgr = [np.ascontiguousarray(np.asarray(im)[:, :, ::-1]) for im in images]
+        H, W = bgr[0].shape[:2]
         if self._openpose is None:            # (no weights registered and no file: ValueError naming models/body_pose_model.pth)
-            H, W = bgr[0].shape[:2]
             self._openpose = O.OpenPose(device=getattr(self.options, "device", 0), max_batch=4, max_h=max(H, 1024), max_w=max(W, 1024))
-        return [O.select_person(p) for p in self._openpose.pose25(bgr)]
+        if not self.detect_hands:
+            return [O.select_person(p) for p in self._openpose.pose25(bgr)]
+        from . import openpose_hand as OH
+        if self._openpose_hand is None:       # (no weights registered and no file: ValueError naming models/hand_pose_model.pth)
+            self._openpose_hand = OH.OpenPoseHand(device=getattr(self.options, "device", 0), max_hands=16, max_h=max(H, 1024),
+                                                  max_w=max(W, 1024))
+        return [OH.select_person_entry(p) for p in OH.detect_people(self._openpose, self._openpose_hand, bgr)]
 
     def __call__(self, images, c2ws, Ks, keypoints=None, gender="male", keyframe=25, use_frames=list(range(48)),
                  use_mask=False, masks=None, mask_frames=None, render_skip=12, output_folder=None,

@@ -1,6 +1,6 @@
 // Host side of the OpenPose body estimator (reference openpose/body.py Body.__call__, openpose/model.py bodypose_model): the layer
 // list, the resident weights, the buffers (grown to the largest call) and the launch sequence.  Kernels: openpose_kernels.hip.
-#include "bf_host.h"
+#include "openpose_host.h"
 
 #include <cmath>
 
@@ -11,20 +11,7 @@
 #define OP_CAT 192                     // the stage input: out1 0:128 | L1 128:166 | 0 0 | L2 168:187 | 0 x 5
 #define OP_NSCALE 4
 
-struct OpConv {
-    const float *x, *w, *bias;
-    float *y;
-    int ldx, cin, ldo, cout, coutp, k, relu;
-};
-struct OpConvLaunch {
-    OpConv g[2];
-    int n, H, W;
-};
 extern "C" __global__ void bf_op_input_kernel(int, int, int, int, int, int, int, double, const uint8_t *, float4 *);
-extern "C" __global__ void bf_op_conv128_kernel(OpConvLaunch);
-extern "C" __global__ void bf_op_conv64_kernel(OpConvLaunch);
-extern "C" __global__ void bf_op_conv7_kernel(OpConvLaunch);
-extern "C" __global__ void bf_op_pool_kernel(int, int, int, int, const float4 *, float4 *);
 extern "C" __global__ void bf_op_up8_kernel(int, int, int, int, int, const float *, float *);
 extern "C" __global__ void bf_op_maps_kernel(int, int, int, int, int, double, double, const float *, double *, double *);
 extern "C" __global__ void bf_op_gauss_kernel(int, int, int, int, int, const double *, double *);
@@ -34,20 +21,13 @@ extern "C" __global__ void bf_op_pairs_kernel(int, int, int, const double *, con
 namespace {
 const double SCALE_SEARCH[OP_NSCALE] = {0.5, 1.0, 1.5, 2.0};     // body.py:61
 
-struct OpLayer { size_t w, b; int cin, cout, coutp, k; };       // packed [k*k*cin][coutp] then the bias [coutp]; cin padded to 4
-
 // The order bodyfitting_amd/openpose.py pack() writes: the VGG front (conv1_1 .. conv4_4_CPM); conv5_1_CPM L1 | L2 as one 128 -> 256
 // layer; conv5_2 .. conv5_5 each L1 then L2; per stage 2 .. 6: Mconv1 L1 | L2 as one 192 -> 256 layer on the padded concat, then
 // Mconv2 .. Mconv7 each L1 then L2.
 std::vector<OpLayer> op_layers(size_t *total) {
     std::vector<OpLayer> L;
     size_t at = 0;
-    auto add = [&](int cin, int cout, int k) {
-        const int cp = (cin + 3) / 4 * 4, co = (cout + 3) / 4 * 4;
-        OpLayer l{at, at + (size_t)k * k * cp * co, cp, cout, co, k};
-        at = l.b + co;
-        L.push_back(l);
-    };
+    auto add = [&](int cin, int cout, int k) { op_add_layer(L, &at, cin, cout, k); };
     const int vgg[12][2] = {{3, 64}, {64, 64}, {64, 128}, {128, 128}, {128, 256}, {256, 256}, {256, 256}, {256, 256}, {256, 512},
                             {512, 512}, {512, 256}, {256, 128}};
     for (int i = 0; i < 12; ++i) add(vgg[i][0], vgg[i][1], 3);
@@ -69,30 +49,6 @@ std::vector<OpLayer> op_layers(size_t *total) {
     return L;
 }
 
-OpConv conv_of(const float *wts, const OpLayer &l, const float *x, int ldx, float *y, int ldo, int relu) {
-    OpConv c;
-    c.x = x; c.w = wts + l.w; c.bias = wts + l.b; c.y = y;
-    c.ldx = ldx; c.cin = l.cin; c.ldo = ldo; c.cout = l.cout; c.coutp = l.coutp; c.k = l.k; c.relu = relu;
-    return c;
-}
-
-// one launch of one or two convolutions of the same n x H x W grid (BN = 64 tiles when no output has more than 64 channels)
-int launch_conv(hipStream_t s, int n, int H, int W, const OpConv &a, const OpConv *b = nullptr) {
-    OpConvLaunch L;
-    L.g[0] = a; L.g[1] = b ? *b : a; L.n = n; L.H = H; L.W = W;
-    const long long M = (long long)n * H * W;
-    const int maxc = b ? std::max(a.cout, b->cout) : a.cout;
-    const int bn = maxc <= 64 ? 64 : 128;
-    const dim3 grid((unsigned)((M + 127) / 128), (unsigned)((maxc + bn - 1) / bn), b ? 2 : 1);
-    if (bn == 64) hipLaunchKernelGGL(bf_op_conv64_kernel, grid, dim3(256), 0, s, L);
-    else if (a.k == 7) hipLaunchKernelGGL(bf_op_conv7_kernel, grid, dim3(256), 0, s, L);
-    else hipLaunchKernelGGL(bf_op_conv128_kernel, grid, dim3(256), 0, s, L);
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
-}
-
-unsigned blocks(long long total) { return (unsigned)((total + 255) / 256); }
-
 struct ScaleDims { double s; int h, w, Hp, Wp, hq, wq; };
 ScaleDims scale_dims(int H, int W, int m) {
     ScaleDims d;
@@ -104,14 +60,6 @@ ScaleDims scale_dims(int H, int W, int m) {
     return d;
 }
 
-template <typename T>
-hipError_t ensure(hipStream_t s, DevBuf<T> &b, size_t count) {
-    if (b.n >= count && b.p) return hipSuccess;
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    b.release();
-    return b.alloc(count);
-}
 }  // namespace
 
 struct bf_openpose {
@@ -138,17 +86,17 @@ static int op_reserve(bf_openpose *op, int n, int H, int W) {
     }
     const size_t pix = (size_t)n * H * W;
     hipStream_t s = op->stream;
-    HIP_TRY(ensure(s, op->img, pix * 3));
-    HIP_TRY(ensure(s, op->inp, act / 16));
-    for (int i = 0; i < 2; ++i) HIP_TRY(ensure(s, op->act[i], act));
-    HIP_TRY(ensure(s, op->cat, cat));
-    for (int i = 0; i < 2; ++i) HIP_TRY(ensure(s, op->br[i], cat / OP_CAT * 1024));
-    HIP_TRY(ensure(s, op->out, out));
-    HIP_TRY(ensure(s, op->heat, pix * OP_NHEAT));
-    HIP_TRY(ensure(s, op->paf, pix * OP_NPAF));
-    HIP_TRY(ensure(s, op->tmp, pix * OP_NPART));
-    HIP_TRY(ensure(s, op->bl, pix * OP_NPART));
-    HIP_TRY(ensure(s, op->counts, (size_t)n));
+    HIP_TRY(op_ensure(s, op->img, pix * 3));
+    HIP_TRY(op_ensure(s, op->inp, act / 16));
+    for (int i = 0; i < 2; ++i) HIP_TRY(op_ensure(s, op->act[i], act));
+    HIP_TRY(op_ensure(s, op->cat, cat));
+    for (int i = 0; i < 2; ++i) HIP_TRY(op_ensure(s, op->br[i], cat / OP_CAT * 1024));
+    HIP_TRY(op_ensure(s, op->out, out));
+    HIP_TRY(op_ensure(s, op->heat, pix * OP_NHEAT));
+    HIP_TRY(op_ensure(s, op->paf, pix * OP_NPAF));
+    HIP_TRY(op_ensure(s, op->tmp, pix * OP_NPART));
+    HIP_TRY(op_ensure(s, op->bl, pix * OP_NPART));
+    HIP_TRY(op_ensure(s, op->counts, (size_t)n));
     return BF_OK;
 }
 
@@ -181,7 +129,7 @@ static int op_network(bf_openpose *op, int n, int Hp, int Wp) {
         x = y; cin = L[i].cout;
         if (pi < 3 && i == pool_after[pi]) {
             float *z = x == A ? B : A;
-            hipLaunchKernelGGL(bf_op_pool_kernel, dim3(blocks((long long)n * (H / 2) * (W / 2) * (cin / 4))), dim3(256), 0, s, n, H, W, cin,
+            hipLaunchKernelGGL(bf_op_pool_kernel, dim3(op_blocks((long long)n * (H / 2) * (W / 2) * (cin / 4))), dim3(256), 0, s, n, H, W, cin,
                                (const float4 *)x, (float4 *)z);
             HIP_TRY(hipGetLastError());
             x = z; H /= 2; W /= 2; ++pi;
@@ -234,7 +182,7 @@ static int op_scale(bf_openpose *op, int n, int H, int W, int m, const float *in
         HIP_TRY(hipMemcpyAsync(op->out.p, injected, q * sizeof(float), hipMemcpyHostToDevice, s));
     } else {
         const long long px = (long long)n * d.Hp * d.Wp;
-        hipLaunchKernelGGL(bf_op_input_kernel, dim3(blocks(px)), dim3(256), 0, s, n, H, W, d.h, d.w, d.Hp, d.Wp, 1.0 / d.s,
+        hipLaunchKernelGGL(bf_op_input_kernel, dim3(op_blocks(px)), dim3(256), 0, s, n, H, W, d.h, d.w, d.Hp, d.Wp, 1.0 / d.s,
                            (const uint8_t *)op->img.p, (float4 *)op->inp.p);
         HIP_TRY(hipGetLastError());
         if (in_host) HIP_TRY(hipMemcpyAsync(in_host, op->inp.p, (size_t)px * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -242,10 +190,10 @@ static int op_scale(bf_openpose *op, int n, int H, int W, int m, const float *in
         if (out_host) HIP_TRY(hipMemcpyAsync(out_host, op->out.p, q * sizeof(float), hipMemcpyDeviceToHost, s));
     }
     float *up = op->act[0].p;                                    // n x h x w x 57 <= n x Hp x Wp x 64
-    hipLaunchKernelGGL(bf_op_up8_kernel, dim3(blocks((long long)n * d.h * d.w * OP_NOUT)), dim3(256), 0, s, n, d.h, d.w, d.hq, d.wq,
+    hipLaunchKernelGGL(bf_op_up8_kernel, dim3(op_blocks((long long)n * d.h * d.w * OP_NOUT)), dim3(256), 0, s, n, d.h, d.w, d.hq, d.wq,
                        (const float *)op->out.p, up);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(bf_op_maps_kernel, dim3(blocks((long long)n * H * W * OP_NOUT)), dim3(256), 0, s, n, H, W, d.h, d.w,
+    hipLaunchKernelGGL(bf_op_maps_kernel, dim3(op_blocks((long long)n * H * W * OP_NOUT)), dim3(256), 0, s, n, H, W, d.h, d.w,
                        1.0 / ((double)H / d.h), 1.0 / ((double)W / d.w), (const float *)up, op->heat.p, op->paf.p);
     HIP_TRY(hipGetLastError());
     return BF_OK;
@@ -348,15 +296,15 @@ int bf_openpose_peaks(bf_openpose *op, int n, int cap, double *blurred, int *cou
     HIP_TRY(hipSetDevice(op->device));
     hipStream_t s = op->stream;
     const int H = op->map_h, W = op->map_w;
-    HIP_TRY(ensure(s, op->peaks, (size_t)n * cap * 3));
-    HIP_TRY(ensure(s, op->scores, (size_t)n * cap));
+    HIP_TRY(op_ensure(s, op->peaks, (size_t)n * cap * 3));
+    HIP_TRY(op_ensure(s, op->scores, (size_t)n * cap));
     const long long total = (long long)n * H * W * OP_NPART;
-    hipLaunchKernelGGL(bf_op_gauss_kernel, dim3(blocks(total)), dim3(256), 0, s, n, H, W, 0, OP_NHEAT, (const double *)op->heat.p, op->tmp.p);
+    hipLaunchKernelGGL(bf_op_gauss_kernel, dim3(op_blocks(total)), dim3(256), 0, s, n, H, W, 0, OP_NHEAT, (const double *)op->heat.p, op->tmp.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(bf_op_gauss_kernel, dim3(blocks(total)), dim3(256), 0, s, n, H, W, 1, OP_NPART, (const double *)op->tmp.p, op->bl.p);
+    hipLaunchKernelGGL(bf_op_gauss_kernel, dim3(op_blocks(total)), dim3(256), 0, s, n, H, W, 1, OP_NPART, (const double *)op->tmp.p, op->bl.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(op->counts.p, 0, (size_t)n * sizeof(int), s));
-    hipLaunchKernelGGL(bf_op_peaks_kernel, dim3(blocks(total)), dim3(256), 0, s, n, H, W, (const double *)op->bl.p, (const double *)op->heat.p,
+    hipLaunchKernelGGL(bf_op_peaks_kernel, dim3(op_blocks(total)), dim3(256), 0, s, n, H, W, (const double *)op->bl.p, (const double *)op->heat.p,
                        cap, op->counts.p, op->peaks.p, op->scores.p);
     HIP_TRY(hipGetLastError());
     if (blurred) HIP_TRY(hipMemcpyAsync(blurred, op->bl.p, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -381,9 +329,9 @@ int bf_openpose_pairs(bf_openpose *op, int view, int npairs, const int *jobs, do
     }
     HIP_TRY(hipSetDevice(op->device));
     hipStream_t s = op->stream;
-    HIP_TRY(ensure(s, op->jobs, (size_t)npairs * 5));
-    HIP_TRY(ensure(s, op->jscore, (size_t)npairs));
-    HIP_TRY(ensure(s, op->jcnt, (size_t)npairs));
+    HIP_TRY(op_ensure(s, op->jobs, (size_t)npairs * 5));
+    HIP_TRY(op_ensure(s, op->jscore, (size_t)npairs));
+    HIP_TRY(op_ensure(s, op->jcnt, (size_t)npairs));
     HIP_TRY(hipMemcpyAsync(op->jobs.p, jobs, (size_t)npairs * 5 * sizeof(int), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(bf_op_pairs_kernel, dim3((npairs + 63) / 64), dim3(64), 0, s, npairs, H, W,
                        (const double *)(op->paf.p + (size_t)view * H * W * OP_NPAF), (const int *)op->jobs.p, op->jscore.p, op->jcnt.p);

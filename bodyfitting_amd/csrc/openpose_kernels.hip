@@ -8,32 +8,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "openpose_device.h"
+
 #define OP_NPAF 38
 #define OP_NHEAT 19
 #define OP_NOUT 57
 #define OP_NPART 18
 #define OP_GR 12                  // scipy's radius int(4 * sigma + 0.5) for sigma = 3
-
-// interpolateCubic(x, coeffs), A = -0.75, in float
-__device__ __forceinline__ void op_cubic(float x, float c[4]) {
-    const float A = -0.75f;
-    const float x1 = x + 1.f;
-    c[0] = ((A * x1 - 5.f * A) * x1 + 8.f * A) * x1 - 4.f * A;
-    c[1] = ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
-    const float y = 1.f - x;
-    c[2] = ((A + 2.f) * y - (A + 3.f)) * y * y + 1.f;
-    c[3] = 1.f - c[0] - c[1] - c[2];
-}
-
-// one destination index of a cubic resize: the source coordinate (float)((d + 0.5) * scale - 0.5), floored; taps s - 1 .. s + 2
-// clamped to the source (OpenCV replicates the border); coefficients of the fraction
-__device__ __forceinline__ void op_axis(int d, double scale, int n, int idx[4], float c[4]) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    const int s = (int)floorf(f);
-    f -= (float)s;
-    op_cubic(f, c);
-    for (int j = 0; j < 4; ++j) idx[j] = min(max(s - 1 + j, 0), n - 1);
-}
 
 // body.py:73-75 for one scale: cv2.resize(img, fx=s, fy=s, INTER_CUBIC) on uint8 BGR through OpenCV's fixed-point path (coefficients
 // saturate_cast<short>(c * 2048), an int horizontal sum per source row, then (sum_k h_k * b_k + 2^21) >> 22 saturated to uchar),

@@ -1,2 +1,3 @@
-"""`openpose` of the reference (openpose/body.py, openpose/infer_openpose.py) on the HIP path: `from openpose.body import Body`
-resolves here when bodyfitting_amd/dropin is on sys.path.  Hands (openpose/hand.py) and drawing are not provided."""
+"""`openpose` of the reference (openpose/body.py, openpose/hand.py, openpose/util.py, openpose/infer_openpose.py) on the HIP path:
+`from openpose.body import Body` and `from openpose.hand import Hand` resolve here when bodyfitting_amd/dropin is on sys.path.
+util's drawing functions return the canvas unchanged (said once on stderr)."""

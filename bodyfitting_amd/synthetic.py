@@ -786,3 +786,18 @@ def make_openpose_weights(seed=0):
         sd[name + ".weight"] = (rng.standard_normal((cout, cin, k, k)) * std).astype(np.float32)
         sd[name + ".bias"] = rng.normal(0.05, 0.05, cout).astype(np.float32)
     return sd
+
+
+def make_openpose_hand_weights(seed=0):
+    """A synthetic hand_pose_model.pth state dict, scaled as make_openpose_weights: He-normal convolutions, biases around 0.05, and
+    the map outputs (conv6_2_CPM, Mconv7) scaled down so the maps stay in the range of heatmaps"""
+    from . import openpose_hand
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for name, (cout, cin, k) in openpose_hand.hand_conv_shapes().items():
+        std = np.sqrt(2.0 / (k * k * cin))
+        if name.startswith("Mconv7") or name.startswith("conv6_2"):
+            std *= 0.25
+        sd[name + ".weight"] = (rng.standard_normal((cout, cin, k, k)) * std).astype(np.float32)
+        sd[name + ".bias"] = rng.normal(0.05, 0.05, cout).astype(np.float32)
+    return sd

@@ -475,6 +475,36 @@ int bf_openpose_pairs(bf_openpose *op, int view, int npairs, const int *jobs, do
 int bf_openpose_selftest_conv(int device, int n, int H, int W, int cin, int cout, int k, int relu, const float *x, const float *w,
                               const float *bias, float *y);
 
+/* ---- OpenPose hand estimator (openpose/hand.py Hand.__call__, openpose/model.py handpose_model, openpose/util.py npmax) -------------
+ * The 21-part hand CPM on crops of views, in fp32 at hand.py's four scales, through the body estimator's convolution kernels: per crop
+ * cv2.resize INTER_CUBIC (uint8, the crop's own edges replicated), padRightDownCorner, /256 - 0.5, the VGG front and five stages; then
+ * the float x8 resize, the crop and the resize to the crop's size, accumulated into float64 heatmap_avg (+= heatmap / 4).  Crops of
+ * one network size run as one batch (up to max_hands).  Weights are packed by bodyfitting_amd/openpose_hand.py in the order
+ * openpose_hand_api.hip lists them (bf_openpose_hand_n_weights floats).  bgr[n_views][H][W][3] uint8, 13 <= H <= max_h,
+ * 13 <= W <= max_w; boxes[n_hands][5] = (view, x, y, w, h), the crop bgr[view][y:y+h, x:x+w], inside its view and at least 13 on a
+ * side (anything else: BF_ERR_INVALID).  Each maps / inject call leaves its maps resident for bf_openpose_hand_peaks. */
+typedef struct bf_openpose_hand bf_openpose_hand;
+int64_t bf_openpose_hand_n_weights(void);
+int bf_openpose_hand_create(int device, const float *weights, int64_t n_weights, int max_hands, int max_h, int max_w, bf_openpose_hand **out);
+void bf_openpose_hand_destroy(bf_openpose_hand *h);
+/* heat: per crop heatmap_avg[h][w][22] float64, the crops end to end in box order (may be NULL) */
+int bf_openpose_hand_maps(bf_openpose_hand *h, int n_views, int H, int W, const uint8_t *bgr, int n_hands, const int *boxes, double *heat);
+/* the network alone: per scale (0.5, 1, 1.5, 2 x 368 / h), per crop in box order, concatenated, inputs[Hp][Wp][4] (channel 3 zero;
+ * may be NULL) and outputs[Hp/8][Wp/8][22] (Mconv7_stage6) */
+int bf_openpose_hand_network(bf_openpose_hand *h, int n_views, int H, int W, const uint8_t *bgr, int n_hands, const int *boxes, float *inputs,
+                             float *outputs);
+/* test hook: everything after the network on injected outputs (bf_openpose_hand_network's layout, n_outputs floats); only the boxes'
+ * w and h are read */
+int bf_openpose_hand_inject(bf_openpose_hand *h, int n_hands, const int *boxes, const float *outputs, int64_t n_outputs, double *heat);
+/* on the n resident crops (n = the last call's n_hands), per part 0..20: gaussian_filter(sigma=3) (blurred: per crop [h][w][21] end to
+ * end, may be NULL); the 8-connected components of blurred > 0.05, the one with the largest np.sum of heatmap_avg (the first on a
+ * tie), and util.npmax of heatmap_avg zeroed off it -> peaks[n][21][2] = (x, y) in crop coordinates, scores[n][21] = the zeroed map
+ * there, found[n][21] = 1; an empty mask gives (0, 0), 0, 0 */
+int bf_openpose_hand_peaks(bf_openpose_hand *h, int n, double *blurred, int *peaks, double *scores, int *found);
+/* test hook: skimage.measure.label(binary, connectivity=2) of binary[n][H][W] (0 / 1) -> labels[n][H][W] (0 off the mask, components
+ * numbered 1.. by the raster order of their first pixel), counts[n] */
+int bf_openpose_hand_selftest_label(int device, int n, int H, int W, const uint8_t *binary, int *labels, int *counts);
+
 /* Device time of the kernels of the last bf_fit on this batch, from HIP events on the batch's
  * stream: ms[0] = fit loop kernel(s), ms[1] = final full-mesh forward kernel, ms[2] = joints kernel +
  * result fetch, ms[3] = whole call.  (With BF_FIT_DENSE every iteration's mesh pass is inside ms[0].) */
