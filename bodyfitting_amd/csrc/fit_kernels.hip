@@ -18,11 +18,13 @@
 // instruction count:
 //   waves 0-2  chain specialists: wave r carries matrix row r of every joint (row r of G_i depends only on row r of G_parent),
 //              lane = joint; the local transforms [R_j | rel_j] are in LDS when the iteration starts (the rotation formed by the
-//              lane that stepped the joint's dofs, rel_j by wave 3 with the betas), two tree levels per round through ds_bpermute;
+//              lane that stepped the joint's dofs, rel_j with the betas), two tree levels per round through ds_bpermute;
 //              then skinning of the selector vertices, the 48-view projection, the reverse skinning + subtree sums, and on wave 0
 //              the reverse Rodrigues + Adam for the pose;
-//   wave 3     skinning / projection like the others; the betas' gradient, step and everything the next forward pass derives
-//              from them; the priors' share of dL/dtheta (arg-min component, angle prior) for the Adam phase;
+//   wave 3     skinning / projection like the others; the priors' share of dL/dtheta (arg-min component, angle prior) for the Adam
+//              phase; the betas' gradient, step and everything the next forward pass derives from them - in the SMPL instance
+//              outside the dense schedule those are dealt over waves 1-3 (16 lanes per beta, then a third of the tables each;
+//              transl / scale on wave 3), elsewhere wave 3's alone;
 //   waves 4-7  GMM specialists: the symmetrised precision rows of components 2g, 2g+1 live in VGPRs for the whole launch; they
 //              also carry what needs few registers and only LDS inputs: the pose blend of the selector vertices (phase A) and
 //              d(pose feature) (phase F).
@@ -148,6 +150,10 @@ __device__ inline float wave_sum(float v) {
     float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
     return (a + b) + (c + d);
 }
+
+// relaxed workgroup-scope LDS read of a hand-over between waves (through the carve's generic pointers a volatile read stays a flat
+// access, whose null test gfx950 has no instruction for: "Illegal instruction detected: V_CMP_NE_U32_e32 0, $src_shared_base")
+__device__ inline int bf_lds_get(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 // sin and cos of a non-negative angle of moderate size (|a| < ~1e4): Cody-Waite reduction by pi/2 in three
 // parts, then the classic degree-7 / degree-8 minimax kernels on [-pi/4, pi/4]; about 1 ulp, ~30 instructions
@@ -380,6 +386,15 @@ fit_kernel(FitTab T, FrameIO io, HyperDev hp, int n_iters, int mode, const float
     const int cp = ci > 0 ? T.parents[ci] : 0;
     const unsigned long long cmask = c_on ? T.desc[ci] : 0ull;       // strict descendants of ci
     (void)cr; (void)cp; (void)cmask; (void)w_feat;                    // (only the two-phase variants read them)
+    // The sized SMPL instance outside the dense schedule deals the Adam phase's betas over waves 1-3, 16 lanes (one DPP row) per beta:
+    // wave w, lane (l = 4 (w - 1) + lane / 16, s = lane % 16) sums joints s, s + 16 and selector outputs s, s + 16, s + 32 of dL/dbeta_l.
+    // The parents of the lane's two joints live in one register (packed), so its reads of S.G do not wait for reads of S.par.
+    constexpr bool BETA_DEAL = NJ == 24 && NB > 0 && NB <= 10 && NS > 0 && NS * 3 <= 36 && !EXT;
+    const int bt_s = lane & 15;
+    const int bt_par = (BETA_DEAL && wave >= 1 && wave <= 3) ? (bt_s > 0 ? T.parents[bt_s] : 0) | ((bt_s + 16 < nj ? T.parents[bt_s + 16] : 0) << 8) : 0;
+    // waves 1-3 add 1 each once their betas are stepped (3 (it + 1) after iteration it): each then forms a part of what the next
+    // forward pass derives from all ten.  (A free word of the carve: S.scal[0].)
+    int *const bt_flag = (int *)S.scal;
     // projection role (geometry waves 0-3 only, so the GMM waves keep their registers for the precision rows): a lane
     // owns a PAIR of loss joints (2 ps, 2 ps + 1) on one view lane, ps = 4 * wave + lane / 16, view lane = lane % 16.
     // Both joints see the same projection matrix, so every multiply-add of the projection, the GMoF and the
@@ -507,7 +522,8 @@ fit_kernel(FitTab T, FrameIO io, HyperDev hp, int n_iters, int mode, const float
     auto beta_rows = [&](const float *bq, auto parts_c) {
         constexpr int NQ = NB ? (NB + 4) / 4 : 1;
         constexpr int parts = decltype(parts_c)::value;
-        const int o = lane < ns3 ? lane : 0, i0 = lane, i1 = lane + 64 < nj3 ? lane + 64 : 0;
+        const int lq = bf_launder(lane);          // (fresh where it is called: these addresses must not become loop invariants)
+        const int o = lq < ns3 ? lq : 0, i0 = lq, i1 = lq + 64 < nj3 ? lq + 64 : 0;
         float4 sq[NQ], ja[NQ], ra[NQ], jb[NQ], rb[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
@@ -522,10 +538,10 @@ fit_kernel(FitTab T, FrameIO io, HyperDev hp, int n_iters, int mode, const float
             for (int q = 0; q < NQ; ++q) acc += t[q].x * bq[4 * q] + t[q].y * bq[4 * q + 1] + t[q].z * bq[4 * q + 2] + t[q].w * bq[4 * q + 3];
             return acc;
         };
-        if ((parts & 4) && lane < ns3) { S.vs[lane] = dot(sq); S.dvsel[lane] = 0.f; }
+        if ((parts & 4) && lq < ns3) { S.vs[lq] = dot(sq); S.dvsel[lq] = 0.f; }
         // (rel_j[r], i = 3 j + r: L[12 j + 4 r + 3] = L[4 i + 3] when the rotations are formed ahead)
-        if (parts & 1) { S.J[i0] = dot(ja); S.dGt[i0] = 0.f; if (lane + 64 < nj3) { S.J[i1] = dot(jb); S.dGt[i1] = 0.f; } }
-        if (parts & 2) { (ROT_AHEAD ? S.L[4 * i0 + 3] : S.rel[i0]) = dot(ra); if (lane + 64 < nj3) (ROT_AHEAD ? S.L[4 * i1 + 3] : S.rel[i1]) = dot(rb); }
+        if (parts & 1) { S.J[i0] = dot(ja); S.dGt[i0] = 0.f; if (lq + 64 < nj3) { S.J[i1] = dot(jb); S.dGt[i1] = 0.f; } }
+        if (parts & 2) { (ROT_AHEAD ? S.L[4 * i0 + 3] : S.rel[i0]) = dot(ra); if (lq + 64 < nj3) (ROT_AHEAD ? S.L[4 * i1 + 3] : S.rel[i1]) = dot(rb); }
     };
     auto beta_dependent = [&](const float *P) {
         const float *beta = P + T.off_beta;
@@ -595,6 +611,7 @@ fit_kernel(FitTab T, FrameIO io, HyperDev hp, int n_iters, int mode, const float
     };
     if (EXT && tid == 0) ((int *)S.part)[BF_POSE_STATE_FLAG] = 0;          // (the chain waves' cue: no iteration's token yet)
     if (wave == 3) beta_dependent(S.pa);
+    if (BETA_DEAL && tid == 0) *bt_flag = 0;           // (before the prologue's barrier)
     if (ROT_AHEAD && wave == 0 && lane < nj) {
         const int po = lane > 0 ? T.off_pose + 3 * (lane - 1) : T.off_orient;
         rotations_ahead(lane, 0.f + S.pa[po], 0.f + S.pa[po + 1], 0.f + S.pa[po + 2]);
@@ -1143,7 +1160,7 @@ fit_kernel(FitTab T, FrameIO io, HyperDev hp, int n_iters, int mode, const float
                     bf_theta3(Pcur, wj, t3, S.thk, S.tho, S.pmean, S.hcomp, T.n_pca, T.off_lh, T.off_rh);
                     th0 = t3[0]; th1 = t3[1]; th2 = t3[2];
                 }
-                // rel_j = J_j - J_parent (rel_0 = J_0) was formed from the betas by wave 3 at the end of the previous
+                // rel_j = J_j - J_parent (rel_0 = J_0) was formed from the betas in the Adam phase of the previous
                 // iteration (or in the prologue); read it before the Rodrigues arithmetic so the latency hides under it
                 float a0, a1, a2;
                 if (ROT_AHEAD) {
@@ -1565,9 +1582,11 @@ fit_kernel(FitTab T, FrameIO io, HyperDev hp, int n_iters, int mode, const float
         // ================= phase I (+K): the reverse sweep's last step and the Adam step in ONE phase, each parameter
         // stepped by the lane that finishes its gradient:
         //   wave 0, lane = joint: dL/dR_i, Rodrigues reverse, + GMM / angle prior, Adam for the joint's three pose dofs
-        //   wave 1, lanes 0-3:    transl / scale from the pair-slot sums of the projection phase
+        //   wave 1, lanes 0-3:    transl / scale from the pair-slot sums of the projection phase (BETA_DEAL: wave 3, lanes 32-35)
         //   wave 3:               geometric dL/dbeta (6 lanes per beta, summed through a wave-private LDS strip), + shape
         //                         prior, Adam, then everything the next forward pass derives from the betas
+        //   (BETA_DEAL) waves 1-3: the same for betas 0-3, 4-7, 8-9, 16 lanes per beta summed by DPP; after a join on a counter in LDS
+        //                         (every beta stepped) wave 1 forms J, wave 2 rel, wave 3 the shaped selector vertices
         // Every consumer takes the arg-min GMM component from the eight q values itself (no hand-off between waves).
         const int tq = bf_launder(tid);
         auto adam = [&](int pidx, float pval, float am, float av, float grad) {
@@ -1659,14 +1678,85 @@ fit_kernel(FitTab T, FrameIO io, HyperDev hp, int n_iters, int mode, const float
             }
             BF_MARK(51, 0, it, t_iter);
         }
-        if (tq >= 64 && tq < 68) {                                   // transl / scale
+        if (!BETA_DEAL && tq >= 64 && tq < 68) {                        // transl / scale
             const int pidx = tq - 64;
             const float pval = Pcur[pidx], am = S.am[pidx], av = S.av[pidx], psum = S.scal[3 + pidx], sc3 = Pcur[3];
             const float grad = psum * (pidx < 3 ? sc3 * cscale : cscale) + (ext ? ext[EXT_T + pidx] + ext[EXT_K + pidx] : 0.f);
             S.g[pidx] = grad;                                        // (kept for the debug dump)
             adam(pidx, pval, am, av, grad);
         }
-        if (wave == 3) {
+        if (BETA_DEAL && wave >= 1 && wave <= 3) {
+            // geometric part of dL/dbeta: sum Jd.dJ + Jdrel.drel + sel_sd.dvp with dL/drel_i = GR_p^T t_i formed inline; lane
+            // (l = 4 (wave - 1) + lane / 16, s = lane % 16): joints s, s + 16 and outputs s, s + 16, s + 32, every read in one batch;
+            // the 16 lanes of beta l are one DPP row.  Lane 0 of a row steps its beta; wave 3's lanes 32-35 (no beta) transl / scale.
+            const int lq = bf_launder(lane);          // (fresh per phase: keeps this phase's address arithmetic out of the loop-invariant set)
+            const int s = lq & 15, l = 4 * (wave - 1) + (lq >> 4), lc = min(l, nb - 1);
+            const bool bstep = s == 0 && l < nb, tstep = wave == 3 && lq >= 32 && lq < 36;
+            const int pidx = tstep ? lq - 32 : T.off_beta + lc;
+            int ji[2], pj[2];
+            bool jon[2];
+            ji[0] = s; pj[0] = bt_par & 0xff; jon[0] = true;
+            ji[1] = min(s + 16, nj - 1); pj[1] = bt_par >> 8; jon[1] = s + 16 < nj;
+            float tv[2][3], dj[2][3], jd[2][3], jr[2][3], sw[3], sd[3];
+            float4 ga[2][3];
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const int i = ji[m];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    tv[m][k] = S.tt[i * 3 + k]; dj[m][k] = S.dJ[i * 3 + k];
+                    jd[m][k] = S.Jd[(i * 3 + k) * nbp + lc]; jr[m][k] = S.Jdrel[(i * 3 + k) * nbp + lc];
+                }
+                ga[m][0] = *(const float4 *)(S.G + pj[m] * 12); ga[m][1] = *(const float4 *)(S.G + pj[m] * 12 + 4);
+                ga[m][2] = *(const float4 *)(S.G + pj[m] * 12 + 8);
+            }
+#pragma unroll
+            for (int m = 0; m < 3; ++m) { const int o = min(s + 16 * m, ns3 - 1); sw[m] = S.sel_sd[o * nbp + lc]; sd[m] = S.dvp[o]; }
+            const float pval = Pcur[pidx], am = S.am[pidx], av = S.av[pidx], psum = S.scal[3 + (tstep ? lq - 32 : 0)], sc3 = Pcur[3];
+            __builtin_amdgcn_sched_barrier(0);
+            float acc = 0.f;
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                float e0 = tv[m][0], e1 = tv[m][1], e2 = tv[m][2];
+                if (ji[m] > 0) {
+                    e0 = ga[m][0].x * tv[m][0] + ga[m][1].x * tv[m][1] + ga[m][2].x * tv[m][2];
+                    e1 = ga[m][0].y * tv[m][0] + ga[m][1].y * tv[m][1] + ga[m][2].y * tv[m][2];
+                    e2 = ga[m][0].z * tv[m][0] + ga[m][1].z * tv[m][1] + ga[m][2].z * tv[m][2];
+                }
+                const float q = jd[m][0] * dj[m][0] + jr[m][0] * e0 + jd[m][1] * dj[m][1] + jr[m][1] * e1 + jd[m][2] * dj[m][2] + jr[m][2] * e2;
+                acc += jon[m] ? q : 0.f;
+            }
+#pragma unroll
+            for (int m = 0; m < 3; ++m) acc += (s + 16 * m < ns3) ? sw[m] * sd[m] : 0.f;
+            const float g = row16_sum(acc);
+            BF_MARK(52, 192, it, t_iter);
+            if (bstep || tstep) {
+                float grad;
+                if (tstep) grad = psum * (pidx < 3 ? sc3 * cscale : cscale);
+                else grad = g;
+                S.g[pidx] = grad;                                    // (kept for the debug dump)
+                adam(pidx, pval, am, av, tstep ? grad : grad + 2.f * hp.w_shape * pval);
+            }
+            BF_MARK(53, 192, it, t_iter);
+            // everything the next forward pass derives from the betas, once all three waves have stepped theirs (the join: each adds
+            // 1; the wait is a few LDS round trips, the three waves run the same instructions), a part per wave: wave 1 the rest
+            // joints J (+ zeroed dGt), wave 2 the offsets rel, wave 3 the shaped selector vertices (+ zeroed dvsel)
+            if (lq == 0) __hip_atomic_fetch_add(bt_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            while (bf_lds_get(bt_flag) < 3 * (it + 1)) __builtin_amdgcn_s_sleep(1);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            {
+                constexpr int NQB = NB ? (NB + 4) / 4 : 1;
+                const float *beta = (mode == 0 ? Pnext : Pcur) + T.off_beta;
+                float bq[4 * NQB];
+#pragma unroll
+                for (int c = 0; c < 4 * NQB; ++c) bq[c] = c < nb ? beta[c] : (c == nb ? 1.0f : 0.f);
+                if (wave == 1) beta_rows(bq, std::integral_constant<int, 1>());
+                else if (wave == 2) beta_rows(bq, std::integral_constant<int, 2>());
+                else beta_rows(bq, std::integral_constant<int, 4>());
+            }
+            BF_MARK(54, 192, it, t_iter);
+        }
+        if (!BETA_DEAL && wave == 3) {
             // geometric part of dL/dbeta: sum Jd.dJ + Jdrel.drel + sel_sd.dvp with dL/drel_i = GR_p^T t_i formed inline;
             // lane = (beta l = lane / 6, slice sl = lane % 6): joints sl, sl + 6, sl + 12, sl + 18 and outputs sl + 6 m
             const int l = min(lane / 6, nb - 1), sl = lane - (lane / 6) * 6;
