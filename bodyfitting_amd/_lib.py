@@ -173,6 +173,12 @@ SIGNATURES = {
     "bf_openpose_hand_inject": (C.c_int, [_VP, C.c_int, _IP, _FP, C.c_int64, _DP]),
     "bf_openpose_hand_peaks": (C.c_int, [_VP, C.c_int, _DP, _IP, _DP, _IP]),
     "bf_openpose_hand_selftest_label": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_uint8), _IP, _IP]),
+    "bf_views_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "bf_views_destroy": (None, [_VP]),
+    "bf_views_bbox": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _IP]),
+    "bf_views_prepare": (C.c_int, [_VP, C.c_int, _IP, C.POINTER(C.c_void_p), _IP, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                   C.POINTER(C.c_int64)]),
+    "bf_views_last_timing": (C.c_int, [_VP, _FP, C.POINTER(C.c_int64)]),
     "bf_batch_debug_dump": (C.c_int, [_VP, _FP, C.c_int]),
     "bf_batch_debug_disp_moment": (C.c_int, [_VP, _FP]),
 }

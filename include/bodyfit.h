@@ -505,6 +505,26 @@ int bf_openpose_hand_peaks(bf_openpose_hand *h, int n, double *blurred, int *pea
  * numbered 1.. by the raster order of their first pixel), counts[n] */
 int bf_openpose_hand_selftest_label(int device, int n, int H, int W, const uint8_t *binary, int *labels, int *counts);
 
+/* ---- GeneBody view preparation (apps/genebody_fitting.py:111-142 get_data, utils/io_utils.py:97-136 image_cropping) ----------------
+ * Every view of a frame at once.  bf_views_bbox uploads the masks whole (masks[n] -> [H][W] uint8 each, one size per call) and leaves
+ * them resident: bbox[n][4] = (top, left, bottom, right), the min / max row and column of mask != 0 (max inclusive, as np.max of
+ * np.where); a view whose mask is empty is an error that names it.  The crop rectangle is image_cropping's host arithmetic
+ * (bodyfitting_amd/genebody.py); bf_views_prepare takes the rectangle numpy slicing reads, rects[n][4] = (top, left, bottom, right)
+ * with 0 <= top < bottom <= H and 0 <= left < right <= W, uploads only the rows top..bottom of each images[i] ([H][W][3] uint8, RGB), per
+ * view, writes cv2.resize((img * (msk > 128)[..., None])[top:bottom, left:right], (L, L)) to out_images[n][L][L][3], the mask crop
+ * resized the same way to out_masks[i] ([n][L][L]; only where mask_view[i] != 0), and sums[i] = the integer sum of view i's
+ * resized bytes (np.mean(img) > 10 <=> sums[i] > 30 L^2).  Both resizes are INTER_LINEAR in OpenCV's 8-bit fixed-point arithmetic
+ * (the app passes its INTER_CUBIC / INTER_NEAREST as the positional dst).  Buffers start at the sizes given to create and grow. */
+typedef struct bf_views bf_views;
+int bf_views_create(int device, int max_views, int max_h, int max_w, int L, bf_views **out);
+void bf_views_destroy(bf_views *v);
+int bf_views_bbox(bf_views *v, int n, int H, int W, const uint8_t *const *masks, int *bbox);
+int bf_views_prepare(bf_views *v, int n, const int *rects, const uint8_t *const *images, const int *mask_view, uint8_t *out_images,
+                     uint8_t *out_masks, int64_t *sums);
+/* device time of the last calls from HIP events on the object's stream: ms[6] = bbox (mask upload, kernels, download), prepare (crop
+ * upload, kernel, download); bytes[3] = masks up, crops (+ job table) up, results down */
+int bf_views_last_timing(bf_views *v, float *ms, int64_t *bytes);
+
 /* Device time of the kernels of the last bf_fit on this batch, from HIP events on the batch's
  * stream: ms[0] = fit loop kernel(s), ms[1] = final full-mesh forward kernel, ms[2] = joints kernel +
  * result fetch, ms[3] = whole call.  (With BF_FIT_DENSE every iteration's mesh pass is inside ms[0].) */
