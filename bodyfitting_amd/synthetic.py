@@ -162,10 +162,13 @@ def load_template(model_type, nv):
     return d["verts"].astype(np.float64), d["faces"].astype(np.int32)
 
 
-def skinning_weights(verts, prims, nj, top=4):
+def skinning_weights(verts, prims, nj, top=4, floor=None):
     """[nv,nj] with `top` non-zeros per row: joint i's pull on a vertex falls off with the vertex's distance to the SURFACE of the
     round cones joint i moves, measured against the nearest cone's - so a vertex of the inner left thigh belongs to the left leg
-    although the right leg's bone is as close - over a blend width of 0.3 x the local limb radius."""
+    although the right leg's bone is as close - over a blend width of 0.3 x the local limb radius.
+    floor=None (every default model): the kept weights below 1e-4 of the largest are cut, so a row may keep fewer than `top`.
+    floor=x: `top` may also be one count per vertex; the kept weights are raised to at least x before the rows are normalised, so
+    every row has exactly its count of non-zeros (also where the count reaches a joint with no pull at all, as SMPL-X's eyes)."""
     nv = len(verts)
     d = np.full((nv, nj), 1.0e3)
     r_near = np.full(nv, 0.02)
@@ -181,6 +184,13 @@ def skinning_weights(verts, prims, nj, top=4):
         d_near = np.where(take, dp, d_near)
         r_near = np.where(take, r, r_near)
     w = np.exp(-(d - d.min(1, keepdims=True)) / (0.3 * r_near)[:, None])
+    if floor is not None:
+        order = np.argsort(-w, axis=1, kind="stable")
+        counts = np.broadcast_to(np.asarray(top), (nv,))
+        ranked = np.where(np.arange(nj)[None] < counts[:, None], np.maximum(np.take_along_axis(w, order, 1), floor), 0.0)
+        out = np.zeros_like(w)
+        np.put_along_axis(out, order, ranked, 1)
+        return out / out.sum(1, keepdims=True)
     keep = np.argsort(-w, axis=1, kind="stable")[:, :top]
     out = np.zeros_like(w)
     np.put_along_axis(out, keep, np.take_along_axis(w, keep, 1), 1)
@@ -211,8 +221,26 @@ def make_gmm(seed=0, n_comp=8, dim=69):
     return {"means": means, "covars": covars, "weights": weights}
 
 
-def make_model(model_type="smpl", seed=0, nv=None):
-    """Synthetic body model with the tensor layout of smplx 0.1.13."""
+WIDE_FLOOR = 1e-3        # the least weight a bone of a widened skinning row keeps (of the row's largest, before normalising)
+
+
+def bone_counts(nv, bones):
+    """bones per vertex: an int for every vertex, or (lo, hi) - vertex v gets hi - v % (hi - lo + 1), so both ends occur and
+    neighbouring rows differ in width (rows padded to the kernels' sparse width, and rows that fill it)"""
+    if np.ndim(bones) == 0:
+        lo = hi = int(bones)
+    else:
+        lo, hi = (int(b) for b in bones)
+    if not 1 <= lo <= hi:
+        raise ValueError(f"bones={bones!r}: need 1 <= lo <= hi")
+    return hi - np.arange(nv) % (hi - lo + 1)
+
+
+def make_model(model_type="smpl", seed=0, nv=None, bones=4, wide=None):
+    """Synthetic body model with the tensor layout of smplx 0.1.13.
+    bones: non-zero skinning weights per vertex - 4 (the default: the rows every golden was made from, which keep at most 4), an
+    exact count for every vertex, or a (lo, hi) range (bone_counts); wide: {vertex: bones} rows widened on top of that.  A widened
+    row keeps exactly its count (skinning_weights(floor=WIDE_FLOOR)); everything but lbs_weights is the same whatever the width."""
     rng = np.random.default_rng(seed)
     if model_type == "smpl":
         parents, rest = SMPL_PARENTS, _SMPL_REST.copy()
@@ -229,8 +257,16 @@ def make_model(model_type="smpl", seed=0, nv=None):
     # template: one closed genus-0 surface of a human's area with near-uniform triangles (tools/make_template.py)
     verts, faces = load_template(model_type, nv)
     prims = body_primitives(model_type)
-    # skinning weights: 4 non-zeros per row, smooth across the joints
-    lbs = skinning_weights(verts, prims, nj)
+    # skinning weights: 4 non-zeros per row (or `bones` / `wide`), smooth across the joints
+    if np.max(bone_counts(nv, bones)) > nj or (wide and max(wide.values()) > nj):
+        raise ValueError(f"more bones per vertex than the model's {nj} joints")
+    if np.ndim(bones) == 0 and int(bones) == 4:
+        lbs = skinning_weights(verts, prims, nj)
+    else:
+        lbs = skinning_weights(verts, prims, nj, bone_counts(nv, bones), floor=WIDE_FLOOR)
+    if wide:
+        rows = np.array(sorted(wide), dtype=np.int64)
+        lbs[rows] = skinning_weights(verts[rows], prims, nj, np.array([wide[v] for v in rows.tolist()]), floor=WIDE_FLOOR)
 
     # joint regressor: mean of the 32 template vertices nearest to each rest joint (dense storage)
     jreg = np.zeros((nj, nv))

@@ -1,0 +1,192 @@
+"""Skinning width on the CPU: synthetic.make_model(bones=..., wide=...) gives models with more than four bones per vertex, the default
+model is the one every golden was made from, the oracle's dense LBS equals a per-vertex restatement on wide rows, and `width_class`
+mirrors how derive_tables (csrc/model_api.hip) sorts a model into the kernels' skinning paths - MeshTab::v_nnz (4, 8, 0 = dense)
+and FitTab::sel_nnz (the loss selector rows: 1..8, 0 = dense or none)."""
+import numpy as np
+import pytest
+import torch
+
+from bodyfitting_amd import synthetic as S
+from oracle import smplify_oracle as O
+
+N_LOSS_JOINTS = {"smpl": 25, "smplx": 135}      # the keypoint loss's joints (native.model_desc)
+
+
+def width_class(model):
+    """(v_nnz, sel_nnz) as derive_tables sets them: the most bones of any vertex -> 4 / 8 / 0; the most of the selector vertices
+    the routed keypoint loss reads (none when the loss is dense, more than 32 joints) -> that count if <= BF_SEL_NNZ = 8, else 0"""
+    lw = np.asarray(model["lbs_weights"])
+    nnz = (lw != 0).sum(1)
+    most = int(nnz.max())
+    nl = N_LOSS_JOINTS[model.get("model_type", "smpl")]
+    jm = np.asarray(model["joint_map"])[:nl] if nl <= 32 else np.zeros(0, np.int64)
+    sel = np.asarray(model["selector_ids"])[jm[jm >= lw.shape[1]] - lw.shape[1]]
+    s = int(nnz[sel].max()) if len(sel) else 0
+    return (4 if most <= 4 else 8 if most <= 8 else 0), (s if s <= 8 else 0)
+
+
+def loss_selectors(model):
+    """the selector vertices the SMPL keypoint loss reads (FitTab's selector rows), in joint-map order"""
+    nj = np.asarray(model["lbs_weights"]).shape[1]
+    jm = np.asarray(model["joint_map"])[:N_LOSS_JOINTS["smpl"]]
+    return [int(v) for v in np.asarray(model["selector_ids"])[jm[jm >= nj] - nj]]
+
+
+def quiet_vertex(model):
+    """a vertex no selector and no regressor row touches: widening it moves v_nnz and nothing the fit's selector rows read"""
+    busy = set(np.asarray(model["selector_ids"]).tolist())
+    for k in ("J_regressor_extra", "J_regressor"):
+        if k in model:
+            busy |= set(np.nonzero(np.asarray(model[k]).any(0))[0].tolist())
+    return next(v for v in range(np.asarray(model["v_template"]).shape[0]) if v not in busy)
+
+
+def _edges(faces):
+    f = np.asarray(faces)
+    return np.unique(np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), 1), axis=0)
+
+
+@pytest.fixture(scope="module")
+def wide_smpl():
+    return {b: S.make_model("smpl", bones=b) for b in ((5, 8), (9, 12), 8, 12)}
+
+
+@pytest.mark.parametrize("model_type", ["smpl", "smplx"])
+def test_default_width_is_the_golden_model(model_type):
+    """no option, bones=4 and an empty override are the same arrays, bit for bit: the goldens' model"""
+    a = S.make_model(model_type)
+    for b in (S.make_model(model_type, bones=4), S.make_model(model_type, bones=4, wide={})):
+        assert sorted(a) == sorted(b)
+        for k in a:
+            if k != "model_type":
+                np.testing.assert_array_equal(np.asarray(a[k]), np.asarray(b[k]), err_msg=k)
+    assert (np.asarray(a["lbs_weights"]) != 0).sum(1).max() == 4
+    assert S.model_digest(a) == S.model_digest(S.make_model(model_type, bones=4))
+
+
+def test_wide_rows_have_exactly_the_requested_bones(wide_smpl):
+    """every row keeps exactly its count (no weight lost to a cut after the top-k), sums to 1, and is non-negative; a range gives
+    every count in it; only lbs_weights depends on the width"""
+    base = S.make_model("smpl")
+    for bones, m in wide_smpl.items():
+        lw = np.asarray(m["lbs_weights"], np.float64)
+        nnz = (lw != 0).sum(1)
+        np.testing.assert_array_equal(nnz, S.bone_counts(len(lw), bones), err_msg=str(bones))
+        if isinstance(bones, tuple):
+            assert set(nnz.tolist()) == set(range(bones[0], bones[1] + 1))
+        assert (lw >= 0).all()
+        np.testing.assert_allclose(lw.sum(1), 1.0, atol=1e-6)
+        # the kept weights include the default row's bones with their order of pull (the floor only lifts the smallest)
+        top1 = np.asarray(base["lbs_weights"]).argmax(1)
+        assert np.mean(lw.argmax(1) == top1) > 0.999
+        for k in m:
+            if k not in ("model_type", "lbs_weights"):
+                np.testing.assert_array_equal(np.asarray(m[k]), np.asarray(base[k]), err_msg=k)
+
+
+def test_wide_weights_are_smooth(wide_smpl):
+    """across the template's edges a wide row moves about as much as a default one: the floor adds jumps of ~WIDE_FLOOR where the
+    set of kept bones changes, nothing more"""
+    base = S.make_model("smpl")
+    e = _edges(base["faces"])
+    jump = lambda lw: np.abs(np.asarray(lw, np.float64)[e[:, 0]] - np.asarray(lw, np.float64)[e[:, 1]]).sum(1)    # noqa: E731
+    j0 = jump(base["lbs_weights"])
+    for bones, m in wide_smpl.items():
+        j = jump(m["lbs_weights"])
+        assert np.median(j) <= np.median(j0) + 8 * S.WIDE_FLOOR, bones
+        assert np.percentile(j, 99) <= np.percentile(j0, 99) + 8 * S.WIDE_FLOOR, bones
+        assert j.max() <= j0.max() + 0.05, bones
+
+
+def test_override_widens_only_its_rows():
+    """wide={v: n}: row v has n bones and the largest weights of the default row in the same order; every other row is the default's"""
+    base = S.make_model("smpl")
+    v, s = quiet_vertex(base), loss_selectors(base)[0]
+    m = S.make_model("smpl", wide={v: 9, s: 6})
+    a, b = np.asarray(base["lbs_weights"]), np.asarray(m["lbs_weights"])
+    rest = np.ones(len(a), bool)
+    rest[[v, s]] = False
+    np.testing.assert_array_equal(a[rest], b[rest])
+    assert (b[v] != 0).sum() == 9 and (b[s] != 0).sum() == 6
+    assert b[v].argmax() == a[v].argmax() and b[s].argmax() == a[s].argmax()
+    with pytest.raises(ValueError):
+        S.make_model("smpl", bones=25)
+    with pytest.raises(ValueError):
+        S.make_model("smpl", bones=(6, 5))
+
+
+def test_width_classes_of_the_variants():
+    """the classes the GPU tests rely on (tests/test_gpu_skinning_width.py): no variant lands on the 4-bone path by accident"""
+    base = S.make_model("smpl")
+    assert width_class(base) == (4, 4)
+    assert width_class(S.make_model("smpl", bones=(5, 8)))[0] == 8 and 5 <= width_class(S.make_model("smpl", bones=(5, 8)))[1] <= 8
+    assert width_class(S.make_model("smpl", bones=(9, 12))) == (0, 0)
+    assert width_class(S.make_model("smpl", wide={quiet_vertex(base): 9})) == (0, 4)
+    assert width_class(S.make_model("smpl", wide={loss_selectors(base)[0]: 6})) == (8, 6)
+    assert width_class(S.make_model("smpl", nv=690, bones=(5, 8)))[0] == 8
+    assert width_class(S.make_model("smpl", nv=690, bones=(9, 12))) == (0, 0)
+    # SMPL-X: 135 loss joints - the keypoint loss is dense, the fit has no selector rows (sel_nnz 0 at every width)
+    assert width_class(S.make_model("smplx")) == (4, 0)
+    assert width_class(S.make_model("smplx", bones=(5, 8))) == (8, 0)
+    assert width_class(S.make_model("smplx", bones=(9, 12))) == (0, 0)
+
+
+def _rodrigues(r):
+    """smplx's batch_rodrigues for one joint (the 1e-8 is added to every component before the norm)"""
+    a = np.linalg.norm(r + 1e-8)
+    k = r / a
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * K @ K
+
+
+def lbs_per_vertex(model, betas, full_pose):
+    """fp64 linear blend skinning, one vertex at a time over its non-zero weights: the vertices of one body"""
+    vt, sd = np.asarray(model["v_template"], np.float64), np.asarray(model["shapedirs"], np.float64)
+    pd, jr = np.asarray(model["posedirs"], np.float64), np.asarray(model["J_regressor"], np.float64)
+    lw, parents = np.asarray(model["lbs_weights"], np.float64), np.asarray(model["parents"])
+    nj = lw.shape[1]
+    v_shaped = vt + sd[:, :, :len(betas)] @ betas
+    J = jr @ v_shaped
+    R = [_rodrigues(full_pose[3 * j:3 * j + 3]) for j in range(nj)]
+    feat = np.concatenate([(R[j] - np.eye(3)).reshape(-1) for j in range(1, nj)])
+    v_posed = v_shaped + (feat @ pd).reshape(-1, 3)
+    G = []
+    for j in range(nj):
+        L = np.eye(4)
+        L[:3, :3], L[:3, 3] = R[j], J[j] - (J[parents[j]] if j else 0.0)
+        G.append(L if j == 0 else G[parents[j]] @ L)
+    A = []
+    for j in range(nj):
+        a = G[j].copy()
+        a[:3, 3] -= G[j][:3, :3] @ J[j]
+        A.append(a)
+    out = np.empty_like(v_posed)
+    for v in range(len(vt)):
+        T = np.zeros((4, 4))
+        for j in np.nonzero(lw[v])[0]:
+            T += lw[v, j] * A[j]
+        out[v] = T[:3, :3] @ v_posed[v] + T[:3, 3]
+    return out
+
+
+@pytest.mark.parametrize("model_type,bones", [("smpl", (5, 8)), ("smpl", (9, 12)), ("smplx", (9, 12))])
+def test_oracle_forward_equals_per_vertex_lbs(model_type, bones):
+    """O.smpl_forward / O.smplx_forward (one dense einsum over lbs_weights) on a wide model against the per-vertex loop"""
+    m = S.make_model(model_type, nv=690 if model_type == "smpl" else 1200, bones=bones)
+    tm = O.to_torch_model(m, torch.float64)
+    rng = np.random.default_rng(3)
+    t = lambda x: torch.tensor(np.asarray(x, np.float64)[None])          # noqa: E731
+    betas, orient = rng.normal(0, 0.8, 10), rng.normal(0, 0.6, 3)
+    if model_type == "smpl":
+        pose = rng.normal(0, 0.3, 69)
+        got = O.smpl_forward(tm, t(betas), t(orient), t(pose))["vertices"][0].numpy()
+        full = np.concatenate([orient, pose])
+    else:
+        body, eyes, lh, rh = rng.normal(0, 0.3, 63), rng.normal(0, 0.1, 6), rng.normal(0, 0.5, 6), rng.normal(0, 0.5, 6)
+        r = O.smplx_forward(tm, t(betas), t(orient), t(body), t(eyes[:3]), t(eyes[3:]), t(lh), t(rh))
+        got, full = r["vertices"][0].numpy(), r["full_pose"][0].numpy()
+        np.testing.assert_allclose(full[75:120], lh @ np.asarray(m["left_hand_components"], np.float64) + np.asarray(m["pose_mean"], np.float64)[75:120], atol=1e-12)
+        betas = np.concatenate([betas, np.zeros(np.asarray(m["shapedirs"]).shape[2] - 10)])
+    want = lbs_per_vertex(m, betas, full)
+    np.testing.assert_allclose(got, want, rtol=0, atol=1e-12)
+    assert np.abs(want - np.asarray(m["v_template"])).max() > 0.05                # (a posed body, not the template)
