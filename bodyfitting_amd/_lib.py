@@ -179,6 +179,15 @@ SIGNATURES = {
     "bf_views_prepare": (C.c_int, [_VP, C.c_int, _IP, C.POINTER(C.c_void_p), _IP, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                    C.POINTER(C.c_int64)]),
     "bf_views_last_timing": (C.c_int, [_VP, _FP, C.POINTER(C.c_int64)]),
+    "bf_inpaint_n_weights": (C.c_int64, []),
+    "bf_inpaint_create": (C.c_int, [C.c_int, _FP, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "bf_inpaint_destroy": (None, [_VP]),
+    "bf_inpaint_run": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _FP]),
+    "bf_inpaint_hole_mask": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, _FP, C.POINTER(C.c_uint8)]),
+    "bf_inpaint_texture": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, _FP, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "bf_morph_u8": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "bf_inpaint_select_faces": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, _FP, C.POINTER(C.c_uint8)]),
+    "bf_inpaint_selftest_conv": (C.c_int, [C.c_int] * 7 + [_FP] * 6),
     "bf_batch_debug_dump": (C.c_int, [_VP, _FP, C.c_int]),
     "bf_batch_debug_disp_moment": (C.c_int, [_VP, _FP]),
 }

@@ -21,6 +21,9 @@ The HMR weights of the initial estimate (`hmr.HMR`) are the state dict registere
 The OpenPose body weights (`openpose.OpenPose`) are the state dict registered with `register_openpose(...)`, else the reference's
 `models/body_pose_model.pth` (openpose/infer_openpose.py:53), packed once; the hand weights (`openpose_hand.OpenPoseHand`) likewise
 `register_openpose_hand(...)`, else `models/hand_pose_model.pth`.
+
+The LBAM texture inpainter (`inpaint.Inpainter`, TextureFitting(inpaint=True)) takes the state dict registered with
+`register_inpainter(...)`, else `external/LBAM_NoBN_ParisStreetView.pth` relative to the working directory (texture_fitting.py:189).
 """
 from __future__ import annotations
 
@@ -42,6 +45,13 @@ _OPENPOSE = {}
 OPENPOSE_WEIGHTS = os.path.join("models", "body_pose_model.pth")      # infer_openpose.py:53, relative to the working directory
 _OPENPOSE_HAND = {}
 OPENPOSE_HAND_WEIGHTS = os.path.join("models", "hand_pose_model.pth")  # next to the body weights
+_INPAINTER = {}
+INPAINTER_WEIGHTS = os.path.join("external", "LBAM_NoBN_ParisStreetView.pth")   # texture_fitting.py:189, relative to the working directory
+
+
+class InpainterWeightsMissing(FileNotFoundError, NotImplementedError):
+    """No LBAM weights: the reference's torch.load raises FileNotFoundError here; NotImplementedError as well, for callers that
+    treated TextureFitting(inpaint=True) as unavailable"""
 
 
 def _drop_kid(model_type=None, gender=None):
@@ -235,3 +245,24 @@ def get_openpose_hand(path=None):
                          f"registered with assets.register_openpose_hand(); alternatively pass keypoints=")
     _OPENPOSE_HAND["packed"] = openpose_hand.pack_hand(openpose_hand.load_hand_weights(path))
     return _OPENPOSE_HAND["packed"]
+
+
+def register_inpainter(state_dict):
+    """LBAM inpainting weights held in memory: a state dict with LBAMModel(4, 3)'s keys (`ec1.conv.conv.weight`, ...,
+    `dc7.weight`).  None forgets them.  A missing or unexpected key raises ValueError."""
+    _INPAINTER.clear()
+    if state_dict is not None:
+        from . import inpaint
+        _INPAINTER["packed"] = inpaint.pack(inpaint.match_state(state_dict))
+
+
+def get_inpainter(path=INPAINTER_WEIGHTS):
+    """-> the packed float32 weights for inpaint.Inpainter, read once per process: the registered ones, else `path`"""
+    if "packed" in _INPAINTER:
+        return _INPAINTER["packed"]
+    from . import inpaint
+    if not os.path.exists(path):
+        raise InpainterWeightsMissing(f"no texture inpainter: TextureFitting(inpaint=True) needs {path} (the reference's LBAM "
+                                      f"weights) or weights registered with assets.register_inpainter() (DESIGN.md section 14)")
+    _INPAINTER["packed"] = inpaint.pack(inpaint.load_weights(path))
+    return _INPAINTER["packed"]

@@ -1,1 +1,2 @@
 from .smpl import SMPL  # noqa: F401
+from .inpaint import Inpainter  # noqa: F401

@@ -837,3 +837,28 @@ def make_openpose_hand_weights(seed=0):
         sd[name + ".weight"] = (rng.standard_normal((cout, cin, k, k)) * std).astype(np.float32)
         sd[name + ".bias"] = rng.normal(0.05, 0.05, cout).astype(np.float32)
     return sd
+
+
+def make_lbam_weights(seed=0):
+    """A synthetic LBAM_NoBN state dict (all 79 keys of LBAMModel(4, 3)): He-normal convolutions scaled so the features stay O(1)
+    through the seven levels (the attention maps multiply them by up to `a`), and GaussActivation parameters drawn partly outside
+    GaussActivation.forward's clamp ranges, so the clamp is exercised"""
+    from . import inpaint
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for key, shape in inpaint.expected_keys().items():
+        if len(shape) == 0:
+            g = key.rsplit(".", 1)[1]
+            lo, hi = {"a": (0.8, 2.2), "mu": (-0.2, 1.2), "sigma1": (0.3, 2.4), "sigma2": (0.3, 2.4)}[g]
+            sd[key] = np.float32(rng.uniform(lo, hi))
+            continue
+        transposed = key.startswith("dc")
+        cin = shape[0] if transposed else shape[1]
+        fan_in = cin * 16 / (4 if transposed else 1)          # a transposed 4 x 4, stride 2 output sums 2 x 2 taps per input channel
+        std = np.sqrt(2.0 / fan_in)
+        if "maskConv" in key or "reverseMaskConv" in key:
+            std *= 1.5
+        elif key.startswith("ec") or key.startswith("dc"):
+            std *= 0.7
+        sd[key] = (rng.standard_normal(shape) * std).astype(np.float32)
+    return sd

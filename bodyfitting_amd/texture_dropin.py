@@ -6,6 +6,8 @@
 Files are read by `obj_textures.load_obj` (nr.load_obj), the loop is `texture_fitting.TextureFitting.fit`, every render is
 libbodyfit's (bf_texfit_*).  No torch, neural_renderer or CUDA import on this path.
 
+`TextureFitting(inpaint=True)` runs the LBAM inpainter, its hole mask and post-processing on the GPU (inpaint.Inpainter).
+
 Two things differ from the reference on purpose: `video.mp4` (both places) is not written - there is no video encoder here - and
 `render_texture_mesh(..., pose_only=True)` reads only the `v` lines, so a mesh without textures no longer raises in that mode.
 """
@@ -17,6 +19,7 @@ import sys
 
 import numpy as np
 
+from . import inpaint as IP
 from . import obj_textures as OT
 from . import texture_fitting as TF
 
@@ -192,26 +195,49 @@ def _uv_obj(filename):
 
 def render_texture_map(renderer, objdir, textures=None, morph=False):
     """texture_fitting.py:149-171: the UV-space image of `textures` (default: the renderer's fitted ones) over the UV OBJ `objdir`
-    -> uint8 [H, W, 3] RGB (the reference's to8b)"""
-    if morph:
-        raise NotImplementedError("render_texture_map(morph=True) needs cv2's morphology; the texture loop calls it with morph=False")
+    -> uint8 [H, W, 3] RGB (the reference's to8b).  morph=True: pixels the UV triangles do not cover (depth >= 2) take the 3 x 3
+    erosion of the image, as cv2.erode / cv2.dilate give it (bf_morph_u8)"""
     uv, uv_faces = _uv_obj(objdir)
-    rgb, _ = renderer.render_texture(uv, uv_faces, textures)
-    return to8b(rgb.transpose((1, 2, 0))[:, :, ::-1])
+    rgb, depth = renderer.render_texture(uv, uv_faces, textures)
+    tex_img = to8b(rgb.transpose((1, 2, 0))[:, :, ::-1])
+    if morph:
+        device = renderer.device
+        valid_mask = (depth[:, :, None] < 2).astype(np.uint8)
+        valid_mask2 = IP.morph_u8(IP.MORPH_DILATE, 3, valid_mask[:, :, 0], device)[:, :, None]
+        tex_img2 = IP.morph_u8(IP.MORPH_ERODE, 3, tex_img, device)
+        tex_img = (valid_mask2 - valid_mask) * tex_img2 + valid_mask * tex_img + (1 - valid_mask2) * tex_img2
+    return tex_img
 
 
 class TextureFitting:
-    """smplify/texture_fitting.py:173-301.  inpaint=True raises NotImplementedError (the inpainting CNN is out of scope, DESIGN.md
-    section 9).  `debug` is taken for its truth value (apps/rp_fitting.py passes distutils' `debug` function)."""
+    """smplify/texture_fitting.py:173-301.  inpaint=True resolves the LBAM weights here (`assets.get_inpainter()`: the registered
+    ones, else external/LBAM_NoBN_ParisStreetView.pth; neither raises assets.InpainterWeightsMissing) and runs the network on the
+    GPU, opened on the first `inpaint`.  `debug` is taken for its truth value (apps/rp_fitting.py passes distutils' `debug`
+    function)."""
 
     def __init__(self, smpl_uv_dir, tex_img_size=1024, render_img_size=512, lrate=1e-2, iter_num=200, debug=False, render=True,
                  inpaint=False, logging=False, device=0):
-        if inpaint:
-            raise NotImplementedError("TextureFitting(inpaint=True): the inpainting CNN (models/inpaint.py) is out of scope "
-                                      "(DESIGN.md section 9)")
         self.debug, self.render, self.iter_num, self.lrate = debug, render, iter_num, lrate
         self.tex_img_size, self.img_size, self.is_inpaint, self.logging = tex_img_size, render_img_size, inpaint, logging
         self.smpl_uv_dir, self.device = smpl_uv_dir, device
+        self.inpainter = None
+        if self.is_inpaint:
+            from . import assets
+            self._inpaint_weights = assets.get_inpainter()
+
+    def inpaint(self, img):
+        """texture_fitting.py:191-214 on the GPU: the hole mask of the UV faces with grey samples, Inpainter(img, mask), the uint8
+        round trip and the erode / dilate post-processing -> uint8 [H, W, 3]"""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        uv = load_obj_uv(self.smpl_uv_dir)
+        uv = uv * img.shape[0]
+        if self.inpainter is None:
+            weights = getattr(self, "_inpaint_weights", None)
+            if weights is None:
+                from . import assets
+                weights = assets.get_inpainter()
+            self.inpainter = IP.Inpainter.from_packed(weights, device=self.device)
+        return self.inpainter.texture(img, uv)
 
     def views(self, center, dist):
         """the view of every iteration (:255-263): five rounds of the 18-view ring, then sphere2rot at np.random.uniform(0, pi),
@@ -263,6 +289,9 @@ class TextureFitting:
         textures, losses = fitter.fit(smpl, scan, poses=poses, far=2 * dist, before_step=before_step, after_fit=after_fit)
         if self.debug:
             _no_video(os.path.join(debug_dir, 'video.mp4'))
-        _imwrite(os.path.join(output_dir, "smpl.png"), out['tex_img'])
+        tex_img = out['tex_img']
+        if self.is_inpaint:
+            tex_img = self.inpaint(tex_img)
+        _imwrite(os.path.join(output_dir, "smpl.png"), tex_img)
         self.textures, self.losses = textures, losses
         return textures, losses

@@ -81,7 +81,7 @@ class Renderer:
     def __init__(self, image_size, texture_size, near, far, background=(1.0, 1.0, 1.0), anti_aliasing=True, K=None,
                  orig_size=None, device=0):
         self._lib = _lib.load()
-        self.image_size, self.texture_size = int(image_size), int(texture_size)
+        self.image_size, self.texture_size, self.device = int(image_size), int(texture_size), int(device)
         self.K = np.ascontiguousarray(K if K is not None else
                                       [[image_size, 0.0, image_size // 2], [0.0, image_size, image_size // 2], [0.0, 0.0, 1.0]],
                                       dtype=np.float32).reshape(3, 3)

@@ -525,6 +525,33 @@ int bf_views_prepare(bf_views *v, int n, const int *rects, const uint8_t *const 
  * upload, kernel, download); bytes[3] = masks up, crops (+ job table) up, results down */
 int bf_views_last_timing(bf_views *v, float *ms, int64_t *bytes);
 
+/* ---- LBAM texture inpainting (models/inpaint.py Inpainter, LBAMModel(4, 3); smplify/texture_fitting.py:191-214 inpaint) ------------
+ * The network in fp32 on the exact-fp32 MFMA, NHWC.  Weights are packed by bodyfitting_amd/inpaint.py in the order inpaint_api.hip
+ * lists them (bf_inpaint_n_weights floats, the clamped GaussActivation parameters last).  Images are uint8 [n][H][W][3]; H and W are
+ * multiples of 128 within max_h x max_w and 1 <= n <= max_batch (anything else: BF_ERR_INVALID).  face_uv[n_faces][3][2] float32 are
+ * the UV triangles in pixels (load_obj_uv(...) * H). */
+typedef struct bf_inpaint bf_inpaint;
+int64_t bf_inpaint_n_weights(void);
+int bf_inpaint_create(int device, const float *weights, int64_t n_weights, int max_batch, int max_h, int max_w, bf_inpaint **out);
+void bf_inpaint_destroy(bf_inpaint *h);
+/* Inpainter.__call__ per image: mask 255 = hole (a byte >= 128 counts); out[n][H][W][3] float32, known pixels float32(v / 255) */
+int bf_inpaint_run(bf_inpaint *h, int n, int H, int W, const uint8_t *image, const uint8_t *mask, float *out);
+/* the hole mask of TextureFitting.inpaint: the faces with more than 63 / 6 grey samples, filled as cv2.drawContours(..., -1) fills
+ * them -> mask[H][W][3] (0 / 255); a sample index outside [-size, size) (numpy's IndexError) is BF_ERR_INVALID */
+int bf_inpaint_hole_mask(bf_inpaint *h, int H, int W, const uint8_t *img, int n_faces, const float *face_uv, uint8_t *mask);
+/* the whole of TextureFitting.inpaint on img[H][W][3] -> out[H][W][3]; mask (may be NULL) receives the hole mask */
+int bf_inpaint_texture(bf_inpaint *h, int H, int W, const uint8_t *img, int n_faces, const float *face_uv, uint8_t *out, uint8_t *mask);
+/* cv2.erode (op 0) / cv2.dilate (op 1) with np.ones((k, k)) (odd k <= 31), pixels outside the image ignored, on in[n][H][W][C] */
+int bf_morph_u8(int device, int op, int k, int n, int H, int W, int C, const uint8_t *in, uint8_t *out);
+/* test hook: the face test alone -> selected[n_faces] (0 / 1) */
+int bf_inpaint_select_faces(bf_inpaint *h, int H, int W, const uint8_t *img, int n_faces, const float *face_uv, uint8_t *selected);
+/* test hook: one convolution of the inpainting kernels on host arrays, no epilogue - deconv 0: 4 x 4, stride 2, padding 1 of
+ * x[n][H][W][cin] (cin a multiple of 4) with w packed [16 cin][coutp] in (ky, kx, ci) order -> y[n][H/2][W/2][cout], and with xm / wm
+ * (may be NULL) the second operand of the same launch -> ym; deconv 1: ConvTranspose2d(4, 2, 1) with w packed per phase
+ * [4][4 cin][coutp] -> y[n][2H][2W][cout].  coutp = cout rounded up to 4. */
+int bf_inpaint_selftest_conv(int device, int deconv, int n, int H, int W, int cin, int cout, const float *x, const float *xm, const float *w,
+                             const float *wm, float *y, float *ym);
+
 /* Device time of the kernels of the last bf_fit on this batch, from HIP events on the batch's
  * stream: ms[0] = fit loop kernel(s), ms[1] = final full-mesh forward kernel, ms[2] = joints kernel +
  * result fetch, ms[3] = whole call.  (With BF_FIT_DENSE every iteration's mesh pass is inside ms[0].) */
