@@ -188,6 +188,7 @@ SIGNATURES = {
     "bf_morph_u8": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "bf_inpaint_select_faces": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, _FP, C.POINTER(C.c_uint8)]),
     "bf_inpaint_selftest_conv": (C.c_int, [C.c_int] * 7 + [_FP] * 6),
+    "bf_overlay_stamp": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _FP, _DP, C.POINTER(C.c_uint8)]),
     "bf_batch_debug_dump": (C.c_int, [_VP, _FP, C.c_int]),
     "bf_batch_debug_disp_moment": (C.c_int, [_VP, _FP]),
 }

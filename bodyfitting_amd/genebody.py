@@ -321,7 +321,33 @@ def write_png(path, img):
     Image.fromarray(np.asarray(img)).save(path)
 
 
-class runner:
+class Detection:
+    """the `openpose` task on the GPU, shared by the GeneBody and RenderPeople runners: the estimators (`_openpose`, and
+    `_openpose_hand` when `use_hand_face`) are made on `device` at the first call and kept for the run"""
+    _openpose = _openpose_hand = None
+
+    def detect_and_write(self, images, use_frames, wrt_dir):
+        """openpose.bin --image_dir --write_json [--hand] on the GPU: view use_frames[i]'s image (RGB) flipped to BGR, as openpose.bin
+        reads the PNG, detected, and written to wrt_dir/<view %02d>_keypoints.json"""
+        from . import openpose as O
+        if not images:
+            return
+        bgr = np.ascontiguousarray(np.stack([np.asarray(im)[:, :, ::-1] for im in images]))     # what openpose.bin reads from the PNG
+        H, W = bgr.shape[1:3]
+        if self._openpose is None:
+            self._openpose = O.OpenPose(device=self.device, max_batch=4, max_h=max(H, 1024), max_w=max(W, 1024))
+        if self.use_hand_face:
+            from . import openpose_hand as OH
+            if self._openpose_hand is None:
+                self._openpose_hand = OH.OpenPoseHand(device=self.device, max_hands=16, max_h=max(H, 1024), max_w=max(W, 1024))
+            people, write = OH.detect_people(self._openpose, self._openpose_hand, bgr), OH.write_json
+        else:
+            people, write = self._openpose.pose25(bgr), O.write_json
+        for view, p in zip(use_frames, people):
+            write(os.path.join(wrt_dir, '%02d_keypoints.json' % view), p)
+
+
+class runner(Detection):
     """genebody_fitting.py:61-215 with the GPU stages.  `prep`: the view-preparation object (default a ViewPrep on --device)."""
 
     def __init__(self, args, prep=None):
@@ -405,23 +431,7 @@ class runner:
         os.makedirs(wrt_dir, exist_ok=True)
         if len([dir_ for dir_ in os.listdir(wrt_dir) if '.json' in dir_]) >= len(data[0]):
             return
-        from . import openpose as O
-        images, use_frames = data[0], data[4]
-        if not images:
-            return
-        bgr = np.ascontiguousarray(np.stack([np.asarray(im)[:, :, ::-1] for im in images]))     # what openpose.bin reads from the PNG
-        H, W = bgr.shape[1:3]
-        if self._openpose is None:
-            self._openpose = O.OpenPose(device=self.device, max_batch=4, max_h=max(H, 1024), max_w=max(W, 1024))
-        if self.use_hand_face:
-            from . import openpose_hand as OH
-            if self._openpose_hand is None:
-                self._openpose_hand = OH.OpenPoseHand(device=self.device, max_hands=16, max_h=max(H, 1024), max_w=max(W, 1024))
-            people, write = OH.detect_people(self._openpose, self._openpose_hand, bgr), OH.write_json
-        else:
-            people, write = self._openpose.pose25(bgr), O.write_json
-        for view, p in zip(use_frames, people):
-            write(os.path.join(wrt_dir, '%02d_keypoints.json' % view), p)
+        self.detect_and_write(data[0], data[4], wrt_dir)
 
     def read_openpose(self, frame):
         from .io import load_openpose

@@ -552,6 +552,14 @@ int bf_inpaint_select_faces(bf_inpaint *h, int H, int W, const uint8_t *img, int
 int bf_inpaint_selftest_conv(int device, int deconv, int n, int H, int W, int cin, int cout, const float *x, const float *xm, const float *w,
                              const float *wm, float *y, float *ym);
 
+/* ---- fit-check overlay (smplify/body_fitting.py:34-42 check_smpl_fitting) -------------------------------------------------------
+ * n views at once: images[n] -> [H][W][3] uint8 each, verts[nv][3] float32, cams[n][21] double = the rotation R'[3][3] (row-major)
+ * cv2.projectPoints rebuilds from the Rodrigues vector, t[3] and K[3][3].  Every vertex is projected as cv2.projectPoints does with
+ * zero distortion (double, rounded to float32); one with 0 <= x < W and 0 <= y < H is truncated to (int x, int y) and stamped as
+ * cv2.circle(img, (x, y), 1, (0, 255, 0), -1) draws it (the plus of five pixels, clipped at the edges) -> out[n][H][W][3] */
+int bf_overlay_stamp(int device, int n, int H, int W, const uint8_t *const *images, int nv, const float *verts, const double *cams,
+                     uint8_t *out);
+
 /* Device time of the kernels of the last bf_fit on this batch, from HIP events on the batch's
  * stream: ms[0] = fit loop kernel(s), ms[1] = final full-mesh forward kernel, ms[2] = joints kernel +
  * result fetch, ms[3] = whole call.  (With BF_FIT_DENSE every iteration's mesh pass is inside ms[0].) */
