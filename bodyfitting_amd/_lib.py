@@ -65,6 +65,7 @@ SIGNATURES = {
     "bf_batch_dense_resident": (C.c_int, [_VP]),
     "bf_smpl_forward": (C.c_int, [_VP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP]),
     "bf_model_forward": (C.c_int, [_VP, C.c_int, _FP, _FP, _FP]),
+    "bf_smpl_vjp": (C.c_int, [_VP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "bf_batch_create": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(_VP)]),
     "bf_batch_destroy": (None, [_VP]),
     "bf_batch_set_cameras": (C.c_int, [_VP, _FP, _FP]),

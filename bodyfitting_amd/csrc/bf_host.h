@@ -352,6 +352,7 @@ int bf_launch_mesh(bf_model *m, MeshScratch *scr, int n, const float *state_dev,
 int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDev &hd, FrameIO io);
 int bf_dense_loss_grad(bf_batch *b, const bf_hyper &h, const HyperDev &hd, FrameIO io);
 int bf_ensure_dense_buffers(bf_batch *b);
+int bf_ensure_posedirsT_locked(bf_model *m, hipStream_t stream);   // (caller holds m->lazy) posedirsT built on first use
 int bf_masks_finalize(bf_batch *b);      // no-op unless a deferred bf_batch_set_masks is pending
 void bf_masks_commit(bf_batch *b);       // no-op unless bf_batch_stage_masks has staged the next frame's silhouettes
 HyperDev bf_to_dev(const bf_hyper &h);

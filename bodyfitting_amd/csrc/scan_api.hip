@@ -327,6 +327,22 @@ int bf_scan_nearest_backward(bf_scan *s, int n, const int32_t *face_ids, const f
     return BF_OK;
 }
 
+// [3NV][npf] transpose for the reverse pass (thread = pose-feature row, contiguous reads), built on the device once per model: the
+// caller holds the model's lock (bf_model::lazy), and the table is finished before anybody can see the pointer (batches of the model run on
+// other streams).  Used by the dense schedule and by bf_smpl_vjp.
+int bf_ensure_posedirsT_locked(bf_model *m, hipStream_t stream) {
+    if (m->posedirsT.p) return BF_OK;
+    const size_t nv3 = (size_t)m->nv * 3;
+    DevBuf<float> t;
+    HIP_TRY(t.alloc((size_t)nv3 * m->npf));
+    hipLaunchKernelGGL(bf_transpose_kernel, dim3((nv3 + 31) / 32, (m->npf + 31) / 32), dim3(256), 0, stream,
+                       (const float *)m->posedirs.p, m->npf, (int)nv3, t.p, m->mesh.pd_pitch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    m->posedirsT.p = t.p; m->posedirsT.n = t.n; t.p = nullptr;
+    return BF_OK;
+}
+
 int bf_ensure_dense_buffers(bf_batch *b) {
     bf_model *m = b->m;
     const size_t F = b->F, nv3 = (size_t)m->nv * 3;
@@ -342,18 +358,8 @@ int bf_ensure_dense_buffers(bf_batch *b) {
         HIP_TRY(bf_memset_sync(b->ext.p, 0, b->ext.n * sizeof(float)));
     }
     {
-        // [3NV][npf] transpose for the reverse pass (thread = pose-feature row, contiguous reads), built on the device once per
-        // model: under the model's lock and finished before anybody can see the pointer (batches of the model run on other streams)
         std::lock_guard<std::mutex> g(m->lazy);
-        if (!m->posedirsT.p) {
-            DevBuf<float> t;
-            HIP_TRY(t.alloc((size_t)nv3 * m->npf));
-            hipLaunchKernelGGL(bf_transpose_kernel, dim3((nv3 + 31) / 32, (m->npf + 31) / 32), dim3(256), 0, b->stream,
-                               (const float *)m->posedirs.p, m->npf, (int)nv3, t.p, m->mesh.pd_pitch);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(b->stream));
-            m->posedirsT.p = t.p; m->posedirsT.n = t.n; t.p = nullptr;
-        }
+        { int rt = bf_ensure_posedirsT_locked(m, b->stream); if (rt) return rt; }
         for (bf_model::Sub *U : {&m->sub, &m->sub_kp}) {
             if (!U->on || U->posedirsT.p) continue;
             const size_t sv3 = (size_t)U->mesh.nv * 3;

@@ -119,6 +119,25 @@ class DeviceModel:
                                              _lib.fptr(verts), _lib.fptr(joints), _lib.fptr(jori)), "bf_smpl_forward")
         return verts, joints, jori
 
+    def vjp(self, betas, global_orient, body_pose, dverts=None, djoints=None, djoints_ori=None):
+        """The backward of `forward` (bf_smpl_vjp): cotangents of vertices[n,NV,3], joints[n,n_joint_map,3] and
+        joints_ori[n,NJ+n_selector,3] (None = zero) -> dbetas[n,NB], dglobal_orient[n,3], dbody_pose[n,3(NJ-1)].
+        SMPL-kind models only."""
+        betas = _f32(betas, (-1, self.n_betas))
+        n = betas.shape[0]
+        orient = _f32(global_orient, (n, 3))
+        pose = _f32(body_pose, (n, 3 * (self.n_joints - 1)))
+        dv = None if dverts is None else _f32(dverts, (n, self.n_verts, 3))
+        dj = None if djoints is None else _f32(djoints, (n, self.n_joint_map, 3))
+        djo = None if djoints_ori is None else _f32(djoints_ori, (n, self.n_joints + self.n_selector, 3))
+        dbetas = np.empty((n, self.n_betas), np.float32)
+        dorient = np.empty((n, 3), np.float32)
+        dpose = np.empty((n, 3 * (self.n_joints - 1)), np.float32)
+        _lib.check(self._lib.bf_smpl_vjp(self._h, n, _lib.fptr(betas), _lib.fptr(orient), _lib.fptr(pose), _lib.fptr(dv),
+                                         _lib.fptr(dj), _lib.fptr(djo), _lib.fptr(dbetas), _lib.fptr(dorient), _lib.fptr(dpose)),
+                   "bf_smpl_vjp")
+        return dbetas, dorient, dpose
+
     def forward_packed(self, params):
         """vertices / joints (model space) of packed parameter vectors [n, n_params] - any model kind"""
         p = _f32(params, (-1, self.n_params))

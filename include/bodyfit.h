@@ -146,6 +146,16 @@ int bf_model_fit_instance(const bf_model *m);
 int bf_smpl_forward(bf_model *m, int n, const float *betas, const float *global_orient,
                     const float *body_pose, float *vertices, float *joints, float *joints_ori);
 
+/* models.smpl.SMPL.forward's vector-Jacobian product: the backward torch.autograd runs through smplx's lbs() and the
+ * wrapper of models/smpl.py:69-83, for `n` parameter sets betas[n,NB], global_orient[n,3], body_pose[n,3(NJ-1)].
+ * Cotangents dvertices[n,NV,3], djoints[n,n_joint_map,3], djoints_ori[n,NJ+n_selector,3] (any may be NULL = zero) ->
+ * dbetas[n,NB], dglobal_orient[n,3], dbody_pose[n,3(NJ-1)] (any may be NULL = not wanted).  SMPL-kind models only
+ * (SMPL-X: BF_ERR_UNSUPPORTED).  Stateless: the pose state and the pose-blended vertices are recomputed by the call; every
+ * sum has a fixed order, so equal inputs give equal bits. */
+int bf_smpl_vjp(bf_model *m, int n, const float *betas, const float *global_orient, const float *body_pose,
+                const float *dvertices, const float *djoints, const float *djoints_ori,
+                float *dbetas, float *dglobal_orient, float *dbody_pose);
+
 /* The model's forward for `n` packed parameter vectors params[n,n_params] (any model kind): vertices[n,NV,3] in
  * model space and joints[n,n_joint_map,3], both before the similarity (either may be NULL). */
 int bf_model_forward(bf_model *m, int n, const float *params, float *vertices, float *joints);
