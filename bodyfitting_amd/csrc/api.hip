@@ -158,9 +158,10 @@ void bf_use_arena(bf_batch *b, int k) {
     b->cur = k;
 }
 
-// input arena k becomes the one `keypoints`, `params0`, `ndiv` point at (host = true: at its pinned staging buffer itself)
+// input arena k becomes the one `keypoints`, `params0`, `ndiv` point at (host = true: at its pinned staging buffer itself;
+// k >= 2: arena (k - 2) % 2 of fit lane (k - 2) / 2, device side only)
 void bf_use_inputs(bf_batch *b, int k, bool host) {
-    float *base = host ? b->h_in[k] : b->in_dev[k].p;
+    float *base = k >= 2 ? b->lanes[(k - 2) / 2].in_dev[(k - 2) % 2].p : (host ? b->h_in[k] : b->in_dev[k].p);
     const bf_model *m = b->m;
     b->keypoints.slice(base + b->in_off[0], (size_t)b->F * b->V * m->nl_loss * 3);
     b->params0.slice(base + b->in_off[1], (size_t)b->F * m->np);
@@ -215,7 +216,127 @@ int bf_flush_tail(bf_batch *b) {
     return BF_OK;
 }
 
+/* Fit lanes.  A frame-after-frame fit (the tail-aside conditions of fit_impl) is one workgroup per frame on one CU for ~380 us while
+ * the other CUs idle, and the frames of a capture are independent (every call carries BF_FIT_RESET).  With n_lanes > 1 such a fit goes
+ * to the next lane (round robin): a stream of its own with its own Adam moments, result arena, mesh scratch and input arenas, so fit
+ * i + 1 starts on another CU as soon as it is issued while fit i runs.  A lane's stream holds [input transfer] fit, mesh, joints,
+ * hand-over: its own work in order.  Lanes are ordered against each other and against the batch stream by HIP events only
+ * (no device-side waits): lanes that end up sharing a hardware queue run one after another, never hang.
+ *   - Lanes take over (lanes_engage) behind everything on the batch stream.  Every entry point that is not a lane fit or a staging drains
+ *     them first (bf_lanes_drain, from bf_sync_all / bf_guard_arena / fit_impl): it waits for the lane streams and trades the last lane
+ *     fit's result arena and Adam moments for the batch's own - the state the tail-aside path leaves - so that continuing fits,
+ *     setters, reads, the graph and dense paths run exactly as without lanes.
+ *   - bf_batch_stage_inputs fills the next lane's input arena (two per lane, filled alternately) on that lane's stream: the transfer
+ *     is ordered behind the fits that last read the arena - the lane's own by stream order, another lane's (a fit that re-used the
+ *     inputs without a new staging) by its event - and never behind a running fit of another lane.
+ * BF_FIT_LANES=<n> sets the lane count (1: no lanes, the single-stream path); a batch uses at most (CUs / frames) of them. */
+static int fit_lanes_wanted() {
+    static const int d = [] { const char *e = getenv("BF_FIT_LANES"); const int v = e ? atoi(e) : 4; return std::max(1, std::min(v, 32)); }();
+    return d;
+}
+
+static void lanes_release(bf_batch *b) {
+    if (!b->lanes) return;
+    for (int j = 0; j < b->n_lanes; ++j)              // (a lane's fit may read another lane's input arena: all of them first)
+        if (b->lanes[j].stream) (void)hipStreamSynchronize(b->lanes[j].stream);
+    for (int j = 0; j < b->n_lanes; ++j) {
+        BfLane &l = b->lanes[j];
+        if (l.stream) (void)hipStreamDestroy(l.stream);
+        if (l.ev_copied) (void)hipEventDestroy(l.ev_copied);
+        if (l.h_res) (void)hipHostFree(l.h_res);
+        for (int a = 0; a < 2; ++a) {
+            if (l.ev_in[a]) (void)hipEventDestroy(l.ev_in[a]);
+            if (l.h_in[a]) (void)hipHostFree(l.h_in[a]);
+        }
+    }
+    b->lanes.reset();                     // (the lanes' device buffers)
+    if (b->ev_engage) { (void)hipEventDestroy(b->ev_engage); b->ev_engage = nullptr; }
+}
+
+static int lanes_create(bf_batch *b) {
+    if (b->lanes) return BF_OK;
+    const bf_model *m = b->m;
+    const size_t F = b->F, np = m->np, n_res = b->res.n;
+    b->lanes.reset(new BfLane[b->n_lanes]);
+    int least = 0, greatest = 0;
+    bool ok = hipEventCreateWithFlags(&b->ev_engage, hipEventDisableTiming) == hipSuccess &&
+              hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
+    for (int j = 0; j < b->n_lanes && ok; ++j) {
+        BfLane &l = b->lanes[j];
+        // the lane streams on the HIGHEST priority: the runtime keeps a pool of hardware queues per priority (GPU_MAX_HW_QUEUES each),
+        // and in the normal pool the null stream and the batch stream already hold two of four - three lanes there ran as two,
+        // four on the high pool run as four (profiles/fit_lanes.md)
+        ok = hipStreamCreateWithPriority(&l.stream, hipStreamNonBlocking, greatest) == hipSuccess &&
+             hipEventCreateWithFlags(&l.ev_copied, hipEventDisableTiming) == hipSuccess &&
+             l.adam_m.alloc(F * np) == hipSuccess && l.adam_v.alloc(F * np) == hipSuccess && l.vraw.alloc(b->vraw.n) == hipSuccess &&
+             l.xpart.alloc(b->xpart.n) == hipSuccess && l.res.alloc(n_res) == hipSuccess &&
+             hipHostMalloc((void **)&l.h_res, n_res * sizeof(float)) == hipSuccess &&
+             bf_memset_sync(l.res.p, 0, n_res * sizeof(float)) == hipSuccess;
+        if (ok) std::memset(l.h_res, 0, n_res * sizeof(float));
+        for (int a = 0; a < 2 && ok; ++a) {
+            ok = l.in_dev[a].alloc(b->in_total) == hipSuccess && bf_memset_sync(l.in_dev[a].p, 0, b->in_total * sizeof(float)) == hipSuccess &&
+                 hipHostMalloc((void **)&l.h_in[a], b->in_total * sizeof(float)) == hipSuccess &&
+                 hipEventCreateWithFlags(&l.ev_in[a], hipEventDisableTiming) == hipSuccess;
+        }
+    }
+    if (!ok) { lanes_release(b); return fail(BF_ERR_HIP, "fit lanes: creating a lane's stream or buffers failed"); }
+    return BF_OK;
+}
+
+// the lanes take over behind everything on the batch stream (the inputs, parameters and cameras set there): a lane's stream waits for
+// that point before its first work of the period (lane_begin)
+static int lanes_engage(bf_batch *b) {
+    if (b->lanes_on) return BF_OK;
+    { int rc = lanes_create(b); if (rc) return rc; }
+    { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
+    HIP_TRY(hipEventRecord(b->ev_engage, b->stream));
+    for (int j = 0; j < b->n_lanes; ++j) b->lanes[j].need_engage = true;
+    b->lanes_on = true;
+    return BF_OK;
+}
+
+static int lane_begin(bf_batch *b, BfLane &l) {
+    if (l.need_engage) { HIP_TRY(hipStreamWaitEvent(l.stream, b->ev_engage, 0)); l.need_engage = false; }
+    l.busy = true;
+    return BF_OK;
+}
+
+int bf_lanes_drain(bf_batch *b) {
+    if (!b->lanes_on) return BF_OK;
+    b->lanes_on = false;
+    for (int j = 0; j < b->n_lanes; ++j)
+        if (b->lanes[j].busy) { HIP_TRY(hipStreamSynchronize(b->lanes[j].stream)); b->lanes[j].busy = false; }
+    const int j = b->lane_last;
+    b->lane_last = -1;
+    if (j < 0) return BF_OK;              // (inputs staged, no lane fit since the lanes took over)
+    // The last lane fit lands where the tail-aside path leaves a fit - in the result arena the previous fit did not use, with its Adam
+    // moments as the batch's - by trading buffers: the lane takes the batch's arena k and moments (its next fit overwrites them), no
+    // copy.  Nothing on the device uses either side any more (the lane waited for the batch stream before its fit and has finished;
+    // a pipelined fetch of arena k is waited for here); the graphs captured with the old addresses are dropped.
+    BfLane &l = b->lanes[j];
+    { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
+    const int k = b->cur ^ 1;
+    if (b->copy_pending[k]) { HIP_TRY(hipEventSynchronize(b->ev_copied[k])); b->copy_pending[k] = false; }
+    std::swap(k ? b->res_b.p : b->res.p, l.res.p);
+    std::swap(k ? b->h_res_b : b->h_res, l.h_res);
+    std::swap(b->adam_m.p, l.adam_m.p);
+    std::swap(b->adam_v.p, l.adam_v.p);
+    if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
+    for (auto &g : b->graph_pipe) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    bf_use_arena(b, k);
+    b->arena_seq[k] = l.seq;
+    b->arena_fetched[k] = l.fetched;
+    b->arena_has_v[k] = l.has_v;
+    l.seq = -1;                           // (the lane now holds the batch's old arena)
+    l.fetched = l.has_v = false;
+    return BF_OK;
+}
+
+// bf_batch_stage_inputs on a batch with lanes: the next lane's other input arena, its transfer on that lane's stream
+static int stage_lane(bf_batch *b, const float *keypoints, const int32_t *n_use_frames, const float *init_betas, const float *init_pose);
+
 int bf_sync_all(bf_batch *b) {
+    { int rl_ = bf_lanes_drain(b); if (rl_) return rl_; }
     { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
     if (b->copy_stream) HIP_TRY(hipStreamSynchronize(b->copy_stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -233,6 +354,7 @@ int bf_sync_all(bf_batch *b) {
 }
 
 int bf_guard_arena(bf_batch *b) {
+    { int rl_ = bf_lanes_drain(b); if (rl_) return rl_; }
     { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
     if (b->copy_pending[b->cur]) {
         HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_copied[b->cur], 0));
@@ -314,6 +436,13 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
     }
     if (!ok) { bf_batch_destroy(b); return fail(BF_ERR_HIP, "bf_batch_create: device allocation failed"); }
     b->fit_smem = smem;
+    {
+        // fit lanes (created on first use): one frame's fit per CU, so at most CUs / frames of them; not with the bring-up staging modes
+        int n_cus = 0;
+        (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, m->device);
+        const int d = std::min(fit_lanes_wanted(), std::max(n_cus, 1) / n_frames);
+        b->n_lanes = (b->stage_mode == 0 && d > 1) ? d : 1;
+    }
     *out = b;
     return BF_OK;
 }
@@ -321,6 +450,7 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
 void bf_batch_destroy(bf_batch *b) {
     if (!b) return;
     b->tail_k = -1;                       // (a tail never enqueued: nobody will read that result)
+    lanes_release(b);                     // (waits for the lanes' work: it reads the batch's inputs, cameras and Adam table)
     if (b->copy_stream) (void)hipStreamSynchronize(b->copy_stream);
     if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
     { std::lock_guard<std::mutex> lk(bf_scan_links()); bf_batch_unlink_scans(b); }      // (its scans outlive it: they forget this batch)
@@ -464,6 +594,7 @@ int bf_batch_stage_inputs(bf_batch *b, const float *keypoints, const int32_t *n_
         for (int f = 0; f < b->F; ++f)
             if (n_use_frames[f] <= 0) return fail(BF_ERR_INVALID, "bf_batch_stage_inputs: n_use_frames must be positive");
     HIP_TRY(hipSetDevice(b->m->device));
+    if (b->n_lanes > 1) return stage_lane(b, keypoints, n_use_frames, init_betas, init_pose);
     const int k = b->in_cur ^ 1;
     if (b->in_pending[k]) {                 // (the transfer of two stagings ago: behind a fit that has long finished)
         HIP_TRY(hipEventSynchronize(b->ev_in[k]));
@@ -510,6 +641,38 @@ int bf_batch_stage_inputs(bf_batch *b, const float *keypoints, const int32_t *n_
         b->in_pending[k] = true;
         bf_use_inputs(b, k, false);
     }
+    b->staged = true;
+    return BF_OK;
+}
+
+static int stage_lane(bf_batch *b, const float *keypoints, const int32_t *n_use_frames, const float *init_betas, const float *init_pose) {
+    { int rc = lanes_engage(b); if (rc) return rc; }
+    const int j = b->lane_next;             // (the lane the next frame-after-frame fit goes to)
+    BfLane &l = b->lanes[j];
+    { int rc = lane_begin(b, l); if (rc) return rc; }
+    const int a = l.in_next;
+    l.in_next ^= 1;
+    if (l.in_pending[a]) {                  // (this buffer's previous transfer: queued on this lane two of its fits ago)
+        HIP_TRY(hipEventSynchronize(l.ev_in[a]));
+        l.in_pending[a] = false;
+    }
+    float *h = l.h_in[a];
+    std::memcpy(h + b->in_off[0], keypoints, (size_t)b->F * b->V * b->m->nl_loss * 3 * sizeof(float));
+    pack_init(b, init_betas, init_pose, h + b->in_off[1]);
+    int *nd = (int *)(h + b->in_off[2]);
+    for (int f = 0; f < b->F; ++f) nd[f] = n_use_frames ? n_use_frames[f] : b->V;
+    // the fits that read arena a since it was last filled: this lane's are ahead in its stream; another lane's (a fit that re-used
+    // the inputs without a staging of its own) is waited for through that lane's last event
+    for (int r = 0; r < b->n_lanes; ++r)
+        if (r != j && ((l.in_readers[a] >> r) & 1u)) HIP_TRY(hipStreamWaitEvent(l.stream, b->lanes[r].ev_copied, 0));
+    l.in_readers[a] = 0;
+    const size_t n4 = b->in_total / 4;
+    hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, l.stream,
+                       (const float4 *)h, (float4 *)l.in_dev[a].p, n4);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(l.ev_in[a], l.stream));
+    l.in_pending[a] = true;
+    bf_use_inputs(b, 2 + 2 * j + a, false);
     b->staged = true;
     return BF_OK;
 }
@@ -623,6 +786,42 @@ static int enqueue_plain(bf_batch *b, int n_iters, const HyperDev &hd, const Fra
 
 static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags);
 
+// a frame-after-frame fit on the next lane: fit, mesh, joints and hand-over of the lane's result arena, in the lane's stream order
+static int lane_fit(bf_batch *b, int n_iters, const HyperDev &hd, bool big_fetch) {
+    bf_model *m = b->m;
+    { int rc = lanes_engage(b); if (rc) return rc; }
+    const int j = b->lane_next;
+    b->lane_next = (j + 1) % b->n_lanes;
+    BfLane &l = b->lanes[j];
+    { int rc = lane_begin(b, l); if (rc) return rc; }
+    b->lane_last = j;
+    l.seq = -1; l.fetched = false; l.has_v = false;             // (bf_fit numbers the lane's result once the whole call went out)
+    b->fetched = false; b->have_result = false;
+    if (b->in_cur >= 2) b->lanes[(b->in_cur - 2) / 2].in_readers[(b->in_cur - 2) % 2] |= 1u << j;
+    float *d = l.res.p;
+    FrameIO io = bf_frame_io(b, false);
+    io.params0 = b->params0.p;                  // re-arm inside the fit kernel
+    io.params = d + b->res_off[0]; io.terms = d + b->res_off[1]; io.state = d + b->res_off[2];
+    io.adam_m = l.adam_m.p; io.adam_v = l.adam_v.p;
+    HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, n_iters, 0, b->adam_tab.p, b->steps_done, b->fit_smem, l.stream, nullptr));
+    int rc = bf_launch_mesh(m, &l.scratch, b->F, io.state, l.vraw.p, d + b->res_off[4], l.xpart.p, d + b->res_off[3], nullptr,
+                            l.stream, nullptr, nullptr);
+    if (rc) return rc;                          // (the lane's result stays unfetched and without a mesh: nothing reads it)
+    if (big_fetch) {
+        HIP_TRY(hipMemcpyAsync(l.h_res, d, b->res.n * sizeof(float), hipMemcpyDeviceToHost, l.stream));
+    } else {
+        const size_t n4 = b->res.n / 4;
+        hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, l.stream,
+                           (const float4 *)d, (float4 *)l.h_res, n4);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(l.ev_copied, l.stream));
+    b->fetched = true;
+    b->have_result = true;
+    b->steps_done += n_iters;
+    return BF_OK;
+}
+
 int bf_fit(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
     if (!b || n_iters <= 0) return fail(BF_ERR_INVALID, "bf_fit: bad argument");
     if (b->scans_lost)
@@ -632,7 +831,7 @@ int bf_fit(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
     bf_masks_commit(b);                       // (silhouettes staged with bf_batch_stage_masks become this fit's)
     int rc = bf_flush_tail(b);
     if (rc) return rc;
-    if (b->in_aside[b->in_cur]) {
+    if (b->in_cur < 2 && b->in_aside[b->in_cur]) {
         // inputs staged aside: their transfer was queued on the second stream a few microseconds ago and runs under the fit in flight.
         // Waiting for it HERE, on the host, keeps a wait packet out of the batch stream (the fit in flight has hundreds of
         // microseconds to go); only if it does not show up in time does the stream wait for it.
@@ -645,7 +844,15 @@ int bf_fit(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
     }
     rc = fit_impl(b, n_iters, hyper, flags);
     if (rc) return rc;
-    b->in_reader[b->in_cur] = b->fit_seq;       // (this fit's number, given to its arena below)
+    if (b->lane_last >= 0) {                  // (went to a lane: every other call drains the lanes first, which clears lane_last)
+        BfLane &l = b->lanes[b->lane_last];
+        l.seq = b->fit_seq++;
+        l.fetched = b->fetched;
+        l.has_v = b->have_result;
+        b->staged = false;
+        return BF_OK;
+    }
+    if (b->in_cur < 2) b->in_reader[b->in_cur] = b->fit_seq;       // (this fit's number, given to its arena below)
     if (b->has_masks) {                       // (the arena these masks live in may be overwritten once this fit is done)
         if (!b->ev_masks_used) HIP_TRY(hipEventCreateWithFlags(&b->ev_masks_used, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(b->ev_masks_used, b->stream));
@@ -664,6 +871,16 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
     bf_hyper h;
     if (hyper) h = *hyper; else bf_hyper_default(&h);
     const bool reset = flags & BF_FIT_RESET;
+    const bool dense_losses = !b->scans.empty() || b->has_masks || m->kp_dense;
+    if (dense_losses) flags &= ~BF_FIT_DENSE;
+    const bool dense = flags & BF_FIT_DENSE, want_v = !(flags & BF_FIT_NO_VERTICES), fetch = flags & BF_FIT_FETCH;
+    // Calls issued back to back without timing records (frame after frame, as the reference's loop does): the fit kernel is a
+    // latency chain of one workgroup per frame, so the mesh / joints / result hand-over of a call runs on the second stream UNDER the
+    // next call's fit kernel; the two result arenas alternate as in the pipelined fetch.  With fit lanes such a call goes to the next
+    // lane instead; every other call first finds the last fit in the batch's own buffers (bf_lanes_drain).
+    const bool tail_aside = (flags & BF_FIT_NOTIME) && !(flags & BF_FIT_GRAPH) && reset && !dense_losses && !dense && fetch && want_v;
+    const bool lane = tail_aside && b->n_lanes > 1;
+    if (!lane) { int rl_ = bf_lanes_drain(b); if (rl_) return rl_; }
     if (reset) { b->steps_done = 0; b->have_result = false; }
     int rc = ensure_adam_tab(b, h, b->steps_done + n_iters);
     if (rc) return rc;
@@ -671,9 +888,6 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
     FrameIO io = bf_frame_io(b, false);
     rc = bf_ensure_fit_image(b, io, hd);          // (once per model: the fit kernel's batched prologue, before any graph captures a launch)
     if (rc) return rc;
-    const bool dense_losses = !b->scans.empty() || b->has_masks || m->kp_dense;
-    if (dense_losses) flags &= ~BF_FIT_DENSE;
-    const bool dense = flags & BF_FIT_DENSE, want_v = !(flags & BF_FIT_NO_VERTICES), fetch = flags & BF_FIT_FETCH;
     b->ev = b->ring.data() + (size_t)(b->ring_n % bf_batch::kRing) * 4;
     for (int k = 0; k < 4; ++k)
         if (!b->ev[k]) HIP_TRY(hipEventCreate(&b->ev[k]));
@@ -681,10 +895,7 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
     // (a small fetch is cheaper as a copy node inside the graph than as a second stream with two event hand-offs)
     const bool big_fetch = (want_v ? b->res.n : b->res_small) * sizeof(float) >= (size_t)512 * 1024;
     const bool pipelined = (flags & BF_FIT_GRAPH) && reset && !dense_losses && !dense && fetch && big_fetch;
-    // Calls issued back to back without timing records (frame after frame, as the reference's loop does): the fit kernel is a
-    // latency chain of one workgroup per frame, so the mesh / joints / result hand-over of a call runs on the second stream UNDER the
-    // next call's fit kernel; the two result arenas alternate as in the pipelined fetch.
-    const bool tail_aside = (flags & BF_FIT_NOTIME) && !(flags & BF_FIT_GRAPH) && reset && !dense_losses && !dense && fetch && want_v;
+    if (lane) return lane_fit(b, n_iters, hd, big_fetch);
     if (!pipelined && !tail_aside) {                // (a pipelined fetch may still be reading the arena this call writes)
         rc = bf_guard_arena(b);
         if (rc) return rc;
@@ -698,7 +909,7 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
             if (rc) return rc;
             { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
         }
-        bf_graph_key key{n_iters, flags, (pipelined ? (b->cur ^ 1) : b->cur) | (b->in_cur << 4) | ((int)b->in_host << 5), h};   // (the captured nodes hold the arenas' addresses)
+        bf_graph_key key{n_iters, flags, (pipelined ? (b->cur ^ 1) : b->cur) | (b->in_cur << 4) | ((int)b->in_host << 12), h};   // (the captured nodes hold the arenas' addresses)
         if (pipelined) {
             // pipelined fetch: this fit writes the result arena the previous one did not use; its device-to-host copy
             // runs on the copy stream, under the kernels of whatever is enqueued next
@@ -889,14 +1100,21 @@ int bf_batch_get_previous(bf_batch *b, float *params, float *vertices, float *jo
     if (!b) return fail(BF_ERR_INVALID, "bf_batch_get_previous: null batch");
     const bf_model *m = b->m;
     HIP_TRY(hipSetDevice(m->device));
-    const int k = b->cur ^ 1;
-    if (b->fit_seq < 2 || b->arena_seq[k] != b->fit_seq - 2 || b->arena_seq[b->cur] != b->fit_seq - 1 || !b->arena_fetched[k])
+    // (while a lane holds the last fit, the batch's current arena holds the fit before it, if that was not a lane fit)
+    const int k = b->lane_last >= 0 ? b->cur : b->cur ^ 1;
+    // with fit lanes the fit before the last may be held by a lane (which keeps it until that lane's next fit)
+    int lane = -1;
+    for (int j = 0; b->lanes && b->fit_seq >= 2 && j < b->n_lanes; ++j)
+        if (b->lanes[j].seq == b->fit_seq - 2) lane = j;
+    const bool last_held = b->lane_last >= 0 ? b->lanes[b->lane_last].seq == b->fit_seq - 1 : b->arena_seq[b->cur] == b->fit_seq - 1;
+    const bool held = lane >= 0 ? b->lanes[lane].fetched : (b->arena_seq[k] == b->fit_seq - 2 && b->arena_fetched[k]);
+    if (b->fit_seq < 2 || !held || !last_held)
         return fail(BF_ERR_INVALID, "bf_batch_get_previous: the previous fit's result is not held in the other arena (both fits need "
                                     "BF_FIT_RESET | BF_FIT_FETCH | BF_FIT_NOTIME on the keypoint-only path)");
-    if ((vertices || joints) && !b->arena_has_v[k]) return fail(BF_ERR_INVALID, "bf_batch_get_previous: no mesh was evaluated");
+    if ((vertices || joints) && !(lane >= 0 ? b->lanes[lane].has_v : b->arena_has_v[k])) return fail(BF_ERR_INVALID, "bf_batch_get_previous: no mesh was evaluated");
     { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
-    HIP_TRY(hipEventSynchronize(b->ev_copied[k]));
-    const float *h = k ? b->h_res_b : b->h_res;
+    HIP_TRY(hipEventSynchronize(lane >= 0 ? b->lanes[lane].ev_copied : b->ev_copied[k]));
+    const float *h = lane >= 0 ? b->lanes[lane].h_res : (k ? b->h_res_b : b->h_res);
     if (params) std::memcpy(params, h + b->res_off[0], b->res_cnt[0] * sizeof(float));
     if (loss_terms) std::memcpy(loss_terms, h + b->res_off[1], b->res_cnt[1] * sizeof(float));
     if (joints) std::memcpy(joints, h + b->res_off[3], b->res_cnt[3] * sizeof(float));
@@ -943,6 +1161,7 @@ int bf_batch_get_result(bf_batch *b, float *vertices, float *joints, float *full
 int bf_batch_export_params_dev(bf_batch *b, void *dst_dev) {
     if (!b || !dst_dev) return fail(BF_ERR_INVALID, "bf_batch_export_params_dev: null argument");
     HIP_TRY(hipSetDevice(b->m->device));
+    { int rl_ = bf_lanes_drain(b); if (rl_) return rl_; }
     HIP_TRY(hipMemcpyAsync(dst_dev, b->params.p, b->params.n * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
     { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
     return BF_OK;

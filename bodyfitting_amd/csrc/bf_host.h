@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -192,6 +193,29 @@ struct bf_model {
 
 struct bf_graph_key { int n_iters; uint32_t flags; int arena; bf_hyper h; };     // (arena: the result arena its nodes point at)
 
+// A fit lane (BF_FIT_LANES, api.hip): everything a frame-after-frame fit (RESET | FETCH | NOTIME, keypoint-only) and its tail write,
+// on a stream of its own, so that consecutive frames' fits run side by side on different CUs.  Successive fits go to successive lanes;
+// nothing orders one lane behind another but HIP events.
+struct BfLane {
+    hipStream_t stream = nullptr;
+    MeshScratch scratch;            // the tail's MFMA mesh path, on this lane's stream only
+    DevBuf<float> adam_m, adam_v, vraw, xpart;
+    DevBuf<float> res;              // result arena [params | terms | state | joints | vout], the batch's layout (res_off / res_cnt)
+    float *h_res = nullptr;         // its pinned mirror (the tail's hand-over)
+    hipEvent_t ev_copied = nullptr; // the lane's last fit, mesh and hand-over have finished
+    long long seq = -1;             // the fit whose result the arena holds (-1: none)
+    bool fetched = false, has_v = false;
+    // two input arenas [keypoints | params0 | ndiv], each fed from its own pinned buffer by a transfer on this lane's stream
+    DevBuf<float> in_dev[2];
+    float *h_in[2] = {nullptr, nullptr};
+    hipEvent_t ev_in[2] = {nullptr, nullptr};   // the transfer out of h_in[a] has finished
+    bool in_pending[2] = {false, false};
+    unsigned in_readers[2] = {0, 0};            // lanes whose fits read arena a since it was last filled (bit per lane)
+    int in_next = 0;                            // arena the next staging into this lane fills
+    bool need_engage = false;                   // the stream has yet to wait for the batch stream (bf_batch::ev_engage)
+    bool busy = false;                          // work was enqueued since the lanes were last drained
+};
+
 struct bf_batch {
     bf_model *m = nullptr;
     int F = 0, V = 0;
@@ -322,6 +346,15 @@ struct bf_batch {
     DevBuf<const float *> scan_fn;
     int disp_steps = 0;
     bool have_disp = false;
+    // fit lanes (api.hip, BF_FIT_LANES): n_lanes > 1 gives frame-after-frame fits lanes of their own, created on first use.
+    // lanes_on: lane work may be in flight or a lane holds the newest fit - every other entry point drains the lanes first
+    // (bf_lanes_drain), which hands the last lane fit back to the batch's own buffers.  in_cur >= 2 names input arena
+    // (in_cur - 2) % 2 of lane (in_cur - 2) / 2.
+    int n_lanes = 1;
+    std::unique_ptr<BfLane[]> lanes;
+    bool lanes_on = false;
+    int lane_next = 0, lane_last = -1;
+    hipEvent_t ev_engage = nullptr;     // recorded on the batch stream when the lanes take over: every lane stream waits for it
 };
 
 struct bf_scan {
@@ -357,7 +390,8 @@ int bf_masks_finalize(bf_batch *b);      // no-op unless a deferred bf_batch_set
 void bf_masks_commit(bf_batch *b);       // no-op unless bf_batch_stage_masks has staged the next frame's silhouettes
 HyperDev bf_to_dev(const bf_hyper &h);
 int bf_flush_tail(bf_batch *b);          // enqueue the deferred mesh / hand-over tail of the last frame-after-frame fit (api.hip)
-int bf_sync_all(bf_batch *b);            // copy stream, then compute stream
+int bf_sync_all(bf_batch *b);            // lanes, copy stream, then compute stream
+int bf_lanes_drain(bf_batch *b);         // no-op unless fit lanes are on: wait for them, hand the last lane fit back to the batch
 int bf_guard_arena(bf_batch *b);         // the compute stream waits for a fetch still reading the current arena
 void bf_use_arena(bf_batch *b, int k);
 void bf_use_inputs(bf_batch *b, int k, bool host);
