@@ -147,9 +147,24 @@ __global__ void __launch_bounds__(256) bf_publish_kernel(const float4 *__restric
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) dst[i] = src[i];
 }
 
+static int publish(hipStream_t stream, float *dst, const float *src, size_t n_floats) {      // (slices are 256-byte multiples: float4 clean)
+    const size_t n4 = n_floats / 4;
+    hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, stream,
+                       (const float4 *)src, (float4 *)dst, n4);
+    HIP_TRY(hipGetLastError());
+    return BF_OK;
+}
+
+// the first n_floats of a result arena go to its pinned mirror: as a copy command (`big`: the caller's choice) or through the kernel above
+static int hand_over(hipStream_t stream, ResultArena &r, size_t n_floats, bool big) {
+    if (!big) return publish(stream, r.host, r.dev.p, n_floats);
+    HIP_TRY(hipMemcpyAsync(r.host, r.dev.p, n_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
+    return BF_OK;
+}
+
 // result arena k becomes the one the DevBuf views and the pinned mirrors point at
-void bf_use_arena(bf_batch *b, int k) {
-    float *d = k ? b->res_b.p : b->res.p, *h = k ? b->h_res_b : b->h_res;
+static void bf_use_arena(bf_batch *b, int k) {
+    float *d = b->arena[k].dev.p, *h = b->arena[k].host;
     b->params.slice(d + b->res_off[0], b->res_cnt[0]); b->terms.slice(d + b->res_off[1], b->res_cnt[1]);
     b->state.slice(d + b->res_off[2], b->res_cnt[2]); b->joints.slice(d + b->res_off[3], b->res_cnt[3]);
     b->vout.slice(d + b->res_off[4], b->res_cnt[4]);
@@ -158,10 +173,13 @@ void bf_use_arena(bf_batch *b, int k) {
     b->cur = k;
 }
 
-// input arena k becomes the one `keypoints`, `params0`, `ndiv` point at (host = true: at its pinned staging buffer itself;
-// k >= 2: arena (k - 2) % 2 of fit lane (k - 2) / 2, device side only)
-void bf_use_inputs(bf_batch *b, int k, bool host) {
-    float *base = k >= 2 ? b->lanes[(k - 2) / 2].in_dev[(k - 2) % 2].p : (host ? b->h_in[k] : b->in_dev[k].p);
+// the input arena an `in_cur` value names: 0 / 1 the batch's own, 2 + 2 * j + a arena a of fit lane j
+static InputArena &input_arena(bf_batch *b, int k) { return k >= 2 ? b->lanes[(k - 2) / 2].in[(k - 2) % 2] : b->in[k]; }
+
+// input arena k becomes the one `keypoints`, `params0`, `ndiv` point at (host = true: at its pinned staging buffer itself)
+static void bf_use_inputs(bf_batch *b, int k, bool host) {
+    InputArena &in = input_arena(b, k);
+    float *base = host ? in.host : in.dev.p;
     const bf_model *m = b->m;
     b->keypoints.slice(base + b->in_off[0], (size_t)b->F * b->V * m->nl_loss * 3);
     b->params0.slice(base + b->in_off[1], (size_t)b->F * m->np);
@@ -180,39 +198,30 @@ static hipError_t write_input(bf_batch *b, void *dst, const void *src, size_t by
 // second stream, behind the fit that filled it.  Every entry point that looks at results, events of the second stream or starts
 // another fit comes through here first (bf_sync_all, bf_fit, bf_batch_get_previous, bf_batch_stage_inputs, bf_batch_destroy).
 static int flush_tail_body(bf_batch *b, int k) {
-    bf_model *m = b->m;
-    HIP_TRY(hipStreamWaitEvent(b->copy_stream, b->ev_done[k], 0));
-    float *d = k ? b->res_b.p : b->res.p;            // (arena k's slices by address: the views may already have moved on)
-    int rc = bf_launch_mesh(m, &b->scratch, b->F, d + b->res_off[2], b->vraw.p, d + b->res_off[4], b->xpart.p, d + b->res_off[3], nullptr,
-                            b->copy_stream, nullptr, nullptr);
-    if (rc) return rc;
-    if (b->tail_big) {
-        HIP_TRY(hipMemcpyAsync(k ? b->h_res_b : b->h_res, d, b->res.n * sizeof(float), hipMemcpyDeviceToHost, b->copy_stream));
-    } else {
-        const size_t n4 = b->res.n / 4;
-        hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, b->copy_stream,
-                           (const float4 *)d, (float4 *)(k ? b->h_res_b : b->h_res), n4);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(b->ev_copied[k], b->copy_stream));
+    ResultArena &r = b->arena[k];
+    HIP_TRY(hipStreamWaitEvent(b->copy_stream, r.ev_done, 0));
+    float *d = r.dev.p;                              // (arena k's slices by address: the views may already have moved on)
+    BF_TRY(bf_launch_mesh(b->m, &b->scratch, b->F, d + b->res_off[2], b->vraw.p, d + b->res_off[4], b->xpart.p, d + b->res_off[3], nullptr,
+                          b->copy_stream, nullptr, nullptr));
+    BF_TRY(hand_over(b->copy_stream, r, b->res_total, b->tail_big));
+    HIP_TRY(hipEventRecord(r.ev_copied, b->copy_stream));
     return BF_OK;
 }
 int bf_flush_tail(bf_batch *b) {
     const int k = b->tail_k;
     if (k < 0) return BF_OK;
     b->tail_k = -1;
+    ResultArena &r = b->arena[k];
     const int rc = flush_tail_body(b, k);
     if (rc) {
-        // the mesh / copy / event of arena k did not all go out: ev_copied[k] still carries its previous (completed) record, so a
+        // the mesh / copy / event of arena k did not all go out: its ev_copied still carries its previous (completed) record, so a
         // wait on it would pass and hand out the pinned buffer's OLD contents.  Nothing of this arena may be read any more:
-        // bf_batch_get_previous (arena_fetched) and bf_batch_get_result (have_result) then fail instead.
-        b->arena_fetched[k] = false;
-        b->arena_has_v[k] = false;
-        b->copy_pending[k] = false;
+        // bf_batch_get_previous (`fetched`) and bf_batch_get_result (have_result) then fail instead.
+        r.fetched = r.has_v = r.copy_pending = false;
         if (k == b->cur) b->have_result = false;
         return rc;
     }
-    b->tail_seq = b->arena_seq[k];
+    b->tail_seq = r.seq;
     return BF_OK;
 }
 
@@ -239,24 +248,16 @@ static void lanes_release(bf_batch *b) {
     if (!b->lanes) return;
     for (int j = 0; j < b->n_lanes; ++j)              // (a lane's fit may read another lane's input arena: all of them first)
         if (b->lanes[j].stream) (void)hipStreamSynchronize(b->lanes[j].stream);
-    for (int j = 0; j < b->n_lanes; ++j) {
-        BfLane &l = b->lanes[j];
-        if (l.stream) (void)hipStreamDestroy(l.stream);
-        if (l.ev_copied) (void)hipEventDestroy(l.ev_copied);
-        if (l.h_res) (void)hipHostFree(l.h_res);
-        for (int a = 0; a < 2; ++a) {
-            if (l.ev_in[a]) (void)hipEventDestroy(l.ev_in[a]);
-            if (l.h_in[a]) (void)hipHostFree(l.h_in[a]);
-        }
-    }
-    b->lanes.reset();                     // (the lanes' device buffers)
+    for (int j = 0; j < b->n_lanes; ++j)
+        if (b->lanes[j].stream) (void)hipStreamDestroy(b->lanes[j].stream);
+    b->lanes.reset();                     // (the lanes' buffers and arenas)
     if (b->ev_engage) { (void)hipEventDestroy(b->ev_engage); b->ev_engage = nullptr; }
 }
 
 static int lanes_create(bf_batch *b) {
     if (b->lanes) return BF_OK;
     const bf_model *m = b->m;
-    const size_t F = b->F, np = m->np, n_res = b->res.n;
+    const size_t F = b->F, np = m->np;
     b->lanes.reset(new BfLane[b->n_lanes]);
     int least = 0, greatest = 0;
     bool ok = hipEventCreateWithFlags(&b->ev_engage, hipEventDisableTiming) == hipSuccess &&
@@ -267,17 +268,9 @@ static int lanes_create(bf_batch *b) {
         // and in the normal pool the null stream and the batch stream already hold two of four - three lanes there ran as two,
         // four on the high pool run as four (profiles/fit_lanes.md)
         ok = hipStreamCreateWithPriority(&l.stream, hipStreamNonBlocking, greatest) == hipSuccess &&
-             hipEventCreateWithFlags(&l.ev_copied, hipEventDisableTiming) == hipSuccess &&
              l.adam_m.alloc(F * np) == hipSuccess && l.adam_v.alloc(F * np) == hipSuccess && l.vraw.alloc(b->vraw.n) == hipSuccess &&
-             l.xpart.alloc(b->xpart.n) == hipSuccess && l.res.alloc(n_res) == hipSuccess &&
-             hipHostMalloc((void **)&l.h_res, n_res * sizeof(float)) == hipSuccess &&
-             bf_memset_sync(l.res.p, 0, n_res * sizeof(float)) == hipSuccess;
-        if (ok) std::memset(l.h_res, 0, n_res * sizeof(float));
-        for (int a = 0; a < 2 && ok; ++a) {
-            ok = l.in_dev[a].alloc(b->in_total) == hipSuccess && bf_memset_sync(l.in_dev[a].p, 0, b->in_total * sizeof(float)) == hipSuccess &&
-                 hipHostMalloc((void **)&l.h_in[a], b->in_total * sizeof(float)) == hipSuccess &&
-                 hipEventCreateWithFlags(&l.ev_in[a], hipEventDisableTiming) == hipSuccess;
-        }
+             l.xpart.alloc(b->xpart.n) == hipSuccess && l.arena.create(b->res_total) == hipSuccess &&
+             l.in[0].create(b->in_total) == hipSuccess && l.in[1].create(b->in_total) == hipSuccess;
     }
     if (!ok) { lanes_release(b); return fail(BF_ERR_HIP, "fit lanes: creating a lane's stream or buffers failed"); }
     return BF_OK;
@@ -287,8 +280,8 @@ static int lanes_create(bf_batch *b) {
 // that point before its first work of the period (lane_begin)
 static int lanes_engage(bf_batch *b) {
     if (b->lanes_on) return BF_OK;
-    { int rc = lanes_create(b); if (rc) return rc; }
-    { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
+    BF_TRY(lanes_create(b));
+    BF_TRY(bf_flush_tail(b));
     HIP_TRY(hipEventRecord(b->ev_engage, b->stream));
     for (int j = 0; j < b->n_lanes; ++j) b->lanes[j].need_engage = true;
     b->lanes_on = true;
@@ -314,21 +307,16 @@ int bf_lanes_drain(bf_batch *b) {
     // copy.  Nothing on the device uses either side any more (the lane waited for the batch stream before its fit and has finished;
     // a pipelined fetch of arena k is waited for here); the graphs captured with the old addresses are dropped.
     BfLane &l = b->lanes[j];
-    { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
+    BF_TRY(bf_flush_tail(b));
     const int k = b->cur ^ 1;
-    if (b->copy_pending[k]) { HIP_TRY(hipEventSynchronize(b->ev_copied[k])); b->copy_pending[k] = false; }
-    std::swap(k ? b->res_b.p : b->res.p, l.res.p);
-    std::swap(k ? b->h_res_b : b->h_res, l.h_res);
+    ResultArena &r = b->arena[k];
+    if (r.copy_pending) { HIP_TRY(hipEventSynchronize(r.ev_copied)); r.copy_pending = false; }
+    r.trade_buffers(l.arena);
     std::swap(b->adam_m.p, l.adam_m.p);
     std::swap(b->adam_v.p, l.adam_v.p);
     if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
     for (auto &g : b->graph_pipe) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     bf_use_arena(b, k);
-    b->arena_seq[k] = l.seq;
-    b->arena_fetched[k] = l.fetched;
-    b->arena_has_v[k] = l.has_v;
-    l.seq = -1;                           // (the lane now holds the batch's old arena)
-    l.fetched = l.has_v = false;
     return BF_OK;
 }
 
@@ -336,11 +324,11 @@ int bf_lanes_drain(bf_batch *b) {
 static int stage_lane(bf_batch *b, const float *keypoints, const int32_t *n_use_frames, const float *init_betas, const float *init_pose);
 
 int bf_sync_all(bf_batch *b) {
-    { int rl_ = bf_lanes_drain(b); if (rl_) return rl_; }
-    { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
+    BF_TRY(bf_lanes_drain(b));
+    BF_TRY(bf_flush_tail(b));
     if (b->copy_stream) HIP_TRY(hipStreamSynchronize(b->copy_stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    b->copy_pending[0] = b->copy_pending[1] = false;
+    b->arena[0].copy_pending = b->arena[1].copy_pending = false;
     if (b->h_door_err && *b->h_door_err) {
         const int who = *b->h_door_err;
         *b->h_door_err = 0;
@@ -354,11 +342,12 @@ int bf_sync_all(bf_batch *b) {
 }
 
 int bf_guard_arena(bf_batch *b) {
-    { int rl_ = bf_lanes_drain(b); if (rl_) return rl_; }
-    { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
-    if (b->copy_pending[b->cur]) {
-        HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_copied[b->cur], 0));
-        b->copy_pending[b->cur] = false;
+    BF_TRY(bf_lanes_drain(b));
+    BF_TRY(bf_flush_tail(b));
+    ResultArena &r = b->arena[b->cur];
+    if (r.copy_pending) {
+        HIP_TRY(hipStreamWaitEvent(b->stream, r.ev_copied, 0));
+        r.copy_pending = false;
     }
     return BF_OK;
 }
@@ -380,13 +369,8 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
         const size_t n_kp = F * n_views * m->nl_loss * 3;
         b->in_off[0] = 0; b->in_off[1] = up(n_kp); b->in_off[2] = b->in_off[1] + up(F * np);
         b->in_total = b->in_off[2] + up(F);
-        if (const char *e = getenv("BF_STAGE_MODE")) b->stage_mode = !strcmp(e, "memcpy") ? 1 : (!strcmp(e, "zerocopy") ? 2 : 0);
-        for (int k = 0; k < 2; ++k) {
-            ok = ok && b->in_dev[k].alloc(b->in_total) == hipSuccess && bf_memset_sync(b->in_dev[k].p, 0, b->in_total * sizeof(float)) == hipSuccess;
-            ok = ok && hipHostMalloc((void **)&b->h_in[k], b->in_total * sizeof(float)) == hipSuccess;
-            ok = ok && hipEventCreateWithFlags(&b->ev_in[k], hipEventDisableTiming) == hipSuccess;
-            if (ok) std::memset(b->h_in[k], 0, b->in_total * sizeof(float));
-        }
+        if (const char *e = getenv("BF_STAGE_MODE")) b->stage_zerocopy = !strcmp(e, "zerocopy");
+        ok = ok && b->in[0].create(b->in_total) == hipSuccess && b->in[1].create(b->in_total) == hipSuccess;
         if (ok) bf_use_inputs(b, 0, false);
     }
     {
@@ -395,9 +379,7 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
                      n_joints = F * m->n_joint_map * 3, n_v = F * m->nv * 3;
         const size_t o_terms = up(n_par), o_state = o_terms + up(n_terms), o_joints = o_state + up(n_state),
                      o_v = o_joints + up(n_joints), total = o_v + up(n_v);
-        ok = ok && b->res.alloc(total) == hipSuccess && b->res_b.alloc(total) == hipSuccess;
-        ok = ok && hipHostMalloc((void **)&b->h_res, total * sizeof(float)) == hipSuccess;
-        ok = ok && hipHostMalloc((void **)&b->h_res_b, total * sizeof(float)) == hipSuccess;
+        ok = ok && b->arena[0].create(total) == hipSuccess && b->arena[1].create(total) == hipSuccess;
         {
             // the second stream on the LOWEST priority: the runtime keeps a pool of hardware queues per priority, so it never shares a
             // queue with a batch's main stream (streams that share one run in order, and the hand-over of a call would no longer run
@@ -406,14 +388,10 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
             ok = ok && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
                  hipStreamCreateWithPriority(&b->copy_stream, hipStreamNonBlocking, least) == hipSuccess;
         }
-        for (int k = 0; k < 2; ++k)
-            ok = ok && hipEventCreateWithFlags(&b->ev_done[k], hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&b->ev_copied[k], hipEventDisableTiming) == hipSuccess;
         if (ok) {
-            ok = bf_memset_sync(b->res.p, 0, total * sizeof(float)) == hipSuccess && bf_memset_sync(b->res_b.p, 0, total * sizeof(float)) == hipSuccess;
             const size_t offs[5] = {0, o_terms, o_state, o_joints, o_v}, cnts[5] = {n_par, n_terms, n_state, n_joints, n_v};
             for (int i = 0; i < 5; ++i) { b->res_off[i] = offs[i]; b->res_cnt[i] = cnts[i]; }
-            b->res_small = o_v;
+            b->res_small = o_v; b->res_total = total;
             bf_use_arena(b, 0);
         }
     }
@@ -421,7 +399,7 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
     if (ok) {
         const std::vector<int> nd(F, n_views);
         for (int k = 0; k < 2; ++k)
-            ok = ok && hipMemcpy(b->in_dev[k].p + b->in_off[2], nd.data(), F * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+            ok = ok && hipMemcpy(b->in[k].dev.p + b->in_off[2], nd.data(), F * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
     }
     ok = ok && b->adam_m.alloc(F * np) == hipSuccess;
     ok = ok && b->adam_v.alloc(F * np) == hipSuccess && b->grads.alloc(F * np) == hipSuccess;
@@ -437,11 +415,11 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
     if (!ok) { bf_batch_destroy(b); return fail(BF_ERR_HIP, "bf_batch_create: device allocation failed"); }
     b->fit_smem = smem;
     {
-        // fit lanes (created on first use): one frame's fit per CU, so at most CUs / frames of them; not with the bring-up staging modes
+        // fit lanes (created on first use): one frame's fit per CU, so at most CUs / frames of them; not with zero-copy staging
         int n_cus = 0;
         (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, m->device);
         const int d = std::min(fit_lanes_wanted(), std::max(n_cus, 1) / n_frames);
-        b->n_lanes = (b->stage_mode == 0 && d > 1) ? d : 1;
+        b->n_lanes = (!b->stage_zerocopy && d > 1) ? d : 1;
     }
     *out = b;
     return BF_OK;
@@ -456,8 +434,6 @@ void bf_batch_destroy(bf_batch *b) {
     { std::lock_guard<std::mutex> lk(bf_scan_links()); bf_batch_unlink_scans(b); }      // (its scans outlive it: they forget this batch)
     if (b->graph_exec) (void)hipGraphExecDestroy(b->graph_exec);
     for (auto &e : b->ring) if (e) (void)hipEventDestroy(e);
-    if (b->h_res) (void)hipHostFree(b->h_res);
-    if (b->h_res_b) (void)hipHostFree(b->h_res_b);
     if (b->h_pc_weight) (void)hipHostFree(b->h_pc_weight);
     if (b->h_masks) (void)hipHostFree(b->h_masks);
     for (float *q : b->mk_retired) (void)hipFree(q);
@@ -469,13 +445,7 @@ void bf_batch_destroy(bf_batch *b) {
     if (b->mk_stage.h_masks) (void)hipHostFree(b->mk_stage.h_masks);
     if (b->mk_stage.h_ccount) (void)hipHostFree(b->mk_stage.h_ccount);
     for (auto &e : b->ev_dense) if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) {
-        if (b->h_in[k]) (void)hipHostFree(b->h_in[k]);
-        if (b->ev_in[k]) (void)hipEventDestroy(b->ev_in[k]);
-        if (b->graph_pipe[k]) (void)hipGraphExecDestroy(b->graph_pipe[k]);
-        if (b->ev_done[k]) (void)hipEventDestroy(b->ev_done[k]);
-        if (b->ev_copied[k]) (void)hipEventDestroy(b->ev_copied[k]);
-    }
+    for (auto &g : b->graph_pipe) if (g) (void)hipGraphExecDestroy(g);
     if (b->copy_stream) (void)hipStreamDestroy(b->copy_stream);
     if (b->fit_stream) { (void)hipStreamSynchronize(b->fit_stream); (void)hipStreamDestroy(b->fit_stream); }
     for (auto &e : b->ev_door) if (e) (void)hipEventDestroy(e);
@@ -522,7 +492,7 @@ int bf_batch_set_cameras(bf_batch *b, const float *c2w, const float *K) {
                     (float)((double)k[r * 3] * w2c[c] + (double)k[r * 3 + 1] * w2c[4 + c] + (double)k[r * 3 + 2] * w2c[8 + c]);
     }
     // bf_fit is asynchronous on the batch's own (non-blocking) stream: a fit still in flight reads these inputs
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     HIP_TRY(hipMemcpy(b->proj.p, proj.data(), proj.size() * sizeof(float), hipMemcpyHostToDevice));
     return BF_OK;
 }
@@ -536,7 +506,7 @@ int bf_batch_set_keypoints(bf_batch *b, const float *keypoints, const int32_t *n
             if (n_use_frames[f] <= 0) return fail(BF_ERR_INVALID, "bf_batch_set_keypoints: n_use_frames must be positive");
             nd[f] = n_use_frames[f];
         }
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }      // (a fit still in flight reads the old keypoints)
+    BF_TRY(bf_sync_all(b));      // (a fit still in flight reads the old keypoints)
     HIP_TRY(write_input(b, b->keypoints.p, keypoints, b->keypoints.n * sizeof(float)));
     HIP_TRY(write_input(b, b->ndiv.p, nd.data(), nd.size() * sizeof(int)));
     return BF_OK;
@@ -556,7 +526,7 @@ static int reset_adam(bf_batch *b, const float *params_host) {
 int bf_batch_reset(bf_batch *b) {
     if (!b) return fail(BF_ERR_INVALID, "bf_batch_reset: null batch");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rg_ = bf_guard_arena(b); if (rg_) return rg_; }
+    BF_TRY(bf_guard_arena(b));
     // (hipMemcpyDefault: with BF_STAGE_MODE=zerocopy params0 is a view into the pinned staging buffer, not device memory)
     HIP_TRY(hipMemcpyAsync(b->params.p, b->params0.p, b->params.n * sizeof(float), hipMemcpyDefault, b->stream));
     HIP_TRY(hipMemsetAsync(b->adam_m.p, 0, b->adam_m.n * sizeof(float), b->stream));
@@ -583,6 +553,21 @@ static void pack_init(const bf_batch *b, const float *init_betas, const float *i
     }
 }
 
+// keypoints | params0 | ndiv of the next frame packed into an input arena's pinned staging buffer, once its previous transfer has left it
+static int pack_staging(const bf_batch *b, InputArena &in, const float *keypoints, const int32_t *n_use_frames, const float *init_betas,
+                        const float *init_pose) {
+    if (in.pending) {
+        HIP_TRY(hipEventSynchronize(in.ev));
+        in.pending = false;
+    }
+    float *h = in.host;
+    std::memcpy(h + b->in_off[0], keypoints, (size_t)b->F * b->V * b->m->nl_loss * 3 * sizeof(float));
+    pack_init(b, init_betas, init_pose, h + b->in_off[1]);
+    int *nd = (int *)(h + b->in_off[2]);
+    for (int f = 0; f < b->F; ++f) nd[f] = n_use_frames ? n_use_frames[f] : b->V;
+    return BF_OK;
+}
+
 /* The next frame's keypoints and initial estimate, WITHOUT draining the work in flight (apps/genebody_fitting.py:183-192 hands
  * SMPLify a new frame's detections and HMR estimate every call; loss.py:160 re-uploads the keypoints every iteration).  The
  * inputs are packed into the pinned staging buffer the fit in flight does not use and their transfer into the other device
@@ -596,82 +581,51 @@ int bf_batch_stage_inputs(bf_batch *b, const float *keypoints, const int32_t *n_
     HIP_TRY(hipSetDevice(b->m->device));
     if (b->n_lanes > 1) return stage_lane(b, keypoints, n_use_frames, init_betas, init_pose);
     const int k = b->in_cur ^ 1;
-    if (b->in_pending[k]) {                 // (the transfer of two stagings ago: behind a fit that has long finished)
-        HIP_TRY(hipEventSynchronize(b->ev_in[k]));
-        b->in_pending[k] = false;
-    }
-    float *h = b->h_in[k];
-    std::memcpy(h + b->in_off[0], keypoints, (size_t)b->F * b->V * b->m->nl_loss * 3 * sizeof(float));
-    pack_init(b, init_betas, init_pose, h + b->in_off[1]);
-    int *nd = (int *)(h + b->in_off[2]);
-    for (int f = 0; f < b->F; ++f) nd[f] = n_use_frames ? n_use_frames[f] : b->V;
-    if (b->stage_mode == 2) {
-        // zero-copy: the fit kernel's prologue reads the pinned buffer itself; bf_fit records ev_in[k] behind the fit that read it
+    InputArena &in = b->in[k];
+    BF_TRY(pack_staging(b, in, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: behind a fit that has long finished)
+    if (b->stage_zerocopy) {
+        // zero-copy: the fit kernel's prologue reads the pinned buffer itself; bf_fit records in.ev behind the fit that read it
         bf_use_inputs(b, k, true);
-    } else {
-        const size_t n4 = b->in_total / 4;
-        b->in_aside[k] = false;
-        if (b->stage_mode == 0 && b->tail_k >= 0 && b->copy_stream && b->in_reader[k] <= b->tail_seq) {
-            // Frame after frame (the fit in flight has its tail still to be enqueued): the transfer goes on the second stream, AHEAD of
-            // that tail, and runs under the fit in flight; the batch stream then holds that fit and the next one back to back (the
-            // transfer in between cost its 4.6 us and a second dispatch gap: ~13 us of a 430 us step).  Arena k was last read by fit
-            // in_reader[k], whose tail - it starts by waiting for that fit - is already on the second stream: the transfer is ordered
-            // behind it.  The fit that reads arena k waits for ev_in[k] (bf_fit: on the host while the fit in flight runs).
-            hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, b->copy_stream,
-                               (const float4 *)h, (float4 *)b->in_dev[k].p, n4);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(b->ev_in[k], b->copy_stream));
-            b->in_pending[k] = true;
-            b->in_aside[k] = true;
-            bf_use_inputs(b, k, false);
-            b->staged = true;
-            return bf_flush_tail(b);
-        }
-        { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
-        if (b->stage_mode == 1) {
-            HIP_TRY(hipMemcpyAsync(b->in_dev[k].p, h, b->in_total * sizeof(float), hipMemcpyHostToDevice, b->stream));
-        } else {
-            // (a kernel that reads the pinned buffer over PCIe with coalesced 16-byte loads: one more dispatch on the queue the fit
-            //  kernel is on, no engine hand-over)
-            hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, b->stream,
-                               (const float4 *)h, (float4 *)b->in_dev[k].p, n4);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(b->ev_in[k], b->stream));
-        b->in_pending[k] = true;
-        bf_use_inputs(b, k, false);
+        b->staged = true;
+        return BF_OK;
     }
+    // Frame after frame (the fit in flight has its tail still to be enqueued): the transfer goes on the second stream, AHEAD of
+    // that tail, and runs under the fit in flight; the batch stream then holds that fit and the next one back to back (the
+    // transfer in between cost its 4.6 us and a second dispatch gap: ~13 us of a 430 us step).  Arena k was last read by fit
+    // in_reader[k], whose tail - it starts by waiting for that fit - is already on the second stream: the transfer is ordered
+    // behind it.  The fit that reads arena k waits for in.ev (bf_fit: on the host while the fit in flight runs).
+    // Otherwise it goes on the batch stream, behind the tail's enqueueing (a kernel that reads the pinned buffer over PCIe with coalesced
+    // 16-byte loads: one more dispatch on the queue the fit kernel is on, no engine hand-over).
+    const bool aside = b->tail_k >= 0 && b->copy_stream && b->in_reader[k] <= b->tail_seq;
+    const hipStream_t stream = aside ? b->copy_stream : b->stream;
+    b->in_aside[k] = false;
+    if (!aside) BF_TRY(bf_flush_tail(b));
+    BF_TRY(publish(stream, in.dev.p, in.host, b->in_total));
+    HIP_TRY(hipEventRecord(in.ev, stream));
+    in.pending = true;
+    b->in_aside[k] = aside;
+    bf_use_inputs(b, k, false);
     b->staged = true;
-    return BF_OK;
+    return aside ? bf_flush_tail(b) : BF_OK;
 }
 
 static int stage_lane(bf_batch *b, const float *keypoints, const int32_t *n_use_frames, const float *init_betas, const float *init_pose) {
-    { int rc = lanes_engage(b); if (rc) return rc; }
+    BF_TRY(lanes_engage(b));
     const int j = b->lane_next;             // (the lane the next frame-after-frame fit goes to)
     BfLane &l = b->lanes[j];
-    { int rc = lane_begin(b, l); if (rc) return rc; }
+    BF_TRY(lane_begin(b, l));
     const int a = l.in_next;
     l.in_next ^= 1;
-    if (l.in_pending[a]) {                  // (this buffer's previous transfer: queued on this lane two of its fits ago)
-        HIP_TRY(hipEventSynchronize(l.ev_in[a]));
-        l.in_pending[a] = false;
-    }
-    float *h = l.h_in[a];
-    std::memcpy(h + b->in_off[0], keypoints, (size_t)b->F * b->V * b->m->nl_loss * 3 * sizeof(float));
-    pack_init(b, init_betas, init_pose, h + b->in_off[1]);
-    int *nd = (int *)(h + b->in_off[2]);
-    for (int f = 0; f < b->F; ++f) nd[f] = n_use_frames ? n_use_frames[f] : b->V;
+    InputArena &in = l.in[a];
+    BF_TRY(pack_staging(b, in, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: queued on this lane two of its fits ago)
     // the fits that read arena a since it was last filled: this lane's are ahead in its stream; another lane's (a fit that re-used
     // the inputs without a staging of its own) is waited for through that lane's last event
     for (int r = 0; r < b->n_lanes; ++r)
-        if (r != j && ((l.in_readers[a] >> r) & 1u)) HIP_TRY(hipStreamWaitEvent(l.stream, b->lanes[r].ev_copied, 0));
-    l.in_readers[a] = 0;
-    const size_t n4 = b->in_total / 4;
-    hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, l.stream,
-                       (const float4 *)h, (float4 *)l.in_dev[a].p, n4);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(l.ev_in[a], l.stream));
-    l.in_pending[a] = true;
+        if (r != j && ((in.readers >> r) & 1u)) HIP_TRY(hipStreamWaitEvent(l.stream, b->lanes[r].arena.ev_copied, 0));
+    in.readers = 0;
+    BF_TRY(publish(l.stream, in.dev.p, in.host, b->in_total));
+    HIP_TRY(hipEventRecord(in.ev, l.stream));
+    in.pending = true;
     bf_use_inputs(b, 2 + 2 * j + a, false);
     b->staged = true;
     return BF_OK;
@@ -683,7 +637,7 @@ int bf_batch_set_init(bf_batch *b, const float *init_betas, const float *init_po
     const bf_model *m = b->m;
     std::vector<float> p((size_t)b->F * m->np, 0.f);
     pack_init(b, init_betas, init_pose, p.data());
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     HIP_TRY(hipMemcpy(b->params.p, p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice));
     return reset_adam(b, p.data());
 }
@@ -691,7 +645,7 @@ int bf_batch_set_init(bf_batch *b, const float *init_betas, const float *init_po
 int bf_batch_set_params(bf_batch *b, const float *params) {
     if (!b || !params) return fail(BF_ERR_INVALID, "bf_batch_set_params: null argument");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     HIP_TRY(hipMemcpy(b->params.p, params, b->params.n * sizeof(float), hipMemcpyHostToDevice));
     return reset_adam(b, params);
 }
@@ -699,7 +653,7 @@ int bf_batch_set_params(bf_batch *b, const float *params) {
 int bf_batch_get_params(bf_batch *b, float *params) {
     if (!b || !params) return fail(BF_ERR_INVALID, "bf_batch_get_params: null argument");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     if (b->fetched) std::memcpy(params, b->h_params, b->params.n * sizeof(float));
     else HIP_TRY(hipMemcpy(params, b->params.p, b->params.n * sizeof(float), hipMemcpyDeviceToHost));
     return BF_OK;
@@ -731,7 +685,7 @@ static int ensure_adam_tab(bf_batch *b, const bf_hyper &h, int upto) {
         tab[(size_t)(t - 1) * 3 + 1] = (float)((double)h.lr / bc1);
         tab[(size_t)(t - 1) * 3 + 2] = (float)std::sqrt(bc2);
     }
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     if (b->adam_tab.p) { (void)hipFree(b->adam_tab.p); b->adam_tab.p = nullptr; }
     HIP_TRY(b->adam_tab.upload(tab));
     b->adam_cap = cap;
@@ -739,7 +693,7 @@ static int ensure_adam_tab(bf_batch *b, const bf_hyper &h, int upto) {
     return BF_OK;
 }
 
-FrameIO bf_frame_io(bf_batch *b, bool want_grads) {
+static FrameIO bf_frame_io(bf_batch *b, bool want_grads) {
     FrameIO io;
     io.n_frames = b->F; io.n_views = b->V;
     io.proj = b->proj.p; io.keypoints = b->keypoints.p; io.ndiv = b->ndiv.p;
@@ -760,27 +714,36 @@ FrameIO bf_frame_io(bf_batch *b, bool want_grads) {
 static int enqueue_plain(bf_batch *b, int n_iters, const HyperDev &hd, const FrameIO &io, bool reset, bool want_v, bool fetch,
                          int adam_t0, hipEvent_t *ev) {
     bf_model *m = b->m;
-    const size_t fb = sizeof(float);
     FrameIO io2 = io;
     if (reset) io2.params0 = b->params0.p;      // re-arm inside the fit kernel: no copy / memset commands
     HIP_TRY(bf_fit_launch(&m->fit, &io2, &hd, n_iters, 0, b->adam_tab.p, adam_t0, b->fit_smem, b->stream, nullptr));
     if (ev) HIP_TRY(hipEventRecord(ev[1], b->stream));
     if (want_v) {
-        int rc = bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream,
-                                ev ? ev[2] : nullptr, nullptr);
-        if (rc) return rc;
+        BF_TRY(bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream,
+                              ev ? ev[2] : nullptr, nullptr));
     } else if (ev) HIP_TRY(hipEventRecord(ev[2], b->stream));
     if (fetch) {
         // one copy of the result arena: [params | terms | state | joints] and, when they were built, the vertices
-        const size_t nfl = want_v ? b->res.n : b->res_small;          // (slices are 256-byte multiples: float4 clean)
-        if (nfl * fb < (size_t)512 * 1024) {
-            const size_t n4 = nfl / 4;
-            hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, b->stream,
-                               (const float4 *)(b->cur ? b->res_b.p : b->res.p), (float4 *)(b->cur ? b->h_res_b : b->h_res), n4);
-            HIP_TRY(hipGetLastError());
-        } else
-        HIP_TRY(hipMemcpyAsync(b->cur ? b->h_res_b : b->h_res, b->cur ? b->res_b.p : b->res.p, nfl * fb, hipMemcpyDeviceToHost, b->stream));
+        const size_t nfl = want_v ? b->res_total : b->res_small;
+        BF_TRY(hand_over(b->stream, b->arena[b->cur], nfl, nfl * sizeof(float) >= (size_t)512 * 1024));
     }
+    return BF_OK;
+}
+
+// `exec` holds a re-armed sparse-schedule call captured for `key`: captured now unless the graph there already is that one
+static int ensure_graph(bf_batch *b, hipGraphExec_t &exec, bf_graph_key &exec_key, const bf_graph_key &key, int n_iters, const HyperDev &hd,
+                        const FrameIO &io, bool want_v, bool fetch) {
+    if (exec && std::memcmp(&key, &exec_key, sizeof key) == 0) return BF_OK;
+    if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
+    hipGraph_t graph = nullptr;
+    HIP_TRY(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue_plain(b, n_iters, hd, io, true, want_v, fetch, 0, nullptr);
+    hipError_t e = hipStreamEndCapture(b->stream, &graph);
+    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    HIP_TRY(e);
+    HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    (void)hipGraphDestroy(graph);
+    exec_key = key;
     return BF_OK;
 }
 
@@ -789,33 +752,27 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
 // a frame-after-frame fit on the next lane: fit, mesh, joints and hand-over of the lane's result arena, in the lane's stream order
 static int lane_fit(bf_batch *b, int n_iters, const HyperDev &hd, bool big_fetch) {
     bf_model *m = b->m;
-    { int rc = lanes_engage(b); if (rc) return rc; }
+    BF_TRY(lanes_engage(b));
     const int j = b->lane_next;
     b->lane_next = (j + 1) % b->n_lanes;
     BfLane &l = b->lanes[j];
-    { int rc = lane_begin(b, l); if (rc) return rc; }
+    BF_TRY(lane_begin(b, l));
     b->lane_last = j;
-    l.seq = -1; l.fetched = false; l.has_v = false;             // (bf_fit numbers the lane's result once the whole call went out)
+    ResultArena &r = l.arena;
+    r.seq = -1; r.fetched = false; r.has_v = false;             // (bf_fit numbers the lane's result once the whole call went out)
     b->fetched = false; b->have_result = false;
-    if (b->in_cur >= 2) b->lanes[(b->in_cur - 2) / 2].in_readers[(b->in_cur - 2) % 2] |= 1u << j;
-    float *d = l.res.p;
+    if (b->in_cur >= 2) input_arena(b, b->in_cur).readers |= 1u << j;
+    float *d = r.dev.p;
     FrameIO io = bf_frame_io(b, false);
     io.params0 = b->params0.p;                  // re-arm inside the fit kernel
     io.params = d + b->res_off[0]; io.terms = d + b->res_off[1]; io.state = d + b->res_off[2];
     io.adam_m = l.adam_m.p; io.adam_v = l.adam_v.p;
     HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, n_iters, 0, b->adam_tab.p, b->steps_done, b->fit_smem, l.stream, nullptr));
-    int rc = bf_launch_mesh(m, &l.scratch, b->F, io.state, l.vraw.p, d + b->res_off[4], l.xpart.p, d + b->res_off[3], nullptr,
-                            l.stream, nullptr, nullptr);
-    if (rc) return rc;                          // (the lane's result stays unfetched and without a mesh: nothing reads it)
-    if (big_fetch) {
-        HIP_TRY(hipMemcpyAsync(l.h_res, d, b->res.n * sizeof(float), hipMemcpyDeviceToHost, l.stream));
-    } else {
-        const size_t n4 = b->res.n / 4;
-        hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, l.stream,
-                           (const float4 *)d, (float4 *)l.h_res, n4);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(l.ev_copied, l.stream));
+    // (a failure from here on: the lane's result stays unfetched and without a mesh, nothing reads it)
+    BF_TRY(bf_launch_mesh(m, &l.scratch, b->F, io.state, l.vraw.p, d + b->res_off[4], l.xpart.p, d + b->res_off[3], nullptr,
+                          l.stream, nullptr, nullptr));
+    BF_TRY(hand_over(l.stream, r, b->res_total, big_fetch));
+    HIP_TRY(hipEventRecord(r.ev_copied, l.stream));
     b->fetched = true;
     b->have_result = true;
     b->steps_done += n_iters;
@@ -829,39 +786,34 @@ int bf_fit(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
     if (b->staged && !(flags & BF_FIT_RESET))
         return fail(BF_ERR_INVALID, "bf_fit: inputs were staged with bf_batch_stage_inputs - the fit of a new frame starts from its initial estimate (BF_FIT_RESET)");
     bf_masks_commit(b);                       // (silhouettes staged with bf_batch_stage_masks become this fit's)
-    int rc = bf_flush_tail(b);
-    if (rc) return rc;
+    BF_TRY(bf_flush_tail(b));
     if (b->in_cur < 2 && b->in_aside[b->in_cur]) {
         // inputs staged aside: their transfer was queued on the second stream a few microseconds ago and runs under the fit in flight.
         // Waiting for it HERE, on the host, keeps a wait packet out of the batch stream (the fit in flight has hundreds of
         // microseconds to go); only if it does not show up in time does the stream wait for it.
+        const hipEvent_t staged = b->in[b->in_cur].ev;
         hipError_t q = hipErrorNotReady;
         const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(500);
-        while ((q = hipEventQuery(b->ev_in[b->in_cur])) == hipErrorNotReady && std::chrono::steady_clock::now() < t_end) { }
-        if (q == hipErrorNotReady) HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_in[b->in_cur], 0));
+        while ((q = hipEventQuery(staged)) == hipErrorNotReady && std::chrono::steady_clock::now() < t_end) { }
+        if (q == hipErrorNotReady) HIP_TRY(hipStreamWaitEvent(b->stream, staged, 0));
         else HIP_TRY(q);
         b->in_aside[b->in_cur] = false;
     }
-    rc = fit_impl(b, n_iters, hyper, flags);
-    if (rc) return rc;
-    if (b->lane_last >= 0) {                  // (went to a lane: every other call drains the lanes first, which clears lane_last)
-        BfLane &l = b->lanes[b->lane_last];
-        l.seq = b->fit_seq++;
-        l.fetched = b->fetched;
-        l.has_v = b->have_result;
-        b->staged = false;
-        return BF_OK;
-    }
-    if (b->in_cur < 2) b->in_reader[b->in_cur] = b->fit_seq;       // (this fit's number, given to its arena below)
-    if (b->has_masks) {                       // (the arena these masks live in may be overwritten once this fit is done)
-        if (!b->ev_masks_used) HIP_TRY(hipEventCreateWithFlags(&b->ev_masks_used, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(b->ev_masks_used, b->stream));
+    BF_TRY(fit_impl(b, n_iters, hyper, flags));
+    // (went to a lane: every other call drains the lanes first, which clears lane_last)
+    ResultArena &r = b->lane_last >= 0 ? b->lanes[b->lane_last].arena : b->arena[b->cur];
+    if (b->lane_last < 0) {
+        if (b->in_cur < 2) b->in_reader[b->in_cur] = b->fit_seq;       // (this fit's number, given to its arena below)
+        if (b->has_masks) {                       // (the arena these masks live in may be overwritten once this fit is done)
+            if (!b->ev_masks_used) HIP_TRY(hipEventCreateWithFlags(&b->ev_masks_used, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(b->ev_masks_used, b->stream));
+        }
+        if (b->in_host) { HIP_TRY(hipEventRecord(b->in[b->in_cur].ev, b->stream)); b->in[b->in_cur].pending = true; }   // (zero-copy: this fit read the pinned buffer)
     }
     b->staged = false;
-    if (b->in_host) { HIP_TRY(hipEventRecord(b->ev_in[b->in_cur], b->stream)); b->in_pending[b->in_cur] = true; }   // (zero-copy: this fit read the pinned buffer)
-    b->arena_seq[b->cur] = b->fit_seq++;
-    b->arena_fetched[b->cur] = b->fetched;
-    b->arena_has_v[b->cur] = b->have_result;
+    r.seq = b->fit_seq++;
+    r.fetched = b->fetched;
+    r.has_v = b->have_result;
     return BF_OK;
 }
 
@@ -880,84 +832,52 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
     // lane instead; every other call first finds the last fit in the batch's own buffers (bf_lanes_drain).
     const bool tail_aside = (flags & BF_FIT_NOTIME) && !(flags & BF_FIT_GRAPH) && reset && !dense_losses && !dense && fetch && want_v;
     const bool lane = tail_aside && b->n_lanes > 1;
-    if (!lane) { int rl_ = bf_lanes_drain(b); if (rl_) return rl_; }
+    if (!lane) BF_TRY(bf_lanes_drain(b));
     if (reset) { b->steps_done = 0; b->have_result = false; }
-    int rc = ensure_adam_tab(b, h, b->steps_done + n_iters);
-    if (rc) return rc;
+    BF_TRY(ensure_adam_tab(b, h, b->steps_done + n_iters));
     HyperDev hd = bf_to_dev(h);
     FrameIO io = bf_frame_io(b, false);
-    rc = bf_ensure_fit_image(b, io, hd);          // (once per model: the fit kernel's batched prologue, before any graph captures a launch)
-    if (rc) return rc;
+    BF_TRY(bf_ensure_fit_image(b, io, hd));       // (once per model: the fit kernel's batched prologue, before any graph captures a launch)
     b->ev = b->ring.data() + (size_t)(b->ring_n % bf_batch::kRing) * 4;
     for (int k = 0; k < 4; ++k)
         if (!b->ev[k]) HIP_TRY(hipEventCreate(&b->ev[k]));
     const size_t fb = sizeof(float);
     // (a small fetch is cheaper as a copy node inside the graph than as a second stream with two event hand-offs)
-    const bool big_fetch = (want_v ? b->res.n : b->res_small) * sizeof(float) >= (size_t)512 * 1024;
+    const bool big_fetch = (want_v ? b->res_total : b->res_small) * sizeof(float) >= (size_t)512 * 1024;
     const bool pipelined = (flags & BF_FIT_GRAPH) && reset && !dense_losses && !dense && fetch && big_fetch;
     if (lane) return lane_fit(b, n_iters, hd, big_fetch);
-    if (!pipelined && !tail_aside) {                // (a pipelined fetch may still be reading the arena this call writes)
-        rc = bf_guard_arena(b);
-        if (rc) return rc;
-    }
+    if (!pipelined && !tail_aside) BF_TRY(bf_guard_arena(b));      // (a pipelined fetch may still be reading the arena this call writes)
     if ((flags & BF_FIT_GRAPH) && reset && !dense_losses && !dense) {
         // the whole call as one hipGraph launch: the host issues a single command per fit
         // the MFMA batch path may grow its scratch buffer: make sure that happened before capturing
         if (want_v && b->F >= BF_MFMA_MIN_FRAMES && b->scratch.pose_off.n < (size_t)b->F * m->nv * 3) {
-            { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
-            rc = bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, nullptr, nullptr);
-            if (rc) return rc;
-            { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+            BF_TRY(bf_sync_all(b));
+            BF_TRY(bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, nullptr, nullptr));
+            BF_TRY(bf_sync_all(b));
         }
-        bf_graph_key key{n_iters, flags, (pipelined ? (b->cur ^ 1) : b->cur) | (b->in_cur << 4) | ((int)b->in_host << 12), h};   // (the captured nodes hold the arenas' addresses)
+        // pipelined fetch: this fit writes the result arena the previous one did not use; its device-to-host copy
+        // runs on the copy stream, under the kernels of whatever is enqueued next
+        const int k = pipelined ? b->cur ^ 1 : b->cur;
+        ResultArena &r = b->arena[k];
+        const bf_graph_key key{n_iters, flags, k | (b->in_cur << 4) | ((int)b->in_host << 12), h};   // (the captured nodes hold the arenas' addresses)
         if (pipelined) {
-            // pipelined fetch: this fit writes the result arena the previous one did not use; its device-to-host copy
-            // runs on the copy stream, under the kernels of whatever is enqueued next
-            const int k = b->cur ^ 1;
-            if (b->copy_pending[k]) { HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_copied[k], 0)); b->copy_pending[k] = false; }
+            if (r.copy_pending) { HIP_TRY(hipStreamWaitEvent(b->stream, r.ev_copied, 0)); r.copy_pending = false; }
             bf_use_arena(b, k);
             io = bf_frame_io(b, false);
-            if (!b->graph_pipe[k] || std::memcmp(&key, &b->graph_pipe_key[k], sizeof key) != 0) {
-                if (b->graph_pipe[k]) { (void)hipGraphExecDestroy(b->graph_pipe[k]); b->graph_pipe[k] = nullptr; }
-                hipGraph_t graph = nullptr;
-                HIP_TRY(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
-                rc = enqueue_plain(b, n_iters, hd, io, true, want_v, false, 0, nullptr);
-                hipError_t e = hipStreamEndCapture(b->stream, &graph);
-                if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-                HIP_TRY(e);
-                HIP_TRY(hipGraphInstantiate(&b->graph_pipe[k], graph, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(graph);
-                b->graph_pipe_key[k] = key;
-            }
-            HIP_TRY(hipEventRecord(b->ev[0], b->stream));
-            HIP_TRY(hipGraphLaunch(b->graph_pipe[k], b->stream));
-            HIP_TRY(hipEventRecord(b->ev[1], b->stream));       // (no events inside a graph: the whole call is charged to ms[0])
-            HIP_TRY(hipEventRecord(b->ev[2], b->stream));
-            HIP_TRY(hipEventRecord(b->ev[3], b->stream));
-            HIP_TRY(hipEventRecord(b->ev_done[k], b->stream));
-            HIP_TRY(hipStreamWaitEvent(b->copy_stream, b->ev_done[k], 0));
-            HIP_TRY(hipMemcpyAsync(k ? b->h_res_b : b->h_res, k ? b->res_b.p : b->res.p, (want_v ? b->res.n : b->res_small) * fb,
-                                   hipMemcpyDeviceToHost, b->copy_stream));
-            HIP_TRY(hipEventRecord(b->ev_copied[k], b->copy_stream));
-            b->copy_pending[k] = true;
-        } else {
-        if (!b->graph_exec || std::memcmp(&key, &b->graph_key, sizeof key) != 0) {
-            if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
-            hipGraph_t graph = nullptr;
-            HIP_TRY(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
-            rc = enqueue_plain(b, n_iters, hd, io, true, want_v, fetch, 0, nullptr);
-            hipError_t e = hipStreamEndCapture(b->stream, &graph);
-            if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-            HIP_TRY(e);
-            HIP_TRY(hipGraphInstantiate(&b->graph_exec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
-            b->graph_key = key;
         }
+        hipGraphExec_t &exec = pipelined ? b->graph_pipe[k] : b->graph_exec;      // (the pipelined graphs hold kernels only)
+        BF_TRY(ensure_graph(b, exec, pipelined ? b->graph_pipe_key[k] : b->graph_key, key, n_iters, hd, io, want_v, fetch && !pipelined));
         HIP_TRY(hipEventRecord(b->ev[0], b->stream));
-        HIP_TRY(hipGraphLaunch(b->graph_exec, b->stream));
+        HIP_TRY(hipGraphLaunch(exec, b->stream));
         HIP_TRY(hipEventRecord(b->ev[1], b->stream));       // (no events inside a graph: the whole call is charged to ms[0])
         HIP_TRY(hipEventRecord(b->ev[2], b->stream));
         HIP_TRY(hipEventRecord(b->ev[3], b->stream));
+        if (pipelined) {
+            HIP_TRY(hipEventRecord(r.ev_done, b->stream));
+            HIP_TRY(hipStreamWaitEvent(b->copy_stream, r.ev_done, 0));
+            BF_TRY(hand_over(b->copy_stream, r, want_v ? b->res_total : b->res_small, true));
+            HIP_TRY(hipEventRecord(r.ev_copied, b->copy_stream));
+            r.copy_pending = true;
         }
         b->fetched = fetch;
         b->ring_n += 1;
@@ -969,9 +889,10 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
     const bool notime = (flags & BF_FIT_NOTIME) && !dense_losses && !dense;
     if (tail_aside) {
         const int k = b->cur ^ 1;
-        if (b->copy_pending[k]) {      // (arena k's hand-over of two calls ago: normally long done - then no wait packet goes into the stream)
-            if (hipEventQuery(b->ev_copied[k]) != hipSuccess) HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_copied[k], 0));
-            b->copy_pending[k] = false;
+        ResultArena &r = b->arena[k];
+        if (r.copy_pending) {          // (arena k's hand-over of two calls ago: normally long done - then no wait packet goes into the stream)
+            if (hipEventQuery(r.ev_copied) != hipSuccess) HIP_TRY(hipStreamWaitEvent(b->stream, r.ev_copied, 0));
+            r.copy_pending = false;
         }
         bf_use_arena(b, k);
         FrameIO io2 = bf_frame_io(b, false);
@@ -979,45 +900,30 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
         static const bool own_signal = [] { const char *e = getenv("BF_FIT_DONE_EVENT"); return !(e && e[0] == '0'); }();
         static const int n_cus = [] { int v = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v > 0 ? v : 256; }();
         const bool crowded = b->F >= n_cus;
-        const bool signal_here = own_signal && !crowded;       // (ev_done[k] completes with the fit's own dispatch: no marker packet between this fit and the next)
-        HIP_TRY(bf_fit_launch(&m->fit, &io2, &hd, n_iters, 0, b->adam_tab.p, b->steps_done, b->fit_smem, b->stream, signal_here ? b->ev_done[k] : nullptr));
+        const bool signal_here = own_signal && !crowded;       // (ev_done completes with the fit's own dispatch: no marker packet between this fit and the next)
+        HIP_TRY(bf_fit_launch(&m->fit, &io2, &hd, n_iters, 0, b->adam_tab.p, b->steps_done, b->fit_smem, b->stream, signal_here ? r.ev_done : nullptr));
         // A batch that fills the machine (a frame's workgroup per CU, one workgroup fits per CU): under the NEXT fit the mesh kernels
         // would only get the CUs that fit's workgroups leave as they finish - measured 379 us for a 33 us GEMM at 256 frames.  The mesh
         // then goes on the fit's own stream, ahead of the next fit (0.462 + 0.074 ms instead of 0.601); only the copy stays aside.
+        if (crowded) BF_TRY(bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, nullptr, nullptr));
+        if (!signal_here) HIP_TRY(hipEventRecord(r.ev_done, b->stream));
         if (crowded) {
-            rc = bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, nullptr, nullptr);
-            if (rc) return rc;
-        }
-        if (!signal_here) HIP_TRY(hipEventRecord(b->ev_done[k], b->stream));
-        if (!crowded) {
+            HIP_TRY(hipStreamWaitEvent(b->copy_stream, r.ev_done, 0));
+            BF_TRY(hand_over(b->copy_stream, r, b->res_total, big_fetch));
+            HIP_TRY(hipEventRecord(r.ev_copied, b->copy_stream));
+        } else {
             // the rest - wait for this fit, mesh, joints, hand-over, on the second stream - is enqueued at the next entry point
             // (bf_flush_tail): a bf_batch_stage_inputs that follows puts the next frame's inputs ahead of it
             b->tail_k = k; b->tail_big = big_fetch;
-            b->copy_pending[k] = true;
-            b->fetched = true;
-            b->steps_done += n_iters;
-            b->have_result = true;
-            return BF_OK;
         }
-        HIP_TRY(hipStreamWaitEvent(b->copy_stream, b->ev_done[k], 0));
-        if (big_fetch) {
-            HIP_TRY(hipMemcpyAsync(k ? b->h_res_b : b->h_res, k ? b->res_b.p : b->res.p, b->res.n * fb, hipMemcpyDeviceToHost, b->copy_stream));
-        } else {
-            const size_t n4 = b->res.n / 4;
-            hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, b->copy_stream,
-                               (const float4 *)(k ? b->res_b.p : b->res.p), (float4 *)(k ? b->h_res_b : b->h_res), n4);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(b->ev_copied[k], b->copy_stream));
-        b->copy_pending[k] = true;
+        r.copy_pending = true;
         b->fetched = true;
         b->steps_done += n_iters;
         b->have_result = true;
         return BF_OK;
     }
     if (notime) {
-        rc = enqueue_plain(b, n_iters, hd, io, reset, want_v, fetch, b->steps_done, nullptr);
-        if (rc) return rc;
+        BF_TRY(enqueue_plain(b, n_iters, hd, io, reset, want_v, fetch, b->steps_done, nullptr));
         b->fetched = fetch;
         b->steps_done += n_iters;
         b->have_result = want_v;
@@ -1025,8 +931,7 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
     }
     HIP_TRY(hipEventRecord(b->ev[0], b->stream));
     if (!dense_losses && !dense) {
-        rc = enqueue_plain(b, n_iters, hd, io, reset, want_v, fetch, b->steps_done, b->ev);
-        if (rc) return rc;
+        BF_TRY(enqueue_plain(b, n_iters, hd, io, reset, want_v, fetch, b->steps_done, b->ev));
     } else {
         if (reset) {
             HIP_TRY(hipMemcpyAsync(b->params.p, b->params0.p, b->params.n * fb, hipMemcpyDefault, b->stream));   // (params0 may be pinned host memory: zero-copy staging)
@@ -1034,27 +939,21 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
             HIP_TRY(hipMemsetAsync(b->adam_v.p, 0, b->adam_v.n * fb, b->stream));
         }
         if (dense_losses) {
-            rc = bf_fit_with_scans(b, n_iters, h, hd, io);
-            if (rc) return rc;
+            BF_TRY(bf_fit_with_scans(b, n_iters, h, hd, io));
             HIP_TRY(hipEventRecord(b->ev[1], b->stream));
             if (want_v) {
-                rc = bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, b->ev[2], nullptr);
-                if (rc) return rc;
+                BF_TRY(bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, b->ev[2], nullptr));
             } else HIP_TRY(hipEventRecord(b->ev[2], b->stream));
         } else {
             // reference-literal schedule: every iteration evaluates the whole mesh (smplify.py:179-190)
             for (int it = 0; it < n_iters; ++it) {
                 HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, 1, 0, b->adam_tab.p, b->steps_done + it, b->fit_smem, b->stream, nullptr));
-                rc = bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, nullptr, nullptr);
-                if (rc) return rc;
+                BF_TRY(bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, nullptr, nullptr));
             }
             HIP_TRY(hipEventRecord(b->ev[1], b->stream));
             HIP_TRY(hipEventRecord(b->ev[2], b->stream));
         }
-        if (fetch) {
-            HIP_TRY(hipMemcpyAsync(b->cur ? b->h_res_b : b->h_res, b->cur ? b->res_b.p : b->res.p,
-                                   ((want_v || dense) ? b->res.n : b->res_small) * fb, hipMemcpyDeviceToHost, b->stream));
-        }
+        if (fetch) BF_TRY(hand_over(b->stream, b->arena[b->cur], (want_v || dense) ? b->res_total : b->res_small, true));      // (always a copy command here)
     }
     b->fetched = fetch;
     HIP_TRY(hipEventRecord(b->ev[3], b->stream));
@@ -1079,7 +978,7 @@ int bf_loss_grad(bf_batch *b, const bf_hyper *hyper, float *terms, float *grads)
     FrameIO io = bf_frame_io(b, true);
     if (m->kp_dense) { rc = bf_dense_loss_grad(b, h, hd, io); if (rc) return rc; }
     else HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, 1, 1, b->adam_tab.p, 0, b->fit_smem, b->stream, nullptr));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     if (terms) HIP_TRY(hipMemcpy(terms, b->terms.p, b->terms.n * sizeof(float), hipMemcpyDeviceToHost));
     if (grads) HIP_TRY(hipMemcpy(grads, b->grads.p, b->grads.n * sizeof(float), hipMemcpyDeviceToHost));
     return BF_OK;
@@ -1088,7 +987,7 @@ int bf_loss_grad(bf_batch *b, const bf_hyper *hyper, float *terms, float *grads)
 int bf_batch_sync(bf_batch *b) {
     if (!b) return fail(BF_ERR_INVALID, "bf_batch_sync: null batch");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     return BF_OK;
 }
 
@@ -1103,18 +1002,17 @@ int bf_batch_get_previous(bf_batch *b, float *params, float *vertices, float *jo
     // (while a lane holds the last fit, the batch's current arena holds the fit before it, if that was not a lane fit)
     const int k = b->lane_last >= 0 ? b->cur : b->cur ^ 1;
     // with fit lanes the fit before the last may be held by a lane (which keeps it until that lane's next fit)
-    int lane = -1;
+    const ResultArena *prev = &b->arena[k];
     for (int j = 0; b->lanes && b->fit_seq >= 2 && j < b->n_lanes; ++j)
-        if (b->lanes[j].seq == b->fit_seq - 2) lane = j;
-    const bool last_held = b->lane_last >= 0 ? b->lanes[b->lane_last].seq == b->fit_seq - 1 : b->arena_seq[b->cur] == b->fit_seq - 1;
-    const bool held = lane >= 0 ? b->lanes[lane].fetched : (b->arena_seq[k] == b->fit_seq - 2 && b->arena_fetched[k]);
-    if (b->fit_seq < 2 || !held || !last_held)
+        if (b->lanes[j].arena.seq == b->fit_seq - 2) prev = &b->lanes[j].arena;
+    const ResultArena &r = *prev, &last = b->lane_last >= 0 ? b->lanes[b->lane_last].arena : b->arena[b->cur];
+    if (b->fit_seq < 2 || r.seq != b->fit_seq - 2 || !r.fetched || last.seq != b->fit_seq - 1)
         return fail(BF_ERR_INVALID, "bf_batch_get_previous: the previous fit's result is not held in the other arena (both fits need "
                                     "BF_FIT_RESET | BF_FIT_FETCH | BF_FIT_NOTIME on the keypoint-only path)");
-    if ((vertices || joints) && !(lane >= 0 ? b->lanes[lane].has_v : b->arena_has_v[k])) return fail(BF_ERR_INVALID, "bf_batch_get_previous: no mesh was evaluated");
-    { int rt_ = bf_flush_tail(b); if (rt_) return rt_; }
-    HIP_TRY(hipEventSynchronize(lane >= 0 ? b->lanes[lane].ev_copied : b->ev_copied[k]));
-    const float *h = lane >= 0 ? b->lanes[lane].h_res : (k ? b->h_res_b : b->h_res);
+    if ((vertices || joints) && !r.has_v) return fail(BF_ERR_INVALID, "bf_batch_get_previous: no mesh was evaluated");
+    BF_TRY(bf_flush_tail(b));
+    HIP_TRY(hipEventSynchronize(r.ev_copied));
+    const float *h = r.host;
     if (params) std::memcpy(params, h + b->res_off[0], b->res_cnt[0] * sizeof(float));
     if (loss_terms) std::memcpy(loss_terms, h + b->res_off[1], b->res_cnt[1] * sizeof(float));
     if (joints) std::memcpy(joints, h + b->res_off[3], b->res_cnt[3] * sizeof(float));
@@ -1133,7 +1031,7 @@ int bf_batch_get_result(bf_batch *b, float *vertices, float *joints, float *full
     if (!b) return fail(BF_ERR_INVALID, "bf_batch_get_result: null batch");
     const bf_model *m = b->m;
     HIP_TRY(hipSetDevice(m->device));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     if ((vertices || joints) && !b->have_result)
         return fail(BF_ERR_INVALID, "bf_batch_get_result: no mesh was evaluated (BF_FIT_NO_VERTICES or no bf_fit yet)");
     if (b->fetched) {
@@ -1161,9 +1059,9 @@ int bf_batch_get_result(bf_batch *b, float *vertices, float *joints, float *full
 int bf_batch_export_params_dev(bf_batch *b, void *dst_dev) {
     if (!b || !dst_dev) return fail(BF_ERR_INVALID, "bf_batch_export_params_dev: null argument");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rl_ = bf_lanes_drain(b); if (rl_) return rl_; }
+    BF_TRY(bf_lanes_drain(b));
     HIP_TRY(hipMemcpyAsync(dst_dev, b->params.p, b->params.n * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     return BF_OK;
 }
 
@@ -1188,7 +1086,7 @@ int bf_batch_timing_reset(bf_batch *b) {
 int bf_batch_timing_sum(bf_batch *b, float ms[4], int32_t *n_calls) {
     if (!b || !ms || !n_calls) return fail(BF_ERR_INVALID, "bf_batch_timing_sum: null argument");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     int n = std::min(b->ring_n, (int)bf_batch::kRing);
     double acc[4] = {0, 0, 0, 0};
     for (int i = 0; i < n; ++i) {
@@ -1213,7 +1111,7 @@ int bf_batch_mesh_span(bf_batch *b, int reps, float us[3]) {
     bf_model *m = b->m;
     if (bf_mesh_use_multi(m->npf, 1)) return fail(BF_ERR_UNSUPPORTED, "bf_batch_mesh_span: this model's single-frame forward is bf_mesh_multi_kernel");
     HIP_TRY(hipSetDevice(m->device));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     DevBuf<unsigned long long> d_span;
     HIP_TRY(d_span.alloc(2));
     double sum = 0.0, lo = 1e30, hi = 0.0;
@@ -1237,7 +1135,7 @@ int bf_batch_mesh_span(bf_batch *b, int reps, float us[3]) {
 int bf_batch_debug_dump(bf_batch *b, float *dst, int n) {
     if (!b || !dst || n <= 0 || n > 8192) return fail(BF_ERR_INVALID, "bf_batch_debug_dump: bad argument");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     HIP_TRY(hipMemcpy(dst, b->debug.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return BF_OK;
 }

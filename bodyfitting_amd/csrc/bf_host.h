@@ -25,6 +25,8 @@ int bf_fail(int code, const std::string &msg);
         if (e_ != hipSuccess)                                                                      \
             return fail(BF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));            \
     } while (0)
+// a call of this library that has already said why it failed: pass its code on
+#define BF_TRY(call) do { if (int rc_ = (call)) return rc_; } while (0)
 
 // hipMemset of device memory returns before the fill has run, and the fill is on the NULL stream: work enqueued afterwards on a
 // non-blocking stream (every stream of this library) is not ordered behind it.  Fills that are not stream-ordered wait here.
@@ -148,6 +150,72 @@ struct MeshScratch {
     DevBuf<float> featT;          // [K padded][F padded] pose features of a batch, frame-minor (the GEMM's A operand)
 };
 
+// What an arena of either kind is made of: a device buffer and a pinned host buffer of the same size, both zero-filled.
+inline hipError_t bf_alloc_mirrored(DevBuf<float> &dev, float **host, size_t n_floats) {
+    hipError_t e = dev.alloc(n_floats);
+    if (e == hipSuccess) e = bf_memset_sync(dev.p, 0, n_floats * sizeof(float));
+    if (e == hipSuccess) e = hipHostMalloc((void **)host, n_floats * sizeof(float));
+    if (e == hipSuccess) std::memset(*host, 0, n_floats * sizeof(float));
+    return e;
+}
+
+// A result arena: ONE device buffer [params | terms | state | joints | vout] (the batch's layout: res_off / res_cnt) mirrored by ONE
+// pinned host buffer, so a fetch is a single device-to-host copy of the prefix that is wanted.  A batch has two - a fresh fit
+// (BF_FIT_RESET + FETCH, pipelined or frame after frame) writes the one the previous fit did not use and its hand-over runs on a second
+// stream, under the next fit's kernels - and every fit lane has one.  Whoever owns it waits for its streams before it goes.
+struct ResultArena {
+    DevBuf<float> dev;
+    float *host = nullptr;
+    hipEvent_t ev_done = nullptr;   // the fit that fills the arena has finished (a lane's tail follows its fit in stream order: unused there)
+    hipEvent_t ev_copied = nullptr; // the arena's last fit, mesh and hand-over have finished
+    bool copy_pending = false;      // the hand-over ev_copied stands for has not been waited for yet
+    long long seq = -1;             // the fit whose result the arena holds (-1: none)
+    bool fetched = false, has_v = false;
+    ResultArena() = default;
+    ResultArena(const ResultArena &) = delete;
+    hipError_t create(size_t n_floats) {
+        hipError_t e = bf_alloc_mirrored(dev, &host, n_floats);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_done, hipEventDisableTiming);
+        return e == hipSuccess ? hipEventCreateWithFlags(&ev_copied, hipEventDisableTiming) : e;
+    }
+    // This arena takes `from`'s buffers and what is known of their contents; `from` gets this one's, as holding nothing.  The events and
+    // copy_pending stay: they speak of work on their owner's streams (which the caller has waited for), not of the memory.
+    void trade_buffers(ResultArena &from) {
+        std::swap(dev.p, from.dev.p);
+        std::swap(host, from.host);
+        seq = from.seq; fetched = from.fetched; has_v = from.has_v;
+        from.seq = -1;
+        from.fetched = from.has_v = false;
+    }
+    ~ResultArena() {
+        if (ev_done) (void)hipEventDestroy(ev_done);
+        if (ev_copied) (void)hipEventDestroy(ev_copied);
+        if (host) (void)hipHostFree(host);
+    }
+};
+
+// An input arena [keypoints | params0 | ndiv] (the batch's layout: in_off / in_total), fed from its own pinned staging buffer by a
+// transfer on a stream of its owner.  Two per batch and two per fit lane: the next frame's inputs are packed into the staging buffer
+// the fit in flight does not read - the setter never drains a stream (the reference pays 48 keypoint host-to-device copies per
+// ITERATION, loss.py:160).
+struct InputArena {
+    DevBuf<float> dev;
+    float *host = nullptr;
+    hipEvent_t ev = nullptr;        // the transfer out of `host` has finished
+    bool pending = false;           // ... and has not been waited for yet
+    unsigned readers = 0;           // a lane's arena: the lanes whose fits read it since it was last filled (bit per lane)
+    InputArena() = default;
+    InputArena(const InputArena &) = delete;
+    hipError_t create(size_t n_floats) {
+        hipError_t e = bf_alloc_mirrored(dev, &host, n_floats);
+        return e == hipSuccess ? hipEventCreateWithFlags(&ev, hipEventDisableTiming) : e;
+    }
+    ~InputArena() {
+        if (ev) (void)hipEventDestroy(ev);
+        if (host) (void)hipHostFree(host);
+    }
+};
+
 struct bf_model {
     int device = 0;
     int nv = 0, nj = 0, nb = 0, npf = 0, ns = 0, nl = 0, np = 0, n_levels = 0;
@@ -200,17 +268,8 @@ struct BfLane {
     hipStream_t stream = nullptr;
     MeshScratch scratch;            // the tail's MFMA mesh path, on this lane's stream only
     DevBuf<float> adam_m, adam_v, vraw, xpart;
-    DevBuf<float> res;              // result arena [params | terms | state | joints | vout], the batch's layout (res_off / res_cnt)
-    float *h_res = nullptr;         // its pinned mirror (the tail's hand-over)
-    hipEvent_t ev_copied = nullptr; // the lane's last fit, mesh and hand-over have finished
-    long long seq = -1;             // the fit whose result the arena holds (-1: none)
-    bool fetched = false, has_v = false;
-    // two input arenas [keypoints | params0 | ndiv], each fed from its own pinned buffer by a transfer on this lane's stream
-    DevBuf<float> in_dev[2];
-    float *h_in[2] = {nullptr, nullptr};
-    hipEvent_t ev_in[2] = {nullptr, nullptr};   // the transfer out of h_in[a] has finished
-    bool in_pending[2] = {false, false};
-    unsigned in_readers[2] = {0, 0};            // lanes whose fits read arena a since it was last filled (bit per lane)
+    ResultArena arena;              // (its mirror is filled by the tail's hand-over)
+    InputArena in[2];               // each fed by a transfer on this lane's stream
     int in_next = 0;                            // arena the next staging into this lane fills
     bool need_engage = false;                   // the stream has yet to wait for the batch stream (bf_batch::ev_engage)
     bool busy = false;                          // work was enqueued since the lanes were last drained
@@ -228,20 +287,15 @@ struct bf_batch {
     hipEvent_t *ev = nullptr;       // the triple of the last call
     bool timed = false;
     DevBuf<float> params0;          // parameters of the last set_init / set_params / stage_inputs (a view into the current input arena)
-    // Per-frame inputs [keypoints | params0 | ndiv] live in TWO device arenas, each fed from its own pinned staging buffer:
-    // bf_batch_stage_inputs packs the next frame's inputs into the staging buffer the fit in flight does not read and queues
-    // their transfer on the batch stream - the setter never drains the stream (the reference pays 48 keypoint host-to-device
-    // copies per ITERATION, loss.py:160).  `keypoints`, `ndiv`, `params0` are views into arena in_cur.
-    DevBuf<float> in_dev[2];
-    float *h_in[2] = {nullptr, nullptr};
+    // Per-frame inputs live in TWO input arenas: bf_batch_stage_inputs fills the one the fit in flight does not read and queues its
+    // transfer on the batch stream.  `keypoints`, `ndiv`, `params0` are views into arena in_cur.
+    InputArena in[2];
     size_t in_off[3] = {0, 0, 0}, in_total = 0;          // float offsets of keypoints, params0, ndiv inside an arena
-    hipEvent_t ev_in[2] = {nullptr, nullptr};            // the transfer out of staging buffer k has finished
-    bool in_pending[2] = {false, false};
     int in_cur = 0;
     // Staging ASIDE (round 5): the transfer of the next frame's inputs rides on the second stream, AHEAD of the mesh / hand-over tail of
     // the fit in flight - which is why that tail is enqueued late (`tail_k`: at the next entry point, bf_flush_tail) - so that the batch
     // stream holds fit kernel after fit kernel with nothing in between.  in_aside[k]: arena k's transfer is on the second stream and
-    // the fit that reads it must see ev_in[k] first; in_reader[k]: sequence number of the last fit that read arena k (-1: none);
+    // the fit that reads it must see in[k].ev first; in_reader[k]: sequence number of the last fit that read arena k (-1: none);
     // tail_seq: the last fit whose tail - it starts by waiting for that fit - is already on the second stream.
     bool in_aside[2] = {false, false};
     long long in_reader[2] = {-1, -1};
@@ -249,18 +303,11 @@ struct bf_batch {
     int tail_k = -1;                // result arena whose tail is still to be enqueued (-1: none)
     bool tail_big = false;
     bool in_host = false;           // the views point at the pinned staging buffer itself (BF_STAGE_MODE=zerocopy)
-    int stage_mode = 0;             // 0 = copy kernel reading pinned memory, 1 = hipMemcpyAsync, 2 = zero-copy
+    bool stage_zerocopy = false;    // staged inputs stay in pinned memory, the fit kernel's prologue reads them there (no copy kernel, no lanes)
     bool staged = false;            // inputs were staged since the last fit: the next bf_fit must carry BF_FIT_RESET
-    long long fit_seq = 0;          // fits issued so far; arena_seq[k] = the fit whose result result-arena k holds
-    long long arena_seq[2] = {-1, -1};
-    bool arena_fetched[2] = {false, false}, arena_has_v[2] = {false, false};
-    // results live in ONE device arena [params | terms | state | joints | vout] mirrored by ONE pinned host arena, so a
-    // fetch is a single device-to-host copy of the prefix that is wanted
-    // Two such pairs: a fresh fit (BF_FIT_RESET + GRAPH + FETCH) writes the arena the previous fit did not use and its
-    // fetch runs on a second stream, under the next fit's kernels.
-    DevBuf<float> res;              // (device arena 0; arena 1 is res_b)
-    DevBuf<float> res_b;
-    float *h_res = nullptr, *h_res_b = nullptr;
+    long long fit_seq = 0;          // fits issued so far (a result arena's `seq` is one of these numbers)
+    ResultArena arena[2];
+    size_t res_total = 0;           // floats of a result arena
     size_t res_small = 0;           // floats up to the end of `joints` (everything but the vertices)
     size_t res_off[5] = {0, 0, 0, 0, 0}, res_cnt[5] = {0, 0, 0, 0, 0};   // params, terms, state, joints, vout
     int cur = 0;                    // arena the DevBuf views / h_* pointers are on
@@ -280,8 +327,6 @@ struct bf_batch {
     int *h_resident = nullptr;          // pinned, device-visible: workgroups of the persistent launch that have started (this call)
     int kp_tickets = 0;                 // keypoint workgroups launched beside the search since the doors were last zeroed (BF_DOOR_KP's target)
     int *h_door_err = nullptr;          // pinned; copied from door[BF_DOOR_ERR] at the end of a call, read by bf_sync_all
-    hipEvent_t ev_done[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
-    bool copy_pending[2] = {false, false};
     hipGraphExec_t graph_pipe[2] = {nullptr, nullptr};   // kernels-only graphs of the pipelined path, one per arena
     bf_graph_key graph_pipe_key[2]{};
     float *h_params = nullptr, *h_vout = nullptr, *h_joints = nullptr, *h_terms = nullptr, *h_state = nullptr;
@@ -393,9 +438,6 @@ int bf_flush_tail(bf_batch *b);          // enqueue the deferred mesh / hand-ove
 int bf_sync_all(bf_batch *b);            // lanes, copy stream, then compute stream
 int bf_lanes_drain(bf_batch *b);         // no-op unless fit lanes are on: wait for them, hand the last lane fit back to the batch
 int bf_guard_arena(bf_batch *b);         // the compute stream waits for a fetch still reading the current arena
-void bf_use_arena(bf_batch *b, int k);
-void bf_use_inputs(bf_batch *b, int k, bool host);
-FrameIO bf_frame_io(bf_batch *b, bool want_grads);
 }
 extern "C" void bf_fit_image_segments(int nj, int nb, int npf, int ns, int nl, int np, int seg[6]);
 extern "C" size_t bf_fit_smem_bytes(int nj, int nb, int npf, int ns, int nl, int np, int nviews);

@@ -156,7 +156,7 @@ struct bf_group {
 // one has returned, with the first failure (in device order) as this thread's error
 static int run_all(bf_group *g, const std::function<int(bf_group_peer &)> &fn) {
     if (!g->peers[0].worker) {
-        for (auto &p : g->peers) { int rc = fn(p); if (rc) return rc; }
+        for (auto &p : g->peers) BF_TRY(fn(p));
         return BF_OK;
     }
     for (auto &p : g->peers) { bf_group_peer *pp = &p; p.worker->post([pp, &fn] { return fn(*pp); }); }

@@ -359,7 +359,7 @@ int bf_ensure_dense_buffers(bf_batch *b) {
     }
     {
         std::lock_guard<std::mutex> g(m->lazy);
-        { int rt = bf_ensure_posedirsT_locked(m, b->stream); if (rt) return rt; }
+        BF_TRY(bf_ensure_posedirsT_locked(m, b->stream));
         for (bf_model::Sub *U : {&m->sub, &m->sub_kp}) {
             if (!U->on || U->posedirsT.p) continue;
             const size_t sv3 = (size_t)U->mesh.nv * 3;
@@ -379,7 +379,7 @@ int bf_ensure_dense_buffers(bf_batch *b) {
 int bf_batch_set_scans(bf_batch *b, bf_scan *const *scans) {
     if (!b) return fail(BF_ERR_INVALID, "bf_batch_set_scans: null batch");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     // (`scans_lost` is cleared only where the caller has said what this batch's scans are now: on a detach, or once the new scans
     //  are linked - a rejected array leaves a batch that lost its scans failing its fits)
     if (!scans) {                                  // detach
@@ -522,7 +522,7 @@ static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, bool l
     const int F = b->F, nv = Q.nv, nblk = (nv + 255) / 256;
     const bool scans = late && !b->scans.empty(), masks = late && b->has_masks, kp = m->kp_dense;
     const bool acc_mode = fold_acc_on();          // (read once per pass)
-    if (masks) { int rf = bf_masks_finalize(b); if (rf) return rf; }
+    if (masks) BF_TRY(bf_masks_finalize(b));
     if (!door) {                     // (with the resident fit launch every state comes from it)
         hipLaunchKernelGGL(bf_pose_state_kernel, dim3(F), dim3(128), 0, b->stream, m->fit, (const float *)nullptr,
                            (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, b->state.p,
@@ -795,7 +795,7 @@ int bf_batch_dense_timing(bf_batch *b, int enable, float ms[6]) {
     HIP_TRY(hipSetDevice(b->m->device));
     if (ms) {
         if (!b->dense_timed) return fail(BF_ERR_INVALID, "bf_batch_dense_timing: no dense iteration has been timed (enable, then bf_fit with a dense loss)");
-        { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+        BF_TRY(bf_sync_all(b));
         for (int k = 0; k < 6; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], b->ev_dense[k], b->ev_dense[k + 1]));
     }
     b->dense_timing = enable != 0;
@@ -921,7 +921,7 @@ int bf_batch_set_masks(bf_batch *b, int n_masks, const int32_t *view_index, int 
         }
         for (size_t i = 0; i < npix0; ++i) b->h_masks[i] = masks[i] > 128;
     }
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     if (n_masks <= 0 || !masks) { b->has_masks = false; b->masks_pending = false; return BF_OK; }   // (bf_sync_all above drained a deferred extraction)
     const int F = b->F, nv = b->m->nv;
     // (a frame loop hands over new masks of the same shape every frame: device buffers are kept and only grown - a dozen hipFree /
@@ -1140,7 +1140,7 @@ int bf_masks_finalize(bf_batch *b) {
 int bf_batch_mask_loss(bf_batch *b, const bf_hyper *hyper, float *loss, float *dverts) {
     if (!b || !b->has_masks) return fail(BF_ERR_INVALID, "bf_batch_mask_loss: no masks attached");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rf = bf_masks_finalize(b); if (rf) return rf; }
+    BF_TRY(bf_masks_finalize(b));
     bf_hyper h;
     if (hyper) h = *hyper; else bf_hyper_default(&h);
     HyperDev hd = bf_to_dev(h);
@@ -1153,7 +1153,7 @@ int bf_batch_mask_loss(bf_batch *b, const bf_hyper *hyper, float *loss, float *d
     HIP_TRY(hipMemsetAsync(b->dvout.p, 0, b->dvout.n * sizeof(float), b->stream));
     rc = launch_mask_kernels(b, 1.0f, true);
     if (rc) return rc;
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     if (loss) HIP_TRY(hipMemcpy(loss, b->mk_loss.p, (size_t)b->F * sizeof(float), hipMemcpyDeviceToHost));
     if (dverts) HIP_TRY(hipMemcpy(dverts, b->dvout.p, b->dvout.n * sizeof(float), hipMemcpyDeviceToHost));
     return BF_OK;
@@ -1171,7 +1171,7 @@ int bf_fit_displacement(bf_batch *b, int n_iters, const bf_hyper *hyper) {
     bf_hyper h;
     if (hyper) h = *hyper; else bf_hyper_default(&h);
     const int F = b->F, nv = m->nv, nf = (int)m->faces_host.size() / 3;
-    { int rg_ = bf_guard_arena(b); if (rg_) return rg_; }
+    BF_TRY(bf_guard_arena(b));
     std::unique_lock<std::mutex> lazy(m->lazy);
     if (!m->faces_d.p) {
         // vertex -> (face, corner) lists in the order compute_normal_torch adds them: corner by corner, faces ascending
@@ -1232,7 +1232,7 @@ int bf_batch_get_displacement(bf_batch *b, float *displacement) {
     if (!b || !displacement) return fail(BF_ERR_INVALID, "bf_batch_get_displacement: null argument");
     if (!b->have_disp) return fail(BF_ERR_INVALID, "bf_batch_get_displacement: no bf_fit_displacement yet");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     HIP_TRY(hipMemcpy(displacement, b->disp.p, b->disp.n * sizeof(float), hipMemcpyDeviceToHost));
     return BF_OK;
 }
@@ -1241,7 +1241,7 @@ int bf_batch_get_displacement(bf_batch *b, float *displacement) {
 int bf_batch_debug_disp_moment(bf_batch *b, float *m_out) {
     if (!b || !m_out || !b->have_disp) return fail(BF_ERR_INVALID, "bf_batch_debug_disp_moment: bad argument");
     HIP_TRY(hipSetDevice(b->m->device));
-    { int rs_ = bf_sync_all(b); if (rs_) return rs_; }
+    BF_TRY(bf_sync_all(b));
     HIP_TRY(hipMemcpy(m_out, b->disp_m.p, b->disp_m.n * sizeof(float), hipMemcpyDeviceToHost));
     return BF_OK;
 }
