@@ -102,8 +102,11 @@ def rodrigues_bwd(theta, cache, dR):
     return dn / a[:, None] + (da / a)[:, None] * u
 
 
-def loss_grad(tab, gmm_bufs, views, params, c=0.3, imsize=512):
-    """Objective value, its four terms and the analytic gradient w.r.t. the 86 optimised scalars."""
+def loss_grad(tab, gmm_bufs, views, params, c=0.3, imsize=512, sigma=SIGMA, pose_prior_weight=4.78, angle_prior_weight=15.2,
+              shape_prior_weight=5.0):
+    """Objective value, its four terms and the analytic gradient w.r.t. the 86 optimised scalars.  sigma and the three prior
+    weights: the keyword arguments of loss.py:139-141 (the weights enter squared)."""
+    W_POSE, W_ANGLE, W_SHAPE = pose_prior_weight ** 2, angle_prior_weight ** 2, shape_prior_weight ** 2
     dt = tab["J_template"].dtype
     P, kp, ndiv = views
     means, prec, nllw = (np.asarray(x, dtype=dt) for x in gmm_bufs)
@@ -143,7 +146,7 @@ def loss_grad(tab, gmm_bufs, views, params, c=0.3, imsize=512):
     uv = pix[:, :, :2] / pix[:, :, 2:3]
     coeff = dt.type(imsize / 1024.0)
     r = (kp[:, :, :2] - uv) / coeff
-    s2 = dt.type(SIGMA * SIGMA)
+    s2 = dt.type(sigma * sigma)
     rho = s2 * r * r / (s2 + r * r)
     conf2 = kp[:, :, 2] ** 2
     loss_2d = (conf2 * rho.sum(-1)).sum() / ndiv
@@ -234,18 +237,22 @@ def adam_step(params, grads, state, step, dtype, beta1=0.9, beta2=0.999, eps=1e-
         state[k] = (m, v)
 
 
-def fit(model, gmm_bufs, problem, num_iters=100, dtype=np.float64, snapshots=()):
-    """The loop of smplify.py:177-213 driven by the analytic gradient; returns stepped parameters."""
+def fit(model, gmm_bufs, problem, num_iters=100, dtype=np.float64, snapshots=(), start=None, constant_scale=None, **loss_kw):
+    """The loop of smplify.py:177-213 driven by the analytic gradient; returns stepped parameters.  start: parameter dict to begin
+    at instead of the initial estimate with zero translation and unit scale (the loop a library call continues after
+    bf_batch_set_params); constant_scale (default: the problem's) and loss_grad's keywords are passed on."""
     tab = build_fit_tables(model, dtype)
     views = build_views(problem, dtype)
     params = {"global_transl": np.zeros(3, dtype), "scale": np.ones(1, dtype),
               "pose": np.asarray(problem["init_pose"][0, 3:], dtype=dtype),
               "betas": np.asarray(problem["init_betas"][0], dtype=dtype),
               "global_orient": np.asarray(problem["init_pose"][0, :3], dtype=dtype)}
+    if start is not None:
+        params = {k: np.asarray(start[k], dtype=dtype).reshape(params[k].shape).copy() for k in params}
+    c = problem.get("constant_scale", 0.3) if constant_scale is None else constant_scale
     state, snaps, losses = {}, {}, []
     for i in range(num_iters):
-        loss, _, grads, _ = loss_grad(tab, gmm_bufs, views, params, problem.get("constant_scale", 0.3),
-                                      problem["imsize"])
+        loss, _, grads, _ = loss_grad(tab, gmm_bufs, views, params, c, problem["imsize"], **loss_kw)
         losses.append(loss)
         adam_step(params, grads, state, i + 1, dtype)
         if (i + 1) in snapshots:

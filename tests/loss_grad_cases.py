@@ -1,0 +1,465 @@
+"""Cases of the keypoint-loss gradient sweep, shared by tests/test_loss_grad_cases.py (CPU: every case is well posed) and
+tests/test_gpu_loss_grad_sweep.py (MI355X: bf_loss_grad against the fp64 oracle at every case).
+
+A case = (axis, name, model kind + size, problem, parameter point, hyper overrides) plus what the tests need to know about it:
+the parameter blocks that must be exactly zero, the base band it falls under and whether a short fit is run from it (axis H).
+Everything is built from fixed seeds; nothing here touches a GPU.
+
+Axes:
+  A  view counts of the sparse kernel (sized SMPL instance and the table-driven kid instance), with missing views
+  B  view counts of the dense kernel (SMPL-X), across its LDS / global-memory switch
+  C  the 79 rows of dynamic face-contour landmarks
+  D  each GMM component as the arg-min (and its priors-only variant)
+  E  hyper-parameters, one at a time and all at once
+  F  priors and pose extremes (and their priors-only variants)
+  G  keypoint edges
+  H  = the cases of A..E flagged `loop`: ten Adam steps from the case's point
+"""
+import functools
+import zlib
+
+import numpy as np
+import torch
+
+from bodyfitting_amd import model_files, synthetic as S
+from oracle import analytic as A
+from oracle import smplify_oracle as O
+
+SMPL_BLOCKS = ("global_transl", "scale", "pose", "betas", "global_orient")
+TERMS = ("reprojection_loss", "pose_prior_loss", "angle_prior_loss", "shape_prior_loss")
+KID_BETA = 0.4
+NV_SMALL = {"smpl": 690, "kid": 690, "smplx": 1200}
+# The largest view count bf_batch_create accepts (one workgroup's 160 KB of LDS, 48 bytes per view behind the model's own arrays).
+# Nothing on the CPU can ask the library for it, so the numbers stand here for the case builders and the GPU test asserts them
+# against the library: bf_batch_create(V_MAX) succeeds, bf_batch_create(V_MAX + 1) is BF_ERR_UNSUPPORTED.
+V_MAX = {"smpl": 604, "kid": 604, "smplx": 1238}
+VIEWS_A = (1, 2, 3, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 96)
+VIEWS_B = (1, 3, 4, 11, 12, 13, 24, 25, 48, 117, 118, 119, 120, 144)
+HYPER_KEYS = ("sigma", "pose_prior_weight", "angle_prior_weight", "shape_prior_weight", "constant_scale", "imsize")
+MIN_DEPTH = 0.2
+# without keypoints nothing depends on the similarity, the root orientation or (SMPL-X) the eyes and the hands
+PRIORS_ONLY_ZERO = {"smpl": ("global_transl", "scale", "global_orient"), "kid": ("global_transl", "scale", "global_orient"),
+                    "smplx": ("global_transl", "scale", "global_orient", "leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose")}
+
+
+class Case:
+    def __init__(self, axis, name, kind, size, problem, params, hyper=None, zero_blocks=(), base="default", loop=False):
+        self.axis, self.name, self.kind, self.size = axis, name, kind, size
+        self.problem, self.params, self.hyper = problem, params, dict(hyper or {})
+        self.zero_blocks, self.base, self.loop = tuple(zero_blocks), base, loop
+        assert set(self.hyper) <= set(HYPER_KEYS), self.hyper
+        assert self.hyper.get("imsize", problem["imsize"]) == problem["imsize"]          # the problem is built for the image size
+
+    @property
+    def id(self):
+        return f"{self.axis}-{self.kind}-{self.size}-{self.name}"
+
+    @property
+    def blocks(self):
+        return O.SMPLX_PARAMS if self.kind == "smplx" else SMPL_BLOCKS
+
+    @property
+    def n_views(self):
+        return len(self.problem["c2ws"])
+
+    def library_hyper(self):
+        """keyword arguments of native.make_hyper: the overrides plus what the oracle reads off the problem"""
+        return {"imsize": self.problem["imsize"], "constant_scale": self.problem.get("constant_scale", 0.3), **self.hyper}
+
+    def oracle_keywords(self):
+        return {k: v for k, v in self.hyper.items() if k != "imsize"}
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# models and problems
+# ----------------------------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def model(kind, size):
+    nv = NV_SMALL[kind] if size == "small" else None
+    if kind == "smplx":
+        return S.make_model("smplx", seed=0, nv=nv)
+    adult = S.make_model("smpl", seed=0, nv=nv)
+    return model_files.kid_model(adult, S.make_kid_template(adult)) if kind == "kid" else adult
+
+
+@functools.lru_cache(maxsize=None)
+def gmm():
+    return S.make_gmm(seed=0)
+
+
+@functools.lru_cache(maxsize=None)
+def gmm_bufs():
+    return S.gmm_buffers(gmm())
+
+
+def _seed(*parts):
+    return zlib.crc32(repr(parts).encode())
+
+
+def problem(kind, size, frame, n_views, missing=(), **kw):
+    m = model(kind, size)
+    if kind == "smplx":
+        assert not missing
+        return S.make_problem_smplx(m, frame, n_views, **kw)
+    if kind == "kid":
+        return S.as_kid_problem(S.make_problem(S.kid_problem_model(m, KID_BETA), frame=frame, n_views=n_views, missing_views=tuple(missing), **kw), KID_BETA)
+    return S.make_problem(m, frame=frame, n_views=n_views, missing_views=tuple(missing), **kw)
+
+
+def point(kind, prob, seed):
+    """an ordinary parameter point: the initial estimate jittered, a few centimetres of translation, a scale near one"""
+    rng = np.random.default_rng(_seed("point", kind, seed))
+    init = np.asarray(prob["init_pose"], np.float64)[0]
+    nbody = 63 if kind == "smplx" else 69
+    p = {"global_transl": rng.normal(0, 0.03, 3), "scale": np.array([rng.uniform(0.9, 1.15)]),
+         "pose": init[3:3 + nbody] + rng.normal(0, 0.05, nbody), "betas": rng.normal(0, 0.5, 10),
+         "global_orient": init[:3] + rng.normal(0, 0.05, 3)}
+    if kind == "kid":
+        p["betas"] = np.concatenate([p["betas"], [0.3]])
+    if kind == "smplx":
+        p.update(leye_pose=rng.normal(0, 0.03, 3), reye_pose=rng.normal(0, 0.03, 3), left_hand_pose=rng.normal(0, 0.3, 6),
+                 right_hand_pose=rng.normal(0, 0.3, 6))
+    return {k: np.asarray(v, np.float64) for k, v in p.items()}
+
+
+def _edit_keypoints(prob, fn):
+    """a copy of the problem with fn(view index, {part: array copy}) applied to every present view"""
+    out = dict(prob)
+    kps = []
+    for v, k in enumerate(prob["keypoints"]):
+        if k is None:
+            kps.append(None)
+            continue
+        k2 = {part: np.array(a, np.float32) for part, a in k.items()}
+        fn(v, k2)
+        kps.append(k2)
+    out["keypoints"] = kps
+    return out
+
+
+def without_confidence(prob):
+    """the problem with every confidence of every view zero: the priors alone remain"""
+    def zero(v, k):
+        for a in k.values():
+            a[:, 2] = 0.0
+    return _edit_keypoints(prob, zero)
+
+
+def _base_for_views(kind, n_views):
+    # the project's existing exception for the sparse kernel's streamed views (tests/test_gpu_parity.py, 60 views): 2e-5 of the
+    # block's maximum; everything else is held to the baseline 5e-6
+    return "streamed" if kind != "smplx" and n_views > 48 else "default"
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the axes
+# ----------------------------------------------------------------------------------------------------------------------------
+
+def axis_a():
+    out = []
+    loops = {("smpl", 3), ("smpl", 33), ("smpl", 65), ("kid", 49), ("smpl", V_MAX["smpl"])}
+    for kind in ("smpl", "kid"):
+        views = VIEWS_A + (V_MAX[kind],)
+        for V in views:
+            pr = problem(kind, "small", 2, V)
+            out.append(Case("A", f"V{V}", kind, "small", pr, point(kind, pr, ("A", V)), base=_base_for_views(kind, V),
+                            loop=(kind, V) in loops))
+        for V in (17, 49, 65):
+            variants = [("first-missing", (0,)), ("last-missing", (V - 1,))]
+            if V > 48:
+                variants.append(("streamed-missing", tuple(range(48, V))))
+                only = 48 if V == 49 else 56
+                variants.append((f"only-view-{only}", tuple(v for v in range(V) if v != only)))
+                if V > 49:          # (with 49 views that is the plain case: view 48 is the only streamed one)
+                    variants.append((f"only-streamed-view-{only}", tuple(v for v in range(48, V) if v != only)))
+            for name, missing in variants:
+                pr = problem(kind, "small", 3, V, missing=missing)
+                out.append(Case("A", f"V{V}-{name}", kind, "small", pr, point(kind, pr, ("A", V, name)), base=_base_for_views(kind, V)))
+        for V in (views[0], views[-1]):
+            pr = problem(kind, "full", 2, V)
+            out.append(Case("A", f"V{V}", kind, "full", pr, point(kind, pr, ("A", V)), base=_base_for_views(kind, V)))
+    return out
+
+
+def axis_b():
+    out = []
+    views = VIEWS_B + (V_MAX["smplx"],)
+    for V in views:
+        pr = problem("smplx", "small", 1, V)
+        out.append(Case("B", f"V{V}", "smplx", "small", pr, point("smplx", pr, ("B", V)), loop=V in (12, 118, 119)))
+    for V in (views[0], views[-1]):
+        pr = problem("smplx", "full", 1, V)
+        out.append(Case("B", f"V{V}", "smplx", "full", pr, point("smplx", pr, ("B", V))))
+    return out
+
+
+NECK, NECK_CHAIN_REST = 12, (3, 6, 9)      # smplx's neck_kin_chain is 12 -> 9 -> 6 -> 3 -> 0
+CONTOUR_DEGREES = tuple(range(-45, 45))
+# yaw through the whole chain (the kernel reads the neck's GLOBAL rotation): global_orient, spine joints 3 / 6 / 9 and the neck itself
+CONTOUR_CHAIN = (
+    ("chain-left", {0: (0.05, 0.30, -0.04), 3: (0.02, 0.10, 0.03), 6: (-0.03, 0.08, 0.0), 9: (0.0, 0.05, 0.02), 12: (0.04, 0.12, -0.02)}),
+    ("chain-right", {0: (-0.04, -0.25, 0.06), 3: (0.03, -0.12, 0.0), 6: (0.0, -0.07, 0.04), 9: (-0.02, -0.04, 0.0), 12: (0.0, -0.10, 0.03)}),
+    ("chain-mixed", {0: (0.10, 0.45, 0.0), 3: (0.0, -0.20, 0.05), 6: (0.05, 0.15, 0.0), 9: (0.0, -0.30, 0.0), 12: (-0.05, 0.08, 0.05)}),
+)
+
+
+def _contour_params(size, neck_chain):
+    """global_orient, the spine joints and the neck as given ({joint: axis-angle}, missing = zero); every other joint at one fixed random point"""
+    pr = problem("smplx", size, 0, 4)
+    p = point("smplx", pr, ("C",))
+    rng = np.random.default_rng(_seed("contour-pose"))
+    p["pose"] = rng.normal(0, 0.15, 63)
+    p["global_orient"] = np.asarray(neck_chain.get(0, (0.0, 0.0, 0.0)), np.float64)
+    for j in NECK_CHAIN_REST + (NECK,):
+        p["pose"][3 * (j - 1):3 * j] = neck_chain.get(j, (0.0, 0.0, 0.0))
+    return pr, p
+
+
+def axis_c():
+    out = []
+    for d in CONTOUR_DEGREES:
+        pr, p = _contour_params("small", {NECK: (0.0, np.deg2rad(d + 0.25), 0.0)})
+        out.append(Case("C", f"neck{d:+03d}", "smplx", "small", pr, p, loop=d in (10, 44)))
+    for name, chain in CONTOUR_CHAIN:
+        pr, p = _contour_params("small", chain)
+        out.append(Case("C", name, "smplx", "small", pr, p))
+    for d in (CONTOUR_DEGREES[0], CONTOUR_DEGREES[-1]):
+        pr, p = _contour_params("full", {NECK: (0.0, np.deg2rad(d + 0.25), 0.0)})
+        out.append(Case("C", f"neck{d:+03d}", "smplx", "full", pr, p))
+    return out
+
+
+def neck_yaw_degrees(case):
+    """-yaw * 180 / pi of the neck's global rotation in float64: what find_dynamic_lmk_idx_and_bcoords rounds to the row"""
+    m = model(case.kind, case.size)
+    fp = S.smplx_full_pose(m, case.params["global_orient"], case.params["pose"], case.params["leye_pose"], case.params["reye_pose"],
+                           case.params["left_hand_pose"], case.params["right_hand_pose"])
+    rel = np.eye(3)
+    for j in m["neck_kin_chain"]:
+        rel = S._rodrigues64(fp[3 * j:3 * j + 3]) @ rel
+    return float(-np.arctan2(-rel[2, 0], np.hypot(rel[0, 0], rel[1, 0])) * 180.0 / np.pi)
+
+
+def _with_priors_only(case):
+    return [case, Case(case.axis, case.name + "-priors-only", case.kind, case.size, without_confidence(case.problem), case.params,
+                       case.hyper, zero_blocks=PRIORS_ONLY_ZERO[case.kind], base=case.base)]
+
+
+def axis_d():
+    out = []
+    means = np.asarray(gmm()["means"], np.float64)
+    for kind, size in (("smpl", "small"), ("kid", "small"), ("smplx", "small"), ("smpl", "full"), ("smplx", "full")):
+        for m in range(8) if size == "small" else (0, 7):
+            pr = problem(kind, size, 4, 8)
+            p = point(kind, pr, ("D", m))
+            rng = np.random.default_rng(_seed("gmm", m))
+            pose = means[m] + rng.normal(0, 0.05, 69)
+            p["pose"] = pose[:63] if kind == "smplx" else pose
+            out += _with_priors_only(Case("D", f"component{m}", kind, size, pr, p, loop=(kind, size, m) in (("smpl", "small", 1), ("smpl", "small", 7))))
+    return out
+
+
+HYPER_SWEEP = (
+    ("sigma10", {"sigma": 10.0}), ("sigma1000", {"sigma": 1000.0}),
+    ("pose-weight0", {"pose_prior_weight": 0.0}), ("pose-weight47.8", {"pose_prior_weight": 47.8}),
+    ("angle-weight0", {"angle_prior_weight": 0.0}), ("angle-weight152", {"angle_prior_weight": 152.0}),
+    ("shape-weight0", {"shape_prior_weight": 0.0}), ("shape-weight50", {"shape_prior_weight": 50.0}),
+    ("cscale0.1", {"constant_scale": 0.1}), ("cscale1.0", {"constant_scale": 1.0}),
+    ("imsize256", {"imsize": 256}), ("imsize1024", {"imsize": 1024}),
+    ("all-at-once", {"sigma": 40.0, "pose_prior_weight": 9.56, "angle_prior_weight": 30.4, "shape_prior_weight": 2.5, "constant_scale": 0.5,
+                     "imsize": 1024}),
+)
+HYPER_MODELS = (("smpl", "full"), ("smplx", "small"))      # the sized instance on the suite's shared device model, and the dense kernel
+
+
+def hyper_default_case(kind, size):
+    """the default-hyper case evaluated before the hyper sweep on a device model and once more after it (bit-identical)"""
+    pr = problem(kind, size, 5, 8)
+    return Case("E", "default-hyper", kind, size, pr, point(kind, pr, ("E",)))
+
+
+def axis_e():
+    out = []
+    for kind, size in HYPER_MODELS:
+        out.append(hyper_default_case(kind, size))
+        for name, hyper in HYPER_SWEEP:
+            kw = {}
+            if "imsize" in hyper:
+                kw["imsize"] = hyper["imsize"]
+            if "constant_scale" in hyper:
+                kw["constant_scale"] = hyper["constant_scale"]
+            pr = problem(kind, size, 5, 8, **kw)
+            out.append(Case("E", name, kind, size, pr, point(kind, pr, ("E",)), hyper=hyper, loop=name == "all-at-once"))
+    return out
+
+
+ANGLE_DOFS = (9, 12, 52, 55)
+
+
+def axis_f():
+    out = []
+    for kind, size in (("smpl", "small"), ("smplx", "small"), ("smpl", "full"), ("smplx", "full")):
+        cases = []
+        pr = problem(kind, size, 1, 8)
+        patterns = [tuple(1.0 if (bits >> i) & 1 else -1.0 for i in range(4)) for bits in range(16)]
+        if kind == "smplx":
+            patterns = [patterns[i] for i in (0, 15, 5, 10, 3, 6)]                 # the two all-same-sign ones and four mixed ones
+        for signs in patterns:
+            p = point(kind, pr, ("F", "angle"))
+            for dof, sg in zip(ANGLE_DOFS, signs):
+                p["pose"][dof] = 1.5 * sg
+            cases.append(Case("F", "angles" + "".join("+" if s > 0 else "-" for s in signs), kind, size, pr, p))
+        for mag in (3.10, 3.14):
+            for which, joints in (("root", (0,)), ("body", (4, 16, 18)), ("root+body", (0, 4, 16, 18))):
+                p = point(kind, pr, ("F", "pi"))
+                rng = np.random.default_rng(_seed("axis", which))
+                for j in joints:
+                    ax = rng.normal(size=3)
+                    ax *= mag / np.linalg.norm(ax)
+                    if j == 0:
+                        p["global_orient"] = ax
+                    else:
+                        p["pose"][3 * (j - 1):3 * j] = ax
+                cases.append(Case("F", f"theta{mag:.2f}-{which}", kind, size, pr, p))
+        for name, sg in (("+3", np.ones(10)), ("-3", -np.ones(10)), ("+-3", np.where(np.arange(10) % 2 == 0, 1.0, -1.0))):
+            p = point(kind, pr, ("F", "betas"))
+            p["betas"][:10] = 3.0 * sg
+            cases.append(Case("F", "betas" + name, kind, size, pr, p))
+        for sc in (0.3, 3.0):
+            for name, t in (("+1m", (1.0, 1.0, 1.0)), ("-1m", (-1.0, -1.0, -1.0))):
+                p = point(kind, pr, ("F", "scale"))
+                p["scale"] = np.array([sc])
+                p["global_transl"] = np.asarray(t, np.float64)
+                cases.append(Case("F", f"scale{sc}-transl{name}", kind, size, pr, p))
+        if size == "full":
+            cases = [cases[0], cases[-1]]
+        for c in cases:
+            out += _with_priors_only(c)
+    return out
+
+
+def axis_g():
+    out = []
+    for kind, size in (("smpl", "small"), ("smplx", "small"), ("smpl", "full"), ("smplx", "full")):
+        base = problem(kind, size, 3, 8)
+        cases = []
+
+        def add(name, pr, **kw):
+            cases.append(Case("G", name, kind, size, pr, point(kind, pr, ("G", name)), **kw))
+
+        def zero_view(v, k):
+            if v == 2:
+                for a in k.values():
+                    a[:, 2] = 0.0
+        add("view-with-zero-confidence", _edit_keypoints(base, zero_view))
+
+        def loud(v, k):
+            for a in k.values():
+                a[:, 2] *= 2.5
+        add("confidence-above-one", _edit_keypoints(base, loud))
+
+        def outside(v, k):
+            rng = np.random.default_rng(_seed("outside", v))
+            for a in k.values():
+                far = rng.uniform(size=len(a)) < 0.3
+                a[far, :2] += rng.choice([-3000.0, 2500.0], size=(int(far.sum()), 2))
+        add("keypoints-outside-image", _edit_keypoints(base, outside))
+        if kind == "smplx":
+            pr49 = problem(kind, size, 3, 49)
+            pr49["keypoints"] = [k if v == 48 else None for v, k in enumerate(pr49["keypoints"])]
+        else:
+            pr49 = problem(kind, size, 3, 49, missing=tuple(range(48)))
+        add("only-view-48-of-49", pr49, base=_base_for_views(kind, 49))
+        add("divisor-3-of-8-views", dict(base, use_frames=list(range(3))))
+        add("divisor-20-for-8-views", dict(base, use_frames=list(range(20))))
+        if kind == "smplx":
+            def no_body(v, k):
+                k["pose"][:, 2] = 0.0
+            add("body-confidence-zero", _edit_keypoints(base, no_body))
+
+            def face_only(v, k):
+                for part in ("pose", "hand_left", "hand_right"):
+                    k[part][:, 2] = 0.0
+            add("face-landmarks-only", _edit_keypoints(base, face_only))
+        out += cases if size == "small" else [cases[0], cases[-1]]
+    return out
+
+
+AXES = (("A", axis_a), ("B", axis_b), ("C", axis_c), ("D", axis_d), ("E", axis_e), ("F", axis_f), ("G", axis_g))
+
+
+@functools.lru_cache(maxsize=None)
+def all_cases():
+    """every case, axis by axis"""
+    out = []
+    for _, fn in AXES:
+        out += fn()
+    ids = [c.id for c in out]
+    assert len(set(ids)) == len(ids)
+    return tuple(out)
+
+
+def loop_cases():
+    return tuple(c for c in all_cases() if c.loop)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the oracle at a case
+# ----------------------------------------------------------------------------------------------------------------------------
+
+def oracle(case, dtype=torch.float64):
+    """-> dict(terms, grads, joints (world space, [loss joints, 3]), row (SMPL-X: the dynamic-contour row, else None))"""
+    m = model(case.kind, case.size)
+    if case.kind == "smplx":
+        _, terms, grads, joints, _, row = O.smplx_loss_and_grad(m, gmm_bufs(), case.problem, case.params, dtype=dtype, **case.oracle_keywords())
+    else:
+        _, terms, grads, joints, _ = O.loss_and_grad(m, gmm_bufs(), case.problem, case.params, dtype=dtype, **case.oracle_keywords())
+        joints, row = joints[:O.SKELETON_LENGTH], None
+    return {"terms": terms, "grads": grads, "joints": joints, "row": row}
+
+
+def oracle_loop(case, n_iters=10, double=True):
+    """the reference loop started at the case's point -> the stepped parameters (dict over case.blocks)"""
+    m = model(case.kind, case.size)
+    if case.kind == "smplx":
+        res = O.fit_smplx(m, gmm_bufs(), case.problem, num_iters=n_iters, dtype=torch.float64 if double else torch.float32,
+                          start=case.params, **case.oracle_keywords())
+        return res["params"]
+    params, _, _ = A.fit(m, gmm_bufs(), case.problem, n_iters, dtype=np.float64 if double else np.float32, start=case.params,
+                         **case.oracle_keywords())
+    return params
+
+
+def depths(case, joints):
+    """projected depth p2 of every loss joint in every present view, [present views, loss joints] (float64)"""
+    w2c = np.linalg.inv(np.asarray(case.problem["c2ws"], np.float32).astype(np.float64))
+    present = [v for v, k in enumerate(case.problem["keypoints"]) if k is not None]
+    X = np.asarray(joints, np.float64)
+    return np.stack([X @ w2c[v, 2, :3] + w2c[v, 2, 3] for v in present])
+
+
+def gmm_gap(case):
+    """(arg-min component, runner-up's nll minus the arg-min's) of the merged GMM prior at the case's body pose"""
+    means, prec, w = (np.asarray(x, np.float64) for x in gmm_bufs())
+    pose = np.concatenate([case.params["pose"], np.zeros(69 - len(case.params["pose"]))])
+    d = pose[None] - means
+    q = 0.5 * np.einsum("mi,mij,mj->m", d, prec, d) - np.log(w)
+    order = np.argsort(q)
+    return int(order[0]), float(q[order[1]] - q[order[0]])
+
+
+def band(g64, g32, base="default"):
+    """The band of one parameter block: max(base * M, 8 * err32) with M = max|g64| and err32 = max|g32 - g64|, the error of torch's own
+    float32 autograd of the same oracle at the same point.  base: 5e-6 (what test_loss_terms_and_gradient holds at the baseline
+    point); 2e-5 for the sparse kernel's streamed views (test_more_than_48_views_streams_the_rest).  The factor 8: the kernels use
+    v_rcp_f32 / __expf (1 ulp each) where torch divides and calls exp.  -> (band, M, err32)"""
+    M = float(np.abs(g64).max())
+    err32 = float(np.abs(np.asarray(g32, np.float64) - g64).max())
+    return max({"default": 5e-6, "streamed": 2e-5}[base] * M, 8.0 * err32), M, err32
+
+
+def term_band(t64, t32):
+    """relative band of a loss term: max(3e-6, 8 * rel32)"""
+    rel32 = abs(t32 - t64) / abs(t64) if t64 != 0 else 0.0
+    return max(3e-6, 8.0 * rel32)
