@@ -36,6 +36,24 @@ class ModelDesc(C.Structure):
     ]
 
 
+class SmplxParams(C.Structure):          # bf_smplx_params
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in (
+        "betas", "global_orient", "body_pose", "jaw_pose", "leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose")]
+
+
+class SmplxOutputs(C.Structure):         # bf_smplx_outputs
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in ("vertices", "joints", "joints_all", "full_pose")] + [("dyn_row", C.POINTER(C.c_int32))]
+
+
+class SmplxCotangents(C.Structure):      # bf_smplx_cotangents
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in ("dvertices", "djoints", "djoints_all", "dfull_pose")]
+
+
+class SmplxGrads(C.Structure):           # bf_smplx_grads
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in (
+        "dbetas", "dglobal_orient", "dbody_pose", "djaw_pose", "dleye_pose", "dreye_pose", "dleft_hand_pose", "dright_hand_pose")]
+
+
 class Hyper(C.Structure):
     _fields_ = [(n, C.c_float) for n in (
         "sigma", "pose_prior_weight", "angle_prior_weight", "shape_prior_weight", "constant_scale",
@@ -66,6 +84,8 @@ SIGNATURES = {
     "bf_smpl_forward": (C.c_int, [_VP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP]),
     "bf_model_forward": (C.c_int, [_VP, C.c_int, _FP, _FP, _FP]),
     "bf_smpl_vjp": (C.c_int, [_VP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "bf_smplx_forward": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), C.POINTER(SmplxOutputs)]),
+    "bf_smplx_vjp": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), C.POINTER(SmplxCotangents), C.POINTER(SmplxGrads)]),
     "bf_batch_create": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(_VP)]),
     "bf_batch_destroy": (None, [_VP]),
     "bf_batch_set_cameras": (C.c_int, [_VP, _FP, _FP]),

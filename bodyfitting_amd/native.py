@@ -72,6 +72,9 @@ def model_desc(model, gmm):
         d.n_dyn_rows, d.n_lmk_dynamic = keep["dyn_f"].shape
         d.dynamic_lmk_faces_idx, d.dynamic_lmk_bary_coords = _lib.iptr(keep["dyn_f"]), _lib.fptr(keep["dyn_b"])
         d.neck_joint = int(np.asarray(model["neck_kin_chain"])[0])
+        info["n_hand_pca"] = keep["lhc"].shape[0]
+        # all joints smplx returns before a joint_mapper: chain | selector vertices | extra regressor rows | 51 + 17 landmarks
+        info["n_joints_all"] = info["n_joints"] + info["n_selector"] + keep["j_regressor_extra"].shape[0] + len(keep["lmk_f"]) + keep["dyn_f"].shape[1]
     d.gmm_components, d.gmm_dim = keep["gmm_means"].shape
     if info["faces"] is not None:
         keep["faces"] = _i32(info["faces"].reshape(-1, 3))
@@ -137,6 +140,44 @@ class DeviceModel:
                                          _lib.fptr(dj), _lib.fptr(djo), _lib.fptr(dbetas), _lib.fptr(dorient), _lib.fptr(dpose)),
                    "bf_smpl_vjp")
         return dbetas, dorient, dpose
+
+    def _smplx_params(self, betas, global_orient, body_pose, jaw_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose):
+        if self.model_type != "smplx":
+            raise _lib.BodyfitError("forward_smplx / vjp_smplx: SMPL-X-kind models only (bf_smplx_forward)")
+        betas = _f32(betas, (-1, self.n_betas))
+        n = betas.shape[0]
+        opt = lambda a, w: None if a is None else _f32(a, (n, w))          # noqa: E731
+        arrays = (betas, _f32(global_orient, (n, 3)), _f32(body_pose, (n, 63)), opt(jaw_pose, 3), opt(leye_pose, 3), opt(reye_pose, 3),
+                  opt(left_hand_pose, self.n_hand_pca), opt(right_hand_pose, self.n_hand_pca))
+        return n, arrays, _lib.SmplxParams(*[_lib.fptr(a) for a in arrays])
+
+    def forward_smplx(self, betas, global_orient, body_pose, jaw_pose=None, leye_pose=None, reye_pose=None, left_hand_pose=None,
+                      right_hand_pose=None):
+        """smplx.create(model_type='smplx', ...).forward as smplify.py:177-190 calls it (bf_smplx_forward), model space; an
+        argument left None is zeros.  -> dict(vertices[n,NV,3], joints[n,n_joint_map,3] (the model's joint_map: 135),
+        joints_all[n,144,3] (what smplx returns before a joint_mapper), full_pose[n,165], dyn_row[n] int32)."""
+        n, keep, par = self._smplx_params(betas, global_orient, body_pose, jaw_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose)
+        out = {"vertices": np.empty((n, self.n_verts, 3), np.float32), "joints": np.empty((n, self.n_joint_map, 3), np.float32),
+               "joints_all": np.empty((n, self.n_joints_all, 3), np.float32), "full_pose": np.empty((n, 3 * self.n_joints), np.float32),
+               "dyn_row": np.empty(n, np.int32)}
+        dst = _lib.SmplxOutputs(*[_lib.fptr(out[k]) for k in ("vertices", "joints", "joints_all", "full_pose")], _lib.iptr(out["dyn_row"]))
+        _lib.check(self._lib.bf_smplx_forward(self._h, n, C.byref(par), C.byref(dst)), "bf_smplx_forward")
+        return out
+
+    def vjp_smplx(self, betas, global_orient, body_pose, jaw_pose=None, leye_pose=None, reye_pose=None, left_hand_pose=None,
+                  right_hand_pose=None, dverts=None, djoints=None, djoints_all=None, dfull_pose=None):
+        """The backward of `forward_smplx` (bf_smplx_vjp): cotangents of vertices, joints, joints_all, full_pose (None = zero) ->
+        (dbetas, dglobal_orient, dbody_pose, djaw_pose, dleye_pose, dreye_pose, dleft_hand_pose, dright_hand_pose), each [n, .].
+        No gradient flows through the contour landmarks' row choice."""
+        n, keep, par = self._smplx_params(betas, global_orient, body_pose, jaw_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose)
+        shapes = ((n, self.n_verts, 3), (n, self.n_joint_map, 3), (n, self.n_joints_all, 3), (n, 3 * self.n_joints))
+        cots = [None if a is None else _f32(a, sh) for a, sh in zip((dverts, djoints, djoints_all, dfull_pose), shapes)]
+        widths = (self.n_betas, 3, 63, 3, 3, 3, self.n_hand_pca, self.n_hand_pca)
+        grads = tuple(np.empty((n, w), np.float32) for w in widths)
+        cot = _lib.SmplxCotangents(*[_lib.fptr(a) for a in cots])
+        dst = _lib.SmplxGrads(*[_lib.fptr(g) for g in grads])
+        _lib.check(self._lib.bf_smplx_vjp(self._h, n, C.byref(par), C.byref(cot), C.byref(dst)), "bf_smplx_vjp")
+        return grads
 
     def forward_packed(self, params):
         """vertices / joints (model space) of packed parameter vectors [n, n_params] - any model kind"""

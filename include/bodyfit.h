@@ -156,6 +156,37 @@ int bf_smpl_vjp(bf_model *m, int n, const float *betas, const float *global_orie
                 const float *dvertices, const float *djoints, const float *djoints_ori,
                 float *dbetas, float *dglobal_orient, float *dbody_pose);
 
+/* smplx.create(model_type='smplx', use_pca=True, flat_hand_mean=False, use_face_contour=True)'s forward (smplify.py:59-80,
+ * 177-190) and its vector-Jacobian product for `n` parameter sets of an SMPL-X-kind model; SMPL-kind models: BF_ERR_UNSUPPORTED.
+ * `expression` is not an input: the device model carries the shape directions only (bf_model_create: n_betas <= 12), so the
+ * expression coefficients stay zero, as they do in the reference loop, which never optimises them (smplify.py:167-173). */
+typedef struct bf_smplx_params {          /* betas, global_orient, body_pose are required; a NULL among the others = zeros */
+    const float *betas;                    /* [n,NB] */
+    const float *global_orient;            /* [n,3] */
+    const float *body_pose;                /* [n,63] */
+    const float *jaw_pose, *leye_pose, *reye_pose;           /* [n,3] each */
+    const float *left_hand_pose, *right_hand_pose;           /* [n,n_hand_pca] PCA coefficients */
+} bf_smplx_params;
+typedef struct bf_smplx_outputs {         /* model space, no similarity; any may be NULL */
+    float *vertices;                       /* [n,NV,3] */
+    float *joints;                         /* [n,n_joint_map,3]: the 135 joints of the model's joint_map */
+    float *joints_all;                     /* [n,NJ+n_selector+n_extra+68,3]: the 144 joints smplx returns before a joint_mapper */
+    float *full_pose;                      /* [n,3 NJ]: the assembled pose, pose_mean included */
+    int32_t *dyn_row;                      /* [n]: the row of the contour table the neck chain's yaw selects */
+} bf_smplx_outputs;
+typedef struct bf_smplx_cotangents {      /* shapes of bf_smplx_outputs; a NULL = zero */
+    const float *dvertices, *djoints, *djoints_all, *dfull_pose;
+} bf_smplx_cotangents;
+typedef struct bf_smplx_grads {           /* shapes of bf_smplx_params; a NULL = not wanted */
+    float *dbetas, *dglobal_orient, *dbody_pose, *djaw_pose, *dleye_pose, *dreye_pose, *dleft_hand_pose, *dright_hand_pose;
+} bf_smplx_grads;
+/* With jaw_pose NULL, `vertices` and `joints` are bit for bit bf_model_forward's of the same values in packed order. */
+int bf_smplx_forward(bf_model *m, int n, const bf_smplx_params *in, const bf_smplx_outputs *out);
+/* Stateless like bf_smpl_vjp: the forward is recomputed by the call; every sum has a fixed order (no float atomics), so equal
+ * inputs give equal bits.  The contour landmarks' row is an integer look-up: no gradient flows through the choice, only through
+ * the barycentric combination of the chosen faces' vertices. */
+int bf_smplx_vjp(bf_model *m, int n, const bf_smplx_params *in, const bf_smplx_cotangents *cot, const bf_smplx_grads *grads);
+
 /* The model's forward for `n` packed parameter vectors params[n,n_params] (any model kind): vertices[n,NV,3] in
  * model space and joints[n,n_joint_map,3], both before the similarity (either may be NULL). */
 int bf_model_forward(bf_model *m, int n, const float *params, float *vertices, float *joints);

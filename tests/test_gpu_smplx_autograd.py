@@ -1,0 +1,292 @@
+"""The differentiable SMPL-X model behind smplx.create on the MI355X: bf_smplx_vjp (DeviceModel.vjp_smplx) against float64 torch
+autograd of the oracle's smplx forward, the integer contour row, the forward, determinism, the torch path's parity with the
+numpy path, and the oracle's restatement of the reference loop (smplify.py:177-213, torch Adam) run with its SMPL-X forward
+swapped for the HIP model under torch autograd.
+
+Band of the VJP (the convention of tests/test_gpu_smpl_autograd.py): max|HIP - fp64| <= 4 * max|torch fp32 - fp64| + 1e-6 * max|fp64|
+per gradient block.  Every test prints its figures before it asserts.  Checked without a GPU: every frame of every seed used here
+sits at least 1e-3 degrees from a rounding boundary of the contour row, fp32 and fp64 torch choose the same row on all of them, and
+the 8 x 17 frames of the branch test fall 46 / 22 / 38 / 30 into the four branches."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+from bodyfitting_amd import _lib, assets
+from bodyfitting_amd import native as N
+from bodyfitting_amd import synthetic as S
+from oracle import smplify_oracle as O
+
+pytestmark = pytest.mark.gpu
+SIZES = (1, 2, 3, 5, 8, 9, 17, 64)        # the 1-, 2-, 4- and 8-frame instances of the mesh reverse and their tails
+CASES = ("vertices", "joints", "joints_all", "full_pose", "all")
+INPUTS = ("betas", "global_orient", "body_pose", "jaw_pose", "leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose")
+COT_ARG = {"vertices": "dverts", "joints": "djoints", "joints_all": "djoints_all", "full_pose": "dfull_pose"}
+ROW_MARGIN = 1e-3                         # degrees between -yaw and the nearest rounding boundary of the contour row
+FIT_TOL = 1e-4
+BF_ERR_UNSUPPORTED = -3                   # include/bodyfit.h
+
+
+def _params(n, seed):
+    """Frame 0: eyes, jaw and hand PCA exactly zero (the reference's start: the Rodrigues singular point for eyes and jaw).
+    Frame 1 (n > 1): |theta| near pi at the root, at one body joint and at the jaw, hand PCA coefficients of order 1."""
+    rng = np.random.default_rng(seed)
+    p = {"betas": rng.normal(0, 0.7, (n, 10)), "global_orient": rng.normal(0, 0.8, (n, 3)), "body_pose": rng.normal(0, 0.3, (n, 63)),
+         "jaw_pose": rng.normal(0, 0.2, (n, 3)), "leye_pose": rng.normal(0, 0.2, (n, 3)), "reye_pose": rng.normal(0, 0.2, (n, 3)),
+         "left_hand_pose": rng.normal(0, 0.4, (n, 6)), "right_hand_pose": rng.normal(0, 0.4, (n, 6))}
+    p = {k: v.astype(np.float32) for k, v in p.items()}
+    for k in ("jaw_pose", "leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose"):
+        p[k][0] = 0.0
+    if n > 1:
+        p["global_orient"][1] = np.array([0.6, -0.48, 0.64], np.float32) * 3.13
+        p["body_pose"][1, 45:48] = np.array([-0.28, 0.96, 0.0], np.float32) * 3.1
+        p["jaw_pose"][1] = np.array([0.8, 0.0, -0.6], np.float32) * 3.12
+        p["left_hand_pose"][1] = np.array([1.2, -0.9, 1.0, 0.8, -1.1, 0.7], np.float32)
+        p["right_hand_pose"][1] = np.array([-1.0, 1.1, -0.8, 0.9, 1.2, -0.7], np.float32)
+    return p
+
+
+def _oracle(m, p, dtype, grad=False, mapped=False):
+    x = {k: torch.tensor(p[k], dtype=dtype, requires_grad=grad) for k in INPUTS}
+    out = O.smplx_forward(m, x["betas"], x["global_orient"], x["body_pose"], x["leye_pose"], x["reye_pose"], x["left_hand_pose"],
+                          x["right_hand_pose"], jaw_pose=x["jaw_pose"], mapped=mapped)
+    return x, out
+
+
+def _check_rows(dev, m64, p):
+    """dyn_row of the device == the fp64 oracle's for EVERY frame; the inputs must sit away from a rounding boundary"""
+    _, ref = _oracle(m64, p, torch.float64)
+    # -yaw in degrees, from the oracle's own full pose (the expressions of O.smplx_forward)
+    R = O.batch_rodrigues(ref["full_pose"].reshape(-1, 3)).view(len(p["betas"]), -1, 3, 3)
+    rel = torch.eye(3, dtype=torch.float64).unsqueeze(0).expand(len(p["betas"]), -1, -1)
+    for j in m64["neck_kin_chain"]:
+        rel = torch.bmm(R[:, int(j)], rel)
+    deg = (-torch.atan2(-rel[:, 2, 0], torch.sqrt(rel[:, 0, 0] ** 2 + rel[:, 1, 0] ** 2)) * 180.0 / np.pi).numpy()
+    margin = np.abs(deg - np.floor(deg) - 0.5)
+    assert (margin >= ROW_MARGIN).all(), ("a frame sits on a rounding boundary of the contour row: pick another seed", margin.min())
+    rows = ref["dyn_row"].numpy()
+    got = dev.forward_smplx(**p)["dyn_row"]
+    assert got.dtype == np.int32
+    np.testing.assert_array_equal(got, rows)
+    return rows
+
+
+def _cotangents(n, dev, seed):
+    rng = np.random.default_rng(seed + 100)
+    return {"vertices": rng.normal(0, 1, (n, dev.n_verts, 3)).astype(np.float32),
+            "joints": rng.normal(0, 1, (n, dev.n_joint_map, 3)).astype(np.float32),
+            "joints_all": rng.normal(0, 1, (n, dev.n_joints_all, 3)).astype(np.float32),
+            "full_pose": rng.normal(0, 1, (n, 3 * dev.n_joints)).astype(np.float32)}
+
+
+def _torch_grads(model, dtype, p, cot):
+    """per case: torch autograd of O.smplx_forward in `dtype` -> the eight gradient blocks as float64 numpy"""
+    m = O.to_torch_model(model, dtype)
+    x, out = _oracle(m, p, dtype, grad=True, mapped=False)
+    xm, mapped = _oracle(m, p, dtype, grad=True, mapped=True)
+    res = {}
+    for case in CASES:
+        keys = ("vertices", "joints", "joints_all", "full_pose") if case == "all" else (case,)
+        g = [np.zeros(p[k].shape) for k in INPUTS]
+        for k in keys:
+            src, xs = (mapped["joints"], xm) if k == "joints" else (out["joints" if k == "joints_all" else k], x)
+            gk = torch.autograd.grad((src * torch.as_tensor(cot[k], dtype=dtype)).sum(), [xs[i] for i in INPUTS], retain_graph=True,
+                                     allow_unused=True)
+            g = [a if b is None else a + b.detach().numpy().astype(np.float64) for a, b in zip(g, gk)]
+        res[case] = g
+    return res
+
+
+def _band_check(name, got, f32, f64):
+    err = float(np.abs(got.astype(np.float64) - f64).max())
+    ref_err = float(np.abs(f32 - f64).max())
+    band = 4 * ref_err + 1e-6 * float(np.abs(f64).max())
+    assert err <= band, (name, err, ref_err, band)
+    return err / band if band > 0 else 0.0
+
+
+def _vjp_against_autograd(dev, model, n, seed):
+    p = _params(n, seed)
+    cot = _cotangents(n, dev, seed)
+    _check_rows(dev, O.to_torch_model(model, torch.float64), p)
+    g64 = _torch_grads(model, torch.float64, p, cot)
+    g32 = _torch_grads(model, torch.float32, p, cot)
+    worst = 0.0
+    for case in CASES:
+        kw = {COT_ARG[k]: cot[k] for k in COT_ARG if case in (k, "all")}
+        got = dev.vjp_smplx(**p, **kw)
+        for i, name in enumerate(INPUTS):
+            assert got[i].dtype == np.float32 and got[i].shape == g64[case][i].shape
+            share = _band_check(f"n={n} {case} d{name}", got[i], g32[case][i], g64[case][i])
+            print(f"n={n} {case} d{name}: {share:.3f} of the band")
+            worst = max(worst, share)
+    print(f"n={n}: worst error at {worst:.2f} of the band")
+
+
+@pytest.fixture(scope="module")
+def full():
+    model = S.make_model("smplx", seed=0)
+    dev = N.DeviceModel(model, S.make_gmm(seed=0), device=0)
+    yield model, dev
+    dev.close()
+
+
+@pytest.fixture(scope="module")
+def small():
+    model = S.make_model("smplx", seed=0, nv=1200)        # 38 tiles: the split single-frame instance of the mesh reverse
+    dev = N.DeviceModel(model, S.make_gmm(seed=0), device=0)
+    yield model, dev
+    dev.close()
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_vjp_full_model_matches_fp64_autograd(full, n):
+    model, dev = full
+    assert dev.n_verts == 10475 and dev.n_joints_all == 144 and dev.n_joint_map == 135
+    _vjp_against_autograd(dev, model, n, seed=n)
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_vjp_small_model_matches_fp64_autograd(small, n):
+    model, dev = small
+    assert dev.n_verts == 1200
+    _vjp_against_autograd(dev, model, n, seed=50 + n)
+
+
+def test_contour_row_matches_the_oracle_on_every_frame_and_branch(small):
+    """8 seeds x 17 frames: the device's row is the fp64 oracle's on every frame, and the frames cover the four branches of
+    find_dynamic_lmk_idx_and_bcoords: 0..38, the clamp 39, 40..77 (negative yaw) and 78 (below -39 degrees)"""
+    model, dev = small
+    m64 = O.to_torch_model(model, torch.float64)
+    rows = np.concatenate([_check_rows(dev, m64, _params(17, seed)) for seed in range(200, 208)])
+    counts = [int(((rows >= 0) & (rows <= 38)).sum()), int((rows == 39).sum()), int(((rows >= 40) & (rows <= 77)).sum()), int((rows == 78).sum())]
+    print("frames per branch (0..38, 39, 40..77, 78):", counts)
+    assert len(rows) == 136 and sum(counts) == 136 and min(counts) > 0, counts
+
+
+@pytest.mark.parametrize("n", [1, 5])
+def test_forward_matches_the_oracle_and_the_packed_forward(full, n):
+    model, dev = full
+    p = _params(n, 300 + n)
+    m64 = O.to_torch_model(model, torch.float64)
+    _check_rows(dev, m64, p)
+    got = dev.forward_smplx(**p)
+    _, ref = _oracle(m64, p, torch.float64, mapped=False)
+    _, ref_m = _oracle(m64, p, torch.float64, mapped=True)
+    np.testing.assert_allclose(got["vertices"], ref["vertices"].numpy(), rtol=0, atol=3e-6)
+    np.testing.assert_allclose(got["joints"], ref_m["joints"].numpy(), rtol=0, atol=3e-6)
+    np.testing.assert_allclose(got["joints_all"], ref["joints"].numpy(), rtol=0, atol=3e-6)
+    np.testing.assert_allclose(got["full_pose"], ref["full_pose"].numpy(), rtol=0, atol=3e-6)
+    # without a jaw pose: bit for bit the packed forward of the same values
+    q = dict(p, jaw_pose=None)
+    got = dev.forward_smplx(**q)
+    packed = np.stack([N.pack_params({"global_transl": np.zeros(3), "scale": np.ones(1), "pose": p["body_pose"][i], "betas": p["betas"][i],
+                                      "global_orient": p["global_orient"][i], "leye_pose": p["leye_pose"][i], "reye_pose": p["reye_pose"][i],
+                                      "left_hand_pose": p["left_hand_pose"][i], "right_hand_pose": p["right_hand_pose"][i]})
+                       for i in range(n)]).astype(np.float32)
+    verts, joints = dev.forward_packed(packed)
+    np.testing.assert_array_equal(got["vertices"], verts)
+    np.testing.assert_array_equal(got["joints"], joints)
+
+
+def test_vjp_is_deterministic_and_smpl_models_are_refused(full, dev_model):
+    model, dev = full
+    n = 9
+    p = _params(n, 7)
+    cot = _cotangents(n, dev, 7)
+    kw = {COT_ARG[k]: cot[k] for k in COT_ARG}
+    a = dev.vjp_smplx(**p, **kw)
+    b = dev.vjp_smplx(**p, **kw)
+    for x, y in zip(a, b):
+        np.testing.assert_array_equal(x, y)
+    z = {"betas": np.zeros((1, 10)), "global_orient": np.zeros((1, 3)), "body_pose": np.zeros((1, 63))}
+    with pytest.raises(_lib.BodyfitError):
+        dev_model.forward_smplx(**z)
+    with pytest.raises(_lib.BodyfitError):
+        dev_model.vjp_smplx(**z, dverts=np.zeros((1, dev_model.n_verts, 3)))
+    # ... at the C ABI as well (the Python wrapper refuses first)
+    keep = [np.zeros((1, w), np.float32) for w in (10, 3, 63)]
+    par = _lib.SmplxParams(*[_lib.fptr(a) for a in keep])
+    out, cotz, gr = _lib.SmplxOutputs(), _lib.SmplxCotangents(), _lib.SmplxGrads()
+    assert dev_model._lib.bf_smplx_forward(dev_model._h, 1, C.byref(par), C.byref(out)) == BF_ERR_UNSUPPORTED
+    assert dev_model._lib.bf_smplx_vjp(dev_model._h, 1, C.byref(par), C.byref(cotz), C.byref(gr)) == BF_ERR_UNSUPPORTED
+    assert b"SMPL-X-kind" in dev_model._lib.bf_last_error()
+
+
+JOINT_MAPPER = dict(use_hands=True, use_face=True, use_face_contour=True, openpose_format="coco25")
+
+
+@pytest.fixture
+def dropin(full, gmm, monkeypatch):
+    """the model object smplify.py:59-80 creates, on the device model of this module"""
+    model, dev = full
+    monkeypatch.setattr(assets, "_MODELS", {("smplx", "neutral"): model})
+    monkeypatch.setattr(assets, "_GMM", {"gmm": gmm})
+    monkeypatch.setattr(assets, "_DEVICE_MODELS", {("smplx", "neutral", 0): dev})
+    from bodyfitting_amd import smplx as X
+    joint_mapper = X.JointMapper(X.smpl_to_openpose("smplx", **JOINT_MAPPER))
+    model_params = dict(model_path="data", model_type="smplx", joint_mapper=joint_mapper, ext="npz", gender="neutral",
+                        create_global_orient=True, create_body_pose=True, create_betas=True, create_left_hand_pose=True,
+                        create_right_hand_pose=True, create_expression=True, create_jaw_pose=True, create_leye_pose=True,
+                        create_reye_pose=True, create_transl=False, use_face_contour=True, dtype=torch.float32)
+    obj = X.create(**model_params).to(torch.device("cpu"))
+    assert obj._dev is dev
+    return obj
+
+
+def test_torch_path_matches_numpy_path_and_the_vjp(dropin):
+    n = 5
+    p = _params(n, 11)
+    dev = dropin._dev
+    ref = dropin(**p, return_full_pose=True)
+    direct = dev.forward_smplx(**p)
+    np.testing.assert_array_equal(ref.vertices, direct["vertices"])
+    np.testing.assert_array_equal(ref.joints, direct["joints"])          # the joint mapper's 135 = the model's joint_map
+    # the reference passes jaw and eyes as [B, 1, 3] (smplify.py:118-120)
+    x = {k: torch.tensor(p[k].reshape(n, 1, 3) if k in ("jaw_pose", "leye_pose", "reye_pose") else p[k], requires_grad=True) for k in INPUTS}
+    out = dropin(**x, return_full_pose=True)
+    for k in ("vertices", "joints", "full_pose"):
+        assert getattr(out, k).dtype == torch.float32
+        np.testing.assert_array_equal(getattr(out, k).detach().numpy(), getattr(ref, k))
+    cot = _cotangents(n, dev, 11)
+    total = sum((getattr(out, k) * torch.as_tensor(cot[k])).sum() for k in ("vertices", "joints", "full_pose"))
+    total.backward()
+    want = dev.vjp_smplx(**p, dverts=cot["vertices"], djoints=cot["joints"], dfull_pose=cot["full_pose"])
+    for k, w in zip(INPUTS, want):
+        assert x[k].grad.shape == x[k].shape
+        np.testing.assert_array_equal(x[k].grad.numpy().reshape(w.shape), w, err_msg=k)
+
+
+def test_oracle_loop_on_the_hip_model_holds_the_smplx_golden(monkeypatch, dropin, full, gmm_bufs):
+    """O.fit_smplx with its forward swapped for the drop-in under torch autograd reproduces tests/golden/smplx_8view_40it.npz"""
+    model, dev = full
+    rows = []
+
+    def shim(m, betas, global_orient, body_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose, jaw_pose=None, expression=None,
+             mapped=True):
+        out = dropin(betas=betas, global_orient=global_orient, body_pose=body_pose, leye_pose=leye_pose, reye_pose=reye_pose,
+                     left_hand_pose=left_hand_pose, right_hand_pose=right_hand_pose, jaw_pose=jaw_pose, return_full_pose=True)
+        rows.append(int(dropin.dyn_row[0]))
+        return {"vertices": out.vertices, "joints": out.joints, "full_pose": out.full_pose, "dyn_row": torch.as_tensor(dropin.dyn_row)}
+
+    monkeypatch.setattr(O, "smplx_forward", shim)
+    g = load_golden("smplx_8view_40it.npz")
+    prob = S.make_problem_smplx(model, frame=0, n_views=8)
+    res = O.fit_smplx(model, gmm_bufs, prob, 40, snapshots=(1, 2, 10, 40))
+    assert len(rows) == 40
+    worst = {}
+    for k in (1, 2, 10, 40):
+        for name in O.SMPLX_PARAMS:
+            worst[f"it{k}_{name}"] = float(np.abs(res["snapshots"][k][name] - g[f"it{k}_{name}"]).max())
+    worst["joints"] = float(np.abs(res["joints"] - g["joints"]).max())
+    worst["vertices"] = float(np.abs(res["vertices"][::53] - g["vertices_sample"]).max())
+    worst["full_pose"] = float(np.abs(res["full_pose"] - g["full_pose"]).max())
+    print("largest distance from the golden:", max(worst, key=worst.get), max(worst.values()))
+    for k in (1, 2, 10, 40):
+        for name in O.SMPLX_PARAMS:
+            np.testing.assert_allclose(res["snapshots"][k][name], g[f"it{k}_{name}"], rtol=0, atol=FIT_TOL, err_msg=f"it{k} {name}")
+    np.testing.assert_allclose(res["joints"], g["joints"], rtol=0, atol=FIT_TOL)
+    np.testing.assert_allclose(res["vertices"][::53], g["vertices_sample"], rtol=0, atol=FIT_TOL)
+    np.testing.assert_allclose(res["full_pose"], g["full_pose"], rtol=0, atol=FIT_TOL)
