@@ -20,6 +20,14 @@
 #define BF_GEMM_KB 26        // K pairs per register block of the pose-blend GEMM (A operand resident in VGPRs)  // from this batch size on the pose blend runs as one fp32-MFMA GEMM for all frames
 #define BF_MESH_TILE 32     // vertices per workgroup of the full-mesh forward
 #define BF_MESH_RG 8        // pose-feature row groups per workgroup (split-K inside the workgroup)
+// LDS tables of the body models' forward / reverse kernels (model_grad_kernels.hip); bf_grad_check (model_grad_api.hip) refuses a
+// model beyond them, so a kernel's arrays and the host's test read the same numbers
+#define BF_GRAD_MAX_ALL 192     // chain + selector + extra + landmark joints the fold stages (SMPL: 24 + 21 + 9, SMPL-X: 55 + 21 + 0 + 68)
+#define BF_GRAD_MAX_MAP 256     // joint_map entries (SMPL: 49, SMPL-X: 135)
+#define BF_GRAD_MAX_SEL 128     // selector vertices (21)
+#define BF_GRAD_MAX_LMK 96      // face landmarks (SMPL-X: 51 static + 17 on the contour), three (vertex, weight) entries each
+#define BF_GRAD_MAX_NP 128      // packed parameters per frame of the pose assembly (SMPL-X: 98)
+#define BF_GRAD_MAX_JOINTS 64   // chain joints: one lane each in the chain kernel's single wave (SMPL: 24, SMPL-X: 55)
 
 // Model-level tables of the fit, all resident in HBM for the life of the model.
 struct FitTab {

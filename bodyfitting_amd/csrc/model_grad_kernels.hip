@@ -1,36 +1,51 @@
-// Reverse of models.smpl.SMPL.forward (smplx lbs() + the wrapper of models/smpl.py:69-83) for gfx950: the two kernels the
-// stand-alone vector-Jacobian product bf_smpl_vjp (smpl_grad_api.hip) adds around the dense schedule's reverse mesh pass.
+// The body models' forward ends and reverse pass for gfx950: the kernels bf_smpl_vjp, bf_smplx_forward and bf_smplx_vjp
+// (model_grad_api.hip) add around the pose-state kernel, the dense schedule's mesh passes and bf_ext_reduce_kernel.  The reverse is
+// that of models.smpl.SMPL.forward (smplx lbs() + the wrapper of models/smpl.py:69-83) and of smplx.create(model_type='smplx').forward.
 //
-//   bf_smpl_vjp_fold_kernel   dL/d(joints49), dL/d(joints45), dL/dvertices -> dL/dvertices of the mesh reverse + dL/d(posed chain joints)
-//   bf_smpl_vjp_chain_kernel  the reduced mesh-reverse row + dL/d(posed chain joints) -> dL/dtheta, dL/dbeta
+//   bf_model_vjp_fold_kernel       dL/d(mapped joints), dL/d(smplx joints), dL/dvertices -> dL/dvertices of the mesh reverse + dL/d(posed chain joints)
+//   bf_smpl_vjp_chain_kernel       the reduced mesh-reverse row + dL/d(posed chain joints) -> dL/dtheta, dL/dbeta
+//   bf_smplx_pose_assemble_kernel  the eight parameter blocks -> full_pose (hands = PCA . components, + pose_mean, jaw as an input)
+//   bf_smplx_dyn_row_kernel        the contour-table row the neck chain's yaw selects (an output of the forward)
+//   bf_smplx_pose_reverse_kernel   dL/dtheta (+ dL/dfull_pose) -> the pass-through thetas and the hand PCA coefficients' gradients
 //
 // The math is the reverse half of oracle/analytic.py: loss_grad, with the skinning sums taken from bf_ext_reduce_kernel's row.
 // No float atomics: every sum has a fixed order, so a call's bits do not depend on timing.
+// The LDS tables are sized by BF_GRAD_MAX_* (bf_internal.h), which the host checks a model against.
 #include "bf_internal.h"
 #include "pose_state_body.h"
 
 #define BF_VJP_FOLD_THREADS 256
-#define BF_VJP_MAX_ALL 128     // chain + selector + extra joints the fold stages in LDS (SMPL: 24 + 21 + 9)
-#define BF_VJP_MAX_MAP 256     // joint_map entries (SMPL: 49)
-#define BF_VJP_MAX_JOINTS 64   // chain joints: one lane each in the chain kernel's single wave (SMPL: 24)
 
-// grid (ceil(NV / 256), n), 256 threads.  Per frame f:
-//   dall[j] = sum over i ascending with joint_map[i] == j of djoints[i]  (+ djoints_ori[j] for j < NJ + n_selector)
+// grid (ceil(NV / 256), n), 256 threads.  All joints in smplx order: chain | selector vertices | J_regressor_extra rows | landmarks
+// (nlm of them: the model's with lmk_vid given, none without - SMPL).  Per frame f:
+//   dall[j] = sum over i ascending with joint_map[i] == j of djoints[i]  (+ ddirect[j] for j < n_direct)
 //   dchain[f][j] = dall[j] for the NJ chain joints (workgroup x = 0 writes it)
 //   dv[f][v] = dvertices[f][v] + sum over s ascending with selector_ids[s] == v of dall[NJ + s]
 //              + sum over e ascending of J_regressor_extra[e][v] dall[NJ + n_selector + e]
-// Any of dvertices / djoints / djoints_ori may be null (= zero).
+//              + sum over the landmark entries q = 3 l + c ascending with lmk_vid[f][q] == v of lmk_w[f][q] dall[first landmark + l]
+// ddirect[n][n_direct][3]: the cotangent of the joints the model returns itself - SMPL's joints_ori (NJ + n_selector of them),
+// SMPL-X's joints_all (all).
+// lmk_vid / lmk_w: the corner vertices and barycentric weights the forward recompute used for this frame (bf_joints_body); the
+// row choice behind them is an integer look-up and carries no gradient.  Several landmarks share vertices, hence a gather.
+// Without landmarks their staging, its barrier and the last term are skipped, not taken as zero: -0 + 0 is +0, and SMPL's dv
+// keeps the sign it has without that term.
+// Any of dvertices / djoints / ddirect may be null (= zero).
 extern "C" __global__ void __launch_bounds__(BF_VJP_FOLD_THREADS)
-bf_smpl_vjp_fold_kernel(MeshTab M, const float *__restrict__ dvertices, const float *__restrict__ djoints, const float *__restrict__ djoints_ori,
-                        float *__restrict__ dv, float *__restrict__ dchain) {
-    __shared__ float s_dall[BF_VJP_MAX_ALL * 3];
-    __shared__ int s_map[BF_VJP_MAX_MAP];
-    __shared__ int s_sel[BF_VJP_MAX_ALL];
+bf_model_vjp_fold_kernel(MeshTab M, const float *__restrict__ dvertices, const float *__restrict__ djoints, const float *__restrict__ ddirect,
+                         int n_direct, const int *__restrict__ lmk_vid, const float *__restrict__ lmk_w, float *__restrict__ dv,
+                         float *__restrict__ dchain) {
+    __shared__ float s_dall[BF_GRAD_MAX_ALL * 3];
+    __shared__ int s_map[BF_GRAD_MAX_MAP];
+    __shared__ int s_sel[BF_GRAD_MAX_SEL];
+    __shared__ int s_lv[BF_GRAD_MAX_LMK * 3];
+    __shared__ float s_lc[BF_GRAD_MAX_LMK * 3 * 3];       // per entry: weight x the landmark's cotangent
     const int nj = M.nj, nv = M.nv, nsel = M.n_selector, ne = M.n_extra, nmap = M.n_joint_map;
-    const int n_ori = nj + nsel, n_all = n_ori + ne;
+    const int nlm = lmk_vid ? M.n_lmk_static + M.n_lmk_dyn : 0;
+    const int n_ori = nj + nsel, lm0 = n_ori + ne, n_all = lm0 + nlm;
     const int tid = threadIdx.x, f = blockIdx.y;
     for (int i = tid; i < nmap; i += BF_VJP_FOLD_THREADS) s_map[i] = M.joint_map[i];
     for (int i = tid; i < nsel; i += BF_VJP_FOLD_THREADS) s_sel[i] = M.selector_ids[i];
+    for (int i = tid; i < nlm * 3; i += BF_VJP_FOLD_THREADS) s_lv[i] = lmk_vid[(size_t)f * nlm * 3 + i];
     __syncthreads();
     for (int i = tid; i < n_all * 3; i += BF_VJP_FOLD_THREADS) {
         const int j = i / 3, k = i - j * 3;
@@ -40,14 +55,21 @@ bf_smpl_vjp_fold_kernel(MeshTab M, const float *__restrict__ dvertices, const fl
             for (int q = 0; q < nmap; ++q)
                 if (s_map[q] == j) acc += dj[q * 3];
         }
-        if (djoints_ori && j < n_ori) acc += djoints_ori[((size_t)f * n_ori + j) * 3 + k];
+        if (ddirect && j < n_direct) acc += ddirect[((size_t)f * n_direct + j) * 3 + k];
         s_dall[i] = acc;
         if (j < nj && blockIdx.x == 0) dchain[((size_t)f * nj + j) * 3 + k] = acc;
     }
     __syncthreads();
+    if (nlm) {                                                   // (block-uniform)
+        for (int i = tid; i < nlm * 9; i += BF_VJP_FOLD_THREADS) {
+            const int q = i / 3, k = i - q * 3, l = q / 3;
+            s_lc[i] = lmk_w[(size_t)f * nlm * 3 + q] * s_dall[(lm0 + l) * 3 + k];
+        }
+        __syncthreads();
+    }
     const int v = blockIdx.x * BF_VJP_FOLD_THREADS + tid;
     if (v >= nv) return;
-    float sel[3] = {0.f, 0.f, 0.f}, ext[3] = {0.f, 0.f, 0.f};
+    float sel[3] = {0.f, 0.f, 0.f}, ext[3] = {0.f, 0.f, 0.f}, lmk[3] = {0.f, 0.f, 0.f};
     for (int s = 0; s < nsel; ++s)
         if (s_sel[s] == v) {
             sel[0] += s_dall[(nj + s) * 3]; sel[1] += s_dall[(nj + s) * 3 + 1]; sel[2] += s_dall[(nj + s) * 3 + 2];
@@ -57,11 +79,14 @@ bf_smpl_vjp_fold_kernel(MeshTab M, const float *__restrict__ dvertices, const fl
         const float *d = s_dall + (n_ori + e) * 3;
         ext[0] += w * d[0]; ext[1] += w * d[1]; ext[2] += w * d[2];
     }
+    for (int q = 0; q < nlm * 3; ++q)                            // (every lane reads the same LDS word: a broadcast)
+        if (s_lv[q] == v) { lmk[0] += s_lc[q * 3]; lmk[1] += s_lc[q * 3 + 1]; lmk[2] += s_lc[q * 3 + 2]; }
     const size_t o = ((size_t)f * nv + v) * 3;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float g = dvertices ? dvertices[o + k] : 0.f;
-        dv[o + k] = (g + sel[k]) + ext[k];
+        const float body = (g + sel[k]) + ext[k];
+        dv[o + k] = nlm ? body + lmk[k] : body;
     }
 }
 
@@ -112,7 +137,7 @@ __device__ inline void vjp_rodrigues(const float *th, const float *dR, float *g)
 extern "C" __global__ void __launch_bounds__(64)
 bf_smpl_vjp_chain_kernel(FitTab T, const float *__restrict__ state, const float *__restrict__ ext, int ext_stride,
                          const float *__restrict__ dchain, float *__restrict__ dtheta, float *__restrict__ dbeta) {
-    constexpr int MJ = BF_VJP_MAX_JOINTS;
+    constexpr int MJ = BF_GRAD_MAX_JOINTS;
     __shared__ float s_R[MJ * 9], s_GR[MJ * 9], s_J[MJ * 3], s_dGR[MJ * 9], s_dGt[MJ * 3], s_dJ[MJ * 3], s_cGR[MJ * 9], s_drel[MJ * 3];
     __shared__ float s_dR[MJ * 9];
     const int nj = T.nj, nb = T.nb, npf = T.npf, tid = threadIdx.x, f = blockIdx.x;
@@ -213,5 +238,82 @@ bf_smpl_vjp_chain_kernel(FitTab T, const float *__restrict__ state, const float 
         float acc = 0.f;
         for (int r = 0; r < nj * 3; ++r) acc += T.Jd[r * nb + tid] * s_dJ[r];
         dbeta[(size_t)f * nb + tid] = row[npf + nj * 12 + tid] + acc;
+    }
+}
+
+// ---- the SMPL-X specific ends: what bf_smplx_forward / bf_smplx_vjp put before and behind the passes above
+
+// grid (n), one wave per frame.  The blocks go into the optimiser-order parameter vector in LDS and every joint's theta is then
+// bf_theta3 of it - the expressions bf_pose_state_kernel's packed path evaluates, so equal values give equal bits there and here.
+// The jaw (th_kind 1: a constant of the packed path) takes `jaw` on top when it is given.  leye / reye / lh / rh / jaw may be
+// null (= zeros).  Out: full[n][3 NJ], and the same thetas as bf_pose_state_kernel's non-packed path reads them:
+// th_root[n][3], th_rest[n][3 (NJ - 1)].
+extern "C" __global__ void __launch_bounds__(64)
+bf_smplx_pose_assemble_kernel(FitTab T, const float *__restrict__ orient, const float *__restrict__ body_pose, const float *__restrict__ jaw,
+                              const float *__restrict__ leye, const float *__restrict__ reye, const float *__restrict__ lh,
+                              const float *__restrict__ rh, float *__restrict__ full, float *__restrict__ th_root, float *__restrict__ th_rest) {
+    __shared__ float s_pk[BF_GRAD_MAX_NP];
+    const int tid = threadIdx.x, nj = T.nj, np = T.np, n_pca = T.n_pca;
+    const size_t f = blockIdx.x;
+    const int off_leye = T.off_orient + 3, off_reye = T.off_orient + 6;
+    for (int i = tid; i < np; i += 64) {
+        float x = 0.f;
+        if (i >= T.off_pose && i < T.off_pose + T.nbp) x = body_pose[f * T.nbp + (i - T.off_pose)];
+        else if (i >= T.off_orient && i < off_leye) x = orient[f * 3 + (i - T.off_orient)];
+        else if (i >= off_leye && i < off_reye) x = leye ? leye[f * 3 + (i - off_leye)] : 0.f;
+        else if (i >= off_reye && i < T.off_lh) x = reye ? reye[f * 3 + (i - off_reye)] : 0.f;
+        else if (i >= T.off_lh && i < T.off_rh) x = lh ? lh[f * n_pca + (i - T.off_lh)] : 0.f;
+        else if (i >= T.off_rh && i < T.off_rh + n_pca) x = rh ? rh[f * n_pca + (i - T.off_rh)] : 0.f;
+        s_pk[i] = x;
+    }
+    __syncthreads();
+    if (tid < nj) {
+        float th[3];
+        bf_theta3(s_pk, tid, th, T.th_kind, T.th_off, T.pose_mean, T.hand_comp, n_pca, T.off_lh, T.off_rh);
+        if (jaw && T.th_kind[tid] == 1) { th[0] += jaw[f * 3]; th[1] += jaw[f * 3 + 1]; th[2] += jaw[f * 3 + 2]; }
+        float *dst = tid == 0 ? th_root + f * 3 : th_rest + f * 3 * (nj - 1) + 3 * (tid - 1);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { full[f * 3 * nj + tid * 3 + k] = th[k]; dst[k] = th[k]; }
+    }
+}
+
+// One thread per frame: find_dynamic_lmk_idx_and_bcoords' row, the expression of bf_joints_body (joints_body.h) on the same state.
+extern "C" __global__ void __launch_bounds__(64)
+bf_smplx_dyn_row_kernel(MeshTab M, const float *__restrict__ state, int n, int *__restrict__ row) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= n) return;
+    StateView st = bf_state_view(const_cast<float *>(state) + (size_t)f * bf_state_stride(M.nj, M.npf, M.nb), M.nj, M.npf, M.nb);
+    const float *G = st.GR + M.neck_joint * 9;
+    float yaw = atan2f(-G[6], sqrtf(G[0] * G[0] + G[3] * G[3]));
+    int y = (int)rintf(fminf(-yaw * 180.0f / 3.14159265358979323846f, 39.f));
+    if (y < 0) y = y < -39 ? 78 : 39 - y;
+    row[f] = y;
+}
+
+// grid (n), one wave per frame: the reverse of bf_smplx_pose_assemble_kernel.  tot = dtheta (+ dfull_pose when given);
+//   out[f][0 .. 3 NJ)            = tot: the thetas that are inputs themselves (root, body, jaw, eyes) are read from here
+//   out[f][3 NJ + h n_pca + c]   = sum over k ascending of hand_comp[h][c][k] tot_hand_h[k]      (h = 0 left, 1 right; 45 entries)
+extern "C" __global__ void __launch_bounds__(64)
+bf_smplx_pose_reverse_kernel(FitTab T, const float *__restrict__ dtheta, const float *__restrict__ dfull, float *__restrict__ out) {
+    __shared__ float s_hand[2 * 45];
+    const int tid = threadIdx.x, nj = T.nj, n_pca = T.n_pca, stride = 3 * nj + 2 * n_pca;
+    const size_t f = blockIdx.x;
+    if (tid < nj) {
+        const int kind = T.th_kind[tid], off = T.th_off[tid];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const size_t i = f * 3 * nj + tid * 3 + k;
+            const float g = dfull ? dtheta[i] + dfull[i] : dtheta[i];
+            out[f * stride + tid * 3 + k] = g;
+            if (kind >= 2) s_hand[(kind - 2) * 45 + off * 3 + k] = g;
+        }
+    }
+    __syncthreads();
+    if (tid < 2 * n_pca) {
+        const int h = tid / n_pca;
+        const float *comp = T.hand_comp + (size_t)tid * 45;          // [2][n_pca][45]
+        float acc = 0.f;
+        for (int k = 0; k < 45; ++k) acc += comp[k] * s_hand[h * 45 + k];
+        out[f * stride + 3 * nj + tid] = acc;
     }
 }

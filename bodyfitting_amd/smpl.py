@@ -15,7 +15,7 @@ from dataclasses import dataclass, asdict
 
 import numpy as np
 
-from . import assets
+from . import _autograd, assets
 
 
 @dataclass
@@ -68,7 +68,8 @@ class SMPL:
         like = next(x for x in (betas, global_orient, body_pose, transl) if _is_tensor(x))
         betas, global_orient, body_pose = (x if _is_tensor(x) else torch.as_tensor(np.asarray(x), dtype=like.dtype, device=like.device)
                                            for x in (betas, global_orient, body_pose))
-        verts, joints, jori = _smpl_function().apply(self._dev, betas, global_orient, body_pose)
+        dev = self._dev
+        verts, joints, jori = _autograd.apply(dev.forward, lambda x, cot: dev.vjp(*x, *cot), (betas, global_orient, body_pose))
         if transl is not None:
             # smplx adds transl to the vertices and its 45 joints; the wrapper's 9 extra joints are J_regressor_extra (v + t), i.e. each
             # moves by its regressor row's sum times t (models/smpl.py:71-75)
@@ -98,42 +99,3 @@ class SMPL:
 
 def _is_tensor(x):
     return hasattr(x, "detach") and hasattr(x, "requires_grad")
-
-
-_FUNCTION = []
-
-
-def _smpl_function():
-    """The torch.autograd.Function of the torch path, defined on first use: forward = DeviceModel.forward, backward =
-    DeviceModel.vjp, both through host memory.  Outputs come back as the device model returns them (float32 for the HIP model)
-    on the inputs' device.  Once differentiable."""
-    if _FUNCTION:
-        return _FUNCTION[0]
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    def host(t):
-        return None if t is None else t.detach().cpu().numpy()
-
-    class SMPLFunction(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, dev, betas, global_orient, body_pose):
-            ctx.set_materialize_grads(False)            # (an unused output's cotangent stays None = zero: nothing is copied for it)
-            ctx.dev = dev
-            ctx.save_for_backward(betas, global_orient, body_pose)
-            out = dev.forward(host(betas), host(global_orient), host(body_pose))
-            return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(betas.device) for a in out)
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, dverts, djoints, djoints_ori):
-            betas, global_orient, body_pose = ctx.saved_tensors
-            want = ctx.needs_input_grad[1:]
-            if not any(want) or (dverts is None and djoints is None and djoints_ori is None):
-                return None, None, None, None
-            grads = ctx.dev.vjp(host(betas), host(global_orient), host(body_pose), host(dverts), host(djoints), host(djoints_ori))
-            return (None,) + tuple(torch.from_numpy(np.ascontiguousarray(g)).reshape(x.shape).to(x.device) if w else None
-                                   for g, x, w in zip(grads, (betas, global_orient, body_pose), want))
-
-    _FUNCTION.append(SMPLFunction)
-    return SMPLFunction

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import assets, layout
+from . import _autograd, assets, layout
 from .smpl import SMPL, ModelOutput, _is_tensor
 
 N_CONTOUR = 17          # the landmarks `use_face_contour` adds at the end of smplx's joints
@@ -143,7 +143,17 @@ class SMPLX:
             elif v is not None and not _is_tensor(v):
                 v = torch.as_tensor(np.asarray(v), dtype=like.dtype, device=like.device)
             x[k] = v
-        verts, joints_all, full_pose = _smplx_function().apply(self._dev, self, *[x[k] for k in _INPUTS])
+        dev = self._dev
+
+        def forward(*arrays):
+            out = dev.forward_smplx(*arrays)
+            self.dyn_row = out["dyn_row"]
+            return out["vertices"], out["joints_all"], out["full_pose"]
+
+        def vjp(arrays, cot):
+            return dev.vjp_smplx(*arrays, dverts=cot[0], djoints_all=cot[1], dfull_pose=cot[2])
+
+        verts, joints_all, full_pose = _autograd.apply(forward, vjp, [x[k] for k in _INPUTS])
         joints = self._map(joints_all)
         if transl is not None:                          # smplx: joints += transl.unsqueeze(1); vertices += transl.unsqueeze(1)
             t = transl if _is_tensor(transl) else torch.as_tensor(np.asarray(transl), dtype=verts.dtype, device=verts.device)
@@ -166,48 +176,3 @@ def create(model_path=None, model_type="smpl", **kwargs):
     if kind == "smpl":
         return SMPL(model_path, **kwargs)
     raise NotImplementedError(f"model_type={model_type!r}: 'smpl' and 'smplx' run on the device")
-
-
-_FUNCTION = []
-
-
-def _smplx_function():
-    """The torch.autograd.Function of the torch path, defined on first use: forward = DeviceModel.forward_smplx, backward =
-    DeviceModel.vjp_smplx, both through host memory.  Returns vertices, joints_all, full_pose as the device model returns them
-    (float32 for the HIP model) on the inputs' device.  Once differentiable."""
-    if _FUNCTION:
-        return _FUNCTION[0]
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    def host(t):
-        return None if t is None else t.detach().cpu().numpy()
-
-    class SMPLXFunction(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, dev, owner, *inputs):
-            ctx.set_materialize_grads(False)            # (an unused output's cotangent stays None = zero: nothing is copied for it)
-            ctx.dev = dev
-            ctx.present = [t is not None for t in inputs]
-            ctx.save_for_backward(*[t for t in inputs if t is not None])
-            out = dev.forward_smplx(*[host(t) for t in inputs])
-            owner.dyn_row = out["dyn_row"]
-            device = inputs[0].device
-            return tuple(torch.from_numpy(np.ascontiguousarray(out[k])).to(device) for k in ("vertices", "joints_all", "full_pose"))
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, dverts, djoints_all, dfull_pose):
-            saved = iter(ctx.saved_tensors)
-            inputs = [next(saved) if p else None for p in ctx.present]
-            want = ctx.needs_input_grad[2:]
-            if not any(want) or (dverts is None and djoints_all is None and dfull_pose is None):
-                return (None,) * (2 + len(inputs))
-            grads = ctx.dev.vjp_smplx(*[host(t) for t in inputs], dverts=host(dverts), djoints_all=host(djoints_all),
-                                      dfull_pose=host(dfull_pose))
-            return (None, None) + tuple(
-                torch.from_numpy(np.ascontiguousarray(g)).reshape(x.shape).to(device=x.device, dtype=x.dtype) if w else None
-                for g, x, w in zip(grads, inputs, want))
-
-    _FUNCTION.append(SMPLXFunction)
-    return SMPLXFunction

@@ -33,12 +33,13 @@ def timed(fn, reps, warmup):
     return float(np.median(ts)), float(np.min(ts))
 
 
-def summarize(db):
+def summarize(db, opens="bf_pose_state_kernel"):
+    """`opens`: the kernel whose dispatch starts a call of the tool that was traced"""
     import sqlite3
     rows = sqlite3.connect(db).execute("select name, grid_x, workgroup_x, duration from kernels order by start").fetchall()
     calls, cur = [], None
     for name, gx, wx, dur in rows:
-        if name.startswith("bf_pose_state_kernel"):
+        if name.startswith(opens):
             cur = {"n": gx // wx, "kernels": {}}
             calls.append(cur)
         if cur is not None:
@@ -46,7 +47,7 @@ def summarize(db):
             cur["kernels"][k] = cur["kernels"].get(k, 0.0) + dur * 1e-3
     groups = {}
     for c in calls:
-        kind = "vjp" if "bf_smpl_vjp_fold_kernel" in c["kernels"] else "forward"
+        kind = "vjp" if "bf_model_vjp_fold_kernel" in c["kernels"] else "forward"
         groups.setdefault((c["n"], kind), []).append(c["kernels"])
     for (n, kind), cs in sorted(groups.items()):
         names = sorted({k for c in cs for k in c})

@@ -22,28 +22,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bodyfitting_amd import native as N, synthetic as S   # noqa: E402
-from bench_smpl_grad import timed                         # noqa: E402
-
-
-def summarize(db):
-    import sqlite3
-    rows = sqlite3.connect(db).execute("select name, grid_x, workgroup_x, duration from kernels order by start").fetchall()
-    calls, cur = [], None
-    for name, gx, wx, dur in rows:
-        if name.startswith("bf_smplx_pose_assemble_kernel"):
-            cur = {"n": gx // wx, "kernels": {}}
-            calls.append(cur)
-        if cur is not None:
-            k = "copies (runtime)" if name.startswith("__amd_rocclr") else name.split("(")[0]
-            cur["kernels"][k] = cur["kernels"].get(k, 0.0) + dur * 1e-3
-    groups = {}
-    for c in calls:
-        kind = "vjp" if "bf_smplx_vjp_fold_kernel" in c["kernels"] else "forward"
-        groups.setdefault((c["n"], kind), []).append(c["kernels"])
-    for (n, kind), cs in sorted(groups.items()):
-        names = sorted({k for c in cs for k in c})
-        mean = {k: round(sum(c.get(k, 0.0) for c in cs) / len(cs), 2) for k in names}
-        print(json.dumps({"n": n, "call": kind, "calls": len(cs), "device_us_per_call": round(sum(mean.values()), 1), "kernels_us": mean}))
+from bench_smpl_grad import summarize, timed                     # noqa: E402
 
 
 def main():
@@ -55,7 +34,7 @@ def main():
     ap.add_argument("--summarize", metavar="DB", help="print the kernel split of a rocprofv3 run of this tool and exit")
     a = ap.parse_args()
     if a.summarize:
-        return summarize(a.summarize)
+        return summarize(a.summarize, opens="bf_smplx_pose_assemble_kernel")
     gmm = S.make_gmm(seed=0)
     dev = N.DeviceModel(S.make_model("smplx", seed=0), gmm, device=0)
     smpl = None if a.no_smpl else N.DeviceModel(S.make_model("smpl", seed=0), gmm, device=0)
