@@ -54,6 +54,13 @@ class SmplxGrads(C.Structure):           # bf_smplx_grads
         "dbetas", "dglobal_orient", "dbody_pose", "djaw_pose", "dleye_pose", "dreye_pose", "dleft_hand_pose", "dright_hand_pose")]
 
 
+class KeypointLossIn(C.Structure):      # bf_keypoint_loss_in
+    _fields_ = [("n", C.c_int32), ("n_views", C.c_int32), ("n_rows", C.c_int32),
+                ("joints", C.POINTER(C.c_float)), ("w2c", C.POINTER(C.c_float)), ("K", C.POINTER(C.c_float)),
+                ("keypoints", C.POINTER(C.c_float)), ("present", C.POINTER(C.c_uint8)), ("divisor", C.POINTER(C.c_int32)),
+                ("pose_dim", C.c_int32), ("poses", C.POINTER(C.c_float)), ("n_betas", C.c_int32), ("betas", C.POINTER(C.c_float))]
+
+
 class Hyper(C.Structure):
     _fields_ = [(n, C.c_float) for n in (
         "sigma", "pose_prior_weight", "angle_prior_weight", "shape_prior_weight", "constant_scale",
@@ -86,6 +93,9 @@ SIGNATURES = {
     "bf_smpl_vjp": (C.c_int, [_VP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "bf_smplx_forward": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), C.POINTER(SmplxOutputs)]),
     "bf_smplx_vjp": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), C.POINTER(SmplxCotangents), C.POINTER(SmplxGrads)]),
+    "bf_gmm_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.POINTER(_VP)]),
+    "bf_gmm_destroy": (None, [_VP]),
+    "bf_keypoint_loss": (C.c_int, [C.c_int, _VP, C.POINTER(KeypointLossIn), C.POINTER(Hyper), _FP, _FP, _FP, _FP, _FP]),
     "bf_batch_create": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(_VP)]),
     "bf_batch_destroy": (None, [_VP]),
     "bf_batch_set_cameras": (C.c_int, [_VP, _FP, _FP]),

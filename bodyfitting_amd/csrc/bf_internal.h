@@ -28,6 +28,24 @@
 #define BF_GRAD_MAX_LMK 96      // face landmarks (SMPL-X: 51 static + 17 on the contour), three (vertex, weight) entries each
 #define BF_GRAD_MAX_NP 128      // packed parameters per frame of the pose assembly (SMPL-X: 98)
 #define BF_GRAD_MAX_JOINTS 64   // chain joints: one lane each in the chain kernel's single wave (SMPL: 24, SMPL-X: 55)
+// LDS tables of the stand-alone keypoint loss (kp_loss_kernels.hip); bf_kp_loss_check (kp_loss_api.hip) refuses a call beyond them
+#define BF_KPL_MAX_ROWS 256     // joint rows of a problem (SMPL: 25, SMPL-X with hands + face: 135)
+#define BF_KPL_MAX_DIM 128      // dimension of the GMM prior (69)
+#define BF_KPL_MAX_COMP 16      // its components (8)
+#define BF_KPL_MAX_BETAS 16     // shape coefficients (10, kid: 11)
+#define BF_KPL_THREADS 512
+#define BF_KPL_CHUNK 64         // views whose cameras are staged in LDS at a time
+
+// One launch of bf_keypoint_loss_kernel: `n` problems, one workgroup each.  Any pointer may be null as include/bodyfit.h says.
+struct KpLossIO {
+    int n_views, n_rows, pose_dim, n_betas, gmm_comp, gmm_dim;
+    const float *joints, *w2c, *K, *keypoints;
+    const unsigned char *present;
+    const int *divisor;
+    const float *poses, *betas, *dterms;
+    const float *g_means, *g_prec, *g_logw;
+    float *terms, *djoints, *dposes, *dbetas;
+};
 
 // Model-level tables of the fit, all resident in HBM for the life of the model.
 struct FitTab {

@@ -1,0 +1,201 @@
+"""`smplify.loss` of the reference (smplify/loss.py) on the HIP path: `multiview_keypoint_loss` - the reprojection term over the
+views, MaxMixturePrior's merged likelihood, the angle prior and the shape prior - as ONE kernel launch (bf_keypoint_loss) and,
+for torch tensors, its vector-Jacobian product behind a torch.autograd.Function.  This is the second half of a user's own
+optimisation loop (smplify.py:177-213); the first half is the body model (smpl.py, smplx.py).
+
+torch tensors in -> (total, losses) with `total` a float32 scalar tensor on model_joints' device, differentiable (once) with respect
+to model_joints, poses and betas; numpy in -> floats out.  torch is imported only when tensors arrive.
+
+`perspective_projection`, `gmof`, `angle_prior` and `reprojection_loss` are the reference's small functions, in torch or numpy as
+their arguments are.  The silhouette, scan and SMPL+D losses run fused inside `SMPLify`; their stand-alone versions are not here yet
+and raise NotImplementedError.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _autograd
+from .keypoints import FACE_MAPPING, pack_keypoints_smplx          # noqa: F401  (FACE_MAPPING: a name of loss.py, re-exported)
+from . import prior as _prior
+
+SKELETON_LENGTH = 25          # loss.py:17-20
+HANDS_LENGTH = 42
+FACE_LENGTH = 68
+LOSS_KEYS = ("reprojection_loss", "pose_prior_loss", "angle_prior_loss", "shape_prior_loss")
+_ANGLE_IDX, _ANGLE_SIGN = [55 - 3, 58 - 3, 12 - 3, 15 - 3], [1.0, -1.0, -1.0, -1.0]
+
+
+def _is_tensor(x):
+    return hasattr(x, "detach") and hasattr(x, "requires_grad")
+
+
+def _host(a, dtype=np.float32):
+    return np.asarray(a.detach().cpu().numpy() if _is_tensor(a) else a, dtype)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the reference's small functions (loss.py:22-61,132-136)
+# ----------------------------------------------------------------------------------------------------------------------------
+
+def perspective_projection(points, rotation, translation, K):
+    """points[bs,N,3], rotation[bs,3,3], translation[bs,3], K[3,3] -> [bs,N,2] (loss.py:22-43: no epsilon on the depth)"""
+    if _is_tensor(points):
+        import torch
+        K = torch.as_tensor(np.asarray(K), dtype=torch.float32, device=points.device) if isinstance(K, np.ndarray) else K
+        cam = torch.einsum("bij,bkj->bki", rotation, points) + translation.unsqueeze(1)
+        pix = torch.einsum("ij,bkj->bki", K, cam)
+    else:
+        points, rotation, translation, K = (np.asarray(a) for a in (points, rotation, translation, K))
+        cam = np.einsum("bij,bkj->bki", rotation, points) + translation[:, None]
+        pix = np.einsum("ij,bkj->bki", K, cam)
+    return (pix / pix[:, :, -1:])[:, :, :-1]
+
+
+def gmof(x, sigma):
+    """Geman-McClure error function (loss.py:45-51)"""
+    x_squared, sigma_squared = x ** 2, sigma ** 2
+    return (sigma_squared * x_squared) / (sigma_squared + x_squared)
+
+
+def angle_prior(pose):
+    """exp(theta * sign) ** 2 on the knees' and elbows' bending dofs (loss.py:54-61), pose[B, >= 56] -> [B, 4]"""
+    if _is_tensor(pose):
+        import torch
+        return torch.exp(pose[:, _ANGLE_IDX] * torch.tensor(_ANGLE_SIGN, device=pose.device, dtype=pose.dtype)) ** 2
+    pose = np.asarray(pose)
+    return np.exp(pose[:, _ANGLE_IDX] * np.asarray(_ANGLE_SIGN, pose.dtype)) ** 2
+
+
+def reprojection_loss(cord, cord_gt, conf, scale_coeff, sigma):
+    """loss.py:132-136"""
+    err = gmof((cord_gt - cord) / scale_coeff, sigma)
+    return ((conf ** 2) * err.sum(-1)).sum(-1)
+
+
+def _fused_only(name):
+    def stub(*args, **kwargs):
+        raise NotImplementedError(f"smplify.loss.{name}: SMPLify runs this loss fused inside its fit kernels "
+                                  "(bodyfitting_amd.smplify); the stand-alone differentiable version is a follow-up")
+    stub.__name__ = name
+    return stub
+
+
+multview_mask_loss = _fused_only("multview_mask_loss")
+extract_countours = _fused_only("extract_countours")
+point_cloud_loss_mesh_grid = _fused_only("point_cloud_loss_mesh_grid")
+normal_loss_mesh_grid = _fused_only("normal_loss_mesh_grid")
+normal_laplacian_smoothness = _fused_only("normal_laplacian_smoothness")
+point_cloud_loss_chamfer_naive = _fused_only("point_cloud_loss_chamfer_naive")
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# multiview_keypoint_loss (loss.py:139-230)
+# ----------------------------------------------------------------------------------------------------------------------------
+
+def _no_grad_input(name, x):
+    items = x if isinstance(x, (list, tuple)) else [x]
+    for it in items:
+        values = it.values() if isinstance(it, dict) else [it]
+        if any(_is_tensor(v) and v.requires_grad for v in values):
+            raise ValueError(f"multiview_keypoint_loss: {name} requires grad; gradients flow to model_joints, poses and betas only")
+
+
+def _pack_views(w2cs, Ks, keypoints, n_use, use_hand_face, rows):
+    """-> w2c[1,V,4,4], K[1,V,3,3], kp[1,V,rows,3], present[1,V] over the V = len(use_frames) views the reference loops over"""
+    if len(keypoints) < n_use or len(w2cs) < n_use or len(Ks) < n_use:
+        raise ValueError(f"multiview_keypoint_loss: {n_use} use_frames but fewer cameras or keypoint entries")
+    w2c = np.stack([_host(w2cs[i]).reshape(4, 4) for i in range(n_use)])[None]
+    K = np.stack([_host(Ks[i]).reshape(3, 3) for i in range(n_use)])[None]
+    kp = np.zeros((1, n_use, rows, 3), np.float32)
+    present = np.zeros((1, n_use), np.uint8)
+    groups = {"hand": False, "face": False}
+    for i in range(n_use):
+        k = keypoints[i]
+        if k is None:                                              # loss.py:157
+            continue
+        present[0, i] = 1
+        if use_hand_face:
+            # (hands and face: every joint of a part weighted by the part's summed squared confidences, loss.py:168-181 - keypoints.py)
+            kp[0, i] = pack_keypoints_smplx({part: _host(a) for part, a in k.items()})
+            groups["hand"] |= "hand_left" in k or "hand_right" in k
+            groups["face"] |= "face" in k
+        else:
+            kp[0, i] = _host(k["pose"])[:SKELETON_LENGTH]
+    if not present.any():
+        raise ValueError("multiview_keypoint_loss: no view has keypoints (the reference fails in torch.stack)")
+    if use_hand_face:
+        for name, seen in groups.items():
+            if not seen:
+                raise ValueError(f"multiview_keypoint_loss: use_hand_face with no {name} keypoints in any view (the reference fails in torch.stack)")
+    return w2c, K, kp, present
+
+
+def multiview_keypoint_loss(w2cs, Ks, keypoints, model_joints, poses, betas, use_frames, pose_prior, sigma=100,
+                            shape_prior_weight=5, angle_prior_weight=15.2, output='sum', debug=False, imsize=512,
+                            pose_prior_weight=4.78, use_hand_face=False, output_folder=None, verts=None, device=None):
+    """The reference's signature plus `device` (the GPU; None: the prior's, else 0).  w2cs[V,4,4], Ks[V,3,3] (tensors, arrays or
+    lists of them), keypoints: per view None or the OpenPose dict ('pose', with use_hand_face optionally 'hand_left', 'hand_right',
+    'face'), model_joints[1,J,3] (the first 25 are compared; with use_hand_face J = 135), poses[1,69] (63 with use_hand_face),
+    betas[1,NB].  pose_prior: this project's MaxMixturePrior, any object with means / precisions / nll_weights, or another
+    callable (called as pose_prior(poses69, None) outside the kernel).  -> (total, {four terms as host values}).
+    debug, output_folder and verts are accepted and ignored (their use is commented out in the reference)."""
+    from . import native
+    if output != 'sum':
+        raise ValueError("multiview_keypoint_loss: only output='sum' is supported (the reference returns a function object otherwise)")
+    tensors = any(_is_tensor(x) for x in (model_joints, poses, betas))
+    for name, x in (("model_joints", model_joints), ("poses", poses), ("betas", betas)):
+        if tensors and not _is_tensor(x):
+            raise ValueError(f"multiview_keypoint_loss: {name} is not a tensor while others are")
+        _prior._require_float32("multiview_keypoint_loss", name, x)
+    for name, x in (("w2cs", w2cs), ("Ks", Ks), ("keypoints", [k for k in keypoints if k is not None])):
+        _no_grad_input(name, x)
+    if model_joints.ndim != 3 or model_joints.shape[0] != 1 or poses.shape[0] != 1 or betas.shape[0] != 1:
+        raise ValueError("multiview_keypoint_loss: batch size must be 1 (the reference projects row 0 only)")
+    rows = SKELETON_LENGTH + HANDS_LENGTH + FACE_LENGTH if use_hand_face else SKELETON_LENGTH
+    if model_joints.shape[1] < rows or (use_hand_face and model_joints.shape[1] != rows):
+        raise ValueError(f"multiview_keypoint_loss: model_joints has {model_joints.shape[1]} joints, {rows} are compared")
+    n_use = len(use_frames)
+    w2c, K, kp, present = _pack_views(w2cs, Ks, keypoints, n_use, use_hand_face, rows)
+    divisor = np.array([n_use], np.int32)
+
+    gmm, generic = None, None
+    if isinstance(pose_prior, _prior.MaxMixturePrior) or _prior.is_gmm_like(pose_prior):
+        gmm = _prior.device_gmm(pose_prior, device)
+    elif callable(pose_prior):
+        generic = pose_prior
+    else:
+        raise ValueError("multiview_keypoint_loss: pose_prior must be a MaxMixturePrior, an object with its buffers, or a callable")
+    if device is None:
+        device = gmm.device if gmm is not None else 0
+    hyper = native.make_hyper(sigma=sigma, shape_prior_weight=shape_prior_weight, angle_prior_weight=angle_prior_weight,
+                              pose_prior_weight=pose_prior_weight, imsize=imsize)
+    common = dict(w2c=w2c, K=K, keypoints=kp, present=present, divisor=divisor, gmm=gmm, hyper=hyper, device=device)
+
+    def forward(j, p, b):
+        return (native.keypoint_loss(j, poses=p, betas=b, want=("terms",), **common)["terms"],)
+
+    def vjp(arrays, cotangents):
+        j, p, b = arrays
+        out = native.keypoint_loss(j, poses=p, betas=b, dterms=cotangents[0], want=("djoints", "dposes", "dbetas"), **common)
+        return out["djoints"], out["dposes"], out["dbetas"]
+
+    w2 = pose_prior_weight ** 2
+    if not tensors:
+        terms = forward(np.asarray(model_joints)[:, :rows], np.asarray(poses), np.asarray(betas))[0][0]
+        losses = {k: float(terms[i]) for i, k in enumerate(LOSS_KEYS)}
+        if generic is not None:
+            p69 = np.concatenate([np.asarray(poses), np.zeros_like(np.asarray(poses)[:, :6])], -1) if use_hand_face else np.asarray(poses)
+            losses["pose_prior_loss"] = float(w2 * np.asarray(_host(generic(p69, None))).reshape(-1)[0])
+        return float(sum(losses.values())), losses
+
+    import torch
+    terms = _autograd.apply(forward, vjp, (model_joints[:, :rows], poses, betas))[0]
+    total = terms.sum()
+    host = terms.detach().cpu().numpy()
+    losses = {"reprojection_loss": host[0, 0], "pose_prior_loss": host[:, 1], "angle_prior_loss": host[:, 2], "shape_prior_loss": host[:, 3]}
+    if generic is not None:
+        p69 = torch.cat([poses, torch.zeros_like(poses[:, :6])], dim=-1) if use_hand_face else poses          # loss.py:206-207
+        extra = w2 * generic(p69, None)
+        total = total + extra.sum()
+        losses["pose_prior_loss"] = extra.detach().cpu().numpy()
+    return total, losses

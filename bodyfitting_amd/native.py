@@ -313,6 +313,101 @@ def make_hyper(**kw):
     return h
 
 
+class Gmm:
+    """MaxMixturePrior's buffers (means[M,D], precisions[M,D,D], nll_weights[M]) uploaded once to one GPU (bf_gmm)."""
+
+    def __init__(self, means, precisions, nll_weights, device=0):
+        lib = _lib.load()
+        self._lib = lib
+        means = _f32(means)
+        self.n_components, self.dim = means.shape
+        prec = _f32(precisions, (self.n_components, self.dim, self.dim))
+        nllw = _f32(nll_weights, (self.n_components,))
+        self.device = int(device)
+        self._h = C.c_void_p()
+        _lib.check(lib.bf_gmm_create(self.device, self.n_components, self.dim, _lib.fptr(means), _lib.fptr(prec), _lib.fptr(nllw),
+                                     C.byref(self._h)), "bf_gmm_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bf_gmm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+KP_LOSS_OUTPUTS = ("terms", "djoints", "dposes", "dbetas")
+
+
+def keypoint_loss(joints, w2c=None, K=None, keypoints=None, present=None, divisor=None, poses=None, betas=None, gmm=None, hyper=None,
+                  dterms=None, want=KP_LOSS_OUTPUTS, device=0):
+    """bf_keypoint_loss: multiview_keypoint_loss (loss.py:139-230) of n independent problems and its vector-Jacobian product.
+    joints[n,R,3] (None: no rows), w2c[n,V,4,4], K[n,V,3,3], keypoints[n,V,R,3], present[n,V] (None: all), divisor[n] - w2c None =
+    no views; poses[n,pose_dim] / betas[n,NB] (None: that prior is off); gmm: a `Gmm` or None; hyper: make_hyper(...) or None;
+    dterms[n,4] (None: ones).  -> dict over `want` (a subset of KP_LOSS_OUTPUTS): terms[n,4], djoints[n,R,3], dposes, dbetas."""
+    unknown = set(want) - set(KP_LOSS_OUTPUTS)
+    if unknown:
+        raise TypeError(f"unknown output(s) {sorted(unknown)}")
+    if ("dposes" in want and poses is None) or ("dbetas" in want and betas is None):
+        raise ValueError("keypoint_loss: a gradient was asked for an input that was not passed")
+    q = _lib.KeypointLossIn()
+    keep = {}
+    if joints is not None:
+        keep["joints"] = _f32(joints)
+        if keep["joints"].ndim != 3 or keep["joints"].shape[2] != 3:
+            raise ValueError("joints must be [n, rows, 3]")
+        n, rows = keep["joints"].shape[:2]
+    else:
+        first = poses if poses is not None else betas
+        if first is None:
+            raise ValueError("keypoint_loss needs joints, poses or betas")
+        n, rows = np.asarray(first).reshape(-1, np.asarray(first).shape[-1]).shape[0], 0
+    n_views = 0
+    if w2c is not None:
+        keep["w2c"] = _f32(w2c)
+        n_views = keep["w2c"].shape[1] if keep["w2c"].ndim == 4 else -1
+        keep["w2c"] = keep["w2c"].reshape(n, n_views, 4, 4)
+        keep["K"] = _f32(K, (n, n_views, 3, 3))
+        keep["keypoints"] = _f32(keypoints, (n, n_views, rows, 3))
+        keep["divisor"] = _i32(divisor).reshape(n)
+        if present is not None:
+            keep["present"] = np.ascontiguousarray(np.asarray(present).reshape(n, n_views) != 0, dtype=np.uint8)
+            q.present = keep["present"].ctypes.data_as(C.POINTER(C.c_uint8))
+        q.w2c, q.K, q.keypoints, q.divisor = (_lib.fptr(keep["w2c"]), _lib.fptr(keep["K"]), _lib.fptr(keep["keypoints"]),
+                                              _lib.iptr(keep["divisor"]))
+    q.n, q.n_views, q.n_rows, q.joints = n, n_views, rows, _lib.fptr(keep.get("joints"))
+    if poses is not None:
+        keep["poses"] = _f32(poses)
+        keep["poses"] = keep["poses"].reshape(n, keep["poses"].shape[-1])
+        q.pose_dim, q.poses = keep["poses"].shape[1], _lib.fptr(keep["poses"])
+    if betas is not None:
+        keep["betas"] = _f32(betas)
+        keep["betas"] = keep["betas"].reshape(n, keep["betas"].shape[-1])
+        q.n_betas, q.betas = keep["betas"].shape[1], _lib.fptr(keep["betas"])
+    if dterms is not None:
+        keep["dterms"] = _f32(dterms, (n, 4))
+    out = {}
+    if "terms" in want:
+        out["terms"] = np.empty((n, 4), np.float32)
+    if "djoints" in want:
+        out["djoints"] = np.zeros((n, rows, 3), np.float32)
+    if "dposes" in want:
+        out["dposes"] = np.empty((n, q.pose_dim), np.float32)
+    if "dbetas" in want:
+        out["dbetas"] = np.empty((n, q.n_betas), np.float32)
+    if gmm is not None:
+        device = gmm.device
+    _lib.check(_lib.load().bf_keypoint_loss(int(device), gmm._h if gmm is not None else None, C.byref(q),
+                                            C.byref(hyper) if hyper is not None else None, _lib.fptr(keep.get("dterms")),
+                                            _lib.fptr(out.get("terms")), _lib.fptr(out.get("djoints")), _lib.fptr(out.get("dposes")),
+                                            _lib.fptr(out.get("dbetas"))), "bf_keypoint_loss")
+    return out
+
+
 class FrameBatch:
     """F independent frames x V views resident on the model's GPU."""
 

@@ -187,6 +187,37 @@ int bf_smplx_forward(bf_model *m, int n, const bf_smplx_params *in, const bf_smp
  * the barycentric combination of the chosen faces' vertices. */
 int bf_smplx_vjp(bf_model *m, int n, const bf_smplx_params *in, const bf_smplx_cotangents *cot, const bf_smplx_grads *grads);
 
+/* MaxMixturePrior's buffers (smplify/prior.py:142-160) on one device, uploaded once: means[M,D], precisions[M,D,D],
+ * nll_weights[M] (positive).  At most 16 components of at most 128 dimensions (BF_ERR_UNSUPPORTED beyond). */
+typedef struct bf_gmm bf_gmm;
+int bf_gmm_create(int device, int n_components, int dim, const float *means, const float *precisions,
+                  const float *nll_weights, bf_gmm **out);
+void bf_gmm_destroy(bf_gmm *g);
+
+/* multiview_keypoint_loss (smplify/loss.py:139-230) for `n` independent problems - each one set of world-space joints, V views,
+ * one body pose and one betas vector - and its vector-Jacobian product with respect to joints, poses and betas. */
+typedef struct bf_keypoint_loss_in {
+    int32_t n, n_views, n_rows;     /* problems, views per problem, joint rows (25 for SMPL, 135 for SMPL-X with hands + face; <= 256) */
+    const float *joints;            /* [n,n_rows,3] world space, as smplify.py:189 scales them */
+    const float *w2c;               /* [n,V,4,4]; rows 0..2 are read */
+    const float *K;                 /* [n,V,3,3] */
+    const float *keypoints;         /* [n,V,n_rows,3] x, y, confidence; a group absent from a present view = zero confidences */
+    const uint8_t *present;         /* [n,V], NULL = all present; an absent view is skipped, not projected */
+    const int32_t *divisor;         /* [n] = len(use_frames), positive */
+    int32_t pose_dim;  const float *poses;    /* [n,pose_dim], NULL = no pose / angle prior; pose_dim > 55 and <= the GMM's dim
+                                                 (the pose is zero-padded to it, loss.py:206-207) */
+    int32_t n_betas;   const float *betas;    /* [n,n_betas], NULL = no shape prior; n_betas <= 16 */
+} bf_keypoint_loss_in;
+/* terms[n,4] = reprojection, pose prior, angle prior, shape prior (loss.py:219-224), weighted as the reference weights them
+ * with sigma, the three prior weights and imsize of `hyper` (NULL: bf_hyper_default; its other fields are not read).
+ * djoints[n,n_rows,3], dposes[n,pose_dim], dbetas[n,n_betas] = the gradient of sum(dterms * terms), dterms[n,4] (NULL = ones).
+ * `terms` and every gradient may be NULL = not wanted.  gmm NULL: the pose prior term is 0.  The GMM term is the minimum over
+ * the components (ties: the lowest), its gradient that of the arg-min component alone.  V = 0 or every view absent: the
+ * reprojection term is 0 and djoints exactly 0.  Host pointers; stateless apart from `gmm`; every sum has a fixed order (no
+ * float atomics), so equal inputs give equal bits and a problem's result does not depend on its neighbours in the call. */
+int bf_keypoint_loss(int device, const bf_gmm *gmm, const bf_keypoint_loss_in *in, const bf_hyper *hyper,
+                     const float *dterms, float *terms, float *djoints, float *dposes, float *dbetas);
+
 /* The model's forward for `n` packed parameter vectors params[n,n_params] (any model kind): vertices[n,NV,3] in
  * model space and joints[n,n_joint_map,3], both before the similarity (either may be NULL). */
 int bf_model_forward(bf_model *m, int n, const float *params, float *vertices, float *joints);
