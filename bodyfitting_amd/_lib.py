@@ -96,6 +96,13 @@ SIGNATURES = {
     "bf_gmm_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.POINTER(_VP)]),
     "bf_gmm_destroy": (None, [_VP]),
     "bf_keypoint_loss": (C.c_int, [C.c_int, _VP, C.POINTER(KeypointLossIn), C.POINTER(Hyper), _FP, _FP, _FP, _FP, _FP]),
+    "bf_topo_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _IP, C.POINTER(_VP)]),
+    "bf_topo_destroy": (None, [_VP]),
+    "bf_vertex_normals": (C.c_int, [_VP, _FP, _FP]),
+    "bf_vertex_normals_vjp": (C.c_int, [_VP, _FP, _FP, _FP]),
+    "bf_normal_laplacian": (C.c_int, [_VP, _FP, _FP, _FP]),
+    "bf_scan_point_loss": (C.c_int, [_VP, C.c_int, _FP, _FP, _IP, _FP, _FP]),
+    "bf_normal_loss": (C.c_int, [C.c_int, C.c_int, _FP, _FP, _FP, _FP]),
     "bf_batch_create": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(_VP)]),
     "bf_batch_destroy": (None, [_VP]),
     "bf_batch_set_cameras": (C.c_int, [_VP, _FP, _FP]),

@@ -143,6 +143,20 @@ struct DevBuf {
     ~DevBuf() { drop(); }
 };
 
+// vertex -> (face, corner) lists in the order compute_normal_torch (io_utils.py:406-428) adds a vertex's face normals up: corner by
+// corner, faces ascending.  start[nv + 1] = CSR offsets, adj[3 nf] = face * 4 + corner.  `faces` holds 3 nf indices inside [0, nv).
+// Shared by the SMPL+D stage (bf_fit_displacement) and bf_topo_create.
+inline void bf_build_vertex_adjacency(const std::vector<int> &faces, int nv, std::vector<int> &start, std::vector<int> &adj) {
+    const int nf = (int)(faces.size() / 3);
+    start.assign((size_t)nv + 1, 0);
+    adj.assign(faces.size(), 0);
+    for (int v : faces) ++start[v + 1];
+    for (int v = 0; v < nv; ++v) start[v + 1] += start[v];
+    std::vector<int> fill(start.begin(), start.end() - 1);
+    for (int c = 0; c < 3; ++c)
+        for (int f = 0; f < nf; ++f) adj[fill[faces[f * 3 + c]]++] = f * 4 + c;
+}
+
 // Scratch of the MFMA batch path of the full-mesh forward (>= BF_MFMA_MIN_FRAMES frames).  Owned by whoever owns the stream
 // the forward runs on (a bf_batch, or a one-off forward call): two batches of one model never share it.
 struct MeshScratch {

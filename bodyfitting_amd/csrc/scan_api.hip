@@ -1175,12 +1175,8 @@ int bf_fit_displacement(bf_batch *b, int n_iters, const bf_hyper *hyper) {
     std::unique_lock<std::mutex> lazy(m->lazy);
     if (!m->faces_d.p) {
         // vertex -> (face, corner) lists in the order compute_normal_torch adds them: corner by corner, faces ascending
-        std::vector<int> start(nv + 1, 0), adj(m->faces_host.size());
-        for (int v : m->faces_host) ++start[v + 1];
-        for (int v = 0; v < nv; ++v) start[v + 1] += start[v];
-        std::vector<int> fill(start.begin(), start.end() - 1);
-        for (int c = 0; c < 3; ++c)
-            for (int f = 0; f < nf; ++f) adj[fill[m->faces_host[f * 3 + c]]++] = f * 4 + c;
+        std::vector<int> start, adj;
+        bf_build_vertex_adjacency(m->faces_host, nv, start, adj);
         HIP_TRY(m->adj_start.upload(start));
         HIP_TRY(m->adj.upload(adj));
         HIP_TRY(m->faces_d.upload(m->faces_host));        // (blocking uploads; faces_d last: it is the "built" flag)

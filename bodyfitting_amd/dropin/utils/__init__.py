@@ -1,5 +1,6 @@
-"""`utils.mesh_grid_searcher` of the reference resolves here (smplify/smplify.py:15); every other `utils.*` module
-(`utils.io_utils`, apps/genebody_fitting.py:14) still resolves to a `utils` package further down sys.path - the reference's own."""
+"""`utils.mesh_grid_searcher` and `utils.io_utils` of the reference resolve here (smplify/smplify.py:14-15); every other `utils.*`
+module still resolves to a `utils` package further down sys.path - the reference's own - and so does every name of `utils.io_utils`
+but `compute_normal_torch` and `load_obj_mesh` (apps/genebody_fitting.py:14; io_utils.py here hands them on)."""
 import os
 import sys
 

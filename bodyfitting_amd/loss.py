@@ -7,14 +7,25 @@ torch tensors in -> (total, losses) with `total` a float32 scalar tensor on mode
 to model_joints, poses and betas; numpy in -> floats out.  torch is imported only when tensors arrive.
 
 `perspective_projection`, `gmof`, `angle_prior` and `reprojection_loss` are the reference's small functions, in torch or numpy as
-their arguments are.  The silhouette, scan and SMPL+D losses run fused inside `SMPLify`; their stand-alone versions are not here yet
-and raise NotImplementedError.
+their arguments are.
+
+The scan term and the SMPL+D stage's losses of that loop (smplify.py:205-206,236-245) are here too, each one HIP call that returns
+the gradient for cotangent 1 with the value: `point_cloud_loss_mesh_grid` (bf_scan_point_loss: the search, then one Frobenius norm;
+the gradient goes to `points`), `normal_loss_mesh_grid` (bf_normal_loss, to `point_norm`) and `normal_laplacian_smoothness`
+(bf_normal_laplacian, to `norms`); `compute_normal_torch` is in normals.py.  torch tensors in -> a 0-dim float32 tensor on the
+inputs' device, differentiable once; numpy in -> a float.  The two scan losses of one iteration query the same points: the searcher
+keeps its last query's answer, so the second one does not search again.  They take this project's MeshGridSearcher, arrays and
+tensors; anything else raises NotImplementedError (SMPLify's fused stage is the other path), every other refusal is a ValueError.
+
+The silhouette loss, the contours and the chamfer loss run fused inside `SMPLify` only; their stand-alone versions raise
+NotImplementedError.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _autograd
+from . import normals as _normals
 from .keypoints import FACE_MAPPING, pack_keypoints_smplx          # noqa: F401  (FACE_MAPPING: a name of loss.py, re-exported)
 from . import prior as _prior
 
@@ -82,10 +93,112 @@ def _fused_only(name):
 
 multview_mask_loss = _fused_only("multview_mask_loss")
 extract_countours = _fused_only("extract_countours")
-point_cloud_loss_mesh_grid = _fused_only("point_cloud_loss_mesh_grid")
-normal_loss_mesh_grid = _fused_only("normal_loss_mesh_grid")
-normal_laplacian_smoothness = _fused_only("normal_laplacian_smoothness")
 point_cloud_loss_chamfer_naive = _fused_only("point_cloud_loss_chamfer_naive")
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the scan term and the SMPL+D stage's losses (loss.py:233-242,260-288)
+# ----------------------------------------------------------------------------------------------------------------------------
+
+def _scalar_loss(who, x, call):
+    """`call(array, want_grad)` -> (value, gradient for cotangent 1 or None): ONE native call per evaluation - the gradient comes
+    back with the value when `x` asks for one, and the backward only scales it.  -> a 0-dim tensor on x's device, or a float."""
+    if not _is_tensor(x):
+        return float(call(x, False)[0])
+    import torch
+    kept = []
+    want_grad = bool(x.requires_grad and torch.is_grad_enabled())          # (read here: grad mode is off inside a Function's forward)
+
+    def forward(a):
+        value, grad = call(a, want_grad)
+        kept.append(grad)
+        return (np.asarray(value).reshape(1),)
+
+    def vjp(arrays, cotangents):
+        if kept[0] is None:
+            raise RuntimeError(f"{who}: no gradient was computed with the forward")
+        return (kept[0] * np.asarray(cotangents[0]).reshape(-1)[0],)
+
+    return _autograd.apply(forward, vjp, (x,))[0].reshape(())
+
+
+def _scan_of(who, mesh_grid_searcher):
+    from .mesh_grid_searcher import MeshGridSearcher
+    if not isinstance(mesh_grid_searcher, MeshGridSearcher):
+        raise NotImplementedError(f"smplify.loss.{who}: mesh_grid_searcher is a {type(mesh_grid_searcher).__name__}; {_normals.FUSED_PATH}")
+    if mesh_grid_searcher._scan is None:
+        raise ValueError(f"{who}: the searcher has no mesh (set_mesh was not called)")
+    if getattr(mesh_grid_searcher, "_mesh_wants_grad", False):
+        raise ValueError(f"{who}: the scan requires grad; no gradient flows to it (the reference detaches the closest points)")
+    return mesh_grid_searcher._scan
+
+
+def point_cloud_loss_mesh_grid(mesh_grid_searcher, points):
+    """loss.py:233-242: sqrt(sum |P - C|^2) over all of points[..., 3] with C their closest points on the searcher's mesh,
+    detached.  The gradient (P - C) / loss goes to `points`, exactly zero where the loss is zero."""
+    who = "point_cloud_loss_mesh_grid"
+    scan = _scan_of(who, mesh_grid_searcher)
+    _normals.require_array("smplify.loss." + who, "points", points)
+    _prior._require_float32(who, "points", points)
+    if _normals.require_rows3(who, "points", points) == 0:
+        raise ValueError(f"{who}: no points")
+
+    def call(p, want_grad):
+        p = p.reshape(-1, 3)
+        value, ids, nearest, grad = scan.point_loss(p, want_grad=want_grad)
+        mesh_grid_searcher._remember_query(p, ids, nearest)
+        return value, grad
+
+    return _scalar_loss(who, points, call)
+
+
+def normal_loss_mesh_grid(mesh_grid_searcher, points, face_norm_mesh=None, point_norm=None):
+    """loss.py:260-271: mean(1 - sum(face_norm_mesh[closest face of points] * point_norm, -1)); face_norm_mesh[NF,3] the scan's face
+    normals as the caller built them (smplify.py:149: un-normalised).  The gradient goes to `point_norm` only.  (The reference's
+    parameter list; the last two have no default there.)"""
+    who = "normal_loss_mesh_grid"
+    scan = _scan_of(who, mesh_grid_searcher)
+    named = (("points", points), ("face_norm_mesh", face_norm_mesh), ("point_norm", point_norm))
+    for name, x in named:
+        _normals.require_array("smplify.loss." + who, name, x)
+    _normals.require_same_kind(who, named)
+    for name, x in named:
+        _prior._require_float32(who, name, x)
+    _normals.require_no_grad(who, "face_norm_mesh", face_norm_mesh)
+    rows = [_normals.require_rows3(who, name, x) for name, x in named]
+    if rows[0] == 0:
+        raise ValueError(f"{who}: no points")
+    if rows[0] != rows[2]:
+        raise ValueError(f"{who}: points has {rows[0]} rows, point_norm {rows[2]}")
+    if face_norm_mesh.ndim != 2 or rows[1] != scan.n_faces:
+        raise ValueError(f"{who}: face_norm_mesh must be [{scan.n_faces}, 3] (one row per face of the searcher's mesh), not {tuple(face_norm_mesh.shape)}")
+    from . import native
+    ids, _ = mesh_grid_searcher._query(_host(points, None).reshape(-1, 3))
+    closest = _host(face_norm_mesh, None)[ids]                 # (gathered here: N rows go up, not the scan's table)
+
+    def call(pn, want_grad):
+        return native.normal_loss(closest, pn.reshape(-1, 3), want_grad=want_grad, device=scan.device)
+
+    return _scalar_loss(who, point_norm, call)
+
+
+def normal_laplacian_smoothness(norms, faces):
+    """loss.py:273-288: the mean over faces of |na-nb|^2 + |nc-na|^2 + |nb-nc|^2 of norms[..., 3].  The gradient goes to `norms`."""
+    from . import native
+    who = "normal_laplacian_smoothness"
+    _normals.require_array("smplify.loss." + who, "norms", norms)
+    _normals.require_array("smplify.loss." + who, "faces", faces)
+    _normals.require_same_kind(who, (("norms", norms), ("faces", faces)))
+    _prior._require_float32(who, "norms", norms)
+    n = _normals.require_rows3(who, "norms", norms)
+    if n == 0:
+        raise ValueError(f"{who}: no normals")
+    topo = _normals.topology_for(who, faces, n, _normals.device_index(norms))
+
+    def call(a, want_grad):
+        return native.normal_laplacian(topo, a.reshape(-1, 3), want_grad=want_grad)
+
+    return _scalar_loss(who, norms, call)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

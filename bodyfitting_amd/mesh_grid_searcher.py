@@ -48,6 +48,8 @@ class MeshGridSearcher:
         self.verts = _to_np(verts, np.float32).reshape(-1, 3)
         self.faces = _to_np(faces, np.int32).reshape(-1, 3)
         self._scan = Scan(self.verts, self.faces, device=self._device_index(device))
+        self._mesh_wants_grad = any(getattr(a, "requires_grad", False) for a in (verts, faces))
+        self._last_query = None
         dims, origin, step = self._scan.grid_info()
         self.step = np.float32(step)
         self.num = np.concatenate([dims, [int(np.prod(dims))]]).astype(np.int32)          # [nx, ny, nz, nx ny nz]
@@ -71,12 +73,27 @@ class MeshGridSearcher:
         if getattr(self, "_scan", None) is not None:
             self._scan.close()
             self._scan = None
+        self._last_query = None
 
     def __del__(self):  # pragma: no cover
         try:
             self.close()
         except Exception:
             pass
+
+    def _remember_query(self, points, ids, nearest):
+        """the scan losses of one iteration query the same points (smplify.py:239-240): the last query's answer is kept beside a
+        copy of its points"""
+        self._last_query = (np.array(points, copy=True), ids, nearest)
+
+    def _query(self, points):
+        """-> (face ids, nearest points) of points[n,3]: the last query's when these are its points, else a search"""
+        last = getattr(self, "_last_query", None)
+        if last is not None and np.array_equal(last[0], points):
+            return last[1], last[2]
+        pts, ids, _ = self._scan.nearest_points(points)
+        self._remember_query(points, ids, pts)
+        return ids, pts
 
     def _need_mesh(self):
         if self._scan is None:

@@ -195,7 +195,7 @@ class Scan:
         self._lib = _lib.load()
         v = _f32(verts, (-1, 3))
         f = _i32(np.asarray(faces).reshape(-1, 3))
-        self.n_verts, self.n_faces = len(v), len(f)
+        self.n_verts, self.n_faces, self.device = len(v), len(f), int(device)
         self._h = C.c_void_p()
         _lib.check(self._lib.bf_scan_create(int(device), len(v), _lib.fptr(v), len(f), _lib.iptr(f), C.byref(self._h)),
                    "bf_scan_create")
@@ -268,6 +268,19 @@ class Scan:
         return (pts, ids, bary, us.value) if reps > 0 else (pts, ids, bary)
 
 
+    def point_loss(self, points, want_grad=True):
+        """bf_scan_point_loss: point_cloud_loss_mesh_grid (loss.py:233-242) of points[n,3] in one call - the search, then the
+        reduction on the points already uploaded.  -> (loss float32 scalar, face ids [n], nearest points [n,3], dpoints [n,3] =
+        the gradient for cotangent 1, exactly zero where the loss is zero; None unless want_grad)"""
+        p = _f32(points, (-1, 3))
+        loss = np.empty(1, np.float32)
+        ids = np.empty(len(p), np.int32)
+        pts = np.empty((len(p), 3), np.float32)
+        dp = np.empty((len(p), 3), np.float32) if want_grad else None
+        _lib.check(self._lib.bf_scan_point_loss(self._h, len(p), _lib.fptr(p), _lib.fptr(loss), _lib.iptr(ids), _lib.fptr(pts), _lib.fptr(dp)),
+                   "bf_scan_point_loss")
+        return loss[0], ids, pts, dp
+
     def nearest_points_backward(self, face_ids, bary, dnearest):
         """dL/d(query points) from dL/d(nearest points): SurfaceNearest.backward w.r.t. its first argument (point-to-plane
         where the closest point lies on a face, along the edge on an edge, zero at a corner)"""
@@ -278,6 +291,68 @@ class Scan:
         _lib.check(self._lib.bf_scan_nearest_backward(self._h, len(ids), _lib.iptr(ids), _lib.fptr(b), _lib.fptr(g), _lib.fptr(out)),
                    "bf_scan_nearest_backward")
         return out
+
+
+class Topology:
+    """A mesh's faces[NF,3] and its vertex -> (face, corner) lists uploaded once to one GPU (bf_topo): what compute_normal_torch
+    and normal_laplacian_smoothness walk."""
+
+    def __init__(self, n_verts, faces, device=0):
+        lib = _lib.load()
+        self._lib = lib
+        f = _i32(np.asarray(faces).reshape(-1, 3))
+        self.n_verts, self.n_faces, self.device = int(n_verts), len(f), int(device)
+        self._h = C.c_void_p()
+        _lib.check(lib.bf_topo_create(self.device, self.n_verts, self.n_faces, _lib.iptr(f), C.byref(self._h)), "bf_topo_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bf_topo_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def vertex_normals(topo, verts):
+    """bf_vertex_normals: compute_normal_torch (io_utils.py:406-428), verts[NV,3] -> normals[NV,3]"""
+    v = _f32(verts, (topo.n_verts, 3))
+    out = np.empty((topo.n_verts, 3), np.float32)
+    _lib.check(topo._lib.bf_vertex_normals(topo._h, _lib.fptr(v), _lib.fptr(out)), "bf_vertex_normals")
+    return out
+
+
+def vertex_normals_vjp(topo, verts, dnormals):
+    """bf_vertex_normals_vjp: dnormals[NV,3] (any cotangent of the normals) -> dverts[NV,3]"""
+    v = _f32(verts, (topo.n_verts, 3))
+    dn = _f32(dnormals, (topo.n_verts, 3))
+    out = np.empty((topo.n_verts, 3), np.float32)
+    _lib.check(topo._lib.bf_vertex_normals_vjp(topo._h, _lib.fptr(v), _lib.fptr(dn), _lib.fptr(out)), "bf_vertex_normals_vjp")
+    return out
+
+
+def normal_laplacian(topo, norms, want_grad=True):
+    """bf_normal_laplacian: normal_laplacian_smoothness (loss.py:273-288) of norms[NV,3] -> (loss float32 scalar, dnorms[NV,3] =
+    the gradient for cotangent 1; None unless want_grad)"""
+    n = _f32(norms, (topo.n_verts, 3))
+    loss = np.empty(1, np.float32)
+    dn = np.empty((topo.n_verts, 3), np.float32) if want_grad else None
+    _lib.check(topo._lib.bf_normal_laplacian(topo._h, _lib.fptr(n), _lib.fptr(loss), _lib.fptr(dn)), "bf_normal_laplacian")
+    return loss[0], dn
+
+
+def normal_loss(closest_face_norms, point_norms, want_grad=True, device=0):
+    """bf_normal_loss: normal_loss_mesh_grid (loss.py:260-271) behind the search, closest_face_norms[n,3] = face_norm_mesh[closest
+    face] -> (loss float32 scalar, dpoint_norms[n,3] = the gradient for cotangent 1; None unless want_grad)"""
+    fn = _f32(closest_face_norms, (-1, 3))
+    pn = _f32(point_norms, (len(fn), 3))
+    loss = np.empty(1, np.float32)
+    dpn = np.empty((len(fn), 3), np.float32) if want_grad else None
+    _lib.check(_lib.load().bf_normal_loss(int(device), len(fn), _lib.fptr(fn), _lib.fptr(pn), _lib.fptr(loss), _lib.fptr(dpn)), "bf_normal_loss")
+    return loss[0], dpn
 
 
 def set_nearest_rule(rule):

@@ -218,6 +218,35 @@ typedef struct bf_keypoint_loss_in {
 int bf_keypoint_loss(int device, const bf_gmm *gmm, const bf_keypoint_loss_in *in, const bf_hyper *hyper,
                      const float *dterms, float *terms, float *djoints, float *dposes, float *dbetas);
 
+/* The SMPL+D stage's losses (smplify.py:236-245) as stand-alone calls with their gradients, for a user's own torch loop: what
+ * bf_fit_displacement evaluates fused, one mesh per call.  Host pointers; the calls' buffers come from the device's block cache;
+ * no float atomics, every scalar is reduced in one order that depends on the sizes alone, so equal inputs give equal bits.
+ * At most 2^28 vertices, faces or points (BF_ERR_UNSUPPORTED beyond).
+ *
+ * A mesh topology on one device, uploaded once: faces[n_faces,3] and the vertex -> (face, corner) lists in the order
+ * compute_normal_torch (utils/io_utils.py:406-428) adds a vertex's face normals up - corner by corner, faces ascending.  A face
+ * index outside [0, n_verts) is BF_ERR_INVALID. */
+typedef struct bf_topo bf_topo;
+int bf_topo_create(int device, int n_verts, int n_faces, const int32_t *faces, bf_topo **out);
+void bf_topo_destroy(bf_topo *t);
+/* compute_normal_torch: verts[n_verts,3] -> normals[n_verts,3]; face normals n / (|n| + 1e-8), summed per vertex, divided by
+ * (|sum| + 1e-8) again.  A vertex in no face gets exactly zero. */
+int bf_vertex_normals(const bf_topo *t, const float *verts, float *normals);
+/* ... and its vector-Jacobian product: dverts[n_verts,3] = the gradient of sum(dnormals * normals), dnormals[n_verts,3] any
+ * cotangent.  Where a length is zero torch's rule holds (d = dn / 1e-8, no projection term). */
+int bf_vertex_normals_vjp(const bf_topo *t, const float *verts, const float *dnormals, float *dverts);
+/* normal_laplacian_smoothness (smplify/loss.py:273-288): loss[1] = mean over faces of |na-nb|^2 + |nc-na|^2 + |nb-nc|^2 of
+ * norms[n_verts,3]; dnorms[n_verts,3] = its gradient for cotangent 1.  Either output may be NULL = not wanted. */
+int bf_normal_laplacian(const bf_topo *t, const float *norms, float *loss, float *dnorms);
+/* point_cloud_loss_mesh_grid (smplify/loss.py:233-242): bf_scan_nearest's launch for points[n,3], then loss[1] = sqrt(sum
+ * |P - C|^2) over all points with the closest points C detached, and dpoints[n,3] = (P - C) / loss for cotangent 1 - exactly zero
+ * where the loss is zero.  face_ids[n] and nearest[n,3] are bf_scan_nearest's.  Every output may be NULL = not wanted. */
+int bf_scan_point_loss(bf_scan *s, int n, const float *points, float *loss, int32_t *face_ids, float *nearest, float *dpoints);
+/* normal_loss_mesh_grid (smplify/loss.py:260-271) behind the search: closest_face_norms[n,3] = face_norm_mesh[closest face]
+ * (gathered by the caller, un-normalised as smplify.py:149 builds them), point_norms[n,3] -> loss[1] = mean(1 - sum(fn * pn)),
+ * dpoint_norms[n,3] = -fn / n for cotangent 1.  Either output may be NULL = not wanted. */
+int bf_normal_loss(int device, int n, const float *closest_face_norms, const float *point_norms, float *loss, float *dpoint_norms);
+
 /* The model's forward for `n` packed parameter vectors params[n,n_params] (any model kind): vertices[n,NV,3] in
  * model space and joints[n,n_joint_map,3], both before the similarity (either may be NULL). */
 int bf_model_forward(bf_model *m, int n, const float *params, float *vertices, float *joints);
