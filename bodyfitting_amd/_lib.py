@@ -69,6 +69,7 @@ class Hyper(C.Structure):
 
 CONTOUR_OPENCV_FIRST, CONTOUR_RASTER_FIRST, CONTOUR_LONGEST = 0, 1, 2
 NEAREST_REFERENCE, NEAREST_FAST = 0, 1
+DENSE_GRAD_LATE, DENSE_GRAD_SUBMODEL = 1, 2
 FIT_DEFAULT, FIT_DENSE, FIT_NO_VERTICES, FIT_FETCH, FIT_RESET, FIT_GRAPH, FIT_NOTIME = 0, 1, 2, 4, 8, 16, 32
 
 # every entry point include/bodyfit.h declares: name -> (restype, argtypes)
@@ -85,6 +86,7 @@ SIGNATURES = {
     "bf_model_destroy": (None, [_VP]),
     "bf_model_n_params": (C.c_int, [_VP]),
     "bf_model_fit_instance": (C.c_int, [_VP]),
+    "bf_model_sub_vertices": (C.c_int, [_VP, C.c_int, _IP]),
     "bf_device_cache_trim": (C.c_int64, [C.c_int]),
     "bf_batch_dense_timing": (C.c_int, [_VP, C.c_int, _FP]),
     "bf_batch_dense_resident": (C.c_int, [_VP]),
@@ -115,6 +117,7 @@ SIGNATURES = {
     "bf_batch_get_params": (C.c_int, [_VP, _FP]),
     "bf_fit": (C.c_int, [_VP, C.c_int, C.POINTER(Hyper), C.c_uint32]),
     "bf_loss_grad": (C.c_int, [_VP, C.POINTER(Hyper), _FP, _FP]),
+    "bf_dense_iter_grad": (C.c_int, [_VP, C.POINTER(Hyper), C.c_uint32, _FP, _FP, _FP]),
     "bf_batch_sync": (C.c_int, [_VP]),
     "bf_batch_get_result": (C.c_int, [_VP, _FP, _FP, _FP, _FP]),
     "bf_batch_export_params_dev": (C.c_int, [_VP, _VP]),
@@ -229,6 +232,7 @@ SIGNATURES = {
     "bf_overlay_stamp": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _FP, _DP, C.POINTER(C.c_uint8)]),
     "bf_batch_debug_dump": (C.c_int, [_VP, _FP, C.c_int]),
     "bf_batch_debug_disp_moment": (C.c_int, [_VP, _FP]),
+    "bf_batch_debug_vertices": (C.c_int, [_VP, _FP]),
 }
 
 _lib = None

@@ -984,6 +984,43 @@ int bf_loss_grad(bf_batch *b, const bf_hyper *hyper, float *terms, float *grads)
     return BF_OK;
 }
 
+int bf_dense_iter_grad(bf_batch *b, const bf_hyper *hyper, uint32_t flags, const float *dverts_extra, float *terms, float *grads) {
+    if (!b) return fail(BF_ERR_INVALID, "bf_dense_iter_grad: null batch");
+    if (flags & ~(uint32_t)(BF_DENSE_GRAD_LATE | BF_DENSE_GRAD_SUBMODEL)) return fail(BF_ERR_INVALID, "bf_dense_iter_grad: unknown flag");
+    const bool late = flags & BF_DENSE_GRAD_LATE;
+    if (b->scans_lost)
+        return fail(BF_ERR_INVALID, "bf_dense_iter_grad: a scan this batch held was destroyed (bf_scan_destroy) - call bf_batch_set_scans again (NULL: go on without scans)");
+    if (b->staged) return fail(BF_ERR_INVALID, "bf_dense_iter_grad: inputs were staged with bf_batch_stage_inputs - there are no current parameters before the next bf_fit");
+    if (late && b->scans.empty() && !b->has_masks)
+        return fail(BF_ERR_INVALID, "bf_dense_iter_grad: BF_DENSE_GRAD_LATE with neither scans nor silhouettes attached");
+    bf_model *m = b->m;
+    HIP_TRY(hipSetDevice(m->device));
+    BF_TRY(bf_flush_tail(b));
+    BF_TRY(bf_lanes_drain(b));
+    bf_hyper h;
+    if (hyper) h = *hyper; else bf_hyper_default(&h);
+    BF_TRY(ensure_adam_tab(b, h, 1));
+    HyperDev hd = bf_to_dev(h);
+    BF_TRY(bf_guard_arena(b));
+    FrameIO io = bf_frame_io(b, true);
+    std::vector<float> t6(terms ? (size_t)b->F * 6 : 0);
+    if (!m->kp_dense && !late && !dverts_extra) {
+        // a model whose keypoint loss the fit kernel computes itself: bf_fit runs the iterations before the switch-on as plain fit
+        // launches (bf_fit_with_scans' n_plain), with no mesh pass and no outside gradient blocks - and so does this call
+        HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, 1, 1, b->adam_tab.p, 0, b->fit_smem, b->stream, nullptr));
+        BF_TRY(bf_sync_all(b));
+        if (terms) {
+            std::vector<float> t4((size_t)b->F * 4);
+            HIP_TRY(hipMemcpy(t4.data(), b->terms.p, t4.size() * sizeof(float), hipMemcpyDeviceToHost));
+            for (int f = 0; f < b->F; ++f) std::copy(t4.begin() + (size_t)f * 4, t4.begin() + (size_t)f * 4 + 4, t6.begin() + (size_t)f * 6);
+        }
+    } else
+        BF_TRY(bf_dense_iter_eval(b, h, hd, io, late, flags & BF_DENSE_GRAD_SUBMODEL, dverts_extra, terms ? t6.data() : nullptr));
+    if (terms) std::copy(t6.begin(), t6.end(), terms);
+    if (grads) HIP_TRY(hipMemcpy(grads, b->grads.p, b->grads.n * sizeof(float), hipMemcpyDeviceToHost));
+    return BF_OK;
+}
+
 int bf_batch_sync(bf_batch *b) {
     if (!b) return fail(BF_ERR_INVALID, "bf_batch_sync: null batch");
     HIP_TRY(hipSetDevice(b->m->device));
@@ -1128,6 +1165,15 @@ int bf_batch_mesh_span(bf_batch *b, int reps, float us[3]) {
         sum += t; lo = std::min(lo, t); hi = std::max(hi, t);
     }
     us[0] = (float)(sum / reps); us[1] = (float)lo; us[2] = (float)hi;
+    return BF_OK;
+}
+
+/* test hook: the body vertices the last mesh pass left on the device */
+int bf_batch_debug_vertices(bf_batch *b, float *vertices) {
+    if (!b || !vertices) return fail(BF_ERR_INVALID, "bf_batch_debug_vertices: null argument");
+    HIP_TRY(hipSetDevice(b->m->device));
+    BF_TRY(bf_sync_all(b));
+    HIP_TRY(hipMemcpy(vertices, b->vout.p, b->vout.n * sizeof(float), hipMemcpyDeviceToHost));
     return BF_OK;
 }
 

@@ -265,6 +265,8 @@ struct bf_model {
         KpIO kp{};
         DevBuf<float> v_template, shapedirs, posedirs, lbs_weights, j_extra, v_nzw, posedirsT;
         DevBuf<int> v_nzj, selector_ids, faces, lmk_fv, dyn_fv;
+        DevBuf<int> verts;            // [mesh.nv] the full model's vertex of every sub-model vertex
+        std::vector<int> verts_host;
     } sub, sub_kp;                // (sub_kp: the keypoint-only sub-model of the iterations before the dense losses switch on - no sampled vertices)
     DevBuf<float> posedirsT;      // [3NV][npf], built on first use of the dense reverse pass (under `lazy`, device-synchronised)
     DevBuf<float> fit_image;      // FitTab::lds_image of the dense-schedule fit instance, built on first use (under `lazy`)
@@ -443,6 +445,8 @@ int bf_launch_mesh(bf_model *m, MeshScratch *scr, int n, const float *state_dev,
 //  mproj: project the sampled vertices into the mask views as well - only the 1..15-frame kernel does, *projected says so)
 int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDev &hd, FrameIO io);
 int bf_dense_loss_grad(bf_batch *b, const bf_hyper &h, const HyperDev &hd, FrameIO io);
+int bf_dense_iter_eval(bf_batch *b, const bf_hyper &h, const HyperDev &hd, FrameIO io, bool late, bool use_sub, const float *dverts_extra,
+                       float *terms6);
 int bf_ensure_dense_buffers(bf_batch *b);
 int bf_ensure_posedirsT_locked(bf_model *m, hipStream_t stream);   // (caller holds m->lazy) posedirsT built on first use
 int bf_masks_finalize(bf_batch *b);      // no-op unless a deferred bf_batch_set_masks is pending

@@ -22,8 +22,8 @@
 //              then skinning of the selector vertices, the 48-view projection, the reverse skinning + subtree sums, and on wave 0
 //              the reverse Rodrigues + Adam for the pose;
 //   wave 3     skinning / projection like the others; the priors' share of dL/dtheta (arg-min component, angle prior) for the Adam
-//              phase; the betas' gradient, step and everything the next forward pass derives from them - in the SMPL instance
-//              outside the dense schedule those are dealt over waves 1-3 (16 lanes per beta, then a third of the tables each;
+//              phase; the betas' gradient, step and everything the next forward pass derives from them - in the SMPL instances
+//              (with and without outside blocks) those are dealt over waves 1-3 (16 lanes per beta, then a third of the tables each;
 //              transl / scale on wave 3), elsewhere wave 3's alone;
 //   waves 4-7  GMM specialists: the symmetrised precision rows of components 2g, 2g+1 live in VGPRs for the whole launch; they
 //              also carry what needs few registers and only LDS inputs: the pose blend of the selector vertices (phase A) and
@@ -386,10 +386,11 @@ fit_kernel(FitTab T, FrameIO io, HyperDev hp, int n_iters, int mode, const float
     const int cp = ci > 0 ? T.parents[ci] : 0;
     const unsigned long long cmask = c_on ? T.desc[ci] : 0ull;       // strict descendants of ci
     (void)cr; (void)cp; (void)cmask; (void)w_feat;                    // (only the two-phase variants read them)
-    // The sized SMPL instance outside the dense schedule deals the Adam phase's betas over waves 1-3, 16 lanes (one DPP row) per beta:
+    // The sized SMPL instances (with and without outside gradient blocks: one order of sums, so a dense iteration whose blocks are zero
+    // gives the plain iteration's bits) deal the Adam phase's betas over waves 1-3, 16 lanes (one DPP row) per beta:
     // wave w, lane (l = 4 (w - 1) + lane / 16, s = lane % 16) sums joints s, s + 16 and selector outputs s, s + 16, s + 32 of dL/dbeta_l.
     // The parents of the lane's two joints live in one register (packed), so its reads of S.G do not wait for reads of S.par.
-    constexpr bool BETA_DEAL = NJ == 24 && NB > 0 && NB <= 10 && NS > 0 && NS * 3 <= 36 && !EXT;
+    constexpr bool BETA_DEAL = NJ == 24 && NB > 0 && NB <= 10 && NS > 0 && NS * 3 <= 36;
     const int bt_s = lane & 15;
     const int bt_par = (BETA_DEAL && wave >= 1 && wave <= 3) ? (bt_s > 0 ? T.parents[bt_s] : 0) | ((bt_s + 16 < nj ? T.parents[bt_s + 16] : 0) << 8) : 0;
     // waves 1-3 add 1 each once their betas are stepped (3 (it + 1) after iteration it): each then forms a part of what the next
@@ -1732,8 +1733,8 @@ fit_kernel(FitTab T, FrameIO io, HyperDev hp, int n_iters, int mode, const float
             BF_MARK(52, 192, it, t_iter);
             if (bstep || tstep) {
                 float grad;
-                if (tstep) grad = psum * (pidx < 3 ? sc3 * cscale : cscale);
-                else grad = g;
+                if (tstep) { grad = psum * (pidx < 3 ? sc3 * cscale : cscale); if (ext) grad += ext[EXT_T + pidx] + ext[EXT_K + pidx]; }
+                else { grad = g; if (ext) grad += ext[EXT_B + lc]; }
                 S.g[pidx] = grad;                                    // (kept for the debug dump)
                 adam(pidx, pval, am, av, tstep ? grad : grad + 2.f * hp.w_shape * pval);
             }

@@ -274,7 +274,7 @@ void deal_pairs(FitTab &T, const LossJoints &lj) {
 //   sub_kp  (round 5) only what the dense keypoint loss reads - selector vertices, the landmark faces' corners, the support of
 //           the extra regressor: the iterations BEFORE the silhouette / scan losses switch on (i <= num_iters // 3,
 //           smplify.py:197,205) touch nothing else, with or without a scan attached.
-struct SubTables { bool on = false; int n_samp = 0, nv = 0; std::vector<int> selector_ids, faces; Gather g; Corners lmk; };
+struct SubTables { bool on = false; int n_samp = 0, nv = 0; std::vector<int> selector_ids, faces, verts; Gather g; Corners lmk; };
 // off (the full model serves) when it would hold more than max_tenths / 10 of the vertices; `kv` flags the vertices the dense
 // keypoint loss reads, `nnz` is the full model's sparse skinning width
 SubTables derive_sub(const bf_model_desc *d, const std::vector<char> &kv, bool sampled_first, int max_tenths, int nnz) {
@@ -287,6 +287,7 @@ SubTables derive_sub(const bf_model_desc *d, const std::vector<char> &kv, bool s
     s.nv = (int)verts.size();
     if (s.nv == 0 || s.nv * 10 > nv * max_tenths) return SubTables{};
     s.on = true;
+    s.verts = verts;
     s.g = gather_vertices(d, verts, pd_pitch_of(3 * s.nv), nnz);
     for (int i = 0; i < d->n_selector; ++i) s.selector_ids.push_back(pos[d->selector_ids[i]]);
     if (d->model_kind == 1) {            // faces re-indexed; a corner outside the sub-model belongs to a face no landmark uses
@@ -411,6 +412,7 @@ void fill_sub(Uploader &up, bf_model::Sub &U, const bf_model &m, const SubTables
     Q.v_nzj = up(U.v_nzj, s.g.zj); Q.v_nzw = up(U.v_nzw, s.g.zw); Q.selector_ids = up(U.selector_ids, s.selector_ids);
     if (!s.faces.empty()) { Q.faces = up(U.faces, s.faces); Q.lmk_fv = up(U.lmk_fv, s.lmk.sfv); Q.dyn_fv = up(U.dyn_fv, s.lmk.dfv); }
     U.kp = m.kp; U.kp.nv = s.nv; U.kp.selector_ids = Q.selector_ids; U.kp.j_extra = Q.j_extra;
+    up(U.verts, s.verts); U.verts_host = s.verts;
     U.ns = s.n_samp; U.on = true;
 }
 
@@ -449,6 +451,13 @@ int bf_model_create(const bf_model_desc *d, int device, bf_model **out) {
 
 void bf_model_destroy(bf_model *model_handle) { std::unique_ptr<bf_model> drop(model_handle); }
 int bf_model_n_params(const bf_model *m) { return m ? m->np : 0; }
+int bf_model_sub_vertices(const bf_model *m, int which, int32_t *ids) {
+    if (!m || which < 0 || which > 1) return fail(BF_ERR_INVALID, "bf_model_sub_vertices: bad argument");
+    const bf_model::Sub &U = which ? m->sub_kp : m->sub;
+    if (!U.on) return 0;
+    if (ids) std::copy(U.verts_host.begin(), U.verts_host.end(), ids);
+    return (int)U.verts_host.size();
+}
 int bf_model_fit_instance(const bf_model *m) { return (m && bf_fit_is_sized_smpl(&m->fit)) ? 1 : 0; }
 
 }  // extern "C"

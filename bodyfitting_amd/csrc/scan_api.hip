@@ -10,6 +10,7 @@ extern "C" void bf_nearest_launch(dim3 grid, hipStream_t stream, const ScanDev *
                                   float *bary, int warm);        // scan_kernels.hip: the rule selected by bf_nearest_rule_set / BF_NEAREST_RULE
 extern "C" __global__ void bf_pc_partial_kernel(const float *, const float *, int, float *);
 extern "C" __global__ void bf_pc_grad_kernel(const float *, const float *, int, const float *, const float *, float *, float *, int, int *, int);
+extern "C" __global__ void bf_dv_add_kernel(float *, const float *, const int *, int, int);
 extern "C" int bf_mesh_bwd_multi_launch(const MeshTab *, const float *, const float *, int, const float *, const float *, const float *, float *, hipStream_t,
                                         const float *, int, int, int, int, int *, const MaskFold *);
 extern "C" __global__ void bf_ext_reduce_kernel(const float *, int, int, float *, int, int *, int);
@@ -509,7 +510,10 @@ static bool fold_acc_on() { return bf_mask_fold_get() == BF_MASK_FOLD_SUMS; }
 static bool door_coherent() { const char *e = std::getenv("BF_DOOR_COHERENT"); return !(e && e[0] == '0'); }
 
 static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, bool late, float mask_weight, int *door = nullptr, int door_k = 0,
-                      const bf_model::Sub *sub = nullptr, bool timed = false) {
+                      const bf_model::Sub *sub = nullptr, bool timed = false, bool eval = false, const float *dv_extra = nullptr) {
+    // eval (bf_dense_iter_grad): dL/dvertices starts from zero whatever the model, the silhouette's loss value is summed, the
+    // projection runs as a launch of its own (it leaves the binary term's partial sums), and dv_extra[F][NV][3] (device, full-model
+    // vertex order) is added onto dL/dvertices just before the reverse mesh pass
     bf_model *m = b->m;
     // (timed: events between the kernel classes of this pass, for bf_batch_dense_timing)
     auto mark = [&](int k) -> hipError_t {
@@ -546,11 +550,11 @@ static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, bool l
         HIP_TRY(hipEventCreateWithFlags(&b->ev_aux[1], hipEventDisableTiming));
     }
     int rc = bf_launch_mesh(m, &b->scratch, F, b->state.p, b->vraw.p, b->vout.p, kp ? b->xpart.p : nullptr, nullptr, nullptr, b->stream, nullptr,
-                            b->vposed.p, nullptr, nullptr, nullptr, (kp || masks) ? b->dvout.p : nullptr, &zeroed, kp, masks ? &mp : nullptr,
+                            b->vposed.p, nullptr, nullptr, nullptr, (kp || masks || eval) ? b->dvout.p : nullptr, &zeroed, kp, (masks && !eval) ? &mp : nullptr,
                             &projected, door, (F * door_k) | (door_coherent() ? 0x40000000 : 0), sub ? &Q : nullptr,
                             kp_aside ? b->ev_aux[0] : nullptr, &forked);
     if (rc) return rc;
-    if ((kp || masks) && !zeroed) HIP_TRY(hipMemsetAsync(b->dvout.p, 0, b->dvout.n * sizeof(float), b->stream));
+    if ((kp || masks || eval) && !zeroed) HIP_TRY(hipMemsetAsync(b->dvout.p, 0, b->dvout.n * sizeof(float), b->stream));
     HIP_TRY(mark(1));                         // [0,1] pose state (when not resident) + forward mesh pass
     // The dense keypoint loss and the closest-point search both only read the mesh: with scans attached the keypoint workgroups (one
     // per frame, a ~25 us latency chain) run on the batch's second stream UNDER the search - that stream is idle during a dense loop
@@ -576,7 +580,7 @@ static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, bool l
     // with a scan as well, bf_pc_grad_kernel adds onto (keypoints + silhouette): keep that order of additions
     const bool fold_views = masks && !scans;
     const bool fold_acc = fold_views && acc_mode;
-    if (masks) { rc = launch_mask_kernels(b, mask_weight, false, !fold_views, kp ? &h : nullptr, projected, sub, fold_acc); if (rc) return rc; }
+    if (masks) { rc = launch_mask_kernels(b, mask_weight, eval, !fold_views, kp ? &h : nullptr, projected, sub, fold_acc); if (rc) return rc; }
     HIP_TRY(mark(2));                         // [1,2] keypoint loss (on this stream) and / or the silhouette kernels
     if (scans) {
         bf_nearest_launch(dim3((nv + 3) / 4, F), b->stream, (const ScanDev *)b->scan_dev.p,
@@ -591,6 +595,11 @@ static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, bool l
                            b->dvout.p, b->pc_loss.p, (kp || masks) ? 1 : 0, kp_door ? door : (int *)nullptr, b->kp_tickets);
     }
     if (!scans) HIP_TRY(mark(3));
+    if (dv_extra) {
+        hipLaunchKernelGGL(bf_dv_add_kernel, dim3((nv * 3 + 255) / 256, F), dim3(256), 0, b->stream, b->dvout.p, dv_extra,
+                           sub ? (const int *)sub->verts.p : (const int *)nullptr, nv, m->nv);
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(mark(4));                         // [3,4] point-cloud loss + gradient (+ the join with the keypoint workgroups of the second stream)
     const int EXT = m->npf + m->nj * 12 + m->nb + 4;
     int part_rows = Q.n_tiles;             // (two per tile when the reverse pass splits its tiles: one frame, a small grid)
@@ -696,14 +705,9 @@ static int ensure_fit_stream(bf_batch *b, const FrameIO &io, const HyperDev &hd)
     return BF_OK;
 }
 
-// the loop of smplify.py:177-213 when a dense loss is present (use_mask, use_mesh, or the SMPL-X keypoints
-// with hands + face): iterations that need no dense loss run as one persistent launch; every other iteration
-// is state -> mesh -> losses -> reverse mesh pass -> one fit-kernel iteration (smplify.py:197-210).
-int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDev &hd, FrameIO io) {
-    bf_model *m = b->m;
-    // iterations of THIS call that run before the dense losses switch on: local index it <= thr
-    const int F = b->F, thr = h.dense_after < 0.f ? n_iters / 3 : (int)h.dense_after - b->steps_done;
-    const int n_plain = m->kp_dense ? 0 : std::max(0, std::min(n_iters, thr + 1));
+// what every dense pass of a call reads besides the batch's own buffers: the scans' weights, the silhouette's image size and distance form
+static int dense_prepare(bf_batch *b, const bf_hyper &h) {
+    const int F = b->F;
     if (!b->scans.empty()) {
         // 5 * imsize / scan_height (smplify.py:206,210) of the scans attached NOW and of THIS call's imsize: F floats, staged in
         // pinned memory and copied on the batch's stream (a reused batch gets new scans on every SMPLify.__call__)
@@ -717,18 +721,16 @@ int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDe
         HIP_TRY(hipMemcpyAsync(b->pc_weight.p, b->h_pc_weight, (size_t)F * sizeof(float), hipMemcpyHostToDevice, b->stream));
     }
     if (b->has_masks) { b->mask.imsize = h.imsize; b->mask.cdist = h.mask_cdist_form != 0.f; }
-    int rc = bf_ensure_dense_buffers(b);
-    if (rc) return rc;
-    if (n_plain > 0)
-        HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, n_plain, 0, b->adam_tab.p, b->steps_done, b->fit_smem, b->stream, nullptr));
-    if (n_plain < n_iters) { rc = bf_ensure_fit_image(b, io, hd); if (rc) return rc; }
-    // The dense iterations with the fit kernel RESIDENT (one launch on a second stream, paced by doorbells, BfDoor) when the
-    // forward pass is a kernel that knows how to wait (1..15 frames); BF_DENSE_PERSISTENT=0, or a larger batch, keeps one fit launch
-    // per iteration, with the pose state from bf_pose_state_kernel every time.
+    return bf_ensure_dense_buffers(b);
+}
+
+// the sub-models of a fit loop's dense iterations: before (early) and after (late) the silhouette / scan losses switch on
+static void dense_subs(bf_batch *b, const bf_model::Sub *&sub_early, const bf_model::Sub *&sub_late) {
+    bf_model *m = b->m;
     // (read on every call: a test switches them between two calls of one process)
     const bool sub_ok = [] { const char *e = std::getenv("BF_DENSE_SUBMODEL"); return !(e && e[0] == '0'); }();
     // (the sub-model of iteration `it`: before the dense losses switch on only the keypoint loss's vertices matter - with or without scans)
-    const bf_model::Sub *const sub_late = (sub_ok && m->sub.on && b->scans.empty()) ? &m->sub : nullptr;
+    sub_late = (sub_ok && m->sub.on && b->scans.empty()) ? &m->sub : nullptr;
     const bool sub_kp_ok = [] { const char *e = std::getenv("BF_DENSE_SUBMODEL_KP"); return !(e && e[0] == '0'); }();      // (bring-up switch, like BF_DENSE_SUBMODEL)
     // With silhouettes attached too (round 6; BF_DENSE_SUBMODEL_KP_MASKS=0 keeps rounds 4-5's schedule): the iterations before the
     // silhouette switches on run on the 899 keypoint vertices instead of the 3,285 sampled-first ones - another summation order of those
@@ -736,7 +738,27 @@ int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDe
     // the chaotic end state moved from 1.9 % to 3.9 % of the reference's, outside a band that was 3 x the larger of TWO perturbed
     // reference runs; round 6 measures the reference under ten perturbations (tests/ref_drift.py).
     const bool sub_kp_masks = [] { const char *e = std::getenv("BF_DENSE_SUBMODEL_KP_MASKS"); return !(e && e[0] == '0'); }();
-    const bf_model::Sub *const sub_early = (sub_ok && sub_kp_ok && m->sub_kp.on && (!b->has_masks || sub_kp_masks)) ? &m->sub_kp : sub_late;
+    sub_early = (sub_ok && sub_kp_ok && m->sub_kp.on && (!b->has_masks || sub_kp_masks)) ? &m->sub_kp : sub_late;
+}
+
+// the loop of smplify.py:177-213 when a dense loss is present (use_mask, use_mesh, or the SMPL-X keypoints
+// with hands + face): iterations that need no dense loss run as one persistent launch; every other iteration
+// is state -> mesh -> losses -> reverse mesh pass -> one fit-kernel iteration (smplify.py:197-210).
+int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDev &hd, FrameIO io) {
+    bf_model *m = b->m;
+    // iterations of THIS call that run before the dense losses switch on: local index it <= thr
+    const int F = b->F, thr = h.dense_after < 0.f ? n_iters / 3 : (int)h.dense_after - b->steps_done;
+    const int n_plain = m->kp_dense ? 0 : std::max(0, std::min(n_iters, thr + 1));
+    int rc = dense_prepare(b, h);
+    if (rc) return rc;
+    if (n_plain > 0)
+        HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, n_plain, 0, b->adam_tab.p, b->steps_done, b->fit_smem, b->stream, nullptr));
+    if (n_plain < n_iters) { rc = bf_ensure_fit_image(b, io, hd); if (rc) return rc; }
+    // The dense iterations with the fit kernel RESIDENT (one launch on a second stream, paced by doorbells, BfDoor) when the
+    // forward pass is a kernel that knows how to wait (1..15 frames); BF_DENSE_PERSISTENT=0, or a larger batch, keeps one fit launch
+    // per iteration, with the pose state from bf_pose_state_kernel every time.
+    const bf_model::Sub *sub_early = nullptr, *sub_late = nullptr;
+    dense_subs(b, sub_early, sub_late);
     auto sub_of = [&](int it) { return it > thr ? sub_late : sub_early; };
     const bool door_ok = [] { const char *e = std::getenv("BF_DENSE_PERSISTENT"); return !(e && e[0] == '0'); }();
     const int n_dense = n_iters - n_plain;
@@ -810,6 +832,53 @@ int bf_dense_loss_grad(bf_batch *b, const bf_hyper &h, const HyperDev &hd, Frame
     if (rc) return rc;
     io.ext = b->ext.p;
     HIP_TRY(bf_fit_launch(&b->m->fit, &io, &hd, 1, 1, b->adam_tab.p, 0, b->fit_smem, b->stream, nullptr));
+    return BF_OK;
+}
+
+// bf_dense_iter_grad: what one dense iteration of bf_fit_with_scans hands to Adam, evaluated without the update (launch-per-iteration
+// route, no doorbells).  terms6[6] per frame on the host, or null.
+int bf_dense_iter_eval(bf_batch *b, const bf_hyper &h, const HyperDev &hd, FrameIO io, bool late, bool use_sub, const float *dverts_extra,
+                       float *terms6) {
+    bf_model *m = b->m;
+    const int F = b->F;
+    int rc = dense_prepare(b, h);
+    if (rc) return rc;
+    const bool scans = late && !b->scans.empty(), masks = late && b->has_masks;
+    const bf_model::Sub *sub = nullptr;
+    if (use_sub) {
+        const bf_model::Sub *sub_early = nullptr, *sub_late = nullptr;
+        dense_subs(b, sub_early, sub_late);
+        sub = late ? sub_late : sub_early;
+    }
+    DevBuf<float> extra;
+    if (dverts_extra) HIP_TRY(extra.upload(std::vector<float>(dverts_extra, dverts_extra + (size_t)F * m->nv * 3)));
+    // the closest-point search warm-starts from the faces of the call before it: this call keeps them as it found them
+    DevBuf<int> faces_kept;
+    const bool warm = b->cface_valid;
+    if (scans && warm) {
+        HIP_TRY(faces_kept.alloc(b->cface.n));
+        HIP_TRY(hipMemcpyAsync(faces_kept.p, b->cface.p, b->cface.n * sizeof(int), hipMemcpyDeviceToDevice, b->stream));
+    }
+    rc = dense_pass(b, h, hd, late, 5.0f, nullptr, 0, sub, false, true, extra.p);
+    if (rc) return rc;
+    if (scans) {
+        if (warm) HIP_TRY(hipMemcpyAsync(b->cface.p, faces_kept.p, b->cface.n * sizeof(int), hipMemcpyDeviceToDevice, b->stream));
+        b->cface_valid = warm;
+    }
+    io.ext = b->ext.p;
+    HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, 1, 1, b->adam_tab.p, 0, b->fit_smem, b->stream, nullptr));
+    BF_TRY(bf_sync_all(b));
+    if (terms6) {
+        std::vector<float> t4((size_t)F * 4), mk(F, 0.f), pc(F, 0.f);
+        HIP_TRY(hipMemcpy(t4.data(), b->terms.p, t4.size() * sizeof(float), hipMemcpyDeviceToHost));
+        if (masks) HIP_TRY(hipMemcpy(mk.data(), b->mk_loss.p, (size_t)F * sizeof(float), hipMemcpyDeviceToHost));
+        if (scans) HIP_TRY(hipMemcpy(pc.data(), b->pc_loss.p, (size_t)F * sizeof(float), hipMemcpyDeviceToHost));
+        for (int f = 0; f < F; ++f) {
+            std::copy(t4.begin() + (size_t)f * 4, t4.begin() + (size_t)f * 4 + 4, terms6 + (size_t)f * 6);
+            terms6[(size_t)f * 6 + 4] = 5.0f * mk[f];
+            terms6[(size_t)f * 6 + 5] = pc[f];          // (bf_pc_grad_kernel leaves weight * norm)
+        }
+    }
     return BF_OK;
 }
 

@@ -540,6 +540,16 @@ bf_pc_grad_kernel(const float *__restrict__ P, const float *__restrict__ C, int 
     }
 }
 
+// grid (ceil(3 n / 256), F): dvout[f][i] += extra[f][verts ? verts[i] : i] for the n vertices of the (sub-)model the mesh passes run on;
+// extra[F][nv_full][3] is in the full model's vertex order (bf_dense_iter_grad's dverts_extra)
+extern "C" __global__ void __launch_bounds__(256)
+bf_dv_add_kernel(float *__restrict__ dvout, const float *__restrict__ extra, const int *__restrict__ verts, int n, int nv_full) {
+    const int id = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (id >= n * 3) return;
+    const int i = id / 3, c = id - i * 3, v = verts ? verts[i] : i;
+    dvout[(size_t)f * n * 3 + id] += extra[((size_t)f * nv_full + v) * 3 + c];
+}
+
 // Reverse of the full-mesh forward for one 32-vertex tile and up to FPW frames.  grid (n_tiles, ceil(F / FPW)), 512 threads.
 //   in : dvout[F][NV][3] = dL/d((v + t) s c), vposed[F][NV][3] (pose-blended vertices saved by the forward),
 //        vraw[F][NV][3], state

@@ -98,6 +98,17 @@ class DeviceModel:
         self.n_params = lib.bf_model_n_params(self._h)
         self.fit_instance = "sized" if lib.bf_model_fit_instance(self._h) else "table-driven"
 
+    def sub_vertices(self, which):
+        """full-model vertex ids of a sub-model of the dense iterations, in its order (bf_model_sub_vertices): which = 0 the
+        sampled-first one, 1 the keypoint-only one; an empty array when the model has none"""
+        n = self._lib.bf_model_sub_vertices(self._h, int(which), None)
+        if n < 0:
+            _lib.check(n, "bf_model_sub_vertices")
+        ids = np.empty(n, np.int32)
+        if n:
+            self._lib.bf_model_sub_vertices(self._h, int(which), _lib.iptr(ids))
+        return ids
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.bf_model_destroy(self._h)
@@ -611,6 +622,18 @@ class FrameBatch:
         _lib.check(self._lib.bf_loss_grad(self._h, hp, _lib.fptr(terms), _lib.fptr(grads)), "bf_loss_grad")
         return terms, grads
 
+    def dense_iter_grad(self, hyper=None, late=False, sub_model=False, dverts_extra=None):
+        """(terms[F,6], grads[F,n_params]) of one dense iteration of fit() at the current parameters, without the step
+        (bf_dense_iter_grad); dverts_extra[F,NV,3]: a cotangent added onto dL/d(body vertices)"""
+        terms = np.empty((self.F, 6), np.float32)
+        grads = np.empty((self.F, self.model.n_params), np.float32)
+        hp = C.byref(hyper) if hyper is not None else None
+        extra = None if dverts_extra is None else _f32(dverts_extra, (self.F, self.model.n_verts, 3))
+        flags = (_lib.DENSE_GRAD_LATE if late else 0) | (_lib.DENSE_GRAD_SUBMODEL if sub_model else 0)
+        _lib.check(self._lib.bf_dense_iter_grad(self._h, hp, flags, _lib.fptr(extra), _lib.fptr(terms), _lib.fptr(grads)),
+                   "bf_dense_iter_grad")
+        return terms, grads
+
     # -- outputs -----------------------------------------------------------------------------
     def get_params(self):
         p = np.empty((self.F, self.model.n_params), np.float32)
@@ -677,6 +700,18 @@ class FrameBatch:
         """True / False: the last dense fit ran with the fit kernel resident / one launch per iteration; None: no dense fit yet"""
         r = self._lib.bf_batch_dense_resident(self._h)
         return None if r < 0 else bool(r)
+
+    def debug_vertices(self):
+        """the body vertices [F,NV,3] the last full-model mesh pass left on the device (bf_batch_debug_vertices)"""
+        v = np.empty((self.F, self.model.n_verts, 3), np.float32)
+        _lib.check(self._lib.bf_batch_debug_vertices(self._h, _lib.fptr(v)), "bf_batch_debug_vertices")
+        return v
+
+    def disp_moment(self):
+        """first Adam moment [F,NV,3] of the SMPL+D displacement (bf_batch_debug_disp_moment)"""
+        m = np.empty((self.F, self.model.n_verts, 3), np.float32)
+        _lib.check(self._lib.bf_batch_debug_disp_moment(self._h, _lib.fptr(m)), "bf_batch_debug_disp_moment")
+        return m
 
     def debug_dump(self, n):
         out = np.zeros(n, np.float32)

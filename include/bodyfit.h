@@ -139,6 +139,11 @@ int bf_model_n_params(const bf_model *m);
  * 1 = sizes fixed at compile time (24 joints, 10 betas, 11 loss selector vertices with at most 4 bones each, 25 loss joints: SMPL
  * as models/smpl.py:56-66 builds it), 0 = table-driven (any other model; ~2.5x more cycles per iteration) */
 int bf_model_fit_instance(const bf_model *m);
+/* test hook: the full-model vertex ids of a sub-model the dense iterations run on, in the sub-model's order.  which = 0: the
+ * "sampled first" sub-model (every 4th vertex, then what the keypoint loss reads), 1: the keypoint-only one.  -> their number
+ * (0: the model has no such sub-model); ids may be NULL. */
+int bf_model_sub_vertices(const bf_model *m, int which, int32_t *ids);
+
 
 /* models.smpl.SMPL.forward (models/smpl.py:69-83) for `n` parameter sets:
  * betas[n,NB], global_orient[n,3], body_pose[n,3(NJ-1)] ->
@@ -289,6 +294,31 @@ int bf_fit(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags);
  * parameters, no update: terms[F,4] = reprojection, pose_prior, angle_prior, shape_prior
  * (loss.py:219-224); grads[F,n_params]. */
 int bf_loss_grad(bf_batch *b, const bf_hyper *hyper, float *terms, float *grads);
+/* The gradient one dense iteration of bf_fit hands to Adam, read without taking the step (a test hook, like bf_loss_grad).
+ * At the batch's current parameters it runs that iteration's passes one launch after the other (pose state, forward mesh,
+ * keypoint / silhouette / scan losses, reverse mesh pass, reduction - the schedule bf_fit uses when the fit kernel is not
+ * resident) and then the fit kernel without its update.
+ *   flags  BF_DENSE_GRAD_LATE: the iteration is one after the switch-on (smplify.py:197,205): the silhouette and scan terms are
+ *          on with bf_fit's weights, 5 and 5 * imsize / scan_height.  With neither scans nor silhouettes attached: BF_ERR_INVALID.
+ *          BF_DENSE_GRAD_SUBMODEL: the mesh passes run on the sub-model bf_fit would choose for such an iteration (none where
+ *          bf_fit would use the full model: then the flag changes nothing); without it they run on the full model.
+ *   dverts_extra[F,NV,3] (host, the full model's vertex order; may be NULL) is added onto dL/d(body vertices) just before the
+ *          reverse mesh pass, at the vertices that pass runs on: the objective becomes L + sum(dverts_extra * body_vertices).
+ *   terms[F,6] = reprojection, pose_prior, angle_prior, shape_prior (as bf_loss_grad), 5 x silhouette loss,
+ *          5 * imsize / scan_height x point-cloud loss; the last two are 0 without BF_DENSE_GRAD_LATE (or with nothing of their
+ *          kind attached).  grads[F,n_params].  Either may be NULL.
+ * With flags 0 and no dverts_extra, grads are bf_loss_grad's bit for bit: SMPL-kind models, whose keypoint loss the fit kernel
+ * computes itself, then take the plain fit launch bf_fit uses for such an iteration, without a mesh pass.  (Through the mesh
+ * passes - a dverts_extra, even of zeros - the sized SMPL instance of the fit kernel sums dL/dbetas in another order than its plain
+ * instance: equal to rounding, not to the bit.)  The silhouette's projection runs as a launch of its own here (bf_fit folds it into
+ * the forward mesh pass; the arithmetic is shared).
+ * Synchronous.  Parameters, Adam state, the step count and the closest-point search's warm start stay as they were: a bf_fit
+ * continued afterwards gives the bits it would have given without the call.  The vertices / joints / loss terms that
+ * bf_batch_get_result reads on the device are overwritten (results already fetched with BF_FIT_FETCH are not).
+ * A batch whose scan was destroyed, or whose next inputs are staged, is refused with BF_ERR_INVALID, as by bf_fit. */
+#define BF_DENSE_GRAD_LATE     1u
+#define BF_DENSE_GRAD_SUBMODEL 2u
+int bf_dense_iter_grad(bf_batch *b, const bf_hyper *hyper, uint32_t flags, const float *dverts_extra, float *terms, float *grads);
 int bf_batch_sync(bf_batch *b);
 
 /* rtn_dict of smplify.py:216-226 after bf_fit (any pointer may be NULL):
@@ -689,6 +719,9 @@ int bf_batch_dense_resident(const bf_batch *b);
 int bf_batch_debug_dump(bf_batch *b, float *dst, int n);
 /* first Adam moment of the SMPL+D displacement (after one step = 0.1 x the gradient) */
 int bf_batch_debug_disp_moment(bf_batch *b, float *m_out);
+/* vertices[F,NV,3]: the body vertices the last full-model mesh pass of the batch left on the device (after bf_dense_iter_grad
+ * without BF_DENSE_GRAD_SUBMODEL: the ones its losses were evaluated at) */
+int bf_batch_debug_vertices(bf_batch *b, float *vertices);
 
 #ifdef __cplusplus
 }

@@ -541,3 +541,58 @@ def smplx_loss_and_grad(model, gmm_bufs, problem, params, dtype=torch.float64, c
     loss.backward()
     return (float(loss), {k: float(v) for k, v in terms.items()}, {k: v.grad.numpy()[0].copy() for k, v in P.items()},
             mj.detach().numpy()[0], bv.detach().numpy()[0], int(out["dyn_row"][0]))
+
+
+DENSE_TERMS = ("reprojection_loss", "pose_prior_loss", "angle_prior_loss", "shape_prior_loss", "mask_loss", "scan_loss")
+
+
+def dense_loss_and_grad(model, gmm_bufs, problem, params, dtype=torch.float64, cot=None, masks=None, closest=None, scan_height=None,
+                        constant_scale=None, **loss_kw):
+    """What one iteration of the loop after its switch-on differentiates (smplify.py:189-210), evaluated once at `params` (a dict over
+    the model kind's parameter blocks) for SMPL, kid and SMPL-X models:
+
+        keypoint terms + 5 x multview_mask_loss + 5 * imsize / scan_height x point_cloud_loss + sum(cot * body_vertices)
+
+    masks: None or dict(contours=[C_i,2] arrays, masks=[M,H,W] 0 / 1, views=[M] indices into the problem's views), distances exact;
+    closest: None or [NV,3], the scan's closest points - given by the caller and constant, as the reference detaches them - with
+    scan_height, which also sets the constant scale to scan_height / 1.7 (smplify.py:156) unless constant_scale is given;
+    cot: None or [NV,3], a cotangent on body_vertices (not a reference term: it loads every vertex on its own).
+    -> (terms: dict over DENSE_TERMS, the last two weighted as above; grads: dict of the blocks; body_vertices[NV,3])."""
+    smplx = model.get("model_type", "smpl") == "smplx"
+    m = to_torch_model(model, dtype)
+    gmm = to_torch_gmm(gmm_bufs, dtype)
+    w2cs = torch.inverse(torch.as_tensor(np.asarray(problem["c2ws"]), dtype=torch.float32).to(dtype))
+    Kt = torch.as_tensor(np.asarray(problem["Ks"]), dtype=torch.float32).to(dtype)
+    if constant_scale is None and closest is not None:
+        constant_scale = float(scan_height) / 1.7
+    c, loss_kw = _loss_keywords(problem, constant_scale, loss_kw)
+    names = SMPLX_PARAMS if smplx else ("global_transl", "scale", "pose", "betas", "global_orient")
+    P = {k: torch.tensor(np.asarray(params[k], np.float64).reshape(1, -1), dtype=dtype, requires_grad=True) for k in names}
+    if smplx:
+        from bodyfitting_amd.keypoints import pack_keypoints_smplx
+        kps = [None if k is None else torch.as_tensor(pack_keypoints_smplx(k)).to(dtype) for k in problem["keypoints"]]
+        out = smplx_forward(m, P["betas"], P["global_orient"], P["pose"], P["leye_pose"], P["reye_pose"], P["left_hand_pose"], P["right_hand_pose"])
+    else:
+        kps = [None if k is None else torch.as_tensor(np.asarray(k["pose"]), dtype=torch.float32).to(dtype) for k in problem["keypoints"]]
+        out = smpl_forward(m, P["betas"], P["global_orient"], P["pose"])
+    mj = (out["joints"] + P["global_transl"]) * P["scale"] * c
+    bv = (out["vertices"] + P["global_transl"]) * P["scale"] * c
+    imsize = problem["imsize"]
+    loss, terms = multiview_keypoint_loss(w2cs, Kt, kps, mj, P["pose"], P["betas"], len(problem["use_frames"]), gmm, imsize=imsize,
+                                          use_hand_face=smplx, **loss_kw)
+    terms = dict(terms, mask_loss=torch.zeros((), dtype=dtype), scan_loss=torch.zeros((), dtype=dtype))
+    if masks is not None:
+        idx = list(masks["views"])
+        terms["mask_loss"] = 5 * multview_mask_loss([torch.as_tensor(np.asarray(cc), dtype=dtype) for cc in masks["contours"]],
+                                                    torch.as_tensor(np.asarray(masks["masks"]), dtype=dtype), bv[0], w2cs[idx], Kt[idx],
+                                                    imsize=imsize, pairwise="exact")
+        loss = loss + terms["mask_loss"]
+    if closest is not None:
+        from oracle import mesh_oracle as MO
+        terms["scan_loss"] = 5 * (MO.point_cloud_loss(bv, torch.as_tensor(np.asarray(closest, np.float64)[None], dtype=dtype)) / float(scan_height) * imsize)
+        loss = loss + terms["scan_loss"]
+    if cot is not None:
+        loss = loss + (torch.as_tensor(np.asarray(cot, np.float64), dtype=dtype) * bv[0]).sum()
+    loss.backward()
+    return ({k: float(terms[k].detach()) for k in DENSE_TERMS}, {k: v.grad.numpy()[0].astype(np.float64) for k, v in P.items()},
+            bv.detach().numpy()[0])
