@@ -1,26 +1,15 @@
 // Host side of libbodyfit: the C ABI of include/bodyfit.h over the gfx950 kernels.
 #include "bf_host.h"
+#include "fit_kernels.h"
+#include "mesh_kernels.h"
 #include <chrono>
 
-extern "C" hipError_t bf_fit_launch(const FitTab *, const FrameIO *, const HyperDev *, int, int, const float *, int, size_t, hipStream_t, hipEvent_t);
-extern "C" __global__ void bf_pose_state_kernel(FitTab, const float *, const float *, const float *, const float *, float *, const float *, const float *, float);
-extern "C" __global__ void bf_mesh_kernel(MeshTab, const float *, float *, float *, float *, float *, const float *, int *, int);
-extern "C" __global__ void bf_mesh_span_kernel(MeshTab, const float *, float *, float *, float *, unsigned long long *);
-extern "C" int bf_mesh_use_multi(int npf, int n);
-extern "C" int bf_mesh_multi_launch(const MeshTab *, const float *, int, float *, float *, float *, float *, float *, hipStream_t, const MaskProj *, int *, int, hipEvent_t);
-extern "C" __global__ void bf_mesh_epilogue_kernel(MeshTab, const float *, const float *, float *, float *, float *, float *);
-extern "C" hipError_t bf_poseblend_launch(const MeshTab *M, const float *state, int n, float *featT, int kpad, int fpad, float *pose_off, hipStream_t stream);
-extern "C" bool bf_mesh_batch32_fits(const MeshTab *M);
-extern "C" hipError_t bf_mesh_batch32_launch(const MeshTab *M, const float *state, int n, float *vraw, float *vout, float *xpart, hipStream_t stream);
-extern "C" void bf_mesh_epilogue_batch_launch(const MeshTab *M, const float *state, const float *pose_off, int n, float *vraw, float *vout, float *xpart, hipStream_t stream);
-extern "C" __global__ void bf_joints_kernel(MeshTab, const float *, const float *, const float *, float *, float *, float *, int *, float *);
-extern "C" size_t bf_fit_smem_bytes(int, int, int, int, int, int, int);
 
 // The HIP runtime multiplexes all streams of a process over its hardware queues, and streams that share a queue run in order.  A batch
 // uses up to three streams that must run side by side (batch stream; second stream for a call's mesh tail / the side kernels of a dense
 // iteration; the resident fit launch's stream).  How many queues a process gets is the host's setting (GPU_MAX_HW_QUEUES): the library
 // never changes it.  When the resident launch shares a queue with the batch stream its self-test fails and every dense iteration pays a
-// fit launch instead - same results, slower (scan_api.hip).
+// fit launch instead - same results, slower (dense_api.hip).
 
 std::string &bf_err_slot() { thread_local std::string e; return e; }
 int bf_fail(int code, const std::string &msg) { bf_err_slot() = msg; return code; }
@@ -54,6 +43,7 @@ void bf_hyper_default(bf_hyper *h) {
     h->dense_after = -1.f;
 }
 
+}  // extern "C"
 int bf_launch_mesh(bf_model *m, MeshScratch *scr, int n, const float *state_dev, float *vraw, float *vout, float *xpart, float *joints,
                    float *joints_ori, hipStream_t stream, hipEvent_t after_mesh, float *vposed, float *jraw, int *lmk_vid,
                    float *lmk_w, float *dvzero, bool *zeroed, bool want_xpart, const MaskProj *mproj, bool *projected, int *door, int door_target,
@@ -112,6 +102,7 @@ int bf_launch_mesh(bf_model *m, MeshScratch *scr, int n, const float *state_dev,
     return BF_OK;
 }
 
+extern "C" {
 int bf_smpl_forward(bf_model *m, int n, const float *betas, const float *global_orient, const float *body_pose,
                     float *vertices, float *joints, float *joints_ori) {
     if (!m || n <= 0 || !betas || !global_orient || !body_pose) return fail(BF_ERR_INVALID, "bf_smpl_forward: bad argument");
@@ -143,10 +134,11 @@ int bf_smpl_forward(bf_model *m, int n, const float *betas, const float *global_
 
 // A small fetch as a kernel: device arena -> pinned host mirror with plain stores over PCIe (posted writes, visible to the
 // host when the stream drains); a copy node costs ~20 us of fixed overhead for the same 90 KB.
-__global__ void __launch_bounds__(256) bf_publish_kernel(const float4 *__restrict__ src, float4 *__restrict__ dst, size_t n4) {
+__global__ void __launch_bounds__(256) __attribute__((visibility("hidden"))) bf_publish_kernel(const float4 *__restrict__ src, float4 *__restrict__ dst, size_t n4) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) dst[i] = src[i];
 }
 
+}  // extern "C"
 static int publish(hipStream_t stream, float *dst, const float *src, size_t n_floats) {      // (slices are 256-byte multiples: float4 clean)
     const size_t n4 = n_floats / 4;
     hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, stream,
@@ -352,6 +344,7 @@ int bf_guard_arena(bf_batch *b) {
     return BF_OK;
 }
 
+extern "C" {
 int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
     if (!m || !out || n_frames <= 0 || n_views <= 0) return fail(BF_ERR_INVALID, "bf_batch_create: bad argument");
     *out = nullptr;
@@ -659,6 +652,7 @@ int bf_batch_get_params(bf_batch *b, float *params) {
     return BF_OK;
 }
 
+}  // extern "C"
 HyperDev bf_to_dev(const bf_hyper &h) {
     HyperDev d;
     d.sigma2 = h.sigma * h.sigma;
@@ -671,6 +665,7 @@ HyperDev bf_to_dev(const bf_hyper &h) {
     return d;
 }
 
+extern "C" {
 // torch.optim.Adam evaluates the bias corrections in python floats (double): SURVEY.md 10C
 static int ensure_adam_tab(bf_batch *b, const bf_hyper &h, int upto) {
     bool same = b->adam_cap >= upto && b->adam_hyper.lr == h.lr && b->adam_hyper.lr_transl_scale == h.lr_transl_scale &&

@@ -1,4 +1,4 @@
-// Host-side private definitions shared by api.hip and scan_api.hip.
+// Host-side private definitions shared by the host files (*_api.hip, api.hip, group.hip).
 #pragma once
 #include "../../include/bodyfit.h"
 #include "bf_internal.h"
@@ -430,10 +430,10 @@ struct bf_scan {
 
 
 inline std::mutex &bf_scan_links() { static std::mutex mu; return mu; }      // guards bf_scan::holders and bf_batch::scans of every object
-extern "C" void bf_batch_unlink_scans(struct bf_batch *b);                                // (caller holds bf_scan_links(); device idle) batch forgets its scans, scans forget the batch
+void bf_batch_unlink_scans(struct bf_batch *b);                                // (caller holds bf_scan_links(); device idle) batch forgets its scans, scans forget the batch
 
-// shared between api.hip and scan_api.hip
-extern "C" {
+// Shared between the host files (api.hip, dense_api.hip, mask_api.hip, scan_api.hip): ordinary C++ functions, hidden in the library like
+// everything include/bodyfit.h does not declare - a declaration here that differs from its definition fails to link.
 int bf_ensure_fit_image(struct bf_batch *b, FrameIO io, const HyperDev &hd);
 int bf_launch_mesh(bf_model *m, MeshScratch *scr, int n, const float *state_dev, float *vraw, float *vout, float *xpart, float *joints,
                    float *joints_ori, hipStream_t stream, hipEvent_t after_mesh, float *vposed, float *jraw = nullptr,
@@ -456,8 +456,7 @@ int bf_flush_tail(bf_batch *b);          // enqueue the deferred mesh / hand-ove
 int bf_sync_all(bf_batch *b);            // lanes, copy stream, then compute stream
 int bf_lanes_drain(bf_batch *b);         // no-op unless fit lanes are on: wait for them, hand the last lane fit back to the batch
 int bf_guard_arena(bf_batch *b);         // the compute stream waits for a fetch still reading the current arena
-}
-extern "C" void bf_fit_image_segments(int nj, int nb, int npf, int ns, int nl, int np, int seg[6]);
-extern "C" size_t bf_fit_smem_bytes(int nj, int nb, int npf, int ns, int nl, int np, int nviews);
-extern "C" hipError_t bf_fit_launch(const FitTab *, const FrameIO *, const HyperDev *, int, int, const float *, int, size_t, hipStream_t, hipEvent_t);
-extern "C" bool bf_fit_is_sized_smpl(const FitTab *);
+// `with_kp`: the dense keypoint loss rides in the contour launch (bf_kp_contour_kernel) instead of a launch of its own
+int launch_mask_kernels(bf_batch *b, float weight, bool want_loss, bool sum_views = true, const bf_hyper *with_kp = nullptr,
+                        bool projected = false, const bf_model::Sub *sub = nullptr, bool fold_acc = false);
+int launch_state_and_mesh(bf_batch *b, const HyperDev &hd);

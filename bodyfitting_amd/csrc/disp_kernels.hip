@@ -10,6 +10,7 @@
 // Kernels per iteration: faces -> vertices(+P) -> [nearest, pc_partial from scan_kernels.hip] ->
 // vertex gradient -> face gradient -> vertex gather + Adam.
 #include "bf_internal.h"
+#include "disp_kernels.h"
 #ifndef BF_ADJ_BATCH
 #define BF_ADJ_BATCH 8        // incident faces of a vertex walked together (a closed triangle mesh averages six)
 #endif

@@ -37,6 +37,7 @@
 #include "bf_internal.h"
 #include <hip/hip_ext.h>
 #include "pose_state_body.h"
+#include "fit_kernels.h"
 #include <type_traits>
 
 // Diagnostic build only (-DBF_STAMP, libbodyfit_stamp.so; the product library has no stamps).  Round 5: the stamps are LIGHT - EVERY
@@ -2130,8 +2131,6 @@ extern "C" hipError_t bf_fit_launch_table(const FitTab *T, const FrameIO *io, co
     return fit_launch_one(fit_kernel<0, 0, 0, 0, false>, have, T, io, hp, n_iters, mode, adam_tab, adam_t0, smem, stream, done);
 }
 #else
-extern "C" hipError_t bf_fit_launch_table(const FitTab *, const FrameIO *, const HyperDev *, int, int, const float *, int, size_t, hipStream_t, hipEvent_t);
-
 // The three contiguous runs of model-constant arrays in the carve, as (first float4, float4 count): Jtrel .. nzj | sel_pd2 .. par |
 // pk .. pb_ (each run may contain a scratch array or two; copying them is cheaper than splitting the run)
 extern "C" void bf_fit_image_segments(int nj, int nb, int npf, int ns, int nl, int np, int seg[6]) {

@@ -13,6 +13,7 @@
 //   bf_inside_mesh_kernel  MeshGridSearcher.inside_mesh: parity of the triangles an axis ray crosses (kernel.cu:461-641)
 #include <hip/hip_runtime.h>
 #include "bf_internal.h"
+#include "grid_kernels.h"
 
 struct GridBox { int lo[3], hi[3]; };
 

@@ -91,7 +91,7 @@ int need_rccl() {
 }  // namespace
 
 // One host thread per device of a group.  A dense bf_fit (silhouette / scan losses) enqueues a few launches per iteration for
-// hundreds of iterations and waits for its resident fit launch to be running before it returns (scan_api.hip): issued from ONE
+// hundreds of iterations and waits for its resident fit launch to be running before it returns (dense_api.hip): issued from ONE
 // thread, device k+1 would start after device k's whole sequence is queued.  Every device's calls therefore come from its own
 // thread; the caller's thread posts the job to all of them and waits until every one has returned.
 struct bf_worker {

@@ -1,6 +1,7 @@
 // Host side of the HMR forward pass (reference models/hmr.py: ResNet-50 v1.5 + the iterative regressor, in eval()): the network's
 // layer list, the resident weights, the activation buffers for max_batch images and the launch sequence.  Kernels: hmr_kernels.hip.
 #include "bf_host.h"
+#include "hmr_kernels.h"
 
 #define HMR_RES 224
 #define HMR_FEAT 2048
@@ -8,17 +9,6 @@
 #define HMR_XC (HMR_FEAT + HMR_NSTATE)
 #define HMR_HIDDEN 1024
 #define HMR_ITERS 3                        // HMR.forward's n_iter (hmr.py:140)
-
-struct HmrConv {
-    const float *x, *w, *bias, *res;
-    float *y;
-    int n, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, ldo, relu;
-};
-extern "C" __global__ void bf_hmr_resize_kernel(int, int, int, double, double, const uint8_t *, uint8_t *, float *, float3, float3);
-extern "C" __global__ void bf_hmr_conv_kernel(HmrConv);
-extern "C" __global__ void bf_hmr_maxpool_kernel(int, int, int, int, int, int, const float *, float *);
-extern "C" __global__ void bf_hmr_avgpool_kernel(int, const float *, float *);
-extern "C" __global__ void bf_hmr_init_state_kernel(int, const float *, float *);
 
 namespace {
 struct HmrLayer { size_t w, b; int cin, cout, k, stride, pad; };     // offsets of the packed [K][Cout] weight and the bias

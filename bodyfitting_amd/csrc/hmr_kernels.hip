@@ -2,6 +2,7 @@
 // as one implicit-GEMM kernel on the exact-fp32 MFMA, the pools and the regressor's state.  Host side: hmr_api.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "hmr_kernels.h"
 
 #define HMR_RES 224
 #define HMR_FEAT 2048
@@ -57,12 +58,6 @@ extern "C" __global__ __launch_bounds__(256) void bf_hmr_resize_kernel(int n, in
 // workgroup of four waves, each wave one 32 x 32 block on v_mfma_f32_32x32x2_f32, K staged through LDS 16 at a time.  Every output is
 // a k-ordered fp32 fma chain from 0 whatever the tile, batch size or position, so a batch equals its single images bit for bit;
 // out-of-range rows, columns, k and the spatial padding are zeros in LDS.
-struct HmrConv {
-    const float *x, *w, *bias, *res;
-    float *y;
-    int n, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, ldo, relu;
-};
-
 #define HC_BM 64
 #define HC_BN 64
 #define HC_BK 16

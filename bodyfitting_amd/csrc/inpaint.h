@@ -29,3 +29,19 @@ struct IpConv {
     int deconv, epi, splits, kper;
     float ga, gmu, gs1, gs2;      // GaussActivation (a, mu, sigma1, sigma2), clamped
 };
+
+// the kernels of inpaint_kernels.hip, declared once for the definitions and the host file that launches them
+#pragma GCC visibility push(hidden)       // (a kernel's host-side handle does not follow -fvisibility: see the Makefile)
+extern "C" __global__ void bf_ip_prepare_kernel(long long npx, const uint8_t *img, const uint8_t *msk, float4 *x, float4 *mk, float4 *rmk);
+extern "C" __global__ void bf_ip_enc_kernel(IpConv p);
+extern "C" __global__ void bf_ip_rev128_kernel(IpConv p);
+extern "C" __global__ void bf_ip_rev64_kernel(IpConv p);
+extern "C" __global__ void bf_ip_dec128_kernel(IpConv p);
+extern "C" __global__ void bf_ip_dec64_kernel(IpConv p);
+extern "C" __global__ void bf_ip_reduce_kernel(IpConv p, int dual);
+extern "C" __global__ void bf_ip_faces_kernel(int n_faces, int H, int W, const uint8_t *img, const float *uv, uint8_t *sel, int *err);
+extern "C" __global__ void bf_ip_fill_kernel(int n_faces, int H, int W, const float *uv, const uint8_t *sel, uint8_t *mask);
+extern "C" __global__ void bf_ip_morph_kernel(int op, int k, int n, int H, int W, int C, const uint8_t *in, uint8_t *out);
+extern "C" __global__ void bf_ip_quantize_kernel(long long count, const float *out, uint8_t *img, uint8_t *mask);
+extern "C" __global__ void bf_ip_combine_kernel(long long count, const uint8_t *img, const uint8_t *img2, const uint8_t *mask, const uint8_t *mask_d, uint8_t *out);
+#pragma GCC visibility pop

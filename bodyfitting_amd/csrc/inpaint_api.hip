@@ -4,18 +4,6 @@
 #include "bf_host.h"
 #include "inpaint.h"
 
-extern "C" __global__ void bf_ip_prepare_kernel(long long, const uint8_t *, const uint8_t *, float4 *, float4 *, float4 *);
-extern "C" __global__ void bf_ip_enc_kernel(IpConv);
-extern "C" __global__ void bf_ip_rev128_kernel(IpConv);
-extern "C" __global__ void bf_ip_rev64_kernel(IpConv);
-extern "C" __global__ void bf_ip_dec128_kernel(IpConv);
-extern "C" __global__ void bf_ip_dec64_kernel(IpConv);
-extern "C" __global__ void bf_ip_reduce_kernel(IpConv, int);
-extern "C" __global__ void bf_ip_faces_kernel(int, int, int, const uint8_t *, const float *, uint8_t *, int *);
-extern "C" __global__ void bf_ip_fill_kernel(int, int, int, const float *, const uint8_t *, uint8_t *);
-extern "C" __global__ void bf_ip_morph_kernel(int, int, int, int, int, int, const uint8_t *, uint8_t *);
-extern "C" __global__ void bf_ip_quantize_kernel(long long, const float *, uint8_t *, uint8_t *);
-extern "C" __global__ void bf_ip_combine_kernel(long long, const uint8_t *, const uint8_t *, const uint8_t *, const uint8_t *, uint8_t *);
 
 namespace {
 const int ENC[8] = {4, 64, 128, 256, 512, 512, 512, 512};        // ec1..ec7: ENC[l - 1] -> ENC[l] (ec1's input padded 4, mask 3 -> 4)

@@ -2,8 +2,8 @@
 // MaxMixturePrior as one stateless call on host arrays - what a user's own torch loop (smplify.py:177-213) evaluates behind the
 // body model.  One launch of bf_keypoint_loss_kernel (kp_loss_kernels.hip); the call's buffers come from the device's block cache.
 #include "bf_host.h"
+#include "kp_loss_kernels.h"
 
-extern "C" __global__ void bf_keypoint_loss_kernel(KpLossIO, HyperDev);
 
 struct bf_gmm {
     int device = 0, n_comp = 0, dim = 0;

@@ -18,6 +18,7 @@
 // No atomics; every sum has one order that depends on the sizes alone, so equal inputs give equal bits and a problem's result does
 // not depend on the problems beside it.
 #include "bf_internal.h"
+#include "kp_loss_kernels.h"
 
 namespace {
 __device__ __forceinline__ float kpl_wave_sum(float v) {

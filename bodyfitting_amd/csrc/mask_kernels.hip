@@ -17,6 +17,7 @@
 // which is noisier (about 1e-2 px at 512 px) - see DESIGN.md.
 #include "bf_internal.h"
 #include "loss_bodies.h"
+#include "mask_kernels.h"
 
 namespace {
 __device__ inline float mk_wave_sum(float v) {

@@ -19,6 +19,7 @@
 #include "pose_state_body.h"
 #include "joints_body.h"
 #include "loss_bodies.h"
+#include "mesh_kernels.h"
 #include <cstring>
 #include <type_traits>
 

@@ -3,20 +3,9 @@
 // mesh_loss_kernels.hip; the call's buffers come from the device's block cache; everything runs on the NULL stream, like
 // bf_scan_nearest.
 #include "bf_host.h"
+#include "mesh_loss_kernels.h"
+#include "scan_kernels.h"
 
-extern "C" void bf_nearest_launch(dim3 grid, hipStream_t stream, const ScanDev *scans, const float *points, int n, int *face, float *pts,
-                                  float *bary, int warm);
-extern "C" __global__ void bf_ml_face_kernel(const int *, int, const float *, float *);
-extern "C" __global__ void bf_ml_vertex_kernel(const int *, const int *, int, const float *, float *, float *);
-extern "C" __global__ void bf_ml_vraw_kernel(int, const float *, const float *, float *);
-extern "C" __global__ void bf_ml_fgrad_kernel(const int *, int, const float *, const float *, const float *, float *);
-extern "C" __global__ void bf_ml_gather_kernel(const int *, const int *, int, const float *, float *);
-extern "C" __global__ void bf_ml_lap_partial_kernel(const int *, int, const float *, float *);
-extern "C" __global__ void bf_ml_lap_grad_kernel(const int *, const int *, const int *, int, int, const float *, float *);
-extern "C" __global__ void bf_ml_pc_partial_kernel(int, const float *, const float *, float *);
-extern "C" __global__ void bf_ml_pc_grad_kernel(int, const float *, const float *, const float *, float *);
-extern "C" __global__ void bf_ml_normal_partial_kernel(int, const float *, const float *, float *, float *);
-extern "C" __global__ void bf_ml_finish_kernel(const float *, int, int, float, float *);
 
 struct bf_topo {
     int device = 0, nv = 0, nf = 0;

@@ -8,6 +8,7 @@
 // BF_ADJ_BATCH at a time with the additions in list order, no atomics.  A scalar is reduced in one order that depends on the sizes
 // alone: 256 values per block (lanes by xor-shuffle, the four waves as (0 + 1) + (2 + 3)), then ONE block over the block sums.
 #include "bf_internal.h"
+#include "mesh_loss_kernels.h"
 #ifndef BF_ADJ_BATCH
 #define BF_ADJ_BATCH 8        // incident faces of a vertex walked together (disp_kernels.hip)
 #endif

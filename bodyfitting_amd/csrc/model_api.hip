@@ -2,10 +2,11 @@
 // the host tables are derived from it without a HIP call (derive_tables), then each table struct - FitTab, MeshTab, KpIO, the
 // sub-models - uploads what it points at and takes the pointers (fill_*).
 #include "bf_host.h"
+#include "fit_kernels.h"
+#include "mesh_kernels.h"
 #include <memory>
 #include <numeric>
 
-extern "C" size_t bf_mesh_smem_bytes(int, int, int);
 
 namespace {
 
@@ -459,5 +460,32 @@ int bf_model_sub_vertices(const bf_model *m, int which, int32_t *ids) {
     return (int)U.verts_host.size();
 }
 int bf_model_fit_instance(const bf_model *m) { return (m && bf_fit_is_sized_smpl(&m->fit)) ? 1 : 0; }
+
+// generic forward from packed parameters (bf_model_forward)
+int bf_model_forward(bf_model *m, int n, const float *params, float *vertices, float *joints) {
+    if (!m || n <= 0 || !params) return fail(BF_ERR_INVALID, "bf_model_forward: bad argument");
+    HIP_TRY(hipSetDevice(m->device));
+    DevBuf<float> d_p, d_state, d_vraw, d_j, d_xp;
+    MeshScratch scratch;
+    HIP_TRY(d_p.upload(std::vector<float>(params, params + (size_t)n * m->np)));
+    HIP_TRY(d_state.alloc((size_t)n * bf_state_stride(m->nj, m->npf, m->nb)));
+    HIP_TRY(d_vraw.alloc((size_t)n * m->nv * 3));
+    HIP_TRY(d_j.alloc((size_t)n * m->n_joint_map * 3));
+    HIP_TRY(d_xp.alloc((size_t)n * m->mesh.n_tiles * std::max(m->n_extra, 1) * 3));
+    std::vector<float> zero((size_t)n * m->np, 0.f);
+    // model space: similarity parameters are ignored (transl 0, scale 1, constant scale 1)
+    std::vector<float> pk(params, params + (size_t)n * m->np);
+    for (int i = 0; i < n; ++i) { float *q = pk.data() + (size_t)i * m->np; q[0] = q[1] = q[2] = 0.f; q[3] = 1.f; }
+    HIP_TRY(hipMemcpy(d_p.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(bf_pose_state_kernel, dim3(n), dim3(128), 0, 0, m->fit, (const float *)nullptr, (const float *)nullptr,
+                       (const float *)nullptr, (const float *)nullptr, d_state.p, (const float *)d_p.p, (const float *)nullptr, 1.0f);
+    HIP_TRY(hipGetLastError());
+    int rc = bf_launch_mesh(m, &scratch, n, d_state.p, d_vraw.p, nullptr, d_xp.p, d_j.p, nullptr, 0, nullptr, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (vertices) HIP_TRY(hipMemcpy(vertices, d_vraw.p, d_vraw.n * sizeof(float), hipMemcpyDeviceToHost));
+    if (joints) HIP_TRY(hipMemcpy(joints, d_j.p, d_j.n * sizeof(float), hipMemcpyDeviceToHost));
+    return BF_OK;
+}
 
 }  // extern "C"

@@ -12,17 +12,10 @@
 // bf_smplx_pose_reverse_kernel (dtheta + dfull_pose -> the parameter blocks) behind its reverse.
 // Stateless: nothing stays on the device between calls but the model's lazily built posedirsT.
 #include "bf_host.h"
+#include "mesh_kernels.h"
+#include "model_grad_kernels.h"
+#include "scan_kernels.h"
 
-extern "C" __global__ void bf_pose_state_kernel(FitTab, const float *, const float *, const float *, const float *, float *, const float *, const float *, float);
-extern "C" int bf_mesh_bwd_multi_launch(const MeshTab *, const float *, const float *, int, const float *, const float *, const float *, float *, hipStream_t,
-                                        const float *, int, int, int, int, int *, const MaskFold *);
-extern "C" __global__ void bf_ext_reduce_kernel(const float *, int, int, float *, int, int *, int);
-extern "C" __global__ void bf_model_vjp_fold_kernel(MeshTab, const float *, const float *, const float *, int, const int *, const float *, float *, float *);
-extern "C" __global__ void bf_smpl_vjp_chain_kernel(FitTab, const float *, const float *, int, const float *, float *, float *);
-extern "C" __global__ void bf_smplx_pose_assemble_kernel(FitTab, const float *, const float *, const float *, const float *, const float *, const float *,
-                                                         const float *, float *, float *, float *);
-extern "C" __global__ void bf_smplx_dyn_row_kernel(MeshTab, const float *, int, int *);
-extern "C" __global__ void bf_smplx_pose_reverse_kernel(FitTab, const float *, const float *, float *);
 
 // the model is of the entry point's kind and fits the kernels' LDS tables (BF_GRAD_MAX_*, bf_internal.h)
 static int bf_grad_check(const bf_model *m, int kind, const char *who) {

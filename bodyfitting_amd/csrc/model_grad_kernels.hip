@@ -13,6 +13,7 @@
 // The LDS tables are sized by BF_GRAD_MAX_* (bf_internal.h), which the host checks a model against.
 #include "bf_internal.h"
 #include "pose_state_body.h"
+#include "model_grad_kernels.h"
 
 #define BF_VJP_FOLD_THREADS 256
 

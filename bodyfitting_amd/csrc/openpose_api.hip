@@ -11,12 +11,6 @@
 #define OP_CAT 192                     // the stage input: out1 0:128 | L1 128:166 | 0 0 | L2 168:187 | 0 x 5
 #define OP_NSCALE 4
 
-extern "C" __global__ void bf_op_input_kernel(int, int, int, int, int, int, int, double, const uint8_t *, float4 *);
-extern "C" __global__ void bf_op_up8_kernel(int, int, int, int, int, const float *, float *);
-extern "C" __global__ void bf_op_maps_kernel(int, int, int, int, int, double, double, const float *, double *, double *);
-extern "C" __global__ void bf_op_gauss_kernel(int, int, int, int, int, const double *, double *);
-extern "C" __global__ void bf_op_peaks_kernel(int, int, int, const double *, const double *, int, int *, int *, double *);
-extern "C" __global__ void bf_op_pairs_kernel(int, int, int, const double *, const int *, double *, int *);
 
 namespace {
 const double SCALE_SEARCH[OP_NSCALE] = {0.5, 1.0, 1.5, 2.0};     // body.py:61

@@ -10,12 +10,6 @@
 #define OH_NSCALE 4
 #define OH_MIN_SIDE 13                // scipy's reflect on a line of 13 or more needs one reflection (radius 12)
 
-extern "C" __global__ void bf_oh_input_kernel(int, int, int, int, int, const OhBox *, const uint8_t *, float4 *);
-extern "C" __global__ void bf_oh_up8_kernel(int, int, long long, const OhBox *, const float *, float *);
-extern "C" __global__ void bf_oh_maps_kernel(long long, const OhBox *, const float *, double *);
-extern "C" __global__ void bf_oh_gauss_kernel(int, int, const OhBox *, const double *, double *);
-extern "C" __global__ void bf_oh_pick_kernel(const OhBox *, long long, const double *, const double *, int *, double *, int *, double *, int *);
-extern "C" __global__ void bf_oh_label_kernel(int, int, const uint8_t *, int *, int *, int *);
 
 namespace {
 const double OH_SCALE_SEARCH[OH_NSCALE] = {0.5, 1.0, 1.5, 2.0};   // hand.py:27

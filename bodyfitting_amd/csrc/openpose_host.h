@@ -2,20 +2,7 @@
 // descriptor of openpose_kernels.hip, a packed layer, the launch of one or two convolutions, and the grow-only device buffers.
 #pragma once
 #include "bf_host.h"
-
-struct OpConv {
-    const float *x, *w, *bias;
-    float *y;
-    int ldx, cin, ldo, cout, coutp, k, relu;
-};
-struct OpConvLaunch {
-    OpConv g[2];
-    int n, H, W;
-};
-extern "C" __global__ void bf_op_conv128_kernel(OpConvLaunch);
-extern "C" __global__ void bf_op_conv64_kernel(OpConvLaunch);
-extern "C" __global__ void bf_op_conv7_kernel(OpConvLaunch);
-extern "C" __global__ void bf_op_pool_kernel(int, int, int, int, const float4 *, float4 *);
+#include "openpose_kernels.h"
 
 struct OpLayer { size_t w, b; int cin, cout, coutp, k; };       // packed [k*k*cin][coutp] then the bias [coutp]; cin padded to 4
 

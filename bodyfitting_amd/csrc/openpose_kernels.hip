@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "openpose_device.h"
+#include "openpose_kernels.h"
 
 #define OP_NPAF 38
 #define OP_NHEAT 19
@@ -62,16 +63,6 @@ extern "C" __global__ __launch_bounds__(256) void bf_op_input_kernel(int n, int 
 // wave owns (BM / WM) x (BN / WN) outputs as 32 x 32 blocks of v_mfma_f32_32x32x2_f32.  Every output is a k-ordered fp32 chain
 // from 0 whatever the tile, batch size or position, so a batch equals its single images bit for bit; out-of-range rows, columns,
 // k and the spatial padding are zeros.
-struct OpConv {
-    const float *x, *w, *bias;
-    float *y;
-    int ldx, cin, ldo, cout, coutp, k, relu;
-};
-struct OpConvLaunch {
-    OpConv g[2];
-    int n, H, W;
-};
-
 #define OC_BM 128
 #define OC_BK 16
 typedef float op_f32x16 __attribute__((ext_vector_type(16)));

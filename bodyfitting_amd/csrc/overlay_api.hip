@@ -1,9 +1,9 @@
 // Host side of the fit-check overlay (reference smplify/body_fitting.py:34-42): the views go up once, every vertex of every view is
 // stamped in one launch, the views come back.  Kernel: overlay_kernels.hip; cameras: bodyfitting_amd/overlay.py.
 #include "bf_host.h"
+#include "overlay_kernels.h"
 
 #define OV_CAM 21
-extern "C" __global__ void bf_overlay_stamp_kernel(int, int, int, const float *, const double *, uint8_t *);
 
 extern "C" {
 

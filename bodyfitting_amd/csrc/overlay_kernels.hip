@@ -3,6 +3,7 @@
 // Rodrigues round trip and the numpy restatement: bodyfitting_amd/overlay.py.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "overlay_kernels.h"
 
 #define OV_THREADS 256
 

@@ -1,49 +1,19 @@
-// Host side of the scan (use_mesh) path: grid construction, closest-point queries, and the per-iteration
-// schedule of smplify.py:205-213 with the point-cloud loss switched on after num_iters // 3.
+// Host side of the scan (use_mesh) objects: grid construction, the closest-point, inside and intersection queries, and attaching a
+// frame's scans to a batch.  The per-iteration schedule that fits against them is dense_api.hip.
 #include "bf_host.h"
-#include <algorithm>
-#include <atomic>
-#include <chrono>
+#include "grid_kernels.h"
+#include "scan_kernels.h"
 
-extern "C" __global__ void bf_pose_state_kernel(FitTab, const float *, const float *, const float *, const float *, float *, const float *, const float *, float);
-extern "C" void bf_nearest_launch(dim3 grid, hipStream_t stream, const ScanDev *scans, const float *points, int n, int *face, float *pts,
-                                  float *bary, int warm);        // scan_kernels.hip: the rule selected by bf_nearest_rule_set / BF_NEAREST_RULE
-extern "C" __global__ void bf_pc_partial_kernel(const float *, const float *, int, float *);
-extern "C" __global__ void bf_pc_grad_kernel(const float *, const float *, int, const float *, const float *, float *, float *, int, int *, int);
-extern "C" __global__ void bf_dv_add_kernel(float *, const float *, const int *, int, int);
-extern "C" int bf_mesh_bwd_multi_launch(const MeshTab *, const float *, const float *, int, const float *, const float *, const float *, float *, hipStream_t,
-                                        const float *, int, int, int, int, int *, const MaskFold *);
-extern "C" __global__ void bf_ext_reduce_kernel(const float *, int, int, float *, int, int *, int);
-extern "C" int bf_mesh_use_multi(int npf, int n);
-extern "C" __global__ void bf_door_probe_kernel(int *);
-extern "C" __global__ void bf_door_ring_kernel(int *);
-extern "C" __global__ void bf_kp_loss_kernel(KpIO, const float *, const float *, const float *, const float *, const int *, const int *,
-                                             const float *, float *, float *, float *, MeshTab, const float *, const float *, int *);
-extern "C" __global__ void bf_grid_count_kernel(ScanDev, int *);
-extern "C" __global__ void bf_grid_scan_kernel(int *, int *, int);
-extern "C" __global__ void bf_grid_fill_kernel(ScanDev, int *, int *);
-extern "C" __global__ void bf_grid_pack_kernel(ScanDev, const int *, int *, float4 *, float4 *, int);
-extern "C" __global__ void bf_face_normal_kernel(const float *, const int *, int, float *);
-extern "C" __global__ void bf_inside_mesh_kernel(ScanDev, const float *, int, float *);
-extern "C" __global__ void bf_intersect_kernel(ScanDev, const float *, const float *, int, unsigned char *);
-extern "C" __global__ void bf_nearest_backward_kernel(ScanDev, int, const int *, const float *, const float *, float *);
-extern "C" __global__ void bf_transpose_kernel(const float *, int, int, float *, int);
-extern "C" __global__ void bf_contour_kernel(const unsigned char *, int, int, int, int, float *, int *, unsigned *);
-extern "C" __global__ void bf_kp_contour_kernel(KpIO, const float *, const float *, const float *, const float *, const int *, const int *,
-                                                const float *, float *, float *, float *, MaskIO, const float *, int *, float *, float *,
-                                                MeshTab, const float *, const float *);
-extern "C" __global__ void bf_mask_project_kernel(MaskIO, const float *, const float *, float *, float *, float *);
-extern "C" __global__ void bf_mask_contour_kernel(MaskIO, const float *, int *, float *, float *);
-extern "C" __global__ void bf_mask_gather_kernel(MaskIO, const float *, const float *, const float *, const int *, const float *, float *);
-extern "C" __global__ void bf_mask_loss_kernel(MaskIO, const float *, float *);
-extern "C" __global__ void bf_mask_gsum_kernel(MaskIO, const float *, float *);
-extern "C" __global__ void bf_disp_face_kernel(const int *, int, int, const float *, const float *, float *);
-extern "C" __global__ void bf_disp_vertex_kernel(const int *, const int *, int, int, const float *, const float *, const float *, float *, float *);
-extern "C" __global__ void bf_disp_vgrad_kernel(const int *, const int *, const int *, int, int, const float *, const float *const *,
-                                                const int *, const float *, float *, const float *, const float *, float *);
-extern "C" __global__ void bf_disp_fgrad_kernel(const int *, int, int, const float *, const float *, const float *, float *);
-extern "C" __global__ void bf_disp_adam_kernel(const int *, const int *, int, int, const float *, const float *, const float *, int,
-                                               const float *, float *, float *, float *, float, float, float, float, float);
+void bf_batch_unlink_scans(bf_batch *b) {
+    for (bf_scan *sc : b->scans) {
+        if (!sc) continue;
+        auto it = std::find(sc->holders.begin(), sc->holders.end(), b);
+        if (it != sc->holders.end()) sc->holders.erase(it);
+    }
+    b->scans.clear();
+    b->cface_valid = false;
+    if (b->cscale.p) { (void)hipFree(b->cscale.p); b->cscale.p = nullptr; }
+}
 
 extern "C" {
 
@@ -162,16 +132,6 @@ void bf_scan_destroy(bf_scan *s) {
     delete s;
 }
 
-void bf_batch_unlink_scans(bf_batch *b) {
-    for (bf_scan *sc : b->scans) {
-        if (!sc) continue;
-        auto it = std::find(sc->holders.begin(), sc->holders.end(), b);
-        if (it != sc->holders.end()) sc->holders.erase(it);
-    }
-    b->scans.clear();
-    b->cface_valid = false;
-    if (b->cscale.p) { (void)hipFree(b->cscale.p); b->cscale.p = nullptr; }
-}
 int64_t bf_device_cache_trim(int device) {
     if (device < 0 || device >= 16 || hipSetDevice(device) != hipSuccess) return -1;
     return (int64_t)bf_pool_trim(device);
@@ -286,8 +246,6 @@ int bf_scan_nearest_hinted(bf_scan *s, int n, const float *points, const float *
 
 // self-tests of the reference-arithmetic rule (nearest_rule_ref.h): its division helper against the caller's IEEE quotients, and the
 // per-triangle rule on explicit patches
-extern "C" __global__ void bf_nearest_quot_kernel(int, const float *, const float *, float *);
-extern "C" __global__ void bf_nearest_rule_kernel(int, const float *, float *, float *, int);
 int bf_nearest_selftest_quot(int device, int n, const float *num, const float *den, float *out) {
     if (n <= 0 || !num || !den || !out) return fail(BF_ERR_INVALID, "bf_nearest_selftest_quot: bad argument");
     HIP_TRY(hipSetDevice(device));
@@ -325,54 +283,6 @@ int bf_scan_nearest_backward(bf_scan *s, int n, const int32_t *face_ids, const f
                        (const float *)d_g.p, d_o.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(dpoints, d_o.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
-}
-
-// [3NV][npf] transpose for the reverse pass (thread = pose-feature row, contiguous reads), built on the device once per model: the
-// caller holds the model's lock (bf_model::lazy), and the table is finished before anybody can see the pointer (batches of the model run on
-// other streams).  Used by the dense schedule and by bf_smpl_vjp.
-int bf_ensure_posedirsT_locked(bf_model *m, hipStream_t stream) {
-    if (m->posedirsT.p) return BF_OK;
-    const size_t nv3 = (size_t)m->nv * 3;
-    DevBuf<float> t;
-    HIP_TRY(t.alloc((size_t)nv3 * m->npf));
-    hipLaunchKernelGGL(bf_transpose_kernel, dim3((nv3 + 31) / 32, (m->npf + 31) / 32), dim3(256), 0, stream,
-                       (const float *)m->posedirs.p, m->npf, (int)nv3, t.p, m->mesh.pd_pitch);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    m->posedirsT.p = t.p; m->posedirsT.n = t.n; t.p = nullptr;
-    return BF_OK;
-}
-
-int bf_ensure_dense_buffers(bf_batch *b) {
-    bf_model *m = b->m;
-    const size_t F = b->F, nv3 = (size_t)m->nv * 3;
-    const int EXT = m->npf + m->nj * 12 + m->nb + 4, EXT_FULL = EXT + m->nj * 3 + 4;
-    if (!b->dvout.p) {
-        bool ok = b->dvout.alloc(F * nv3) == hipSuccess && b->vposed.alloc(F * nv3) == hipSuccess &&
-                  b->cpts.alloc(F * nv3) == hipSuccess && b->cface.alloc(F * m->nv) == hipSuccess && !(b->cface_valid = false) &&
-                  b->ext_part.alloc(F * m->mesh.n_tiles * EXT) == hipSuccess && b->ext.alloc(F * EXT_FULL) == hipSuccess &&
-                  b->jraw.alloc(F * std::max(m->n_all, 1) * 3) == hipSuccess && b->lmk_vid.alloc(F * std::max(m->n_lmk, 1) * 3) == hipSuccess &&
-                  b->lmk_w.alloc(F * std::max(m->n_lmk, 1) * 3) == hipSuccess &&
-                  b->pc_partial.alloc(F * ((m->nv + 255) / 256)) == hipSuccess && b->pc_loss.alloc(F) == hipSuccess;
-        if (!ok) return fail(BF_ERR_HIP, "dense-loss buffers: device allocation failed");
-        HIP_TRY(bf_memset_sync(b->ext.p, 0, b->ext.n * sizeof(float)));
-    }
-    {
-        std::lock_guard<std::mutex> g(m->lazy);
-        BF_TRY(bf_ensure_posedirsT_locked(m, b->stream));
-        for (bf_model::Sub *U : {&m->sub, &m->sub_kp}) {
-            if (!U->on || U->posedirsT.p) continue;
-            const size_t sv3 = (size_t)U->mesh.nv * 3;
-            DevBuf<float> t;
-            HIP_TRY(t.alloc(sv3 * m->npf));
-            hipLaunchKernelGGL(bf_transpose_kernel, dim3((sv3 + 31) / 32, (m->npf + 31) / 32), dim3(256), 0, b->stream,
-                               (const float *)U->posedirs.p, m->npf, (int)sv3, t.p, U->mesh.pd_pitch);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(b->stream));
-            U->posedirsT.p = t.p; U->posedirsT.n = t.n; t.p = nullptr;
-        }
-    }
     return BF_OK;
 }
 
@@ -419,896 +329,6 @@ int bf_batch_set_scans(bf_batch *b, bf_scan *const *scans) {
     if (b->scan_fn.p && b->scan_fn.n == fn.size()) HIP_TRY(hipMemcpy((void *)b->scan_fn.p, fn.data(), fn.size() * sizeof(const float *), hipMemcpyHostToDevice));
     else { b->scan_fn.release(); HIP_TRY(b->scan_fn.upload(fn)); }
     return bf_ensure_dense_buffers(b);
-}
-
-static size_t kp_smem(const KpIO &K) {
-    const int NLP = (K.nl + 31) & ~31, slots = std::max(1, 512 / NLP);
-    // (the joints prologue's scratch, 32*3 + 256*3 + 4 floats, fits the head of this)
-    // (+ sort keys, item weights, + the index tables staged in LDS: joint map, chain-joint CSR, selector ids)
-    return sizeof(float) * std::max<size_t>(1024, (size_t)slots * NLP * 4 + (size_t)K.nl * 4 + (size_t)K.nl * 3 + 8 + 1024 + (size_t)K.nl * 3 + 16 +
-                                                   (size_t)K.nl * 2 + K.nj + 1 + K.n_selector + 16);
-
-}
-static KpIO kp_io(bf_batch *b, const bf_hyper &h, const bf_model::Sub *sub = nullptr) {
-    KpIO K = sub ? sub->kp : b->m->kp;
-    K.n_views = b->V; K.sigma2 = h.sigma * h.sigma; K.coeff = h.imsize / 1024.0f;
-    return K;
-}
-// (the keypoint workgroup computes the joints itself from the mesh pass's vraw / xpart: no bf_joints_kernel launch)
-static int launch_kp(bf_batch *b, const bf_hyper &h, const bf_model::Sub *sub = nullptr, hipStream_t on = nullptr, int *door = nullptr) {
-    const KpIO K = kp_io(b, h, sub);
-    hipLaunchKernelGGL(bf_kp_loss_kernel, dim3(b->F), dim3(512), kp_smem(K), on ? on : b->stream, K, (const float *)b->jraw.p, (const float *)b->state.p,
-                       (const float *)b->proj.p, (const float *)b->keypoints.p, (const int *)b->ndiv.p, (const int *)b->lmk_vid.p,
-                       (const float *)b->lmk_w.p, b->ext.p, b->dvout.p, b->terms.p, sub ? sub->mesh : b->m->mesh, (const float *)b->vraw.p,
-                       (const float *)b->xpart.p, door);
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
-}
-
-// `with_kp`: the dense keypoint loss rides in the contour launch (bf_kp_contour_kernel) instead of a launch of its own
-static int launch_mask_kernels(bf_batch *b, float weight, bool want_loss, bool sum_views = true, const bf_hyper *with_kp = nullptr,
-                               bool projected = false, const bf_model::Sub *sub = nullptr, bool fold_acc = false) {
-    // fold_acc: the contour scan adds its gradients into the fixed-point sums (MaskIO::acc) and the reverse mesh pass takes them from
-    // there (MaskFold): no gather launch
-    MaskIO K = b->mask;
-    K.weight = weight;
-    K.acc = fold_acc ? b->mk_acc.p : nullptr;
-    if (sub) { K.nv = sub->mesh.nv; K.sstride = 1; }
-    const int F = b->F;
-    // (projected: the forward mesh pass already wrote uvi / duvb for its sampled vertices)
-    if (!projected) hipLaunchKernelGGL(bf_mask_project_kernel, dim3(K.proj_blocks, K.n_masks, F), dim3(256), 0, b->stream, K, (const float *)b->vout.p,
-                       (const float *)b->proj.p, b->mk_uvi.p, b->mk_duvb.p, b->mk_part.p);
-    if (with_kp) {
-        const KpIO Q = kp_io(b, *with_kp, sub);
-        hipLaunchKernelGGL(bf_kp_contour_kernel, dim3((K.cmax * 16 + 511) / 512 + 1, K.n_masks, F), dim3(512), kp_smem(Q), b->stream, Q,
-                           (const float *)b->jraw.p, (const float *)b->state.p, (const float *)b->proj.p, (const float *)b->keypoints.p,
-                           (const int *)b->ndiv.p, (const int *)b->lmk_vid.p, (const float *)b->lmk_w.p, b->ext.p, b->dvout.p, b->terms.p,
-                           K, (const float *)b->mk_uvi.p, b->mk_choice.p, b->mk_cgrad.p, b->mk_part.p, sub ? sub->mesh : b->m->mesh, (const float *)b->vraw.p,
-                           (const float *)b->xpart.p);
-    } else
-    hipLaunchKernelGGL(bf_mask_contour_kernel, dim3((K.cmax * 16 + 255) / 256, K.n_masks, F), dim3(256), 0, b->stream, K,
-                       (const float *)b->mk_uvi.p, b->mk_choice.p, b->mk_cgrad.p, b->mk_part.p);
-    if (!fold_acc)
-    hipLaunchKernelGGL(bf_mask_gather_kernel, dim3((K.ns + 63) / 64, K.n_masks, F), dim3(256), 0, b->stream, K, (const float *)b->proj.p,
-                       (const float *)b->mk_uvi.p, (const float *)b->mk_duvb.p, (const int *)b->mk_choice.p,
-                       (const float *)b->mk_cgrad.p, b->mk_gpart.p);
-    // (sum_views = false: the reverse mesh pass adds the views itself while it loads dL/dvertices)
-    if (sum_views) hipLaunchKernelGGL(bf_mask_gsum_kernel, dim3(K.proj_blocks, F), dim3(256), 0, b->stream, K, (const float *)b->mk_gpart.p, b->dvout.p);
-    // (the loss VALUE is a serial sum over the partial blocks: only when somebody reads it - the fit loop needs the gradient)
-    if (want_loss) hipLaunchKernelGGL(bf_mask_loss_kernel, dim3(F), dim3(64), 0, b->stream, K, (const float *)b->mk_part.p, b->mk_loss.p);
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
-}
-
-static int launch_state_and_mesh(bf_batch *b, const HyperDev &hd) {
-    bf_model *m = b->m;
-    hipLaunchKernelGGL(bf_pose_state_kernel, dim3(b->F), dim3(128), 0, b->stream, m->fit, (const float *)nullptr,
-                       (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, b->state.p,
-                       (const float *)b->params.p, (const float *)b->cscale.p, hd.cscale);
-    HIP_TRY(hipGetLastError());
-    return bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, nullptr, nullptr, nullptr, b->stream, nullptr, b->vposed.p);
-}
-
-// one dense iteration's forward + loss + reverse passes up to `ext` (everything except the fit kernel itself)
-// door / door_k: the persistent fit launch's doorbells and this pass's 1-based dense iteration (null / 0: fit launches per iteration)
-// sub: run the mesh passes on a sub-model (bf_model::Sub): the sampled-first one for fit loops without scans, the keypoint-only one for
-// the iterations before the dense losses switch on; null = the full model
-// BF_DOOR_COHERENT=0: the kernels that wait for the resident fit launch read its pose states with plain loads (see bf_ld_state)
-// bf_mask_fold_set / BF_MASK_FOLD=gather: the silhouette's contour gradients through bf_mask_gather_kernel's ordered walk (rounds 2-4)
-// instead of the contour scan's fixed-point atomic sums (MaskIO::acc)
-static std::atomic<int> &mask_fold_cell() {
-    static std::atomic<int> cell([] { const char *e = std::getenv("BF_MASK_FOLD"); return (e && e[0] == 'g') ? BF_MASK_FOLD_GATHER : BF_MASK_FOLD_SUMS; }());
-    return cell;
-}
-extern "C" int bf_mask_fold_get(void) { return mask_fold_cell().load(std::memory_order_relaxed); }
-extern "C" int bf_mask_fold_set(int mode) {
-    if (mode != BF_MASK_FOLD_SUMS && mode != BF_MASK_FOLD_GATHER) return -1;
-    mask_fold_cell().store(mode, std::memory_order_relaxed);
-    return 0;
-}
-static bool fold_acc_on() { return bf_mask_fold_get() == BF_MASK_FOLD_SUMS; }
-static bool door_coherent() { const char *e = std::getenv("BF_DOOR_COHERENT"); return !(e && e[0] == '0'); }
-
-static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, bool late, float mask_weight, int *door = nullptr, int door_k = 0,
-                      const bf_model::Sub *sub = nullptr, bool timed = false, bool eval = false, const float *dv_extra = nullptr) {
-    // eval (bf_dense_iter_grad): dL/dvertices starts from zero whatever the model, the silhouette's loss value is summed, the
-    // projection runs as a launch of its own (it leaves the binary term's partial sums), and dv_extra[F][NV][3] (device, full-model
-    // vertex order) is added onto dL/dvertices just before the reverse mesh pass
-    bf_model *m = b->m;
-    // (timed: events between the kernel classes of this pass, for bf_batch_dense_timing)
-    auto mark = [&](int k) -> hipError_t {
-        if (!timed) return hipSuccess;
-        if (!b->ev_dense[k]) { hipError_t e = hipEventCreate(&b->ev_dense[k]); if (e != hipSuccess) return e; }
-        return hipEventRecord(b->ev_dense[k], b->stream);
-    };
-    HIP_TRY(mark(0));
-    const MeshTab &Q = sub ? sub->mesh : m->mesh;
-    const int F = b->F, nv = Q.nv, nblk = (nv + 255) / 256;
-    const bool scans = late && !b->scans.empty(), masks = late && b->has_masks, kp = m->kp_dense;
-    const bool acc_mode = fold_acc_on();          // (read once per pass)
-    if (masks) BF_TRY(bf_masks_finalize(b));
-    if (!door) {                     // (with the resident fit launch every state comes from it)
-        hipLaunchKernelGGL(bf_pose_state_kernel, dim3(F), dim3(128), 0, b->stream, m->fit, (const float *)nullptr,
-                           (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, b->state.p,
-                           (const float *)b->params.p, (const float *)b->cscale.p, hd.cscale);
-        HIP_TRY(hipGetLastError());
-    }
-    bool zeroed = false;                      // dL/dvertices = 0 before the keypoint / silhouette kernels add into it
-    // (kp: the mesh pass leaves the extra-regressor partials in xpart; the joints are formed by the keypoint workgroup)
-    MaskProj mp;
-    bool projected = false;
-    if (masks) {
-        mp.on = 1; mp.K = b->mask; mp.K.weight = mask_weight; mp.proj = b->proj.p; mp.uvi = b->mk_uvi.p; mp.duvb = b->mk_duvb.p;
-        mp.K.acc = (acc_mode && !scans) ? b->mk_acc.p : nullptr;      // (zeroed by the projection that precedes the contour scan)
-        if (sub) { mp.K.nv = nv; mp.K.sstride = 1; }
-    }
-    const bool kp_aside = kp && !masks && scans && b->copy_stream;       // (see below)
-    const bool kp_door = kp_aside && door && b->kp_door_ok;              // the join of the second stream's keypoint workgroups: doorbell or event
-    bool forked = false;                                                  // ev_aux[0] completes with the mesh dispatch itself
-    if (kp_aside && !b->ev_aux[0]) {
-        HIP_TRY(hipEventCreateWithFlags(&b->ev_aux[0], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&b->ev_aux[1], hipEventDisableTiming));
-    }
-    int rc = bf_launch_mesh(m, &b->scratch, F, b->state.p, b->vraw.p, b->vout.p, kp ? b->xpart.p : nullptr, nullptr, nullptr, b->stream, nullptr,
-                            b->vposed.p, nullptr, nullptr, nullptr, (kp || masks || eval) ? b->dvout.p : nullptr, &zeroed, kp, (masks && !eval) ? &mp : nullptr,
-                            &projected, door, (F * door_k) | (door_coherent() ? 0x40000000 : 0), sub ? &Q : nullptr,
-                            kp_aside ? b->ev_aux[0] : nullptr, &forked);
-    if (rc) return rc;
-    if ((kp || masks || eval) && !zeroed) HIP_TRY(hipMemsetAsync(b->dvout.p, 0, b->dvout.n * sizeof(float), b->stream));
-    HIP_TRY(mark(1));                         // [0,1] pose state (when not resident) + forward mesh pass
-    // The dense keypoint loss and the closest-point search both only read the mesh: with scans attached the keypoint workgroups (one
-    // per frame, a ~25 us latency chain) run on the batch's second stream UNDER the search - that stream is idle during a dense loop
-    // and, being on another priority, has a hardware queue of its own - and are joined before bf_pc_grad_kernel adds onto their
-    // dL/dvertices.
-    // (With a silhouette loss instead the keypoint workgroups ride in the contour launch: taking them out onto the second stream was
-    //  measured slower - 0.093 vs 0.085 ms per iteration - the fork / join costs more than the 7 us the merged launch waits for them.)
-    if (kp_aside) {
-        // (the fork: the mesh dispatch's own completion signal when it could carry one - a record here is a marker packet between the
-        //  mesh pass and the search, ~4 us of the batch stream's time per iteration)
-        if (!forked || !zeroed) HIP_TRY(hipEventRecord(b->ev_aux[0], b->stream));
-        HIP_TRY(hipStreamWaitEvent(b->copy_stream, b->ev_aux[0], 0));
-        // (the join: with the resident launch's doorbells at hand the keypoint workgroups count themselves off there and
-        //  bf_pc_grad_kernel waits for the count - BF_DOOR_KP; without them an event on the second stream and a wait on this one)
-        //  The doorbell join needs the second stream's kernels to RUN while bf_pc_grad_kernel's workgroups spin on the batch stream: it is
-        //  used only when ensure_fit_stream's second probe has shown that pair of streams side by side (kp_door_ok; BF_KP_JOIN=event
-        //  forces the stream-level join) - the event join cannot fail that way.
-        rc = launch_kp(b, h, sub, b->copy_stream, kp_door ? door : nullptr);
-        if (rc) return rc;
-        if (kp_door) b->kp_tickets += F;
-        else HIP_TRY(hipEventRecord(b->ev_aux[1], b->copy_stream));
-    } else if (kp && !masks) { rc = launch_kp(b, h, sub); if (rc) return rc; }
-    // with a scan as well, bf_pc_grad_kernel adds onto (keypoints + silhouette): keep that order of additions
-    const bool fold_views = masks && !scans;
-    const bool fold_acc = fold_views && acc_mode;
-    if (masks) { rc = launch_mask_kernels(b, mask_weight, eval, !fold_views, kp ? &h : nullptr, projected, sub, fold_acc); if (rc) return rc; }
-    HIP_TRY(mark(2));                         // [1,2] keypoint loss (on this stream) and / or the silhouette kernels
-    if (scans) {
-        bf_nearest_launch(dim3((nv + 3) / 4, F), b->stream, (const ScanDev *)b->scan_dev.p,
-                          (const float *)b->vout.p, nv, b->cface.p, b->cpts.p, (float *)nullptr, b->cface_valid ? 1 : 0);   // (one wave per query; warm start from the previous call's faces)
-        b->cface_valid = true;
-        HIP_TRY(mark(3));                     // [2,3] closest-point search
-        hipLaunchKernelGGL(bf_pc_partial_kernel, dim3(nblk, F), dim3(256), 0, b->stream, (const float *)b->vout.p,
-                           (const float *)b->cpts.p, nv, b->pc_partial.p);
-        if (kp_aside && !kp_door) HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_aux[1], 0));
-        hipLaunchKernelGGL(bf_pc_grad_kernel, dim3(nblk, F), dim3(256), 0, b->stream, (const float *)b->vout.p,
-                           (const float *)b->cpts.p, nv, (const float *)b->pc_partial.p, (const float *)b->pc_weight.p,
-                           b->dvout.p, b->pc_loss.p, (kp || masks) ? 1 : 0, kp_door ? door : (int *)nullptr, b->kp_tickets);
-    }
-    if (!scans) HIP_TRY(mark(3));
-    if (dv_extra) {
-        hipLaunchKernelGGL(bf_dv_add_kernel, dim3((nv * 3 + 255) / 256, F), dim3(256), 0, b->stream, b->dvout.p, dv_extra,
-                           sub ? (const int *)sub->verts.p : (const int *)nullptr, nv, m->nv);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(mark(4));                         // [3,4] point-cloud loss + gradient (+ the join with the keypoint workgroups of the second stream)
-    const int EXT = m->npf + m->nj * 12 + m->nb + 4;
-    int part_rows = Q.n_tiles;             // (two per tile when the reverse pass splits its tiles: one frame, a small grid)
-    {
-        MaskFold fold = {};
-        if (fold_acc) { fold.acc = b->mk_acc.p; fold.uvi = b->mk_uvi.p; fold.duvb = b->mk_duvb.p; fold.proj = b->proj.p; fold.view_index = b->mask.view_index; fold.n_views = b->V; }
-        const int e = bf_mesh_bwd_multi_launch(&Q, sub ? sub->posedirsT.p : m->posedirsT.p, b->state.p, F, b->dvout.p, b->vposed.p, b->vraw.p, b->ext_part.p,
-                                               b->stream, (fold_views && !fold_acc) ? (const float *)b->mk_gpart.p : nullptr, b->mask.n_masks, b->mask.ns, sub ? 1 : 4,
-                                               (sub && sub == &m->sub_kp) ? Q.n_tiles : m->mesh.n_tiles, &part_rows, fold_acc ? &fold : nullptr);      // (keypoint-only sub-model: no tile split - a batch of 8 and its single frames keep the same partial sums)
-        if (e) return fail(BF_ERR_HIP, std::string("bf_mesh_bwd_multi_kernel: ") + hipGetErrorString((hipError_t)e));
-    }
-    HIP_TRY(mark(5));                         // [4,5] reverse mesh pass
-    hipLaunchKernelGGL(bf_ext_reduce_kernel, dim3((EXT + BF_RED_COLS - 1) / BF_RED_COLS, F), dim3(8 * BF_RED_COLS), 0, b->stream,
-                       (const float *)b->ext_part.p, part_rows, EXT, b->ext.p, EXT + m->nj * 3 + 4, door, door_k);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(mark(6));                         // [5,6] reduction of the partial blocks (rings the resident fit launch)
-    if (timed) b->dense_timed = true;
-    return BF_OK;
-}
-
-// FitTab::lds_image of the model's dense-schedule fit instance: one launch in mode 2 runs the kernel's ordinary prologue and
-// dumps the LDS segment (everything up to the per-view projection matrices, which come last in the carve).  Built once per
-// model, under its lock, finished before the pointer becomes visible.
-int bf_ensure_fit_image(bf_batch *b, FrameIO io, const HyperDev &hd) {
-    bf_model *m = b->m;
-    std::lock_guard<std::mutex> g(m->lazy);
-    if (m->fit.lds_image) return BF_OK;
-    int seg[6];
-    bf_fit_image_segments(m->fit.nj, m->fit.nb, m->fit.npf, m->fit.ns, m->fit.nl, m->fit.np, seg);
-    const size_t bytes = (size_t)(seg[4] + seg[5] + 2 * ((m->fit.np + 3) / 4)) * 16;      // up to the end of am / av: everything before proj
-    FitTab T = m->fit;
-    T.lds_image_n4 = (int)(bytes / 16);
-    HIP_TRY(m->fit_image.alloc(bytes / sizeof(float)));
-    io.ext = nullptr; io.image_out = m->fit_image.p; io.n_frames = 1;      // (the carve, hence the image, is the same for every instance of the model's sizes)
-    HIP_TRY(bf_fit_launch(&T, &io, &hd, 1, 2, b->adam_tab.p, 0, b->fit_smem, b->stream, nullptr));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    m->fit.lds_image_n4 = T.lds_image_n4;
-    bf_fit_image_segments(m->fit.nj, m->fit.nb, m->fit.npf, m->fit.ns, m->fit.nl, m->fit.np, &m->fit.img_seg[0][0]);
-    std::atomic_thread_fence(std::memory_order_release);      // (launches on other threads copy m->fit without the lock: sizes before the pointer)
-    m->fit.lds_image = m->fit_image.p;
-    return BF_OK;
-}
-
-// First use of the resident fit launch on a batch: its stream (highest priority), events, doorbells, the warm-up launch and the
-// self-test that the fit stream really runs beside the batch stream (b->door_usable).
-static int ensure_fit_stream(bf_batch *b, const FrameIO &io, const HyperDev &hd) {
-    if (b->fit_stream) return BF_OK;
-    bf_model *m = b->m;
-    // the fit stream gets the highest priority: the runtime keeps a pool of hardware queues per priority, so it does not end
-    // up on the queue of this (or another) batch's ordinary stream - where the dense kernels would queue up BEHIND the
-    // resident launch that is waiting for them
-    int least = 0, greatest = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIP_TRY(hipStreamCreateWithPriority(&b->fit_stream, hipStreamNonBlocking, greatest));
-    HIP_TRY(hipEventCreateWithFlags(&b->ev_door[0], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&b->ev_door[1], hipEventDisableTiming));
-    HIP_TRY(b->door.alloc(BF_DOOR_INTS));
-    HIP_TRY(hipHostMalloc((void **)&b->h_door_err, sizeof(int)));
-    HIP_TRY(hipHostMalloc((void **)&b->h_resident, sizeof(int)));
-    *b->h_door_err = 0;
-    // first use of the new stream: its queue, the kernel's code object and scratch come up now, not under a mesh pass that is
-    // already waiting for this launch (mode 2 = prologue only)
-    FrameIO iow = io;
-    iow.ext = b->ext.p; iow.image_out = nullptr; iow.n_frames = 1;
-    HIP_TRY(bf_fit_launch(&m->fit, &iow, &hd, 1, 2, b->adam_tab.p, 0, b->fit_smem, b->fit_stream, nullptr));
-    HIP_TRY(hipStreamSynchronize(b->fit_stream));
-    // ... and checked: do the two streams really run side by side? (bf_door_probe_kernel)
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(bf_memset_sync(b->door.p, 0, BF_DOOR_STATE * sizeof(int)));
-    hipLaunchKernelGGL(bf_door_probe_kernel, dim3(1), dim3(64), 0, b->fit_stream, b->door.p);
-    hipLaunchKernelGGL(bf_door_ring_kernel, dim3(1), dim3(64), 0, b->stream, b->door.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(b->fit_stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    int verdict = 0;
-    HIP_TRY(hipMemcpy(&verdict, b->door.p + BF_DOOR_TICKET, sizeof(int), hipMemcpyDeviceToHost));
-    b->door_usable = verdict == 1;
-    // the same question for the pair (batch stream, second stream): config 5's keypoint workgroups run on the second stream and are
-    // joined by a doorbell that bf_pc_grad_kernel's workgroups wait on (BF_DOOR_KP) - only if that stream's kernels run beside them
-    b->kp_door_ok = false;
-    const char *kj = getenv("BF_KP_JOIN");
-    if (b->door_usable && b->copy_stream && !(kj && kj[0] == 'e')) {
-        HIP_TRY(hipStreamSynchronize(b->copy_stream));
-        HIP_TRY(bf_memset_sync(b->door.p, 0, BF_DOOR_STATE * sizeof(int)));
-        hipLaunchKernelGGL(bf_door_probe_kernel, dim3(1), dim3(64), 0, b->stream, b->door.p);
-        hipLaunchKernelGGL(bf_door_ring_kernel, dim3(1), dim3(64), 0, b->copy_stream, b->door.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        HIP_TRY(hipStreamSynchronize(b->copy_stream));
-        int v2 = 0;
-        HIP_TRY(hipMemcpy(&v2, b->door.p + BF_DOOR_TICKET, sizeof(int), hipMemcpyDeviceToHost));
-        b->kp_door_ok = v2 == 1;
-    }
-    if (!b->door_usable) {
-        // said once per process: the dense loops still give the same results, about three times slower (one fit launch per iteration)
-        static std::atomic<bool> told{false};
-        if (!told.exchange(true))
-            std::fprintf(stderr, "libbodyfit: the resident fit launch is off - its stream shares a hardware queue with the batch stream (self-test "
-                                 "verdict %d).  The dense loops (use_mask / use_mesh / SMPL-X) fall back to one fit launch per iteration: same "
-                                 "results, ~3x slower.  HIP multiplexes a process's streams over the hardware queues GPU_MAX_HW_QUEUES allows; "
-                                 "fewer streams elsewhere in the process leave more of them to the batch.\n", verdict);
-    }
-    return BF_OK;
-}
-
-// what every dense pass of a call reads besides the batch's own buffers: the scans' weights, the silhouette's image size and distance form
-static int dense_prepare(bf_batch *b, const bf_hyper &h) {
-    const int F = b->F;
-    if (!b->scans.empty()) {
-        // 5 * imsize / scan_height (smplify.py:206,210) of the scans attached NOW and of THIS call's imsize: F floats, staged in
-        // pinned memory and copied on the batch's stream (a reused batch gets new scans on every SMPLify.__call__)
-        if (b->pc_weight.n != (size_t)F) {
-            if (b->pc_weight.p) { HIP_TRY(hipStreamSynchronize(b->stream)); (void)hipFree(b->pc_weight.p); b->pc_weight.p = nullptr; }
-            HIP_TRY(b->pc_weight.alloc(F));
-        }
-        if (!b->h_pc_weight) HIP_TRY(hipHostMalloc((void **)&b->h_pc_weight, (size_t)F * sizeof(float)));
-        else HIP_TRY(hipStreamSynchronize(b->stream));      // (an earlier call's copy may still be reading the staging buffer)
-        for (int f = 0; f < F; ++f) b->h_pc_weight[f] = 5.0f * h.imsize / b->scans[f]->dev.height;
-        HIP_TRY(hipMemcpyAsync(b->pc_weight.p, b->h_pc_weight, (size_t)F * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    }
-    if (b->has_masks) { b->mask.imsize = h.imsize; b->mask.cdist = h.mask_cdist_form != 0.f; }
-    return bf_ensure_dense_buffers(b);
-}
-
-// the sub-models of a fit loop's dense iterations: before (early) and after (late) the silhouette / scan losses switch on
-static void dense_subs(bf_batch *b, const bf_model::Sub *&sub_early, const bf_model::Sub *&sub_late) {
-    bf_model *m = b->m;
-    // (read on every call: a test switches them between two calls of one process)
-    const bool sub_ok = [] { const char *e = std::getenv("BF_DENSE_SUBMODEL"); return !(e && e[0] == '0'); }();
-    // (the sub-model of iteration `it`: before the dense losses switch on only the keypoint loss's vertices matter - with or without scans)
-    sub_late = (sub_ok && m->sub.on && b->scans.empty()) ? &m->sub : nullptr;
-    const bool sub_kp_ok = [] { const char *e = std::getenv("BF_DENSE_SUBMODEL_KP"); return !(e && e[0] == '0'); }();      // (bring-up switch, like BF_DENSE_SUBMODEL)
-    // With silhouettes attached too (round 6; BF_DENSE_SUBMODEL_KP_MASKS=0 keeps rounds 4-5's schedule): the iterations before the
-    // silhouette switches on run on the 899 keypoint vertices instead of the 3,285 sampled-first ones - another summation order of those
-    // mesh passes, nothing else (`test_sub_model_loop_matches_the_full_model_loop`: 2e-5 at the switch).  Round 5 left it out because
-    // the chaotic end state moved from 1.9 % to 3.9 % of the reference's, outside a band that was 3 x the larger of TWO perturbed
-    // reference runs; round 6 measures the reference under ten perturbations (tests/ref_drift.py).
-    const bool sub_kp_masks = [] { const char *e = std::getenv("BF_DENSE_SUBMODEL_KP_MASKS"); return !(e && e[0] == '0'); }();
-    sub_early = (sub_ok && sub_kp_ok && m->sub_kp.on && (!b->has_masks || sub_kp_masks)) ? &m->sub_kp : sub_late;
-}
-
-// the loop of smplify.py:177-213 when a dense loss is present (use_mask, use_mesh, or the SMPL-X keypoints
-// with hands + face): iterations that need no dense loss run as one persistent launch; every other iteration
-// is state -> mesh -> losses -> reverse mesh pass -> one fit-kernel iteration (smplify.py:197-210).
-int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDev &hd, FrameIO io) {
-    bf_model *m = b->m;
-    // iterations of THIS call that run before the dense losses switch on: local index it <= thr
-    const int F = b->F, thr = h.dense_after < 0.f ? n_iters / 3 : (int)h.dense_after - b->steps_done;
-    const int n_plain = m->kp_dense ? 0 : std::max(0, std::min(n_iters, thr + 1));
-    int rc = dense_prepare(b, h);
-    if (rc) return rc;
-    if (n_plain > 0)
-        HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, n_plain, 0, b->adam_tab.p, b->steps_done, b->fit_smem, b->stream, nullptr));
-    if (n_plain < n_iters) { rc = bf_ensure_fit_image(b, io, hd); if (rc) return rc; }
-    // The dense iterations with the fit kernel RESIDENT (one launch on a second stream, paced by doorbells, BfDoor) when the
-    // forward pass is a kernel that knows how to wait (1..15 frames); BF_DENSE_PERSISTENT=0, or a larger batch, keeps one fit launch
-    // per iteration, with the pose state from bf_pose_state_kernel every time.
-    const bf_model::Sub *sub_early = nullptr, *sub_late = nullptr;
-    dense_subs(b, sub_early, sub_late);
-    auto sub_of = [&](int it) { return it > thr ? sub_late : sub_early; };
-    const bool door_ok = [] { const char *e = std::getenv("BF_DENSE_PERSISTENT"); return !(e && e[0] == '0'); }();
-    const int n_dense = n_iters - n_plain;
-    if (door_ok && n_dense >= 1 && F < BF_MFMA_MIN_FRAMES) { rc = ensure_fit_stream(b, io, hd); if (rc) return rc; }
-    if (n_dense >= 1) b->dense_resident = (door_ok && F < BF_MFMA_MIN_FRAMES && b->door_usable) ? 1 : 0;
-    if (door_ok && n_dense >= 1 && F < BF_MFMA_MIN_FRAMES && b->door_usable) {
-        *(volatile int *)b->h_resident = 0;
-        HIP_TRY(hipMemsetAsync(b->door.p, 0, BF_DOOR_INTS * sizeof(int), b->stream));
-        b->kp_tickets = 0;
-        HIP_TRY(hipEventRecord(b->ev_door[0], b->stream));              // parameters / Adam state / doorbells as the loop finds them
-        HIP_TRY(hipStreamWaitEvent(b->fit_stream, b->ev_door[0], 0));
-        FrameIO io2 = io;
-        io2.ext = b->ext.p; io2.door = b->door.p; io2.door_resident = b->h_resident;
-        HIP_TRY(bf_fit_launch(&m->fit, &io2, &hd, n_dense, 0, b->adam_tab.p, b->steps_done + n_plain, b->fit_smem, b->fit_stream, nullptr));
-        HIP_TRY(hipEventRecord(b->ev_door[1], b->fit_stream));
-        for (int it = n_plain; it < n_iters; ++it) {
-            if (it == n_plain) {
-                // the mesh passes WAIT for the fit launch: every one of its workgroups must be running before such a
-                // pass can fill the machine
-                const auto t0 = std::chrono::steady_clock::now();
-                while (*(volatile int *)b->h_resident < F) {
-                    if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) {
-                        const int one = 1;      // let everybody through, then fail the call
-                        (void)hipMemcpy(b->door.p + BF_DOOR_ERR, &one, sizeof one, hipMemcpyHostToDevice);
-                        (void)hipStreamSynchronize(b->fit_stream);
-                        return fail(BF_ERR_HIP, "dense schedule: the persistent fit launch did not start");
-                    }
-                }
-            }
-            rc = dense_pass(b, h, hd, it > thr, 5.0f, b->door.p, it - n_plain + 1, sub_of(it), b->dense_timing && it == n_iters - 1);
-            if (rc) {               // do not leave the resident launch waiting for bells that will not ring
-                const int one = 1;
-                (void)hipMemcpy(b->door.p + BF_DOOR_ERR, &one, sizeof one, hipMemcpyHostToDevice);
-                (void)hipStreamSynchronize(b->fit_stream);
-                return rc;
-            }
-        }
-        HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_door[1], 0));       // the last iteration's step, terms and state
-        HIP_TRY(hipMemcpyAsync(b->h_door_err, b->door.p + BF_DOOR_ERR, sizeof(int), hipMemcpyDeviceToHost, b->stream));
-        return BF_OK;
-    }
-    for (int it = n_plain; it < n_iters; ++it) {
-        rc = dense_pass(b, h, hd, it > thr, 5.0f, nullptr, 0, sub_of(it), b->dense_timing && it == n_iters - 1);                    // smplify.py:210
-        if (rc) return rc;
-        FrameIO io2 = io;
-        io2.ext = b->ext.p;
-        HIP_TRY(bf_fit_launch(&m->fit, &io2, &hd, 1, 0, b->adam_tab.p, b->steps_done + it, b->fit_smem, b->stream, nullptr));
-    }
-    return BF_OK;
-}
-
-int bf_batch_dense_resident(const bf_batch *b) { return b ? b->dense_resident : -1; }
-
-int bf_batch_dense_timing(bf_batch *b, int enable, float ms[6]) {
-    if (!b) return fail(BF_ERR_INVALID, "bf_batch_dense_timing: null batch");
-    HIP_TRY(hipSetDevice(b->m->device));
-    if (ms) {
-        if (!b->dense_timed) return fail(BF_ERR_INVALID, "bf_batch_dense_timing: no dense iteration has been timed (enable, then bf_fit with a dense loss)");
-        BF_TRY(bf_sync_all(b));
-        for (int k = 0; k < 6; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], b->ev_dense[k], b->ev_dense[k + 1]));
-    }
-    b->dense_timing = enable != 0;
-    return BF_OK;
-}
-
-// bf_loss_grad for models whose keypoint loss is dense (SMPL-X): one evaluation, no update
-int bf_dense_loss_grad(bf_batch *b, const bf_hyper &h, const HyperDev &hd, FrameIO io) {
-    int rc = bf_ensure_dense_buffers(b);
-    if (rc) return rc;
-    rc = dense_pass(b, h, hd, false, 5.0f);
-    if (rc) return rc;
-    io.ext = b->ext.p;
-    HIP_TRY(bf_fit_launch(&b->m->fit, &io, &hd, 1, 1, b->adam_tab.p, 0, b->fit_smem, b->stream, nullptr));
-    return BF_OK;
-}
-
-// bf_dense_iter_grad: what one dense iteration of bf_fit_with_scans hands to Adam, evaluated without the update (launch-per-iteration
-// route, no doorbells).  terms6[6] per frame on the host, or null.
-int bf_dense_iter_eval(bf_batch *b, const bf_hyper &h, const HyperDev &hd, FrameIO io, bool late, bool use_sub, const float *dverts_extra,
-                       float *terms6) {
-    bf_model *m = b->m;
-    const int F = b->F;
-    int rc = dense_prepare(b, h);
-    if (rc) return rc;
-    const bool scans = late && !b->scans.empty(), masks = late && b->has_masks;
-    const bf_model::Sub *sub = nullptr;
-    if (use_sub) {
-        const bf_model::Sub *sub_early = nullptr, *sub_late = nullptr;
-        dense_subs(b, sub_early, sub_late);
-        sub = late ? sub_late : sub_early;
-    }
-    DevBuf<float> extra;
-    if (dverts_extra) HIP_TRY(extra.upload(std::vector<float>(dverts_extra, dverts_extra + (size_t)F * m->nv * 3)));
-    // the closest-point search warm-starts from the faces of the call before it: this call keeps them as it found them
-    DevBuf<int> faces_kept;
-    const bool warm = b->cface_valid;
-    if (scans && warm) {
-        HIP_TRY(faces_kept.alloc(b->cface.n));
-        HIP_TRY(hipMemcpyAsync(faces_kept.p, b->cface.p, b->cface.n * sizeof(int), hipMemcpyDeviceToDevice, b->stream));
-    }
-    rc = dense_pass(b, h, hd, late, 5.0f, nullptr, 0, sub, false, true, extra.p);
-    if (rc) return rc;
-    if (scans) {
-        if (warm) HIP_TRY(hipMemcpyAsync(b->cface.p, faces_kept.p, b->cface.n * sizeof(int), hipMemcpyDeviceToDevice, b->stream));
-        b->cface_valid = warm;
-    }
-    io.ext = b->ext.p;
-    HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, 1, 1, b->adam_tab.p, 0, b->fit_smem, b->stream, nullptr));
-    BF_TRY(bf_sync_all(b));
-    if (terms6) {
-        std::vector<float> t4((size_t)F * 4), mk(F, 0.f), pc(F, 0.f);
-        HIP_TRY(hipMemcpy(t4.data(), b->terms.p, t4.size() * sizeof(float), hipMemcpyDeviceToHost));
-        if (masks) HIP_TRY(hipMemcpy(mk.data(), b->mk_loss.p, (size_t)F * sizeof(float), hipMemcpyDeviceToHost));
-        if (scans) HIP_TRY(hipMemcpy(pc.data(), b->pc_loss.p, (size_t)F * sizeof(float), hipMemcpyDeviceToHost));
-        for (int f = 0; f < F; ++f) {
-            std::copy(t4.begin() + (size_t)f * 4, t4.begin() + (size_t)f * 4 + 4, terms6 + (size_t)f * 6);
-            terms6[(size_t)f * 6 + 4] = 5.0f * mk[f];
-            terms6[(size_t)f * 6 + 5] = pc[f];          // (bf_pc_grad_kernel leaves weight * norm)
-        }
-    }
-    return BF_OK;
-}
-
-// generic forward from packed parameters (bf_model_forward)
-int bf_model_forward(bf_model *m, int n, const float *params, float *vertices, float *joints) {
-    if (!m || n <= 0 || !params) return fail(BF_ERR_INVALID, "bf_model_forward: bad argument");
-    HIP_TRY(hipSetDevice(m->device));
-    DevBuf<float> d_p, d_state, d_vraw, d_j, d_xp;
-    MeshScratch scratch;
-    HIP_TRY(d_p.upload(std::vector<float>(params, params + (size_t)n * m->np)));
-    HIP_TRY(d_state.alloc((size_t)n * bf_state_stride(m->nj, m->npf, m->nb)));
-    HIP_TRY(d_vraw.alloc((size_t)n * m->nv * 3));
-    HIP_TRY(d_j.alloc((size_t)n * m->n_joint_map * 3));
-    HIP_TRY(d_xp.alloc((size_t)n * m->mesh.n_tiles * std::max(m->n_extra, 1) * 3));
-    std::vector<float> zero((size_t)n * m->np, 0.f);
-    // model space: similarity parameters are ignored (transl 0, scale 1, constant scale 1)
-    std::vector<float> pk(params, params + (size_t)n * m->np);
-    for (int i = 0; i < n; ++i) { float *q = pk.data() + (size_t)i * m->np; q[0] = q[1] = q[2] = 0.f; q[3] = 1.f; }
-    HIP_TRY(hipMemcpy(d_p.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(bf_pose_state_kernel, dim3(n), dim3(128), 0, 0, m->fit, (const float *)nullptr, (const float *)nullptr,
-                       (const float *)nullptr, (const float *)nullptr, d_state.p, (const float *)d_p.p, (const float *)nullptr, 1.0f);
-    HIP_TRY(hipGetLastError());
-    int rc = bf_launch_mesh(m, &scratch, n, d_state.p, d_vraw.p, nullptr, d_xp.p, d_j.p, nullptr, 0, nullptr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    if (vertices) HIP_TRY(hipMemcpy(vertices, d_vraw.p, d_vraw.n * sizeof(float), hipMemcpyDeviceToHost));
-    if (joints) HIP_TRY(hipMemcpy(joints, d_j.p, d_j.n * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
-}
-
-// use_mask=True (smplify.py:138-144): masks[F,M,H,W] uint8 as read from disk (thresholded > 128 here),
-// view_index[M] = position of each mask view among the V views (use_frames.index(frame), smplify.py:141-142),
-// contours: for every (frame, mask view) contour_count points (x, y), concatenated in contour_xy
-// (extract_countours, loss.py:73-83 - the caller extracts them; the loss only sums over the points).
-// Contours of n binary masks on the device (bf_contour_kernel).  d_bin[n][H][W] -> counts (host), d_xy[n][2][cap][2] (device slab;
-// half[i] says which half holds mask i's contour).
-// The slab is grown and the kernel re-run when a contour is longer than the first guess.
-static int contours_on_device(const unsigned char *d_bin, int n, int H, int W, int select, std::vector<int> &counts, std::vector<int> &half,
-                              DevBuf<float> &d_xy, int &cap) {
-    const int wpr = (W + 31) / 32;
-    const size_t plane_bytes = (size_t)3 * H * wpr * sizeof(unsigned);
-    const bool in_lds = plane_bytes <= 150 * 1024;
-    DevBuf<unsigned> planes;
-    DevBuf<int> d_cnt;
-    if (!in_lds) HIP_TRY(planes.alloc((size_t)n * 3 * H * wpr));
-    HIP_TRY(d_cnt.alloc(2 * (size_t)n));
-    if (in_lds && plane_bytes > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)bf_contour_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plane_bytes));
-    counts.assign(n, 0);
-    cap = std::max(64, 4 * (H + W));
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (d_xy.p) { (void)hipFree(d_xy.p); d_xy.p = nullptr; }
-        HIP_TRY(d_xy.alloc((size_t)n * 2 * cap * 2));
-        hipLaunchKernelGGL(bf_contour_kernel, dim3(n), dim3(256), in_lds ? plane_bytes : 0, 0, d_bin, H, W, cap, select, d_xy.p, d_cnt.p,
-                           in_lds ? (unsigned *)nullptr : planes.p);
-        HIP_TRY(hipGetLastError());
-        std::vector<int> both(2 * (size_t)n);
-        HIP_TRY(hipMemcpy(both.data(), d_cnt.p, both.size() * sizeof(int), hipMemcpyDeviceToHost));
-        counts.assign(both.begin(), both.begin() + n);
-        half.assign(both.begin() + n, both.end());
-        const int longest = *std::max_element(counts.begin(), counts.end());
-        if (longest <= cap) return BF_OK;
-        cap = longest;
-    }
-    return fail(BF_ERR_HIP, "contour extraction: inconsistent contour length");
-}
-
-// extract_countours (smplify/loss.py:73-83): masks[n][H][W] uint8, non-zero = foreground (the reference passes
-// (mask > 128) * 255) -> counts[n] and, when xy != NULL, the contours' (x, y) points concatenated (sum(counts) pairs,
-// which the caller learns from a first call with xy == NULL).
-int bf_extract_contours(int device, int n, int H, int W, const uint8_t *masks, int32_t *counts, float *xy, int select) {
-    if (n <= 0 || H <= 0 || W <= 0 || !masks || !counts || select < 0 || select > 2) return fail(BF_ERR_INVALID, "bf_extract_contours: bad argument");
-    if (bf_device_count() <= device || device < 0) return fail(BF_ERR_NO_DEVICE, "bf_extract_contours: no such HIP device");
-    HIP_TRY(hipSetDevice(device));
-    DevBuf<unsigned char> d_bin;
-    HIP_TRY(d_bin.upload(std::vector<unsigned char>(masks, masks + (size_t)n * H * W)));
-    std::vector<int> cnt, half;
-    DevBuf<float> d_xy;
-    int cap = 0;
-    int rc = contours_on_device(d_bin.p, n, H, W, select, cnt, half, d_xy, cap);
-    if (rc) return rc;
-    size_t o = 0;
-    for (int i = 0; i < n; ++i) {
-        counts[i] = cnt[i];
-        if (xy && cnt[i] > 0) HIP_TRY(hipMemcpy(xy + o * 2, d_xy.p + ((size_t)i * 2 + half[i]) * cap * 2, (size_t)cnt[i] * 2 * sizeof(float), hipMemcpyDeviceToHost));
-        o += cnt[i];
-    }
-    return BF_OK;
-}
-
-int bf_batch_set_masks(bf_batch *b, int n_masks, const int32_t *view_index, int H, int W, const uint8_t *masks,
-                       const int32_t *contour_count, const float *contour_xy, int contour_select) {
-    if (!b || contour_select < 0 || contour_select > 2) return fail(BF_ERR_INVALID, "bf_batch_set_masks: null batch / bad contour_select");
-    HIP_TRY(hipSetDevice(b->m->device));
-    if (n_masks > 0 && masks) {
-        if (!view_index || (contour_count && !contour_xy) || H <= 0 || W <= 0) return fail(BF_ERR_INVALID, "bf_batch_set_masks: bad argument");
-        for (int i = 0; i < n_masks; ++i)
-            if (view_index[i] < 0 || view_index[i] >= b->V) return fail(BF_ERR_INVALID, "bf_batch_set_masks: view index out of range");
-        // The host's share - binarising 2 MB per frame (smplify.py:139) into the pinned staging buffer - happens BEFORE the wait for the
-        // work in flight: in a frame loop that is the previous frame's fit, and the buffer is free (its last upload, ev_masks, went out
-        // early in that fit).
-        const size_t npix0 = (size_t)b->F * n_masks * H * W;
-        if (b->ev_masks) HIP_TRY(hipEventSynchronize(b->ev_masks));
-        if (b->h_masks_n < npix0) {
-            if (b->h_masks) (void)hipHostFree(b->h_masks);
-            b->h_masks = nullptr;
-            HIP_TRY(hipHostMalloc((void **)&b->h_masks, npix0));
-            b->h_masks_n = npix0;
-        }
-        for (size_t i = 0; i < npix0; ++i) b->h_masks[i] = masks[i] > 128;
-    }
-    BF_TRY(bf_sync_all(b));
-    if (n_masks <= 0 || !masks) { b->has_masks = false; b->masks_pending = false; return BF_OK; }   // (bf_sync_all above drained a deferred extraction)
-    const int F = b->F, nv = b->m->nv;
-    // (a frame loop hands over new masks of the same shape every frame: device buffers are kept and only grown - a dozen hipFree /
-    //  hipMalloc pairs cost more than the contour extraction itself)
-    auto ensure = [](auto &buf, size_t count) -> hipError_t {
-        if (buf.p && buf.n >= count && !buf.view) return hipSuccess;
-        if (buf.p && !buf.view) (void)hipFree((void *)buf.p);
-        buf.p = nullptr;
-        return buf.alloc(count);
-    };
-    const size_t npix = (size_t)F * n_masks * H * W, fm = (size_t)F * n_masks;
-    const int ns = (nv + 3) / 4, pblocks = (ns + 255) / 256;
-    // (binarised into pinned staging above, before the wait)
-    HIP_TRY(ensure(b->mk_masks, npix));
-    HIP_TRY(ensure(b->mk_view, n_masks)); HIP_TRY(ensure(b->mk_cstart, fm)); HIP_TRY(ensure(b->mk_ccount, fm));
-    HIP_TRY(hipMemcpy(b->mk_view.p, view_index, (size_t)n_masks * sizeof(int), hipMemcpyHostToDevice));
-    b->mk_view_host.assign(view_index, view_index + n_masks);
-    b->mk_stage.staged = false;                              // (masks set synchronously supersede staged ones)
-    HIP_TRY(ensure(b->mk_uvi, fm * ns * 4)); HIP_TRY(ensure(b->mk_duvb, fm * ns * 2)); HIP_TRY(ensure(b->mk_gpart, fm * ns * 3)); HIP_TRY(ensure(b->mk_acc, fm * ns * 2));
-    HIP_TRY(ensure(b->mk_loss, F));
-    MaskIO &K0 = b->mask;
-    K0.nv = nv; K0.ns = ns; K0.n_views = b->V; K0.n_masks = n_masks; K0.H = H; K0.W = W; K0.proj_blocks = pblocks;
-    K0.cdist = 1; K0.sstride = 4; K0.imsize = 512.f; K0.eps = 10.f; K0.weight = 5.f;
-    K0.view_index = b->mk_view.p; K0.masks = b->mk_masks.p;
-    b->masks_pending = false;
-    b->mk_on_device = !contour_count;
-    if (!contour_count) {
-        // DEFERRED: upload + border following on the second stream; lengths into pinned memory; bf_masks_finalize does the rest
-        if (!b->ev_masks) HIP_TRY(hipEventCreateWithFlags(&b->ev_masks, hipEventDisableTiming));
-        if (b->h_ccount_n < 2 * fm) {
-            if (b->h_ccount) (void)hipHostFree(b->h_ccount);
-            b->h_ccount = nullptr;
-            HIP_TRY(hipHostMalloc((void **)&b->h_ccount, 2 * fm * sizeof(int)));
-            b->h_ccount_n = 2 * fm;
-        }
-        const int wpr = (W + 31) / 32;
-        const size_t plane_bytes = (size_t)3 * H * wpr * sizeof(unsigned);
-        const bool in_lds = plane_bytes <= 150 * 1024;
-        if (!in_lds) HIP_TRY(ensure(b->mk_planes, fm * 3 * H * wpr));
-        if (in_lds && plane_bytes > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void *)bf_contour_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plane_bytes));
-        b->mk_cap = std::max(b->mk_cap, std::max(64, 4 * (H + W)));
-        b->mk_select = contour_select;
-        HIP_TRY(ensure(b->mk_slab, fm * 2 * (size_t)b->mk_cap * 2));
-        HIP_TRY(ensure(b->mk_cnt2, 2 * fm));
-        for (float *q : b->mk_retired) (void)hipFree(q);          // (buffers a finalize inside a fit could not free: see there)
-        b->mk_retired.clear();
-        // everything bf_masks_finalize fills is sized NOW, for borders as long as the slab holds: it runs in the middle of a fit, with
-        // the resident fit launch waiting for kernels that are not enqueued yet - a hipFree there (it waits for the device) would
-        // never return
-        {
-            const size_t cap = (size_t)b->mk_cap;
-            HIP_TRY(ensure(b->mk_cxy, fm * cap * 2)); HIP_TRY(ensure(b->mk_choice, fm * cap)); HIP_TRY(ensure(b->mk_cgrad, fm * cap * 2));
-            HIP_TRY(ensure(b->mk_part, fm * (pblocks + (cap * 16 + 255) / 256)));
-        }
-        hipStream_t cs = b->copy_stream;
-        HIP_TRY(hipMemcpyAsync(b->mk_masks.p, b->h_masks, npix, hipMemcpyHostToDevice, cs));
-        hipLaunchKernelGGL(bf_contour_kernel, dim3((unsigned)fm), dim3(256), in_lds ? plane_bytes : 0, cs, (const unsigned char *)b->mk_masks.p, H, W,
-                           b->mk_cap, contour_select, b->mk_slab.p, b->mk_cnt2.p, in_lds ? (unsigned *)nullptr : b->mk_planes.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(b->h_ccount, b->mk_cnt2.p, 2 * fm * sizeof(int), hipMemcpyDeviceToHost, cs));
-        HIP_TRY(hipEventRecord(b->ev_masks, cs));
-        b->masks_pending = true;
-        b->has_masks = true;
-        K0.cmax = 1; K0.part_stride = pblocks + 1;         // (placeholders until finalize; nothing reads them before)
-        return bf_ensure_dense_buffers(b);
-    }
-    HIP_TRY(hipMemcpy(b->mk_masks.p, b->h_masks, npix, hipMemcpyHostToDevice));
-    std::vector<int> start(fm), count(contour_count, contour_count + fm);
-    int total = 0, cmax = 1;
-    for (size_t i = 0; i < fm; ++i) {
-        if (count[i] < 0) return fail(BF_ERR_INVALID, "bf_batch_set_masks: negative contour count");
-        start[i] = total; total += count[i]; cmax = std::max(cmax, count[i]);
-    }
-    const int stride = pblocks + (cmax * 16 + 255) / 256;     // (16 lanes per contour point)
-    HIP_TRY(hipMemcpy(b->mk_cstart.p, start.data(), fm * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->mk_ccount.p, count.data(), fm * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(ensure(b->mk_cxy, (size_t)std::max(total, 1) * 2));
-    if (total > 0) HIP_TRY(hipMemcpy(b->mk_cxy.p, contour_xy, (size_t)total * 2 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(ensure(b->mk_choice, fm * cmax)); HIP_TRY(ensure(b->mk_cgrad, fm * cmax * 2));
-    HIP_TRY(ensure(b->mk_part, fm * stride));
-    MaskIO &K = b->mask;
-    K.cmax = cmax; K.part_stride = stride;
-    K.contour_start = b->mk_cstart.p; K.contour_count = b->mk_ccount.p; K.contour_xy = b->mk_cxy.p;
-    b->has_masks = true;
-    return bf_ensure_dense_buffers(b);
-}
-
-/* The NEXT frame's silhouettes, WITHOUT draining the work in flight (the frame loop of apps/genebody_fitting.py:183-192 hands SMPLify
- * new masks with every frame): same views and shape as the masks attached with bf_batch_set_masks (contours extracted on the device).
- * They are binarised into a second pinned buffer, uploaded and border-followed into a second arena on the batch's second stream - under
- * the fit in flight - and the next bf_fit switches to that arena (bf_masks_commit).  Two-deep like bf_batch_stage_inputs: staging waits
- * for the fit that last read the arena it overwrites. */
-int bf_batch_stage_masks(bf_batch *b, int n_masks, const int32_t *view_index, int H, int W, const uint8_t *masks, int contour_select) {
-    if (!b || !view_index || !masks || contour_select < 0 || contour_select > 2) return fail(BF_ERR_INVALID, "bf_batch_stage_masks: bad argument");
-    const MaskIO &K = b->mask;
-    if (!b->has_masks || !b->mk_on_device || K.n_masks != n_masks || K.H != H || K.W != W || (int)b->mk_view_host.size() != n_masks ||
-        !std::equal(view_index, view_index + n_masks, b->mk_view_host.begin()))
-        return fail(BF_ERR_INVALID, "bf_batch_stage_masks: the first frame's masks go through bf_batch_set_masks (device contours); later frames must "
-                                    "keep its views and shape");
-    HIP_TRY(hipSetDevice(b->m->device));
-    bf_batch::MaskStage &S = b->mk_stage;
-    const size_t fm = (size_t)b->F * n_masks, npix = fm * H * W;
-    if (S.ev_used) HIP_TRY(hipEventSynchronize(S.ev_used));          // the fit that read this arena two frames ago
-    if (S.ev) HIP_TRY(hipEventSynchronize(S.ev));
-    if (S.h_masks_n < npix) {
-        if (S.h_masks) (void)hipHostFree(S.h_masks);
-        S.h_masks = nullptr;
-        HIP_TRY(hipHostMalloc((void **)&S.h_masks, npix));
-        S.h_masks_n = npix;
-    }
-    for (size_t i = 0; i < npix; ++i) S.h_masks[i] = masks[i] > 128;
-    if (S.h_ccount_n < 2 * fm) {
-        if (S.h_ccount) (void)hipHostFree(S.h_ccount);
-        S.h_ccount = nullptr;
-        HIP_TRY(hipHostMalloc((void **)&S.h_ccount, 2 * fm * sizeof(int)));
-        S.h_ccount_n = 2 * fm;
-    }
-    const int wpr = (W + 31) / 32;
-    const size_t plane_bytes = (size_t)3 * H * wpr * sizeof(unsigned);
-    const bool in_lds = plane_bytes <= 150 * 1024;
-    // (first use, or the active arena's slab has grown since: fresh blocks - nothing is freed while a fit may be running)
-    auto fresh = [&](auto &buf, size_t count) -> hipError_t {
-        if (buf.p && buf.n >= count) return hipSuccess;
-        if (buf.p) b->mk_retired.push_back((float *)(void *)buf.p);
-        buf.p = nullptr;
-        return buf.alloc(count);
-    };
-    HIP_TRY(fresh(S.masks, npix));
-    HIP_TRY(fresh(S.slab, fm * 2 * (size_t)b->mk_cap * 2));
-    HIP_TRY(fresh(S.cnt2, 2 * fm));
-    if (!in_lds) HIP_TRY(fresh(S.planes, fm * 3 * H * wpr));
-    if (!S.ev) HIP_TRY(hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-    S.select = contour_select;
-    hipStream_t cs = b->copy_stream;
-    HIP_TRY(hipMemcpyAsync(S.masks.p, S.h_masks, npix, hipMemcpyHostToDevice, cs));
-    hipLaunchKernelGGL(bf_contour_kernel, dim3((unsigned)fm), dim3(256), in_lds ? plane_bytes : 0, cs, (const unsigned char *)S.masks.p, H, W,
-                       b->mk_cap, contour_select, S.slab.p, S.cnt2.p, in_lds ? (unsigned *)nullptr : S.planes.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(S.h_ccount, S.cnt2.p, 2 * fm * sizeof(int), hipMemcpyDeviceToHost, cs));
-    HIP_TRY(hipEventRecord(S.ev, cs));
-    S.staged = true;
-    return BF_OK;
-}
-
-// bf_fit's first act when masks were staged: the two arenas change places (pointers only; the kernels of the fit still in flight
-// hold the old ones by value) and the contours are pending again (bf_masks_finalize).
-void bf_masks_commit(bf_batch *b) {
-    bf_batch::MaskStage &S = b->mk_stage;
-    if (!S.staged) return;
-    S.staged = false;
-    auto swap_buf = [](auto &x, auto &y) { std::swap(x.p, y.p); std::swap(x.n, y.n); };
-    std::swap(b->h_masks, S.h_masks); std::swap(b->h_masks_n, S.h_masks_n);
-    std::swap(b->h_ccount, S.h_ccount); std::swap(b->h_ccount_n, S.h_ccount_n);
-    std::swap(b->ev_masks, S.ev); std::swap(b->ev_masks_used, S.ev_used);
-    swap_buf(b->mk_masks, S.masks); swap_buf(b->mk_slab, S.slab); swap_buf(b->mk_cnt2, S.cnt2); swap_buf(b->mk_planes, S.planes);
-    std::swap(b->mk_select, S.select);
-    b->mask.masks = b->mk_masks.p;
-    b->mask.cmax = 1; b->mask.part_stride = b->mask.proj_blocks + 1;      // (placeholders until finalize, as after bf_batch_set_masks)
-    b->masks_pending = true;
-}
-
-// The second half of a deferred bf_batch_set_masks: wait (host) for the border following on the second stream, then size and fill
-// what depends on the contour lengths.  Everything queued here goes onto the BATCH stream, in front of the kernels that read it.
-int bf_masks_finalize(bf_batch *b) {
-    if (!b->masks_pending) return BF_OK;
-    b->masks_pending = false;
-    HIP_TRY(hipEventSynchronize(b->ev_masks));
-    MaskIO &K = b->mask;
-    const size_t fm = (size_t)b->F * K.n_masks;
-    int longest = 0;
-    for (size_t i = 0; i < fm; ++i) longest = std::max(longest, b->h_ccount[i]);
-    if (longest > b->mk_cap) {
-        // A border longer than the slab (more than 4 (H + W) points; the kernel counted it without storing): follow again with room
-        // for it.  This may be the middle of a fit whose resident launch waits for kernels that are not enqueued yet, so nothing is
-        // FREED here (hipFree waits for the device): the outgrown buffers are retired and freed by the next bf_batch_set_masks.
-        auto regrow = [&](auto &buf, size_t count) -> hipError_t {
-            if (buf.p && !buf.view) b->mk_retired.push_back((float *)(void *)buf.p);
-            buf.p = nullptr;
-            return buf.alloc(count);
-        };
-        b->mk_cap = longest;
-        const size_t cap = (size_t)longest;
-        HIP_TRY(regrow(b->mk_slab, fm * 2 * cap * 2));
-        HIP_TRY(regrow(b->mk_cxy, fm * cap * 2)); HIP_TRY(regrow(b->mk_choice, fm * cap)); HIP_TRY(regrow(b->mk_cgrad, fm * cap * 2));
-        HIP_TRY(regrow(b->mk_part, fm * (K.proj_blocks + (cap * 16 + 255) / 256)));
-        const int wpr = (K.W + 31) / 32;
-        const size_t plane_bytes = (size_t)3 * K.H * wpr * sizeof(unsigned);
-        const bool in_lds = plane_bytes <= 150 * 1024;
-        hipLaunchKernelGGL(bf_contour_kernel, dim3((unsigned)fm), dim3(256), in_lds ? plane_bytes : 0, b->copy_stream, (const unsigned char *)b->mk_masks.p,
-                           K.H, K.W, b->mk_cap, b->mk_select, b->mk_slab.p, b->mk_cnt2.p, in_lds ? (unsigned *)nullptr : b->mk_planes.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(b->h_ccount, b->mk_cnt2.p, 2 * fm * sizeof(int), hipMemcpyDeviceToHost, b->copy_stream));
-        HIP_TRY(hipStreamSynchronize(b->copy_stream));
-    }
-    std::vector<int> start(fm);
-    int total = 0, cmax = 1;
-    for (size_t i = 0; i < fm; ++i) { start[i] = total; total += b->h_ccount[i]; cmax = std::max(cmax, b->h_ccount[i]); }
-    const int stride = K.proj_blocks + (cmax * 16 + 255) / 256;
-    int *h = b->h_ccount;                                     // [0, fm): lengths; [fm, 2 fm): halves -> reused below for the offsets
-    std::vector<int> half(h + fm, h + 2 * fm);
-    for (size_t i = 0; i < fm; ++i) h[fm + i] = start[i];
-    HIP_TRY(hipMemcpyAsync(b->mk_ccount.p, h, fm * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->mk_cstart.p, h + fm, fm * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    for (size_t i = 0; i < fm; ++i)
-        if (h[i] > 0)
-            HIP_TRY(hipMemcpyAsync(b->mk_cxy.p + (size_t)start[i] * 2, b->mk_slab.p + (i * 2 + half[i]) * (size_t)b->mk_cap * 2,
-                                   (size_t)h[i] * 2 * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
-    K.cmax = cmax; K.part_stride = stride;
-    K.contour_start = b->mk_cstart.p; K.contour_count = b->mk_ccount.p; K.contour_xy = b->mk_cxy.p;
-    return BF_OK;
-}
-
-// multview_mask_loss (loss.py:85-130) at the current parameters: loss[F] (unweighted, as the function
-// returns it) and its gradient w.r.t. body_vertices dverts[F,NV,3] (non-zero on every 4th vertex only).
-int bf_batch_mask_loss(bf_batch *b, const bf_hyper *hyper, float *loss, float *dverts) {
-    if (!b || !b->has_masks) return fail(BF_ERR_INVALID, "bf_batch_mask_loss: no masks attached");
-    HIP_TRY(hipSetDevice(b->m->device));
-    BF_TRY(bf_masks_finalize(b));
-    bf_hyper h;
-    if (hyper) h = *hyper; else bf_hyper_default(&h);
-    HyperDev hd = bf_to_dev(h);
-    b->mask.imsize = h.imsize;
-    b->mask.cdist = h.mask_cdist_form != 0.f;
-    int rc = bf_guard_arena(b);
-    if (rc) return rc;
-    rc = launch_state_and_mesh(b, hd);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(b->dvout.p, 0, b->dvout.n * sizeof(float), b->stream));
-    rc = launch_mask_kernels(b, 1.0f, true);
-    if (rc) return rc;
-    BF_TRY(bf_sync_all(b));
-    if (loss) HIP_TRY(hipMemcpy(loss, b->mk_loss.p, (size_t)b->F * sizeof(float), hipMemcpyDeviceToHost));
-    if (dverts) HIP_TRY(hipMemcpy(dverts, b->dvout.p, b->dvout.n * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
-}
-
-int bf_fit_displacement(bf_batch *b, int n_iters, const bf_hyper *hyper) {
-    if (!b || n_iters <= 0) return fail(BF_ERR_INVALID, "bf_fit_displacement: bad argument");
-    bf_model *m = b->m;
-    if (b->scans_lost)
-        return fail(BF_ERR_INVALID, "bf_fit_displacement: a scan this batch held was destroyed (bf_scan_destroy) - call bf_batch_set_scans again");
-    if (b->scans.empty()) return fail(BF_ERR_INVALID, "bf_fit_displacement: no scans attached (bf_batch_set_scans)");
-    if (!b->have_result) return fail(BF_ERR_INVALID, "bf_fit_displacement: run bf_fit first (the stage starts from its vertices)");
-    if (m->faces_host.empty()) return fail(BF_ERR_INVALID, "bf_fit_displacement: the model was created without faces");
-    HIP_TRY(hipSetDevice(m->device));
-    bf_hyper h;
-    if (hyper) h = *hyper; else bf_hyper_default(&h);
-    const int F = b->F, nv = m->nv, nf = (int)m->faces_host.size() / 3;
-    BF_TRY(bf_guard_arena(b));
-    std::unique_lock<std::mutex> lazy(m->lazy);
-    if (!m->faces_d.p) {
-        // vertex -> (face, corner) lists in the order compute_normal_torch adds them: corner by corner, faces ascending
-        std::vector<int> start, adj;
-        bf_build_vertex_adjacency(m->faces_host, nv, start, adj);
-        HIP_TRY(m->adj_start.upload(start));
-        HIP_TRY(m->adj.upload(adj));
-        HIP_TRY(m->faces_d.upload(m->faces_host));        // (blocking uploads; faces_d last: it is the "built" flag)
-    }
-    lazy.unlock();
-    const size_t nv3 = (size_t)F * nv * 3;
-    if (!b->disp.p) {
-        bool ok = b->disp.alloc(nv3) == hipSuccess && b->disp_m.alloc(nv3) == hipSuccess && b->disp_v.alloc(nv3) == hipSuccess &&
-                  b->disp_base.alloc(nv3) == hipSuccess && b->disp_P.alloc(nv3) == hipSuccess && b->disp_dv.alloc(nv3) == hipSuccess &&
-                  b->disp_fn.alloc((size_t)F * nf * 4) == hipSuccess && b->disp_vn.alloc((size_t)F * nv * 4) == hipSuccess &&
-                  b->disp_dPf.alloc((size_t)F * nf * 9) == hipSuccess;
-        if (!ok) return fail(BF_ERR_HIP, "bf_fit_displacement: device allocation failed");
-    }
-    // zeros for disp and its moments; the base is the mesh of the last forward, detached (smplify.py:229-231)
-    HIP_TRY(hipMemsetAsync(b->disp.p, 0, nv3 * sizeof(float), b->stream));
-    HIP_TRY(hipMemsetAsync(b->disp_m.p, 0, nv3 * sizeof(float), b->stream));
-    HIP_TRY(hipMemsetAsync(b->disp_v.p, 0, nv3 * sizeof(float), b->stream));
-    HIP_TRY(hipMemcpyAsync(b->disp_base.p, b->vout.p, nv3 * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
-    const dim3 gv((nv + 255) / 256, F), gf((nf + 255) / 256, F);
-    const int nblk = (nv + 255) / 256;
-    const double b1 = h.adam_beta1, b2 = h.adam_beta2;
-    for (int it = 1; it <= n_iters; ++it) {
-        hipLaunchKernelGGL(bf_disp_face_kernel, gf, dim3(256), 0, b->stream, (const int *)m->faces_d.p, nf, nv,
-                           (const float *)b->disp_base.p, (const float *)b->disp.p, b->disp_fn.p);
-        hipLaunchKernelGGL(bf_disp_vertex_kernel, gv, dim3(256), 0, b->stream, (const int *)m->adj_start.p, (const int *)m->adj.p, nf, nv,
-                           (const float *)b->disp_base.p, (const float *)b->disp.p, (const float *)b->disp_fn.p, b->disp_P.p, b->disp_vn.p);
-        bf_nearest_launch(dim3((nv + 3) / 4, F), b->stream, (const ScanDev *)b->scan_dev.p, (const float *)b->disp_P.p, nv,
-                          b->cface.p, b->cpts.p, (float *)nullptr, b->cface_valid ? 1 : 0);
-        b->cface_valid = true;
-        hipLaunchKernelGGL(bf_disp_vgrad_kernel, gv, dim3(256), 0, b->stream, (const int *)m->faces_d.p, (const int *)m->adj_start.p,
-                           (const int *)m->adj.p, nf, nv, (const float *)b->disp_vn.p, (const float *const *)b->scan_fn.p,
-                           (const int *)b->cface.p, (const float *)b->cscale.p, b->disp_dv.p, (const float *)b->disp_P.p,
-                           (const float *)b->cpts.p, b->pc_partial.p);      // (+ the block sums of |P - C|^2: was bf_pc_partial_kernel)
-        hipLaunchKernelGGL(bf_disp_fgrad_kernel, gf, dim3(256), 0, b->stream, (const int *)m->faces_d.p, nf, nv, (const float *)b->disp_P.p,
-                           (const float *)b->disp_fn.p, (const float *)b->disp_dv.p, b->disp_dPf.p);
-        const float step_size = (float)((double)h.lr_displacement / (1.0 - std::pow(b1, it)));
-        const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, it));
-        hipLaunchKernelGGL(bf_disp_adam_kernel, gv, dim3(256), 0, b->stream, (const int *)m->adj_start.p, (const int *)m->adj.p, nf, nv,
-                           (const float *)b->disp_P.p, (const float *)b->cpts.p, (const float *)b->pc_partial.p, nblk,
-                           (const float *)b->disp_dPf.p, b->disp.p, b->disp_m.p, b->disp_v.p, step_size, bc2_sqrt, h.adam_beta1,
-                           h.adam_beta2, h.adam_eps);
-        HIP_TRY(hipGetLastError());
-    }
-    b->have_disp = true;
-    return BF_OK;
-}
-
-int bf_batch_get_displacement(bf_batch *b, float *displacement) {
-    if (!b || !displacement) return fail(BF_ERR_INVALID, "bf_batch_get_displacement: null argument");
-    if (!b->have_disp) return fail(BF_ERR_INVALID, "bf_batch_get_displacement: no bf_fit_displacement yet");
-    HIP_TRY(hipSetDevice(b->m->device));
-    BF_TRY(bf_sync_all(b));
-    HIP_TRY(hipMemcpy(displacement, b->disp.p, b->disp.n * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
-}
-
-/* test hook: first Adam moment of the displacement (after one step it is 0.1 x the gradient) */
-int bf_batch_debug_disp_moment(bf_batch *b, float *m_out) {
-    if (!b || !m_out || !b->have_disp) return fail(BF_ERR_INVALID, "bf_batch_debug_disp_moment: bad argument");
-    HIP_TRY(hipSetDevice(b->m->device));
-    BF_TRY(bf_sync_all(b));
-    HIP_TRY(hipMemcpy(m_out, b->disp_m.p, b->disp_m.n * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include "bf_internal.h"
 #include "loss_bodies.h"
 #include "joints_body.h"
+#include "scan_kernels.h"
 #include "../../include/bodyfit.h"
 #include <cstdlib>
 #include "nearest_rule_ref.h"
@@ -138,7 +139,7 @@ constexpr int NN_QCAP = 64 * (NN_PASSES + 1);   // a wave's queue of screened re
 // diagnostic build (make CXXFLAGS+=-DBF_NEAREST_STATS): [0] queries [1] searches (1 + retries) [2] groups of cell lists [3] trips through
 // the screen [4] screen passes [5] records screened [6] rule passes [7] records through the rule
 __device__ unsigned long long bf_nearest_stats[8];
-extern "C" int bf_nearest_stats_read(unsigned long long *out, int reset) {
+extern "C" __attribute__((visibility("default"))) int bf_nearest_stats_read(unsigned long long *out, int reset) {   // (in no header: tools look it up by name)
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(bf_nearest_stats), sizeof(bf_nearest_stats)) != hipSuccess) return 1;
     if (reset) { unsigned long long z[8] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(bf_nearest_stats), z, sizeof z); }
     return 0;
@@ -794,7 +795,7 @@ extern "C" int bf_mesh_bwd_multi_launch(const MeshTab *M, const float *posedirsT
 
 
 // grid (ceil(EXT/32), F), 256 threads = 32 outputs x 8 tile chunks: ext[f][i] = sum over the tiles of part[f][tile][i].
-// Self-test of the two streams the resident fit launch needs (scan_api.hip): `probe` on the fit stream waits (bounded) for a
+// Self-test of the two streams the resident fit launch needs (dense_api.hip): `probe` on the fit stream waits (bounded) for a
 // bell that `ring` on the batch stream sets.  If the runtime has put both streams on one hardware queue the ring cannot start while
 // the probe runs, and the probe reports 2 instead of 1: the batch then keeps one fit launch per iteration.
 extern "C" __global__ void bf_door_probe_kernel(int *door) {

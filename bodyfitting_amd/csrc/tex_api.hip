@@ -1,23 +1,9 @@
 // Host side of the texture-fitting loop (reference smplify/texture_fitting.py:240-275; kernels: tex_kernels.hip).
 #include "bf_host.h"
+#include "grid_kernels.h"
+#include "tex_kernels.h"
 
 #include <memory>
-
-struct TexView { float R[9], t[3], K[9], orig; };
-extern "C" __global__ void bf_tex_project_kernel(int, const float *, TexView, float *);
-extern "C" __global__ void bf_tex_face_kernel(int, const int *, const float *, int, int, float *, int *, int *, int *, int, int);
-extern "C" __global__ void bf_tex_raster_kernel(int, int, const float *, const int *, const int *, const float *, int, float, float, float, float,
-                                                float, float *, float *, int);
-extern "C" __global__ void bf_tex_compose_kernel(int, int, const float *, float *);
-extern "C" __global__ void bf_tex_depth_kernel(int, int, const float *, float *);
-extern "C" __global__ void bf_tex_loss_kernel(int, const float *, const float *, float *, double *);
-extern "C" __global__ void bf_tex_backward_kernel(int, int, int, int, const float *, const float *, int, const float *, float *);
-extern "C" __global__ void bf_tex_backward_large_kernel(int, int, int, const float *, const float *, int, const float *, float *);
-extern "C" __global__ void bf_tex_adam_kernel(size_t, float *, float *, float *, const float *, float, float, float, float, float, float);
-extern "C" __global__ void bf_grid_scan_kernel(int *, int *, int);
-struct TexImage { const unsigned char *p; int h, w; };
-extern "C" __global__ void bf_tex_load_kernel(long long, int, const float *, const int *, const float *, const TexImage *, const float *, int, int,
-                                              float *);
 
 #define BF_TEX_TILE 8
 #define BF_TEX_REC 20

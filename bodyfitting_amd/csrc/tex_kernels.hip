@@ -19,12 +19,11 @@
 //   bf_tex_adam_kernel      torch.optim.Adam (defaults) on every texel
 //   bf_tex_load_kernel      load_textures_cuda_kernel (cuda/load_textures_cuda_kernel.cu): the per-face texture cubes of nr.load_obj
 #include "bf_internal.h"
+#include "tex_kernels.h"
 
 #define BF_TEX_TILE 8
 #define BF_TEX_REC 20            // floats per face record
 #define BF_TEX_GATHER_MAX 4096   // faces whose pixel box is larger go through the per-pixel atomic path of the backward pass
-
-struct TexView { float R[9], t[3], K[9], orig; };
 
 extern "C" __global__ void __launch_bounds__(256)
 bf_tex_project_kernel(int nv, const float *__restrict__ verts, TexView V, float *__restrict__ pv) {
@@ -357,8 +356,6 @@ bf_tex_adam_kernel(size_t n, float *__restrict__ p, float *__restrict__ m, float
 // Wrapping is applied ONCE per face, to the face's own copy of its UV corners.  (The reference wraps the shared `faces` array in
 // place from every thread of the face; where mod() is not idempotent - exact integers, MIRRORED_REPEAT at integer boundaries - its
 // result depends on how many threads got there first.  DESIGN.md section 2.)
-struct TexImage { const unsigned char *p; int h, w; };
-
 #define BF_TEX_REPEAT 0
 #define BF_TEX_MIRRORED_REPEAT 1
 #define BF_TEX_CLAMP_TO_EDGE 2

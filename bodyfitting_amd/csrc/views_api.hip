@@ -2,15 +2,7 @@
 // masks, the crop buffer, the outputs (all grown to the largest frame seen) and the launch sequence.  Kernels: views_kernels.hip.
 // The crop rectangle itself is image_cropping's scalar arithmetic and stays on the host (bodyfitting_amd/genebody.py).
 #include "bf_host.h"
-
-struct VwJob {
-    long long img_off, msk_off;
-    int ch, cw, mask_slot;
-};
-extern "C" __global__ void bf_views_bbox_init_kernel(int, int *);
-extern "C" __global__ void bf_views_bbox_kernel(int, int, long long, const uint8_t *, int *);
-extern "C" __global__ void bf_views_prepare_kernel(int, int, const VwJob *, const uint8_t *, const uint8_t *, uint8_t *, uint8_t *,
-                                                   unsigned long long *);
+#include "views_kernels.h"
 
 struct bf_views {
     int device = 0, L = 0;

@@ -3,14 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <climits>
 #include <cstdint>
+#include "views_kernels.h"
 
 #define VW_THREADS 256
-
-struct VwJob {
-    long long img_off;            // the crop's first image byte in the row buffer; rows W * 3 bytes apart
-    long long msk_off;            // the crop's first mask byte in the mask buffer; rows W bytes apart
-    int ch, cw, mask_slot;        // mask_slot >= 0: the resized mask goes to out_masks[mask_slot]
-};
 
 // per view (top, left, bottom, right) = (INT_MAX, INT_MAX, -1, -1): what the atomics of bf_views_bbox_kernel reduce into
 extern "C" __global__ __launch_bounds__(VW_THREADS) void bf_views_bbox_init_kernel(int n, int *__restrict__ bbox) {

@@ -22,6 +22,8 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* the library is built with hidden visibility: what is declared in here, and nothing else, is exported */
+#pragma GCC visibility push(default)
 
 typedef enum bf_status {
     BF_OK = 0,
@@ -723,6 +725,7 @@ int bf_batch_debug_disp_moment(bf_batch *b, float *m_out);
  * without BF_DENSE_GRAD_SUBMODEL: the ones its losses were evaluated at) */
 int bf_batch_debug_vertices(bf_batch *b, float *vertices);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

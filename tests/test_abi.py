@@ -1,4 +1,4 @@
-"""The C-ABI library loads on a box without a GPU and exports every symbol include/bodyfit.h declares."""
+"""The C-ABI library loads on a box without a GPU and exports the symbols include/bodyfit.h declares, and no others."""
 import ctypes
 import os
 import re
@@ -26,6 +26,20 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared_symbols():
         assert hasattr(lib, name), name
+
+
+def test_library_exports_exactly_the_declared_symbols():
+    """host code is compiled with hidden visibility and include/bodyfit.h sets default visibility around its declarations: the
+    dynamic bf_* symbols the library defines are the header's, no kernel handle, launcher or bf_host.h helper beside them
+    (bf_nearest_stats_read exists only in a -DBF_NEAREST_STATS build, which the product is not)"""
+    import shutil
+    import subprocess
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.fail(f"{_lib.LIB_PATH} not built - run __graft_entry__.build()")
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = sorted({line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("bf_")})
+    assert exported == declared_symbols()
 
 
 def test_no_compute_without_gpu_is_an_error_not_a_fallback(smpl_model, gmm):
