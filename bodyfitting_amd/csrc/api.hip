@@ -44,59 +44,50 @@ void bf_hyper_default(bf_hyper *h) {
 }
 
 }  // extern "C"
-int bf_launch_mesh(bf_model *m, MeshScratch *scr, int n, const float *state_dev, float *vraw, float *vout, float *xpart, float *joints,
-                   float *joints_ori, hipStream_t stream, hipEvent_t after_mesh, float *vposed, float *jraw, int *lmk_vid,
-                   float *lmk_w, float *dvzero, bool *zeroed, bool want_xpart, const MaskProj *mproj, bool *projected, int *door, int door_target,
-                   const MeshTab *tab, hipEvent_t mesh_done, bool *mesh_done_set) {
-    if (mesh_done_set) *mesh_done_set = false;
-    if (zeroed) *zeroed = false;
-    if (projected) *projected = false;
-    const bool need_x = joints || joints_ori || jraw || want_xpart;
-    const MeshTab &Q = tab ? *tab : m->mesh;          // (the sampled-first sub-model inside a dense loop without scans)
+int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &told) {
+    told = MeshPassDone{};
+    const int n = p.n;
+    const hipStream_t stream = p.stream;
+    float *const xpart = (p.joints || p.joints_ori || p.jraw || p.want_xpart) ? p.xpart : nullptr;
+    const MeshTab &Q = p.tab ? *p.tab : m->mesh;          // (the sampled-first sub-model inside a dense loop without scans)
     dim3 grid(Q.n_tiles, n);
     const float *pose_off = nullptr;
-    if (n >= BF_MFMA_MIN_FRAMES && n <= BF_BATCH32_MAX_FRAMES && !tab && !vposed && bf_mesh_batch32_fits(&m->mesh)) {
+    if (n >= BF_MFMA_MIN_FRAMES && n <= BF_BATCH32_MAX_FRAMES && !p.tab && !p.vposed && bf_mesh_batch32_fits(&m->mesh)) {
         // one or two 32-frame blocks: pose blend on the matrix cores with the epilogue behind the accumulators, ONE launch
         // (13.4 us instead of 4.6 + 15.5 + 14.5 at 32 frames; from 128 frames on the 128-frame GEMM tile below wins)
-        HIP_TRY(bf_mesh_batch32_launch(&m->mesh, state_dev, n, vraw, vout, need_x ? xpart : (float *)nullptr, stream));
-    } else if (n >= BF_MFMA_MIN_FRAMES && !tab) {
+        HIP_TRY(bf_mesh_batch32_launch(&m->mesh, p.state, n, p.vraw, p.vout, xpart, stream));
+    } else if (n >= BF_MFMA_MIN_FRAMES && !p.tab) {
         // batched pose blend on the matrix cores (posedirs streamed once for up to 256 frames), then the per-frame
         // shape / skinning part only
         const size_t ncols = (size_t)m->nv * 3;
+        MeshScratch *scr = p.scr;
         if (!scr) return fail(BF_ERR_INVALID, "bf_launch_mesh: the batched path needs a scratch owner");
         // (the scratch belongs to this stream's owner, so draining this stream is enough before a buffer is replaced)
-        if (scr->pose_off.n < (size_t)n * ncols) {
-            if (scr->pose_off.p) { HIP_TRY(hipStreamSynchronize(stream)); (void)hipFree(scr->pose_off.p); scr->pose_off.p = nullptr; }
-            HIP_TRY(scr->pose_off.alloc((size_t)n * ncols));
-        }
+        HIP_TRY(bf_grow(stream, scr->pose_off, (size_t)n * ncols));
         // A operand of the GEMM: the pose features of the batch, frame-minor and zero padded
         const int kpad = ((m->npf + 2 * BF_GEMM_KB - 1) / (2 * BF_GEMM_KB)) * 2 * BF_GEMM_KB, fpad = ((n + 127) / 128) * 128;
-        if (scr->featT.n < (size_t)kpad * fpad) {
-            if (scr->featT.p) { HIP_TRY(hipStreamSynchronize(stream)); (void)hipFree(scr->featT.p); scr->featT.p = nullptr; }
-            HIP_TRY(scr->featT.alloc((size_t)kpad * fpad));
-        }
-        HIP_TRY(bf_poseblend_launch(&m->mesh, state_dev, n, scr->featT.p, kpad, fpad, scr->pose_off.p, stream));
+        HIP_TRY(bf_grow(stream, scr->featT, (size_t)kpad * fpad));
+        HIP_TRY(bf_poseblend_launch(&m->mesh, p.state, n, scr->featT.p, kpad, fpad, scr->pose_off.p, stream));
         pose_off = scr->pose_off.p;
-        if (m->mesh.v_nnz == 4 && m->nb <= 12 && !vposed) {
-            bf_mesh_epilogue_batch_launch(&m->mesh, state_dev, pose_off, n, vraw, vout, need_x ? xpart : (float *)nullptr, stream);
+        if (m->mesh.v_nnz == 4 && m->nb <= 12 && !p.vposed) {
+            bf_mesh_epilogue_batch_launch(&m->mesh, p.state, pose_off, n, p.vraw, p.vout, xpart, stream);
         } else
-        hipLaunchKernelGGL(bf_mesh_epilogue_kernel, grid, dim3(128), 0, stream, m->mesh, state_dev, pose_off, vraw, vout,
-                           need_x ? xpart : (float *)nullptr, vposed);
+        hipLaunchKernelGGL(bf_mesh_epilogue_kernel, grid, dim3(128), 0, stream, m->mesh, p.state, pose_off, p.vraw, p.vout, xpart, p.vposed);
     } else if (bf_mesh_use_multi(m->npf, n)) {
-        const int e = bf_mesh_multi_launch(&Q, state_dev, n, vraw, vout, need_x ? xpart : (float *)nullptr, vposed,
-                                           dvzero, stream, mproj, door, door_target, mesh_done);
+        const int e = bf_mesh_multi_launch(&Q, p.state, n, p.vraw, p.vout, xpart, p.vposed, p.dvzero, stream, p.mproj, p.door, p.door_target,
+                                           p.mesh_done);
         if (e) return fail(BF_ERR_HIP, std::string("bf_mesh_multi_kernel: ") + hipGetErrorString((hipError_t)e));
-        if (mesh_done && mesh_done_set) *mesh_done_set = true;          // (the event completes with the mesh dispatch: the caller records nothing)
-        if (projected && mproj) *projected = true;
-        if (zeroed && dvzero) *zeroed = true;
+        told.mesh_done_set = p.mesh_done != nullptr;          // (the event completes with the mesh dispatch: the caller records nothing)
+        told.projected = p.mproj != nullptr;
+        told.zeroed = p.dvzero != nullptr;
     } else
     hipLaunchKernelGGL(bf_mesh_kernel, grid, dim3(BF_MESH_TILE * 3 * BF_MESH_RG), m->mesh_smem, stream, Q,
-                       state_dev, vraw, vout, need_x ? xpart : (float *)nullptr, vposed, pose_off, door, door_target);
+                       p.state, p.vraw, p.vout, xpart, p.vposed, pose_off, p.door, p.door_target);
     HIP_TRY(hipGetLastError());
-    if (after_mesh) HIP_TRY(hipEventRecord(after_mesh, stream));
-    if (joints || joints_ori || jraw) {
-        hipLaunchKernelGGL(bf_joints_kernel, dim3(n), dim3(256), 0, stream, Q, state_dev, (const float *)vraw,
-                           (const float *)xpart, joints, joints_ori, jraw, lmk_vid, lmk_w);
+    if (p.after_mesh) HIP_TRY(hipEventRecord(p.after_mesh, stream));
+    if (p.joints || p.joints_ori || p.jraw) {
+        hipLaunchKernelGGL(bf_joints_kernel, dim3(n), dim3(256), 0, stream, Q, p.state, (const float *)p.vraw,
+                           (const float *)p.xpart, p.joints, p.joints_ori, p.jraw, p.lmk_vid, p.lmk_w);
         HIP_TRY(hipGetLastError());
     }
     return BF_OK;
@@ -123,8 +114,10 @@ int bf_smpl_forward(bf_model *m, int n, const float *betas, const float *global_
                        (const float *)d_or.p, (const float *)d_bp.p, (const float *)nullptr, d_state.p,
                        (const float *)nullptr, (const float *)nullptr, 1.0f);
     HIP_TRY(hipGetLastError());
-    int rc = bf_launch_mesh(m, &scratch, n, d_state.p, d_vraw.p, nullptr, d_xp.p, d_j.p, d_jo.p, 0, nullptr, nullptr);
-    if (rc) return rc;
+    MeshPass mesh;
+    mesh.scr = &scratch; mesh.n = n; mesh.state = d_state.p;
+    mesh.vraw = d_vraw.p; mesh.xpart = d_xp.p; mesh.joints = d_j.p; mesh.joints_ori = d_jo.p;
+    BF_TRY(bf_launch_mesh(m, mesh));
     HIP_TRY(hipDeviceSynchronize());
     if (vertices) HIP_TRY(hipMemcpy(vertices, d_vraw.p, (size_t)n * nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (joints) HIP_TRY(hipMemcpy(joints, d_j.p, d_j.n * sizeof(float), hipMemcpyDeviceToHost));
@@ -151,6 +144,33 @@ static int publish(hipStream_t stream, float *dst, const float *src, size_t n_fl
 static int hand_over(hipStream_t stream, ResultArena &r, size_t n_floats, bool big) {
     if (!big) return publish(stream, r.host, r.dev.p, n_floats);
     HIP_TRY(hipMemcpyAsync(r.host, r.dev.p, n_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
+    return BF_OK;
+}
+
+// the result mesh of a batch: vertices and mapped joints of its F frames from their pose states, on `stream` with that stream's owner's
+// scratch; `after_mesh`: an event recorded between the mesh and the joints pass
+static int result_mesh(bf_batch *b, MeshScratch *scr, const float *state, float *vraw, float *vout, float *xpart, float *joints,
+                       hipStream_t stream, hipEvent_t after_mesh = nullptr) {
+    MeshPass p;
+    p.scr = scr; p.n = b->F; p.state = state; p.stream = stream;
+    p.vraw = vraw; p.vout = vout; p.xpart = xpart; p.joints = joints;
+    p.after_mesh = after_mesh;
+    return bf_launch_mesh(b->m, p);
+}
+// ... into the batch's current arena, on the batch stream
+static int result_mesh(bf_batch *b, hipEvent_t after_mesh = nullptr) {
+    return result_mesh(b, &b->scratch, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, b->stream, after_mesh);
+}
+
+// the tail of a fit: mesh, joints and hand-over of the first n_floats of result arena r on `stream` (scratch, vraw, xpart: that stream's
+// owner's), then ev_copied.  `after`: the event the stream waits for first; with_mesh = false: the arena already holds its mesh.
+static int enqueue_tail(bf_batch *b, ResultArena &r, hipStream_t stream, MeshScratch *scr, float *vraw, float *xpart, size_t n_floats,
+                        bool big, hipEvent_t after = nullptr, bool with_mesh = true) {
+    if (after) HIP_TRY(hipStreamWaitEvent(stream, after, 0));
+    float *d = r.dev.p;                              // (the arena's slices by address: the batch's views may be on another one)
+    if (with_mesh) BF_TRY(result_mesh(b, scr, d + b->res_off[2], vraw, d + b->res_off[4], xpart, d + b->res_off[3], stream));
+    BF_TRY(hand_over(stream, r, n_floats, big));
+    HIP_TRY(hipEventRecord(r.ev_copied, stream));
     return BF_OK;
 }
 
@@ -186,25 +206,15 @@ static hipError_t write_input(bf_batch *b, void *dst, const void *src, size_t by
     return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
 }
 
-// the deferred part of a frame-after-frame call (fit_impl, `tail_aside`): mesh + joints + hand-over of result arena tail_k on the
+// the deferred part of a frame-after-frame call (fit_tail_aside): mesh + joints + hand-over of result arena tail_k on the
 // second stream, behind the fit that filled it.  Every entry point that looks at results, events of the second stream or starts
 // another fit comes through here first (bf_sync_all, bf_fit, bf_batch_get_previous, bf_batch_stage_inputs, bf_batch_destroy).
-static int flush_tail_body(bf_batch *b, int k) {
-    ResultArena &r = b->arena[k];
-    HIP_TRY(hipStreamWaitEvent(b->copy_stream, r.ev_done, 0));
-    float *d = r.dev.p;                              // (arena k's slices by address: the views may already have moved on)
-    BF_TRY(bf_launch_mesh(b->m, &b->scratch, b->F, d + b->res_off[2], b->vraw.p, d + b->res_off[4], b->xpart.p, d + b->res_off[3], nullptr,
-                          b->copy_stream, nullptr, nullptr));
-    BF_TRY(hand_over(b->copy_stream, r, b->res_total, b->tail_big));
-    HIP_TRY(hipEventRecord(r.ev_copied, b->copy_stream));
-    return BF_OK;
-}
 int bf_flush_tail(bf_batch *b) {
     const int k = b->tail_k;
     if (k < 0) return BF_OK;
     b->tail_k = -1;
     ResultArena &r = b->arena[k];
-    const int rc = flush_tail_body(b, k);
+    const int rc = enqueue_tail(b, r, b->copy_stream, &b->scratch, b->vraw.p, b->xpart.p, b->res_total, b->tail_big, r.ev_done);
     if (rc) {
         // the mesh / copy / event of arena k did not all go out: its ev_copied still carries its previous (completed) record, so a
         // wait on it would pass and hand out the pinned buffer's OLD contents.  Nothing of this arena may be read any more:
@@ -217,7 +227,7 @@ int bf_flush_tail(bf_batch *b) {
     return BF_OK;
 }
 
-/* Fit lanes.  A frame-after-frame fit (the tail-aside conditions of fit_impl) is one workgroup per frame on one CU for ~380 us while
+/* Fit lanes.  A frame-after-frame fit (the tail-aside conditions of fit_plan) is one workgroup per frame on one CU for ~380 us while
  * the other CUs idle, and the frames of a capture are independent (every call carries BF_FIT_RESET).  With n_lanes > 1 such a fit goes
  * to the next lane (round robin): a stream of its own with its own Adam moments, result arena, mesh scratch and input arenas, so fit
  * i + 1 starts on another CU as soon as it is issued while fit i runs.  A lane's stream holds [input transfer] fit, mesh, joints,
@@ -411,6 +421,7 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
         // fit lanes (created on first use): one frame's fit per CU, so at most CUs / frames of them; not with zero-copy staging
         int n_cus = 0;
         (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, m->device);
+        if (n_cus > 0) b->n_cus = n_cus;
         const int d = std::min(fit_lanes_wanted(), std::max(n_cus, 1) / n_frames);
         b->n_lanes = (!b->stage_zerocopy && d > 1) ? d : 1;
     }
@@ -516,14 +527,20 @@ static int reset_adam(bf_batch *b, const float *params_host) {
     return BF_OK;
 }
 
-int bf_batch_reset(bf_batch *b) {
-    if (!b) return fail(BF_ERR_INVALID, "bf_batch_reset: null batch");
-    HIP_TRY(hipSetDevice(b->m->device));
-    BF_TRY(bf_guard_arena(b));
+// the re-arm as stream commands: the parameters back to the initial estimate, the Adam moments to zero
+static int rearm(bf_batch *b) {
     // (hipMemcpyDefault: with BF_STAGE_MODE=zerocopy params0 is a view into the pinned staging buffer, not device memory)
     HIP_TRY(hipMemcpyAsync(b->params.p, b->params0.p, b->params.n * sizeof(float), hipMemcpyDefault, b->stream));
     HIP_TRY(hipMemsetAsync(b->adam_m.p, 0, b->adam_m.n * sizeof(float), b->stream));
     HIP_TRY(hipMemsetAsync(b->adam_v.p, 0, b->adam_v.n * sizeof(float), b->stream));
+    return BF_OK;
+}
+
+int bf_batch_reset(bf_batch *b) {
+    if (!b) return fail(BF_ERR_INVALID, "bf_batch_reset: null batch");
+    HIP_TRY(hipSetDevice(b->m->device));
+    BF_TRY(bf_guard_arena(b));
+    BF_TRY(rearm(b));
     b->steps_done = 0;
     b->have_result = false;
     b->fetched = false;
@@ -704,35 +721,77 @@ static FrameIO bf_frame_io(bf_batch *b, bool want_grads) {
     return io;
 }
 
+// floats of a result arena a fetch hands over: [params | terms | state | joints] and, when they were built, the vertices
+static size_t result_floats(const bf_batch *b, bool with_v) { return with_v ? b->res_total : b->res_small; }
+
+// How one bf_fit call is put on the GPU.  fit_plan names the route from the flags and the batch's facts before anything is issued;
+// fit_impl dispatches on it to one function per route, each the HIP call sequence of that route.
+enum class FitRoute {
+    LANE,                       // frame after frame on the next fit lane's stream
+    GRAPH,                      // the whole call as one hipGraph launch
+    GRAPH_PIPELINED,            // ... of kernels only; the fetch runs on the second stream, under whatever is enqueued next
+    TAIL_ASIDE,                 // frame after frame on the batch stream; mesh, joints and hand-over deferred to the second stream
+    TAIL_ASIDE_CROWDED,         // ... of a batch that fills the machine: the mesh stays on the batch stream, only the copy goes aside
+    UNTIMED,                    // the sparse schedule without event records
+    TIMED_SPARSE,               // the sparse schedule between the call's timing events
+    TIMED_DENSE_LOSSES,         // scans, silhouettes or a dense keypoint loss: bf_fit_with_scans
+    TIMED_REFERENCE_LITERAL,    // BF_FIT_DENSE: every iteration evaluates the whole mesh
+};
+struct FitCall {
+    uint32_t flags;             // (BF_FIT_DENSE cleared when dense losses are present)
+    bool reset, want_v, fetch;
+    bool big_fetch;             // the fetch is 512 KB or more: a copy command (below that the publish kernel)
+    int n_iters;
+    FitRoute route;
+};
+// what the routes leave differently: the result is in the pinned mirror, it has vertices, the call's timing events were recorded
+struct FitDone { bool fetched, has_v, timed; };
+
+static FitCall fit_plan(const bf_batch *b, int n_iters, uint32_t flags) {
+    FitCall c;
+    const bool dense_losses = !b->scans.empty() || b->has_masks || b->m->kp_dense;
+    if (dense_losses) flags &= ~BF_FIT_DENSE;
+    const bool dense = flags & BF_FIT_DENSE, sparse = !dense_losses && !dense;
+    c.flags = flags; c.n_iters = n_iters;
+    c.reset = flags & BF_FIT_RESET; c.want_v = !(flags & BF_FIT_NO_VERTICES); c.fetch = flags & BF_FIT_FETCH;
+    // (a small fetch is cheaper as a copy node inside the graph than as a second stream with two event hand-offs)
+    c.big_fetch = result_floats(b, c.want_v) * sizeof(float) >= (size_t)512 * 1024;
+    // Calls issued back to back without timing records (frame after frame, as the reference's loop does): the fit kernel is a
+    // latency chain of one workgroup per frame, so the mesh / joints / result hand-over of a call runs on the second stream UNDER the
+    // next call's fit kernel; the two result arenas alternate as in the pipelined fetch.  With fit lanes such a call goes to the next
+    // lane instead; every other call first finds the last fit in the batch's own buffers (bf_lanes_drain).
+    const bool tail_aside = (flags & BF_FIT_NOTIME) && !(flags & BF_FIT_GRAPH) && c.reset && sparse && c.fetch && c.want_v;
+    if (tail_aside && b->n_lanes > 1) c.route = FitRoute::LANE;
+    else if ((flags & BF_FIT_GRAPH) && c.reset && sparse) c.route = (c.fetch && c.big_fetch) ? FitRoute::GRAPH_PIPELINED : FitRoute::GRAPH;
+    else if (tail_aside) c.route = b->F >= b->n_cus ? FitRoute::TAIL_ASIDE_CROWDED : FitRoute::TAIL_ASIDE;
+    else if ((flags & BF_FIT_NOTIME) && sparse) c.route = FitRoute::UNTIMED;
+    else if (sparse) c.route = FitRoute::TIMED_SPARSE;
+    else c.route = dense_losses ? FitRoute::TIMED_DENSE_LOSSES : FitRoute::TIMED_REFERENCE_LITERAL;
+    return c;
+}
+
 // stream work of one sparse-schedule call: [re-arm] -> persistent fit -> [mesh + joints] -> [fetch]; `ev` = event
 // records between the parts (null inside a graph capture)
-static int enqueue_plain(bf_batch *b, int n_iters, const HyperDev &hd, const FrameIO &io, bool reset, bool want_v, bool fetch,
-                         int adam_t0, hipEvent_t *ev) {
-    bf_model *m = b->m;
-    FrameIO io2 = io;
-    if (reset) io2.params0 = b->params0.p;      // re-arm inside the fit kernel: no copy / memset commands
-    HIP_TRY(bf_fit_launch(&m->fit, &io2, &hd, n_iters, 0, b->adam_tab.p, adam_t0, b->fit_smem, b->stream, nullptr));
+static int enqueue_plain(bf_batch *b, const FitCall &c, const HyperDev &hd, hipEvent_t *ev) {
+    FrameIO io = bf_frame_io(b, false);
+    if (c.reset) io.params0 = b->params0.p;      // re-arm inside the fit kernel: no copy / memset commands
+    HIP_TRY(bf_fit_launch(&b->m->fit, &io, &hd, c.n_iters, 0, b->adam_tab.p, b->steps_done, b->fit_smem, b->stream, nullptr));
     if (ev) HIP_TRY(hipEventRecord(ev[1], b->stream));
-    if (want_v) {
-        BF_TRY(bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream,
-                              ev ? ev[2] : nullptr, nullptr));
+    if (c.want_v) {
+        BF_TRY(result_mesh(b, ev ? ev[2] : nullptr));
     } else if (ev) HIP_TRY(hipEventRecord(ev[2], b->stream));
-    if (fetch) {
-        // one copy of the result arena: [params | terms | state | joints] and, when they were built, the vertices
-        const size_t nfl = want_v ? b->res_total : b->res_small;
-        BF_TRY(hand_over(b->stream, b->arena[b->cur], nfl, nfl * sizeof(float) >= (size_t)512 * 1024));
-    }
+    // one copy of the result arena
+    if (c.fetch) BF_TRY(hand_over(b->stream, b->arena[b->cur], result_floats(b, c.want_v), c.big_fetch));
     return BF_OK;
 }
 
-// `exec` holds a re-armed sparse-schedule call captured for `key`: captured now unless the graph there already is that one
-static int ensure_graph(bf_batch *b, hipGraphExec_t &exec, bf_graph_key &exec_key, const bf_graph_key &key, int n_iters, const HyperDev &hd,
-                        const FrameIO &io, bool want_v, bool fetch) {
+// `exec` holds the re-armed sparse-schedule call `c` captured for `key`: captured now unless the graph there already is that one
+static int ensure_graph(bf_batch *b, hipGraphExec_t &exec, bf_graph_key &exec_key, const bf_graph_key &key, const FitCall &c, const HyperDev &hd) {
     if (exec && std::memcmp(&key, &exec_key, sizeof key) == 0) return BF_OK;
     if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
     hipGraph_t graph = nullptr;
     HIP_TRY(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_plain(b, n_iters, hd, io, true, want_v, fetch, 0, nullptr);
+    const int rc = enqueue_plain(b, c, hd, nullptr);
     hipError_t e = hipStreamEndCapture(b->stream, &graph);
     if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
     HIP_TRY(e);
@@ -742,11 +801,8 @@ static int ensure_graph(bf_batch *b, hipGraphExec_t &exec, bf_graph_key &exec_ke
     return BF_OK;
 }
 
-static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags);
-
-// a frame-after-frame fit on the next lane: fit, mesh, joints and hand-over of the lane's result arena, in the lane's stream order
-static int lane_fit(bf_batch *b, int n_iters, const HyperDev &hd, bool big_fetch) {
-    bf_model *m = b->m;
+// LANE: fit, mesh, joints and hand-over of the next lane's result arena, in the lane's stream order
+static int fit_lane(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &done) {
     BF_TRY(lanes_engage(b));
     const int j = b->lane_next;
     b->lane_next = (j + 1) % b->n_lanes;
@@ -755,22 +811,194 @@ static int lane_fit(bf_batch *b, int n_iters, const HyperDev &hd, bool big_fetch
     b->lane_last = j;
     ResultArena &r = l.arena;
     r.seq = -1; r.fetched = false; r.has_v = false;             // (bf_fit numbers the lane's result once the whole call went out)
-    b->fetched = false; b->have_result = false;
+    b->fetched = false; b->have_result = false;                 // (a failure from here on: the lane's result stays unfetched and without a mesh, nothing reads it)
     if (b->in_cur >= 2) input_arena(b, b->in_cur).readers |= 1u << j;
     float *d = r.dev.p;
     FrameIO io = bf_frame_io(b, false);
     io.params0 = b->params0.p;                  // re-arm inside the fit kernel
     io.params = d + b->res_off[0]; io.terms = d + b->res_off[1]; io.state = d + b->res_off[2];
     io.adam_m = l.adam_m.p; io.adam_v = l.adam_v.p;
-    HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, n_iters, 0, b->adam_tab.p, b->steps_done, b->fit_smem, l.stream, nullptr));
-    // (a failure from here on: the lane's result stays unfetched and without a mesh, nothing reads it)
-    BF_TRY(bf_launch_mesh(m, &l.scratch, b->F, io.state, l.vraw.p, d + b->res_off[4], l.xpart.p, d + b->res_off[3], nullptr,
-                          l.stream, nullptr, nullptr));
-    BF_TRY(hand_over(l.stream, r, b->res_total, big_fetch));
-    HIP_TRY(hipEventRecord(r.ev_copied, l.stream));
-    b->fetched = true;
-    b->have_result = true;
-    b->steps_done += n_iters;
+    HIP_TRY(bf_fit_launch(&b->m->fit, &io, &hd, c.n_iters, 0, b->adam_tab.p, b->steps_done, b->fit_smem, l.stream, nullptr));
+    BF_TRY(enqueue_tail(b, r, l.stream, &l.scratch, l.vraw.p, l.xpart.p, b->res_total, c.big_fetch));
+    done = {true, true, false};
+    return BF_OK;
+}
+
+// both graph routes: the MFMA batch path may grow its scratch buffer - make sure that happened before capturing
+static int graph_grow_scratch(bf_batch *b, const FitCall &c) {
+    if (c.want_v && b->F >= BF_MFMA_MIN_FRAMES && b->scratch.pose_off.n < (size_t)b->F * b->m->nv * 3) {
+        BF_TRY(bf_sync_all(b));
+        BF_TRY(result_mesh(b));
+        BF_TRY(bf_sync_all(b));
+    }
+    return BF_OK;
+}
+
+// both graph routes: the graph of call `c` into result arena k (the current one), captured if need be, launched between the timing events
+static int graph_replay(bf_batch *b, const FitCall &c, const bf_hyper &h, const HyperDev &hd, int k, hipGraphExec_t &exec, bf_graph_key &exec_key) {
+    const bf_graph_key key{c.n_iters, c.flags, k | (b->in_cur << 4) | ((int)b->in_host << 12), h};   // (the captured nodes hold the arenas' addresses)
+    BF_TRY(ensure_graph(b, exec, exec_key, key, c, hd));
+    HIP_TRY(hipEventRecord(b->ev[0], b->stream));
+    HIP_TRY(hipGraphLaunch(exec, b->stream));
+    HIP_TRY(hipEventRecord(b->ev[1], b->stream));       // (no events inside a graph: the whole call is charged to ms[0])
+    HIP_TRY(hipEventRecord(b->ev[2], b->stream));
+    HIP_TRY(hipEventRecord(b->ev[3], b->stream));
+    return BF_OK;
+}
+
+// GRAPH: the whole call as one hipGraph launch - the host issues a single command per fit
+static int fit_graph(bf_batch *b, const FitCall &c, const bf_hyper &h, const HyperDev &hd, FitDone &done) {
+    BF_TRY(graph_grow_scratch(b, c));
+    BF_TRY(graph_replay(b, c, h, hd, b->cur, b->graph_exec, b->graph_key));
+    done = {c.fetch, c.want_v, true};
+    return BF_OK;
+}
+
+// GRAPH_PIPELINED: this fit writes the result arena the previous one did not use; its device-to-host copy
+// runs on the copy stream, under the kernels of whatever is enqueued next
+static int fit_graph_pipelined(bf_batch *b, const FitCall &c, const bf_hyper &h, const HyperDev &hd, FitDone &done) {
+    BF_TRY(graph_grow_scratch(b, c));
+    const int k = b->cur ^ 1;
+    ResultArena &r = b->arena[k];
+    if (r.copy_pending) { HIP_TRY(hipStreamWaitEvent(b->stream, r.ev_copied, 0)); r.copy_pending = false; }
+    bf_use_arena(b, k);
+    FitCall kernels = c;                                // (the pipelined graphs hold kernels only)
+    kernels.fetch = false;
+    BF_TRY(graph_replay(b, kernels, h, hd, k, b->graph_pipe[k], b->graph_pipe_key[k]));
+    HIP_TRY(hipEventRecord(r.ev_done, b->stream));
+    BF_TRY(enqueue_tail(b, r, b->copy_stream, &b->scratch, b->vraw.p, b->xpart.p, result_floats(b, c.want_v), true, r.ev_done, false));
+    r.copy_pending = true;
+    done = {true, c.want_v, true};
+    return BF_OK;
+}
+
+// both tail-aside routes: the fit into the result arena the previous one did not use - the current one from here on - re-armed inside
+// the kernel; own_signal: the arena's ev_done completes with the fit's own dispatch
+static int tail_aside_fit(bf_batch *b, const FitCall &c, const HyperDev &hd, bool own_signal) {
+    const int k = b->cur ^ 1;
+    ResultArena &r = b->arena[k];
+    if (r.copy_pending) {          // (arena k's hand-over of two calls ago: normally long done - then no wait packet goes into the stream)
+        if (hipEventQuery(r.ev_copied) != hipSuccess) HIP_TRY(hipStreamWaitEvent(b->stream, r.ev_copied, 0));
+        r.copy_pending = false;
+    }
+    bf_use_arena(b, k);
+    FrameIO io = bf_frame_io(b, false);
+    io.params0 = b->params0.p;                  // re-arm inside the fit kernel
+    HIP_TRY(bf_fit_launch(&b->m->fit, &io, &hd, c.n_iters, 0, b->adam_tab.p, b->steps_done, b->fit_smem, b->stream, own_signal ? r.ev_done : nullptr));
+    return BF_OK;
+}
+
+// TAIL_ASIDE: the rest - wait for this fit, mesh, joints, hand-over, on the second stream - is enqueued at the next entry point
+// (bf_flush_tail): a bf_batch_stage_inputs that follows puts the next frame's inputs ahead of it
+static int fit_tail_aside(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &done) {
+    // (ev_done completes with the fit's own dispatch: no marker packet between this fit and the next)
+    static const bool own_signal = [] { const char *e = getenv("BF_FIT_DONE_EVENT"); return !(e && e[0] == '0'); }();
+    BF_TRY(tail_aside_fit(b, c, hd, own_signal));
+    ResultArena &r = b->arena[b->cur];
+    if (!own_signal) HIP_TRY(hipEventRecord(r.ev_done, b->stream));
+    b->tail_k = b->cur; b->tail_big = c.big_fetch;
+    r.copy_pending = true;
+    done = {true, true, false};
+    return BF_OK;
+}
+
+// TAIL_ASIDE_CROWDED.  A batch that fills the machine (a frame's workgroup per CU, one workgroup fits per CU): under the NEXT fit the
+// mesh kernels would only get the CUs that fit's workgroups leave as they finish - measured 379 us for a 33 us GEMM at 256 frames.  The
+// mesh then goes on the fit's own stream, ahead of the next fit (0.462 + 0.074 ms instead of 0.601); only the copy stays aside.
+static int fit_tail_aside_crowded(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &done) {
+    BF_TRY(tail_aside_fit(b, c, hd, false));
+    ResultArena &r = b->arena[b->cur];
+    BF_TRY(result_mesh(b));
+    HIP_TRY(hipEventRecord(r.ev_done, b->stream));
+    BF_TRY(enqueue_tail(b, r, b->copy_stream, &b->scratch, b->vraw.p, b->xpart.p, b->res_total, c.big_fetch, r.ev_done, false));
+    r.copy_pending = true;
+    done = {true, true, false};
+    return BF_OK;
+}
+
+// UNTIMED
+static int fit_untimed(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &done) {
+    BF_TRY(enqueue_plain(b, c, hd, nullptr));
+    done = {c.fetch, c.want_v, false};
+    return BF_OK;
+}
+
+// TIMED_SPARSE
+static int fit_timed_sparse(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &done) {
+    HIP_TRY(hipEventRecord(b->ev[0], b->stream));
+    BF_TRY(enqueue_plain(b, c, hd, b->ev));
+    HIP_TRY(hipEventRecord(b->ev[3], b->stream));
+    done = {c.fetch, c.want_v, true};
+    return BF_OK;
+}
+
+// TIMED_DENSE_LOSSES: the loop with scans, silhouettes or the dense keypoint loss (dense_api.hip), then the result mesh
+static int fit_timed_dense_losses(bf_batch *b, const FitCall &c, const bf_hyper &h, const HyperDev &hd, FitDone &done) {
+    HIP_TRY(hipEventRecord(b->ev[0], b->stream));
+    if (c.reset) BF_TRY(rearm(b));
+    BF_TRY(bf_fit_with_scans(b, c.n_iters, h, hd, bf_frame_io(b, false)));
+    HIP_TRY(hipEventRecord(b->ev[1], b->stream));
+    if (c.want_v) {
+        BF_TRY(result_mesh(b, b->ev[2]));
+    } else HIP_TRY(hipEventRecord(b->ev[2], b->stream));
+    if (c.fetch) BF_TRY(hand_over(b->stream, b->arena[b->cur], result_floats(b, c.want_v), true));      // (always a copy command here)
+    HIP_TRY(hipEventRecord(b->ev[3], b->stream));
+    done = {c.fetch, c.want_v, true};
+    return BF_OK;
+}
+
+// TIMED_REFERENCE_LITERAL: every iteration evaluates the whole mesh (smplify.py:179-190)
+static int fit_timed_reference_literal(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &done) {
+    const FrameIO io = bf_frame_io(b, false);
+    HIP_TRY(hipEventRecord(b->ev[0], b->stream));
+    if (c.reset) BF_TRY(rearm(b));
+    for (int it = 0; it < c.n_iters; ++it) {
+        HIP_TRY(bf_fit_launch(&b->m->fit, &io, &hd, 1, 0, b->adam_tab.p, b->steps_done + it, b->fit_smem, b->stream, nullptr));
+        BF_TRY(result_mesh(b));
+    }
+    HIP_TRY(hipEventRecord(b->ev[1], b->stream));
+    HIP_TRY(hipEventRecord(b->ev[2], b->stream));
+    if (c.fetch) BF_TRY(hand_over(b->stream, b->arena[b->cur], b->res_total, true));      // (always a copy command here)
+    HIP_TRY(hipEventRecord(b->ev[3], b->stream));
+    done = {c.fetch, true, true};
+    return BF_OK;
+}
+
+static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
+    HIP_TRY(hipSetDevice(b->m->device));
+    bf_hyper h;
+    if (hyper) h = *hyper; else bf_hyper_default(&h);
+    const FitCall c = fit_plan(b, n_iters, flags);
+    // preamble: the lanes drained (or kept, for a lane fit), the counters, the Adam table, the fit image and this call's ring events
+    if (c.route != FitRoute::LANE) BF_TRY(bf_lanes_drain(b));
+    if (c.reset) { b->steps_done = 0; b->have_result = false; }
+    BF_TRY(ensure_adam_tab(b, h, b->steps_done + n_iters));
+    const HyperDev hd = bf_to_dev(h);
+    BF_TRY(bf_ensure_fit_image(b, bf_frame_io(b, false), hd));       // (once per model: the fit kernel's batched prologue, before any graph captures a launch)
+    b->ev = b->ring.data() + (size_t)(b->ring_n % bf_batch::kRing) * 4;
+    for (int k = 0; k < 4; ++k)
+        if (!b->ev[k]) HIP_TRY(hipEventCreate(&b->ev[k]));
+    // a pipelined fetch may still be reading the arena this call writes: the routes that write the current one wait for it
+    const bool other_arena = c.route == FitRoute::LANE || c.route == FitRoute::GRAPH_PIPELINED || c.route == FitRoute::TAIL_ASIDE ||
+                             c.route == FitRoute::TAIL_ASIDE_CROWDED;
+    if (!other_arena) BF_TRY(bf_guard_arena(b));
+    FitDone done{};
+    switch (c.route) {
+    case FitRoute::LANE:                    BF_TRY(fit_lane(b, c, hd, done)); break;
+    case FitRoute::GRAPH:                   BF_TRY(fit_graph(b, c, h, hd, done)); break;
+    case FitRoute::GRAPH_PIPELINED:         BF_TRY(fit_graph_pipelined(b, c, h, hd, done)); break;
+    case FitRoute::TAIL_ASIDE:              BF_TRY(fit_tail_aside(b, c, hd, done)); break;
+    case FitRoute::TAIL_ASIDE_CROWDED:      BF_TRY(fit_tail_aside_crowded(b, c, hd, done)); break;
+    case FitRoute::UNTIMED:                 BF_TRY(fit_untimed(b, c, hd, done)); break;
+    case FitRoute::TIMED_SPARSE:            BF_TRY(fit_timed_sparse(b, c, hd, done)); break;
+    case FitRoute::TIMED_DENSE_LOSSES:      BF_TRY(fit_timed_dense_losses(b, c, h, hd, done)); break;
+    case FitRoute::TIMED_REFERENCE_LITERAL: BF_TRY(fit_timed_reference_literal(b, c, hd, done)); break;
+    }
+    // epilogue: the bookkeeping the routes differ in, once
+    b->fetched = done.fetched;
+    b->have_result = done.has_v;
+    b->steps_done += n_iters;           // (a graph call carries BF_FIT_RESET: from zero)
+    if (done.timed) { b->ring_n += 1; b->timed = true; }
     return BF_OK;
 }
 
@@ -809,153 +1037,6 @@ int bf_fit(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
     r.seq = b->fit_seq++;
     r.fetched = b->fetched;
     r.has_v = b->have_result;
-    return BF_OK;
-}
-
-static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
-    bf_model *m = b->m;
-    HIP_TRY(hipSetDevice(m->device));
-    bf_hyper h;
-    if (hyper) h = *hyper; else bf_hyper_default(&h);
-    const bool reset = flags & BF_FIT_RESET;
-    const bool dense_losses = !b->scans.empty() || b->has_masks || m->kp_dense;
-    if (dense_losses) flags &= ~BF_FIT_DENSE;
-    const bool dense = flags & BF_FIT_DENSE, want_v = !(flags & BF_FIT_NO_VERTICES), fetch = flags & BF_FIT_FETCH;
-    // Calls issued back to back without timing records (frame after frame, as the reference's loop does): the fit kernel is a
-    // latency chain of one workgroup per frame, so the mesh / joints / result hand-over of a call runs on the second stream UNDER the
-    // next call's fit kernel; the two result arenas alternate as in the pipelined fetch.  With fit lanes such a call goes to the next
-    // lane instead; every other call first finds the last fit in the batch's own buffers (bf_lanes_drain).
-    const bool tail_aside = (flags & BF_FIT_NOTIME) && !(flags & BF_FIT_GRAPH) && reset && !dense_losses && !dense && fetch && want_v;
-    const bool lane = tail_aside && b->n_lanes > 1;
-    if (!lane) BF_TRY(bf_lanes_drain(b));
-    if (reset) { b->steps_done = 0; b->have_result = false; }
-    BF_TRY(ensure_adam_tab(b, h, b->steps_done + n_iters));
-    HyperDev hd = bf_to_dev(h);
-    FrameIO io = bf_frame_io(b, false);
-    BF_TRY(bf_ensure_fit_image(b, io, hd));       // (once per model: the fit kernel's batched prologue, before any graph captures a launch)
-    b->ev = b->ring.data() + (size_t)(b->ring_n % bf_batch::kRing) * 4;
-    for (int k = 0; k < 4; ++k)
-        if (!b->ev[k]) HIP_TRY(hipEventCreate(&b->ev[k]));
-    const size_t fb = sizeof(float);
-    // (a small fetch is cheaper as a copy node inside the graph than as a second stream with two event hand-offs)
-    const bool big_fetch = (want_v ? b->res_total : b->res_small) * sizeof(float) >= (size_t)512 * 1024;
-    const bool pipelined = (flags & BF_FIT_GRAPH) && reset && !dense_losses && !dense && fetch && big_fetch;
-    if (lane) return lane_fit(b, n_iters, hd, big_fetch);
-    if (!pipelined && !tail_aside) BF_TRY(bf_guard_arena(b));      // (a pipelined fetch may still be reading the arena this call writes)
-    if ((flags & BF_FIT_GRAPH) && reset && !dense_losses && !dense) {
-        // the whole call as one hipGraph launch: the host issues a single command per fit
-        // the MFMA batch path may grow its scratch buffer: make sure that happened before capturing
-        if (want_v && b->F >= BF_MFMA_MIN_FRAMES && b->scratch.pose_off.n < (size_t)b->F * m->nv * 3) {
-            BF_TRY(bf_sync_all(b));
-            BF_TRY(bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, nullptr, nullptr));
-            BF_TRY(bf_sync_all(b));
-        }
-        // pipelined fetch: this fit writes the result arena the previous one did not use; its device-to-host copy
-        // runs on the copy stream, under the kernels of whatever is enqueued next
-        const int k = pipelined ? b->cur ^ 1 : b->cur;
-        ResultArena &r = b->arena[k];
-        const bf_graph_key key{n_iters, flags, k | (b->in_cur << 4) | ((int)b->in_host << 12), h};   // (the captured nodes hold the arenas' addresses)
-        if (pipelined) {
-            if (r.copy_pending) { HIP_TRY(hipStreamWaitEvent(b->stream, r.ev_copied, 0)); r.copy_pending = false; }
-            bf_use_arena(b, k);
-            io = bf_frame_io(b, false);
-        }
-        hipGraphExec_t &exec = pipelined ? b->graph_pipe[k] : b->graph_exec;      // (the pipelined graphs hold kernels only)
-        BF_TRY(ensure_graph(b, exec, pipelined ? b->graph_pipe_key[k] : b->graph_key, key, n_iters, hd, io, want_v, fetch && !pipelined));
-        HIP_TRY(hipEventRecord(b->ev[0], b->stream));
-        HIP_TRY(hipGraphLaunch(exec, b->stream));
-        HIP_TRY(hipEventRecord(b->ev[1], b->stream));       // (no events inside a graph: the whole call is charged to ms[0])
-        HIP_TRY(hipEventRecord(b->ev[2], b->stream));
-        HIP_TRY(hipEventRecord(b->ev[3], b->stream));
-        if (pipelined) {
-            HIP_TRY(hipEventRecord(r.ev_done, b->stream));
-            HIP_TRY(hipStreamWaitEvent(b->copy_stream, r.ev_done, 0));
-            BF_TRY(hand_over(b->copy_stream, r, want_v ? b->res_total : b->res_small, true));
-            HIP_TRY(hipEventRecord(r.ev_copied, b->copy_stream));
-            r.copy_pending = true;
-        }
-        b->fetched = fetch;
-        b->ring_n += 1;
-        b->steps_done = n_iters;
-        b->timed = true;
-        b->have_result = want_v;
-        return BF_OK;
-    }
-    const bool notime = (flags & BF_FIT_NOTIME) && !dense_losses && !dense;
-    if (tail_aside) {
-        const int k = b->cur ^ 1;
-        ResultArena &r = b->arena[k];
-        if (r.copy_pending) {          // (arena k's hand-over of two calls ago: normally long done - then no wait packet goes into the stream)
-            if (hipEventQuery(r.ev_copied) != hipSuccess) HIP_TRY(hipStreamWaitEvent(b->stream, r.ev_copied, 0));
-            r.copy_pending = false;
-        }
-        bf_use_arena(b, k);
-        FrameIO io2 = bf_frame_io(b, false);
-        io2.params0 = b->params0.p;                  // re-arm inside the fit kernel
-        static const bool own_signal = [] { const char *e = getenv("BF_FIT_DONE_EVENT"); return !(e && e[0] == '0'); }();
-        static const int n_cus = [] { int v = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v > 0 ? v : 256; }();
-        const bool crowded = b->F >= n_cus;
-        const bool signal_here = own_signal && !crowded;       // (ev_done completes with the fit's own dispatch: no marker packet between this fit and the next)
-        HIP_TRY(bf_fit_launch(&m->fit, &io2, &hd, n_iters, 0, b->adam_tab.p, b->steps_done, b->fit_smem, b->stream, signal_here ? r.ev_done : nullptr));
-        // A batch that fills the machine (a frame's workgroup per CU, one workgroup fits per CU): under the NEXT fit the mesh kernels
-        // would only get the CUs that fit's workgroups leave as they finish - measured 379 us for a 33 us GEMM at 256 frames.  The mesh
-        // then goes on the fit's own stream, ahead of the next fit (0.462 + 0.074 ms instead of 0.601); only the copy stays aside.
-        if (crowded) BF_TRY(bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, nullptr, nullptr));
-        if (!signal_here) HIP_TRY(hipEventRecord(r.ev_done, b->stream));
-        if (crowded) {
-            HIP_TRY(hipStreamWaitEvent(b->copy_stream, r.ev_done, 0));
-            BF_TRY(hand_over(b->copy_stream, r, b->res_total, big_fetch));
-            HIP_TRY(hipEventRecord(r.ev_copied, b->copy_stream));
-        } else {
-            // the rest - wait for this fit, mesh, joints, hand-over, on the second stream - is enqueued at the next entry point
-            // (bf_flush_tail): a bf_batch_stage_inputs that follows puts the next frame's inputs ahead of it
-            b->tail_k = k; b->tail_big = big_fetch;
-        }
-        r.copy_pending = true;
-        b->fetched = true;
-        b->steps_done += n_iters;
-        b->have_result = true;
-        return BF_OK;
-    }
-    if (notime) {
-        BF_TRY(enqueue_plain(b, n_iters, hd, io, reset, want_v, fetch, b->steps_done, nullptr));
-        b->fetched = fetch;
-        b->steps_done += n_iters;
-        b->have_result = want_v;
-        return BF_OK;
-    }
-    HIP_TRY(hipEventRecord(b->ev[0], b->stream));
-    if (!dense_losses && !dense) {
-        BF_TRY(enqueue_plain(b, n_iters, hd, io, reset, want_v, fetch, b->steps_done, b->ev));
-    } else {
-        if (reset) {
-            HIP_TRY(hipMemcpyAsync(b->params.p, b->params0.p, b->params.n * fb, hipMemcpyDefault, b->stream));   // (params0 may be pinned host memory: zero-copy staging)
-            HIP_TRY(hipMemsetAsync(b->adam_m.p, 0, b->adam_m.n * fb, b->stream));
-            HIP_TRY(hipMemsetAsync(b->adam_v.p, 0, b->adam_v.n * fb, b->stream));
-        }
-        if (dense_losses) {
-            BF_TRY(bf_fit_with_scans(b, n_iters, h, hd, io));
-            HIP_TRY(hipEventRecord(b->ev[1], b->stream));
-            if (want_v) {
-                BF_TRY(bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, b->ev[2], nullptr));
-            } else HIP_TRY(hipEventRecord(b->ev[2], b->stream));
-        } else {
-            // reference-literal schedule: every iteration evaluates the whole mesh (smplify.py:179-190)
-            for (int it = 0; it < n_iters; ++it) {
-                HIP_TRY(bf_fit_launch(&m->fit, &io, &hd, 1, 0, b->adam_tab.p, b->steps_done + it, b->fit_smem, b->stream, nullptr));
-                BF_TRY(bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, nullptr, b->stream, nullptr, nullptr));
-            }
-            HIP_TRY(hipEventRecord(b->ev[1], b->stream));
-            HIP_TRY(hipEventRecord(b->ev[2], b->stream));
-        }
-        if (fetch) BF_TRY(hand_over(b->stream, b->arena[b->cur], (want_v || dense) ? b->res_total : b->res_small, true));      // (always a copy command here)
-    }
-    b->fetched = fetch;
-    HIP_TRY(hipEventRecord(b->ev[3], b->stream));
-    b->ring_n += 1;
-    b->steps_done += n_iters;
-    b->timed = true;
-    b->have_result = want_v || dense;
     return BF_OK;
 }
 

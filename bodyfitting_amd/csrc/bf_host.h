@@ -143,6 +143,18 @@ struct DevBuf {
     ~DevBuf() { drop(); }
 };
 
+// A grow-only buffer used on one stream: replaced by a larger one once that stream has drained (nothing else uses it); contents undefined
+template <typename T>
+hipError_t bf_grow(hipStream_t s, DevBuf<T> &b, size_t count) {
+    if (b.n >= count && b.p) return hipSuccess;
+    if (b.p) {
+        hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return e;
+    }
+    b.release();
+    return b.alloc(count);
+}
+
 // vertex -> (face, corner) lists in the order compute_normal_torch (io_utils.py:406-428) adds a vertex's face normals up: corner by
 // corner, faces ascending.  start[nv + 1] = CSR offsets, adj[3 nf] = face * 4 + corner.  `faces` holds 3 nf indices inside [0, nv).
 // Shared by the SMPL+D stage (bf_fit_displacement) and bf_topo_create.
@@ -412,6 +424,7 @@ struct bf_batch {
     // (bf_lanes_drain), which hands the last lane fit back to the batch's own buffers.  in_cur >= 2 names input arena
     // (in_cur - 2) % 2 of lane (in_cur - 2) / 2.
     int n_lanes = 1;
+    int n_cus = 256;                    // compute units of the model's device (bf_batch_create)
     std::unique_ptr<BfLane[]> lanes;
     bool lanes_on = false;
     int lane_next = 0, lane_last = -1;
@@ -435,14 +448,32 @@ void bf_batch_unlink_scans(struct bf_batch *b);                                /
 // Shared between the host files (api.hip, dense_api.hip, mask_api.hip, scan_api.hip): ordinary C++ functions, hidden in the library like
 // everything include/bodyfit.h does not declare - a declaration here that differs from its definition fails to link.
 int bf_ensure_fit_image(struct bf_batch *b, FrameIO io, const HyperDev &hd);
-int bf_launch_mesh(bf_model *m, MeshScratch *scr, int n, const float *state_dev, float *vraw, float *vout, float *xpart, float *joints,
-                   float *joints_ori, hipStream_t stream, hipEvent_t after_mesh, float *vposed, float *jraw = nullptr,
-                   int *lmk_vid = nullptr, float *lmk_w = nullptr, float *dvzero = nullptr, bool *zeroed = nullptr, bool want_xpart = false,
-                   const MaskProj *mproj = nullptr, bool *projected = nullptr, int *door = nullptr, int door_target = 0,
-                   const MeshTab *tab = nullptr, hipEvent_t mesh_done = nullptr, bool *mesh_done_set = nullptr);
-// (dvzero: a [n][NV][3] buffer the forward pass should zero while it is at it - only the 1..15-frame kernel does, *zeroed says so;
-//  want_xpart: fill xpart although no joints are asked for here - the caller forms them itself;
-//  mproj: project the sampled vertices into the mask views as well - only the 1..15-frame kernel does, *projected says so)
+// One forward mesh pass of `n` frames from their pose states, and the joints pass behind it when joints, joints_ori or jraw is asked for.
+// Null / zero fields are left out of the pass.
+struct MeshPass {
+    // what is read
+    MeshScratch *scr = nullptr;         // the stream owner's scratch: the batched path (>= BF_MFMA_MIN_FRAMES frames) needs one
+    int n = 0;
+    const float *state = nullptr;
+    hipStream_t stream = nullptr;
+    const MeshTab *tab = nullptr;       // the sampled-first sub-model inside a dense loop without scans (null: the model's own table)
+    // what is written
+    float *vraw = nullptr, *vout = nullptr, *xpart = nullptr, *vposed = nullptr;
+    float *joints = nullptr, *joints_ori = nullptr, *jraw = nullptr;
+    int *lmk_vid = nullptr;
+    float *lmk_w = nullptr;
+    // what rides along
+    float *dvzero = nullptr;            // a [n][NV][3] buffer the forward pass should zero while it is at it - only the 1..15-frame kernel does, `zeroed` says so
+    bool want_xpart = false;            // fill xpart although no joints are asked for here - the caller forms them itself
+    const MaskProj *mproj = nullptr;    // project the sampled vertices into the mask views as well - only the 1..15-frame kernel does, `projected` says so
+    int *door = nullptr;                // the resident fit launch's doorbells the pass waits on, up to door_target
+    int door_target = 0;
+    hipEvent_t after_mesh = nullptr;    // recorded between the mesh and the joints pass
+    hipEvent_t mesh_done = nullptr;     // completes with the mesh dispatch itself where the kernel can carry it: `mesh_done_set` says so
+};
+struct MeshPassDone { bool zeroed = false, projected = false, mesh_done_set = false; };      // (cleared by bf_launch_mesh)
+int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &done);
+inline int bf_launch_mesh(bf_model *m, const MeshPass &p) { MeshPassDone unasked; return bf_launch_mesh(m, p, unasked); }
 int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDev &hd, FrameIO io);
 int bf_dense_loss_grad(bf_batch *b, const bf_hyper &h, const HyperDev &hd, FrameIO io);
 int bf_dense_iter_eval(bf_batch *b, const bf_hyper &h, const HyperDev &hd, FrameIO io, bool late, bool use_sub, const float *dverts_extra,

@@ -119,13 +119,14 @@ int launch_state_and_mesh(bf_batch *b, const HyperDev &hd) {
                        (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, b->state.p,
                        (const float *)b->params.p, (const float *)b->cscale.p, hd.cscale);
     HIP_TRY(hipGetLastError());
-    return bf_launch_mesh(m, &b->scratch, b->F, b->state.p, b->vraw.p, b->vout.p, nullptr, nullptr, nullptr, b->stream, nullptr, b->vposed.p);
+    MeshPass mesh;
+    mesh.scr = &b->scratch; mesh.n = b->F; mesh.state = b->state.p; mesh.stream = b->stream;
+    mesh.vraw = b->vraw.p; mesh.vout = b->vout.p; mesh.vposed = b->vposed.p;
+    return bf_launch_mesh(m, mesh);
 }
 
 // one dense iteration's forward + loss + reverse passes up to `ext` (everything except the fit kernel itself)
-// door / door_k: the persistent fit launch's doorbells and this pass's 1-based dense iteration (null / 0: fit launches per iteration)
-// sub: run the mesh passes on a sub-model (bf_model::Sub): the sampled-first one for fit loops without scans, the keypoint-only one for
-// the iterations before the dense losses switch on; null = the full model
+// (its options: DensePass below)
 // BF_DOOR_COHERENT=0: the kernels that wait for the resident fit launch read its pose states with plain loads (see bf_ld_state)
 // bf_mask_fold_set / BF_MASK_FOLD=gather: the silhouette's contour gradients through bf_mask_gather_kernel's ordered walk (rounds 2-4)
 // instead of the contour scan's fixed-point atomic sums (MaskIO::acc)
@@ -142,52 +143,67 @@ extern "C" int bf_mask_fold_set(int mode) {
 static bool fold_acc_on() { return bf_mask_fold_get() == BF_MASK_FOLD_SUMS; }
 static bool door_coherent() { const char *e = std::getenv("BF_DOOR_COHERENT"); return !(e && e[0] == '0'); }
 
-static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, bool late, float mask_weight, int *door = nullptr, int door_k = 0,
-                      const bf_model::Sub *sub = nullptr, bool timed = false, bool eval = false, const float *dv_extra = nullptr) {
+struct DensePass {
+    bool late = false;                      // past the switch-on: the scan and silhouette losses count
+    float mask_weight = 0.f;
+    int *door = nullptr;                    // the persistent fit launch's doorbells and this pass's 1-based dense iteration
+    int door_k = 0;                         // (null / 0: fit launches per iteration)
+    // run the mesh passes on a sub-model (bf_model::Sub): the sampled-first one for fit loops without scans, the keypoint-only one for
+    // the iterations before the dense losses switch on; null = the full model
+    const bf_model::Sub *sub = nullptr;
+    bool timed = false;                     // events between the kernel classes of this pass, for bf_batch_dense_timing
     // eval (bf_dense_iter_grad): dL/dvertices starts from zero whatever the model, the silhouette's loss value is summed, the
     // projection runs as a launch of its own (it leaves the binary term's partial sums), and dv_extra[F][NV][3] (device, full-model
     // vertex order) is added onto dL/dvertices just before the reverse mesh pass
+    bool eval = false;
+    const float *dv_extra = nullptr;
+};
+static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, const DensePass &o) {
     bf_model *m = b->m;
-    // (timed: events between the kernel classes of this pass, for bf_batch_dense_timing)
     auto mark = [&](int k) -> hipError_t {
-        if (!timed) return hipSuccess;
+        if (!o.timed) return hipSuccess;
         if (!b->ev_dense[k]) { hipError_t e = hipEventCreate(&b->ev_dense[k]); if (e != hipSuccess) return e; }
         return hipEventRecord(b->ev_dense[k], b->stream);
     };
     HIP_TRY(mark(0));
-    const MeshTab &Q = sub ? sub->mesh : m->mesh;
+    const MeshTab &Q = o.sub ? o.sub->mesh : m->mesh;
     const int F = b->F, nv = Q.nv, nblk = (nv + 255) / 256;
-    const bool scans = late && !b->scans.empty(), masks = late && b->has_masks, kp = m->kp_dense;
+    const bool scans = o.late && !b->scans.empty(), masks = o.late && b->has_masks, kp = m->kp_dense;
     const bool acc_mode = fold_acc_on();          // (read once per pass)
     if (masks) BF_TRY(bf_masks_finalize(b));
-    if (!door) {                     // (with the resident fit launch every state comes from it)
+    if (!o.door) {                     // (with the resident fit launch every state comes from it)
         hipLaunchKernelGGL(bf_pose_state_kernel, dim3(F), dim3(128), 0, b->stream, m->fit, (const float *)nullptr,
                            (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, b->state.p,
                            (const float *)b->params.p, (const float *)b->cscale.p, hd.cscale);
         HIP_TRY(hipGetLastError());
     }
-    bool zeroed = false;                      // dL/dvertices = 0 before the keypoint / silhouette kernels add into it
-    // (kp: the mesh pass leaves the extra-regressor partials in xpart; the joints are formed by the keypoint workgroup)
     MaskProj mp;
-    bool projected = false;
     if (masks) {
-        mp.on = 1; mp.K = b->mask; mp.K.weight = mask_weight; mp.proj = b->proj.p; mp.uvi = b->mk_uvi.p; mp.duvb = b->mk_duvb.p;
+        mp.on = 1; mp.K = b->mask; mp.K.weight = o.mask_weight; mp.proj = b->proj.p; mp.uvi = b->mk_uvi.p; mp.duvb = b->mk_duvb.p;
         mp.K.acc = (acc_mode && !scans) ? b->mk_acc.p : nullptr;      // (zeroed by the projection that precedes the contour scan)
-        if (sub) { mp.K.nv = nv; mp.K.sstride = 1; }
+        if (o.sub) { mp.K.nv = nv; mp.K.sstride = 1; }
     }
     const bool kp_aside = kp && !masks && scans && b->copy_stream;       // (see below)
-    const bool kp_door = kp_aside && door && b->kp_door_ok;              // the join of the second stream's keypoint workgroups: doorbell or event
-    bool forked = false;                                                  // ev_aux[0] completes with the mesh dispatch itself
+    const bool kp_door = kp_aside && o.door && b->kp_door_ok;              // the join of the second stream's keypoint workgroups: doorbell or event
     if (kp_aside && !b->ev_aux[0]) {
         HIP_TRY(hipEventCreateWithFlags(&b->ev_aux[0], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&b->ev_aux[1], hipEventDisableTiming));
     }
-    int rc = bf_launch_mesh(m, &b->scratch, F, b->state.p, b->vraw.p, b->vout.p, kp ? b->xpart.p : nullptr, nullptr, nullptr, b->stream, nullptr,
-                            b->vposed.p, nullptr, nullptr, nullptr, (kp || masks || eval) ? b->dvout.p : nullptr, &zeroed, kp, (masks && !eval) ? &mp : nullptr,
-                            &projected, door, (F * door_k) | (door_coherent() ? 0x40000000 : 0), sub ? &Q : nullptr,
-                            kp_aside ? b->ev_aux[0] : nullptr, &forked);
+    MeshPass mesh;
+    mesh.scr = &b->scratch; mesh.n = F; mesh.state = b->state.p; mesh.stream = b->stream;
+    if (o.sub) mesh.tab = &Q;
+    mesh.vraw = b->vraw.p; mesh.vout = b->vout.p; mesh.vposed = b->vposed.p;
+    // (kp: the mesh pass leaves the extra-regressor partials in xpart; the joints are formed by the keypoint workgroup)
+    if (kp) { mesh.xpart = b->xpart.p; mesh.want_xpart = true; }
+    if (kp || masks || o.eval) mesh.dvzero = b->dvout.p;      // dL/dvertices = 0 before the keypoint / silhouette kernels add into it
+    if (masks && !o.eval) mesh.mproj = &mp;
+    mesh.door = o.door; mesh.door_target = (F * o.door_k) | (door_coherent() ? 0x40000000 : 0);
+    if (kp_aside) mesh.mesh_done = b->ev_aux[0];            // (the fork completes with the mesh dispatch itself where it can)
+    MeshPassDone did;
+    int rc = bf_launch_mesh(m, mesh, did);
     if (rc) return rc;
-    if ((kp || masks || eval) && !zeroed) HIP_TRY(hipMemsetAsync(b->dvout.p, 0, b->dvout.n * sizeof(float), b->stream));
+    const bool zeroed = did.zeroed, projected = did.projected, forked = did.mesh_done_set;
+    if ((kp || masks || o.eval) && !zeroed) HIP_TRY(hipMemsetAsync(b->dvout.p, 0, b->dvout.n * sizeof(float), b->stream));
     HIP_TRY(mark(1));                         // [0,1] pose state (when not resident) + forward mesh pass
     // The dense keypoint loss and the closest-point search both only read the mesh: with scans attached the keypoint workgroups (one
     // per frame, a ~25 us latency chain) run on the batch's second stream UNDER the search - that stream is idle during a dense loop
@@ -205,15 +221,15 @@ static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, bool l
         //  The doorbell join needs the second stream's kernels to RUN while bf_pc_grad_kernel's workgroups spin on the batch stream: it is
         //  used only when ensure_fit_stream's second probe has shown that pair of streams side by side (kp_door_ok; BF_KP_JOIN=event
         //  forces the stream-level join) - the event join cannot fail that way.
-        rc = launch_kp(b, h, sub, b->copy_stream, kp_door ? door : nullptr);
+        rc = launch_kp(b, h, o.sub, b->copy_stream, kp_door ? o.door : nullptr);
         if (rc) return rc;
         if (kp_door) b->kp_tickets += F;
         else HIP_TRY(hipEventRecord(b->ev_aux[1], b->copy_stream));
-    } else if (kp && !masks) { rc = launch_kp(b, h, sub); if (rc) return rc; }
+    } else if (kp && !masks) { rc = launch_kp(b, h, o.sub); if (rc) return rc; }
     // with a scan as well, bf_pc_grad_kernel adds onto (keypoints + silhouette): keep that order of additions
     const bool fold_views = masks && !scans;
     const bool fold_acc = fold_views && acc_mode;
-    if (masks) { rc = launch_mask_kernels(b, mask_weight, eval, !fold_views, kp ? &h : nullptr, projected, sub, fold_acc); if (rc) return rc; }
+    if (masks) { rc = launch_mask_kernels(b, o.mask_weight, o.eval, !fold_views, kp ? &h : nullptr, projected, o.sub, fold_acc); if (rc) return rc; }
     HIP_TRY(mark(2));                         // [1,2] keypoint loss (on this stream) and / or the silhouette kernels
     if (scans) {
         bf_nearest_launch(dim3((nv + 3) / 4, F), b->stream, (const ScanDev *)b->scan_dev.p,
@@ -225,12 +241,12 @@ static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, bool l
         if (kp_aside && !kp_door) HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_aux[1], 0));
         hipLaunchKernelGGL(bf_pc_grad_kernel, dim3(nblk, F), dim3(256), 0, b->stream, (const float *)b->vout.p,
                            (const float *)b->cpts.p, nv, (const float *)b->pc_partial.p, (const float *)b->pc_weight.p,
-                           b->dvout.p, b->pc_loss.p, (kp || masks) ? 1 : 0, kp_door ? door : (int *)nullptr, b->kp_tickets);
+                           b->dvout.p, b->pc_loss.p, (kp || masks) ? 1 : 0, kp_door ? o.door : (int *)nullptr, b->kp_tickets);
     }
     if (!scans) HIP_TRY(mark(3));
-    if (dv_extra) {
-        hipLaunchKernelGGL(bf_dv_add_kernel, dim3((nv * 3 + 255) / 256, F), dim3(256), 0, b->stream, b->dvout.p, dv_extra,
-                           sub ? (const int *)sub->verts.p : (const int *)nullptr, nv, m->nv);
+    if (o.dv_extra) {
+        hipLaunchKernelGGL(bf_dv_add_kernel, dim3((nv * 3 + 255) / 256, F), dim3(256), 0, b->stream, b->dvout.p, o.dv_extra,
+                           o.sub ? (const int *)o.sub->verts.p : (const int *)nullptr, nv, m->nv);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(mark(4));                         // [3,4] point-cloud loss + gradient (+ the join with the keypoint workgroups of the second stream)
@@ -239,17 +255,17 @@ static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, bool l
     {
         MaskFold fold = {};
         if (fold_acc) { fold.acc = b->mk_acc.p; fold.uvi = b->mk_uvi.p; fold.duvb = b->mk_duvb.p; fold.proj = b->proj.p; fold.view_index = b->mask.view_index; fold.n_views = b->V; }
-        const int e = bf_mesh_bwd_multi_launch(&Q, sub ? sub->posedirsT.p : m->posedirsT.p, b->state.p, F, b->dvout.p, b->vposed.p, b->vraw.p, b->ext_part.p,
-                                               b->stream, (fold_views && !fold_acc) ? (const float *)b->mk_gpart.p : nullptr, b->mask.n_masks, b->mask.ns, sub ? 1 : 4,
-                                               (sub && sub == &m->sub_kp) ? Q.n_tiles : m->mesh.n_tiles, &part_rows, fold_acc ? &fold : nullptr);      // (keypoint-only sub-model: no tile split - a batch of 8 and its single frames keep the same partial sums)
+        const int e = bf_mesh_bwd_multi_launch(&Q, o.sub ? o.sub->posedirsT.p : m->posedirsT.p, b->state.p, F, b->dvout.p, b->vposed.p, b->vraw.p, b->ext_part.p,
+                                               b->stream, (fold_views && !fold_acc) ? (const float *)b->mk_gpart.p : nullptr, b->mask.n_masks, b->mask.ns, o.sub ? 1 : 4,
+                                               (o.sub && o.sub == &m->sub_kp) ? Q.n_tiles : m->mesh.n_tiles, &part_rows, fold_acc ? &fold : nullptr);      // (keypoint-only sub-model: no tile split - a batch of 8 and its single frames keep the same partial sums)
         if (e) return fail(BF_ERR_HIP, std::string("bf_mesh_bwd_multi_kernel: ") + hipGetErrorString((hipError_t)e));
     }
     HIP_TRY(mark(5));                         // [4,5] reverse mesh pass
     hipLaunchKernelGGL(bf_ext_reduce_kernel, dim3((EXT + BF_RED_COLS - 1) / BF_RED_COLS, F), dim3(8 * BF_RED_COLS), 0, b->stream,
-                       (const float *)b->ext_part.p, part_rows, EXT, b->ext.p, EXT + m->nj * 3 + 4, door, door_k);
+                       (const float *)b->ext_part.p, part_rows, EXT, b->ext.p, EXT + m->nj * 3 + 4, o.door, o.door_k);
     HIP_TRY(hipGetLastError());
     HIP_TRY(mark(6));                         // [5,6] reduction of the partial blocks (rings the resident fit launch)
-    if (timed) b->dense_timed = true;
+    if (o.timed) b->dense_timed = true;
     return BF_OK;
 }
 
@@ -374,6 +390,14 @@ static void dense_subs(bf_batch *b, const bf_model::Sub *&sub_early, const bf_mo
     sub_early = (sub_ok && sub_kp_ok && m->sub_kp.on && (!b->has_masks || sub_kp_masks)) ? &m->sub_kp : sub_late;
 }
 
+// a call that fails while the fit launch is resident: let everybody through (BF_DOOR_ERR) and wait for the launch, so that it is not
+// left waiting for bells that will not ring
+static void door_release(bf_batch *b) {
+    const int one = 1;
+    (void)hipMemcpy(b->door.p + BF_DOOR_ERR, &one, sizeof one, hipMemcpyHostToDevice);
+    (void)hipStreamSynchronize(b->fit_stream);
+}
+
 // the loop of smplify.py:177-213 when a dense loss is present (use_mask, use_mesh, or the SMPL-X keypoints
 // with hands + face): iterations that need no dense loss run as one persistent launch; every other iteration
 // is state -> mesh -> losses -> reverse mesh pass -> one fit-kernel iteration (smplify.py:197-210).
@@ -392,9 +416,14 @@ int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDe
     // per iteration, with the pose state from bf_pose_state_kernel every time.
     const bf_model::Sub *sub_early = nullptr, *sub_late = nullptr;
     dense_subs(b, sub_early, sub_late);
-    auto sub_of = [&](int it) { return it > thr ? sub_late : sub_early; };
     const bool door_ok = [] { const char *e = std::getenv("BF_DENSE_PERSISTENT"); return !(e && e[0] == '0'); }();
     const int n_dense = n_iters - n_plain;
+    DensePass pass;
+    pass.mask_weight = 5.0f;                                            // smplify.py:210
+    auto pass_of = [&](int it) -> const DensePass & {
+        pass.late = it > thr; pass.sub = it > thr ? sub_late : sub_early; pass.timed = b->dense_timing && it == n_iters - 1;
+        return pass;
+    };
     if (door_ok && n_dense >= 1 && F < BF_MFMA_MIN_FRAMES) { rc = ensure_fit_stream(b, io, hd); if (rc) return rc; }
     if (n_dense >= 1) b->dense_resident = (door_ok && F < BF_MFMA_MIN_FRAMES && b->door_usable) ? 1 : 0;
     if (door_ok && n_dense >= 1 && F < BF_MFMA_MIN_FRAMES && b->door_usable) {
@@ -414,27 +443,21 @@ int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDe
                 const auto t0 = std::chrono::steady_clock::now();
                 while (*(volatile int *)b->h_resident < F) {
                     if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) {
-                        const int one = 1;      // let everybody through, then fail the call
-                        (void)hipMemcpy(b->door.p + BF_DOOR_ERR, &one, sizeof one, hipMemcpyHostToDevice);
-                        (void)hipStreamSynchronize(b->fit_stream);
+                        door_release(b);
                         return fail(BF_ERR_HIP, "dense schedule: the persistent fit launch did not start");
                     }
                 }
             }
-            rc = dense_pass(b, h, hd, it > thr, 5.0f, b->door.p, it - n_plain + 1, sub_of(it), b->dense_timing && it == n_iters - 1);
-            if (rc) {               // do not leave the resident launch waiting for bells that will not ring
-                const int one = 1;
-                (void)hipMemcpy(b->door.p + BF_DOOR_ERR, &one, sizeof one, hipMemcpyHostToDevice);
-                (void)hipStreamSynchronize(b->fit_stream);
-                return rc;
-            }
+            pass.door = b->door.p; pass.door_k = it - n_plain + 1;
+            rc = dense_pass(b, h, hd, pass_of(it));
+            if (rc) { door_release(b); return rc; }
         }
         HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_door[1], 0));       // the last iteration's step, terms and state
         HIP_TRY(hipMemcpyAsync(b->h_door_err, b->door.p + BF_DOOR_ERR, sizeof(int), hipMemcpyDeviceToHost, b->stream));
         return BF_OK;
     }
     for (int it = n_plain; it < n_iters; ++it) {
-        rc = dense_pass(b, h, hd, it > thr, 5.0f, nullptr, 0, sub_of(it), b->dense_timing && it == n_iters - 1);                    // smplify.py:210
+        rc = dense_pass(b, h, hd, pass_of(it));
         if (rc) return rc;
         FrameIO io2 = io;
         io2.ext = b->ext.p;
@@ -463,7 +486,9 @@ int bf_batch_dense_timing(bf_batch *b, int enable, float ms[6]) {
 int bf_dense_loss_grad(bf_batch *b, const bf_hyper &h, const HyperDev &hd, FrameIO io) {
     int rc = bf_ensure_dense_buffers(b);
     if (rc) return rc;
-    rc = dense_pass(b, h, hd, false, 5.0f);
+    DensePass pass;
+    pass.mask_weight = 5.0f;
+    rc = dense_pass(b, h, hd, pass);
     if (rc) return rc;
     io.ext = b->ext.p;
     HIP_TRY(bf_fit_launch(&b->m->fit, &io, &hd, 1, 1, b->adam_tab.p, 0, b->fit_smem, b->stream, nullptr));
@@ -494,7 +519,10 @@ int bf_dense_iter_eval(bf_batch *b, const bf_hyper &h, const HyperDev &hd, Frame
         HIP_TRY(faces_kept.alloc(b->cface.n));
         HIP_TRY(hipMemcpyAsync(faces_kept.p, b->cface.p, b->cface.n * sizeof(int), hipMemcpyDeviceToDevice, b->stream));
     }
-    rc = dense_pass(b, h, hd, late, 5.0f, nullptr, 0, sub, false, true, extra.p);
+    DensePass pass;
+    pass.late = late; pass.mask_weight = 5.0f; pass.sub = sub;
+    pass.eval = true; pass.dv_extra = extra.p;
+    rc = dense_pass(b, h, hd, pass);
     if (rc) return rc;
     if (scans) {
         if (warm) HIP_TRY(hipMemcpyAsync(b->cface.p, faces_kept.p, b->cface.n * sizeof(int), hipMemcpyDeviceToDevice, b->stream));

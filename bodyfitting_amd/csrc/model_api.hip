@@ -480,8 +480,10 @@ int bf_model_forward(bf_model *m, int n, const float *params, float *vertices, f
     hipLaunchKernelGGL(bf_pose_state_kernel, dim3(n), dim3(128), 0, 0, m->fit, (const float *)nullptr, (const float *)nullptr,
                        (const float *)nullptr, (const float *)nullptr, d_state.p, (const float *)d_p.p, (const float *)nullptr, 1.0f);
     HIP_TRY(hipGetLastError());
-    int rc = bf_launch_mesh(m, &scratch, n, d_state.p, d_vraw.p, nullptr, d_xp.p, d_j.p, nullptr, 0, nullptr, nullptr);
-    if (rc) return rc;
+    MeshPass mesh;
+    mesh.scr = &scratch; mesh.n = n; mesh.state = d_state.p;
+    mesh.vraw = d_vraw.p; mesh.xpart = d_xp.p; mesh.joints = d_j.p;
+    BF_TRY(bf_launch_mesh(m, mesh));
     HIP_TRY(hipDeviceSynchronize());
     if (vertices) HIP_TRY(hipMemcpy(vertices, d_vraw.p, d_vraw.n * sizeof(float), hipMemcpyDeviceToHost));
     if (joints) HIP_TRY(hipMemcpy(joints, d_j.p, d_j.n * sizeof(float), hipMemcpyDeviceToHost));

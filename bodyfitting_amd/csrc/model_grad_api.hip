@@ -62,7 +62,11 @@ struct ModelPass {
         hipLaunchKernelGGL(bf_pose_state_kernel, dim3(n), dim3(128), 0, 0, m->fit, beta, th_root, th_rest, (const float *)nullptr, state.p,
                            (const float *)nullptr, (const float *)nullptr, 1.0f);
         HIP_TRY(hipGetLastError());
-        return bf_launch_mesh(m, &scratch, n, state.p, vraw.p, nullptr, xpart.p, joints.p, nullptr, 0, nullptr, vposed.p, jraw.p, lmk_vid.p, lmk_w.p);
+        MeshPass mesh;
+        mesh.scr = &scratch; mesh.n = n; mesh.state = state.p;
+        mesh.vraw = vraw.p; mesh.xpart = xpart.p; mesh.vposed = vposed.p;
+        mesh.joints = joints.p; mesh.jraw = jraw.p; mesh.lmk_vid = lmk_vid.p; mesh.lmk_w = lmk_w.p;
+        return bf_launch_mesh(m, mesh);
     }
 
     // After forward(..., true): the cotangents on the device (any may be null = zero; ddirect covers the first n_direct joints) ->

@@ -80,17 +80,17 @@ static int op_reserve(bf_openpose *op, int n, int H, int W) {
     }
     const size_t pix = (size_t)n * H * W;
     hipStream_t s = op->stream;
-    HIP_TRY(op_ensure(s, op->img, pix * 3));
-    HIP_TRY(op_ensure(s, op->inp, act / 16));
-    for (int i = 0; i < 2; ++i) HIP_TRY(op_ensure(s, op->act[i], act));
-    HIP_TRY(op_ensure(s, op->cat, cat));
-    for (int i = 0; i < 2; ++i) HIP_TRY(op_ensure(s, op->br[i], cat / OP_CAT * 1024));
-    HIP_TRY(op_ensure(s, op->out, out));
-    HIP_TRY(op_ensure(s, op->heat, pix * OP_NHEAT));
-    HIP_TRY(op_ensure(s, op->paf, pix * OP_NPAF));
-    HIP_TRY(op_ensure(s, op->tmp, pix * OP_NPART));
-    HIP_TRY(op_ensure(s, op->bl, pix * OP_NPART));
-    HIP_TRY(op_ensure(s, op->counts, (size_t)n));
+    HIP_TRY(bf_grow(s, op->img, pix * 3));
+    HIP_TRY(bf_grow(s, op->inp, act / 16));
+    for (int i = 0; i < 2; ++i) HIP_TRY(bf_grow(s, op->act[i], act));
+    HIP_TRY(bf_grow(s, op->cat, cat));
+    for (int i = 0; i < 2; ++i) HIP_TRY(bf_grow(s, op->br[i], cat / OP_CAT * 1024));
+    HIP_TRY(bf_grow(s, op->out, out));
+    HIP_TRY(bf_grow(s, op->heat, pix * OP_NHEAT));
+    HIP_TRY(bf_grow(s, op->paf, pix * OP_NPAF));
+    HIP_TRY(bf_grow(s, op->tmp, pix * OP_NPART));
+    HIP_TRY(bf_grow(s, op->bl, pix * OP_NPART));
+    HIP_TRY(bf_grow(s, op->counts, (size_t)n));
     return BF_OK;
 }
 
@@ -290,8 +290,8 @@ int bf_openpose_peaks(bf_openpose *op, int n, int cap, double *blurred, int *cou
     HIP_TRY(hipSetDevice(op->device));
     hipStream_t s = op->stream;
     const int H = op->map_h, W = op->map_w;
-    HIP_TRY(op_ensure(s, op->peaks, (size_t)n * cap * 3));
-    HIP_TRY(op_ensure(s, op->scores, (size_t)n * cap));
+    HIP_TRY(bf_grow(s, op->peaks, (size_t)n * cap * 3));
+    HIP_TRY(bf_grow(s, op->scores, (size_t)n * cap));
     const long long total = (long long)n * H * W * OP_NPART;
     hipLaunchKernelGGL(bf_op_gauss_kernel, dim3(op_blocks(total)), dim3(256), 0, s, n, H, W, 0, OP_NHEAT, (const double *)op->heat.p, op->tmp.p);
     HIP_TRY(hipGetLastError());
@@ -323,9 +323,9 @@ int bf_openpose_pairs(bf_openpose *op, int view, int npairs, const int *jobs, do
     }
     HIP_TRY(hipSetDevice(op->device));
     hipStream_t s = op->stream;
-    HIP_TRY(op_ensure(s, op->jobs, (size_t)npairs * 5));
-    HIP_TRY(op_ensure(s, op->jscore, (size_t)npairs));
-    HIP_TRY(op_ensure(s, op->jcnt, (size_t)npairs));
+    HIP_TRY(bf_grow(s, op->jobs, (size_t)npairs * 5));
+    HIP_TRY(bf_grow(s, op->jscore, (size_t)npairs));
+    HIP_TRY(bf_grow(s, op->jcnt, (size_t)npairs));
     HIP_TRY(hipMemcpyAsync(op->jobs.p, jobs, (size_t)npairs * 5 * sizeof(int), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(bf_op_pairs_kernel, dim3((npairs + 63) / 64), dim3(64), 0, s, npairs, H, W,
                        (const double *)(op->paf.p + (size_t)view * H * W * OP_NPAF), (const int *)op->jobs.p, op->jscore.p, op->jcnt.p);

@@ -180,14 +180,14 @@ static int oh_run(bf_openpose_hand *h, int n_views, int H, int W, const uint8_t 
         q = std::max(q, k * (c.Hp / 8) * (c.Wp / 8));
         for (size_t j = 0; j < k; ++j) up = std::max(up, (size_t)desc[c.desc + j].rh * desc[c.desc + j].rw * OH_NMAP);
     }
-    if (bgr) HIP_TRY(op_ensure(s, h->img, (size_t)n_views * H * W * 3));
-    HIP_TRY(op_ensure(s, h->inp, act / 16));
-    for (int i = 0; i < 2; ++i) HIP_TRY(op_ensure(s, h->act[i], act));
-    HIP_TRY(op_ensure(s, h->cat, q * OH_CAT));
-    for (int i = 0; i < 2; ++i) HIP_TRY(op_ensure(s, h->br[i], q * 512));
-    HIP_TRY(op_ensure(s, h->out, q * OH_NMAP));
-    HIP_TRY(op_ensure(s, h->heat, (size_t)total * OH_NMAP));
-    HIP_TRY(op_ensure(s, h->desc, desc.size()));
+    if (bgr) HIP_TRY(bf_grow(s, h->img, (size_t)n_views * H * W * 3));
+    HIP_TRY(bf_grow(s, h->inp, act / 16));
+    for (int i = 0; i < 2; ++i) HIP_TRY(bf_grow(s, h->act[i], act));
+    HIP_TRY(bf_grow(s, h->cat, q * OH_CAT));
+    for (int i = 0; i < 2; ++i) HIP_TRY(bf_grow(s, h->br[i], q * 512));
+    HIP_TRY(bf_grow(s, h->out, q * OH_NMAP));
+    HIP_TRY(bf_grow(s, h->heat, (size_t)total * OH_NMAP));
+    HIP_TRY(bf_grow(s, h->desc, desc.size()));
     h->resident.clear(); h->resident_px = 0;
     if (bgr) HIP_TRY(hipMemcpyAsync(h->img.p, bgr, (size_t)n_views * H * W * 3, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(h->desc.p, desc.data(), desc.size() * sizeof(OhBox), hipMemcpyHostToDevice, s));
@@ -318,12 +318,12 @@ int bf_openpose_hand_peaks(bf_openpose_hand *h, int n, double *blurred, int *pea
     const long long total = h->resident_px;
     long long most = 0;
     for (const OhBox &d : h->resident) most = std::max(most, (long long)d.bh * d.bw);
-    HIP_TRY(op_ensure(s, h->res_desc, (size_t)n));
-    HIP_TRY(op_ensure(s, h->tmp, (size_t)total * OH_NPART));
-    HIP_TRY(op_ensure(s, h->bl, (size_t)total * OH_NPART));
-    HIP_TRY(op_ensure(s, h->peaks, (size_t)n * OH_NPART * 2));
-    HIP_TRY(op_ensure(s, h->scores, (size_t)n * OH_NPART));
-    HIP_TRY(op_ensure(s, h->found, (size_t)n * OH_NPART));
+    HIP_TRY(bf_grow(s, h->res_desc, (size_t)n));
+    HIP_TRY(bf_grow(s, h->tmp, (size_t)total * OH_NPART));
+    HIP_TRY(bf_grow(s, h->bl, (size_t)total * OH_NPART));
+    HIP_TRY(bf_grow(s, h->peaks, (size_t)n * OH_NPART * 2));
+    HIP_TRY(bf_grow(s, h->scores, (size_t)n * OH_NPART));
+    HIP_TRY(bf_grow(s, h->found, (size_t)n * OH_NPART));
     HIP_TRY(hipMemcpyAsync(h->res_desc.p, h->resident.data(), (size_t)n * sizeof(OhBox), hipMemcpyHostToDevice, s));
     const dim3 grid(op_blocks(most * OH_NPART), n);
     hipLaunchKernelGGL(bf_oh_gauss_kernel, grid, dim3(256), 0, s, 0, OH_NMAP, (const OhBox *)h->res_desc.p, (const double *)h->heat.p, h->tmp.p);
@@ -339,8 +339,8 @@ int bf_openpose_hand_peaks(bf_openpose_hand *h, int n, double *blurred, int *pea
             if (j > i && (size_t)(cpx + p) * OH_NPART * 32 > OH_PICK_SCRATCH) break;
             cpx += p; ++j;
         }
-        HIP_TRY(op_ensure(s, h->iscr, (size_t)cpx * OH_NPART * 4));
-        HIP_TRY(op_ensure(s, h->dscr, (size_t)cpx * OH_NPART * 2));
+        HIP_TRY(bf_grow(s, h->iscr, (size_t)cpx * OH_NPART * 4));
+        HIP_TRY(bf_grow(s, h->dscr, (size_t)cpx * OH_NPART * 2));
         hipLaunchKernelGGL(bf_oh_pick_kernel, dim3(OH_NPART, j - i), dim3(256), 0, s, (const OhBox *)(h->res_desc.p + i), h->resident[i].px,
                            (const double *)h->bl.p, (const double *)h->heat.p, h->iscr.p, h->dscr.p, h->peaks.p + (size_t)i * OH_NPART * 2,
                            h->scores.p + (size_t)i * OH_NPART, h->found.p + (size_t)i * OH_NPART);

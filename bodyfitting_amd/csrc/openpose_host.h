@@ -1,5 +1,5 @@
 // Host-side pieces shared by the OpenPose body (openpose_api.hip) and hand (openpose_hand_api.hip) estimators: the convolution
-// descriptor of openpose_kernels.hip, a packed layer, the launch of one or two convolutions, and the grow-only device buffers.
+// descriptor of openpose_kernels.hip, a packed layer, the launch of one or two convolutions.  (Their grow-only device buffers: bf_grow, bf_host.h.)
 #pragma once
 #include "bf_host.h"
 #include "openpose_kernels.h"
@@ -45,12 +45,3 @@ inline int launch_pool(hipStream_t s, int n, int H, int W, int C, const float *x
 }
 
 inline unsigned op_blocks(long long total) { return (unsigned)((total + 255) / 256); }
-
-template <typename T>
-hipError_t op_ensure(hipStream_t s, DevBuf<T> &b, size_t count) {
-    if (b.n >= count && b.p) return hipSuccess;
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    b.release();
-    return b.alloc(count);
-}

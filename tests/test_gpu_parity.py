@@ -363,6 +363,34 @@ def test_back_to_back_fits_hand_their_tail_to_the_second_stream(dev_model, smpl_
     r.close(); b.close()
 
 
+@pytest.mark.parametrize("route", ["crowded", "one_lane_by_frame_count"])
+def test_back_to_back_fits_of_a_batch_too_large_for_lanes(dev_model, smpl_model, route):
+    """A batch gets fit lanes unless compute units / frames < 2, so only a batch of more than half the machine's CUs reaches the
+    single-stream tail-aside routes in process: with a frame per CU ("crowded") the mesh stays on the batch stream and only the copy
+    goes aside; with CUs // 2 + 1 frames the whole tail is deferred to the second stream, on the >= 128-frame GEMM mesh path.  Whichever
+    call is read back, and through whichever getter, the results are those of one plain call."""
+    from bodyfitting_amd import _lib
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n_frames = cus if route == "crowded" else cus // 2 + 1
+    probs = [S.make_problem(smpl_model, frame=f, n_views=2) for f in range(4)]
+    probs = [probs[f % 4] for f in range(n_frames)]
+    r, b = _batch(dev_model, probs), _batch(dev_model, probs)
+    r.fit(4, flags=_lib.FIT_FETCH)
+    want_p, want_r = r.get_params(), r.get_result()
+    fast = _lib.FIT_FETCH | _lib.FIT_RESET | _lib.FIT_NOTIME
+    b.fit(4, flags=fast)
+    b.fit(4, flags=fast)
+    prev = b.get_previous()                                                  # the first fit's, under the second
+    b.fit(4, flags=fast)
+    np.testing.assert_array_equal(prev[0], want_p)
+    for x, y in zip(prev[1:], want_r):
+        np.testing.assert_array_equal(x, y)
+    np.testing.assert_array_equal(b.get_params(), want_p)
+    for x, y in zip(b.get_result(), want_r):
+        np.testing.assert_array_equal(x, y)
+    r.close(); b.close()
+
+
 def test_more_than_48_views_streams_the_rest(dev_model, smpl_model, gmm_bufs):
     """Views past the 48 staged in LDS are streamed from global memory by the projection phase: 60 views against the
     fp64 oracle (gradient) and the fp64 analytic loop (a short fit)."""
