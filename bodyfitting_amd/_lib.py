@@ -143,6 +143,10 @@ SIGNATURES = {
     "bf_batch_stage_masks": (C.c_int, [_VP, C.c_int, _IP, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int]),
     "bf_extract_contours": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), _IP, _FP, C.c_int]),
     "bf_batch_mask_loss": (C.c_int, [_VP, C.POINTER(Hyper), _FP, _FP]),
+    "bf_silhouette_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), _IP, _FP, C.c_int, C.POINTER(_VP)]),
+    "bf_silhouette_destroy": (None, [_VP]),
+    "bf_silhouette_contours": (C.c_int, [_VP, _IP, _FP]),
+    "bf_silhouette_loss": (C.c_int, [_VP, C.c_int, C.c_int, _FP, _FP, _FP, C.c_float, C.c_float, C.c_int, _FP, _FP, _FP]),
     "bf_fit_displacement": (C.c_int, [_VP, C.c_int, C.POINTER(Hyper)]),
     "bf_batch_get_displacement": (C.c_int, [_VP, _FP]),
     "bf_batch_last_timing": (C.c_int, [_VP, _FP]),

@@ -480,6 +480,9 @@ int bf_dense_iter_eval(bf_batch *b, const bf_hyper &h, const HyperDev &hd, Frame
                        float *terms6);
 int bf_ensure_dense_buffers(bf_batch *b);
 int bf_ensure_posedirsT_locked(bf_model *m, hipStream_t stream);   // (caller holds m->lazy) posedirsT built on first use
+// contours of n binary masks on the device (mask_api.hip): shared by bf_extract_contours and bf_silhouette_create
+int bf_contours_on_device(const unsigned char *d_bin, int n, int H, int W, int select, std::vector<int> &counts, std::vector<int> &half,
+                          DevBuf<float> &d_xy, int &cap);
 int bf_masks_finalize(bf_batch *b);      // no-op unless a deferred bf_batch_set_masks is pending
 void bf_masks_commit(bf_batch *b);       // no-op unless bf_batch_stage_masks has staged the next frame's silhouettes
 HyperDev bf_to_dev(const bf_hyper &h);

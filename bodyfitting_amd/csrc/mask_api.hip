@@ -10,7 +10,7 @@
 // Contours of n binary masks on the device (bf_contour_kernel).  d_bin[n][H][W] -> counts (host), d_xy[n][2][cap][2] (device slab;
 // half[i] says which half holds mask i's contour).
 // The slab is grown and the kernel re-run when a contour is longer than the first guess.
-static int contours_on_device(const unsigned char *d_bin, int n, int H, int W, int select, std::vector<int> &counts, std::vector<int> &half,
+int bf_contours_on_device(const unsigned char *d_bin, int n, int H, int W, int select, std::vector<int> &counts, std::vector<int> &half,
                               DevBuf<float> &d_xy, int &cap) {
     const int wpr = (W + 31) / 32;
     const size_t plane_bytes = (size_t)3 * H * wpr * sizeof(unsigned);
@@ -53,7 +53,7 @@ int bf_extract_contours(int device, int n, int H, int W, const uint8_t *masks, i
     std::vector<int> cnt, half;
     DevBuf<float> d_xy;
     int cap = 0;
-    int rc = contours_on_device(d_bin.p, n, H, W, select, cnt, half, d_xy, cap);
+    int rc = bf_contours_on_device(d_bin.p, n, H, W, select, cnt, half, d_xy, cap);
     if (rc) return rc;
     size_t o = 0;
     for (int i = 0; i < n; ++i) {

@@ -17,10 +17,15 @@ inputs' device, differentiable once; numpy in -> a float.  The two scan losses o
 keeps its last query's answer, so the second one does not search again.  They take this project's MeshGridSearcher, arrays and
 tensors; anything else raises NotImplementedError (SMPLify's fused stage is the other path), every other refusal is a ValueError.
 
-The silhouette loss, the contours and the chamfer loss run fused inside `SMPLify` only; their stand-alone versions raise
-NotImplementedError.
+The silhouette term of that loop (smplify.py:144,198) is here as well: `extract_countours` follows the masks' external borders on
+the GPU and keeps masks and contours there (a `native.Silhouette`, remembered per masks object and GPU), and `multview_mask_loss`
+evaluates the loss on the vertices the caller holds as ONE bf_silhouette_loss call - three launches - whose gradient goes to
+`smpl_verts`.  The chamfer loss (called nowhere in the reference) runs nowhere: its stand-alone version raises NotImplementedError.
 """
 from __future__ import annotations
+
+import hashlib
+import weakref
 
 import numpy as np
 
@@ -91,8 +96,6 @@ def _fused_only(name):
     return stub
 
 
-multview_mask_loss = _fused_only("multview_mask_loss")
-extract_countours = _fused_only("extract_countours")
 point_cloud_loss_chamfer_naive = _fused_only("point_cloud_loss_chamfer_naive")
 
 
@@ -100,9 +103,10 @@ point_cloud_loss_chamfer_naive = _fused_only("point_cloud_loss_chamfer_naive")
 # the scan term and the SMPL+D stage's losses (loss.py:233-242,260-288)
 # ----------------------------------------------------------------------------------------------------------------------------
 
-def _scalar_loss(who, x, call):
+def _scalar_loss(who, x, call, plus_zero=False):
     """`call(array, want_grad)` -> (value, gradient for cotangent 1 or None): ONE native call per evaluation - the gradient comes
-    back with the value when `x` asks for one, and the backward only scales it.  -> a 0-dim tensor on x's device, or a float."""
+    back with the value when `x` asks for one, and the backward only scales it.  -> a 0-dim tensor on x's device, or a float.
+    plus_zero: the scaled gradient's zeros are +0 whatever the cotangent's sign (0 * -2.5 is -0)."""
     if not _is_tensor(x):
         return float(call(x, False)[0])
     import torch
@@ -117,7 +121,8 @@ def _scalar_loss(who, x, call):
     def vjp(arrays, cotangents):
         if kept[0] is None:
             raise RuntimeError(f"{who}: no gradient was computed with the forward")
-        return (kept[0] * np.asarray(cotangents[0]).reshape(-1)[0],)
+        scaled = kept[0] * np.asarray(cotangents[0]).reshape(-1)[0]
+        return (scaled + 0.0 if plus_zero else scaled,)
 
     return _autograd.apply(forward, vjp, (x,))[0].reshape(())
 
@@ -199,6 +204,185 @@ def normal_laplacian_smoothness(norms, faces):
         return native.normal_laplacian(topo, a.reshape(-1, 3), want_grad=want_grad)
 
     return _scalar_loss(who, norms, call)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the silhouette term (loss.py:73-130)
+# ----------------------------------------------------------------------------------------------------------------------------
+
+_SILHOUETTES = {}           # key -> dict(ref, version, sil, contours (host [C,2] arrays), given (what extract_countours returned))
+_SILHOUETTE_SLOTS = 4       # mask sets kept at a time; the oldest goes first
+MASK_STRIDE = 4             # loss.py:99: every 4th vertex
+
+
+def _items(x):
+    return list(x) if isinstance(x, (list, tuple)) else [x]
+
+
+def _require_arrays(who, name, x):
+    """an array, a tensor or a list of them; anything else: NotImplementedError (what the stand-alone stubs raised for anything)"""
+    if isinstance(x, (list, tuple)):
+        for it in x:
+            _normals.require_array("smplify.loss." + who, f"an item of {name}", it)
+    else:
+        _normals.require_array("smplify.loss." + who, name, x)
+
+
+def _masks_host(who, masks):
+    """-> uint8 [M,H,W] of 0 / 1"""
+    host = masks.detach().cpu().numpy() if _is_tensor(masks) else np.asarray(masks)
+    if host.ndim == 2:
+        host = host[None]
+    if host.ndim != 3 or 0 in host.shape:
+        raise ValueError(f"{who}: masks must be [M,H,W] (or [H,W]), not {tuple(host.shape)}")
+    if not ((host == 0) | (host == 1)).all():
+        raise ValueError(f"{who}: masks must hold 0 / 1 only (the reference reads them as numbers: mask < 0.1, 1 - mask)")
+    return np.ascontiguousarray(host != 0, dtype=np.uint8)
+
+
+def _masks_key(masks, device, contour_key):
+    """-> (key, (weak reference, version) of a tensor or (None, 0)); like normals.topology_for: a tensor by identity and version, an
+    array by a digest of its bytes"""
+    if _is_tensor(masks):
+        return ("tensor", id(masks), int(device), contour_key), (weakref.ref(masks), masks._version)
+    a = np.ascontiguousarray(masks)
+    digest = hashlib.sha1(a.tobytes() + repr((a.shape, a.dtype.str)).encode()).hexdigest()
+    return ("array", digest, int(device), contour_key), (None, 0)
+
+
+def _silhouette_hit(key, masks):
+    hit = _SILHOUETTES.get(key)
+    if hit is None:
+        return None
+    if _is_tensor(masks) and not (hit["ref"]() is masks and hit["version"] == masks._version):
+        return None
+    return hit
+
+
+def _silhouette_store(key, entry, sil, contours, given):
+    old = _SILHOUETTES.pop(key, None)
+    if old is not None:
+        old["sil"].close()
+    while len(_SILHOUETTES) >= _SILHOUETTE_SLOTS:
+        _SILHOUETTES.pop(next(iter(_SILHOUETTES)))["sil"].close()
+    _SILHOUETTES[key] = {"ref": entry[0], "version": entry[1], "sil": sil, "contours": contours, "given": given}
+    return _SILHOUETTES[key]
+
+
+def extract_countours(masks, device=None):
+    """loss.py:73-83: masks[M,H,W] (or [H,W]; a tensor or an array of any dtype holding 0 / 1) -> a list of M float32 [C,1,2] items of
+    (x, y) points in border order - OpenCV's shape - tensors on masks' device, or arrays.  Per mask the external border the
+    reference keeps (loss.py:80: OpenCV's first listed contour), followed on the GPU `device` (None: masks', else 0).  The masks
+    and contours stay on the GPU for the `multview_mask_loss` that follows."""
+    from . import native
+    who = "extract_countours"
+    _normals.require_array("smplify.loss." + who, "masks", masks)
+    _normals.require_no_grad(who, "masks", masks)
+    if device is None:
+        device = _normals.device_index(masks)
+    key, entry = _masks_key(masks, device, None)
+    hit = _silhouette_hit(key, masks)
+    if hit is None:
+        host = _masks_host(who, masks)
+        empty = [i for i in range(len(host)) if not host[i].any()]
+        if empty:
+            raise ValueError(f"{who}: mask {empty[0]} has no foreground (the reference fails in np.argmax of an empty list)")
+        sil = native.Silhouette(host, None, device=device)           # (contour_select: OpenCV's first listed contour, the default)
+        hit = _silhouette_store(key, entry, sil, [np.asarray(c, np.float32).reshape(-1, 2) for c in sil.contours()], None)
+    out = [c.reshape(-1, 1, 2).copy() for c in hit["contours"]]
+    if _is_tensor(masks):
+        import torch
+        out = [torch.from_numpy(c).to(masks.device) for c in out]
+        hit["given"] = [(weakref.ref(c), c._version) for c in out]
+    return out
+
+
+def _silhouette_for(who, masks, contours, device):
+    """the `native.Silhouette` of (masks, contours) on GPU `device`: the one extract_countours built when these are its contours,
+    else one with the caller's contours uploaded"""
+    from . import native
+    key, entry = _masks_key(masks, device, None)
+    hit = _silhouette_hit(key, masks)
+    if hit is not None and len(hit["contours"]) == len(contours):
+        given = hit["given"]
+        if given is not None and all(_is_tensor(c) and r() is c and ver == c._version for c, (r, ver) in zip(contours, given)):
+            return hit["sil"]
+    host = []
+    for i, c in enumerate(contours):
+        a = _host(c)
+        if a.ndim not in (2, 3) or a.shape[-1] != 2 or (a.ndim == 3 and a.shape[1] != 1):
+            raise ValueError(f"{who}: contour {i} must be [C,1,2] or [C,2], not {tuple(a.shape)}")
+        if a.shape[0] == 0:
+            raise ValueError(f"{who}: contour {i} has no points")
+        host.append(np.ascontiguousarray(a.reshape(-1, 2)))
+    if hit is not None and len(hit["contours"]) == len(host) and all(np.array_equal(a, b) for a, b in zip(host, hit["contours"])):
+        return hit["sil"]
+    digest = hashlib.sha1(b"".join(a.tobytes() for a in host) + repr([len(a) for a in host]).encode()).hexdigest()
+    key, entry = _masks_key(masks, device, digest)
+    hit = _silhouette_hit(key, masks)
+    if hit is None:
+        hit = _silhouette_store(key, entry, native.Silhouette(_masks_host(who, masks), host, device=device), host, None)
+    return hit["sil"]
+
+
+def multview_mask_loss(contours, masks, smpl_verts=None, smpl_faces=None, w2cs=None, Ks=None, mask_frames=None, epsilon=10, imsize=512,
+                       device=None, pairwise=None):
+    """loss.py:85-130, the reference's parameters in its order (from the third on they have no default there) plus `device` (the
+    GPU; None: smpl_verts', else 0) and `pairwise` (None or 'cdist': distances in torch.cdist's float32 form, as the reference and
+    SMPLify compute them; 'exact': (a - b)^2 sums).  contours: M items [C,1,2] or [C,2]; masks[M,H,W] of 0 / 1; smpl_verts[1,N,3]
+    or [N,3] float32 - every 4th vertex is used; smpl_faces is accepted and ignored (the reference only converts it); w2cs[M,4,4],
+    Ks[M,3,3] (tensors, arrays or lists of them); of mask_frames only the length is read.  -> the unweighted loss: a 0-dim float32
+    tensor on smpl_verts' device, differentiable once with respect to smpl_verts, or a float for arrays.  A view none of whose
+    sampled vertices lies inside the image contributes its binary term only (the reference raises in torch.min)."""
+    who = "multview_mask_loss"
+    named = (("contours", contours), ("masks", masks), ("smpl_verts", smpl_verts), ("w2cs", w2cs), ("Ks", Ks))
+    for name, x in named:
+        _require_arrays(who, name, x)
+    if isinstance(masks, (list, tuple)) or isinstance(smpl_verts, (list, tuple)):
+        raise ValueError(f"{who}: masks and smpl_verts must be one tensor or array each, not a list")
+    flat = [(name, it) for name, x in named for it in _items(x)]
+    if len({_is_tensor(it) for _, it in flat}) > 1:
+        raise ValueError(f"{who}: the arguments mix torch tensors and numpy arrays")
+    for name, it in flat:
+        if name != "smpl_verts":
+            _normals.require_no_grad(who, name, it)
+    _prior._require_float32(who, "smpl_verts", smpl_verts)
+    if smpl_verts.ndim not in (2, 3) or smpl_verts.shape[-1] != 3 or (smpl_verts.ndim == 3 and smpl_verts.shape[0] != 1) or smpl_verts.shape[-2] == 0:
+        raise ValueError(f"{who}: smpl_verts must be [1,N,3] or [N,3], not {tuple(smpl_verts.shape)}")
+    if mask_frames is None:
+        raise ValueError(f"{who}: mask_frames is missing (its length is the number of views)")
+    n_masks = 1 if masks.ndim == 2 else len(masks)
+    contours, w2cs, Ks = list(contours), list(w2cs), list(Ks)
+    if not (len(mask_frames) == n_masks == len(contours) == len(w2cs) == len(Ks)):
+        raise ValueError(f"{who}: {len(mask_frames)} mask_frames, {n_masks} masks, {len(contours)} contours, {len(w2cs)} w2cs and {len(Ks)} Ks "
+                         "(the reference fails in .view)")
+    if masks.ndim not in (2, 3):
+        raise ValueError(f"{who}: masks must be [M,H,W], not {tuple(masks.shape)}")
+    imsize, epsilon = float(imsize), float(epsilon)
+    if not np.isfinite(epsilon):
+        raise ValueError(f"{who}: epsilon must be finite")
+    if not (np.isfinite(imsize) and imsize > 0):
+        raise ValueError(f"{who}: imsize must be finite and positive")
+    if imsize > min(masks.shape[-2:]):
+        raise ValueError(f"{who}: imsize {imsize:g} is larger than the masks ({masks.shape[-2]} x {masks.shape[-1]}): the reference indexes "
+                         "beyond the mask as soon as a chosen vertex lies there")
+    if pairwise not in (None, "cdist", "exact"):
+        raise ValueError(f"{who}: pairwise must be None, 'cdist' or 'exact'")
+    try:
+        w2c = np.stack([_host(a).reshape(4, 4) for a in w2cs])
+        K = np.stack([_host(a).reshape(3, 3) for a in Ks])
+    except ValueError:
+        raise ValueError(f"{who}: w2cs must be [M,4,4] and Ks [M,3,3]") from None
+    if device is None:
+        device = _normals.device_index(smpl_verts)
+    sil = _silhouette_for(who, masks, contours, device)
+
+    def call(v, want_grad):
+        value, _, grad = sil.loss(v.reshape(-1, 3), w2c, K, imsize=imsize, epsilon=epsilon, stride=MASK_STRIDE,
+                                  cdist_form=pairwise != "exact", want_grad=want_grad)
+        return value, grad
+
+    return _scalar_loss(who, smpl_verts, call, plus_zero=True)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

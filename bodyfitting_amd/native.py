@@ -366,6 +366,66 @@ def normal_loss(closest_face_norms, point_norms, want_grad=True, device=0):
     return loss[0], dpn
 
 
+class Silhouette:
+    """The masks[M,H,W] (truthy = foreground) of M views and one contour per view, kept on one GPU (bf_silhouette): what
+    multview_mask_loss (loss.py:85-130) compares a caller's vertices with.  contours: None = the external borders are followed on
+    the device and the one `contour_select` names is kept, else M arrays [C,2] (or [C,1,2]) of (x, y) points."""
+
+    def __init__(self, masks, contours=None, device=0, contour_select=_lib.CONTOUR_OPENCV_FIRST):
+        lib = _lib.load()
+        self._lib = lib
+        m = np.ascontiguousarray(np.asarray(masks) != 0, dtype=np.uint8)
+        if m.ndim == 2:
+            m = m[None]
+        self.n_views, self.H, self.W = m.shape
+        self.device = int(device)
+        counts = xy = None
+        if contours is not None:
+            pts = [_f32(c, (-1, 2)) for c in contours]
+            if len(pts) != self.n_views:
+                raise ValueError(f"Silhouette: {len(pts)} contours for {self.n_views} masks")
+            counts = np.array([len(p) for p in pts], np.int32)
+            xy = np.ascontiguousarray(np.concatenate(pts + [np.zeros((1, 2), np.float32)]))
+        self._h = C.c_void_p()
+        _lib.check(lib.bf_silhouette_create(self.device, self.n_views, self.H, self.W, m.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                            _lib.iptr(counts), _lib.fptr(xy), int(contour_select), C.byref(self._h)), "bf_silhouette_create")
+
+    def contours(self):
+        """-> list of M float32[C,2] arrays of (x, y) points in border order (bf_silhouette_contours)"""
+        counts = np.zeros(self.n_views, np.int32)
+        _lib.check(self._lib.bf_silhouette_contours(self._h, _lib.iptr(counts), None), "bf_silhouette_contours")
+        xy = np.zeros((max(int(counts.sum()), 1), 2), np.float32)
+        _lib.check(self._lib.bf_silhouette_contours(self._h, _lib.iptr(counts), _lib.fptr(xy)), "bf_silhouette_contours")
+        ends = np.cumsum(counts)
+        return [xy[e - c:e].copy() for c, e in zip(counts, ends)]
+
+    def loss(self, verts, w2c, K, imsize=512, epsilon=10, stride=4, cdist_form=True, want_grad=True):
+        """bf_silhouette_loss on verts[N,3][::stride] with cameras w2c[M,4,4], K[M,3,3] -> (value float32 scalar, view_terms[M,2] =
+        per view (contour term, binary term), dverts[N,3] = the gradient for cotangent 1; None unless want_grad).  cdist_form:
+        distances as torch.cdist computes them in float32 (expanded form beyond 25 inside vertices of a view), else direct sums"""
+        v = _f32(verts, (-1, 3))
+        w = _f32(w2c, (self.n_views, 4, 4))
+        k = _f32(K, (self.n_views, 3, 3))
+        loss = np.empty(1, np.float32)
+        terms = np.empty((self.n_views, 2), np.float32)
+        dv = np.empty((len(v), 3), np.float32) if want_grad else None
+        _lib.check(self._lib.bf_silhouette_loss(self._h, len(v), int(stride), _lib.fptr(v), _lib.fptr(w), _lib.fptr(k), float(imsize),
+                                                float(epsilon), int(bool(cdist_form)), _lib.fptr(loss), _lib.fptr(terms), _lib.fptr(dv)),
+                   "bf_silhouette_loss")
+        return loss[0], terms, dv
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bf_silhouette_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def set_nearest_rule(rule):
     """The arithmetic of every closest-point search of the process: "reference" (default: search_nearest_proj as the reference's
     source evaluates it in float32, mesh_grid_kernel.cu:12-109 + matrix.h) or "fast" (2 x 2 normal equations, v_rcp_f32).

@@ -447,6 +447,51 @@ int bf_extract_contours(int device, int n, int H, int W, const uint8_t *masks, i
  * w.r.t. body_vertices, dverts[F,NV,3] (either may be NULL) */
 int bf_batch_mask_loss(bf_batch *b, const bf_hyper *hyper, float *loss, float *dverts);
 
+/* multview_mask_loss (smplify/loss.py:85-130) on vertices the CALLER holds - their own model's, SMPL+D displaced ones, the drop-in
+ * SMPL's with their own similarity - for a user's own torch loop (smplify.py:198): no model and no batch behind it.
+ *
+ * A silhouette object = the M views' masks[M,H,W] (uint8, non-zero = foreground) and one contour per view, on one device for the
+ * object's life.  contour_count == NULL: the external borders are followed on the device, as bf_batch_set_masks does it, and the
+ * one contour_select names is kept (BF_CONTOUR_*).  Otherwise contour_count[M] points per view, concatenated as (x, y) pairs in
+ * contour_xy (contour_select is not read); a view may have no points - it then contributes its binary term only.
+ * Limits (BF_ERR_UNSUPPORTED beyond): M <= 65535 (a grid dimension), H, W <= 16384 (pixel coordinates and H * W stay exact in
+ * float32 / int), a contour of at most BF_SIL_MAX_CONTOUR = 2^22 points (16 lanes per point in an int).  The object is used by
+ * one thread at a time. */
+#define BF_SIL_MAX_VIEWS   65535
+#define BF_SIL_MAX_SIDE    16384
+#define BF_SIL_MAX_CONTOUR (1 << 22)
+typedef struct bf_silhouette bf_silhouette;
+int bf_silhouette_create(int device, int n_views, int H, int W, const uint8_t *masks, const int32_t *contour_count,
+                         const float *contour_xy, int contour_select, bf_silhouette **out);
+void bf_silhouette_destroy(bf_silhouette *s);
+/* The contours the object holds: counts[M] and, when xy != NULL, their (x, y) points concatenated (sum(counts) pairs; call with
+ * xy == NULL first), as bf_extract_contours. */
+int bf_silhouette_contours(const bf_silhouette *s, int32_t *counts, float *xy);
+/* One evaluation on the sampled vertices verts[::stride] (ceil(n_verts / stride) of them; the reference hard-codes 4) of
+ * verts[n_verts,3], with cameras w2c[M,4,4] (rows 0..2 are read) and K[M,3,3]:
+ *   per view  pixels = K (R x + t) / z, no epsilon on the depth; inside = 0 <= u, v < imsize;
+ *     contour term  sum over the contour's points of w * the distance to the nearest inside vertex (first minimum, as torch.min
+ *                   picks it), w = epsilon where the mask is < 0.1 at that vertex's truncated pixel, else 1; a view with no
+ *                   inside vertex has contour term exactly 0;
+ *     binary term   epsilon * sum over ALL sampled vertices of bilinear(1 - mask) at the pixel normalised by imsize (grid_sample,
+ *                   zeros padding, align_corners=False).
+ * cdist_form != 0: distances as torch.cdist computes them in float32 (what the reference computes): its expanded form -
+ * bf_hyper.mask_cdist_form's - in a view with more than 25 inside vertices, direct (a - b)^2 sums in a view with fewer, where
+ * torch does not switch to the expanded form either; 0: direct sums everywhere.
+ * loss[1] = the unweighted value, as the function returns it; view_terms[M,2] = per view (contour term, binary term); loss is
+ * their float32 sum taken in memory order (view 0's contour term, view 0's binary term, view 1's ...).  dverts[n_verts,3] = the
+ * gradient for cotangent 1, exactly zero (every bit) at vertices that are not sampled.  Every output may be NULL = not wanted.
+ * Three launches and one read-back per call.  No float atomics: the contour term's gradient is summed as 64-bit fixed-point
+ * numbers (exact, so order-free), everything else in a fixed order - equal inputs give equal bits, and a view's view_terms row
+ * and its share of dverts do not depend on which other views are in the call.
+ * The fixed-point sums hold steps of 2^-40 in 63 bits: a call with max(|epsilon|, 1) * (longest contour) > BF_SIL_MAX_SUM = 2^20
+ * (|sum| 2^60 at most: a factor of 8 below the overflow) is REFUSED with BF_ERR_UNSUPPORTED - there is no second, ordered path.
+ * BF_ERR_INVALID, before any launch: n_verts < 1, stride < 1, imsize or epsilon not finite, imsize <= 0; more than 2^28
+ * vertices: BF_ERR_UNSUPPORTED. */
+#define BF_SIL_MAX_SUM (1 << 20)
+int bf_silhouette_loss(bf_silhouette *s, int n_verts, int stride, const float *verts, const float *w2c, const float *K,
+                       float imsize, float epsilon, int cdist_form, float *loss, float *view_terms, float *dverts);
+
 /* SMPL+D stage (displacement=True, smplify.py:228-247): n_iters Adam steps (lr 5e-2) on a per-vertex
  * displacement of the vertices returned by the last bf_fit, against each frame's scan:
  * loss = icp + (normal_loss + laplacian) * constant_scale * 0.1.  Needs faces in the model and scans. */
