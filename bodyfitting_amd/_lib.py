@@ -193,6 +193,15 @@ SIGNATURES = {
     "bf_texfit_render_depth": (C.c_int, [_VP, C.c_int, _FP, _FP, _FP, C.c_float, _FP, _FP]),
     "bf_texfit_load_textures": (C.c_int, [C.c_int, C.c_int, _FP, _IP, _FP, C.c_int, C.POINTER(C.c_void_p), _IP, _IP, C.c_int, C.c_int,
                                           C.c_int, _FP, _FP]),
+    "bf_nr_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _FP, C.POINTER(_VP)]),
+    "bf_nr_destroy": (None, [_VP]),
+    "bf_nr_set_light": (C.c_int, [_VP, C.c_float, C.c_float, _FP, _FP, _FP]),
+    "bf_nr_mesh_create": (C.c_int, [_VP, C.c_int, _FP, C.c_int, _IP, C.c_int, _FP, C.POINTER(_VP)]),
+    "bf_nr_mesh_set_textures": (C.c_int, [_VP, _FP]),
+    "bf_nr_mesh_destroy": (None, [_VP]),
+    "bf_nr_render": (C.c_int, [_VP, _VP, _FP, _FP, _FP, C.c_float, C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.POINTER(_VP)]),
+    "bf_nr_tape_texture_grad": (C.c_int, [_VP, _FP, _FP]),
+    "bf_nr_tape_destroy": (None, [_VP]),
     "bf_hmr_n_weights": (C.c_int64, []),
     "bf_hmr_create": (C.c_int, [C.c_int, _FP, C.c_int64, _FP, C.c_int, C.POINTER(_VP)]),
     "bf_hmr_destroy": (None, [_VP]),

@@ -1,0 +1,244 @@
+// Host side of the stand-alone neural_renderer.Renderer (thirdparty/neural_renderer/neural_renderer/renderer.py; kernels:
+// nr_kernels.hip, and tex_kernels.hip's projection / compose / depth).  Three objects: the renderer (image size, planes, light, one
+// stream), a mesh resident on its device, and a tape - what the texture VJP needs of ONE render (pixel map, face records, light rows,
+// flags), so that several renders of one mesh can be differentiated in one graph.
+#include "bf_host.h"
+#include "grid_kernels.h"
+#include "nr_kernels.h"
+#include "tex_bodies.h"
+
+#include <climits>
+
+struct bf_nr {
+    unsigned long long id = 0;        // never reused: meshes and tapes name their renderer by it (bf_nr_live)
+    int device = 0, out = 0, is = 0, tiles = 0, aa = 1;
+    float near = 0.1f, far = 100.f, bg[3] = {0.f, 0.f, 0.f};
+    NrLight light{0.5f, 0.5f, {1.f, 1.f, 1.f}, {1.f, 1.f, 1.f}, {0.f, 1.f, 0.f}, 1};      // renderer.py:17-19
+    hipStream_t stream = nullptr;
+    DevBuf<float> rgb, image, depth_image, alpha_image, grad_image;
+    DevBuf<int> tile_start, cursor;
+    int *h_total = nullptr;           // pinned: the number of tile-list entries the last render needed
+};
+
+// what one render leaves for its backward pass; the mesh's own (overwritten by its next render) or a tape's
+struct NrFrame {
+    DevBuf<float> pix, frec, light;
+    int alloc(size_t npx, size_t nrec, bool lit) {
+        HIP_TRY(pix.alloc_pooled(npx * 5)); HIP_TRY(frec.alloc_pooled(nrec * BF_TEX_REC));
+        if (lit) HIP_TRY(light.alloc_pooled(nrec * 3));
+        return BF_OK;
+    }
+};
+
+struct bf_nr_mesh {
+    unsigned long long owner = 0;
+    int device = 0, nv = 0, nf = 0, ts = 0;
+    bool has_tex = false;
+    DevBuf<float> verts, tex, pv;
+    DevBuf<int> faces, tile_list;
+};
+
+struct bf_nr_tape {
+    unsigned long long owner = 0;
+    int device = 0, nf = 0, nrec = 0, ts = 0, lit = 0;
+    NrFrame frame;
+};
+
+static std::mutex &nr_mu() { static std::mutex mu; return mu; }
+static std::map<unsigned long long, bf_nr *> &nr_live() { static std::map<unsigned long long, bf_nr *> live; return live; }
+static bf_nr *nr_find(unsigned long long id) {
+    std::lock_guard<std::mutex> lk(nr_mu());
+    auto it = nr_live().find(id);
+    return it == nr_live().end() ? nullptr : it->second;
+}
+
+// one attempt: everything up to the host copies, on the renderer's stream.  F: where pix / frec / light go.
+static int nr_render_once(bf_nr *r, bf_nr_mesh *M, NrFrame &F, const TexView &V, int nrec, bool lit, bool want_rgb, float *rgb, float *depth,
+                          float *alpha) {
+    const int is = r->is, tiles = r->tiles, ntile = tiles * tiles, cap = (int)M->tile_list.n;
+    NrLight L = r->light;
+    L.on = lit ? 1 : 0;
+    float *light = lit ? F.light.p : nullptr;
+    hipLaunchKernelGGL(bf_tex_project_kernel, dim3((M->nv + 255) / 256), dim3(256), 0, r->stream, M->nv, (const float *)M->verts.p, V, M->pv.p);
+    HIP_TRY(hipMemsetAsync(r->tile_start.p, 0, (size_t)(ntile + 1) * sizeof(int), r->stream));
+    hipLaunchKernelGGL(bf_nr_face_kernel, dim3((nrec + 255) / 256), dim3(256), 0, r->stream, M->nf, nrec, (const int *)M->faces.p, (const float *)M->pv.p,
+                       (const float *)M->verts.p, L, is, tiles, F.frec.p, light, r->tile_start.p, (int *)nullptr, (int *)nullptr, 0, cap);
+    hipLaunchKernelGGL(bf_grid_scan_kernel, dim3(1), dim3(1024), 0, r->stream, r->tile_start.p, r->cursor.p, ntile + 1);
+    HIP_TRY(hipMemcpyAsync(r->h_total, r->tile_start.p + ntile, sizeof(int), hipMemcpyDeviceToHost, r->stream));
+    hipLaunchKernelGGL(bf_nr_face_kernel, dim3((nrec + 255) / 256), dim3(256), 0, r->stream, M->nf, nrec, (const int *)M->faces.p, (const float *)M->pv.p,
+                       (const float *)M->verts.p, L, is, tiles, F.frec.p, light, r->tile_start.p, r->cursor.p, M->tile_list.p, 1, cap);
+    hipLaunchKernelGGL(bf_nr_raster_kernel, dim3((ntile + 3) / 4), dim3(256), 0, r->stream, is, tiles, M->nf, (const float *)F.frec.p, (const float *)light,
+                       (const int *)r->tile_start.p, (const int *)M->tile_list.p, want_rgb ? (const float *)M->tex.p : (const float *)nullptr, M->ts,
+                       r->near, r->far, r->bg[0], r->bg[1], r->bg[2], F.pix.p, r->rgb.p, cap);
+    const int npo = r->out * r->out;
+    if (rgb) {
+        hipLaunchKernelGGL(bf_tex_compose_kernel, dim3((3 * npo + 255) / 256), dim3(256), 0, r->stream, r->out, r->aa, (const float *)r->rgb.p, r->image.p);
+        HIP_TRY(hipMemcpyAsync(rgb, r->image.p, (size_t)3 * npo * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    }
+    if (depth) {
+        hipLaunchKernelGGL(bf_tex_depth_kernel, dim3((npo + 255) / 256), dim3(256), 0, r->stream, r->out, r->aa, (const float *)F.pix.p, r->depth_image.p);
+        HIP_TRY(hipMemcpyAsync(depth, r->depth_image.p, (size_t)npo * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    }
+    if (alpha) {
+        hipLaunchKernelGGL(bf_nr_alpha_kernel, dim3((npo + 255) / 256), dim3(256), 0, r->stream, r->out, r->aa, (const float *)F.pix.p, r->alpha_image.p);
+        HIP_TRY(hipMemcpyAsync(alpha, r->alpha_image.p, (size_t)npo * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return BF_OK;
+}
+
+extern "C" {
+
+void bf_nr_destroy(bf_nr *r) {
+    if (!r) return;
+    { std::lock_guard<std::mutex> lk(nr_mu()); nr_live().erase(r->id); }
+    (void)hipSetDevice(r->device);
+    if (r->stream) { (void)hipStreamSynchronize(r->stream); (void)hipStreamDestroy(r->stream); }
+    if (r->h_total) (void)hipHostFree(r->h_total);
+    delete r;
+}
+
+int bf_nr_create(int device, int image_size, int anti_aliasing, float near, float far, const float *background, bf_nr **out) {
+    if (!out) return fail(BF_ERR_INVALID, "bf_nr_create: null output");
+    *out = nullptr;
+    if (image_size <= 0 || !(near < far)) return fail(BF_ERR_INVALID, "bf_nr_create: image_size must be positive and near < far");
+    if (image_size > 4096) return fail(BF_ERR_UNSUPPORTED, "bf_nr_create: image_size above 4096");
+    if (device < 0 || device >= bf_device_count()) return fail(BF_ERR_NO_DEVICE, "bf_nr_create: no such HIP device");
+    HIP_TRY(hipSetDevice(device));
+    auto *r = new bf_nr();
+    static std::atomic<unsigned long long> next_id{1};
+    r->id = next_id++;
+    r->device = device; r->out = image_size; r->aa = anti_aliasing ? 1 : 0; r->is = image_size * (r->aa ? 2 : 1);
+    r->tiles = (r->is + BF_TEX_TILE - 1) / BF_TEX_TILE;
+    r->near = near; r->far = far;
+    if (background) std::memcpy(r->bg, background, sizeof r->bg);
+    const size_t npo = (size_t)image_size * image_size, npx = (size_t)r->is * r->is, ntile = (size_t)r->tiles * r->tiles;
+    const bool ok = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) == hipSuccess && r->rgb.alloc(npx * 3) == hipSuccess &&
+                    r->image.alloc(npo * 3) == hipSuccess && r->depth_image.alloc(npo) == hipSuccess && r->alpha_image.alloc(npo) == hipSuccess &&
+                    r->grad_image.alloc(npo * 3) == hipSuccess && r->tile_start.alloc(ntile + 1) == hipSuccess &&
+                    r->cursor.alloc(ntile + 1) == hipSuccess && hipHostMalloc((void **)&r->h_total, sizeof(int)) == hipSuccess;
+    if (!ok) { bf_nr_destroy(r); return fail(BF_ERR_HIP, "bf_nr_create: device allocation failed"); }
+    *r->h_total = 0;
+    { std::lock_guard<std::mutex> lk(nr_mu()); nr_live()[r->id] = r; }
+    *out = r;
+    return BF_OK;
+}
+
+int bf_nr_set_light(bf_nr *r, float ambient, float directional, const float *color_ambient, const float *color_directional, const float *direction) {
+    if (!r || !color_ambient || !color_directional || !direction) return fail(BF_ERR_INVALID, "bf_nr_set_light: null argument");
+    r->light.ambient = ambient; r->light.directional = directional;
+    std::memcpy(r->light.color_ambient, color_ambient, 3 * sizeof(float));
+    std::memcpy(r->light.color_directional, color_directional, 3 * sizeof(float));
+    std::memcpy(r->light.direction, direction, 3 * sizeof(float));
+    return BF_OK;
+}
+
+void bf_nr_mesh_destroy(bf_nr_mesh *m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    if (bf_nr *r = nr_find(m->owner)) (void)hipStreamSynchronize(r->stream);
+    delete m;
+}
+
+int bf_nr_mesh_set_textures(bf_nr_mesh *m, const float *textures) {
+    if (!m || !textures) return fail(BF_ERR_INVALID, "bf_nr_mesh_set_textures: null argument");
+    if (!m->ts) return fail(BF_ERR_INVALID, "bf_nr_mesh_set_textures: the mesh was created without a texture size");
+    bf_nr *r = nr_find(m->owner);
+    if (!r) return fail(BF_ERR_INVALID, "bf_nr_mesh_set_textures: the mesh's renderer was destroyed");
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    const size_t ntex = (size_t)m->nf * m->ts * m->ts * m->ts * 3;
+    if (!m->tex.p) HIP_TRY(m->tex.alloc(ntex));
+    HIP_TRY(hipMemcpy(m->tex.p, textures, ntex * sizeof(float), hipMemcpyHostToDevice));
+    m->has_tex = true;
+    return BF_OK;
+}
+
+int bf_nr_mesh_create(bf_nr *r, int n_verts, const float *verts, int n_faces, const int32_t *faces, int texture_size, const float *textures,
+                      bf_nr_mesh **out) {
+    if (!out) return fail(BF_ERR_INVALID, "bf_nr_mesh_create: null output");
+    *out = nullptr;
+    if (!r || n_verts <= 0 || n_faces <= 0 || !verts || !faces) return fail(BF_ERR_INVALID, "bf_nr_mesh_create: bad argument");
+    if (texture_size < 0 || texture_size == 1 || (textures && !texture_size))
+        return fail(BF_ERR_INVALID, "bf_nr_mesh_create: texture_size must be 0 (no textures) or at least 2");
+    if (texture_size > 16) return fail(BF_ERR_UNSUPPORTED, "bf_nr_mesh_create: texture_size above 16");
+    if (n_faces > INT_MAX / 2) return fail(BF_ERR_UNSUPPORTED, "bf_nr_mesh_create: 2 x n_faces does not fit an int");
+    for (size_t i = 0; i < (size_t)n_faces * 3; ++i)
+        if (faces[i] < 0 || faces[i] >= n_verts) return fail(BF_ERR_INVALID, "bf_nr_mesh_create: face index out of range");
+    HIP_TRY(hipSetDevice(r->device));
+    std::unique_ptr<bf_nr_mesh> m(new bf_nr_mesh());
+    m->owner = r->id; m->device = r->device; m->nv = n_verts; m->nf = n_faces; m->ts = texture_size;
+    HIP_TRY(m->verts.upload(std::vector<float>(verts, verts + (size_t)n_verts * 3)));
+    HIP_TRY(m->faces.upload(std::vector<int>(faces, faces + (size_t)n_faces * 3)));
+    HIP_TRY(m->pv.alloc((size_t)n_verts * 3));
+    HIP_TRY(m->tile_list.alloc((size_t)n_faces * 4 + (size_t)r->tiles * r->tiles + 1024));         // (first guess; grown when a render says so)
+    if (textures) BF_TRY(bf_nr_mesh_set_textures(m.get(), textures));
+    *out = m.release();
+    return BF_OK;
+}
+
+void bf_nr_tape_destroy(bf_nr_tape *tape) {
+    if (!tape) return;
+    (void)hipSetDevice(tape->device);
+    if (bf_nr *r = nr_find(tape->owner)) (void)hipStreamSynchronize(r->stream);      // (the pool hands the blocks out again: nothing may still read them)
+    delete tape;
+}
+
+int bf_nr_render(bf_nr *r, bf_nr_mesh *m, const float *K, const float *R, const float *t, float orig_size, int fill_back, int lightoff, int ndc,
+                 float *rgb, float *depth, float *alpha, bf_nr_tape **tape) {
+    if (tape) *tape = nullptr;
+    if (!r || !m) return fail(BF_ERR_INVALID, "bf_nr_render: null handle");
+    if (m->owner != r->id) return fail(BF_ERR_INVALID, "bf_nr_render: the mesh belongs to another renderer");
+    if (!ndc && (!K || !R || !t || !(orig_size > 0.f))) return fail(BF_ERR_INVALID, "bf_nr_render: K, R, t and a positive orig_size are needed unless ndc is set");
+    if ((rgb || tape) && !m->has_tex) return fail(BF_ERR_INVALID, "bf_nr_render: rgb or a tape asked of a mesh without textures");
+    HIP_TRY(hipSetDevice(r->device));
+    TexView V{};
+    V.orig = -1.f;                                    // (bf_tex_project_kernel: pass the vertices through)
+    if (!ndc) { std::memcpy(V.R, R, sizeof V.R); std::memcpy(V.t, t, sizeof V.t); std::memcpy(V.K, K, sizeof V.K); V.orig = orig_size; }
+    const int nrec = fill_back ? 2 * m->nf : m->nf;
+    const bool lit = !lightoff && (rgb || tape);
+    const size_t npx = (size_t)r->is * r->is;
+    std::unique_ptr<bf_nr_tape> tp;
+    NrFrame scratch;
+    if (tape) {
+        tp.reset(new bf_nr_tape());
+        tp->owner = r->id; tp->device = r->device; tp->nf = m->nf; tp->nrec = nrec; tp->ts = m->ts; tp->lit = lit;
+    }
+    NrFrame &F = tape ? tp->frame : scratch;
+    BF_TRY(F.alloc(npx, (size_t)nrec, lit));
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        BF_TRY(nr_render_once(r, m, F, V, nrec, lit, rgb || tape, rgb, depth, alpha));
+        const size_t need = (size_t)std::max(*r->h_total, 0);
+        if (need <= m->tile_list.n) {
+            if (tape) *tape = tp.release();
+            return BF_OK;
+        }
+        m->tile_list.release();
+        HIP_TRY(m->tile_list.alloc(need + need / 2 + 1024));
+    }
+    return fail(BF_ERR_HIP, "bf_nr_render: the tile lists keep overflowing");
+}
+
+int bf_nr_tape_texture_grad(bf_nr_tape *tape, const float *grad_rgb, float *grad_textures) {
+    if (!tape || !grad_rgb || !grad_textures) return fail(BF_ERR_INVALID, "bf_nr_tape_texture_grad: null argument");
+    bf_nr *r = nr_find(tape->owner);
+    if (!r) return fail(BF_ERR_INVALID, "bf_nr_tape_texture_grad: the tape outlived its renderer");
+    HIP_TRY(hipSetDevice(r->device));
+    const int ts = tape->ts;
+    const size_t ntex = (size_t)tape->nf * ts * ts * ts * 3;
+    DevBuf<float> grad;
+    HIP_TRY(grad.alloc_pooled(ntex));
+    const float *light = tape->lit ? tape->frame.light.p : nullptr;
+    HIP_TRY(hipMemcpyAsync(r->grad_image.p, grad_rgb, r->grad_image.n * sizeof(float), hipMemcpyHostToDevice, r->stream));
+    hipLaunchKernelGGL(bf_nr_backward_kernel, dim3(tape->nf), dim3(64), (size_t)ts * ts * ts * 3 * sizeof(float), r->stream, tape->nf, tape->nrec, r->is,
+                       r->out, r->aa, (const float *)tape->frame.pix.p, (const float *)tape->frame.frec.p, light, ts, (const float *)r->grad_image.p, grad.p);
+    hipLaunchKernelGGL(bf_nr_backward_large_kernel, dim3((r->is * r->is + 255) / 256), dim3(256), 0, r->stream, tape->nf, r->is, r->out, r->aa,
+                       (const float *)tape->frame.pix.p, (const float *)tape->frame.frec.p, light, ts, (const float *)r->grad_image.p, grad.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(grad_textures, grad.p, ntex * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return BF_OK;
+}
+
+}  // extern "C"

@@ -426,6 +426,101 @@ class Silhouette:
             pass
 
 
+class NrRenderer:
+    """bf_nr: neural_renderer.Renderer's image size, planes, background and light on one GPU (renderer.py:12-63)"""
+
+    def __init__(self, image_size, anti_aliasing=True, near=0.1, far=100.0, background=(0.0, 0.0, 0.0), device=0):
+        self._lib = _lib.load()
+        self.image_size, self.device = int(image_size), int(device)
+        self._h = C.c_void_p()
+        _lib.check(self._lib.bf_nr_create(self.device, self.image_size, int(bool(anti_aliasing)), float(near), float(far),
+                                          _lib.fptr(_f32(background, (3,))), C.byref(self._h)), "bf_nr_create")
+
+    def set_light(self, ambient, directional, color_ambient, color_directional, direction):
+        _lib.check(self._lib.bf_nr_set_light(self._h, float(ambient), float(directional), _lib.fptr(_f32(color_ambient, (3,))),
+                                             _lib.fptr(_f32(color_directional, (3,))), _lib.fptr(_f32(direction, (3,)))), "bf_nr_set_light")
+
+    def render(self, mesh, K=None, R=None, t=None, orig_size=1.0, fill_back=True, lightoff=False, ndc=False, want=("rgb", "depth", "alpha"),
+               tape=False):
+        """bf_nr_render -> (rgb[3,is,is] | None, depth[is,is] | None, alpha[is,is] | None, NrTape | None): the outputs named in `want`"""
+        n = self.image_size
+        rgb = np.empty((3, n, n), np.float32) if "rgb" in want else None
+        depth = np.empty((n, n), np.float32) if "depth" in want else None
+        alpha = np.empty((n, n), np.float32) if "alpha" in want else None
+        cam = [None, None, None] if ndc else [_f32(K, (3, 3)), _f32(R, (3, 3)), _f32(t, (3,))]
+        h = C.c_void_p()
+        _lib.check(self._lib.bf_nr_render(self._h, mesh._h, _lib.fptr(cam[0]), _lib.fptr(cam[1]), _lib.fptr(cam[2]), float(orig_size),
+                                          int(bool(fill_back)), int(bool(lightoff)), int(bool(ndc)), _lib.fptr(rgb), _lib.fptr(depth),
+                                          _lib.fptr(alpha), C.byref(h) if tape else None), "bf_nr_render")
+        return rgb, depth, alpha, (NrTape(h, mesh.textures_shape) if tape else None)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bf_nr_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NrMesh:
+    """bf_nr_mesh: vertices[NV,3], faces[NF,3] and (optionally) textures[NF,ts,ts,ts,3] resident on the renderer's GPU"""
+
+    def __init__(self, renderer, verts, faces, texture_size=0, textures=None):
+        self._lib = _lib.load()
+        v, f = _f32(verts, (-1, 3)), _i32(np.asarray(faces).reshape(-1, 3))
+        ts = int(texture_size)
+        self.textures_shape = (len(f), ts, ts, ts, 3)
+        tex = None if textures is None else _f32(textures, self.textures_shape)
+        self._h = C.c_void_p()
+        _lib.check(self._lib.bf_nr_mesh_create(renderer._h, len(v), _lib.fptr(v), len(f), _lib.iptr(f), ts, _lib.fptr(tex), C.byref(self._h)),
+                   "bf_nr_mesh_create")
+
+    def set_textures(self, textures):
+        _lib.check(self._lib.bf_nr_mesh_set_textures(self._h, _lib.fptr(_f32(textures, self.textures_shape))), "bf_nr_mesh_set_textures")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bf_nr_mesh_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NrTape:
+    """bf_nr_tape: what the texture VJP needs of one render"""
+
+    def __init__(self, handle, textures_shape):
+        self._lib, self._h, self.textures_shape = _lib.load(), handle, tuple(textures_shape)
+
+    def texture_grad(self, grad_rgb):
+        """grad_rgb[3,is,is] -> d / d textures [NF,ts,ts,ts,3] (bf_nr_tape_texture_grad)"""
+        if not self._h:
+            raise _lib.BodyfitError("NrTape.texture_grad: the tape was closed")
+        g = np.ascontiguousarray(grad_rgb, dtype=np.float32)
+        out = np.empty(self.textures_shape, np.float32)
+        _lib.check(self._lib.bf_nr_tape_texture_grad(self._h, _lib.fptr(g), _lib.fptr(out)), "bf_nr_tape_texture_grad")
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bf_nr_tape_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def set_nearest_rule(rule):
     """The arithmetic of every closest-point search of the process: "reference" (default: search_nearest_proj as the reference's
     source evaluates it in float32, mesh_grid_kernel.cu:12-109 + matrix.h) or "fast" (2 x 2 normal equations, v_rcp_f32).

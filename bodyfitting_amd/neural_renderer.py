@@ -1,0 +1,345 @@
+"""`import neural_renderer as nr` for callers of the reference (smplify/texture_fitting.py:8,240-275, utils/renderer.py, utils/io_utils.py,
+test/correspondence.py): `Renderer`, `load_obj`, `save_obj` and `__version__` on the HIP path (libbodyfit's bf_nr_*; kernels:
+csrc/nr_kernels.hip and the rasteriser shared with the fused texture-fitting loop).  `bodyfitting_amd/dropin_nr/neural_renderer`
+re-exports this module under the reference's import name.
+
+`Renderer` is thirdparty/neural_renderer/neural_renderer/renderer.py:11-346 for camera_mode='projection' with zero distortion:
+fill-back, ambient + directional light, rgb / depth / alpha, and the gradient of any loss on the rgb image with respect to the
+`textures` - what `loss.backward()` of the loop of texture_fitting.py:262-270 needs.  The soft-edge gradient to vertices and
+cameras (backward_pixel_map, backward_depth_map) is NOT built: inputs that ask for it raise NotImplementedError instead of coming
+back detached.  Every other name of the reference package raises NotImplementedError on access.
+
+Tensors in give float32 tensors out on the vertices' device; arrays in give arrays out.  The device meshes are remembered per
+(vertices, faces) object and GPU - a tensor by identity and `_version`, an array by a digest, four at a time - and a mesh's textures
+go up again only when their object or `_version` changed: in the reference's loop the scan's once, the fitted ones once per
+`optimizer.step()`.  torch is imported on first use only.
+"""
+from __future__ import annotations
+
+import hashlib
+import os
+import weakref
+
+import numpy as np
+
+from . import _autograd
+from . import native
+from . import obj_textures as OT
+
+__version__ = '1.1.3'            # thirdparty/neural_renderer/neural_renderer/__init__.py:14
+name = 'neural_renderer_pytorch'
+
+# the names of the reference package (__init__.py:1-12) that are not supplied
+_NOT_BUILT = ("get_points_from_angles", "lighting", "look", "look_at", "Mesh", "perspective", "projection", "orthogonal", "rasterize_rgbad",
+              "rasterize", "rasterize_silhouettes", "rasterize_depth", "Rasterize", "vertices_to_faces", "cuda")
+_MESH_SLOTS = 4
+_NO_VERTEX_GRAD = ("neural_renderer.Renderer: the soft-edge vertex gradient (backward_pixel_map, backward_depth_map of "
+                   "cuda/rasterize_cuda_kernel.cu) is not built - only `textures` is differentiated; detach {what} first")
+
+
+def __getattr__(attr):
+    if attr in _NOT_BUILT:
+        raise NotImplementedError(f"neural_renderer.{attr} is not supplied by bodyfitting_amd (Renderer, load_obj, save_obj and __version__ are)")
+    raise AttributeError(f"module {__name__!r} has no attribute {attr!r}")
+
+
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "_version")
+
+
+def _host(x, dtype=np.float32):
+    if x is None:
+        return None
+    if _is_tensor(x):
+        x = x.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(x), dtype=dtype)
+
+
+def _gpu_of(x):
+    return x.device.index or 0 if _is_tensor(x) and x.device.type == "cuda" else 0
+
+
+def _stamp(x):
+    """what tells whether `x` is still what was last seen: (weak reference, version) of a tensor, a digest of an array"""
+    if _is_tensor(x):
+        return ("tensor", weakref.ref(x), x._version)
+    a = np.ascontiguousarray(x)
+    return ("array", hashlib.sha1(a.tobytes() + repr((a.shape, a.dtype.str)).encode()).hexdigest(), 0)
+
+
+def _same(stamp, x):
+    if stamp is None or (stamp[0] == "tensor") != _is_tensor(x):
+        return False
+    if stamp[0] == "tensor":
+        return stamp[1]() is x and stamp[2] == x._version
+    return stamp == _stamp(x)
+
+
+class _Tapes:
+    """the tapes of one differentiable render (one per batch item), freed by the backward pass or with the graph"""
+
+    def __init__(self):
+        self.tapes = []
+
+    def close(self):
+        for tp in self.tapes:
+            tp.close()
+        self.tapes = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Renderer:
+    """renderer.py:11-63, the same constructor list and defaults"""
+
+    def __init__(self, image_size=256, anti_aliasing=True, background_color=[0, 0, 0],
+                 fill_back=True, camera_mode='projection',
+                 K=None, R=None, t=None, dist_coeffs=None, orig_size=1024,
+                 perspective=True, viewing_angle=30, camera_direction=[0, 0, 1],
+                 near=0.1, far=100,
+                 light_intensity_ambient=0.5, light_intensity_directional=0.5,
+                 light_color_ambient=[1, 1, 1], light_color_directional=[1, 1, 1],
+                 light_direction=[0, 1, 0]):
+        if camera_mode in ('look', 'look_at', 'orthogonal'):
+            raise NotImplementedError(f"neural_renderer.Renderer: camera_mode={camera_mode!r} is not built (only 'projection')")
+        if camera_mode != 'projection':
+            raise ValueError('Camera mode has to be one of projection, look or look_at')
+        self.image_size, self.anti_aliasing, self.background_color, self.fill_back = image_size, anti_aliasing, background_color, fill_back
+        self.camera_mode, self.K, self.R, self.t, self.orig_size = camera_mode, K, R, t, orig_size
+        self.dist_coeffs = self._zero_distortion(dist_coeffs)
+        self.perspective, self.viewing_angle, self.camera_direction = perspective, viewing_angle, camera_direction
+        self.near, self.far = near, far
+        self.light_intensity_ambient, self.light_intensity_directional = light_intensity_ambient, light_intensity_directional
+        self.light_color_ambient, self.light_color_directional = light_color_ambient, light_color_directional
+        self.light_direction = light_direction
+        self.rasterizer_eps = 1e-3
+        self._native = {}           # gpu -> (configuration, native.NrRenderer)
+        self._meshes = {}           # key -> dict(v, f: stamps; gpu, ts, meshes [per batch item], tex: stamp of what was last sent)
+
+    # ---- nn.Module's surface the reference's callers touch ----
+    def to(self, *args, **kwargs):
+        return self
+
+    def cuda(self, *args, **kwargs):
+        return self
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+    @staticmethod
+    def _zero_distortion(dist_coeffs):
+        if dist_coeffs is not None and np.any(_host(dist_coeffs) != 0):
+            raise NotImplementedError("neural_renderer.Renderer: non-zero dist_coeffs are not built (projection.py:25-34)")
+        return None
+
+    def close(self):
+        for entry in self._meshes.values():
+            for m in entry["meshes"]:
+                m.close()
+        self._meshes = {}
+        for _, r in self._native.values():
+            r.close()
+        self._native = {}
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- device objects ----
+    def _renderer_on(self, gpu):
+        cfg = (int(self.image_size), bool(self.anti_aliasing), float(self.near), float(self.far), tuple(float(c) for c in _host(self.background_color).reshape(3)))
+        have = self._native.get(gpu)
+        if have is None or have[0] != cfg:
+            if have is not None:                         # its meshes go with it
+                for key in [k for k, e in self._meshes.items() if e["gpu"] == gpu]:
+                    for m in self._meshes.pop(key)["meshes"]:
+                        m.close()
+                have[1].close()
+            have = (cfg, native.NrRenderer(cfg[0], cfg[1], cfg[2], cfg[3], cfg[4], device=gpu))
+            self._native[gpu] = have
+        have[1].set_light(self.light_intensity_ambient, self.light_intensity_directional, _host(self.light_color_ambient).reshape(3),
+                          _host(self.light_color_directional).reshape(3), _host(self.light_direction).reshape(3))
+        return have[1]
+
+    def _meshes_for(self, r, gpu, vertices, faces, v_host, f_host, textures, tex_host):
+        """the device meshes (one per batch item) of these vertices and faces, with `textures` (may be None) sent if they changed.
+        v_host / f_host / tex_host: callables that give the host arrays, called only when something has to go up"""
+        sv, sf = _stamp(vertices), _stamp(faces)
+        key = (sv[0], id(vertices) if sv[0] == "tensor" else sv[1], sf[0], id(faces) if sf[0] == "tensor" else sf[1], gpu)
+        entry = self._meshes.get(key)
+        ts = 0 if textures is None else int(textures.shape[2])
+        if entry is not None and not (_same(entry["v"], vertices) and _same(entry["f"], faces) and (textures is None or entry["ts"] == ts)):
+            for m in self._meshes.pop(key)["meshes"]:
+                m.close()
+            entry = None
+        if entry is None:
+            v, f = v_host(), f_host()
+            while len(self._meshes) >= _MESH_SLOTS:
+                for m in self._meshes.pop(next(iter(self._meshes)))["meshes"]:
+                    m.close()
+            entry = {"v": sv, "f": sf, "gpu": gpu, "ts": ts, "tex": None, "meshes": [native.NrMesh(r, v[b], f[b], ts) for b in range(len(v))]}
+            self._meshes[key] = entry
+        if textures is not None and not _same(entry["tex"], textures):
+            tex = tex_host()
+            for b, m in enumerate(entry["meshes"]):
+                m.set_textures(tex[b])
+            entry["tex"] = _stamp(textures)
+        return entry["meshes"]
+
+    # ---- the one render path ----
+    def _render(self, vertices, faces, textures, K, R, t, dist_coeffs, orig_size, lightoff, want, fill_back=None, ndc=False, like=None):
+        self._zero_distortion(dist_coeffs)
+        if self.camera_mode != 'projection':
+            raise NotImplementedError(f"neural_renderer.Renderer: camera_mode={self.camera_mode!r} is not built (only 'projection')")
+        like = vertices if like is None else like
+        K, R, t = (self.K if K is None else K), (self.R if R is None else R), (self.t if t is None else t)
+        orig_size = self.orig_size if orig_size is None else orig_size
+        grad_on = False
+        if any(_is_tensor(x) for x in (vertices, textures, K, R, t)):
+            import torch
+            grad_on = torch.is_grad_enabled()
+        if grad_on:
+            for what, x in (("vertices", vertices), ("K", K), ("R", R), ("t", t)):
+                if _is_tensor(x) and x.requires_grad:
+                    raise NotImplementedError(_NO_VERTEX_GRAD.format(what=what))
+        if getattr(vertices, "ndim", 0) != 3 or vertices.shape[2] != 3:
+            raise ValueError(f"vertices must be [B, NV, 3], not {tuple(getattr(vertices, 'shape', ()))}")
+        B = int(vertices.shape[0])
+        if getattr(faces, "ndim", 0) != 3 or faces.shape[0] != B or faces.shape[2] != 3:
+            raise ValueError(f"faces must be [B, NF, 3] with B = {B}, not {tuple(getattr(faces, 'shape', ()))}")
+        if "rgb" in want:
+            if textures is None:
+                raise ValueError("textures are needed for an rgb render")
+            sh = tuple(textures.shape)
+            if len(sh) != 6 or sh[0] != B or sh[1] != faces.shape[1] or sh[5] != 3 or not (sh[2] == sh[3] == sh[4]):
+                raise ValueError(f"textures must be [B, NF, ts, ts, ts, 3] with B = {B}, NF = {faces.shape[1]}, not {sh}")
+        else:
+            textures = None
+        cams = None
+        if not ndc:
+            if K is None or R is None or t is None:
+                raise ValueError("K, R and t are needed (as arguments or from the constructor) with camera_mode='projection'")
+            Kh, Rh, th = _host(K).reshape(-1, 3, 3), _host(R).reshape(-1, 3, 3), _host(t).reshape(-1, 3)
+            for nm, a in (("K", Kh), ("R", Rh), ("t", th)):
+                if len(a) not in (1, B):
+                    raise ValueError(f"{nm} must have batch size 1 or {B}, not {len(a)}")
+            cams = [(Kh[b % len(Kh)], Rh[b % len(Rh)], th[b % len(th)]) for b in range(B)]
+        gpu = _gpu_of(like)
+        r = self._renderer_on(gpu)
+        fill_back = self.fill_back if fill_back is None else fill_back
+        tex_ref = textures
+
+        def run(tex_host, tape):
+            meshes = self._meshes_for(r, gpu, vertices, faces, lambda: _host(vertices), lambda: _host(faces, np.int32), tex_ref, tex_host)
+            outs, tapes = [], []
+            for b, m in enumerate(meshes):
+                cam = dict(ndc=True) if ndc else dict(K=cams[b][0], R=cams[b][1], t=cams[b][2], orig_size=float(orig_size))
+                rgb, depth, alpha, tp = r.render(m, fill_back=fill_back, lightoff=lightoff, want=want, tape=tape, **cam)
+                outs.append((rgb, depth, alpha))
+                tapes.append(tp)
+            stacked = tuple(np.stack([o[i] for o in outs]) for i, nm in enumerate(("rgb", "depth", "alpha")) if nm in want)
+            return stacked, tapes
+
+        if grad_on and _is_tensor(textures) and textures.requires_grad:
+            held = _Tapes()
+
+            def forward(tex_array):
+                out, held.tapes = run(lambda: tex_array, True)
+                return out
+
+            def vjp(arrays, cotangents):
+                if not held.tapes:
+                    raise RuntimeError("neural_renderer.Renderer: this render's tape was freed by an earlier backward pass")
+                g_rgb = cotangents[0] if "rgb" in want else None        # depth and alpha cotangents: zero
+                if g_rgb is None:
+                    grad = np.zeros(arrays[0].shape, np.float32)
+                else:
+                    grad = np.stack([tp.texture_grad(g_rgb[b]) for b, tp in enumerate(held.tapes)])
+                held.close()
+                return [grad]
+
+            out = _autograd.apply(forward, vjp, [textures])
+            out = tuple(o.to(like.device) for o in out) if _is_tensor(like) else out
+        else:
+            out, _ = run(lambda: _host(tex_ref), False)
+            if _is_tensor(like):
+                import torch
+                out = tuple(torch.from_numpy(o).to(like.device) for o in out)
+        return out
+
+    # ---- the reference's methods ----
+    def forward(self, vertices, faces, textures=None, mode=None, K=None, R=None, t=None, dist_coeffs=None, orig_size=None, lightoff=False):
+        """renderer.py:65-80"""
+        if mode is None:
+            return self.render(vertices, faces, textures, K, R, t, dist_coeffs, orig_size, lightoff=lightoff)
+        elif mode == 'rgb':
+            return self.render_rgb(vertices, faces, textures, K, R, t, dist_coeffs, orig_size, lightoff=lightoff)
+        elif mode == 'silhouettes':
+            return self.render_silhouettes(vertices, faces, K, R, t, dist_coeffs, orig_size)
+        elif mode == 'depth':
+            return self.render_depth(vertices, faces, K, R, t, dist_coeffs, orig_size)
+        raise ValueError("mode should be one of None, 'silhouettes' or 'depth'")
+
+    def render_silhouettes(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        """renderer.py:82-126 -> alpha [B, H, W]"""
+        return self._render(vertices, faces, None, K, R, t, dist_coeffs, orig_size, True, ("alpha",))[0]
+
+    def render_depth(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        """renderer.py:128-172 -> depth [B, H, W] (far where nothing is drawn)"""
+        return self._render(vertices, faces, None, K, R, t, dist_coeffs, orig_size, True, ("depth",))[0]
+
+    def render_rgb(self, vertices, faces, textures, K=None, R=None, t=None, dist_coeffs=None, orig_size=None, lightoff=False):
+        """renderer.py:174-232 -> rgb [B, 3, H, W]"""
+        return self._render(vertices, faces, textures, K, R, t, dist_coeffs, orig_size, lightoff, ("rgb",))[0]
+
+    def render(self, vertices, faces, textures, K=None, R=None, t=None, dist_coeffs=None, orig_size=None, lightoff=False):
+        """renderer.py:234-292 -> (rgb [B, 3, H, W], depth [B, H, W], alpha [B, H, W])"""
+        return self._render(vertices, faces, textures, K, R, t, dist_coeffs, orig_size, lightoff, ("rgb", "depth", "alpha"))
+
+    def render_texture(self, filename_obj, textures):
+        """renderer.py:294-346: the UV-space image of `textures` [1, NF, ts, ts, ts, 3] over the OBJ's `vt` triangles, front and
+        back, unlit -> (rgb [1, 3, H, W], depth [1, H, W])"""
+        from .texture_dropin import _uv_obj
+        uv, uv_faces = _uv_obj(filename_obj)
+        verts = np.ascontiguousarray(np.concatenate([uv * 2.0 - 1.0, np.ones((len(uv), 1))], 1), dtype=np.float32)[None]      # :303-304
+        return self._render(verts, np.ascontiguousarray(uv_faces, dtype=np.int32)[None], textures, None, None, None, None, None, True,
+                            ("rgb", "depth"), fill_back=True, ndc=True, like=textures)
+
+
+def _torch_device():
+    import torch
+    return torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")      # (the reference's .cuda(); host tensors where there is no GPU to hold them)
+
+
+def load_obj(filename_obj, normalization=False, texture_size=4, load_texture=False, texture_wrapping='REPEAT', use_bilinear=True):
+    """load_obj.py:98-152 through obj_textures.load_obj -> (vertices float32 [NV, 3], faces int32 [NF, 3]) or, with load_texture,
+    (vertices, faces, textures float32 [NF, ts, ts, ts, 3]): tensors on the GPU as the reference returns them"""
+    import torch
+    out = OT.load_obj(filename_obj, normalization=normalization, texture_size=texture_size, load_texture=load_texture,
+                      texture_wrapping=texture_wrapping, use_bilinear=use_bilinear)
+    dev = _torch_device()
+    return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in out)
+
+
+def save_obj(filename, vertices, faces, textures=None):
+    """save_obj.py:40-83 without textures: `v` and `f` lines as the reference writes them"""
+    if textures is not None:
+        raise NotImplementedError("neural_renderer.save_obj: the textured form (create_texture_image, save_obj.py:10-37,44-49) is not built")
+    v, f = _host(vertices, np.float64), _host(faces, np.int64)
+    assert v.ndim == 2
+    assert f.ndim == 2
+    with open(filename, 'w') as fh:
+        fh.write('# %s\n' % os.path.basename(filename))
+        fh.write('#\n')
+        fh.write('\n')
+        for vertex in v:
+            fh.write('v %.8f %.8f %.8f\n' % (vertex[0], vertex[1], vertex[2]))
+        fh.write('\n')
+        for face in f:
+            fh.write('f %d %d %d\n' % (face[0] + 1, face[1] + 1, face[2] + 1))

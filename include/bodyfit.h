@@ -599,6 +599,48 @@ int bf_texfit_step(bf_texfit *x, const float *R, const float *t, const float *K,
 int bf_texfit_loss_grad(bf_texfit *x, const float *R, const float *t, const float *K, float orig_size, double *loss, float *grad);
 int bf_texfit_get_textures(bf_texfit *x, float *textures);
 
+/* ---- neural_renderer.Renderer, stand-alone (thirdparty/neural_renderer/neural_renderer/renderer.py:11-346) --------------------------
+ * The renderer of the torch loop of smplify/texture_fitting.py:240-275 and of utils/io_utils.py's lit renders as an object of its
+ * own, camera_mode='projection' with zero distortion: a renderer (image size, planes, background, light), meshes resident on its
+ * device, and per render a tape from which the textures' gradient of ANY rgb cotangent is formed (backward_textures,
+ * cuda/rasterize_cuda_kernel.cu:498-540).  bodyfitting_amd/neural_renderer.py is the drop-in `import neural_renderer` on top.
+ * Limits: image_size in [1, 4096], texture_size 0 (a mesh without textures) or in [2, 16], 2 x n_faces inside an int -
+ * BF_ERR_UNSUPPORTED above the upper ends; inconsistent arguments are BF_ERR_INVALID before any launch. */
+typedef struct bf_nr bf_nr;
+typedef struct bf_nr_mesh bf_nr_mesh;
+typedef struct bf_nr_tape bf_nr_tape;
+/* Renderer.__init__ (renderer.py:12-63): anti_aliasing = 2 x 2 super-sampling, background[3] (NULL: black, the reference's default),
+ * near < far.  The light starts as the reference's defaults (:17-19): ambient 0.5, directional 0.5, white, direction (0, 1, 0). */
+int bf_nr_create(int device, int image_size, int anti_aliasing, float near, float far, const float *background, bf_nr **out);
+void bf_nr_destroy(bf_nr *r);
+/* light_intensity_ambient / _directional, light_color_ambient[3] / _directional[3], light_direction[3] (renderer.py:55-60) as
+ * nr.lighting (lighting.py:5-57) reads them; a term whose intensity is exactly 0 is skipped (:36,40) */
+int bf_nr_set_light(bf_nr *r, float ambient, float directional, const float *color_ambient, const float *color_directional, const float *direction);
+/* the `vertices`, `faces`, `textures` arguments of Renderer.render* (renderer.py:65-292) kept on the renderer's device:
+ * verts[n_verts][3], faces[n_faces][3] (an index outside [0, n_verts): BF_ERR_INVALID), textures[n_faces][ts][ts][ts][3] or NULL
+ * (set them later; texture_size 0 with NULL: a mesh for silhouette / depth renders only) */
+int bf_nr_mesh_create(bf_nr *r, int n_verts, const float *verts, int n_faces, const int32_t *faces, int texture_size, const float *textures,
+                      bf_nr_mesh **out);
+/* new texture values for the same mesh (texture_fitting.py:270: what optimizer.step() changed); tapes made before stay valid */
+int bf_nr_mesh_set_textures(bf_nr_mesh *m, const float *textures);
+void bf_nr_mesh_destroy(bf_nr_mesh *m);
+/* Renderer.render / render_rgb / render_silhouettes / render_depth (renderer.py:82-292) and, with ndc != 0, render_texture's
+ * rasterisation (:334-346: the vertices are normalised device coordinates already; K, R, t, orig_size are ignored).  K[9], R[9], t[3]
+ * world to camera (projection.py:6-42).  fill_back (:176-178): every face is also drawn with its corners reversed and its texture
+ * cube's axes 0 and 2 exchanged - without a doubled texture copy.  lightoff (:180): no lighting; otherwise every face record is lit
+ * from its world-space corners (lighting.py:5-57).  -> rgb[3][image_size][image_size], depth[image_size][image_size] (far where
+ * empty) and alpha[image_size][image_size] (rasterize.py:181-184), flipped and 2 x 2-pooled (rasterize.py:305-326); each may be NULL.
+ * tape (may be NULL) receives what bf_nr_tape_texture_grad needs of THIS render.  rgb or a tape of a mesh without textures, a mesh
+ * of another renderer: BF_ERR_INVALID.  Tile lists that overflow their first guess are grown and the render repeated. */
+int bf_nr_render(bf_nr *r, bf_nr_mesh *m, const float *K, const float *R, const float *t, float orig_size, int fill_back, int lightoff, int ndc,
+                 float *rgb, float *depth, float *alpha, bf_nr_tape **tape);
+/* backward_textures (cuda/rasterize_cuda_kernel.cu:498-540) of the taped render through pooling, flip, background mask, sampling
+ * weight x light and the back records' axis exchange: grad_rgb[3][image_size][image_size] ->
+ * grad_textures[n_faces][ts][ts][ts][3], fully written (front and back contributions of a face add).  The textures themselves are
+ * not read: the tape outlives bf_nr_mesh_set_textures and its mesh.  A tape whose renderer was destroyed: BF_ERR_INVALID. */
+int bf_nr_tape_texture_grad(bf_nr_tape *tape, const float *grad_rgb, float *grad_textures);
+void bf_nr_tape_destroy(bf_nr_tape *tape);
+
 /* ---- HMR initial estimate (smplify/body_fitting.py:17-75, models/hmr.py) ----------------------------------------------------------
  * The reference's run_hmr on the GPU in fp32: cv2.resize to 224 x 224 (INTER_LINEAR, OpenCV's 8-bit fixed-point arithmetic), /255,
  * Normalize(IMG_NORM_MEAN, IMG_NORM_STD), ResNet-50 v1.5 in eval() and the iterative regressor (n_iter = 3).  Weights are packed by
