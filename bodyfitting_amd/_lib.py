@@ -202,6 +202,9 @@ SIGNATURES = {
     "bf_nr_render": (C.c_int, [_VP, _VP, _FP, _FP, _FP, C.c_float, C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.POINTER(_VP)]),
     "bf_nr_tape_texture_grad": (C.c_int, [_VP, _FP, _FP]),
     "bf_nr_tape_destroy": (None, [_VP]),
+    "bf_nr_mesh_set_vertices": (C.c_int, [_VP, _FP]),
+    "bf_nr_render_taped": (C.c_int, [_VP, _VP, _FP, _FP, _FP, C.c_float, C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.c_int, C.POINTER(_VP)]),
+    "bf_nr_tape_vertex_grad": (C.c_int, [_VP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "bf_hmr_n_weights": (C.c_int64, []),
     "bf_hmr_create": (C.c_int, [C.c_int, _FP, C.c_int64, _FP, C.c_int, C.POINTER(_VP)]),
     "bf_hmr_destroy": (None, [_VP]),

@@ -191,3 +191,287 @@ bf_nr_backward_large_kernel(int nf, int is, int out, int aa, const float *__rest
     float *gt = grad_tex + (size_t)(back ? k - nf : k) * ts * ts * ts * 3;
     nr_pixel_vjp(pp, rec, light, k, back, ts, g, [&](int at, float v) { atomicAdd(gt + at, v); });
 }
+
+// ---- the geometry gradient: backward_pixel_map + backward_depth_map (cuda/rasterize_cuda_kernel.cu:245-503,543-592), the light's and
+// the projection's reverse (lighting.py:41-52, projection.py:19-42) ----
+//   bf_nr_unlit_kernel      per super-sampled pixel the texture sample WITHOUT the light, sum(wt * texel): what dL/dlight multiplies
+//   bf_nr_geometry_kernel   one wave per record: the soft-edge walks (lanes share a walk's pixels), then the depth terms and dL/dlight
+//                           gathered over the record's pixel box; every row of grad_frec / grad_lrec written once, fixed order
+//   bf_nr_fold_kernel       one thread per vertex: its incident (record, corner) rows in table order, then the projection's reverse;
+//                           per block a fixed-order tree of dp and dp (x) v
+//   bf_nr_fold_sum_kernel   the blocks' partial sums in block order -> grad_R[9] | grad_t[3]
+extern "C" __global__ void __launch_bounds__(256)
+bf_nr_unlit_kernel(int is, int nf, const float *__restrict__ pix, const float *__restrict__ frec, const float *__restrict__ textures, int ts,
+                   float *__restrict__ unlit) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= is * is) return;
+    const float *pp = pix + (size_t)i * 5;
+    const int k = __float_as_int(pp[4]);
+    float acc[3] = {0.f, 0.f, 0.f};
+    if (k >= 0) {
+        const bool back = k >= nf;
+        const float w[3] = {pp[0], pp[1], pp[2]};
+        int idx[8];
+        float wt[8];
+        tex_corners(w, pp[3], frec + (size_t)k * BF_TEX_REC, ts, idx, wt);
+        const float *tex = textures + (size_t)(back ? k - nf : k) * ts * ts * ts * 3;
+#pragma unroll
+        for (int corner = 0; corner < 8; ++corner) {
+            const int at = nr_texel(idx[corner], ts, back) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += wt[corner] * tex[at + c];
+        }
+    }
+    unlit[(size_t)i * 3] = acc[0]; unlit[(size_t)i * 3 + 1] = acc[1]; unlit[(size_t)i * 3 + 2] = acc[2];
+}
+
+__device__ __forceinline__ float nr_wave_sum(float v) {      // fixed butterfly: equal inputs, equal bits
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// one line d0 of one edge along one axis: axis 0 walks columns (d0 = x, d1 = y), axis 1 rows (d0 = y, d1 = x)
+struct NrLine { float p00, p10, cross; int d0, axis; };
+
+__device__ __forceinline__ size_t nr_line_pixel(const NrLine &ln, int d1, int is) {
+    return ln.axis == 0 ? (size_t)d1 * is + ln.d0 : (size_t)ln.d0 * is + d1;
+}
+
+// diff_grad of pixel o against the reference pixel's (alpha, rgb): (alpha - alpha_ref) g_alpha, then the three colour terms, float32
+__device__ __forceinline__ float nr_diff_grad(const NrGeo &G, size_t o, float a_ref, const float rgb_ref[3]) {
+    const int yi = (int)(o / G.is), xi = (int)(o - (size_t)yi * G.is);
+    float diff = 0.f;
+    if (G.g_alpha) {
+        const float a = __float_as_int(G.pix[o * 5 + 4]) >= 0 ? 1.f : 0.f;
+        diff += (a - a_ref) * tex_pixel_grad1(yi, xi, G.is, G.out, G.aa, G.g_alpha);
+    }
+    if (G.g_rgb) {
+        float g[3];
+        tex_pixel_grad(yi, xi, G.is, G.out, G.aa, G.g_rgb, g);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) diff += (G.rgbmap[o * 3 + c] - rgb_ref[c]) * g[c];
+    }
+    return diff;
+}
+
+// pixels d1 in [from, to] of a line, dealt to the lanes: acc0 / acc1 -= diff_grad / dist for the edge's two end points.  own >= 0: only
+// pixels whose record is `own` (the "in" walk)
+__device__ __forceinline__ void nr_walk(const NrGeo &G, const NrLine &ln, int from, int to, int own, int lane, float a_ref, const float rgb_ref[3],
+                                        float &acc0, float &acc1) {
+    const float fd0 = (float)ln.d0;
+    for (int d1 = from + lane; d1 <= to; d1 += 64) {
+        const size_t o = nr_line_pixel(ln, d1, G.is);
+        if (own >= 0 && __float_as_int(G.pix[o * 5 + 4]) != own) continue;
+        const float diff = nr_diff_grad(G, o, a_ref, rgb_ref);
+        if (diff <= 0.f) continue;
+        const float off = (float)d1 - ln.cross;
+        if (ln.p10 != fd0) acc0 -= diff / tex_edge_dist(ln.p10 - ln.p00, ln.p10 - fd0, off, G.is);
+        if (ln.p00 != fd0) acc1 -= diff / tex_edge_dist(ln.p10 - ln.p00, fd0 - ln.p00, off, G.is);
+    }
+}
+
+// grid nrec, one wave per record k.  grad_frec[nrec][3][3]: dL/d(the record's projected corners); grad_lrec[nrec][3][3] (NULL unless
+// the render was lit with a directional term and has an rgb cotangent): dL/d(its world-space corners) through its light row.
+extern "C" __global__ void __launch_bounds__(64)
+bf_nr_geometry_kernel(NrGeo G, NrLight L, float *__restrict__ grad_frec, float *__restrict__ grad_lrec) {
+    __shared__ float s_g[9], s_p[6];
+    const int k = blockIdx.x, lane = threadIdx.x, is = G.is;
+    const bool back = k >= G.nf;
+    const int fn = back ? k - G.nf : k;
+    int vid[3];
+    float f[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        vid[c] = G.faces[(size_t)fn * 3 + (back ? 2 - c : c)];
+        const float *v = G.pv + (size_t)vid[c] * 3;
+        f[c * 3] = v[0]; f[c * 3 + 1] = v[1]; f[c * 3 + 2] = v[2];
+    }
+    const TexTri tri = tex_tri(f);
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) s_g[i] = 0.f;
+#pragma unroll
+        for (int n = 0; n < 3; ++n) { s_p[2 * n] = 0.5f * (tri.x[n] * is + is - 1); s_p[2 * n + 1] = 0.5f * (tri.y[n] * is + is - 1); }
+    }
+    __builtin_amdgcn_wave_barrier();
+    const bool shown = !tex_back_facing(tri);                        // (:270 - a record that shows its back gets zeros)
+    if (shown && (G.g_rgb || G.g_alpha)) {
+        for (int e = 0; e < 3; ++e) {
+            const int i0 = e, i1 = (e + 1) % 3, i2 = (e + 2) % 3;
+            for (int axis = 0; axis < 2; ++axis) {
+                const float p00 = s_p[2 * i0 + axis], p01 = s_p[2 * i0 + 1 - axis], p10 = s_p[2 * i1 + axis], p11 = s_p[2 * i1 + 1 - axis];
+                const float p20 = s_p[2 * i2 + axis], p21 = s_p[2 * i2 + 1 - axis];
+                if (p00 == p10) continue;                            // axis-parallel: no line, or the reference's 0 / 0 at an integer coordinate
+                const int direction = (axis == 0) == (p00 < p10) ? -1 : 1;
+                const int d0_from = (int)fmaxf(fminf(ceilf(fminf(p00, p10)), (float)is), 0.f);
+                const int d0_to = (int)fminf(fmaxf(fmaxf(p00, p10), -2.f), is - 1.f);        // ((int) truncates: (-1, 0) -> 0 as in the reference)
+                float acc0 = 0.f, acc1 = 0.f;
+                for (int d0 = d0_from; d0 <= d0_to; ++d0) {
+                    NrLine ln{p00, p10, tex_edge_cross(p00, p01, p10, p11, (float)d0), d0, axis};
+                    if (!(ln.cross > -2.f && ln.cross < is + 1.f)) continue;                 // (d1_in would be off the image)
+                    const int d1_in = direction > 0 ? (int)floorf(ln.cross) : (int)ceilf(ln.cross), d1_out = d1_in + direction;
+                    if (d1_in < 0 || is <= d1_in || d1_out < 0 || is <= d1_out) continue;
+                    const size_t o_in = nr_line_pixel(ln, d1_in, is), o_out = nr_line_pixel(ln, d1_out, is);
+                    const int k_in = __float_as_int(G.pix[o_in * 5 + 4]), k_out = __float_as_int(G.pix[o_out * 5 + 4]);
+                    float rgb_in[3] = {0.f, 0.f, 0.f}, rgb_out[3] = {0.f, 0.f, 0.f};
+                    if (G.g_rgb) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) { rgb_in[c] = G.rgbmap[o_in * 3 + c]; rgb_out[c] = G.rgbmap[o_out * 3 + c]; }
+                    }
+                    if (k_in == k) {                                 // out: from the crossing to the image border
+                        const int lim = direction > 0 ? is - 1 : 0;
+                        nr_walk(G, ln, max(min(d1_out, lim), 0), min(max(d1_out, lim), is - 1), -1, lane, k_in >= 0 ? 1.f : 0.f, rgb_in, acc0, acc1);
+                    }
+                    {                                                // in: from the crossing to the other edge, over this record's pixels
+                        const float fd0 = (float)d0;
+                        const float c2 = (fd0 - p00) * (fd0 - p20) < 0 ? tex_edge_cross(p00, p01, p20, p21, fd0) : tex_edge_cross(p20, p21, p10, p11, fd0);
+                        const int lim = tex_to_int(direction > 0 ? ceilf(c2) : floorf(c2), -1, is);
+                        nr_walk(G, ln, max(min(d1_in, lim), 0), min(max(d1_in, lim), is - 1), k, lane, k_out >= 0 ? 1.f : 0.f, rgb_out, acc0, acc1);
+                    }
+                }
+                acc0 = nr_wave_sum(acc0); acc1 = nr_wave_sum(acc1);
+                if (lane == 0) { s_g[i0 * 3 + 1 - axis] += acc0; s_g[i1 * 3 + 1 - axis] += acc1; }
+            }
+        }
+    }
+    // depth terms and dL/dlight: the pixels this record owns, gathered over its box
+    float gd[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dl[3] = {0.f, 0.f, 0.f};
+    const float *rec = G.frec + (size_t)k * BF_TEX_REC;
+    const int bx = __float_as_int(rec[18]), by = __float_as_int(rec[19]);
+    const int x0 = bx & 0xffff, x1 = bx >> 16, y0 = by & 0xffff, y1 = by >> 16, W = x1 - x0 + 1, H = y1 - y0 + 1;
+    if (W > 0 && H > 0 && (G.g_depth || grad_lrec)) {
+        float tmp[2] = {0.f, 0.f};
+#pragma unroll
+        for (int l = 0; l < 2; ++l)
+#pragma unroll
+            for (int m = 0; m < 3; ++m) tmp[l] += -rec[9 + 3 * m + l] / rec[3 * m + 2];
+        for (int p = lane; p < W * H; p += 64) {
+            const int yi = y0 + p / W, xi = x0 + p % W;
+            const size_t o = (size_t)yi * is + xi;
+            const float *pp = G.pix + o * 5;
+            if (__float_as_int(pp[4]) != k) continue;
+            if (G.g_depth) {
+                const float g = tex_pixel_grad1(yi, xi, is, G.out, G.aa, G.g_depth), depth2 = pp[3] * pp[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float z = rec[3 * c + 2];
+                    gd[3 * c + 2] += g * pp[c] * depth2 / (z * z);
+#pragma unroll
+                    for (int l = 0; l < 2; ++l) gd[3 * c + l] += -g * tmp[l] * pp[c] * depth2 * is / 2;
+                }
+            }
+            if (grad_lrec) {
+                float g[3];
+                tex_pixel_grad(yi, xi, is, G.out, G.aa, G.g_rgb, g);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) dl[c] += G.unlit[o * 3 + c] * g[c];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) gd[i] = nr_wave_sum(gd[i]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dl[c] = nr_wave_sum(dl[c]);
+    __builtin_amdgcn_wave_barrier();
+    if (lane != 0) return;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) grad_frec[(size_t)k * 9 + i] = s_g[i] + gd[i];
+    if (!grad_lrec) return;
+    // the reverse of nr_face_light: light = .. + directional * (color * relu(n^ . d)), n^ = n / max(|n|, 1e-5), n = (c0 - c1) x (c2 - c1)
+    float out[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float *c0 = G.verts + (size_t)vid[0] * 3, *c1 = G.verts + (size_t)vid[1] * 3, *c2 = G.verts + (size_t)vid[2] * 3;
+    float a[3], b[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { a[c] = c0[c] - c1[c]; b[c] = c2[c] - c1[c]; }
+    const float n[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+    const float norm = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]), len = fmaxf(norm, 1e-5f);
+    const float nh[3] = {n[0] / len, n[1] / len, n[2] / len};
+    const float s = (nh[0] * L.direction[0] + nh[1] * L.direction[1]) + nh[2] * L.direction[2];
+    if (s > 0.f) {                                                   // (relu: derivative 0 at 0)
+        const float dcos = L.directional * ((dl[0] * L.color_directional[0] + dl[1] * L.color_directional[1]) + dl[2] * L.color_directional[2]);
+        float dn[3] = {dcos * L.direction[0], dcos * L.direction[1], dcos * L.direction[2]};       // d / d n^
+        if (norm >= 1e-5f) {                                         // (below it the denominator is the constant 1e-5)
+            const float along = (nh[0] * dn[0] + nh[1] * dn[1]) + nh[2] * dn[2];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dn[c] = dn[c] - nh[c] * along;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dn[c] = dn[c] / len;
+        const float da[3] = {b[1] * dn[2] - b[2] * dn[1], b[2] * dn[0] - b[0] * dn[2], b[0] * dn[1] - b[1] * dn[0]};       // b x dn
+        const float db[3] = {dn[1] * a[2] - dn[2] * a[1], dn[2] * a[0] - dn[0] * a[2], dn[0] * a[1] - dn[1] * a[0]};       // dn x a
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { out[c] = da[c]; out[3 + c] = -(da[c] + db[c]); out[6 + c] = db[c]; }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) grad_lrec[(size_t)k * 9 + i] = out[i];
+}
+
+// thread = vertex i.  vstart[nv + 1], ventry[]: its (record * 3 + corner) rows, ascending; rows of records >= nrec are not drawn.
+// V.orig < 0 (ndc): grad_verts is the sum itself.  partial[blocks][12]: the block's sums of dp (x) v [9] | dp [3], NULL with ndc.
+extern "C" __global__ void __launch_bounds__(256)
+bf_nr_fold_kernel(int nv, int nrec, const int *__restrict__ vstart, const int *__restrict__ ventry, const float *__restrict__ grad_frec,
+                  const float *__restrict__ grad_lrec, const float *__restrict__ verts, TexView V, float *__restrict__ grad_verts,
+                  float *__restrict__ partial) {
+    __shared__ float s_r[12][256];
+    const int i = blockIdx.x * 256 + threadIdx.x, tid = threadIdx.x;
+    float gn[3] = {0.f, 0.f, 0.f}, gw[3] = {0.f, 0.f, 0.f}, red[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (i < nv) {
+        for (int e = vstart[i]; e < vstart[i + 1]; ++e) {
+            const int row = ventry[e];
+            if (row >= nrec * 3) break;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gn[c] += grad_frec[(size_t)row * 3 + c];
+            if (grad_lrec) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) gw[c] += grad_lrec[(size_t)row * 3 + c];
+            }
+        }
+        float gv[3];
+        if (V.orig < 0.f) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gv[c] = gn[c] + gw[c];
+        } else {
+            const float a = verts[(size_t)i * 3], b = verts[(size_t)i * 3 + 1], c = verts[(size_t)i * 3 + 2];
+            const float x = ((a * V.R[0] + b * V.R[1]) + c * V.R[2]) + V.t[0];
+            const float y = ((a * V.R[3] + b * V.R[4]) + c * V.R[5]) + V.t[1];
+            const float z = ((a * V.R[6] + b * V.R[7]) + c * V.R[8]) + V.t[2];
+            const float zi = z + 1e-9f;
+            const float du = gn[0] * 2.f / V.orig, dw = -(gn[1] * 2.f / V.orig);      // u = 2 (u - orig / 2) / orig; v = orig - v first
+            const float dx_ = du * V.K[0] + dw * V.K[3], dy_ = du * V.K[1] + dw * V.K[4];
+            const float dp[3] = {dx_ / zi, dy_ / zi, gn[2] - (dx_ * x + dy_ * y) / (zi * zi)};
+            const float v[3] = {a, b, c};
+#pragma unroll
+            for (int j = 0; j < 3; ++j) gv[j] = ((V.R[j] * dp[0] + V.R[3 + j] * dp[1]) + V.R[6 + j] * dp[2]) + gw[j];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                red[9 + r] = dp[r];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) red[3 * r + j] = dp[r] * v[j];
+            }
+        }
+        grad_verts[(size_t)i * 3] = gv[0]; grad_verts[(size_t)i * 3 + 1] = gv[1]; grad_verts[(size_t)i * 3 + 2] = gv[2];
+    }
+    if (!partial) return;                                            // (block-uniform)
+#pragma unroll
+    for (int q = 0; q < 12; ++q) s_r[q][tid] = red[q];
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (tid < s) {
+#pragma unroll
+            for (int q = 0; q < 12; ++q) s_r[q][tid] += s_r[q][tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid < 12) partial[(size_t)blockIdx.x * 12 + tid] = s_r[tid][0];
+}
+
+// one block of 64: lane q < 12 adds the blocks' partial sums in block order -> out[12] = grad_R[9] | grad_t[3]
+extern "C" __global__ void __launch_bounds__(64)
+bf_nr_fold_sum_kernel(int blocks, const float *__restrict__ partial, float *__restrict__ out) {
+    const int q = threadIdx.x;
+    if (q >= 12) return;
+    float s = 0.f;
+    for (int b = 0; b < blocks; ++b) s += partial[(size_t)b * 12 + q];
+    out[q] = s;
+}

@@ -179,3 +179,26 @@ __device__ __forceinline__ void tex_pixel_grad(int yi, int xi, int is, int out, 
 #pragma unroll
     for (int c = 0; c < 3; ++c) g[c] = grad_image[((size_t)c * out + oy) * out + ox] * (aa ? 0.25f : 1.f);
 }
+
+// the same for a one-channel map (depth, alpha)
+__device__ __forceinline__ float tex_pixel_grad1(int yi, int xi, int is, int out, int aa, const float *__restrict__ grad_map) {
+    const int yf = is - 1 - yi, oy = aa ? yf >> 1 : yf, ox = aa ? xi >> 1 : xi;
+    return grad_map[(size_t)oy * out + ox] * (aa ? 0.25f : 1.f);
+}
+
+// backward_pixel_map's signed distance of pixel d1 from an edge's end point, in normalised device units (rasterize_cuda_kernel.cu:404-405):
+// `num / den * off * 2. / is` - float32 up to the literal 2., double from there, rounded back - pushed away from 0 by rasterizer_eps = 1e-3
+__device__ __forceinline__ float tex_edge_dist(float num, float den, float off, int is) {
+    const float d = (float)((double)(num / den * off) * 2. / (double)is);
+    return 0.f < d ? d + 1e-3f : d - 1e-3f;
+}
+
+// the crossing of line d0 with the edge (a0, a1) -> (b0, b1), first coordinate along the line index (rasterize_cuda_kernel.cu:317,421,424)
+__device__ __forceinline__ float tex_edge_cross(float a0, float a1, float b0, float b1, float d0) {
+    return (b1 - a1) / (b0 - a0) * (d0 - a0) + a1;
+}
+
+// float -> int as the reference's target converts it: NaN -> 0, saturating (here: to [lo, hi], which the callers clamp to anyway)
+__device__ __forceinline__ int tex_to_int(float v, int lo, int hi) {
+    return v != v ? 0 : (int)fminf(fmaxf(v, (float)lo), (float)hi);
+}

@@ -426,6 +426,9 @@ class Silhouette:
             pass
 
 
+TAPE_TEXTURES, TAPE_GEOMETRY = 1, 2          # BF_NR_TAPE_*
+
+
 class NrRenderer:
     """bf_nr: neural_renderer.Renderer's image size, planes, background and light on one GPU (renderer.py:12-63)"""
 
@@ -454,6 +457,20 @@ class NrRenderer:
                                           _lib.fptr(alpha), C.byref(h) if tape else None), "bf_nr_render")
         return rgb, depth, alpha, (NrTape(h, mesh.textures_shape) if tape else None)
 
+    def render_taped(self, mesh, K=None, R=None, t=None, orig_size=1.0, fill_back=True, lightoff=False, ndc=False, want=("rgb", "depth", "alpha"),
+                     flags=TAPE_GEOMETRY):
+        """bf_nr_render_taped: `render` with a tape that keeps what `flags` (TAPE_TEXTURES | TAPE_GEOMETRY) names"""
+        n = self.image_size
+        rgb = np.empty((3, n, n), np.float32) if "rgb" in want else None
+        depth = np.empty((n, n), np.float32) if "depth" in want else None
+        alpha = np.empty((n, n), np.float32) if "alpha" in want else None
+        cam = [None, None, None] if ndc else [_f32(K, (3, 3)), _f32(R, (3, 3)), _f32(t, (3,))]
+        h = C.c_void_p()
+        _lib.check(self._lib.bf_nr_render_taped(self._h, mesh._h, _lib.fptr(cam[0]), _lib.fptr(cam[1]), _lib.fptr(cam[2]), float(orig_size),
+                                                int(bool(fill_back)), int(bool(lightoff)), int(bool(ndc)), _lib.fptr(rgb), _lib.fptr(depth),
+                                                _lib.fptr(alpha), int(flags), C.byref(h)), "bf_nr_render_taped")
+        return rgb, depth, alpha, NrTape(h, mesh.textures_shape, mesh.n_verts, n)
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.bf_nr_destroy(self._h)
@@ -473,7 +490,7 @@ class NrMesh:
         self._lib = _lib.load()
         v, f = _f32(verts, (-1, 3)), _i32(np.asarray(faces).reshape(-1, 3))
         ts = int(texture_size)
-        self.textures_shape = (len(f), ts, ts, ts, 3)
+        self.textures_shape, self.n_verts = (len(f), ts, ts, ts, 3), len(v)
         tex = None if textures is None else _f32(textures, self.textures_shape)
         self._h = C.c_void_p()
         _lib.check(self._lib.bf_nr_mesh_create(renderer._h, len(v), _lib.fptr(v), len(f), _lib.iptr(f), ts, _lib.fptr(tex), C.byref(self._h)),
@@ -481,6 +498,9 @@ class NrMesh:
 
     def set_textures(self, textures):
         _lib.check(self._lib.bf_nr_mesh_set_textures(self._h, _lib.fptr(_f32(textures, self.textures_shape))), "bf_nr_mesh_set_textures")
+
+    def set_vertices(self, verts):
+        _lib.check(self._lib.bf_nr_mesh_set_vertices(self._h, _lib.fptr(_f32(verts, (self.n_verts, 3)))), "bf_nr_mesh_set_vertices")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -495,10 +515,24 @@ class NrMesh:
 
 
 class NrTape:
-    """bf_nr_tape: what the texture VJP needs of one render"""
+    """bf_nr_tape: what the texture VJP and (a geometry tape) the vertex / camera VJP need of one render"""
 
-    def __init__(self, handle, textures_shape):
+    def __init__(self, handle, textures_shape, n_verts=0, image_size=0):
         self._lib, self._h, self.textures_shape = _lib.load(), handle, tuple(textures_shape)
+        self.n_verts, self.image_size = int(n_verts), int(image_size)
+
+    def vertex_grad(self, grad_rgb=None, grad_depth=None, grad_alpha=None, camera=True):
+        """cotangents in the outputs' shapes (None: zero) -> (d / d vertices [NV,3], d / d R [3,3], d / d t [3]); camera=False (an
+        ndc render has none): the last two are None (bf_nr_tape_vertex_grad)"""
+        if not self._h:
+            raise _lib.BodyfitError("NrTape.vertex_grad: the tape was closed")
+        n = self.image_size
+        g = [None if x is None else _f32(x, shape) for x, shape in ((grad_rgb, (3, n, n)), (grad_depth, (n, n)), (grad_alpha, (n, n)))]
+        gv = np.empty((self.n_verts, 3), np.float32)
+        gR, gt = (np.empty((3, 3), np.float32), np.empty(3, np.float32)) if camera else (None, None)
+        _lib.check(self._lib.bf_nr_tape_vertex_grad(self._h, _lib.fptr(g[0]), _lib.fptr(g[1]), _lib.fptr(g[2]), _lib.fptr(gv), _lib.fptr(gR),
+                                                    _lib.fptr(gt)), "bf_nr_tape_vertex_grad")
+        return gv, gR, gt
 
     def texture_grad(self, grad_rgb):
         """grad_rgb[3,is,is] -> d / d textures [NF,ts,ts,ts,3] (bf_nr_tape_texture_grad)"""

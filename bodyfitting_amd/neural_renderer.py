@@ -5,9 +5,17 @@ re-exports this module under the reference's import name.
 
 `Renderer` is thirdparty/neural_renderer/neural_renderer/renderer.py:11-346 for camera_mode='projection' with zero distortion:
 fill-back, ambient + directional light, rgb / depth / alpha, and the gradient of any loss on the rgb image with respect to the
-`textures` - what `loss.backward()` of the loop of texture_fitting.py:262-270 needs.  The soft-edge gradient to vertices and
-cameras (backward_pixel_map, backward_depth_map) is NOT built: inputs that ask for it raise NotImplementedError instead of coming
-back detached.  Every other name of the reference package raises NotImplementedError on access.
+`textures` - what `loss.backward()` of the loop of texture_fitting.py:262-270 needs.  Every other name of the reference package
+raises NotImplementedError on access.
+
+The soft-edge gradient to `vertices`, `R` and `t` (backward_pixel_map, backward_depth_map, and the reverse of lighting.py and
+projection.py; bf_nr_render_taped + bf_nr_tape_vertex_grad) is behind a switch that is off by default:
+`GEOMETRY_GRAD`, read once at import from the environment variable BF_NR_GEOMETRY_GRAD ("1" = on), is what a new Renderer's
+`geometry_grad` attribute starts as; set the attribute like the reference's callers set `renderer.image_size`.  Off, inputs that ask
+for that gradient raise NotImplementedError instead of coming back detached.  On, `vertices`, `R`, `t` and `textures` that require
+grad are the inputs of one autograd node per render (rgb, depth and alpha cotangents all count), a vertex tensor changed in place
+(`optimizer.step()`) keeps its device mesh and only its positions go up again, and `K` that requires grad is still refused: K is
+not differentiated.
 
 Tensors in give float32 tensors out on the vertices' device; arrays in give arrays out.  The device meshes are remembered per
 (vertices, faces) object and GPU - a tensor by identity and `_version`, an array by a digest, four at a time - and a mesh's textures
@@ -33,6 +41,9 @@ name = 'neural_renderer_pytorch'
 _NOT_BUILT = ("get_points_from_angles", "lighting", "look", "look_at", "Mesh", "perspective", "projection", "orthogonal", "rasterize_rgbad",
               "rasterize", "rasterize_silhouettes", "rasterize_depth", "Rasterize", "vertices_to_faces", "cuda")
 _MESH_SLOTS = 4
+GEOMETRY_GRAD = os.environ.get("BF_NR_GEOMETRY_GRAD", "") == "1"
+_NO_K_GRAD = ("neural_renderer.Renderer: K is not differentiated (geometry_grad covers `vertices`, `R` and `t`, not the intrinsics); "
+              "detach K first")
 _NO_VERTEX_GRAD = ("neural_renderer.Renderer: the soft-edge vertex gradient (backward_pixel_map, backward_depth_map of "
                    "cuda/rasterize_cuda_kernel.cu) is not built - only `textures` is differentiated; detach {what} first")
 
@@ -81,6 +92,11 @@ class _Tapes:
     def __init__(self):
         self.tapes = []
 
+    def live(self):
+        if not self.tapes:
+            raise RuntimeError("neural_renderer.Renderer: this render's tape was freed by an earlier backward pass")
+        return self.tapes
+
     def close(self):
         for tp in self.tapes:
             tp.close()
@@ -117,6 +133,7 @@ class Renderer:
         self.light_color_ambient, self.light_color_directional = light_color_ambient, light_color_directional
         self.light_direction = light_direction
         self.rasterizer_eps = 1e-3
+        self.geometry_grad = GEOMETRY_GRAD     # not a constructor parameter (the list above is the reference's)
         self._native = {}           # gpu -> (configuration, native.NrRenderer)
         self._meshes = {}           # key -> dict(v, f: stamps; gpu, ts, meshes [per batch item], tex: stamp of what was last sent)
 
@@ -174,6 +191,12 @@ class Renderer:
         key = (sv[0], id(vertices) if sv[0] == "tensor" else sv[1], sf[0], id(faces) if sf[0] == "tensor" else sf[1], gpu)
         entry = self._meshes.get(key)
         ts = 0 if textures is None else int(textures.shape[2])
+        if (entry is not None and self.geometry_grad and sv[0] == "tensor" and entry["v"][1]() is vertices and entry["v"][2] != sv[2] and
+                _same(entry["f"], faces) and (textures is None or entry["ts"] == ts)):
+            v = v_host()                                 # changed in place (optimizer.step()): the same topology, new positions
+            for b, m in enumerate(entry["meshes"]):
+                m.set_vertices(v[b])
+            entry["v"] = sv
         if entry is not None and not (_same(entry["v"], vertices) and _same(entry["f"], faces) and (textures is None or entry["ts"] == ts)):
             for m in self._meshes.pop(key)["meshes"]:
                 m.close()
@@ -204,9 +227,15 @@ class Renderer:
         if any(_is_tensor(x) for x in (vertices, textures, K, R, t)):
             import torch
             grad_on = torch.is_grad_enabled()
-        if grad_on:
+
+        def wants_grad(x):
+            return grad_on and _is_tensor(x) and x.requires_grad
+
+        if wants_grad(K) and self.geometry_grad:
+            raise NotImplementedError(_NO_K_GRAD)
+        if not self.geometry_grad:
             for what, x in (("vertices", vertices), ("K", K), ("R", R), ("t", t)):
-                if _is_tensor(x) and x.requires_grad:
+                if wants_grad(x):
                     raise NotImplementedError(_NO_VERTEX_GRAD.format(what=what))
         if getattr(vertices, "ndim", 0) != 3 or vertices.shape[2] != 3:
             raise ValueError(f"vertices must be [B, NV, 3], not {tuple(getattr(vertices, 'shape', ()))}")
@@ -235,18 +264,50 @@ class Renderer:
         fill_back = self.fill_back if fill_back is None else fill_back
         tex_ref = textures
 
-        def run(tex_host, tape):
+        def run(tex_host, tape, flags=None):
             meshes = self._meshes_for(r, gpu, vertices, faces, lambda: _host(vertices), lambda: _host(faces, np.int32), tex_ref, tex_host)
             outs, tapes = [], []
             for b, m in enumerate(meshes):
                 cam = dict(ndc=True) if ndc else dict(K=cams[b][0], R=cams[b][1], t=cams[b][2], orig_size=float(orig_size))
-                rgb, depth, alpha, tp = r.render(m, fill_back=fill_back, lightoff=lightoff, want=want, tape=tape, **cam)
+                if flags is None:
+                    rgb, depth, alpha, tp = r.render(m, fill_back=fill_back, lightoff=lightoff, want=want, tape=tape, **cam)
+                else:
+                    rgb, depth, alpha, tp = r.render_taped(m, fill_back=fill_back, lightoff=lightoff, want=want, flags=flags, **cam)
                 outs.append((rgb, depth, alpha))
                 tapes.append(tp)
             stacked = tuple(np.stack([o[i] for o in outs]) for i, nm in enumerate(("rgb", "depth", "alpha")) if nm in want)
             return stacked, tapes
 
-        if grad_on and _is_tensor(textures) and textures.requires_grad:
+        geometry = [x if wants_grad(x) else None for x in (vertices, None if ndc else R, None if ndc else t)] if self.geometry_grad else [None] * 3
+        if any(x is not None for x in geometry):
+            held = _Tapes()
+            tex_in = textures if wants_grad(textures) else None
+            flags = native.TAPE_GEOMETRY | (native.TAPE_TEXTURES if tex_in is not None else 0)
+            names = [nm for nm in ("rgb", "depth", "alpha") if nm in want]
+
+            def forward(v_array, tex_array, R_array, t_array):
+                out, held.tapes = run((lambda: tex_array) if tex_in is not None else (lambda: _host(tex_ref)), True, flags)
+                return out
+
+            def vjp(arrays, cotangents):
+                held.live()
+                g = dict(zip(names, cotangents))
+                per_item = [tp.vertex_grad(*[None if g.get(nm) is None else g[nm][b] for nm in ("rgb", "depth", "alpha")], camera=not ndc)
+                            for b, tp in enumerate(held.tapes)]
+                grads = [np.stack([p[0] for p in per_item]), None, None, None]
+                if tex_in is not None:
+                    grads[1] = (np.zeros(arrays[1].shape, np.float32) if g.get("rgb") is None else
+                                np.stack([tp.texture_grad(g["rgb"][b]) for b, tp in enumerate(held.tapes)]))
+                for slot, i, x in ((2, 1, arrays[2]), (3, 2, arrays[3])):
+                    if x is not None:                        # a camera shared by the batch takes the sum over its items
+                        each = np.stack([p[i] for p in per_item])
+                        grads[slot] = each if x.size == each.size else each.sum(0, dtype=np.float32)
+                held.close()
+                return grads
+
+            out = _autograd.apply(forward, vjp, [geometry[0], tex_in, geometry[1], geometry[2]])
+            out = tuple(o.to(like.device) for o in out) if _is_tensor(like) else out
+        elif grad_on and _is_tensor(textures) and textures.requires_grad:
             held = _Tapes()
 
             def forward(tex_array):
@@ -254,8 +315,7 @@ class Renderer:
                 return out
 
             def vjp(arrays, cotangents):
-                if not held.tapes:
-                    raise RuntimeError("neural_renderer.Renderer: this render's tape was freed by an earlier backward pass")
+                held.live()
                 g_rgb = cotangents[0] if "rgb" in want else None        # depth and alpha cotangents: zero
                 if g_rgb is None:
                     grad = np.zeros(arrays[0].shape, np.float32)

@@ -639,6 +639,27 @@ int bf_nr_render(bf_nr *r, bf_nr_mesh *m, const float *K, const float *R, const 
  * grad_textures[n_faces][ts][ts][ts][3], fully written (front and back contributions of a face add).  The textures themselves are
  * not read: the tape outlives bf_nr_mesh_set_textures and its mesh.  A tape whose renderer was destroyed: BF_ERR_INVALID. */
 int bf_nr_tape_texture_grad(bf_nr_tape *tape, const float *grad_rgb, float *grad_textures);
+/* new positions verts[n_verts][3] for the same topology (what optimizer.step() changed); tapes made before stay valid */
+int bf_nr_mesh_set_vertices(bf_nr_mesh *m, const float *verts);
+/* bf_nr_render with a say in what the tape keeps: tape_flags is a non-empty set of the two below (bf_nr_render with a tape is
+ * BF_NR_TAPE_TEXTURES).  A geometry tape owns, beside a texture tape's pixel map, face records and light rows: this render's
+ * vertices (world and projected), K, R, t, orig_size, the light, the super-sampled colours with the background and - lit, with a
+ * directional term - the unlit texture sample per pixel; it shares the mesh's faces and vertex -> (record, corner) table by
+ * reference count.  It outlives bf_nr_mesh_set_textures, bf_nr_mesh_set_vertices and its mesh.  Without BF_NR_TAPE_TEXTURES (and
+ * without rgb) the mesh needs no textures. */
+#define BF_NR_TAPE_TEXTURES 1
+#define BF_NR_TAPE_GEOMETRY 2
+int bf_nr_render_taped(bf_nr *r, bf_nr_mesh *m, const float *K, const float *R, const float *t, float orig_size, int fill_back, int lightoff, int ndc,
+                       float *rgb, float *depth, float *alpha, int tape_flags, bf_nr_tape **tape);
+/* backward_pixel_map and backward_depth_map (cuda/rasterize_cuda_kernel.cu:245-503,543-592) of the taped render for the cotangents
+ * of its outputs (each in its output's shape, NULL = zero), the reverse of the light (lighting.py:41-52) for a lit colour render, the
+ * sum over each vertex's face corners and the reverse of projection.py:19-42 -> grad_verts[n_verts][3], fully written, and
+ * grad_R[9], grad_t[3] (each may be NULL).  After an ndc render grad_verts is with respect to the vertices as given and grad_R /
+ * grad_t must be NULL.  K is not differentiated.  A line of an edge that is axis-parallel at an integer pixel coordinate (0 / 0 in
+ * the reference) is skipped.  Equal inputs give equal bits.  BF_ERR_INVALID: a tape without BF_NR_TAPE_GEOMETRY, a cotangent for an
+ * output the render did not produce, a tape whose renderer was destroyed. */
+int bf_nr_tape_vertex_grad(bf_nr_tape *tape, const float *grad_rgb, const float *grad_depth, const float *grad_alpha, float *grad_verts, float *grad_R,
+                           float *grad_t);
 void bf_nr_tape_destroy(bf_nr_tape *tape);
 
 /* ---- HMR initial estimate (smplify/body_fitting.py:17-75, models/hmr.py) ----------------------------------------------------------
