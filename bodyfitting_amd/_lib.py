@@ -249,6 +249,7 @@ SIGNATURES = {
     "bf_batch_debug_dump": (C.c_int, [_VP, _FP, C.c_int]),
     "bf_batch_debug_disp_moment": (C.c_int, [_VP, _FP]),
     "bf_batch_debug_vertices": (C.c_int, [_VP, _FP]),
+    "bf_batch_lane_stats": (C.c_int, [_VP, _IP]),
 }
 
 _lib = None

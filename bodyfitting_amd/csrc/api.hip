@@ -52,11 +52,27 @@ int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &told) {
     const MeshTab &Q = p.tab ? *p.tab : m->mesh;          // (the sampled-first sub-model inside a dense loop without scans)
     dim3 grid(Q.n_tiles, n);
     const float *pose_off = nullptr;
-    if (n >= BF_MFMA_MIN_FRAMES && n <= BF_BATCH32_MAX_FRAMES && !p.tab && !p.vposed && bf_mesh_batch32_fits(&m->mesh)) {
+    // a fit-lane group (p.per): the kernel is chosen as for one call's frames.  bf_mesh_kernel's blocks are (tile, frame) - one launch
+    // covers the group; the kernels below tile over frames, so each call's frames get a pass of their own
+    const int n_sel = (p.per > 0 && p.per < n) ? p.per : n;
+    const bool plain = !(n_sel >= BF_MFMA_MIN_FRAMES && !p.tab) && !bf_mesh_use_multi(m->npf, n_sel);
+    if (n_sel < n && !plain) {
+        if (n % n_sel || p.vposed || p.dvzero || p.mproj || p.door || p.mesh_done)
+            return fail(BF_ERR_INVALID, "bf_launch_mesh: a grouped pass carries the result mesh of whole calls only");
+        MeshPass q = p;
+        q.per = 0; q.n = n_sel; q.joints = q.joints_ori = q.jraw = nullptr; q.want_xpart = xpart != nullptr; q.after_mesh = nullptr;
+        const size_t s_state = bf_state_stride(m->nj, m->npf, m->nb), s_v = (size_t)m->nv * 3, s_x = (size_t)Q.n_tiles * Q.n_extra * 3;
+        for (int c = 0; c < n / n_sel; ++c) {
+            const size_t f0 = (size_t)c * n_sel;
+            q.state = p.state + f0 * s_state; q.vraw = p.vraw + f0 * s_v; q.vout = p.vout ? p.vout + f0 * s_v : nullptr;
+            q.xpart = p.xpart ? p.xpart + f0 * s_x : nullptr;
+            BF_TRY(bf_launch_mesh(m, q));
+        }
+    } else if (!plain && n >= BF_MFMA_MIN_FRAMES && n <= BF_BATCH32_MAX_FRAMES && !p.tab && !p.vposed && bf_mesh_batch32_fits(&m->mesh)) {
         // one or two 32-frame blocks: pose blend on the matrix cores with the epilogue behind the accumulators, ONE launch
         // (13.4 us instead of 4.6 + 15.5 + 14.5 at 32 frames; from 128 frames on the 128-frame GEMM tile below wins)
         HIP_TRY(bf_mesh_batch32_launch(&m->mesh, p.state, n, p.vraw, p.vout, xpart, stream));
-    } else if (n >= BF_MFMA_MIN_FRAMES && !p.tab) {
+    } else if (!plain && n >= BF_MFMA_MIN_FRAMES && !p.tab) {
         // batched pose blend on the matrix cores (posedirs streamed once for up to 256 frames), then the per-frame
         // shape / skinning part only
         const size_t ncols = (size_t)m->nv * 3;
@@ -73,7 +89,7 @@ int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &told) {
             bf_mesh_epilogue_batch_launch(&m->mesh, p.state, pose_off, n, p.vraw, p.vout, xpart, stream);
         } else
         hipLaunchKernelGGL(bf_mesh_epilogue_kernel, grid, dim3(128), 0, stream, m->mesh, p.state, pose_off, p.vraw, p.vout, xpart, p.vposed);
-    } else if (bf_mesh_use_multi(m->npf, n)) {
+    } else if (!plain) {
         const int e = bf_mesh_multi_launch(&Q, p.state, n, p.vraw, p.vout, xpart, p.vposed, p.dvzero, stream, p.mproj, p.door, p.door_target,
                                            p.mesh_done);
         if (e) return fail(BF_ERR_HIP, std::string("bf_mesh_multi_kernel: ") + hipGetErrorString((hipError_t)e));
@@ -131,7 +147,27 @@ __global__ void __launch_bounds__(256) __attribute__((visibility("hidden"))) bf_
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) dst[i] = src[i];
 }
 
+
+// Three ranges in one launch: a call's keypoints, initial parameters and view counts into their places in the [W F] arrays of a fit
+// lane's input arena - from the slot's pinned staging buffer (PCIe reads) or from the batch's current inputs on the device.  The
+// places of a slot are float-aligned only (n_params is 86): 4-byte accesses, coalesced.
+struct BfSeg3 { const float *src[3]; float *dst[3]; unsigned n[3]; };
+__global__ void __launch_bounds__(256) __attribute__((visibility("hidden"))) bf_publish3_kernel(BfSeg3 s) {
+    for (int k = 0; k < 3; ++k) {
+        const float *__restrict__ src = s.src[k];
+        float *__restrict__ dst = s.dst[k];
+        for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < s.n[k]; i += gridDim.x * 256) dst[i] = src[i];
+    }
+}
+
 }  // extern "C"
+static int publish3(hipStream_t stream, const BfSeg3 &seg) {
+    const unsigned most = std::max(seg.n[0], std::max(seg.n[1], seg.n[2]));
+    hipLaunchKernelGGL(bf_publish3_kernel, dim3(std::min(std::max((most + 255) / 256, 1u), 64u)), dim3(256), 0, stream, seg);
+    HIP_TRY(hipGetLastError());
+    return BF_OK;
+}
+
 static int publish(hipStream_t stream, float *dst, const float *src, size_t n_floats) {      // (slices are 256-byte multiples: float4 clean)
     const size_t n4 = n_floats / 4;
     hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, stream,
@@ -185,20 +221,41 @@ static void bf_use_arena(bf_batch *b, int k) {
     b->cur = k;
 }
 
-// the input arena an `in_cur` value names: 0 / 1 the batch's own, 2 + 2 * j + a arena a of fit lane j
-static InputArena &input_arena(bf_batch *b, int k) { return k >= 2 ? b->lanes[(k - 2) / 2].in[(k - 2) % 2] : b->in[k]; }
-
-// input arena k becomes the one `keypoints`, `params0`, `ndiv` point at (host = true: at its pinned staging buffer itself)
+// input arena k of the batch's own two becomes the one `keypoints`, `params0`, `ndiv` point at (host = true: at its pinned staging
+// buffer itself)
 static void bf_use_inputs(bf_batch *b, int k, bool host) {
-    InputArena &in = input_arena(b, k);
+    InputArena &in = b->in[k];
     float *base = host ? in.host : in.dev.p;
     const bf_model *m = b->m;
     b->keypoints.slice(base + b->in_off[0], (size_t)b->F * b->V * m->nl_loss * 3);
     b->params0.slice(base + b->in_off[1], (size_t)b->F * m->np);
     b->ndiv.slice((int *)(base + b->in_off[2]), (size_t)b->F);
     b->in_cur = k;
+    b->in_slot = 0;
     b->in_host = host;
 }
+
+// where slot `slot` of a lane's input arena keeps its frames: keypoints, params0, ndiv
+struct SlotPlace { float *kp, *p0; int *ndiv; };
+static SlotPlace slot_place(const bf_batch *b, LaneInputs &in, int slot) {
+    const size_t F = b->F;
+    float *base = in.dev.p;
+    return {base + b->gin_off[0] + slot * F * b->V * b->m->nl_loss * 3, base + b->gin_off[1] + slot * F * b->m->np,
+            (int *)(base + b->gin_off[2]) + slot * F};
+}
+
+// ... of input arena a of fit lane j (in_cur = 2 + 2 * j + a, in_slot = slot)
+static void bf_use_lane_inputs(bf_batch *b, int j, int a, int slot) {
+    const SlotPlace at = slot_place(b, b->lanes[j].in[a], slot);
+    b->keypoints.slice(at.kp, (size_t)b->F * b->V * b->m->nl_loss * 3);
+    b->params0.slice(at.p0, (size_t)b->F * b->m->np);
+    b->ndiv.slice(at.ndiv, (size_t)b->F);
+    b->in_cur = 2 + 2 * j + a;
+    b->in_slot = slot;
+    b->in_host = false;
+}
+// the lane slot the views are on (in_cur >= 2)
+static LaneSlot &current_lane_slot(bf_batch *b) { return b->lanes[(b->in_cur - 2) / 2].in[(b->in_cur - 2) % 2].slot[b->in_slot]; }
 
 // a synchronous setter's write into the current input arena (the stream is idle)
 static hipError_t write_input(bf_batch *b, void *dst, const void *src, size_t bytes) {
@@ -229,22 +286,40 @@ int bf_flush_tail(bf_batch *b) {
 
 /* Fit lanes.  A frame-after-frame fit (the tail-aside conditions of fit_plan) is one workgroup per frame on one CU for ~380 us while
  * the other CUs idle, and the frames of a capture are independent (every call carries BF_FIT_RESET).  With n_lanes > 1 such a fit goes
- * to the next lane (round robin): a stream of its own with its own Adam moments, result arena, mesh scratch and input arenas, so fit
- * i + 1 starts on another CU as soon as it is issued while fit i runs.  A lane's stream holds [input transfer] fit, mesh, joints,
- * hand-over: its own work in order.  Lanes are ordered against each other and against the batch stream by HIP events only
- * (no device-side waits): lanes that end up sharing a hardware queue run one after another, never hang.
+ * to a lane: a stream of its own with its own Adam moments, result arena, mesh scratch and input arenas, so that fits of consecutive
+ * calls run side by side on different CUs.  A lane's stream holds [input transfers] fit, mesh, joints, hand-over: its own work in order.
+ * Lanes are ordered against each other and against the batch stream by HIP events only (no device-side waits): lanes that end up
+ * sharing a hardware queue run one after another, never hang.
+ *   - Lane GROUPS.  The lanes that run side by side are as many as the high-priority pool has hardware queues (four), but the fit kernel
+ *     takes any number of independent frames, one workgroup each, in hardly more time.  So a lane call does not launch at once: it
+ *     JOINS the open group of lane `lane_next` - slot after slot of that lane's input arena, up to W calls - and one launch of G F
+ *     workgroups, one tail and one hand-over serve the G calls that joined (lane_launch).  The group goes out when a call joins while
+ *     its lane is idle (a slow feeder gets G = 1 and no added latency), when it is full (behind the lane's running group), when its
+ *     calls would differ in iterations or hyper-parameters, and at every entry point that drains or reads.  Then `lane_next` moves on.
+ *     BF_FIT_LANE_WIDTH=<n> caps W (default 8; 1: a launch per call, the call sequence before groups); a batch uses at most
+ *     CUs / (lanes x frames).  BF_FIT_LANE_FILL=1 turns the idle rule off - groups fill to W or to a flush - so that tests can force
+ *     group shapes.
  *   - Lanes take over (lanes_engage) behind everything on the batch stream.  Every entry point that is not a lane fit or a staging drains
- *     them first (bf_lanes_drain, from bf_sync_all / bf_guard_arena / fit_impl): it waits for the lane streams and trades the last lane
- *     fit's result arena and Adam moments for the batch's own - the state the tail-aside path leaves - so that continuing fits,
- *     setters, reads, the graph and dense paths run exactly as without lanes.
- *   - bf_batch_stage_inputs fills the next lane's input arena (two per lane, filled alternately) on that lane's stream: the transfer
- *     is ordered behind the fits that last read the arena - the lane's own by stream order, another lane's (a fit that re-used the
- *     inputs without a new staging) by its event - and never behind a running fit of another lane.
+ *     them first (bf_lanes_drain, from bf_sync_all / bf_guard_arena / fit_impl): it launches the open group, waits for the lane streams
+ *     and leaves the last lane fit's result and Adam moments in the batch's own buffers - the state the tail-aside path leaves - so
+ *     that continuing fits, setters, reads, the graph and dense paths run exactly as without lanes.
+ *   - bf_batch_stage_inputs fills the open group's next slot on that lane's stream at once (two input arenas per lane, a group each):
+ *     the transfer is ordered behind the fits that last read the arena by stream order, behind another lane's use of the slot (a call
+ *     without a staging of its own that took the current inputs from it) by that lane's event, and never behind a running fit of
+ *     another lane.  The host waits when the slot's own previous transfer - queued two of the lane's groups ago - has not left its
+ *     pinned buffer.
  * BF_FIT_LANES=<n> sets the lane count (1: no lanes, the single-stream path); a batch uses at most (CUs / frames) of them. */
-static int fit_lanes_wanted() {
-    static const int d = [] { const char *e = getenv("BF_FIT_LANES"); const int v = e ? atoi(e) : 4; return std::max(1, std::min(v, 32)); }();
-    return d;
+static FrameIO bf_frame_io(bf_batch *b, bool want_grads);       // (the batch's own launch arguments: below, with the fit routes)
+static int env_int(const char *name, int dflt, int lo, int hi) {
+    const char *e = getenv(name);
+    return std::max(lo, std::min(e ? atoi(e) : dflt, hi));
 }
+static int fit_lanes_wanted() { static const int d = env_int("BF_FIT_LANES", 4, 1, 32); return d; }
+static int fit_lane_width_wanted() { static const int d = env_int("BF_FIT_LANE_WIDTH", 8, 1, 64); return d; }
+static bool fit_lane_fill() { static const bool d = env_int("BF_FIT_LANE_FILL", 0, 0, 1) == 1; return d; }
+// a group's hand-over from this size on is a copy command, below it the publish kernel: the threshold fit_plan uses for a call.  Measured
+// for groups (profiles/fit_lane_groups.md): the publish kernel for full groups is the slowest, always copying no better than this
+static constexpr size_t kLaneCopyBytes = (size_t)512 * 1024;
 
 static void lanes_release(bf_batch *b) {
     if (!b->lanes) return;
@@ -256,10 +331,14 @@ static void lanes_release(bf_batch *b) {
     if (b->ev_engage) { (void)hipEventDestroy(b->ev_engage); b->ev_engage = nullptr; }
 }
 
+static size_t up64(size_t n) { return (n + 63) & ~(size_t)63; }          // 256-byte slices
+
 static int lanes_create(bf_batch *b) {
     if (b->lanes) return BF_OK;
     const bf_model *m = b->m;
-    const size_t F = b->F, np = m->np;
+    const size_t F = b->F, np = m->np, W = b->lane_w;
+    size_t res_w = 0;                     // a result arena whose arrays hold W calls' frames (W = 1: the batch's res_total)
+    for (int i = 0; i < 5; ++i) res_w += up64(W * b->res_cnt[i]);
     b->lanes.reset(new BfLane[b->n_lanes]);
     int least = 0, greatest = 0;
     bool ok = hipEventCreateWithFlags(&b->ev_engage, hipEventDisableTiming) == hipSuccess &&
@@ -270,10 +349,13 @@ static int lanes_create(bf_batch *b) {
         // and in the normal pool the null stream and the batch stream already hold two of four - three lanes there ran as two,
         // four on the high pool run as four (profiles/fit_lanes.md)
         ok = hipStreamCreateWithPriority(&l.stream, hipStreamNonBlocking, greatest) == hipSuccess &&
-             l.adam_m.alloc(F * np) == hipSuccess && l.adam_v.alloc(F * np) == hipSuccess && l.vraw.alloc(b->vraw.n) == hipSuccess &&
-             l.xpart.alloc(b->xpart.n) == hipSuccess && l.arena.create(b->res_total) == hipSuccess &&
-             l.in[0].create(b->in_total) == hipSuccess && l.in[1].create(b->in_total) == hipSuccess;
+             l.adam_m.alloc(W * F * np) == hipSuccess && l.adam_v.alloc(W * F * np) == hipSuccess && l.vraw.alloc(W * b->vraw.n) == hipSuccess &&
+             l.xpart.alloc(W * b->xpart.n) == hipSuccess && l.arena.create(res_w) == hipSuccess &&
+             l.in[0].create(b->gin_total, b->in_total, (int)W) == hipSuccess && l.in[1].create(b->gin_total, b->in_total, (int)W) == hipSuccess &&
+             (W == 1 || hipEventCreateWithFlags(&l.ev_join, hipEventDisableTiming) == hipSuccess);
     }
+    if (ok && W > 1) ok = b->proj_rep.alloc(W * b->proj.n) == hipSuccess;
+    b->proj_rep_stale = true;
     if (!ok) { lanes_release(b); return fail(BF_ERR_HIP, "fit lanes: creating a lane's stream or buffers failed"); }
     return BF_OK;
 }
@@ -284,6 +366,11 @@ static int lanes_engage(bf_batch *b) {
     if (b->lanes_on) return BF_OK;
     BF_TRY(lanes_create(b));
     BF_TRY(bf_flush_tail(b));
+    if (b->lane_w > 1 && b->proj_rep_stale) {          // (the cameras change through a setter that drains: once per set_cameras)
+        for (int w = 0; w < b->lane_w; ++w)
+            HIP_TRY(hipMemcpyAsync(b->proj_rep.p + (size_t)w * b->proj.n, b->proj.p, b->proj.n * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
+        b->proj_rep_stale = false;
+    }
     HIP_TRY(hipEventRecord(b->ev_engage, b->stream));
     for (int j = 0; j < b->n_lanes; ++j) b->lanes[j].need_engage = true;
     b->lanes_on = true;
@@ -296,8 +383,48 @@ static int lane_begin(bf_batch *b, BfLane &l) {
     return BF_OK;
 }
 
+// The open group of lane j goes out: ONE fit launch for the G F frames of the G calls that joined, the tail for all of them (each
+// call's frames through the kernel and the blocks they would get alone: MeshPass::per), one hand-over of the group's floats, ev_copied.
+// The result arrays are packed for G F frames - FrameIO is array-major over n_frames - and their offsets stay with the group (`held`).
+// The lane's group is closed whatever happens, and the next call joins the next lane.
+static int lane_launch(bf_batch *b, int j) {
+    BfLane &l = b->lanes[j];
+    const int G = l.n_open;
+    if (!G) return BF_OK;
+    l.open = false; l.n_open = 0; l.slot_staged = false;        // (a slot staged past the last call stays the batch's current inputs: the next call copies it)
+    if (b->lane_next == j) b->lane_next = (j + 1) % b->n_lanes;
+    bf_model *m = b->m;
+    ResultArena &r = l.arena;
+    BfLane::Held h;
+    h.seq0 = l.open_seq0; h.G = G;
+    for (int i = 0; i < 5; ++i) { h.off[i] = h.total; h.total += up64((size_t)G * b->res_cnt[i]); }
+    l.held = BfLane::Held{};                                    // (a failure from here on: the arena holds nothing that may be read)
+    r.seq = -1; r.fetched = r.has_v = false;
+    float *d = r.dev.p;
+    FrameIO io = bf_frame_io(b, false);
+    io.n_frames = G * b->F;
+    if (l.borrowed) { io.keypoints = l.bor_kp; io.params0 = l.bor_p0; io.ndiv = l.bor_ndiv; }
+    else { const SlotPlace at = slot_place(b, l.in[l.open_a], 0); io.keypoints = at.kp; io.params0 = at.p0; io.ndiv = at.ndiv; }      // (re-arm inside the fit kernel)
+    if (b->lane_w > 1) io.proj = b->proj_rep.p;
+    io.params = d + h.off[0]; io.terms = d + h.off[1]; io.state = d + h.off[2];
+    io.adam_m = l.adam_m.p; io.adam_v = l.adam_v.p;
+    HIP_TRY(bf_fit_launch(&m->fit, &io, &l.open_hd, l.open_iters, 0, b->adam_tab.p, 0, b->fit_smem, l.stream, nullptr));
+    MeshPass p;
+    p.scr = &l.scratch; p.n = G * b->F; p.per = b->F; p.state = d + h.off[2]; p.stream = l.stream;
+    p.vraw = l.vraw.p; p.vout = d + h.off[4]; p.xpart = l.xpart.p; p.joints = d + h.off[3];
+    BF_TRY(bf_launch_mesh(m, p));
+    BF_TRY(hand_over(l.stream, r, h.total, h.total * sizeof(float) >= kLaneCopyBytes));
+    HIP_TRY(hipEventRecord(r.ev_copied, l.stream));
+    l.held = h;
+    r.seq = h.seq0 + G - 1; r.fetched = r.has_v = true;         // (the arena's newest fit: what a trade in bf_lanes_drain hands on)
+    b->lane_launches += 1;
+    b->lane_max_g = std::max(b->lane_max_g, G);
+    return BF_OK;
+}
+
 int bf_lanes_drain(bf_batch *b) {
     if (!b->lanes_on) return BF_OK;
+    for (int j = 0; j < b->n_lanes; ++j) BF_TRY(lane_launch(b, j));       // (the open group, if calls have joined one)
     b->lanes_on = false;
     for (int j = 0; j < b->n_lanes; ++j)
         if (b->lanes[j].busy) { HIP_TRY(hipStreamSynchronize(b->lanes[j].stream)); b->lanes[j].busy = false; }
@@ -305,19 +432,40 @@ int bf_lanes_drain(bf_batch *b) {
     b->lane_last = -1;
     if (j < 0) return BF_OK;              // (inputs staged, no lane fit since the lanes took over)
     // The last lane fit lands where the tail-aside path leaves a fit - in the result arena the previous fit did not use, with its Adam
-    // moments as the batch's - by trading buffers: the lane takes the batch's arena k and moments (its next fit overwrites them), no
-    // copy.  Nothing on the device uses either side any more (the lane waited for the batch stream before its fit and has finished;
-    // a pipelined fetch of arena k is waited for here); the graphs captured with the old addresses are dropped.
+    // moments as the batch's.  Nothing on the device uses either side any more (the lane waited for the batch stream before its fit and
+    // has finished; a pipelined fetch of arena k is waited for here).
     BfLane &l = b->lanes[j];
     BF_TRY(bf_flush_tail(b));
     const int k = b->cur ^ 1;
     ResultArena &r = b->arena[k];
     if (r.copy_pending) { HIP_TRY(hipEventSynchronize(r.ev_copied)); r.copy_pending = false; }
-    r.trade_buffers(l.arena);
-    std::swap(b->adam_m.p, l.adam_m.p);
-    std::swap(b->adam_v.p, l.adam_v.p);
-    if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
-    for (auto &g : b->graph_pipe) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    if (!l.held.G) {                      // (its launch failed: no result anywhere)
+        b->fetched = b->have_result = false;
+        return fail(BF_ERR_HIP, "fit lanes: the last lane fit was not launched");
+    }
+    if (b->lane_w == 1) {
+        // equal-sized buffers: by trading them - the lane takes the batch's arena k and moments (its next fit overwrites them), no
+        // copy; the graphs captured with the old addresses are dropped
+        r.trade_buffers(l.arena);
+        l.held = BfLane::Held{};
+        std::swap(b->adam_m.p, l.adam_m.p);
+        std::swap(b->adam_v.p, l.adam_v.p);
+        if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
+        for (auto &g : b->graph_pipe) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    } else {
+        // a group's arena is laid out for G calls: the last slot's slices are copied, device to device on the batch stream and mirror
+        // to mirror on the host - once per drain, off the step's path.  The group stays readable in the lane (bf_batch_get_previous).
+        const BfLane::Held &h = l.held;
+        const size_t s = h.G - 1, n_adam = (size_t)b->F * b->m->np;
+        for (int i = 0; i < 5; ++i) {
+            const size_t from = h.off[i] + s * b->res_cnt[i];
+            HIP_TRY(hipMemcpyAsync(r.dev.p + b->res_off[i], l.arena.dev.p + from, b->res_cnt[i] * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
+            std::memcpy(r.host + b->res_off[i], l.arena.host + from, b->res_cnt[i] * sizeof(float));
+        }
+        HIP_TRY(hipMemcpyAsync(b->adam_m.p, l.adam_m.p + s * n_adam, n_adam * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->adam_v.p, l.adam_v.p + s * n_adam, n_adam * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
+        r.seq = h.seq0 + (long long)s; r.fetched = r.has_v = true;
+    }
     bf_use_arena(b, k);
     return BF_OK;
 }
@@ -424,6 +572,11 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
         if (n_cus > 0) b->n_cus = n_cus;
         const int d = std::min(fit_lanes_wanted(), std::max(n_cus, 1) / n_frames);
         b->n_lanes = (!b->stage_zerocopy && d > 1) ? d : 1;
+        // ... and a lane launch carries up to W calls' frames, the lanes' groups together at most a frame per CU
+        b->lane_w = std::min(fit_lane_width_wanted(), std::max(1, std::max(n_cus, 1) / (b->n_lanes * n_frames)));
+        const size_t W = b->lane_w, n_kp = F * n_views * m->nl_loss * 3;
+        b->gin_off[0] = 0; b->gin_off[1] = up64(W * n_kp); b->gin_off[2] = b->gin_off[1] + up64(W * F * np);
+        b->gin_total = b->gin_off[2] + up64(W * F);
     }
     *out = b;
     return BF_OK;
@@ -432,6 +585,8 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
 void bf_batch_destroy(bf_batch *b) {
     if (!b) return;
     b->tail_k = -1;                       // (a tail never enqueued: nobody will read that result)
+    for (int j = 0; b->lanes && j < b->n_lanes; ++j)          // (calls that joined a group were promised a fit: it goes out before the wait)
+        if (b->lanes[j].n_open && hipSetDevice(b->m->device) == hipSuccess) (void)lane_launch(b, j);
     lanes_release(b);                     // (waits for the lanes' work: it reads the batch's inputs, cameras and Adam table)
     if (b->copy_stream) (void)hipStreamSynchronize(b->copy_stream);
     if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
@@ -498,6 +653,7 @@ int bf_batch_set_cameras(bf_batch *b, const float *c2w, const float *K) {
     // bf_fit is asynchronous on the batch's own (non-blocking) stream: a fit still in flight reads these inputs
     BF_TRY(bf_sync_all(b));
     HIP_TRY(hipMemcpy(b->proj.p, proj.data(), proj.size() * sizeof(float), hipMemcpyHostToDevice));
+    b->proj_rep_stale = true;
     return BF_OK;
 }
 
@@ -563,14 +719,14 @@ static void pack_init(const bf_batch *b, const float *init_betas, const float *i
     }
 }
 
-// keypoints | params0 | ndiv of the next frame packed into an input arena's pinned staging buffer, once its previous transfer has left it
-static int pack_staging(const bf_batch *b, InputArena &in, const float *keypoints, const int32_t *n_use_frames, const float *init_betas,
-                        const float *init_pose) {
-    if (in.pending) {
-        HIP_TRY(hipEventSynchronize(in.ev));
-        in.pending = false;
+// keypoints | params0 | ndiv of the next frame packed into a pinned staging buffer (`h`; `ev`, `pending`: its transfer), once its previous
+// transfer has left it
+static int pack_staging(const bf_batch *b, float *h, hipEvent_t ev, bool &pending, const float *keypoints, const int32_t *n_use_frames,
+                        const float *init_betas, const float *init_pose) {
+    if (pending) {
+        HIP_TRY(hipEventSynchronize(ev));
+        pending = false;
     }
-    float *h = in.host;
     std::memcpy(h + b->in_off[0], keypoints, (size_t)b->F * b->V * b->m->nl_loss * 3 * sizeof(float));
     pack_init(b, init_betas, init_pose, h + b->in_off[1]);
     int *nd = (int *)(h + b->in_off[2]);
@@ -592,7 +748,7 @@ int bf_batch_stage_inputs(bf_batch *b, const float *keypoints, const int32_t *n_
     if (b->n_lanes > 1) return stage_lane(b, keypoints, n_use_frames, init_betas, init_pose);
     const int k = b->in_cur ^ 1;
     InputArena &in = b->in[k];
-    BF_TRY(pack_staging(b, in, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: behind a fit that has long finished)
+    BF_TRY(pack_staging(b, in.host, in.ev, in.pending, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: behind a fit that has long finished)
     if (b->stage_zerocopy) {
         // zero-copy: the fit kernel's prologue reads the pinned buffer itself; bf_fit records in.ev behind the fit that read it
         bf_use_inputs(b, k, true);
@@ -621,22 +777,36 @@ int bf_batch_stage_inputs(bf_batch *b, const float *keypoints, const int32_t *n_
 
 static int stage_lane(bf_batch *b, const float *keypoints, const int32_t *n_use_frames, const float *init_betas, const float *init_pose) {
     BF_TRY(lanes_engage(b));
-    const int j = b->lane_next;             // (the lane the next frame-after-frame fit goes to)
+    const int j = b->lane_next;             // (the lane the next frame-after-frame fit joins)
     BfLane &l = b->lanes[j];
     BF_TRY(lane_begin(b, l));
-    const int a = l.in_next;
-    l.in_next ^= 1;
-    InputArena &in = l.in[a];
-    BF_TRY(pack_staging(b, in, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: queued on this lane two of its fits ago)
-    // the fits that read arena a since it was last filled: this lane's are ahead in its stream; another lane's (a fit that re-used
-    // the inputs without a staging of its own) is waited for through that lane's last event
+    if (!l.n_open) {                        // no call has joined: a group on the lane's other arena (a staging after a staging: no wait for the first one's transfer)
+        l.open = true;
+        l.open_a = l.in_next;
+        l.in_next ^= 1;
+    }
+    const int a = l.open_a, slot = l.n_open;
+    LaneInputs &in = l.in[a];
+    LaneSlot &q = in.slot[slot];
+    float *h = in.host + (size_t)slot * b->in_total;
+    BF_TRY(pack_staging(b, h, q.ev, q.pending, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: queued two of this lane's groups ago)
+    // what read arena a since it was last filled: this lane's fits are ahead in its stream; another lane's use of this slot (a call
+    // without a staging of its own: W = 1 its fit reads the slot in place, else it copied the slot when it joined) is waited for
+    // through that lane's event
     for (int r = 0; r < b->n_lanes; ++r)
-        if (r != j && ((in.readers >> r) & 1u)) HIP_TRY(hipStreamWaitEvent(l.stream, b->lanes[r].arena.ev_copied, 0));
-    in.readers = 0;
-    BF_TRY(publish(l.stream, in.dev.p, in.host, b->in_total));
-    HIP_TRY(hipEventRecord(in.ev, l.stream));
-    in.pending = true;
-    bf_use_inputs(b, 2 + 2 * j + a, false);
+        if (r != j && ((q.readers >> r) & 1u))
+            HIP_TRY(hipStreamWaitEvent(l.stream, b->lane_w == 1 ? b->lanes[r].arena.ev_copied : b->lanes[r].ev_join, 0));
+    q.readers = 0;
+    if (b->lane_w == 1) BF_TRY(publish(l.stream, in.dev.p, h, b->in_total));
+    else {
+        const SlotPlace at = slot_place(b, in, slot);
+        BF_TRY(publish3(l.stream, BfSeg3{{h + b->in_off[0], h + b->in_off[1], h + b->in_off[2]}, {at.kp, at.p0, (float *)at.ndiv},
+                                         {(unsigned)b->keypoints.n, (unsigned)b->params0.n, (unsigned)b->ndiv.n}}));
+    }
+    HIP_TRY(hipEventRecord(q.ev, l.stream));
+    q.pending = true;
+    bf_use_lane_inputs(b, j, a, slot);
+    l.slot_staged = true;
     b->staged = true;
     return BF_OK;
 }
@@ -801,26 +971,55 @@ static int ensure_graph(bf_batch *b, hipGraphExec_t &exec, bf_graph_key &exec_ke
     return BF_OK;
 }
 
-// LANE: fit, mesh, joints and hand-over of the next lane's result arena, in the lane's stream order
+// LANE: the call joins the open group of the next lane - its inputs are in the group's next slot (staged there, or copied from the
+// batch's current inputs now) - and the group is launched if its lane is idle or it is full (lane_launch)
 static int fit_lane(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &done) {
     BF_TRY(lanes_engage(b));
-    const int j = b->lane_next;
-    b->lane_next = (j + 1) % b->n_lanes;
+    {
+        // one launch, one n_iters and one set of hyper-parameters: a call that differs starts a group of its own
+        BfLane &o = b->lanes[b->lane_next];
+        if (o.n_open && (o.open_iters != c.n_iters || std::memcmp(&o.open_hd, &hd, sizeof hd) != 0)) BF_TRY(lane_launch(b, b->lane_next));
+    }
+    const int j = b->lane_next, W = b->lane_w;
     BfLane &l = b->lanes[j];
     BF_TRY(lane_begin(b, l));
+    b->fetched = false; b->have_result = false;                 // (a failure from here on: nothing of this call may be read)
+    const int slot = l.n_open;
+    if (slot == 0) { l.open_seq0 = b->fit_seq; l.open_iters = c.n_iters; l.open_hd = hd; l.borrowed = false; }
+    if (!l.slot_staged && W == 1) {
+        // a launch per call: the fit reads the current inputs in place.  Another lane's slot is read without a wait for its transfer,
+        // as before groups (width 1 is that call sequence): the transfer went out on its lane ahead of a fit launch that has since
+        // been issued, and the group path below, which copies earlier - at join time - does wait
+        l.borrowed = true;
+        l.bor_kp = b->keypoints.p; l.bor_p0 = b->params0.p; l.bor_ndiv = b->ndiv.p;
+        if (b->in_cur >= 2) current_lane_slot(b).readers |= 1u << j;
+    } else if (!l.slot_staged) {
+        // no staging of its own: the current inputs (whatever keypoints / params0 / ndiv point at), copied on the lane's stream
+        if (!l.open) { l.open_a = l.in_next; l.in_next ^= 1; }
+        const SlotPlace at = slot_place(b, l.in[l.open_a], slot);
+        if (at.kp != b->keypoints.p) {                          // (else they are this very slot's)
+            if (b->in_cur >= 2 && (b->in_cur - 2) / 2 != j) {   // another lane's slot: behind its transfer, and its next staging behind this copy
+                LaneSlot &src = current_lane_slot(b);
+                HIP_TRY(hipStreamWaitEvent(l.stream, src.ev, 0));
+                src.readers |= 1u << j;
+            }
+            BF_TRY(publish3(l.stream, BfSeg3{{b->keypoints.p, b->params0.p, (const float *)b->ndiv.p}, {at.kp, at.p0, (float *)at.ndiv},
+                                             {(unsigned)b->keypoints.n, (unsigned)b->params0.n, (unsigned)b->ndiv.n}}));
+            HIP_TRY(hipEventRecord(l.ev_join, l.stream));
+        }
+    }
+    l.open = true; l.slot_staged = false;
+    l.n_open = slot + 1;
     b->lane_last = j;
-    ResultArena &r = l.arena;
-    r.seq = -1; r.fetched = false; r.has_v = false;             // (bf_fit numbers the lane's result once the whole call went out)
-    b->fetched = false; b->have_result = false;                 // (a failure from here on: the lane's result stays unfetched and without a mesh, nothing reads it)
-    if (b->in_cur >= 2) input_arena(b, b->in_cur).readers |= 1u << j;
-    float *d = r.dev.p;
-    FrameIO io = bf_frame_io(b, false);
-    io.params0 = b->params0.p;                  // re-arm inside the fit kernel
-    io.params = d + b->res_off[0]; io.terms = d + b->res_off[1]; io.state = d + b->res_off[2];
-    io.adam_m = l.adam_m.p; io.adam_v = l.adam_v.p;
-    HIP_TRY(bf_fit_launch(&b->m->fit, &io, &hd, c.n_iters, 0, b->adam_tab.p, b->steps_done, b->fit_smem, l.stream, nullptr));
-    BF_TRY(enqueue_tail(b, r, l.stream, &l.scratch, l.vraw.p, l.xpart.p, b->res_total, c.big_fetch));
+    b->lane_calls += 1;
     done = {true, true, false};
+    if (l.n_open >= W) return lane_launch(b, j);                // full: behind the lane's running group, in stream order
+    if (!fit_lane_fill()) {                                     // the lane is idle: now, a slow feeder waits for nobody
+        const hipError_t q = hipEventQuery(l.arena.ev_copied);
+        if (q == hipSuccess) return lane_launch(b, j);
+        (void)hipGetLastError();
+        if (q != hipErrorNotReady) HIP_TRY(q);
+    }
     return BF_OK;
 }
 
@@ -836,7 +1035,7 @@ static int graph_grow_scratch(bf_batch *b, const FitCall &c) {
 
 // both graph routes: the graph of call `c` into result arena k (the current one), captured if need be, launched between the timing events
 static int graph_replay(bf_batch *b, const FitCall &c, const bf_hyper &h, const HyperDev &hd, int k, hipGraphExec_t &exec, bf_graph_key &exec_key) {
-    const bf_graph_key key{c.n_iters, c.flags, k | (b->in_cur << 4) | ((int)b->in_host << 12), h};   // (the captured nodes hold the arenas' addresses)
+    const bf_graph_key key{c.n_iters, c.flags, k | (b->in_cur << 4) | ((int)b->in_host << 12) | (b->in_slot << 16), h};   // (the captured nodes hold the arenas' addresses)
     BF_TRY(ensure_graph(b, exec, exec_key, key, c, hd));
     HIP_TRY(hipEventRecord(b->ev[0], b->stream));
     HIP_TRY(hipGraphLaunch(exec, b->stream));
@@ -1023,17 +1222,16 @@ int bf_fit(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
         b->in_aside[b->in_cur] = false;
     }
     BF_TRY(fit_impl(b, n_iters, hyper, flags));
-    // (went to a lane: every other call drains the lanes first, which clears lane_last)
-    ResultArena &r = b->lane_last >= 0 ? b->lanes[b->lane_last].arena : b->arena[b->cur];
-    if (b->lane_last < 0) {
-        if (b->in_cur < 2) b->in_reader[b->in_cur] = b->fit_seq;       // (this fit's number, given to its arena below)
-        if (b->has_masks) {                       // (the arena these masks live in may be overwritten once this fit is done)
-            if (!b->ev_masks_used) HIP_TRY(hipEventCreateWithFlags(&b->ev_masks_used, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(b->ev_masks_used, b->stream));
-        }
-        if (b->in_host) { HIP_TRY(hipEventRecord(b->in[b->in_cur].ev, b->stream)); b->in[b->in_cur].pending = true; }   // (zero-copy: this fit read the pinned buffer)
-    }
     b->staged = false;
+    // (went to a lane - every other call drains the lanes first, which clears lane_last: the call's number is its place in its group)
+    if (b->lane_last >= 0) { b->fit_seq++; return BF_OK; }
+    ResultArena &r = b->arena[b->cur];
+    if (b->in_cur < 2) b->in_reader[b->in_cur] = b->fit_seq;       // (this fit's number, given to its arena below)
+    if (b->has_masks) {                       // (the arena these masks live in may be overwritten once this fit is done)
+        if (!b->ev_masks_used) HIP_TRY(hipEventCreateWithFlags(&b->ev_masks_used, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(b->ev_masks_used, b->stream));
+    }
+    if (b->in_host) { HIP_TRY(hipEventRecord(b->in[b->in_cur].ev, b->stream)); b->in[b->in_cur].pending = true; }   // (zero-copy: this fit read the pinned buffer)
     r.seq = b->fit_seq++;
     r.fetched = b->fetched;
     r.has_v = b->have_result;
@@ -1112,28 +1310,35 @@ int bf_batch_get_previous(bf_batch *b, float *params, float *vertices, float *jo
     if (!b) return fail(BF_ERR_INVALID, "bf_batch_get_previous: null batch");
     const bf_model *m = b->m;
     HIP_TRY(hipSetDevice(m->device));
+    const long long want = b->fit_seq - 2;
+    // with fit lanes the fit before the last may be held by a lane (which keeps its group until that lane's next launch) - in a
+    // launched group, or in the open one, which then goes out now: slot `slot` of lane `lane`
+    int lane = -1, slot = 0;
+    for (int j = 0; b->lanes && want >= 0 && j < b->n_lanes; ++j) {
+        BfLane &l = b->lanes[j];
+        if (l.n_open && want >= l.open_seq0 && want < l.open_seq0 + l.n_open) BF_TRY(lane_launch(b, j));
+        if (l.held.G && want >= l.held.seq0 && want < l.held.seq0 + l.held.G) { lane = j; slot = (int)(want - l.held.seq0); }
+    }
     // (while a lane holds the last fit, the batch's current arena holds the fit before it, if that was not a lane fit)
-    const int k = b->lane_last >= 0 ? b->cur : b->cur ^ 1;
-    // with fit lanes the fit before the last may be held by a lane (which keeps it until that lane's next fit)
-    const ResultArena *prev = &b->arena[k];
-    for (int j = 0; b->lanes && b->fit_seq >= 2 && j < b->n_lanes; ++j)
-        if (b->lanes[j].arena.seq == b->fit_seq - 2) prev = &b->lanes[j].arena;
-    const ResultArena &r = *prev, &last = b->lane_last >= 0 ? b->lanes[b->lane_last].arena : b->arena[b->cur];
-    if (b->fit_seq < 2 || r.seq != b->fit_seq - 2 || !r.fetched || last.seq != b->fit_seq - 1)
+    const ResultArena &r = lane >= 0 ? b->lanes[lane].arena : b->arena[b->lane_last >= 0 ? b->cur : b->cur ^ 1];
+    const bool held = lane >= 0 || (r.seq == want && r.fetched), last_held = b->lane_last >= 0 || b->arena[b->cur].seq == b->fit_seq - 1;
+    if (b->fit_seq < 2 || !held || !last_held)
         return fail(BF_ERR_INVALID, "bf_batch_get_previous: the previous fit's result is not held in the other arena (both fits need "
                                     "BF_FIT_RESET | BF_FIT_FETCH | BF_FIT_NOTIME on the keypoint-only path)");
-    if ((vertices || joints) && !r.has_v) return fail(BF_ERR_INVALID, "bf_batch_get_previous: no mesh was evaluated");
+    if ((vertices || joints) && lane < 0 && !r.has_v) return fail(BF_ERR_INVALID, "bf_batch_get_previous: no mesh was evaluated");
     BF_TRY(bf_flush_tail(b));
-    HIP_TRY(hipEventSynchronize(r.ev_copied));
+    HIP_TRY(hipEventSynchronize(r.ev_copied));          // (only that result's hand-over: a lane's group, never the stream)
+    size_t off[5];
+    for (int i = 0; i < 5; ++i) off[i] = lane >= 0 ? b->lanes[lane].held.off[i] + (size_t)slot * b->res_cnt[i] : b->res_off[i];
     const float *h = r.host;
-    if (params) std::memcpy(params, h + b->res_off[0], b->res_cnt[0] * sizeof(float));
-    if (loss_terms) std::memcpy(loss_terms, h + b->res_off[1], b->res_cnt[1] * sizeof(float));
-    if (joints) std::memcpy(joints, h + b->res_off[3], b->res_cnt[3] * sizeof(float));
-    if (vertices) std::memcpy(vertices, h + b->res_off[4], b->res_cnt[4] * sizeof(float));
+    if (params) std::memcpy(params, h + off[0], b->res_cnt[0] * sizeof(float));
+    if (loss_terms) std::memcpy(loss_terms, h + off[1], b->res_cnt[1] * sizeof(float));
+    if (joints) std::memcpy(joints, h + off[3], b->res_cnt[3] * sizeof(float));
+    if (vertices) std::memcpy(vertices, h + off[4], b->res_cnt[4] * sizeof(float));
     if (full_pose) {
         const size_t stride = bf_state_stride(m->nj, m->npf, m->nb);
         for (int f = 0; f < b->F; ++f) {
-            StateView v = bf_state_view(const_cast<float *>(h) + b->res_off[2] + (size_t)f * stride, m->nj, m->npf, m->nb);
+            StateView v = bf_state_view(const_cast<float *>(h) + off[2] + (size_t)f * stride, m->nj, m->npf, m->nb);
             std::memcpy(full_pose + (size_t)f * 3 * m->nj, v.theta, sizeof(float) * 3 * m->nj);
         }
     }
@@ -1241,6 +1446,13 @@ int bf_batch_mesh_span(bf_batch *b, int reps, float us[3]) {
         sum += t; lo = std::min(lo, t); hi = std::max(hi, t);
     }
     us[0] = (float)(sum / reps); us[1] = (float)lo; us[2] = (float)hi;
+    return BF_OK;
+}
+
+/* test hook: fit-lane groups since the batch was created - out[0] lane launches, out[1] lane calls, out[2] the largest group, out[3] W */
+int bf_batch_lane_stats(bf_batch *b, int32_t out[4]) {
+    if (!b || !out) return fail(BF_ERR_INVALID, "bf_batch_lane_stats: null argument");
+    out[0] = b->lane_launches; out[1] = b->lane_calls; out[2] = b->lane_max_g; out[3] = b->n_lanes > 1 ? b->lane_w : 1;
     return BF_OK;
 }
 

@@ -289,18 +289,64 @@ struct bf_model {
 
 struct bf_graph_key { int n_iters; uint32_t flags; int arena; bf_hyper h; };     // (arena: the result arena its nodes point at)
 
+// A fit lane's input arena: the device arrays of up to W calls' frames, array-major like FrameIO ([W F] keypoints | [W F] params0 |
+// [W F] ndiv: bf_batch::gin_off), and per slot one pinned staging buffer in the batch's packed layout (in_off / in_total) with the event
+// of its transfer.  W = 1 is the batch's own layout: one slot, one transfer of in_total floats.
+struct LaneSlot {
+    hipEvent_t ev = nullptr;        // the slot's last fill (transfer out of its staging buffer, or a device-side copy) has finished
+    bool pending = false;           // ... a transfer, not waited for yet
+    unsigned readers = 0;           // the lanes that read the slot in place (W = 1) or copied it (W > 1) since it was last filled (bit per lane)
+};
+struct LaneInputs {
+    DevBuf<float> dev;
+    float *host = nullptr;          // [W][in_total]
+    std::vector<LaneSlot> slot;
+    LaneInputs() = default;
+    LaneInputs(const LaneInputs &) = delete;
+    hipError_t create(size_t n_dev, size_t n_slot, int w) {
+        slot.resize(w);
+        hipError_t e = dev.alloc(n_dev);
+        if (e == hipSuccess) e = bf_memset_sync(dev.p, 0, n_dev * sizeof(float));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&host, n_slot * w * sizeof(float));
+        if (e == hipSuccess) std::memset(host, 0, n_slot * w * sizeof(float));
+        for (int i = 0; i < w && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&slot[i].ev, hipEventDisableTiming);
+        return e;
+    }
+    ~LaneInputs() {
+        for (auto &q : slot) if (q.ev) (void)hipEventDestroy(q.ev);
+        if (host) (void)hipHostFree(host);
+    }
+};
+
 // A fit lane (BF_FIT_LANES, api.hip): everything a frame-after-frame fit (RESET | FETCH | NOTIME, keypoint-only) and its tail write,
-// on a stream of its own, so that consecutive frames' fits run side by side on different CUs.  Successive fits go to successive lanes;
+// on a stream of its own, so that consecutive frames' fits run side by side on different CUs.  Successive groups go to successive lanes;
 // nothing orders one lane behind another but HIP events.
+// A lane launch carries a GROUP of up to W consecutive calls' frames (BF_FIT_LANE_WIDTH): the calls join the lane's open group, slot
+// after slot, and one fit launch of G F workgroups, one tail and one hand-over serve all G of them.  Every buffer here is sized for W
+// calls; a launched group's result arrays are packed for its G F frames (`held.off`).
 struct BfLane {
     hipStream_t stream = nullptr;
     MeshScratch scratch;            // the tail's MFMA mesh path, on this lane's stream only
     DevBuf<float> adam_m, adam_v, vraw, xpart;
     ResultArena arena;              // (its mirror is filled by the tail's hand-over)
-    InputArena in[2];               // each fed by a transfer on this lane's stream
-    int in_next = 0;                            // arena the next staging into this lane fills
+    LaneInputs in[2];               // each slot fed on this lane's stream
+    int in_next = 0;                            // arena the next group of this lane fills
     bool need_engage = false;                   // the stream has yet to wait for the batch stream (bf_batch::ev_engage)
     bool busy = false;                          // work was enqueued since the lanes were last drained
+    hipEvent_t ev_join = nullptr;               // (W > 1) the lane's last device-side copy of current inputs into a slot has finished
+    // the open group: calls that joined and wait for their launch
+    bool open = false;                          // a group is open (by a staging or a fit) on input arena open_a
+    int open_a = 0, n_open = 0;                 // ... with n_open calls joined
+    bool slot_staged = false;                   // slot n_open was staged into: the next call to join finds its inputs there
+    bool borrowed = false;                      // (W = 1) the group's call reads the batch's current inputs in place
+    const float *bor_kp = nullptr, *bor_p0 = nullptr;
+    const int *bor_ndiv = nullptr;
+    long long open_seq0 = -1;                   // the first joined call's fit number
+    int open_iters = 0;
+    HyperDev open_hd{};
+    // the launched group the result arena holds (or will, once ev_copied completes): fits seq0 .. seq0 + G - 1, slot after slot
+    struct Held { long long seq0 = -1; int G = 0; size_t off[5] = {0, 0, 0, 0, 0}, total = 0; } held;
+    ~BfLane() { if (ev_join) (void)hipEventDestroy(ev_join); }
 };
 
 struct bf_batch {
@@ -427,7 +473,13 @@ struct bf_batch {
     int n_cus = 256;                    // compute units of the model's device (bf_batch_create)
     std::unique_ptr<BfLane[]> lanes;
     bool lanes_on = false;
-    int lane_next = 0, lane_last = -1;
+    int lane_next = 0, lane_last = -1;  // the lane the next call joins; the lane whose newest group (open or launched) ends with the last lane fit
+    int lane_w = 1;                     // W: calls per lane launch at most = min(BF_FIT_LANE_WIDTH, CUs / (lanes x frames))
+    size_t gin_off[3] = {0, 0, 0}, gin_total = 0;   // a lane's input arena: float offsets of its [W F] keypoints, params0, ndiv arrays
+    int in_slot = 0;                    // (in_cur >= 2) the slot of that lane arena the views are on
+    DevBuf<float> proj_rep;             // (W > 1) the projection table W times over: FrameIO::proj of a group launch
+    bool proj_rep_stale = true;         // ... has yet to be copied from `proj` (new cameras)
+    int lane_launches = 0, lane_calls = 0, lane_max_g = 0;      // bf_batch_lane_stats
     hipEvent_t ev_engage = nullptr;     // recorded on the batch stream when the lanes take over: every lane stream waits for it
 };
 
@@ -454,6 +506,8 @@ struct MeshPass {
     // what is read
     MeshScratch *scr = nullptr;         // the stream owner's scratch: the batched path (>= BF_MFMA_MIN_FRAMES frames) needs one
     int n = 0;
+    int per = 0;                        // > 0: the n frames are n / per independent calls' of `per` frames each (a fit-lane group) and every
+                                        // call's frames get the kernel and the blocks they would get alone - the bits do not depend on the group
     const float *state = nullptr;
     hipStream_t stream = nullptr;
     const MeshTab *tab = nullptr;       // the sampled-first sub-model inside a dense loop without scans (null: the model's own table)
@@ -488,7 +542,7 @@ void bf_masks_commit(bf_batch *b);       // no-op unless bf_batch_stage_masks ha
 HyperDev bf_to_dev(const bf_hyper &h);
 int bf_flush_tail(bf_batch *b);          // enqueue the deferred mesh / hand-over tail of the last frame-after-frame fit (api.hip)
 int bf_sync_all(bf_batch *b);            // lanes, copy stream, then compute stream
-int bf_lanes_drain(bf_batch *b);         // no-op unless fit lanes are on: wait for them, hand the last lane fit back to the batch
+int bf_lanes_drain(bf_batch *b);         // no-op unless fit lanes are on: launch the open group, wait for the lanes, hand the last lane fit back to the batch
 int bf_guard_arena(bf_batch *b);         // the compute stream waits for a fetch still reading the current arena
 // `with_kp`: the dense keypoint loss rides in the contour launch (bf_kp_contour_kernel) instead of a launch of its own
 int launch_mask_kernels(bf_batch *b, float weight, bool want_loss, bool sum_views = true, const bf_hyper *with_kp = nullptr,

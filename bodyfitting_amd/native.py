@@ -896,6 +896,12 @@ class FrameBatch:
         _lib.check(self._lib.bf_batch_debug_vertices(self._h, _lib.fptr(v)), "bf_batch_debug_vertices")
         return v
 
+    def lane_stats(self):
+        """fit-lane groups since the batch was created -> {"launches", "calls", "max_group", "width"} (bf_batch_lane_stats)"""
+        out = np.zeros(4, np.int32)
+        _lib.check(self._lib.bf_batch_lane_stats(self._h, _lib.iptr(out)), "bf_batch_lane_stats")
+        return {"launches": int(out[0]), "calls": int(out[1]), "max_group": int(out[2]), "width": int(out[3])}
+
     def disp_moment(self):
         """first Adam moment [F,NV,3] of the SMPL+D displacement (bf_batch_debug_disp_moment)"""
         m = np.empty((self.F, self.model.n_verts, 3), np.float32)
