@@ -2,6 +2,7 @@
 #include "bf_host.h"
 #include "fit_kernels.h"
 #include "mesh_kernels.h"
+#include <cassert>
 #include <chrono>
 
 
@@ -13,6 +14,39 @@
 
 std::string &bf_err_slot() { thread_local std::string e; return e; }
 int bf_fail(int code, const std::string &msg) { bf_err_slot() = msg; return code; }
+
+// Host time spent inside bf_batch_stage_inputs and bf_fit, summed per batch and printed when the batch goes - a build-time switch, so
+// that the product build carries no timers: make variant TAG=timers VSRC=api VFLAGS=-DBF_HOST_TIMERS (profiles/lane_feed.md)
+#ifdef BF_HOST_TIMERS
+struct BfHostSums { long long ns[2] = {0, 0}, n[2] = {0, 0}; };
+static std::mutex &host_sums_mu() { static std::mutex mu; return mu; }      // (batches of a group are driven from several threads)
+static std::map<const void *, BfHostSums> &host_sums() { static std::map<const void *, BfHostSums> s; return s; }
+static BfHostSums *host_sums_of(const void *b) { std::lock_guard<std::mutex> lk(host_sums_mu()); return &host_sums()[b]; }      // (node addresses are stable)
+struct BfHostTimed {
+    static constexpr long long kSkip = 16;
+    BfHostSums *s; int k;
+    std::chrono::steady_clock::time_point t0;
+    BfHostTimed(const void *b, int k_) : s(b ? host_sums_of(b) : nullptr), k(k_), t0(std::chrono::steady_clock::now()) {}
+    ~BfHostTimed() {
+        if (!s) return;
+        const long long dt = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        if (++s->n[k] > kSkip) s->ns[k] += dt;          // (the first calls create lanes, events and tables)
+    }
+};
+static void host_sums_report(const void *b) {
+    std::lock_guard<std::mutex> lk(host_sums_mu());
+    auto it = host_sums().find(b);
+    if (it == host_sums().end()) return;
+    const BfHostSums &s = it->second;
+    const long long n0 = s.n[0] - BfHostTimed::kSkip, n1 = s.n[1] - BfHostTimed::kSkip;
+    std::fprintf(stderr, "BF_HOST_TIMERS batch %p: bf_batch_stage_inputs %lld calls %.3f us each; bf_fit %lld calls %.3f us each (first %lld of each left out)\n",
+                 b, s.n[0], n0 > 0 ? s.ns[0] * 1e-3 / n0 : 0.0, s.n[1], n1 > 0 ? s.ns[1] * 1e-3 / n1 : 0.0, BfHostTimed::kSkip);
+    host_sums().erase(it);
+}
+#define BF_HOST_TIMED(b, k) BfHostTimed host_timed_((b), (k))
+#else
+#define BF_HOST_TIMED(b, k) do { } while (0)
+#endif
 
 extern "C" {
 
@@ -232,16 +266,15 @@ static void bf_use_inputs(bf_batch *b, int k, bool host) {
     b->ndiv.slice((int *)(base + b->in_off[2]), (size_t)b->F);
     b->in_cur = k;
     b->in_slot = 0;
+    b->in_pinned = false;
     b->in_host = host;
 }
 
 // where slot `slot` of a lane's input arena keeps its frames: keypoints, params0, ndiv
 struct SlotPlace { float *kp, *p0; int *ndiv; };
 static SlotPlace slot_place(const bf_batch *b, LaneInputs &in, int slot) {
-    const size_t F = b->F;
     float *base = in.dev.p;
-    return {base + b->gin_off[0] + slot * F * b->V * b->m->nl_loss * 3, base + b->gin_off[1] + slot * F * b->m->np,
-            (int *)(base + b->gin_off[2]) + slot * F};
+    return {base + bf_slot_off(b->gin, 0, slot), base + bf_slot_off(b->gin, 1, slot), (int *)(base + bf_slot_off(b->gin, 2, slot))};
 }
 
 // ... of input arena a of fit lane j (in_cur = 2 + 2 * j + a, in_slot = slot)
@@ -254,8 +287,8 @@ static void bf_use_lane_inputs(bf_batch *b, int j, int a, int slot) {
     b->in_slot = slot;
     b->in_host = false;
 }
-// the lane slot the views are on (in_cur >= 2)
-static LaneSlot &current_lane_slot(bf_batch *b) { return b->lanes[(b->in_cur - 2) / 2].in[(b->in_cur - 2) % 2].slot[b->in_slot]; }
+// the lane arena the views are on (in_cur >= 2)
+static LaneInputs &current_lane_inputs(bf_batch *b) { return b->lanes[(b->in_cur - 2) / 2].in[(b->in_cur - 2) % 2]; }
 
 // a synchronous setter's write into the current input arena (the stream is idle)
 static hipError_t write_input(bf_batch *b, void *dst, const void *src, size_t bytes) {
@@ -287,7 +320,7 @@ int bf_flush_tail(bf_batch *b) {
 /* Fit lanes.  A frame-after-frame fit (the tail-aside conditions of fit_plan) is one workgroup per frame on one CU for ~380 us while
  * the other CUs idle, and the frames of a capture are independent (every call carries BF_FIT_RESET).  With n_lanes > 1 such a fit goes
  * to a lane: a stream of its own with its own Adam moments, result arena, mesh scratch and input arenas, so that fits of consecutive
- * calls run side by side on different CUs.  A lane's stream holds [input transfers] fit, mesh, joints, hand-over: its own work in order.
+ * calls run side by side on different CUs.  A lane's stream holds [input transfer] fit, mesh, joints, hand-over: its own work in order.
  * Lanes are ordered against each other and against the batch stream by HIP events only (no device-side waits): lanes that end up
  * sharing a hardware queue run one after another, never hang.
  *   - Lane GROUPS.  The lanes that run side by side are as many as the high-priority pool has hardware queues (four), but the fit kernel
@@ -296,18 +329,30 @@ int bf_flush_tail(bf_batch *b) {
  *     workgroups, one tail and one hand-over serve the G calls that joined (lane_launch).  The group goes out when a call joins while
  *     its lane is idle (a slow feeder gets G = 1 and no added latency), when it is full (behind the lane's running group), when its
  *     calls would differ in iterations or hyper-parameters, and at every entry point that drains or reads.  Then `lane_next` moves on.
- *     BF_FIT_LANE_WIDTH=<n> caps W (default 8; 1: a launch per call, the call sequence before groups); a batch uses at most
+ *     BF_FIT_LANE_WIDTH=<n> caps W (default 32; 1: a launch per call, the call sequence before groups); a batch uses at most
  *     CUs / (lanes x frames).  BF_FIT_LANE_FILL=1 turns the idle rule off - groups fill to W or to a flush - so that tests can force
  *     group shapes.
  *   - Lanes take over (lanes_engage) behind everything on the batch stream.  Every entry point that is not a lane fit or a staging drains
  *     them first (bf_lanes_drain, from bf_sync_all / bf_guard_arena / fit_impl): it launches the open group, waits for the lane streams
  *     and leaves the last lane fit's result and Adam moments in the batch's own buffers - the state the tail-aside path leaves - so
  *     that continuing fits, setters, reads, the graph and dense paths run exactly as without lanes.
- *   - bf_batch_stage_inputs fills the open group's next slot on that lane's stream at once (two input arenas per lane, a group each):
- *     the transfer is ordered behind the fits that last read the arena by stream order, behind another lane's use of the slot (a call
- *     without a staging of its own that took the current inputs from it) by that lane's event, and never behind a running fit of
- *     another lane.  The host waits when the slot's own previous transfer - queued two of the lane's groups ago - has not left its
- *     pinned buffer.
+ *   - HOST-FED groups (W > 1).  bf_batch_stage_inputs issues no GPU work: it packs the call's inputs into the next slot of the open
+ *     group's PINNED arena - laid out like the device arena, slot for slot (lane_slots.h; two arenas per lane, a group each) - and
+ *     points the batch's views at the slot's place on the device.  lane_launch moves all the group's slots with ONE transfer ahead of
+ *     the fit launch (lane_feed: a prefix of slots is three contiguous ranges), a slot staged past the last joined call with them, and
+ *     records the arena's event behind it; a drain that finds only such a slot sends it alone, so that whoever reads the views on the
+ *     device next - a plain fit, bf_loss_grad, a continuing fit - finds them filled.  The transfer is ordered behind this lane's fits
+ *     that last read the arena by stream order and never behind a running fit of another lane.  The lane opens the arena again two of
+ *     its groups later; the host waits then only if that transfer has not finished (lane_open).  The fit kernel always reads the device
+ *     arena (large view counts and the table-driven instances read the keypoints inside the loop): no zero-copy here.
+ *   - A call WITHOUT a staging of its own takes the batch's current inputs: by a host copy, pinned slot to pinned slot, while their
+ *     pinned copy is valid (the usual re-fit: no device copy, no event, no wait between lanes - the views move to the new slot), and by
+ *     a device-side copy on the lane's stream when they are in device memory only - after a synchronous setter, a device-side
+ *     producer or a drain (bf_batch::in_pinned is cleared by every drain).  A group is host-fed or device-fed, never both: a call of
+ *     the other kind launches the open group first.  A device-fed group gets no transfer at launch; the next transfer into an arena a
+ *     device-side copy read from waits for that copy through the copying lane's event (LaneInputs::readers).
+ *   - W = 1 keeps the call sequence before groups: a staging transfers its slot - the arena - at once on the lane's stream, and a call
+ *     without a staging of its own reads the current inputs in place.
  * BF_FIT_LANES=<n> sets the lane count (1: no lanes, the single-stream path); a batch uses at most (CUs / frames) of them. */
 static FrameIO bf_frame_io(bf_batch *b, bool want_grads);       // (the batch's own launch arguments: below, with the fit routes)
 static int env_int(const char *name, int dflt, int lo, int hi) {
@@ -315,7 +360,7 @@ static int env_int(const char *name, int dflt, int lo, int hi) {
     return std::max(lo, std::min(e ? atoi(e) : dflt, hi));
 }
 static int fit_lanes_wanted() { static const int d = env_int("BF_FIT_LANES", 4, 1, 32); return d; }
-static int fit_lane_width_wanted() { static const int d = env_int("BF_FIT_LANE_WIDTH", 8, 1, 64); return d; }
+static int fit_lane_width_wanted() { static const int d = env_int("BF_FIT_LANE_WIDTH", 32, 1, 64); return d; }
 static bool fit_lane_fill() { static const bool d = env_int("BF_FIT_LANE_FILL", 0, 0, 1) == 1; return d; }
 // a group's hand-over from this size on is a copy command, below it the publish kernel: the threshold fit_plan uses for a call.  Measured
 // for groups (profiles/fit_lane_groups.md): the publish kernel for full groups is the slowest, always copying no better than this
@@ -331,7 +376,7 @@ static void lanes_release(bf_batch *b) {
     if (b->ev_engage) { (void)hipEventDestroy(b->ev_engage); b->ev_engage = nullptr; }
 }
 
-static size_t up64(size_t n) { return (n + 63) & ~(size_t)63; }          // 256-byte slices
+static size_t up64(size_t n) { return bf_up64(n); }          // 256-byte slices
 
 static int lanes_create(bf_batch *b) {
     if (b->lanes) return BF_OK;
@@ -351,7 +396,7 @@ static int lanes_create(bf_batch *b) {
         ok = hipStreamCreateWithPriority(&l.stream, hipStreamNonBlocking, greatest) == hipSuccess &&
              l.adam_m.alloc(W * F * np) == hipSuccess && l.adam_v.alloc(W * F * np) == hipSuccess && l.vraw.alloc(W * b->vraw.n) == hipSuccess &&
              l.xpart.alloc(W * b->xpart.n) == hipSuccess && l.arena.create(res_w) == hipSuccess &&
-             l.in[0].create(b->gin_total, b->in_total, (int)W) == hipSuccess && l.in[1].create(b->gin_total, b->in_total, (int)W) == hipSuccess &&
+             l.in[0].create(b->gin.total) == hipSuccess && l.in[1].create(b->gin.total) == hipSuccess &&
              (W == 1 || hipEventCreateWithFlags(&l.ev_join, hipEventDisableTiming) == hipSuccess);
     }
     if (ok && W > 1) ok = b->proj_rep.alloc(W * b->proj.n) == hipSuccess;
@@ -383,15 +428,40 @@ static int lane_begin(bf_batch *b, BfLane &l) {
     return BF_OK;
 }
 
-// The open group of lane j goes out: ONE fit launch for the G F frames of the G calls that joined, the tail for all of them (each
-// call's frames through the kernel and the blocks they would get alone: MeshPass::per), one hand-over of the group's floats, ev_copied.
+// The one input transfer of a host-fed group of lane j: slots [0, n) of arena `in` - the G calls that joined and, if there is one, the slot
+// staged past them; a prefix of slots is three contiguous ranges (bf_slot_prefix) - from the pinned buffer to their places on the device,
+// on the lane's stream ahead of the fit, and the arena's event behind it.  This lane's earlier fits that read the arena are ahead in
+// stream order; another lane's device-side copy of one of its slots (`readers`) is waited for through that lane's event.
+static int lane_feed(bf_batch *b, int j, LaneInputs &in, int n) {
+    BfLane &l = b->lanes[j];
+    for (int r = 0; r < b->n_lanes; ++r)
+        if (r != j && ((in.readers >> r) & 1u)) HIP_TRY(hipStreamWaitEvent(l.stream, b->lanes[r].ev_join, 0));
+    in.readers = 0;
+    BfRange rg[3];
+    bf_slot_prefix(b->gin, n, rg);
+    BfSeg3 seg;
+    for (int k = 0; k < 3; ++k) { seg.src[k] = in.host + rg[k].off; seg.dst[k] = in.dev.p + rg[k].off; seg.n[k] = (unsigned)rg[k].n; }
+    BF_TRY(publish3(l.stream, seg));
+    HIP_TRY(hipEventRecord(in.ev, l.stream));
+    in.pending = true;
+    b->feed_transfers += 1;
+    return BF_OK;
+}
+
+// The open group of lane j goes out: for a host-fed group its one input transfer, then ONE fit launch for the G F frames of the G calls
+// that joined, the tail for all of them (each call's frames through the kernel and the blocks they would get alone: MeshPass::per), one
+// hand-over of the group's floats, ev_copied.
 // The result arrays are packed for G F frames - FrameIO is array-major over n_frames - and their offsets stay with the group (`held`).
 // The lane's group is closed whatever happens, and the next call joins the next lane.
 static int lane_launch(bf_batch *b, int j) {
     BfLane &l = b->lanes[j];
     const int G = l.n_open;
-    if (!G) return BF_OK;
+    // a host-fed group: its slots [0, G) and a slot staged past the last joined call are in the pinned buffer only
+    const int n_feed = (b->lane_w > 1 && l.open_host) ? G + (l.slot_staged ? 1 : 0) : 0;
+    if (!G && !n_feed) return BF_OK;
+    LaneInputs &in_open = l.in[l.open_a];
     l.open = false; l.n_open = 0; l.slot_staged = false;        // (a slot staged past the last call stays the batch's current inputs: the next call copies it)
+    if (!G) return lane_feed(b, j, in_open, n_feed);            // (a drain with nothing joined: the staged slot alone, for whoever reads the views next)
     if (b->lane_next == j) b->lane_next = (j + 1) % b->n_lanes;
     bf_model *m = b->m;
     ResultArena &r = l.arena;
@@ -408,6 +478,7 @@ static int lane_launch(bf_batch *b, int j) {
     if (b->lane_w > 1) io.proj = b->proj_rep.p;
     io.params = d + h.off[0]; io.terms = d + h.off[1]; io.state = d + h.off[2];
     io.adam_m = l.adam_m.p; io.adam_v = l.adam_v.p;
+    if (n_feed) BF_TRY(lane_feed(b, j, in_open, n_feed));
     HIP_TRY(bf_fit_launch(&m->fit, &io, &l.open_hd, l.open_iters, 0, b->adam_tab.p, 0, b->fit_smem, l.stream, nullptr));
     MeshPass p;
     p.scr = &l.scratch; p.n = G * b->F; p.per = b->F; p.state = d + h.off[2]; p.stream = l.stream;
@@ -424,6 +495,7 @@ static int lane_launch(bf_batch *b, int j) {
 
 int bf_lanes_drain(bf_batch *b) {
     if (!b->lanes_on) return BF_OK;
+    b->in_pinned = false;                 // (what follows a drain may write the device slot alone: a setter, a device-side producer)
     for (int j = 0; j < b->n_lanes; ++j) BF_TRY(lane_launch(b, j));       // (the open group, if calls have joined one)
     b->lanes_on = false;
     for (int j = 0; j < b->n_lanes; ++j)
@@ -574,9 +646,7 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
         b->n_lanes = (!b->stage_zerocopy && d > 1) ? d : 1;
         // ... and a lane launch carries up to W calls' frames, the lanes' groups together at most a frame per CU
         b->lane_w = std::min(fit_lane_width_wanted(), std::max(1, std::max(n_cus, 1) / (b->n_lanes * n_frames)));
-        const size_t W = b->lane_w, n_kp = F * n_views * m->nl_loss * 3;
-        b->gin_off[0] = 0; b->gin_off[1] = up64(W * n_kp); b->gin_off[2] = b->gin_off[1] + up64(W * F * np);
-        b->gin_total = b->gin_off[2] + up64(W * F);
+        b->gin = bf_lane_layout(b->lane_w, n_frames, F * n_views * m->nl_loss * 3, m->np);      // (W = 1: in_off / in_total)
     }
     *out = b;
     return BF_OK;
@@ -584,6 +654,9 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
 
 void bf_batch_destroy(bf_batch *b) {
     if (!b) return;
+#ifdef BF_HOST_TIMERS
+    host_sums_report(b);
+#endif
     b->tail_k = -1;                       // (a tail never enqueued: nobody will read that result)
     for (int j = 0; b->lanes && j < b->n_lanes; ++j)          // (calls that joined a group were promised a fit: it goes out before the wait)
         if (b->lanes[j].n_open && hipSetDevice(b->m->device) == hipSuccess) (void)lane_launch(b, j);
@@ -705,18 +778,10 @@ int bf_batch_reset(bf_batch *b) {
 }
 
 // net_output of smplify.py:103 -> the packed optimiser vector: transl = 0, scale = 1 (:126-128), body pose, betas, root orientation
+// (bf_pack_init, lane_slots.h)
+static BfInitMap init_map(const bf_model *m) { return {m->np, m->nb, m->fit.nbp, m->fit.off_pose, m->fit.off_beta, m->fit.off_orient}; }
 static void pack_init(const bf_batch *b, const float *init_betas, const float *init_pose, float *dst) {
-    const bf_model *m = b->m;
-    const int np = m->np, nb = m->nb;
-    const int pose_stride = 72;                  // net_output poses are [F,72] for both model kinds (smplify.py:108-112)
-    std::memset(dst, 0, (size_t)b->F * np * sizeof(float));
-    for (int f = 0; f < b->F; ++f) {
-        float *q = dst + (size_t)f * np;
-        q[3] = 1.0f;                                                             // body_scale = 1, transl = 0
-        std::memcpy(q + m->fit.off_pose, init_pose + (size_t)f * pose_stride + 3, sizeof(float) * m->fit.nbp);
-        std::memcpy(q + m->fit.off_beta, init_betas + (size_t)f * nb, sizeof(float) * nb);
-        std::memcpy(q + m->fit.off_orient, init_pose + (size_t)f * pose_stride, sizeof(float) * 3);
-    }
+    bf_pack_init(init_map(b->m), b->F, init_betas, init_pose, dst);
 }
 
 // keypoints | params0 | ndiv of the next frame packed into a pinned staging buffer (`h`; `ev`, `pending`: its transfer), once its previous
@@ -729,8 +794,7 @@ static int pack_staging(const bf_batch *b, float *h, hipEvent_t ev, bool &pendin
     }
     std::memcpy(h + b->in_off[0], keypoints, (size_t)b->F * b->V * b->m->nl_loss * 3 * sizeof(float));
     pack_init(b, init_betas, init_pose, h + b->in_off[1]);
-    int *nd = (int *)(h + b->in_off[2]);
-    for (int f = 0; f < b->F; ++f) nd[f] = n_use_frames ? n_use_frames[f] : b->V;
+    bf_fill_ndiv((int32_t *)(h + b->in_off[2]), b->F, n_use_frames, b->V);
     return BF_OK;
 }
 
@@ -740,6 +804,7 @@ static int pack_staging(const bf_batch *b, float *h, hipEvent_t ev, bool &pendin
  * arena is queued on the batch stream, behind that fit - or, frame after frame, on the second stream under it (below); the next
  * bf_fit - which must carry BF_FIT_RESET - reads them. */
 int bf_batch_stage_inputs(bf_batch *b, const float *keypoints, const int32_t *n_use_frames, const float *init_betas, const float *init_pose) {
+    BF_HOST_TIMED(b, 0);
     if (!b || !keypoints || !init_betas || !init_pose) return fail(BF_ERR_INVALID, "bf_batch_stage_inputs: null argument");
     if (n_use_frames)
         for (int f = 0; f < b->F; ++f)
@@ -775,8 +840,46 @@ int bf_batch_stage_inputs(bf_batch *b, const float *keypoints, const int32_t *n_
     return aside ? bf_flush_tail(b) : BF_OK;
 }
 
+// input arena `a` of lane l is opened for a new group.  Its pinned buffer may still be read by the transfer of the group it held - issued
+// two of this lane's groups ago, behind fits that have normally long finished: the host waits only if that transfer has not completed
+// (the back-pressure of a feeder that runs ahead of the device)
+static int lane_open(bf_batch *b, BfLane &l, bool host_fed) {
+    l.open = true;
+    l.open_a = l.in_next;
+    l.in_next ^= 1;
+    l.open_host = host_fed;
+    LaneInputs &in = l.in[l.open_a];
+    if (host_fed && in.pending) {
+        if (hipEventQuery(in.ev) != hipSuccess) {
+            (void)hipGetLastError();
+            HIP_TRY(hipEventSynchronize(in.ev));
+            b->feed_waits += 1;
+        }
+        in.pending = false;
+    }
+    return BF_OK;
+}
+
 static int stage_lane(bf_batch *b, const float *keypoints, const int32_t *n_use_frames, const float *init_betas, const float *init_pose) {
     BF_TRY(lanes_engage(b));
+    if (b->lane_w > 1) {
+        // Host-fed groups: NO GPU work here.  The call's inputs are packed into slot n_open of the open arena's pinned buffer - a second
+        // staging before a fit rewrites the same slot - and the views point at the slot's place on the device, which the group's one
+        // transfer fills when the group is launched (lane_launch; every drain comes through there, so whoever reads the views on the
+        // device finds them filled).  Until then the pinned slot is the only valid copy: in_pinned.
+        if (b->lanes[b->lane_next].n_open && !b->lanes[b->lane_next].open_host) BF_TRY(lane_launch(b, b->lane_next));   // (a device-fed group: it goes out first)
+        const int j = b->lane_next;
+        BfLane &l = b->lanes[j];
+        BF_TRY(lane_begin(b, l));
+        if (!l.open) BF_TRY(lane_open(b, l, true));
+        bf_pack_slot(b->gin, l.in[l.open_a].host, l.n_open, init_map(b->m), b->F, b->V, keypoints, n_use_frames, init_betas, init_pose);
+        bf_use_lane_inputs(b, j, l.open_a, l.n_open);
+        b->in_pinned = true;
+        l.slot_staged = true;
+        b->staged = true;
+        return BF_OK;
+    }
+    // W = 1, a launch per call: the slot is the arena, filled by a transfer of its own at once (the call sequence before groups)
     const int j = b->lane_next;             // (the lane the next frame-after-frame fit joins)
     BfLane &l = b->lanes[j];
     BF_TRY(lane_begin(b, l));
@@ -785,27 +888,19 @@ static int stage_lane(bf_batch *b, const float *keypoints, const int32_t *n_use_
         l.open_a = l.in_next;
         l.in_next ^= 1;
     }
-    const int a = l.open_a, slot = l.n_open;
+    const int a = l.open_a;
     LaneInputs &in = l.in[a];
-    LaneSlot &q = in.slot[slot];
-    float *h = in.host + (size_t)slot * b->in_total;
-    BF_TRY(pack_staging(b, h, q.ev, q.pending, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: queued two of this lane's groups ago)
-    // what read arena a since it was last filled: this lane's fits are ahead in its stream; another lane's use of this slot (a call
-    // without a staging of its own: W = 1 its fit reads the slot in place, else it copied the slot when it joined) is waited for
-    // through that lane's event
+    BF_TRY(pack_staging(b, in.host, in.ev, in.pending, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: queued two of this lane's groups ago)
+    // what read arena a since it was last filled: this lane's fits are ahead in its stream; another lane's fit that read it in place (a
+    // call without a staging of its own) is waited for through that lane's event
     for (int r = 0; r < b->n_lanes; ++r)
-        if (r != j && ((q.readers >> r) & 1u))
-            HIP_TRY(hipStreamWaitEvent(l.stream, b->lane_w == 1 ? b->lanes[r].arena.ev_copied : b->lanes[r].ev_join, 0));
-    q.readers = 0;
-    if (b->lane_w == 1) BF_TRY(publish(l.stream, in.dev.p, h, b->in_total));
-    else {
-        const SlotPlace at = slot_place(b, in, slot);
-        BF_TRY(publish3(l.stream, BfSeg3{{h + b->in_off[0], h + b->in_off[1], h + b->in_off[2]}, {at.kp, at.p0, (float *)at.ndiv},
-                                         {(unsigned)b->keypoints.n, (unsigned)b->params0.n, (unsigned)b->ndiv.n}}));
-    }
-    HIP_TRY(hipEventRecord(q.ev, l.stream));
-    q.pending = true;
-    bf_use_lane_inputs(b, j, a, slot);
+        if (r != j && ((in.readers >> r) & 1u)) HIP_TRY(hipStreamWaitEvent(l.stream, b->lanes[r].arena.ev_copied, 0));
+    in.readers = 0;
+    BF_TRY(publish(l.stream, in.dev.p, in.host, b->in_total));
+    HIP_TRY(hipEventRecord(in.ev, l.stream));
+    in.pending = true;
+    b->feed_transfers += 1;
+    bf_use_lane_inputs(b, j, a, 0);
     l.slot_staged = true;
     b->staged = true;
     return BF_OK;
@@ -867,8 +962,12 @@ static int ensure_adam_tab(bf_batch *b, const bf_hyper &h, int upto) {
         tab[(size_t)(t - 1) * 3 + 1] = (float)((double)h.lr / bc1);
         tab[(size_t)(t - 1) * 3 + 2] = (float)std::sqrt(bc2);
     }
-    BF_TRY(bf_sync_all(b));
-    if (b->adam_tab.p) { (void)hipFree(b->adam_tab.p); b->adam_tab.p = nullptr; }
+    // a table in use is replaced behind everything that reads it; a batch's first table has no reader yet, and building it must not
+    // drain the lanes - the first fit of a stream of staged frames would find its slot sent ahead and its group closed
+    if (b->adam_tab.p) {
+        BF_TRY(bf_sync_all(b));
+        (void)hipFree(b->adam_tab.p); b->adam_tab.p = nullptr;
+    }
     HIP_TRY(b->adam_tab.upload(tab));
     b->adam_cap = cap;
     b->adam_hyper = h;
@@ -971,16 +1070,21 @@ static int ensure_graph(bf_batch *b, hipGraphExec_t &exec, bf_graph_key &exec_ke
     return BF_OK;
 }
 
-// LANE: the call joins the open group of the next lane - its inputs are in the group's next slot (staged there, or copied from the
-// batch's current inputs now) - and the group is launched if its lane is idle or it is full (lane_launch)
+// LANE: the call joins the open group of the next lane - its inputs are in the group's next slot: staged there, or copied from the
+// batch's current inputs now, on the host where their pinned copy is valid and on the device otherwise - and the group is launched if
+// its lane is idle or it is full (lane_launch).  A group is host-fed or device-fed, never both: a call of the other kind launches the
+// open group first, as a call with other iterations or hyper-parameters does.
 static int fit_lane(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &done) {
     BF_TRY(lanes_engage(b));
+    const int W = b->lane_w;
     {
-        // one launch, one n_iters and one set of hyper-parameters: a call that differs starts a group of its own
+        // one launch, one n_iters, one set of hyper-parameters and one way of feeding: a call that differs starts a group of its own
         BfLane &o = b->lanes[b->lane_next];
-        if (o.n_open && (o.open_iters != c.n_iters || std::memcmp(&o.open_hd, &hd, sizeof hd) != 0)) BF_TRY(lane_launch(b, b->lane_next));
+        const bool host_fed = o.slot_staged || b->in_pinned;
+        if (o.n_open && (o.open_iters != c.n_iters || std::memcmp(&o.open_hd, &hd, sizeof hd) != 0 || (W > 1 && o.open_host != host_fed)))
+            BF_TRY(lane_launch(b, b->lane_next));
     }
-    const int j = b->lane_next, W = b->lane_w;
+    const int j = b->lane_next;
     BfLane &l = b->lanes[j];
     BF_TRY(lane_begin(b, l));
     b->fetched = false; b->have_result = false;                 // (a failure from here on: nothing of this call may be read)
@@ -989,23 +1093,36 @@ static int fit_lane(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &
     if (!l.slot_staged && W == 1) {
         // a launch per call: the fit reads the current inputs in place.  Another lane's slot is read without a wait for its transfer,
         // as before groups (width 1 is that call sequence): the transfer went out on its lane ahead of a fit launch that has since
-        // been issued, and the group path below, which copies earlier - at join time - does wait
+        // been issued
         l.borrowed = true;
         l.bor_kp = b->keypoints.p; l.bor_p0 = b->params0.p; l.bor_ndiv = b->ndiv.p;
-        if (b->in_cur >= 2) current_lane_slot(b).readers |= 1u << j;
+        if (b->in_cur >= 2) current_lane_inputs(b).readers |= 1u << j;
+    } else if (!l.slot_staged && b->in_pinned) {
+        // No staging of its own, and the pinned mirror of the slot the views are on holds the current inputs (the usual re-fit): copied
+        // on the host into this group's next slot - no device copy, no event - and the views move there.
+        // INVARIANT: the source is the previous call's slot at the latest (every host-fed call leaves the views on its own slot), so its
+        // arena belongs to the newest group of its lane or to the open one, and a pinned arena is rewritten only when its lane opens it
+        // again two groups later - which takes calls that would have moved the views on.  The source is never the slot written here.
+        if (!l.open) BF_TRY(lane_open(b, l, true));
+        const LaneInputs &src = current_lane_inputs(b);
+        LaneInputs &dst = l.in[l.open_a];
+        assert(!(&src == &dst && b->in_slot == slot) && "a re-fit's pinned source is the previous call's slot, never the one it joins");
+        bf_copy_slot(b->gin, dst.host, slot, src.host, b->in_slot);
+        bf_use_lane_inputs(b, j, l.open_a, slot);
+        b->in_pinned = true;
+        b->feed_host_copies += 1;
     } else if (!l.slot_staged) {
-        // no staging of its own: the current inputs (whatever keypoints / params0 / ndiv point at), copied on the lane's stream
-        if (!l.open) { l.open_a = l.in_next; l.in_next ^= 1; }
+        // no staging of its own, the current inputs in device memory only (after a synchronous setter, a device-side producer, a drain):
+        // whatever keypoints / params0 / ndiv point at, copied on the lane's stream.  A lane slot they point at was filled before the
+        // drain that left them there: nothing to wait for; its arena's next transfer waits for this copy (`readers`).
+        if (!l.open) BF_TRY(lane_open(b, l, false));
         const SlotPlace at = slot_place(b, l.in[l.open_a], slot);
         if (at.kp != b->keypoints.p) {                          // (else they are this very slot's)
-            if (b->in_cur >= 2 && (b->in_cur - 2) / 2 != j) {   // another lane's slot: behind its transfer, and its next staging behind this copy
-                LaneSlot &src = current_lane_slot(b);
-                HIP_TRY(hipStreamWaitEvent(l.stream, src.ev, 0));
-                src.readers |= 1u << j;
-            }
+            if (b->in_cur >= 2 && (b->in_cur - 2) / 2 != j) current_lane_inputs(b).readers |= 1u << j;
             BF_TRY(publish3(l.stream, BfSeg3{{b->keypoints.p, b->params0.p, (const float *)b->ndiv.p}, {at.kp, at.p0, (float *)at.ndiv},
                                              {(unsigned)b->keypoints.n, (unsigned)b->params0.n, (unsigned)b->ndiv.n}}));
             HIP_TRY(hipEventRecord(l.ev_join, l.stream));
+            b->feed_dev_copies += 1;
         }
     }
     l.open = true; l.slot_staged = false;
@@ -1202,6 +1319,7 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
 }
 
 int bf_fit(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
+    BF_HOST_TIMED(b, 1);
     if (!b || n_iters <= 0) return fail(BF_ERR_INVALID, "bf_fit: bad argument");
     if (b->scans_lost)
         return fail(BF_ERR_INVALID, "bf_fit: a scan this batch held was destroyed (bf_scan_destroy) - call bf_batch_set_scans again (NULL: go on without scans)");
@@ -1453,6 +1571,14 @@ int bf_batch_mesh_span(bf_batch *b, int reps, float us[3]) {
 int bf_batch_lane_stats(bf_batch *b, int32_t out[4]) {
     if (!b || !out) return fail(BF_ERR_INVALID, "bf_batch_lane_stats: null argument");
     out[0] = b->lane_launches; out[1] = b->lane_calls; out[2] = b->lane_max_g; out[3] = b->n_lanes > 1 ? b->lane_w : 1;
+    return BF_OK;
+}
+
+/* test hook: how the fit lanes were fed - out[0] input transfers, out[1] host-side slot copies, out[2] device-side slot copies, out[3] host
+ * waits on a pinned arena */
+int bf_batch_lane_feed_stats(bf_batch *b, int64_t out[4]) {
+    if (!b || !out) return fail(BF_ERR_INVALID, "bf_batch_lane_feed_stats: null argument");
+    out[0] = b->feed_transfers; out[1] = b->feed_host_copies; out[2] = b->feed_dev_copies; out[3] = b->feed_waits;
     return BF_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/bodyfit.h"
 #include "bf_internal.h"
+#include "lane_slots.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -290,30 +291,26 @@ struct bf_model {
 struct bf_graph_key { int n_iters; uint32_t flags; int arena; bf_hyper h; };     // (arena: the result arena its nodes point at)
 
 // A fit lane's input arena: the device arrays of up to W calls' frames, array-major like FrameIO ([W F] keypoints | [W F] params0 |
-// [W F] ndiv: bf_batch::gin_off), and per slot one pinned staging buffer in the batch's packed layout (in_off / in_total) with the event
-// of its transfer.  W = 1 is the batch's own layout: one slot, one transfer of in_total floats.
-struct LaneSlot {
-    hipEvent_t ev = nullptr;        // the slot's last fill (transfer out of its staging buffer, or a device-side copy) has finished
-    bool pending = false;           // ... a transfer, not waited for yet
-    unsigned readers = 0;           // the lanes that read the slot in place (W = 1) or copied it (W > 1) since it was last filled (bit per lane)
-};
+// [W F] ndiv: bf_batch::gin, lane_slots.h), and ONE pinned buffer of the same layout - slot s of the pinned buffer mirrors slot s of the
+// device arrays, array by array.  A staging packs into the pinned slot and issues nothing; when the group is launched, one transfer on
+// the lane's stream moves the prefix of slots that were filled (three contiguous ranges) and `ev` is recorded behind it.  The arena is
+// opened again two of its lane's groups later: whoever opens it waits for `ev` on the host if that transfer has not finished.
+// W = 1 is the batch's own layout: one slot, filled by a transfer of its own at every staging (the call sequence before groups).
 struct LaneInputs {
     DevBuf<float> dev;
-    float *host = nullptr;          // [W][in_total]
-    std::vector<LaneSlot> slot;
+    float *host = nullptr;          // [gin.total], the device arena's layout
+    hipEvent_t ev = nullptr;        // the last transfer out of `host` has finished
+    bool pending = false;           // ... and has not been waited for yet
+    unsigned readers = 0;           // the lanes that read the device arrays from outside since they were last filled (bit per lane): W = 1 a fit
+                                    // that read the slot in place, W > 1 a device-side copy of a slot - the next transfer waits for them
     LaneInputs() = default;
     LaneInputs(const LaneInputs &) = delete;
-    hipError_t create(size_t n_dev, size_t n_slot, int w) {
-        slot.resize(w);
-        hipError_t e = dev.alloc(n_dev);
-        if (e == hipSuccess) e = bf_memset_sync(dev.p, 0, n_dev * sizeof(float));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&host, n_slot * w * sizeof(float));
-        if (e == hipSuccess) std::memset(host, 0, n_slot * w * sizeof(float));
-        for (int i = 0; i < w && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&slot[i].ev, hipEventDisableTiming);
-        return e;
+    hipError_t create(size_t n_floats) {
+        hipError_t e = bf_alloc_mirrored(dev, &host, n_floats);
+        return e == hipSuccess ? hipEventCreateWithFlags(&ev, hipEventDisableTiming) : e;
     }
     ~LaneInputs() {
-        for (auto &q : slot) if (q.ev) (void)hipEventDestroy(q.ev);
+        if (ev) (void)hipEventDestroy(ev);
         if (host) (void)hipHostFree(host);
     }
 };
@@ -329,7 +326,7 @@ struct BfLane {
     MeshScratch scratch;            // the tail's MFMA mesh path, on this lane's stream only
     DevBuf<float> adam_m, adam_v, vraw, xpart;
     ResultArena arena;              // (its mirror is filled by the tail's hand-over)
-    LaneInputs in[2];               // each slot fed on this lane's stream
+    LaneInputs in[2];               // fed on this lane's stream
     int in_next = 0;                            // arena the next group of this lane fills
     bool need_engage = false;                   // the stream has yet to wait for the batch stream (bf_batch::ev_engage)
     bool busy = false;                          // work was enqueued since the lanes were last drained
@@ -338,6 +335,8 @@ struct BfLane {
     bool open = false;                          // a group is open (by a staging or a fit) on input arena open_a
     int open_a = 0, n_open = 0;                 // ... with n_open calls joined
     bool slot_staged = false;                   // slot n_open was staged into: the next call to join finds its inputs there
+    bool open_host = false;                     // (W > 1) the open group is host-fed: its slots were packed into the pinned buffer and go to the device
+                                                // with the launch's one transfer; else device-fed: each slot was copied on the device when its call joined
     bool borrowed = false;                      // (W = 1) the group's call reads the batch's current inputs in place
     const float *bor_kp = nullptr, *bor_p0 = nullptr;
     const int *bor_ndiv = nullptr;
@@ -475,11 +474,14 @@ struct bf_batch {
     bool lanes_on = false;
     int lane_next = 0, lane_last = -1;  // the lane the next call joins; the lane whose newest group (open or launched) ends with the last lane fit
     int lane_w = 1;                     // W: calls per lane launch at most = min(BF_FIT_LANE_WIDTH, CUs / (lanes x frames))
-    size_t gin_off[3] = {0, 0, 0}, gin_total = 0;   // a lane's input arena: float offsets of its [W F] keypoints, params0, ndiv arrays
+    BfLaneLayout gin;                   // a lane's input arena: its [W F] keypoints, params0, ndiv arrays (lane_slots.h)
     int in_slot = 0;                    // (in_cur >= 2) the slot of that lane arena the views are on
+    bool in_pinned = false;             // (in_cur >= 2, W > 1) the pinned mirror of that slot holds the current inputs: a call without a staging of its
+                                        // own copies them on the host.  Cleared by every drain - what follows may write the device slot alone
     DevBuf<float> proj_rep;             // (W > 1) the projection table W times over: FrameIO::proj of a group launch
     bool proj_rep_stale = true;         // ... has yet to be copied from `proj` (new cameras)
     int lane_launches = 0, lane_calls = 0, lane_max_g = 0;      // bf_batch_lane_stats
+    long long feed_transfers = 0, feed_host_copies = 0, feed_dev_copies = 0, feed_waits = 0;    // bf_batch_lane_feed_stats
     hipEvent_t ev_engage = nullptr;     // recorded on the batch stream when the lanes take over: every lane stream waits for it
 };
 

@@ -26,6 +26,31 @@ def _i32(a):
     return np.ascontiguousarray(np.asarray(a), dtype=np.int32)
 
 
+_F32, _I32 = np.dtype(np.float32), np.dtype(np.int32)
+
+
+def conforming_address(a, dtype, size):
+    """the address of `a` if it already is what the library reads - an ndarray of `dtype`, C-contiguous, `size` elements - else None.
+    Nothing is converted, copied or kept: the caller's array outlives the call it is passed to."""
+    if type(a) is np.ndarray and (a.dtype is dtype or a.dtype == dtype) and a.size == size and a.flags.c_contiguous:
+        try:
+            return C.addressof(C.c_char.from_buffer(a))         # (the buffer protocol: a third of the time a.ctypes takes)
+        except (TypeError, ValueError):                         # a read-only or an empty array
+            return a.ctypes.data
+    return None
+
+
+def stage_addresses(F, n_kp, n_betas, keypoints, n_use_frames, init_betas, init_pose):
+    """stage_inputs' arguments as four addresses when all of them conform (n_use_frames: None, or int32[F]), else None"""
+    kp = conforming_address(keypoints, _F32, n_kp)
+    b = conforming_address(init_betas, _F32, F * n_betas)
+    p = conforming_address(init_pose, _F32, F * 72)
+    nd = None if n_use_frames is None else conforming_address(n_use_frames, _I32, F)
+    if kp is None or b is None or p is None or (nd is None and n_use_frames is not None):
+        return None
+    return kp, nd, b, p
+
+
 def model_desc(model, gmm):
     """-> (ModelDesc for bf_model_create / bf_group_create, dict of the model's sizes, the arrays the descriptor points into -
     keep them alive until the call returned)."""
@@ -692,6 +717,8 @@ class FrameBatch:
         self.F, self.V = int(n_frames), int(n_views)
         self._h = C.c_void_p()
         _lib.check(self._lib.bf_batch_create(dev_model._h, self.F, self.V, C.byref(self._h)), "bf_batch_create")
+        self._n_kp = self.F * self.V * self.model.n_loss_joints * 3
+        self._stage_by_address = _lib.by_address("bf_batch_stage_inputs")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -722,7 +749,13 @@ class FrameBatch:
 
     def stage_inputs(self, keypoints, n_use_frames, init_betas, init_pose):
         """the NEXT frame's keypoints + initial estimate without waiting for the fit in flight (bf_batch_stage_inputs); the next
-        fit() must carry FIT_RESET.  Arrays that already are C-contiguous float32 / int32 of the right shape are passed as they are."""
+        fit() must carry FIT_RESET.  Arrays that already are C-contiguous float32 / int32 of the right size are passed as they are, by
+        address (the frame loop's case: the call costs what the library does); everything else - lists, other dtypes, strided views, a
+        scalar n_use_frames, poses wider than 72 - is converted first."""
+        at = stage_addresses(self.F, self._n_kp, self.model.n_betas, keypoints, n_use_frames, init_betas, init_pose)
+        if at is not None:
+            _lib.check(self._stage_by_address(self._h, at[0], at[1], at[2], at[3]), "bf_batch_stage_inputs")
+            return
         kp = _f32(keypoints, (self.F, self.V, self.model.n_loss_joints, 3))
         nd = None if n_use_frames is None else _i32(np.broadcast_to(np.asarray(n_use_frames), (self.F,)))
         b = _f32(init_betas, (self.F, self.model.n_betas))
@@ -901,6 +934,13 @@ class FrameBatch:
         out = np.zeros(4, np.int32)
         _lib.check(self._lib.bf_batch_lane_stats(self._h, _lib.iptr(out)), "bf_batch_lane_stats")
         return {"launches": int(out[0]), "calls": int(out[1]), "max_group": int(out[2]), "width": int(out[3])}
+
+    def lane_feed_stats(self):
+        """how the fit lanes were fed since the batch was created -> {"transfers", "host_copies", "device_copies", "waits"}
+        (bf_batch_lane_feed_stats)"""
+        out = np.zeros(4, np.int64)
+        _lib.check(self._lib.bf_batch_lane_feed_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_int64))), "bf_batch_lane_feed_stats")
+        return {"transfers": int(out[0]), "host_copies": int(out[1]), "device_copies": int(out[2]), "waits": int(out[3])}
 
     def disp_moment(self):
         """first Adam moment [F,NV,3] of the SMPL+D displacement (bf_batch_debug_disp_moment)"""

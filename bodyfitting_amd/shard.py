@@ -24,7 +24,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .native import FrameBatch, _f32, _i32
+from .native import FrameBatch, _f32, _i32, stage_addresses
 
 
 # ---- the partition (host arithmetic in libbodyfit) -----------------------------------------------------------------
@@ -87,6 +87,8 @@ class _BorrowedBatch(FrameBatch):
         self._h = C.c_void_p(self._lib.bf_group_batch(group._h, i))
         self.V = group.V
         self.F = group.shards[i][2]
+        self._n_kp = self.F * self.V * self.model.n_loss_joints * 3
+        self._stage_by_address = _lib.by_address("bf_batch_stage_inputs")
 
     def close(self):
         self._h = None
@@ -155,7 +157,12 @@ class Group:
         _lib.check(self._lib.bf_group_set_init(self._h, _lib.fptr(b), _lib.fptr(p)), "bf_group_set_init")
 
     def stage_inputs(self, keypoints, n_use_frames, init_betas, init_pose):
-        """the whole job's NEXT frames, without draining the devices (bf_group_stage_inputs); the next fit() needs FIT_RESET"""
+        """the whole job's NEXT frames, without draining the devices (bf_group_stage_inputs); the next fit() needs FIT_RESET.  Conforming
+        arrays go by address, as in FrameBatch.stage_inputs."""
+        at = stage_addresses(self.F, self.F * self.V * self.info["n_loss_joints"] * 3, self.info["n_betas"], keypoints, n_use_frames, init_betas, init_pose)
+        if at is not None:
+            _lib.check(_lib.by_address("bf_group_stage_inputs")(self._h, at[0], at[1], at[2], at[3]), "bf_group_stage_inputs")
+            return
         kp = _f32(keypoints, (self.F, self.V, self.info["n_loss_joints"], 3))
         nd = None if n_use_frames is None else _i32(np.broadcast_to(np.asarray(n_use_frames), (self.F,)))
         b = _f32(init_betas, (self.F, self.info["n_betas"]))

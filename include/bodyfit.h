@@ -835,6 +835,11 @@ int bf_batch_debug_vertices(bf_batch *b, float *vertices);
 /* Fit-lane groups of the batch since it was created (api.hip; BF_FIT_LANES, BF_FIT_LANE_WIDTH): out[0] lane launches, out[1] the
  * frame-after-frame calls they carried, out[2] the most calls one launch carried, out[3] W, the most it may carry (1 without lanes) */
 int bf_batch_lane_stats(bf_batch *b, int32_t out[4]);
+/* How the fit lanes of the batch were fed since it was created: out[0] input transfers issued (host-fed groups: one per lane launch, and
+ * one for a slot that a drain found staged with no call joined; a launch per call, BF_FIT_LANE_WIDTH=1: one per staging), out[1] calls
+ * without a staging of their own whose inputs were copied on the host, pinned slot to pinned slot, out[2] such calls whose inputs were
+ * copied on the device, out[3] times the host had to wait for a pinned arena's previous transfer before filling it again */
+int bf_batch_lane_feed_stats(bf_batch *b, int64_t out[4]);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
