@@ -1,0 +1,163 @@
+"""The frame-loop routes of bf_fit (fit_plan, csrc/api.hip) on the models no other route test uses: the kid model (87 parameters, 11
+betas, the table-driven fit kernel, the 12-direction mesh instances), SMPL with a 6-bone loss selector (8-wide mesh), SMPL with one
+9-bone vertex (the sized fit instance beside a dense mesh tail) and the 690-vertex models with 5..8 and 9..12 bones per vertex.
+
+Lane groups, a launch per call and the single-stream route each run in a child of their own (tests/lane_models_child.py), which holds
+every streamed frame - every slot of a group, with a loss divisor that differs from slot to slot - bit for bit against the frame fitted
+alone.  Here: the streamed parameters must not depend on the setting; streamed frame 0 is held to the reference loop in fp64
+(oracle.smplify_oracle.fit on the CPU) at the project's 1e-4, so that routes agreeing with one another on a wrong answer would show;
+and the graph, pipelined-graph and untimed routes, which need no process of their own, give the bits of a plain call."""
+import numpy as np
+import pytest
+import torch
+
+from bodyfitting_amd import _lib, native as N
+from oracle import smplify_oracle as O
+from lane_models_child import ITERS, LANE_VARIANTS, VIEWS, ndiv_of
+from width_variants import Variants, smpl_problem
+
+pytestmark = pytest.mark.gpu
+PARAMS = ("global_transl", "scale", "pose", "betas", "global_orient")
+FIT_TOL = 1e-4                                           # the project's bound on a fit against the reference loop
+SETTINGS = [(1, 0, None), (3, 1, None), (8, 1, None), (1, 0, 1)]          # (BF_FIT_LANE_WIDTH, BF_FIT_LANE_FILL, BF_FIT_LANES or None)
+IDS = ["width1", "width3-fill", "width8-fill", "lanes1"]
+
+
+def _child(tmp_path, width, fill, lanes):
+    import conftest
+    import lane_models_child
+    if conftest.FRESH is None:
+        pytest.skip("no fork server")
+    out = str(tmp_path / "out.npz")
+    p = conftest.FRESH.Process(target=lane_models_child.models, args=(out, width, fill, lanes))
+    p.start()
+    p.join(600)
+    if p.is_alive():
+        p.terminate()
+        pytest.fail("the child hung")
+    err = tmp_path / "out.npz.err"
+    assert p.exitcode == 0, "exit code %s\n%s" % (p.exitcode, err.read_text() if err.exists() else "")
+    return np.load(out)
+
+
+@pytest.fixture(scope="module")
+def width_one(tmp_path_factory):
+    return _child(tmp_path_factory.mktemp("lane_models_1_0"), *SETTINGS[0])
+
+
+@pytest.fixture(scope="module")
+def variants(gmm):
+    v = Variants(gmm)
+    yield v
+    v.close()
+
+
+def test_a_launch_per_call_gives_the_frames_fitted_alone(width_one):
+    """the child's own assertions passed (every comparison with the frame fitted alone); what it hands on has the variants' sizes"""
+    for name in LANE_VARIANTS:
+        n_params = 87 if name == "kid" else 86
+        assert width_one[f"streamed_{name}"].shape == (8, n_params) and np.isfinite(width_one[f"streamed_{name}"]).all()
+        assert width_one[f"batch4_{name}"].shape == (10 * 4, n_params)
+        assert width_one[f"batch16_{name}"].shape == (5 * 16, n_params)
+        assert width_one[f"frame0_vertices_{name}"].shape == (690 if name.startswith("nv690") else 6890, 3)
+
+
+@pytest.mark.parametrize("width,fill,lanes", SETTINGS[1:], ids=IDS[1:])
+def test_streamed_frames_do_not_depend_on_the_setting(tmp_path, width_one, width, fill, lanes):
+    """groups of three, groups of eight (four for the 16-frame batches) and the single-stream route: the child's comparisons with the
+    frames fitted alone pass, and every streamed parameter is the launch-per-call child's, bit for bit"""
+    got = _child(tmp_path, width, fill, lanes)
+    for name in LANE_VARIANTS:
+        for key in (f"streamed_{name}", f"batch4_{name}", f"batch16_{name}"):
+            np.testing.assert_array_equal(got[key], width_one[key], err_msg=key)
+
+
+@pytest.mark.parametrize("name", LANE_VARIANTS)
+def test_streamed_frame_is_the_reference_loop(width_one, variants, gmm_bufs, name):
+    """streamed frame 0 (all 5 views count: n_use_frames = 5) after 20 iterations against oracle.smplify_oracle.fit in fp64 on the CPU, every
+    parameter group, the joints, the vertices and the full pose at 1e-4 (the bound of test_kid_fit_matches_oracle_loop and of the
+    skinning-width fits, there at 100 iterations).  Bit equality with the frame fitted alone only shows that the routes agree"""
+    model = variants.get(name)[0]
+    prob = smpl_problem(name, model, frame=0, n_views=VIEWS)
+    assert len(prob["use_frames"]) == int(ndiv_of(0, 1)[0])
+    want = O.fit(model, gmm_bufs, prob, ITERS, dtype=torch.float64)
+    nb = 11 if name == "kid" else 10
+    got = N.split_params(width_one[f"streamed_{name}"][0], 24, nb)
+    worst = 0.0
+    for k in PARAMS:
+        ref = want[k] if k != "global_transl" else want["raw_transl"]
+        worst = max(worst, float(np.abs(got[k] - ref).max()))
+    mesh = {k: float(np.abs(width_one[f"frame0_{k}_{name}"] - want[k]).max()) for k in ("vertices", "joints", "full_pose")}
+    print(f"{name}: streamed frame 0 against the reference loop after {ITERS} iterations: parameters {worst:.3g}, " +
+          ", ".join(f"{k} {v:.3g}" for k, v in mesh.items()) + f" (bound {FIT_TOL:g})")
+    for k in PARAMS:
+        ref = want[k] if k != "global_transl" else want["raw_transl"]
+        np.testing.assert_allclose(got[k], ref, rtol=0, atol=FIT_TOL, err_msg=f"{name} {k}")
+    for k in ("vertices", "joints", "full_pose"):
+        np.testing.assert_allclose(width_one[f"frame0_{k}_{name}"], want[k], rtol=0, atol=FIT_TOL, err_msg=f"{name} {k}")
+    if name == "kid":
+        assert got["betas"].shape == (11,)
+
+
+def _batch(dev, problems):
+    """the frames with the divisors the children stream them with (5, 3, 4, ...: the loss's divisor only)"""
+    c2w, K, kp, _, betas, pose = N.pack_problem(problems)
+    b = N.FrameBatch(dev, len(problems), c2w.shape[1])
+    b.set_cameras(c2w, K); b.set_keypoints(kp, ndiv_of(0, len(problems))); b.set_init(betas, pose)
+    return b
+
+
+def _same(b, a, what, vertices=True):
+    np.testing.assert_array_equal(b.get_params(), a.get_params(), err_msg=what)
+    for x, y, k in zip(b.get_result(vertices), a.get_result(vertices), ("vertices", "joints", "full_pose", "loss_terms")):
+        if x is not None:
+            np.testing.assert_array_equal(x, y, err_msg=f"{what}: {k}")
+
+
+@pytest.mark.parametrize("name", LANE_VARIANTS)
+def test_graph_and_untimed_routes_equal_the_plain_call(variants, name):
+    """GRAPH (RESET | FETCH | GRAPH, three replays; another call shape re-captures) and UNTIMED (RESET | NOTIME | NO_VERTICES | FETCH)
+    on a 2-frame batch - the table-driven fit kernel (the sized one for 4+1) and bf_mesh_multi_kernel's 8-wide / dense / 12-direction
+    loops inside a captured graph - against a plain fit(n, FETCH | RESET) of a second batch, bit for bit"""
+    model, dev = variants.get(name)
+    probs = [smpl_problem(name, model, frame=f, n_views=VIEWS) for f in (0, 1)]
+    a, b = _batch(dev, probs), _batch(dev, probs)
+    plain = _lib.FIT_FETCH | _lib.FIT_RESET
+    a.fit(ITERS, flags=plain)
+    for i in range(3):
+        b.fit(ITERS, flags=plain | _lib.FIT_GRAPH)
+        _same(b, a, f"{name}: graph replay {i}")
+    a.fit(12, flags=plain)
+    b.fit(12, flags=plain | _lib.FIT_GRAPH)                                   # a different call shape re-captures
+    _same(b, a, f"{name}: re-captured graph")
+    a.fit(ITERS, flags=plain)
+    b.fit(ITERS, flags=_lib.FIT_RESET | _lib.FIT_NOTIME | _lib.FIT_NO_VERTICES | _lib.FIT_FETCH)
+    _same(b, a, f"{name}: untimed", vertices=False)
+    a.close()
+    b.close()
+
+
+def test_kid_pipelined_graph_equals_the_plain_call(variants):
+    """kid, 8 frames: the result is 661 KB, above the 512 KB from which RESET | FETCH | GRAPH takes GRAPH_PIPELINED (kernels only in
+    the graph, the fetch on the second stream, the two result arenas in turn).  Read through get_result and, after a second call on
+    other inputs, through get_previous; both against plain calls of a second batch, bit for bit"""
+    model, dev = variants.get("kid")
+    first = [smpl_problem("kid", model, frame=f, n_views=VIEWS) for f in range(8)]
+    second = [smpl_problem("kid", model, frame=20 + f, n_views=VIEWS) for f in range(8)]
+    plain = _lib.FIT_FETCH | _lib.FIT_RESET
+    a, a2, b = _batch(dev, first), _batch(dev, second), _batch(dev, first)
+    assert 8 * dev.n_verts * 3 * 4 >= 512 * 1024
+    a.fit(ITERS, flags=plain)
+    a2.fit(ITERS, flags=plain)
+    b.fit(ITERS, flags=plain | _lib.FIT_GRAPH)
+    _same(b, a, "kid: pipelined graph, get_result")
+    _, _, kp, _, betas, pose = N.pack_problem(second)
+    b.stage_inputs(kp, ndiv_of(0, 8), betas, pose)
+    b.fit(ITERS, flags=plain | _lib.FIT_GRAPH)
+    prev = b.get_previous()
+    for x, y, k in zip(prev, (a.get_params(),) + a.get_result(), ("params", "vertices", "joints", "full_pose", "loss_terms")):
+        np.testing.assert_array_equal(x, y, err_msg=f"kid: pipelined graph, get_previous: {k}")
+    _same(b, a2, "kid: second pipelined graph call")
+    a.close()
+    a2.close()
+    b.close()

@@ -20,72 +20,19 @@ import pytest
 import torch
 
 from conftest import load_golden
-from bodyfitting_amd import model_files, native as N, synthetic as S
+from bodyfitting_amd import native as N, synthetic as S
 from oracle import smplify_oracle as O
 from oracle.contour_oracle import border_pixels_rowmajor_all as extract_contours
 import ref_drift as RD
-from test_skinning_width import loss_selectors, quiet_vertex, width_class
+from width_variants import Variants, quiet_vertex, smpl_problem as _smpl_problem          # (the table of variants, their class check and problems)
 
 pytestmark = pytest.mark.gpu
 PARAMS = ("global_transl", "scale", "pose", "betas", "global_orient")
-KID_BETA = 0.4
 MASK_FRAMES = [1, 3, 5, 7]
 # the forward's dispatch boundaries (api.hip bf_launch_mesh): 1 frame (bf_mesh_kernel or the one-frame multi kernel, `pre` rows for
 # v_nnz 4 / 8 and nb <= 10 / 12), 2..15 (bf_mesh_multi_kernel, 2 / 4 / 8 frames per workgroup), 16..64 (bf_mesh_batch32_kernel - v_nnz 4
 # only - else the pose-blend GEMM), > 64 (GEMM + bf_mesh_epilogue_batch_kernel for v_nnz 4, bf_mesh_epilogue_kernel otherwise)
 FORWARD_N = (1, 2, 8, 9, 15, 16, 17, 32, 33, 64, 65, 128, 129)
-
-# name -> (model type, nv, bones, override key, kid, expected (v_nnz, sel_nnz or a range), fit instance)
-VARIANTS = {
-    "smpl_B8": ("smpl", None, (5, 8), None, False, (8, (5, 8)), "table-driven"),
-    "smpl_BD": ("smpl", None, (9, 12), None, False, (0, 0), "table-driven"),
-    "smpl_4+1": ("smpl", None, 4, "quiet", False, (0, 4), "sized"),
-    "smpl_4+S": ("smpl", None, 4, "selector", False, (8, 6), "table-driven"),
-    "kid_B8": ("smpl", None, (5, 8), None, True, (8, (5, 8)), "table-driven"),
-    "smplx_4": ("smplx", None, 4, None, False, (4, 0), "table-driven"),
-    "smplx_B8": ("smplx", None, (5, 8), None, False, (8, 0), "table-driven"),
-    "smplx_BD": ("smplx", None, (9, 12), None, False, (0, 0), "table-driven"),
-    "nv690_B8": ("smpl", 690, (5, 8), None, False, (8, (5, 8)), "table-driven"),
-    "nv690_BD": ("smpl", 690, (9, 12), None, False, (0, 0), "table-driven"),
-}
-
-
-def build_model(name):
-    kind, nv, bones, over, kid, _, _ = VARIANTS[name]
-    wide = None
-    if over:
-        base = S.make_model(kind, nv=nv)
-        wide = {quiet_vertex(base): 9} if over == "quiet" else {loss_selectors(base)[0]: 6}
-    model = S.make_model(kind, seed=0, nv=nv, bones=bones, wide=wide)
-    if kid:
-        model = model_files.kid_model(model, S.make_kid_template(model))
-    return model
-
-
-class Variants:
-    """the variants' models and device models, built on first use and checked for their class"""
-
-    def __init__(self, gmm):
-        self.gmm, self.models, self.devs, self.cache = gmm, {}, {}, {}
-
-    def get(self, name):
-        if name not in self.devs:
-            model = build_model(name)
-            want_class, want_instance = VARIANTS[name][5:]
-            v_nnz, sel_nnz = width_class(model)
-            assert v_nnz == want_class[0], (name, v_nnz)
-            if isinstance(want_class[1], tuple):
-                assert want_class[1][0] <= sel_nnz <= want_class[1][1], (name, sel_nnz)
-            else:
-                assert sel_nnz == want_class[1], (name, sel_nnz)
-            dev = N.DeviceModel(model, self.gmm, device=0)
-            assert dev.fit_instance == want_instance, (name, dev.fit_instance)
-            self.models[name], self.devs[name] = model, dev
-        return self.models[name], self.devs[name]
-
-    def close(self):
-        for d in self.devs.values():
-            d.close()
 
 
 @pytest.fixture(scope="module")
@@ -100,12 +47,6 @@ def _batch(dev, problems):
     b = N.FrameBatch(dev, len(problems), c2w.shape[1])
     b.set_cameras(c2w, K); b.set_keypoints(kp, ndiv); b.set_init(betas, pose)
     return b
-
-
-def _smpl_problem(name, model, frame=0, n_views=48, **kw):
-    if VARIANTS[name][4]:
-        return S.as_kid_problem(S.make_problem(S.kid_problem_model(model, KID_BETA), frame=frame, n_views=n_views, **kw), KID_BETA)
-    return S.make_problem(model, frame=frame, n_views=n_views, **kw)
 
 
 # ---- a. forward at every dispatch boundary ------------------------------------------------------------------------------------

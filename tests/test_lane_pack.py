@@ -9,7 +9,7 @@ import subprocess
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CASES = [(F, V, W, n_params) for F in (1, 4) for V in (1, 12, 50) for W in (1, 3, 8) for n_params in (86, 87)]
+CASES = [(F, V, W, n_params) for F in (1, 4, 16) for V in (1, 5, 12, 50) for W in (1, 3, 8) for n_params in (86, 87)]
 
 
 @pytest.fixture(scope="module")

@@ -8,37 +8,7 @@ import torch
 
 from bodyfitting_amd import synthetic as S
 from oracle import smplify_oracle as O
-
-N_LOSS_JOINTS = {"smpl": 25, "smplx": 135}      # the keypoint loss's joints (native.model_desc)
-
-
-def width_class(model):
-    """(v_nnz, sel_nnz) as derive_tables sets them: the most bones of any vertex -> 4 / 8 / 0; the most of the selector vertices
-    the routed keypoint loss reads (none when the loss is dense, more than 32 joints) -> that count if <= BF_SEL_NNZ = 8, else 0"""
-    lw = np.asarray(model["lbs_weights"])
-    nnz = (lw != 0).sum(1)
-    most = int(nnz.max())
-    nl = N_LOSS_JOINTS[model.get("model_type", "smpl")]
-    jm = np.asarray(model["joint_map"])[:nl] if nl <= 32 else np.zeros(0, np.int64)
-    sel = np.asarray(model["selector_ids"])[jm[jm >= lw.shape[1]] - lw.shape[1]]
-    s = int(nnz[sel].max()) if len(sel) else 0
-    return (4 if most <= 4 else 8 if most <= 8 else 0), (s if s <= 8 else 0)
-
-
-def loss_selectors(model):
-    """the selector vertices the SMPL keypoint loss reads (FitTab's selector rows), in joint-map order"""
-    nj = np.asarray(model["lbs_weights"]).shape[1]
-    jm = np.asarray(model["joint_map"])[:N_LOSS_JOINTS["smpl"]]
-    return [int(v) for v in np.asarray(model["selector_ids"])[jm[jm >= nj] - nj]]
-
-
-def quiet_vertex(model):
-    """a vertex no selector and no regressor row touches: widening it moves v_nnz and nothing the fit's selector rows read"""
-    busy = set(np.asarray(model["selector_ids"]).tolist())
-    for k in ("J_regressor_extra", "J_regressor"):
-        if k in model:
-            busy |= set(np.nonzero(np.asarray(model[k]).any(0))[0].tolist())
-    return next(v for v in range(np.asarray(model["v_template"]).shape[0]) if v not in busy)
+from width_variants import loss_selectors, quiet_vertex, width_class          # (shared with the GPU tests and their child processes)
 
 
 def _edges(faces):
