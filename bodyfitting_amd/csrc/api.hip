@@ -2,6 +2,7 @@
 #include "bf_host.h"
 #include "fit_kernels.h"
 #include "mesh_kernels.h"
+#include "mesh_choice.h"
 #include <cassert>
 #include <chrono>
 
@@ -48,6 +49,8 @@ static void host_sums_report(const void *b) {
 #define BF_HOST_TIMED(b, k) do { } while (0)
 #endif
 
+static_assert(kBfMeshMfmaMinFrames == BF_MFMA_MIN_FRAMES && kBfMeshBatch32MaxFrames == BF_BATCH32_MAX_FRAMES, "mesh_choice.h repeats bf_internal.h's thresholds");
+
 extern "C" {
 
 const char *bf_last_error(void) { return bf_err_slot().c_str(); }
@@ -86,27 +89,33 @@ int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &told) {
     const MeshTab &Q = p.tab ? *p.tab : m->mesh;          // (the sampled-first sub-model inside a dense loop without scans)
     dim3 grid(Q.n_tiles, n);
     const float *pose_off = nullptr;
-    // a fit-lane group (p.per): the kernel is chosen as for one call's frames.  bf_mesh_kernel's blocks are (tile, frame) - one launch
-    // covers the group; the kernels below tile over frames, so each call's frames get a pass of their own
-    const int n_sel = (p.per > 0 && p.per < n) ? p.per : n;
-    const bool plain = !(n_sel >= BF_MFMA_MIN_FRAMES && !p.tab) && !bf_mesh_use_multi(m->npf, n_sel);
-    if (n_sel < n && !plain) {
-        if (n % n_sel || p.vposed || p.dvzero || p.mproj || p.door || p.mesh_done)
+    // which kernel, in how many passes (mesh_choice.h).  A fit-lane group (p.per) of calls below the matrix-core threshold is ONE launch of
+    // the multi-frame kernel over all its frames: a tile's posedirs slice is streamed once per eight frames, not once per frame
+    // (bf_mesh_kernel's grid (tiles, frames)) or once per call; the kernels do the same arithmetic in the same order per frame, and the
+    // group's state, vertex and extra-joint partial arrays are frame-major and contiguous, which is how the kernel indexes them
+    // ((frame, tile, extra) for xpart).  A group of larger calls gets a pass per call, each the matrix-core kernel the call gets alone.
+    const bool group = p.per > 0 && p.per < n;
+    assert(bf_mesh_choice_multi(m->npf, 1) == (bf_mesh_use_multi(m->npf, 1) != 0) && "mesh_choice.h and bf_mesh_use_multi agree on the single-frame kernel");
+    const BfMeshChoice ch = bf_mesh_choice(p.per, n, m->npf, p.tab != nullptr, (p.vposed ? BF_MESH_CHOICE_VPOSED : 0u) |
+                                           (bf_mesh_batch32_fits(&m->mesh) ? BF_MESH_CHOICE_BATCH32_FITS : 0u));
+    if (group && n % p.per) return fail(BF_ERR_INVALID, "bf_launch_mesh: a grouped pass carries whole calls only");
+    if (ch.passes > 1) {
+        if (p.vposed || p.dvzero || p.mproj || p.door || p.mesh_done)
             return fail(BF_ERR_INVALID, "bf_launch_mesh: a grouped pass carries the result mesh of whole calls only");
         MeshPass q = p;
-        q.per = 0; q.n = n_sel; q.joints = q.joints_ori = q.jraw = nullptr; q.want_xpart = xpart != nullptr; q.after_mesh = nullptr;
+        q.per = 0; q.n = ch.frames; q.joints = q.joints_ori = q.jraw = nullptr; q.want_xpart = xpart != nullptr; q.after_mesh = nullptr;
         const size_t s_state = bf_state_stride(m->nj, m->npf, m->nb), s_v = (size_t)m->nv * 3, s_x = (size_t)Q.n_tiles * Q.n_extra * 3;
-        for (int c = 0; c < n / n_sel; ++c) {
-            const size_t f0 = (size_t)c * n_sel;
+        for (int c = 0; c < ch.passes; ++c) {
+            const size_t f0 = (size_t)c * ch.frames;
             q.state = p.state + f0 * s_state; q.vraw = p.vraw + f0 * s_v; q.vout = p.vout ? p.vout + f0 * s_v : nullptr;
             q.xpart = p.xpart ? p.xpart + f0 * s_x : nullptr;
             BF_TRY(bf_launch_mesh(m, q));
         }
-    } else if (!plain && n >= BF_MFMA_MIN_FRAMES && n <= BF_BATCH32_MAX_FRAMES && !p.tab && !p.vposed && bf_mesh_batch32_fits(&m->mesh)) {
+    } else if (ch.kernel == BfMeshKernel::BATCH32) {
         // one or two 32-frame blocks: pose blend on the matrix cores with the epilogue behind the accumulators, ONE launch
         // (13.4 us instead of 4.6 + 15.5 + 14.5 at 32 frames; from 128 frames on the 128-frame GEMM tile below wins)
         HIP_TRY(bf_mesh_batch32_launch(&m->mesh, p.state, n, p.vraw, p.vout, xpart, stream));
-    } else if (!plain && n >= BF_MFMA_MIN_FRAMES && !p.tab) {
+    } else if (ch.kernel == BfMeshKernel::GEMM) {
         // batched pose blend on the matrix cores (posedirs streamed once for up to 256 frames), then the per-frame
         // shape / skinning part only
         const size_t ncols = (size_t)m->nv * 3;
@@ -123,7 +132,7 @@ int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &told) {
             bf_mesh_epilogue_batch_launch(&m->mesh, p.state, pose_off, n, p.vraw, p.vout, xpart, stream);
         } else
         hipLaunchKernelGGL(bf_mesh_epilogue_kernel, grid, dim3(128), 0, stream, m->mesh, p.state, pose_off, p.vraw, p.vout, xpart, p.vposed);
-    } else if (!plain) {
+    } else if (ch.kernel == BfMeshKernel::MULTI) {
         const int e = bf_mesh_multi_launch(&Q, p.state, n, p.vraw, p.vout, xpart, p.vposed, p.dvzero, stream, p.mproj, p.door, p.door_target,
                                            p.mesh_done);
         if (e) return fail(BF_ERR_HIP, std::string("bf_mesh_multi_kernel: ") + hipGetErrorString((hipError_t)e));
@@ -327,8 +336,12 @@ int bf_flush_tail(bf_batch *b) {
  *     takes any number of independent frames, one workgroup each, in hardly more time.  So a lane call does not launch at once: it
  *     JOINS the open group of lane `lane_next` - slot after slot of that lane's input arena, up to W calls - and one launch of G F
  *     workgroups, one tail and one hand-over serve the G calls that joined (lane_launch).  The group goes out when a call joins while
- *     its lane is idle (a slow feeder gets G = 1 and no added latency), when it is full (behind the lane's running group), when its
- *     calls would differ in iterations or hyper-parameters, and at every entry point that drains or reads.  Then `lane_next` moves on.
+ *     its lane is idle (a slow feeder gets G = 1 and no added latency) - unless the feeder is fast and the group young, see
+ *     BF_FIT_LANE_HOLD_US below - when it is full (behind the lane's running group), when its calls would differ in iterations or
+ *     hyper-parameters, and at every entry point that drains or reads.  Then `lane_next` moves on.
+ *     BF_FIT_LANE_HOLD_US=<H> (default 100): a group that finds its lane idle is still held while the call before came less than H
+ *     microseconds ago AND the group's first call joined less than H ago - a burst fills groups instead of sending its first calls out
+ *     alone; a lone or slow caller never waits, and H bounds what a burst's frames can be held.  0: an idle lane always launches.
  *     BF_FIT_LANE_WIDTH=<n> caps W (default 32; 1: a launch per call, the call sequence before groups); a batch uses at most
  *     CUs / (lanes x frames).  BF_FIT_LANE_FILL=1 turns the idle rule off - groups fill to W or to a flush - so that tests can force
  *     group shapes.
@@ -359,9 +372,15 @@ static int env_int(const char *name, int dflt, int lo, int hi) {
     const char *e = getenv(name);
     return std::max(lo, std::min(e ? atoi(e) : dflt, hi));
 }
+#ifndef BF_FIT_LANE_HOLD_US_DEFAULT
+#define BF_FIT_LANE_HOLD_US_DEFAULT 100
+#endif
 static int fit_lanes_wanted() { static const int d = env_int("BF_FIT_LANES", 4, 1, 32); return d; }
 static int fit_lane_width_wanted() { static const int d = env_int("BF_FIT_LANE_WIDTH", 32, 1, 64); return d; }
 static bool fit_lane_fill() { static const bool d = env_int("BF_FIT_LANE_FILL", 0, 0, 1) == 1; return d; }
+// H of the idle rule (fit_lane): a group that finds its lane idle is held while the feeder is fast - the call before this one less than H ago -
+// and the group younger than H.  0: an idle lane always launches (the rule before the hold)
+static std::chrono::microseconds fit_lane_hold() { static const int d = env_int("BF_FIT_LANE_HOLD_US", BF_FIT_LANE_HOLD_US_DEFAULT, 0, 10000000); return std::chrono::microseconds(d); }
 // a group's hand-over from this size on is a copy command, below it the publish kernel: the threshold fit_plan uses for a call.  Measured
 // for groups (profiles/fit_lane_groups.md): the publish kernel for full groups is the slowest, always copying no better than this
 static constexpr size_t kLaneCopyBytes = (size_t)512 * 1024;
@@ -449,7 +468,7 @@ static int lane_feed(bf_batch *b, int j, LaneInputs &in, int n) {
 }
 
 // The open group of lane j goes out: for a host-fed group its one input transfer, then ONE fit launch for the G F frames of the G calls
-// that joined, the tail for all of them (each call's frames through the kernel and the blocks they would get alone: MeshPass::per), one
+// that joined, the tail for all of them (ONE multi-frame mesh launch for calls below 16 frames, a pass per call above: MeshPass::per), one
 // hand-over of the group's floats, ev_copied.
 // The result arrays are packed for G F frames - FrameIO is array-major over n_frames - and their offsets stay with the group (`held`).
 // The lane's group is closed whatever happens, and the next call joins the next lane.
@@ -1089,7 +1108,12 @@ static int fit_lane(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &
     BF_TRY(lane_begin(b, l));
     b->fetched = false; b->have_result = false;                 // (a failure from here on: nothing of this call may be read)
     const int slot = l.n_open;
-    if (slot == 0) { l.open_seq0 = b->fit_seq; l.open_iters = c.n_iters; l.open_hd = hd; l.borrowed = false; }
+    // the feed, for the idle rule below: ONE clock read per call
+    const auto now = std::chrono::steady_clock::now();
+    const std::chrono::microseconds H = fit_lane_hold();
+    const bool fast_feed = b->lane_called && now - b->lane_t_call < H;
+    b->lane_t_call = now; b->lane_called = true;
+    if (slot == 0) { l.open_seq0 = b->fit_seq; l.open_iters = c.n_iters; l.open_hd = hd; l.borrowed = false; l.t_first = now; }
     if (!l.slot_staged && W == 1) {
         // a launch per call: the fit reads the current inputs in place.  Another lane's slot is read without a wait for its transfer,
         // as before groups (width 1 is that call sequence): the transfer went out on its lane ahead of a fit launch that has since
@@ -1131,11 +1155,20 @@ static int fit_lane(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &
     b->lane_calls += 1;
     done = {true, true, false};
     if (l.n_open >= W) return lane_launch(b, j);                // full: behind the lane's running group, in stream order
-    if (!fit_lane_fill()) {                                     // the lane is idle: now, a slow feeder waits for nobody
-        const hipError_t q = hipEventQuery(l.arena.ev_copied);
-        if (q == hipSuccess) return lane_launch(b, j);
-        (void)hipGetLastError();
-        if (q != hipErrorNotReady) HIP_TRY(q);
+    if (!fit_lane_fill()) {
+        // The lane is idle: now - a slow feeder waits for nobody, and a fast feeder's first call after a pause goes out alone - UNLESS the
+        // feeder is fast (the call before this one came less than H ago) and the group is young (its first call joined less than H ago).
+        // Then it is held exactly as a group behind a busy lane is: a burst fills groups instead of sending its first calls out one by
+        // one, each a whole launch sequence and a lane cycle for one frame.  The group goes out when it is full, at the first call that
+        // finds the feeder slow or the group H old, and at every read, drain, sync or destroy - H bounds what the rule adds to a burst's
+        // frames.  W = 1 and H = 0: the idle rule alone.
+        const bool hold = W > 1 && fast_feed && now - l.t_first < H;
+        if (!hold) {
+            const hipError_t q = hipEventQuery(l.arena.ev_copied);
+            if (q == hipSuccess) return lane_launch(b, j);
+            (void)hipGetLastError();
+            if (q != hipErrorNotReady) HIP_TRY(q);
+        }
     }
     return BF_OK;
 }

@@ -5,6 +5,7 @@
 #include "lane_slots.h"
 
 #include <atomic>
+#include <chrono>
 #include <cstdlib>
 #include <algorithm>
 #include <cmath>
@@ -341,6 +342,7 @@ struct BfLane {
     const float *bor_kp = nullptr, *bor_p0 = nullptr;
     const int *bor_ndiv = nullptr;
     long long open_seq0 = -1;                   // the first joined call's fit number
+    std::chrono::steady_clock::time_point t_first{};    // ... and when it joined (the idle rule's hold, BF_FIT_LANE_HOLD_US)
     int open_iters = 0;
     HyperDev open_hd{};
     // the launched group the result arena holds (or will, once ev_copied completes): fits seq0 .. seq0 + G - 1, slot after slot
@@ -481,6 +483,8 @@ struct bf_batch {
     DevBuf<float> proj_rep;             // (W > 1) the projection table W times over: FrameIO::proj of a group launch
     bool proj_rep_stale = true;         // ... has yet to be copied from `proj` (new cameras)
     int lane_launches = 0, lane_calls = 0, lane_max_g = 0;      // bf_batch_lane_stats
+    bool lane_called = false;           // a LANE-route call has been issued on this batch,
+    std::chrono::steady_clock::time_point lane_t_call{};        // ... the last one then: the feeder is fast while calls follow within H (fit_lane)
     long long feed_transfers = 0, feed_host_copies = 0, feed_dev_copies = 0, feed_waits = 0;    // bf_batch_lane_feed_stats
     hipEvent_t ev_engage = nullptr;     // recorded on the batch stream when the lanes take over: every lane stream waits for it
 };
@@ -509,7 +513,8 @@ struct MeshPass {
     MeshScratch *scr = nullptr;         // the stream owner's scratch: the batched path (>= BF_MFMA_MIN_FRAMES frames) needs one
     int n = 0;
     int per = 0;                        // > 0: the n frames are n / per independent calls' of `per` frames each (a fit-lane group) and every
-                                        // call's frames get the kernel and the blocks they would get alone - the bits do not depend on the group
+                                        // frame gets the bits it gets in a pass of its call alone: one multi-frame launch for calls below 16
+                                        // frames, a pass per call from there on (mesh_choice.h)
     const float *state = nullptr;
     hipStream_t stream = nullptr;
     const MeshTab *tab = nullptr;       // the sampled-first sub-model inside a dense loop without scans (null: the model's own table)
