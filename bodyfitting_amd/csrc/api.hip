@@ -95,6 +95,10 @@ int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &told) {
     // group's state, vertex and extra-joint partial arrays are frame-major and contiguous, which is how the kernel indexes them
     // ((frame, tile, extra) for xpart).  A group of larger calls gets a pass per call, each the matrix-core kernel the call gets alone.
     const bool group = p.per > 0 && p.per < n;
+    // the arena's pinned mirror, for the kernels that store to it themselves (the plain and the multi-frame kernel): a pass that hands over
+    // is a result pass - vertices and mapped joints into an arena - with no doorbell, sub-model table or vposed
+    const BfHandOver *const ho = (p.mirror && p.vout && p.joints && !p.door && !p.tab && !p.vposed) ? p.mirror : nullptr;
+    bool mirrored = false;
     assert(bf_mesh_choice_multi(m->npf, 1) == (bf_mesh_use_multi(m->npf, 1) != 0) && "mesh_choice.h and bf_mesh_use_multi agree on the single-frame kernel");
     const BfMeshChoice ch = bf_mesh_choice(p.per, n, m->npf, p.tab != nullptr, (p.vposed ? BF_MESH_CHOICE_VPOSED : 0u) |
                                            (bf_mesh_batch32_fits(&m->mesh) ? BF_MESH_CHOICE_BATCH32_FITS : 0u));
@@ -104,6 +108,7 @@ int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &told) {
             return fail(BF_ERR_INVALID, "bf_launch_mesh: a grouped pass carries the result mesh of whole calls only");
         MeshPass q = p;
         q.per = 0; q.n = ch.frames; q.joints = q.joints_ori = q.jraw = nullptr; q.want_xpart = xpart != nullptr; q.after_mesh = nullptr;
+        q.mirror = nullptr;                               // (calls of 16 frames and more: the matrix-core kernels, which leave the hand-over to a copy command)
         const size_t s_state = bf_state_stride(m->nj, m->npf, m->nb), s_v = (size_t)m->nv * 3, s_x = (size_t)Q.n_tiles * Q.n_extra * 3;
         for (int c = 0; c < ch.passes; ++c) {
             const size_t f0 = (size_t)c * ch.frames;
@@ -134,20 +139,24 @@ int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &told) {
         hipLaunchKernelGGL(bf_mesh_epilogue_kernel, grid, dim3(128), 0, stream, m->mesh, p.state, pose_off, p.vraw, p.vout, xpart, p.vposed);
     } else if (ch.kernel == BfMeshKernel::MULTI) {
         const int e = bf_mesh_multi_launch(&Q, p.state, n, p.vraw, p.vout, xpart, p.vposed, p.dvzero, stream, p.mproj, p.door, p.door_target,
-                                           p.mesh_done);
+                                           p.mesh_done, ho ? ho->vout : nullptr);
         if (e) return fail(BF_ERR_HIP, std::string("bf_mesh_multi_kernel: ") + hipGetErrorString((hipError_t)e));
         told.mesh_done_set = p.mesh_done != nullptr;          // (the event completes with the mesh dispatch: the caller records nothing)
         told.projected = p.mproj != nullptr;
         told.zeroed = p.dvzero != nullptr;
-    } else
-    hipLaunchKernelGGL(bf_mesh_kernel, grid, dim3(BF_MESH_TILE * 3 * BF_MESH_RG), m->mesh_smem, stream, Q,
-                       p.state, p.vraw, p.vout, xpart, p.vposed, pose_off, p.door, p.door_target);
+        mirrored = ho != nullptr;
+    } else {
+        hipLaunchKernelGGL(bf_mesh_kernel, grid, dim3(BF_MESH_TILE * 3 * BF_MESH_RG), m->mesh_smem, stream, Q,
+                           p.state, p.vraw, p.vout, xpart, p.vposed, pose_off, p.door, p.door_target, ho ? ho->vout : (float *)nullptr);
+        mirrored = ho != nullptr;
+    }
     HIP_TRY(hipGetLastError());
     if (p.after_mesh) HIP_TRY(hipEventRecord(p.after_mesh, stream));
     if (p.joints || p.joints_ori || p.jraw) {
         hipLaunchKernelGGL(bf_joints_kernel, dim3(n), dim3(256), 0, stream, Q, p.state, (const float *)p.vraw,
-                           (const float *)p.xpart, p.joints, p.joints_ori, p.jraw, p.lmk_vid, p.lmk_w);
+                           (const float *)p.xpart, p.joints, p.joints_ori, p.jraw, p.lmk_vid, p.lmk_w, mirrored ? *ho : BfHandOver{});
         HIP_TRY(hipGetLastError());
+        told.handed_over = mirrored;                      // (vertices by the mesh launch, the four small slices by this one: nothing left to copy)
     }
     return BF_OK;
 }
@@ -203,7 +212,27 @@ __global__ void __launch_bounds__(256) __attribute__((visibility("hidden"))) bf_
     }
 }
 
+
+// Seven ranges in one launch: what a drain hands back from a lane's group to the batch - the five result slices of the group's last slot
+// and its two Adam-moment rows, device to device (bf_lanes_drain).  Float-aligned places like the above: 4-byte accesses.
+struct BfSeg7 { const float *src[7]; float *dst[7]; unsigned n[7]; };
+__global__ void __launch_bounds__(256) __attribute__((visibility("hidden"))) bf_publish7_kernel(BfSeg7 s) {
+    for (int k = 0; k < 7; ++k) {
+        const float *__restrict__ src = s.src[k];
+        float *__restrict__ dst = s.dst[k];
+        for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < s.n[k]; i += gridDim.x * 256) dst[i] = src[i];
+    }
+}
+
 }  // extern "C"
+static int publish7(hipStream_t stream, const BfSeg7 &seg) {
+    unsigned most = 1;
+    for (int k = 0; k < 7; ++k) most = std::max(most, seg.n[k]);
+    hipLaunchKernelGGL(bf_publish7_kernel, dim3(std::min((most + 255) / 256, 64u)), dim3(256), 0, stream, seg);
+    HIP_TRY(hipGetLastError());
+    return BF_OK;
+}
+
 static int publish3(hipStream_t stream, const BfSeg3 &seg) {
     const unsigned most = std::max(seg.n[0], std::max(seg.n[1], seg.n[2]));
     hipLaunchKernelGGL(bf_publish3_kernel, dim3(std::min(std::max((most + 255) / 256, 1u), 64u)), dim3(256), 0, stream, seg);
@@ -228,27 +257,61 @@ static int hand_over(hipStream_t stream, ResultArena &r, size_t n_floats, bool b
 
 // the result mesh of a batch: vertices and mapped joints of its F frames from their pose states, on `stream` with that stream's owner's
 // scratch; `after_mesh`: an event recorded between the mesh and the joints pass
+// `mirror`: the arena's pinned mirror, for a pass that may hand its results over itself; *handed_over then says whether it did
 static int result_mesh(bf_batch *b, MeshScratch *scr, const float *state, float *vraw, float *vout, float *xpart, float *joints,
-                       hipStream_t stream, hipEvent_t after_mesh = nullptr) {
+                       hipStream_t stream, hipEvent_t after_mesh = nullptr, const BfHandOver *mirror = nullptr, bool *handed_over = nullptr) {
     MeshPass p;
     p.scr = scr; p.n = b->F; p.state = state; p.stream = stream;
     p.vraw = vraw; p.vout = vout; p.xpart = xpart; p.joints = joints;
     p.after_mesh = after_mesh;
-    return bf_launch_mesh(b->m, p);
+    p.mirror = mirror;
+    MeshPassDone did;
+    const int rc = bf_launch_mesh(b->m, p, did);
+    if (handed_over) *handed_over = did.handed_over;
+    return rc;
 }
 // ... into the batch's current arena, on the batch stream
 static int result_mesh(bf_batch *b, hipEvent_t after_mesh = nullptr) {
     return result_mesh(b, &b->scratch, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, b->stream, after_mesh);
 }
 
+// Whether the tail of `n_frames` frames whose arena prefix is `bytes` long lets its mesh and joints kernels store into the pinned mirror
+// themselves (MeshPass::mirror) instead of a hand-over behind them.  Stores over PCIe are no faster than the copy engine: a one-round
+// mesh grid issues them all at its end, and the kernel then lasts its stream plus the transfer (33 -> 71 us at 32 frames).  What they
+// save is the copy command's start-up behind the joints pass and a launch.  Measured, fit end to end of hand-over (profiles/lane_tail.md):
+// against the copy command - 7 frames and more, 512 KB as in kLaneCopyBytes - the stores win at every size (47 -> 31 us at 7 frames,
+// 104 -> 80 at 32); against the publish kernel below that they win for a lone frame (17.8 -> 14.9 us, the lone caller's round trip 479 ->
+// 452 us) and tie at 2-6 frames (medians 0.6-2 us lower, not below the other's fastest): those keep the publish kernel.
+static constexpr size_t kTailStoreBytes = (size_t)512 * 1024;
+static bool tail_stores(const bf_batch *b, size_t bytes, int n_frames) {
+    if (b->tail_handover != bf_batch::TailHandOver::BY_SIZE) return b->tail_handover == bf_batch::TailHandOver::STORE;
+    return n_frames == 1 || bytes >= kTailStoreBytes;
+}
+
+// where the five slices of an arena laid out by `off` (the batch's res_off, or a lane group's) live on the device and in the pinned mirror
+static BfHandOver arena_mirror(const bf_batch *b, const ResultArena &r, const size_t off[5]) {
+    BfHandOver ho;
+    ho.d_params = r.dev.p + off[0]; ho.d_terms = r.dev.p + off[1];
+    ho.params = r.host + off[0]; ho.terms = r.host + off[1]; ho.state = r.host + off[2]; ho.joints = r.host + off[3]; ho.vout = r.host + off[4];
+    ho.np = b->m->np; ho.nt = (int)(b->res_cnt[1] / b->F);
+    return ho;
+}
+
 // the tail of a fit: mesh, joints and hand-over of the first n_floats of result arena r on `stream` (scratch, vraw, xpart: that stream's
 // owner's), then ev_copied.  `after`: the event the stream waits for first; with_mesh = false: the arena already holds its mesh.
+// A whole-arena tail with its mesh (bf_flush_tail) lets the mesh and joints kernels store into the mirror themselves where tail_stores says
+// so, and issues a hand-over only if the pass took kernels that do not (MeshPassDone::handed_over).
 static int enqueue_tail(bf_batch *b, ResultArena &r, hipStream_t stream, MeshScratch *scr, float *vraw, float *xpart, size_t n_floats,
                         bool big, hipEvent_t after = nullptr, bool with_mesh = true) {
     if (after) HIP_TRY(hipStreamWaitEvent(stream, after, 0));
     float *d = r.dev.p;                              // (the arena's slices by address: the batch's views may be on another one)
-    if (with_mesh) BF_TRY(result_mesh(b, scr, d + b->res_off[2], vraw, d + b->res_off[4], xpart, d + b->res_off[3], stream));
-    BF_TRY(hand_over(stream, r, n_floats, big));
+    bool handed_over = false;
+    if (with_mesh) {
+        const BfHandOver ho = arena_mirror(b, r, b->res_off);
+        const bool store = n_floats == b->res_total && tail_stores(b, n_floats * sizeof(float), b->F);
+        BF_TRY(result_mesh(b, scr, d + b->res_off[2], vraw, d + b->res_off[4], xpart, d + b->res_off[3], stream, nullptr, store ? &ho : nullptr, &handed_over));
+    }
+    if (!handed_over) BF_TRY(hand_over(stream, r, n_floats, big));
     HIP_TRY(hipEventRecord(r.ev_copied, stream));
     return BF_OK;
 }
@@ -502,8 +565,12 @@ static int lane_launch(bf_batch *b, int j) {
     MeshPass p;
     p.scr = &l.scratch; p.n = G * b->F; p.per = b->F; p.state = d + h.off[2]; p.stream = l.stream;
     p.vraw = l.vraw.p; p.vout = d + h.off[4]; p.xpart = l.xpart.p; p.joints = d + h.off[3];
-    BF_TRY(bf_launch_mesh(m, p));
-    BF_TRY(hand_over(l.stream, r, h.total, h.total * sizeof(float) >= kLaneCopyBytes));
+    // the group's hand-over: by the tail's own kernels where they store into the mirror (calls below 16 frames), else behind them
+    const BfHandOver ho = arena_mirror(b, r, h.off);
+    if (tail_stores(b, h.total * sizeof(float), G * b->F)) p.mirror = &ho;
+    MeshPassDone did;
+    BF_TRY(bf_launch_mesh(m, p, did));
+    if (!did.handed_over) BF_TRY(hand_over(l.stream, r, h.total, h.total * sizeof(float) >= kLaneCopyBytes));
     HIP_TRY(hipEventRecord(r.ev_copied, l.stream));
     l.held = h;
     r.seq = h.seq0 + G - 1; r.fetched = r.has_v = true;         // (the arena's newest fit: what a trade in bf_lanes_drain hands on)
@@ -517,19 +584,47 @@ int bf_lanes_drain(bf_batch *b) {
     b->in_pinned = false;                 // (what follows a drain may write the device slot alone: a setter, a device-side producer)
     for (int j = 0; j < b->n_lanes; ++j) BF_TRY(lane_launch(b, j));       // (the open group, if calls have joined one)
     b->lanes_on = false;
-    for (int j = 0; j < b->n_lanes; ++j)
-        if (b->lanes[j].busy) { HIP_TRY(hipStreamSynchronize(b->lanes[j].stream)); b->lanes[j].busy = false; }
     const int j = b->lane_last;
     b->lane_last = -1;
-    if (j < 0) return BF_OK;              // (inputs staged, no lane fit since the lanes took over)
     // The last lane fit lands where the tail-aside path leaves a fit - in the result arena the previous fit did not use, with its Adam
-    // moments as the batch's.  Nothing on the device uses either side any more (the lane waited for the batch stream before its fit and
-    // has finished; a pipelined fetch of arena k is waited for here).
-    BfLane &l = b->lanes[j];
-    BF_TRY(bf_flush_tail(b));
+    // moments as the batch's.
     const int k = b->cur ^ 1;
     ResultArena &r = b->arena[k];
-    if (r.copy_pending) { HIP_TRY(hipEventSynchronize(r.ev_copied)); r.copy_pending = false; }
+    const bool by_kernel = j >= 0 && b->lane_w > 1 && b->lanes[j].held.G > 0;
+    if (by_kernel) {
+        // A group's arena is laid out for G calls: the last slot's five slices and its two Adam-moment rows are copied, device to device, by
+        // ONE launch on the lane's own stream - behind that lane's fit, tail and hand-over, so it ends with the lane instead of starting a
+        // chain of copy commands after every lane has been waited for (a bracket ends in exactly one drain: this is on its path).
+        // Nothing on the device still uses arena k or the batch's moments when this launch runs:
+        //  - the batch stream: lane j has fitted since the lanes took over, so its stream has waited for ev_engage (lane_begin), which
+        //    lanes_engage recorded behind everything on the batch stream; and while the lanes are on nothing is issued there - every entry
+        //    point but a lane fit or a staging comes through this drain first, and a staging with W > 1 issues no GPU work;
+        //  - the second stream: a deferred tail is enqueued and a pipelined fetch of arena k waited for just below, on the host;
+        //  - the other lanes use their own arenas and moments, and of the batch's only inputs, cameras and the Adam table - not written here.
+        // And nothing reads them before this launch has finished: the lane's stream is waited for below, before this function returns.
+        BfLane &l = b->lanes[j];
+        BF_TRY(bf_flush_tail(b));
+        if (r.copy_pending) { HIP_TRY(hipEventSynchronize(r.ev_copied)); r.copy_pending = false; }
+        const BfLane::Held &h = l.held;
+        const size_t s = h.G - 1, n_adam = (size_t)b->F * b->m->np;
+        BfSeg7 seg;
+        for (int i = 0; i < 5; ++i) {
+            seg.src[i] = l.arena.dev.p + h.off[i] + s * b->res_cnt[i]; seg.dst[i] = r.dev.p + b->res_off[i]; seg.n[i] = (unsigned)b->res_cnt[i];
+        }
+        seg.src[5] = l.adam_m.p + s * n_adam; seg.dst[5] = b->adam_m.p; seg.n[5] = (unsigned)n_adam;
+        seg.src[6] = l.adam_v.p + s * n_adam; seg.dst[6] = b->adam_v.p; seg.n[6] = (unsigned)n_adam;
+        BF_TRY(publish7(l.stream, seg));
+    }
+    for (int q = 0; q < b->n_lanes; ++q)
+        if (b->lanes[q].busy) { HIP_TRY(hipStreamSynchronize(b->lanes[q].stream)); b->lanes[q].busy = false; }
+    if (j < 0) return BF_OK;              // (inputs staged, no lane fit since the lanes took over)
+    BfLane &l = b->lanes[j];
+    if (!by_kernel) {
+        // (W = 1, or no group to hand back.)  Nothing on the device uses either side any more (the lane waited for the batch stream before its
+        // fit and has finished; a pipelined fetch of arena k is waited for here).
+        BF_TRY(bf_flush_tail(b));
+        if (r.copy_pending) { HIP_TRY(hipEventSynchronize(r.ev_copied)); r.copy_pending = false; }
+    }
     if (!l.held.G) {                      // (its launch failed: no result anywhere)
         b->fetched = b->have_result = false;
         return fail(BF_ERR_HIP, "fit lanes: the last lane fit was not launched");
@@ -544,17 +639,12 @@ int bf_lanes_drain(bf_batch *b) {
         if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
         for (auto &g : b->graph_pipe) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     } else {
-        // a group's arena is laid out for G calls: the last slot's slices are copied, device to device on the batch stream and mirror
-        // to mirror on the host - once per drain, off the step's path.  The group stays readable in the lane (bf_batch_get_previous).
+        // ... and mirror to mirror on the host, now that the lane's hand-over has been waited for.  The group stays readable in the lane
+        // (bf_batch_get_previous).
         const BfLane::Held &h = l.held;
-        const size_t s = h.G - 1, n_adam = (size_t)b->F * b->m->np;
-        for (int i = 0; i < 5; ++i) {
-            const size_t from = h.off[i] + s * b->res_cnt[i];
-            HIP_TRY(hipMemcpyAsync(r.dev.p + b->res_off[i], l.arena.dev.p + from, b->res_cnt[i] * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
-            std::memcpy(r.host + b->res_off[i], l.arena.host + from, b->res_cnt[i] * sizeof(float));
-        }
-        HIP_TRY(hipMemcpyAsync(b->adam_m.p, l.adam_m.p + s * n_adam, n_adam * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
-        HIP_TRY(hipMemcpyAsync(b->adam_v.p, l.adam_v.p + s * n_adam, n_adam * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
+        const size_t s = h.G - 1;
+        for (int i = 0; i < 5; ++i)
+            std::memcpy(r.host + b->res_off[i], l.arena.host + h.off[i] + s * b->res_cnt[i], b->res_cnt[i] * sizeof(float));
         r.seq = h.seq0 + (long long)s; r.fetched = r.has_v = true;
     }
     bf_use_arena(b, k);
@@ -612,6 +702,8 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
         b->in_off[0] = 0; b->in_off[1] = up(n_kp); b->in_off[2] = b->in_off[1] + up(F * np);
         b->in_total = b->in_off[2] + up(F);
         if (const char *e = getenv("BF_STAGE_MODE")) b->stage_zerocopy = !strcmp(e, "zerocopy");
+        if (const char *e = getenv("BF_TAIL_HANDOVER"))          // (copy: the sequence before the kernels stored into the mirror)
+            b->tail_handover = !strcmp(e, "copy") ? bf_batch::TailHandOver::COPY : !strcmp(e, "store") ? bf_batch::TailHandOver::STORE : bf_batch::TailHandOver::BY_SIZE;
         ok = ok && b->in[0].create(b->in_total) == hipSuccess && b->in[1].create(b->in_total) == hipSuccess;
         if (ok) bf_use_inputs(b, 0, false);
     }

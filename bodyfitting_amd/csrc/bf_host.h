@@ -482,6 +482,10 @@ struct bf_batch {
                                         // own copies them on the host.  Cleared by every drain - what follows may write the device slot alone
     DevBuf<float> proj_rep;             // (W > 1) the projection table W times over: FrameIO::proj of a group launch
     bool proj_rep_stale = true;         // ... has yet to be copied from `proj` (new cameras)
+    enum class TailHandOver { BY_SIZE, STORE, COPY };
+    TailHandOver tail_handover = TailHandOver::BY_SIZE;         // BF_TAIL_HANDOVER (store | copy; unset: by size), read once per batch: whether a tail's
+                                        // kernels store into the pinned mirror themselves (MeshPass::mirror) - store: wherever they can; copy: never, the
+                                        // hand-over is a launch or a copy command behind them; by size: where that measured faster (tail_stores, api.hip)
     int lane_launches = 0, lane_calls = 0, lane_max_g = 0;      // bf_batch_lane_stats
     bool lane_called = false;           // a LANE-route call has been issued on this batch,
     std::chrono::steady_clock::time_point lane_t_call{};        // ... the last one then: the feeder is fast while calls follow within H (fit_lane)
@@ -531,8 +535,11 @@ struct MeshPass {
     int door_target = 0;
     hipEvent_t after_mesh = nullptr;    // recorded between the mesh and the joints pass
     hipEvent_t mesh_done = nullptr;     // completes with the mesh dispatch itself where the kernel can carry it: `mesh_done_set` says so
+    const BfHandOver *mirror = nullptr; // the pinned mirror of the result arena the pass fills (vout, joints: its slices): the mesh kernel stores its
+                                        // vertices there too and the joints kernel the arena's small slices - only the kernels below 16 frames per call do,
+                                        // and never with a doorbell, a sub-model table or vposed; `handed_over` says so, the caller copies otherwise
 };
-struct MeshPassDone { bool zeroed = false, projected = false, mesh_done_set = false; };      // (cleared by bf_launch_mesh)
+struct MeshPassDone { bool zeroed = false, projected = false, mesh_done_set = false, handed_over = false; };      // (cleared by bf_launch_mesh)
 int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &done);
 inline int bf_launch_mesh(bf_model *m, const MeshPass &p) { MeshPassDone unasked; return bf_launch_mesh(m, p, unasked); }
 int bf_fit_with_scans(bf_batch *b, int n_iters, const bf_hyper &h, const HyperDev &hd, FrameIO io);

@@ -247,6 +247,15 @@ struct MaskProj {
     float *uvi, *duvb;        // bf_mask_project_kernel's outputs
 };
 
+// The pinned mirror of the result arena a forward pass fills, for a tail that hands its results over itself (MeshPass::mirror): the mesh
+// kernel stores each vertex to `vout` as well, and bf_joints_kernel stores its joints to `joints` and copies its frame's rows of the arena's
+// params / terms / state slices.  Every array is frame-major like its device twin; the mirror's addresses are the host's (hipHostMalloc).
+struct BfHandOver {
+    const float *d_params = nullptr, *d_terms = nullptr;      // device rows [n][np], [n][nt] (the state rows are the pass's own `state`)
+    float *params = nullptr, *terms = nullptr, *state = nullptr, *joints = nullptr, *vout = nullptr;
+    int np = 0, nt = 0;
+};
+
 
 // Doorbells between the dense kernels of an iteration (batch stream) and the persistent fit launch (second stream) - the fit
 // kernel stays resident for all dense iterations of a call instead of being launched once per iteration (a launch starts with

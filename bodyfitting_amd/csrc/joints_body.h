@@ -83,3 +83,22 @@ __device__ __forceinline__ void bf_joints_body(const MeshTab &M, const float *__
         for (int i = tid; i < M.n_joint_map * 3; i += NT)
             joints[(size_t)frame * M.n_joint_map * 3 + i] = s_all[M.joint_map[i / 3] * 3 + i % 3];
 }
+
+// The hand-over of a tail's small slices, run by bf_joints_kernel's workgroup behind the body above: the frame's mapped joints - still in
+// the body's s_all, which nothing has written since its last barrier - go to the mirror as they went to the arena, and the frame's rows
+// of the arena's params, terms and state slices are copied there.  Those rows were written by the fit launch ahead of this kernel in
+// stream order (the body has read the state row); plain 4-byte stores to pinned host memory, posted, visible to the host once the stream's
+// next event has completed - what bf_publish_kernel does to the same buffer.
+template <int NT>
+__device__ __forceinline__ void bf_joints_hand_over(const MeshTab &M, const float *__restrict__ state, const BfHandOver &ho, const int frame,
+                                                    const float *lds) {
+    const float *s_all = lds + 32 * 3;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < M.n_joint_map * 3; i += NT)
+        ho.joints[(size_t)frame * M.n_joint_map * 3 + i] = s_all[M.joint_map[i / 3] * 3 + i % 3];
+    __syncthreads();
+    const size_t stride = bf_state_stride(M.nj, M.npf, M.nb);
+    for (int i = tid; i < ho.np; i += NT) ho.params[(size_t)frame * ho.np + i] = ho.d_params[(size_t)frame * ho.np + i];
+    for (int i = tid; i < ho.nt; i += NT) ho.terms[(size_t)frame * ho.nt + i] = ho.d_terms[(size_t)frame * ho.nt + i];
+    for (size_t i = tid; i < stride; i += NT) ho.state[(size_t)frame * stride + i] = state[(size_t)frame * stride + i];
+}

@@ -60,7 +60,7 @@ bf_pose_state_kernel(FitTab T, const float *__restrict__ betas, const float *__r
 template <bool SPAN>
 __device__ __forceinline__ void bf_mesh_body(const MeshTab &M, const float *__restrict__ state, float *__restrict__ vraw, float *__restrict__ vout,
                float *__restrict__ xpart, float *__restrict__ vposed, const float *__restrict__ pose_off, int *door, int door_target,
-               unsigned long long *span) {
+               unsigned long long *span, float *__restrict__ vmirror) {
     const unsigned long long t_begin = SPAN ? (unsigned long long)wall_clock64() : 0ull;
     constexpr int COLS = BF_MESH_TILE * 3;
     extern __shared__ __align__(16) float sm[];
@@ -182,7 +182,9 @@ __device__ __forceinline__ void bf_mesh_body(const MeshTab &M, const float *__re
             r = t0 * s_vp[vl * 3] + t1 * s_vp[vl * 3 + 1] + t2 * s_vp[vl * 3 + 2] + tt;
             size_t o = (size_t)frame * ncols + gcol;
             if (vraw) vraw[o] = r;
-            if (vout) vout[o] = (r + s_beta[nb + k]) * s_beta[nb + 3] * s_beta[nb + 4];
+            const float vo = (r + s_beta[nb + k]) * s_beta[nb + 3] * s_beta[nb + 4];
+            if (vout) vout[o] = vo;
+            if (vmirror) vmirror[o] = vo;            // (the pass hands its vertices over itself: the same value to the arena's pinned mirror, MeshPass::mirror)
             if (vposed) vposed[o] = s_vp[col];       // kept for the dense reverse pass
         }
         s_red[col] = r;                          // (own column of the reduce buffer: no hazard)
@@ -205,13 +207,14 @@ __device__ __forceinline__ void bf_mesh_body(const MeshTab &M, const float *__re
 }
 extern "C" __global__ void __launch_bounds__(BF_MESH_TILE * 3 * BF_MESH_RG)
 bf_mesh_kernel(MeshTab M, const float *__restrict__ state, float *__restrict__ vraw, float *__restrict__ vout,
-               float *__restrict__ xpart, float *__restrict__ vposed, const float *__restrict__ pose_off, int *door, int door_target) {
-    bf_mesh_body<false>(M, state, vraw, vout, xpart, vposed, pose_off, door, door_target, nullptr);
+               float *__restrict__ xpart, float *__restrict__ vposed, const float *__restrict__ pose_off, int *door, int door_target,
+               float *__restrict__ vmirror) {
+    bf_mesh_body<false>(M, state, vraw, vout, xpart, vposed, pose_off, door, door_target, nullptr, vmirror);
 }
 extern "C" __global__ void __launch_bounds__(BF_MESH_TILE * 3 * BF_MESH_RG)
 bf_mesh_span_kernel(MeshTab M, const float *__restrict__ state, float *__restrict__ vraw, float *__restrict__ vout,
                     float *__restrict__ xpart, unsigned long long *span) {
-    bf_mesh_body<true>(M, state, vraw, vout, xpart, nullptr, nullptr, nullptr, 0, span);
+    bf_mesh_body<true>(M, state, vraw, vout, xpart, nullptr, nullptr, nullptr, 0, span, nullptr);
 }
 
 // Small batches (2..15 frames) and models whose pose feature is longer than the 8 x BF_MESH_PF rows the kernel above
@@ -240,7 +243,8 @@ bf_mesh_span_kernel(MeshTab M, const float *__restrict__ state, float *__restric
 template <int FPW, int PNB = 10>
 __global__ void __launch_bounds__(BF_MESH_TILE * 3 * BF_MESH_RG, FPW == 8 ? BF_MM_OCC8 : 1)
 bf_mesh_multi_kernel(MeshTab M, const float *__restrict__ state, int n_frames, float *__restrict__ vraw, float *__restrict__ vout,
-                     float *__restrict__ xpart, float *__restrict__ vposed, float *__restrict__ dvzero, MaskProj mp, int *door, int door_target) {
+                     float *__restrict__ xpart, float *__restrict__ vposed, float *__restrict__ dvzero, MaskProj mp, int *door, int door_target,
+                     float *__restrict__ vmirror) {
     static_assert(FPW == 1 || FPW == 2 || FPW == 4 || FPW == 8, "frames per workgroup");
     constexpr int COLS = BF_MESH_TILE * 3;
     extern __shared__ __align__(16) float sm[];
@@ -426,7 +430,9 @@ bf_mesh_multi_kernel(MeshTab M, const float *__restrict__ state, int n_frames, f
         const size_t o = (size_t)(fbase + f) * ncols + gcol;
         const float *sb = s_beta + f * 32 + nb;
         if (vraw) vraw[o] = r;
-        if (vout) vout[o] = (r + sb[k]) * sb[3] * sb[4];
+        const float vo = (r + sb[k]) * sb[3] * sb[4];
+        if (vout) vout[o] = vo;
+        if (vmirror) vmirror[o] = vo;                         // (the arena's pinned mirror, as in bf_mesh_kernel: 384 contiguous bytes per frame and tile)
         if (vposed) vposed[o] = vp[k];
         if (dvzero) dvzero[o] = 0.f;                          // dL/dvertices starts the iteration at zero: saves a memset launch
     }
@@ -475,7 +481,8 @@ bf_mesh_multi_kernel(MeshTab M, const float *__restrict__ state, int n_frames, f
 }
 
 extern "C" int bf_mesh_multi_launch(const MeshTab *M, const float *state, int n, float *vraw, float *vout, float *xpart, float *vposed,
-                                    float *dvzero, hipStream_t stream, const MaskProj *mproj, int *door, int door_target, hipEvent_t done) {
+                                    float *dvzero, hipStream_t stream, const MaskProj *mproj, int *door, int door_target, hipEvent_t done,
+                                    float *vmirror) {
     // (`done`: an event that completes with this dispatch - its own completion signal instead of a marker packet behind it)
     MaskProj mp;
     if (mproj) mp = *mproj; else { std::memset(&mp, 0, sizeof mp); }
@@ -493,19 +500,19 @@ extern "C" int bf_mesh_multi_launch(const MeshTab *M, const float *state, int n,
     }
     switch (fpw) {
     case 1: if (M->nb > 10) {          // (11 or 12 shape directions: the `pre` path's rows sized for 12)
-                if (done) hipExtLaunchKernelGGL((bf_mesh_multi_kernel<1, 12>), grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
-                else hipLaunchKernelGGL((bf_mesh_multi_kernel<1, 12>), grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
-             } else if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<1>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
-             else hipLaunchKernelGGL(bf_mesh_multi_kernel<1>, grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
+                if (done) hipExtLaunchKernelGGL((bf_mesh_multi_kernel<1, 12>), grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target, vmirror);
+                else hipLaunchKernelGGL((bf_mesh_multi_kernel<1, 12>), grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target, vmirror);
+             } else if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<1>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target, vmirror);
+             else hipLaunchKernelGGL(bf_mesh_multi_kernel<1>, grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target, vmirror);
              break;
-    case 2: if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<2>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
-             else hipLaunchKernelGGL(bf_mesh_multi_kernel<2>, grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
+    case 2: if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<2>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target, vmirror);
+             else hipLaunchKernelGGL(bf_mesh_multi_kernel<2>, grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target, vmirror);
              break;
-    case 4: if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<4>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
-             else hipLaunchKernelGGL(bf_mesh_multi_kernel<4>, grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
+    case 4: if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<4>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target, vmirror);
+             else hipLaunchKernelGGL(bf_mesh_multi_kernel<4>, grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target, vmirror);
              break;
-    default: if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<8>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
-             else hipLaunchKernelGGL(bf_mesh_multi_kernel<8>, grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target);
+    default: if (done) hipExtLaunchKernelGGL(bf_mesh_multi_kernel<8>, grid, block, smem, stream, nullptr, done, 0, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target, vmirror);
+             else hipLaunchKernelGGL(bf_mesh_multi_kernel<8>, grid, block, smem, stream, *M, state, n, vraw, vout, xpart, vposed, dvzero, mp, door, door_target, vmirror);
              break;
     }
     return (int)hipGetLastError();
@@ -528,9 +535,10 @@ extern "C" size_t bf_mesh_smem_bytes(int nj, int npf, int nb) {
 extern "C" __global__ void __launch_bounds__(256)
 bf_joints_kernel(MeshTab M, const float *__restrict__ state, const float *__restrict__ vraw,
                  const float *__restrict__ xpart, float *__restrict__ joints, float *__restrict__ joints_ori,
-                 float *__restrict__ jraw, int *__restrict__ lmk_vid, float *__restrict__ lmk_w) {
+                 float *__restrict__ jraw, int *__restrict__ lmk_vid, float *__restrict__ lmk_w, BfHandOver ho) {
     __shared__ float lds[BF_JOINTS_LDS];
     bf_joints_body<256>(M, state, vraw, xpart, joints, joints_ori, jraw, lmk_vid, lmk_w, blockIdx.x, lds);
+    if (ho.joints) bf_joints_hand_over<256>(M, state, ho, blockIdx.x, lds);        // (the tail hands its small slices over itself)
 }
 
 

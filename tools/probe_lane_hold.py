@@ -5,7 +5,9 @@ shapes (bf_batch_lane_stats / bf_batch_lane_feed_stats) and a host-clock timelin
 
   python tools/probe_lane_hold.py shapes [--brackets 11] [--steps 100]   group shapes, per-bracket wall, timeline of the last bracket
   python tools/probe_lane_hold.py latency [--trips 50]                   sequential stage; fit; get_result round trips
-  python tools/probe_lane_hold.py trace-summary DIR                      durations by kernel and grid from a rocprofv3 --kernel-trace run
+  python tools/probe_lane_hold.py drain [--trips 50]                     bf_batch_sync alone: entered with every lane idle and one result held in a lane
+  python tools/probe_lane_hold.py trace-summary DIR [--handover store]   durations by kernel and grid from a rocprofv3 --kernel-trace run; lane cycle
+                                                                         and tail by G (store: the tail ends with the joints pass, which hands over)
 
 The BF_* settings are the process's environment (the library reads them once).  One JSON line per mode on stdout."""
 import argparse
@@ -76,6 +78,8 @@ def shapes(a):
            "bracket_wall_us": {"median": statistics.median(plain), "min": min(plain), "max": max(plain), "all": [round(x) for x in plain]},
            "frames_per_s_median": a.steps / statistics.median(plain) * 1e6,
            "feed_us_median": statistics.median(r["feed_us"] for r in per_bracket),
+           "sync_wait_us": {"median": statistics.median(r["wall_us"] - r["feed_us"] for r in per_bracket),
+                            "min": min(r["wall_us"] - r["feed_us"] for r in per_bracket), "max": max(r["wall_us"] - r["feed_us"] for r in per_bracket)},
            "launches_per_bracket": [r["launches"] for r in per_bracket],
            "lane_stats": batch.lane_stats(), "feed_stats": batch.lane_feed_stats(),
            "traced_bracket": {"groups": groups, "fit_call_us_first8": [round(x, 1) for x in fit_us[:8]],
@@ -95,6 +99,25 @@ def latency(a):
         trips.append((time.perf_counter_ns() - t0) / 1e3)
     print(json.dumps({"mode": "latency", "env": {k: v for k, v in os.environ.items() if k.startswith("BF_FIT_")}, "trips": a.trips,
                       "round_trip_us": {"median": statistics.median(trips), "min": min(trips), "max": max(trips)}, "lane_stats": batch.lane_stats()}))
+
+
+def drain(a):
+    """the drain alone: a call that goes out at once (a lone call after a pause finds its lane idle), a pause in which its lane finishes,
+    then bf_batch_sync on the host clock - nothing to wait for but what the drain itself issues to hand the result back to the batch"""
+    batch, feed, flags = setup(a.views)
+    for _ in range(20):
+        batch.stage_inputs(*feed.next()); batch.fit(a.iters, flags=flags); batch.sync()
+    us = []
+    for _ in range(a.trips):
+        batch.stage_inputs(*feed.next()); batch.fit(a.iters, flags=flags)
+        time.sleep(0.003)
+        t0 = time.perf_counter_ns()
+        batch.sync()
+        us.append((time.perf_counter_ns() - t0) / 1e3)
+    st = batch.lane_stats()
+    assert st["launches"] == st["calls"] == 20 + a.trips, st           # (every call went out alone, before its pause)
+    print(json.dumps({"mode": "drain", "env": {k: v for k, v in os.environ.items() if k.startswith("BF_")}, "trips": a.trips,
+                      "sync_us": {"median": statistics.median(us), "min": min(us), "max": max(us)}, "lane_stats": st}))
 
 
 def trace_summary(a):
@@ -120,7 +143,7 @@ def trace_summary(a):
                 copies.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
     copies.sort()
     qkey = "Queue_Id" if rows and "Queue_Id" in rows[0] else None
-    cycles = collections.defaultdict(list)
+    cycles, tails = collections.defaultdict(list), collections.defaultdict(list)
     if qkey:
         perq = collections.defaultdict(list)
         for r in rows:
@@ -135,19 +158,25 @@ def trace_summary(a):
                 if not nxt:
                     continue
                 j_end = int(nxt[0]["End_Timestamp"])
-                end = next((e for s, e in copies if s >= j_end), None) if G * 82680 * 4 >= 512 * 1024 else None
+                end = next((e for s, e in copies if s >= j_end), None) if G * 82680 * 4 >= 512 * 1024 and a.handover == "copy" else None
+                if end is None and a.handover == "store":
+                    end = j_end
                 if end is None:
                     pub = [x for x in rs[i + 1:i + 5] if "publish_kernel" in x["Kernel_Name"] and int(x["Start_Timestamp"]) >= j_end]
                     end = int(pub[0]["End_Timestamp"]) if pub else j_end
                 cycles[G].append((end - int(r["Start_Timestamp"])) / 1e3)
+                tails[G].append((end - int(r["End_Timestamp"])) / 1e3)
     print(json.dumps({"mode": "trace-summary", "file": f[0], "kernels": out,
                       "lane_cycle_us_by_G": {G: {"n": len(d), "median": round(statistics.median(d), 1), "min": round(min(d), 1), "max": round(max(d), 1)}
-                                             for G, d in sorted(cycles.items())}}))
+                                             for G, d in sorted(cycles.items())},
+                      "tail_us_by_G": {G: {"n": len(d), "median": round(statistics.median(d), 1), "min": round(min(d), 1), "max": round(max(d), 1)}
+                                       for G, d in sorted(tails.items())},
+                      "d2h_copies": len(copies)}))
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("shapes", "latency", "trace-summary"))
+    ap.add_argument("mode", choices=("shapes", "latency", "drain", "trace-summary"))
     ap.add_argument("dir", nargs="?")
     ap.add_argument("--brackets", type=int, default=11)
     ap.add_argument("--steps", type=int, default=100)
@@ -155,5 +184,6 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--views", type=int, default=48)
     ap.add_argument("--trips", type=int, default=50)
+    ap.add_argument("--handover", choices=("copy", "store"), default="copy")
     a = ap.parse_args()
-    {"shapes": shapes, "latency": latency, "trace-summary": trace_summary}[a.mode](a)
+    {"shapes": shapes, "latency": latency, "drain": drain, "trace-summary": trace_summary}[a.mode](a)
