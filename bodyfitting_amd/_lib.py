@@ -248,6 +248,7 @@ SIGNATURES = {
     "bf_overlay_stamp": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _FP, _DP, C.POINTER(C.c_uint8)]),
     "bf_batch_debug_dump": (C.c_int, [_VP, _FP, C.c_int]),
     "bf_batch_debug_disp_moment": (C.c_int, [_VP, _FP]),
+    "bf_batch_debug_disp_moment2": (C.c_int, [_VP, _FP]),
     "bf_batch_debug_vertices": (C.c_int, [_VP, _FP]),
     "bf_batch_lane_stats": (C.c_int, [_VP, _IP]),
     "bf_batch_lane_feed_stats": (C.c_int, [_VP, C.POINTER(C.c_int64)]),

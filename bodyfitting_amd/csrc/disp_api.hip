@@ -87,4 +87,13 @@ int bf_batch_debug_disp_moment(bf_batch *b, float *m_out) {
     return BF_OK;
 }
 
+/* test hook: second Adam moment of the displacement */
+int bf_batch_debug_disp_moment2(bf_batch *b, float *v_out) {
+    if (!b || !v_out || !b->have_disp) return fail(BF_ERR_INVALID, "bf_batch_debug_disp_moment2: bad argument");
+    HIP_TRY(hipSetDevice(b->m->device));
+    BF_TRY(bf_sync_all(b));
+    HIP_TRY(hipMemcpy(v_out, b->disp_v.p, b->disp_v.n * sizeof(float), hipMemcpyDeviceToHost));
+    return BF_OK;
+}
+
 }  // extern "C"

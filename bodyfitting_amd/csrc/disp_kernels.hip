@@ -157,7 +157,7 @@ bf_disp_adam_kernel(const int *__restrict__ adj_start, const int *__restrict__ a
     if (v >= nv) return;
     float tot = 0.f;
     for (int b = 0; b < n_partial; ++b) tot += pc_partial[(size_t)fr * n_partial + b];     // fixed order
-    const float inorm = 1.0f / sqrtf(tot);
+    const float inorm = tot > 0.f ? 1.0f / sqrtf(tot) : 0.f;                              // (torch's rule for the norm at zero: a zero gradient)
     const size_t o = ((size_t)fr * nv + v) * 3;
     float g[3] = {(P[o] - C[o]) * inorm, (P[o + 1] - C[o + 1]) * inorm, (P[o + 2] - C[o + 2]) * inorm};
     const int i0 = adj_start[v], i1 = adj_start[v + 1];

@@ -533,7 +533,7 @@ bf_pc_grad_kernel(const float *__restrict__ P, const float *__restrict__ C, int 
     }
     if (id >= n) return;
     const size_t o = ((size_t)f * n + id) * 3;
-    const float k = w / norm;
+    const float k = norm > 0.f ? w / norm : 0.f;                      // (torch's rule for the norm at zero: a zero gradient)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float g = k * (P[o + c] - C[o + c]);

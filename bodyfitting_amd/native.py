@@ -948,6 +948,12 @@ class FrameBatch:
         _lib.check(self._lib.bf_batch_debug_disp_moment(self._h, _lib.fptr(m)), "bf_batch_debug_disp_moment")
         return m
 
+    def disp_moment2(self):
+        """second Adam moment [F,NV,3] of the SMPL+D displacement (bf_batch_debug_disp_moment2)"""
+        v = np.empty((self.F, self.model.n_verts, 3), np.float32)
+        _lib.check(self._lib.bf_batch_debug_disp_moment2(self._h, _lib.fptr(v)), "bf_batch_debug_disp_moment2")
+        return v
+
     def debug_dump(self, n):
         out = np.zeros(n, np.float32)
         _lib.check(self._lib.bf_batch_debug_dump(self._h, _lib.fptr(out), int(n)), "bf_batch_debug_dump")

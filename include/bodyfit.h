@@ -829,6 +829,8 @@ int bf_batch_dense_resident(const bf_batch *b);
 int bf_batch_debug_dump(bf_batch *b, float *dst, int n);
 /* first Adam moment of the SMPL+D displacement (after one step = 0.1 x the gradient) */
 int bf_batch_debug_disp_moment(bf_batch *b, float *m_out);
+/* second Adam moment of the SMPL+D displacement, [F,NV,3] like the first */
+int bf_batch_debug_disp_moment2(bf_batch *b, float *v_out);
 /* vertices[F,NV,3]: the body vertices the last full-model mesh pass of the batch left on the device (after bf_dense_iter_grad
  * without BF_DENSE_GRAD_SUBMODEL: the ones its losses were evaluated at) */
 int bf_batch_debug_vertices(bf_batch *b, float *vertices);

@@ -7,7 +7,7 @@ that every one is well posed, so nothing is skipped or filtered here).
      at batch sizes on both sides of every frames-per-workgroup instance of bf_mesh_bwd_multi_kernel; SMPL, kid, 8-wide and dense
      skinning rows, SMPL-X
   b. the same on the sub-models bf_fit runs its mesh passes on (one frame: the split tiles)
-  c. the scan term, two frames with scans of different height
+  c. the scan term, two frames with scans of different height; and at zero distance, every vertex on its closest point
   d. the silhouette term under both folds, with and without the sub-model, and together with a scan
   e. the call leaves the batch as it found it, and refuses what it cannot evaluate
   f. the fused SMPL+D stage's gradient away from zero displacement, read out of its first Adam moment
@@ -261,6 +261,68 @@ def test_scan_term_matches_fp64_autograd(devs, name, F):
     assert not failures, "\n  ".join(failures)
 
 
+def test_scan_term_at_zero_distance(devs):
+    """Every vertex exactly on its closest point: scans built from the batch's own float32 vertices at the parameter point.  The
+    Frobenius norm is zero there and torch's rule for its gradient is zero (as bf_ml_pc_grad_kernel keeps it): terms[5] == 0, and the
+    gradient is finite and the oracle's - DC.scan_evaluate's objective with closest = vertices - inside the band of every block.
+    With a scan attached the constant scale is the scan's, height / 1.7, and the vertices carry it as a factor; so that attaching the
+    scans leaves the vertices where they were, each scan gets two more vertices, in no face, that make its height h with
+    float32(h / 1.7f) the constant scale c0 the vertices were formed with (the point's scale is 0.85 of the case's: the body fits inside)"""
+    name = "smpl690"
+    dev = devs(name)
+    model = DC.model(name)
+    items = DC.SCAN_FRAMES
+    probs = [DC.scan_problem(name, f, sc)[0] for f, sc in items]
+    params = [DC.scan_params(name, f, sc) for f, sc in items]
+    for p in params:
+        p["scale"] = p["scale"] * 0.85
+    h = np.float32(probs[0]["constant_scale"]) * np.float32(1.7)
+    c0 = h / np.float32(1.7)
+    assert h.dtype == c0.dtype == np.float32
+    b = _batch(dev, probs, params)
+    hp = _hyper(probs[0], constant_scale=float(c0))
+    scans, svs = [], []
+    try:
+        b.dense_iter_grad(hp, dverts_extra=np.zeros((len(items), dev.n_verts, 3), np.float32))       # (a full-model mesh pass at the point)
+        verts = b.debug_vertices()
+        for i in range(len(items)):
+            lo, hi = verts[i][:, 1].min(), verts[i][:, 1].max()
+            assert hi - lo < h
+            y0 = np.float32(np.floor((lo - (h - (hi - lo)) / 2) * 1024) / 1024)                        # (a multiple of 2^-10: y0 + h is exact)
+            y1 = np.float32(y0 + h)
+            assert y0 <= lo and y1 >= hi and np.float32(y1 - y0) == h
+            x, z = verts[i][:, 0].mean(), verts[i][:, 2].mean()
+            svs.append(np.concatenate([verts[i], np.array([[x, y0, z], [x, y1, z]], np.float32)]))
+            assert np.float32(DC.scan_cscale(svs[i])) == c0
+            scans.append(N.Scan(svs[i], np.asarray(model["faces"]).reshape(-1, 3)))
+        for i, s in enumerate(scans):                        # the precondition, on the device
+            pts = s.nearest_points(verts[i])[0]
+            np.testing.assert_array_equal(pts.view(np.uint32), verts[i].view(np.uint32), err_msg=f"frame {i}: a vertex is not its own closest point")
+        b.set_scans(scans)
+        terms, grads = b.dense_iter_grad(hp, late=True)
+        np.testing.assert_array_equal(b.debug_vertices().view(np.uint32), verts.view(np.uint32), err_msg="attaching the scans moved the vertices")
+    finally:
+        b.close()
+        for s in scans:
+            s.close()
+    assert np.isfinite(terms).all() and np.isfinite(grads).all(), f"{int((~np.isfinite(grads)).sum())} of {grads.size} gradient entries are not finite"
+    assert not terms[:, 5].any() and not terms[:, 4].any()
+    failures = []
+    for i, (f, sc) in enumerate(items):
+        # (closest = vertices on the oracle's side too: its own body vertices in each precision, so that its norm is exactly zero as the
+        #  device's is; the constant scale and the height are those of the scan, the device's float32 vertices)
+        kw = dict(scan_height=DC.scan_height(svs[i]), constant_scale=DC.scan_cscale(svs[i]))
+        args = (model, DC.LC.gmm_bufs(), probs[i], params[i])
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)
+            r64 = O.dense_loss_and_grad(*args, closest=O.dense_loss_and_grad(*args, **kw)[2], **kw)
+            r32 = O.dense_loss_and_grad(*args, dtype=torch.float32, closest=O.dense_loss_and_grad(*args, dtype=torch.float32, **kw)[2], **kw)
+        assert r64[0]["scan_loss"] == 0.0 and r32[0]["scan_loss"] == 0.0
+        np.testing.assert_allclose(verts[i], r64[2], rtol=0, atol=5e-6 * max(1.0, np.abs(r64[2]).max()))
+        failures += _hold(f"c zero distance frame {i}", name, dev, terms[i], grads[i], r64, r32)
+    assert not failures, "\n  ".join(failures)
+
+
 # ---- d. silhouette term ----------------------------------------------------------------------------------------------------
 
 def _mask_batch(dev):
@@ -407,8 +469,7 @@ def test_displacement_gradient_after_three_steps(devs):
     base + the device's displacement after three steps, closest points and face ids from the reference's search at those float32
     vertices, on a two-frame batch whose scans differ in height (per-frame constant scale, block sums and face normals).
     Band: the block band of DESIGN.md 2.3, max(5e-6 M, 8 err32), plus the read-out's own rounding 19 * 2^-24 * max|m|."""
-    from oracle import mesh_oracle as MO
-    from oracle import nearest_ref as NR
+    import disp_stage_cases as D
     name = "smpl690"
     dev = devs(name)
     model = DC.model(name)
@@ -428,36 +489,14 @@ def test_displacement_gradient_after_three_steps(devs):
     assert np.abs(d3).max() > 0.01                                        # three steps of 5 cm: well away from zero
     w = float(np.float32(1.0) - np.float32(0.9))
     grad = m3.astype(np.float64) + (m4.astype(np.float64) - m3) / w
-    faces_t = torch.as_tensor(np.asarray(model["faces"]), dtype=torch.long)
+    faces = np.asarray(model["faces"]).reshape(-1, 3)
     failures = []
     for i, (f, sc) in enumerate(DC.SCAN_FRAMES):
         _, sv, sf = DC.scan_problem(name, f, sc)
-        P32 = base[i] + d3[i]                                             # (float32, as the stage forms it)
-        ids, closest = DC.closest_points(sv, sf, P32)
-        # A vertex whose closest point lies on a scan edge or corner is equally far from the faces around it, bit for bit in the
-        # reference's own arithmetic, and the reference's answer there hangs on the order of its cell lists (test_gpu_scan.py).  The
-        # normal term reads the face's normal, so among such tied faces the oracle takes the one the device's search returns - after
-        # checking that it IS a tie: the reference's rule gives both faces the same float32 distance.
-        tied = np.nonzero(ids_dev[i] != ids)[0]
-        if len(tied):
-            _, d_dev, _ = NR.rule(sv, sf, ids_dev[i][tied], P32[tied])
-            _, d_ref, _ = NR.rule(sv, sf, ids[tied], P32[tied])
-            assert (d_dev.view(np.uint32) == d_ref.view(np.uint32)).all(), "the device's search chose a face the reference ranks behind its own"
-            assert len(tied) < 0.1 * len(ids)
-            ids = np.where(ids_dev[i] != ids, ids_dev[i], ids)
-        tris = sv.astype(np.float64)[sf]
-        fnorm32 = np.cross(tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0]).astype(np.float32)
-        c = DC.scan_cscale(sv)
-        g = {}
-        for dt in (torch.float64, torch.float32):
-            disp = torch.tensor(d3[i], dtype=dt, requires_grad=True)
-            P = torch.tensor(base[i], dtype=dt) + disp
-            norms = MO.compute_normal_torch(P, faces_t)
-            fn = torch.tensor(fnorm32, dtype=dt)[torch.as_tensor(ids, dtype=torch.long)]
-            loss = MO.point_cloud_loss(P, torch.tensor(closest, dtype=dt)) + (
-                MO.normal_loss(fn, norms) + MO.normal_laplacian_smoothness(norms, faces_t)) * c * 0.1
-            loss.backward()
-            g[dt] = disp.grad.numpy().astype(np.float64)
+        # (the reference's search at the float32 base + d3, its ties with the device's search settled and capped, and the float64 and
+        #  float32 autograd of the objective: disp_stage_cases.reference / settle_ties, shared with test_gpu_disp_stage.py)
+        ref = D.reference(faces, sv, sf, base[i], d3[i], ids_dev[i])
+        g = {torch.float64: ref["g64"], torch.float32: ref["g32"]}
         band, M, err32 = DC.band(g[torch.float64], g[torch.float32])
         readout = 19 * 2.0 ** -24 * float(max(np.abs(m3[i]).max(), np.abs(m4[i]).max()))
         err = float(np.abs(grad[i] - g[torch.float64]).max())
