@@ -5,6 +5,8 @@ Restates, in numpy / torch:
   * insert_grid_surface (cell lists of the grid)    thirdparty/mesh_grid/mesh_grid_kernel.cu:110-157,178-236
   * MeshGridSearcher.inside_mesh (axis-ray parity)   thirdparty/mesh_grid/mesh_grid_kernel.cu:461-641
   * MeshGridSearcher.intersects_any (any-hit rays)   thirdparty/mesh_grid/mesh_grid_kernel.cu:742-1026,1029-1231
+    (and, of no reference code: winding_number - the float64 truth the inside rule is held to on closed meshes - and ray_grazing -
+    the rays on which a float32 walk over the grid may differ from the brute force)
   * the per-triangle closest-point rule             thirdparty/mesh_grid/mesh_grid_kernel.cu:12-109
     (KKT solve for the barycentric coefficients; if one is negative, fall back to the edge opposite
     the MOST NEGATIVE coefficient and clamp to its end points - which is not the exact closest point
@@ -105,10 +107,12 @@ def axis_ray_hits(q, axis, plus, tri):
     return all(want_negative == bool(ci < 0) for ci in c)
 
 
-def inside_mesh(verts, faces, queries, step, origin, num, tri_num, tri_idx):
+def inside_mesh(verts, faces, queries, step, origin, num, tri_num, tri_idx, memory=15):
     """search_inside_mesh_kernel (mesh_grid_kernel.cu:569-641): +1 when the axis ray towards the nearest grid wall crosses
-    an odd number of distinct triangles (distinct among the last 15 hits, the kernel's `visited[16]`), -1 otherwise and
-    for queries off the grid.  tri_num / tri_idx as insert_grid_surface returns them.  Pure-Python loops: small cases."""
+    an odd number of distinct triangles (distinct among the last `memory` = 15 hits, the kernel's `visited[16]`), -1 otherwise
+    and for queries off the grid.  memory=None remembers every hit: the count of distinct triangles, what the rule would be with
+    an unlimited memory (for cases that show where the two part).  tri_num / tri_idx as insert_grid_surface returns them.
+    Pure-Python loops: small cases."""
     f = np.float32
     v = np.asarray(verts, f)
     fa = np.asarray(faces, np.int64).reshape(-1, 3)
@@ -131,10 +135,96 @@ def inside_mesh(verts, faces, queries, step, origin, num, tri_num, tri_idx):
             for t in np.asarray(tri_idx[start[cell]:start[cell + 1]], np.int64) - 1:
                 if not axis_ray_hits(q, a, plus, v[fa[t]]) or t in seen:
                     continue
-                seen = (seen + [t])[-15:]
+                seen = seen + [t] if memory is None else (seen + [t])[-memory:]
                 hits += 1
             x[a] += 1 if plus else -1
         out[qi] = 1 if hits % 2 else -1
+    return out
+
+
+def inside_walks(queries, step, origin, num):
+    """The walk inside_mesh takes per query, without the triangles: (direction int[Q] in the kernel's order -x +x -y +y -z +z, or -1
+    off the grid; cells walked int[Q], the start cell included; the six distances to_end int[Q,6])."""
+    f = np.float32
+    num = np.asarray(num, np.int64)
+    xf = (np.asarray(queries, f).reshape(-1, 3) - np.asarray(origin, f)) / f(step)
+    on = np.all((xf >= 0) & (xf < num.astype(f)), 1)
+    x = np.where(on[:, None], xf, 0).astype(np.int64)
+    to_end = np.stack([x[:, 0], num[0] - 1 - x[:, 0], x[:, 1], num[1] - 1 - x[:, 1], x[:, 2], num[2] - 1 - x[:, 2]], 1)
+    direction = np.argmin(to_end, 1)
+    cells = to_end[np.arange(len(x)), direction] + 1
+    return np.where(on, direction, -1), np.where(on, cells, 0), to_end
+
+
+def winding_number(verts, faces, q):
+    """Generalised winding number of the mesh about each query in float64, by the solid-angle formula of Van Oosterom and Strackee
+    (1983): 1 inside a closed, outward-oriented surface, 0 outside, -1 inside an inward-oriented one.  Independent of any grid or ray."""
+    tri = np.asarray(verts, np.float32).astype(np.float64)[np.asarray(faces, np.int64).reshape(-1, 3)]
+    out = np.empty(len(q))
+    for i, p in enumerate(np.asarray(q, np.float32).astype(np.float64).reshape(-1, 3)):
+        a, b, c = tri[:, 0] - p, tri[:, 1] - p, tri[:, 2] - p
+        la, lb, lc = np.linalg.norm(a, axis=1), np.linalg.norm(b, axis=1), np.linalg.norm(c, axis=1)
+        numer = np.einsum("ij,ij->i", a, np.cross(b, c))
+        denom = la * lb * lc + np.einsum("ij,ij->i", a, b) * lc + np.einsum("ij,ij->i", b, c) * la + np.einsum("ij,ij->i", c, a) * lb
+        out[i] = np.arctan2(numer, denom).sum() / (2 * np.pi)
+    return out
+
+
+def ray_grazing(verts, faces, o, d, step, origin, dims, in_plane_axis=None):
+    """Is the ray one on which a float32 walk over the grid may answer differently from the brute force?  float64.  True when some
+    triangle the ray hits (exact test, t >= 0) is hit at a point closer than m to a grid plane or to the triangle's boundary, with
+    m = 2 (nx + ny + nz + 3) 2^-24 S and S the largest coordinate magnitude among the origin, the hit point and the grid's corners:
+    the walk accumulates at most nx + ny + nz + 3 float32 steps (its own guard), one ulp of S each, doubled for the entry point.
+
+    in_plane_axis = k is for a ray that lies IN a grid plane of axis k (origin on a cell wall, direction[k] = 0): every point of it is
+    at distance 0 from that plane, and the walk stays in one of the two slabs of cells beside it - which one is decided by a rounding.
+    The planes of axis k are then left out, and a hit counts as grazing unless the triangle reaches more than m to both sides of the
+    ray's plane, i.e. is listed in both slabs.  -> bool[R]"""
+    V = np.asarray(verts, np.float32).astype(np.float64)
+    tri = V[np.asarray(faces, np.int64).reshape(-1, 3)]
+    org = np.asarray(origin, np.float32).astype(np.float64)
+    dims = np.asarray(dims, np.int64)
+    step = float(np.float32(step))
+    far = org + step * dims
+    s_grid = max(np.abs(org).max(), np.abs(far).max())
+    k_steps = 2.0 * (int(dims.sum()) + 3) * 2.0 ** -24
+    a, e1, e2 = tri[:, 0], tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    edges = [(tri[:, i], tri[:, (i + 1) % 3] - tri[:, i]) for i in range(3)]
+    O = np.asarray(o, np.float32).astype(np.float64).reshape(-1, 3)
+    D = np.asarray(d, np.float32).astype(np.float64).reshape(-1, 3)
+    out = np.zeros(len(O), bool)
+    for r, (p, w) in enumerate(zip(O, D)):
+        if not w.any():
+            continue
+        h = np.cross(w, e2)
+        det = np.einsum("ij,ij->i", e1, h)
+        ok = det != 0
+        inv = 1.0 / np.where(ok, det, 1.0)
+        s = p - a
+        u = np.einsum("ij,ij->i", s, h) * inv
+        qv = np.cross(s, e1)
+        v = (qv @ w) * inv
+        t = np.einsum("ij,ij->i", e2, qv) * inv
+        hit = np.nonzero(ok & (u >= 0) & (v >= 0) & (u + v <= 1) & (t >= 0))[0]
+        if not len(hit):
+            continue
+        x = p + t[hit, None] * w                                             # hit points [H,3]
+        m = k_steps * np.maximum(max(s_grid, np.abs(p).max()), np.abs(x).max(1))
+        g = (x - org) / step
+        to_plane = np.abs(g - np.round(g)) * step                            # [H,3]
+        if in_plane_axis is not None:
+            k = in_plane_axis
+            to_plane[:, k] = np.inf
+            lo, hi = tri[hit][:, :, k].min(1), tri[hit][:, :, k].max(1)
+            if np.any((lo >= p[k] - m) | (hi <= p[k] + m)):
+                out[r] = True
+                continue
+        to_edge = np.full(len(hit), np.inf)
+        for e0, ed in edges:
+            rel = x - e0[hit]
+            along = np.clip(np.einsum("ij,ij->i", rel, ed[hit]) / np.maximum(np.einsum("ij,ij->i", ed[hit], ed[hit]), 1e-300), 0, 1)
+            to_edge = np.minimum(to_edge, np.linalg.norm(rel - along[:, None] * ed[hit], axis=1))
+        out[r] = bool(np.any((to_plane.min(1) < m) | (to_edge < m)))
     return out
 
 
@@ -437,16 +527,20 @@ def nearest_backward(verts, faces, points, face_ids, bary, dnearest):
     V = torch.as_tensor(np.asarray(verts, np.float64))
     tri = V[torch.as_tensor(np.asarray(faces, np.int64))[torch.as_tensor(np.asarray(face_ids, np.int64))]]      # [Q,3,3]
     p = torch.tensor(np.asarray(points, np.float64), requires_grad=True)
-    b = np.asarray(bary)
+    b = np.array(bary)
     zeros = (b == 0).sum(1)
     a, e1, e2 = tri[:, 0], tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
     n = torch.cross(e1, e2, dim=1)
-    c_face = p - n * ((p - a) * n).sum(1, keepdim=True) / (n * n).sum(1, keepdim=True)
+    # (a triangle without area has no plane, an edge without length no line: the projection is then the identity / the constant end
+    #  point, as the device kernel's `nn > 0` / `ee > 0` guards have it - and no 0/0 leaks into the rows that take another form)
+    nn = (n * n).sum(1, keepdim=True)
+    c_face = p - n * ((p - a) * n).sum(1, keepdim=True) / torch.where(nn > 0, nn, torch.ones_like(nn))
     z = np.where(b[:, 0] == 0, 0, np.where(b[:, 1] == 0, 1, 2))
     ar = torch.arange(len(b))
     vj, vk = tri[ar, torch.as_tensor((z + 1) % 3)], tri[ar, torch.as_tensor((z + 2) % 3)]
     d = vk - vj
-    c_edge = vj + d * ((p - vj) * d).sum(1, keepdim=True) / (d * d).sum(1, keepdim=True)
+    dd = (d * d).sum(1, keepdim=True)
+    c_edge = vj + d * ((p - vj) * d).sum(1, keepdim=True) / torch.where(dd > 0, dd, torch.ones_like(dd))
     c_corner = (torch.as_tensor(b, dtype=torch.float64)[:, :, None] * tri).sum(1)
     zt = torch.as_tensor(zeros)[:, None]
     c = torch.where(zt == 0, c_face, torch.where(zt == 1, c_edge, c_corner))

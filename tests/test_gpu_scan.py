@@ -88,8 +88,13 @@ def test_intersects_any_matches_the_bruteforce_rule(small):
     d[-30:] = sv[sf[rng.integers(0, len(sf), 30)]].mean(1) - o[-30:]        # far rays aimed at the middle of a triangle
     got = scan.intersects_any(o, d)
     want = MO.intersects_any(sv, sf, o, d)
-    print("intersects_any: rays that differ from the brute force", int((got != want).sum()), "of", len(got))
+    false_hits, missed = got & ~want, want & ~got
+    print("intersects_any: rays that differ from the brute force", int((got != want).sum()), "of", len(got),
+          "- hits no triangle gives", int(false_hits.sum()), ", hits the walk missed", int(missed.sum()))
     assert np.mean(got == want) > 0.995                                  # (a grazing ray may differ by a float32 rounding in the walk)
+    assert not false_hits.any()                                          # a reported hit is a hit of some triangle
+    dims, origin, step = scan.grid_info()
+    assert MO.ray_grazing(sv, sf, o[missed], d[missed], step, origin, dims).all()      # ... and only a grazing ray may be missed
     assert want[-30:].all() and got[-30:].all() and 0.2 < want.mean() < 0.95
     assert not scan.intersects_any(o[:4], np.zeros((4, 3), np.float32)).any()
     scan.close()
