@@ -1,5 +1,5 @@
 // Host side of libbodyfit: the C ABI of include/bodyfit.h over the gfx950 kernels.
-#include "bf_host.h"
+#include "lanes.h"
 #include "fit_kernels.h"
 #include "mesh_kernels.h"
 #include "mesh_choice.h"
@@ -199,48 +199,8 @@ __global__ void __launch_bounds__(256) __attribute__((visibility("hidden"))) bf_
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) dst[i] = src[i];
 }
 
-
-// Three ranges in one launch: a call's keypoints, initial parameters and view counts into their places in the [W F] arrays of a fit
-// lane's input arena - from the slot's pinned staging buffer (PCIe reads) or from the batch's current inputs on the device.  The
-// places of a slot are float-aligned only (n_params is 86): 4-byte accesses, coalesced.
-struct BfSeg3 { const float *src[3]; float *dst[3]; unsigned n[3]; };
-__global__ void __launch_bounds__(256) __attribute__((visibility("hidden"))) bf_publish3_kernel(BfSeg3 s) {
-    for (int k = 0; k < 3; ++k) {
-        const float *__restrict__ src = s.src[k];
-        float *__restrict__ dst = s.dst[k];
-        for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < s.n[k]; i += gridDim.x * 256) dst[i] = src[i];
-    }
-}
-
-
-// Seven ranges in one launch: what a drain hands back from a lane's group to the batch - the five result slices of the group's last slot
-// and its two Adam-moment rows, device to device (bf_lanes_drain).  Float-aligned places like the above: 4-byte accesses.
-struct BfSeg7 { const float *src[7]; float *dst[7]; unsigned n[7]; };
-__global__ void __launch_bounds__(256) __attribute__((visibility("hidden"))) bf_publish7_kernel(BfSeg7 s) {
-    for (int k = 0; k < 7; ++k) {
-        const float *__restrict__ src = s.src[k];
-        float *__restrict__ dst = s.dst[k];
-        for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < s.n[k]; i += gridDim.x * 256) dst[i] = src[i];
-    }
-}
-
 }  // extern "C"
-static int publish7(hipStream_t stream, const BfSeg7 &seg) {
-    unsigned most = 1;
-    for (int k = 0; k < 7; ++k) most = std::max(most, seg.n[k]);
-    hipLaunchKernelGGL(bf_publish7_kernel, dim3(std::min((most + 255) / 256, 64u)), dim3(256), 0, stream, seg);
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
-}
-
-static int publish3(hipStream_t stream, const BfSeg3 &seg) {
-    const unsigned most = std::max(seg.n[0], std::max(seg.n[1], seg.n[2]));
-    hipLaunchKernelGGL(bf_publish3_kernel, dim3(std::min(std::max((most + 255) / 256, 1u), 64u)), dim3(256), 0, stream, seg);
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
-}
-
-static int publish(hipStream_t stream, float *dst, const float *src, size_t n_floats) {      // (slices are 256-byte multiples: float4 clean)
+int bf_publish(hipStream_t stream, float *dst, const float *src, size_t n_floats) {      // (slices are 256-byte multiples: float4 clean)
     const size_t n4 = n_floats / 4;
     hipLaunchKernelGGL(bf_publish_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 64)), dim3(256), 0, stream,
                        (const float4 *)src, (float4 *)dst, n4);
@@ -250,29 +210,19 @@ static int publish(hipStream_t stream, float *dst, const float *src, size_t n_fl
 
 // the first n_floats of a result arena go to its pinned mirror: as a copy command (`big`: the caller's choice) or through the kernel above
 static int hand_over(hipStream_t stream, ResultArena &r, size_t n_floats, bool big) {
-    if (!big) return publish(stream, r.host, r.dev.p, n_floats);
+    if (!big) return bf_publish(stream, r.host, r.dev.p, n_floats);
     HIP_TRY(hipMemcpyAsync(r.host, r.dev.p, n_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
     return BF_OK;
 }
 
-// the result mesh of a batch: vertices and mapped joints of its F frames from their pose states, on `stream` with that stream's owner's
-// scratch; `after_mesh`: an event recorded between the mesh and the joints pass
-// `mirror`: the arena's pinned mirror, for a pass that may hand its results over itself; *handed_over then says whether it did
-static int result_mesh(bf_batch *b, MeshScratch *scr, const float *state, float *vraw, float *vout, float *xpart, float *joints,
-                       hipStream_t stream, hipEvent_t after_mesh = nullptr, const BfHandOver *mirror = nullptr, bool *handed_over = nullptr) {
-    MeshPass p;
-    p.scr = scr; p.n = b->F; p.state = state; p.stream = stream;
-    p.vraw = vraw; p.vout = vout; p.xpart = xpart; p.joints = joints;
-    p.after_mesh = after_mesh;
-    p.mirror = mirror;
-    MeshPassDone did;
-    const int rc = bf_launch_mesh(b->m, p, did);
-    if (handed_over) *handed_over = did.handed_over;
-    return rc;
-}
-// ... into the batch's current arena, on the batch stream
+// the result mesh of a batch: vertices and mapped joints of its F frames from their pose states into the batch's current arena, on the
+// batch stream; `after_mesh`: an event recorded between the mesh and the joints pass
 static int result_mesh(bf_batch *b, hipEvent_t after_mesh = nullptr) {
-    return result_mesh(b, &b->scratch, b->state.p, b->vraw.p, b->vout.p, b->xpart.p, b->joints.p, b->stream, after_mesh);
+    MeshPass p;
+    p.scr = &b->scratch; p.n = b->F; p.state = b->state.p; p.stream = b->stream;
+    p.vraw = b->vraw.p; p.vout = b->vout.p; p.xpart = b->xpart.p; p.joints = b->joints.p;
+    p.after_mesh = after_mesh;
+    return bf_launch_mesh(b->m, p);
 }
 
 // Whether the tail of `n_frames` frames whose arena prefix is `bytes` long lets its mesh and joints kernels store into the pinned mirror
@@ -297,27 +247,39 @@ static BfHandOver arena_mirror(const bf_batch *b, const ResultArena &r, const si
     return ho;
 }
 
-// the tail of a fit: mesh, joints and hand-over of the first n_floats of result arena r on `stream` (scratch, vraw, xpart: that stream's
-// owner's), then ev_copied.  `after`: the event the stream waits for first; with_mesh = false: the arena already holds its mesh.
-// A whole-arena tail with its mesh (bf_flush_tail) lets the mesh and joints kernels store into the mirror themselves where tail_stores says
-// so, and issues a hand-over only if the pass took kernels that do not (MeshPassDone::handed_over).
-static int enqueue_tail(bf_batch *b, ResultArena &r, hipStream_t stream, MeshScratch *scr, float *vraw, float *xpart, size_t n_floats,
-                        bool big, hipEvent_t after = nullptr, bool with_mesh = true) {
-    if (after) HIP_TRY(hipStreamWaitEvent(stream, after, 0));
-    float *d = r.dev.p;                              // (the arena's slices by address: the batch's views may be on another one)
-    bool handed_over = false;
+// The tail of a fit - of a batch's call or of a lane's group: mesh and joints of the arena's n_frames frames (`per` > 0: calls of `per`
+// frames each, MeshPass::per) from the states the fit left in it, the hand-over of its first n_floats to the pinned mirror, then ev_copied,
+// all on `on.stream` with that stream's owner's scratch.  The arena's slices are taken by address through `off`: the batch's views may be on
+// another arena.  with_mesh = false: the arena already holds its mesh.  may_store: the mesh and joints kernels store into the mirror
+// themselves where tail_stores says so for these n_floats and frames; the hand-over - a copy command (`big`) or the publish kernel - is
+// issued only if the pass took kernels that do not (MeshPassDone::handed_over).
+int bf_enqueue_tail(bf_batch *b, ResultArena &r, const size_t off[5], int n_frames, int per, const TailOn &on, size_t n_floats,
+                    bool with_mesh, bool may_store, bool big) {
+    float *d = r.dev.p;
+    MeshPassDone did;
     if (with_mesh) {
-        const BfHandOver ho = arena_mirror(b, r, b->res_off);
-        const bool store = n_floats == b->res_total && tail_stores(b, n_floats * sizeof(float), b->F);
-        BF_TRY(result_mesh(b, scr, d + b->res_off[2], vraw, d + b->res_off[4], xpart, d + b->res_off[3], stream, nullptr, store ? &ho : nullptr, &handed_over));
+        const BfHandOver ho = arena_mirror(b, r, off);
+        MeshPass p;
+        p.scr = on.scr; p.n = n_frames; p.per = per; p.state = d + off[2]; p.stream = on.stream;
+        p.vraw = on.vraw; p.vout = d + off[4]; p.xpart = on.xpart; p.joints = d + off[3];
+        if (may_store && tail_stores(b, n_floats * sizeof(float), n_frames)) p.mirror = &ho;
+        BF_TRY(bf_launch_mesh(b->m, p, did));
     }
-    if (!handed_over) BF_TRY(hand_over(stream, r, n_floats, big));
-    HIP_TRY(hipEventRecord(r.ev_copied, stream));
+    if (!did.handed_over) BF_TRY(hand_over(on.stream, r, n_floats, big));
+    HIP_TRY(hipEventRecord(r.ev_copied, on.stream));
     return BF_OK;
 }
 
+// ... of a call of the batch, on the second stream behind `after` (the fit, or the mesh, that filled arena r).  Only a whole-arena tail with
+// its mesh (bf_flush_tail) may store into the mirror.
+static int enqueue_tail(bf_batch *b, ResultArena &r, size_t n_floats, bool big, hipEvent_t after, bool with_mesh = true) {
+    HIP_TRY(hipStreamWaitEvent(b->copy_stream, after, 0));
+    return bf_enqueue_tail(b, r, b->res_off, b->F, 0, {b->copy_stream, &b->scratch, b->vraw.p, b->xpart.p}, n_floats, with_mesh,
+                           n_floats == b->res_total, big);
+}
+
 // result arena k becomes the one the DevBuf views and the pinned mirrors point at
-static void bf_use_arena(bf_batch *b, int k) {
+void bf_use_arena(bf_batch *b, int k) {
     float *d = b->arena[k].dev.p, *h = b->arena[k].host;
     b->params.slice(d + b->res_off[0], b->res_cnt[0]); b->terms.slice(d + b->res_off[1], b->res_cnt[1]);
     b->state.slice(d + b->res_off[2], b->res_cnt[2]); b->joints.slice(d + b->res_off[3], b->res_cnt[3]);
@@ -327,44 +289,26 @@ static void bf_use_arena(bf_batch *b, int k) {
     b->cur = k;
 }
 
-// input arena k of the batch's own two becomes the one `keypoints`, `params0`, `ndiv` point at (host = true: at its pinned staging
-// buffer itself)
+// `keypoints`, `params0`, `ndiv` become views of one call's frames at kp / p0 / ndiv, and the cursor says where that is: the one place
+// that moves either
+void bf_set_inputs(bf_batch *b, const InputCursor &at, float *kp, float *p0, int *ndiv) {
+    b->keypoints.slice(kp, (size_t)b->F * b->V * b->m->nl_loss * 3);
+    b->params0.slice(p0, (size_t)b->F * b->m->np);
+    b->ndiv.slice(ndiv, (size_t)b->F);
+    b->in_at = at;
+}
+
+// input arena k of the batch's own two becomes the current one (host = true: its pinned staging buffer itself)
 static void bf_use_inputs(bf_batch *b, int k, bool host) {
-    InputArena &in = b->in[k];
-    float *base = host ? in.host : in.dev.p;
-    const bf_model *m = b->m;
-    b->keypoints.slice(base + b->in_off[0], (size_t)b->F * b->V * m->nl_loss * 3);
-    b->params0.slice(base + b->in_off[1], (size_t)b->F * m->np);
-    b->ndiv.slice((int *)(base + b->in_off[2]), (size_t)b->F);
-    b->in_cur = k;
-    b->in_slot = 0;
-    b->in_pinned = false;
-    b->in_host = host;
+    float *base = host ? b->in[k].host : b->in[k].dev.p;
+    InputCursor at;
+    at.arena = k; at.host = host;
+    bf_set_inputs(b, at, base + b->in_off[0], base + b->in_off[1], (int *)(base + b->in_off[2]));
 }
-
-// where slot `slot` of a lane's input arena keeps its frames: keypoints, params0, ndiv
-struct SlotPlace { float *kp, *p0; int *ndiv; };
-static SlotPlace slot_place(const bf_batch *b, LaneInputs &in, int slot) {
-    float *base = in.dev.p;
-    return {base + bf_slot_off(b->gin, 0, slot), base + bf_slot_off(b->gin, 1, slot), (int *)(base + bf_slot_off(b->gin, 2, slot))};
-}
-
-// ... of input arena a of fit lane j (in_cur = 2 + 2 * j + a, in_slot = slot)
-static void bf_use_lane_inputs(bf_batch *b, int j, int a, int slot) {
-    const SlotPlace at = slot_place(b, b->lanes[j].in[a], slot);
-    b->keypoints.slice(at.kp, (size_t)b->F * b->V * b->m->nl_loss * 3);
-    b->params0.slice(at.p0, (size_t)b->F * b->m->np);
-    b->ndiv.slice(at.ndiv, (size_t)b->F);
-    b->in_cur = 2 + 2 * j + a;
-    b->in_slot = slot;
-    b->in_host = false;
-}
-// the lane arena the views are on (in_cur >= 2)
-static LaneInputs &current_lane_inputs(bf_batch *b) { return b->lanes[(b->in_cur - 2) / 2].in[(b->in_cur - 2) % 2]; }
 
 // a synchronous setter's write into the current input arena (the stream is idle)
 static hipError_t write_input(bf_batch *b, void *dst, const void *src, size_t bytes) {
-    if (b->in_host) { std::memcpy(dst, src, bytes); return hipSuccess; }
+    if (b->in_at.host) { std::memcpy(dst, src, bytes); return hipSuccess; }
     return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
 }
 
@@ -376,7 +320,7 @@ int bf_flush_tail(bf_batch *b) {
     if (k < 0) return BF_OK;
     b->tail_k = -1;
     ResultArena &r = b->arena[k];
-    const int rc = enqueue_tail(b, r, b->copy_stream, &b->scratch, b->vraw.p, b->xpart.p, b->res_total, b->tail_big, r.ev_done);
+    const int rc = enqueue_tail(b, r, b->res_total, b->tail_big, r.ev_done);
     if (rc) {
         // the mesh / copy / event of arena k did not all go out: its ev_copied still carries its previous (completed) record, so a
         // wait on it would pass and hand out the pinned buffer's OLD contents.  Nothing of this arena may be read any more:
@@ -389,270 +333,26 @@ int bf_flush_tail(bf_batch *b) {
     return BF_OK;
 }
 
-/* Fit lanes.  A frame-after-frame fit (the tail-aside conditions of fit_plan) is one workgroup per frame on one CU for ~380 us while
- * the other CUs idle, and the frames of a capture are independent (every call carries BF_FIT_RESET).  With n_lanes > 1 such a fit goes
- * to a lane: a stream of its own with its own Adam moments, result arena, mesh scratch and input arenas, so that fits of consecutive
- * calls run side by side on different CUs.  A lane's stream holds [input transfer] fit, mesh, joints, hand-over: its own work in order.
- * Lanes are ordered against each other and against the batch stream by HIP events only (no device-side waits): lanes that end up
- * sharing a hardware queue run one after another, never hang.
- *   - Lane GROUPS.  The lanes that run side by side are as many as the high-priority pool has hardware queues (four), but the fit kernel
- *     takes any number of independent frames, one workgroup each, in hardly more time.  So a lane call does not launch at once: it
- *     JOINS the open group of lane `lane_next` - slot after slot of that lane's input arena, up to W calls - and one launch of G F
- *     workgroups, one tail and one hand-over serve the G calls that joined (lane_launch).  The group goes out when a call joins while
- *     its lane is idle (a slow feeder gets G = 1 and no added latency) - unless the feeder is fast and the group young, see
- *     BF_FIT_LANE_HOLD_US below - when it is full (behind the lane's running group), when its calls would differ in iterations or
- *     hyper-parameters, and at every entry point that drains or reads.  Then `lane_next` moves on.
- *     BF_FIT_LANE_HOLD_US=<H> (default 100): a group that finds its lane idle is still held while the call before came less than H
- *     microseconds ago AND the group's first call joined less than H ago - a burst fills groups instead of sending its first calls out
- *     alone; a lone or slow caller never waits, and H bounds what a burst's frames can be held.  0: an idle lane always launches.
- *     BF_FIT_LANE_WIDTH=<n> caps W (default 32; 1: a launch per call, the call sequence before groups); a batch uses at most
- *     CUs / (lanes x frames).  BF_FIT_LANE_FILL=1 turns the idle rule off - groups fill to W or to a flush - so that tests can force
- *     group shapes.
- *   - Lanes take over (lanes_engage) behind everything on the batch stream.  Every entry point that is not a lane fit or a staging drains
- *     them first (bf_lanes_drain, from bf_sync_all / bf_guard_arena / fit_impl): it launches the open group, waits for the lane streams
- *     and leaves the last lane fit's result and Adam moments in the batch's own buffers - the state the tail-aside path leaves - so
- *     that continuing fits, setters, reads, the graph and dense paths run exactly as without lanes.
- *   - HOST-FED groups (W > 1).  bf_batch_stage_inputs issues no GPU work: it packs the call's inputs into the next slot of the open
- *     group's PINNED arena - laid out like the device arena, slot for slot (lane_slots.h; two arenas per lane, a group each) - and
- *     points the batch's views at the slot's place on the device.  lane_launch moves all the group's slots with ONE transfer ahead of
- *     the fit launch (lane_feed: a prefix of slots is three contiguous ranges), a slot staged past the last joined call with them, and
- *     records the arena's event behind it; a drain that finds only such a slot sends it alone, so that whoever reads the views on the
- *     device next - a plain fit, bf_loss_grad, a continuing fit - finds them filled.  The transfer is ordered behind this lane's fits
- *     that last read the arena by stream order and never behind a running fit of another lane.  The lane opens the arena again two of
- *     its groups later; the host waits then only if that transfer has not finished (lane_open).  The fit kernel always reads the device
- *     arena (large view counts and the table-driven instances read the keypoints inside the loop): no zero-copy here.
- *   - A call WITHOUT a staging of its own takes the batch's current inputs: by a host copy, pinned slot to pinned slot, while their
- *     pinned copy is valid (the usual re-fit: no device copy, no event, no wait between lanes - the views move to the new slot), and by
- *     a device-side copy on the lane's stream when they are in device memory only - after a synchronous setter, a device-side
- *     producer or a drain (bf_batch::in_pinned is cleared by every drain).  A group is host-fed or device-fed, never both: a call of
- *     the other kind launches the open group first.  A device-fed group gets no transfer at launch; the next transfer into an arena a
- *     device-side copy read from waits for that copy through the copying lane's event (LaneInputs::readers).
- *   - W = 1 keeps the call sequence before groups: a staging transfers its slot - the arena - at once on the lane's stream, and a call
- *     without a staging of its own reads the current inputs in place.
- * BF_FIT_LANES=<n> sets the lane count (1: no lanes, the single-stream path); a batch uses at most (CUs / frames) of them. */
-static FrameIO bf_frame_io(bf_batch *b, bool want_grads);       // (the batch's own launch arguments: below, with the fit routes)
-static int env_int(const char *name, int dflt, int lo, int hi) {
-    const char *e = getenv(name);
-    return std::max(lo, std::min(e ? atoi(e) : dflt, hi));
-}
-#ifndef BF_FIT_LANE_HOLD_US_DEFAULT
-#define BF_FIT_LANE_HOLD_US_DEFAULT 100
-#endif
-static int fit_lanes_wanted() { static const int d = env_int("BF_FIT_LANES", 4, 1, 32); return d; }
-static int fit_lane_width_wanted() { static const int d = env_int("BF_FIT_LANE_WIDTH", 32, 1, 64); return d; }
-static bool fit_lane_fill() { static const bool d = env_int("BF_FIT_LANE_FILL", 0, 0, 1) == 1; return d; }
-// H of the idle rule (fit_lane): a group that finds its lane idle is held while the feeder is fast - the call before this one less than H ago -
-// and the group younger than H.  0: an idle lane always launches (the rule before the hold)
-static std::chrono::microseconds fit_lane_hold() { static const int d = env_int("BF_FIT_LANE_HOLD_US", BF_FIT_LANE_HOLD_US_DEFAULT, 0, 10000000); return std::chrono::microseconds(d); }
-// a group's hand-over from this size on is a copy command, below it the publish kernel: the threshold fit_plan uses for a call.  Measured
-// for groups (profiles/fit_lane_groups.md): the publish kernel for full groups is the slowest, always copying no better than this
-static constexpr size_t kLaneCopyBytes = (size_t)512 * 1024;
-
-static void lanes_release(bf_batch *b) {
-    if (!b->lanes) return;
-    for (int j = 0; j < b->n_lanes; ++j)              // (a lane's fit may read another lane's input arena: all of them first)
-        if (b->lanes[j].stream) (void)hipStreamSynchronize(b->lanes[j].stream);
-    for (int j = 0; j < b->n_lanes; ++j)
-        if (b->lanes[j].stream) (void)hipStreamDestroy(b->lanes[j].stream);
-    b->lanes.reset();                     // (the lanes' buffers and arenas)
-    if (b->ev_engage) { (void)hipEventDestroy(b->ev_engage); b->ev_engage = nullptr; }
+// net_output of smplify.py:103 -> the packed optimiser vector: transl = 0, scale = 1 (:126-128), body pose, betas, root orientation
+// (bf_pack_init, lane_slots.h)
+BfInitMap bf_init_map(const bf_model *m) { return {m->np, m->nb, m->fit.nbp, m->fit.off_pose, m->fit.off_beta, m->fit.off_orient}; }
+static void pack_init(const bf_batch *b, const float *init_betas, const float *init_pose, float *dst) {
+    bf_pack_init(bf_init_map(b->m), b->F, init_betas, init_pose, dst);
 }
 
-static size_t up64(size_t n) { return bf_up64(n); }          // 256-byte slices
-
-static int lanes_create(bf_batch *b) {
-    if (b->lanes) return BF_OK;
-    const bf_model *m = b->m;
-    const size_t F = b->F, np = m->np, W = b->lane_w;
-    size_t res_w = 0;                     // a result arena whose arrays hold W calls' frames (W = 1: the batch's res_total)
-    for (int i = 0; i < 5; ++i) res_w += up64(W * b->res_cnt[i]);
-    b->lanes.reset(new BfLane[b->n_lanes]);
-    int least = 0, greatest = 0;
-    bool ok = hipEventCreateWithFlags(&b->ev_engage, hipEventDisableTiming) == hipSuccess &&
-              hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
-    for (int j = 0; j < b->n_lanes && ok; ++j) {
-        BfLane &l = b->lanes[j];
-        // the lane streams on the HIGHEST priority: the runtime keeps a pool of hardware queues per priority (GPU_MAX_HW_QUEUES each),
-        // and in the normal pool the null stream and the batch stream already hold two of four - three lanes there ran as two,
-        // four on the high pool run as four (profiles/fit_lanes.md)
-        ok = hipStreamCreateWithPriority(&l.stream, hipStreamNonBlocking, greatest) == hipSuccess &&
-             l.adam_m.alloc(W * F * np) == hipSuccess && l.adam_v.alloc(W * F * np) == hipSuccess && l.vraw.alloc(W * b->vraw.n) == hipSuccess &&
-             l.xpart.alloc(W * b->xpart.n) == hipSuccess && l.arena.create(res_w) == hipSuccess &&
-             l.in[0].create(b->gin.total) == hipSuccess && l.in[1].create(b->gin.total) == hipSuccess &&
-             (W == 1 || hipEventCreateWithFlags(&l.ev_join, hipEventDisableTiming) == hipSuccess);
+// keypoints | params0 | ndiv of the next frame packed into a pinned staging buffer (`h`; `ev`, `pending`: its transfer), once its previous
+// transfer has left it
+int bf_pack_staging(const bf_batch *b, float *h, hipEvent_t ev, bool &pending, const float *keypoints, const int32_t *n_use_frames,
+                    const float *init_betas, const float *init_pose) {
+    if (pending) {
+        HIP_TRY(hipEventSynchronize(ev));
+        pending = false;
     }
-    if (ok && W > 1) ok = b->proj_rep.alloc(W * b->proj.n) == hipSuccess;
-    b->proj_rep_stale = true;
-    if (!ok) { lanes_release(b); return fail(BF_ERR_HIP, "fit lanes: creating a lane's stream or buffers failed"); }
+    std::memcpy(h + b->in_off[0], keypoints, (size_t)b->F * b->V * b->m->nl_loss * 3 * sizeof(float));
+    pack_init(b, init_betas, init_pose, h + b->in_off[1]);
+    bf_fill_ndiv((int32_t *)(h + b->in_off[2]), b->F, n_use_frames, b->V);
     return BF_OK;
 }
-
-// the lanes take over behind everything on the batch stream (the inputs, parameters and cameras set there): a lane's stream waits for
-// that point before its first work of the period (lane_begin)
-static int lanes_engage(bf_batch *b) {
-    if (b->lanes_on) return BF_OK;
-    BF_TRY(lanes_create(b));
-    BF_TRY(bf_flush_tail(b));
-    if (b->lane_w > 1 && b->proj_rep_stale) {          // (the cameras change through a setter that drains: once per set_cameras)
-        for (int w = 0; w < b->lane_w; ++w)
-            HIP_TRY(hipMemcpyAsync(b->proj_rep.p + (size_t)w * b->proj.n, b->proj.p, b->proj.n * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
-        b->proj_rep_stale = false;
-    }
-    HIP_TRY(hipEventRecord(b->ev_engage, b->stream));
-    for (int j = 0; j < b->n_lanes; ++j) b->lanes[j].need_engage = true;
-    b->lanes_on = true;
-    return BF_OK;
-}
-
-static int lane_begin(bf_batch *b, BfLane &l) {
-    if (l.need_engage) { HIP_TRY(hipStreamWaitEvent(l.stream, b->ev_engage, 0)); l.need_engage = false; }
-    l.busy = true;
-    return BF_OK;
-}
-
-// The one input transfer of a host-fed group of lane j: slots [0, n) of arena `in` - the G calls that joined and, if there is one, the slot
-// staged past them; a prefix of slots is three contiguous ranges (bf_slot_prefix) - from the pinned buffer to their places on the device,
-// on the lane's stream ahead of the fit, and the arena's event behind it.  This lane's earlier fits that read the arena are ahead in
-// stream order; another lane's device-side copy of one of its slots (`readers`) is waited for through that lane's event.
-static int lane_feed(bf_batch *b, int j, LaneInputs &in, int n) {
-    BfLane &l = b->lanes[j];
-    for (int r = 0; r < b->n_lanes; ++r)
-        if (r != j && ((in.readers >> r) & 1u)) HIP_TRY(hipStreamWaitEvent(l.stream, b->lanes[r].ev_join, 0));
-    in.readers = 0;
-    BfRange rg[3];
-    bf_slot_prefix(b->gin, n, rg);
-    BfSeg3 seg;
-    for (int k = 0; k < 3; ++k) { seg.src[k] = in.host + rg[k].off; seg.dst[k] = in.dev.p + rg[k].off; seg.n[k] = (unsigned)rg[k].n; }
-    BF_TRY(publish3(l.stream, seg));
-    HIP_TRY(hipEventRecord(in.ev, l.stream));
-    in.pending = true;
-    b->feed_transfers += 1;
-    return BF_OK;
-}
-
-// The open group of lane j goes out: for a host-fed group its one input transfer, then ONE fit launch for the G F frames of the G calls
-// that joined, the tail for all of them (ONE multi-frame mesh launch for calls below 16 frames, a pass per call above: MeshPass::per), one
-// hand-over of the group's floats, ev_copied.
-// The result arrays are packed for G F frames - FrameIO is array-major over n_frames - and their offsets stay with the group (`held`).
-// The lane's group is closed whatever happens, and the next call joins the next lane.
-static int lane_launch(bf_batch *b, int j) {
-    BfLane &l = b->lanes[j];
-    const int G = l.n_open;
-    // a host-fed group: its slots [0, G) and a slot staged past the last joined call are in the pinned buffer only
-    const int n_feed = (b->lane_w > 1 && l.open_host) ? G + (l.slot_staged ? 1 : 0) : 0;
-    if (!G && !n_feed) return BF_OK;
-    LaneInputs &in_open = l.in[l.open_a];
-    l.open = false; l.n_open = 0; l.slot_staged = false;        // (a slot staged past the last call stays the batch's current inputs: the next call copies it)
-    if (!G) return lane_feed(b, j, in_open, n_feed);            // (a drain with nothing joined: the staged slot alone, for whoever reads the views next)
-    if (b->lane_next == j) b->lane_next = (j + 1) % b->n_lanes;
-    bf_model *m = b->m;
-    ResultArena &r = l.arena;
-    BfLane::Held h;
-    h.seq0 = l.open_seq0; h.G = G;
-    for (int i = 0; i < 5; ++i) { h.off[i] = h.total; h.total += up64((size_t)G * b->res_cnt[i]); }
-    l.held = BfLane::Held{};                                    // (a failure from here on: the arena holds nothing that may be read)
-    r.seq = -1; r.fetched = r.has_v = false;
-    float *d = r.dev.p;
-    FrameIO io = bf_frame_io(b, false);
-    io.n_frames = G * b->F;
-    if (l.borrowed) { io.keypoints = l.bor_kp; io.params0 = l.bor_p0; io.ndiv = l.bor_ndiv; }
-    else { const SlotPlace at = slot_place(b, l.in[l.open_a], 0); io.keypoints = at.kp; io.params0 = at.p0; io.ndiv = at.ndiv; }      // (re-arm inside the fit kernel)
-    if (b->lane_w > 1) io.proj = b->proj_rep.p;
-    io.params = d + h.off[0]; io.terms = d + h.off[1]; io.state = d + h.off[2];
-    io.adam_m = l.adam_m.p; io.adam_v = l.adam_v.p;
-    if (n_feed) BF_TRY(lane_feed(b, j, in_open, n_feed));
-    HIP_TRY(bf_fit_launch(&m->fit, &io, &l.open_hd, l.open_iters, 0, b->adam_tab.p, 0, b->fit_smem, l.stream, nullptr));
-    MeshPass p;
-    p.scr = &l.scratch; p.n = G * b->F; p.per = b->F; p.state = d + h.off[2]; p.stream = l.stream;
-    p.vraw = l.vraw.p; p.vout = d + h.off[4]; p.xpart = l.xpart.p; p.joints = d + h.off[3];
-    // the group's hand-over: by the tail's own kernels where they store into the mirror (calls below 16 frames), else behind them
-    const BfHandOver ho = arena_mirror(b, r, h.off);
-    if (tail_stores(b, h.total * sizeof(float), G * b->F)) p.mirror = &ho;
-    MeshPassDone did;
-    BF_TRY(bf_launch_mesh(m, p, did));
-    if (!did.handed_over) BF_TRY(hand_over(l.stream, r, h.total, h.total * sizeof(float) >= kLaneCopyBytes));
-    HIP_TRY(hipEventRecord(r.ev_copied, l.stream));
-    l.held = h;
-    r.seq = h.seq0 + G - 1; r.fetched = r.has_v = true;         // (the arena's newest fit: what a trade in bf_lanes_drain hands on)
-    b->lane_launches += 1;
-    b->lane_max_g = std::max(b->lane_max_g, G);
-    return BF_OK;
-}
-
-int bf_lanes_drain(bf_batch *b) {
-    if (!b->lanes_on) return BF_OK;
-    b->in_pinned = false;                 // (what follows a drain may write the device slot alone: a setter, a device-side producer)
-    for (int j = 0; j < b->n_lanes; ++j) BF_TRY(lane_launch(b, j));       // (the open group, if calls have joined one)
-    b->lanes_on = false;
-    const int j = b->lane_last;
-    b->lane_last = -1;
-    // The last lane fit lands where the tail-aside path leaves a fit - in the result arena the previous fit did not use, with its Adam
-    // moments as the batch's.
-    const int k = b->cur ^ 1;
-    ResultArena &r = b->arena[k];
-    const bool by_kernel = j >= 0 && b->lane_w > 1 && b->lanes[j].held.G > 0;
-    if (by_kernel) {
-        // A group's arena is laid out for G calls: the last slot's five slices and its two Adam-moment rows are copied, device to device, by
-        // ONE launch on the lane's own stream - behind that lane's fit, tail and hand-over, so it ends with the lane instead of starting a
-        // chain of copy commands after every lane has been waited for (a bracket ends in exactly one drain: this is on its path).
-        // Nothing on the device still uses arena k or the batch's moments when this launch runs:
-        //  - the batch stream: lane j has fitted since the lanes took over, so its stream has waited for ev_engage (lane_begin), which
-        //    lanes_engage recorded behind everything on the batch stream; and while the lanes are on nothing is issued there - every entry
-        //    point but a lane fit or a staging comes through this drain first, and a staging with W > 1 issues no GPU work;
-        //  - the second stream: a deferred tail is enqueued and a pipelined fetch of arena k waited for just below, on the host;
-        //  - the other lanes use their own arenas and moments, and of the batch's only inputs, cameras and the Adam table - not written here.
-        // And nothing reads them before this launch has finished: the lane's stream is waited for below, before this function returns.
-        BfLane &l = b->lanes[j];
-        BF_TRY(bf_flush_tail(b));
-        if (r.copy_pending) { HIP_TRY(hipEventSynchronize(r.ev_copied)); r.copy_pending = false; }
-        const BfLane::Held &h = l.held;
-        const size_t s = h.G - 1, n_adam = (size_t)b->F * b->m->np;
-        BfSeg7 seg;
-        for (int i = 0; i < 5; ++i) {
-            seg.src[i] = l.arena.dev.p + h.off[i] + s * b->res_cnt[i]; seg.dst[i] = r.dev.p + b->res_off[i]; seg.n[i] = (unsigned)b->res_cnt[i];
-        }
-        seg.src[5] = l.adam_m.p + s * n_adam; seg.dst[5] = b->adam_m.p; seg.n[5] = (unsigned)n_adam;
-        seg.src[6] = l.adam_v.p + s * n_adam; seg.dst[6] = b->adam_v.p; seg.n[6] = (unsigned)n_adam;
-        BF_TRY(publish7(l.stream, seg));
-    }
-    for (int q = 0; q < b->n_lanes; ++q)
-        if (b->lanes[q].busy) { HIP_TRY(hipStreamSynchronize(b->lanes[q].stream)); b->lanes[q].busy = false; }
-    if (j < 0) return BF_OK;              // (inputs staged, no lane fit since the lanes took over)
-    BfLane &l = b->lanes[j];
-    if (!by_kernel) {
-        // (W = 1, or no group to hand back.)  Nothing on the device uses either side any more (the lane waited for the batch stream before its
-        // fit and has finished; a pipelined fetch of arena k is waited for here).
-        BF_TRY(bf_flush_tail(b));
-        if (r.copy_pending) { HIP_TRY(hipEventSynchronize(r.ev_copied)); r.copy_pending = false; }
-    }
-    if (!l.held.G) {                      // (its launch failed: no result anywhere)
-        b->fetched = b->have_result = false;
-        return fail(BF_ERR_HIP, "fit lanes: the last lane fit was not launched");
-    }
-    if (b->lane_w == 1) {
-        // equal-sized buffers: by trading them - the lane takes the batch's arena k and moments (its next fit overwrites them), no
-        // copy; the graphs captured with the old addresses are dropped
-        r.trade_buffers(l.arena);
-        l.held = BfLane::Held{};
-        std::swap(b->adam_m.p, l.adam_m.p);
-        std::swap(b->adam_v.p, l.adam_v.p);
-        if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
-        for (auto &g : b->graph_pipe) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    } else {
-        // ... and mirror to mirror on the host, now that the lane's hand-over has been waited for.  The group stays readable in the lane
-        // (bf_batch_get_previous).
-        const BfLane::Held &h = l.held;
-        const size_t s = h.G - 1;
-        for (int i = 0; i < 5; ++i)
-            std::memcpy(r.host + b->res_off[i], l.arena.host + h.off[i] + s * b->res_cnt[i], b->res_cnt[i] * sizeof(float));
-        r.seq = h.seq0 + (long long)s; r.fetched = r.has_v = true;
-    }
-    bf_use_arena(b, k);
-    return BF_OK;
-}
-
-// bf_batch_stage_inputs on a batch with lanes: the next lane's other input arena, its transfer on that lane's stream
-static int stage_lane(bf_batch *b, const float *keypoints, const int32_t *n_use_frames, const float *init_betas, const float *init_pose);
 
 int bf_sync_all(bf_batch *b) {
     BF_TRY(bf_lanes_drain(b));
@@ -697,10 +397,9 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
     b->ring.assign((size_t)bf_batch::kRing * 4, nullptr);
     b->ev = b->ring.data();          // (the events of a slot are created when the slot is first used: 4096 creations cost 4 ms)
     {
-        auto up = [](size_t n) { return (n + 63) & ~(size_t)63; };
         const size_t n_kp = F * n_views * m->nl_loss * 3;
-        b->in_off[0] = 0; b->in_off[1] = up(n_kp); b->in_off[2] = b->in_off[1] + up(F * np);
-        b->in_total = b->in_off[2] + up(F);
+        b->in_off[0] = 0; b->in_off[1] = bf_up64(n_kp); b->in_off[2] = b->in_off[1] + bf_up64(F * np);
+        b->in_total = b->in_off[2] + bf_up64(F);
         if (const char *e = getenv("BF_STAGE_MODE")) b->stage_zerocopy = !strcmp(e, "zerocopy");
         if (const char *e = getenv("BF_TAIL_HANDOVER"))          // (copy: the sequence before the kernels stored into the mirror)
             b->tail_handover = !strcmp(e, "copy") ? bf_batch::TailHandOver::COPY : !strcmp(e, "store") ? bf_batch::TailHandOver::STORE : bf_batch::TailHandOver::BY_SIZE;
@@ -708,11 +407,10 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
         if (ok) bf_use_inputs(b, 0, false);
     }
     {
-        auto up = [](size_t n) { return (n + 63) & ~(size_t)63; };          // 256-byte slices
         const size_t n_par = F * np, n_terms = F * 4, n_state = F * bf_state_stride(m->nj, m->npf, m->nb),
                      n_joints = F * m->n_joint_map * 3, n_v = F * m->nv * 3;
-        const size_t o_terms = up(n_par), o_state = o_terms + up(n_terms), o_joints = o_state + up(n_state),
-                     o_v = o_joints + up(n_joints), total = o_v + up(n_v);
+        const size_t o_terms = bf_up64(n_par), o_state = o_terms + bf_up64(n_terms), o_joints = o_state + bf_up64(n_state),
+                     o_v = o_joints + bf_up64(n_joints), total = o_v + bf_up64(n_v);          // 256-byte slices
         ok = ok && b->arena[0].create(total) == hipSuccess && b->arena[1].create(total) == hipSuccess;
         {
             // the second stream on the LOWEST priority: the runtime keeps a pool of hardware queues per priority, so it never shares a
@@ -749,15 +447,10 @@ int bf_batch_create(bf_model *m, int n_frames, int n_views, bf_batch **out) {
     if (!ok) { bf_batch_destroy(b); return fail(BF_ERR_HIP, "bf_batch_create: device allocation failed"); }
     b->fit_smem = smem;
     {
-        // fit lanes (created on first use): one frame's fit per CU, so at most CUs / frames of them; not with zero-copy staging
         int n_cus = 0;
         (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, m->device);
         if (n_cus > 0) b->n_cus = n_cus;
-        const int d = std::min(fit_lanes_wanted(), std::max(n_cus, 1) / n_frames);
-        b->n_lanes = (!b->stage_zerocopy && d > 1) ? d : 1;
-        // ... and a lane launch carries up to W calls' frames, the lanes' groups together at most a frame per CU
-        b->lane_w = std::min(fit_lane_width_wanted(), std::max(1, std::max(n_cus, 1) / (b->n_lanes * n_frames)));
-        b->gin = bf_lane_layout(b->lane_w, n_frames, F * n_views * m->nl_loss * 3, m->np);      // (W = 1: in_off / in_total)
+        bf_lanes_configure(b, n_cus);         // (fit lanes: created on first use)
     }
     *out = b;
     return BF_OK;
@@ -769,9 +462,7 @@ void bf_batch_destroy(bf_batch *b) {
     host_sums_report(b);
 #endif
     b->tail_k = -1;                       // (a tail never enqueued: nobody will read that result)
-    for (int j = 0; b->lanes && j < b->n_lanes; ++j)          // (calls that joined a group were promised a fit: it goes out before the wait)
-        if (b->lanes[j].n_open && hipSetDevice(b->m->device) == hipSuccess) (void)lane_launch(b, j);
-    lanes_release(b);                     // (waits for the lanes' work: it reads the batch's inputs, cameras and Adam table)
+    bf_lanes_destroy(b);                  // (launches the open groups and waits for the lanes' work: it reads the batch's inputs, cameras and Adam table)
     if (b->copy_stream) (void)hipStreamSynchronize(b->copy_stream);
     if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
     { std::lock_guard<std::mutex> lk(bf_scan_links()); bf_batch_unlink_scans(b); }      // (its scans outlive it: they forget this batch)
@@ -837,7 +528,7 @@ int bf_batch_set_cameras(bf_batch *b, const float *c2w, const float *K) {
     // bf_fit is asynchronous on the batch's own (non-blocking) stream: a fit still in flight reads these inputs
     BF_TRY(bf_sync_all(b));
     HIP_TRY(hipMemcpy(b->proj.p, proj.data(), proj.size() * sizeof(float), hipMemcpyHostToDevice));
-    b->proj_rep_stale = true;
+    bf_lanes_cameras_changed(b);
     return BF_OK;
 }
 
@@ -888,27 +579,6 @@ int bf_batch_reset(bf_batch *b) {
     return BF_OK;
 }
 
-// net_output of smplify.py:103 -> the packed optimiser vector: transl = 0, scale = 1 (:126-128), body pose, betas, root orientation
-// (bf_pack_init, lane_slots.h)
-static BfInitMap init_map(const bf_model *m) { return {m->np, m->nb, m->fit.nbp, m->fit.off_pose, m->fit.off_beta, m->fit.off_orient}; }
-static void pack_init(const bf_batch *b, const float *init_betas, const float *init_pose, float *dst) {
-    bf_pack_init(init_map(b->m), b->F, init_betas, init_pose, dst);
-}
-
-// keypoints | params0 | ndiv of the next frame packed into a pinned staging buffer (`h`; `ev`, `pending`: its transfer), once its previous
-// transfer has left it
-static int pack_staging(const bf_batch *b, float *h, hipEvent_t ev, bool &pending, const float *keypoints, const int32_t *n_use_frames,
-                        const float *init_betas, const float *init_pose) {
-    if (pending) {
-        HIP_TRY(hipEventSynchronize(ev));
-        pending = false;
-    }
-    std::memcpy(h + b->in_off[0], keypoints, (size_t)b->F * b->V * b->m->nl_loss * 3 * sizeof(float));
-    pack_init(b, init_betas, init_pose, h + b->in_off[1]);
-    bf_fill_ndiv((int32_t *)(h + b->in_off[2]), b->F, n_use_frames, b->V);
-    return BF_OK;
-}
-
 /* The next frame's keypoints and initial estimate, WITHOUT draining the work in flight (apps/genebody_fitting.py:183-192 hands
  * SMPLify a new frame's detections and HMR estimate every call; loss.py:160 re-uploads the keypoints every iteration).  The
  * inputs are packed into the pinned staging buffer the fit in flight does not use and their transfer into the other device
@@ -921,10 +591,10 @@ int bf_batch_stage_inputs(bf_batch *b, const float *keypoints, const int32_t *n_
         for (int f = 0; f < b->F; ++f)
             if (n_use_frames[f] <= 0) return fail(BF_ERR_INVALID, "bf_batch_stage_inputs: n_use_frames must be positive");
     HIP_TRY(hipSetDevice(b->m->device));
-    if (b->n_lanes > 1) return stage_lane(b, keypoints, n_use_frames, init_betas, init_pose);
-    const int k = b->in_cur ^ 1;
+    if (bf_lanes_enabled(b)) return bf_lanes_stage(b, keypoints, n_use_frames, init_betas, init_pose);
+    const int k = b->in_at.arena ^ 1;
     InputArena &in = b->in[k];
-    BF_TRY(pack_staging(b, in.host, in.ev, in.pending, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: behind a fit that has long finished)
+    BF_TRY(bf_pack_staging(b, in.host, in.ev, in.pending, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: behind a fit that has long finished)
     if (b->stage_zerocopy) {
         // zero-copy: the fit kernel's prologue reads the pinned buffer itself; bf_fit records in.ev behind the fit that read it
         bf_use_inputs(b, k, true);
@@ -942,79 +612,13 @@ int bf_batch_stage_inputs(bf_batch *b, const float *keypoints, const int32_t *n_
     const hipStream_t stream = aside ? b->copy_stream : b->stream;
     b->in_aside[k] = false;
     if (!aside) BF_TRY(bf_flush_tail(b));
-    BF_TRY(publish(stream, in.dev.p, in.host, b->in_total));
+    BF_TRY(bf_publish(stream, in.dev.p, in.host, b->in_total));
     HIP_TRY(hipEventRecord(in.ev, stream));
     in.pending = true;
     b->in_aside[k] = aside;
     bf_use_inputs(b, k, false);
     b->staged = true;
     return aside ? bf_flush_tail(b) : BF_OK;
-}
-
-// input arena `a` of lane l is opened for a new group.  Its pinned buffer may still be read by the transfer of the group it held - issued
-// two of this lane's groups ago, behind fits that have normally long finished: the host waits only if that transfer has not completed
-// (the back-pressure of a feeder that runs ahead of the device)
-static int lane_open(bf_batch *b, BfLane &l, bool host_fed) {
-    l.open = true;
-    l.open_a = l.in_next;
-    l.in_next ^= 1;
-    l.open_host = host_fed;
-    LaneInputs &in = l.in[l.open_a];
-    if (host_fed && in.pending) {
-        if (hipEventQuery(in.ev) != hipSuccess) {
-            (void)hipGetLastError();
-            HIP_TRY(hipEventSynchronize(in.ev));
-            b->feed_waits += 1;
-        }
-        in.pending = false;
-    }
-    return BF_OK;
-}
-
-static int stage_lane(bf_batch *b, const float *keypoints, const int32_t *n_use_frames, const float *init_betas, const float *init_pose) {
-    BF_TRY(lanes_engage(b));
-    if (b->lane_w > 1) {
-        // Host-fed groups: NO GPU work here.  The call's inputs are packed into slot n_open of the open arena's pinned buffer - a second
-        // staging before a fit rewrites the same slot - and the views point at the slot's place on the device, which the group's one
-        // transfer fills when the group is launched (lane_launch; every drain comes through there, so whoever reads the views on the
-        // device finds them filled).  Until then the pinned slot is the only valid copy: in_pinned.
-        if (b->lanes[b->lane_next].n_open && !b->lanes[b->lane_next].open_host) BF_TRY(lane_launch(b, b->lane_next));   // (a device-fed group: it goes out first)
-        const int j = b->lane_next;
-        BfLane &l = b->lanes[j];
-        BF_TRY(lane_begin(b, l));
-        if (!l.open) BF_TRY(lane_open(b, l, true));
-        bf_pack_slot(b->gin, l.in[l.open_a].host, l.n_open, init_map(b->m), b->F, b->V, keypoints, n_use_frames, init_betas, init_pose);
-        bf_use_lane_inputs(b, j, l.open_a, l.n_open);
-        b->in_pinned = true;
-        l.slot_staged = true;
-        b->staged = true;
-        return BF_OK;
-    }
-    // W = 1, a launch per call: the slot is the arena, filled by a transfer of its own at once (the call sequence before groups)
-    const int j = b->lane_next;             // (the lane the next frame-after-frame fit joins)
-    BfLane &l = b->lanes[j];
-    BF_TRY(lane_begin(b, l));
-    if (!l.n_open) {                        // no call has joined: a group on the lane's other arena (a staging after a staging: no wait for the first one's transfer)
-        l.open = true;
-        l.open_a = l.in_next;
-        l.in_next ^= 1;
-    }
-    const int a = l.open_a;
-    LaneInputs &in = l.in[a];
-    BF_TRY(pack_staging(b, in.host, in.ev, in.pending, keypoints, n_use_frames, init_betas, init_pose));      // (its last transfer: queued two of this lane's groups ago)
-    // what read arena a since it was last filled: this lane's fits are ahead in its stream; another lane's fit that read it in place (a
-    // call without a staging of its own) is waited for through that lane's event
-    for (int r = 0; r < b->n_lanes; ++r)
-        if (r != j && ((in.readers >> r) & 1u)) HIP_TRY(hipStreamWaitEvent(l.stream, b->lanes[r].arena.ev_copied, 0));
-    in.readers = 0;
-    BF_TRY(publish(l.stream, in.dev.p, in.host, b->in_total));
-    HIP_TRY(hipEventRecord(in.ev, l.stream));
-    in.pending = true;
-    b->feed_transfers += 1;
-    bf_use_lane_inputs(b, j, a, 0);
-    l.slot_staged = true;
-    b->staged = true;
-    return BF_OK;
 }
 
 int bf_batch_set_init(bf_batch *b, const float *init_betas, const float *init_pose) {
@@ -1046,6 +650,32 @@ int bf_batch_get_params(bf_batch *b, float *params) {
 }
 
 }  // extern "C"
+FrameIO bf_frame_io(bf_batch *b, bool want_grads) {
+    FrameIO io;
+    io.n_frames = b->F; io.n_views = b->V;
+    io.proj = b->proj.p; io.keypoints = b->keypoints.p; io.ndiv = b->ndiv.p;
+    io.params = b->params.p; io.params0 = nullptr; io.adam_m = b->adam_m.p; io.adam_v = b->adam_v.p;
+    io.grads = want_grads ? b->grads.p : nullptr;
+    io.terms = b->terms.p; io.state = b->state.p;
+    io.debug = b->debug.p;
+    io.cscale = b->cscale.p;          // null unless scans are attached
+    io.ext = nullptr;
+    io.image_out = nullptr;
+    io.door = nullptr;
+    io.door_resident = nullptr;
+    return io;
+}
+
+// full_pose[F, 3 nj] out of the F state rows a fit left at `state` (host memory)
+static void full_pose_of(const bf_batch *b, const float *state, float *full_pose) {
+    const bf_model *m = b->m;
+    const size_t stride = bf_state_stride(m->nj, m->npf, m->nb);
+    for (int f = 0; f < b->F; ++f) {
+        StateView v = bf_state_view(const_cast<float *>(state) + (size_t)f * stride, m->nj, m->npf, m->nb);
+        std::memcpy(full_pose + (size_t)f * 3 * m->nj, v.theta, sizeof(float) * 3 * m->nj);
+    }
+}
+
 HyperDev bf_to_dev(const bf_hyper &h) {
     HyperDev d;
     d.sigma2 = h.sigma * h.sigma;
@@ -1085,22 +715,6 @@ static int ensure_adam_tab(bf_batch *b, const bf_hyper &h, int upto) {
     return BF_OK;
 }
 
-static FrameIO bf_frame_io(bf_batch *b, bool want_grads) {
-    FrameIO io;
-    io.n_frames = b->F; io.n_views = b->V;
-    io.proj = b->proj.p; io.keypoints = b->keypoints.p; io.ndiv = b->ndiv.p;
-    io.params = b->params.p; io.params0 = nullptr; io.adam_m = b->adam_m.p; io.adam_v = b->adam_v.p;
-    io.grads = want_grads ? b->grads.p : nullptr;
-    io.terms = b->terms.p; io.state = b->state.p;
-    io.debug = b->debug.p;
-    io.cscale = b->cscale.p;          // null unless scans are attached
-    io.ext = nullptr;
-    io.image_out = nullptr;
-    io.door = nullptr;
-    io.door_resident = nullptr;
-    return io;
-}
-
 // floats of a result arena a fetch hands over: [params | terms | state | joints] and, when they were built, the vertices
 static size_t result_floats(const bf_batch *b, bool with_v) { return with_v ? b->res_total : b->res_small; }
 
@@ -1124,8 +738,9 @@ struct FitCall {
     int n_iters;
     FitRoute route;
 };
-// what the routes leave differently: the result is in the pinned mirror, it has vertices, the call's timing events were recorded
-struct FitDone { bool fetched, has_v, timed; };
+// what the routes leave differently: the result is in the pinned mirror, it has vertices, the call's timing events were recorded, the call
+// is in a fit lane's group (the lane holds its result)
+struct FitDone { bool fetched, has_v, timed, on_lane = false; };
 
 static FitCall fit_plan(const bf_batch *b, int n_iters, uint32_t flags) {
     FitCall c;
@@ -1141,7 +756,7 @@ static FitCall fit_plan(const bf_batch *b, int n_iters, uint32_t flags) {
     // next call's fit kernel; the two result arenas alternate as in the pipelined fetch.  With fit lanes such a call goes to the next
     // lane instead; every other call first finds the last fit in the batch's own buffers (bf_lanes_drain).
     const bool tail_aside = (flags & BF_FIT_NOTIME) && !(flags & BF_FIT_GRAPH) && c.reset && sparse && c.fetch && c.want_v;
-    if (tail_aside && b->n_lanes > 1) c.route = FitRoute::LANE;
+    if (tail_aside && bf_lanes_enabled(b)) c.route = FitRoute::LANE;
     else if ((flags & BF_FIT_GRAPH) && c.reset && sparse) c.route = (c.fetch && c.big_fetch) ? FitRoute::GRAPH_PIPELINED : FitRoute::GRAPH;
     else if (tail_aside) c.route = b->F >= b->n_cus ? FitRoute::TAIL_ASIDE_CROWDED : FitRoute::TAIL_ASIDE;
     else if ((flags & BF_FIT_NOTIME) && sparse) c.route = FitRoute::UNTIMED;
@@ -1181,87 +796,10 @@ static int ensure_graph(bf_batch *b, hipGraphExec_t &exec, bf_graph_key &exec_ke
     return BF_OK;
 }
 
-// LANE: the call joins the open group of the next lane - its inputs are in the group's next slot: staged there, or copied from the
-// batch's current inputs now, on the host where their pinned copy is valid and on the device otherwise - and the group is launched if
-// its lane is idle or it is full (lane_launch).  A group is host-fed or device-fed, never both: a call of the other kind launches the
-// open group first, as a call with other iterations or hyper-parameters does.
+// LANE: the call joins the open group of the next lane, which goes out when lanes.hip's rules say so
 static int fit_lane(bf_batch *b, const FitCall &c, const HyperDev &hd, FitDone &done) {
-    BF_TRY(lanes_engage(b));
-    const int W = b->lane_w;
-    {
-        // one launch, one n_iters, one set of hyper-parameters and one way of feeding: a call that differs starts a group of its own
-        BfLane &o = b->lanes[b->lane_next];
-        const bool host_fed = o.slot_staged || b->in_pinned;
-        if (o.n_open && (o.open_iters != c.n_iters || std::memcmp(&o.open_hd, &hd, sizeof hd) != 0 || (W > 1 && o.open_host != host_fed)))
-            BF_TRY(lane_launch(b, b->lane_next));
-    }
-    const int j = b->lane_next;
-    BfLane &l = b->lanes[j];
-    BF_TRY(lane_begin(b, l));
-    b->fetched = false; b->have_result = false;                 // (a failure from here on: nothing of this call may be read)
-    const int slot = l.n_open;
-    // the feed, for the idle rule below: ONE clock read per call
-    const auto now = std::chrono::steady_clock::now();
-    const std::chrono::microseconds H = fit_lane_hold();
-    const bool fast_feed = b->lane_called && now - b->lane_t_call < H;
-    b->lane_t_call = now; b->lane_called = true;
-    if (slot == 0) { l.open_seq0 = b->fit_seq; l.open_iters = c.n_iters; l.open_hd = hd; l.borrowed = false; l.t_first = now; }
-    if (!l.slot_staged && W == 1) {
-        // a launch per call: the fit reads the current inputs in place.  Another lane's slot is read without a wait for its transfer,
-        // as before groups (width 1 is that call sequence): the transfer went out on its lane ahead of a fit launch that has since
-        // been issued
-        l.borrowed = true;
-        l.bor_kp = b->keypoints.p; l.bor_p0 = b->params0.p; l.bor_ndiv = b->ndiv.p;
-        if (b->in_cur >= 2) current_lane_inputs(b).readers |= 1u << j;
-    } else if (!l.slot_staged && b->in_pinned) {
-        // No staging of its own, and the pinned mirror of the slot the views are on holds the current inputs (the usual re-fit): copied
-        // on the host into this group's next slot - no device copy, no event - and the views move there.
-        // INVARIANT: the source is the previous call's slot at the latest (every host-fed call leaves the views on its own slot), so its
-        // arena belongs to the newest group of its lane or to the open one, and a pinned arena is rewritten only when its lane opens it
-        // again two groups later - which takes calls that would have moved the views on.  The source is never the slot written here.
-        if (!l.open) BF_TRY(lane_open(b, l, true));
-        const LaneInputs &src = current_lane_inputs(b);
-        LaneInputs &dst = l.in[l.open_a];
-        assert(!(&src == &dst && b->in_slot == slot) && "a re-fit's pinned source is the previous call's slot, never the one it joins");
-        bf_copy_slot(b->gin, dst.host, slot, src.host, b->in_slot);
-        bf_use_lane_inputs(b, j, l.open_a, slot);
-        b->in_pinned = true;
-        b->feed_host_copies += 1;
-    } else if (!l.slot_staged) {
-        // no staging of its own, the current inputs in device memory only (after a synchronous setter, a device-side producer, a drain):
-        // whatever keypoints / params0 / ndiv point at, copied on the lane's stream.  A lane slot they point at was filled before the
-        // drain that left them there: nothing to wait for; its arena's next transfer waits for this copy (`readers`).
-        if (!l.open) BF_TRY(lane_open(b, l, false));
-        const SlotPlace at = slot_place(b, l.in[l.open_a], slot);
-        if (at.kp != b->keypoints.p) {                          // (else they are this very slot's)
-            if (b->in_cur >= 2 && (b->in_cur - 2) / 2 != j) current_lane_inputs(b).readers |= 1u << j;
-            BF_TRY(publish3(l.stream, BfSeg3{{b->keypoints.p, b->params0.p, (const float *)b->ndiv.p}, {at.kp, at.p0, (float *)at.ndiv},
-                                             {(unsigned)b->keypoints.n, (unsigned)b->params0.n, (unsigned)b->ndiv.n}}));
-            HIP_TRY(hipEventRecord(l.ev_join, l.stream));
-            b->feed_dev_copies += 1;
-        }
-    }
-    l.open = true; l.slot_staged = false;
-    l.n_open = slot + 1;
-    b->lane_last = j;
-    b->lane_calls += 1;
-    done = {true, true, false};
-    if (l.n_open >= W) return lane_launch(b, j);                // full: behind the lane's running group, in stream order
-    if (!fit_lane_fill()) {
-        // The lane is idle: now - a slow feeder waits for nobody, and a fast feeder's first call after a pause goes out alone - UNLESS the
-        // feeder is fast (the call before this one came less than H ago) and the group is young (its first call joined less than H ago).
-        // Then it is held exactly as a group behind a busy lane is: a burst fills groups instead of sending its first calls out one by
-        // one, each a whole launch sequence and a lane cycle for one frame.  The group goes out when it is full, at the first call that
-        // finds the feeder slow or the group H old, and at every read, drain, sync or destroy - H bounds what the rule adds to a burst's
-        // frames.  W = 1 and H = 0: the idle rule alone.
-        const bool hold = W > 1 && fast_feed && now - l.t_first < H;
-        if (!hold) {
-            const hipError_t q = hipEventQuery(l.arena.ev_copied);
-            if (q == hipSuccess) return lane_launch(b, j);
-            (void)hipGetLastError();
-            if (q != hipErrorNotReady) HIP_TRY(q);
-        }
-    }
+    BF_TRY(bf_lanes_fit(b, c.n_iters, hd));
+    done = {true, true, false, true};
     return BF_OK;
 }
 
@@ -1277,7 +815,8 @@ static int graph_grow_scratch(bf_batch *b, const FitCall &c) {
 
 // both graph routes: the graph of call `c` into result arena k (the current one), captured if need be, launched between the timing events
 static int graph_replay(bf_batch *b, const FitCall &c, const bf_hyper &h, const HyperDev &hd, int k, hipGraphExec_t &exec, bf_graph_key &exec_key) {
-    const bf_graph_key key{c.n_iters, c.flags, k | (b->in_cur << 4) | ((int)b->in_host << 12) | (b->in_slot << 16), h};   // (the captured nodes hold the arenas' addresses)
+    const InputCursor &at = b->in_at;
+    const bf_graph_key key{c.n_iters, c.flags, k | (at.arena << 4) | (at.lane << 5) | ((int)at.on_lane << 10) | ((int)at.host << 12) | (at.slot << 16), h};   // (the captured nodes hold the arenas' addresses)
     BF_TRY(ensure_graph(b, exec, exec_key, key, c, hd));
     HIP_TRY(hipEventRecord(b->ev[0], b->stream));
     HIP_TRY(hipGraphLaunch(exec, b->stream));
@@ -1307,7 +846,7 @@ static int fit_graph_pipelined(bf_batch *b, const FitCall &c, const bf_hyper &h,
     kernels.fetch = false;
     BF_TRY(graph_replay(b, kernels, h, hd, k, b->graph_pipe[k], b->graph_pipe_key[k]));
     HIP_TRY(hipEventRecord(r.ev_done, b->stream));
-    BF_TRY(enqueue_tail(b, r, b->copy_stream, &b->scratch, b->vraw.p, b->xpart.p, result_floats(b, c.want_v), true, r.ev_done, false));
+    BF_TRY(enqueue_tail(b, r, result_floats(b, c.want_v), true, r.ev_done, false));
     r.copy_pending = true;
     done = {true, c.want_v, true};
     return BF_OK;
@@ -1351,7 +890,7 @@ static int fit_tail_aside_crowded(bf_batch *b, const FitCall &c, const HyperDev 
     ResultArena &r = b->arena[b->cur];
     BF_TRY(result_mesh(b));
     HIP_TRY(hipEventRecord(r.ev_done, b->stream));
-    BF_TRY(enqueue_tail(b, r, b->copy_stream, &b->scratch, b->vraw.p, b->xpart.p, b->res_total, c.big_fetch, r.ev_done, false));
+    BF_TRY(enqueue_tail(b, r, b->res_total, c.big_fetch, r.ev_done, false));
     r.copy_pending = true;
     done = {true, true, false};
     return BF_OK;
@@ -1405,7 +944,8 @@ static int fit_timed_reference_literal(bf_batch *b, const FitCall &c, const Hype
     return BF_OK;
 }
 
-static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
+// `done`: what the call's route left (the batch's own bookkeeping is done here)
+static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags, FitDone &done) {
     HIP_TRY(hipSetDevice(b->m->device));
     bf_hyper h;
     if (hyper) h = *hyper; else bf_hyper_default(&h);
@@ -1423,7 +963,6 @@ static int fit_impl(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t fl
     const bool other_arena = c.route == FitRoute::LANE || c.route == FitRoute::GRAPH_PIPELINED || c.route == FitRoute::TAIL_ASIDE ||
                              c.route == FitRoute::TAIL_ASIDE_CROWDED;
     if (!other_arena) BF_TRY(bf_guard_arena(b));
-    FitDone done{};
     switch (c.route) {
     case FitRoute::LANE:                    BF_TRY(fit_lane(b, c, hd, done)); break;
     case FitRoute::GRAPH:                   BF_TRY(fit_graph(b, c, h, hd, done)); break;
@@ -1452,29 +991,29 @@ int bf_fit(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
         return fail(BF_ERR_INVALID, "bf_fit: inputs were staged with bf_batch_stage_inputs - the fit of a new frame starts from its initial estimate (BF_FIT_RESET)");
     bf_masks_commit(b);                       // (silhouettes staged with bf_batch_stage_masks become this fit's)
     BF_TRY(bf_flush_tail(b));
-    if (b->in_cur < 2 && b->in_aside[b->in_cur]) {
+    if (!b->in_at.on_lane && b->in_aside[b->in_at.arena]) {
         // inputs staged aside: their transfer was queued on the second stream a few microseconds ago and runs under the fit in flight.
         // Waiting for it HERE, on the host, keeps a wait packet out of the batch stream (the fit in flight has hundreds of
         // microseconds to go); only if it does not show up in time does the stream wait for it.
-        const hipEvent_t staged = b->in[b->in_cur].ev;
+        const hipEvent_t staged = b->in[b->in_at.arena].ev;
         hipError_t q = hipErrorNotReady;
         const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(500);
         while ((q = hipEventQuery(staged)) == hipErrorNotReady && std::chrono::steady_clock::now() < t_end) { }
         if (q == hipErrorNotReady) HIP_TRY(hipStreamWaitEvent(b->stream, staged, 0));
         else HIP_TRY(q);
-        b->in_aside[b->in_cur] = false;
+        b->in_aside[b->in_at.arena] = false;
     }
-    BF_TRY(fit_impl(b, n_iters, hyper, flags));
+    FitDone done{};
+    BF_TRY(fit_impl(b, n_iters, hyper, flags, done));
     b->staged = false;
-    // (went to a lane - every other call drains the lanes first, which clears lane_last: the call's number is its place in its group)
-    if (b->lane_last >= 0) { b->fit_seq++; return BF_OK; }
+    if (done.on_lane) { b->fit_seq++; return BF_OK; }          // (the call's number is its place in its group)
     ResultArena &r = b->arena[b->cur];
-    if (b->in_cur < 2) b->in_reader[b->in_cur] = b->fit_seq;       // (this fit's number, given to its arena below)
+    if (!b->in_at.on_lane) b->in_reader[b->in_at.arena] = b->fit_seq;       // (this fit's number, given to its arena below)
     if (b->has_masks) {                       // (the arena these masks live in may be overwritten once this fit is done)
         if (!b->ev_masks_used) HIP_TRY(hipEventCreateWithFlags(&b->ev_masks_used, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(b->ev_masks_used, b->stream));
     }
-    if (b->in_host) { HIP_TRY(hipEventRecord(b->in[b->in_cur].ev, b->stream)); b->in[b->in_cur].pending = true; }   // (zero-copy: this fit read the pinned buffer)
+    if (b->in_at.host) { HIP_TRY(hipEventRecord(b->in[b->in_at.arena].ev, b->stream)); b->in[b->in_at.arena].pending = true; }   // (zero-copy: this fit read the pinned buffer)
     r.seq = b->fit_seq++;
     r.fetched = b->fetched;
     r.has_v = b->have_result;
@@ -1554,37 +1093,29 @@ int bf_batch_get_previous(bf_batch *b, float *params, float *vertices, float *jo
     const bf_model *m = b->m;
     HIP_TRY(hipSetDevice(m->device));
     const long long want = b->fit_seq - 2;
-    // with fit lanes the fit before the last may be held by a lane (which keeps its group until that lane's next launch) - in a
-    // launched group, or in the open one, which then goes out now: slot `slot` of lane `lane`
-    int lane = -1, slot = 0;
-    for (int j = 0; b->lanes && want >= 0 && j < b->n_lanes; ++j) {
-        BfLane &l = b->lanes[j];
-        if (l.n_open && want >= l.open_seq0 && want < l.open_seq0 + l.n_open) BF_TRY(lane_launch(b, j));
-        if (l.held.G && want >= l.held.seq0 && want < l.held.seq0 + l.held.G) { lane = j; slot = (int)(want - l.held.seq0); }
+    // with fit lanes the fit before the last may be held by a lane, which keeps its group until its next launch (bf_lanes_find); else by a
+    // batch arena - while a lane holds the last fit, the current one, which then holds the fit before it if that was not a lane fit
+    BfLaneResult at;
+    BF_TRY(bf_lanes_find(b, want, at));
+    const bool on_lane = at.arena != nullptr, last_on_lane = bf_lanes_hold_last(b);
+    if (!on_lane) {
+        at.arena = &b->arena[last_on_lane ? b->cur : b->cur ^ 1];
+        std::copy(b->res_off, b->res_off + 5, at.off);
     }
-    // (while a lane holds the last fit, the batch's current arena holds the fit before it, if that was not a lane fit)
-    const ResultArena &r = lane >= 0 ? b->lanes[lane].arena : b->arena[b->lane_last >= 0 ? b->cur : b->cur ^ 1];
-    const bool held = lane >= 0 || (r.seq == want && r.fetched), last_held = b->lane_last >= 0 || b->arena[b->cur].seq == b->fit_seq - 1;
-    if (b->fit_seq < 2 || !held || !last_held)
+    const ResultArena &r = *at.arena;
+    const bool have_it = on_lane || (r.seq == want && r.fetched), have_last = last_on_lane || b->arena[b->cur].seq == b->fit_seq - 1;
+    if (b->fit_seq < 2 || !have_it || !have_last)
         return fail(BF_ERR_INVALID, "bf_batch_get_previous: the previous fit's result is not held in the other arena (both fits need "
                                     "BF_FIT_RESET | BF_FIT_FETCH | BF_FIT_NOTIME on the keypoint-only path)");
-    if ((vertices || joints) && lane < 0 && !r.has_v) return fail(BF_ERR_INVALID, "bf_batch_get_previous: no mesh was evaluated");
+    if ((vertices || joints) && !r.has_v) return fail(BF_ERR_INVALID, "bf_batch_get_previous: no mesh was evaluated");       // (a lane's group always has its mesh)
     BF_TRY(bf_flush_tail(b));
     HIP_TRY(hipEventSynchronize(r.ev_copied));          // (only that result's hand-over: a lane's group, never the stream)
-    size_t off[5];
-    for (int i = 0; i < 5; ++i) off[i] = lane >= 0 ? b->lanes[lane].held.off[i] + (size_t)slot * b->res_cnt[i] : b->res_off[i];
     const float *h = r.host;
-    if (params) std::memcpy(params, h + off[0], b->res_cnt[0] * sizeof(float));
-    if (loss_terms) std::memcpy(loss_terms, h + off[1], b->res_cnt[1] * sizeof(float));
-    if (joints) std::memcpy(joints, h + off[3], b->res_cnt[3] * sizeof(float));
-    if (vertices) std::memcpy(vertices, h + off[4], b->res_cnt[4] * sizeof(float));
-    if (full_pose) {
-        const size_t stride = bf_state_stride(m->nj, m->npf, m->nb);
-        for (int f = 0; f < b->F; ++f) {
-            StateView v = bf_state_view(const_cast<float *>(h) + off[2] + (size_t)f * stride, m->nj, m->npf, m->nb);
-            std::memcpy(full_pose + (size_t)f * 3 * m->nj, v.theta, sizeof(float) * 3 * m->nj);
-        }
-    }
+    if (params) std::memcpy(params, h + at.off[0], b->res_cnt[0] * sizeof(float));
+    if (loss_terms) std::memcpy(loss_terms, h + at.off[1], b->res_cnt[1] * sizeof(float));
+    if (joints) std::memcpy(joints, h + at.off[3], b->res_cnt[3] * sizeof(float));
+    if (vertices) std::memcpy(vertices, h + at.off[4], b->res_cnt[4] * sizeof(float));
+    if (full_pose) full_pose_of(b, h + at.off[2], full_pose);
     return BF_OK;
 }
 
@@ -1605,13 +1136,11 @@ int bf_batch_get_result(bf_batch *b, float *vertices, float *joints, float *full
         if (loss_terms) HIP_TRY(hipMemcpy(loss_terms, b->terms.p, b->terms.n * sizeof(float), hipMemcpyDeviceToHost));
     }
     if (full_pose) {
-        const size_t stride = bf_state_stride(m->nj, m->npf, m->nb);
-        std::vector<float> st((size_t)b->F * stride);
-        if (b->fetched) std::memcpy(st.data(), b->h_state, st.size() * sizeof(float));
-        else HIP_TRY(hipMemcpy(st.data(), b->state.p, st.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (int f = 0; f < b->F; ++f) {
-            StateView v = bf_state_view(st.data() + (size_t)f * stride, m->nj, m->npf, m->nb);
-            std::memcpy(full_pose + (size_t)f * 3 * m->nj, v.theta, sizeof(float) * 3 * m->nj);
+        if (b->fetched) full_pose_of(b, b->h_state, full_pose);
+        else {
+            std::vector<float> st(b->state.n);
+            HIP_TRY(hipMemcpy(st.data(), b->state.p, st.size() * sizeof(float), hipMemcpyDeviceToHost));
+            full_pose_of(b, st.data(), full_pose);
         }
     }
     return BF_OK;
@@ -1689,21 +1218,6 @@ int bf_batch_mesh_span(bf_batch *b, int reps, float us[3]) {
         sum += t; lo = std::min(lo, t); hi = std::max(hi, t);
     }
     us[0] = (float)(sum / reps); us[1] = (float)lo; us[2] = (float)hi;
-    return BF_OK;
-}
-
-/* test hook: fit-lane groups since the batch was created - out[0] lane launches, out[1] lane calls, out[2] the largest group, out[3] W */
-int bf_batch_lane_stats(bf_batch *b, int32_t out[4]) {
-    if (!b || !out) return fail(BF_ERR_INVALID, "bf_batch_lane_stats: null argument");
-    out[0] = b->lane_launches; out[1] = b->lane_calls; out[2] = b->lane_max_g; out[3] = b->n_lanes > 1 ? b->lane_w : 1;
-    return BF_OK;
-}
-
-/* test hook: how the fit lanes were fed - out[0] input transfers, out[1] host-side slot copies, out[2] device-side slot copies, out[3] host
- * waits on a pinned arena */
-int bf_batch_lane_feed_stats(bf_batch *b, int64_t out[4]) {
-    if (!b || !out) return fail(BF_ERR_INVALID, "bf_batch_lane_feed_stats: null argument");
-    out[0] = b->feed_transfers; out[1] = b->feed_host_copies; out[2] = b->feed_dev_copies; out[3] = b->feed_waits;
     return BF_OK;
 }
 

@@ -1,4 +1,4 @@
-// Host-side private definitions shared by the host files (*_api.hip, api.hip, group.hip).
+// Host-side private definitions shared by the host files (*_api.hip, api.hip, lanes.hip, group.hip).
 #pragma once
 #include "../../include/bodyfit.h"
 #include "bf_internal.h"
@@ -226,12 +226,19 @@ struct ResultArena {
 // transfer on a stream of its owner.  Two per batch and two per fit lane: the next frame's inputs are packed into the staging buffer
 // the fit in flight does not read - the setter never drains a stream (the reference pays 48 keypoint host-to-device copies per
 // ITERATION, loss.py:160).
+// A fit lane's arena holds the device arrays of up to W calls' frames, array-major like FrameIO ([W F] keypoints | [W F] params0 |
+// [W F] ndiv: BfLanes::gin, lane_slots.h), and its pinned buffer has the same layout - slot s of the one mirrors slot s of the other,
+// array by array.  A staging packs into the pinned slot and issues nothing; when the group is launched, one transfer on the lane's stream
+// moves the prefix of slots that were filled (three contiguous ranges) and `ev` is recorded behind it.  The arena is opened again two of
+// its lane's groups later: whoever opens it waits for `ev` on the host if that transfer has not finished.  W = 1 is the batch's own
+// layout: one slot, filled by a transfer of its own at every staging (the call sequence before groups).
 struct InputArena {
     DevBuf<float> dev;
-    float *host = nullptr;
-    hipEvent_t ev = nullptr;        // the transfer out of `host` has finished
+    float *host = nullptr;          // the device arena's layout
+    hipEvent_t ev = nullptr;        // the last transfer out of `host` has finished
     bool pending = false;           // ... and has not been waited for yet
-    unsigned readers = 0;           // a lane's arena: the lanes whose fits read it since it was last filled (bit per lane)
+    unsigned readers = 0;           // a lane's arena: the lanes that read the device arrays from outside since they were last filled (bit per lane) -
+                                    // W = 1 a fit that read the slot in place, W > 1 a device-side copy of a slot; the next transfer waits for them
     InputArena() = default;
     InputArena(const InputArena &) = delete;
     hipError_t create(size_t n_floats) {
@@ -291,32 +298,7 @@ struct bf_model {
 
 struct bf_graph_key { int n_iters; uint32_t flags; int arena; bf_hyper h; };     // (arena: the result arena its nodes point at)
 
-// A fit lane's input arena: the device arrays of up to W calls' frames, array-major like FrameIO ([W F] keypoints | [W F] params0 |
-// [W F] ndiv: bf_batch::gin, lane_slots.h), and ONE pinned buffer of the same layout - slot s of the pinned buffer mirrors slot s of the
-// device arrays, array by array.  A staging packs into the pinned slot and issues nothing; when the group is launched, one transfer on
-// the lane's stream moves the prefix of slots that were filled (three contiguous ranges) and `ev` is recorded behind it.  The arena is
-// opened again two of its lane's groups later: whoever opens it waits for `ev` on the host if that transfer has not finished.
-// W = 1 is the batch's own layout: one slot, filled by a transfer of its own at every staging (the call sequence before groups).
-struct LaneInputs {
-    DevBuf<float> dev;
-    float *host = nullptr;          // [gin.total], the device arena's layout
-    hipEvent_t ev = nullptr;        // the last transfer out of `host` has finished
-    bool pending = false;           // ... and has not been waited for yet
-    unsigned readers = 0;           // the lanes that read the device arrays from outside since they were last filled (bit per lane): W = 1 a fit
-                                    // that read the slot in place, W > 1 a device-side copy of a slot - the next transfer waits for them
-    LaneInputs() = default;
-    LaneInputs(const LaneInputs &) = delete;
-    hipError_t create(size_t n_floats) {
-        hipError_t e = bf_alloc_mirrored(dev, &host, n_floats);
-        return e == hipSuccess ? hipEventCreateWithFlags(&ev, hipEventDisableTiming) : e;
-    }
-    ~LaneInputs() {
-        if (ev) (void)hipEventDestroy(ev);
-        if (host) (void)hipHostFree(host);
-    }
-};
-
-// A fit lane (BF_FIT_LANES, api.hip): everything a frame-after-frame fit (RESET | FETCH | NOTIME, keypoint-only) and its tail write,
+// A fit lane (BF_FIT_LANES, lanes.hip): everything a frame-after-frame fit (RESET | FETCH | NOTIME, keypoint-only) and its tail write,
 // on a stream of its own, so that consecutive frames' fits run side by side on different CUs.  Successive groups go to successive lanes;
 // nothing orders one lane behind another but HIP events.
 // A lane launch carries a GROUP of up to W consecutive calls' frames (BF_FIT_LANE_WIDTH): the calls join the lane's open group, slot
@@ -327,9 +309,9 @@ struct BfLane {
     MeshScratch scratch;            // the tail's MFMA mesh path, on this lane's stream only
     DevBuf<float> adam_m, adam_v, vraw, xpart;
     ResultArena arena;              // (its mirror is filled by the tail's hand-over)
-    LaneInputs in[2];               // fed on this lane's stream
+    InputArena in[2];               // fed on this lane's stream
     int in_next = 0;                            // arena the next group of this lane fills
-    bool need_engage = false;                   // the stream has yet to wait for the batch stream (bf_batch::ev_engage)
+    bool need_engage = false;                   // the stream has yet to wait for the batch stream (BfLanes::ev_engage)
     bool busy = false;                          // work was enqueued since the lanes were last drained
     hipEvent_t ev_join = nullptr;               // (W > 1) the lane's last device-side copy of current inputs into a slot has finished
     // the open group: calls that joined and wait for their launch
@@ -350,6 +332,35 @@ struct BfLane {
     ~BfLane() { if (ev_join) (void)hipEventDestroy(ev_join); }
 };
 
+// The fit lanes of a batch (lanes.hip; the rest of the library goes through lanes.h): n > 1 gives frame-after-frame fits lanes of their
+// own, created on first use.  `on`: lane work may be in flight or a lane holds the newest fit - every entry point that is not a lane fit or
+// a staging drains the lanes first (bf_lanes_drain), which hands the last lane fit back to the batch's own buffers.
+struct BfLanes {
+    int n = 1;                          // lanes = min(BF_FIT_LANES, CUs / frames) (lane_policy.h)
+    int W = 1;                          // calls per lane launch at most = min(BF_FIT_LANE_WIDTH, CUs / (lanes x frames))
+    BfLaneLayout gin;                   // a lane's input arena: its [W F] keypoints, params0, ndiv arrays (lane_slots.h)
+    std::unique_ptr<BfLane[]> lane;
+    bool on = false;
+    int next = 0, last = -1;            // the lane the next call joins; the lane whose newest group (open or launched) ends with the last lane fit
+    DevBuf<float> proj_rep;             // (W > 1) the projection table W times over: FrameIO::proj of a group launch
+    bool proj_rep_stale = true;         // ... has yet to be copied from `proj` (new cameras)
+    hipEvent_t ev_engage = nullptr;     // recorded on the batch stream when the lanes take over: every lane stream waits for it
+    bool called = false;                // a LANE-route call has been issued on this batch,
+    std::chrono::steady_clock::time_point t_call{};             // ... the last one then: the feeder is fast while calls follow within H (bf_lanes_fit)
+    int launches = 0, calls = 0, max_g = 0;                     // bf_batch_lane_stats
+    long long feed_transfers = 0, feed_host_copies = 0, feed_dev_copies = 0, feed_waits = 0;    // bf_batch_lane_feed_stats
+};
+
+// Where the current inputs live - what `keypoints`, `params0`, `ndiv` of a batch are views of.  Set together with the views, by
+// bf_set_inputs alone.
+struct InputCursor {
+    bool on_lane = false;           // input arena `arena` of fit lane `lane`; else the batch's own arena `arena`
+    int lane = 0, arena = 0, slot = 0;      // slot: (on_lane) the slot of that lane arena the views are on
+    bool pinned = false;            // (on_lane, W > 1) the pinned mirror of that slot holds the current inputs: a call without a staging of its own
+                                    // copies them on the host.  Cleared by every drain - what follows may write the device slot alone
+    bool host = false;              // the views point at the pinned staging buffer itself (BF_STAGE_MODE=zerocopy)
+};
+
 struct bf_batch {
     bf_model *m = nullptr;
     int F = 0, V = 0;
@@ -363,10 +374,10 @@ struct bf_batch {
     bool timed = false;
     DevBuf<float> params0;          // parameters of the last set_init / set_params / stage_inputs (a view into the current input arena)
     // Per-frame inputs live in TWO input arenas: bf_batch_stage_inputs fills the one the fit in flight does not read and queues its
-    // transfer on the batch stream.  `keypoints`, `ndiv`, `params0` are views into arena in_cur.
+    // transfer on the batch stream.  `keypoints`, `ndiv`, `params0` are views into the arena in_at names (one of these, or a lane's).
     InputArena in[2];
     size_t in_off[3] = {0, 0, 0}, in_total = 0;          // float offsets of keypoints, params0, ndiv inside an arena
-    int in_cur = 0;
+    InputCursor in_at;
     // Staging ASIDE (round 5): the transfer of the next frame's inputs rides on the second stream, AHEAD of the mesh / hand-over tail of
     // the fit in flight - which is why that tail is enqueued late (`tail_k`: at the next entry point, bf_flush_tail) - so that the batch
     // stream holds fit kernel after fit kernel with nothing in between.  in_aside[k]: arena k's transfer is on the second stream and
@@ -377,7 +388,6 @@ struct bf_batch {
     long long tail_seq = -1;
     int tail_k = -1;                // result arena whose tail is still to be enqueued (-1: none)
     bool tail_big = false;
-    bool in_host = false;           // the views point at the pinned staging buffer itself (BF_STAGE_MODE=zerocopy)
     bool stage_zerocopy = false;    // staged inputs stay in pinned memory, the fit kernel's prologue reads them there (no copy kernel, no lanes)
     bool staged = false;            // inputs were staged since the last fit: the next bf_fit must carry BF_FIT_RESET
     long long fit_seq = 0;          // fits issued so far (a result arena's `seq` is one of these numbers)
@@ -466,31 +476,12 @@ struct bf_batch {
     DevBuf<const float *> scan_fn;
     int disp_steps = 0;
     bool have_disp = false;
-    // fit lanes (api.hip, BF_FIT_LANES): n_lanes > 1 gives frame-after-frame fits lanes of their own, created on first use.
-    // lanes_on: lane work may be in flight or a lane holds the newest fit - every other entry point drains the lanes first
-    // (bf_lanes_drain), which hands the last lane fit back to the batch's own buffers.  in_cur >= 2 names input arena
-    // (in_cur - 2) % 2 of lane (in_cur - 2) / 2.
-    int n_lanes = 1;
     int n_cus = 256;                    // compute units of the model's device (bf_batch_create)
-    std::unique_ptr<BfLane[]> lanes;
-    bool lanes_on = false;
-    int lane_next = 0, lane_last = -1;  // the lane the next call joins; the lane whose newest group (open or launched) ends with the last lane fit
-    int lane_w = 1;                     // W: calls per lane launch at most = min(BF_FIT_LANE_WIDTH, CUs / (lanes x frames))
-    BfLaneLayout gin;                   // a lane's input arena: its [W F] keypoints, params0, ndiv arrays (lane_slots.h)
-    int in_slot = 0;                    // (in_cur >= 2) the slot of that lane arena the views are on
-    bool in_pinned = false;             // (in_cur >= 2, W > 1) the pinned mirror of that slot holds the current inputs: a call without a staging of its
-                                        // own copies them on the host.  Cleared by every drain - what follows may write the device slot alone
-    DevBuf<float> proj_rep;             // (W > 1) the projection table W times over: FrameIO::proj of a group launch
-    bool proj_rep_stale = true;         // ... has yet to be copied from `proj` (new cameras)
+    BfLanes lanes;                      // fit lanes (BF_FIT_LANES): lanes.h
     enum class TailHandOver { BY_SIZE, STORE, COPY };
     TailHandOver tail_handover = TailHandOver::BY_SIZE;         // BF_TAIL_HANDOVER (store | copy; unset: by size), read once per batch: whether a tail's
                                         // kernels store into the pinned mirror themselves (MeshPass::mirror) - store: wherever they can; copy: never, the
                                         // hand-over is a launch or a copy command behind them; by size: where that measured faster (tail_stores, api.hip)
-    int lane_launches = 0, lane_calls = 0, lane_max_g = 0;      // bf_batch_lane_stats
-    bool lane_called = false;           // a LANE-route call has been issued on this batch,
-    std::chrono::steady_clock::time_point lane_t_call{};        // ... the last one then: the feeder is fast while calls follow within H (fit_lane)
-    long long feed_transfers = 0, feed_host_copies = 0, feed_dev_copies = 0, feed_waits = 0;    // bf_batch_lane_feed_stats
-    hipEvent_t ev_engage = nullptr;     // recorded on the batch stream when the lanes take over: every lane stream waits for it
 };
 
 struct bf_scan {
@@ -554,6 +545,17 @@ int bf_contours_on_device(const unsigned char *d_bin, int n, int H, int W, int s
 int bf_masks_finalize(bf_batch *b);      // no-op unless a deferred bf_batch_set_masks is pending
 void bf_masks_commit(bf_batch *b);       // no-op unless bf_batch_stage_masks has staged the next frame's silhouettes
 HyperDev bf_to_dev(const bf_hyper &h);
+// the frame loop's pieces that api.hip defines and the fit lanes (lanes.hip) use as well
+FrameIO bf_frame_io(bf_batch *b, bool want_grads);      // the batch's own launch arguments
+int bf_publish(hipStream_t stream, float *dst, const float *src, size_t n_floats);     // a copy by kernel, device arena <-> pinned buffer, whole 256-byte slices
+struct TailOn { hipStream_t stream; MeshScratch *scr; float *vraw, *xpart; };           // the stream a tail runs on and that stream's owner's scratch buffers
+int bf_enqueue_tail(bf_batch *b, ResultArena &r, const size_t off[5], int n_frames, int per, const TailOn &on, size_t n_floats,
+                    bool with_mesh, bool may_store, bool big);
+void bf_use_arena(bf_batch *b, int k);
+void bf_set_inputs(bf_batch *b, const InputCursor &at, float *kp, float *p0, int *ndiv);
+BfInitMap bf_init_map(const bf_model *m);
+int bf_pack_staging(const bf_batch *b, float *h, hipEvent_t ev, bool &pending, const float *keypoints, const int32_t *n_use_frames,
+                    const float *init_betas, const float *init_pose);
 int bf_flush_tail(bf_batch *b);          // enqueue the deferred mesh / hand-over tail of the last frame-after-frame fit (api.hip)
 int bf_sync_all(bf_batch *b);            // lanes, copy stream, then compute stream
 int bf_lanes_drain(bf_batch *b);         // no-op unless fit lanes are on: launch the open group, wait for the lanes, hand the last lane fit back to the batch

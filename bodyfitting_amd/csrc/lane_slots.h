@@ -1,4 +1,4 @@
-// Slot arithmetic and packing of a fit lane's input arena - plain C++, no HIP: api.hip includes it for the device arena and its pinned
+// Slot arithmetic and packing of a fit lane's input arena - plain C++, no HIP: lanes.hip includes it for the device arena and its pinned
 // mirror, tests/lane_pack_main.cpp for a host-only check under the sanitizers.
 //
 // An arena holds the frames of up to W calls, array-major like FrameIO: [W F] keypoints | [W F] params0 | [W F] ndiv, every array on a

@@ -834,7 +834,7 @@ int bf_batch_debug_disp_moment2(bf_batch *b, float *v_out);
 /* vertices[F,NV,3]: the body vertices the last full-model mesh pass of the batch left on the device (after bf_dense_iter_grad
  * without BF_DENSE_GRAD_SUBMODEL: the ones its losses were evaluated at) */
 int bf_batch_debug_vertices(bf_batch *b, float *vertices);
-/* Fit-lane groups of the batch since it was created (api.hip; BF_FIT_LANES, BF_FIT_LANE_WIDTH): out[0] lane launches, out[1] the
+/* Fit-lane groups of the batch since it was created (lanes.hip; BF_FIT_LANES, BF_FIT_LANE_WIDTH): out[0] lane launches, out[1] the
  * frame-after-frame calls they carried, out[2] the most calls one launch carried, out[3] W, the most it may carry (1 without lanes) */
 int bf_batch_lane_stats(bf_batch *b, int32_t out[4]);
 /* How the fit lanes of the batch were fed since it was created: out[0] input transfers issued (host-fed groups: one per lane launch, and

@@ -1,4 +1,4 @@
-"""Fit lanes (BF_FIT_LANES, api.hip): frame-after-frame fits of one batch run side by side on streams of their own.  For one lane (the
+"""Fit lanes (BF_FIT_LANES, lanes.hip): frame-after-frame fits of one batch run side by side on streams of their own.  For one lane (the
 single-stream path), two, three and more lanes than the process has hardware queues (4 on the GPU hosts: lanes then share queues
 and run in turn), every streamed frame - read back as the frame before the last or as the last one, in the capture's call order and
 in irregular ones, for one frame and for a 32-frame batch - must be the bits of the same frame fitted alone (tests/lanes_child.py)."""

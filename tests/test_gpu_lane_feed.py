@@ -1,4 +1,4 @@
-"""Host-fed lane groups (api.hip): with W > 1 a staging packs the call's inputs into a pinned slot and issues no GPU work, a group's
+"""Host-fed lane groups (lanes.hip): with W > 1 a staging packs the call's inputs into a pinned slot and issues no GPU work, a group's
 launch carries one input transfer for all its slots, a re-fit copies its inputs on the host, and a group is fed from the host or on the
 device, never both.  For forced groups of 3 (BF_FIT_LANE_FILL=1), the adaptive default and a launch per call (W = 1, the call sequence
 before groups), every result - seven streamed frames, re-fits, a switch of kind, a slot staged past its group, a double staging, a

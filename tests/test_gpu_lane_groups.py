@@ -1,4 +1,4 @@
-"""Fit-lane groups (BF_FIT_LANE_WIDTH, api.hip): a lane launch carries up to W consecutive frame-after-frame calls.  For a launch per
+"""Fit-lane groups (BF_FIT_LANE_WIDTH, lanes.hip): a lane launch carries up to W consecutive frame-after-frame calls.  For a launch per
 call (W = 1), forced groups of 3 and of 8 (BF_FIT_LANE_FILL=1) and the adaptive default, every streamed frame - in every slot of a full
 group, of a partial one and of the group after it, read back as the frame before the last or as the last one, in the capture's call
 order and in irregular ones, for one frame and for a 32-frame batch - must be the bits of the same frame fitted alone, the forced

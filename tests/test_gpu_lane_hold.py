@@ -1,4 +1,4 @@
-"""The frame loop's idle rule with a hold (BF_FIT_LANE_HOLD_US, csrc/api.hip fit_lane) and the one-launch mesh tail of a lane group
+"""The frame loop's idle rule with a hold (BF_FIT_LANE_HOLD_US, csrc/lanes.hip bf_lanes_fit, csrc/lane_policy.h) and the one-launch mesh tail of a lane group
 (bf_launch_mesh, csrc/mesh_choice.h).  Each setting runs in a child of its own (tests/lane_hold_child.py), which holds every
 streamed frame bit for bit against the frame fitted alone.
 

@@ -1,4 +1,4 @@
-"""The frame-loop routes of bf_fit (fit_plan, csrc/api.hip) on the models no other route test uses: the kid model (87 parameters, 11
+"""The frame-loop routes of bf_fit (fit_plan, csrc/api.hip; lanes: csrc/lanes.hip) on the models no other route test uses: the kid model (87 parameters, 11
 betas, the table-driven fit kernel, the 12-direction mesh instances), SMPL with a 6-bone loss selector (8-wide mesh), SMPL with one
 9-bone vertex (the sized fit instance beside a dense mesh tail) and the 690-vertex models with 5..8 and 9..12 bones per vertex.
 

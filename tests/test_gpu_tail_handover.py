@@ -1,4 +1,4 @@
-"""The frame loop's tail hands its results over itself (csrc/api.hip lane_launch / enqueue_tail, MeshPass::mirror): bf_mesh_kernel and
+"""The frame loop's tail hands its results over itself (csrc/api.hip bf_enqueue_tail, csrc/lanes.hip lane_launch, MeshPass::mirror): bf_mesh_kernel and
 bf_mesh_multi_kernel store every vertex into the arena's pinned mirror as well, bf_joints_kernel its joints and the arena's params /
 terms / state rows; and a drain hands the last slot of a lane's group back to the batch by one kernel on that lane's stream
 (bf_lanes_drain).  BF_TAIL_HANDOVER=store has every tail that can do so, =copy keeps the launch or copy command behind the tail, and
