@@ -95,6 +95,10 @@ SIGNATURES = {
     "bf_smpl_vjp": (C.c_int, [_VP, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "bf_smplx_forward": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), C.POINTER(SmplxOutputs)]),
     "bf_smplx_vjp": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), C.POINTER(SmplxCotangents), C.POINTER(SmplxGrads)]),
+    "bf_model_set_expression": (C.c_int, [_VP, C.c_int, _FP]),
+    "bf_model_n_expression": (C.c_int, [_VP]),
+    "bf_smplx_forward_expr": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), _FP, C.POINTER(SmplxOutputs)]),
+    "bf_smplx_vjp_expr": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), _FP, C.POINTER(SmplxCotangents), C.POINTER(SmplxGrads), _FP]),
     "bf_gmm_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.POINTER(_VP)]),
     "bf_gmm_destroy": (None, [_VP]),
     "bf_keypoint_loss": (C.c_int, [C.c_int, _VP, C.POINTER(KeypointLossIn), C.POINTER(Hyper), _FP, _FP, _FP, _FP, _FP]),

@@ -294,6 +294,12 @@ struct bf_model {
     std::mutex lazy;              // guards the build-on-first-use tables (posedirsT, faces_d / adj)
     std::vector<int> faces_host;  // body-model topology (for the SMPL+D stage), optional
     DevBuf<int> faces_d, adj_start, adj;   // faces and the vertex -> (face, corner) lists, built on first use
+    // SMPL-X expression directions (bf_model_set_expression; n_expr = 0: none attached)
+    int n_expr = 0;
+    DevBuf<float> exprT;          // [n_expr][3][nv]: E transposed, a coefficient's component contiguous over the vertices
+    DevBuf<float> Jx;             // [nj*3][n_expr]   J_regressor E
+    std::vector<int> jreg_start, jreg_v;   // the J_regressor's non-zero weights per joint (CSR), kept on the host for Jx (SMPL-X-kind models)
+    std::vector<float> jreg_w;
 };
 
 struct bf_graph_key { int n_iters; uint32_t flags; int arena; bf_hyper h; };     // (arena: the result arena its nodes point at)

@@ -28,6 +28,7 @@
 #define BF_GRAD_MAX_LMK 96      // face landmarks (SMPL-X: 51 static + 17 on the contour), three (vertex, weight) entries each
 #define BF_GRAD_MAX_NP 128      // packed parameters per frame of the pose assembly (SMPL-X: 98)
 #define BF_GRAD_MAX_JOINTS 64   // chain joints: one lane each in the chain kernel's single wave (SMPL: 24, SMPL-X: 55)
+#define BF_EXPR_MAX 16          // expression coefficients (SMPL-X: 10): the LDS tables and register rows of expr_kernels.hip; bf_model_set_expression refuses more
 // LDS tables of the stand-alone keypoint loss (kp_loss_kernels.hip); bf_kp_loss_check (kp_loss_api.hip) refuses a call beyond them
 #define BF_KPL_MAX_ROWS 256     // joint rows of a problem (SMPL: 25, SMPL-X with hands + face: 135)
 #define BF_KPL_MAX_DIM 128      // dimension of the GMM prior (69)

@@ -438,6 +438,14 @@ int bf_model_create(const bf_model_desc *d, int device, bf_model **out) {
     m->kp_dense = H.fit.kp_dense; m->nl_loss = d->n_loss_joints;     // (kp_dense: the keypoint loss goes through bf_kp_loss_kernel, nl = 0)
     m->mesh_smem = bf_mesh_smem_bytes(m->nj, m->npf, m->nb);
     if (d->n_faces > 0 && d->faces) m->faces_host.assign(d->faces, d->faces + (size_t)d->n_faces * 3);
+    if (m->kind == 1) {                   // the joint regressor's non-zeros stay on the host: bf_model_set_expression contracts it with E
+        for (int j = 0; j < m->nj; ++j) {
+            m->jreg_start.push_back((int)m->jreg_v.size());
+            for (int v = 0; v < m->nv; ++v)
+                if (const float w = d->j_regressor[(size_t)j * m->nv + v]; w != 0.f) { m->jreg_v.push_back(v); m->jreg_w.push_back(w); }
+        }
+        m->jreg_start.push_back((int)m->jreg_v.size());
+    }
 
     Uploader up;
     fill_fit(up, *m, d, H);

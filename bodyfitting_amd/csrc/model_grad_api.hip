@@ -10,10 +10,15 @@
 //            3. bf_smpl_vjp_chain_kernel (table-driven, one lane per joint): the kinematic chain and Rodrigues reversed -> dtheta, dbeta
 // SMPL-X puts bf_smplx_pose_assemble_kernel (blocks -> full_pose) in front, bf_smplx_dyn_row_kernel behind its forward and
 // bf_smplx_pose_reverse_kernel (dtheta + dfull_pose -> the parameter blocks) behind its reverse.
+// With expression coefficients (bf_smplx_forward_expr / bf_smplx_vjp_expr on a model bf_model_set_expression gave directions to) the
+// kernels of expr_kernels.hip go around those passes, which stay as they are: bf_expr_chain_kernel between the pose state and the mesh
+// pass, bf_expr_vertex_kernel between the mesh and the joints pass, bf_expr_reverse_kernel + bf_ext_reduce_kernel in front of the chain
+// reverse, which takes Jx psi into its rest joints and closes dexpression.  Without coefficients the launch sequence is the one above.
 // Stateless: nothing stays on the device between calls but the model's lazily built posedirsT.
 #include "bf_host.h"
 #include "mesh_kernels.h"
 #include "model_grad_kernels.h"
+#include "expr_kernels.h"
 #include "scan_kernels.h"
 
 
@@ -37,6 +42,8 @@ struct ModelPass {
     bf_model *const m;
     const int n;
     DevBuf<float> state, vraw, vposed, xpart, joints, jraw, lmk_w, dv, dchain, part, ext, dtheta, dbeta;
+    DevBuf<float> dJx, epart, emesh, dexpr;         // with expression coefficients only (expr_kernels.hip)
+    const float *expr = nullptr;                    // the coefficients [n][n_expr] on the device: set by a forward that was given them
     DevBuf<int> lmk_vid;
     MeshScratch scratch;
     // (destroyed before the buffers: whatever path leaves the call, no kernel still uses a block when it goes back to the cache)
@@ -46,9 +53,12 @@ struct ModelPass {
     // Model space: no similarity, constant scale 1 - as bf_smpl_forward builds its state, so that the mesh reverse's dvout is dL/dv in
     // model space.  for_reverse: vposed is saved instead of the mapped joints.  An SMPL-X model's joints pass leaves all its joints
     // (jraw) and, for the reverse, every frame's landmark vertices and weights (the contour row of ITS yaw).
-    int forward(const float *beta, const float *th_root, const float *th_rest, bool for_reverse) {
+    // expression (device, [n][n_expr]; null: none - then the launches are the ones of a model without directions): the chain delta
+    // shifts the state's Gt / At in front of the mesh pass, the vertex delta runs between the mesh and the joints pass.
+    int forward(const float *beta, const float *th_root, const float *th_rest, bool for_reverse, const float *expression = nullptr) {
         const size_t N = (size_t)n, nv3 = (size_t)m->nv * 3;
         const bool x = m->kind == 1;
+        expr = expression;
         HIP_TRY(state.alloc_pooled(N * bf_state_stride(m->nj, m->npf, m->nb)));
         HIP_TRY(vraw.alloc_pooled(N * nv3));
         if (for_reverse) HIP_TRY(vposed.alloc_pooled(N * nv3));
@@ -65,13 +75,31 @@ struct ModelPass {
         MeshPass mesh;
         mesh.scr = &scratch; mesh.n = n; mesh.state = state.p;
         mesh.vraw = vraw.p; mesh.xpart = xpart.p; mesh.vposed = vposed.p;
-        mesh.joints = joints.p; mesh.jraw = jraw.p; mesh.lmk_vid = lmk_vid.p; mesh.lmk_w = lmk_w.p;
-        return bf_launch_mesh(m, mesh);
+        if (!expr) {
+            mesh.joints = joints.p; mesh.jraw = jraw.p; mesh.lmk_vid = lmk_vid.p; mesh.lmk_w = lmk_w.p;
+            return bf_launch_mesh(m, mesh);
+        }
+        const int ne = m->n_expr;
+        HIP_TRY(dJx.alloc_pooled(N * m->nj * 3));
+        hipLaunchKernelGGL(bf_expr_chain_kernel, dim3(n), dim3(64), 0, 0, m->fit, state.p, expr, ne, (const float *)m->Jx.p, dJx.p);
+        HIP_TRY(hipGetLastError());
+        BF_TRY(bf_launch_mesh(m, mesh));                          // (no joints asked for: the mesh pass alone)
+        hipLaunchKernelGGL(bf_expr_vertex_kernel, dim3((m->nv + 255) / 256, n), dim3(256), 0, 0, m->mesh, (const float *)state.p, expr, ne,
+                           (const float *)m->exprT.p, vraw.p, vposed.p);
+        HIP_TRY(hipGetLastError());
+        if (m->n_extra > 0) {                                     // the extra-regressor joints' per-tile sums, from the updated vertices
+            hipLaunchKernelGGL(bf_expr_xpart_kernel, dim3(m->mesh.n_tiles, n), dim3(128), 0, 0, m->mesh, (const float *)vraw.p, xpart.p);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(bf_joints_kernel, dim3(n), dim3(256), 0, 0, m->mesh, (const float *)state.p, (const float *)vraw.p,
+                           (const float *)xpart.p, joints.p, (float *)nullptr, jraw.p, lmk_vid.p, lmk_w.p, BfHandOver{});
+        HIP_TRY(hipGetLastError());
+        return BF_OK;
     }
 
     // After forward(..., true): the cotangents on the device (any may be null = zero; ddirect covers the first n_direct joints) ->
     // dtheta[n][3 NJ], dbeta[n][NB], left on the device.  The caller holds the model's posedirsT (bf_ensure_posedirsT_locked).
-    int reverse(const float *dvertices, const float *djoints, const float *ddirect, int n_direct) {
+    int reverse(const float *dvertices, const float *djoints, const float *ddirect, int n_direct, bool want_dexpr = false) {
         const int nj = m->nj, nb = m->nb, nv = m->nv;
         const size_t N = (size_t)n, nv3 = (size_t)nv * 3;
         const int EXT = m->npf + nj * 12 + nb + 4;
@@ -95,9 +123,24 @@ struct ModelPass {
         hipLaunchKernelGGL(bf_ext_reduce_kernel, dim3((EXT + BF_RED_COLS - 1) / BF_RED_COLS, n), dim3(8 * BF_RED_COLS), 0, 0,
                            (const float *)part.p, rows, EXT, ext.p, EXT, (int *)nullptr, 0);
         HIP_TRY(hipGetLastError());
-        // 3. chain + Rodrigues reversed
+        // (with expression coefficients whose gradient is wanted) E_v^T (sum_j w_vj GR_j^T dv_v) per 256-vertex tile, the tiles in tile order
+        const int ne = expr ? m->n_expr : 0, etiles = (nv + 255) / 256;
+        const bool dex = expr && want_dexpr;
+        if (dex) {
+            HIP_TRY(epart.alloc_pooled(N * etiles * ne));
+            HIP_TRY(emesh.alloc_pooled(N * ne));
+            HIP_TRY(dexpr.alloc_pooled(N * ne));
+            hipLaunchKernelGGL(bf_expr_reverse_kernel, dim3(etiles, n), dim3(256), 0, 0, m->mesh, (const float *)state.p, (const float *)dv.p, ne,
+                               (const float *)m->exprT.p, epart.p);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(bf_ext_reduce_kernel, dim3((ne + BF_RED_COLS - 1) / BF_RED_COLS, n), dim3(8 * BF_RED_COLS), 0, 0,
+                               (const float *)epart.p, etiles, ne, emesh.p, ne, (int *)nullptr, 0);
+            HIP_TRY(hipGetLastError());
+        }
+        // 3. chain + Rodrigues reversed (the rest joints with Jx psi; dexpression = the vertex part + Jx^T dL/d(rest joints))
         hipLaunchKernelGGL(bf_smpl_vjp_chain_kernel, dim3(n), dim3(64), 0, 0, m->fit, (const float *)state.p, (const float *)ext.p, EXT,
-                           (const float *)dchain.p, dtheta.p, dbeta.p);
+                           (const float *)dchain.p, dtheta.p, dbeta.p, (const float *)(expr ? dJx.p : nullptr),
+                           (const float *)(expr ? m->Jx.p : nullptr), ne, (const float *)(dex ? emesh.p : nullptr), dex ? dexpr.p : (float *)nullptr);
         HIP_TRY(hipGetLastError());
         return BF_OK;
     }
@@ -170,18 +213,67 @@ extern "C" int bf_smpl_vjp(bf_model *m, int n, const float *betas, const float *
     return fetch_blocks(pass.dtheta.p, N, 3 * nj, {{dglobal_orient, 0, 3}, {dbody_pose, 3, 3 * (nj - 1)}});
 }
 
+// a call's expression argument against the model: coefficients need directions
+static int bf_expr_check(const bf_model *m, const float *expression, const char *who) {
+    if (expression && m->n_expr == 0)
+        return fail(BF_ERR_UNSUPPORTED, std::string(who) + ": the model has no expression directions - call bf_model_set_expression first");
+    return BF_OK;
+}
+
+extern "C" int bf_model_n_expression(const bf_model *m) { return m ? m->n_expr : 0; }
+
+extern "C" int bf_model_set_expression(bf_model *m, int n_expr, const float *exprdirs) {
+    if (!m || !exprdirs) return fail(BF_ERR_INVALID, "bf_model_set_expression: bad argument");
+    BF_TRY(bf_grad_check(m, 1, "bf_model_set_expression"));
+    if (n_expr < 1 || n_expr > BF_EXPR_MAX)
+        return fail(BF_ERR_UNSUPPORTED, "bf_model_set_expression: 1.." + std::to_string(BF_EXPR_MAX) + " expression coefficients supported");
+    std::lock_guard<std::mutex> g(m->lazy);
+    if (m->n_expr != 0) return fail(BF_ERR_INVALID, "bf_model_set_expression: the model has its expression directions already");
+    HIP_TRY(hipSetDevice(m->device));
+    const int nv = m->nv, nj = m->nj, ne = n_expr;
+    // E transposed: [l][k][v]
+    std::vector<float> eT((size_t)ne * 3 * nv);
+    for (int v = 0; v < nv; ++v)
+        for (int k = 0; k < 3; ++k)
+            for (int l = 0; l < ne; ++l) eT[((size_t)l * 3 + k) * nv + v] = exprdirs[((size_t)v * 3 + k) * ne + l];
+    // Jx = J_regressor E: float64 accumulation over a joint's non-zero weights in vertex order, rounded once (as contract_regressor forms Jd)
+    std::vector<float> jx((size_t)nj * 3 * ne);
+    std::vector<double> acc((size_t)3 * ne);
+    for (int j = 0; j < nj; ++j) {
+        std::fill(acc.begin(), acc.end(), 0.0);
+        for (int q = m->jreg_start[j]; q < m->jreg_start[j + 1]; ++q) {
+            const double w = m->jreg_w[q];
+            const float *e = exprdirs + (size_t)m->jreg_v[q] * 3 * ne;
+            for (int i = 0; i < 3 * ne; ++i) acc[i] += w * e[i];
+        }
+        for (int i = 0; i < 3 * ne; ++i) jx[(size_t)j * 3 * ne + i] = (float)acc[i];
+    }
+    HIP_TRY(m->exprT.upload(eT));
+    HIP_TRY(m->Jx.upload(jx));
+    m->n_expr = ne;
+    return BF_OK;
+}
+
 extern "C" int bf_smplx_forward(bf_model *m, int n, const bf_smplx_params *in, const bf_smplx_outputs *out) {
+    return bf_smplx_forward_expr(m, n, in, nullptr, out);
+}
+
+extern "C" int bf_smplx_forward_expr(bf_model *m, int n, const bf_smplx_params *in, const float *expression, const bf_smplx_outputs *out) {
+    const char *who = expression ? "bf_smplx_forward_expr" : "bf_smplx_forward";
     if (!m || n <= 0 || !in || !out || !in->betas || !in->global_orient || !in->body_pose)
-        return fail(BF_ERR_INVALID, "bf_smplx_forward: bad argument");
-    BF_TRY(bf_grad_check(m, 1, "bf_smplx_forward"));
+        return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");
+    BF_TRY(bf_grad_check(m, 1, who));
+    BF_TRY(bf_expr_check(m, expression, who));
     HIP_TRY(hipSetDevice(m->device));
     const size_t N = (size_t)n;
     Inputs x;
     DevBuf<int> d_row;
+    DevBuf<float> d_expr;
     ModelPass pass(m, n);
     BF_TRY(x.upload_and_assemble(m, N, in));
+    if (expression) HIP_TRY(d_expr.upload_pooled(expression, N * m->n_expr));
     HIP_TRY(d_row.alloc_pooled(N));
-    BF_TRY(pass.forward(x.beta.p, x.th_root.p, x.th_rest.p, false));
+    BF_TRY(pass.forward(x.beta.p, x.th_root.p, x.th_rest.p, false, d_expr.p));
     hipLaunchKernelGGL(bf_smplx_dyn_row_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, m->mesh, (const float *)pass.state.p, n, d_row.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -194,32 +286,41 @@ extern "C" int bf_smplx_forward(bf_model *m, int n, const bf_smplx_params *in, c
 }
 
 extern "C" int bf_smplx_vjp(bf_model *m, int n, const bf_smplx_params *in, const bf_smplx_cotangents *cot, const bf_smplx_grads *grads) {
-    if (!m || n <= 0 || !in || !cot || !grads || !in->betas || !in->global_orient || !in->body_pose)
-        return fail(BF_ERR_INVALID, "bf_smplx_vjp: bad argument");
-    BF_TRY(bf_grad_check(m, 1, "bf_smplx_vjp"));
+    return bf_smplx_vjp_expr(m, n, in, nullptr, cot, grads, nullptr);
+}
+
+extern "C" int bf_smplx_vjp_expr(bf_model *m, int n, const bf_smplx_params *in, const float *expression, const bf_smplx_cotangents *cot,
+                                 const bf_smplx_grads *grads, float *dexpression) {
+    const char *who = expression ? "bf_smplx_vjp_expr" : "bf_smplx_vjp";
+    if (!m || n <= 0 || !in || !cot || !grads || !in->betas || !in->global_orient || !in->body_pose || (dexpression && !expression))
+        return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");
+    BF_TRY(bf_grad_check(m, 1, who));
+    BF_TRY(bf_expr_check(m, expression, who));
     if (!grads->dbetas && !grads->dglobal_orient && !grads->dbody_pose && !grads->djaw_pose && !grads->dleye_pose && !grads->dreye_pose &&
-        !grads->dleft_hand_pose && !grads->dright_hand_pose)
+        !grads->dleft_hand_pose && !grads->dright_hand_pose && !dexpression)
         return BF_OK;
     HIP_TRY(hipSetDevice(m->device));
     BF_TRY(ensure_posedirsT(m));
     const int nj = m->nj, nb = m->nb, n_pca = m->fit.n_pca, nbp = m->fit.nbp, OUT = 3 * nj + 2 * n_pca;
     const size_t N = (size_t)n;
     Inputs x;
-    DevBuf<float> d_dvert, d_dj, d_dja, d_dfull, d_out;
+    DevBuf<float> d_dvert, d_dj, d_dja, d_dfull, d_out, d_expr;
     ModelPass pass(m, n);
     BF_TRY(x.upload_and_assemble(m, N, in));
+    if (expression) HIP_TRY(d_expr.upload_pooled(expression, N * m->n_expr));
     if (cot->dvertices) HIP_TRY(d_dvert.upload_pooled(cot->dvertices, N * m->nv * 3));
     if (cot->djoints) HIP_TRY(d_dj.upload_pooled(cot->djoints, N * m->n_joint_map * 3));
     if (cot->djoints_all) HIP_TRY(d_dja.upload_pooled(cot->djoints_all, N * m->n_all * 3));
     if (cot->dfull_pose) HIP_TRY(d_dfull.upload_pooled(cot->dfull_pose, N * 3 * nj));
     HIP_TRY(d_out.alloc_pooled(N * OUT));
-    BF_TRY(pass.forward(x.beta.p, x.th_root.p, x.th_rest.p, true));
-    BF_TRY(pass.reverse(d_dvert.p, d_dj.p, d_dja.p, m->n_all));
+    BF_TRY(pass.forward(x.beta.p, x.th_root.p, x.th_rest.p, true, d_expr.p));
+    BF_TRY(pass.reverse(d_dvert.p, d_dj.p, d_dja.p, m->n_all, dexpression != nullptr));
     // the pose assembly reversed
     hipLaunchKernelGGL(bf_smplx_pose_reverse_kernel, dim3(n), dim3(64), 0, 0, m->fit, (const float *)pass.dtheta.p, (const float *)d_dfull.p, d_out.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     if (grads->dbetas) HIP_TRY(hipMemcpy(grads->dbetas, pass.dbeta.p, N * nb * sizeof(float), hipMemcpyDeviceToHost));
+    if (dexpression) HIP_TRY(hipMemcpy(dexpression, pass.dexpr.p, N * m->n_expr * sizeof(float), hipMemcpyDeviceToHost));
     // full pose order: root | body | jaw | left eye | right eye | hands (through their PCA coefficients, behind the thetas)
     return fetch_blocks(d_out.p, N, OUT, {{grads->dglobal_orient, 0, 3}, {grads->dbody_pose, 3, nbp}, {grads->djaw_pose, 3 + nbp, 3},
                                           {grads->dleye_pose, 6 + nbp, 3}, {grads->dreye_pose, 9 + nbp, 3},

@@ -6,7 +6,7 @@
 extern "C" __global__ void bf_model_vjp_fold_kernel(MeshTab M, const float *dvertices, const float *djoints, const float *ddirect, int n_direct, const int *lmk_vid,
                                                     const float *lmk_w, float *dv, float *dchain);
 extern "C" __global__ void bf_smpl_vjp_chain_kernel(FitTab T, const float *state, const float *ext, int ext_stride, const float *dchain, float *dtheta,
-                                                    float *dbeta);
+                                                    float *dbeta, const float *dJx, const float *Jx, int ne, const float *dexpr_mesh, float *dexpr);
 extern "C" __global__ void bf_smplx_pose_assemble_kernel(FitTab T, const float *orient, const float *body_pose, const float *jaw, const float *leye,
                                                          const float *reye, const float *lh, const float *rh, float *full, float *th_root, float *th_rest);
 extern "C" __global__ void bf_smplx_dyn_row_kernel(MeshTab M, const float *state, int n, int *row);

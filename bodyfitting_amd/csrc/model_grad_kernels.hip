@@ -133,11 +133,15 @@ __device__ inline void vjp_rodrigues(const float *th, const float *dR, float *g)
 // grid (n), one wave per frame.  In: the pose state (GR, theta, beta), the reduced mesh-reverse row
 //   ext[f][EXT] = dfeat[npf] | per joint (sum w dv (x) vp | sum w dv) as 3 rows of 4 | dbeta_mesh[nb] | dt ds
 // and dchain[f][NJ][3] = dL/d(posed chain joints).  Out: dtheta[f][NJ*3], dbeta[f][nb].
+// SMPL-X expression (bf_smplx_vjp_expr; all null / 0 otherwise, and the results are then the bits they are without these arguments):
+// dJx[f][NJ*3] = Jx psi joins the rest joints; dexpr[f][ne] (null: not wanted) = dexpr_mesh[f][ne] + Jx^T dL/d(rest joints).
 // Leaves to root over the levels of FitTab (level_start / level_joints); a parent takes its children's contributions in the
 // order of its CSR child list - one writer per joint and step, no atomics.
 extern "C" __global__ void __launch_bounds__(64)
 bf_smpl_vjp_chain_kernel(FitTab T, const float *__restrict__ state, const float *__restrict__ ext, int ext_stride,
-                         const float *__restrict__ dchain, float *__restrict__ dtheta, float *__restrict__ dbeta) {
+                         const float *__restrict__ dchain, float *__restrict__ dtheta, float *__restrict__ dbeta,
+                         const float *__restrict__ dJx, const float *__restrict__ Jx, int ne, const float *__restrict__ dexpr_mesh,
+                         float *__restrict__ dexpr) {
     constexpr int MJ = BF_GRAD_MAX_JOINTS;
     __shared__ float s_R[MJ * 9], s_GR[MJ * 9], s_J[MJ * 3], s_dGR[MJ * 9], s_dGt[MJ * 3], s_dJ[MJ * 3], s_cGR[MJ * 9], s_drel[MJ * 3];
     __shared__ float s_dR[MJ * 9];
@@ -155,6 +159,7 @@ bf_smpl_vjp_chain_kernel(FitTab T, const float *__restrict__ state, const float 
             float acc = 0.f;
             for (int l = 0; l < nb; ++l) acc += T.Jd[(i * 3 + k) * nb + l] * st.beta[l];
             s_J[i * 3 + k] = T.Jt[i * 3 + k] + acc;
+            if (dJx) s_J[i * 3 + k] += dJx[((size_t)f * nj + i) * 3 + k];
         }
     }
     __syncthreads();
@@ -239,6 +244,12 @@ bf_smpl_vjp_chain_kernel(FitTab T, const float *__restrict__ state, const float 
         float acc = 0.f;
         for (int r = 0; r < nj * 3; ++r) acc += T.Jd[r * nb + tid] * s_dJ[r];
         dbeta[(size_t)f * nb + tid] = row[npf + nj * 12 + tid] + acc;
+    }
+    // dexpression = the expression reverse's vertex part + Jx^T dJ (J rows ascending)
+    if (dexpr && tid < ne) {
+        float acc = 0.f;
+        for (int r = 0; r < nj * 3; ++r) acc += Jx[r * ne + tid] * s_dJ[r];
+        dexpr[(size_t)f * ne + tid] = dexpr_mesh[(size_t)f * ne + tid] + acc;
     }
 }
 

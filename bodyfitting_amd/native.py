@@ -57,7 +57,9 @@ def model_desc(model, gmm):
     model_type = model.get("model_type", "smpl")
     means, prec, nllw = gmm_buffers(gmm) if isinstance(gmm, dict) else gmm
     smplx = model_type == "smplx"
-    n_betas = 10 if smplx else np.asarray(model["shapedirs"]).shape[2]     # expression dirs stay unused (never optimised)
+    # SMPL-X: the 10 shape directions go into the descriptor; the columns behind them are the expression directions, which
+    # DeviceModel attaches apart (bf_model_set_expression) - the fit never optimises expression
+    n_betas = 10 if smplx else np.asarray(model["shapedirs"]).shape[2]
     if "J_regressor_extra" not in model:
         model = dict(model, J_regressor_extra=np.zeros((0, np.asarray(model["v_template"]).shape[0]), np.float32))
     keep = {
@@ -98,6 +100,8 @@ def model_desc(model, gmm):
         d.dynamic_lmk_faces_idx, d.dynamic_lmk_bary_coords = _lib.iptr(keep["dyn_f"]), _lib.fptr(keep["dyn_b"])
         d.neck_joint = int(np.asarray(model["neck_kin_chain"])[0])
         info["n_hand_pca"] = keep["lhc"].shape[0]
+        if np.asarray(model["shapedirs"]).shape[2] > n_betas:
+            keep["exprdirs"] = _f32(np.asarray(model["shapedirs"])[:, :, n_betas:])
         # all joints smplx returns before a joint_mapper: chain | selector vertices | extra regressor rows | 51 + 17 landmarks
         info["n_joints_all"] = info["n_joints"] + info["n_selector"] + keep["j_regressor_extra"].shape[0] + len(keep["lmk_f"]) + keep["dyn_f"].shape[1]
     d.gmm_components, d.gmm_dim = keep["gmm_means"].shape
@@ -109,7 +113,10 @@ def model_desc(model, gmm):
 
 class DeviceModel:
     """Body model + GMM prior uploaded once to one GPU (replaces the per-frame construction at
-    reference smplify/body_fitting.py:82 -> smplify/smplify.py:46-56)."""
+    reference smplify/body_fitting.py:82 -> smplify/smplify.py:46-56).  An SMPL-X model dict whose shapedirs has more than
+    10 columns brings its expression directions (columns 10:), n_expression of them; 0 otherwise."""
+
+    dtype = np.float32          # what the kernels compute in
 
     def __init__(self, model, gmm, device=0):
         lib = _lib.load()
@@ -118,6 +125,9 @@ class DeviceModel:
         self.__dict__.update(info)
         self._h = C.c_void_p()
         _lib.check(lib.bf_model_create(C.byref(d), int(device), C.byref(self._h)), "bf_model_create")
+        if "exprdirs" in keep:              # an SMPL-X model dict whose shapedirs has more than 10 columns: columns 10: are its expression directions
+            _lib.check(lib.bf_model_set_expression(self._h, keep["exprdirs"].shape[2], _lib.fptr(keep["exprdirs"])), "bf_model_set_expression")
+        self.n_expression = lib.bf_model_n_expression(self._h)
         del keep
         self.device = int(device)
         self.n_params = lib.bf_model_n_params(self._h)
@@ -187,33 +197,53 @@ class DeviceModel:
                   opt(left_hand_pose, self.n_hand_pca), opt(right_hand_pose, self.n_hand_pca))
         return n, arrays, _lib.SmplxParams(*[_lib.fptr(a) for a in arrays])
 
+    def _expression(self, expression, n):
+        if expression is None:
+            return None
+        if self.n_expression == 0:
+            raise _lib.BodyfitError("expression: the model has no expression directions (bf_model_set_expression)")
+        return _f32(expression, (n, self.n_expression))
+
     def forward_smplx(self, betas, global_orient, body_pose, jaw_pose=None, leye_pose=None, reye_pose=None, left_hand_pose=None,
-                      right_hand_pose=None):
+                      right_hand_pose=None, expression=None):
         """smplx.create(model_type='smplx', ...).forward as smplify.py:177-190 calls it (bf_smplx_forward), model space; an
-        argument left None is zeros.  -> dict(vertices[n,NV,3], joints[n,n_joint_map,3] (the model's joint_map: 135),
-        joints_all[n,144,3] (what smplx returns before a joint_mapper), full_pose[n,165], dyn_row[n] int32)."""
+        argument left None is zeros.  expression[n,n_expression] (None: the call without it, bit for bit) goes through
+        bf_smplx_forward_expr on a model with expression directions.  -> dict(vertices[n,NV,3], joints[n,n_joint_map,3] (the
+        model's joint_map: 135), joints_all[n,144,3] (what smplx returns before a joint_mapper), full_pose[n,165], dyn_row[n] int32)."""
         n, keep, par = self._smplx_params(betas, global_orient, body_pose, jaw_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose)
+        expr = self._expression(expression, n)
         out = {"vertices": np.empty((n, self.n_verts, 3), np.float32), "joints": np.empty((n, self.n_joint_map, 3), np.float32),
                "joints_all": np.empty((n, self.n_joints_all, 3), np.float32), "full_pose": np.empty((n, 3 * self.n_joints), np.float32),
                "dyn_row": np.empty(n, np.int32)}
         dst = _lib.SmplxOutputs(*[_lib.fptr(out[k]) for k in ("vertices", "joints", "joints_all", "full_pose")], _lib.iptr(out["dyn_row"]))
-        _lib.check(self._lib.bf_smplx_forward(self._h, n, C.byref(par), C.byref(dst)), "bf_smplx_forward")
+        if expr is None:
+            _lib.check(self._lib.bf_smplx_forward(self._h, n, C.byref(par), C.byref(dst)), "bf_smplx_forward")
+        else:
+            _lib.check(self._lib.bf_smplx_forward_expr(self._h, n, C.byref(par), _lib.fptr(expr), C.byref(dst)), "bf_smplx_forward_expr")
         return out
 
     def vjp_smplx(self, betas, global_orient, body_pose, jaw_pose=None, leye_pose=None, reye_pose=None, left_hand_pose=None,
-                  right_hand_pose=None, dverts=None, djoints=None, djoints_all=None, dfull_pose=None):
+                  right_hand_pose=None, dverts=None, djoints=None, djoints_all=None, dfull_pose=None, expression=None, want_dexpression=True):
         """The backward of `forward_smplx` (bf_smplx_vjp): cotangents of vertices, joints, joints_all, full_pose (None = zero) ->
         (dbetas, dglobal_orient, dbody_pose, djaw_pose, dleye_pose, dreye_pose, dleft_hand_pose, dright_hand_pose), each [n, .].
+        With expression[n,n_expression] (bf_smplx_vjp_expr) a ninth entry follows: dexpression[n,n_expression], or None with
+        want_dexpression=False - the other eight are then the same bits.
         No gradient flows through the contour landmarks' row choice."""
         n, keep, par = self._smplx_params(betas, global_orient, body_pose, jaw_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose)
+        expr = self._expression(expression, n)
         shapes = ((n, self.n_verts, 3), (n, self.n_joint_map, 3), (n, self.n_joints_all, 3), (n, 3 * self.n_joints))
         cots = [None if a is None else _f32(a, sh) for a, sh in zip((dverts, djoints, djoints_all, dfull_pose), shapes)]
         widths = (self.n_betas, 3, 63, 3, 3, 3, self.n_hand_pca, self.n_hand_pca)
         grads = tuple(np.empty((n, w), np.float32) for w in widths)
         cot = _lib.SmplxCotangents(*[_lib.fptr(a) for a in cots])
         dst = _lib.SmplxGrads(*[_lib.fptr(g) for g in grads])
-        _lib.check(self._lib.bf_smplx_vjp(self._h, n, C.byref(par), C.byref(cot), C.byref(dst)), "bf_smplx_vjp")
-        return grads
+        if expr is None:
+            _lib.check(self._lib.bf_smplx_vjp(self._h, n, C.byref(par), C.byref(cot), C.byref(dst)), "bf_smplx_vjp")
+            return grads
+        dexpr = np.empty((n, self.n_expression), np.float32) if want_dexpression else None
+        _lib.check(self._lib.bf_smplx_vjp_expr(self._h, n, C.byref(par), _lib.fptr(expr), C.byref(cot), C.byref(dst), _lib.fptr(dexpr)),
+                   "bf_smplx_vjp_expr")
+        return grads + (dexpr,)
 
     def forward_packed(self, params):
         """vertices / joints (model space) of packed parameter vectors [n, n_params] - any model kind"""

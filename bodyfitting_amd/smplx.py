@@ -7,13 +7,18 @@ the neck chain's yaw), put through `joint_mapper` when one was given, as smplx d
 Two paths, as `bodyfitting_amd.smpl.SMPL` has them:
 * numpy in -> numpy out, no gradient.
 * torch tensors in -> torch tensors out on the inputs' device, differentiable w.r.t. betas, global_orient, body_pose, jaw_pose,
-  leye_pose, reye_pose, left_hand_pose and right_hand_pose through the HIP forward and its vector-Jacobian product
-  (bf_smplx_forward / bf_smplx_vjp), once.  The contour landmarks' row is an integer look-up: no gradient flows through the
-  choice.  torch is imported on this path only.
+  leye_pose, reye_pose, left_hand_pose, right_hand_pose and expression through the HIP forward and its vector-Jacobian
+  product (bf_smplx_forward / bf_smplx_vjp and their _expr variants), once.  The contour landmarks' row is an integer look-up:
+  no gradient flows through the choice.  torch is imported on this path only.
 
-What the device model cannot do is refused, not approximated: expression coefficients other than zero (it carries the 10
-shape directions only; the reference never optimises `expression`, smplify.py:167-173), `use_pca=False`, another number of PCA
-components than the model's, `flat_hand_mean=True`, `age='kid'`, a dtype other than float32.
+`expression` [B, n_expression] is an input of its own on a device model with expression directions (a model file's shapedirs
+columns behind the 10 shape directions, `DeviceModel.n_expression` of them): zero or not, it goes through the device and, as a
+tensor that requires grad, gets its gradient.  `expression=None` is the call without it.  On a device model without directions
+zeros pass and are ignored, anything else is refused.
+
+What the device model cannot do is refused, not approximated: `use_pca=False`, another number of PCA components or expression
+coefficients than the model's, `flat_hand_mean=True`, `age='kid'`, a dtype other than float32, an `expression` of another width
+or dtype than the device model's (float32).
 """
 from __future__ import annotations
 
@@ -68,7 +73,7 @@ def _is_float32(dtype):
 
 class SMPLX:
     def __init__(self, model_path=None, gender="neutral", joint_mapper=None, use_face_contour=False, use_pca=True, num_pca_comps=6,
-                 flat_hand_mean=False, age="adult", dtype=None, batch_size=1, ext="npz", device=0, **kwargs):
+                 flat_hand_mean=False, age="adult", dtype=None, batch_size=1, ext="npz", device=0, num_expression_coeffs=None, **kwargs):
         # (create_* and the initial-value keywords of smplx arrive in kwargs: arguments not passed to forward are zeros, smplx's
         #  zero-initialised parameters)
         if not use_pca:
@@ -85,6 +90,10 @@ class SMPLX:
         if int(num_pca_comps) != int(self._dev.n_hand_pca):
             raise ValueError(f"num_pca_comps={num_pca_comps}: the model has {self._dev.n_hand_pca} hand PCA components")
         self.num_pca_comps = int(num_pca_comps)
+        # expression directions of the device model (0: none - zeros pass and are ignored, anything else is refused)
+        self.num_expression_coeffs = int(getattr(self._dev, "n_expression", 0))
+        if self.num_expression_coeffs and num_expression_coeffs is not None and int(num_expression_coeffs) != self.num_expression_coeffs:
+            raise ValueError(f"num_expression_coeffs={num_expression_coeffs}: the model has {self.num_expression_coeffs} expression directions")
         self.faces = np.asarray(assets.get_model("smplx", gender)["faces"])
         self.dyn_row = None             # the contour-table rows of the last forward
 
@@ -96,26 +105,41 @@ class SMPLX:
                 return int(np.prod(tuple(x.shape))) // width if hasattr(x, "shape") else np.asarray(x).size // width
         return self.batch_size
 
-    def _check_expression(self, expression):
+    def _check_expression(self, expression, n):
+        """-> is `expression` an input of the device call.  None never is; on a device model without expression directions zeros
+        pass (and are ignored) and anything else is refused; with directions it must be [n, n_expression] in the device model's
+        dtype (float32 for the HIP model)."""
         if expression is None:
-            return
-        e = expression.detach().cpu().numpy() if _is_tensor(expression) else np.asarray(expression)
-        if np.any(e != 0):
-            raise ValueError("expression: the device model carries the 10 shape directions only - expression coefficients must be zero")
+            return False
+        ne = self.num_expression_coeffs
+        if ne == 0:
+            e = expression.detach().cpu().numpy() if _is_tensor(expression) else np.asarray(expression)
+            if np.any(e != 0):
+                raise ValueError("expression: the device model carries no expression directions - expression coefficients must be zero")
+            return False
+        e = expression if hasattr(expression, "shape") and hasattr(expression, "dtype") else np.asarray(expression)
+        shape = tuple(e.shape)
+        if shape != (n, ne):
+            raise ValueError(f"expression: shape {shape}, the model takes [{n}, {ne}]")
+        want = np.dtype(getattr(self._dev, "dtype", np.float32)).name
+        if str(e.dtype).split(".")[-1] != want:
+            raise ValueError(f"expression: dtype {e.dtype}, the device model computes in {want}")
+        return True
 
     def forward(self, betas=None, global_orient=None, body_pose=None, left_hand_pose=None, right_hand_pose=None, transl=None,
                 expression=None, jaw_pose=None, leye_pose=None, reye_pose=None, return_verts=True, return_full_pose=False, **kwargs):
-        self._check_expression(expression)
         given = dict(betas=betas, global_orient=global_orient, body_pose=body_pose, jaw_pose=jaw_pose, leye_pose=leye_pose,
                      reye_pose=reye_pose, left_hand_pose=left_hand_pose, right_hand_pose=right_hand_pose)
         n = self._batch(given)
-        if any(_is_tensor(x) for x in list(given.values()) + [transl]):
-            return self._forward_torch(n, given, transl, expression, return_verts, return_full_pose)
+        with_expr = self._check_expression(expression, n)
+        if any(_is_tensor(x) for x in list(given.values()) + [transl] + ([expression] if with_expr else [])):
+            return self._forward_torch(n, given, transl, expression, with_expr, return_verts, return_full_pose)
         widths = {"betas": self._dev.n_betas, "body_pose": 63, "left_hand_pose": self.num_pca_comps, "right_hand_pose": self.num_pca_comps}
         for k in ("betas", "global_orient", "body_pose"):
             if given[k] is None:
                 given[k] = np.zeros((n, widths.get(k, 3)), np.float32)
-        out = self._dev.forward_smplx(*[given[k] for k in _INPUTS])
+        extra = {"expression": np.asarray(expression)} if with_expr else {}          # (None: the eight-argument call)
+        out = self._dev.forward_smplx(*[given[k] for k in _INPUTS], **extra)
         self.dyn_row = out["dyn_row"]
         verts, joints = out["vertices"], self._map(out["joints_all"])
         if transl is not None:
@@ -132,9 +156,9 @@ class SMPLX:
         joints = joints_all if self.use_face_contour else joints_all[:, :-N_CONTOUR]
         return joints if self.joint_mapper is None else self.joint_mapper(joints)
 
-    def _forward_torch(self, n, given, transl, expression, return_verts, return_full_pose):
+    def _forward_torch(self, n, given, transl, expression, with_expr, return_verts, return_full_pose):
         import torch
-        like = next(x for x in list(given.values()) + [transl] if _is_tensor(x))
+        like = next(x for x in list(given.values()) + [transl, expression] if _is_tensor(x))
         widths = {"betas": self._dev.n_betas, "body_pose": 63}
         x = {}
         for k, v in given.items():
@@ -145,15 +169,20 @@ class SMPLX:
             x[k] = v
         dev = self._dev
 
+        # with expression the Function has a ninth input, the device calls a keyword more; without, they are the eight-argument calls
         def forward(*arrays):
-            out = dev.forward_smplx(*arrays)
+            out = dev.forward_smplx(*arrays[:8], **({"expression": arrays[8]} if with_expr else {}))
             self.dyn_row = out["dyn_row"]
             return out["vertices"], out["joints_all"], out["full_pose"]
 
         def vjp(arrays, cot):
-            return dev.vjp_smplx(*arrays, dverts=cot[0], djoints_all=cot[1], dfull_pose=cot[2])
+            return dev.vjp_smplx(*arrays[:8], dverts=cot[0], djoints_all=cot[1], dfull_pose=cot[2],
+                                 **({"expression": arrays[8]} if with_expr else {}))
 
-        verts, joints_all, full_pose = _autograd.apply(forward, vjp, [x[k] for k in _INPUTS])
+        inputs = [x[k] for k in _INPUTS]
+        if with_expr:
+            inputs.append(expression if _is_tensor(expression) else torch.as_tensor(np.asarray(expression), device=like.device))
+        verts, joints_all, full_pose = _autograd.apply(forward, vjp, inputs)
         joints = self._map(joints_all)
         if transl is not None:                          # smplx: joints += transl.unsqueeze(1); vertices += transl.unsqueeze(1)
             t = transl if _is_tensor(transl) else torch.as_tensor(np.asarray(transl), dtype=verts.dtype, device=verts.device)

@@ -67,7 +67,8 @@ typedef struct bf_model_desc {
     const int32_t *faces;          /* [n_faces,3] */
     /* ---- SMPL-X (smplx.create(model_type='smplx', use_face_contour=True, use_pca with 6 comps), smplify.py:59-80).
      * model_kind 0 = SMPL (everything below ignored), 1 = SMPL-X: joints 0 root, 1..21 body, 22 jaw, 23/24 eyes,
-     * 25..39 / 40..54 left / right hand; n_betas = 10 (expression stays 0, smplify.py:167-173); the optimised
+     * 25..39 / 40..54 left / right hand; n_betas = 10 (the expression directions are attached apart, by bf_model_set_expression;
+     * the fit leaves expression at 0, smplify.py:167-173); the optimised
      * vector is transl3 scale1 body_pose63 betas10 global_orient3 leye3 reye3 left_hand_pca6 right_hand_pca6 (98). */
     int32_t model_kind;
     const float *pose_mean;                 /* [3 NJ], added to the assembled full pose */
@@ -165,8 +166,9 @@ int bf_smpl_vjp(bf_model *m, int n, const float *betas, const float *global_orie
 
 /* smplx.create(model_type='smplx', use_pca=True, flat_hand_mean=False, use_face_contour=True)'s forward (smplify.py:59-80,
  * 177-190) and its vector-Jacobian product for `n` parameter sets of an SMPL-X-kind model; SMPL-kind models: BF_ERR_UNSUPPORTED.
- * `expression` is not an input: the device model carries the shape directions only (bf_model_create: n_betas <= 12), so the
- * expression coefficients stay zero, as they do in the reference loop, which never optimises them (smplify.py:167-173). */
+ * `expression` is an input of the _expr variants below, on a model bf_model_set_expression gave its directions to; the device
+ * model itself carries the shape directions only (bf_model_create: n_betas <= 12), and the fit never optimises expression
+ * (smplify.py:167-173). */
 typedef struct bf_smplx_params {          /* betas, global_orient, body_pose are required; a NULL among the others = zeros */
     const float *betas;                    /* [n,NB] */
     const float *global_orient;            /* [n,3] */
@@ -193,6 +195,22 @@ int bf_smplx_forward(bf_model *m, int n, const bf_smplx_params *in, const bf_smp
  * inputs give equal bits.  The contour landmarks' row is an integer look-up: no gradient flows through the choice, only through
  * the barycentric combination of the chosen faces' vertices. */
 int bf_smplx_vjp(bf_model *m, int n, const bf_smplx_params *in, const bf_smplx_cotangents *cot, const bf_smplx_grads *grads);
+
+/* SMPL-X expression coefficients (smplx lbs(): v_shaped = v_template + shapedirs betas + exprdirs expression, the rest joints
+ * regressed from it).  bf_model_set_expression attaches exprdirs[NV,3,n_expr] - the columns behind the 10 shape directions of an
+ * SMPL-X file's shapedirs - to an SMPL-X-kind model, once, before any call that uses them: SMPL-kind models and n_expr outside
+ * 1..16 are BF_ERR_UNSUPPORTED, a second call is BF_ERR_INVALID.
+ * bf_model_n_expression: their number, 0 when none is attached. */
+int bf_model_set_expression(bf_model *m, int n_expr, const float *exprdirs);
+int bf_model_n_expression(const bf_model *m);
+/* bf_smplx_forward / bf_smplx_vjp with expression[n,n_expr]; dexpression[n,n_expr] (NULL = not wanted).  expression == NULL is
+ * exactly the call without it: the same launches, the same bits (dexpression must then be NULL).  With expression on a model
+ * without directions: BF_ERR_UNSUPPORTED.  Around the unchanged passes of the model, kernels of their own add the expression
+ * term, which is affine for fixed rotations; every sum has a fixed order, and a dexpression left NULL changes no other bit.
+ * The fit (bf_fit, bf_group_*) and bf_model_forward's packed vector do not take expression. */
+int bf_smplx_forward_expr(bf_model *m, int n, const bf_smplx_params *in, const float *expression, const bf_smplx_outputs *out);
+int bf_smplx_vjp_expr(bf_model *m, int n, const bf_smplx_params *in, const float *expression, const bf_smplx_cotangents *cot,
+                      const bf_smplx_grads *grads, float *dexpression);
 
 /* MaxMixturePrior's buffers (smplify/prior.py:142-160) on one device, uploaded once: means[M,D], precisions[M,D,D],
  * nll_weights[M] (positive).  At most 16 components of at most 128 dimensions (BF_ERR_UNSUPPORTED beyond). */

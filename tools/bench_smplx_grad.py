@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sizes", default="1,8,64,256")
     ap.add_argument("--no-smpl", action="store_true", help="skip the SMPL comparison (the run under the profiler)")
+    ap.add_argument("--expression", action="store_true", help="time every call with expression coefficients as well (expr_* columns; "
+                    "--summarize lists those calls as 'forward +expression' / 'vjp +expression')")
     ap.add_argument("--summarize", metavar="DB", help="print the kernel split of a rocprofv3 run of this tool and exit")
     a = ap.parse_args()
     if a.summarize:
@@ -51,6 +53,13 @@ def main():
                "vjp_ms": round(bwd[0], 3), "vjp_min_ms": round(bwd[1], 3),
                "forward_backward_ms": round(both[0], 3), "forward_backward_min_ms": round(both[1], 3),
                "forward_backward_per_frame_us": round(both[0] * 1e3 / n, 1)}
+        if a.expression:                    # the same calls with expression[n, n_expression] (bf_smplx_forward_expr / bf_smplx_vjp_expr)
+            e = f32(0.7, n, dev.n_expression)
+            x_fwd = timed(lambda: dev.forward_smplx(*p, expression=e), a.reps, a.warmup)
+            x_bwd = timed(lambda: dev.vjp_smplx(*p, **cot, expression=e), a.reps, a.warmup)
+            x_both = timed(lambda: (dev.forward_smplx(*p, expression=e), dev.vjp_smplx(*p, **cot, expression=e)), a.reps, a.warmup)
+            row.update(expr_forward_ms=round(x_fwd[0], 3), expr_vjp_ms=round(x_bwd[0], 3), expr_forward_backward_ms=round(x_both[0], 3),
+                       expr_forward_backward_min_ms=round(x_both[1], 3), expr_over_plain=round(x_both[0] / both[0], 3))
         if smpl is not None:
             q = (p[0], p[1], f32(0.3, n, 69))
             sc = (f32(1, n, smpl.n_verts, 3), f32(1, n, smpl.n_joint_map, 3), f32(1, n, smpl.n_joints + smpl.n_selector, 3))
