@@ -102,6 +102,16 @@ SIGNATURES = {
     "bf_gmm_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.POINTER(_VP)]),
     "bf_gmm_destroy": (None, [_VP]),
     "bf_keypoint_loss": (C.c_int, [C.c_int, _VP, C.POINTER(KeypointLossIn), C.POINTER(Hyper), _FP, _FP, _FP, _FP, _FP]),
+    "bf_workspace_create": (C.c_int, [C.c_int, C.POINTER(_VP)]),
+    "bf_workspace_destroy": (None, [_VP]),
+    # the device route: (model,) workspace, stream, then the host call's arguments as device addresses
+    "bf_smpl_forward_dev": (C.c_int, [_VP, _VP, _VP, C.c_int] + [_VP] * 6),
+    "bf_smpl_vjp_dev": (C.c_int, [_VP, _VP, _VP, C.c_int] + [_VP] * 9),
+    "bf_smplx_forward_dev": (C.c_int, [_VP, _VP, _VP, C.c_int, C.POINTER(SmplxParams), _VP, C.POINTER(SmplxOutputs)]),
+    "bf_smplx_vjp_dev": (C.c_int, [_VP, _VP, _VP, C.c_int, C.POINTER(SmplxParams), _VP, C.POINTER(SmplxCotangents), C.POINTER(SmplxGrads), _VP]),
+    "bf_keypoint_loss_dev": (C.c_int, [_VP, _VP, _VP, C.POINTER(KeypointLossIn), C.POINTER(Hyper)] + [_VP] * 5),
+    "bf_device_pointer_check": (C.c_int, [C.c_int, _VP]),
+    "bf_dev_route_stats": (C.c_int, [C.POINTER(C.c_int64)]),
     "bf_topo_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _IP, C.POINTER(_VP)]),
     "bf_topo_destroy": (None, [_VP]),
     "bf_vertex_normals": (C.c_int, [_VP, _FP, _FP]),
@@ -310,3 +320,8 @@ def fptr(a):
 
 def iptr(a):
     return a.ctypes.data_as(_IP) if a is not None else None
+
+
+def at(address, kind=_FP):
+    """a device address (an integer; 0 / None: NULL) as the pointer type a struct field of the ABI takes"""
+    return C.cast(C.c_void_p(address), kind) if address else None

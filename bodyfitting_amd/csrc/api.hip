@@ -165,6 +165,7 @@ extern "C" {
 int bf_smpl_forward(bf_model *m, int n, const float *betas, const float *global_orient, const float *body_pose,
                     float *vertices, float *joints, float *joints_ori) {
     if (!m || n <= 0 || !betas || !global_orient || !body_pose) return fail(BF_ERR_INVALID, "bf_smpl_forward: bad argument");
+    ++bf_route_stats().host;
     HIP_TRY(hipSetDevice(m->device));
     const int nj = m->nj, nb = m->nb, nv = m->nv;
     const size_t stride = bf_state_stride(nj, m->npf, nb);

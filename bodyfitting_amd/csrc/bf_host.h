@@ -157,6 +157,12 @@ hipError_t bf_grow(hipStream_t s, DevBuf<T> &b, size_t count) {
     return b.alloc(count);
 }
 
+// bf_dev_route_stats: calls of the host entry points a torch loop goes through (bf_smpl_forward, bf_smpl_vjp, bf_smplx_forward[_expr],
+// bf_smplx_vjp[_expr], bf_keypoint_loss), calls of their *_dev twins, device (re)allocations of workspaces, and calls that had to wait
+// for their workspace's previous call on another stream.  Process-wide; counted once the arguments have passed.
+struct BfRouteStats { std::atomic<long long> host{0}, dev{0}, allocs{0}, switches{0}; };
+inline BfRouteStats &bf_route_stats() { static BfRouteStats S; return S; }
+
 // vertex -> (face, corner) lists in the order compute_normal_torch (io_utils.py:406-428) adds a vertex's face normals up: corner by
 // corner, faces ascending.  start[nv + 1] = CSR offsets, adj[3 nf] = face * 4 + corner.  `faces` holds 3 nf indices inside [0, nv).
 // Shared by the SMPL+D stage (bf_fit_displacement) and bf_topo_create.

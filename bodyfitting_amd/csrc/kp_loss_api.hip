@@ -2,6 +2,7 @@
 // MaxMixturePrior as one stateless call on host arrays - what a user's own torch loop (smplify.py:177-213) evaluates behind the
 // body model.  One launch of bf_keypoint_loss_kernel (kp_loss_kernels.hip); the call's buffers come from the device's block cache.
 #include "bf_host.h"
+#include "dev_route.h"
 #include "kp_loss_kernels.h"
 
 
@@ -71,6 +72,7 @@ extern "C" int bf_keypoint_loss(int device, const bf_gmm *gmm, const bf_keypoint
     if (!in) return fail(BF_ERR_INVALID, "bf_keypoint_loss: bad argument");
     if (gmm && gmm->device != device) return fail(BF_ERR_INVALID, "bf_keypoint_loss: the GMM lives on another device");
     BF_TRY(bf_kp_loss_check(gmm, in, dposes, dbetas));
+    ++bf_route_stats().host;
     if (!terms && !djoints && !dposes && !dbetas) return BF_OK;
     bf_hyper h;
     if (hyper) h = *hyper; else bf_hyper_default(&h);
@@ -117,5 +119,49 @@ extern "C" int bf_keypoint_loss(int device, const bf_gmm *gmm, const bf_keypoint
     if (Q.djoints) HIP_TRY(hipMemcpy(djoints, d_dj.p, N * R * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (dposes) HIP_TRY(hipMemcpy(dposes, d_dp.p, N * in->pose_dim * sizeof(float), hipMemcpyDeviceToHost));
     if (dbetas) HIP_TRY(hipMemcpy(dbetas, d_db.p, N * in->n_betas * sizeof(float), hipMemcpyDeviceToHost));
+    return BF_OK;
+}
+
+// The device route (dev_route.h): the same launch on the caller's stream.  Every array of `in` but `divisor` is a device pointer and is
+// read where it lies; the results are written where the caller wants them; divisor[n], validated on the host as above, is the one
+// thing sent, through the workspace, and only when it differs from what the workspace sent last.
+extern "C" int bf_keypoint_loss_dev(bf_workspace *ws, void *stream, const bf_gmm *gmm, const bf_keypoint_loss_in *in, const bf_hyper *hyper,
+                                    const float *dterms, float *terms, float *djoints, float *dposes, float *dbetas) {
+    if (!ws || !in) return fail(BF_ERR_INVALID, "bf_keypoint_loss_dev: bad argument");
+    if (gmm && gmm->device != ws->device) return fail(BF_ERR_INVALID, "bf_keypoint_loss_dev: the GMM lives on another device than the workspace");
+    BF_TRY(bf_kp_loss_check(gmm, in, dposes, dbetas));
+    bf_hyper h;
+    if (hyper) h = *hyper; else bf_hyper_default(&h);
+    if (!(h.imsize > 0.f)) return fail(BF_ERR_INVALID, "bf_keypoint_loss_dev: imsize must be positive");
+    ++bf_route_stats().dev;
+    if (!terms && !djoints && !dposes && !dbetas) return BF_OK;
+    BfDeviceGuard keep;
+    HIP_TRY(hipSetDevice(ws->device));
+    const hipStream_t s = (hipStream_t)stream;
+    const size_t N = (size_t)in->n;
+    const bool views = in->n_views > 0 && in->n_rows > 0;
+    BfWsCall call(ws, s);
+    BF_TRY(call.begin());
+    KpLossIO Q{};
+    Q.n_views = views ? in->n_views : 0;
+    Q.n_rows = in->n_rows;
+    if (in->n_rows > 0) Q.joints = in->joints;
+    if (views) {
+        Q.w2c = in->w2c; Q.K = in->K; Q.keypoints = in->keypoints; Q.present = in->present;
+        BF_TRY(bf_ws_divisor(ws, s, in->divisor, N, &Q.divisor));
+    }
+    if (in->poses) {
+        Q.pose_dim = in->pose_dim;
+        Q.poses = in->poses;
+        if (gmm) { Q.gmm_comp = gmm->n_comp; Q.gmm_dim = gmm->dim; Q.g_means = gmm->means.p; Q.g_prec = gmm->prec.p; Q.g_logw = gmm->logw.p; }
+    }
+    if (in->betas) { Q.n_betas = in->n_betas; Q.betas = in->betas; }
+    Q.dterms = dterms;
+    Q.terms = terms;
+    if (in->n_rows > 0) Q.djoints = djoints;
+    Q.dposes = dposes;
+    Q.dbetas = dbetas;
+    hipLaunchKernelGGL(bf_keypoint_loss_kernel, dim3((unsigned)N), dim3(BF_KPL_THREADS), 0, s, Q, bf_to_dev(h));
+    HIP_TRY(hipGetLastError());
     return BF_OK;
 }

@@ -2,7 +2,16 @@
 #pragma once
 #include "bf_internal.h"
 
+// bf_block_scatter_kernel's destinations: block b is columns [off, off + cnt) of every row and goes to dst[b][n][cnt] (null: not wanted)
+#define BF_SCATTER_MAX 8
+struct BfScatter {
+    float *dst[BF_SCATTER_MAX];
+    int off[BF_SCATTER_MAX], cnt[BF_SCATTER_MAX];
+    int n_blocks;
+};
+
 #pragma GCC visibility push(hidden)       // (a kernel's host-side handle does not follow -fvisibility: see the Makefile)
+extern "C" __global__ void bf_block_scatter_kernel(const float *rows, int n, int stride, BfScatter S);
 extern "C" __global__ void bf_model_vjp_fold_kernel(MeshTab M, const float *dvertices, const float *djoints, const float *ddirect, int n_direct, const int *lmk_vid,
                                                     const float *lmk_w, float *dv, float *dchain);
 extern "C" __global__ void bf_smpl_vjp_chain_kernel(FitTab T, const float *state, const float *ext, int ext_stride, const float *dchain, float *dtheta,

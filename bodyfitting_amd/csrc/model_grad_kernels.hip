@@ -329,3 +329,16 @@ bf_smplx_pose_reverse_kernel(FitTab T, const float *__restrict__ dtheta, const f
         out[f * stride + 3 * nj + tid] = acc;
     }
 }
+
+// One thread per element of rows[n][stride]: the row cut into the caller's blocks, dst[b][f][c - off[b]] = rows[f][c] for the block that
+// holds column c (null dst, or no block: dropped).  This is what the host route does with memcpy after its copy back; a few hundred
+// floats per frame go through plain loads and stores here, and nothing in it is worth tuning.
+extern "C" __global__ void __launch_bounds__(256)
+bf_block_scatter_kernel(const float *__restrict__ rows, int n, int stride, BfScatter S) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n * stride) return;
+    const size_t f = i / stride;
+    const int c = (int)(i - f * stride);
+    for (int b = 0; b < S.n_blocks && b < BF_SCATTER_MAX; ++b)
+        if (S.dst[b] && c >= S.off[b] && c < S.off[b] + S.cnt[b]) S.dst[b][f * S.cnt[b] + (c - S.off[b])] = rows[i];
+}

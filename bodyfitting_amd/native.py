@@ -5,6 +5,7 @@ Host code is plain Python + numpy + ctypes; PyTorch is not involved on this path
 from __future__ import annotations
 
 import ctypes as C
+import threading
 
 import numpy as np
 
@@ -111,6 +112,43 @@ def model_desc(model, gmm):
     return d, info, keep
 
 
+class Workspace:
+    """The scratch of one caller of the device route (bf_workspace): grow-only device buffers and one event on GPU `device`.
+    One call at a time: the *_dev wrappers hold `lock` around theirs."""
+
+    def __init__(self, device=0):
+        self._lib = _lib.load()
+        self.device = int(device)
+        self.lock = threading.Lock()
+        self._h = C.c_void_p()
+        _lib.check(self._lib.bf_workspace_create(self.device, C.byref(self._h)), "bf_workspace_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            with self.lock:
+                self._lib.bf_workspace_destroy(self._h)
+                self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def device_pointer_check(device, address):
+    """does the library's HIP runtime know `address` as memory of GPU `device` (bf_device_pointer_check) - in a torch process: do
+    torch and the library share one runtime, so that a tensor's data_ptr() and a stream's handle mean something in here"""
+    return _lib.load().bf_device_pointer_check(int(device), C.c_void_p(address or None)) == 0
+
+
+def dev_route_stats():
+    """bf_dev_route_stats -> dict(host_calls, dev_calls, allocations, stream_switches), process-wide"""
+    out = (C.c_int64 * 4)()
+    _lib.check(_lib.load().bf_dev_route_stats(out), "bf_dev_route_stats")
+    return dict(zip(("host_calls", "dev_calls", "allocations", "stream_switches"), (int(v) for v in out)))
+
+
 class DeviceModel:
     """Body model + GMM prior uploaded once to one GPU (replaces the per-frame construction at
     reference smplify/body_fitting.py:82 -> smplify/smplify.py:46-56).  An SMPL-X model dict whose shapedirs has more than
@@ -145,6 +183,9 @@ class DeviceModel:
         return ids
 
     def close(self):
+        ws = self.__dict__.pop("_workspace", None)
+        if ws is not None:
+            ws.close()
         if getattr(self, "_h", None):
             self._lib.bf_model_destroy(self._h)
             self._h = None
@@ -154,6 +195,55 @@ class DeviceModel:
             self.close()
         except Exception:
             pass
+
+    def workspace(self):
+        """the model's own `Workspace` for the device route, made on first use and closed with the model"""
+        ws = self.__dict__.get("_workspace")
+        if ws is None:
+            ws = self.__dict__.setdefault("_workspace", Workspace(self.device))
+        return ws
+
+    # The device route (bf_*_dev): the four calls below on device ADDRESSES (integers, e.g. a tensor's data_ptr(); 0 / None = NULL)
+    # of contiguous float32 arrays on the model's GPU, queued on `stream` (a hipStream_t handle, 0: the null stream).  They return
+    # when the work is queued; the arrays must outlive it on that stream.  ws: a `Workspace` (None: the model's own).
+
+    def forward_dev(self, n, stream, betas, global_orient, body_pose, vertices=0, joints=0, joints_ori=0, ws=None):
+        """`forward` into vertices[n,NV,3], joints[n,n_joint_map,3], joints_ori[n,NJ+n_selector,3] (bf_smpl_forward_dev)"""
+        ws = ws or self.workspace()
+        with ws.lock:
+            _lib.check(self._lib.bf_smpl_forward_dev(self._h, ws._h, stream or None, int(n), betas or None, global_orient or None,
+                                                     body_pose or None, vertices or None, joints or None, joints_ori or None),
+                       "bf_smpl_forward_dev")
+
+    def vjp_dev(self, n, stream, betas, global_orient, body_pose, dverts=0, djoints=0, djoints_ori=0, dbetas=0, dglobal_orient=0,
+                dbody_pose=0, ws=None):
+        """`vjp` into dbetas[n,NB], dglobal_orient[n,3], dbody_pose[n,3(NJ-1)]; a gradient left 0 is not computed (bf_smpl_vjp_dev)"""
+        ws = ws or self.workspace()
+        with ws.lock:
+            _lib.check(self._lib.bf_smpl_vjp_dev(self._h, ws._h, stream or None, int(n), betas or None, global_orient or None,
+                                                 body_pose or None, dverts or None, djoints or None, djoints_ori or None,
+                                                 dbetas or None, dglobal_orient or None, dbody_pose or None), "bf_smpl_vjp_dev")
+
+    def forward_smplx_dev(self, n, stream, params, expression=0, vertices=0, joints=0, joints_all=0, full_pose=0, dyn_row=0, ws=None):
+        """`forward_smplx` (bf_smplx_forward_dev): params = the eight addresses in forward_smplx's order (the optional five may be
+        0); dyn_row: an int32[n] array"""
+        ws = ws or self.workspace()
+        par = _lib.SmplxParams(*[_lib.at(a) for a in params])
+        out = _lib.SmplxOutputs(_lib.at(vertices), _lib.at(joints), _lib.at(joints_all), _lib.at(full_pose), _lib.at(dyn_row, _lib._IP))
+        with ws.lock:
+            _lib.check(self._lib.bf_smplx_forward_dev(self._h, ws._h, stream or None, int(n), C.byref(par), expression or None,
+                                                      C.byref(out)), "bf_smplx_forward_dev")
+
+    def vjp_smplx_dev(self, n, stream, params, expression=0, dverts=0, djoints=0, djoints_all=0, dfull_pose=0, grads=(0,) * 8,
+                      dexpression=0, ws=None):
+        """`vjp_smplx` (bf_smplx_vjp_dev): grads = the eight destination addresses in the parameters' order (0: not wanted)"""
+        ws = ws or self.workspace()
+        par = _lib.SmplxParams(*[_lib.at(a) for a in params])
+        cot = _lib.SmplxCotangents(*[_lib.at(a) for a in (dverts, djoints, djoints_all, dfull_pose)])
+        dst = _lib.SmplxGrads(*[_lib.at(a) for a in grads])
+        with ws.lock:
+            _lib.check(self._lib.bf_smplx_vjp_dev(self._h, ws._h, stream or None, int(n), C.byref(par), expression or None,
+                                                  C.byref(cot), C.byref(dst), dexpression or None), "bf_smplx_vjp_dev")
 
     def forward(self, betas, global_orient, body_pose):
         """models.smpl.SMPL.forward (reference models/smpl.py:69-83): -> vertices, joints49, joints45."""
@@ -659,9 +749,19 @@ class Gmm:
                                      C.byref(self._h)), "bf_gmm_create")
 
     def close(self):
+        ws = self.__dict__.pop("_workspace", None)
+        if ws is not None:
+            ws.close()
         if getattr(self, "_h", None):
             self._lib.bf_gmm_destroy(self._h)
             self._h = None
+
+    def workspace(self):
+        """the `Workspace` of device-route losses with this prior, made on first use and closed with it"""
+        ws = self.__dict__.get("_workspace")
+        if ws is None:
+            ws = self.__dict__.setdefault("_workspace", Workspace(self.device))
+        return ws
 
     def __del__(self):  # pragma: no cover
         try:
@@ -736,6 +836,39 @@ def keypoint_loss(joints, w2c=None, K=None, keypoints=None, present=None, diviso
                                             _lib.fptr(out.get("terms")), _lib.fptr(out.get("djoints")), _lib.fptr(out.get("dposes")),
                                             _lib.fptr(out.get("dbetas"))), "bf_keypoint_loss")
     return out
+
+
+_LOSS_WORKSPACES = {}          # device -> the Workspace of device-route losses without a GMM
+
+
+def loss_workspace(gmm=None, device=0):
+    """the workspace a device-route keypoint loss runs on: the GMM's, or, without one, the one of `device`"""
+    if gmm is not None:
+        return gmm.workspace()
+    if int(device) not in _LOSS_WORKSPACES:
+        _LOSS_WORKSPACES[int(device)] = Workspace(device)
+    return _LOSS_WORKSPACES[int(device)]
+
+
+def keypoint_loss_dev(stream, n, rows=0, joints=0, n_views=0, w2c=0, K=0, keypoints=0, present=0, divisor=None, pose_dim=0, poses=0,
+                      n_betas=0, betas=0, gmm=None, hyper=None, dterms=0, terms=0, djoints=0, dposes=0, dbetas=0, device=0, ws=None):
+    """bf_keypoint_loss_dev: `keypoint_loss` on device addresses (integers; 0 = NULL), queued on `stream`.  joints[n,rows,3],
+    w2c[n,V,4,4], K[n,V,3,3], keypoints[n,V,rows,3], present[n,V] uint8, poses[n,pose_dim], betas[n,n_betas], dterms[n,4] ->
+    terms[n,4], djoints, dposes, dbetas (0: not wanted).  divisor stays a host array of n ints.  ws: None = loss_workspace(gmm, device)."""
+    ws = ws or loss_workspace(gmm, device)
+    q = _lib.KeypointLossIn()
+    q.n, q.n_views, q.n_rows, q.joints = int(n), int(n_views), int(rows), _lib.at(joints)
+    keep = None
+    if n_views:
+        keep = _i32(divisor).reshape(n)
+        q.w2c, q.K, q.keypoints, q.divisor = _lib.at(w2c), _lib.at(K), _lib.at(keypoints), _lib.iptr(keep)
+        q.present = _lib.at(present, C.POINTER(C.c_uint8))
+    q.pose_dim, q.poses, q.n_betas, q.betas = int(pose_dim), _lib.at(poses), int(n_betas), _lib.at(betas)
+    with ws.lock:
+        _lib.check(_lib.load().bf_keypoint_loss_dev(ws._h, stream or None, gmm._h if gmm is not None else None, C.byref(q),
+                                                    C.byref(hyper) if hyper is not None else None, dterms or None, terms or None,
+                                                    djoints or None, dposes or None, dbetas or None), "bf_keypoint_loss_dev")
+    del keep
 
 
 class FrameBatch:

@@ -3,7 +3,8 @@ min_m (0.5 d' P_m d - log w_m) and its gradient with respect to the pose, throug
 weight 1 and the other weights 0.
 
 numpy in -> numpy out; torch tensors in -> a differentiable float32 tensor on the pose's device (torch is imported on that path
-only).  `use_merged=False` (prior.py:198-225) and dtypes other than float32 are refused, not approximated.
+only); a float32 tensor on the prior's GPU goes into the kernel where it lies, on torch's current stream (bf_keypoint_loss_dev:
+the device route of _autograd.py).  `use_merged=False` (prior.py:198-225) and dtypes other than float32 are refused, not approximated.
 """
 from __future__ import annotations
 
@@ -58,6 +59,33 @@ def device_gmm(obj, device=None):
     return cache[device]
 
 
+class _DeviceRoute:
+    """merged_log_likelihood on a pose of the prior's GPU (_autograd.apply's device_route): bf_keypoint_loss_dev with no views"""
+
+    def __init__(self, gmm, hyper):
+        self.gmm, self.hyper, self.device = gmm, hyper, gmm.device
+
+    def forward(self, x, stream):
+        import torch
+        from . import native
+        p = x[0]
+        terms = torch.empty((p.shape[0], 4), dtype=torch.float32, device=p.device)
+        native.keypoint_loss_dev(stream, p.shape[0], pose_dim=p.shape[1], poses=p.data_ptr(), gmm=self.gmm, hyper=self.hyper,
+                                 terms=terms.data_ptr())
+        return (terms[:, 1],)
+
+    def vjp(self, x, cotangents, want, stream):
+        import torch
+        from . import native
+        p = x[0]
+        dterms = torch.zeros((p.shape[0], 4), dtype=torch.float32, device=p.device)
+        dterms[:, 1] = cotangents[0].reshape(-1)
+        dposes = torch.empty_like(p)
+        native.keypoint_loss_dev(stream, p.shape[0], pose_dim=p.shape[1], poses=p.data_ptr(), gmm=self.gmm, hyper=self.hyper,
+                                 dterms=dterms.data_ptr(), dposes=dposes.data_ptr())
+        return (dposes,)
+
+
 class MaxMixturePrior:
     def __init__(self, prior_folder="prior", num_gaussians=6, dtype="torch.float32", epsilon=1e-16, use_merged=True, **kwargs):
         if str(dtype) not in _FLOAT32_NAMES:
@@ -101,7 +129,9 @@ class MaxMixturePrior:
         _require_float32("MaxMixturePrior", "pose", pose)
         if pose.ndim != 2:
             raise ValueError("MaxMixturePrior: pose must be [B, D]")
-        return _autograd.apply(forward, vjp, (pose,))[0] if _is_tensor(pose) else forward(pose)[0]
+        if not _is_tensor(pose):
+            return forward(pose)[0]
+        return _autograd.apply(forward, vjp, (pose,), device_route=_DeviceRoute(gmm, hyper))[0]
 
     def forward(self, pose, betas):
         return self.merged_log_likelihood(pose, betas)

@@ -7,7 +7,8 @@ Two paths:
 * numpy in -> numpy out, in model space (`transl` is ignored there: INTEGRATION.md).
 * torch tensors in -> torch tensors out on the inputs' device, differentiable w.r.t. betas / global_orient / body_pose through
   the HIP forward and its vector-Jacobian product (bf_smpl_vjp), and w.r.t. transl as smplx + the wrapper apply it.  torch
-  is imported on this path only.
+  is imported on this path only.  float32 tensors on the model's GPU go into the kernels where they lie, on torch's current
+  stream (bf_smpl_forward_dev / bf_smpl_vjp_dev: the device route of _autograd.py); everything else goes through host memory.
 """
 from __future__ import annotations
 
@@ -69,7 +70,8 @@ class SMPL:
         betas, global_orient, body_pose = (x if _is_tensor(x) else torch.as_tensor(np.asarray(x), dtype=like.dtype, device=like.device)
                                            for x in (betas, global_orient, body_pose))
         dev = self._dev
-        verts, joints, jori = _autograd.apply(dev.forward, lambda x, cot: dev.vjp(*x, *cot), (betas, global_orient, body_pose))
+        verts, joints, jori = _autograd.apply(dev.forward, lambda x, cot: dev.vjp(*x, *cot), (betas, global_orient, body_pose),
+                                              device_route=_DeviceRoute(dev))
         if transl is not None:
             # smplx adds transl to the vertices and its 45 joints; the wrapper's 9 extra joints are J_regressor_extra (v + t), i.e. each
             # moves by its regressor row's sum times t (models/smpl.py:71-75)
@@ -99,3 +101,43 @@ class SMPL:
 
 def _is_tensor(x):
     return hasattr(x, "detach") and hasattr(x, "requires_grad")
+
+
+def require_elements(who, named, n):
+    """every (name, tensor or None, width) holds n * width elements: the kernels index by these sizes"""
+    for name, t, width in named:
+        if t is not None and t.numel() != n * width:
+            raise ValueError(f"{who}: {name} has {t.numel()} elements, [{n}, {width}] are expected")
+
+
+def address(t):
+    return 0 if t is None else t.data_ptr()
+
+
+class _DeviceRoute:
+    """`DeviceModel.forward` / `vjp` on tensors of the model's GPU (_autograd.apply's device_route)"""
+
+    def __init__(self, dev):
+        # (a device model without the *_dev calls - a stand-in - offers no device route)
+        self.dev, self.device = dev, getattr(dev, "device", None) if hasattr(dev, "forward_dev") else None
+
+    def _n(self, x):
+        d = self.dev
+        n = x[0].numel() // d.n_betas
+        require_elements("SMPL.forward", (("betas", x[0], d.n_betas), ("global_orient", x[1], 3), ("body_pose", x[2], 3 * (d.n_joints - 1))), n)
+        return n
+
+    def forward(self, x, stream):
+        import torch
+        d, n = self.dev, self._n(x)
+        out = [torch.empty((n, rows, 3), dtype=torch.float32, device=x[0].device)
+               for rows in (d.n_verts, d.n_joint_map, d.n_joints + d.n_selector)]
+        d.forward_dev(n, stream, *[address(t) for t in x], *[address(t) for t in out])
+        return tuple(out)
+
+    def vjp(self, x, cotangents, want, stream):
+        import torch
+        d, n = self.dev, self._n(x)
+        grads = [torch.empty((n, t.numel() // n), dtype=torch.float32, device=t.device) if w else None for t, w in zip(x, want)]
+        d.vjp_dev(n, stream, *[address(t) for t in x], *[address(c) for c in cotangents], *[address(g) for g in grads])
+        return grads

@@ -9,7 +9,10 @@ Two paths, as `bodyfitting_amd.smpl.SMPL` has them:
 * torch tensors in -> torch tensors out on the inputs' device, differentiable w.r.t. betas, global_orient, body_pose, jaw_pose,
   leye_pose, reye_pose, left_hand_pose, right_hand_pose and expression through the HIP forward and its vector-Jacobian
   product (bf_smplx_forward / bf_smplx_vjp and their _expr variants), once.  The contour landmarks' row is an integer look-up:
-  no gradient flows through the choice.  torch is imported on this path only.
+  no gradient flows through the choice.  torch is imported on this path only.  float32 tensors on the model's GPU go into
+  the kernels where they lie, on torch's current stream (bf_smplx_forward_dev / bf_smplx_vjp_dev: the device route of
+  _autograd.py) - an argument not passed is a NULL pointer there, and `dyn_row` is then an int32 tensor on that GPU, not read
+  back; everything else goes through host memory.
 
 `expression` [B, n_expression] is an input of its own on a device model with expression directions (a model file's shapedirs
 columns behind the 10 shape directions, `DeviceModel.n_expression` of them): zero or not, it goes through the device and, as a
@@ -25,7 +28,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _autograd, assets, layout
-from .smpl import SMPL, ModelOutput, _is_tensor
+from .smpl import SMPL, ModelOutput, _is_tensor, address, require_elements
 
 N_CONTOUR = 17          # the landmarks `use_face_contour` adds at the end of smplx's joints
 _INPUTS = ("betas", "global_orient", "body_pose", "jaw_pose", "leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose")
@@ -182,7 +185,7 @@ class SMPLX:
         inputs = [x[k] for k in _INPUTS]
         if with_expr:
             inputs.append(expression if _is_tensor(expression) else torch.as_tensor(np.asarray(expression), device=like.device))
-        verts, joints_all, full_pose = _autograd.apply(forward, vjp, inputs)
+        verts, joints_all, full_pose = _autograd.apply(forward, vjp, inputs, device_route=_DeviceRoute(self, with_expr))
         joints = self._map(joints_all)
         if transl is not None:                          # smplx: joints += transl.unsqueeze(1); vertices += transl.unsqueeze(1)
             t = transl if _is_tensor(transl) else torch.as_tensor(np.asarray(transl), dtype=verts.dtype, device=verts.device)
@@ -195,6 +198,43 @@ class SMPLX:
     def to(self, *args, **kwargs):
         """nn.Module.to's place in smplify.py:80: the HIP model stays on the constructor's `device`"""
         return self
+
+
+class _DeviceRoute:
+    """`DeviceModel.forward_smplx` / `vjp_smplx` on tensors of the model's GPU (_autograd.apply's device_route): the eight
+    parameter blocks, and with_expr the coefficients behind them"""
+
+    def __init__(self, owner, with_expr):
+        self.owner, self.dev, self.with_expr = owner, owner._dev, with_expr
+        self.device = getattr(self.dev, "device", None) if hasattr(self.dev, "forward_smplx_dev") else None      # (a stand-in offers no device route)
+
+    def _n(self, x):
+        d = self.dev
+        n = x[0].numel() // d.n_betas
+        widths = (d.n_betas, 3, 63, 3, 3, 3, d.n_hand_pca, d.n_hand_pca) + ((d.n_expression,) if self.with_expr else ())
+        require_elements("SMPLX.forward", tuple(zip(_INPUTS + ("expression",), x, widths)), n)
+        return n, widths
+
+    def forward(self, x, stream):
+        import torch
+        d, (n, _) = self.dev, self._n(x)
+        verts, joints_all, full_pose = (torch.empty(shape, dtype=torch.float32, device=x[0].device)
+                                        for shape in ((n, d.n_verts, 3), (n, d.n_joints_all, 3), (n, 3 * d.n_joints)))
+        dyn_row = torch.empty(n, dtype=torch.int32, device=x[0].device)
+        d.forward_smplx_dev(n, stream, [address(t) for t in x[:8]], expression=address(x[8]) if self.with_expr else 0,
+                            vertices=address(verts), joints_all=address(joints_all), full_pose=address(full_pose), dyn_row=address(dyn_row))
+        self.owner.dyn_row = dyn_row
+        return verts, joints_all, full_pose
+
+    def vjp(self, x, cotangents, want, stream):
+        import torch
+        d, (n, widths) = self.dev, self._n(x)
+        grads = [torch.empty((n, w), dtype=torch.float32, device=x[0].device) if t is not None and wanted else None
+                 for t, w, wanted in zip(x, widths, want)]
+        d.vjp_smplx_dev(n, stream, [address(t) for t in x[:8]], expression=address(x[8]) if self.with_expr else 0,
+                        dverts=address(cotangents[0]), djoints_all=address(cotangents[1]), dfull_pose=address(cotangents[2]),
+                        grads=[address(g) for g in grads[:8]], dexpression=address(grads[8]) if self.with_expr else 0)
+        return grads
 
 
 def create(model_path=None, model_type="smpl", **kwargs):

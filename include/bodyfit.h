@@ -243,6 +243,51 @@ typedef struct bf_keypoint_loss_in {
 int bf_keypoint_loss(int device, const bf_gmm *gmm, const bf_keypoint_loss_in *in, const bf_hyper *hyper,
                      const float *dterms, float *terms, float *djoints, float *dposes, float *dbetas);
 
+/* The device route: the five calls above (bf_smpl_forward, bf_smpl_vjp, bf_smplx_forward[_expr], bf_smplx_vjp[_expr],
+ * bf_keypoint_loss) on DEVICE pointers, ordered on the caller's stream.  For a caller whose arrays live on the GPU already and
+ * who shares this library's HIP runtime - a torch process that imported torch before the library was loaded, so that the
+ * loader resolved both to one libamdhip64; bf_device_pointer_check is how to find out.  In a process with two runtimes
+ * pointers and streams must not cross: use the host entry points.
+ *
+ * Every *_dev call issues its host twin's kernels, in its order, with its grids and arguments - equal inputs give the host
+ * twin's bits - on `stream` (a hipStream_t; NULL = the null stream) and returns when the work is queued.  It calls no
+ * hipDeviceSynchronize, hipStreamSynchronize, blocking hipMemcpy, hipMalloc or hipFree, except: a workspace buffer that has to
+ * grow (the first call of a shape), the model's transposed pose directions built by the first reverse call (complete on the
+ * device before that call returns), and a `divisor` that differs from the one sent last.  Every array is a contiguous float32
+ * (dyn_row: int32) device pointer on the model's device and must stay alive until `stream` reaches the end of the call.  NULL
+ * keeps its meaning (an output not wanted, a cotangent of zero).  Bad arguments fail before anything is queued, with the host
+ * twin's refusals.
+ *
+ * A workspace owns the scratch of ONE caller: grow-only device buffers and one event.  One call at a time per workspace (the
+ * caller locks).  A buffer grows only when a call needs more than it holds, after the stream it was last used on has
+ * drained; a second call of the same shapes allocates nothing and waits for nothing.  A call on another stream than the
+ * workspace's previous call first makes its stream wait for the event recorded at the end of that call.
+ * bf_workspace_destroy drains the last stream before it frees.  The device's block cache is not used on this route. */
+typedef struct bf_workspace bf_workspace;
+int bf_workspace_create(int device, bf_workspace **out);
+void bf_workspace_destroy(bf_workspace *ws);
+int bf_smpl_forward_dev(bf_model *m, bf_workspace *ws, void *stream, int n, const float *betas, const float *global_orient,
+                        const float *body_pose, float *vertices, float *joints, float *joints_ori);
+int bf_smpl_vjp_dev(bf_model *m, bf_workspace *ws, void *stream, int n, const float *betas, const float *global_orient,
+                    const float *body_pose, const float *dvertices, const float *djoints, const float *djoints_ori,
+                    float *dbetas, float *dglobal_orient, float *dbody_pose);
+/* the structs of the host calls, holding device pointers; expression NULL = the call without coefficients */
+int bf_smplx_forward_dev(bf_model *m, bf_workspace *ws, void *stream, int n, const bf_smplx_params *in, const float *expression,
+                         const bf_smplx_outputs *out);
+int bf_smplx_vjp_dev(bf_model *m, bf_workspace *ws, void *stream, int n, const bf_smplx_params *in, const float *expression,
+                     const bf_smplx_cotangents *cot, const bf_smplx_grads *grads, float *dexpression);
+/* bf_keypoint_loss_in with device pointers, except `divisor`: a HOST array of n ints, validated on the host and sent by the
+ * call.  The device is the GMM's, which must be the workspace's; without a GMM the workspace's. */
+int bf_keypoint_loss_dev(bf_workspace *ws, void *stream, const bf_gmm *gmm, const bf_keypoint_loss_in *in, const bf_hyper *hyper,
+                         const float *dterms, float *terms, float *djoints, float *dposes, float *dbetas);
+/* BF_OK when this library's HIP runtime knows `p` as device memory of `device`, else BF_ERR_INVALID (NULL, host memory, memory
+ * of another runtime or device).  Never sets bf_last_error and leaves no HIP error behind. */
+int bf_device_pointer_check(int device, const void *p);
+/* test hook, process-wide counts: out[0] calls of the five host entry points named above, out[1] calls of their _dev twins
+ * (both counted once the arguments have passed), out[2] device (re)allocations of workspaces, out[3] calls that had to wait
+ * for their workspace's previous call on another stream. */
+int bf_dev_route_stats(int64_t out[4]);
+
 /* The SMPL+D stage's losses (smplify.py:236-245) as stand-alone calls with their gradients, for a user's own torch loop: what
  * bf_fit_displacement evaluates fused, one mesh per call.  Host pointers; the calls' buffers come from the device's block cache;
  * no float atomics, every scalar is reduced in one order that depends on the sizes alone, so equal inputs give equal bits.

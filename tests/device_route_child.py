@@ -1,0 +1,454 @@
+"""The device route of the torch drop-ins in FRESH processes (tests/test_gpu_device_route.py).  This module imports torch FIRST and the
+library only inside its functions, so that the loader resolves libbodyfit's HIP runtime to the one torch brought: the shared runtime
+is a fact of these tests, not an accident of collection order.  Every function asserts the route it means to measure before it
+measures anything.  The yardstick is the host route - the numpy paths and DeviceModel.vjp / vjp_smplx, which the existing suites hold
+to the float64 oracle: the device route issues the same launches and must give the same bits."""
+import os
+import sys
+
+import numpy as np
+import torch                    # (first: see above)
+
+from lanes_child import _run
+
+CASES = ("vertices", "joints", "joints_ori", "all")
+XCASES = ("vertices", "joints", "full_pose", "all")
+XINPUTS = ("betas", "global_orient", "body_pose", "jaw_pose", "leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose")
+GPU = "cuda:0"
+
+
+def _repo():
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if repo not in sys.path:
+        sys.path.insert(0, repo)
+
+
+def _smpl_params(n, nb, seed):
+    """tests/test_gpu_smpl_autograd.py: _params, draw for draw (row 0: theta = 0, row 1: |theta| near pi)"""
+    rng = np.random.default_rng(seed)
+    betas = rng.normal(0, 0.7, (n, nb)).astype(np.float32)
+    orient = rng.normal(0, 0.8, (n, 3)).astype(np.float32)
+    pose = rng.normal(0, 0.3, (n, 69)).astype(np.float32)
+    orient[0] = 0.0
+    pose[0] = 0.0
+    if n > 1:
+        orient[1] = np.array([0.6, -0.48, 0.64], np.float32) * 3.13
+        pose[1, 0:3] = np.array([0.0, 0.8, -0.6], np.float32) * 3.14
+        pose[1, 45:48] = np.array([-0.28, 0.96, 0.0], np.float32) * 3.1
+    return betas, orient, pose
+
+
+def _smplx_params(n, seed, ne=10):
+    """tests/test_gpu_smplx_expression.py: _params, draw for draw"""
+    rng = np.random.default_rng(seed)
+    p = {"betas": rng.normal(0, 0.7, (n, 10)), "global_orient": rng.normal(0, 0.8, (n, 3)), "body_pose": rng.normal(0, 0.3, (n, 63)),
+         "jaw_pose": rng.normal(0, 0.2, (n, 3)), "leye_pose": rng.normal(0, 0.2, (n, 3)), "reye_pose": rng.normal(0, 0.2, (n, 3)),
+         "left_hand_pose": rng.normal(0, 0.4, (n, 6)), "right_hand_pose": rng.normal(0, 0.4, (n, 6))}
+    p["expression"] = rng.normal(0, 0.7, (n, ne))
+    p = {k: v.astype(np.float32) for k, v in p.items()}
+    for k in ("jaw_pose", "leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose", "expression"):
+        p[k][0] = 0.0
+    if n > 1:
+        p["global_orient"][1] = np.array([0.6, -0.48, 0.64], np.float32) * 3.13
+        p["body_pose"][1, 45:48] = np.array([-0.28, 0.96, 0.0], np.float32) * 3.1
+        p["jaw_pose"][1] = np.array([0.8, 0.0, -0.6], np.float32) * 3.12
+        p["left_hand_pose"][1] = np.array([1.2, -0.9, 1.0, 0.8, -1.1, 0.7], np.float32)
+        p["right_hand_pose"][1] = np.array([-1.0, 1.1, -0.8, 0.9, 1.2, -0.7], np.float32)
+    return p
+
+
+def _cot(shape, seed):
+    return np.random.default_rng(seed + 100).normal(0, 1, shape).astype(np.float32)
+
+
+def _install(kind, model, gmm):
+    """the drop-in of `kind` on `model`, as the existing autograd tests install theirs"""
+    from bodyfitting_amd import assets
+    assets._MODELS.clear(); assets._DEVICE_MODELS.clear()
+    assets._MODELS[(kind, "neutral")] = model
+    assets._GMM["gmm"] = gmm
+    if kind == "smpl":
+        from bodyfitting_amd.smpl import SMPL
+        return SMPL(gender="neutral")
+    from bodyfitting_amd import smplx as X
+    return X.create(model_type="smplx", use_face_contour=True, num_expression_coeffs=10)
+
+
+def _gpu(a, grad=True):
+    return torch.tensor(a, device=GPU, requires_grad=grad)
+
+
+def _took(route):
+    """assert that GPU tensors take `route` in this process"""
+    from bodyfitting_amd import _autograd
+
+    class Offer:
+        device = 0
+    assert _autograd.chosen_route([torch.zeros(3, device=GPU)], Offer()) == route
+
+
+def _equal(got, want, what):
+    got = got.detach().cpu().numpy() if hasattr(got, "detach") else np.asarray(got)
+    assert got.dtype == np.asarray(want).dtype, (what, got.dtype)
+    assert np.array_equal(got, want), f"{what}: differs from the host route (max |diff| {np.abs(got - want).max():.3g})"
+
+
+def _smpl_case(body, n, seed, cases=CASES):
+    """SMPL.forward with GPU tensors against the numpy path, .backward() against DeviceModel.vjp, per case of `cases`"""
+    dev = body._dev
+    betas, orient, pose = _smpl_params(n, dev.n_betas, seed)
+    ref = body(betas=betas, global_orient=orient, body_pose=pose)
+    shapes = {"vertices": (n, dev.n_verts, 3), "joints": (n, dev.n_joint_map, 3), "joints_ori": (n, dev.n_joints + dev.n_selector, 3)}
+    cot = {k: _cot(s, seed + i) for i, (k, s) in enumerate(shapes.items())}
+    grads = {}
+    for case in cases:
+        x = [_gpu(a) for a in (betas, orient, pose)]
+        out = body(betas=x[0], global_orient=x[1], body_pose=x[2])
+        for k in shapes:
+            assert getattr(out, k).device.type == "cuda"
+            _equal(getattr(out, k), getattr(ref, k), f"n={n} {k}")
+        keys = tuple(shapes) if case == "all" else (case,)
+        sum((getattr(out, k) * _gpu(cot[k], False)).sum() for k in keys).backward()
+        want = dev.vjp(betas, orient, pose, **{a: cot[k] if k in keys else None
+                                               for k, a in (("vertices", "dverts"), ("joints", "djoints"), ("joints_ori", "djoints_ori"))})
+        for xi, w, name in zip(x, want, ("dbetas", "dglobal_orient", "dbody_pose")):
+            _equal(xi.grad, w, f"n={n} {case} {name}")
+        grads[case] = [xi.grad.cpu().numpy() for xi in x]
+    return grads
+
+
+def _smplx_case(body, n, seed, with_expr):
+    dev = body._dev
+    p = _smplx_params(n, seed)
+    names = XINPUTS + (("expression",) if with_expr else ())
+    ref = body(**{k: p[k] for k in names}, return_full_pose=True)
+    ref_rows = np.array(body.dyn_row)
+    shapes = {"vertices": (n, dev.n_verts, 3), "joints": (n, dev.n_joints_all, 3), "full_pose": (n, 3 * dev.n_joints)}
+    cot = {k: _cot(s, seed + i) for i, (k, s) in enumerate(shapes.items())}
+    arg = {"vertices": "dverts", "joints": "djoints_all", "full_pose": "dfull_pose"}
+    for case in XCASES:
+        x = {k: _gpu(p[k]) for k in names}
+        out = body(**x, return_full_pose=True)
+        for k in shapes:
+            _equal(getattr(out, k), getattr(ref, k), f"n={n} {k}")
+        assert body.dyn_row.device.type == "cuda" and body.dyn_row.dtype == torch.int32          # (no read-back on this route)
+        _equal(body.dyn_row, ref_rows, f"n={n} dyn_row")
+        keys = tuple(shapes) if case == "all" else (case,)
+        sum((getattr(out, k) * _gpu(cot[k], False)).sum() for k in keys).backward()
+        want = dev.vjp_smplx(*[p[k] for k in XINPUTS], **{arg[k]: cot[k] for k in keys}, **({"expression": p["expression"]} if with_expr else {}))
+        for k, w in zip(names, want):
+            _equal(x[k].grad, w, f"n={n} {case} d{k}")
+    # an argument not passed is a NULL pointer: the eight-argument call's bits with the five optional blocks left out
+    few = {k: _gpu(p[k]) for k in ("betas", "global_orient", "body_pose")}
+    _equal(body(**few).vertices, body(**{k: p[k] for k in few}).vertices, f"n={n} three blocks only")
+
+
+def same_bits(out_path, which):
+    def body():
+        _repo()
+        from bodyfitting_amd import native as N, synthetic as S
+        _took("device")
+        before = N.dev_route_stats()
+        gmm = S.make_gmm(seed=0)
+        if which == "smpl":
+            drop = _install("smpl", S.make_model("smpl", seed=0, nv=690), gmm)
+            for n in (1, 2, 9, 17, 65):
+                _smpl_case(drop, n, 50 + n)
+        elif which == "smpl_full":
+            drop = _install("smpl", S.make_model("smpl", seed=0), gmm)
+            for n in (1, 17):
+                _smpl_case(drop, n, n, cases=("all",))
+        else:
+            drop = _install("smplx", S.make_model("smplx", seed=0, nv=1200), gmm)
+            assert drop.num_expression_coeffs == 10
+            for n in (1, 2, 9, 17, 65):
+                _smplx_case(drop, n, 70 + n, which == "smplx_expr")
+        after = N.dev_route_stats()
+        assert after["dev_calls"] > before["dev_calls"] and after["stream_switches"] == before["stream_switches"]
+        drop._dev.close()
+        return {"ok": np.ones(1)}
+
+    _run(out_path, body)
+
+
+def oracle_band(out_path):
+    """n = 9 on the small SMPL: the device route's gradients against float64 autograd of the oracle, in the project's band"""
+    def body():
+        _repo()
+        from bodyfitting_amd import synthetic as S
+        from oracle import smplify_oracle as O
+        _took("device")
+        model = S.make_model("smpl", seed=0, nv=690)
+        drop = _install("smpl", model, S.make_gmm(seed=0))
+        n, seed, dev = 9, 59, drop._dev
+        got = _smpl_case(drop, n, seed)
+        betas, orient, pose = _smpl_params(n, dev.n_betas, seed)
+        shapes = {"vertices": (n, dev.n_verts, 3), "joints": (n, dev.n_joint_map, 3), "joints_ori": (n, dev.n_joints + dev.n_selector, 3)}
+        cot = {k: _cot(s, seed + i) for i, (k, s) in enumerate(shapes.items())}
+        ref = {}
+        for dtype in (torch.float64, torch.float32):
+            m = O.to_torch_model(model, dtype)
+            x = [torch.tensor(a, dtype=dtype, requires_grad=True) for a in (betas, orient, pose)]
+            out = O.smpl_forward(m, *x)
+            for case in CASES:
+                keys = tuple(shapes) if case == "all" else (case,)
+                total = sum((out[k] * torch.as_tensor(cot[k], dtype=dtype)).sum() for k in keys)
+                g = torch.autograd.grad(total, x, retain_graph=True, allow_unused=True)
+                ref[dtype, case] = [np.zeros(xi.shape) if gi is None else gi.detach().numpy().astype(np.float64) for gi, xi in zip(g, x)]
+        for case in CASES:
+            for i, name in enumerate(("dbetas", "dglobal_orient", "dbody_pose")):
+                f64, f32 = ref[torch.float64, case][i], ref[torch.float32, case][i]
+                err = float(np.abs(got[case][i].astype(np.float64) - f64).max())
+                band = 4 * float(np.abs(f32 - f64).max()) + 1e-6 * float(np.abs(f64).max())
+                print(f"{case} {name}: error {err:.3g}, band {band:.3g}")
+                assert err <= band, (case, name, err, band)
+        dev.close()
+        return {"ok": np.ones(1)}
+
+    _run(out_path, body)
+
+
+def _scene(rows, n_views, seed):
+    import keypoint_loss_cases as KC
+    return KC.scene(rows, n_views, seed)
+
+
+def _loss_inputs(rows, n_views, seed, absent, hand_face):
+    sc = _scene(rows, n_views, seed)
+    rng = np.random.default_rng(seed + 7)
+    keypoints = []
+    for v in range(n_views):
+        k = {"pose": sc["kp"][v][:25]}
+        if hand_face:
+            face70 = np.zeros((70, 3), np.float32)
+            face70[list(range(17, 68)) + list(range(0, 17))] = sc["kp"][v][67:135]
+            k.update(hand_left=sc["kp"][v][25:46], hand_right=sc["kp"][v][46:67], face=face70)
+        keypoints.append(None if v in absent else k)
+    x = [np.asarray(sc["joints"], np.float32), rng.normal(0, 0.2, (1, 63 if hand_face else 69)).astype(np.float32),
+         rng.normal(0, 0.6, (1, 10)).astype(np.float32)]
+    return sc, keypoints, x
+
+
+def keypoint_loss(out_path):
+    def body():
+        _repo()
+        from bodyfitting_amd import assets, loss as L, native as N, synthetic as S
+        from bodyfitting_amd.prior import MaxMixturePrior
+        _took("device")
+        assets._GMM["gmm"] = S.make_gmm(seed=0)
+        prior = MaxMixturePrior()
+        for n_views, absent, hand_face in ((1, (), False), (3, (), False), (3, (1,), False), (3, (), True), (3, (2,), True)):
+            sc, keypoints, x = _loss_inputs(135 if hand_face else 49, n_views, 3 + n_views, absent, hand_face)
+            w2c, K = torch.tensor(np.asarray(sc["w2c"], np.float32)), np.asarray(sc["K"], np.float32)
+            res = {}
+            for where in ("cpu", GPU):
+                t = [torch.tensor(a, device=where, requires_grad=True) for a in x]
+                before = dict(L.VIEW_STATS), N.dev_route_stats()
+                total, losses = L.multiview_keypoint_loss(w2c, K, keypoints, *t, list(range(n_views)), prior, use_hand_face=hand_face)
+                total.backward()
+                # the same cameras again: nothing is packed and nothing is sent
+                again, _ = L.multiview_keypoint_loss(w2c, K, keypoints, *t, list(range(n_views)), prior, use_hand_face=hand_face)
+                stats = N.dev_route_stats()
+                if where == GPU:
+                    assert total.device.type == "cuda"
+                    assert L.VIEW_STATS["packs"] == before[0]["packs"], "the CPU call packed these views already"
+                    assert L.VIEW_STATS["uploads"] == before[0]["uploads"] + 1, L.VIEW_STATS
+                    assert stats["dev_calls"] == before[1]["dev_calls"] + 3 and stats["host_calls"] == before[1]["host_calls"]
+                else:
+                    assert stats["host_calls"] == before[1]["host_calls"] + 3 and stats["dev_calls"] == before[1]["dev_calls"]
+                res[where] = [total.detach().cpu().numpy(), again.detach().cpu().numpy()] + [np.asarray(losses[k]) for k in L.LOSS_KEYS] + \
+                             [ti.grad.cpu().numpy() for ti in t]
+            for a, b, name in zip(res[GPU], res["cpu"], ("total", "again", *L.LOSS_KEYS, "djoints", "dposes", "dbetas")):
+                _equal(a, b, f"{n_views} views, absent {absent}, hand_face {hand_face}: {name}")
+        # the prior alone
+        pose = np.random.default_rng(5).normal(0, 0.3, (4, 69)).astype(np.float32)
+        res = {}
+        for where in ("cpu", GPU):
+            p = torch.tensor(pose, device=where, requires_grad=True)
+            nll = prior(p, None)
+            (nll * torch.tensor([1.0, -2.0, 0.5, 3.0], device=where)).sum().backward()
+            res[where] = [nll.detach().cpu().numpy(), p.grad.cpu().numpy()]
+        for a, b, name in zip(res[GPU], res["cpu"], ("prior", "dpose")):
+            _equal(a, b, name)
+        return {"ok": np.ones(1)}
+
+    _run(out_path, body)
+
+
+def _keypoint_stage(drop, prior, L, sc, keypoints, params, steps, after_step=None):
+    """the reference's loop (smplify.py:177-213) on cuda:0: model, loss, backward, Adam"""
+    w2c, K = torch.tensor(np.asarray(sc["w2c"], np.float32)), np.asarray(sc["K"], np.float32)
+    x = [torch.tensor(a, device=GPU, requires_grad=True) for a in params]
+    opt = torch.optim.Adam(x, lr=1e-2)
+    for i in range(steps):
+        opt.zero_grad()
+        out = drop(betas=x[0], global_orient=x[1], body_pose=x[2])
+        total, _ = L.multiview_keypoint_loss(w2c, K, keypoints, out.joints, x[2], x[0], list(range(len(keypoints))), prior)
+        total.backward()
+        opt.step()
+        if after_step:
+            after_step(i)
+    return [t.detach().cpu().numpy() for t in x]
+
+
+def stays_on_the_device(out_path):
+    """ten steps of the keypoint stage: per step the model's forward, the loss, the loss's reverse and the model's reverse - FOUR
+    calls of the three *_dev entry points, since the loss is entered once for its terms and once for its gradient, as on the host
+    route - none of the host entry points, no allocation after the first step, no stream switch"""
+    def body():
+        _repo()
+        from bodyfitting_amd import assets, loss as L, native as N, synthetic as S
+        from bodyfitting_amd.prior import MaxMixturePrior
+        _took("device")
+        model = S.make_model("smpl", seed=0, nv=690)
+        drop = _install("smpl", model, S.make_gmm(seed=0))
+        prior = MaxMixturePrior()
+        sc, keypoints, _ = _loss_inputs(49, 3, 11, (), False)
+        betas, orient, pose = _smpl_params(1, 10, 3)
+        seen = []
+        start = N.dev_route_stats()
+        _keypoint_stage(drop, prior, L, sc, keypoints, (betas, orient + 0.1, pose + 0.05), 10, lambda i: seen.append(N.dev_route_stats()))
+        end = seen[-1]
+        assert end["host_calls"] == start["host_calls"], (start, end)
+        assert end["dev_calls"] - start["dev_calls"] == 4 * 10, (start, end)
+        assert [s["dev_calls"] - start["dev_calls"] for s in seen] == [4 * (i + 1) for i in range(10)]
+        assert seen[0]["allocations"] > start["allocations"]
+        assert all(s["allocations"] == seen[0]["allocations"] for s in seen), [s["allocations"] for s in seen]
+        assert end["stream_switches"] == start["stream_switches"]
+        drop._dev.close()
+        return {"ok": np.ones(1)}
+
+    _run(out_path, body)
+
+
+def _busy():
+    """a long-running chain on the current stream that ends in a zero of shape []: what the inputs are made to wait for"""
+    a = torch.ones((4096, 4096), device=GPU) * 1e-4
+    for _ in range(6):
+        a = (a @ a) * 1e-3
+    return a.sum() * 0.0
+
+
+def stream_order(out_path):
+    def body():
+        _repo()
+        from bodyfitting_amd import native as N, synthetic as S
+        _took("device")
+        drop = _install("smpl", S.make_model("smpl", seed=0, nv=690), S.make_gmm(seed=0))
+        dev = drop._dev
+        n, seed = 9, 59
+        betas, orient, pose = _smpl_params(n, dev.n_betas, seed)
+        ref = drop(betas=betas, global_orient=orient, body_pose=pose)
+        cot = _cot((n, dev.n_verts, 3), seed), _cot((n, dev.n_joint_map, 3), seed + 1)
+        want = dev.vjp(betas, orient, pose, dverts=cot[0], djoints=cot[1])
+        torch.cuda.synchronize()
+
+        def on_stream(s):
+            """inputs produced on `s` behind a long chain, model and backward with no synchronisation in between"""
+            with torch.cuda.stream(s):
+                zero = _busy()
+                x = [(torch.tensor(a, device=GPU) + zero).requires_grad_(True) for a in (betas, orient, pose)]
+                out = drop(betas=x[0], global_orient=x[1], body_pose=x[2])
+                ((out.vertices * torch.tensor(cot[0], device=GPU)).sum() + (out.joints * torch.tensor(cot[1], device=GPU)).sum()).backward()
+            return x, out
+
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        before = N.dev_route_stats()
+        x, out = on_stream(s1)
+        torch.cuda.synchronize()
+        _equal(out.vertices, ref.vertices, "vertices on a side stream")
+        for xi, w, name in zip(x, want, ("dbetas", "dglobal_orient", "dbody_pose")):
+            _equal(xi.grad, w, f"{name} on a side stream")
+        mid = N.dev_route_stats()
+        assert mid["dev_calls"] == before["dev_calls"] + 2
+        # two streams alternating on one model (one workspace): each call waits for the one before it on the other stream
+        runs = [on_stream(s) for s in (s2, s1, s2, s1)]
+        torch.cuda.synchronize()
+        for x, out in runs:
+            _equal(out.vertices, ref.vertices, "vertices, alternating streams")
+            _equal(out.joints, ref.joints, "joints, alternating streams")
+            for xi, w, name in zip(x, want, ("dbetas", "dglobal_orient", "dbody_pose")):
+                _equal(xi.grad, w, f"{name}, alternating streams")
+        after = N.dev_route_stats()
+        assert after["stream_switches"] >= mid["stream_switches"] + 4, (mid, after)
+        dev.close()
+        return {"ok": np.ones(1)}
+
+    _run(out_path, body)
+
+
+def fallbacks(out_path, switched_off):
+    """switched_off: BF_TORCH_DEVICE_ROUTE=0 in this process - GPU tensors give the same bits through the host entry points alone.
+    Else: CPU tensors on a GPU model take the host route; bf_device_pointer_check refuses what is not device memory and leaves no
+    error behind; the refusals of the *_dev entry points come before any launch."""
+    if switched_off:
+        os.environ["BF_TORCH_DEVICE_ROUTE"] = "0"
+    else:
+        os.environ.pop("BF_TORCH_DEVICE_ROUTE", None)
+
+    def body():
+        _repo()
+        import ctypes as C
+        from bodyfitting_amd import _autograd, _lib, native as N, synthetic as S
+        _took("host" if switched_off else "device")
+        gmm = S.make_gmm(seed=0)
+        drop = _install("smpl", S.make_model("smpl", seed=0, nv=690), gmm)
+        dev = drop._dev
+        before = N.dev_route_stats()
+        if switched_off:
+            _smpl_case(drop, 9, 59, cases=("all",))            # (its asserts: the numpy path's and DeviceModel.vjp's bits)
+            after = N.dev_route_stats()
+            assert after["dev_calls"] == before["dev_calls"] and after["host_calls"] > before["host_calls"]
+            dev.close()
+            return {"ok": np.ones(1)}
+        # CPU tensors on a model of device 0
+        betas, orient, pose = _smpl_params(2, 10, 52)
+        x = [torch.tensor(a, requires_grad=True) for a in (betas, orient, pose)]
+        assert _autograd.chosen_route(x, type("Offer", (), {"device": 0})()) == "host"
+        out = drop(betas=x[0], global_orient=x[1], body_pose=x[2])
+        out.vertices.sum().backward()
+        assert out.vertices.device.type == "cpu" and N.dev_route_stats()["dev_calls"] == before["dev_calls"]
+        # the pointer check
+        lib = _lib.load()
+        host = np.zeros(16, np.float32)
+        said = lib.bf_last_error()
+        bad = lib.bf_device_pointer_check(0, C.c_void_p(host.ctypes.data))
+        null = lib.bf_device_pointer_check(0, None)
+        t = torch.zeros(16, device=GPU)
+        assert bad != 0 and null != 0 and lib.bf_device_pointer_check(0, C.c_void_p(t.data_ptr())) == 0
+        assert lib.bf_device_pointer_check(1, C.c_void_p(t.data_ptr())) != 0          # (memory of device 0 is not device 1's)
+        assert lib.bf_last_error() == said, "the pointer check left a message behind"
+        torch.cuda.synchronize()                                  # (raises if a HIP error was left behind in the shared runtime)
+        stream = torch.cuda.current_stream().cuda_stream
+        g = [torch.tensor(a, device=GPU) for a in (betas, orient, pose)]
+        v = torch.empty((2, dev.n_verts, 3), device=GPU)
+        dev.forward_dev(2, stream, g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), vertices=v.data_ptr())        # the next call succeeds
+        _equal(v, drop(betas=betas, global_orient=orient, body_pose=pose).vertices, "forward_dev after a refused pointer check")
+        # refusals, each before any launch
+        def refused(call):
+            try:
+                call()
+            except _lib.BodyfitError:
+                return True
+            return False
+        xdev = N.DeviceModel(S.make_model("smplx", seed=0, nv=1200), gmm, device=0)
+        bare = dict(S.make_model("smplx", seed=0, nv=1200))
+        bare["shapedirs"] = np.asarray(bare["shapedirs"])[:, :, :10]
+        nodirs = N.DeviceModel(bare, gmm, device=0)
+        assert nodirs.n_expression == 0
+        a = g[0].data_ptr()
+        calls = N.dev_route_stats()["dev_calls"]
+        assert refused(lambda: xdev.forward_dev(2, stream, a, a, a, vertices=v.data_ptr())), "bf_smpl_forward_dev on an SMPL-X model"
+        assert refused(lambda: nodirs.forward_smplx_dev(1, stream, [a, a, a, 0, 0, 0, 0, 0], expression=a, vertices=v.data_ptr()))
+        assert refused(lambda: nodirs.vjp_smplx_dev(1, stream, [a, a, a, 0, 0, 0, 0, 0], expression=a, dverts=v.data_ptr(), grads=[a] + [0] * 7))
+        assert refused(lambda: dev.forward_dev(0, stream, a, a, a, vertices=v.data_ptr())), "n = 0"
+        null_ws = lib.bf_smpl_forward_dev(dev._h, None, None, 2, C.c_void_p(a), C.c_void_p(a), C.c_void_p(a), C.c_void_p(v.data_ptr()), None, None)
+        assert null_ws != 0, "a NULL workspace"
+        assert lib.bf_keypoint_loss_dev(None, None, None, None, None, None, None, None, None, None) != 0
+        assert N.dev_route_stats()["dev_calls"] == calls, "a refused call counted as issued"
+        torch.cuda.synchronize()
+        for d in (xdev, nodirs, dev):
+            d.close()
+        return {"ok": np.ones(1)}
+
+    _run(out_path, body)

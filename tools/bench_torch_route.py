@@ -1,0 +1,122 @@
+"""The keypoint stage of a user's torch loop (smplify.py:177-213) with everything on cuda:0, device route against host route.
+
+    python tools/bench_torch_route.py [--reps 5] [--iters 100] [--views 48] [--out profiles/torch_device_route.json]
+    python tools/bench_torch_route.py --child device --batch 1          (one measurement: what the parent starts)
+
+Workload: the full 6890-vertex SMPL, 48 views, 100 Adam iterations of [SMPL.forward, multiview_keypoint_loss, backward, step] -
+config 2's shape - at one model evaluation per step, and at 64 (one model call on 64 parameter sets; the keypoint loss, whose batch
+is 1 as the reference's, reads row 0, and a torch sum over all 64 rows' joints sends a cotangent through every row).
+Timing: a host clock around the loop, ending in torch.cuda.synchronize(), after a warm-up loop of the same shapes.
+The route is read once per process (BF_TORCH_DEVICE_ROUTE), so every measurement is a child process of its own; this process never
+touches the GPU.  The children alternate device, host, device, ... one at a time; medians and min-max per (route, batch) are printed
+and written as JSON.  The yardstick is the host route of the same build."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def child(route, batch, iters, views, loops):
+    os.environ["BF_TORCH_DEVICE_ROUTE"] = "1" if route == "device" else "0"
+    import numpy as np
+    import torch                                    # (before the library: the device route needs the shared runtime)
+    sys.path.insert(0, REPO)
+    from bodyfitting_amd import _autograd, assets, loss as L, native as N, synthetic as S
+    from bodyfitting_amd.prior import MaxMixturePrior
+    from bodyfitting_amd.smpl import SMPL
+
+    model, gmm = S.make_model("smpl", seed=0), S.make_gmm(seed=0)
+    assets.register_gmm(gmm)
+    assets.register_model(model, "smpl", "neutral")
+    body, prior = SMPL(gender="neutral"), MaxMixturePrior()
+    prob = S.make_problem(model, frame=0, n_views=views)
+    w2c = torch.tensor(np.stack([np.linalg.inv(np.asarray(c, np.float64)) for c in prob["c2ws"]]).astype(np.float32))
+    K = np.asarray(prob["Ks"], np.float32)
+    use = list(range(views))
+    rng = np.random.default_rng(0)
+    init = (np.zeros((batch, 10), np.float32), np.tile(np.asarray(prob["init_pose"], np.float32).reshape(1, 72)[:, :3], (batch, 1)),
+            np.tile(np.asarray(prob["init_pose"], np.float32).reshape(1, 72)[:, 3:], (batch, 1)))
+    init = tuple(a + rng.normal(0, 0.01, a.shape).astype(np.float32) for a in init)
+
+    def loop():
+        x = [torch.tensor(a, device="cuda:0", requires_grad=True) for a in init]
+        opt = torch.optim.Adam(x, lr=1e-2)
+        for _ in range(iters):
+            opt.zero_grad()
+            out = body(betas=x[0], global_orient=x[1], body_pose=x[2])
+            total, _ = L.multiview_keypoint_loss(w2c, K, prob["keypoints"], out.joints[:1] * 0.3, x[2][:1], x[0][:1], use, prior)
+            if batch > 1:
+                total = total + 1e-3 * out.joints.square().sum()
+            total.backward()
+            opt.step()
+        torch.cuda.synchronize()
+        return float(total)
+
+    probe = [torch.zeros(3, device="cuda:0")]
+    took = _autograd.chosen_route(probe, type("Offer", (), {"device": 0})())
+    assert took == route, f"asked for the {route} route, the process takes the {took} route"
+    loop()                                          # warm-up: the same shapes
+    times, stats0 = [], N.dev_route_stats()
+    for _ in range(loops):
+        t0 = time.perf_counter()
+        last = loop()
+        times.append(time.perf_counter() - t0)
+    stats1 = N.dev_route_stats()
+    print(json.dumps({"route": route, "batch": batch, "iters": iters, "views": views, "seconds": times, "final_loss": last,
+                      "calls": {k: stats1[k] - stats0[k] for k in stats1}}))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--child", choices=("device", "host"))
+    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 64])
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--views", type=int, default=48)
+    ap.add_argument("--reps", type=int, default=5, help="measurements per (route, batch), each a process of its own")
+    ap.add_argument("--loops", type=int, default=1, help="timed loops per process, behind its warm-up loop")
+    ap.add_argument("--timeout", type=int, default=300, help="seconds a child may take")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child, a.batch, a.iters, a.views, a.loops)
+    runs = []
+    for batch in a.batches:
+        for rep in range(a.reps):
+            for route in ("device", "host"):
+                cmd = [sys.executable, os.path.abspath(__file__), "--child", route, "--batch", str(batch), "--iters", str(a.iters),
+                       "--views", str(a.views), "--loops", str(a.loops)]
+                done = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
+                if done.returncode != 0:            # (a child that failed ends the run: nothing more is started on the card)
+                    sys.stderr.write(done.stdout[-2000:] + done.stderr[-4000:])
+                    return done.returncode
+                runs.append(json.loads(done.stdout.strip().splitlines()[-1]))
+                print(f"batch {batch:3d} rep {rep} {route:6s}: " + " ".join(f"{t * 1e3:.1f}" for t in runs[-1]["seconds"]) + " ms", flush=True)
+    summary = []
+    for batch in a.batches:
+        row = {"batch": batch}
+        for route in ("device", "host"):
+            t = [s for r in runs if r["batch"] == batch and r["route"] == route for s in r["seconds"]]
+            row[route] = {"median_ms": statistics.median(t) * 1e3, "min_ms": min(t) * 1e3, "max_ms": max(t) * 1e3, "n": len(t)}
+        spread = max(row[r]["max_ms"] - row[r]["min_ms"] for r in ("device", "host"))
+        row["host_minus_device_ms"] = row["host"]["median_ms"] - row["device"]["median_ms"]
+        row["larger_spread_ms"] = spread
+        row["device_faster_beyond_spread"] = row["host_minus_device_ms"] > spread
+        summary.append(row)
+    result = {"iters": a.iters, "views": a.views, "summary": summary, "runs": runs}
+    print(json.dumps({"summary": summary}))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
