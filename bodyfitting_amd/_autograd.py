@@ -83,6 +83,32 @@ def apply(forward, vjp, inputs, device_route=None):
     return _function().apply(forward, vjp, *inputs)
 
 
+class ScalarLossRoute:
+    """The `device_route` of a scalar loss whose native call returns the gradient for cotangent 1 with the value (loss.py:
+    _scalar_loss).  call(tensor, want_grad, stream) -> (value: a float32 tensor [1] on the GPU, gradient: a tensor like `tensor`, or
+    None); the forward keeps the gradient tensor, the reverse scales it on the device by the cotangent where it lies
+    (bf_scale_gradient_dev: one launch, the bits of numpy's float32 `g * c` and `+ 0.0` with plus_zero) - the cotangent is never read
+    back.  device: the GPU of the native object, None when it offers no device route."""
+
+    def __init__(self, who, device, call, want_grad, plus_zero=False):
+        self.who, self.device, self.call, self.want_grad, self.plus_zero = who, device, call, want_grad, plus_zero
+        self.grad = None
+
+    def forward(self, tensors, stream):
+        value, self.grad = self.call(tensors[0], self.want_grad, stream)
+        return (value,)
+
+    def vjp(self, tensors, cotangents, want, stream):
+        import torch
+        from . import native
+        if self.grad is None:
+            raise RuntimeError(f"{self.who}: no gradient was computed with the forward")
+        out = torch.empty_like(self.grad)
+        native.scale_gradient_dev(self.device, stream, self.grad.numel(), self.grad.data_ptr(), cotangents[0].data_ptr(), out.data_ptr(),
+                                  plus_zero=self.plus_zero)
+        return (out,)
+
+
 def _function():
     if _FUNCTION:
         return _FUNCTION[0]

@@ -119,6 +119,14 @@ SIGNATURES = {
     "bf_normal_laplacian": (C.c_int, [_VP, _FP, _FP, _FP]),
     "bf_scan_point_loss": (C.c_int, [_VP, C.c_int, _FP, _FP, _IP, _FP, _FP]),
     "bf_normal_loss": (C.c_int, [C.c_int, C.c_int, _FP, _FP, _FP, _FP]),
+    # their device route: the host call's arguments as device addresses, then workspace, stream
+    "bf_vertex_normals_dev": (C.c_int, [_VP] * 5),
+    "bf_vertex_normals_vjp_dev": (C.c_int, [_VP] * 6),
+    "bf_normal_laplacian_dev": (C.c_int, [_VP] * 6),
+    "bf_scan_point_loss_dev": (C.c_int, [_VP, C.c_int] + [_VP] * 7),
+    "bf_scan_nearest_dev": (C.c_int, [_VP, C.c_int] + [_VP] * 6),
+    "bf_normal_loss_dev": (C.c_int, [C.c_int, C.c_int, _VP, _VP, C.c_int] + [_VP] * 5),
+    "bf_scale_gradient_dev": (C.c_int, [C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP]),
     "bf_batch_create": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(_VP)]),
     "bf_batch_destroy": (None, [_VP]),
     "bf_batch_set_cameras": (C.c_int, [_VP, _FP, _FP]),

@@ -158,7 +158,7 @@ hipError_t bf_grow(hipStream_t s, DevBuf<T> &b, size_t count) {
 }
 
 // bf_dev_route_stats: calls of the host entry points a torch loop goes through (bf_smpl_forward, bf_smpl_vjp, bf_smplx_forward[_expr],
-// bf_smplx_vjp[_expr], bf_keypoint_loss), calls of their *_dev twins, device (re)allocations of workspaces, and calls that had to wait
+// bf_smplx_vjp[_expr], bf_keypoint_loss, the SMPL+D stage's losses of mesh_loss_api.hip, bf_scan_nearest), calls of their *_dev twins, device (re)allocations of workspaces, and calls that had to wait
 // for their workspace's previous call on another stream.  Process-wide; counted once the arguments have passed.
 struct BfRouteStats { std::atomic<long long> host{0}, dev{0}, allocs{0}, switches{0}; };
 inline BfRouteStats &bf_route_stats() { static BfRouteStats S; return S; }
@@ -501,6 +501,7 @@ struct bf_scan {
     std::vector<struct bf_batch *> holders;   // batches that hold this scan (bf_batch_set_scans), one entry per frame slot, under bf_scan_links():
                                               // destroying the scan waits for the device and detaches those batches' scans first
     ScanDev dev{};
+    DevBuf<ScanDev> dev_resident;             // `dev` in device memory for the *_dev calls (mesh_loss_api.hip), made by the first of them
     DevBuf<float> verts, face_norms;
     DevBuf<int> faces, cell_start, cell_tris;
     DevBuf<float> cell_pack, cell_box;

@@ -1,5 +1,5 @@
 // The device route's workspace (include/bodyfit.h: bf_workspace_create, the *_dev entry points): the scratch of ONE caller, on whatever
-// stream that caller runs.  Defined in dev_route_api.hip, used by the *_dev entry points of model_grad_api.hip and kp_loss_api.hip.
+// stream that caller runs.  Defined in dev_route_api.hip, used by the *_dev entry points of model_grad_api.hip, kp_loss_api.hip and mesh_loss_api.hip.
 // The block cache (BfPool) stays out of this route: "nothing on the device still uses a block that is given back" is what a route that
 // never synchronises cannot promise.
 #pragma once

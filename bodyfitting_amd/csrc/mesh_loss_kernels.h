@@ -13,5 +13,7 @@ extern "C" __global__ void bf_ml_lap_grad_kernel(const int *faces, const int *ad
 extern "C" __global__ void bf_ml_pc_partial_kernel(int n, const float *P, const float *C, float *partial);
 extern "C" __global__ void bf_ml_pc_grad_kernel(int n, const float *P, const float *C, const float *loss, float *dP);
 extern "C" __global__ void bf_ml_normal_partial_kernel(int n, const float *fn, const float *pn, float *partial, float *dpn);
+extern "C" __global__ void bf_ml_normal_gather_partial_kernel(int n, const int *ids, const float *table, int n_faces, const float *pn, float *partial, float *dpn);
+extern "C" __global__ void bf_ml_scale_kernel(int n, const float *grad, const float *cotangent, int plus_zero, float *out);
 extern "C" __global__ void bf_ml_finish_kernel(const float *partial, int n_partial, int root, float divisor, float *out);
 #pragma GCC visibility pop

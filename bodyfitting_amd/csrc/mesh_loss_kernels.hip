@@ -199,6 +199,14 @@ bf_ml_pc_grad_kernel(int n, const float *__restrict__ P, const float *__restrict
     for (int k = 0; k < 3; ++k) dP[i * 3 + k] = l > 0.f ? (P[i * 3 + k] - C[i * 3 + k]) / l : 0.f;
 }
 
+// one row of normal_loss_mesh_grid, shared by the two kernels below: 1 - fn . pn_i, and -fn / N into dpn_i for cotangent 1 (dpn may be NULL)
+static __device__ __forceinline__ float ml_normal_row(int i, int n, float f0, float f1, float f2, const float *__restrict__ pn,
+                                                      float *__restrict__ dpn) {
+    const float a = 1.f - (f0 * pn[i * 3] + f1 * pn[i * 3 + 1] + f2 * pn[i * 3 + 2]);
+    if (dpn) { const float k = -1.f / (float)n; dpn[i * 3] = k * f0; dpn[i * 3 + 1] = k * f1; dpn[i * 3 + 2] = k * f2; }
+    return a;
+}
+
 // normal_loss_mesh_grid, grid ceil(N/256): block sums of 1 - fn . pn, and the gradient -fn / N for cotangent 1 (dpn may be NULL)
 extern "C" __global__ void __launch_bounds__(256)
 bf_ml_normal_partial_kernel(int n, const float *__restrict__ fn, const float *__restrict__ pn, float *__restrict__ partial,
@@ -206,13 +214,42 @@ bf_ml_normal_partial_kernel(int n, const float *__restrict__ fn, const float *__
     __shared__ float s4[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
     float a = 0.f;
+    if (i < n) a = ml_normal_row(i, n, fn[i * 3], fn[i * 3 + 1], fn[i * 3 + 2], pn, dpn);
+    const float tot = ml_block_sum(a, s4);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+// ... with the closest faces' normals gathered here: row i takes table[ids[i]] of table[n_faces][3].  The same rows in the same block
+// sums, so the bits are those of the kernel above on table[ids].  An id outside [0, n_faces) is not dereferenced: its row adds 0 to the
+// sum (the mean still divides by N) and gets a zero gradient.
+extern "C" __global__ void __launch_bounds__(256)
+bf_ml_normal_gather_partial_kernel(int n, const int *__restrict__ ids, const float *__restrict__ table, int n_faces,
+                                   const float *__restrict__ pn, float *__restrict__ partial, float *__restrict__ dpn) {
+    __shared__ float s4[4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    float a = 0.f;
     if (i < n) {
-        const float f0 = fn[i * 3], f1 = fn[i * 3 + 1], f2 = fn[i * 3 + 2];
-        a = 1.f - (f0 * pn[i * 3] + f1 * pn[i * 3 + 1] + f2 * pn[i * 3 + 2]);
-        if (dpn) { const float k = -1.f / (float)n; dpn[i * 3] = k * f0; dpn[i * 3 + 1] = k * f1; dpn[i * 3 + 2] = k * f2; }
+        const int f = ids[i];
+        if (f >= 0 && f < n_faces) {
+            const float *row = table + (size_t)f * 3;
+            a = ml_normal_row(i, n, row[0], row[1], row[2], pn, dpn);
+        } else if (dpn) {
+            dpn[i * 3] = 0.f; dpn[i * 3 + 1] = 0.f; dpn[i * 3 + 2] = 0.f;
+        }
     }
     const float tot = ml_block_sum(a, s4);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+// the backward of a scalar loss, grid ceil(N/256): out = grad * cotangent[0] in float32, the cotangent read where it lies; plus_zero:
+// + 0.0f behind the product (a statement of its own: never fused), so a zero is +0 whatever the cotangent's sign
+extern "C" __global__ void __launch_bounds__(256)
+bf_ml_scale_kernel(int n, const float *__restrict__ grad, const float *__restrict__ cotangent, int plus_zero, float *__restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float v = grad[i] * cotangent[0];
+    if (plus_zero) v = v + 0.0f;
+    out[i] = v;
 }
 
 // ONE block: the block sums in a fixed order (thread t takes t, t + 256, ... ascending, then the block's tree) -> out[0] =

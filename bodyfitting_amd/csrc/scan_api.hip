@@ -191,6 +191,7 @@ int bf_scan_intersects(bf_scan *s, int n, const float *origins, const float *dir
 // MeshGridSearcher.nearest_points -> SurfaceNearest (utils/mesh_grid_searcher.py:6-15,81-84)
 int bf_scan_nearest(bf_scan *s, int n, const float *points, int32_t *face_ids, float *nearest, float *bary) {
     if (!s || n <= 0 || !points) return fail(BF_ERR_INVALID, "bf_scan_nearest: bad argument");
+    ++bf_route_stats().host;
     HIP_TRY(hipSetDevice(s->device));
     DevBuf<float> d_p, d_c, d_b;
     DevBuf<int> d_f;

@@ -17,7 +17,11 @@ the gradient for cotangent 1 with the value: `point_cloud_loss_mesh_grid` (bf_sc
 the gradient goes to `points`), `normal_loss_mesh_grid` (bf_normal_loss, to `point_norm`) and `normal_laplacian_smoothness`
 (bf_normal_laplacian, to `norms`); `compute_normal_torch` is in normals.py.  torch tensors in -> a 0-dim float32 tensor on the
 inputs' device, differentiable once; numpy in -> a float.  The two scan losses of one iteration query the same points: the searcher
-keeps its last query's answer, so the second one does not search again.  They take this project's MeshGridSearcher, arrays and
+keeps its last query's answer, so the second one does not search again.  float32 tensors on the scan's / the topology's GPU take
+the device route (bf_scan_point_loss_dev, bf_normal_loss_dev, bf_normal_laplacian_dev): addresses in, the loss a tensor that never
+leaves the GPU, the closest faces' normals gathered in the kernel, the backward a scaling launch that reads the cotangent where it
+lies; the searcher's memo is then the points TENSOR by identity and `_version` (mesh_grid_searcher.memo_hit).
+They take this project's MeshGridSearcher, arrays and
 tensors; anything else raises NotImplementedError (SMPLify's fused stage is the other path), every other refusal is a ValueError.
 
 The silhouette term of that loop (smplify.py:144,198) is here as well: `extract_countours` follows the masks' external borders on
@@ -106,10 +110,12 @@ point_cloud_loss_chamfer_naive = _fused_only("point_cloud_loss_chamfer_naive")
 # the scan term and the SMPL+D stage's losses (loss.py:233-242,260-288)
 # ----------------------------------------------------------------------------------------------------------------------------
 
-def _scalar_loss(who, x, call, plus_zero=False):
+def _scalar_loss(who, x, call, plus_zero=False, device=None, device_call=None):
     """`call(array, want_grad)` -> (value, gradient for cotangent 1 or None): ONE native call per evaluation - the gradient comes
     back with the value when `x` asks for one, and the backward only scales it.  -> a 0-dim tensor on x's device, or a float.
-    plus_zero: the scaled gradient's zeros are +0 whatever the cotangent's sign (0 * -2.5 is -0)."""
+    plus_zero: the scaled gradient's zeros are +0 whatever the cotangent's sign (0 * -2.5 is -0).
+    device, device_call: the GPU a device route is offered on (None: none) and `device_call(tensor, want_grad, stream)` -> (value
+    tensor [1], gradient tensor or None) on it (_autograd.ScalarLossRoute); taken when _autograd.route_for says so for `x`."""
     if not _is_tensor(x):
         return float(call(x, False)[0])
     import torch
@@ -127,7 +133,20 @@ def _scalar_loss(who, x, call, plus_zero=False):
         scaled = kept[0] * np.asarray(cotangents[0]).reshape(-1)[0]
         return (scaled + 0.0 if plus_zero else scaled,)
 
-    return _autograd.apply(forward, vjp, (x,))[0].reshape(())
+    route = None if device_call is None else _autograd.ScalarLossRoute(who, device, device_call, want_grad, plus_zero)
+    return _autograd.apply(forward, vjp, (x,), device_route=route)[0].reshape(())
+
+
+def _takes_device_route(device, *tensors):
+    """do these go the device route of a native object on GPU `device` (None: it offers none)?  _autograd.route_for's rule"""
+    if device is None or not all(_is_tensor(t) and hasattr(t, "data_ptr") for t in tensors):
+        return False
+    return _autograd.chosen_route(list(tensors), type("Offer", (), {"device": device})()) == "device"
+
+
+def _new(like, shape, dtype=None):
+    import torch
+    return torch.empty(shape, dtype=dtype or torch.float32, device=like.device)
 
 
 def _scan_of(who, mesh_grid_searcher):
@@ -157,7 +176,17 @@ def point_cloud_loss_mesh_grid(mesh_grid_searcher, points):
         mesh_grid_searcher._remember_query(p, ids, nearest)
         return value, grad
 
-    return _scalar_loss(who, points, call)
+    def device_call(p, want_grad, stream):
+        import torch
+        n = p.numel() // 3
+        value, ids, nearest = _new(p, 1), _new(p, n, torch.int32), _new(p, (n, 3))
+        grad = _new(p, p.shape) if want_grad else None
+        scan.point_loss_dev(n, stream, p.data_ptr(), loss=value.data_ptr(), face_ids=ids.data_ptr(), nearest=nearest.data_ptr(),
+                            dpoints=0 if grad is None else grad.data_ptr())
+        mesh_grid_searcher._remember_query_dev(points, ids, nearest)          # (the caller's tensor: what the next loss is handed)
+        return value, grad
+
+    return _scalar_loss(who, points, call, device=getattr(scan, "dev_route_device", None), device_call=device_call)
 
 
 def normal_loss_mesh_grid(mesh_grid_searcher, points, face_norm_mesh=None, point_norm=None):
@@ -181,6 +210,21 @@ def normal_loss_mesh_grid(mesh_grid_searcher, points, face_norm_mesh=None, point
     if face_norm_mesh.ndim != 2 or rows[1] != scan.n_faces:
         raise ValueError(f"{who}: face_norm_mesh must be [{scan.n_faces}, 3] (one row per face of the searcher's mesh), not {tuple(face_norm_mesh.shape)}")
     from . import native
+    device = getattr(scan, "dev_route_device", None)
+    if _takes_device_route(device, points, face_norm_mesh, point_norm):
+        # everything is on the scan's GPU: the ids stay there (the tensor memo, or a search queued here) and the kernel gathers
+        import torch
+        ids = mesh_grid_searcher._query_dev(points, torch.cuda.current_stream(points.device).cuda_stream)
+        table = face_norm_mesh.detach().contiguous()
+
+        def device_call(pn, want_grad, stream):
+            value = _new(pn, 1)
+            grad = _new(pn, pn.shape) if want_grad else None
+            native.normal_loss_dev(scan.workspace(), stream, rows[0], ids.data_ptr(), table.data_ptr(), scan.n_faces, pn.data_ptr(),
+                                   loss=value.data_ptr(), dpoint_norms=0 if grad is None else grad.data_ptr())
+            return value, grad
+
+        return _scalar_loss(who, point_norm, None, device=device, device_call=device_call)
     ids, _ = mesh_grid_searcher._query(_host(points, None).reshape(-1, 3))
     closest = _host(face_norm_mesh, None)[ids]                 # (gathered here: N rows go up, not the scan's table)
 
@@ -206,7 +250,13 @@ def normal_laplacian_smoothness(norms, faces):
     def call(a, want_grad):
         return native.normal_laplacian(topo, a.reshape(-1, 3), want_grad=want_grad)
 
-    return _scalar_loss(who, norms, call)
+    def device_call(a, want_grad, stream):
+        value = _new(a, 1)
+        grad = _new(a, a.shape) if want_grad else None
+        native.normal_laplacian_dev(topo, stream, a.data_ptr(), loss=value.data_ptr(), dnorms=0 if grad is None else grad.data_ptr())
+        return value, grad
+
+    return _scalar_loss(who, norms, call, device=getattr(topo, "dev_route_device", None), device_call=device_call)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

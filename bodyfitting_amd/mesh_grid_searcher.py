@@ -6,7 +6,9 @@ Same constructor and methods: `MeshGridSearcher(verts, faces)`, `set_mesh`, `nea
 `inside_mesh(points) -> +1 / -1 per point`, `intersects_any(origins, directions) -> bool per ray`.  The attributes the reference
 leaves on the instance after `set_mesh` are there too (`verts`, `faces`, `step`, `num`, `minmax`, `tri_num`, `tri_idx` - the
 grid the device built, read back lazily).  numpy in -> numpy out; torch tensors in -> torch tensors out on the tensors' device
-(torch is imported only in that case).
+(torch is imported only in that case).  float32 tensors on the scan's GPU are searched where they lie, on torch's current stream
+(bf_scan_nearest_dev, the device route of _autograd.py, on the searcher's own workspace): `nearest_points` then returns tensors that
+never left the GPU.  `inside_mesh` and `intersects_any` go through host memory.
 """
 from __future__ import annotations
 
@@ -19,10 +21,24 @@ def _is_tensor(x):
     return hasattr(x, "detach") and hasattr(x, "cpu")
 
 
+def memo_hit(memo, points):
+    """is `memo` - (points tensor, its _version when it was searched, ...) or None - the answer for `points`?  Only for the SAME
+    tensor object at the same version: the memo holds the tensor by strong reference, so no later tensor can take its identity (or
+    its address) while the memo lives.  Contents are never compared - that is a read-back - and a miss merely searches again."""
+    return memo is not None and memo[0] is points and memo[1] == points._version
+
+
 def _to_np(x, dtype):
     if _is_tensor(x):
         x = x.detach().cpu().numpy()
     return np.ascontiguousarray(np.asarray(x, dtype=dtype))
+
+
+class _Offer:
+    """what _autograd.chosen_route asks of a device route: the GPU it is offered on (None: none)"""
+
+    def __init__(self, device):
+        self.device = device
 
 
 class MeshGridSearcher:
@@ -50,6 +66,7 @@ class MeshGridSearcher:
         self._scan = Scan(self.verts, self.faces, device=self._device_index(device))
         self._mesh_wants_grad = any(getattr(a, "requires_grad", False) for a in (verts, faces))
         self._last_query = None
+        self._last_query_dev = None
         dims, origin, step = self._scan.grid_info()
         self.step = np.float32(step)
         self.num = np.concatenate([dims, [int(np.prod(dims))]]).astype(np.int32)          # [nx, ny, nz, nx ny nz]
@@ -71,9 +88,10 @@ class MeshGridSearcher:
 
     def close(self):
         if getattr(self, "_scan", None) is not None:
-            self._scan.close()
+            self._scan.close()               # (its workspace first: queued searches end before the grid goes)
             self._scan = None
         self._last_query = None
+        self._last_query_dev = None
 
     def __del__(self):  # pragma: no cover
         try:
@@ -95,6 +113,44 @@ class MeshGridSearcher:
         self._remember_query(points, ids, pts)
         return ids, pts
 
+    # the device route's memo: the caller's points TENSOR (held, so that `is` is sound), its _version, and the answer as tensors
+
+    def _remember_query_dev(self, points, ids, nearest):
+        self._last_query_dev = (points, points._version, ids, nearest)
+
+    def _query_dev(self, points, stream):
+        """-> face ids (an int32 tensor [n] on the scan's GPU) of the tensor `points`: the last device query's when `memo_hit`, else a
+        search queued on `stream` (bf_scan_nearest_dev)"""
+        last = getattr(self, "_last_query_dev", None)
+        if memo_hit(last, points):
+            return last[2]
+        ids, nearest = self._search_dev(points, stream)[:2]
+        self._remember_query_dev(points, ids, nearest)
+        return ids
+
+    def _search_dev(self, points, stream, with_coefficients=False):
+        import torch
+        p = points.detach().reshape(-1, 3).contiguous()
+        n = p.shape[0]
+        ids = torch.empty(n, dtype=torch.int32, device=p.device)
+        nearest = torch.empty((n, 3), dtype=torch.float32, device=p.device)
+        bary = torch.empty((n, 3), dtype=torch.float32, device=p.device) if with_coefficients else None
+        self._scan.nearest_points_dev(n, stream, p.data_ptr(), face_ids=ids.data_ptr(), nearest=nearest.data_ptr(),
+                                      bary=0 if bary is None else bary.data_ptr())
+        return ids, nearest, bary
+
+    def _takes_device_route(self, *tensors):
+        """float32 tensors on the scan's GPU, the switch on, the runtimes shared (_autograd.route_for)"""
+        if not all(_is_tensor(t) and hasattr(t, "data_ptr") for t in tensors):
+            return False
+        from . import _autograd
+        return _autograd.chosen_route(list(tensors), _Offer(getattr(self._scan, "dev_route_device", None))) == "device"
+
+    @staticmethod
+    def _stream(points):
+        import torch
+        return torch.cuda.current_stream(points.device).cuda_stream
+
     def _need_mesh(self):
         if self._scan is None:
             raise RuntimeError("MeshGridSearcher: set_mesh() first")
@@ -110,12 +166,18 @@ class MeshGridSearcher:
         """:81-84 -> (nearest_pts[n,3] float32, nearest_faces[n] int32); no gradient, like the reference's SurfaceNearest
         (its backward is commented out, :17-49)"""
         self._need_mesh()
+        if self._takes_device_route(points):
+            ids, pts, _ = self._search_dev(points, self._stream(points))
+            return pts, ids
         pts, ids, _ = self._scan.nearest_points(_to_np(points, np.float32).reshape(-1, 3))
         return self._back(points, pts, ids)
 
     def nearest_points_with_coefficients(self, points):
         """the third output of the kernel (`coeff`, :10-14), which the reference's wrapper drops"""
         self._need_mesh()
+        if self._takes_device_route(points):
+            ids, pts, bary = self._search_dev(points, self._stream(points), with_coefficients=True)
+            return pts, ids, bary
         pts, ids, bary = self._scan.nearest_points(_to_np(points, np.float32).reshape(-1, 3))
         return self._back(points, pts, ids, bary)
 

@@ -149,6 +149,33 @@ def dev_route_stats():
     return dict(zip(("host_calls", "dev_calls", "allocations", "stream_switches"), (int(v) for v in out)))
 
 
+# the device route of the SMPL+D stage's losses and of the closest-point search (bf_*_dev of csrc/mesh_loss_api.hip)
+MESH_LOSS_DEV_SYMBOLS = ("bf_vertex_normals_dev", "bf_vertex_normals_vjp_dev", "bf_normal_laplacian_dev", "bf_scan_point_loss_dev",
+                         "bf_scan_nearest_dev", "bf_normal_loss_dev", "bf_scale_gradient_dev")
+
+
+def offers_mesh_loss_dev(lib):
+    """does the library `lib` export every entry point of that route?  One without them offers no device route there: `Topology` and
+    `Scan` then say `dev_route_device` None and everything takes the host route"""
+    return all(hasattr(lib, name) for name in MESH_LOSS_DEV_SYMBOLS)
+
+
+def _own_workspace(obj):
+    """the `Workspace` of `obj` (a Topology, a Scan), made on first use and closed with it"""
+    ws = obj.__dict__.get("_workspace")
+    if ws is None:
+        ws = obj.__dict__.setdefault("_workspace", Workspace(obj.device))
+    return ws
+
+
+def _close_workspace(obj):
+    """... closed BEFORE the object's own buffers go: closing drains the stream of the workspace's last call, behind which every
+    earlier call on the object is ordered"""
+    ws = obj.__dict__.pop("_workspace", None)
+    if ws is not None:
+        ws.close()
+
+
 class DeviceModel:
     """Body model + GMM prior uploaded once to one GPU (replaces the per-frame construction at
     reference smplify/body_fitting.py:82 -> smplify/smplify.py:46-56).  An SMPL-X model dict whose shapedirs has more than
@@ -356,11 +383,34 @@ class Scan:
         _lib.check(self._lib.bf_scan_create(int(device), len(v), _lib.fptr(v), len(f), _lib.iptr(f), C.byref(self._h)),
                    "bf_scan_create")
         self.height = float(self._lib.bf_scan_height(self._h))
+        self.dev_route_device = self.device if offers_mesh_loss_dev(self._lib) else None       # the GPU a device route is offered on
 
     def close(self):
+        _close_workspace(self)
         if getattr(self, "_h", None):
             self._lib.bf_scan_destroy(self._h)
             self._h = None
+
+    def workspace(self):
+        """the scan's own `Workspace` for the device route, made on first use and closed with the scan"""
+        return _own_workspace(self)
+
+    # The device route: the calls below take device ADDRESSES (integers; 0 / None = NULL) of contiguous arrays on the scan's GPU and
+    # queue their work on `stream` (a hipStream_t handle); nothing is read back.
+
+    def point_loss_dev(self, n, stream, points, loss=0, face_ids=0, nearest=0, dpoints=0, ws=None):
+        """`point_loss` (bf_scan_point_loss_dev): points[n,3] -> loss[1], face_ids[n] int32, nearest[n,3], dpoints[n,3]"""
+        ws = ws or self.workspace()
+        with ws.lock:
+            _lib.check(self._lib.bf_scan_point_loss_dev(self._h, int(n), points or None, loss or None, face_ids or None, nearest or None,
+                                                        dpoints or None, ws._h, stream or None), "bf_scan_point_loss_dev")
+
+    def nearest_points_dev(self, n, stream, points, face_ids=0, nearest=0, bary=0, ws=None):
+        """`nearest_points` (bf_scan_nearest_dev): points[n,3] -> face_ids[n] int32, nearest[n,3], bary[n,3]"""
+        ws = ws or self.workspace()
+        with ws.lock:
+            _lib.check(self._lib.bf_scan_nearest_dev(self._h, int(n), points or None, face_ids or None, nearest or None, bary or None,
+                                                     ws._h, stream or None), "bf_scan_nearest_dev")
 
     def __del__(self):  # pragma: no cover
         try:
@@ -460,11 +510,18 @@ class Topology:
         self.n_verts, self.n_faces, self.device = int(n_verts), len(f), int(device)
         self._h = C.c_void_p()
         _lib.check(lib.bf_topo_create(self.device, self.n_verts, self.n_faces, _lib.iptr(f), C.byref(self._h)), "bf_topo_create")
+        self.dev_route_device = self.device if offers_mesh_loss_dev(lib) else None       # the GPU a device route is offered on
 
     def close(self):
+        _close_workspace(self)
         if getattr(self, "_h", None):
             self._lib.bf_topo_destroy(self._h)
             self._h = None
+
+    def workspace(self):
+        """the topology's own `Workspace` for the device route - the normals, their reverse and the Laplacian share it - made on first
+        use and closed with the topology"""
+        return _own_workspace(self)
 
     def __del__(self):  # pragma: no cover
         try:
@@ -509,6 +566,46 @@ def normal_loss(closest_face_norms, point_norms, want_grad=True, device=0):
     dpn = np.empty((len(fn), 3), np.float32) if want_grad else None
     _lib.check(_lib.load().bf_normal_loss(int(device), len(fn), _lib.fptr(fn), _lib.fptr(pn), _lib.fptr(loss), _lib.fptr(dpn)), "bf_normal_loss")
     return loss[0], dpn
+
+
+# The device route of the five calls above: device ADDRESSES (integers; 0 / None = NULL) of contiguous float32 arrays on the topology's /
+# the given GPU, queued on `stream` (a hipStream_t handle); nothing is read back.  ws: a `Workspace` (None: the topology's own).
+
+def vertex_normals_dev(topo, stream, verts, normals, ws=None):
+    """bf_vertex_normals_dev: verts[NV,3] -> normals[NV,3]"""
+    ws = ws or topo.workspace()
+    with ws.lock:
+        _lib.check(topo._lib.bf_vertex_normals_dev(topo._h, verts or None, normals or None, ws._h, stream or None), "bf_vertex_normals_dev")
+
+
+def vertex_normals_vjp_dev(topo, stream, verts, dnormals, dverts, ws=None):
+    """bf_vertex_normals_vjp_dev: dnormals[NV,3] -> dverts[NV,3]"""
+    ws = ws or topo.workspace()
+    with ws.lock:
+        _lib.check(topo._lib.bf_vertex_normals_vjp_dev(topo._h, verts or None, dnormals or None, dverts or None, ws._h, stream or None),
+                   "bf_vertex_normals_vjp_dev")
+
+
+def normal_laplacian_dev(topo, stream, norms, loss=0, dnorms=0, ws=None):
+    """bf_normal_laplacian_dev: norms[NV,3] -> loss[1], dnorms[NV,3] (the gradient for cotangent 1)"""
+    ws = ws or topo.workspace()
+    with ws.lock:
+        _lib.check(topo._lib.bf_normal_laplacian_dev(topo._h, norms or None, loss or None, dnorms or None, ws._h, stream or None),
+                   "bf_normal_laplacian_dev")
+
+
+def normal_loss_dev(ws, stream, n, face_ids, face_norm_table, n_faces, point_norms, loss=0, dpoint_norms=0):
+    """bf_normal_loss_dev on the workspace's GPU: face_ids[n] int32 and the whole face_norm_table[n_faces,3], gathered in the kernel"""
+    with ws.lock:
+        _lib.check(_lib.load().bf_normal_loss_dev(ws.device, int(n), face_ids or None, face_norm_table or None, int(n_faces),
+                                                  point_norms or None, loss or None, dpoint_norms or None, ws._h, stream or None),
+                   "bf_normal_loss_dev")
+
+
+def scale_gradient_dev(device, stream, n, grad, cotangent, out, plus_zero=False):
+    """bf_scale_gradient_dev: out[n] = grad[n] * cotangent[0] (+ 0.0 with plus_zero), the cotangent read on the device"""
+    _lib.check(_lib.load().bf_scale_gradient_dev(int(device), int(n), grad or None, cotangent or None, int(bool(plus_zero)), out or None,
+                                                 stream or None), "bf_scale_gradient_dev")
 
 
 class Silhouette:

@@ -6,8 +6,11 @@ torch tensors in -> a float32 tensor [NV,3] on the vertices' device, differentia
 numpy out.  torch is imported only when tensors arrive.
 
 The topology - the faces and the vertex -> (face, corner) lists - is uploaded once per faces object and GPU (`topology_for`): a loop
-that passes the same tensor builds it once, an in-place edit of the tensor is seen (its `_version`), arrays are told apart by a
-digest of their bytes.
+that passes the same tensor builds it once - a hit reads nothing of the tensor back, wherever it lives - an in-place edit of the
+tensor is seen (its `_version`), arrays are told apart by a digest of their bytes.
+
+float32 vertices on the topology's GPU go into the kernels where they lie, on torch's current stream (bf_vertex_normals_dev /
+bf_vertex_normals_vjp_dev: the device route of _autograd.py, on the topology's own workspace); everything else goes through host memory.
 """
 from __future__ import annotations
 
@@ -130,4 +133,28 @@ def compute_normal_torch(vertices, faces):
 
     if not _is_tensor(vertices):
         return forward(vertices)[0]
-    return _autograd.apply(forward, vjp, (vertices,))[0]
+    return _autograd.apply(forward, vjp, (vertices,), device_route=_NormalsRoute(topo))[0]
+
+
+class _NormalsRoute:
+    """compute_normal_torch on vertices of the topology's GPU (_autograd.apply's device_route): bf_vertex_normals_dev and
+    bf_vertex_normals_vjp_dev on the tensors' addresses, the results in tensors made here"""
+
+    def __init__(self, topo):
+        self.topo, self.device = topo, getattr(topo, "dev_route_device", None)
+
+    def forward(self, tensors, stream):
+        import torch
+        from . import native
+        v = tensors[0]
+        out = torch.empty((self.topo.n_verts, 3), dtype=torch.float32, device=v.device)
+        native.vertex_normals_dev(self.topo, stream, v.data_ptr(), out.data_ptr())
+        return (out,)
+
+    def vjp(self, tensors, cotangents, want, stream):
+        import torch
+        from . import native
+        v = tensors[0]
+        out = torch.empty((self.topo.n_verts, 3), dtype=torch.float32, device=v.device)
+        native.vertex_normals_vjp_dev(self.topo, stream, v.data_ptr(), cotangents[0].data_ptr(), out.data_ptr())
+        return (out,)

@@ -283,8 +283,9 @@ int bf_keypoint_loss_dev(bf_workspace *ws, void *stream, const bf_gmm *gmm, cons
 /* BF_OK when this library's HIP runtime knows `p` as device memory of `device`, else BF_ERR_INVALID (NULL, host memory, memory
  * of another runtime or device).  Never sets bf_last_error and leaves no HIP error behind. */
 int bf_device_pointer_check(int device, const void *p);
-/* test hook, process-wide counts: out[0] calls of the five host entry points named above, out[1] calls of their _dev twins
- * (both counted once the arguments have passed), out[2] device (re)allocations of workspaces, out[3] calls that had to wait
+/* test hook, process-wide counts: out[0] calls of the five host entry points named above, of the SMPL+D stage's losses below
+ * (bf_vertex_normals, bf_vertex_normals_vjp, bf_normal_laplacian, bf_scan_point_loss, bf_normal_loss) and of bf_scan_nearest,
+ * out[1] calls of the *_dev entry points (both counted once the arguments have passed), out[2] device (re)allocations of workspaces, out[3] calls that had to wait
  * for their workspace's previous call on another stream. */
 int bf_dev_route_stats(int64_t out[4]);
 
@@ -316,6 +317,33 @@ int bf_scan_point_loss(bf_scan *s, int n, const float *points, float *loss, int3
  * (gathered by the caller, un-normalised as smplify.py:149 builds them), point_norms[n,3] -> loss[1] = mean(1 - sum(fn * pn)),
  * dpoint_norms[n,3] = -fn / n for cotangent 1.  Either output may be NULL = not wanted. */
 int bf_normal_loss(int device, int n, const float *closest_face_norms, const float *point_norms, float *loss, float *dpoint_norms);
+
+/* The device route of the calls above and of bf_scan_nearest (see bf_workspace): the twin's arguments as DEVICE pointers, then the
+ * workspace and the stream (a hipStream_t; NULL = the null stream).  Each issues its twin's kernels in its twin's order, with its
+ * grids and arguments, on `stream` - equal inputs give the twin's bits - writes its results through the caller's pointers and
+ * returns when the work is queued: no drain, no copy to the host.  A scalar loss is ONE float in device memory.  Scratch (face
+ * normals, partial sums, an output not wanted) comes from the workspace, which must live on the topology's / scan's device
+ * (BF_ERR_INVALID otherwise, as for a NULL workspace).  The first *_dev call on a scan puts the scan's descriptor into device
+ * memory, once, complete before that call returns.  Bad arguments fail before anything is queued, with the twin's refusals; the
+ * thread's current device is left as it was.  NULL outputs keep the twin's meaning. */
+int bf_vertex_normals_dev(const bf_topo *t, const float *verts, float *normals, bf_workspace *ws, void *stream);
+int bf_vertex_normals_vjp_dev(const bf_topo *t, const float *verts, const float *dnormals, float *dverts, bf_workspace *ws, void *stream);
+int bf_normal_laplacian_dev(const bf_topo *t, const float *norms, float *loss, float *dnorms, bf_workspace *ws, void *stream);
+int bf_scan_point_loss_dev(bf_scan *s, int n, const float *points, float *loss, int32_t *face_ids, float *nearest, float *dpoints,
+                           bf_workspace *ws, void *stream);
+/* bf_scan_nearest (no warm start): face_ids[n], nearest[n,3], bary[n,3], each may be NULL = not wanted */
+int bf_scan_nearest_dev(bf_scan *s, int n, const float *points, int32_t *face_ids, float *nearest, float *bary, bf_workspace *ws,
+                        void *stream);
+/* bf_normal_loss with the gather inside the kernel: face_ids[n] = the closest faces (bf_scan_point_loss_dev's or
+ * bf_scan_nearest_dev's), face_norm_table[n_faces,3] = the caller's whole face_norm_mesh; the bits are bf_normal_loss's on
+ * face_norm_table[face_ids].  An id outside [0, n_faces) is not dereferenced: its row adds 0 to the sum (the mean still divides by
+ * n) and its dpoint_norms row is zero. */
+int bf_normal_loss_dev(int device, int n, const int32_t *face_ids, const float *face_norm_table, int n_faces, const float *point_norms,
+                       float *loss, float *dpoint_norms, bf_workspace *ws, void *stream);
+/* The backward of a scalar loss without reading the cotangent back: out[n] = grad[n] * cotangent[0] in float32, plus_zero != 0:
+ * + 0.0f behind the product (a zero is +0 whatever the cotangent's sign).  All three are device pointers of `device`; out may be
+ * grad.  One launch on `stream`, no workspace. */
+int bf_scale_gradient_dev(int device, int n, const float *grad, const float *cotangent, int plus_zero, float *out, void *stream);
 
 /* The model's forward for `n` packed parameter vectors params[n,n_params] (any model kind): vertices[n,NV,3] in
  * model space and joints[n,n_joint_map,3], both before the similarity (either may be NULL). */

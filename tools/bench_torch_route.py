@@ -9,7 +9,14 @@ is 1 as the reference's, reads row 0, and a torch sum over all 64 rows' joints s
 Timing: a host clock around the loop, ending in torch.cuda.synchronize(), after a warm-up loop of the same shapes.
 The route is read once per process (BF_TORCH_DEVICE_ROUTE), so every measurement is a child process of its own; this process never
 touches the GPU.  The children alternate device, host, device, ... one at a time; medians and min-max per (route, batch) are printed
-and written as JSON.  The yardstick is the host route of the same build."""
+and written as JSON.  The yardstick is the host route of the same build.
+
+    python tools/bench_torch_route.py --stage smpld [--reps 5] [--iters 100] [--out profiles/torch_device_route_smpld.json]
+
+The SMPL+D stage instead (smplify.py:229-245 as written): compute_normal_torch, point_cloud_loss_mesh_grid, normal_loss_mesh_grid,
+normal_laplacian_smoothness, backward, Adam on the displacement - the full SMPL-X topology (10,475 vertices, 20,908 faces) against
+config 5's synthetic scan (83,784 triangles), all tensors on cuda:0, 100 iterations behind one warm-up step per process.
+`--child ROUTE --stage smpld --iters K` is one such process: what a profiler is pointed at."""
 from __future__ import annotations
 
 import argparse
@@ -73,6 +80,64 @@ def child(route, batch, iters, views, loops):
                       "calls": {k: stats1[k] - stats0[k] for k in stats1}}))
 
 
+def child_smpld(route, iters, loops):
+    os.environ["BF_TORCH_DEVICE_ROUTE"] = "1" if route == "device" else "0"
+    import numpy as np
+    import torch                                    # (before the library: the device route needs the shared runtime)
+    sys.path.insert(0, REPO)
+    from bodyfitting_amd import _autograd, native as N, synthetic as S
+    from bodyfitting_amd.loss import normal_laplacian_smoothness, normal_loss_mesh_grid, point_cloud_loss_mesh_grid
+    from bodyfitting_amd.mesh_grid_searcher import MeshGridSearcher
+    from bodyfitting_amd.normals import compute_normal_torch
+
+    device = torch.device("cuda:0")
+    model = S.make_model("smplx", seed=0)
+    _, scan_verts, scan_faces = S.make_scan_problem_smplx(model, 0, n_views=4, subdivide=1)
+    faces = np.asarray(model["faces"], np.int64).reshape(-1, 3)
+    nv = int(np.asarray(model["v_template"]).shape[0])
+    assert nv == 10475 and len(scan_faces) == 83784, (nv, len(scan_faces))
+    # the fitted body the stage starts from: the scan's own first 10,475 vertices (the posed body the scan was subdivided from, with
+    # the scan's noise) moved off the surface by a smooth centimetre
+    rng = np.random.default_rng(3)
+    body = scan_verts[:nv] + 0.01 * np.sin(7.0 * scan_verts[:nv, ::-1]) + rng.normal(0, 0.002, (nv, 3))
+    tris = scan_verts[scan_faces]
+    face_norms = torch.from_numpy(np.cross(tris[::, 1] - tris[::, 0], tris[::, 2] - tris[::, 0])).float().to(device)
+    constant_scale = float((scan_verts.max(0) - scan_verts.min(0))[1] / 1.7)
+    pointsearcher = MeshGridSearcher(verts=scan_verts, faces=scan_faces)
+    body_vertices = torch.from_numpy(body.astype(np.float32)).reshape(1, -1, 3).to(device)
+    smpl_faces = torch.from_numpy(faces).long().to(device)
+
+    def loop(n):
+        disp = torch.zeros_like(body_vertices)
+        disp.requires_grad = True
+        optimizer = torch.optim.Adam([disp], lr=5e-2, betas=(0.9, 0.999))
+        for _ in range(n):
+            deformed_verts = body_vertices + disp
+            deformed_norms = compute_normal_torch(deformed_verts, smpl_faces)
+            icp_loss = point_cloud_loss_mesh_grid(pointsearcher, deformed_verts)
+            norm_loss = normal_loss_mesh_grid(pointsearcher, deformed_verts, face_norms, deformed_norms)
+            smoothness = normal_laplacian_smoothness(deformed_norms, smpl_faces)
+            loss = icp_loss + (norm_loss + smoothness) * constant_scale * 0.1
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+        torch.cuda.synchronize()
+        return float(loss.detach())
+
+    took = _autograd.chosen_route([body_vertices], type("Offer", (), {"device": 0})())
+    assert took == route, f"asked for the {route} route, the process takes the {took} route"
+    first = loop(1)                                 # warm-up: one step of the same shapes
+    times, stats0 = [], N.dev_route_stats()
+    for _ in range(loops):
+        t0 = time.perf_counter()
+        last = loop(iters)
+        times.append(time.perf_counter() - t0)
+    stats1 = N.dev_route_stats()
+    print(json.dumps({"route": route, "batch": 1, "stage": "smpld", "iters": iters, "seconds": times, "first_loss": first, "final_loss": last,
+                      "calls": {k: stats1[k] - stats0[k] for k in stats1}}))
+    pointsearcher.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--child", choices=("device", "host"))
@@ -84,15 +149,18 @@ def main():
     ap.add_argument("--loops", type=int, default=1, help="timed loops per process, behind its warm-up loop")
     ap.add_argument("--timeout", type=int, default=300, help="seconds a child may take")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--stage", choices=("keypoint", "smpld"), default="keypoint", help="smpld: the SMPL+D loop (one evaluation per step)")
     a = ap.parse_args()
     if a.child:
-        return child(a.child, a.batch, a.iters, a.views, a.loops)
+        return child_smpld(a.child, a.iters, a.loops) if a.stage == "smpld" else child(a.child, a.batch, a.iters, a.views, a.loops)
+    if a.stage == "smpld":
+        a.batches = [1]
     runs = []
     for batch in a.batches:
         for rep in range(a.reps):
             for route in ("device", "host"):
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", route, "--batch", str(batch), "--iters", str(a.iters),
-                       "--views", str(a.views), "--loops", str(a.loops)]
+                       "--views", str(a.views), "--loops", str(a.loops), "--stage", a.stage]
                 done = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
                 if done.returncode != 0:            # (a child that failed ends the run: nothing more is started on the card)
                     sys.stderr.write(done.stdout[-2000:] + done.stderr[-4000:])
@@ -110,7 +178,7 @@ def main():
         row["larger_spread_ms"] = spread
         row["device_faster_beyond_spread"] = row["host_minus_device_ms"] > spread
         summary.append(row)
-    result = {"iters": a.iters, "views": a.views, "summary": summary, "runs": runs}
+    result = {"stage": a.stage, "iters": a.iters, "views": a.views, "summary": summary, "runs": runs}
     print(json.dumps({"summary": summary}))
     if a.out:
         with open(a.out, "w") as f:
