@@ -1,5 +1,6 @@
-// Host side of bf_workspace_create / bf_workspace_destroy / bf_device_pointer_check / bf_dev_route_stats (include/bodyfit.h) and of
-// the workspace the *_dev entry points run on (dev_route.h): grow-only device buffers, one event, no block cache.
+// Host side of bf_workspace_create / bf_workspace_destroy / bf_device_pointer_check / bf_dev_route_stats (include/bodyfit.h), of the
+// workspace the *_dev entry points run on - grow-only device buffers, one event, no block cache - and of the call context both routes
+// of an entry point share (BfRouteCall, dev_route.h).
 #include "dev_route.h"
 
 extern "C" int bf_workspace_create(int device, bf_workspace **out) {
@@ -26,8 +27,11 @@ extern "C" void bf_workspace_destroy(bf_workspace *ws) {
     delete ws;
 }
 
-int BfWsCall::begin() {
+int BfRouteCall::begin(int dev) {
+    HIP_TRY(hipSetDevice(dev));
+    device = dev;
     begun = true;
+    if (!ws) return BF_OK;
     ws->plan.begin();
     if (bf_ws_must_wait(ws->used, ws->last, stream)) {
         HIP_TRY(hipStreamWaitEvent(stream, ws->ev, 0));
@@ -36,15 +40,35 @@ int BfWsCall::begin() {
     return BF_OK;
 }
 
-BfWsCall::~BfWsCall() {
+int BfRouteCall::finish() {
+    HIP_TRY(hipGetLastError());
+    if (ws) return BF_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    for (const Back &b : back) HIP_TRY(hipMemcpy(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost));
+    return BF_OK;
+}
+
+BfRouteCall::~BfRouteCall() {
     if (!begun) return;
+    if (!ws) {
+        (void)hipDeviceSynchronize();         // whatever path leaves the call, no kernel still uses a block when it goes back to the cache
+        for (const Owned &b : owned) bf_pool_free(b.p, b.bytes, device);
+        return;
+    }
     // (on a failed record the next call on another stream would wait for an older end: drain instead, once)
     if (hipEventRecord(ws->ev, stream) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
     ws->used = true;
     ws->last = stream;
 }
 
-int bf_ws_take(bf_workspace *ws, size_t bytes, void **p) {
+// the call's next buffer of `bytes` (contents undefined)
+int BfRouteCall::block(size_t bytes, void **p) {
+    if (!ws) {
+        size_t got = 0;
+        HIP_TRY(bf_pool_alloc(p, bytes, &got));
+        owned.push_back({*p, got});
+        return BF_OK;
+    }
     bool grow = false;
     size_t alloc_bytes = 0;
     const size_t k = ws->plan.take(bytes, &grow, &alloc_bytes);

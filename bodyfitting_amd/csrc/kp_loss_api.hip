@@ -1,6 +1,8 @@
-// Host side of bf_gmm_create / bf_gmm_destroy / bf_keypoint_loss (include/bodyfit.h): the reference's multiview_keypoint_loss and
-// MaxMixturePrior as one stateless call on host arrays - what a user's own torch loop (smplify.py:177-213) evaluates behind the
-// body model.  One launch of bf_keypoint_loss_kernel (kp_loss_kernels.hip); the call's buffers come from the device's block cache.
+// Host side of bf_gmm_create / bf_gmm_destroy / bf_keypoint_loss / bf_keypoint_loss_dev (include/bodyfit.h): the reference's
+// multiview_keypoint_loss and MaxMixturePrior as one stateless call - what a user's own torch loop (smplify.py:177-213) evaluates
+// behind the body model.  One launch of bf_keypoint_loss_kernel (kp_loss_kernels.hip), issued by ONE body on a BfRouteCall
+// (dev_route.h); the two entry points check their arguments, count their route and hand it their call: host arrays, the block cache's
+// buffers and a drain, or device pointers on the caller's stream with a bf_workspace.
 #include "bf_host.h"
 #include "dev_route.h"
 #include "kp_loss_kernels.h"
@@ -12,8 +14,6 @@ struct bf_gmm {
 };
 
 namespace {
-struct DrainOnExit { ~DrainOnExit() { (void)hipDeviceSynchronize(); } };
-
 // the sizes against the kernel's LDS tables (BF_KPL_MAX_*, bf_internal.h) and against each other
 int bf_kp_loss_check(const bf_gmm *g, const bf_keypoint_loss_in *in, const float *dposes, const float *dbetas) {
     const char *who = "bf_keypoint_loss: ";
@@ -35,6 +35,43 @@ int bf_kp_loss_check(const bf_gmm *g, const bf_keypoint_loss_in *in, const float
         if (in->n_betas > BF_KPL_MAX_BETAS) return fail(BF_ERR_UNSUPPORTED, std::string(who) + "more than " + std::to_string(BF_KPL_MAX_BETAS) + " betas");
     } else if (dbetas) return fail(BF_ERR_INVALID, std::string(who) + "dbetas asked for without betas");
     return BF_OK;
+}
+
+// The one launch, on either route (sizes checked, an output wanted).  divisor[n] is a host array on both: the host route uploads it with
+// the others, the device route sends it through the workspace, and only when it differs from what the workspace sent last.
+int bf_kp_loss_run(BfRouteCall &c, int device, const bf_gmm *gmm, const bf_keypoint_loss_in *in, const bf_hyper &h, const float *dterms,
+                   float *terms, float *djoints, float *dposes, float *dbetas) {
+    BF_TRY(c.begin(device));
+    const size_t N = (size_t)in->n, V = (size_t)in->n_views, R = (size_t)in->n_rows;
+    const bool views = V > 0 && R > 0;
+    KpLossIO Q{};
+    Q.n_views = views ? in->n_views : 0;
+    Q.n_rows = in->n_rows;
+    if (R > 0) BF_TRY(c.in(in->joints, N * R * 3, Q.joints));
+    if (views) {
+        BF_TRY(c.in(in->w2c, N * V * 16, Q.w2c));
+        BF_TRY(c.in(in->K, N * V * 9, Q.K));
+        BF_TRY(c.in(in->keypoints, N * V * R * 3, Q.keypoints));
+        if (c.ws) BF_TRY(bf_ws_divisor(c.ws, c.stream, in->divisor, N, &Q.divisor));
+        else BF_TRY(c.in(in->divisor, N, Q.divisor));
+        BF_TRY(c.in(in->present, N * V, Q.present));
+    }
+    if (in->poses) {
+        Q.pose_dim = in->pose_dim;
+        BF_TRY(c.in(in->poses, N * in->pose_dim, Q.poses));
+        if (gmm) { Q.gmm_comp = gmm->n_comp; Q.gmm_dim = gmm->dim; Q.g_means = gmm->means.p; Q.g_prec = gmm->prec.p; Q.g_logw = gmm->logw.p; }
+    }
+    if (in->betas) {
+        Q.n_betas = in->n_betas;
+        BF_TRY(c.in(in->betas, N * in->n_betas, Q.betas));
+    }
+    BF_TRY(c.in(dterms, N * 4, Q.dterms));
+    BF_TRY(c.out(terms, N * 4, Q.terms));
+    if (R > 0) BF_TRY(c.out(djoints, N * R * 3, Q.djoints));
+    BF_TRY(c.out(dposes, N * in->pose_dim, Q.dposes));
+    BF_TRY(c.out(dbetas, N * in->n_betas, Q.dbetas));
+    hipLaunchKernelGGL(bf_keypoint_loss_kernel, dim3((unsigned)N), dim3(BF_KPL_THREADS), 0, c.stream, Q, bf_to_dev(h));
+    return c.finish();
 }
 }  // namespace
 
@@ -77,54 +114,12 @@ extern "C" int bf_keypoint_loss(int device, const bf_gmm *gmm, const bf_keypoint
     bf_hyper h;
     if (hyper) h = *hyper; else bf_hyper_default(&h);
     if (!(h.imsize > 0.f)) return fail(BF_ERR_INVALID, "bf_keypoint_loss: imsize must be positive");
-    HIP_TRY(hipSetDevice(device));
-    const size_t N = (size_t)in->n, V = (size_t)in->n_views, R = (size_t)in->n_rows;
-    const bool views = V > 0 && R > 0;
-    DevBuf<float> d_joints, d_w2c, d_K, d_kp, d_poses, d_betas, d_dterms, d_terms, d_dj, d_dp, d_db;
-    DevBuf<unsigned char> d_present;
-    DevBuf<int> d_div;
-    DrainOnExit drain;               // (destroyed before the buffers: no kernel still uses a block when it goes back to the cache)
-    KpLossIO Q{};
-    Q.n_views = views ? in->n_views : 0;
-    Q.n_rows = in->n_rows;
-    if (R > 0) { HIP_TRY(d_joints.upload_pooled(in->joints, N * R * 3)); Q.joints = d_joints.p; }
-    if (views) {
-        HIP_TRY(d_w2c.upload_pooled(in->w2c, N * V * 16));
-        HIP_TRY(d_K.upload_pooled(in->K, N * V * 9));
-        HIP_TRY(d_kp.upload_pooled(in->keypoints, N * V * R * 3));
-        HIP_TRY(d_div.upload_pooled(in->divisor, N));
-        Q.w2c = d_w2c.p; Q.K = d_K.p; Q.keypoints = d_kp.p; Q.divisor = d_div.p;
-        if (in->present) { HIP_TRY(d_present.upload_pooled(in->present, N * V)); Q.present = d_present.p; }
-    }
-    if (in->poses) {
-        Q.pose_dim = in->pose_dim;
-        HIP_TRY(d_poses.upload_pooled(in->poses, N * in->pose_dim));
-        Q.poses = d_poses.p;
-        if (gmm) { Q.gmm_comp = gmm->n_comp; Q.gmm_dim = gmm->dim; Q.g_means = gmm->means.p; Q.g_prec = gmm->prec.p; Q.g_logw = gmm->logw.p; }
-    }
-    if (in->betas) {
-        Q.n_betas = in->n_betas;
-        HIP_TRY(d_betas.upload_pooled(in->betas, N * in->n_betas));
-        Q.betas = d_betas.p;
-    }
-    if (dterms) { HIP_TRY(d_dterms.upload_pooled(dterms, N * 4)); Q.dterms = d_dterms.p; }
-    if (terms) { HIP_TRY(d_terms.alloc_pooled(N * 4)); Q.terms = d_terms.p; }
-    if (djoints && R > 0) { HIP_TRY(d_dj.alloc_pooled(N * R * 3)); Q.djoints = d_dj.p; }
-    if (dposes) { HIP_TRY(d_dp.alloc_pooled(N * in->pose_dim)); Q.dposes = d_dp.p; }
-    if (dbetas) { HIP_TRY(d_db.alloc_pooled(N * in->n_betas)); Q.dbetas = d_db.p; }
-    hipLaunchKernelGGL(bf_keypoint_loss_kernel, dim3((unsigned)N), dim3(BF_KPL_THREADS), 0, 0, Q, bf_to_dev(h));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (terms) HIP_TRY(hipMemcpy(terms, d_terms.p, N * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    if (Q.djoints) HIP_TRY(hipMemcpy(djoints, d_dj.p, N * R * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (dposes) HIP_TRY(hipMemcpy(dposes, d_dp.p, N * in->pose_dim * sizeof(float), hipMemcpyDeviceToHost));
-    if (dbetas) HIP_TRY(hipMemcpy(dbetas, d_db.p, N * in->n_betas * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
+    BfRouteCall c(nullptr, nullptr);
+    return bf_kp_loss_run(c, device, gmm, in, h, dterms, terms, djoints, dposes, dbetas);
 }
 
-// The device route (dev_route.h): the same launch on the caller's stream.  Every array of `in` but `divisor` is a device pointer and is
-// read where it lies; the results are written where the caller wants them; divisor[n], validated on the host as above, is the one
-// thing sent, through the workspace, and only when it differs from what the workspace sent last.
+// The device route: every array of `in` but `divisor` is a device pointer and is read where it lies; the results are written where the
+// caller wants them; divisor[n], validated on the host as above, is the one thing sent (bf_kp_loss_run).
 extern "C" int bf_keypoint_loss_dev(bf_workspace *ws, void *stream, const bf_gmm *gmm, const bf_keypoint_loss_in *in, const bf_hyper *hyper,
                                     const float *dterms, float *terms, float *djoints, float *dposes, float *dbetas) {
     if (!ws || !in) return fail(BF_ERR_INVALID, "bf_keypoint_loss_dev: bad argument");
@@ -135,33 +130,6 @@ extern "C" int bf_keypoint_loss_dev(bf_workspace *ws, void *stream, const bf_gmm
     if (!(h.imsize > 0.f)) return fail(BF_ERR_INVALID, "bf_keypoint_loss_dev: imsize must be positive");
     ++bf_route_stats().dev;
     if (!terms && !djoints && !dposes && !dbetas) return BF_OK;
-    BfDeviceGuard keep;
-    HIP_TRY(hipSetDevice(ws->device));
-    const hipStream_t s = (hipStream_t)stream;
-    const size_t N = (size_t)in->n;
-    const bool views = in->n_views > 0 && in->n_rows > 0;
-    BfWsCall call(ws, s);
-    BF_TRY(call.begin());
-    KpLossIO Q{};
-    Q.n_views = views ? in->n_views : 0;
-    Q.n_rows = in->n_rows;
-    if (in->n_rows > 0) Q.joints = in->joints;
-    if (views) {
-        Q.w2c = in->w2c; Q.K = in->K; Q.keypoints = in->keypoints; Q.present = in->present;
-        BF_TRY(bf_ws_divisor(ws, s, in->divisor, N, &Q.divisor));
-    }
-    if (in->poses) {
-        Q.pose_dim = in->pose_dim;
-        Q.poses = in->poses;
-        if (gmm) { Q.gmm_comp = gmm->n_comp; Q.gmm_dim = gmm->dim; Q.g_means = gmm->means.p; Q.g_prec = gmm->prec.p; Q.g_logw = gmm->logw.p; }
-    }
-    if (in->betas) { Q.n_betas = in->n_betas; Q.betas = in->betas; }
-    Q.dterms = dterms;
-    Q.terms = terms;
-    if (in->n_rows > 0) Q.djoints = djoints;
-    Q.dposes = dposes;
-    Q.dbetas = dbetas;
-    hipLaunchKernelGGL(bf_keypoint_loss_kernel, dim3((unsigned)N), dim3(BF_KPL_THREADS), 0, s, Q, bf_to_dev(h));
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
+    BfRouteCall c(ws, (hipStream_t)stream);
+    return bf_kp_loss_run(c, ws->device, gmm, in, h, dterms, terms, djoints, dposes, dbetas);
 }

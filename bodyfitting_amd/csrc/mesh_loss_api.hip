@@ -1,7 +1,10 @@
-// Host side of bf_topo_* / bf_vertex_normals(_vjp) / bf_normal_laplacian / bf_scan_point_loss / bf_normal_loss (include/bodyfit.h):
-// the SMPL+D stage's losses (smplify.py:236-245) as stateless calls on host arrays, for a user's own torch loop.  Kernels:
-// mesh_loss_kernels.hip; the call's buffers come from the device's block cache; everything runs on the NULL stream, like
-// bf_scan_nearest.  Their device route (bf_*_dev: device pointers, the caller's stream, a bf_workspace) is the second half of this file.
+// Host side of bf_topo_* / bf_vertex_normals(_vjp) / bf_normal_laplacian / bf_scan_point_loss / bf_normal_loss and of their *_dev
+// twins (include/bodyfit.h): the SMPL+D stage's losses (smplify.py:236-245) as stateless calls, for a user's own torch loop.  Kernels:
+// mesh_loss_kernels.hip.  Every operation is ONE body on a BfRouteCall (dev_route.h) and its two entry points are wrappers that check
+// their arguments, count their route and hand the body its call: host arrays on the NULL stream with the block cache's buffers and one
+// drain (like bf_scan_nearest), or device pointers on the caller's stream with a bf_workspace, where nothing is drained, nothing is
+// copied to the host and a scalar loss is one float in device memory.  Both routes of a call issue the same kernels in the same order
+// with the same grids and arguments.
 #include "bf_host.h"
 #include "dev_route.h"
 #include "mesh_loss_kernels.h"
@@ -14,7 +17,6 @@ struct bf_topo {
 };
 
 namespace {
-struct DrainOnExit { ~DrainOnExit() { (void)hipDeviceSynchronize(); } };
 constexpr int BF_ML_MAX = 1 << 28;        // vertices, faces or points of one call: face * 4 + corner and index * 3 stay inside an int
 
 inline unsigned blocks(int n) { return (unsigned)((n + 255) / 256); }
@@ -54,8 +56,12 @@ extern "C" void bf_topo_destroy(bf_topo *t) {
     delete t;
 }
 
+// ----------------------------------------------------------------------------------------------------------------------------------
+// The bodies: one launch sequence per operation, on either route
+// ----------------------------------------------------------------------------------------------------------------------------------
+namespace {
 // face and vertex normals of `d_v` on the device (the forward, and the first half of the reverse)
-static int bf_ml_normals_launch(const bf_topo *t, const float *d_v, float *d_fn, float *d_vn, float *d_out, hipStream_t st = nullptr) {
+int bf_ml_normals_launch(const bf_topo *t, const float *d_v, float *d_fn, float *d_vn, float *d_out, hipStream_t st) {
     hipLaunchKernelGGL(bf_ml_face_kernel, dim3(blocks(t->nf)), dim3(256), 0, st, (const int *)t->faces.p, t->nf, d_v, d_fn);
     hipLaunchKernelGGL(bf_ml_vertex_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->adj_start.p, (const int *)t->adj.p, t->nv,
                        (const float *)d_fn, d_vn, d_out);
@@ -63,151 +69,61 @@ static int bf_ml_normals_launch(const bf_topo *t, const float *d_v, float *d_fn,
     return BF_OK;
 }
 
-extern "C" int bf_vertex_normals(const bf_topo *t, const float *verts, float *normals) {
-    if (!t || !verts || !normals) return fail(BF_ERR_INVALID, "bf_vertex_normals: bad argument");
-    ++bf_route_stats().host;
-    HIP_TRY(hipSetDevice(t->device));
-    const size_t nv = (size_t)t->nv, nf = (size_t)t->nf;
-    DevBuf<float> d_v, d_fn, d_n;
-    DrainOnExit drain;               // (destroyed before the buffers: no kernel still uses a block when it goes back to the cache)
-    HIP_TRY(d_v.upload_pooled(verts, nv * 3));
-    HIP_TRY(d_fn.alloc_pooled(nf * 4)); HIP_TRY(d_n.alloc_pooled(nv * 3));
-    BF_TRY(bf_ml_normals_launch(t, d_v.p, d_fn.p, nullptr, d_n.p));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(normals, d_n.p, nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
+// the last launch of the three scalar losses: d_loss[0] = the nblk block sums of d_part, reduced (mode, divisor: bf_ml_finish_kernel)
+void bf_ml_finish_launch(const BfRouteCall &c, const float *d_part, unsigned nblk, int mode, float divisor, float *d_loss) {
+    hipLaunchKernelGGL(bf_ml_finish_kernel, dim3(1), dim3(256), 0, c.stream, d_part, (int)nblk, mode, divisor, d_loss);
 }
 
-extern "C" int bf_vertex_normals_vjp(const bf_topo *t, const float *verts, const float *dnormals, float *dverts) {
-    if (!t || !verts || !dnormals || !dverts) return fail(BF_ERR_INVALID, "bf_vertex_normals_vjp: bad argument");
-    ++bf_route_stats().host;
-    HIP_TRY(hipSetDevice(t->device));
-    const size_t nv = (size_t)t->nv, nf = (size_t)t->nf;
-    DevBuf<float> d_v, d_dn, d_fn, d_vn, d_raw, d_dPf, d_dv;
-    DrainOnExit drain;
-    HIP_TRY(d_v.upload_pooled(verts, nv * 3));
-    HIP_TRY(d_dn.upload_pooled(dnormals, nv * 3));
-    HIP_TRY(d_fn.alloc_pooled(nf * 4)); HIP_TRY(d_vn.alloc_pooled(nv * 4)); HIP_TRY(d_raw.alloc_pooled(nv * 3));
-    HIP_TRY(d_dPf.alloc_pooled(nf * 9)); HIP_TRY(d_dv.alloc_pooled(nv * 3));
-    BF_TRY(bf_ml_normals_launch(t, d_v.p, d_fn.p, d_vn.p, nullptr));
-    hipLaunchKernelGGL(bf_ml_vraw_kernel, dim3(blocks(t->nv)), dim3(256), 0, 0, t->nv, (const float *)d_vn.p, (const float *)d_dn.p, d_raw.p);
-    hipLaunchKernelGGL(bf_ml_fgrad_kernel, dim3(blocks(t->nf)), dim3(256), 0, 0, (const int *)t->faces.p, t->nf, (const float *)d_v.p,
-                       (const float *)d_fn.p, (const float *)d_raw.p, d_dPf.p);
-    hipLaunchKernelGGL(bf_ml_gather_kernel, dim3(blocks(t->nv)), dim3(256), 0, 0, (const int *)t->adj_start.p, (const int *)t->adj.p, t->nv,
-                       (const float *)d_dPf.p, d_dv.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(dverts, d_dv.p, nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
+int bf_ml_normals(BfRouteCall &c, const bf_topo *t, const float *verts, float *normals) {
+    BF_TRY(c.begin(t->device));
+    const float *d_v = nullptr;
+    float *d_fn = nullptr, *d_n = nullptr;
+    BF_TRY(c.in(verts, (size_t)t->nv * 3, d_v));
+    BF_TRY(c.scratch((size_t)t->nf * 4, d_fn));
+    BF_TRY(c.out(normals, (size_t)t->nv * 3, d_n));
+    BF_TRY(bf_ml_normals_launch(t, d_v, d_fn, nullptr, d_n, c.stream));
+    return c.finish();
 }
 
-extern "C" int bf_normal_laplacian(const bf_topo *t, const float *norms, float *loss, float *dnorms) {
-    if (!t || !norms) return fail(BF_ERR_INVALID, "bf_normal_laplacian: bad argument");
-    ++bf_route_stats().host;
-    if (!loss && !dnorms) return BF_OK;
-    HIP_TRY(hipSetDevice(t->device));
-    const size_t nv = (size_t)t->nv;
+int bf_ml_normals_vjp(BfRouteCall &c, const bf_topo *t, const float *verts, const float *dnormals, float *dverts) {
+    BF_TRY(c.begin(t->device));
+    const hipStream_t st = c.stream;
+    const size_t nv = (size_t)t->nv, nf = (size_t)t->nf;
+    const float *d_v = nullptr, *d_dn = nullptr;
+    float *d_fn = nullptr, *d_vn = nullptr, *d_raw = nullptr, *d_dPf = nullptr, *d_dv = nullptr;
+    BF_TRY(c.in(verts, nv * 3, d_v));
+    BF_TRY(c.in(dnormals, nv * 3, d_dn));
+    BF_TRY(c.scratch(nf * 4, d_fn)); BF_TRY(c.scratch(nv * 4, d_vn)); BF_TRY(c.scratch(nv * 3, d_raw)); BF_TRY(c.scratch(nf * 9, d_dPf));
+    BF_TRY(c.out(dverts, nv * 3, d_dv));
+    BF_TRY(bf_ml_normals_launch(t, d_v, d_fn, d_vn, nullptr, st));
+    hipLaunchKernelGGL(bf_ml_vraw_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, t->nv, (const float *)d_vn, d_dn, d_raw);
+    hipLaunchKernelGGL(bf_ml_fgrad_kernel, dim3(blocks(t->nf)), dim3(256), 0, st, (const int *)t->faces.p, t->nf, d_v, (const float *)d_fn,
+                       (const float *)d_raw, d_dPf);
+    hipLaunchKernelGGL(bf_ml_gather_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->adj_start.p, (const int *)t->adj.p, t->nv,
+                       (const float *)d_dPf, d_dv);
+    return c.finish();
+}
+
+// (loss or dnorms is wanted)
+int bf_ml_laplacian(BfRouteCall &c, const bf_topo *t, const float *norms, float *loss, float *dnorms) {
+    BF_TRY(c.begin(t->device));
+    const hipStream_t st = c.stream;
     const unsigned nblk = blocks(t->nf);
-    DevBuf<float> d_n, d_part, d_loss, d_dn;
-    DrainOnExit drain;
-    HIP_TRY(d_n.upload_pooled(norms, nv * 3));
+    const float *d_n = nullptr;
+    float *d_part = nullptr, *d_loss = nullptr, *d_dn = nullptr;
+    BF_TRY(c.in(norms, (size_t)t->nv * 3, d_n));
     if (loss) {
-        HIP_TRY(d_part.alloc_pooled(nblk)); HIP_TRY(d_loss.alloc_pooled(1));
-        hipLaunchKernelGGL(bf_ml_lap_partial_kernel, dim3(nblk), dim3(256), 0, 0, (const int *)t->faces.p, t->nf, (const float *)d_n.p, d_part.p);
-        hipLaunchKernelGGL(bf_ml_finish_kernel, dim3(1), dim3(256), 0, 0, (const float *)d_part.p, (int)nblk, 0, (float)t->nf, d_loss.p);
+        BF_TRY(c.scratch(nblk, d_part));
+        BF_TRY(c.out(loss, 1, d_loss));
+        hipLaunchKernelGGL(bf_ml_lap_partial_kernel, dim3(nblk), dim3(256), 0, st, (const int *)t->faces.p, t->nf, d_n, d_part);
+        bf_ml_finish_launch(c, d_part, nblk, 0, (float)t->nf, d_loss);
     }
     if (dnorms) {
-        HIP_TRY(d_dn.alloc_pooled(nv * 3));
-        hipLaunchKernelGGL(bf_ml_lap_grad_kernel, dim3(blocks(t->nv)), dim3(256), 0, 0, (const int *)t->faces.p, (const int *)t->adj_start.p,
-                           (const int *)t->adj.p, t->nf, t->nv, (const float *)d_n.p, d_dn.p);
+        BF_TRY(c.out(dnorms, (size_t)t->nv * 3, d_dn));
+        hipLaunchKernelGGL(bf_ml_lap_grad_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->faces.p, (const int *)t->adj_start.p,
+                           (const int *)t->adj.p, t->nf, t->nv, d_n, d_dn);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (loss) HIP_TRY(hipMemcpy(loss, d_loss.p, sizeof(float), hipMemcpyDeviceToHost));
-    if (dnorms) HIP_TRY(hipMemcpy(dnorms, d_dn.p, nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
-}
-
-extern "C" int bf_scan_point_loss(bf_scan *s, int n, const float *points, float *loss, int32_t *face_ids, float *nearest, float *dpoints) {
-    const char *who = "bf_scan_point_loss";
-    if (!s || !points) return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");
-    BF_TRY(bf_ml_check_count(who, "points", n));
-    ++bf_route_stats().host;
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t N = (size_t)n;
-    const unsigned nblk = blocks(n);
-    DevBuf<float> d_p, d_c, d_part, d_loss, d_dp;
-    DevBuf<int> d_f;
-    DevBuf<ScanDev> d_s;
-    DrainOnExit drain;
-    HIP_TRY(d_p.upload_pooled(points, N * 3));
-    HIP_TRY(d_c.alloc_pooled(N * 3)); HIP_TRY(d_f.alloc_pooled(N));
-    HIP_TRY(d_s.upload_pooled(&s->dev, 1));
-    // the closest-point launch of bf_scan_nearest (no warm start, no barycentrics), then the reduction on the points already there
-    bf_nearest_launch(dim3((n + 3) / 4, 1), 0, (const ScanDev *)d_s.p, (const float *)d_p.p, n, d_f.p, d_c.p, (float *)nullptr, 0);
-    if (loss || dpoints) {
-        HIP_TRY(d_part.alloc_pooled(nblk)); HIP_TRY(d_loss.alloc_pooled(1));
-        hipLaunchKernelGGL(bf_ml_pc_partial_kernel, dim3(nblk), dim3(256), 0, 0, n, (const float *)d_p.p, (const float *)d_c.p, d_part.p);
-        hipLaunchKernelGGL(bf_ml_finish_kernel, dim3(1), dim3(256), 0, 0, (const float *)d_part.p, (int)nblk, 1, 1.f, d_loss.p);
-    }
-    if (dpoints) {
-        HIP_TRY(d_dp.alloc_pooled(N * 3));
-        hipLaunchKernelGGL(bf_ml_pc_grad_kernel, dim3(nblk), dim3(256), 0, 0, n, (const float *)d_p.p, (const float *)d_c.p,
-                           (const float *)d_loss.p, d_dp.p);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (loss) HIP_TRY(hipMemcpy(loss, d_loss.p, sizeof(float), hipMemcpyDeviceToHost));
-    if (face_ids) HIP_TRY(hipMemcpy(face_ids, d_f.p, N * sizeof(int), hipMemcpyDeviceToHost));
-    if (nearest) HIP_TRY(hipMemcpy(nearest, d_c.p, N * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (dpoints) HIP_TRY(hipMemcpy(dpoints, d_dp.p, N * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
-}
-
-extern "C" int bf_normal_loss(int device, int n, const float *closest_face_norms, const float *point_norms, float *loss, float *dpoint_norms) {
-    const char *who = "bf_normal_loss";
-    if (!closest_face_norms || !point_norms) return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");
-    BF_TRY(bf_ml_check_count(who, "points", n));
-    ++bf_route_stats().host;
-    if (!loss && !dpoint_norms) return BF_OK;
-    HIP_TRY(hipSetDevice(device));
-    const size_t N = (size_t)n;
-    const unsigned nblk = blocks(n);
-    DevBuf<float> d_fn, d_pn, d_part, d_loss, d_dpn;
-    DrainOnExit drain;
-    HIP_TRY(d_fn.upload_pooled(closest_face_norms, N * 3));
-    HIP_TRY(d_pn.upload_pooled(point_norms, N * 3));
-    HIP_TRY(d_part.alloc_pooled(nblk)); HIP_TRY(d_loss.alloc_pooled(1));
-    if (dpoint_norms) HIP_TRY(d_dpn.alloc_pooled(N * 3));
-    hipLaunchKernelGGL(bf_ml_normal_partial_kernel, dim3(nblk), dim3(256), 0, 0, n, (const float *)d_fn.p, (const float *)d_pn.p, d_part.p,
-                       d_dpn.p);
-    hipLaunchKernelGGL(bf_ml_finish_kernel, dim3(1), dim3(256), 0, 0, (const float *)d_part.p, (int)nblk, 0, (float)n, d_loss.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (loss) HIP_TRY(hipMemcpy(loss, d_loss.p, sizeof(float), hipMemcpyDeviceToHost));
-    if (dpoint_norms) HIP_TRY(hipMemcpy(dpoint_norms, d_dpn.p, N * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
-}
-
-// ----------------------------------------------------------------------------------------------------------------------------------
-// The device route (dev_route.h) of the calls above and of bf_scan_nearest: the twin's kernels in the twin's order, with its grids and
-// arguments, on the caller's stream; every array a device pointer, read and written where it lies; scratch from the workspace.  Nothing
-// is drained and nothing is copied to the host: a scalar loss is one float in device memory.
-// ----------------------------------------------------------------------------------------------------------------------------------
-namespace {
-// what every *_dev call here checks first: -> BF_OK, or the refusal (nothing has been queued)
-int bf_ml_dev_check(const char *who, const bf_workspace *ws, int device) {
-    if (!ws) return fail(BF_ERR_INVALID, std::string(who) + ": the workspace is NULL");
-    if (ws->device != device) return fail(BF_ERR_INVALID, std::string(who) + ": the workspace lives on another device");
-    return BF_OK;
-}
-
-template <class T>
-int bf_ml_take(bf_workspace *ws, size_t count, T **p) {
-    void *v = nullptr;
-    BF_TRY(bf_ws_take(ws, count * sizeof(T), &v));
-    *p = (T *)v;
-    return BF_OK;
+    return c.finish();
 }
 
 // the scan's ScanDev in device memory, made once per scan: complete on the device when this returns (later calls come on any stream)
@@ -221,21 +137,97 @@ int bf_scan_resident(bf_scan *s, const ScanDev **out) {
     *out = s->dev_resident.p;
     return BF_OK;
 }
+
+// the scan's ScanDev where the kernels of `c` read it: the host route uploads it with the call, the device route keeps it resident
+int bf_ml_scan_dev(BfRouteCall &c, bf_scan *s, const ScanDev *&d_s) {
+    if (c.ws) return bf_scan_resident(s, &d_s);
+    return c.in(&s->dev, 1, d_s);
+}
+
+int bf_ml_point_loss(BfRouteCall &c, bf_scan *s, int n, const float *points, float *loss, int32_t *face_ids, float *nearest, float *dpoints) {
+    BF_TRY(c.begin(s->device));
+    const hipStream_t st = c.stream;
+    const size_t N = (size_t)n;
+    const unsigned nblk = blocks(n);
+    const float *d_p = nullptr;
+    const ScanDev *d_s = nullptr;
+    int *d_f = nullptr;
+    float *d_c = nullptr, *d_part = nullptr, *d_loss = nullptr, *d_dp = nullptr;
+    BF_TRY(c.in(points, N * 3, d_p));
+    // (the launch writes both: an output not wanted lands in a buffer of the call)
+    BF_TRY(c.out((int *)face_ids, N, d_f, true));
+    BF_TRY(c.out(nearest, N * 3, d_c, true));
+    BF_TRY(bf_ml_scan_dev(c, s, d_s));
+    // the closest-point launch of bf_scan_nearest (no warm start, no barycentrics), then the reduction on the points already there
+    bf_nearest_launch(dim3((n + 3) / 4, 1), st, d_s, d_p, n, d_f, d_c, (float *)nullptr, 0);
+    if (loss || dpoints) {
+        BF_TRY(c.scratch(nblk, d_part));
+        BF_TRY(c.out(loss, 1, d_loss, true));
+        hipLaunchKernelGGL(bf_ml_pc_partial_kernel, dim3(nblk), dim3(256), 0, st, n, d_p, (const float *)d_c, d_part);
+        bf_ml_finish_launch(c, d_part, nblk, 1, 1.f, d_loss);
+    }
+    if (dpoints) {
+        BF_TRY(c.out(dpoints, N * 3, d_dp));
+        hipLaunchKernelGGL(bf_ml_pc_grad_kernel, dim3(nblk), dim3(256), 0, st, n, d_p, (const float *)d_c, (const float *)d_loss, d_dp);
+    }
+    return c.finish();
+}
+
+// closest_face_norms[n][3] (the host entry: rows gathered by the caller), or face_ids[n] into face_norm_table[n_faces][3] on the device
+// (the device entry: gathered in the kernel).  (loss or dpoint_norms is wanted)
+int bf_ml_normal_loss(BfRouteCall &c, int device, int n, const float *closest_face_norms, const int32_t *face_ids, const float *face_norm_table,
+                      int n_faces, const float *point_norms, float *loss, float *dpoint_norms) {
+    BF_TRY(c.begin(device));
+    const size_t N = (size_t)n;
+    const unsigned nblk = blocks(n);
+    const float *d_fn = nullptr, *d_pn = nullptr;
+    float *d_part = nullptr, *d_loss = nullptr, *d_dpn = nullptr;
+    BF_TRY(c.in(closest_face_norms, N * 3, d_fn));
+    BF_TRY(c.in(point_norms, N * 3, d_pn));
+    BF_TRY(c.scratch(nblk, d_part));
+    BF_TRY(c.out(loss, 1, d_loss, true));
+    BF_TRY(c.out(dpoint_norms, N * 3, d_dpn));
+    if (face_ids)
+        hipLaunchKernelGGL(bf_ml_normal_gather_partial_kernel, dim3(nblk), dim3(256), 0, c.stream, n, (const int *)face_ids, face_norm_table,
+                           n_faces, d_pn, d_part, d_dpn);
+    else
+        hipLaunchKernelGGL(bf_ml_normal_partial_kernel, dim3(nblk), dim3(256), 0, c.stream, n, d_fn, d_pn, d_part, d_dpn);
+    bf_ml_finish_launch(c, d_part, nblk, 0, (float)n, d_loss);
+    return c.finish();
+}
+
+// what every *_dev call here checks first: -> BF_OK, or the refusal (nothing has been queued)
+int bf_ml_dev_check(const char *who, const bf_workspace *ws, int device) {
+    if (!ws) return fail(BF_ERR_INVALID, std::string(who) + ": the workspace is NULL");
+    if (ws->device != device) return fail(BF_ERR_INVALID, std::string(who) + ": the workspace lives on another device");
+    return BF_OK;
+}
 }  // namespace
+
+// ----------------------------------------------------------------------------------------------------------------------------------
+// The entry points: the arguments checked (a refused call has queued nothing), the route counted, the body run on that route's call
+// ----------------------------------------------------------------------------------------------------------------------------------
+extern "C" int bf_vertex_normals(const bf_topo *t, const float *verts, float *normals) {
+    if (!t || !verts || !normals) return fail(BF_ERR_INVALID, "bf_vertex_normals: bad argument");
+    ++bf_route_stats().host;
+    BfRouteCall c(nullptr, nullptr);
+    return bf_ml_normals(c, t, verts, normals);
+}
 
 extern "C" int bf_vertex_normals_dev(const bf_topo *t, const float *verts, float *normals, bf_workspace *ws, void *stream) {
     const char *who = "bf_vertex_normals_dev";
     if (!t || !verts || !normals) return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");
     BF_TRY(bf_ml_dev_check(who, ws, t->device));
     ++bf_route_stats().dev;
-    BfDeviceGuard keep;
-    HIP_TRY(hipSetDevice(t->device));
-    const hipStream_t st = (hipStream_t)stream;
-    BfWsCall call(ws, st);
-    BF_TRY(call.begin());
-    float *d_fn = nullptr;
-    BF_TRY(bf_ml_take(ws, (size_t)t->nf * 4, &d_fn));
-    return bf_ml_normals_launch(t, verts, d_fn, nullptr, normals, st);
+    BfRouteCall c(ws, (hipStream_t)stream);
+    return bf_ml_normals(c, t, verts, normals);
+}
+
+extern "C" int bf_vertex_normals_vjp(const bf_topo *t, const float *verts, const float *dnormals, float *dverts) {
+    if (!t || !verts || !dnormals || !dverts) return fail(BF_ERR_INVALID, "bf_vertex_normals_vjp: bad argument");
+    ++bf_route_stats().host;
+    BfRouteCall c(nullptr, nullptr);
+    return bf_ml_normals_vjp(c, t, verts, dnormals, dverts);
 }
 
 extern "C" int bf_vertex_normals_vjp_dev(const bf_topo *t, const float *verts, const float *dnormals, float *dverts, bf_workspace *ws,
@@ -244,23 +236,16 @@ extern "C" int bf_vertex_normals_vjp_dev(const bf_topo *t, const float *verts, c
     if (!t || !verts || !dnormals || !dverts) return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");
     BF_TRY(bf_ml_dev_check(who, ws, t->device));
     ++bf_route_stats().dev;
-    BfDeviceGuard keep;
-    HIP_TRY(hipSetDevice(t->device));
-    const hipStream_t st = (hipStream_t)stream;
-    const size_t nv = (size_t)t->nv, nf = (size_t)t->nf;
-    BfWsCall call(ws, st);
-    BF_TRY(call.begin());
-    float *d_fn = nullptr, *d_vn = nullptr, *d_raw = nullptr, *d_dPf = nullptr;
-    BF_TRY(bf_ml_take(ws, nf * 4, &d_fn)); BF_TRY(bf_ml_take(ws, nv * 4, &d_vn));
-    BF_TRY(bf_ml_take(ws, nv * 3, &d_raw)); BF_TRY(bf_ml_take(ws, nf * 9, &d_dPf));
-    BF_TRY(bf_ml_normals_launch(t, verts, d_fn, d_vn, nullptr, st));
-    hipLaunchKernelGGL(bf_ml_vraw_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, t->nv, (const float *)d_vn, dnormals, d_raw);
-    hipLaunchKernelGGL(bf_ml_fgrad_kernel, dim3(blocks(t->nf)), dim3(256), 0, st, (const int *)t->faces.p, t->nf, verts, (const float *)d_fn,
-                       (const float *)d_raw, d_dPf);
-    hipLaunchKernelGGL(bf_ml_gather_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->adj_start.p, (const int *)t->adj.p, t->nv,
-                       (const float *)d_dPf, dverts);
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
+    BfRouteCall c(ws, (hipStream_t)stream);
+    return bf_ml_normals_vjp(c, t, verts, dnormals, dverts);
+}
+
+extern "C" int bf_normal_laplacian(const bf_topo *t, const float *norms, float *loss, float *dnorms) {
+    if (!t || !norms) return fail(BF_ERR_INVALID, "bf_normal_laplacian: bad argument");
+    ++bf_route_stats().host;
+    if (!loss && !dnorms) return BF_OK;
+    BfRouteCall c(nullptr, nullptr);
+    return bf_ml_laplacian(c, t, norms, loss, dnorms);
 }
 
 extern "C" int bf_normal_laplacian_dev(const bf_topo *t, const float *norms, float *loss, float *dnorms, bf_workspace *ws, void *stream) {
@@ -269,23 +254,17 @@ extern "C" int bf_normal_laplacian_dev(const bf_topo *t, const float *norms, flo
     BF_TRY(bf_ml_dev_check(who, ws, t->device));
     ++bf_route_stats().dev;
     if (!loss && !dnorms) return BF_OK;
-    BfDeviceGuard keep;
-    HIP_TRY(hipSetDevice(t->device));
-    const hipStream_t st = (hipStream_t)stream;
-    const unsigned nblk = blocks(t->nf);
-    BfWsCall call(ws, st);
-    BF_TRY(call.begin());
-    if (loss) {
-        float *d_part = nullptr;
-        BF_TRY(bf_ml_take(ws, nblk, &d_part));
-        hipLaunchKernelGGL(bf_ml_lap_partial_kernel, dim3(nblk), dim3(256), 0, st, (const int *)t->faces.p, t->nf, norms, d_part);
-        hipLaunchKernelGGL(bf_ml_finish_kernel, dim3(1), dim3(256), 0, st, (const float *)d_part, (int)nblk, 0, (float)t->nf, loss);
-    }
-    if (dnorms)
-        hipLaunchKernelGGL(bf_ml_lap_grad_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->faces.p, (const int *)t->adj_start.p,
-                           (const int *)t->adj.p, t->nf, t->nv, norms, dnorms);
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
+    BfRouteCall c(ws, (hipStream_t)stream);
+    return bf_ml_laplacian(c, t, norms, loss, dnorms);
+}
+
+extern "C" int bf_scan_point_loss(bf_scan *s, int n, const float *points, float *loss, int32_t *face_ids, float *nearest, float *dpoints) {
+    const char *who = "bf_scan_point_loss";
+    if (!s || !points) return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");
+    BF_TRY(bf_ml_check_count(who, "points", n));
+    ++bf_route_stats().host;
+    BfRouteCall c(nullptr, nullptr);
+    return bf_ml_point_loss(c, s, n, points, loss, face_ids, nearest, dpoints);
 }
 
 extern "C" int bf_scan_point_loss_dev(bf_scan *s, int n, const float *points, float *loss, int32_t *face_ids, float *nearest, float *dpoints,
@@ -295,32 +274,11 @@ extern "C" int bf_scan_point_loss_dev(bf_scan *s, int n, const float *points, fl
     BF_TRY(bf_ml_dev_check(who, ws, s->device));
     BF_TRY(bf_ml_check_count(who, "points", n));
     ++bf_route_stats().dev;
-    BfDeviceGuard keep;
-    HIP_TRY(hipSetDevice(s->device));
-    const hipStream_t st = (hipStream_t)stream;
-    const size_t N = (size_t)n;
-    const unsigned nblk = blocks(n);
-    const ScanDev *d_s = nullptr;
-    BF_TRY(bf_scan_resident(s, &d_s));
-    BfWsCall call(ws, st);
-    BF_TRY(call.begin());
-    int *d_f = (int *)face_ids;
-    float *d_c = nearest, *d_loss = loss, *d_part = nullptr;
-    if (!d_f) BF_TRY(bf_ml_take(ws, N, &d_f));
-    if (!d_c) BF_TRY(bf_ml_take(ws, N * 3, &d_c));
-    bf_nearest_launch(dim3((n + 3) / 4, 1), st, d_s, points, n, d_f, d_c, (float *)nullptr, 0);
-    if (loss || dpoints) {
-        BF_TRY(bf_ml_take(ws, nblk, &d_part));
-        if (!d_loss) BF_TRY(bf_ml_take(ws, 1, &d_loss));
-        hipLaunchKernelGGL(bf_ml_pc_partial_kernel, dim3(nblk), dim3(256), 0, st, n, points, (const float *)d_c, d_part);
-        hipLaunchKernelGGL(bf_ml_finish_kernel, dim3(1), dim3(256), 0, st, (const float *)d_part, (int)nblk, 1, 1.f, d_loss);
-    }
-    if (dpoints)
-        hipLaunchKernelGGL(bf_ml_pc_grad_kernel, dim3(nblk), dim3(256), 0, st, n, points, (const float *)d_c, (const float *)d_loss, dpoints);
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
+    BfRouteCall c(ws, (hipStream_t)stream);
+    return bf_ml_point_loss(c, s, n, points, loss, face_ids, nearest, dpoints);
 }
 
+// (bf_scan_nearest, scan_api.hip, allocates with hipMalloc and keeps its own body: this is its launch on the device route)
 extern "C" int bf_scan_nearest_dev(bf_scan *s, int n, const float *points, int32_t *face_ids, float *nearest, float *bary, bf_workspace *ws,
                                    void *stream) {
     const char *who = "bf_scan_nearest_dev";
@@ -328,23 +286,29 @@ extern "C" int bf_scan_nearest_dev(bf_scan *s, int n, const float *points, int32
     BF_TRY(bf_ml_dev_check(who, ws, s->device));
     BF_TRY(bf_ml_check_count(who, "points", n));
     ++bf_route_stats().dev;
-    BfDeviceGuard keep;
-    HIP_TRY(hipSetDevice(s->device));
-    const hipStream_t st = (hipStream_t)stream;
+    BfRouteCall c(ws, (hipStream_t)stream);
+    BF_TRY(c.begin(s->device));
     const size_t N = (size_t)n;
     const ScanDev *d_s = nullptr;
-    BF_TRY(bf_scan_resident(s, &d_s));
-    BfWsCall call(ws, st);
-    BF_TRY(call.begin());
+    int *d_f = nullptr;
+    float *d_c = nullptr, *d_b = nullptr;
     // (the twin's launch writes all three: an output not wanted lands in the workspace)
-    int *d_f = (int *)face_ids;
-    float *d_c = nearest, *d_b = bary;
-    if (!d_f) BF_TRY(bf_ml_take(ws, N, &d_f));
-    if (!d_c) BF_TRY(bf_ml_take(ws, N * 3, &d_c));
-    if (!d_b) BF_TRY(bf_ml_take(ws, N * 3, &d_b));
-    bf_nearest_launch(dim3((n + 3) / 4, 1), st, d_s, points, n, d_f, d_c, d_b, 0);
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
+    BF_TRY(c.out((int *)face_ids, N, d_f, true));
+    BF_TRY(c.out(nearest, N * 3, d_c, true));
+    BF_TRY(c.out(bary, N * 3, d_b, true));
+    BF_TRY(bf_ml_scan_dev(c, s, d_s));
+    bf_nearest_launch(dim3((n + 3) / 4, 1), c.stream, d_s, points, n, d_f, d_c, d_b, 0);
+    return c.finish();
+}
+
+extern "C" int bf_normal_loss(int device, int n, const float *closest_face_norms, const float *point_norms, float *loss, float *dpoint_norms) {
+    const char *who = "bf_normal_loss";
+    if (!closest_face_norms || !point_norms) return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");
+    BF_TRY(bf_ml_check_count(who, "points", n));
+    ++bf_route_stats().host;
+    if (!loss && !dpoint_norms) return BF_OK;
+    BfRouteCall c(nullptr, nullptr);
+    return bf_ml_normal_loss(c, device, n, closest_face_norms, nullptr, nullptr, 0, point_norms, loss, dpoint_norms);
 }
 
 extern "C" int bf_normal_loss_dev(int device, int n, const int32_t *face_ids, const float *face_norm_table, int n_faces,
@@ -356,23 +320,12 @@ extern "C" int bf_normal_loss_dev(int device, int n, const int32_t *face_ids, co
     BF_TRY(bf_ml_check_count(who, "n_faces", n_faces));
     ++bf_route_stats().dev;
     if (!loss && !dpoint_norms) return BF_OK;
-    BfDeviceGuard keep;
-    HIP_TRY(hipSetDevice(device));
-    const hipStream_t st = (hipStream_t)stream;
-    const unsigned nblk = blocks(n);
-    BfWsCall call(ws, st);
-    BF_TRY(call.begin());
-    float *d_part = nullptr, *d_loss = loss;
-    BF_TRY(bf_ml_take(ws, nblk, &d_part));
-    if (!d_loss) BF_TRY(bf_ml_take(ws, 1, &d_loss));
-    hipLaunchKernelGGL(bf_ml_normal_gather_partial_kernel, dim3(nblk), dim3(256), 0, st, n, (const int *)face_ids, face_norm_table, n_faces,
-                       point_norms, d_part, dpoint_norms);
-    hipLaunchKernelGGL(bf_ml_finish_kernel, dim3(1), dim3(256), 0, st, (const float *)d_part, (int)nblk, 0, (float)n, d_loss);
-    HIP_TRY(hipGetLastError());
-    return BF_OK;
+    BfRouteCall c(ws, (hipStream_t)stream);
+    return bf_ml_normal_loss(c, device, n, nullptr, face_ids, face_norm_table, n_faces, point_norms, loss, dpoint_norms);
 }
 
-// the backward of a scalar loss on the device route: out[n] = grad[n] * cotangent[0] (+ 0.0f), the cotangent read on the device
+// the backward of a scalar loss on the device route: out[n] = grad[n] * cotangent[0] (+ 0.0f), the cotangent read on the device.
+// No buffer and no workspace: one launch on the caller's stream.
 extern "C" int bf_scale_gradient_dev(int device, int n, const float *grad, const float *cotangent, int plus_zero, float *out, void *stream) {
     const char *who = "bf_scale_gradient_dev";
     if (!grad || !cotangent || !out) return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");

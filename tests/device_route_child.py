@@ -275,6 +275,118 @@ def keypoint_loss(out_path):
     _run(out_path, body)
 
 
+GUARD = 64                                 # elements behind every output tensor of optional_outputs
+GUARD_BITS = 0x7FC0BEEF                    # ... each this quiet NaN
+
+
+def _guarded(count):
+    """an output of `count` 4-byte elements with GUARD more behind it -> (the whole tensor, the address to hand out)"""
+    t = torch.full((count + GUARD,), GUARD_BITS, device=GPU, dtype=torch.int32)
+    return t, t.data_ptr()
+
+
+def _guard_kept(t, count, what):
+    assert bool((t[count:] == GUARD_BITS).all()), f"{what}: the floats behind the output were written"
+
+
+def _guarded_is(t, want, what):
+    """the first want.size elements of a _guarded tensor hold `want`'s bits and the guard behind them is whole"""
+    assert t[:want.size].cpu().numpy().tobytes() == np.ascontiguousarray(want).tobytes(), f"{what}: differs from the host route"
+    _guard_kept(t, want.size, what)
+
+
+def _two_calls(call, what):
+    """call() twice -> what the second returned: the second may not allocate, neither may switch streams or take the host route"""
+    from bodyfitting_amd import native as N
+    start = N.dev_route_stats()
+    call()
+    mid = N.dev_route_stats()
+    out = call()
+    end = N.dev_route_stats()
+    assert end["allocations"] == mid["allocations"], (what, mid, end)
+    assert end["stream_switches"] == start["stream_switches"] and end["host_calls"] == start["host_calls"], (what, start, end)
+    assert end["dev_calls"] == start["dev_calls"] + 2, (what, start, end)
+    return out
+
+
+def optional_outputs(out_path):
+    """the NULL / non-NULL choices of the outputs through the *_dev entries: bf_keypoint_loss_dev (n = 1, two views, one row: the 16
+    subsets of terms, djoints, dposes, dbetas), bf_smpl_vjp_dev on the 690-vertex model and bf_smplx_vjp_dev with expression on the
+    1200-vertex one at n = 1 and 3 (dbetas only, dglobal_orient only, one hand only, dexpression only).  Every output asked for holds
+    the bits of the host route's all-outputs call and nothing is written behind it"""
+    def body():
+        _repo()
+        import keypoint_loss_cases as KC
+        from bodyfitting_amd import native as N, synthetic as S
+        _took("device")
+        stream = torch.cuda.current_stream().cuda_stream
+        make_gmm = S.make_gmm(seed=0)
+        # the keypoint loss
+        gmm = N.Gmm(*S.gmm_buffers(make_gmm), device=0)
+        sc = KC.scene(1, 2, 31)
+        rng = np.random.default_rng(32)
+        poses, betas = rng.normal(0, 0.2, (1, 69)).astype(np.float32), rng.normal(0, 0.6, (1, 10)).astype(np.float32)
+        divisor = np.array([2], np.int32)
+        host = N.keypoint_loss(sc["joints"], w2c=sc["w2c"][None], K=sc["K"][None], keypoints=sc["kp"][None], divisor=divisor, poses=poses,
+                               betas=betas, gmm=gmm)
+        assert all(np.isfinite(host[k]).all() for k in N.KP_LOSS_OUTPUTS) and host["djoints"].any()
+        t = {k: _gpu(a, False) for k, a in (("joints", sc["joints"]), ("w2c", sc["w2c"]), ("K", sc["K"]), ("kp", sc["kp"]), ("poses", poses),
+                                            ("betas", betas))}
+        for mask in range(16):
+            names = [k for i, k in enumerate(N.KP_LOSS_OUTPUTS) if (mask >> i) & 1]
+
+            def call():
+                out = {k: _guarded(host[k].size) for k in names}
+                N.keypoint_loss_dev(stream, 1, rows=1, joints=t["joints"].data_ptr(), n_views=2, w2c=t["w2c"].data_ptr(), K=t["K"].data_ptr(),
+                                    keypoints=t["kp"].data_ptr(), divisor=divisor, pose_dim=69, poses=t["poses"].data_ptr(), n_betas=10,
+                                    betas=t["betas"].data_ptr(), gmm=gmm, **{k: a for k, (_, a) in out.items()})
+                return out
+            for k, (got, _) in _two_calls(call, f"keypoint loss {names}").items():
+                _guarded_is(got, host[k], f"keypoint loss {names} {k}")
+        torch.cuda.synchronize()
+        gmm.close()
+        # the SMPL reverse
+        dev = N.DeviceModel(S.make_model("smpl", seed=0, nv=690), make_gmm, device=0)
+        for n in (1, 3):
+            x = _smpl_params(n, dev.n_betas, 130 + n)
+            shapes = ((n, dev.n_verts, 3), (n, dev.n_joint_map, 3), (n, dev.n_joints + dev.n_selector, 3))
+            cot = [_cot(s, 130 + n + i) for i, s in enumerate(shapes)]
+            host = dev.vjp(*x, *cot)
+            x_t, cot_t = [_gpu(a, False) for a in x], [_gpu(a, False) for a in cot]
+            for name, i in (("dbetas", 0), ("dglobal_orient", 1)):
+                def call():
+                    out = _guarded(host[i].size)
+                    dev.vjp_dev(n, stream, *[a.data_ptr() for a in x_t], *[a.data_ptr() for a in cot_t], **{name: out[1]})
+                    return out[0]
+                _guarded_is(_two_calls(call, f"smpl n={n} {name} only"), host[i], f"smpl n={n} {name} only")
+        torch.cuda.synchronize()
+        dev.close()
+        # the SMPL-X reverse with expression coefficients
+        dev = N.DeviceModel(S.make_model("smplx", seed=0, nv=1200), make_gmm, device=0)
+        assert dev.n_expression == 10
+        for n in (1, 3):
+            p = _smplx_params(n, 140 + n)
+            shapes = ((n, dev.n_verts, 3), (n, dev.n_joint_map, 3), (n, dev.n_joints_all, 3), (n, 3 * dev.n_joints))
+            cot = [_cot(s, 140 + n + i) for i, s in enumerate(shapes)]
+            host = dev.vjp_smplx(*[p[k] for k in XINPUTS], *cot, expression=p["expression"])
+            assert len(host) == 9 and host[6].any() and host[8].any()
+            p_t, cot_t = {k: _gpu(a, False) for k, a in p.items()}, [_gpu(a, False) for a in cot]
+            for name, i in (("dbetas", 0), ("dglobal_orient", 1), ("dleft_hand_pose", 6), ("dexpression", 8)):
+                def call():
+                    out = _guarded(host[i].size)
+                    grads = [out[1] if j == i else 0 for j in range(8)]
+                    dev.vjp_smplx_dev(n, stream, [p_t[k].data_ptr() for k in XINPUTS], expression=p_t["expression"].data_ptr(),
+                                      dverts=cot_t[0].data_ptr(), djoints=cot_t[1].data_ptr(), djoints_all=cot_t[2].data_ptr(),
+                                      dfull_pose=cot_t[3].data_ptr(), grads=grads, dexpression=out[1] if i == 8 else 0)
+                    return out[0]
+                _guarded_is(_two_calls(call, f"smplx n={n} {name} only"), host[i], f"smplx n={n} {name} only")
+        torch.cuda.synchronize()
+        dev.close()
+        return {"ok": np.ones(1)}
+
+    _run(out_path, body)
+
+
 def _keypoint_stage(drop, prior, L, sc, keypoints, params, steps, after_step=None):
     """the reference's loop (smplify.py:177-213) on cuda:0: model, loss, backward, Adam"""
     w2c, K = torch.tensor(np.asarray(sc["w2c"], np.float32)), np.asarray(sc["K"], np.float32)

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch                    # (first: see above)
 
-from device_route_child import GPU, _busy, _repo, _took
+from device_route_child import GPU, _busy, _guard_kept, _guarded, _repo, _took, _two_calls
 from lanes_child import _run
 
 COTANGENTS = (1.0, 2.5, -1.5)          # 1, one that is not 1, a negative one
@@ -267,6 +267,65 @@ def gather_alone(out_path):
                     _same(out, want, f"scale n={n} c={c} plus_zero={plus_zero}")
         torch.cuda.synchronize()
         ws.close()
+        return {"ok": np.ones(1)}
+
+    _run(out_path, body)
+
+
+def optional_outputs(out_path):
+    """the NULL / non-NULL choices of the outputs through the *_dev entries: bf_scan_point_loss_dev at 1, 5 and 257 points (all 16),
+    bf_normal_laplacian_dev on the 257-vertex fan and bf_normal_loss_dev at 257 points (loss only, gradient only, both, neither).
+    Every output asked for holds the bits of the host route's all-outputs call and nothing is written behind it"""
+    def body():
+        _repo()
+        import scan_loss_cases as SC
+        from bodyfitting_amd import native as N
+        _took("device")
+        searcher, fn = _searcher()
+        scan, stream = searcher._scan, torch.cuda.current_stream().cuda_stream
+        for n in (1, 5, 257):
+            pts = SC.points(n)
+            value, ids, near, dp = scan.point_loss(pts)
+            want = {"loss": np.asarray(value).reshape(1), "face_ids": ids, "nearest": near, "dpoints": dp}
+            pts_t = _gpu(pts)
+            for mask in range(16):
+                names = [k for i, k in enumerate(want) if (mask >> i) & 1]
+
+                def call():
+                    out = {k: _guarded(want[k].size) for k in names}
+                    scan.point_loss_dev(n, stream, pts_t.data_ptr(), **{k: a for k, (_, a) in out.items()})
+                    return out
+                for k, (t, _) in _two_calls(call, f"point loss n={n} {names}").items():
+                    got = t[:want[k].size].cpu().numpy()
+                    assert got.tobytes() == np.ascontiguousarray(want[k]).tobytes(), f"point loss n={n} {names}: {k} differs from the host route"
+                    _guard_kept(t, want[k].size, f"point loss n={n} {names} {k}")
+        verts, faces = SC.fan(255, 2257, lonely=True)
+        topo = N.Topology(len(verts), faces)
+        norms = SC.cotangent("fan257 optional", verts.shape)
+        pts, pn = SC.points(257), SC.cotangent("pn optional", (257, 3))
+        ids = scan.point_loss(pts)[1]
+        host = {"laplacian": N.normal_laplacian(topo, norms), "normal loss": N.normal_loss(fn[ids], pn)}
+        norms_t, pn_t, ids_t, fn_t = _gpu(norms), _gpu(pn), _gpu(ids), _gpu(fn)
+        ws = N.Workspace(0)
+        entries = {"laplacian": lambda loss, grad: N.normal_laplacian_dev(topo, stream, norms_t.data_ptr(), loss=loss, dnorms=grad),
+                   "normal loss": lambda loss, grad: N.normal_loss_dev(ws, stream, 257, ids_t.data_ptr(), fn_t.data_ptr(), len(fn), pn_t.data_ptr(),
+                                                                       loss=loss, dpoint_norms=grad)}
+        for name, entry in entries.items():
+            for want_loss, want_grad in ((True, False), (False, True), (True, True), (False, False)):
+                def call():
+                    loss, grad = _guarded(1) if want_loss else (None, 0), _guarded(257 * 3) if want_grad else (None, 0)
+                    entry(loss[1], grad[1])
+                    return loss[0], grad[0]
+                what = f"{name} loss={want_loss} gradient={want_grad}"
+                loss, grad = _two_calls(call, what)
+                for t, w, on in ((loss, np.asarray(host[name][0]).reshape(1), want_loss), (grad, host[name][1], want_grad)):
+                    if on:
+                        assert t[:w.size].cpu().numpy().tobytes() == np.ascontiguousarray(w).tobytes(), f"{what}: differs from the host route"
+                        _guard_kept(t, w.size, what)
+        torch.cuda.synchronize()
+        ws.close()
+        topo.close()
+        searcher.close()
         return {"ok": np.ones(1)}
 
     _run(out_path, body)

@@ -47,6 +47,13 @@ def test_keypoint_loss_and_prior_give_the_cpu_tensor_calls_bits(tmp_path):
     _child(tmp_path, "keypoint_loss")
 
 
+def test_optional_outputs_of_the_dev_entries(tmp_path):
+    """bf_keypoint_loss_dev with the 16 subsets of its outputs (n = 1, two views, one row), bf_smpl_vjp_dev and bf_smplx_vjp_dev with
+    expression at n = 1 and 3 with one gradient asked for (dbetas, dglobal_orient, one hand, dexpression): the host route's
+    all-outputs bits, 64 floats behind every output untouched, no allocation on a second identical call, no stream switch"""
+    _child(tmp_path, "optional_outputs")
+
+
 def test_a_keypoint_stage_loop_stays_on_the_device(tmp_path):
     """ten Adam steps with everything on cuda:0: only *_dev calls (four per step: the loss is entered for its terms and again for
     its gradient), no allocation after the first step, no stream switch"""

@@ -311,6 +311,24 @@ def test_null_outputs_in_every_combination_and_determinism(gmm_dev, seventeen):
     assert not got["terms"][:, 3].any()
 
 
+def test_optional_outputs_of_one_problem_with_two_views_and_one_row(gmm_dev):
+    """n = 1, two views, one joint row (the fewest of test_row_counts): the 16 subsets of (terms, djoints, dposes, dbetas).  Every
+    output asked for holds the bits of the all-outputs call; the empty subset succeeds and counts once on the host route"""
+    p = _problem(_case("smpl", 2, 2, "views"))            # (test_view_counts' two-view problem)
+    p["joints"], p["kp"] = p["joints"][:1], p["kp"][:, :1]
+    inp = _inp([p])
+    full = _run(inp, gmm_dev)
+    assert all(np.isfinite(full[k]).all() for k in N.KP_LOSS_OUTPUTS) and full["djoints"].any()
+    for mask in range(16):
+        want = tuple(k for i, k in enumerate(N.KP_LOSS_OUTPUTS) if (mask >> i) & 1)
+        before = N.dev_route_stats()["host_calls"]
+        got = _run(inp, gmm_dev, want=want)
+        assert N.dev_route_stats()["host_calls"] == before + 1, want
+        assert set(got) == set(want)
+        for k in want:
+            assert got[k].tobytes() == full[k].tobytes(), (want, k)
+
+
 def test_limits_return_their_error_codes(gmm_dev, seventeen):
     p = seventeen[0]
     V = len(p["w2c"])

@@ -49,6 +49,13 @@ def test_the_gather_kernel_and_the_scaling_kernel_alone(tmp_path):
     _child(tmp_path, "gather_alone")
 
 
+def test_optional_outputs_of_the_dev_entries(tmp_path):
+    """bf_scan_point_loss_dev at 1, 5 and 257 points with all 16 NULL / non-NULL choices of its outputs, bf_normal_laplacian_dev on
+    the 257-vertex fan and bf_normal_loss_dev at 257 points with loss only, gradient only, both and neither: the host route's
+    all-outputs bits, 64 floats behind every output untouched, no allocation on a second identical call, no stream switch"""
+    _child(tmp_path, "optional_outputs")
+
+
 def test_nearest_points_on_gpu_tensors(tmp_path):
     """points, ids (int32) and coefficients: the numpy call's bits, on the tensors' device"""
     _child(tmp_path, "nearest_tensors")

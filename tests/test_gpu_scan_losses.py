@@ -175,6 +175,69 @@ def test_limits_and_their_error_codes(searcher):
     topo.close()
 
 
+def _host_calls():
+    return N.dev_route_stats()["host_calls"]
+
+
+@pytest.mark.parametrize("n", [1, 5, 257])
+def test_scan_point_loss_optional_outputs_in_every_combination(searcher, n):
+    """bf_scan_point_loss at the C ABI: all 16 NULL / non-NULL choices of (loss, face_ids, nearest, dpoints).  Every output asked for
+    holds the bits of the all-outputs call; every call counts once on the host route"""
+    lib, scan, pts = _lib.load(), searcher._scan, SC.points(n)
+    names = ("loss", "face_ids", "nearest", "dpoints")
+
+    def call(mask):
+        out = {"loss": np.full(1, np.nan, np.float32), "face_ids": np.full(n, -7, np.int32), "nearest": np.full((n, 3), np.nan, np.float32),
+               "dpoints": np.full((n, 3), np.nan, np.float32)}
+        out = {k: v for i, (k, v) in enumerate(out.items()) if (mask >> i) & 1}
+        before = _host_calls()
+        rc = lib.bf_scan_point_loss(scan._h, n, _lib.fptr(pts), _lib.fptr(out.get("loss")), _lib.iptr(out.get("face_ids")),
+                                    _lib.fptr(out.get("nearest")), _lib.fptr(out.get("dpoints")))
+        assert rc == 0 and _host_calls() == before + 1, (mask, rc)
+        return out
+
+    full = call(15)
+    assert np.isfinite(full["loss"]).all() and np.isfinite(full["dpoints"]).all() and (full["face_ids"] >= 0).all()
+    for mask in range(16):
+        got = call(mask)
+        assert set(got) == {k for i, k in enumerate(names) if (mask >> i) & 1}
+        for k, v in got.items():
+            assert v.tobytes() == full[k].tobytes(), (mask, k)
+
+
+def test_normal_laplacian_and_normal_loss_optional_outputs(searcher):
+    """bf_normal_laplacian on the 257-vertex fan and bf_normal_loss at 257 points, at the C ABI: loss only, gradient only, both and
+    neither.  What is asked for holds the bits of the call for both; neither returns BF_OK and counts once on the host route"""
+    lib = _lib.load()
+    verts, faces = SC.fan(255, 2257, lonely=True)
+    assert len(verts) == 257
+    topo = N.Topology(len(verts), faces)
+    norms = SC.cotangent("fan257 optional", verts.shape)
+    pts, pn = SC.points(257), SC.cotangent("pn optional", (257, 3))
+    fn = np.ascontiguousarray(SC.scan()[3][searcher.nearest_points(pts)[1]])
+
+    def laplacian(loss, grad):
+        return lib.bf_normal_laplacian(topo._h, _lib.fptr(norms), _lib.fptr(loss), _lib.fptr(grad))
+
+    def normal(loss, grad):
+        return lib.bf_normal_loss(0, 257, _lib.fptr(fn), _lib.fptr(pn), _lib.fptr(loss), _lib.fptr(grad))
+
+    for name, call in (("laplacian", laplacian), ("normal loss", normal)):
+        both = np.full(1, np.nan, np.float32), np.full((257, 3), np.nan, np.float32)
+        assert call(*both) == 0 and np.isfinite(both[0]).all() and np.isfinite(both[1]).all(), name
+        for want_loss, want_grad in ((True, False), (False, True), (True, True), (False, False)):
+            loss = np.full(1, np.nan, np.float32) if want_loss else None
+            grad = np.full((257, 3), np.nan, np.float32) if want_grad else None
+            before = _host_calls()
+            assert call(loss, grad) == 0, (name, want_loss, want_grad)
+            assert _host_calls() == before + 1, (name, want_loss, want_grad)
+            if want_loss:
+                assert loss.tobytes() == both[0].tobytes(), (name, want_grad)
+            if want_grad:
+                assert grad.tobytes() == both[1].tobytes(), (name, want_loss)
+    topo.close()
+
+
 def test_the_users_own_smpl_d_loop_on_the_dropins():
     """smplify.py:236-245 with torch.optim.Adam(lr=5e-2) on the drop-in functions, from the base mesh of
     test_gpu_scan.py::test_displacement_stage_first_steps: its first gradient against the float64 oracle's and its first step

@@ -116,6 +116,31 @@ def test_vjp_kid_model_matches_fp64_autograd(kid, n):
     _vjp_against_autograd(dev, model, n, seed=90 + n)
 
 
+@pytest.mark.parametrize("n", [1, 3])
+def test_vjp_optional_gradients_at_the_c_abi(small, n):
+    """bf_smpl_vjp on the 690-vertex model with one gradient asked for and the others NULL: dbetas only, dglobal_orient only,
+    dbody_pose only.  The one asked for holds the bits of the all-gradients call; none asked for succeeds and counts once"""
+    _, dev = small
+    betas, orient, pose = _params(n, dev.n_betas, 130 + n)
+    cot = _cotangents(n, dev, 130 + n)
+    full = dev.vjp(betas, orient, pose, cot["vertices"], cot["joints"], cot["joints_ori"])
+    assert all(np.isfinite(g).all() and g.any() for g in full)
+
+    def call(which):
+        out = [np.full_like(g, np.nan) if i in which else None for i, g in enumerate(full)]
+        before = N.dev_route_stats()["host_calls"]
+        rc = dev._lib.bf_smpl_vjp(dev._h, n, _lib.fptr(betas), _lib.fptr(orient), _lib.fptr(pose), _lib.fptr(cot["vertices"]),
+                                  _lib.fptr(cot["joints"]), _lib.fptr(cot["joints_ori"]), *[_lib.fptr(o) for o in out])
+        assert rc == 0 and N.dev_route_stats()["host_calls"] == before + 1, which
+        return out
+
+    for which in ((0,), (1,), (2,), ()):
+        for i, got in enumerate(call(which)):
+            assert (got is None) == (i not in which)
+            if got is not None:
+                assert got.tobytes() == full[i].tobytes(), (which, i)
+
+
 def test_vjp_is_deterministic_and_refuses_smplx(dev_model):
     n = 9
     betas, orient, pose = _params(n, 10, 7)

@@ -279,6 +279,32 @@ def test_vjp_is_deterministic_and_dexpression_is_optional(full):
         assert x.tobytes() == y.tobytes()
 
 
+@pytest.mark.parametrize("n", [1, 3])
+def test_vjp_optional_gradients_at_the_c_abi(small, n):
+    """bf_smplx_vjp_expr on this file's small model with one gradient asked for and every other NULL: dbetas only, dglobal_orient
+    only, the left hand only, dexpression only.  The one asked for holds the bits of the all-gradients call; none asked for succeeds"""
+    _, dev = small
+    p = _params(n, 140 + n)
+    cot = _cotangents(n, dev, 140 + n)
+    full = dev.vjp_smplx(**p, **{COT_ARG[k]: cot[k] for k in COT_ARG})
+    assert len(full) == 9 and all(np.isfinite(g).all() for g in full) and full[6].any() and full[8].any()
+    par = _lib.SmplxParams(*[_lib.fptr(p[k]) for k in INPUTS[:8]])
+    cots = _lib.SmplxCotangents(*[_lib.fptr(cot[k]) for k in ("vertices", "joints", "joints_all", "full_pose")])
+
+    def call(which):
+        out = [np.full_like(g, np.nan) if i in which else None for i, g in enumerate(full)]
+        dst = _lib.SmplxGrads(*[_lib.fptr(o) for o in out[:8]])
+        before = N.dev_route_stats()["host_calls"]
+        rc = dev._lib.bf_smplx_vjp_expr(dev._h, n, C.byref(par), _lib.fptr(p["expression"]), C.byref(cots), C.byref(dst), _lib.fptr(out[8]))
+        assert rc == 0 and N.dev_route_stats()["host_calls"] == before + 1, which
+        return out
+
+    for which in ((0,), (1,), (6,), (8,), ()):
+        for i, got in enumerate(call(which)):
+            if i in which:
+                assert got.tobytes() == full[i].tobytes(), (which, i)
+
+
 def test_refusals_at_the_c_abi_and_in_python(small, dev_model, monkeypatch):
     lib = dev_model._lib
     dirs = np.ascontiguousarray(small[0]["shapedirs"][:, :, 10:], np.float32)
