@@ -162,38 +162,6 @@ int bf_launch_mesh(bf_model *m, const MeshPass &p, MeshPassDone &told) {
 }
 
 extern "C" {
-int bf_smpl_forward(bf_model *m, int n, const float *betas, const float *global_orient, const float *body_pose,
-                    float *vertices, float *joints, float *joints_ori) {
-    if (!m || n <= 0 || !betas || !global_orient || !body_pose) return fail(BF_ERR_INVALID, "bf_smpl_forward: bad argument");
-    ++bf_route_stats().host;
-    HIP_TRY(hipSetDevice(m->device));
-    const int nj = m->nj, nb = m->nb, nv = m->nv;
-    const size_t stride = bf_state_stride(nj, m->npf, nb);
-    DevBuf<float> d_beta, d_or, d_bp, d_state, d_vraw, d_j, d_jo, d_xp;
-    MeshScratch scratch;
-    HIP_TRY(d_beta.upload(std::vector<float>(betas, betas + (size_t)n * nb)));
-    HIP_TRY(d_or.upload(std::vector<float>(global_orient, global_orient + (size_t)n * 3)));
-    HIP_TRY(d_bp.upload(std::vector<float>(body_pose, body_pose + (size_t)n * 3 * (nj - 1))));
-    HIP_TRY(d_state.alloc((size_t)n * stride));
-    HIP_TRY(d_vraw.alloc((size_t)n * nv * 3));
-    HIP_TRY(d_xp.alloc((size_t)n * m->mesh.n_tiles * m->n_extra * 3));
-    HIP_TRY(d_j.alloc((size_t)n * m->n_joint_map * 3));
-    HIP_TRY(d_jo.alloc((size_t)n * (nj + m->n_selector) * 3));
-    hipLaunchKernelGGL(bf_pose_state_kernel, dim3(n), dim3(128), 0, 0, m->fit, (const float *)d_beta.p,
-                       (const float *)d_or.p, (const float *)d_bp.p, (const float *)nullptr, d_state.p,
-                       (const float *)nullptr, (const float *)nullptr, 1.0f);
-    HIP_TRY(hipGetLastError());
-    MeshPass mesh;
-    mesh.scr = &scratch; mesh.n = n; mesh.state = d_state.p;
-    mesh.vraw = d_vraw.p; mesh.xpart = d_xp.p; mesh.joints = d_j.p; mesh.joints_ori = d_jo.p;
-    BF_TRY(bf_launch_mesh(m, mesh));
-    HIP_TRY(hipDeviceSynchronize());
-    if (vertices) HIP_TRY(hipMemcpy(vertices, d_vraw.p, (size_t)n * nv * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (joints) HIP_TRY(hipMemcpy(joints, d_j.p, d_j.n * sizeof(float), hipMemcpyDeviceToHost));
-    if (joints_ori) HIP_TRY(hipMemcpy(joints_ori, d_jo.p, d_jo.n * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
-}
-
 // A small fetch as a kernel: device arena -> pinned host mirror with plain stores over PCIe (posted writes, visible to the
 // host when the stream drains); a copy node costs ~20 us of fixed overhead for the same 90 KB.
 __global__ void __launch_bounds__(256) __attribute__((visibility("hidden"))) bf_publish_kernel(const float4 *__restrict__ src, float4 *__restrict__ dst, size_t n4) {

@@ -135,11 +135,12 @@ struct DevBuf {
         }
         return e;
     }
-    hipError_t upload(const std::vector<T> &h) {
-        hipError_t e = alloc(h.size());
+    hipError_t upload(const T *h, size_t count) {
+        hipError_t e = alloc(count);
         if (e != hipSuccess) return e;
-        return h.empty() ? hipSuccess : hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+        return count == 0 ? hipSuccess : hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice);
     }
+    hipError_t upload(const std::vector<T> &h) { return upload(h.data(), h.size()); }
     void drop() { if (p && !view) { if (pool_dev >= 0) bf_pool_free(p, pool_bytes, pool_dev); else (void)hipFree(p); } }
     void release() { drop(); p = nullptr; n = 0; view = false; pool_dev = -1; }
     ~DevBuf() { drop(); }

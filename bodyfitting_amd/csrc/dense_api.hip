@@ -511,7 +511,7 @@ int bf_dense_iter_eval(bf_batch *b, const bf_hyper &h, const HyperDev &hd, Frame
         sub = late ? sub_late : sub_early;
     }
     DevBuf<float> extra;
-    if (dverts_extra) HIP_TRY(extra.upload(std::vector<float>(dverts_extra, dverts_extra + (size_t)F * m->nv * 3)));
+    if (dverts_extra) HIP_TRY(extra.upload(dverts_extra, (size_t)F * m->nv * 3));
     // the closest-point search warm-starts from the faces of the call before it: this call keeps them as it found them
     DevBuf<int> faces_kept;
     const bool warm = b->cface_valid;

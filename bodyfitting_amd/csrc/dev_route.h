@@ -93,3 +93,10 @@ private:
     std::vector<Back> back;             // ... and the device-to-host copies finish() makes
     MeshScratch own_scratch;            // ... and the mesh pass's scratch, freed behind the destructor's drain
 };
+
+// what the *_dev entry points of mesh_loss_api.hip and scan_api.hip check before anything is queued: -> BF_OK, or the refusal
+int bf_ml_check_count(const char *who, const char *what, int n);                // 0 < n <= 2^28 vertices, faces or points of one call
+int bf_ml_dev_check(const char *who, const bf_workspace *ws, int device);      // a workspace, and one of that device
+// the scan's ScanDev in device memory (scan_api.hip): resident, made once per scan / where the kernels of `c` read it
+int bf_scan_resident(struct bf_scan *s, const ScanDev **out);
+int bf_ml_scan_dev(BfRouteCall &c, struct bf_scan *s, const ScanDev *&d_s);

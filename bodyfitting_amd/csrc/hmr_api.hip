@@ -173,8 +173,8 @@ int bf_hmr_create(int device, const float *weights, int64_t n_weights, const flo
     h->device = device; h->max_batch = max_batch; h->layers = std::move(layers);
     const size_t mb = (size_t)max_batch;
     bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
-              h->w.upload(std::vector<float>(weights, weights + total)) == hipSuccess &&
-              h->mean.upload(std::vector<float>(mean_params, mean_params + HMR_NSTATE)) == hipSuccess &&
+              h->w.upload(weights, total) == hipSuccess &&
+              h->mean.upload(mean_params, HMR_NSTATE) == hipSuccess &&
               h->input.alloc(mb * HMR_RES * HMR_RES * 3) == hipSuccess && h->resized.alloc(mb * HMR_RES * HMR_RES * 3) == hipSuccess &&
               h->xc.alloc(mb * HMR_XC) == hipSuccess && h->h1.alloc(mb * HMR_HIDDEN) == hipSuccess && h->h2.alloc(mb * HMR_HIDDEN) == hipSuccess;
     for (int i = 0; i < 4 && ok; ++i) ok = h->act[i].alloc(mb * HMR_ACT) == hipSuccess;
@@ -229,9 +229,9 @@ int bf_hmr_selftest_conv(int device, int n, int H, int W, int cin, int cout, int
     std::memcpy(packed.data(), w, nw * sizeof(float));
     std::memcpy(packed.data() + nw, bias, cout * sizeof(float));
     DevBuf<float> dx, dw, dr, dy;
-    HIP_TRY(dx.upload(std::vector<float>(x, x + nx)));
+    HIP_TRY(dx.upload(x, nx));
     HIP_TRY(dw.upload(packed));
-    if (res) HIP_TRY(dr.upload(std::vector<float>(res, res + ny)));
+    if (res) HIP_TRY(dr.upload(res, ny));
     HIP_TRY(dy.alloc(ny));
     HmrLayer l{0, nw, cin, cout, k, stride, pad};
     if (int rc = launch_conv(nullptr, dw.p, l, n, H, W, dx.p, res ? dr.p : nullptr, relu, dy.p, cout)) return rc;

@@ -221,7 +221,7 @@ int bf_inpaint_create(int device, const float *weights, int64_t n_weights, int m
     std::memcpy(h->gauss, weights + lay.gauss, sizeof(h->gauss));
     const size_t px = (size_t)max_batch * max_h * max_w;
     bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
-              h->w.upload(std::vector<float>(weights, weights + lay.gauss)) == hipSuccess &&
+              h->w.upload(weights, lay.gauss) == hipSuccess &&
               h->xin.alloc(px * 4) == hipSuccess && h->mk.alloc(px * 4) == hipSuccess && h->rmk.alloc(px * 4) == hipSuccess &&
               h->e7.alloc((px >> 14) * 512) == hipSuccess && h->mq[0].alloc(px * 16) == hipSuccess && h->mq[1].alloc(px * 16) == hipSuccess &&
               h->part.alloc(IP_PART_PER_IMAGE * max_batch) == hipSuccess && h->out.alloc(px * 3) == hipSuccess &&
@@ -328,12 +328,12 @@ int bf_inpaint_selftest_conv(int device, int deconv, int n, int H, int W, int ci
     const int coutp = ip_pad4(cout), K = cin * (deconv ? 4 : 16), phases = deconv ? 4 : 1;
     const size_t nx = (size_t)n * H * W * cin, nw = (size_t)phases * K * coutp, ny = (size_t)n * c.Ho * c.Wo * cout;
     DevBuf<float> dx, dxm, dw, dwm, dy, dym, part;
-    HIP_TRY(dx.upload(std::vector<float>(x, x + nx)));
-    HIP_TRY(dw.upload(std::vector<float>(w, w + nw)));
+    HIP_TRY(dx.upload(x, nx));
+    HIP_TRY(dw.upload(w, nw));
     HIP_TRY(dy.alloc(ny));
     if (xm) {
-        HIP_TRY(dxm.upload(std::vector<float>(xm, xm + nx)));
-        HIP_TRY(dwm.upload(std::vector<float>(wm, wm + nw)));
+        HIP_TRY(dxm.upload(xm, nx));
+        HIP_TRY(dwm.upload(wm, nw));
         HIP_TRY(dym.alloc(ny));
     }
     HIP_TRY(part.alloc(IP_PART_PER_IMAGE * n));

@@ -91,8 +91,8 @@ extern "C" int bf_gmm_create(int device, int n_components, int dim, const float 
     std::unique_ptr<bf_gmm> g(new bf_gmm);
     g->device = device; g->n_comp = n_components; g->dim = dim;
     const size_t M = (size_t)n_components, D = (size_t)dim;
-    HIP_TRY(g->means.upload(std::vector<float>(means, means + M * D)));
-    HIP_TRY(g->prec.upload(std::vector<float>(precisions, precisions + M * D * D)));
+    HIP_TRY(g->means.upload(means, M * D));
+    HIP_TRY(g->prec.upload(precisions, M * D * D));
     HIP_TRY(g->logw.upload(logw));
     *out = g.release();
     return BF_OK;

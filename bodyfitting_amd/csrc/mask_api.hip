@@ -49,7 +49,7 @@ int bf_extract_contours(int device, int n, int H, int W, const uint8_t *masks, i
     if (bf_device_count() <= device || device < 0) return fail(BF_ERR_NO_DEVICE, "bf_extract_contours: no such HIP device");
     HIP_TRY(hipSetDevice(device));
     DevBuf<unsigned char> d_bin;
-    HIP_TRY(d_bin.upload(std::vector<unsigned char>(masks, masks + (size_t)n * H * W)));
+    HIP_TRY(d_bin.upload(masks, (size_t)n * H * W));
     std::vector<int> cnt, half;
     DevBuf<float> d_xy;
     int cap = 0;

@@ -2,7 +2,7 @@
 // twins (include/bodyfit.h): the SMPL+D stage's losses (smplify.py:236-245) as stateless calls, for a user's own torch loop.  Kernels:
 // mesh_loss_kernels.hip.  Every operation is ONE body on a BfRouteCall (dev_route.h) and its two entry points are wrappers that check
 // their arguments, count their route and hand the body its call: host arrays on the NULL stream with the block cache's buffers and one
-// drain (like bf_scan_nearest), or device pointers on the caller's stream with a bf_workspace, where nothing is drained, nothing is
+// drain, or device pointers on the caller's stream with a bf_workspace, where nothing is drained, nothing is
 // copied to the host and a scalar loss is one float in device memory.  Both routes of a call issue the same kernels in the same order
 // with the same grids and arguments.
 #include "bf_host.h"
@@ -20,13 +20,19 @@ namespace {
 constexpr int BF_ML_MAX = 1 << 28;        // vertices, faces or points of one call: face * 4 + corner and index * 3 stay inside an int
 
 inline unsigned blocks(int n) { return (unsigned)((n + 255) / 256); }
+}  // namespace
 
 int bf_ml_check_count(const char *who, const char *what, int n) {
     if (n <= 0) return fail(BF_ERR_INVALID, std::string(who) + ": " + what + " must be positive");
     if (n > BF_ML_MAX) return fail(BF_ERR_UNSUPPORTED, std::string(who) + ": more than " + std::to_string(BF_ML_MAX) + " " + what);
     return BF_OK;
 }
-}  // namespace
+
+int bf_ml_dev_check(const char *who, const bf_workspace *ws, int device) {
+    if (!ws) return fail(BF_ERR_INVALID, std::string(who) + ": the workspace is NULL");
+    if (ws->device != device) return fail(BF_ERR_INVALID, std::string(who) + ": the workspace lives on another device");
+    return BF_OK;
+}
 
 extern "C" int bf_topo_create(int device, int n_verts, int n_faces, const int32_t *faces, bf_topo **out) {
     const char *who = "bf_topo_create";
@@ -126,24 +132,6 @@ int bf_ml_laplacian(BfRouteCall &c, const bf_topo *t, const float *norms, float 
     return c.finish();
 }
 
-// the scan's ScanDev in device memory, made once per scan: complete on the device when this returns (later calls come on any stream)
-int bf_scan_resident(bf_scan *s, const ScanDev **out) {
-    static std::mutex mu;
-    std::lock_guard<std::mutex> g(mu);
-    if (!s->dev_resident.p) {
-        HIP_TRY(s->dev_resident.upload(std::vector<ScanDev>(1, s->dev)));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-    }
-    *out = s->dev_resident.p;
-    return BF_OK;
-}
-
-// the scan's ScanDev where the kernels of `c` read it: the host route uploads it with the call, the device route keeps it resident
-int bf_ml_scan_dev(BfRouteCall &c, bf_scan *s, const ScanDev *&d_s) {
-    if (c.ws) return bf_scan_resident(s, &d_s);
-    return c.in(&s->dev, 1, d_s);
-}
-
 int bf_ml_point_loss(BfRouteCall &c, bf_scan *s, int n, const float *points, float *loss, int32_t *face_ids, float *nearest, float *dpoints) {
     BF_TRY(c.begin(s->device));
     const hipStream_t st = c.stream;
@@ -158,7 +146,7 @@ int bf_ml_point_loss(BfRouteCall &c, bf_scan *s, int n, const float *points, flo
     BF_TRY(c.out((int *)face_ids, N, d_f, true));
     BF_TRY(c.out(nearest, N * 3, d_c, true));
     BF_TRY(bf_ml_scan_dev(c, s, d_s));
-    // the closest-point launch of bf_scan_nearest (no warm start, no barycentrics), then the reduction on the points already there
+    // the closest-point launch of scan_nearest (scan_api.hip; no warm start, no barycentrics), then the reduction on the points already there
     bf_nearest_launch(dim3((n + 3) / 4, 1), st, d_s, d_p, n, d_f, d_c, (float *)nullptr, 0);
     if (loss || dpoints) {
         BF_TRY(c.scratch(nblk, d_part));
@@ -194,13 +182,6 @@ int bf_ml_normal_loss(BfRouteCall &c, int device, int n, const float *closest_fa
         hipLaunchKernelGGL(bf_ml_normal_partial_kernel, dim3(nblk), dim3(256), 0, c.stream, n, d_fn, d_pn, d_part, d_dpn);
     bf_ml_finish_launch(c, d_part, nblk, 0, (float)n, d_loss);
     return c.finish();
-}
-
-// what every *_dev call here checks first: -> BF_OK, or the refusal (nothing has been queued)
-int bf_ml_dev_check(const char *who, const bf_workspace *ws, int device) {
-    if (!ws) return fail(BF_ERR_INVALID, std::string(who) + ": the workspace is NULL");
-    if (ws->device != device) return fail(BF_ERR_INVALID, std::string(who) + ": the workspace lives on another device");
-    return BF_OK;
 }
 }  // namespace
 
@@ -276,29 +257,6 @@ extern "C" int bf_scan_point_loss_dev(bf_scan *s, int n, const float *points, fl
     ++bf_route_stats().dev;
     BfRouteCall c(ws, (hipStream_t)stream);
     return bf_ml_point_loss(c, s, n, points, loss, face_ids, nearest, dpoints);
-}
-
-// (bf_scan_nearest, scan_api.hip, allocates with hipMalloc and keeps its own body: this is its launch on the device route)
-extern "C" int bf_scan_nearest_dev(bf_scan *s, int n, const float *points, int32_t *face_ids, float *nearest, float *bary, bf_workspace *ws,
-                                   void *stream) {
-    const char *who = "bf_scan_nearest_dev";
-    if (!s || !points) return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");
-    BF_TRY(bf_ml_dev_check(who, ws, s->device));
-    BF_TRY(bf_ml_check_count(who, "points", n));
-    ++bf_route_stats().dev;
-    BfRouteCall c(ws, (hipStream_t)stream);
-    BF_TRY(c.begin(s->device));
-    const size_t N = (size_t)n;
-    const ScanDev *d_s = nullptr;
-    int *d_f = nullptr;
-    float *d_c = nullptr, *d_b = nullptr;
-    // (the twin's launch writes all three: an output not wanted lands in the workspace)
-    BF_TRY(c.out((int *)face_ids, N, d_f, true));
-    BF_TRY(c.out(nearest, N * 3, d_c, true));
-    BF_TRY(c.out(bary, N * 3, d_b, true));
-    BF_TRY(bf_ml_scan_dev(c, s, d_s));
-    bf_nearest_launch(dim3((n + 3) / 4, 1), c.stream, d_s, points, n, d_f, d_c, d_b, 0);
-    return c.finish();
 }
 
 extern "C" int bf_normal_loss(int device, int n, const float *closest_face_norms, const float *point_norms, float *loss, float *dpoint_norms) {

@@ -2,6 +2,7 @@
 // the host tables are derived from it without a HIP call (derive_tables), then each table struct - FitTab, MeshTab, KpIO, the
 // sub-models - uploads what it points at and takes the pointers (fill_*).
 #include "bf_host.h"
+#include "dev_route.h"
 #include "fit_kernels.h"
 #include "mesh_kernels.h"
 #include <memory>
@@ -469,33 +470,30 @@ int bf_model_sub_vertices(const bf_model *m, int which, int32_t *ids) {
 }
 int bf_model_fit_instance(const bf_model *m) { return (m && bf_fit_is_sized_smpl(&m->fit)) ? 1 : 0; }
 
-// generic forward from packed parameters (bf_model_forward)
+// generic forward from packed parameters (bf_model_forward): a stateless call on host arrays, on the host route of a BfRouteCall
 int bf_model_forward(bf_model *m, int n, const float *params, float *vertices, float *joints) {
     if (!m || n <= 0 || !params) return fail(BF_ERR_INVALID, "bf_model_forward: bad argument");
-    HIP_TRY(hipSetDevice(m->device));
-    DevBuf<float> d_p, d_state, d_vraw, d_j, d_xp;
-    MeshScratch scratch;
-    HIP_TRY(d_p.upload(std::vector<float>(params, params + (size_t)n * m->np)));
-    HIP_TRY(d_state.alloc((size_t)n * bf_state_stride(m->nj, m->npf, m->nb)));
-    HIP_TRY(d_vraw.alloc((size_t)n * m->nv * 3));
-    HIP_TRY(d_j.alloc((size_t)n * m->n_joint_map * 3));
-    HIP_TRY(d_xp.alloc((size_t)n * m->mesh.n_tiles * std::max(m->n_extra, 1) * 3));
-    std::vector<float> zero((size_t)n * m->np, 0.f);
+    BfRouteCall c(nullptr, nullptr);
+    BF_TRY(c.begin(m->device));
+    const size_t N = (size_t)n;
     // model space: similarity parameters are ignored (transl 0, scale 1, constant scale 1)
-    std::vector<float> pk(params, params + (size_t)n * m->np);
+    std::vector<float> pk(params, params + N * m->np);
     for (int i = 0; i < n; ++i) { float *q = pk.data() + (size_t)i * m->np; q[0] = q[1] = q[2] = 0.f; q[3] = 1.f; }
-    HIP_TRY(hipMemcpy(d_p.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(bf_pose_state_kernel, dim3(n), dim3(128), 0, 0, m->fit, (const float *)nullptr, (const float *)nullptr,
-                       (const float *)nullptr, (const float *)nullptr, d_state.p, (const float *)d_p.p, (const float *)nullptr, 1.0f);
+    const float *d_p = nullptr;
+    float *d_state = nullptr, *d_vraw = nullptr, *d_j = nullptr, *d_xp = nullptr;
+    BF_TRY(c.in(pk.data(), pk.size(), d_p));
+    BF_TRY(c.scratch(N * bf_state_stride(m->nj, m->npf, m->nb), d_state));
+    BF_TRY(c.out(vertices, N * m->nv * 3, d_vraw, true));
+    BF_TRY(c.out(joints, N * m->n_joint_map * 3, d_j, true));
+    BF_TRY(c.scratch(N * m->mesh.n_tiles * std::max(m->n_extra, 1) * 3, d_xp));
+    hipLaunchKernelGGL(bf_pose_state_kernel, dim3(n), dim3(128), 0, c.stream, m->fit, (const float *)nullptr, (const float *)nullptr,
+                       (const float *)nullptr, (const float *)nullptr, d_state, d_p, (const float *)nullptr, 1.0f);
     HIP_TRY(hipGetLastError());
     MeshPass mesh;
-    mesh.scr = &scratch; mesh.n = n; mesh.state = d_state.p;
-    mesh.vraw = d_vraw.p; mesh.xpart = d_xp.p; mesh.joints = d_j.p;
+    mesh.scr = c.mesh_scratch(); mesh.n = n; mesh.state = d_state; mesh.stream = c.stream;
+    mesh.vraw = d_vraw; mesh.xpart = d_xp; mesh.joints = d_j;
     BF_TRY(bf_launch_mesh(m, mesh));
-    HIP_TRY(hipDeviceSynchronize());
-    if (vertices) HIP_TRY(hipMemcpy(vertices, d_vraw.p, d_vraw.n * sizeof(float), hipMemcpyDeviceToHost));
-    if (joints) HIP_TRY(hipMemcpy(joints, d_j.p, d_j.n * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
+    return c.finish();
 }
 
 }  // extern "C"

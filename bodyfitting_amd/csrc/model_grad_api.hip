@@ -1,5 +1,5 @@
-// Host side of bf_smpl_vjp, bf_smplx_forward and bf_smplx_vjp (include/bodyfit.h): the reverse torch.autograd runs through
-// models.smpl.SMPL.forward (smplx's lbs() and models/smpl.py:69-83), smplx.create(model_type='smplx', ...)'s forward as the reference
+// Host side of bf_smpl_forward, bf_smpl_vjp, bf_smplx_forward and bf_smplx_vjp (include/bodyfit.h): models.smpl.SMPL.forward, the reverse
+// torch.autograd runs through it (smplx's lbs() and models/smpl.py:69-83), smplx.create(model_type='smplx', ...)'s forward as the reference
 // calls it (smplify.py:177-190) and its reverse - all on the dense schedule's mesh passes, through one ModelPass:
 //   forward  bf_pose_state_kernel (non-packed thetas, no similarity, constant scale 1) + the mesh pass; for the reverse it saves the
 //            pose-blended vertices and, on an SMPL-X model, the landmarks' vertices / weights of every frame
@@ -19,8 +19,7 @@
 // their route and hand the body their call.  The launches, their order, grids and arguments are the same on both routes; what differs
 // is where the arrays live (host arrays and the block cache's buffers, or device pointers and workspace slots), the stream (the NULL
 // stream, or the caller's) and the end: the host route drains the device and copies, the device route waits for nothing and cuts the
-// gradient rows into the caller's blocks with bf_block_scatter_kernel.  bf_smpl_forward (api.hip) allocates with hipMalloc and keeps
-// its own body; bf_smpl_forward_dev is that body's launches on the device route.
+// gradient rows into the caller's blocks with bf_block_scatter_kernel.
 #include "bf_host.h"
 #include "dev_route.h"
 #include "mesh_kernels.h"
@@ -68,7 +67,7 @@ struct ModelPass {
         return rc;
     }
 
-    // Model space: no similarity, constant scale 1 - as bf_smpl_forward builds its state, so that the mesh reverse's dvout is dL/dv in
+    // Model space: no similarity, constant scale 1 - as smpl_forward builds its state, so that the mesh reverse's dvout is dL/dv in
     // model space.  for_reverse: vposed is saved instead of the mapped joints.  An SMPL-X model's joints pass leaves all its joints
     // (jraw) and, for the reverse, every frame's landmark vertices and weights (the contour row of ITS yaw).
     // expression (device, [n][n_expr]; null: none - then the launches are the ones of a model without directions): the chain delta
@@ -213,7 +212,33 @@ struct Inputs {
     }
 };
 
-// the bodies of bf_smpl_vjp, bf_smplx_forward_expr and bf_smplx_vjp_expr and of their *_dev twins (arguments checked, an output wanted)
+// the bodies of bf_smpl_forward, bf_smpl_vjp, bf_smplx_forward_expr and bf_smplx_vjp_expr and of their *_dev twins (arguments checked)
+// models.smpl.SMPL.forward: the joints pass writes the mapped joints and joints_ori whoever wants them
+int smpl_forward(BfRouteCall &c, bf_model *m, int n, const float *betas, const float *global_orient, const float *body_pose,
+                 float *vertices, float *joints, float *joints_ori) {
+    BF_TRY(c.begin(m->device));
+    const size_t N = (size_t)n;
+    const float *d_beta = nullptr, *d_or = nullptr, *d_bp = nullptr;
+    BF_TRY(c.in(betas, N * m->nb, d_beta));
+    BF_TRY(c.in(global_orient, N * 3, d_or));
+    BF_TRY(c.in(body_pose, N * 3 * (m->nj - 1), d_bp));
+    ModelPass pass(m, n, c);
+    float *jori = nullptr;
+    BF_TRY(pass.need(pass.state, N * bf_state_stride(m->nj, m->npf, m->nb)));
+    BF_TRY(pass.need(pass.vraw, N * m->nv * 3, vertices));
+    BF_TRY(pass.need(pass.xpart, N * m->mesh.n_tiles * m->n_extra * 3));
+    BF_TRY(pass.need(pass.joints, N * m->n_joint_map * 3, joints));
+    BF_TRY(pass.need(jori, N * (m->nj + m->n_selector) * 3, joints_ori));
+    hipLaunchKernelGGL(bf_pose_state_kernel, dim3(n), dim3(128), 0, c.stream, m->fit, d_beta, d_or, d_bp, (const float *)nullptr, pass.state,
+                       (const float *)nullptr, (const float *)nullptr, 1.0f);
+    HIP_TRY(hipGetLastError());
+    MeshPass mesh;
+    mesh.scr = c.mesh_scratch(); mesh.n = n; mesh.state = pass.state; mesh.stream = c.stream;
+    mesh.vraw = pass.vraw; mesh.xpart = pass.xpart; mesh.joints = pass.joints; mesh.joints_ori = jori;
+    BF_TRY(pass.launch_mesh(mesh));
+    return c.finish();
+}
+
 int smpl_vjp(BfRouteCall &c, bf_model *m, int n, const float *betas, const float *global_orient, const float *body_pose,
              const float *dvertices, const float *djoints, const float *djoints_ori, float *dbetas, float *dglobal_orient, float *dbody_pose) {
     BF_TRY(c.begin(m->device));
@@ -321,7 +346,14 @@ extern "C" int bf_smpl_vjp_dev(bf_model *m, bf_workspace *ws, void *stream, int 
     return smpl_vjp(c, m, n, betas, global_orient, body_pose, dvertices, djoints, djoints_ori, dbetas, dglobal_orient, dbody_pose);
 }
 
-// bf_smpl_forward's buffers and launches (api.hip) on the device route
+extern "C" int bf_smpl_forward(bf_model *m, int n, const float *betas, const float *global_orient, const float *body_pose,
+                               float *vertices, float *joints, float *joints_ori) {
+    if (!m || n <= 0 || !betas || !global_orient || !body_pose) return fail(BF_ERR_INVALID, "bf_smpl_forward: bad argument");
+    ++bf_route_stats().host;
+    BfRouteCall c(nullptr, nullptr);
+    return smpl_forward(c, m, n, betas, global_orient, body_pose, vertices, joints, joints_ori);
+}
+
 extern "C" int bf_smpl_forward_dev(bf_model *m, bf_workspace *ws, void *stream, int n, const float *betas, const float *global_orient,
                                    const float *body_pose, float *vertices, float *joints, float *joints_ori) {
     const char *who = "bf_smpl_forward_dev";
@@ -330,22 +362,7 @@ extern "C" int bf_smpl_forward_dev(bf_model *m, bf_workspace *ws, void *stream, 
     if (m->kind != 0) return fail(BF_ERR_UNSUPPORTED, std::string(who) + ": SMPL-kind models only");
     ++bf_route_stats().dev;
     BfRouteCall c(ws, (hipStream_t)stream);
-    BF_TRY(c.begin(m->device));
-    const size_t N = (size_t)n;
-    ModelPass pass(m, n, c);
-    float *jori = nullptr;
-    BF_TRY(pass.need(pass.state, N * bf_state_stride(m->nj, m->npf, m->nb)));
-    BF_TRY(pass.need(pass.vraw, N * m->nv * 3, vertices));
-    BF_TRY(pass.need(pass.xpart, N * m->mesh.n_tiles * m->n_extra * 3));
-    BF_TRY(pass.need(pass.joints, N * m->n_joint_map * 3, joints));
-    BF_TRY(pass.need(jori, N * (m->nj + m->n_selector) * 3, joints_ori));
-    hipLaunchKernelGGL(bf_pose_state_kernel, dim3(n), dim3(128), 0, c.stream, m->fit, betas, global_orient, body_pose, (const float *)nullptr,
-                       pass.state, (const float *)nullptr, (const float *)nullptr, 1.0f);
-    HIP_TRY(hipGetLastError());
-    MeshPass mesh;
-    mesh.scr = c.mesh_scratch(); mesh.n = n; mesh.state = pass.state; mesh.stream = c.stream;
-    mesh.vraw = pass.vraw; mesh.xpart = pass.xpart; mesh.joints = pass.joints; mesh.joints_ori = jori;
-    return pass.launch_mesh(mesh);
+    return smpl_forward(c, m, n, betas, global_orient, body_pose, vertices, joints, joints_ori);
 }
 
 extern "C" int bf_model_n_expression(const bf_model *m) { return m ? m->n_expr : 0; }

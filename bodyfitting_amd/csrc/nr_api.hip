@@ -218,9 +218,9 @@ int bf_nr_mesh_create(bf_nr *r, int n_verts, const float *verts, int n_faces, co
     HIP_TRY(hipSetDevice(r->device));
     std::unique_ptr<bf_nr_mesh> m(new bf_nr_mesh());
     m->owner = r->id; m->device = r->device; m->nv = n_verts; m->nf = n_faces; m->ts = texture_size;
-    HIP_TRY(m->verts.upload(std::vector<float>(verts, verts + (size_t)n_verts * 3)));
+    HIP_TRY(m->verts.upload(verts, (size_t)n_verts * 3));
     m->topo = std::make_shared<NrTopology>();
-    HIP_TRY(m->topo->faces.upload(std::vector<int>(faces, faces + (size_t)n_faces * 3)));
+    HIP_TRY(m->topo->faces.upload(faces, (size_t)n_faces * 3));
     {   // counting sort of (record * 3 + corner) by vertex, records ascending
         std::vector<int> start((size_t)n_verts + 1, 0), entry((size_t)n_faces * 6);
         for (size_t i = 0; i < (size_t)n_faces * 3; ++i) start[(size_t)faces[i] + 1] += 2;

@@ -253,7 +253,7 @@ int bf_openpose_create(int device, const float *weights, int64_t n_weights, int 
     auto *op = new bf_openpose();
     op->device = device; op->max_batch = max_batch; op->max_h = max_h; op->max_w = max_w; op->layers = std::move(layers);
     const bool ok = hipStreamCreateWithFlags(&op->stream, hipStreamNonBlocking) == hipSuccess &&
-                    op->w.upload(std::vector<float>(weights, weights + total)) == hipSuccess;
+                    op->w.upload(weights, total) == hipSuccess;
     if (!ok) { bf_openpose_destroy(op); return fail(BF_ERR_HIP, "bf_openpose_create: device allocation failed"); }
     *out = op;
     return BF_OK;

@@ -280,7 +280,7 @@ int bf_openpose_hand_create(int device, const float *weights, int64_t n_weights,
     auto *h = new bf_openpose_hand();
     h->device = device; h->max_hands = max_hands; h->max_h = max_h; h->max_w = max_w; h->layers = std::move(layers);
     const bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
-                    h->w.upload(std::vector<float>(weights, weights + total)) == hipSuccess;
+                    h->w.upload(weights, total) == hipSuccess;
     if (!ok) { bf_openpose_hand_destroy(h); return fail(BF_ERR_HIP, "bf_openpose_hand_create: device allocation failed"); }
     *out = h;
     return BF_OK;
@@ -363,7 +363,7 @@ int bf_openpose_hand_selftest_label(int device, int n, int H, int W, const uint8
     const size_t N = (size_t)H * W;
     DevBuf<uint8_t> db;
     DevBuf<int> scr, dl, dc;
-    HIP_TRY(db.upload(std::vector<uint8_t>(binary, binary + N * n)));
+    HIP_TRY(db.upload(binary, N * n));
     HIP_TRY(scr.alloc(N * 4 * n));
     HIP_TRY(dl.alloc(N * n));
     HIP_TRY(dc.alloc((size_t)n));

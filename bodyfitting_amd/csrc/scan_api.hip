@@ -1,6 +1,7 @@
 // Host side of the scan (use_mesh) objects: grid construction, the closest-point, inside and intersection queries, and attaching a
 // frame's scans to a batch.  The per-iteration schedule that fits against them is dense_api.hip.
 #include "bf_host.h"
+#include "dev_route.h"
 #include "grid_kernels.h"
 #include "scan_kernels.h"
 
@@ -160,52 +161,92 @@ int bf_scan_grid_lists(const bf_scan *s, int32_t *tri_num, int32_t *tri_idx, int
     return BF_OK;
 }
 
+// The queries below are stateless calls on host arrays: each runs on the host route of a BfRouteCall (dev_route.h), which uploads the
+// inputs into blocks of the device's cache, hands the kernels blocks for their outputs, drains the device once and copies back.  Only
+// bf_scan_nearest is one of the calls a torch loop goes through: it has a *_dev twin and counts its route (bf_dev_route_stats).
+
 // MeshGridSearcher.inside_mesh (utils/mesh_grid_searcher.py:86-91 -> search_inside_mesh, mesh_grid.cpp:74-90)
 int bf_scan_inside(bf_scan *s, int n, const float *points, float *signs) {
     if (!s || n <= 0 || !points || !signs) return fail(BF_ERR_INVALID, "bf_scan_inside: bad argument");
-    HIP_TRY(hipSetDevice(s->device));
-    DevBuf<float> d_p, d_s;
-    HIP_TRY(d_p.upload(std::vector<float>(points, points + (size_t)n * 3)));
-    HIP_TRY(d_s.alloc(n));
-    hipLaunchKernelGGL(bf_inside_mesh_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->dev, (const float *)d_p.p, n, d_s.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(signs, d_s.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
+    BfRouteCall c(nullptr, nullptr);
+    BF_TRY(c.begin(s->device));
+    const float *d_p = nullptr;
+    float *d_s = nullptr;
+    BF_TRY(c.in(points, (size_t)n * 3, d_p));
+    BF_TRY(c.out(signs, (size_t)n, d_s));
+    hipLaunchKernelGGL(bf_inside_mesh_kernel, dim3((n + 255) / 256), dim3(256), 0, c.stream, s->dev, d_p, n, d_s);
+    return c.finish();
 }
 
 // MeshGridSearcher.intersects_any (utils/mesh_grid_searcher.py:93-99 -> search_intersect, mesh_grid.cpp:92-110)
 int bf_scan_intersects(bf_scan *s, int n, const float *origins, const float *directions, uint8_t *hit) {
     if (!s || n <= 0 || !origins || !directions || !hit) return fail(BF_ERR_INVALID, "bf_scan_intersects: bad argument");
-    HIP_TRY(hipSetDevice(s->device));
-    DevBuf<float> d_o, d_d;
-    DevBuf<unsigned char> d_h;
-    HIP_TRY(d_o.upload(std::vector<float>(origins, origins + (size_t)n * 3)));
-    HIP_TRY(d_d.upload(std::vector<float>(directions, directions + (size_t)n * 3)));
-    HIP_TRY(d_h.alloc(n));
-    hipLaunchKernelGGL(bf_intersect_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->dev, (const float *)d_o.p, (const float *)d_d.p, n, d_h.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(hit, d_h.p, (size_t)n, hipMemcpyDeviceToHost));
+    BfRouteCall c(nullptr, nullptr);
+    BF_TRY(c.begin(s->device));
+    const float *d_o = nullptr, *d_d = nullptr;
+    unsigned char *d_h = nullptr;
+    BF_TRY(c.in(origins, (size_t)n * 3, d_o));
+    BF_TRY(c.in(directions, (size_t)n * 3, d_d));
+    BF_TRY(c.out((unsigned char *)hit, (size_t)n, d_h));
+    hipLaunchKernelGGL(bf_intersect_kernel, dim3((n + 255) / 256), dim3(256), 0, c.stream, s->dev, d_o, d_d, n, d_h);
+    return c.finish();
+}
+
+}  // extern "C"
+
+// the scan's ScanDev in device memory, made once per scan: complete on the device when this returns (later calls come on any stream)
+int bf_scan_resident(bf_scan *s, const ScanDev **out) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> g(mu);
+    if (!s->dev_resident.p) {
+        HIP_TRY(s->dev_resident.upload(&s->dev, 1));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    *out = s->dev_resident.p;
     return BF_OK;
 }
 
-// MeshGridSearcher.nearest_points -> SurfaceNearest (utils/mesh_grid_searcher.py:6-15,81-84)
+// the scan's ScanDev where the kernels of `c` read it: the host route uploads it with the call, the device route keeps it resident
+int bf_ml_scan_dev(BfRouteCall &c, bf_scan *s, const ScanDev *&d_s) {
+    if (c.ws) return bf_scan_resident(s, &d_s);
+    return c.in(&s->dev, 1, d_s);
+}
+
+// MeshGridSearcher.nearest_points -> SurfaceNearest (utils/mesh_grid_searcher.py:6-15,81-84): the body of bf_scan_nearest and of
+// bf_scan_nearest_dev.  The launch writes all three outputs: one not wanted lands in a buffer of the call
+static int scan_nearest(BfRouteCall &c, bf_scan *s, int n, const float *points, int32_t *face_ids, float *nearest, float *bary) {
+    BF_TRY(c.begin(s->device));
+    const size_t N = (size_t)n;
+    const float *d_p = nullptr;
+    const ScanDev *d_s = nullptr;
+    int *d_f = nullptr;
+    float *d_c = nullptr, *d_b = nullptr;
+    BF_TRY(c.in(points, N * 3, d_p));
+    BF_TRY(c.out((int *)face_ids, N, d_f, true));
+    BF_TRY(c.out(nearest, N * 3, d_c, true));
+    BF_TRY(c.out(bary, N * 3, d_b, true));
+    BF_TRY(bf_ml_scan_dev(c, s, d_s));
+    bf_nearest_launch(dim3((n + 3) / 4, 1), c.stream, d_s, d_p, n, d_f, d_c, d_b, 0);
+    return c.finish();
+}
+
+extern "C" {
+
 int bf_scan_nearest(bf_scan *s, int n, const float *points, int32_t *face_ids, float *nearest, float *bary) {
     if (!s || n <= 0 || !points) return fail(BF_ERR_INVALID, "bf_scan_nearest: bad argument");
     ++bf_route_stats().host;
-    HIP_TRY(hipSetDevice(s->device));
-    DevBuf<float> d_p, d_c, d_b;
-    DevBuf<int> d_f;
-    DevBuf<ScanDev> d_s;
-    HIP_TRY(d_p.upload(std::vector<float>(points, points + (size_t)n * 3)));
-    HIP_TRY(d_c.alloc((size_t)n * 3)); HIP_TRY(d_b.alloc((size_t)n * 3)); HIP_TRY(d_f.alloc(n));
-    HIP_TRY(d_s.upload(std::vector<ScanDev>(1, s->dev)));
-    bf_nearest_launch(dim3((n + 3) / 4, 1), 0, (const ScanDev *)d_s.p, (const float *)d_p.p, n, d_f.p, d_c.p, d_b.p, 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (face_ids) HIP_TRY(hipMemcpy(face_ids, d_f.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    if (nearest) HIP_TRY(hipMemcpy(nearest, d_c.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (bary) HIP_TRY(hipMemcpy(bary, d_b.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
+    BfRouteCall c(nullptr, nullptr);
+    return scan_nearest(c, s, n, points, face_ids, nearest, bary);
+}
+
+int bf_scan_nearest_dev(bf_scan *s, int n, const float *points, int32_t *face_ids, float *nearest, float *bary, bf_workspace *ws, void *stream) {
+    const char *who = "bf_scan_nearest_dev";
+    if (!s || !points) return fail(BF_ERR_INVALID, std::string(who) + ": bad argument");
+    BF_TRY(bf_ml_dev_check(who, ws, s->device));
+    BF_TRY(bf_ml_check_count(who, "points", n));
+    ++bf_route_stats().dev;
+    BfRouteCall c(ws, (hipStream_t)stream);
+    return scan_nearest(c, s, n, points, face_ids, nearest, bary);
 }
 
 /* bf_scan_nearest with a GUESS per query: hint[n,3] = where the caller believes the nearest point is (the fit loop hands the search its
@@ -215,76 +256,82 @@ int bf_scan_nearest(bf_scan *s, int n, const float *points, int32_t *face_ids, f
 int bf_scan_nearest_hinted(bf_scan *s, int n, const float *points, const float *hint, int32_t *face_ids, float *nearest, float *bary,
                            int reps, float *kernel_us) {
     if (!s || n <= 0 || !points) return fail(BF_ERR_INVALID, "bf_scan_nearest_hinted: bad argument");
-    HIP_TRY(hipSetDevice(s->device));
-    DevBuf<float> d_p, d_c, d_b, d_h;
-    DevBuf<int> d_f;
-    DevBuf<ScanDev> d_s;
-    HIP_TRY(d_p.upload(std::vector<float>(points, points + (size_t)n * 3)));
-    HIP_TRY(d_c.alloc((size_t)n * 3)); HIP_TRY(d_b.alloc((size_t)n * 3)); HIP_TRY(d_f.alloc(n));
-    if (hint) HIP_TRY(d_h.upload(std::vector<float>(hint, hint + (size_t)n * 3)));
-    HIP_TRY(d_s.upload(std::vector<ScanDev>(1, s->dev)));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    struct Events {                         // destroyed on every way out
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
+    BfRouteCall c(nullptr, nullptr);
+    BF_TRY(c.begin(s->device));
+    const size_t N = (size_t)n;
+    const float *d_p = nullptr, *d_h = nullptr;
+    const ScanDev *d_s = nullptr;
+    int *d_f = nullptr;
+    float *d_c = nullptr, *d_b = nullptr;
+    BF_TRY(c.in(points, N * 3, d_p));
+    BF_TRY(c.in(hint, N * 3, d_h));
+    BF_TRY(c.out((int *)face_ids, N, d_f, true));
+    BF_TRY(c.out(nearest, N * 3, d_c, true));
+    BF_TRY(c.out(bary, N * 3, d_b, true));
+    BF_TRY(bf_ml_scan_dev(c, s, d_s));
+    HIP_TRY(hipEventCreate(&ev.e0)); HIP_TRY(hipEventCreate(&ev.e1));
     double total_ms = 0.0;
     for (int r = 0; r < std::max(reps, 1); ++r) {
-        if (hint) HIP_TRY(hipMemcpyAsync(d_c.p, d_h.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, 0));
-        HIP_TRY(hipEventRecord(e0, 0));
-        bf_nearest_launch(dim3((n + 3) / 4, 1), 0, (const ScanDev *)d_s.p, (const float *)d_p.p, n, d_f.p, d_c.p, d_b.p, hint ? 1 : 0);
-        HIP_TRY(hipEventRecord(e1, 0));
+        if (hint) HIP_TRY(hipMemcpyAsync(d_c, d_h, N * 3 * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
+        HIP_TRY(hipEventRecord(ev.e0, c.stream));
+        bf_nearest_launch(dim3((n + 3) / 4, 1), c.stream, d_s, d_p, n, d_f, d_c, d_b, hint ? 1 : 0);
+        HIP_TRY(hipEventRecord(ev.e1, c.stream));
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventSynchronize(ev.e1));
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
         total_ms += ms;
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (kernel_us) *kernel_us = (float)(total_ms * 1e3 / std::max(reps, 1));
-    if (face_ids) HIP_TRY(hipMemcpy(face_ids, d_f.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    if (nearest) HIP_TRY(hipMemcpy(nearest, d_c.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (bary) HIP_TRY(hipMemcpy(bary, d_b.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
+    return c.finish();
 }
 
 // self-tests of the reference-arithmetic rule (nearest_rule_ref.h): its division helper against the caller's IEEE quotients, and the
 // per-triangle rule on explicit patches
 int bf_nearest_selftest_quot(int device, int n, const float *num, const float *den, float *out) {
     if (n <= 0 || !num || !den || !out) return fail(BF_ERR_INVALID, "bf_nearest_selftest_quot: bad argument");
-    HIP_TRY(hipSetDevice(device));
-    DevBuf<float> d_n, d_d, d_o;
-    HIP_TRY(d_n.upload(std::vector<float>(num, num + n))); HIP_TRY(d_d.upload(std::vector<float>(den, den + n))); HIP_TRY(d_o.alloc(n));
-    hipLaunchKernelGGL(bf_nearest_quot_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, (const float *)d_n.p, (const float *)d_d.p, d_o.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_o.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
+    BfRouteCall c(nullptr, nullptr);
+    BF_TRY(c.begin(device));
+    const float *d_n = nullptr, *d_d = nullptr;
+    float *d_o = nullptr;
+    BF_TRY(c.in(num, (size_t)n, d_n));
+    BF_TRY(c.in(den, (size_t)n, d_d));
+    BF_TRY(c.out(out, (size_t)n, d_o));
+    hipLaunchKernelGGL(bf_nearest_quot_kernel, dim3((n + 255) / 256), dim3(256), 0, c.stream, n, d_n, d_d, d_o);
+    return c.finish();
 }
 int bf_nearest_selftest_rule(int device, int n, const float *patches, int general, float *dist, float *coeff) {
     if (n <= 0 || !patches || !dist || !coeff) return fail(BF_ERR_INVALID, "bf_nearest_selftest_rule: bad argument");
-    HIP_TRY(hipSetDevice(device));
-    DevBuf<float> d_p, d_d, d_c;
-    HIP_TRY(d_p.upload(std::vector<float>(patches, patches + (size_t)n * 9))); HIP_TRY(d_d.alloc(n)); HIP_TRY(d_c.alloc((size_t)n * 3));
-    hipLaunchKernelGGL(bf_nearest_rule_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, n, (const float *)d_p.p, d_d.p, d_c.p, general);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(dist, d_d.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(coeff, d_c.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
+    BfRouteCall c(nullptr, nullptr);
+    BF_TRY(c.begin(device));
+    const float *d_p = nullptr;
+    float *d_d = nullptr, *d_c = nullptr;
+    BF_TRY(c.in(patches, (size_t)n * 9, d_p));
+    BF_TRY(c.out(dist, (size_t)n, d_d));
+    BF_TRY(c.out(coeff, (size_t)n * 3, d_c));
+    hipLaunchKernelGGL(bf_nearest_rule_kernel, dim3((n + 63) / 64), dim3(64), 0, c.stream, n, d_p, d_d, d_c, general);
+    return c.finish();
 }
 
 // SurfaceNearest.backward with respect to the query points (utils/mesh_grid_searcher.py:17-49, unfinished in the reference):
 // dpoints = (d nearest / d points)^T dnearest for the faces / coefficients bf_scan_nearest returned
 int bf_scan_nearest_backward(bf_scan *s, int n, const int32_t *face_ids, const float *bary, const float *dnearest, float *dpoints) {
     if (!s || n <= 0 || !face_ids || !bary || !dnearest || !dpoints) return fail(BF_ERR_INVALID, "bf_scan_nearest_backward: bad argument");
-    HIP_TRY(hipSetDevice(s->device));
-    DevBuf<int> d_f;
-    DevBuf<float> d_b, d_g, d_o;
-    HIP_TRY(d_f.upload(std::vector<int>(face_ids, face_ids + n)));
-    HIP_TRY(d_b.upload(std::vector<float>(bary, bary + (size_t)n * 3)));
-    HIP_TRY(d_g.upload(std::vector<float>(dnearest, dnearest + (size_t)n * 3)));
-    HIP_TRY(d_o.alloc((size_t)n * 3));
-    hipLaunchKernelGGL(bf_nearest_backward_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->dev, n, (const int *)d_f.p, (const float *)d_b.p,
-                       (const float *)d_g.p, d_o.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(dpoints, d_o.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return BF_OK;
+    BfRouteCall c(nullptr, nullptr);
+    BF_TRY(c.begin(s->device));
+    const int *d_f = nullptr;
+    const float *d_b = nullptr, *d_g = nullptr;
+    float *d_o = nullptr;
+    BF_TRY(c.in((const int *)face_ids, (size_t)n, d_f));
+    BF_TRY(c.in(bary, (size_t)n * 3, d_b));
+    BF_TRY(c.in(dnearest, (size_t)n * 3, d_g));
+    BF_TRY(c.out(dpoints, (size_t)n * 3, d_o));
+    hipLaunchKernelGGL(bf_nearest_backward_kernel, dim3((n + 255) / 256), dim3(256), 0, c.stream, s->dev, n, d_f, d_b, d_g, d_o);
+    return c.finish();
 }
 
 // use_mesh=True, meshfile per frame (smplify.py:146-156): one scan per frame; constant_scale = scan_height / 1.7

@@ -1,7 +1,8 @@
 // Host side of bf_silhouette_* (include/bodyfit.h): multview_mask_loss (smplify/loss.py:85-130) on vertices the caller holds, as one
 // call on host arrays for a user's own torch loop.  The object keeps the views' masks and contours on the device and the call's
 // buffers between calls; an evaluation is one upload (projection rows + vertices), three launches (silhouette_kernels.hip) and one
-// read-back (loss, view terms, gradient), with no host wait in between.  Everything runs on the NULL stream, like bf_scan_nearest.
+// read-back (loss, view terms, gradient), with no host wait in between.  Everything runs on the NULL stream, like the host route
+// of the stateless calls (dev_route.h) - whose buffers, unlike this object's, come from the block cache call by call.
 #include "bf_host.h"
 #include "silhouette_kernels.h"
 

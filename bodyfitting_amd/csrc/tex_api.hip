@@ -168,9 +168,9 @@ static int tex_set_mesh(bf_texfit *x, int which, int n_verts, const float *verts
     M.release();
     M.nv = n_verts; M.nf = n_faces;
     const size_t ntex = (size_t)n_faces * x->ts * x->ts * x->ts * 3, npx = (size_t)x->is * x->is, ntile = (size_t)x->tiles * x->tiles;
-    HIP_TRY(M.verts.upload(std::vector<float>(verts, verts + (size_t)n_verts * 3)));
-    HIP_TRY(M.faces.upload(std::vector<int>(faces, faces + (size_t)n_faces * 3)));
-    HIP_TRY(M.tex.upload(std::vector<float>(textures, textures + ntex)));
+    HIP_TRY(M.verts.upload(verts, (size_t)n_verts * 3));
+    HIP_TRY(M.faces.upload(faces, (size_t)n_faces * 3));
+    HIP_TRY(M.tex.upload(textures, ntex));
     HIP_TRY(M.pv.alloc((size_t)n_verts * 3)); HIP_TRY(M.frec.alloc((size_t)n_faces * BF_TEX_REC));
     HIP_TRY(M.pix.alloc(npx * 5)); HIP_TRY(M.rgb.alloc(npx * 3));
     HIP_TRY(M.tile_start.alloc(ntile + 1)); HIP_TRY(M.cursor.alloc(ntile + 1));

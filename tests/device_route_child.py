@@ -564,3 +564,82 @@ def fallbacks(out_path, switched_off):
         return {"ok": np.ones(1)}
 
     _run(out_path, body)
+
+
+def smpl_forward_outputs(out_path):
+    """bf_smpl_forward and bf_smpl_forward_dev on the 690-vertex model at n = 1, 3, 15 and 16 (both sides of the mesh pass's choice of
+    path) with each of the seven non-empty subsets of (vertices, joints, joints_ori): on both routes every output asked for holds the
+    bits of the host route's all-outputs call; on the device route nothing is written behind an output and a second identical call
+    allocates nothing.  The host entry counts one host call and nothing else, and runs with all three outputs NULL.  Then the
+    refusals of both entries, each before anything is queued or counted."""
+    def body():
+        _repo()
+        import ctypes as C
+        from bodyfitting_amd import _lib, native as N, synthetic as S
+        _took("device")
+        lib = _lib.load()
+        stream = torch.cuda.current_stream().cuda_stream
+        gmm = S.make_gmm(seed=0)
+        dev = N.DeviceModel(S.make_model("smpl", seed=0, nv=690), gmm, device=0)
+        names = ("vertices", "joints", "joints_ori")
+        others = ("dev_calls", "allocations", "stream_switches")
+
+        def host_call(n, x, out):
+            before = N.dev_route_stats()
+            _lib.check(lib.bf_smpl_forward(dev._h, n, *[_lib.fptr(a) for a in x], *[_lib.fptr(out.get(k)) for k in names]), "bf_smpl_forward")
+            after = N.dev_route_stats()
+            assert after["host_calls"] == before["host_calls"] + 1 and all(after[k] == before[k] for k in others), (before, after)
+
+        for n in (1, 3, 15, 16):
+            x = _smpl_params(n, dev.n_betas, 150 + n)
+            host = dict(zip(names, dev.forward(*x)))
+            assert all(np.isfinite(a).all() for a in host.values())
+            x_t = [_gpu(a, False) for a in x]
+            for mask in range(1, 8):
+                asked = [k for i, k in enumerate(names) if (mask >> i) & 1]
+                out = {k: np.full(host[k].shape, np.nan, np.float32) for k in asked}
+                host_call(n, x, out)
+                for k in asked:
+                    assert out[k].tobytes() == host[k].tobytes(), f"host route n={n} {asked}: {k} differs from the all-outputs call"
+
+                def call():
+                    o = {k: _guarded(host[k].size) for k in asked}
+                    dev.forward_dev(n, stream, *[a.data_ptr() for a in x_t], **{k: a for k, (_, a) in o.items()})
+                    return o
+                for k, (t, _) in _two_calls(call, f"smpl forward n={n} {asked}").items():
+                    _guarded_is(t, host[k], f"smpl forward n={n} {asked} {k}")
+            host_call(n, x, {})                                   # all three NULL: the call runs and returns without error
+        torch.cuda.synchronize()
+        # refusals
+        INVALID, UNSUPPORTED = -1, -3
+        xdev = N.DeviceModel(S.make_model("smplx", seed=0, nv=1200), gmm, device=0)
+        ws = dev.workspace()
+        a_t = torch.zeros(3 * 1200 * 3, device=GPU)
+        a, h = C.c_void_p(a_t.data_ptr()), _lib.fptr(np.zeros(3 * 1200 * 3, np.float32))
+        before = N.dev_route_stats()
+        bad, said = b": bad argument", lambda: lib.bf_last_error()
+        for args in ((None, 1, h, h, h), (dev._h, 0, h, h, h), (dev._h, -1, h, h, h), (dev._h, 1, None, h, h), (dev._h, 1, h, None, h),
+                     (dev._h, 1, h, h, None)):
+            assert lib.bf_smpl_forward(*args, h, None, None) == INVALID and said() == b"bf_smpl_forward" + bad, (args, said())
+        who = b"bf_smpl_forward_dev"
+        for args in ((None, ws._h, None, 1, a, a, a), (dev._h, None, None, 1, a, a, a), (dev._h, ws._h, None, 0, a, a, a),
+                     (dev._h, ws._h, None, 1, None, a, a), (dev._h, ws._h, None, 1, a, None, a), (dev._h, ws._h, None, 1, a, a, None)):
+            assert lib.bf_smpl_forward_dev(*args, a, None, None) == INVALID and said() == who + bad, (args, said())
+        assert lib.bf_smpl_forward_dev(xdev._h, xdev.workspace()._h, None, 1, a, a, a, a, None, None) == UNSUPPORTED
+        assert said() == who + b": SMPL-kind models only", said()
+        if torch.cuda.device_count() > 1:
+            far = N.Workspace(1)
+            assert lib.bf_smpl_forward_dev(dev._h, far._h, None, 1, a, a, a, a, None, None) == INVALID
+            assert said() == who + b": the workspace lives on another device than the model", said()
+            far.close()
+        else:
+            print("one GPU: a workspace of another device not tried")
+        assert N.dev_route_stats() == before, "a refused call was counted or allocated"
+        # the host entry does not look at the model's kind
+        assert lib.bf_smpl_forward(xdev._h, 1, h, h, h, None, None, None) == 0, said()
+        torch.cuda.synchronize()
+        for d in (xdev, dev):
+            d.close()
+        return {"ok": np.ones(1)}
+
+    _run(out_path, body)

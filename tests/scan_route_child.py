@@ -681,3 +681,80 @@ def fallbacks(out_path, switched_off):
         return {"ok": np.ones(1)}
 
     _run(out_path, body)
+
+
+def nearest_outputs(out_path):
+    """bf_scan_nearest and bf_scan_nearest_dev at n = 1, 3, 4, 5 and 257 points (the launch is (n + 3) / 4 groups) with each non-empty
+    subset of (face_ids, nearest, bary): the words of the all-outputs call, the host call and the *_dev call agreeing word for word,
+    nothing written behind an output of the device route and no allocation on a second identical call.  bf_scan_nearest counts one
+    host call and nothing else.  Then the refusals of both entries, each before anything is queued or counted."""
+    def body():
+        _repo()
+        import ctypes as C
+        import scan_loss_cases as SC
+        from bodyfitting_amd import _lib, native as N
+        _took("device")
+        lib = _lib.load()
+        searcher, _ = _searcher()
+        scan, stream = searcher._scan, torch.cuda.current_stream().cuda_stream
+        names = ("face_ids", "nearest", "bary")
+        words = lambda a: np.ascontiguousarray(a).reshape(-1).view(np.uint32)          # noqa: E731
+
+        def host_call(n, pts, out):
+            before = _stats()
+            _lib.check(lib.bf_scan_nearest(scan._h, n, _lib.fptr(pts), _lib.iptr(out.get("face_ids")), _lib.fptr(out.get("nearest")),
+                                           _lib.fptr(out.get("bary"))), "bf_scan_nearest")
+            after = _stats()
+            assert after["host_calls"] == before["host_calls"] + 1, (before, after)
+            assert all(after[k] == before[k] for k in ("dev_calls", "allocations", "stream_switches")), (before, after)
+
+        for n in (1, 3, 4, 5, 257):
+            pts = SC.points(n)
+            near, ids, bary = scan.nearest_points(pts)
+            want = {"face_ids": ids, "nearest": near, "bary": bary}
+            assert ids.dtype == np.int32 and (ids >= 0).all() and np.isfinite(near).all() and np.isfinite(bary).all()
+            pts_t = _gpu(pts)
+            for mask in range(1, 8):
+                asked = [k for i, k in enumerate(names) if (mask >> i) & 1]
+                out = {k: np.full(want[k].shape, -7, want[k].dtype) for k in asked}
+                host_call(n, pts, out)
+
+                def call():
+                    o = {k: _guarded(want[k].size) for k in asked}
+                    scan.nearest_points_dev(n, stream, pts_t.data_ptr(), **{k: a for k, (_, a) in o.items()})
+                    return o
+                got = _two_calls(call, f"nearest n={n} {asked}")
+                for k in asked:
+                    t = got[k][0]
+                    _same(words(out[k]), words(want[k]), f"host route n={n} {asked}: {k} against the all-outputs call")
+                    _same(words(t[:want[k].size].cpu().numpy()), words(out[k]), f"n={n} {asked}: {k}, device route against host route")
+                    _guard_kept(t, want[k].size, f"nearest n={n} {asked} {k}")
+        torch.cuda.synchronize()
+        # refusals
+        INVALID, UNSUPPORTED = -1, -3
+        ws = scan.workspace()
+        a_t = torch.zeros(64, device=GPU)
+        a, h, s = C.c_void_p(a_t.data_ptr()), _lib.fptr(np.zeros(64, np.float32)), scan._h
+        before = _stats()
+        for args in ((None, 1, h), (s, 0, h), (s, -1, h), (s, 1, None)):
+            assert lib.bf_scan_nearest(*args, None, h, None) == INVALID and lib.bf_last_error() == b"bf_scan_nearest: bad argument", args
+        who = b"bf_scan_nearest_dev: "
+        for args, code, text in (((None, 1, a, None, a, None, ws._h, None), INVALID, b"bad argument"),
+                                 ((s, 1, None, None, a, None, ws._h, None), INVALID, b"bad argument"),
+                                 ((s, 1, a, None, a, None, None, None), INVALID, b"the workspace is NULL"),
+                                 ((s, 0, a, None, a, None, ws._h, None), INVALID, b"points must be positive"),
+                                 ((s, (1 << 28) + 1, a, None, a, None, ws._h, None), UNSUPPORTED, b"more than 268435456 points")):
+            assert lib.bf_scan_nearest_dev(*args) == code and lib.bf_last_error() == who + text, (args, lib.bf_last_error())
+        if torch.cuda.device_count() > 1:
+            far = N.Workspace(1)
+            assert lib.bf_scan_nearest_dev(s, 1, a, None, a, None, far._h, None) == INVALID
+            assert lib.bf_last_error() == who + b"the workspace lives on another device", lib.bf_last_error()
+            far.close()
+        else:
+            print("one GPU: a workspace of another device not tried")
+        assert _stats() == before, "a refused call was counted or allocated"
+        torch.cuda.synchronize()
+        searcher.close()
+        return {"ok": np.ones(1)}
+
+    _run(out_path, body)

@@ -72,3 +72,12 @@ def test_fallbacks_and_refusals(tmp_path, switched_off):
     route, the pointer check refuses NULL and host memory without leaving an error, and the *_dev calls refuse an SMPL-X model in
     bf_smpl_forward_dev, coefficients without directions, a NULL workspace and n = 0 before anything is queued"""
     _child(tmp_path, "fallbacks", switched_off)
+
+
+def test_smpl_forward_optional_outputs_on_both_routes(tmp_path):
+    """bf_smpl_forward / bf_smpl_forward_dev on the 690-vertex model at n = 1, 3, 15, 16 with each non-empty subset of (vertices,
+    joints, joints_ori): the bits of the host all-outputs call on both routes, the guard behind each device output whole, no
+    allocation on a second identical call; the host entry counts one host call, runs with all three outputs NULL and does not look
+    at the model's kind; both entries refuse NULL arguments, n = 0, a NULL workspace and (the device entry) an SMPL-X model with
+    their own messages and count nothing"""
+    _child(tmp_path, "smpl_forward_outputs")

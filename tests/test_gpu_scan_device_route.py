@@ -90,3 +90,11 @@ def test_fallbacks_and_refusals(tmp_path, switched_off):
     take the host route, and the *_dev entries refuse a NULL workspace, n = 0 and n beyond the limit before anything is queued and
     leave no HIP error behind"""
     _child(tmp_path, "fallbacks", switched_off)
+
+
+def test_nearest_optional_outputs_on_both_routes(tmp_path):
+    """bf_scan_nearest / bf_scan_nearest_dev at 1, 3, 4, 5 and 257 points with each non-empty subset of (face_ids, nearest, bary): the
+    all-outputs call's words, host and device route agreeing word for word, the guard behind each device output whole; the host
+    entry counts one host call; both entries refuse NULL arguments, n = 0, n beyond the limit and a NULL workspace with their own
+    messages and count nothing"""
+    _child(tmp_path, "nearest_outputs")
