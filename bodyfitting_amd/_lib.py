@@ -97,6 +97,9 @@ SIGNATURES = {
     "bf_smplx_vjp": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), C.POINTER(SmplxCotangents), C.POINTER(SmplxGrads)]),
     "bf_model_set_expression": (C.c_int, [_VP, C.c_int, _FP]),
     "bf_model_n_expression": (C.c_int, [_VP]),
+    "bf_model_set_shape_space": (C.c_int, [_VP, C.c_int, C.c_int, _FP]),
+    "bf_model_n_betas": (C.c_int, [_VP]),
+    "bf_model_shape_ext_wide": (C.c_int, [_VP]),
     "bf_smplx_forward_expr": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), _FP, C.POINTER(SmplxOutputs)]),
     "bf_smplx_vjp_expr": (C.c_int, [_VP, C.c_int, C.POINTER(SmplxParams), _FP, C.POINTER(SmplxCotangents), C.POINTER(SmplxGrads), _FP]),
     "bf_gmm_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.POINTER(_VP)]),

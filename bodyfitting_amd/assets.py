@@ -162,10 +162,52 @@ def gmm_buffers(gmm):
     return means, precisions, nll_weights.astype(np.float32)
 
 
-def get_device_model(model_type="smpl", gender="neutral", device=0, age="adult", kid_template_path=None):
-    """The HIP-resident model, created once per (type, gender, device) - (type, gender, device, 'kid') for a kid."""
+def shape_space_counts(model):
+    """(num_betas, num_expression_coeffs) of an SMPL-X model dict: "num_betas" (absent: 10) shape columns, expression behind them"""
+    nb = int(model.get("num_betas", 10))
+    return nb, int(np.asarray(model["shapedirs"]).shape[2]) - nb
+
+
+def shape_space_model(model_type, gender, num_betas, num_expression_coeffs):
+    """The SMPL-X model dict with exactly these counts: the registered (or loaded) one when it has them; that dict's columns sliced
+    when it holds at least as many of both; else the model file read again for them (model_files.load_smplx).  Nothing is clamped:
+    a source without the columns is a ValueError that says what it holds."""
+    base = get_model(model_type, gender)
+    nb0, ne0 = shape_space_counts(base)
+    nb, ne = int(num_betas), int(num_expression_coeffs)
+    if (nb, ne) == (nb0, ne0):
+        return base
+    if nb < 10 or ne < 0:
+        raise ValueError(f"num_betas={nb}, num_expression_coeffs={ne}: at least 10 betas and no negative count")
+    if nb <= nb0 and ne <= ne0:
+        sd = np.asarray(base["shapedirs"])
+        out = dict(base, shapedirs=np.ascontiguousarray(np.concatenate([sd[:, :, :nb], sd[:, :, nb0:nb0 + ne]], axis=2)))
+        out["num_betas"] = nb
+        return out
+    model = model_files.load(model_type, gender, num_betas=nb, num_expression_coeffs=ne)
+    if model is None:
+        raise ValueError(f"num_betas={nb}, num_expression_coeffs={ne}: the {model_type}/{gender} model at hand holds {nb0} shape and {ne0} "
+                         f"expression directions and there is no model file to read more from")
+    return model
+
+
+def get_device_model(model_type="smpl", gender="neutral", device=0, age="adult", kid_template_path=None, num_betas=None,
+                     num_expression_coeffs=None):
+    """The HIP-resident model, created once per (type, gender, device) - (type, gender, device, 'kid') for a kid.
+    num_betas / num_expression_coeffs (SMPL-X; None: the model's own): counts other than the model's own get a device model of their
+    own under (type, gender, device, 'space', num_betas, num_expression_coeffs), built from `shape_space_model`."""
     from .native import DeviceModel
     _check_age(model_type, age)
+    if num_betas is not None or num_expression_coeffs is not None:
+        if model_type != "smplx":
+            raise ValueError("num_betas / num_expression_coeffs: SMPL-X only (models.smpl.SMPL keeps the model's own betas)")
+        nb0, ne0 = shape_space_counts(get_model(model_type, gender))
+        nb, ne = nb0 if num_betas is None else int(num_betas), ne0 if num_expression_coeffs is None else int(num_expression_coeffs)
+        if (nb, ne) != (nb0, ne0):
+            key = (model_type, gender, int(device), "space", nb, ne)
+            if key not in _DEVICE_MODELS:
+                _DEVICE_MODELS[key] = DeviceModel(shape_space_model(model_type, gender, nb, ne), get_gmm(), device=device)
+            return _DEVICE_MODELS[key]
     key = (model_type, gender, int(device)) + (("kid",) if age == "kid" else ())
     if key not in _DEVICE_MODELS:
         _DEVICE_MODELS[key] = DeviceModel(get_model(model_type, gender, age, kid_template_path), get_gmm(), device=device)

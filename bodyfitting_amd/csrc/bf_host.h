@@ -301,10 +301,16 @@ struct bf_model {
     std::mutex lazy;              // guards the build-on-first-use tables (posedirsT, faces_d / adj)
     std::vector<int> faces_host;  // body-model topology (for the SMPL+D stage), optional
     DevBuf<int> faces_d, adj_start, adj;   // faces and the vertex -> (face, corner) lists, built on first use
-    // SMPL-X expression directions (bf_model_set_expression; n_expr = 0: none attached)
-    int n_expr = 0;
-    DevBuf<float> exprT;          // [n_expr][3][nv]: E transposed, a coefficient's component contiguous over the vertices
-    DevBuf<float> Jx;             // [nj*3][n_expr]   J_regressor E
+    // SMPL-X extension directions: the expression directions (bf_model_set_expression), or a shape space's directions from the eleventh
+    // beta on followed by its expression directions (bf_model_set_shape_space).  n_ext = 0: none attached
+    int n_expr = 0;               // expression coefficients of a call
+    int nb_total = 0;             // betas of a call (0: nb - no shape space attached)
+    int n_ext = 0;                // directions attached = (nb_total - nb) + n_expr: a frame's extension coefficients are [betas[nb:], expression]
+    bool ext_wide = false;        // the kernels of shape_ext_kernels.hip serve them (n_ext > BF_EXPR_MAX, or BF_SHAPE_EXT_WIDE=1 at the attachment)
+    DevBuf<float> exprT;          // [n_ext][3][nv]: E transposed, a coefficient's component contiguous over the vertices
+    DevBuf<float> Jx;             // [nj*3][n_ext]   J_regressor E
+    DevBuf<float> extVK;          // (ext_wide) [nv][3][n_ext]: E as it arrives, a vertex component's coefficients contiguous - the wide reverse
+    DevBuf<float> JxT;            // (ext_wide) [n_ext][nj*3]: Jx transposed - the wide chain delta
     std::vector<int> jreg_start, jreg_v;   // the J_regressor's non-zero weights per joint (CSR), kept on the host for Jx (SMPL-X-kind models)
     std::vector<float> jreg_w;
 };

@@ -29,6 +29,9 @@
 #define BF_GRAD_MAX_NP 128      // packed parameters per frame of the pose assembly (SMPL-X: 98)
 #define BF_GRAD_MAX_JOINTS 64   // chain joints: one lane each in the chain kernel's single wave (SMPL: 24, SMPL-X: 55)
 #define BF_EXPR_MAX 16          // expression coefficients (SMPL-X: 10): the LDS tables and register rows of expr_kernels.hip; bf_model_set_expression refuses more
+#define BF_SHAPE_EXT_MAX 390    // extension directions of a shape space (bf_model_set_shape_space: 290 betas behind the tenth + 100 expression): the LDS
+                                // tables of shape_ext_kernels.hip, which serve a model with more than BF_EXPR_MAX of them
+#define BF_EXT_FB 8             // frames one workgroup of the wide vertex delta / reverse walks the directions for (their sums stay in registers)
 // LDS tables of the stand-alone keypoint loss (kp_loss_kernels.hip); bf_kp_loss_check (kp_loss_api.hip) refuses a call beyond them
 #define BF_KPL_MAX_ROWS 256     // joint rows of a problem (SMPL: 25, SMPL-X with hands + face: 135)
 #define BF_KPL_MAX_DIM 128      // dimension of the GMM prior (69)

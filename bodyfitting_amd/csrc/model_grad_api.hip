@@ -14,6 +14,10 @@
 // kernels of expr_kernels.hip go around those passes, which stay as they are: bf_expr_chain_kernel between the pose state and the mesh
 // pass, bf_expr_vertex_kernel between the mesh and the joints pass, bf_expr_reverse_kernel + bf_ext_reduce_kernel in front of the chain
 // reverse, which takes Jx psi into its rest joints and closes dexpression.  Without coefficients the launch sequence is the one above.
+// A shape space (bf_model_set_shape_space: betas beyond the tenth, up to 100 expression coefficients) rides the same way: the model's
+// passes see the ten core betas, and a frame's extension coefficients [betas[10:], expression] take expression's place.
+// bf_shape_ext_pack_kernel cuts the caller's rows into those two blocks, bf_shape_ext_join_kernel puts the two gradients back into rows
+// for deliver_blocks; up to BF_EXPR_MAX directions run on expr_kernels.hip's kernels, more (bf_model::ext_wide) on shape_ext_kernels.hip's.
 // Stateless: nothing stays on the device between calls but the model's lazily built posedirsT.
 // Every operation is ONE body on a BfRouteCall (dev_route.h); its host entry point and its *_dev twin check their arguments, count
 // their route and hand the body their call.  The launches, their order, grids and arguments are the same on both routes; what differs
@@ -25,6 +29,7 @@
 #include "mesh_kernels.h"
 #include "model_grad_kernels.h"
 #include "expr_kernels.h"
+#include "shape_ext_kernels.h"
 #include "scan_kernels.h"
 
 
@@ -51,7 +56,7 @@ struct ModelPass {
     float *state = nullptr, *vraw = nullptr, *vposed = nullptr, *xpart = nullptr, *joints = nullptr, *jraw = nullptr, *lmk_w = nullptr;
     float *dv = nullptr, *dchain = nullptr, *part = nullptr, *ext = nullptr, *dtheta = nullptr, *dbeta = nullptr;
     float *dJx = nullptr, *epart = nullptr, *emesh = nullptr, *dexpr = nullptr;         // with expression coefficients only (expr_kernels.hip)
-    const float *expr = nullptr;                    // the coefficients [n][n_expr] on the device: set by a forward that was given them
+    const float *expr = nullptr;                    // the extension coefficients [n][n_ext] on the device: set by a forward that was given them
     int *lmk_vid = nullptr;
     ModelPass(bf_model *model, int frames, BfRouteCall &call) : m(model), n(frames), c(call) {}
 
@@ -96,13 +101,20 @@ struct ModelPass {
             mesh.joints = joints; mesh.jraw = jraw; mesh.lmk_vid = lmk_vid; mesh.lmk_w = lmk_w;
             return launch_mesh(mesh);
         }
-        const int ne = m->n_expr;
+        const int ne = m->n_ext, fblocks = (n + BF_EXT_FB - 1) / BF_EXT_FB;
         BF_TRY(need(dJx, N * m->nj * 3));
-        hipLaunchKernelGGL(bf_expr_chain_kernel, dim3(n), dim3(64), 0, c.stream, m->fit, state, expr, ne, (const float *)m->Jx.p, dJx);
+        if (m->ext_wide)
+            hipLaunchKernelGGL(bf_shape_ext_chain_kernel, dim3(n), dim3(256), 0, c.stream, m->fit, state, expr, ne, (const float *)m->JxT.p, dJx);
+        else
+            hipLaunchKernelGGL(bf_expr_chain_kernel, dim3(n), dim3(64), 0, c.stream, m->fit, state, expr, ne, (const float *)m->Jx.p, dJx);
         HIP_TRY(hipGetLastError());
         BF_TRY(launch_mesh(mesh));                             // (no joints asked for: the mesh pass alone)
-        hipLaunchKernelGGL(bf_expr_vertex_kernel, dim3((m->nv + 255) / 256, n), dim3(256), 0, c.stream, m->mesh, (const float *)state, expr, ne,
-                           (const float *)m->exprT.p, vraw, vposed);
+        if (m->ext_wide)
+            hipLaunchKernelGGL(bf_shape_ext_vertex_kernel, dim3((m->nv + 255) / 256, fblocks), dim3(256), 0, c.stream, m->mesh, (const float *)state,
+                               expr, ne, n, (const float *)m->exprT.p, vraw, vposed);
+        else
+            hipLaunchKernelGGL(bf_expr_vertex_kernel, dim3((m->nv + 255) / 256, n), dim3(256), 0, c.stream, m->mesh, (const float *)state, expr, ne,
+                               (const float *)m->exprT.p, vraw, vposed);
         HIP_TRY(hipGetLastError());
         if (m->n_extra > 0) {                                     // the extra-regressor joints' per-tile sums, from the updated vertices
             hipLaunchKernelGGL(bf_expr_xpart_kernel, dim3(m->mesh.n_tiles, n), dim3(128), 0, c.stream, m->mesh, (const float *)vraw, xpart);
@@ -141,14 +153,18 @@ struct ModelPass {
                            (const float *)part, rows, EXT, ext, EXT, (int *)nullptr, 0);
         HIP_TRY(hipGetLastError());
         // (with expression coefficients whose gradient is wanted) E_v^T (sum_j w_vj GR_j^T dv_v) per 256-vertex tile, the tiles in tile order
-        const int ne = expr ? m->n_expr : 0, etiles = (nv + 255) / 256;
+        const int ne = expr ? m->n_ext : 0, etiles = (nv + 255) / 256;
         const bool dex = expr && want_dexpr;
         if (dex) {
             BF_TRY(need(epart, N * etiles * ne));
             BF_TRY(need(emesh, N * ne));
             BF_TRY(need(dexpr, N * ne, to.dexpr));
-            hipLaunchKernelGGL(bf_expr_reverse_kernel, dim3(etiles, n), dim3(256), 0, c.stream, m->mesh, (const float *)state, (const float *)dv, ne,
-                               (const float *)m->exprT.p, epart);
+            if (m->ext_wide)
+                hipLaunchKernelGGL(bf_shape_ext_reverse_kernel, dim3(etiles, (n + BF_EXT_FB - 1) / BF_EXT_FB), dim3(256), 0, c.stream, m->mesh,
+                                   (const float *)state, (const float *)dv, ne, n, (const float *)m->extVK.p, epart);
+            else
+                hipLaunchKernelGGL(bf_expr_reverse_kernel, dim3(etiles, n), dim3(256), 0, c.stream, m->mesh, (const float *)state, (const float *)dv, ne,
+                                   (const float *)m->exprT.p, epart);
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(bf_ext_reduce_kernel, dim3((ne + BF_RED_COLS - 1) / BF_RED_COLS, n), dim3(8 * BF_RED_COLS), 0, c.stream,
                                (const float *)epart, etiles, ne, emesh, ne, (int *)nullptr, 0);
@@ -166,13 +182,16 @@ struct ModelPass {
 // rows[n][stride] on the device -> per block (dst, off, cnt), dst[n][cnt] = rows[.][off .. off + cnt) (null dst: not wanted), and the
 // call finished: the host route drains, fetches the rows once and cuts them on the host; the device route cuts them with one launch
 struct Block { float *dst; int off, cnt; };
-int deliver_blocks(BfRouteCall &c, const float *rows, size_t N, int stride, std::initializer_list<Block> blocks) {
+// the betas a call takes: the shape space's when one is attached, else the model's own
+int bf_nb_total(const bf_model *m) { return m->nb_total ? m->nb_total : m->nb; }
+// last = false: more kernels follow - nothing is finished; the host route's copy waits for the NULL stream's work as every hipMemcpy does
+int deliver_blocks(BfRouteCall &c, const float *rows, size_t N, int stride, std::initializer_list<Block> blocks, bool last = true) {
     BfScatter S{};
     for (const Block &b : blocks)
         if (b.dst && b.cnt > 0) { S.dst[S.n_blocks] = b.dst; S.off[S.n_blocks] = b.off; S.cnt[S.n_blocks] = b.cnt; ++S.n_blocks; }
     if (c.ws && S.n_blocks > 0)
         hipLaunchKernelGGL(bf_block_scatter_kernel, dim3((unsigned)((N * stride + 255) / 256)), dim3(256), 0, c.stream, rows, (int)N, stride, S);
-    BF_TRY(c.finish());
+    if (last) BF_TRY(c.finish());
     if (c.ws || S.n_blocks == 0) return BF_OK;
     std::vector<float> g(N * stride);
     HIP_TRY(hipMemcpy(g.data(), rows, g.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -190,11 +209,12 @@ int ensure_posedirsT(bf_model *m, hipStream_t stream) {
 // SMPL-X: the parameter blocks where the kernels read them and the thetas assembled from them
 struct Inputs {
     const float *beta = nullptr, *orient = nullptr, *body = nullptr, *jaw = nullptr, *leye = nullptr, *reye = nullptr, *lh = nullptr, *rh = nullptr;
+    const float *ext = nullptr;             // the extension coefficients [n][n_ext], or null: none - the launches of a call without expression
     float *full = nullptr, *th_root = nullptr, *th_rest = nullptr;
-    // full_to: the caller's full_pose array, or null
-    int bind(BfRouteCall &c, const bf_model *m, size_t N, const bf_smplx_params *in, float *full_to) {
-        const int n_pca = m->fit.n_pca, nj = m->nj;
-        BF_TRY(c.in(in->betas, N * m->nb, beta));
+    // full_to: the caller's full_pose array, or null.  expression: the caller's [n][n_expr], or null
+    int bind(BfRouteCall &c, const bf_model *m, size_t N, const bf_smplx_params *in, const float *expression, float *full_to) {
+        const int n_pca = m->fit.n_pca, nj = m->nj, nbt = bf_nb_total(m);
+        BF_TRY(c.in(in->betas, N * nbt, beta));
         BF_TRY(c.in(in->global_orient, N * 3, orient));
         BF_TRY(c.in(in->body_pose, N * m->fit.nbp, body));
         BF_TRY(c.in(in->jaw_pose, N * 3, jaw));
@@ -208,6 +228,15 @@ struct Inputs {
         hipLaunchKernelGGL(bf_smplx_pose_assemble_kernel, dim3((unsigned)N), dim3(64), 0, c.stream, m->fit, orient, body, jaw, leye, reye, lh, rh,
                            full, th_root, th_rest);
         HIP_TRY(hipGetLastError());
+        BF_TRY(c.in(expression, N * m->n_expr, ext));
+        if (nbt > m->nb) {                  // a shape space: the caller's rows cut into the core block and [betas[nb:], expression]
+            float *core = nullptr, *e = nullptr;
+            BF_TRY(c.scratch(N * m->nb, core));
+            BF_TRY(c.scratch(N * m->n_ext, e));
+            hipLaunchKernelGGL(bf_shape_ext_pack_kernel, dim3((unsigned)N), dim3(64), 0, c.stream, beta, ext, nbt, m->n_expr, m->nb, core, e);
+            HIP_TRY(hipGetLastError());
+            beta = core; ext = e;
+        }
         return BF_OK;
     }
 };
@@ -263,14 +292,12 @@ int smplx_forward(BfRouteCall &c, bf_model *m, int n, const bf_smplx_params *in,
     BF_TRY(c.begin(m->device));
     const size_t N = (size_t)n;
     Inputs x;
-    const float *d_expr = nullptr;
     int *d_row = nullptr;
-    BF_TRY(x.bind(c, m, N, in, out->full_pose));
-    BF_TRY(c.in(expression, N * m->n_expr, d_expr));
+    BF_TRY(x.bind(c, m, N, in, expression, out->full_pose));
     BF_TRY(c.out((int *)out->dyn_row, N, d_row, true));
     ModelPass pass(m, n, c);
     pass.to.vraw = out->vertices; pass.to.joints = out->joints; pass.to.jraw = out->joints_all;
-    BF_TRY(pass.forward(x.beta, x.th_root, x.th_rest, false, d_expr));
+    BF_TRY(pass.forward(x.beta, x.th_root, x.th_rest, false, x.ext));
     hipLaunchKernelGGL(bf_smplx_dyn_row_kernel, dim3((n + 63) / 64), dim3(64), 0, c.stream, m->mesh, (const float *)pass.state, n, d_row);
     return c.finish();
 }
@@ -282,19 +309,29 @@ int smplx_vjp(BfRouteCall &c, bf_model *m, int n, const bf_smplx_params *in, con
     const int nj = m->nj, n_pca = m->fit.n_pca, nbp = m->fit.nbp, OUT = 3 * nj + 2 * n_pca;
     const size_t N = (size_t)n;
     Inputs x;
-    const float *d_expr = nullptr, *d_dvert = nullptr, *d_dj = nullptr, *d_dja = nullptr, *d_dfull = nullptr;
+    const float *d_dvert = nullptr, *d_dj = nullptr, *d_dja = nullptr, *d_dfull = nullptr;
     float *d_out = nullptr;
-    BF_TRY(x.bind(c, m, N, in, nullptr));
-    BF_TRY(c.in(expression, N * m->n_expr, d_expr));
+    BF_TRY(x.bind(c, m, N, in, expression, nullptr));
     BF_TRY(c.in(cot->dvertices, N * m->nv * 3, d_dvert));
     BF_TRY(c.in(cot->djoints, N * m->n_joint_map * 3, d_dj));
     BF_TRY(c.in(cot->djoints_all, N * m->n_all * 3, d_dja));
     BF_TRY(c.in(cot->dfull_pose, N * 3 * nj, d_dfull));
     BF_TRY(c.scratch(N * OUT, d_out));
     ModelPass pass(m, n, c);
-    pass.to.dbeta = grads->dbetas; pass.to.dexpr = dexpression;
-    BF_TRY(pass.forward(x.beta, x.th_root, x.th_rest, true, d_expr));
-    BF_TRY(pass.reverse(d_dvert, d_dj, d_dja, m->n_all, dexpression != nullptr));
+    // (a shape space: dbetas[n][NB] = the core gradient | the head of the extension's, dexpression its tail - joined into rows below)
+    const int nbt = bf_nb_total(m);
+    const bool space = nbt > m->nb;
+    if (!space) { pass.to.dbeta = grads->dbetas; pass.to.dexpr = dexpression; }
+    BF_TRY(pass.forward(x.beta, x.th_root, x.th_rest, true, x.ext));
+    BF_TRY(pass.reverse(d_dvert, d_dj, d_dja, m->n_all, space ? grads->dbetas || dexpression : dexpression != nullptr));
+    if (space && (grads->dbetas || dexpression)) {
+        float *rows = nullptr;
+        BF_TRY(c.scratch(N * (nbt + m->n_expr), rows));
+        hipLaunchKernelGGL(bf_shape_ext_join_kernel, dim3(n), dim3(64), 0, c.stream, (const float *)pass.dbeta, (const float *)pass.dexpr, m->nb,
+                           m->n_ext, rows);
+        HIP_TRY(hipGetLastError());
+        BF_TRY(deliver_blocks(c, rows, N, nbt + m->n_expr, {{grads->dbetas, 0, nbt}, {dexpression, nbt, m->n_expr}}, false));
+    }
     // the pose assembly reversed
     hipLaunchKernelGGL(bf_smplx_pose_reverse_kernel, dim3(n), dim3(64), 0, c.stream, m->fit, (const float *)pass.dtheta, d_dfull, d_out);
     HIP_TRY(hipGetLastError());
@@ -367,20 +404,18 @@ extern "C" int bf_smpl_forward_dev(bf_model *m, bf_workspace *ws, void *stream, 
 
 extern "C" int bf_model_n_expression(const bf_model *m) { return m ? m->n_expr : 0; }
 
-extern "C" int bf_model_set_expression(bf_model *m, int n_expr, const float *exprdirs) {
-    if (!m || !exprdirs) return fail(BF_ERR_INVALID, "bf_model_set_expression: bad argument");
-    BF_TRY(bf_grad_check(m, 1, "bf_model_set_expression"));
-    if (n_expr < 1 || n_expr > BF_EXPR_MAX)
-        return fail(BF_ERR_UNSUPPORTED, "bf_model_set_expression: 1.." + std::to_string(BF_EXPR_MAX) + " expression coefficients supported");
-    std::lock_guard<std::mutex> g(m->lazy);
-    if (m->n_expr != 0) return fail(BF_ERR_INVALID, "bf_model_set_expression: the model has its expression directions already");
+// dirs[NV][3][L] onto the model as its extension directions: the transposed copy, Jx, and for the wide kernels the second layout and
+// Jx transposed.  The caller holds m->lazy and has checked the counts; the model counts no directions unless every upload succeeded.
+static int bf_attach_directions(bf_model *m, int nb_total, int n_expr, int L, const float *dirs) {
     HIP_TRY(hipSetDevice(m->device));
-    const int nv = m->nv, nj = m->nj, ne = n_expr;
+    const int nv = m->nv, nj = m->nj, ne = L;
+    const char *sw = getenv("BF_SHAPE_EXT_WIDE");
+    const bool wide = L > BF_EXPR_MAX || (sw && sw[0] == '1' && sw[1] == 0);
     // E transposed: [l][k][v]
     std::vector<float> eT((size_t)ne * 3 * nv);
     for (int v = 0; v < nv; ++v)
         for (int k = 0; k < 3; ++k)
-            for (int l = 0; l < ne; ++l) eT[((size_t)l * 3 + k) * nv + v] = exprdirs[((size_t)v * 3 + k) * ne + l];
+            for (int l = 0; l < ne; ++l) eT[((size_t)l * 3 + k) * nv + v] = dirs[((size_t)v * 3 + k) * ne + l];
     // Jx = J_regressor E: float64 accumulation over a joint's non-zero weights in vertex order, rounded once (as contract_regressor forms Jd)
     std::vector<float> jx((size_t)nj * 3 * ne);
     std::vector<double> acc((size_t)3 * ne);
@@ -388,15 +423,50 @@ extern "C" int bf_model_set_expression(bf_model *m, int n_expr, const float *exp
         std::fill(acc.begin(), acc.end(), 0.0);
         for (int q = m->jreg_start[j]; q < m->jreg_start[j + 1]; ++q) {
             const double w = m->jreg_w[q];
-            const float *e = exprdirs + (size_t)m->jreg_v[q] * 3 * ne;
+            const float *e = dirs + (size_t)m->jreg_v[q] * 3 * ne;
             for (int i = 0; i < 3 * ne; ++i) acc[i] += w * e[i];
         }
         for (int i = 0; i < 3 * ne; ++i) jx[(size_t)j * 3 * ne + i] = (float)acc[i];
     }
     HIP_TRY(m->exprT.upload(eT));
     HIP_TRY(m->Jx.upload(jx));
-    m->n_expr = ne;
+    if (wide) {
+        std::vector<float> jxT((size_t)ne * nj * 3);
+        for (int r = 0; r < nj * 3; ++r)
+            for (int l = 0; l < ne; ++l) jxT[(size_t)l * nj * 3 + r] = jx[(size_t)r * ne + l];
+        HIP_TRY(m->JxT.upload(jxT));
+        HIP_TRY(m->extVK.upload(std::vector<float>(dirs, dirs + (size_t)nv * 3 * ne)));
+    }
+    m->n_expr = n_expr;
+    m->nb_total = nb_total;
+    m->ext_wide = wide;
+    m->n_ext = L;
     return BF_OK;
+}
+
+extern "C" int bf_model_set_expression(bf_model *m, int n_expr, const float *exprdirs) {
+    if (!m || !exprdirs) return fail(BF_ERR_INVALID, "bf_model_set_expression: bad argument");
+    BF_TRY(bf_grad_check(m, 1, "bf_model_set_expression"));
+    if (n_expr < 1 || n_expr > BF_EXPR_MAX)
+        return fail(BF_ERR_UNSUPPORTED, "bf_model_set_expression: 1.." + std::to_string(BF_EXPR_MAX) + " expression coefficients supported");
+    std::lock_guard<std::mutex> g(m->lazy);
+    if (m->n_ext != 0) return fail(BF_ERR_INVALID, "bf_model_set_expression: the model has its expression directions already");
+    return bf_attach_directions(m, 0, n_expr, n_expr, exprdirs);
+}
+
+extern "C" int bf_model_n_betas(const bf_model *m) { return m ? bf_nb_total(m) : 0; }
+extern "C" int bf_model_shape_ext_wide(const bf_model *m) { return m && m->ext_wide ? 1 : 0; }
+
+extern "C" int bf_model_set_shape_space(bf_model *m, int n_betas, int n_expr, const float *dirs) {
+    if (!m || !dirs) return fail(BF_ERR_INVALID, "bf_model_set_shape_space: bad argument");
+    BF_TRY(bf_grad_check(m, 1, "bf_model_set_shape_space"));
+    const int L = n_betas - m->nb + n_expr;
+    if (n_betas < 10 || n_betas > 300 || n_betas < m->nb || n_expr < 0 || n_expr > 100 || L < 1 || L > BF_SHAPE_EXT_MAX)
+        return fail(BF_ERR_UNSUPPORTED, "bf_model_set_shape_space: 10..300 betas and 0..100 expression coefficients supported, at least one "
+                                        "direction beyond the model's " + std::to_string(m->nb) + " betas");
+    std::lock_guard<std::mutex> g(m->lazy);
+    if (m->n_ext != 0) return fail(BF_ERR_INVALID, "bf_model_set_shape_space: the model has its shape space or expression directions already");
+    return bf_attach_directions(m, n_betas, n_expr, L, dirs);
 }
 
 extern "C" int bf_smplx_forward(bf_model *m, int n, const bf_smplx_params *in, const bf_smplx_outputs *out) {

@@ -245,12 +245,14 @@ bf_smpl_vjp_chain_kernel(FitTab T, const float *__restrict__ state, const float 
         for (int r = 0; r < nj * 3; ++r) acc += T.Jd[r * nb + tid] * s_dJ[r];
         dbeta[(size_t)f * nb + tid] = row[npf + nj * 12 + tid] + acc;
     }
-    // dexpression = the expression reverse's vertex part + Jx^T dJ (J rows ascending)
-    if (dexpr && tid < ne) {
-        float acc = 0.f;
-        for (int r = 0; r < nj * 3; ++r) acc += Jx[r * ne + tid] * s_dJ[r];
-        dexpr[(size_t)f * ne + tid] = dexpr_mesh[(size_t)f * ne + tid] + acc;
-    }
+    // dexpression = the expression reverse's vertex part + Jx^T dJ (J rows ascending); a lane walks the coefficients tid, tid + 64, ..:
+    // a shape space (bf_model_set_shape_space) brings up to BF_SHAPE_EXT_MAX of them
+    if (dexpr)
+        for (int l = tid; l < ne; l += 64) {
+            float acc = 0.f;
+            for (int r = 0; r < nj * 3; ++r) acc += Jx[r * ne + l] * s_dJ[r];
+            dexpr[(size_t)f * ne + l] = dexpr_mesh[(size_t)f * ne + l] + acc;
+        }
 }
 
 // ---- the SMPL-X specific ends: what bf_smplx_forward / bf_smplx_vjp put before and behind the passes above

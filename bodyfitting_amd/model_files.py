@@ -114,19 +114,30 @@ def load_smpl(path, extra_regressor=None, h36m_regressor=None, vertex_ids=None):
     return m
 
 
-def load_smplx(path, vertex_ids=None, use_face_contour=True):
-    """`SMPLX_{GENDER}.npz` (or .pkl) -> model dict, with the options smplify.py:60-80 passes to smplx.create."""
+def load_smplx(path, vertex_ids=None, use_face_contour=True, num_betas=N_BETAS, num_expression_coeffs=N_EXPRESSION):
+    """`SMPLX_{GENDER}.npz` (or .pkl) -> model dict, with the options smplify.py:60-80 passes to smplx.create.
+    num_betas / num_expression_coeffs: smplx.create's - the dict's shapedirs are the file's shape columns `:num_betas` followed by
+    its expression columns (`300:300 + ne` of a v1.1 file's 400, `10:10 + ne` of a v1.0 file's 20), and "num_betas" says where the
+    one group ends.  A file without the columns asked for is a ValueError: nothing is clamped."""
     d = _read(path)
     m = _common(d, "smplx", vertex_ids)
     shapedirs = _dense(d["shapedirs"])
     n = shapedirs.shape[2]
+    nb, ne = int(num_betas), int(num_expression_coeffs)
+    if nb < N_BETAS or ne < 0:
+        raise ValueError(f"num_betas={nb}, num_expression_coeffs={ne}: at least {N_BETAS} betas and no negative count")
     if n >= 300 + N_EXPRESSION:                      # v1.1: 300 shape + 100 expression directions
-        expr = shapedirs[:, :, 300:300 + N_EXPRESSION]
+        n_shape, e0 = 300, 300
     elif n >= N_BETAS + N_EXPRESSION:                # v1.0: 10 + 10
-        expr = shapedirs[:, :, N_BETAS:N_BETAS + N_EXPRESSION]
+        n_shape, e0 = N_BETAS, N_BETAS
     else:
         raise ValueError(f"SMPL-X shapedirs with {n} columns: need the shape and the expression directions")
-    m["shapedirs"] = np.ascontiguousarray(np.concatenate([shapedirs[:, :, :N_BETAS], expr], axis=2))
+    if nb > n_shape or e0 + ne > n:
+        raise ValueError(f"{path}: num_betas={nb}, num_expression_coeffs={ne} asked of a file that holds {n} shapedirs columns = "
+                         f"{n_shape} shape and {n - e0} expression directions")
+    m["shapedirs"] = np.ascontiguousarray(np.concatenate([shapedirs[:, :, :nb], shapedirs[:, :, e0:e0 + ne]], axis=2))
+    if nb != N_BETAS:
+        m["num_betas"] = nb                          # (absent: 10 - what every dict without the key means)
     m["left_hand_components"] = _dense(d["hands_componentsl"])[:N_HAND_PCA].copy()
     m["right_hand_components"] = _dense(d["hands_componentsr"])[:N_HAND_PCA].copy()
     nj = m["lbs_weights"].shape[1]
@@ -206,8 +217,8 @@ def find(model_type, gender, folder="data"):
     return None
 
 
-def load(model_type, gender, folder="data", vertex_ids=None):
-    """-> model dict, or None when the folder has no such file."""
+def load(model_type, gender, folder="data", vertex_ids=None, num_betas=N_BETAS, num_expression_coeffs=N_EXPRESSION):
+    """-> model dict, or None when the folder has no such file.  num_betas / num_expression_coeffs: SMPL-X only (load_smplx)."""
     path = find(model_type, gender, folder)
     if path is None:
         return None
@@ -216,4 +227,4 @@ def load(model_type, gender, folder="data", vertex_ids=None):
         if not os.path.exists(extra):
             raise FileNotFoundError(f"{extra}: models.smpl.SMPL needs it next to the model (config.py:1, models/smpl.py:62)")
         return load_smpl(path, extra, h36m if os.path.exists(h36m) else None, vertex_ids)
-    return load_smplx(path, vertex_ids)
+    return load_smplx(path, vertex_ids, num_betas=num_betas, num_expression_coeffs=num_expression_coeffs)

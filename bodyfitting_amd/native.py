@@ -58,9 +58,13 @@ def model_desc(model, gmm):
     model_type = model.get("model_type", "smpl")
     means, prec, nllw = gmm_buffers(gmm) if isinstance(gmm, dict) else gmm
     smplx = model_type == "smplx"
-    # SMPL-X: the 10 shape directions go into the descriptor; the columns behind them are the expression directions, which
-    # DeviceModel attaches apart (bf_model_set_expression) - the fit never optimises expression
+    # SMPL-X: the 10 core shape directions go into the descriptor; the columns behind them - shape directions from the eleventh to
+    # the dict's "num_betas" (absent: 10), then the expression directions - are attached apart by DeviceModel
+    # (bf_model_set_expression / bf_model_set_shape_space): the fit optimises the ten core betas and nothing else
     n_betas = 10 if smplx else np.asarray(model["shapedirs"]).shape[2]
+    num_betas = int(model.get("num_betas", 10)) if smplx else n_betas
+    if smplx and not 10 <= num_betas <= np.asarray(model["shapedirs"]).shape[2]:
+        raise ValueError(f"num_betas={num_betas}: an SMPL-X model dict holds 10 .. shapedirs.shape[2] = {np.asarray(model['shapedirs']).shape[2]} shape directions")
     if "J_regressor_extra" not in model:
         model = dict(model, J_regressor_extra=np.zeros((0, np.asarray(model["v_template"]).shape[0]), np.float32))
     keep = {
@@ -73,7 +77,8 @@ def model_desc(model, gmm):
     }
     info = {"model_type": model_type}
     info["n_verts"], info["n_joints"] = keep["lbs_weights"].shape
-    info["n_betas"] = keep["shapedirs"].shape[2]
+    info["n_betas"] = keep["shapedirs"].shape[2]           # the descriptor's: what the fit and the packed parameter vector carry
+    info["num_betas"] = num_betas                          # what the stand-alone smplx calls take (DeviceModel.n_betas)
     info["n_selector"] = len(keep["selector_ids"])
     info["n_joint_map"] = len(keep["joint_map"])
     info["faces"] = _i32(model["faces"]) if "faces" in model else None
@@ -179,7 +184,9 @@ def _close_workspace(obj):
 class DeviceModel:
     """Body model + GMM prior uploaded once to one GPU (replaces the per-frame construction at
     reference smplify/body_fitting.py:82 -> smplify/smplify.py:46-56).  An SMPL-X model dict whose shapedirs has more than
-    10 columns brings its expression directions (columns 10:), n_expression of them; 0 otherwise."""
+    10 columns brings its expression directions (columns 10:), n_expression of them; 0 otherwise.  A dict with "num_betas" > 10 has
+    that many shape directions in front of them: `n_betas` is then that total - the width of forward_smplx's / vjp_smplx's betas -
+    while the fit and the packed parameter vector keep the first `n_core_betas` = 10."""
 
     dtype = np.float32          # what the kernels compute in
 
@@ -190,9 +197,17 @@ class DeviceModel:
         self.__dict__.update(info)
         self._h = C.c_void_p()
         _lib.check(lib.bf_model_create(C.byref(d), int(device), C.byref(self._h)), "bf_model_create")
-        if "exprdirs" in keep:              # an SMPL-X model dict whose shapedirs has more than 10 columns: columns 10: are its expression directions
-            _lib.check(lib.bf_model_set_expression(self._h, keep["exprdirs"].shape[2], _lib.fptr(keep["exprdirs"])), "bf_model_set_expression")
+        self.n_core_betas = self.n_betas
+        if "exprdirs" in keep:              # an SMPL-X model dict whose shapedirs has more than 10 columns: the shape directions from the eleventh on, then the expression directions
+            n_ext = keep["exprdirs"].shape[2]
+            n_expr = n_ext - (self.num_betas - self.n_core_betas)
+            if self.num_betas == self.n_core_betas and n_expr <= 16:
+                _lib.check(lib.bf_model_set_expression(self._h, n_expr, _lib.fptr(keep["exprdirs"])), "bf_model_set_expression")
+            else:
+                _lib.check(lib.bf_model_set_shape_space(self._h, self.num_betas, n_expr, _lib.fptr(keep["exprdirs"])), "bf_model_set_shape_space")
         self.n_expression = lib.bf_model_n_expression(self._h)
+        self.n_betas = lib.bf_model_n_betas(self._h)
+        self.shape_ext_wide = bool(lib.bf_model_shape_ext_wide(self._h))       # the directions run on shape_ext_kernels.hip
         del keep
         self.device = int(device)
         self.n_params = lib.bf_model_n_params(self._h)
@@ -1003,7 +1018,7 @@ class FrameBatch:
         _lib.check(self._lib.bf_batch_set_keypoints(self._h, _lib.fptr(kp), _lib.iptr(nd)), "bf_batch_set_keypoints")
 
     def set_init(self, init_betas, init_pose):
-        b = _f32(init_betas, (self.F, self.model.n_betas))
+        b = _f32(init_betas, (self.F, self.model.n_core_betas))
         p = _f32(np.asarray(init_pose).reshape(self.F, -1)[:, :72], (self.F, 72))
         _lib.check(self._lib.bf_batch_set_init(self._h, _lib.fptr(b), _lib.fptr(p)), "bf_batch_set_init")
 
@@ -1012,13 +1027,13 @@ class FrameBatch:
         fit() must carry FIT_RESET.  Arrays that already are C-contiguous float32 / int32 of the right size are passed as they are, by
         address (the frame loop's case: the call costs what the library does); everything else - lists, other dtypes, strided views, a
         scalar n_use_frames, poses wider than 72 - is converted first."""
-        at = stage_addresses(self.F, self._n_kp, self.model.n_betas, keypoints, n_use_frames, init_betas, init_pose)
+        at = stage_addresses(self.F, self._n_kp, self.model.n_core_betas, keypoints, n_use_frames, init_betas, init_pose)
         if at is not None:
             _lib.check(self._stage_by_address(self._h, at[0], at[1], at[2], at[3]), "bf_batch_stage_inputs")
             return
         kp = _f32(keypoints, (self.F, self.V, self.model.n_loss_joints, 3))
         nd = None if n_use_frames is None else _i32(np.broadcast_to(np.asarray(n_use_frames), (self.F,)))
-        b = _f32(init_betas, (self.F, self.model.n_betas))
+        b = _f32(init_betas, (self.F, self.model.n_core_betas))
         p = _f32(np.asarray(init_pose).reshape(self.F, -1)[:, :72], (self.F, 72))
         _lib.check(self._lib.bf_batch_stage_inputs(self._h, _lib.fptr(kp), _lib.iptr(nd), _lib.fptr(b), _lib.fptr(p)), "bf_batch_stage_inputs")
 

@@ -14,6 +14,11 @@ Two paths, as `bodyfitting_amd.smpl.SMPL` has them:
   _autograd.py) - an argument not passed is a NULL pointer there, and `dyn_row` is then an int32 tensor on that GPU, not read
   back; everything else goes through host memory.
 
+`num_betas` (10 .. 300) and `num_expression_coeffs` (0 .. 100) are smplx.create's: other counts than the registered model's own get
+a device model of their own (`assets.get_device_model(..., num_betas=, num_expression_coeffs=)`: the registered dict's columns when
+it holds them, else the model file's), `betas` is then [B, num_betas] and `expression` [B, num_expression_coeffs].  The betas beyond
+the tenth ride with the expression coefficients around the model's passes (bf_model_set_shape_space).
+
 `expression` [B, n_expression] is an input of its own on a device model with expression directions (a model file's shapedirs
 columns behind the 10 shape directions, `DeviceModel.n_expression` of them): zero or not, it goes through the device and, as a
 tensor that requires grad, gets its gradient.  `expression=None` is the call without it.  On a device model without directions
@@ -76,7 +81,8 @@ def _is_float32(dtype):
 
 class SMPLX:
     def __init__(self, model_path=None, gender="neutral", joint_mapper=None, use_face_contour=False, use_pca=True, num_pca_comps=6,
-                 flat_hand_mean=False, age="adult", dtype=None, batch_size=1, ext="npz", device=0, num_expression_coeffs=None, **kwargs):
+                 flat_hand_mean=False, age="adult", dtype=None, batch_size=1, ext="npz", device=0, num_expression_coeffs=None, num_betas=10,
+                 **kwargs):
         # (create_* and the initial-value keywords of smplx arrive in kwargs: arguments not passed to forward are zeros, smplx's
         #  zero-initialised parameters)
         if not use_pca:
@@ -89,7 +95,20 @@ class SMPLX:
             raise ValueError(f"dtype={dtype}: the HIP model computes in float32")
         self.batch_size, self.gender = batch_size, gender
         self.joint_mapper, self.use_face_contour = joint_mapper, bool(use_face_contour)
-        self._dev = assets.get_device_model("smplx", gender, device)
+        if int(num_betas) < 10:
+            raise ValueError(f"num_betas={num_betas}: the device model carries the ten core betas; 10 .. 300 are supported")
+        # (the default construction asks for the model as before; other counts get a device model of their own)
+        space = {}
+        if int(num_betas) != 10:
+            space["num_betas"] = int(num_betas)
+        if num_expression_coeffs is not None:
+            space["num_expression_coeffs"] = int(num_expression_coeffs)
+        self._dev = assets.get_device_model("smplx", gender, device, **space)
+        if int(self._dev.n_betas) != 10 and "num_betas" not in space:       # a model registered with more: its first ten, as smplx cuts a file's
+            self._dev = assets.get_device_model("smplx", gender, device, num_betas=10, **space)
+        if int(self._dev.n_betas) != int(num_betas):
+            raise ValueError(f"num_betas={num_betas}: the device model takes {self._dev.n_betas} betas")
+        self.num_betas = int(num_betas)
         if int(num_pca_comps) != int(self._dev.n_hand_pca):
             raise ValueError(f"num_pca_comps={num_pca_comps}: the model has {self._dev.n_hand_pca} hand PCA components")
         self.num_pca_comps = int(num_pca_comps)

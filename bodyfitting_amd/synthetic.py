@@ -325,6 +325,38 @@ def make_model(model_type="smpl", seed=0, nv=None, bones=4, wide=None):
     return out
 
 
+def widen_shape_space(model, num_betas, num_expression_coeffs, seed=0):
+    """An SMPL-X model dict of `make_model` (10 + 10 columns; or any dict with "num_betas") widened to `num_betas` shape and
+    `num_expression_coeffs` expression directions, the way an SMPL-X v1.1 file offers up to 300 + 100: the columns it has are kept
+    (or cut), the added ones are drawn from `seed` by make_model's recipe for shape directions - a smooth affine deformation about the
+    centre plus a little per-vertex noise - divided by 1 + index / 10, the index counted from 10 in both added groups (later
+    principal directions move the mesh less).  The betas' columns are drawn first, then the expression's.  -> a new dict with
+    "num_betas"; `model` is not changed."""
+    nb0 = int(model.get("num_betas", 10))
+    sd = np.asarray(model["shapedirs"])
+    ne0, nb, ne = sd.shape[2] - nb0, int(num_betas), int(num_expression_coeffs)
+    if nb < 10 or ne < 0:
+        raise ValueError(f"num_betas={nb}, num_expression_coeffs={ne}: at least 10 betas and no negative count")
+    rng = np.random.default_rng(90000 + seed)
+    verts = np.asarray(model["v_template"], np.float64)
+    centre = verts.mean(0)
+
+    def group(have, first, count):
+        cols = [have[:, :, :count].astype(np.float64)]
+        for idx in range(first, count):
+            a = rng.normal(0.0, 0.012, size=(3, 3))
+            a[np.diag_indices(3)] += rng.normal(0.0, 0.02, size=3)
+            d = (verts - centre) @ a.T + rng.normal(0.0, 0.0008, size=verts.shape)
+            cols.append((d / (1.0 + idx / 10.0))[:, :, None])
+        return np.concatenate(cols, axis=2)
+
+    out = dict(model)
+    out["shapedirs"] = np.ascontiguousarray(np.concatenate([group(sd[:, :, :nb0], nb0, nb), group(sd[:, :, nb0:], ne0, ne)], axis=2),
+                                            dtype=np.float32)
+    out["num_betas"] = nb
+    return out
+
+
 def _add_smplx_extras(out, rng, verts, faces, rest, taken):
     """SMPL-X only pieces: hand PCA, pose mean, expression split, landmarks."""
     nv = verts.shape[0]

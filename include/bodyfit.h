@@ -170,7 +170,7 @@ int bf_smpl_vjp(bf_model *m, int n, const float *betas, const float *global_orie
  * model itself carries the shape directions only (bf_model_create: n_betas <= 12), and the fit never optimises expression
  * (smplify.py:167-173). */
 typedef struct bf_smplx_params {          /* betas, global_orient, body_pose are required; a NULL among the others = zeros */
-    const float *betas;                    /* [n,NB] */
+    const float *betas;                    /* [n,NB]; [n,n_betas] after bf_model_set_shape_space (bf_model_n_betas) */
     const float *global_orient;            /* [n,3] */
     const float *body_pose;                /* [n,63] */
     const float *jaw_pose, *leye_pose, *reye_pose;           /* [n,3] each */
@@ -203,6 +203,23 @@ int bf_smplx_vjp(bf_model *m, int n, const bf_smplx_params *in, const bf_smplx_c
  * bf_model_n_expression: their number, 0 when none is attached. */
 int bf_model_set_expression(bf_model *m, int n_expr, const float *exprdirs);
 int bf_model_n_expression(const bf_model *m);
+/* A wider shape space for the four smplx entry points below and their _dev twins: n_betas (10..300) is the number of betas they
+ * then take, n_expr (0..100) the number of expression coefficients, and dirs[NV,3,(n_betas-10)+n_expr] holds the shape directions
+ * from the eleventh on followed by the expression directions (an SMPL-X v1.1 file: columns 10:n_betas and 300:300+n_expr).  At
+ * least one direction; values outside those ranges and SMPL-kind models are BF_ERR_UNSUPPORTED.  Attached once, instead of
+ * bf_model_set_expression: after either call the other one, or the same one again, is BF_ERR_INVALID.  Afterwards betas is
+ * [n,n_betas], dbetas [n,n_betas], expression [n,n_expr] (NULL = zero coefficients; dexpression must then be NULL) and
+ * dexpression [n,n_expr].  The ten core betas stay where they are - in the device model, the fit and bf_model_forward, which know
+ * nothing of the rest; a frame's other coefficients [betas[10:], expression] go around the model's passes the way expression
+ * does.  Up to 16 such directions run on the kernels behind bf_model_set_expression, more on kernels of their own that walk the
+ * directions once per block of 8 frames (the environment variable BF_SHAPE_EXT_WIDE=1, read at either attachment, sends any
+ * number through those); both keep every sum in a fixed order.  Device memory: the directions once, and a second time in
+ * [NV,3,L] order for the wide reverse - 2 x 12 NV L bytes.
+ * bf_model_n_betas: the betas a call takes - n_betas after the attachment, else the model's own.
+ * bf_model_shape_ext_wide: 1 when the attached directions run on the wide kernels, else 0. */
+int bf_model_set_shape_space(bf_model *m, int n_betas, int n_expr, const float *dirs);
+int bf_model_n_betas(const bf_model *m);
+int bf_model_shape_ext_wide(const bf_model *m);
 /* bf_smplx_forward / bf_smplx_vjp with expression[n,n_expr]; dexpression[n,n_expr] (NULL = not wanted).  expression == NULL is
  * exactly the call without it: the same launches, the same bits (dexpression must then be NULL).  With expression on a model
  * without directions: BF_ERR_UNSUPPORTED.  Around the unchanged passes of the model, kernels of their own add the expression

@@ -47,7 +47,7 @@ def summarize(db, opens="bf_pose_state_kernel"):
             cur["kernels"][k] = cur["kernels"].get(k, 0.0) + dur * 1e-3
     groups = {}
     for c in calls:
-        kind = ("vjp" if "bf_model_vjp_fold_kernel" in c["kernels"] else "forward") + (" +expression" if "bf_expr_chain_kernel" in c["kernels"] else "")
+        kind = ("vjp" if "bf_model_vjp_fold_kernel" in c["kernels"] else "forward") + (" +expression" if "bf_expr_chain_kernel" in c["kernels"] or "bf_shape_ext_chain_kernel" in c["kernels"] else "")
         groups.setdefault((c["n"], kind), []).append(c["kernels"])
     for (n, kind), cs in sorted(groups.items()):
         names = sorted({k for c in cs for k in c})

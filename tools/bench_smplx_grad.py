@@ -6,6 +6,11 @@ and next to them, re-measured in the same process, the SMPL figures of tools/ben
 host clock around whole calls (each call synchronises the device before it returns), host staging included; the median of --reps
 calls after --warmup.  One JSON object per line.   usage: python tools/bench_smplx_grad.py [--reps R] [--warmup W] [--sizes 1,8,64,256]
 
+--shape-space NB,NE widens the model to NB betas and NE expression coefficients (synthetic.widen_shape_space; bf_model_set_shape_space):
+betas are then [n, NB], --expression times the calls with expression[n, NE], and every row carries the algorithmic direction bytes of
+a call - 12 NV L bytes of directions, L = NB - 10 + NE, walked once per frame by the kernels behind bf_model_set_expression and once
+per block of 8 frames by the wide ones (the environment variable BF_SHAPE_EXT_WIDE=1 sends any width through those).
+
 The backward's device time comes from a separate run under
 `rocprofv3 --kernel-trace --stats -d <dir> -o <name> -- python tools/bench_smplx_grad.py --no-smpl`;
 `python tools/bench_smplx_grad.py --summarize <dir>/<name>_results.db` then prints, per n and per kind of call (forward / vjp), the
@@ -33,17 +38,22 @@ def main():
     ap.add_argument("--no-smpl", action="store_true", help="skip the SMPL comparison (the run under the profiler)")
     ap.add_argument("--expression", action="store_true", help="time every call with expression coefficients as well (expr_* columns; "
                     "--summarize lists those calls as 'forward +expression' / 'vjp +expression')")
+    ap.add_argument("--shape-space", metavar="NB,NE", help="betas and expression coefficients of the model (default: the synthetic model's 10,10)")
     ap.add_argument("--summarize", metavar="DB", help="print the kernel split of a rocprofv3 run of this tool and exit")
     a = ap.parse_args()
     if a.summarize:
         return summarize(a.summarize, opens="bf_smplx_pose_assemble_kernel")
     gmm = S.make_gmm(seed=0)
-    dev = N.DeviceModel(S.make_model("smplx", seed=0), gmm, device=0)
+    model = S.make_model("smplx", seed=0)
+    if a.shape_space:
+        model = S.widen_shape_space(model, *(int(v) for v in a.shape_space.split(",")), seed=0)
+    dev = N.DeviceModel(model, gmm, device=0)
+    n_ext = dev.n_betas - dev.n_core_betas + dev.n_expression
     smpl = None if a.no_smpl else N.DeviceModel(S.make_model("smpl", seed=0), gmm, device=0)
     rng = np.random.default_rng(0)
     f32 = lambda sd, *shape: rng.normal(0, sd, shape).astype(np.float32)          # noqa: E731
     for n in (int(s) for s in a.sizes.split(",")):
-        p = (f32(0.7, n, 10), f32(0.8, n, 3), f32(0.3, n, 63), f32(0.2, n, 3), f32(0.2, n, 3), f32(0.2, n, 3), f32(0.4, n, 6), f32(0.4, n, 6))
+        p = (f32(0.7, n, dev.n_betas), f32(0.8, n, 3), f32(0.3, n, 63), f32(0.2, n, 3), f32(0.2, n, 3), f32(0.2, n, 3), f32(0.4, n, 6), f32(0.4, n, 6))
         cot = dict(dverts=f32(1, n, dev.n_verts, 3), djoints_all=f32(1, n, dev.n_joints_all, 3), dfull_pose=f32(1, n, 3 * dev.n_joints))
         fwd = timed(lambda: dev.forward_smplx(*p), a.reps, a.warmup)
         bwd = timed(lambda: dev.vjp_smplx(*p, **cot), a.reps, a.warmup)
@@ -53,7 +63,11 @@ def main():
                "vjp_ms": round(bwd[0], 3), "vjp_min_ms": round(bwd[1], 3),
                "forward_backward_ms": round(both[0], 3), "forward_backward_min_ms": round(both[1], 3),
                "forward_backward_per_frame_us": round(both[0] * 1e3 / n, 1)}
-        if a.expression:                    # the same calls with expression[n, n_expression] (bf_smplx_forward_expr / bf_smplx_vjp_expr)
+        # one walk over the directions: the forward's vertex delta; the vjp's forward walks them again and its reverse the second copy
+        walks = -(-n // 8) if dev.shape_ext_wide else n
+        row.update(n_betas=dev.n_betas, n_expression=dev.n_expression, wide_kernels=dev.shape_ext_wide,
+                   direction_bytes_per_walk=12 * dev.n_verts * n_ext, direction_walks_forward=walks, direction_walks_vjp=2 * walks)
+        if a.expression and dev.n_expression:          # the same calls with expression[n, n_expression] (bf_smplx_forward_expr / bf_smplx_vjp_expr)
             e = f32(0.7, n, dev.n_expression)
             x_fwd = timed(lambda: dev.forward_smplx(*p, expression=e), a.reps, a.warmup)
             x_bwd = timed(lambda: dev.vjp_smplx(*p, **cot, expression=e), a.reps, a.warmup)
@@ -61,7 +75,7 @@ def main():
             row.update(expr_forward_ms=round(x_fwd[0], 3), expr_vjp_ms=round(x_bwd[0], 3), expr_forward_backward_ms=round(x_both[0], 3),
                        expr_forward_backward_min_ms=round(x_both[1], 3), expr_over_plain=round(x_both[0] / both[0], 3))
         if smpl is not None:
-            q = (p[0], p[1], f32(0.3, n, 69))
+            q = (np.ascontiguousarray(p[0][:, :10]), p[1], f32(0.3, n, 69))
             sc = (f32(1, n, smpl.n_verts, 3), f32(1, n, smpl.n_joint_map, 3), f32(1, n, smpl.n_joints + smpl.n_selector, 3))
             s_both = timed(lambda: (smpl.forward(*q), smpl.vjp(*q, *sc)), a.reps, a.warmup)
             s_bwd = timed(lambda: smpl.vjp(*q, *sc), a.reps, a.warmup)
