@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hmr_kernels.h"
+#include "resize_axis.h"
 
 #define HMR_RES 224
 #define HMR_FEAT 2048
@@ -15,20 +16,7 @@
 // weight at the borders, rows clamp only the row index.  Horizontal pass: an int sum per row; vertical pass as VResizeLinear<uchar>:
 // (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2.  Then /255 and Normalize(IMG_NORM_MEAN, IMG_NORM_STD) in fp32.
 // One thread per output pixel (all three channels); out[n][224][224][3] NHWC.  The numpy restatement is bodyfitting_amd/hmr.py.
-__device__ __forceinline__ void hmr_axis(int d, double scale, int size, int clamp_weight, int *s0, int *s1, int *a0, int *a1) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (clamp_weight) {
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= size - 1) { f = 0.f; s = size - 1; }
-    }
-    *a0 = (int)rintf((1.f - f) * 2048.f);
-    *a1 = (int)rintf(f * 2048.f);
-    *s0 = min(max(s, 0), size - 1);
-    *s1 = min(max(s + 1, 0), size - 1);
-}
-
+// The axis itself is resize_axis.h's.
 extern "C" __global__ __launch_bounds__(256) void bf_hmr_resize_kernel(int n, int H, int W, double scale_y, double scale_x,
                                                                        const uint8_t *__restrict__ src, uint8_t *__restrict__ resized,
                                                                        float *__restrict__ out, float3 mean, float3 stdv) {
@@ -36,8 +24,8 @@ extern "C" __global__ __launch_bounds__(256) void bf_hmr_resize_kernel(int n, in
     if (i >= n * HMR_RES * HMR_RES) return;
     const int b = i / (HMR_RES * HMR_RES), r = i % (HMR_RES * HMR_RES), dy = r / HMR_RES, dx = r % HMR_RES;
     int x0, x1, a0, a1, y0, y1, b0, b1;
-    hmr_axis(dx, scale_x, W, 1, &x0, &x1, &a0, &a1);
-    hmr_axis(dy, scale_y, H, 0, &y0, &y1, &b0, &b1);
+    bf_resize_axis(dx, scale_x, W, 1, &x0, &x1, &a0, &a1);
+    bf_resize_axis(dy, scale_y, H, 0, &y0, &y1, &b0, &b1);
     const bool edge = x0 == W - 1;            // (sx + 1 >= width: OpenCV's tail loop, S[sx] * 2048 without the second tap)
     const uint8_t *img = src + (size_t)b * H * W * 3;
     const float m[3] = {mean.x, mean.y, mean.z}, sd[3] = {stdv.x, stdv.y, stdv.z};

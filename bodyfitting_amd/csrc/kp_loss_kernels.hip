@@ -19,14 +19,7 @@
 // not depend on the problems beside it.
 #include "bf_internal.h"
 #include "kp_loss_kernels.h"
-
-namespace {
-__device__ __forceinline__ float kpl_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-}  // namespace
+#include "wave_ops.h"
 
 extern "C" __global__ void __launch_bounds__(BF_KPL_THREADS) bf_keypoint_loss_kernel(KpLossIO Q, HyperDev H) {
     __shared__ float4 s_part[BF_KPL_THREADS];                     // [slots][NLP] dL/dX and the loss share of (row, slot)
@@ -119,7 +112,7 @@ extern "C" __global__ void __launch_bounds__(BF_KPL_THREADS) bf_keypoint_loss_ke
         if (wave == 0) {
             float acc = 0.f;
             for (int q = lane; q < R; q += 64) acc += s_ls[q];
-            acc = kpl_wave_sum(acc);
+            acc = bf_wave_sum(acc);
             if (lane == 0 && Q.terms) Q.terms[(size_t)p * 4] = acc / ndiv;
         }
     }
@@ -141,7 +134,7 @@ extern "C" __global__ void __launch_bounds__(BF_KPL_THREADS) bf_keypoint_loss_ke
             const float *mu = Q.g_means + (size_t)m * D;
             float a = 0.f;
             for (int i = lane; i < D; i += 64) a += s_z[m * BF_KPL_MAX_DIM + i] * (s_pose[i] - mu[i]);      // (69 dofs: a second round of five lanes)
-            a = kpl_wave_sum(a);
+            a = bf_wave_sum(a);
             if (lane == 0) s_ll[m] = 0.5f * a - Q.g_logw[m];
         }
         __syncthreads();

@@ -3,14 +3,7 @@
 // hides the keypoint workgroup's ~20 us latency chain under the scan's arithmetic.
 #pragma once
 #include "bf_internal.h"
-
-namespace {
-__device__ inline float lb_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-}  // namespace
+#include "wave_ops.h"
 
 // One sampled vertex X (world space, similarity applied) in mask view m of frame f: uvi = (u, v, inside, 1 / pix_z), duvb =
 // d(binary term) / duv * weight; returns the vertex's share of the binary term (loss.py:95-104,119-128).  Shared by
@@ -175,8 +168,7 @@ __device__ __forceinline__ void bf_kp_loss_body(int f, float *sm, KpIO Q, const 
                 else if (which == 3) acc += chain ? s_g[q * 4] * (s_x[q * 3] + t0) + s_g[q * 4 + 1] * (s_x[q * 3 + 1] + t1) + s_g[q * 4 + 2] * (s_x[q * 3 + 2] + t2) : 0.f;
                 else acc += s_g[q * 4 + 3];
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+            acc = bf_wave_sum(acc);
             if (lane == 0) {
                 if (which < 3) e[EXT_K + which] = acc * sc;
                 else if (which == 3) e[EXT_K + 3] = acc * cs;
@@ -375,7 +367,7 @@ __device__ __forceinline__ void bf_mask_contour_body(int bx, int m, int f, float
         }
         if (!K.acc) { choice[o] = bidx; cgrad[o * 2] = gx; cgrad[o * 2 + 1] = gy; }      // (the gather kernel's inputs: not in sums mode)
     }
-    lval = lb_wave_sum(lval);
+    lval = bf_wave_sum(lval);
     if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = lval;
     __syncthreads();
     if (threadIdx.x == 0) {

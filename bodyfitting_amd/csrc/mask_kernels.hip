@@ -19,14 +19,6 @@
 #include "loss_bodies.h"
 #include "mask_kernels.h"
 
-namespace {
-__device__ inline float mk_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-}  // namespace
-
 // grid (ceil(Ns/256), M, F).  uvi[F][M][Ns] = (u, v, inside, 1/pix_z);  duvb[F][M][Ns][2] = d(binary term)/duv * weight
 extern "C" __global__ void __launch_bounds__(256)
 bf_mask_project_kernel(MaskIO K, const float *__restrict__ vout, const float *__restrict__ proj_all, float *__restrict__ uvi,
@@ -38,11 +30,8 @@ bf_mask_project_kernel(MaskIO K, const float *__restrict__ vout, const float *__
         const float *X = vout + ((size_t)f * K.nv + (size_t)s * K.sstride) * 3;
         lval = bf_mask_project_one(K, X[0], X[1], X[2], proj_all, f, m, s, uvi, duvb);
     }
-    lval = mk_wave_sum(lval);
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = lval;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        loss_part[((size_t)f * K.n_masks + m) * K.part_stride + blockIdx.x] = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+    const float tot = bf_block_sum_256(bf_wave_sum(lval), sred);
+    if (threadIdx.x == 0) loss_part[((size_t)f * K.n_masks + m) * K.part_stride + blockIdx.x] = tot;
 }
 
 // grid (ceil(16 Cmax/256), M, F).  For contour point c: choice[F][M][Cmax] = sampled vertex (or -1),

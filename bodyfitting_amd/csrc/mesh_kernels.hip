@@ -23,14 +23,6 @@
 #include <cstring>
 #include <type_traits>
 
-namespace {
-__device__ inline float m_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-}  // namespace
-
 // One 128-thread workgroup per parameter set (body: pose_state_body.h).
 // A pose state published by the resident fit launch, read by a kernel that waited for its doorbell.  `coherent` (bit 30 of the
 // door target): device-scope loads that are served past this XCD's non-coherent caches - correctness then no longer rests on

@@ -9,18 +9,10 @@
 // alone: 256 values per block (lanes by xor-shuffle, the four waves as (0 + 1) + (2 + 3)), then ONE block over the block sums.
 #include "bf_internal.h"
 #include "mesh_loss_kernels.h"
+#include "wave_ops.h"
 #ifndef BF_ADJ_BATCH
 #define BF_ADJ_BATCH 8        // incident faces of a vertex walked together (disp_kernels.hip)
 #endif
-
-// the sum of `a` over the block's 256 threads, valid in thread 0 (all threads call it)
-static __device__ __forceinline__ float ml_block_sum(float a, float *s4) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = a;
-    __syncthreads();
-    return (s4[0] + s4[1]) + (s4[2] + s4[3]);
-}
 
 // through n = x / (|x| + 1e-8):  dx = dn / s - n (n . dn) / |x|, and at |x| = 0 torch's rule dx = dn / 1e-8
 static __device__ __forceinline__ void ml_unnormalise(const float4 n, float g0, float g1, float g2, float *o) {
@@ -140,7 +132,7 @@ bf_ml_lap_partial_kernel(const int *__restrict__ faces, int nf, const float *__r
         }
         t = ab + ca + bc;
     }
-    const float tot = ml_block_sum(t, s4);
+    const float tot = bf_block_sum_256(bf_wave_sum(t), s4);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
@@ -185,7 +177,7 @@ bf_ml_pc_partial_kernel(int n, const float *__restrict__ P, const float *__restr
         const float d0 = P[i * 3] - C[i * 3], d1 = P[i * 3 + 1] - C[i * 3 + 1], d2 = P[i * 3 + 2] - C[i * 3 + 2];
         a = d0 * d0 + d1 * d1 + d2 * d2;
     }
-    const float tot = ml_block_sum(a, s4);
+    const float tot = bf_block_sum_256(bf_wave_sum(a), s4);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
@@ -215,7 +207,7 @@ bf_ml_normal_partial_kernel(int n, const float *__restrict__ fn, const float *__
     const int i = blockIdx.x * 256 + threadIdx.x;
     float a = 0.f;
     if (i < n) a = ml_normal_row(i, n, fn[i * 3], fn[i * 3 + 1], fn[i * 3 + 2], pn, dpn);
-    const float tot = ml_block_sum(a, s4);
+    const float tot = bf_block_sum_256(bf_wave_sum(a), s4);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
@@ -237,7 +229,7 @@ bf_ml_normal_gather_partial_kernel(int n, const int *__restrict__ ids, const flo
             dpn[i * 3] = 0.f; dpn[i * 3 + 1] = 0.f; dpn[i * 3 + 2] = 0.f;
         }
     }
-    const float tot = ml_block_sum(a, s4);
+    const float tot = bf_block_sum_256(bf_wave_sum(a), s4);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
@@ -259,6 +251,6 @@ bf_ml_finish_kernel(const float *__restrict__ partial, int n_partial, int root, 
     __shared__ float s4[4];
     float a = 0.f;
     for (int i = threadIdx.x; i < n_partial; i += 256) a += partial[i];
-    const float tot = ml_block_sum(a, s4);
+    const float tot = bf_block_sum_256(bf_wave_sum(a), s4);
     if (threadIdx.x == 0) out[0] = root ? sqrtf(tot) : tot / divisor;
 }

@@ -16,6 +16,7 @@
 //   bf_nr_backward_large_kernel  records whose pixel box exceeds BF_TEX_GATHER_MAX: per pixel, global atomicAdd (runs after the gather)
 #include "bf_internal.h"
 #include "nr_kernels.h"
+#include "wave_ops.h"
 #include "tex_bodies.h"
 
 // lighting.py:33-52 for one face from its world-space corners c0, c1, c2 (3 floats each), float32, in this order:
@@ -225,12 +226,6 @@ bf_nr_unlit_kernel(int is, int nf, const float *__restrict__ pix, const float *_
     unlit[(size_t)i * 3] = acc[0]; unlit[(size_t)i * 3 + 1] = acc[1]; unlit[(size_t)i * 3 + 2] = acc[2];
 }
 
-__device__ __forceinline__ float nr_wave_sum(float v) {      // fixed butterfly: equal inputs, equal bits
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // one line d0 of one edge along one axis: axis 0 walks columns (d0 = x, d1 = y), axis 1 rows (d0 = y, d1 = x)
 struct NrLine { float p00, p10, cross; int d0, axis; };
 
@@ -330,7 +325,7 @@ bf_nr_geometry_kernel(NrGeo G, NrLight L, float *__restrict__ grad_frec, float *
                         nr_walk(G, ln, max(min(d1_in, lim), 0), min(max(d1_in, lim), is - 1), k, lane, k_out >= 0 ? 1.f : 0.f, rgb_out, acc0, acc1);
                     }
                 }
-                acc0 = nr_wave_sum(acc0); acc1 = nr_wave_sum(acc1);
+                acc0 = bf_wave_sum(acc0); acc1 = bf_wave_sum(acc1);
                 if (lane == 0) { s_g[i0 * 3 + 1 - axis] += acc0; s_g[i1 * 3 + 1 - axis] += acc1; }
             }
         }
@@ -370,9 +365,9 @@ bf_nr_geometry_kernel(NrGeo G, NrLight L, float *__restrict__ grad_frec, float *
         }
     }
 #pragma unroll
-    for (int i = 0; i < 9; ++i) gd[i] = nr_wave_sum(gd[i]);
+    for (int i = 0; i < 9; ++i) gd[i] = bf_wave_sum(gd[i]);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) dl[c] = nr_wave_sum(dl[c]);
+    for (int c = 0; c < 3; ++c) dl[c] = bf_wave_sum(dl[c]);
     __builtin_amdgcn_wave_barrier();
     if (lane != 0) return;
 #pragma unroll

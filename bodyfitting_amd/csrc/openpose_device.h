@@ -1,7 +1,10 @@
 // Device helpers shared by the OpenPose body (openpose_kernels.hip) and hand (openpose_hand_kernels.hip) kernels: OpenCV's
-// INTER_CUBIC coefficients and source taps.  Both files compile with -ffp-contract=off.
+// INTER_CUBIC coefficients and source taps, and the Gaussian filter's border rule.  Both files compile with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
+
+// scipy.ndimage mode 'reflect' (d c b a | a b c d | d c b a), one reflection: index i of a line of n
+__device__ __forceinline__ int op_reflect(int i, int n) { return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i); }
 
 // interpolateCubic(x, coeffs), A = -0.75, in float
 __device__ __forceinline__ void op_cubic(float x, float c[4]) {

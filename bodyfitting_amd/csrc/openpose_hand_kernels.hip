@@ -115,8 +115,6 @@ __constant__ double oh_gauss_w[OH_GR + 1] = {
     0x1.0fa58939b528fp-5, 0x1.26defcaeb0202p-6, 0x1.1e6bccad344bap-7, 0x1.f1e9915139406p-9, 0x1.8345966f69518p-10,
     0x1.0d8a5ad43c165p-11, 0x1.4fbe39149e277p-13, 0x1.763a210dfb306p-15};
 
-__device__ __forceinline__ int oh_reflect(int i, int n) { return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i); }
-
 extern "C" __global__ __launch_bounds__(256) void bf_oh_gauss_kernel(int axis, int src_c, const OhBox *__restrict__ boxes,
                                                                      const double *__restrict__ src, double *__restrict__ dst) {
     const int b = blockIdx.y;
@@ -131,8 +129,8 @@ extern "C" __global__ __launch_bounds__(256) void bf_oh_gauss_kernel(int axis, i
     auto at = [&](int yy, int xx) { return img[((size_t)yy * W + xx) * src_c]; };
     double v = at(y, x) * oh_gauss_w[0];
     for (int j = OH_GR; j >= 1; --j) {
-        const double s = axis == 0 ? at(oh_reflect(y - j, H), x) + at(oh_reflect(y + j, H), x)
-                                   : at(y, oh_reflect(x - j, W)) + at(y, oh_reflect(x + j, W));
+        const double s = axis == 0 ? at(op_reflect(y - j, H), x) + at(op_reflect(y + j, H), x)
+                                   : at(y, op_reflect(x - j, W)) + at(y, op_reflect(x + j, W));
         v = v + s * oh_gauss_w[j];
     }
     dst[B.px * OH_NPART + i] = v;

@@ -259,8 +259,6 @@ __constant__ double op_gauss_w[OP_GR + 1] = {
     0x1.0fa58939b528fp-5, 0x1.26defcaeb0202p-6, 0x1.1e6bccad344bap-7, 0x1.f1e9915139406p-9, 0x1.8345966f69518p-10,
     0x1.0d8a5ad43c165p-11, 0x1.4fbe39149e277p-13, 0x1.763a210dfb306p-15};
 
-__device__ __forceinline__ int op_reflect(int i, int n) { return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i); }
-
 // src[b][H][W][src_c] channels 0..17 -> dst[b][H][W][18]; axis 0 runs along y, 1 along x
 extern "C" __global__ __launch_bounds__(256) void bf_op_gauss_kernel(int n, int H, int W, int axis, int src_c, const double *__restrict__ src,
                                                                      double *__restrict__ dst) {

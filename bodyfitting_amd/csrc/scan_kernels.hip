@@ -77,12 +77,6 @@ __device__ __forceinline__ float closest_rule(const float *p0, const float *p1, 
     return x0 * x0 + x1 * x1 + x2 * x2;
 }
 
-__device__ inline float blk_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 }  // namespace
 
 // wave-wide minimum of a float / an int on the DPP path (all lanes get it)
@@ -506,7 +500,7 @@ bf_pc_partial_kernel(const float *__restrict__ P, const float *__restrict__ C, i
         float d0 = p[0] - c[0], d1 = p[1] - c[1], d2 = p[2] - c[2];
         a = d0 * d0 + d1 * d1 + d2 * d2;
     }
-    a = blk_wave_sum(a);
+    a = bf_wave_sum(a);
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = a;
     __syncthreads();
     if (threadIdx.x == 0) partial[(size_t)f * gridDim.x + blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);

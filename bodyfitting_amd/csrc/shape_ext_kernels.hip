@@ -21,6 +21,7 @@
 // LDS tables are sized by BF_SHAPE_EXT_MAX, BF_EXT_FB and BF_GRAD_MAX_JOINTS (bf_internal.h), which the host checks a model against.
 #include "bf_internal.h"
 #include "shape_ext_kernels.h"
+#include "ext_bodies.h"
 
 #define BF_EXT_THREADS 256
 #define BF_EXT_TILE 256         // vertices per workgroup of the vertex delta and the reverse
@@ -62,27 +63,7 @@ bf_shape_ext_chain_kernel(FitTab T, float *__restrict__ state, const float *__re
         if (tid < 3) s_dGt[tid] = acc;
     }
     __syncthreads();
-    for (int lev = 1; lev < T.n_levels; ++lev) {
-        const int ls = T.level_start[lev], cnt = T.level_start[lev + 1] - ls;
-        if (tid < cnt) {
-            const int i = T.level_joints[ls + tid], p = T.parents[i];
-            const float *G = st.GR + p * 9;
-            const float r0 = s_dJ[i * 3] - s_dJ[p * 3], r1 = s_dJ[i * 3 + 1] - s_dJ[p * 3 + 1], r2 = s_dJ[i * 3 + 2] - s_dJ[p * 3 + 2];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) s_dGt[i * 3 + a] = G[a * 3] * r0 + G[a * 3 + 1] * r1 + G[a * 3 + 2] * r2 + s_dGt[p * 3 + a];
-        }
-        __syncthreads();
-    }
-    if (tid < nj) {
-        const float *G = st.GR + tid * 9;
-        const float d0 = s_dJ[tid * 3], d1 = s_dJ[tid * 3 + 1], d2 = s_dJ[tid * 3 + 2];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float g = s_dGt[tid * 3 + a];
-            st.Gt[tid * 3 + a] += g;
-            st.At[tid * 3 + a] += g - (G[a * 3] * d0 + G[a * 3 + 1] * d1 + G[a * 3 + 2] * d2);
-        }
-    }
+    bf_ext_chain_shift(T, st, s_dJ, s_dGt);
 }
 
 namespace {
@@ -92,22 +73,6 @@ __device__ __forceinline__ void stage_rotations(const MeshTab &M, const float *_
     __syncthreads();
     for (int i = threadIdx.x; i < M.nj * 9; i += BF_EXT_THREADS) s_GR[i] = GR[i];
     __syncthreads();
-}
-// visit(j, w) for the non-zero skinning weights of vertex v in joint order: the model's sparse rows (v_nnz 4 or 8), else its dense row
-template <class F>
-__device__ __forceinline__ void for_each_bone(const MeshTab &M, int v, F visit) {
-    if (M.v_nnz) {
-        const int nnz = M.v_nnz;
-        for (int q = 0; q < nnz; ++q) {
-            const float w = M.v_nzw[(size_t)v * nnz + q];
-            if (w != 0.f) visit(M.v_nzj[(size_t)v * nnz + q], w);
-        }
-    } else {
-        for (int j = 0; j < M.nj; ++j) {
-            const float w = M.lbs_weights[(size_t)v * M.nj + j];
-            if (w != 0.f) visit(j, w);
-        }
-    }
 }
 }  // namespace
 
@@ -153,12 +118,7 @@ bf_shape_ext_vertex_kernel(MeshTab M, const float *__restrict__ state, const flo
         if (!live) continue;
         const float x0 = e0[b], x1 = e1[b], x2 = e2[b];
         float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        for_each_bone(M, v, [&](int j, float w) {
-            const float *G = s_GR + j * 9;
-            a0 += w * (G[0] * x0 + G[1] * x1 + G[2] * x2);
-            a1 += w * (G[3] * x0 + G[4] * x1 + G[5] * x2);
-            a2 += w * (G[6] * x0 + G[7] * x1 + G[8] * x2);
-        });
+        for_each_bone(M, v, [&](int j, float w) { bf_bone_rotate(s_GR, j, w, x0, x1, x2, a0, a1, a2); });
         const size_t o = ((size_t)(f0 + b) * nv + v) * 3;
         vraw[o] += a0; vraw[o + 1] += a1; vraw[o + 2] += a2;
         if (vposed) { vposed[o] += x0; vposed[o + 1] += x1; vposed[o + 2] += x2; }
@@ -187,12 +147,7 @@ bf_shape_ext_reverse_kernel(MeshTab M, const float *__restrict__ state, const fl
         if (v < nv) {
             const size_t o = ((size_t)(f0 + b) * nv + v) * 3;
             const float g0 = dv[o], g1 = dv[o + 1], g2 = dv[o + 2];
-            for_each_bone(M, v, [&](int j, float w) {
-                const float *G = s_GR + j * 9;
-                d0 += w * (G[0] * g0 + G[3] * g1 + G[6] * g2);
-                d1 += w * (G[1] * g0 + G[4] * g1 + G[7] * g2);
-                d2 += w * (G[2] * g0 + G[5] * g1 + G[8] * g2);
-            });
+            for_each_bone(M, v, [&](int j, float w) { bf_bone_rotate_t(s_GR, j, w, g0, g1, g2, d0, d1, d2); });
         }
         s_d[tid * FB + b] = make_float4(d0, d1, d2, 0.f);
     }

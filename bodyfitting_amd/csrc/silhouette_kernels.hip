@@ -29,10 +29,8 @@ bf_sil_project_kernel(MaskIO K, const float *__restrict__ verts, const float *__
         const float *X = verts + (size_t)s * K.sstride * 3;
         lval = bf_mask_project_one(K, X[0], X[1], X[2], proj, 0, m, s, uvi, duvb);
     }
-    lval = lb_wave_sum(lval);
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = lval;
-    __syncthreads();
-    if (threadIdx.x == 0) loss_part[(size_t)m * K.part_stride + blockIdx.x] = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+    const float tot = bf_block_sum_256(bf_wave_sum(lval), sred);
+    if (threadIdx.x == 0) loss_part[(size_t)m * K.part_stride + blockIdx.x] = tot;
 }
 
 // grid (ceil(16 Cmax/256), M): sixteen lanes per contour point (loss_bodies.h); K.acc is set, so nothing but the sums and the
@@ -73,7 +71,7 @@ bf_sil_finish_kernel(MaskIO K, const float *__restrict__ proj, const float *__re
             float b = 0.f, c = 0.f;
             for (int i = lane; i < K.proj_blocks; i += 64) b += p[i];
             for (int i = lane; i < nc; i += 64) c += p[K.proj_blocks + i];
-            b = lb_wave_sum(b); c = lb_wave_sum(c);
+            b = bf_wave_sum(b); c = bf_wave_sum(c);
             if (lane == 0) { terms[1 + 2 * (size_t)m] = c; terms[2 + 2 * (size_t)m] = b; }
         }
         __threadfence_block();

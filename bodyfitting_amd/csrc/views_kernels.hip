@@ -4,6 +4,8 @@
 #include <climits>
 #include <cstdint>
 #include "views_kernels.h"
+#include "wave_ops.h"
+#include "resize_axis.h"
 
 #define VW_THREADS 256
 
@@ -11,15 +13,6 @@
 extern "C" __global__ __launch_bounds__(VW_THREADS) void bf_views_bbox_init_kernel(int n, int *__restrict__ bbox) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n * 4) bbox[i] = (i & 3) < 2 ? INT_MAX : -1;
-}
-
-__device__ __forceinline__ int vw_wave_min(int v) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int vw_wave_max(int v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
 }
 
 // np.where(mask != 0) -> min / max row and column, per view.  masks: n views of H * W bytes, view v at v * stride (stride a multiple of
@@ -48,7 +41,7 @@ extern "C" __global__ __launch_bounds__(VW_THREADS) void bf_views_bbox_kernel(in
         }
     }
     __shared__ int red[4][VW_THREADS / 64];
-    top = vw_wave_min(top); left = vw_wave_min(left); bottom = vw_wave_max(bottom); right = vw_wave_max(right);
+    top = bf_wave_min(top); left = bf_wave_min(left); bottom = bf_wave_max(bottom); right = bf_wave_max(right);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { red[0][wave] = top; red[1][wave] = left; red[2][wave] = bottom; red[3][wave] = right; }
     __syncthreads();
@@ -63,24 +56,6 @@ extern "C" __global__ __launch_bounds__(VW_THREADS) void bf_views_bbox_kernel(in
             atomicMax(bbox + v * 4 + 3, right);
         }
     }
-}
-
-// One axis of cv2.resize INTER_LINEAR on 8-bit data (as bf_hmr_resize_kernel, any n_src -> L): OpenCV's scale 1 / (L / n_src) in
-// double, the source coordinate (d + 0.5) * scale - 0.5 rounded to float and floored, 11-bit coefficients.  Columns clamp coordinate
-// and weight at the borders, rows only the index.
-__device__ __forceinline__ void vw_axis(int d, int L, int n_src, int clamp_weight, int *s0, int *s1, int *a0, int *a1) {
-    const double scale = 1.0 / ((double)L / (double)n_src);
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (clamp_weight) {
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= n_src - 1) { f = 0.f; s = n_src - 1; }
-    }
-    *a0 = (int)rintf((1.f - f) * 2048.f);
-    *a1 = (int)rintf(f * 2048.f);
-    *s0 = min(max(s, 0), n_src - 1);
-    *s1 = min(max(s + 1, 0), n_src - 1);
 }
 
 // VResizeLinear<uchar>: (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2
@@ -104,8 +79,9 @@ extern "C" __global__ __launch_bounds__(VW_THREADS) void bf_views_prepare_kernel
     if (i < L * L) {
         const int dy = i / L, dx = i % L;
         int x0, x1, a0, a1, y0, y1, b0, b1;
-        vw_axis(dx, L, j.cw, 1, &x0, &x1, &a0, &a1);
-        vw_axis(dy, L, j.ch, 0, &y0, &y1, &b0, &b1);
+        // any crop size -> L: OpenCV's scale 1 / (L / n_src) in double
+        bf_resize_axis(dx, 1.0 / ((double)L / (double)j.cw), j.cw, 1, &x0, &x1, &a0, &a1);
+        bf_resize_axis(dy, 1.0 / ((double)L / (double)j.ch), j.ch, 0, &y0, &y1, &b0, &b1);
         const bool edge = x0 == j.cw - 1;     // OpenCV's tail loop: S[sx] * 2048 without the second tap
         const uint8_t *m0 = masks + j.msk_off + (long long)y0 * W, *m1 = masks + j.msk_off + (long long)y1 * W;
         const uint8_t *r0 = crops + j.img_off + (long long)y0 * W * 3, *r1 = crops + j.img_off + (long long)y1 * W * 3;
