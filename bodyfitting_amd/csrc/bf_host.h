@@ -166,7 +166,7 @@ inline BfRouteStats &bf_route_stats() { static BfRouteStats S; return S; }
 
 // vertex -> (face, corner) lists in the order compute_normal_torch (io_utils.py:406-428) adds a vertex's face normals up: corner by
 // corner, faces ascending.  start[nv + 1] = CSR offsets, adj[3 nf] = face * 4 + corner.  `faces` holds 3 nf indices inside [0, nv).
-// Shared by the SMPL+D stage (bf_fit_displacement) and bf_topo_create.
+// Shared by the SMPL+D stage (bf_fit_displacement) and bf_topo_create, through BfTopoDev below.
 inline void bf_build_vertex_adjacency(const std::vector<int> &faces, int nv, std::vector<int> &start, std::vector<int> &adj) {
     const int nf = (int)(faces.size() / 3);
     start.assign((size_t)nv + 1, 0);
@@ -177,6 +177,20 @@ inline void bf_build_vertex_adjacency(const std::vector<int> &faces, int nv, std
     for (int c = 0; c < 3; ++c)
         for (int f = 0; f < nf; ++f) adj[fill[faces[f * 3 + c]]++] = f * 4 + c;
 }
+
+// A mesh's topology on the device: its faces and the lists above.  build() uploads on the current device (blocking); faces last: it
+// is the "built" flag of a record built on first use (bf_model's, under `lazy`)
+struct BfTopoDev {
+    DevBuf<int> faces, adj_start, adj;
+    bool built() const { return faces.p != nullptr; }
+    hipError_t build(const std::vector<int> &faces_host, int nv) {
+        std::vector<int> start, list;
+        bf_build_vertex_adjacency(faces_host, nv, start, list);
+        hipError_t e = adj_start.upload(start);
+        if (e == hipSuccess) e = adj.upload(list);
+        return e == hipSuccess ? faces.upload(faces_host) : e;
+    }
+};
 
 // Scratch of the MFMA batch path of the full-mesh forward (>= BF_MFMA_MIN_FRAMES frames).  Owned by whoever owns the stream
 // the forward runs on (a bf_batch, or a one-off forward call): two batches of one model never share it.
@@ -298,9 +312,9 @@ struct bf_model {
     } sub, sub_kp;                // (sub_kp: the keypoint-only sub-model of the iterations before the dense losses switch on - no sampled vertices)
     DevBuf<float> posedirsT;      // [3NV][npf], built on first use of the dense reverse pass (under `lazy`, device-synchronised)
     DevBuf<float> fit_image;      // FitTab::lds_image of the dense-schedule fit instance, built on first use (under `lazy`)
-    std::mutex lazy;              // guards the build-on-first-use tables (posedirsT, faces_d / adj)
+    std::mutex lazy;              // guards the build-on-first-use tables (posedirsT, topo)
     std::vector<int> faces_host;  // body-model topology (for the SMPL+D stage), optional
-    DevBuf<int> faces_d, adj_start, adj;   // faces and the vertex -> (face, corner) lists, built on first use
+    BfTopoDev topo;               // faces_host and its vertex -> (face, corner) lists on the device, built on first use
     // SMPL-X extension directions: the expression directions (bf_model_set_expression), or a shape space's directions from the eleventh
     // beta on followed by its expression directions (bf_model_set_shape_space).  n_ext = 0: none attached
     int n_expr = 0;               // expression coefficients of a call

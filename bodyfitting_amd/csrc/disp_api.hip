@@ -18,14 +18,7 @@ int bf_fit_displacement(bf_batch *b, int n_iters, const bf_hyper *hyper) {
     const int F = b->F, nv = m->nv, nf = (int)m->faces_host.size() / 3;
     BF_TRY(bf_guard_arena(b));
     std::unique_lock<std::mutex> lazy(m->lazy);
-    if (!m->faces_d.p) {
-        // vertex -> (face, corner) lists in the order compute_normal_torch adds them: corner by corner, faces ascending
-        std::vector<int> start, adj;
-        bf_build_vertex_adjacency(m->faces_host, nv, start, adj);
-        HIP_TRY(m->adj_start.upload(start));
-        HIP_TRY(m->adj.upload(adj));
-        HIP_TRY(m->faces_d.upload(m->faces_host));        // (blocking uploads; faces_d last: it is the "built" flag)
-    }
+    if (!m->topo.built()) HIP_TRY(m->topo.build(m->faces_host, nv));
     lazy.unlock();
     const size_t nv3 = (size_t)F * nv * 3;
     if (!b->disp.p) {
@@ -41,25 +34,26 @@ int bf_fit_displacement(bf_batch *b, int n_iters, const bf_hyper *hyper) {
     HIP_TRY(hipMemsetAsync(b->disp_v.p, 0, nv3 * sizeof(float), b->stream));
     HIP_TRY(hipMemcpyAsync(b->disp_base.p, b->vout.p, nv3 * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
     const dim3 gv((nv + 255) / 256, F), gf((nf + 255) / 256, F);
+    const int *faces = m->topo.faces.p, *adj_start = m->topo.adj_start.p, *adj = m->topo.adj.p;
     const int nblk = (nv + 255) / 256;
     const double b1 = h.adam_beta1, b2 = h.adam_beta2;
     for (int it = 1; it <= n_iters; ++it) {
-        hipLaunchKernelGGL(bf_disp_face_kernel, gf, dim3(256), 0, b->stream, (const int *)m->faces_d.p, nf, nv,
+        hipLaunchKernelGGL(bf_disp_face_kernel, gf, dim3(256), 0, b->stream, faces, nf, nv,
                            (const float *)b->disp_base.p, (const float *)b->disp.p, b->disp_fn.p);
-        hipLaunchKernelGGL(bf_disp_vertex_kernel, gv, dim3(256), 0, b->stream, (const int *)m->adj_start.p, (const int *)m->adj.p, nf, nv,
+        hipLaunchKernelGGL(bf_disp_vertex_kernel, gv, dim3(256), 0, b->stream, adj_start, adj, nf, nv,
                            (const float *)b->disp_base.p, (const float *)b->disp.p, (const float *)b->disp_fn.p, b->disp_P.p, b->disp_vn.p);
         bf_nearest_launch(dim3((nv + 3) / 4, F), b->stream, (const ScanDev *)b->scan_dev.p, (const float *)b->disp_P.p, nv,
                           b->cface.p, b->cpts.p, (float *)nullptr, b->cface_valid ? 1 : 0);
         b->cface_valid = true;
-        hipLaunchKernelGGL(bf_disp_vgrad_kernel, gv, dim3(256), 0, b->stream, (const int *)m->faces_d.p, (const int *)m->adj_start.p,
-                           (const int *)m->adj.p, nf, nv, (const float *)b->disp_vn.p, (const float *const *)b->scan_fn.p,
+        hipLaunchKernelGGL(bf_disp_vgrad_kernel, gv, dim3(256), 0, b->stream, faces, adj_start, adj, nf, nv,
+                           (const float *)b->disp_vn.p, (const float *const *)b->scan_fn.p,
                            (const int *)b->cface.p, (const float *)b->cscale.p, b->disp_dv.p, (const float *)b->disp_P.p,
                            (const float *)b->cpts.p, b->pc_partial.p);      // (+ the block sums of |P - C|^2: was bf_pc_partial_kernel)
-        hipLaunchKernelGGL(bf_disp_fgrad_kernel, gf, dim3(256), 0, b->stream, (const int *)m->faces_d.p, nf, nv, (const float *)b->disp_P.p,
+        hipLaunchKernelGGL(bf_disp_fgrad_kernel, gf, dim3(256), 0, b->stream, faces, nf, nv, (const float *)b->disp_P.p,
                            (const float *)b->disp_fn.p, (const float *)b->disp_dv.p, b->disp_dPf.p);
         const float step_size = (float)((double)h.lr_displacement / (1.0 - std::pow(b1, it)));
         const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, it));
-        hipLaunchKernelGGL(bf_disp_adam_kernel, gv, dim3(256), 0, b->stream, (const int *)m->adj_start.p, (const int *)m->adj.p, nf, nv,
+        hipLaunchKernelGGL(bf_disp_adam_kernel, gv, dim3(256), 0, b->stream, adj_start, adj, nf, nv,
                            (const float *)b->disp_P.p, (const float *)b->cpts.p, (const float *)b->pc_partial.p, nblk,
                            (const float *)b->disp_dPf.p, b->disp.p, b->disp_m.p, b->disp_v.p, step_size, bc2_sqrt, h.adam_beta1,
                            h.adam_beta2, h.adam_eps);

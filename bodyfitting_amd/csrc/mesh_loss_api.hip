@@ -13,7 +13,7 @@
 
 struct bf_topo {
     int device = 0, nv = 0, nf = 0;
-    DevBuf<int> faces, adj_start, adj;
+    BfTopoDev d;
 };
 
 namespace {
@@ -44,14 +44,10 @@ extern "C" int bf_topo_create(int device, int n_verts, int n_faces, const int32_
     const size_t n3 = (size_t)n_faces * 3;
     for (size_t i = 0; i < n3; ++i)
         if (faces[i] < 0 || faces[i] >= n_verts) return fail(BF_ERR_INVALID, std::string(who) + ": face index out of range");
-    std::vector<int> host(faces, faces + n3), start, adj;
-    bf_build_vertex_adjacency(host, n_verts, start, adj);
     HIP_TRY(hipSetDevice(device));
     std::unique_ptr<bf_topo> t(new bf_topo);
     t->device = device; t->nv = n_verts; t->nf = n_faces;
-    HIP_TRY(t->faces.upload(host));
-    HIP_TRY(t->adj_start.upload(start));
-    HIP_TRY(t->adj.upload(adj));
+    HIP_TRY(t->d.build(std::vector<int>(faces, faces + n3), n_verts));
     *out = t.release();
     return BF_OK;
 }
@@ -68,8 +64,8 @@ extern "C" void bf_topo_destroy(bf_topo *t) {
 namespace {
 // face and vertex normals of `d_v` on the device (the forward, and the first half of the reverse)
 int bf_ml_normals_launch(const bf_topo *t, const float *d_v, float *d_fn, float *d_vn, float *d_out, hipStream_t st) {
-    hipLaunchKernelGGL(bf_ml_face_kernel, dim3(blocks(t->nf)), dim3(256), 0, st, (const int *)t->faces.p, t->nf, d_v, d_fn);
-    hipLaunchKernelGGL(bf_ml_vertex_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->adj_start.p, (const int *)t->adj.p, t->nv,
+    hipLaunchKernelGGL(bf_ml_face_kernel, dim3(blocks(t->nf)), dim3(256), 0, st, (const int *)t->d.faces.p, t->nf, d_v, d_fn);
+    hipLaunchKernelGGL(bf_ml_vertex_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->d.adj_start.p, (const int *)t->d.adj.p, t->nv,
                        (const float *)d_fn, d_vn, d_out);
     HIP_TRY(hipGetLastError());
     return BF_OK;
@@ -103,9 +99,9 @@ int bf_ml_normals_vjp(BfRouteCall &c, const bf_topo *t, const float *verts, cons
     BF_TRY(c.out(dverts, nv * 3, d_dv));
     BF_TRY(bf_ml_normals_launch(t, d_v, d_fn, d_vn, nullptr, st));
     hipLaunchKernelGGL(bf_ml_vraw_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, t->nv, (const float *)d_vn, d_dn, d_raw);
-    hipLaunchKernelGGL(bf_ml_fgrad_kernel, dim3(blocks(t->nf)), dim3(256), 0, st, (const int *)t->faces.p, t->nf, d_v, (const float *)d_fn,
+    hipLaunchKernelGGL(bf_ml_fgrad_kernel, dim3(blocks(t->nf)), dim3(256), 0, st, (const int *)t->d.faces.p, t->nf, d_v, (const float *)d_fn,
                        (const float *)d_raw, d_dPf);
-    hipLaunchKernelGGL(bf_ml_gather_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->adj_start.p, (const int *)t->adj.p, t->nv,
+    hipLaunchKernelGGL(bf_ml_gather_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->d.adj_start.p, (const int *)t->d.adj.p, t->nv,
                        (const float *)d_dPf, d_dv);
     return c.finish();
 }
@@ -121,13 +117,13 @@ int bf_ml_laplacian(BfRouteCall &c, const bf_topo *t, const float *norms, float 
     if (loss) {
         BF_TRY(c.scratch(nblk, d_part));
         BF_TRY(c.out(loss, 1, d_loss));
-        hipLaunchKernelGGL(bf_ml_lap_partial_kernel, dim3(nblk), dim3(256), 0, st, (const int *)t->faces.p, t->nf, d_n, d_part);
+        hipLaunchKernelGGL(bf_ml_lap_partial_kernel, dim3(nblk), dim3(256), 0, st, (const int *)t->d.faces.p, t->nf, d_n, d_part);
         bf_ml_finish_launch(c, d_part, nblk, 0, (float)t->nf, d_loss);
     }
     if (dnorms) {
         BF_TRY(c.out(dnorms, (size_t)t->nv * 3, d_dn));
-        hipLaunchKernelGGL(bf_ml_lap_grad_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->faces.p, (const int *)t->adj_start.p,
-                           (const int *)t->adj.p, t->nf, t->nv, d_n, d_dn);
+        hipLaunchKernelGGL(bf_ml_lap_grad_kernel, dim3(blocks(t->nv)), dim3(256), 0, st, (const int *)t->d.faces.p, (const int *)t->d.adj_start.p,
+                           (const int *)t->d.adj.p, t->nf, t->nv, d_n, d_dn);
     }
     return c.finish();
 }

@@ -17,6 +17,7 @@
 #include "bf_internal.h"
 #include "loss_bodies.h"
 #include "joints_body.h"
+#include "mesh_normal_bodies.h"
 #include "scan_kernels.h"
 #include "../../include/bodyfit.h"
 #include <cstdlib>
@@ -495,11 +496,7 @@ bf_pc_partial_kernel(const float *__restrict__ P, const float *__restrict__ C, i
     __shared__ float s[4];
     const int id = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
     float a = 0.f;
-    if (id < n) {
-        const float *p = P + ((size_t)f * n + id) * 3, *c = C + ((size_t)f * n + id) * 3;
-        float d0 = p[0] - c[0], d1 = p[1] - c[1], d2 = p[2] - c[2];
-        a = d0 * d0 + d1 * d1 + d2 * d2;
-    }
+    if (id < n) a = bf_sqdist_row(P + ((size_t)f * n + id) * 3, C + ((size_t)f * n + id) * 3);
     a = bf_wave_sum(a);
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = a;
     __syncthreads();

@@ -3,8 +3,8 @@
 // same order, so a different order is a different function with a different name - never an edit to one of these.
 // Reductions that are NOT these, on purpose: the ascending butterflies (1, 2, 4, ..) of expr_kernels.hip and joints_body.h, the
 // quad sum of kp_loss_kernels.hip, the DPP / readlane minima of scan_kernels.hip and the fit kernel's DPP row sums.
-// Two sites keep the descending loop written out, because folding them moved an instruction of their kernel (profiles/helper_fold.md):
-// bf_disp_vgrad_kernel (disp_kernels.hip) and the unsigned byte sum of bf_views_prepare_kernel (views_kernels.hip).
+// One site keeps the descending loop written out, because folding it moved an instruction of its kernel (profiles/helper_fold.md):
+// the unsigned byte sum of bf_views_prepare_kernel (views_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

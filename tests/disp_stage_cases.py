@@ -24,7 +24,7 @@ from oracle import nearest_ref as NR
 
 MODEL = "smpl690"                    # dense_grad_cases' name of S.make_model("smpl", seed=0, nv=690)
 NV = 690
-ADJ_BATCH = SC.ADJ_BATCH             # BF_ADJ_BATCH of csrc/disp_kernels.hip
+ADJ_BATCH = SC.ADJ_BATCH             # BF_ADJ_BATCH of csrc/mesh_normal_bodies.h
 FACE_BLOCK_EDGE = 5 * SC.BLOCK       # 1280: five full blocks of bf_disp_face_kernel / bf_disp_fgrad_kernel
 HUBS = (8, 9, 16, 17, 25)            # one full batch, one entry more, two full batches, a third batch, a fourth
 FACE_COUNTS = (FACE_BLOCK_EDGE - 1, FACE_BLOCK_EDGE, FACE_BLOCK_EDGE + 1)

@@ -18,7 +18,7 @@ import torch
 from bodyfitting_amd import synthetic as S
 from oracle import mesh_oracle as MO
 
-ADJ_BATCH = 8                      # BF_ADJ_BATCH of csrc/mesh_loss_kernels.hip: incident faces walked together
+ADJ_BATCH = 8                      # BF_ADJ_BATCH of csrc/mesh_normal_bodies.h: incident faces walked together
 BLOCK = 256                        # threads per block = faces, vertices or points per block sum
 WELL_POSED = 1e-5
 
