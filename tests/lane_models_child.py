@@ -47,6 +47,7 @@ def models(out_path, width, fill, lanes=None):
             sys.path.insert(0, repo)
         from bodyfitting_amd import _lib, native as N, synthetic as S
         from width_variants import Variants, smpl_problem
+        import loss_grad_cases as LC
         fast = _lib.FIT_RESET | _lib.FIT_FETCH | _lib.FIT_NOTIME
         variants = Variants(S.make_gmm(seed=0))
         out = {}
@@ -61,6 +62,13 @@ def models(out_path, width, fill, lanes=None):
                 got = []
                 for s in range(n_sets):
                     c2w, K, kp, _, betas, pose = N.pack_problem([smpl_problem(name, model, frame=base + 10 * s + f, n_views=VIEWS) for f in range(n_frames)])
+                    if (n_frames, base, s) == (1, 0, 1):
+                        # the second streamed frame starts with its root at 2 pi + 1e-3 and a leaf of the chain (joint 20) at 4.7 rad
+                        # (axis R of tests/loss_grad_cases.py): past the wrap and in quadrant 3 of the fit kernel's sine / cosine
+                        assert pose.shape == (1, 72)
+                        pose = pose.copy()
+                        pose[0, 0:3] = LC.Sweep(2 * LC.PI + 1e-3, "general", "root").theta
+                        pose[0, 60:63] = LC.Sweep(4.7, "-y", "leaf").theta
                     got.append((c2w, K, kp, ndiv_of(s, n_frames), betas, pose))
                 return got
 

@@ -1,7 +1,9 @@
 """The hand-derived gradient of the multi-view keypoint objective, swept: bf_loss_grad (fit_kernels.hip's sized SMPL instance and
 its table-driven instance; for SMPL-X bf_kp_loss_body + joints_body.h) against float64 torch autograd of oracle/smplify_oracle.py
 at every case of tests/loss_grad_cases.py - view counts across every staging edge of both kernels, all 79 face-contour rows, every
-GMM component, non-default hyper-parameters, prior / pose extremes and keypoint edges - and, for a subset, ten Adam steps from the
+GMM component, non-default hyper-parameters, prior / pose extremes, keypoint edges and one joint angle swept from 1e-6 rad to beyond
+4 pi (axis R: every quadrant, wrap and rounding edge of sincos_small, either side of rodrigues_fwd's Taylor switch;
+profiles/rodrigues_sweep.md) - and, for a subset, ten Adam steps from the
 case's point against the oracle's loop (the loop consumes the same gradient).  tests/test_loss_grad_cases.py proves on the CPU
 that every case is well posed, so nothing is skipped or filtered here: every case, every term, every component of every block.
 
@@ -195,4 +197,15 @@ def test_report():
         w = max(rows, key=lambda r: r[3] / r[6])
         ratio = max((r[3] / r[5] for r in rows if r[5] > 0), default=float("nan"))
         print(f"{axis} | {len({r[1] for r in rows})} | {len(rows)} | {w[1]} : {w[2]} | {w[3] / w[4]:.2e} | {w[5] / w[4]:.2e} | {w[3] / w[6]:.3f} | {ratio:.1f}")
+    # axis R by angle group and parameter block (profiles/rodrigues_sweep.md)
+    group = {c.id: c.group for c in CASES if c.axis == "R"}
+    print("\nR: angle group | block | blocks | worst case | err / M | err32 / M | err / band | worst err / err32")
+    for g in ("near zero", "rounding edges of n", "centres and wrap", "far"):
+        for k in LC.O.SMPLX_PARAMS:
+            rows = [r for r in RESULTS if r[0] == "R" and group[r[1]] == g and r[2] == k]
+            if not rows:
+                continue
+            w = max(rows, key=lambda r: r[3] / r[6])
+            ratio = max((r[3] / r[5] for r in rows if r[5] > 0), default=float("nan"))
+            print(f"{g} | {k} | {len(rows)} | {w[1]} | {w[3] / w[4]:.2e} | {w[5] / w[4]:.2e} | {w[3] / w[6]:.3f} | {ratio:.1f}")
     assert all(np.isfinite(r[3]) for r in RESULTS)

@@ -598,3 +598,40 @@ def test_smplify_stream_yields_the_frames_of_the_call_path(smpl_model, gmm):
     with pytest.raises(ValueError):
         list(fitter.stream([((p["init_betas"], p["init_pose"]), kps, [np.zeros((64, 64), np.uint8)] * 1)], *args, use_frames=sub, mask_frames=None))
     fitter.close()
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# the joint-angle sweep through the pose-state forward (tests/model_sweep_cases.py): m_rodrigues from 1e-6 rad to beyond 4 pi
+# --------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module", params=["smpl", "kid"])
+def sweep_dev(request):
+    import model_sweep_cases as MS
+    dev = N.DeviceModel(MS.model(request.param), S.make_gmm(seed=0), device=0)
+    yield request.param, dev
+    dev.close()
+
+
+def _sweep_forward(dev, p, lo, hi):
+    verts, joints, jori = dev.forward(p["betas"][lo:hi], p["global_orient"][lo:hi], p["body_pose"][lo:hi])
+    return {"vertices": verts, "joints": joints, "joints_ori": jori}
+
+
+def test_angle_sweep_forward_matches_the_oracle_frame_by_frame(sweep_dev):
+    """every angle, axis and joint set of axis R as one batch (>= 16 frames: the matrix-core mesh pass behind the pose state), in
+    calls of five frames (the multi-frame kernel) and frame by frame: vertices, joints and joints_ori of EVERY frame within
+    max(3e-6, 8 * err32) of the float64 oracle; below 16 frames a frame's bits do not depend on its neighbours"""
+    import model_sweep_cases as MS
+    kind, dev = sweep_dev
+    p, n = MS.params(kind), len(MS.frames(kind))
+    assert dev.n_verts == 690 and dev.n_betas == p["betas"].shape[1]
+    MS.check_forward(kind, _sweep_forward(dev, p, 0, n), what="forward, one batch")
+    alone = [_sweep_forward(dev, p, f, f + 1) for f in range(n)]
+    MS.check_forward(kind, {k: np.concatenate([a[k] for a in alone]) for k in alone[0]}, what="forward, frame alone")
+    for lo in range(0, n, 5):
+        got = _sweep_forward(dev, p, lo, min(lo + 5, n))
+        MS.check_forward(kind, got, first=lo, what="forward, five frames")
+        for k, v in got.items():
+            for i in range(len(v)):
+                assert np.array_equal(v[i], alone[lo + i][k][0]), (kind, k, lo + i, MS.frames(kind)[lo + i].name)
+    MS.report(kind)

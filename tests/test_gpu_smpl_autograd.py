@@ -224,3 +224,30 @@ def test_oracle_loop_on_the_hip_model_holds_cfg2(monkeypatch, dropin, smpl_model
         band = max(FIT_TOL, RD.K * own)
         print("cfg2 frame 3 global_transl:", RD.position(err, owns))
     np.testing.assert_allclose(res["global_transl"], g["final_global_transl"], atol=band)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# the joint-angle sweep through the reverse of the chain (tests/model_sweep_cases.py): vjp_rodrigues from 1e-6 rad to beyond 4 pi
+# --------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("kind", ["smpl", "kid"])
+def test_vjp_over_the_angle_sweep_matches_fp64_autograd_frame_by_frame(kind):
+    """every angle, axis and joint set of axis R as the frames of one batch of the 690-vertex model, cotangents "all" and "joints":
+    _band_check's band per FRAME and gradient block, and once more on the pose-gradient row of every swept joint against that row's
+    own float64 maximum and float32 error (a block-wide maximum would wave a lone small joint's error through)"""
+    import model_sweep_cases as MS
+    model = MS.model(kind)
+    dev = N.DeviceModel(model, S.make_gmm(seed=0), device=0)
+    try:
+        p, n = MS.params(kind), len(MS.frames(kind))
+        cot = _cotangents(n, dev, 400)
+        args = (p["betas"], p["global_orient"], p["body_pose"])
+        g64 = _torch_grads(model, torch.float64, *args, cot)
+        g32 = _torch_grads(model, torch.float32, *args, cot)
+        for case in ("all", "joints"):
+            kw = {arg: cot[k] if case in (k, "all") else None for k, arg in (("vertices", "dverts"), ("joints", "djoints"), ("joints_ori", "djoints_ori"))}
+            got = dev.vjp(*args, **kw)
+            MS.check_vjp(kind, case, ["betas", "global_orient", "body_pose"], got, g32[case], g64[case])
+        MS.report(kind)
+    finally:
+        dev.close()

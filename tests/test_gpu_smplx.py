@@ -346,3 +346,38 @@ def test_stream_of_smplx_frames_with_silhouettes_equals_the_call_path(sx, tmp_pa
         for key in ("vertices", "joints", "pose", "betas", "global_orient", "global_transl", "scale", "full_pose", "left_hand_pose", "leye_pose"):
             assert np.array_equal(res[key], one[key]), (i, key)
     fitter.close()
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# the joint-angle sweep through the pose-state forward (tests/model_sweep_cases.py): m_rodrigues from 1e-6 rad to beyond 4 pi
+# --------------------------------------------------------------------------------------------------------------------------------
+
+def test_angle_sweep_forward_matches_the_oracle_frame_by_frame():
+    """every angle, axis and joint set of axis R, and the jaw and the left eye, as one batch of the 1,200-vertex model (>= 16 frames:
+    the matrix-core mesh pass behind the pose state), in calls of five frames (the multi-frame kernel) and frame by frame: vertices,
+    the 135 mapped joints, all joints, the full pose and the contour row of EVERY frame against the float64 oracle, the floats
+    within max(3e-6, 8 * err32); below 16 frames a frame's bits do not depend on its neighbours"""
+    import model_sweep_cases as MS
+    dev = N.DeviceModel(MS.model("smplx"), S.make_gmm(seed=0), device=0)
+    try:
+        p, n = MS.params("smplx"), len(MS.frames("smplx"))
+        rows = MS.forward_oracle("smplx")[0]["dyn_row"]
+
+        def forward(lo, hi, what):
+            got = dev.forward_smplx(**{k: v[lo:hi] for k, v in p.items()})
+            np.testing.assert_array_equal(got["dyn_row"], rows[lo:hi], err_msg=what)
+            got = {k: got[k] for k in ("vertices", "joints", "joints_all", "full_pose")}
+            MS.check_forward("smplx", got, first=lo, what=what)
+            return got
+
+        assert dev.n_verts == 1200
+        forward(0, n, "forward, one batch")
+        alone = [forward(f, f + 1, "forward, frame alone") for f in range(n)]
+        for lo in range(0, n, 5):
+            got = forward(lo, min(lo + 5, n), "forward, five frames")
+            for k, v in got.items():
+                for i in range(len(v)):
+                    assert np.array_equal(v[i], alone[lo + i][k][0]), (k, lo + i, MS.frames("smplx")[lo + i].name)
+        MS.report("smplx")
+    finally:
+        dev.close()

@@ -290,3 +290,26 @@ def test_oracle_loop_on_the_hip_model_holds_the_smplx_golden(monkeypatch, dropin
     np.testing.assert_allclose(res["joints"], g["joints"], rtol=0, atol=FIT_TOL)
     np.testing.assert_allclose(res["vertices"][::53], g["vertices_sample"], rtol=0, atol=FIT_TOL)
     np.testing.assert_allclose(res["full_pose"], g["full_pose"], rtol=0, atol=FIT_TOL)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# the joint-angle sweep through the reverse of the chain (tests/model_sweep_cases.py): vjp_rodrigues from 1e-6 rad to beyond 4 pi
+# --------------------------------------------------------------------------------------------------------------------------------
+
+def test_vjp_over_the_angle_sweep_matches_fp64_autograd_frame_by_frame(small):
+    """every angle, axis and joint set of axis R, and the jaw and the left eye, as the frames of one batch of the 1,200-vertex model,
+    cotangents "all" and "joints": _band_check's band per FRAME and gradient block, and once more on the pose-gradient row of every
+    swept joint against that row's own float64 maximum and float32 error"""
+    import model_sweep_cases as MS
+    model, dev = small
+    assert model["v_template"].shape == MS.model("smplx")["v_template"].shape
+    p, n = dict(MS.params("smplx")), len(MS.frames("smplx"))
+    cot = _cotangents(n, dev, 400)
+    np.testing.assert_array_equal(dev.forward_smplx(**p)["dyn_row"], MS.forward_oracle("smplx")[0]["dyn_row"])
+    g64 = _torch_grads(model, torch.float64, p, cot)
+    g32 = _torch_grads(model, torch.float32, p, cot)
+    for case in ("all", "joints"):
+        kw = {COT_ARG[k]: cot[k] for k in COT_ARG if case in (k, "all")}
+        got = dev.vjp_smplx(**p, **kw)
+        MS.check_vjp("smplx", case, list(INPUTS), got, g32[case], g64[case])
+    MS.report("smplx")

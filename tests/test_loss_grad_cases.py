@@ -8,6 +8,8 @@ tests/test_gpu_loss_grad_sweep.py never has to leave a case, a view, a joint or 
     reference's own float32 arithmetic is worse than that would be ill conditioned and gets rebuilt, not banded;
   * axis C: the neck sweep reaches exactly the rows 0..78 and every yaw stays clear of a rounding boundary;
   * axis D: the GMM arg-min is the intended component with more than 0.5 to the runner-up (float32 cannot flip it);
+  * axis R: the swept angles reach every quadrant of the fit kernel's sine / cosine on every model kind, its wrap (n >= 4, n >= 8),
+    both sides of u = 1e-3 and an angle whose float32 cosine is 1; SMPL-X yaws stay 1e-3 degrees from a rounding boundary;
   * axis H: the oracle's float32 and float64 loops from the case's point agree to 1e-5 after the ten steps.
 """
 import functools
@@ -42,13 +44,42 @@ def test_the_sweep_covers_every_axis():
         assert any(c.size == "full" for c in cases), a
     # H: one case per view-count regime of A and B, two contour rows >= 40, two GMM components, the all-at-once hypers
     loops = LC.loop_cases()
-    assert {c.axis for c in loops} == {"A", "B", "C", "D", "E"}
+    assert {c.axis for c in loops} == {"A", "B", "C", "D", "E", "R"}
     va = {c.n_views for c in loops if c.axis == "A"}
     assert min(va) <= 16 and any(16 < v <= 48 for v in va) and any(v > 48 for v in va)
     vb = {c.n_views for c in loops if c.axis == "B"}
     assert any(v <= 118 for v in vb) and any(v >= 119 for v in vb)
     assert sum(c.axis == "C" for c in loops) >= 2 and sum(c.axis == "D" for c in loops) >= 2
     assert any(c.axis == "E" and len(c.hyper) == len(LC.HYPER_KEYS) for c in loops)
+    # R: properties of the INPUTS, in the float32 terms of the fit kernel's sincos_small and rodrigues_fwd (a = ||theta + 1e-8||,
+    # u = a * a, n = rint(a * 0.636619772)), read off the cases' own parameters
+    def numbers(cases):
+        got = []
+        for c in cases:
+            full = np.concatenate([c.params["global_orient"], c.params["pose"]] + ([np.zeros(3), c.params["leye_pose"]] if c.kind == "smplx" else []))
+            for j, th in c.swept.items():
+                assert np.array_equal(full[3 * j:3 * j + 3], th), (c.id, j)              # the case carries the swept vector unchanged
+                got.append(LC.sweep_numbers(full[3 * j:3 * j + 3]))
+        return got
+    for kind in ("smpl", "kid", "smplx"):
+        assert {n & 3 for _, _, n, _ in numbers(c for c in per_axis["R"] if c.kind == kind)} == {0, 1, 2, 3}, kind
+        assert any(n >= 4 for _, _, n, _ in numbers(c for c in per_axis["R"] if c.kind == kind)), kind
+    for kind in ("smpl", "smplx"):
+        small = numbers(c for c in per_axis["R"] if c.kind == kind and c.size == "small")
+        assert any(n >= 8 for _, _, n, _ in small), kind
+        assert any(u < np.float32(1e-3) for _, u, _, _ in small) and any(np.float32(1e-3) <= u < np.float32(1.01e-3) for _, u, _, _ in small), kind
+        assert any(cos_a == 1.0 and a != 0.0 for a, _, _, cos_a in small), kind          # 1 - cos a has no bits left
+        # exact coordinate axes, one of them with a negative zero; the general direction; the angles of R_ALL_AXES_AT on all four
+        vecs = [th for c in per_axis["R"] if c.kind == kind for th in c.swept.values()]
+        assert any(np.count_nonzero(th) == 1 and np.signbit(th[th == 0.0]).any() for th in vecs) and any(np.count_nonzero(th) == 3 for th in vecs)
+    for a in LC.R_ALL_AXES_AT:
+        assert {s.axis for s in LC.sweep() if s.a == a} == set(LC.R_AXIS_NAMES), a
+    # the loops: a leaf in quadrant 3, a root whose steps cross the wrap at 2 pi, a spine joint whose steps cross u = 1e-3
+    assert sorted((c.kind, c.name.split("-")[0], c.name.rsplit("-", 1)[1]) for c in loops if c.axis == "R") == \
+        [("smpl", "2pi", "root"), ("smpl", "4.7", "leaf"), ("smplx", "0.0318", "spine")]
+    # no swept rotation on the knees and elbows but the one declared pair
+    for c in per_axis["R"]:
+        assert all(j not in (4, 5, 18, 19) for j in c.swept) or "knee" in c.name, c.id
 
 
 @pytest.mark.parametrize("i", range(len(CASES)), ids=IDS)
@@ -88,6 +119,20 @@ def test_neck_sweep_reaches_every_contour_row():
     assert all(40 <= rows[d] <= 78 for d in range(1, 45)) and rows[0] == 0
     chain = [_oracles(i)[0]["row"] for i, c in enumerate(CASES) if c.axis == "C" and c.name.startswith("chain")]
     assert len(chain) == 3 and max(chain) >= 40
+
+
+def test_axis_r_contour_rows_stay_clear_of_a_rounding_boundary():
+    """a swept root or spine joint turns the neck: -yaw of every SMPL-X case of axis R sits 1e-3 degrees or more (ROW_MARGIN of
+    tests/test_gpu_smplx_autograd.py) from a rounding boundary of the contour row, and float32 picks the float64 row"""
+    n = 0
+    for i, c in enumerate(CASES):
+        if c.axis == "R" and c.kind == "smplx":
+            y = LC.neck_yaw_degrees(c)
+            assert abs(y - 0.5 - round(y - 0.5)) >= 1e-3, (c.id, y)
+            o64, o32 = _oracles(i)
+            assert 0 <= o64["row"] <= 78 and o32["row"] == o64["row"], c.id
+            n += 1
+    assert n > 30
 
 
 @pytest.mark.parametrize("c", LC.loop_cases(), ids=[c.id for c in LC.loop_cases()])
