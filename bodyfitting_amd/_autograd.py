@@ -28,11 +28,11 @@ def enabled():
     return _ENABLED[0]
 
 
-def route_for(inputs, device_index, enabled, shares_runtime):
+def route_for(inputs, device_index, enabled, shares_runtime, dtypes=("torch.float32",)):
     """-> "device" or "host".  inputs: tensors, arrays or None (an argument not passed); device_index: the GPU of the native object
     that offers a device route (None: it offers none); enabled: the switch; shares_runtime: torch's memory is the library's.
     "device" only when a route is offered, the switch is on, the runtimes are shared and every present input is a float32 tensor
-    on cuda:device_index - and there is one."""
+    on cuda:device_index - and there is one.  dtypes: what the entry reads instead of float32 (the silhouette's masks)."""
     if device_index is None or not enabled or not shares_runtime:
         return "host"
     present = [t for t in inputs if t is not None]
@@ -40,7 +40,7 @@ def route_for(inputs, device_index, enabled, shares_runtime):
         return "host"
     for t in present:
         device = getattr(t, "device", None)
-        if getattr(device, "type", None) != "cuda" or device.index != int(device_index) or str(getattr(t, "dtype", None)) != "torch.float32":
+        if getattr(device, "type", None) != "cuda" or device.index != int(device_index) or str(getattr(t, "dtype", None)) not in dtypes:
             return "host"
     return "device"
 
@@ -58,13 +58,13 @@ def shares_runtime(device_index, address):
     return _SHARED[device_index]
 
 
-def chosen_route(inputs, device_route):
+def chosen_route(inputs, device_route, dtypes=("torch.float32",)):
     """the route `apply` takes for these inputs"""
     device_index = None if device_route is None else device_route.device
-    if route_for(inputs, device_index, enabled(), True) != "device":
+    if route_for(inputs, device_index, enabled(), True, dtypes) != "device":
         return "host"
     address = next(t for t in inputs if t is not None).data_ptr()
-    return route_for(inputs, device_index, True, shares_runtime(device_index, address))
+    return route_for(inputs, device_index, True, shares_runtime(device_index, address), dtypes)
 
 
 def apply(forward, vjp, inputs, device_route=None):

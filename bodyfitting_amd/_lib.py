@@ -172,6 +172,10 @@ SIGNATURES = {
     "bf_silhouette_destroy": (None, [_VP]),
     "bf_silhouette_contours": (C.c_int, [_VP, _IP, _FP]),
     "bf_silhouette_loss": (C.c_int, [_VP, C.c_int, C.c_int, _FP, _FP, _FP, C.c_float, C.c_float, C.c_int, _FP, _FP, _FP]),
+    "bf_silhouette_create_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, _VP, C.POINTER(_VP)]),
+    "bf_silhouette_contours_dev": (C.c_int, [_VP, _VP, _VP]),
+    "bf_silhouette_rows_dev": (C.c_int, [C.c_int, C.c_int, _VP, _VP, _VP, _VP]),
+    "bf_silhouette_loss_dev": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_float, C.c_float, C.c_int, _VP, _VP, _VP, _VP]),
     "bf_fit_displacement": (C.c_int, [_VP, C.c_int, C.POINTER(Hyper)]),
     "bf_batch_get_displacement": (C.c_int, [_VP, _FP]),
     "bf_batch_last_timing": (C.c_int, [_VP, _FP]),

@@ -7,4 +7,7 @@ extern "C" __global__ void bf_sil_project_kernel(MaskIO K, const float *verts, c
 extern "C" __global__ void bf_sil_contour_kernel(MaskIO K, const float *uvi, float *loss_part);
 extern "C" __global__ void bf_sil_finish_kernel(MaskIO K, const float *proj, const float *uvi, const float *duvb, const float *loss_part, float *terms,
                                                 float *dverts);
+extern "C" __global__ void bf_sil_ingest_kernel(const void *masks, int is_float, unsigned long long npix, unsigned plane, unsigned *bin, int *flags,
+                                                int n_views);
+extern "C" __global__ void bf_sil_rows_kernel(const float *K, const float *w2c, int n_views, float *rows);
 #pragma GCC visibility pop

@@ -12,6 +12,11 @@
 //                           full, zeros at unsampled vertices included; its last block reduces the block sums to view_terms[M,2]
 //                           and the loss, in an order that depends on the view's own sizes alone
 // The per-vertex and per-contour-point arithmetic is loss_bodies.h's, shared with the fused fit: the two paths cannot drift apart.
+//
+// Two more for the device route (bf_silhouette_create_dev, bf_silhouette_loss_dev), where masks and cameras are device arrays:
+//   bf_sil_ingest_kernel    masks in the caller's type -> the object's 0 / 1 bytes, a "has foreground" flag per view and one "holds
+//                           a value other than 0 / 1" flag
+//   bf_sil_rows_kernel      thread = row element: the 3 x 4 rows K [R|t] of every view, the host loop's expression in double
 #include "bf_internal.h"
 #include "loss_bodies.h"
 #include "silhouette_kernels.h"
@@ -103,4 +108,63 @@ bf_sil_finish_kernel(MaskIO K, const float *__restrict__ proj, const float *__re
     }
     float *o = dverts + (size_t)v * 3;
     o[0] = g0; o[1] = g1; o[2] = g2;
+}
+
+// grid ceil(ceil(npix / 4) / 256), 256 threads; thread = four consecutive pixels of masks[M][H][W] (float32, or one byte per pixel:
+// uint8 / bool), read element by element - the array is aligned to its element and no further - and stored as ONE word of the
+// object's bytes bin[ceil(npix / 4) * 4] (1 = foreground; the bytes behind npix are written as 0).  flags[M + 1], zeroed by the
+// caller: flags[m] |= 1 when view m has a foreground pixel, flags[M] |= 1 when a pixel is neither 0 nor 1 (a NaN is neither).  A
+// block whose pixels lie in one view raises that view's flag once, through LDS; a block across views (small images) per thread.
+extern "C" __global__ void __launch_bounds__(256)
+bf_sil_ingest_kernel(const void *__restrict__ masks, int is_float, unsigned long long npix, unsigned plane, unsigned *__restrict__ bin,
+                     int *__restrict__ flags, int n_views) {
+    __shared__ int any_fg, any_bad;
+    if (threadIdx.x == 0) { any_fg = 0; any_bad = 0; }
+    __syncthreads();
+    const unsigned long long block_first = (unsigned long long)blockIdx.x * 1024u;
+    const unsigned long long block_last = min(block_first + 1023u, npix - 1);
+    const bool one_view = block_first / plane == block_last / plane;
+    const unsigned long long first = block_first + (unsigned long long)threadIdx.x * 4u;
+    if (first < npix) {
+        unsigned word = 0;
+        bool bad = false;
+        for (unsigned j = 0; j < 4; ++j) {
+            const unsigned long long i = first + j;
+            if (i >= npix) break;
+            bool fg;
+            if (is_float) {
+                const float x = ((const float *)masks)[i];
+                fg = x == 1.f;
+                bad |= !(fg || x == 0.f);
+            } else {
+                const unsigned char x = ((const unsigned char *)masks)[i];
+                fg = x == 1;
+                bad |= x > 1;
+            }
+            if (fg) {
+                word |= 1u << (8 * j);
+                if (one_view) any_fg = 1;          // (a race on purpose, here and for any_bad: every writer stores 1, the read is behind the barrier)
+                else atomicOr(&flags[i / plane], 1);
+            }
+        }
+        bin[first / 4] = word;
+        if (bad) any_bad = 1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (any_fg) atomicOr(&flags[block_first / plane], 1);
+        if (any_bad) atomicOr(&flags[n_views], 1);
+    }
+}
+
+// grid ceil(12 M / 256), 256 threads; thread = one element of rows[M][3][4] = K [R|t] from K[M][3][3] and w2c[M][4][4] (rows 0..2).
+extern "C" __global__ void __launch_bounds__(256)
+bf_sil_rows_kernel(const float *__restrict__ K, const float *__restrict__ w2c, int n_views, float *__restrict__ rows) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_views * 12) return;
+    const int i = e / 12, r = (e % 12) / 4, c = e % 4;
+    const float *k = K + (size_t)i * 9 + r * 3, *w = w2c + (size_t)i * 16 + c;
+    // bf_silhouette_loss' host expression, summed left to right.  A product of two float32 values is exact in double (24 + 24 bits
+    // of significand in 53), so a * b + c rounds once whether the compiler fuses it or not: these are the host loop's bits.
+    rows[e] = (float)((double)k[0] * w[0] + (double)k[1] * w[4] + (double)k[2] * w[8]);
 }

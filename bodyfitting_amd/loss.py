@@ -27,7 +27,9 @@ tensors; anything else raises NotImplementedError (SMPLify's fused stage is the 
 The silhouette term of that loop (smplify.py:144,198) is here as well: `extract_countours` follows the masks' external borders on
 the GPU and keeps masks and contours there (a `native.Silhouette`, remembered per masks object and GPU), and `multview_mask_loss`
 evaluates the loss on the vertices the caller holds as ONE bf_silhouette_loss call - three launches - whose gradient goes to
-`smpl_verts`.  The chamfer loss (called nowhere in the reference) runs nowhere: its stand-alone version raises NotImplementedError.
+`smpl_verts`.  On the device route (float32 / uint8 / bool masks and float32 vertices on that GPU) nothing crosses to the host:
+the masks go in by address (bf_silhouette_create_dev), the contours come back as GPU tensors, the cameras are stacked on the GPU
+once per distinct set (four sets remembered) and the loss is bf_silhouette_loss_dev on torch's current stream.  The chamfer loss (called nowhere in the reference) runs nowhere: its stand-alone version raises NotImplementedError.
 """
 from __future__ import annotations
 
@@ -137,11 +139,11 @@ def _scalar_loss(who, x, call, plus_zero=False, device=None, device_call=None):
     return _autograd.apply(forward, vjp, (x,), device_route=route)[0].reshape(())
 
 
-def _takes_device_route(device, *tensors):
+def _takes_device_route(device, *tensors, dtypes=("torch.float32",)):
     """do these go the device route of a native object on GPU `device` (None: it offers none)?  _autograd.route_for's rule"""
     if device is None or not all(_is_tensor(t) and hasattr(t, "data_ptr") for t in tensors):
         return False
-    return _autograd.chosen_route(list(tensors), type("Offer", (), {"device": device})()) == "device"
+    return _autograd.chosen_route(list(tensors), type("Offer", (), {"device": device})(), dtypes) == "device"
 
 
 def _new(like, shape, dtype=None):
@@ -263,7 +265,7 @@ def normal_laplacian_smoothness(norms, faces):
 # the silhouette term (loss.py:73-130)
 # ----------------------------------------------------------------------------------------------------------------------------
 
-_SILHOUETTES = {}           # key -> dict(ref, version, sil, contours (host [C,2] arrays), given (what extract_countours returned))
+_SILHOUETTES = {}           # key -> dict(ref, version, sil, contours (host [C,2] arrays), given (extract_countours' last hand-outs))
 _SILHOUETTE_SLOTS = 4       # mask sets kept at a time; the oldest goes first
 MASK_STRIDE = 4             # loss.py:99: every 4th vertex
 
@@ -313,13 +315,43 @@ def _silhouette_hit(key, masks):
 
 
 def _silhouette_store(key, entry, sil, contours, given):
+    """contours None: an object made on the device route - its host copies are fetched when something asks (_hit_contours)"""
     old = _SILHOUETTES.pop(key, None)
     if old is not None:
         old["sil"].close()
     while len(_SILHOUETTES) >= _SILHOUETTE_SLOTS:
-        _SILHOUETTES.pop(next(iter(_SILHOUETTES)))["sil"].close()
+        _SILHOUETTES.pop(next(iter(_SILHOUETTES)))["sil"].close()          # (closes the object's workspace, then the object)
     _SILHOUETTES[key] = {"ref": entry[0], "version": entry[1], "sil": sil, "contours": contours, "given": given}
     return _SILHOUETTES[key]
+
+
+def _hit_contours(hit):
+    if hit["contours"] is None:
+        hit["contours"] = [np.asarray(c, np.float32).reshape(-1, 2) for c in hit["sil"].contours()]
+    return hit["contours"]
+
+
+_MASK_DTYPES = {"torch.float32": 1, "torch.uint8": 0, "torch.bool": 0}          # -> native.MASK_FLOAT32 / MASK_UINT8
+
+
+def _masks_route(masks, device):
+    """"device" when extract_countours hands `masks` to the GPU `device` by address: a float32 / uint8 / bool tensor on that GPU,
+    the switch on, one shared runtime and a library that has the entries (_autograd.route_for's rule); else "host" - never an error"""
+    from . import native
+    offers = getattr(native.Silhouette, "offers_dev", None)
+    if offers is None or not _takes_device_route(device, masks, dtypes=tuple(_MASK_DTYPES)):
+        return "host"
+    return "device" if offers() else "host"
+
+
+def _contours_on_device(sil, like):
+    """the object's contours as M GPU tensors [C,1,2]: views split from ONE tensor that bf_silhouette_contours_dev fills"""
+    import torch
+    counts = [int(c) for c in sil.counts()]
+    xy = torch.empty((max(sum(counts), 1), 2), dtype=torch.float32, device=like.device)
+    sil.contours_dev(xy.data_ptr(), torch.cuda.current_stream(like.device).cuda_stream)
+    ends = np.cumsum(counts)
+    return [xy[int(e) - c:int(e)].reshape(-1, 1, 2) for c, e in zip(counts, ends)]
 
 
 def extract_countours(masks, device=None):
@@ -335,6 +367,26 @@ def extract_countours(masks, device=None):
         device = _normals.device_index(masks)
     key, entry = _masks_key(masks, device, None)
     hit = _silhouette_hit(key, masks)
+    on_device = _masks_route(masks, device) == "device"
+    if hit is None and on_device:
+        # the masks go in by address, on torch's current stream: binarised and checked by a kernel, only M + 1 flags come back
+        import torch
+        shape = (1,) + tuple(masks.shape) if masks.ndim == 2 else tuple(masks.shape)
+        if len(shape) != 3 or 0 in shape:
+            raise ValueError(f"{who}: masks must be [M,H,W] (or [H,W]), not {tuple(masks.shape)}")
+        m = masks.detach().contiguous()
+        try:
+            sil = native.Silhouette.from_device(m.data_ptr(), shape, _MASK_DTYPES[str(m.dtype)],
+                                                torch.cuda.current_stream(m.device).cuda_stream, device=device)
+        except native.MasksRefused as e:
+            if e.view is None:
+                raise ValueError(f"{who}: masks must hold 0 / 1 only (the reference reads them as numbers: mask < 0.1, 1 - mask)") from None
+            raise ValueError(f"{who}: mask {e.view} has no foreground (the reference fails in np.argmax of an empty list)") from None
+        hit = _silhouette_store(key, entry, sil, None, None)
+    if on_device and getattr(hit["sil"], "dev_route_device", None) == device:
+        out = _contours_on_device(hit["sil"], masks)
+        _note_given(hit, out)
+        return out
     if hit is None:
         host = _masks_host(who, masks)
         empty = [i for i in range(len(host)) if not host[i].any()]
@@ -342,12 +394,17 @@ def extract_countours(masks, device=None):
             raise ValueError(f"{who}: mask {empty[0]} has no foreground (the reference fails in np.argmax of an empty list)")
         sil = native.Silhouette(host, None, device=device)           # (contour_select: OpenCV's first listed contour, the default)
         hit = _silhouette_store(key, entry, sil, [np.asarray(c, np.float32).reshape(-1, 2) for c in sil.contours()], None)
-    out = [c.reshape(-1, 1, 2).copy() for c in hit["contours"]]
+    out = [c.reshape(-1, 1, 2).copy() for c in _hit_contours(hit)]
     if _is_tensor(masks):
         import torch
         out = [torch.from_numpy(c).to(masks.device) for c in out]
-        hit["given"] = [(weakref.ref(c), c._version) for c in out]
+        _note_given(hit, out)
     return out
+
+
+def _note_given(hit, out):
+    """remember a hand-out of extract_countours beside the earlier ones (the last four): each is recognised by identity later"""
+    hit["given"] = ((hit["given"] or []) + [[(weakref.ref(c), c._version) for c in out]])[-4:]
 
 
 def _silhouette_for(who, masks, contours, device):
@@ -356,10 +413,13 @@ def _silhouette_for(who, masks, contours, device):
     from . import native
     key, entry = _masks_key(masks, device, None)
     hit = _silhouette_hit(key, masks)
-    if hit is not None and len(hit["contours"]) == len(contours):
-        given = hit["given"]
-        if given is not None and all(_is_tensor(c) and r() is c and ver == c._version for c, (r, ver) in zip(contours, given)):
-            return hit["sil"]
+    if hit is not None and hit["sil"].n_views == len(contours):
+        for given in hit["given"] or ():
+            if all(_is_tensor(c) and r() is c and ver == c._version for c, (r, ver) in zip(contours, given)):
+                return hit["sil"]
+    known = _known_contours(masks, contours, device)
+    if known is not None:
+        return known
     host = []
     for i, c in enumerate(contours):
         a = _host(c)
@@ -368,14 +428,80 @@ def _silhouette_for(who, masks, contours, device):
         if a.shape[0] == 0:
             raise ValueError(f"{who}: contour {i} has no points")
         host.append(np.ascontiguousarray(a.reshape(-1, 2)))
-    if hit is not None and len(hit["contours"]) == len(host) and all(np.array_equal(a, b) for a, b in zip(host, hit["contours"])):
-        return hit["sil"]
+    if hit is not None and hit["sil"].n_views == len(host) and all(np.array_equal(a, b) for a, b in zip(host, _hit_contours(hit))):
+        return _remember_contours(masks, contours, device, hit["sil"])
     digest = hashlib.sha1(b"".join(a.tobytes() for a in host) + repr([len(a) for a in host]).encode()).hexdigest()
     key, entry = _masks_key(masks, device, digest)
     hit = _silhouette_hit(key, masks)
     if hit is None:
         hit = _silhouette_store(key, entry, native.Silhouette(_masks_host(who, masks), host, device=device), host, None)
-    return hit["sil"]
+    return _remember_contours(masks, contours, device, hit["sil"])
+
+
+_KNOWN_CONTOURS = []        # dict(masks (weak reference, version), device, items [(tensor, version)], sil): contour tensors that are
+_KNOWN_CONTOUR_SLOTS = 4    # not extract_countours' own and have been read and matched to an object once; the oldest goes first
+
+
+def _known_contours(masks, contours, device):
+    """the object these contour TENSORS were matched to before - the same tensors at the same `_version` beside the same masks - or
+    None: a loop that passes its own contours reads them back once, not at every step.  (The tensors are held while remembered:
+    an identity cannot come back with other contents.)"""
+    if not (_is_tensor(masks) and all(_is_tensor(c) for c in contours)):
+        return None
+    for e in _KNOWN_CONTOURS:
+        if (e["device"] == device and e["masks"][0]() is masks and e["masks"][1] == masks._version and len(e["items"]) == len(contours)
+                and all(t is c and ver == c._version for c, (t, ver) in zip(contours, e["items"]))
+                and any(h["sil"] is e["sil"] for h in _SILHOUETTES.values())):          # (still cached: not closed by an eviction)
+            return e["sil"]
+    return None
+
+
+def _remember_contours(masks, contours, device, sil):
+    if _is_tensor(masks) and all(_is_tensor(c) for c in contours):
+        del _KNOWN_CONTOURS[:max(0, len(_KNOWN_CONTOURS) - _KNOWN_CONTOUR_SLOTS + 1)]
+        _KNOWN_CONTOURS.append({"masks": (weakref.ref(masks), masks._version), "device": device,
+                                "items": [(c, c._version) for c in contours], "sil": sil})
+    return sil
+
+
+def _mask_loss_route(smpl_verts, device):
+    """"device" when multview_mask_loss evaluates on GPU `device` where the vertices lie: _autograd.route_for's rule for `smpl_verts`
+    and a library that has the entries; else "host" - never an error"""
+    from . import native
+    offers = getattr(native.Silhouette, "offers_dev", None)
+    if offers is None or not offers():
+        return "host"
+    return "device" if _takes_device_route(device, smpl_verts) else "host"
+
+
+_CAMERAS = {}               # key -> dict(held (the camera objects: an id in the key cannot be recycled), w2c, K (stacked, on the GPU))
+_CAMERA_SLOTS = 4           # camera sets kept at a time; the oldest goes first
+CAMERA_STATS = {"stacks": 0}          # how often a camera set was stacked on a GPU (the tests read it)
+
+
+def _cameras_for(who, cameras, n_views, torch_device):
+    """w2cs, Ks (each one stacked tensor, or a list of tensors) as float32 [M,4,4] and [M,3,3] on `torch_device`: stacked there once
+    per distinct set - its items by identity and `_version`, like _views_for - and remembered.  GPU cameras are never read back;
+    CPU tensors are sent once per set."""
+    import torch
+    items = [x if _is_tensor(x) else list(x) for x in cameras]
+    flat = [it for x in items for it in ([x] if _is_tensor(x) else x)]
+    key = (str(torch_device), n_views, tuple(len(x) if isinstance(x, list) else -1 for x in items), tuple((id(t), t._version) for t in flat))
+    hit = _CAMERAS.get(key)
+    if hit is not None:
+        return hit["w2c"], hit["K"]
+    out = []
+    try:
+        for x, side in zip(items, (4, 3)):
+            x = x.detach() if _is_tensor(x) else torch.stack([t.detach().reshape(side, side) for t in x])
+            out.append(x.reshape(n_views, side, side).to(device=torch_device, dtype=torch.float32).contiguous())
+    except RuntimeError:
+        raise ValueError(f"{who}: w2cs must be [M,4,4] and Ks [M,3,3]") from None
+    CAMERA_STATS["stacks"] += 1
+    while len(_CAMERAS) >= _CAMERA_SLOTS:
+        _CAMERAS.pop(next(iter(_CAMERAS)))
+    _CAMERAS[key] = {"held": flat, "w2c": out[0], "K": out[1]}
+    return out[0], out[1]
 
 
 def multview_mask_loss(contours, masks, smpl_verts=None, smpl_faces=None, w2cs=None, Ks=None, mask_frames=None, epsilon=10, imsize=512,
@@ -405,6 +531,7 @@ def multview_mask_loss(contours, masks, smpl_verts=None, smpl_faces=None, w2cs=N
     if mask_frames is None:
         raise ValueError(f"{who}: mask_frames is missing (its length is the number of views)")
     n_masks = 1 if masks.ndim == 2 else len(masks)
+    cameras_given = (w2cs, Ks)
     contours, w2cs, Ks = list(contours), list(w2cs), list(Ks)
     if not (len(mask_frames) == n_masks == len(contours) == len(w2cs) == len(Ks)):
         raise ValueError(f"{who}: {len(mask_frames)} mask_frames, {n_masks} masks, {len(contours)} contours, {len(w2cs)} w2cs and {len(Ks)} Ks "
@@ -421,13 +548,28 @@ def multview_mask_loss(contours, masks, smpl_verts=None, smpl_faces=None, w2cs=N
                          "beyond the mask as soon as a chosen vertex lies there")
     if pairwise not in (None, "cdist", "exact"):
         raise ValueError(f"{who}: pairwise must be None, 'cdist' or 'exact'")
+    if device is None:
+        device = _normals.device_index(smpl_verts)
+    if _mask_loss_route(smpl_verts, device) == "device":
+        # float32 vertices on the GPU: everything stays there.  The cameras are stacked on that GPU once per distinct set, the
+        # contours are recognised by identity (else built through the host, once per set), the loss is a tensor that never leaves
+        w2c_t, K_t = _cameras_for(who, cameras_given, n_masks, smpl_verts.device)
+        sil = _silhouette_for(who, masks, contours, device)
+        if getattr(sil, "dev_route_device", None) == device:
+            def device_call(v, want_grad, stream):
+                terms = _new(v, 1 + 2 * n_masks)
+                grad = _new(v, v.shape) if want_grad else None
+                sil.loss_dev(stream, v.numel() // 3, v.data_ptr(), w2c_t.data_ptr(), K_t.data_ptr(), imsize=imsize, epsilon=epsilon,
+                             stride=MASK_STRIDE, cdist_form=pairwise != "exact", terms=terms.data_ptr(),
+                             dverts=0 if grad is None else grad.data_ptr())
+                return terms[:1], grad
+
+            return _scalar_loss(who, smpl_verts, None, plus_zero=True, device=device, device_call=device_call)
     try:
         w2c = np.stack([_host(a).reshape(4, 4) for a in w2cs])
         K = np.stack([_host(a).reshape(3, 3) for a in Ks])
     except ValueError:
         raise ValueError(f"{who}: w2cs must be [M,4,4] and Ks [M,3,3]") from None
-    if device is None:
-        device = _normals.device_index(smpl_verts)
     sil = _silhouette_for(who, masks, contours, device)
 
     def call(v, want_grad):
@@ -501,7 +643,9 @@ def _views_on(views, device):
     """the four packed arrays as tensors on that GPU, sent on first use"""
     import torch
     if device not in views["dev"]:
-        views["dev"][device] = tuple(torch.from_numpy(a).to(device) for a in views["host"])
+        # (contiguous first: cameras from torch.inverse arrive column-major, np.stack keeps that order, and a tensor made from such an
+        # array keeps its strides - the kernel reads by address and would see every w2c transposed)
+        views["dev"][device] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in views["host"])
         VIEW_STATS["uploads"] += 1
     return views["dev"][device]
 

@@ -623,10 +623,60 @@ def scale_gradient_dev(device, stream, n, grad, cotangent, out, plus_zero=False)
                                                  stream or None), "bf_scale_gradient_dev")
 
 
+# the device route of the silhouette term (bf_silhouette_*_dev of csrc/silhouette_api.hip)
+SILHOUETTE_DEV_SYMBOLS = ("bf_silhouette_create_dev", "bf_silhouette_contours_dev", "bf_silhouette_loss_dev", "bf_scale_gradient_dev")
+MASK_UINT8, MASK_FLOAT32 = 0, 1
+SIL_EMPTY_VIEW = 1
+
+
+def silhouette_rows_dev(device, stream, n_views, w2c, K, rows):
+    """bf_silhouette_rows_dev: device addresses of w2c[M,4,4], K[M,3,3] -> rows[M,3,4] = K [R|t], the first launch of
+    bf_silhouette_loss_dev by itself"""
+    _lib.check(_lib.load().bf_silhouette_rows_dev(int(device), int(n_views), w2c or None, K or None, rows or None, stream or None),
+               "bf_silhouette_rows_dev")
+
+
+class MasksRefused(ValueError):
+    """bf_silhouette_create_dev found, on the device, masks it does not take: `view` None = a value other than 0 / 1, else the
+    first view with no foreground"""
+
+    def __init__(self, view):
+        super().__init__("masks hold a value other than 0 / 1" if view is None else f"mask {view} has no foreground")
+        self.view = view
+
+
 class Silhouette:
     """The masks[M,H,W] (truthy = foreground) of M views and one contour per view, kept on one GPU (bf_silhouette): what
     multview_mask_loss (loss.py:85-130) compares a caller's vertices with.  contours: None = the external borders are followed on
-    the device and the one `contour_select` names is kept, else M arrays [C,2] (or [C,1,2]) of (x, y) points."""
+    the device and the one `contour_select` names is kept, else M arrays [C,2] (or [C,1,2]) of (x, y) points.
+    `from_device` builds one from masks that are on the GPU already; `contours_dev` / `loss_dev` are the device route of `contours`
+    / `loss` on any Silhouette (device addresses in, nothing read back), on the object's own `Workspace`."""
+
+    @classmethod
+    def offers_dev(cls, lib=None):
+        """does the library export the silhouette's device route?"""
+        lib = lib or _lib.load()
+        return all(hasattr(lib, name) for name in SILHOUETTE_DEV_SYMBOLS)
+
+    @classmethod
+    def from_device(cls, masks, shape, mask_dtype, stream, device=0, contour_select=_lib.CONTOUR_OPENCV_FIRST):
+        """bf_silhouette_create_dev: masks = the device address of shape = (M, H, W) contiguous elements of MASK_UINT8 (uint8, bool)
+        or MASK_FLOAT32 on GPU `device`, possibly still in flight on `stream`.  Raises MasksRefused for a value other than 0 / 1 or
+        a view without foreground; the pixels never reach the host"""
+        self = cls.__new__(cls)
+        self._lib = lib = _lib.load()
+        self.n_views, self.H, self.W = (int(x) for x in shape)
+        self.device = int(device)
+        self._h = C.c_void_p()
+        rc = lib.bf_silhouette_create_dev(self.device, self.n_views, self.H, self.W, masks or None, int(mask_dtype), int(contour_select),
+                                          stream or None, C.byref(self._h))
+        if rc >= SIL_EMPTY_VIEW:
+            raise MasksRefused(rc - SIL_EMPTY_VIEW)
+        if rc == -1 and b"0 / 1 only" in lib.bf_last_error():
+            raise MasksRefused(None)
+        _lib.check(rc, "bf_silhouette_create_dev")
+        self.dev_route_device = self.device
+        return self
 
     def __init__(self, masks, contours=None, device=0, contour_select=_lib.CONTOUR_OPENCV_FIRST):
         lib = _lib.load()
@@ -646,6 +696,30 @@ class Silhouette:
         self._h = C.c_void_p()
         _lib.check(lib.bf_silhouette_create(self.device, self.n_views, self.H, self.W, m.ctypes.data_as(C.POINTER(C.c_uint8)),
                                             _lib.iptr(counts), _lib.fptr(xy), int(contour_select), C.byref(self._h)), "bf_silhouette_create")
+        self.dev_route_device = self.device if self.offers_dev(lib) else None       # the GPU a device route is offered on
+
+    def workspace(self):
+        """the object's own `Workspace` for the device route, made on first use and closed before the object"""
+        return _own_workspace(self)
+
+    def counts(self):
+        """-> int32[M]: the contours' lengths (host values the object holds: no device work)"""
+        counts = np.zeros(self.n_views, np.int32)
+        _lib.check(self._lib.bf_silhouette_contours(self._h, _lib.iptr(counts), None), "bf_silhouette_contours")
+        return counts
+
+    def contours_dev(self, xy, stream):
+        """bf_silhouette_contours_dev: the sum(counts()) (x, y) pairs copied device to device to the address `xy`, on `stream`"""
+        _lib.check(self._lib.bf_silhouette_contours_dev(self._h, xy or None, stream or None), "bf_silhouette_contours_dev")
+
+    def loss_dev(self, stream, n_verts, verts, w2c, K, imsize=512, epsilon=10, stride=4, cdist_form=True, terms=0, dverts=0, ws=None):
+        """bf_silhouette_loss_dev: device addresses of verts[n_verts,3], w2c[M,4,4], K[M,3,3] -> terms[1 + 2M] (the loss, then per view
+        (contour term, binary term)) and dverts[n_verts,3] (0 = not wanted), queued on `stream`; nothing is read back"""
+        ws = ws or self.workspace()
+        with ws.lock:
+            _lib.check(self._lib.bf_silhouette_loss_dev(self._h, int(n_verts), int(stride), verts or None, w2c or None, K or None, float(imsize),
+                                                        float(epsilon), int(bool(cdist_form)), terms or None, dverts or None, ws._h,
+                                                        stream or None), "bf_silhouette_loss_dev")
 
     def contours(self):
         """-> list of M float32[C,2] arrays of (x, y) points in border order (bf_silhouette_contours)"""
@@ -672,6 +746,7 @@ class Silhouette:
         return loss[0], terms, dv
 
     def close(self):
+        _close_workspace(self)
         if getattr(self, "_h", None):
             self._lib.bf_silhouette_destroy(self._h)
             self._h = None

@@ -301,7 +301,7 @@ int bf_keypoint_loss_dev(bf_workspace *ws, void *stream, const bf_gmm *gmm, cons
  * of another runtime or device).  Never sets bf_last_error and leaves no HIP error behind. */
 int bf_device_pointer_check(int device, const void *p);
 /* test hook, process-wide counts: out[0] calls of the five host entry points named above, of the SMPL+D stage's losses below
- * (bf_vertex_normals, bf_vertex_normals_vjp, bf_normal_laplacian, bf_scan_point_loss, bf_normal_loss) and of bf_scan_nearest,
+ * (bf_vertex_normals, bf_vertex_normals_vjp, bf_normal_laplacian, bf_scan_point_loss, bf_normal_loss), of bf_scan_nearest and of bf_silhouette_loss,
  * out[1] calls of the *_dev entry points (both counted once the arguments have passed), out[2] device (re)allocations of workspaces, out[3] calls that had to wait
  * for their workspace's previous call on another stream. */
 int bf_dev_route_stats(int64_t out[4]);
@@ -599,6 +599,39 @@ int bf_silhouette_contours(const bf_silhouette *s, int32_t *counts, float *xy);
 #define BF_SIL_MAX_SUM (1 << 20)
 int bf_silhouette_loss(bf_silhouette *s, int n_verts, int stride, const float *verts, const float *w2c, const float *K,
                        float imsize, float epsilon, int cdist_form, float *loss, float *view_terms, float *dverts);
+
+/* The device route of the silhouette term (see bf_workspace): extract_countours and multview_mask_loss (smplify/loss.py:73-130)
+ * for a caller whose masks, vertices and cameras are DEVICE arrays of this library's HIP runtime, ordered on `stream` (a
+ * hipStream_t; NULL = the null stream).  Each call counts as a *_dev call in bf_dev_route_stats, bf_silhouette_loss as a host call.
+ *
+ * bf_silhouette_create_dev: masks[M,H,W] contiguous on `device`, one byte per pixel (BF_MASK_UINT8: uint8 or bool) or float32
+ * (BF_MASK_FLOAT32), aligned to its element and no further; it may still be in flight on `stream`.  One launch there reads the
+ * masks in their type, writes the object's 0 / 1 bytes and raises M + 1 flags; the call waits for `stream` and reads the flags -
+ * the pixels never cross to the host.  A value other than 0 / 1 (a NaN is one): BF_ERR_INVALID.  A view with no foreground: the
+ * POSITIVE return value BF_SIL_EMPTY_VIEW + the first such view's index, and no object.  Otherwise the contours are followed as
+ * by bf_silhouette_create(contour_count = NULL): the same storage, contours and limits.  Creation synchronises; it happens once
+ * per masks object.  The thread's current device is left as it was. */
+#define BF_MASK_UINT8      0
+#define BF_MASK_FLOAT32    1
+#define BF_SIL_EMPTY_VIEW  1
+int bf_silhouette_create_dev(int device, int n_views, int H, int W, const void *masks, int mask_dtype, int contour_select,
+                             void *stream, bf_silhouette **out);
+/* The contours' (x, y) points, sum(counts) pairs (counts: bf_silhouette_contours(s, counts, NULL)), copied device to device
+ * into xy on `stream`. */
+int bf_silhouette_contours_dev(const bf_silhouette *s, float *xy, void *stream);
+/* bf_silhouette_loss on device arrays: verts[n_verts,3], w2c[M,4,4], K[M,3,3] float32 on the object's device.  terms[1 + 2M] =
+ * the loss, then view_terms[M,2]; dverts[n_verts,3]; either may be NULL = not wanted, with both NULL nothing is launched.  The
+ * rows K [R|t] are formed by a launch of their own, in double, with the host call's bits; then the host call's three launches
+ * with its grids and arguments - equal inputs give its bits.  Scratch comes from the workspace, which must live on the object's
+ * device (BF_ERR_INVALID otherwise, as for a NULL one); no memset, no copy to the host, no drain.  The host call's refusals,
+ * before anything is queued; the thread's current device is left as it was. */
+int bf_silhouette_loss_dev(bf_silhouette *s, int n_verts, int stride, const float *verts, const float *w2c, const float *K,
+                           float imsize, float epsilon, int cdist_form, float *terms, float *dverts, bf_workspace *ws, void *stream);
+/* TEST HOOK, not part of the feature: that first launch by itself, so that bf_sil_rows_kernel can be held to the float64 expression
+ * on its own (the loss's outputs do not allow it).  rows[M,3,4] = K [R|t] from w2c[M,4,4] and K[M,3,3], device pointers of `device`; each element is
+ * (float)((double)k0 * w0 + (double)k1 * w1 + (double)k2 * w2) summed left to right - a product of two float32 values is exact in
+ * double, so the bits do not depend on whether a multiply-add is fused.  One launch on `stream`, no workspace. */
+int bf_silhouette_rows_dev(int device, int n_views, const float *w2c, const float *K, float *rows, void *stream);
 
 /* SMPL+D stage (displacement=True, smplify.py:228-247): n_iters Adam steps (lr 5e-2) on a per-vertex
  * displacement of the vertices returned by the last bf_fit, against each frame's scan:

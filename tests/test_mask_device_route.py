@@ -1,0 +1,308 @@
+"""The device route of extract_countours / multview_mask_loss without a GPU: when it is taken (_autograd.route_for's rule, never an
+error when it is unavailable), the camera cache, how the contours extract_countours handed out are recognised, the new names of the
+C ABI, and the exactness argument behind bf_sil_rows_kernel.  The route itself runs in tests/test_gpu_mask_device_route.py."""
+import ctypes
+import itertools
+import os
+from fractions import Fraction
+
+import numpy as np
+import pytest
+import torch
+
+import mask_loss_cases as MC
+from bodyfitting_amd import _autograd, _lib
+from bodyfitting_amd import loss as L
+from bodyfitting_amd import native
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_NAMES = ("bf_silhouette_create_dev", "bf_silhouette_contours_dev", "bf_silhouette_rows_dev", "bf_silhouette_loss_dev")
+
+
+class _Device:
+    def __init__(self, kind, index):
+        self.type, self.index = kind, index
+
+
+class _Like:
+    """what the routing rule reads of a tensor"""
+    requires_grad = False
+    _version = 0
+
+    def __init__(self, kind="cuda", index=0, dtype="torch.float32"):
+        self.device, self.dtype = _Device(kind, index), dtype
+
+    def detach(self):
+        return self
+
+    def data_ptr(self):
+        return 4096
+
+
+class OfferingSilhouette(MC.StandInSilhouette):
+    """a stand-in whose library has the device entries; none of them may be reached without a GPU tensor"""
+    contour_reads = 0
+
+    @classmethod
+    def offers_dev(cls, lib=None):
+        return True
+
+    @classmethod
+    def from_device(cls, *args, **kwargs):
+        raise AssertionError("the device route was taken")
+
+    def loss_dev(self, *args, **kwargs):
+        raise AssertionError("the device route was taken")
+
+    def contours(self):
+        type(self).contour_reads += 1
+        return super().contours()
+
+
+@pytest.fixture
+def stand_ins(monkeypatch):
+    MC.install_stand_ins(monkeypatch)
+    monkeypatch.setattr(native, "Silhouette", OfferingSilhouette)
+    monkeypatch.setattr(L, "_CAMERAS", {})
+    monkeypatch.setattr(L, "CAMERA_STATS", {"stacks": 0})
+    monkeypatch.setattr(L, "_KNOWN_CONTOURS", [])
+    OfferingSilhouette.contour_reads = OfferingSilhouette.created = OfferingSilhouette.followed = 0
+    return OfferingSilhouette
+
+
+def test_the_route_is_taken_exactly_under_route_fors_rule(stand_ins, monkeypatch):
+    """masks: a float32 / uint8 / bool tensor on the GPU asked for; vertices: a float32 tensor there; the switch on; one shared
+    runtime; a library with the entries - every other combination is the host route"""
+    kinds = (("cuda", 0), ("cuda", 1), ("cpu", None))
+    mask_dtypes = ("torch.float32", "torch.uint8", "torch.bool", "torch.float64", "torch.int32", "torch.float16")
+    for (kind, index), dtype, enabled, shared, offered in itertools.product(kinds, mask_dtypes, (True, False), (True, False), (True, False)):
+        monkeypatch.setattr(_autograd, "_ENABLED", [enabled])
+        monkeypatch.setattr(_autograd, "_SHARED", {0: shared, 1: shared})
+        monkeypatch.setattr(native, "Silhouette", OfferingSilhouette if offered else MC.StandInSilhouette)
+        t = _Like(kind, index, dtype)
+        want_masks = kind == "cuda" and index == 0 and dtype in ("torch.float32", "torch.uint8", "torch.bool") and enabled and shared and offered
+        assert L._masks_route(t, 0) == ("device" if want_masks else "host"), (kind, index, dtype, enabled, shared, offered)
+        want_verts = kind == "cuda" and index == 0 and dtype == "torch.float32" and enabled and shared and offered
+        assert L._mask_loss_route(t, 0) == ("device" if want_verts else "host"), (kind, index, dtype, enabled, shared, offered)
+        # the rule itself, stated by _autograd
+        assert (_autograd.route_for([t], 0 if offered else None, enabled, shared) == "device") == want_verts
+    # no GPU asked for, numpy, None
+    monkeypatch.setattr(_autograd, "_ENABLED", [True])
+    monkeypatch.setattr(native, "Silhouette", OfferingSilhouette)
+    assert L._masks_route(_Like(), None) == "host" and L._mask_loss_route(_Like(), None) == "host"
+    assert L._masks_route(np.zeros((1, 4, 4), np.float32), 0) == "host" and L._mask_loss_route(np.zeros((4, 3), np.float32), 0) == "host"
+
+
+@pytest.mark.parametrize("switch", ["1", "0"])
+def test_nothing_raises_where_the_route_is_unavailable(stand_ins, monkeypatch, switch):
+    """CPU tensors, numpy and float64 vertices run the host code whatever the switch says, with a library that offers the entries"""
+    monkeypatch.setattr(_autograd, "_ENABLED", [switch != "0"])
+    b = MC.build("views3")
+    c = b["case"]
+    want = MC.references("views3")["f64"]
+    frames = list(range(c.M))
+    # numpy
+    contours = L.extract_countours(b["masks"])
+    value = L.multview_mask_loss(contours, b["masks"], b["verts"], None, b["w2c"], b["K"], frames, epsilon=c.eps, imsize=c.imsize)
+    assert isinstance(value, float) and value == pytest.approx(want[0], rel=1e-5)
+    # CPU tensors, float32 and float64
+    for dtype in (torch.float32, torch.float64):
+        masks = torch.tensor(b["masks"].astype(np.float32))
+        contours = L.extract_countours(masks)
+        assert all(k.device.type == "cpu" for k in contours)
+        v = torch.tensor(b["verts"], dtype=dtype, requires_grad=True)
+        out = L.multview_mask_loss(contours, masks, v, None, torch.tensor(b["w2c"]), torch.tensor(b["K"]), frames, epsilon=c.eps, imsize=c.imsize)
+        out.backward()
+        assert out.device.type == "cpu" and float(out) == pytest.approx(want[0], rel=1e-5)
+        np.testing.assert_allclose(v.grad.numpy(), want[1], rtol=1e-4, atol=1e-5 * np.abs(want[1]).max())
+    assert L.CAMERA_STATS["stacks"] == 0
+
+
+def _camera_set(seed, M=3):
+    rng = np.random.default_rng(seed)
+    return [torch.tensor(rng.normal(size=(4, 4)).astype(np.float32)) for _ in range(M)], [torch.tensor(rng.normal(size=(3, 3)).astype(np.float32)) for _ in range(M)]
+
+
+def test_the_camera_cache(stand_ins):
+    cpu = torch.device("cpu")
+    w2cs, Ks = _camera_set(0)
+    w, k = L._cameras_for("t", (w2cs, Ks), 3, cpu)
+    assert L.CAMERA_STATS["stacks"] == 1 and w.shape == (3, 4, 4) and k.shape == (3, 3, 3) and w.dtype == k.dtype == torch.float32
+    assert w.is_contiguous() and k.is_contiguous()
+    np.testing.assert_array_equal(w.numpy(), np.stack([a.numpy() for a in w2cs]))
+    np.testing.assert_array_equal(k.numpy(), np.stack([a.numpy() for a in Ks]))
+    # the same list objects again: no new stack, the same tensors
+    w2, k2 = L._cameras_for("t", (w2cs, Ks), 3, cpu)
+    assert L.CAMERA_STATS["stacks"] == 1 and w2 is w and k2 is k
+    # new lists of the same items: the items are what is remembered
+    w2, _ = L._cameras_for("t", (list(w2cs), tuple(Ks)), 3, cpu)
+    assert L.CAMERA_STATS["stacks"] == 1 and w2 is w
+    # an in-place edit bumps the item's version: a new stack with the new contents
+    Ks[1].mul_(2.0)
+    _, k3 = L._cameras_for("t", (w2cs, Ks), 3, cpu)
+    assert L.CAMERA_STATS["stacks"] == 2 and k3 is not k
+    np.testing.assert_array_equal(k3.numpy()[1], Ks[1].numpy())
+    # a stacked tensor is one object; float64 and a flat layout are converted
+    stacked = torch.stack(w2cs).double().reshape(3, 16)
+    w4, _ = L._cameras_for("t", (stacked, Ks), 3, cpu)
+    assert L.CAMERA_STATS["stacks"] == 3 and w4.dtype == torch.float32 and w4.shape == (3, 4, 4)
+    assert L._cameras_for("t", (stacked, Ks), 3, cpu)[0] is w4 and L.CAMERA_STATS["stacks"] == 3
+    # four sets are kept and the oldest goes first
+    L._CAMERAS.clear()
+    L.CAMERA_STATS["stacks"] = 0
+    sets = [_camera_set(10 + i) for i in range(5)]
+    for s in sets[:4]:
+        L._cameras_for("t", s, 3, cpu)
+    for s in sets[:4]:
+        L._cameras_for("t", s, 3, cpu)
+    assert L.CAMERA_STATS["stacks"] == 4 and len(L._CAMERAS) == 4
+    L._cameras_for("t", sets[4], 3, cpu)                       # the fifth evicts the first
+    assert L.CAMERA_STATS["stacks"] == 5 and len(L._CAMERAS) == 4
+    for s in sets[1:]:
+        L._cameras_for("t", s, 3, cpu)
+    assert L.CAMERA_STATS["stacks"] == 5
+    L._cameras_for("t", sets[0], 3, cpu)
+    assert L.CAMERA_STATS["stacks"] == 6
+    # the entries hold their items: an id in a key cannot come back with another tensor
+    held = [t for e in L._CAMERAS.values() for t in e["held"]]
+    assert all(any(t is x for x in held) for t in sets[0][0] + sets[0][1])
+    # shapes that are not cameras: the existing text
+    with pytest.raises(ValueError, match=r"w2cs must be \[M,4,4\] and Ks \[M,3,3\]"):
+        L._cameras_for("t", ([torch.zeros(3, 4)] * 3, Ks), 3, cpu)
+    with pytest.raises(ValueError, match=r"w2cs must be \[M,4,4\] and Ks \[M,3,3\]"):
+        L._cameras_for("t", (w2cs, torch.zeros(3, 2, 3)), 3, cpu)
+
+
+def _row_major_on_the_route(host):
+    """the tensors _views_on makes of packed arrays `host`: contiguous, and their memory - what a kernel reads from the address it is
+    handed - holds the arrays' elements in row-major order"""
+    on = L._views_on({"host": host, "dev": {}}, torch.device("cpu"))
+    for t, a in zip(on, host):
+        assert t.is_contiguous() and tuple(t.shape) == a.shape
+        assert t.numpy().flags["C_CONTIGUOUS"]
+        np.testing.assert_array_equal(t.numpy(), a)
+        np.testing.assert_array_equal(np.frombuffer(t.numpy().tobytes(), a.dtype), np.array(a, order="C").reshape(-1))
+    return on
+
+
+def test_packed_views_reach_the_device_route_in_row_major_order():
+    """cameras from torch.inverse (smplify.py:131-135) are column-major tensors, and the packed w2c array keeps that order; the
+    tensors the keypoint loss's device route hands over by address must not: before _views_on made them contiguous the kernel read
+    every w2c transposed, and step one of the loop of tests/test_gpu_mask_device_route.py had a reprojection term of 275837.8
+    instead of 118427.5"""
+    _, prob, _ = MC.loop_problem()
+    w2cs = torch.inverse(torch.tensor(np.asarray(prob["c2ws"], np.float32)))
+    Ks = torch.tensor(np.asarray(prob["Ks"], np.float32))
+    host = L._pack_views(w2cs, Ks, prob["keypoints"], len(prob["use_frames"]), False, L.SKELETON_LENGTH)
+    on = _row_major_on_the_route(host)
+    np.testing.assert_array_equal(on[0].numpy()[0], w2cs.numpy())
+    # whatever order _pack_views returns today: arrays that are certainly not row-major, every matrix stored transposed
+    w2c, K, kp, present = (np.array(a, order="C") for a in host)
+    turned = (np.ascontiguousarray(w2c.transpose(0, 1, 3, 2)).transpose(0, 1, 3, 2), np.ascontiguousarray(K.transpose(0, 1, 3, 2)).transpose(0, 1, 3, 2),
+              kp, present)
+    assert not turned[0].flags["C_CONTIGUOUS"] and not turned[1].flags["C_CONTIGUOUS"]
+    np.testing.assert_array_equal(turned[0], w2c)
+    _row_major_on_the_route(turned)
+
+
+def test_contours_are_recognised_by_identity_and_version(stand_ins):
+    """the tensors extract_countours handed out are the object's own contours without a look at their contents - also for an
+    object made on the device route, whose host copies do not exist yet; a contour edited in place is not recognised: its
+    contents decide, and new contents make a new object"""
+    b = MC.build("views3")
+    masks = torch.tensor(b["masks"].astype(np.float32))
+    contours = L.extract_countours(masks)
+    assert stand_ins.created == 1
+    sil = L._silhouette_for("t", masks, contours, 0)
+    assert stand_ins.created == 1 and sil is next(iter(L._SILHOUETTES.values()))["sil"]
+    # as the device route stores it: no host contours, `given` = what it handed out
+    hit = next(iter(L._SILHOUETTES.values()))
+    hit["contours"] = None
+    reads = stand_ins.contour_reads
+    assert L._silhouette_for("t", masks, contours, 0) is sil and stand_ins.contour_reads == reads and hit["contours"] is None
+    # equal contents under another identity: fetched once, compared, the same object
+    clones = [k.clone() for k in contours]
+    assert L._silhouette_for("t", masks, clones, 0) is sil and stand_ins.contour_reads == reads + 1 and stand_ins.created == 1
+    # ... and from then on these tensors are known by identity and version too: they are not read again
+    read = []
+    real = L._host
+    L._host = lambda a, *args: (read.append(a), real(a, *args))[1]
+    try:
+        assert L._silhouette_for("t", masks, clones, 0) is sil and stand_ins.contour_reads == reads + 1 and not read
+        clones[1].add_(0.0)                                     # (a new version: looked at again, found equal, remembered again)
+        assert L._silhouette_for("t", masks, clones, 0) is sil and len(read) == len(clones)
+        assert L._silhouette_for("t", masks, clones, 0) is sil and len(read) == len(clones)
+    finally:
+        L._host = real
+    # edited in place: the version differs, so the contents are looked at - they differ, and another object is made
+    contours[0][0, 0, 0] += 1.0
+    other = L._silhouette_for("t", masks, contours, 0)
+    assert other is not sil and stand_ins.created == 2
+    np.testing.assert_array_equal(other.contours()[0], contours[0].numpy()[:, 0])
+    # a second extract_countours on the same masks hands out fresh tensors, which are then the recognised ones
+    again = L.extract_countours(masks)
+    assert stand_ins.created == 2 and L._silhouette_for("t", masks, again, 0) is sil
+    # ... beside the earlier hand-out, which stays recognised without a look at its contents (contours[0] was edited: the rest)
+    third = L.extract_countours(masks)
+    read = []
+    real = L._host
+    L._host = lambda a, *args: (read.append(a), real(a, *args))[1]
+    try:
+        assert L._silhouette_for("t", masks, again, 0) is sil and L._silhouette_for("t", masks, third, 0) is sil and not read
+    finally:
+        L._host = real
+
+
+def test_the_new_names_are_in_header_signatures_and_exports():
+    text = open(os.path.join(REPO, "include", "bodyfit.h")).read()
+    for name in NEW_NAMES:
+        assert f"int {name}(" in text, name
+        assert name in _lib.SIGNATURES, name
+    assert "loss.py:73-130" in text
+    for macro in ("BF_MASK_UINT8", "BF_MASK_FLOAT32", "BF_SIL_EMPTY_VIEW"):
+        assert f"#define {macro}" in text
+    assert (native.MASK_UINT8, native.MASK_FLOAT32, native.SIL_EMPTY_VIEW) == (0, 1, 1)
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.fail(f"{_lib.LIB_PATH} not built - run __graft_entry__.build()")
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in NEW_NAMES:
+        assert hasattr(lib, name), name
+    assert set(NEW_NAMES) - {"bf_silhouette_rows_dev"} <= set(native.SILHOUETTE_DEV_SYMBOLS)
+    assert native.Silhouette.offers_dev(lib)
+
+
+def _rounded(x):
+    """a Fraction rounded to the nearest float64, ties to even: what one floating-point operation on exact operands returns"""
+    return float(x)
+
+
+def test_the_rows_expression_rounds_the_same_fused_or_not():
+    """rows = (float)((double)k0 * w0 + (double)k1 * w1 + (double)k2 * w2), left to right.  A product of two float32 values has at
+    most 48 significant bits: exact in float64.  So the unfused evaluation rounds twice, at the two additions, and so does an
+    evaluation that fuses each multiply into the addition behind it - fma(k2, w2, fma(k1, w1, k0 * w0)) - which is what a compiler
+    contracting the expression emits.  Checked on 10,000 random cameras with entries from 1e-3 to 1e4: numpy's float64 statement
+    against the FMA-ordered evaluation in exact rational arithmetic, rounded once per operation; bit for bit, also as float32"""
+    rng = np.random.default_rng(2024)
+    n = 10000
+    mag = lambda shape: (10.0 ** rng.uniform(-3, 4, shape) * rng.choice([-1.0, 1.0], shape)).astype(np.float32)          # noqa: E731
+    K, w2c = mag((n, 3, 3)), mag((n, 4, 4))
+    k, w = K.astype(np.float64), w2c.astype(np.float64)
+    plain = np.empty((n, 3, 4))
+    for r in range(3):
+        for c in range(4):
+            plain[:, r, c] = (k[:, r, 0] * w[:, 0, c] + k[:, r, 1] * w[:, 1, c]) + k[:, r, 2] * w[:, 2, c]
+    fused = np.empty((n, 3, 4))
+    inexact = 0
+    for i in range(n):
+        for r in range(3):
+            k0, k1, k2 = (Fraction(float(K[i, r, j])) for j in range(3))
+            for c in range(4):
+                w0, w1, w2 = (Fraction(float(w2c[i, j, c])) for j in range(3))
+                p0 = _rounded(k0 * w0)                                        # the first product alone: one rounding (none: it is exact)
+                assert Fraction(p0) == k0 * w0
+                a = _rounded(k1 * w1 + Fraction(p0))                          # fma: the exact product added, one rounding
+                inexact += Fraction(a) != k1 * w1 + Fraction(p0)
+                fused[i, r, c] = _rounded(k2 * w2 + Fraction(a))
+    assert inexact > n                                                        # (the additions do round: the test is not vacuous)
+    assert np.array_equal(plain.view(np.uint64), fused.view(np.uint64))
+    assert np.array_equal(plain.astype(np.float32).view(np.uint32), fused.astype(np.float32).view(np.uint32))

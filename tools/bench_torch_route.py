@@ -16,7 +16,15 @@ and written as JSON.  The yardstick is the host route of the same build.
 The SMPL+D stage instead (smplify.py:229-245 as written): compute_normal_torch, point_cloud_loss_mesh_grid, normal_loss_mesh_grid,
 normal_laplacian_smoothness, backward, Adam on the displacement - the full SMPL-X topology (10,475 vertices, 20,908 faces) against
 config 5's synthetic scan (83,784 triangles), all tensors on cuda:0, 100 iterations behind one warm-up step per process.
-`--child ROUTE --stage smpld --iters K` is one such process: what a profiler is pointed at."""
+`--child ROUTE --stage smpld --iters K` is one such process: what a profiler is pointed at.
+
+    python tools/bench_torch_route.py --stage mask --parent-root DIR [--reps 5] [--iters 100] [--out profiles/torch_device_route_mask.json]
+
+The keypoint stage with the silhouette term (smplify.py:177-213 with use_mask=True): the 6,890-vertex SMPL, 8 views with their
+keypoints, 8 masks of 512 x 512 and their contours (extract_countours, once), parameters, cameras and masks on cuda:0; a step is
+[SMPL.forward, the similarity, multiview_keypoint_loss, multview_mask_loss, loss = body + 5 * mask, backward, Adam].  The yardstick
+is the PARENT commit, never this tree's own host route: DIR is a checkout of it with its library built, and the children alternate
+this tree, the parent, this tree, ... (`--child device` / `--child parent`)."""
 from __future__ import annotations
 
 import argparse
@@ -138,9 +146,72 @@ def child_smpld(route, iters, loops):
     pointsearcher.close()
 
 
+def child_mask(side, root, iters, loops):
+    """one process of --stage mask: `side` "device" = this tree on the device route, "parent" = the tree at `root` as it routes"""
+    if side == "device":
+        os.environ["BF_TORCH_DEVICE_ROUTE"] = "1"
+    import numpy as np
+    import torch                                    # (before the library: the device route needs the shared runtime)
+    sys.path.insert(0, root)
+    import bodyfitting_amd
+    assert os.path.realpath(os.path.dirname(os.path.dirname(bodyfitting_amd.__file__))) == os.path.realpath(root), bodyfitting_amd.__file__
+    from bodyfitting_amd import assets, native as N, synthetic as S
+    from bodyfitting_amd.loss import extract_countours, multiview_keypoint_loss, multview_mask_loss
+    from bodyfitting_amd.prior import MaxMixturePrior
+    from bodyfitting_amd.smpl import SMPL
+
+    device = torch.device("cuda:0")
+    views = 8
+    model, gmm = S.make_model("smpl", seed=0), S.make_gmm(seed=0)
+    assets.register_gmm(gmm)
+    assets.register_model(model, "smpl", "neutral")
+    body, prior = SMPL(gender="neutral"), MaxMixturePrior()
+    prob = S.make_problem(model, frame=0, n_views=views, mask_frames=list(range(views)))
+    w2cs = torch.inverse(torch.tensor(np.asarray(prob["c2ws"], np.float32))).to(device)           # smplify.py:131-135
+    Ks = torch.tensor(np.asarray(prob["Ks"], np.float32)).to(device)
+    masks = torch.tensor((np.array(prob["masks"]) > 128).astype(np.float32)).to(device)            # smplify.py:139
+    assert tuple(masks.shape) == (views, 512, 512) and int(np.asarray(model["v_template"]).shape[0]) == 6890
+    mask_ids = [prob["use_frames"].index(f) for f in prob["mask_frames"]]
+    mask_w2cs, mask_Ks = w2cs[mask_ids], Ks[mask_ids]
+    contours = extract_countours(masks)                                                            # smplify.py:144
+    constant_scale = prob.get("constant_scale", 0.3)
+    faces = np.asarray(model["faces"], np.int64)[None]
+    pose0 = np.asarray(prob["init_pose"], np.float32).reshape(1, 72)
+    init = (np.zeros((1, 3), np.float32), np.ones((1, 1), np.float32), pose0[:, 3:], np.asarray(prob["init_betas"], np.float32).reshape(1, -1),
+            pose0[:, :3])
+
+    def loop(n):
+        x = [torch.tensor(a, device=device, requires_grad=True) for a in init]
+        global_transl, body_scale, body_pose, betas, global_orient = x
+        optimizer = torch.optim.Adam(x, lr=1e-2, betas=(0.9, 0.999))
+        for _ in range(n):
+            smpl_output = body(betas=betas, global_orient=global_orient, body_pose=body_pose)
+            model_joints = (smpl_output.joints + global_transl) * body_scale * constant_scale
+            body_vertices = (smpl_output.vertices + global_transl) * body_scale * constant_scale
+            body_loss, _ = multiview_keypoint_loss(w2cs, Ks, prob["keypoints"], model_joints, body_pose, betas, prob["use_frames"], prior,
+                                                   imsize=prob["imsize"])
+            mask_loss = multview_mask_loss(contours, masks, body_vertices, faces, mask_w2cs, mask_Ks, prob["mask_frames"], imsize=prob["imsize"])
+            loss = body_loss + 5 * mask_loss
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+        torch.cuda.synchronize()
+        return float(loss.detach())
+
+    first = loop(1)                                 # warm-up: one step of the same shapes
+    times, stats0 = [], N.dev_route_stats()
+    for _ in range(loops):
+        t0 = time.perf_counter()
+        last = loop(iters)
+        times.append(time.perf_counter() - t0)
+    stats1 = N.dev_route_stats()
+    print(json.dumps({"route": side, "batch": 1, "stage": "mask", "iters": iters, "seconds": times, "first_loss": first, "final_loss": last,
+                      "contour_points": [int(len(c)) for c in contours], "calls": {k: stats1[k] - stats0[k] for k in stats1}}))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--child", choices=("device", "host"))
+    ap.add_argument("--child", choices=("device", "host", "parent"))
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 64])
     ap.add_argument("--iters", type=int, default=100)
@@ -149,8 +220,17 @@ def main():
     ap.add_argument("--loops", type=int, default=1, help="timed loops per process, behind its warm-up loop")
     ap.add_argument("--timeout", type=int, default=300, help="seconds a child may take")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--stage", choices=("keypoint", "smpld"), default="keypoint", help="smpld: the SMPL+D loop (one evaluation per step)")
+    ap.add_argument("--stage", choices=("keypoint", "smpld", "mask"), default="keypoint",
+                    help="smpld: the SMPL+D loop (one evaluation per step); mask: the keypoint stage with the silhouette term, against --parent-root")
+    ap.add_argument("--parent-root", default=None, help="--stage mask: a checkout of the parent commit with its library built")
     a = ap.parse_args()
+    if a.stage == "mask":
+        if a.child:
+            return child_mask(a.child, a.parent_root if a.child == "parent" else REPO, a.iters, a.loops)
+        if not a.parent_root or not os.path.isdir(os.path.join(a.parent_root, "bodyfitting_amd")):
+            ap.error("--stage mask measures against the parent commit: --parent-root DIR (a checkout of it, built)")
+        a.batches = [1]
+    sides = ("device", "parent") if a.stage == "mask" else ("device", "host")
     if a.child:
         return child_smpld(a.child, a.iters, a.loops) if a.stage == "smpld" else child(a.child, a.batch, a.iters, a.views, a.loops)
     if a.stage == "smpld":
@@ -158,9 +238,11 @@ def main():
     runs = []
     for batch in a.batches:
         for rep in range(a.reps):
-            for route in ("device", "host"):
+            for route in sides:
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", route, "--batch", str(batch), "--iters", str(a.iters),
                        "--views", str(a.views), "--loops", str(a.loops), "--stage", a.stage]
+                if a.parent_root:
+                    cmd += ["--parent-root", os.path.abspath(a.parent_root)]
                 done = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
                 if done.returncode != 0:            # (a child that failed ends the run: nothing more is started on the card)
                     sys.stderr.write(done.stdout[-2000:] + done.stderr[-4000:])
@@ -170,13 +252,13 @@ def main():
     summary = []
     for batch in a.batches:
         row = {"batch": batch}
-        for route in ("device", "host"):
+        for route in sides:
             t = [s for r in runs if r["batch"] == batch and r["route"] == route for s in r["seconds"]]
             row[route] = {"median_ms": statistics.median(t) * 1e3, "min_ms": min(t) * 1e3, "max_ms": max(t) * 1e3, "n": len(t)}
-        spread = max(row[r]["max_ms"] - row[r]["min_ms"] for r in ("device", "host"))
-        row["host_minus_device_ms"] = row["host"]["median_ms"] - row["device"]["median_ms"]
+        spread = max(row[r]["max_ms"] - row[r]["min_ms"] for r in sides)
+        row[f"{sides[1]}_minus_device_ms"] = row[sides[1]]["median_ms"] - row["device"]["median_ms"]
         row["larger_spread_ms"] = spread
-        row["device_faster_beyond_spread"] = row["host_minus_device_ms"] > spread
+        row["device_faster_beyond_spread"] = row[f"{sides[1]}_minus_device_ms"] > spread
         summary.append(row)
     result = {"stage": a.stage, "iters": a.iters, "views": a.views, "summary": summary, "runs": runs}
     print(json.dumps({"summary": summary}))
