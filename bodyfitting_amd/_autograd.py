@@ -58,13 +58,24 @@ def shares_runtime(device_index, address):
     return _SHARED[device_index]
 
 
+def takes_device_route(device_index, *tensors, dtypes=("torch.float32",)):
+    """do these go the device route of a native object on GPU device_index (None: it offers none)?  `route_for`'s rule, `shares_runtime`
+    asked only once everything else says "device"; arrays, None and objects without `data_ptr` (no address to hand over): False"""
+    if route_for(tensors, device_index, enabled(), True, dtypes) != "device" or not all(hasattr(t, "data_ptr") for t in tensors):
+        return False
+    return shares_runtime(device_index, tensors[0].data_ptr())
+
+
 def chosen_route(inputs, device_route, dtypes=("torch.float32",)):
     """the route `apply` takes for these inputs"""
-    device_index = None if device_route is None else device_route.device
-    if route_for(inputs, device_index, enabled(), True, dtypes) != "device":
-        return "host"
-    address = next(t for t in inputs if t is not None).data_ptr()
-    return route_for(inputs, device_index, True, shares_runtime(device_index, address), dtypes)
+    present = [t for t in inputs if t is not None]
+    return "device" if takes_device_route(getattr(device_route, "device", None), *present, dtypes=dtypes) else "host"
+
+
+def stream_of(tensor):
+    """the handle of torch's current stream on the tensor's GPU: what a *_dev entry point queues its work on"""
+    import torch
+    return torch.cuda.current_stream(tensor.device).cuda_stream
 
 
 def apply(forward, vjp, inputs, device_route=None):
@@ -152,7 +163,7 @@ def _device_function():
     import torch
     from torch.autograd.function import once_differentiable
 
-    def stream_of(route):
+    def route_stream(route):
         return torch.cuda.current_stream(route.device).cuda_stream
 
     class DeviceFunction(torch.autograd.Function):
@@ -162,7 +173,7 @@ def _device_function():
             ctx.route = route
             ctx.present = [t is not None for t in inputs]
             ctx.save_for_backward(*[t for t in inputs if t is not None])
-            return tuple(route.forward([None if t is None else t.detach().contiguous() for t in inputs], stream_of(route)))
+            return tuple(route.forward([None if t is None else t.detach().contiguous() for t in inputs], route_stream(route)))
 
         @staticmethod
         @once_differentiable
@@ -174,7 +185,7 @@ def _device_function():
                 return (None,) * (1 + len(inputs))
             route = ctx.route
             grads = route.vjp([None if t is None else t.detach().contiguous() for t in inputs],
-                              [None if c is None else c.contiguous() for c in cotangents], want, stream_of(route))
+                              [None if c is None else c.contiguous() for c in cotangents], want, route_stream(route))
             return (None,) + tuple(g.reshape(x.shape) if w and g is not None else None for g, x, w in zip(grads, inputs, want))
 
     _DEVICE_FUNCTION.append(DeviceFunction)

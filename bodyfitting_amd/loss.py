@@ -20,7 +20,7 @@ inputs' device, differentiable once; numpy in -> a float.  The two scan losses o
 keeps its last query's answer, so the second one does not search again.  float32 tensors on the scan's / the topology's GPU take
 the device route (bf_scan_point_loss_dev, bf_normal_loss_dev, bf_normal_laplacian_dev): addresses in, the loss a tensor that never
 leaves the GPU, the closest faces' normals gathered in the kernel, the backward a scaling launch that reads the cotangent where it
-lies; the searcher's memo is then the points TENSOR by identity and `_version` (mesh_grid_searcher.memo_hit).
+lies; the searcher's memo is then the points TENSOR, held, by identity and version (mesh_grid_searcher.memo_hit).
 They take this project's MeshGridSearcher, arrays and
 tensors; anything else raises NotImplementedError (SMPLify's fused stage is the other path), every other refusal is a ValueError.
 
@@ -33,12 +33,10 @@ once per distinct set (four sets remembered) and the loss is bf_silhouette_loss_
 """
 from __future__ import annotations
 
-import hashlib
-import weakref
-
 import numpy as np
 
 from . import _autograd
+from . import _memo
 from . import normals as _normals
 from .keypoints import FACE_MAPPING, pack_keypoints_smplx          # noqa: F401  (FACE_MAPPING: a name of loss.py, re-exported)
 from . import prior as _prior
@@ -139,16 +137,16 @@ def _scalar_loss(who, x, call, plus_zero=False, device=None, device_call=None):
     return _autograd.apply(forward, vjp, (x,), device_route=route)[0].reshape(())
 
 
-def _takes_device_route(device, *tensors, dtypes=("torch.float32",)):
-    """do these go the device route of a native object on GPU `device` (None: it offers none)?  _autograd.route_for's rule"""
-    if device is None or not all(_is_tensor(t) and hasattr(t, "data_ptr") for t in tensors):
-        return False
-    return _autograd.chosen_route(list(tensors), type("Offer", (), {"device": device})(), dtypes) == "device"
+_takes_device_route = _autograd.takes_device_route
 
 
 def _new(like, shape, dtype=None):
     import torch
     return torch.empty(shape, dtype=dtype or torch.float32, device=like.device)
+
+
+def _value_and_grad(x, want_grad, n_values=1):          # (what a `device_call` of _scalar_loss fills, on x's GPU)
+    return _new(x, n_values), (_new(x, x.shape) if want_grad else None)
 
 
 def _scan_of(who, mesh_grid_searcher):
@@ -181,8 +179,7 @@ def point_cloud_loss_mesh_grid(mesh_grid_searcher, points):
     def device_call(p, want_grad, stream):
         import torch
         n = p.numel() // 3
-        value, ids, nearest = _new(p, 1), _new(p, n, torch.int32), _new(p, (n, 3))
-        grad = _new(p, p.shape) if want_grad else None
+        (value, grad), ids, nearest = _value_and_grad(p, want_grad), _new(p, n, torch.int32), _new(p, (n, 3))
         scan.point_loss_dev(n, stream, p.data_ptr(), loss=value.data_ptr(), face_ids=ids.data_ptr(), nearest=nearest.data_ptr(),
                             dpoints=0 if grad is None else grad.data_ptr())
         mesh_grid_searcher._remember_query_dev(points, ids, nearest)          # (the caller's tensor: what the next loss is handed)
@@ -215,13 +212,11 @@ def normal_loss_mesh_grid(mesh_grid_searcher, points, face_norm_mesh=None, point
     device = getattr(scan, "dev_route_device", None)
     if _takes_device_route(device, points, face_norm_mesh, point_norm):
         # everything is on the scan's GPU: the ids stay there (the tensor memo, or a search queued here) and the kernel gathers
-        import torch
-        ids = mesh_grid_searcher._query_dev(points, torch.cuda.current_stream(points.device).cuda_stream)
+        ids = mesh_grid_searcher._query_dev(points, _autograd.stream_of(points))
         table = face_norm_mesh.detach().contiguous()
 
         def device_call(pn, want_grad, stream):
-            value = _new(pn, 1)
-            grad = _new(pn, pn.shape) if want_grad else None
+            value, grad = _value_and_grad(pn, want_grad)
             native.normal_loss_dev(scan.workspace(), stream, rows[0], ids.data_ptr(), table.data_ptr(), scan.n_faces, pn.data_ptr(),
                                    loss=value.data_ptr(), dpoint_norms=0 if grad is None else grad.data_ptr())
             return value, grad
@@ -253,8 +248,7 @@ def normal_laplacian_smoothness(norms, faces):
         return native.normal_laplacian(topo, a.reshape(-1, 3), want_grad=want_grad)
 
     def device_call(a, want_grad, stream):
-        value = _new(a, 1)
-        grad = _new(a, a.shape) if want_grad else None
+        value, grad = _value_and_grad(a, want_grad)
         native.normal_laplacian_dev(topo, stream, a.data_ptr(), loss=value.data_ptr(), dnorms=0 if grad is None else grad.data_ptr())
         return value, grad
 
@@ -265,9 +259,12 @@ def normal_laplacian_smoothness(norms, faces):
 # the silhouette term (loss.py:73-130)
 # ----------------------------------------------------------------------------------------------------------------------------
 
-_SILHOUETTES = {}           # key -> dict(ref, version, sil, contours (host [C,2] arrays), given (extract_countours' last hand-outs))
 _SILHOUETTE_SLOTS = 4       # mask sets kept at a time; the oldest goes first
+_GIVEN_SLOTS = 4            # hand-outs of extract_countours recognised per mask set
 MASK_STRIDE = 4             # loss.py:99: every 4th vertex
+
+
+_SILHOUETTES = {}           # a table of _memo.py: (masks, GPU, contour digest) -> sil, contours (host [C,2] arrays), given (a table of the hand-outs); dropped: closed
 
 
 def _items(x):
@@ -295,34 +292,17 @@ def _masks_host(who, masks):
     return np.ascontiguousarray(host != 0, dtype=np.uint8)
 
 
-def _masks_key(masks, device, contour_key):
-    """-> (key, (weak reference, version) of a tensor or (None, 0)); like normals.topology_for: a tensor by identity and version, an
-    array by a digest of its bytes"""
-    if _is_tensor(masks):
-        return ("tensor", id(masks), int(device), contour_key), (weakref.ref(masks), masks._version)
-    a = np.ascontiguousarray(masks)
-    digest = hashlib.sha1(a.tobytes() + repr((a.shape, a.dtype.str)).encode()).hexdigest()
-    return ("array", digest, int(device), contour_key), (None, 0)
+def _silhouette_hit(masks, device, contour_key):
+    """-> (key, the objects a look-up checks, the entry or None): like normals.topology_for"""
+    seen = []
+    key = (_memo.part(masks, seen), int(device), contour_key)
+    return key, seen, _memo.find(_SILHOUETTES, key, seen)
 
 
-def _silhouette_hit(key, masks):
-    hit = _SILHOUETTES.get(key)
-    if hit is None:
-        return None
-    if _is_tensor(masks) and not (hit["ref"]() is masks and hit["version"] == masks._version):
-        return None
-    return hit
-
-
-def _silhouette_store(key, entry, sil, contours, given):
+def _silhouette_store(key, seen, sil, contours):
     """contours None: an object made on the device route - its host copies are fetched when something asks (_hit_contours)"""
-    old = _SILHOUETTES.pop(key, None)
-    if old is not None:
-        old["sil"].close()
-    while len(_SILHOUETTES) >= _SILHOUETTE_SLOTS:
-        _SILHOUETTES.pop(next(iter(_SILHOUETTES)))["sil"].close()          # (closes the object's workspace, then the object)
-    _SILHOUETTES[key] = {"ref": entry[0], "version": entry[1], "sil": sil, "contours": contours, "given": given}
-    return _SILHOUETTES[key]
+    return _memo.store(_SILHOUETTES, _SILHOUETTE_SLOTS, key, seen, {"sil": sil, "contours": contours, "given": {}},
+                       closed=lambda hit: hit["sil"].close())
 
 
 def _hit_contours(hit):
@@ -334,14 +314,21 @@ def _hit_contours(hit):
 _MASK_DTYPES = {"torch.float32": 1, "torch.uint8": 0, "torch.bool": 0}          # -> native.MASK_FLOAT32 / MASK_UINT8
 
 
-def _masks_route(masks, device):
-    """"device" when extract_countours hands `masks` to the GPU `device` by address: a float32 / uint8 / bool tensor on that GPU,
-    the switch on, one shared runtime and a library that has the entries (_autograd.route_for's rule); else "host" - never an error"""
+def _silhouette_offers():
+    """does the library have the silhouette's device entries?  A condition of both mask routes beside _autograd.takes_device_route"""
     from . import native
     offers = getattr(native.Silhouette, "offers_dev", None)
-    if offers is None or not _takes_device_route(device, masks, dtypes=tuple(_MASK_DTYPES)):
-        return "host"
-    return "device" if offers() else "host"
+    return offers is not None and offers()
+
+
+def _masks_route(masks, device):
+    """"device" when extract_countours hands `masks` to the GPU `device` by address, else "host" - never an error"""
+    return "device" if _takes_device_route(device, masks, dtypes=tuple(_MASK_DTYPES)) and _silhouette_offers() else "host"
+
+
+def _mask_loss_route(smpl_verts, device):
+    """"device" when multview_mask_loss evaluates on GPU `device` where the vertices lie, else "host" - never an error"""
+    return "device" if _silhouette_offers() and _takes_device_route(device, smpl_verts) else "host"
 
 
 def _contours_on_device(sil, like):
@@ -349,7 +336,7 @@ def _contours_on_device(sil, like):
     import torch
     counts = [int(c) for c in sil.counts()]
     xy = torch.empty((max(sum(counts), 1), 2), dtype=torch.float32, device=like.device)
-    sil.contours_dev(xy.data_ptr(), torch.cuda.current_stream(like.device).cuda_stream)
+    sil.contours_dev(xy.data_ptr(), _autograd.stream_of(like))
     ends = np.cumsum(counts)
     return [xy[int(e) - c:int(e)].reshape(-1, 1, 2) for c, e in zip(counts, ends)]
 
@@ -365,27 +352,24 @@ def extract_countours(masks, device=None):
     _normals.require_no_grad(who, "masks", masks)
     if device is None:
         device = _normals.device_index(masks)
-    key, entry = _masks_key(masks, device, None)
-    hit = _silhouette_hit(key, masks)
+    key, seen, hit = _silhouette_hit(masks, device, None)
     on_device = _masks_route(masks, device) == "device"
     if hit is None and on_device:
         # the masks go in by address, on torch's current stream: binarised and checked by a kernel, only M + 1 flags come back
-        import torch
         shape = (1,) + tuple(masks.shape) if masks.ndim == 2 else tuple(masks.shape)
         if len(shape) != 3 or 0 in shape:
             raise ValueError(f"{who}: masks must be [M,H,W] (or [H,W]), not {tuple(masks.shape)}")
         m = masks.detach().contiguous()
         try:
-            sil = native.Silhouette.from_device(m.data_ptr(), shape, _MASK_DTYPES[str(m.dtype)],
-                                                torch.cuda.current_stream(m.device).cuda_stream, device=device)
+            sil = native.Silhouette.from_device(m.data_ptr(), shape, _MASK_DTYPES[str(m.dtype)], _autograd.stream_of(m), device=device)
         except native.MasksRefused as e:
             if e.view is None:
                 raise ValueError(f"{who}: masks must hold 0 / 1 only (the reference reads them as numbers: mask < 0.1, 1 - mask)") from None
             raise ValueError(f"{who}: mask {e.view} has no foreground (the reference fails in np.argmax of an empty list)") from None
-        hit = _silhouette_store(key, entry, sil, None, None)
+        hit = _silhouette_store(key, seen, sil, None)
     if on_device and getattr(hit["sil"], "dev_route_device", None) == device:
         out = _contours_on_device(hit["sil"], masks)
-        _note_given(hit, out)
+        _memo.store(hit["given"], _GIVEN_SLOTS, tuple(map(id, out)), out, {})          # (recognised by identity later)
         return out
     if hit is None:
         host = _masks_host(who, masks)
@@ -393,30 +377,22 @@ def extract_countours(masks, device=None):
         if empty:
             raise ValueError(f"{who}: mask {empty[0]} has no foreground (the reference fails in np.argmax of an empty list)")
         sil = native.Silhouette(host, None, device=device)           # (contour_select: OpenCV's first listed contour, the default)
-        hit = _silhouette_store(key, entry, sil, [np.asarray(c, np.float32).reshape(-1, 2) for c in sil.contours()], None)
+        hit = _silhouette_store(key, seen, sil, [np.asarray(c, np.float32).reshape(-1, 2) for c in sil.contours()])
     out = [c.reshape(-1, 1, 2).copy() for c in _hit_contours(hit)]
     if _is_tensor(masks):
         import torch
         out = [torch.from_numpy(c).to(masks.device) for c in out]
-        _note_given(hit, out)
+        _memo.store(hit["given"], _GIVEN_SLOTS, tuple(map(id, out)), out, {})          # (recognised by identity later)
     return out
-
-
-def _note_given(hit, out):
-    """remember a hand-out of extract_countours beside the earlier ones (the last four): each is recognised by identity later"""
-    hit["given"] = ((hit["given"] or []) + [[(weakref.ref(c), c._version) for c in out]])[-4:]
 
 
 def _silhouette_for(who, masks, contours, device):
     """the `native.Silhouette` of (masks, contours) on GPU `device`: the one extract_countours built when these are its contours,
     else one with the caller's contours uploaded"""
     from . import native
-    key, entry = _masks_key(masks, device, None)
-    hit = _silhouette_hit(key, masks)
-    if hit is not None and hit["sil"].n_views == len(contours):
-        for given in hit["given"] or ():
-            if all(_is_tensor(c) and r() is c and ver == c._version for c, (r, ver) in zip(contours, given)):
-                return hit["sil"]
+    key, seen, hit = _silhouette_hit(masks, device, None)
+    if hit is not None and hit["sil"].n_views == len(contours) and _memo.find(hit["given"], tuple(map(id, contours)), contours) is not None:
+        return hit["sil"]
     known = _known_contours(masks, contours, device)
     if known is not None:
         return known
@@ -430,78 +406,60 @@ def _silhouette_for(who, masks, contours, device):
         host.append(np.ascontiguousarray(a.reshape(-1, 2)))
     if hit is not None and hit["sil"].n_views == len(host) and all(np.array_equal(a, b) for a, b in zip(host, _hit_contours(hit))):
         return _remember_contours(masks, contours, device, hit["sil"])
-    digest = hashlib.sha1(b"".join(a.tobytes() for a in host) + repr([len(a) for a in host]).encode()).hexdigest()
-    key, entry = _masks_key(masks, device, digest)
-    hit = _silhouette_hit(key, masks)
+    digest = _memo.digest(data=b"".join(a.tobytes() for a in host) + repr([len(a) for a in host]).encode())
+    key, seen, hit = _silhouette_hit(masks, device, digest)
     if hit is None:
-        hit = _silhouette_store(key, entry, native.Silhouette(_masks_host(who, masks), host, device=device), host, None)
+        hit = _silhouette_store(key, seen, native.Silhouette(_masks_host(who, masks), host, device=device), host)
     return _remember_contours(masks, contours, device, hit["sil"])
 
 
-_KNOWN_CONTOURS = []        # dict(masks (weak reference, version), device, items [(tensor, version)], sil): contour tensors that are
-_KNOWN_CONTOUR_SLOTS = 4    # not extract_countours' own and have been read and matched to an object once; the oldest goes first
+_KNOWN_CONTOUR_SLOTS = 4    # contour tensors that are not extract_countours' own and have been read and matched to an object once:
+_KNOWN_CONTOURS = {}        # a table of _memo.py: (masks, GPU, contours) -> sil, that object; masks not held, the contours HELD
 
 
 def _known_contours(masks, contours, device):
-    """the object these contour TENSORS were matched to before - the same tensors at the same `_version` beside the same masks - or
+    """the object these contour TENSORS were matched to before - the same tensors at the same version beside the same masks - or
     None: a loop that passes its own contours reads them back once, not at every step.  (The tensors are held while remembered:
     an identity cannot come back with other contents.)"""
     if not (_is_tensor(masks) and all(_is_tensor(c) for c in contours)):
         return None
-    for e in _KNOWN_CONTOURS:
-        if (e["device"] == device and e["masks"][0]() is masks and e["masks"][1] == masks._version and len(e["items"]) == len(contours)
-                and all(t is c and ver == c._version for c, (t, ver) in zip(contours, e["items"]))
-                and any(h["sil"] is e["sil"] for h in _SILHOUETTES.values())):          # (still cached: not closed by an eviction)
-            return e["sil"]
-    return None
+    hit = _memo.find(_KNOWN_CONTOURS, (id(masks), device, tuple(map(id, contours))), [masks, *contours])
+    cached = hit is not None and any(h["sil"] is hit["sil"] for h in _SILHOUETTES.values())          # (not closed by an eviction)
+    return hit["sil"] if cached else None
 
 
 def _remember_contours(masks, contours, device, sil):
     if _is_tensor(masks) and all(_is_tensor(c) for c in contours):
-        del _KNOWN_CONTOURS[:max(0, len(_KNOWN_CONTOURS) - _KNOWN_CONTOUR_SLOTS + 1)]
-        _KNOWN_CONTOURS.append({"masks": (weakref.ref(masks), masks._version), "device": device,
-                                "items": [(c, c._version) for c in contours], "sil": sil})
+        _memo.store(_KNOWN_CONTOURS, _KNOWN_CONTOUR_SLOTS, (id(masks), device, tuple(map(id, contours))), [masks, *contours], {"sil": sil},
+                    hold=[False] + [True] * len(contours))
     return sil
 
 
-def _mask_loss_route(smpl_verts, device):
-    """"device" when multview_mask_loss evaluates on GPU `device` where the vertices lie: _autograd.route_for's rule for `smpl_verts`
-    and a library that has the entries; else "host" - never an error"""
-    from . import native
-    offers = getattr(native.Silhouette, "offers_dev", None)
-    if offers is None or not offers():
-        return "host"
-    return "device" if _takes_device_route(device, smpl_verts) else "host"
-
-
-_CAMERAS = {}               # key -> dict(held (the camera objects: an id in the key cannot be recycled), w2c, K (stacked, on the GPU))
 _CAMERA_SLOTS = 4           # camera sets kept at a time; the oldest goes first
+_CAMERAS = {}               # a table of _memo.py: (device, camera objects) -> w2c, K stacked there; the objects are HELD: their ids are the key
 CAMERA_STATS = {"stacks": 0}          # how often a camera set was stacked on a GPU (the tests read it)
 
 
 def _cameras_for(who, cameras, n_views, torch_device):
     """w2cs, Ks (each one stacked tensor, or a list of tensors) as float32 [M,4,4] and [M,3,3] on `torch_device`: stacked there once
-    per distinct set - its items by identity and `_version`, like _views_for - and remembered.  GPU cameras are never read back;
+    per distinct set - its items by identity and version, like _views_for - and remembered.  GPU cameras are never read back;
     CPU tensors are sent once per set."""
     import torch
     items = [x if _is_tensor(x) else list(x) for x in cameras]
     flat = [it for x in items for it in ([x] if _is_tensor(x) else x)]
-    key = (str(torch_device), n_views, tuple(len(x) if isinstance(x, list) else -1 for x in items), tuple((id(t), t._version) for t in flat))
-    hit = _CAMERAS.get(key)
-    if hit is not None:
-        return hit["w2c"], hit["K"]
-    out = []
-    try:
-        for x, side in zip(items, (4, 3)):
-            x = x.detach() if _is_tensor(x) else torch.stack([t.detach().reshape(side, side) for t in x])
-            out.append(x.reshape(n_views, side, side).to(device=torch_device, dtype=torch.float32).contiguous())
-    except RuntimeError:
-        raise ValueError(f"{who}: w2cs must be [M,4,4] and Ks [M,3,3]") from None
-    CAMERA_STATS["stacks"] += 1
-    while len(_CAMERAS) >= _CAMERA_SLOTS:
-        _CAMERAS.pop(next(iter(_CAMERAS)))
-    _CAMERAS[key] = {"held": flat, "w2c": out[0], "K": out[1]}
-    return out[0], out[1]
+    key = (torch_device, n_views, tuple(len(x) if isinstance(x, list) else -1 for x in items), tuple(map(id, flat)))
+    hit = _memo.find(_CAMERAS, key, flat)
+    if hit is None:
+        out = []
+        try:
+            for x, side in zip(items, (4, 3)):
+                x = x.detach() if _is_tensor(x) else torch.stack([t.detach().reshape(side, side) for t in x])
+                out.append(x.reshape(n_views, side, side).to(device=torch_device, dtype=torch.float32).contiguous())
+        except RuntimeError:
+            raise ValueError(f"{who}: w2cs must be [M,4,4] and Ks [M,3,3]") from None
+        CAMERA_STATS["stacks"] += 1
+        hit = _memo.store(_CAMERAS, _CAMERA_SLOTS, key, flat, {"w2c": out[0], "K": out[1]}, hold=True)
+    return hit["w2c"], hit["K"]
 
 
 def multview_mask_loss(contours, masks, smpl_verts=None, smpl_faces=None, w2cs=None, Ks=None, mask_frames=None, epsilon=10, imsize=512,
@@ -557,8 +515,7 @@ def multview_mask_loss(contours, masks, smpl_verts=None, smpl_faces=None, w2cs=N
         sil = _silhouette_for(who, masks, contours, device)
         if getattr(sil, "dev_route_device", None) == device:
             def device_call(v, want_grad, stream):
-                terms = _new(v, 1 + 2 * n_masks)
-                grad = _new(v, v.shape) if want_grad else None
+                terms, grad = _value_and_grad(v, want_grad, 1 + 2 * n_masks)
                 sil.loss_dev(stream, v.numel() // 3, v.data_ptr(), w2c_t.data_ptr(), K_t.data_ptr(), imsize=imsize, epsilon=epsilon,
                              stride=MASK_STRIDE, cdist_form=pairwise != "exact", terms=terms.data_ptr(),
                              dverts=0 if grad is None else grad.data_ptr())
@@ -592,51 +549,41 @@ def _no_grad_input(name, x):
             raise ValueError(f"multiview_keypoint_loss: {name} requires grad; gradients flow to model_joints, poses and betas only")
 
 
-_VIEWS = {}                 # key -> dict(refs, host (w2c, K, kp, present), dev {gpu: the four as tensors})
 _VIEW_SLOTS = 4             # view sets kept at a time; the oldest goes first
+_VIEWS = {}                 # a table of _memo.py: cameras and keypoints -> host (w2c, K, kp, present), dev {gpu: the four as tensors}; tensors not held
 VIEW_STATS = {"packs": 0, "uploads": 0}          # how often a view set was packed on the host / sent to a GPU (the tests read them)
 
 
 def _views_key(w2cs, Ks, keypoints, n_use, use_hand_face, rows):
-    """-> (key, [(weak reference, version)] of its tensors): like _masks_key, a tensor by identity and version, anything else by a
-    digest of its contents"""
-    refs = []
+    """-> (key, the tensors a look-up checks): like _silhouette_hit, a tensor by identity and version, anything else by a digest of its
+    contents"""
+    seen = []
 
     def one(a):
-        if a is None:
-            return None
-        if _is_tensor(a):
-            refs.append((weakref.ref(a), a._version))
-            return ("tensor", id(a), a._version)
-        a = np.ascontiguousarray(a)
-        return ("array", hashlib.sha1(a.tobytes() + repr((a.shape, a.dtype.str)).encode()).hexdigest())
+        return None if a is None else _memo.part(a, seen)
 
-    def entry(k):
-        return None if k is None else tuple(sorted((part, one(a)) for part, a in k.items()))
+    def entry(k):                # (by part name, whatever order the dict was filled in: `seen` is collected in the key's order)
+        return None if k is None else tuple((part, one(a)) for part, a in sorted(k.items()))
 
     def cameras(x):              # (a stacked tensor is one object: its rows would be new views at every call)
         return one(x) if _is_tensor(x) else tuple(one(x[i]) for i in range(min(n_use, len(x))))
 
     key = (n_use, bool(use_hand_face), rows, cameras(w2cs), cameras(Ks), tuple(entry(keypoints[i]) for i in range(min(n_use, len(keypoints)))))
-    return key, refs
+    return key, seen
 
 
 def _views_for(w2cs, Ks, keypoints, n_use, use_hand_face, rows):
     """the packed views of this call: remembered ones when the same cameras and keypoints come again, else packed now"""
     try:
-        key, refs = _views_key(w2cs, Ks, keypoints, n_use, use_hand_face, rows)
+        key, seen = _views_key(w2cs, Ks, keypoints, n_use, use_hand_face, rows)
     except (TypeError, AttributeError):          # (something that is neither: packed every time, as before)
         return {"host": _pack_views(w2cs, Ks, keypoints, n_use, use_hand_face, rows), "dev": {}}
-    hit = _VIEWS.get(key)
-    if hit is not None and all(r() is not None and r()._version == ver for r, ver in hit["refs"]):
+    hit = _memo.find(_VIEWS, key, seen)
+    if hit is not None:
         return hit
-    _VIEWS.pop(key, None)
     packed = _pack_views(w2cs, Ks, keypoints, n_use, use_hand_face, rows)
     VIEW_STATS["packs"] += 1
-    while len(_VIEWS) >= _VIEW_SLOTS:
-        _VIEWS.pop(next(iter(_VIEWS)))
-    _VIEWS[key] = {"refs": refs, "host": packed, "dev": {}}
-    return _VIEWS[key]
+    return _memo.store(_VIEWS, _VIEW_SLOTS, key, seen, {"host": packed, "dev": {}})
 
 
 def _views_on(views, device):

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _autograd
 from .native import Scan
 
 
@@ -32,13 +33,6 @@ def _to_np(x, dtype):
     if _is_tensor(x):
         x = x.detach().cpu().numpy()
     return np.ascontiguousarray(np.asarray(x, dtype=dtype))
-
-
-class _Offer:
-    """what _autograd.chosen_route asks of a device route: the GPU it is offered on (None: none)"""
-
-    def __init__(self, device):
-        self.device = device
 
 
 class MeshGridSearcher:
@@ -140,16 +134,8 @@ class MeshGridSearcher:
         return ids, nearest, bary
 
     def _takes_device_route(self, *tensors):
-        """float32 tensors on the scan's GPU, the switch on, the runtimes shared (_autograd.route_for)"""
-        if not all(_is_tensor(t) and hasattr(t, "data_ptr") for t in tensors):
-            return False
-        from . import _autograd
-        return _autograd.chosen_route(list(tensors), _Offer(getattr(self._scan, "dev_route_device", None))) == "device"
-
-    @staticmethod
-    def _stream(points):
-        import torch
-        return torch.cuda.current_stream(points.device).cuda_stream
+        """float32 tensors on the scan's GPU, the switch on, the runtimes shared"""
+        return _autograd.takes_device_route(getattr(self._scan, "dev_route_device", None), *tensors)
 
     def _need_mesh(self):
         if self._scan is None:
@@ -167,7 +153,7 @@ class MeshGridSearcher:
         (its backward is commented out, :17-49)"""
         self._need_mesh()
         if self._takes_device_route(points):
-            ids, pts, _ = self._search_dev(points, self._stream(points))
+            ids, pts, _ = self._search_dev(points, _autograd.stream_of(points))
             return pts, ids
         pts, ids, _ = self._scan.nearest_points(_to_np(points, np.float32).reshape(-1, 3))
         return self._back(points, pts, ids)
@@ -176,7 +162,7 @@ class MeshGridSearcher:
         """the third output of the kernel (`coeff`, :10-14), which the reference's wrapper drops"""
         self._need_mesh()
         if self._takes_device_route(points):
-            ids, pts, bary = self._search_dev(points, self._stream(points), with_coefficients=True)
+            ids, pts, bary = self._search_dev(points, _autograd.stream_of(points), with_coefficients=True)
             return pts, ids, bary
         pts, ids, bary = self._scan.nearest_points(_to_np(points, np.float32).reshape(-1, 3))
         return self._back(points, pts, ids, bary)

@@ -166,7 +166,7 @@ def offers_mesh_loss_dev(lib):
 
 
 def _own_workspace(obj):
-    """the `Workspace` of `obj` (a Topology, a Scan), made on first use and closed with it"""
+    """the `Workspace` of `obj` (a DeviceModel, a Gmm, a Topology, a Scan, a Silhouette), made on first use and closed with it"""
     ws = obj.__dict__.get("_workspace")
     if ws is None:
         ws = obj.__dict__.setdefault("_workspace", Workspace(obj.device))
@@ -225,9 +225,7 @@ class DeviceModel:
         return ids
 
     def close(self):
-        ws = self.__dict__.pop("_workspace", None)
-        if ws is not None:
-            ws.close()
+        _close_workspace(self)
         if getattr(self, "_h", None):
             self._lib.bf_model_destroy(self._h)
             self._h = None
@@ -240,10 +238,7 @@ class DeviceModel:
 
     def workspace(self):
         """the model's own `Workspace` for the device route, made on first use and closed with the model"""
-        ws = self.__dict__.get("_workspace")
-        if ws is None:
-            ws = self.__dict__.setdefault("_workspace", Workspace(self.device))
-        return ws
+        return _own_workspace(self)
 
     # The device route (bf_*_dev): the four calls below on device ADDRESSES (integers, e.g. a tensor's data_ptr(); 0 / None = NULL)
     # of contiguous float32 arrays on the model's GPU, queued on `stream` (a hipStream_t handle, 0: the null stream).  They return
@@ -936,19 +931,14 @@ class Gmm:
                                      C.byref(self._h)), "bf_gmm_create")
 
     def close(self):
-        ws = self.__dict__.pop("_workspace", None)
-        if ws is not None:
-            ws.close()
+        _close_workspace(self)
         if getattr(self, "_h", None):
             self._lib.bf_gmm_destroy(self._h)
             self._h = None
 
     def workspace(self):
         """the `Workspace` of device-route losses with this prior, made on first use and closed with it"""
-        ws = self.__dict__.get("_workspace")
-        if ws is None:
-            ws = self.__dict__.setdefault("_workspace", Workspace(self.device))
-        return ws
+        return _own_workspace(self)
 
     def __del__(self):  # pragma: no cover
         try:

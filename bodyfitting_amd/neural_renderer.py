@@ -18,19 +18,18 @@ grad are the inputs of one autograd node per render (rgb, depth and alpha cotang
 not differentiated.
 
 Tensors in give float32 tensors out on the vertices' device; arrays in give arrays out.  The device meshes are remembered per
-(vertices, faces) object and GPU - a tensor by identity and `_version`, an array by a digest, four at a time - and a mesh's textures
-go up again only when their object or `_version` changed: in the reference's loop the scan's once, the fitted ones once per
-`optimizer.step()`.  torch is imported on first use only.
+(vertices, faces) object and GPU - stamps and a table of _memo.py: a tensor by identity and version, an array by a digest, four at
+a time - and a mesh's textures go up again only when their stamp no longer holds: in the reference's loop the scan's once, the
+fitted ones once per `optimizer.step()`.  torch is imported on first use only.
 """
 from __future__ import annotations
 
-import hashlib
 import os
-import weakref
 
 import numpy as np
 
 from . import _autograd
+from . import _memo
 from . import native
 from . import obj_textures as OT
 
@@ -70,20 +69,9 @@ def _gpu_of(x):
     return x.device.index or 0 if _is_tensor(x) and x.device.type == "cuda" else 0
 
 
-def _stamp(x):
-    """what tells whether `x` is still what was last seen: (weak reference, version) of a tensor, a digest of an array"""
-    if _is_tensor(x):
-        return ("tensor", weakref.ref(x), x._version)
-    a = np.ascontiguousarray(x)
-    return ("array", hashlib.sha1(a.tobytes() + repr((a.shape, a.dtype.str)).encode()).hexdigest(), 0)
-
-
-def _same(stamp, x):
-    if stamp is None or (stamp[0] == "tensor") != _is_tensor(x):
-        return False
-    if stamp[0] == "tensor":
-        return stamp[1]() is x and stamp[2] == x._version
-    return stamp == _stamp(x)
+def _close_meshes(entry):
+    for m in entry["meshes"]:
+        m.close()
 
 
 class _Tapes:
@@ -135,7 +123,7 @@ class Renderer:
         self.rasterizer_eps = 1e-3
         self.geometry_grad = GEOMETRY_GRAD     # not a constructor parameter (the list above is the reference's)
         self._native = {}           # gpu -> (configuration, native.NrRenderer)
-        self._meshes = {}           # key -> dict(v, f: stamps; gpu, ts, meshes [per batch item], tex: stamp of what was last sent)
+        self._meshes = {}           # a table of _memo.py: key -> v, f, tex (last sent): stamps; gpu, ts, meshes [per batch item], closed when dropped
 
     # ---- nn.Module's surface the reference's callers touch ----
     def to(self, *args, **kwargs):
@@ -154,10 +142,8 @@ class Renderer:
         return None
 
     def close(self):
-        for entry in self._meshes.values():
-            for m in entry["meshes"]:
-                m.close()
-        self._meshes = {}
+        for key in list(self._meshes):
+            _memo.drop(self._meshes, key, _close_meshes)
         for _, r in self._native.values():
             r.close()
         self._native = {}
@@ -175,8 +161,7 @@ class Renderer:
         if have is None or have[0] != cfg:
             if have is not None:                         # its meshes go with it
                 for key in [k for k, e in self._meshes.items() if e["gpu"] == gpu]:
-                    for m in self._meshes.pop(key)["meshes"]:
-                        m.close()
+                    _memo.drop(self._meshes, key, _close_meshes)
                 have[1].close()
             have = (cfg, native.NrRenderer(cfg[0], cfg[1], cfg[2], cfg[3], cfg[4], device=gpu))
             self._native[gpu] = have
@@ -187,32 +172,29 @@ class Renderer:
     def _meshes_for(self, r, gpu, vertices, faces, v_host, f_host, textures, tex_host):
         """the device meshes (one per batch item) of these vertices and faces, with `textures` (may be None) sent if they changed.
         v_host / f_host / tex_host: callables that give the host arrays, called only when something has to go up"""
-        sv, sf = _stamp(vertices), _stamp(faces)
-        key = (sv[0], id(vertices) if sv[0] == "tensor" else sv[1], sf[0], id(faces) if sf[0] == "tensor" else sf[1], gpu)
-        entry = self._meshes.get(key)
+        sv, sf = _memo.Stamp(vertices), _memo.Stamp(faces)
+        key = (sv.part, sf.part, gpu)
+        entry = _memo.find(self._meshes, key)
         ts = 0 if textures is None else int(textures.shape[2])
-        if (entry is not None and self.geometry_grad and sv[0] == "tensor" and entry["v"][1]() is vertices and entry["v"][2] != sv[2] and
-                _same(entry["f"], faces) and (textures is None or entry["ts"] == ts)):
+        usable = entry is not None and entry["f"].still(faces) and (textures is None or entry["ts"] == ts)
+        if usable and self.geometry_grad and entry["v"].still(vertices, any_version=True) and not entry["v"].still(vertices):
             v = v_host()                                 # changed in place (optimizer.step()): the same topology, new positions
             for b, m in enumerate(entry["meshes"]):
                 m.set_vertices(v[b])
             entry["v"] = sv
-        if entry is not None and not (_same(entry["v"], vertices) and _same(entry["f"], faces) and (textures is None or entry["ts"] == ts)):
-            for m in self._meshes.pop(key)["meshes"]:
-                m.close()
+        if entry is not None and not (usable and entry["v"].still(vertices)):
+            _memo.drop(self._meshes, key, _close_meshes)
             entry = None
         if entry is None:
             v, f = v_host(), f_host()
-            while len(self._meshes) >= _MESH_SLOTS:
-                for m in self._meshes.pop(next(iter(self._meshes)))["meshes"]:
-                    m.close()
+            _memo.room(self._meshes, _MESH_SLOTS, key, _close_meshes)          # (the oldest meshes go before the new ones are made)
             entry = {"v": sv, "f": sf, "gpu": gpu, "ts": ts, "tex": None, "meshes": [native.NrMesh(r, v[b], f[b], ts) for b in range(len(v))]}
-            self._meshes[key] = entry
-        if textures is not None and not _same(entry["tex"], textures):
+            entry = _memo.store(self._meshes, _MESH_SLOTS, key, (), entry, closed=_close_meshes)
+        if textures is not None and not (entry["tex"] is not None and entry["tex"].still(textures)):
             tex = tex_host()
             for b, m in enumerate(entry["meshes"]):
                 m.set_textures(tex[b])
-            entry["tex"] = _stamp(textures)
+            entry["tex"] = _memo.Stamp(textures)
         return entry["meshes"]
 
     # ---- the one render path ----

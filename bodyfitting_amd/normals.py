@@ -5,25 +5,23 @@ torch.autograd.Function - the first line of a user's own SMPL+D loop (smplify.py
 torch tensors in -> a float32 tensor [NV,3] on the vertices' device, differentiable (once) with respect to `vertices`; numpy in ->
 numpy out.  torch is imported only when tensors arrive.
 
-The topology - the faces and the vertex -> (face, corner) lists - is uploaded once per faces object and GPU (`topology_for`): a loop
-that passes the same tensor builds it once - a hit reads nothing of the tensor back, wherever it lives - an in-place edit of the
-tensor is seen (its `_version`), arrays are told apart by a digest of their bytes.
+The topology - the faces and the vertex -> (face, corner) lists - is uploaded once per faces object and GPU (`topology_for`, a
+table of _memo.py): a loop that passes the same tensor builds it once - a hit reads nothing of the tensor back, wherever it lives -
+an in-place edit of the tensor is seen, arrays are told apart by a digest of their int32 bytes.
 
 float32 vertices on the topology's GPU go into the kernels where they lie, on torch's current stream (bf_vertex_normals_dev /
 bf_vertex_normals_vjp_dev: the device route of _autograd.py, on the topology's own workspace); everything else goes through host memory.
 """
 from __future__ import annotations
 
-import hashlib
-import weakref
-
 import numpy as np
 
 from . import _autograd
+from . import _memo
 from . import prior as _prior
 
-_TOPOLOGIES = {}            # key -> (weak reference to the faces tensor or None, its _version, native.Topology)
 _TOPOLOGY_SLOTS = 8         # meshes kept at a time; the oldest goes first
+_TOPOLOGIES = {}            # a table of _memo.py: (faces, n_verts, GPU) -> topo (native.Topology); a faces tensor is not held
 
 FUSED_PATH = ("only numpy arrays and torch tensors (and this project's MeshGridSearcher) are supported here; SMPLify's fused stage "
               "(bodyfitting_amd.smplify) is the other path")
@@ -83,31 +81,20 @@ def _faces_host(who, faces):
 
 def topology_for(who, faces, n_verts, device):
     """The `native.Topology` of `faces` for a mesh of n_verts vertices on GPU `device`, built on first use."""
-    from . import native
     require_array(who, "faces", faces)
     require_no_grad(who, "faces", faces)
-    if _is_tensor(faces):
-        key = ("tensor", id(faces), int(n_verts), int(device))
-        hit = _TOPOLOGIES.get(key)
-        if hit is not None and hit[0]() is faces and hit[1] == faces._version:
-            return hit[2]
-        entry = (weakref.ref(faces), faces._version)
+    host = None if _is_tensor(faces) else _faces_host(who, faces)
+    seen = []
+    key = (_memo.part(faces, seen, None if host is None else host.tobytes()), int(n_verts), int(device))
+    hit = _memo.find(_TOPOLOGIES, key, seen)
+    if hit is not None:
+        return hit["topo"]
+    from . import native
+    if host is None:
         host = _faces_host(who, faces)
-    else:
-        host = _faces_host(who, faces)
-        key = ("array", hashlib.sha1(host.tobytes()).hexdigest(), int(n_verts), int(device))
-        hit = _TOPOLOGIES.get(key)
-        if hit is not None:
-            return hit[2]
-        entry = (None, 0)
     if host.min() < 0 or host.max() >= n_verts:
         raise ValueError(f"{who}: a face index lies outside [0, {n_verts})")
-    topo = native.Topology(n_verts, host, device=device)
-    _TOPOLOGIES.pop(key, None)
-    while len(_TOPOLOGIES) >= _TOPOLOGY_SLOTS:
-        _TOPOLOGIES.pop(next(iter(_TOPOLOGIES)))
-    _TOPOLOGIES[key] = entry + (topo,)
-    return topo
+    return _memo.store(_TOPOLOGIES, _TOPOLOGY_SLOTS, key, seen, {"topo": native.Topology(n_verts, host, device=device)})["topo"]
 
 
 def compute_normal_torch(vertices, faces):

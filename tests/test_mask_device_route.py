@@ -65,7 +65,7 @@ def stand_ins(monkeypatch):
     monkeypatch.setattr(native, "Silhouette", OfferingSilhouette)
     monkeypatch.setattr(L, "_CAMERAS", {})
     monkeypatch.setattr(L, "CAMERA_STATS", {"stacks": 0})
-    monkeypatch.setattr(L, "_KNOWN_CONTOURS", [])
+    monkeypatch.setattr(L, "_KNOWN_CONTOURS", {})
     OfferingSilhouette.contour_reads = OfferingSilhouette.created = OfferingSilhouette.followed = 0
     return OfferingSilhouette
 
@@ -164,7 +164,7 @@ def test_the_camera_cache(stand_ins):
     L._cameras_for("t", sets[0], 3, cpu)
     assert L.CAMERA_STATS["stacks"] == 6
     # the entries hold their items: an id in a key cannot come back with another tensor
-    held = [t for e in L._CAMERAS.values() for t in e["held"]]
+    held = [s.held for e in L._CAMERAS.values() for s in e.stamps]
     assert all(any(t is x for x in held) for t in sets[0][0] + sets[0][1])
     # shapes that are not cameras: the existing text
     with pytest.raises(ValueError, match=r"w2cs must be \[M,4,4\] and Ks \[M,3,3\]"):
@@ -203,6 +203,32 @@ def test_packed_views_reach_the_device_route_in_row_major_order():
     assert not turned[0].flags["C_CONTIGUOUS"] and not turned[1].flags["C_CONTIGUOUS"]
     np.testing.assert_array_equal(turned[0], w2c)
     _row_major_on_the_route(turned)
+
+
+def test_the_view_cache_knows_its_tensors_in_reordered_keypoint_dicts(monkeypatch):
+    """the same camera and keypoint tensors in dicts filled in another order are the same views: packed once, and the entry - with
+    what was sent to a GPU - stays.  (The key sorts a dict's parts; the tensors a look-up checks must come in that order too.)"""
+    monkeypatch.setattr(L, "_VIEWS", {})
+    monkeypatch.setattr(L, "VIEW_STATS", {"packs": 0, "uploads": 0})
+    rng = np.random.default_rng(5)
+    w2cs, Ks = _camera_set(3, M=2)
+    pose = [torch.tensor(rng.normal(size=(25, 3)).astype(np.float32)) for _ in range(2)]
+    face = [torch.tensor(rng.normal(size=(68, 3)).astype(np.float32)) for _ in range(2)]
+    one_way = [{"pose": p, "face": f} for p, f in zip(pose, face)]
+    other_way = [{"face": f, "pose": p} for p, f in zip(pose, face)]
+    first = L._views_for(w2cs, Ks, one_way, 2, False, L.SKELETON_LENGTH)
+    L._views_on(first, torch.device("cpu"))
+    for k in range(6):
+        again = L._views_for(w2cs, Ks, other_way if k % 2 == 0 else one_way, 2, False, L.SKELETON_LENGTH)
+        assert again is first and L._views_on(again, torch.device("cpu")) is first["dev"][torch.device("cpu")]
+    assert L.VIEW_STATS == {"packs": 1, "uploads": 1} and len(L._VIEWS) == 1
+    # ... while another tensor in one place, or an in-place edit, is a new set
+    changed = [dict(one_way[0], face=face[0].clone()), one_way[1]]
+    assert L._views_for(w2cs, Ks, changed, 2, False, L.SKELETON_LENGTH) is not first and L.VIEW_STATS["packs"] == 2
+    pose[1].add_(1.0)
+    edited = L._views_for(w2cs, Ks, other_way, 2, False, L.SKELETON_LENGTH)
+    assert edited is not first and L.VIEW_STATS["packs"] == 3
+    np.testing.assert_array_equal(edited["host"][2][0, 1], pose[1].numpy())
 
 
 def test_contours_are_recognised_by_identity_and_version(stand_ins):
