@@ -438,15 +438,6 @@ void bf_batch_destroy(bf_batch *b) {
     if (b->graph_exec) (void)hipGraphExecDestroy(b->graph_exec);
     for (auto &e : b->ring) if (e) (void)hipEventDestroy(e);
     if (b->h_pc_weight) (void)hipHostFree(b->h_pc_weight);
-    if (b->h_masks) (void)hipHostFree(b->h_masks);
-    for (float *q : b->mk_retired) (void)hipFree(q);
-    if (b->h_ccount) (void)hipHostFree(b->h_ccount);
-    if (b->ev_masks) (void)hipEventDestroy(b->ev_masks);
-    if (b->ev_masks_used) (void)hipEventDestroy(b->ev_masks_used);
-    if (b->mk_stage.ev) (void)hipEventDestroy(b->mk_stage.ev);
-    if (b->mk_stage.ev_used) (void)hipEventDestroy(b->mk_stage.ev_used);
-    if (b->mk_stage.h_masks) (void)hipHostFree(b->mk_stage.h_masks);
-    if (b->mk_stage.h_ccount) (void)hipHostFree(b->mk_stage.h_ccount);
     for (auto &e : b->ev_dense) if (e) (void)hipEventDestroy(e);
     for (auto &g : b->graph_pipe) if (g) (void)hipGraphExecDestroy(g);
     if (b->copy_stream) (void)hipStreamDestroy(b->copy_stream);
@@ -713,7 +704,7 @@ struct FitDone { bool fetched, has_v, timed, on_lane = false; };
 
 static FitCall fit_plan(const bf_batch *b, int n_iters, uint32_t flags) {
     FitCall c;
-    const bool dense_losses = !b->scans.empty() || b->has_masks || b->m->kp_dense;
+    const bool dense_losses = !b->scans.empty() || b->masks.on || b->m->kp_dense;
     if (dense_losses) flags &= ~BF_FIT_DENSE;
     const bool dense = flags & BF_FIT_DENSE, sparse = !dense_losses && !dense;
     c.flags = flags; c.n_iters = n_iters;
@@ -978,10 +969,7 @@ int bf_fit(bf_batch *b, int n_iters, const bf_hyper *hyper, uint32_t flags) {
     if (done.on_lane) { b->fit_seq++; return BF_OK; }          // (the call's number is its place in its group)
     ResultArena &r = b->arena[b->cur];
     if (!b->in_at.on_lane) b->in_reader[b->in_at.arena] = b->fit_seq;       // (this fit's number, given to its arena below)
-    if (b->has_masks) {                       // (the arena these masks live in may be overwritten once this fit is done)
-        if (!b->ev_masks_used) HIP_TRY(hipEventCreateWithFlags(&b->ev_masks_used, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(b->ev_masks_used, b->stream));
-    }
+    BF_TRY(bf_masks_mark_used(b));            // (the arena these masks live in may be overwritten once this fit is done)
     if (b->in_at.host) { HIP_TRY(hipEventRecord(b->in[b->in_at.arena].ev, b->stream)); b->in[b->in_at.arena].pending = true; }   // (zero-copy: this fit read the pinned buffer)
     r.seq = b->fit_seq++;
     r.fetched = b->fetched;
@@ -1016,7 +1004,7 @@ int bf_dense_iter_grad(bf_batch *b, const bf_hyper *hyper, uint32_t flags, const
     if (b->scans_lost)
         return fail(BF_ERR_INVALID, "bf_dense_iter_grad: a scan this batch held was destroyed (bf_scan_destroy) - call bf_batch_set_scans again (NULL: go on without scans)");
     if (b->staged) return fail(BF_ERR_INVALID, "bf_dense_iter_grad: inputs were staged with bf_batch_stage_inputs - there are no current parameters before the next bf_fit");
-    if (late && b->scans.empty() && !b->has_masks)
+    if (late && b->scans.empty() && !b->masks.on)
         return fail(BF_ERR_INVALID, "bf_dense_iter_grad: BF_DENSE_GRAD_LATE with neither scans nor silhouettes attached");
     bf_model *m = b->m;
     HIP_TRY(hipSetDevice(m->device));

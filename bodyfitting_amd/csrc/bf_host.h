@@ -272,6 +272,60 @@ struct InputArena {
     }
 };
 
+// A mask arena: ONE set of what a border-following pass (bf_contour_kernel) reads and writes.  A batch has two (BfMasks): a fit reads
+// one while the next frame's silhouettes are staged into the other.  Whoever owns it waits for its streams before it goes.
+struct MaskArena {
+    unsigned char *h_masks = nullptr;   // pinned: the binarised masks
+    int *h_counts = nullptr;            // pinned: [2 * F * M] contour lengths | which half of the slab holds them
+    size_t h_masks_n = 0, h_counts_n = 0;
+    hipEvent_t ev = nullptr;            // the arena's upload + border following have finished
+    hipEvent_t ev_used = nullptr;       // the last fit that read the arena has finished
+    DevBuf<unsigned char> masks;
+    DevBuf<float> slab;                 // [F*M][2][cap][2] the contour kernel's two-slot slabs
+    DevBuf<int> cnt2;
+    DevBuf<unsigned> planes;            // bit planes of images too large for LDS
+    int select = 0;                     // contour_select of the masks it holds
+    MaskArena() = default;
+    MaskArena(const MaskArena &) = delete;
+    ~MaskArena() {
+        for (hipEvent_t e : {ev, ev_used}) if (e) (void)hipEventDestroy(e);
+        for (void *h : {(void *)h_masks, (void *)h_counts}) if (h) (void)hipHostFree(h);
+    }
+};
+
+// A batch's silhouettes (use_mask, smplify.py:138-144,197-199; mask_api.hip).  "The active arena" is arena[cur], "the one staged into"
+// arena[cur ^ 1].  Contours followed on the device are DEFERRED: attaching or staging queues the upload and the border following on the
+// second stream and returns; what needs their lengths is finished by bf_masks_finalize right before the first kernel that reads them -
+// in a fit the first iteration past dense_after, by which time the keypoint-only iterations in front have long covered the following.
+//  * Freeing.  Finalize and staging free no device or pinned memory: a fit may be in flight - finalize runs in the middle of one, whose
+//    resident launch waits for kernels not enqueued yet, and hipFree waits for the device.  Outgrown device blocks go onto `retired`,
+//    emptied by the next bf_batch_set_masks after its bf_sync_all, and with the batch.  What finalize fills is sized at attach.
+//  * Attach (bf_batch_set_masks) binarises into the active arena's pinned buffer BEFORE bf_sync_all, having waited for that arena's `ev`
+//    alone (in a frame loop the work in flight is the previous fit, and that upload went out early in it), and clears `staged`.
+//    n_masks <= 0 or masks NULL switches the term off, after bf_sync_all.
+//  * Staging (bf_batch_stage_masks) waits for ev_used and ev of arena[cur ^ 1] and nothing else, and sizes that arena's slab to the shared
+//    `cap` - which is how the arena that lags behind a regrow catches up.
+//  * Commit flips `cur` (pointers only: the kernels of a fit still in flight hold the old arena's by value); contours pending again.
+//  * Finalize waits on the host for arena[cur].ev; follows again, on the copy stream with a stream wait, only when a border outgrew
+//    `cap`; queues the count, offset and xy copies on the BATCH stream, in front of the kernels that read them; and reuses the second
+//    half of the pinned counts for the offsets.
+struct BfMasks {
+    bool on = false, pending = false;   // attached; a deferred border following has yet to be finalized
+    bool on_device = false;             // the attached masks' contours were followed on the device (contour_count = NULL)
+    MaskIO io{};
+    MaskArena arena[2];
+    int cur = 0;
+    bool staged = false;                // arena[cur ^ 1] holds the next fit's silhouettes
+    int cap = 0;                        // contour points a slab slot holds: shared by both arenas and the buffers sized by it below
+    std::vector<void *> retired;        // outgrown device blocks nobody could free yet
+    std::vector<int> view_host;         // the view indices the active masks were set with
+    DevBuf<int> view, cstart, ccount, choice;
+    DevBuf<float> cxy, uvi, duvb, cgrad, part, loss, gpart;
+    DevBuf<unsigned long long> acc;     // [F][M][ns][2] fixed-point contour-gradient sums (MaskIO::acc)
+    void free_retired() { for (void *q : retired) (void)hipFree(q); retired.clear(); }
+    ~BfMasks() { free_retired(); }
+};
+
 struct bf_model {
     int device = 0;
     int nv = 0, nj = 0, nb = 0, npf = 0, ns = 0, nl = 0, np = 0, n_levels = 0;
@@ -465,45 +519,7 @@ struct bf_batch {
     DevBuf<int> cface, lmk_vid;
     bool cface_valid = false;       // cface holds the faces of an earlier closest-point call for these scans (warm start)
     DevBuf<float> jraw, lmk_w;
-    // silhouette loss (use_mask, smplify.py:138-144,197-199)
-    bool has_masks = false;
-    MaskIO mask{};
-    // Contours extracted on the device are DEFERRED: bf_batch_set_masks queues the upload of the binarised masks and the border
-    // following on the second stream and returns; the bookkeeping that needs their lengths (cmax-sized buffers, offsets) is finished
-    // by bf_masks_finalize right before the first kernel that reads them - in a fit that is the first iteration past dense_after, by
-    // which time the keypoint-only iterations queued in front have long covered the extraction.
-    bool masks_pending = false;
-    unsigned char *h_masks = nullptr;   // pinned staging of the binarised masks
-    size_t h_masks_n = 0, h_ccount_n = 0;
-    int *h_ccount = nullptr;            // pinned: [2 * F * M] contour lengths | which half of the slab holds them
-    hipEvent_t ev_masks = nullptr;
-    DevBuf<float> mk_slab;              // [F*M][2][cap][2] the contour kernel's two-slot slabs
-    DevBuf<int> mk_cnt2;
-    DevBuf<unsigned> mk_planes;         // bit planes of images too large for LDS
-    int mk_cap = 0, mk_select = 0;
-    bool mk_on_device = false;          // the attached masks' contours were followed on the device (contour_count = NULL)
-    std::vector<float *> mk_retired;    // outgrown buffers a finalize inside a fit could not free
-    // bf_batch_stage_masks: the NEXT frame's silhouettes in an arena of their own (pinned staging, device masks, the contour kernel's
-    // slab and counts), filled on the second stream under the fit in flight; the next bf_fit swaps the two arenas' pointers.
-    struct MaskStage {
-        unsigned char *h_masks = nullptr;
-        size_t h_masks_n = 0, h_ccount_n = 0;
-        int *h_ccount = nullptr;
-        hipEvent_t ev = nullptr;        // the arena's upload + border following have finished
-        hipEvent_t ev_used = nullptr;   // the last fit that read the arena has finished
-        DevBuf<unsigned char> masks;
-        DevBuf<float> slab;
-        DevBuf<int> cnt2;
-        DevBuf<unsigned> planes;
-        int select = 0;
-        bool staged = false;
-    } mk_stage;
-    hipEvent_t ev_masks_used = nullptr; // (the active arena's ev_used)
-    std::vector<int> mk_view_host;      // the view indices the active masks were set with
-    DevBuf<int> mk_view, mk_cstart, mk_ccount, mk_choice;
-    DevBuf<unsigned char> mk_masks;
-    DevBuf<float> mk_cxy, mk_uvi, mk_duvb, mk_cgrad, mk_part, mk_loss, mk_gpart;
-    DevBuf<unsigned long long> mk_acc;       // [F][M][ns][2] fixed-point contour-gradient sums (MaskIO::acc)
+    BfMasks masks;
     // SMPL+D stage (smplify.py:228-247)
     DevBuf<float> disp, disp_m, disp_v, disp_base, disp_P, disp_fn, disp_vn, disp_dv, disp_dPf;
     DevBuf<const float *> scan_fn;
@@ -576,8 +592,10 @@ int bf_ensure_posedirsT_locked(bf_model *m, hipStream_t stream);   // (caller ho
 // contours of n binary masks on the device (mask_api.hip): shared by bf_extract_contours and bf_silhouette_create
 int bf_contours_on_device(const unsigned char *d_bin, int n, int H, int W, int select, std::vector<int> &counts, std::vector<int> &half,
                           DevBuf<float> &d_xy, int &cap);
-int bf_masks_finalize(bf_batch *b);      // no-op unless a deferred bf_batch_set_masks is pending
-void bf_masks_commit(bf_batch *b);       // no-op unless bf_batch_stage_masks has staged the next frame's silhouettes
+// what a fit does with the batch's silhouettes, in this order (the rules: BfMasks)
+void bf_masks_commit(bf_batch *b);       // no-op unless bf_batch_stage_masks has staged the next frame's silhouettes: they become the active ones
+int bf_masks_finalize(bf_batch *b);      // no-op unless a deferred border following is pending: before the first kernel that reads the contours
+int bf_masks_mark_used(bf_batch *b);     // no-op without masks: the fit just queued on the batch stream is the last reader of the active arena
 HyperDev bf_to_dev(const bf_hyper &h);
 // the frame loop's pieces that api.hip defines and the fit lanes (lanes.hip) use as well
 FrameIO bf_frame_io(bf_batch *b, bool want_grads);      // the batch's own launch arguments

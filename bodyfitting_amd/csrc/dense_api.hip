@@ -83,32 +83,32 @@ int launch_mask_kernels(bf_batch *b, float weight, bool want_loss, bool sum_view
                         const bf_model::Sub *sub, bool fold_acc) {
     // fold_acc: the contour scan adds its gradients into the fixed-point sums (MaskIO::acc) and the reverse mesh pass takes them from
     // there (MaskFold): no gather launch
-    MaskIO K = b->mask;
+    MaskIO K = b->masks.io;
     K.weight = weight;
-    K.acc = fold_acc ? b->mk_acc.p : nullptr;
+    K.acc = fold_acc ? b->masks.acc.p : nullptr;
     if (sub) { K.nv = sub->mesh.nv; K.sstride = 1; }
     const int F = b->F;
     // (projected: the forward mesh pass already wrote uvi / duvb for its sampled vertices)
     if (!projected) hipLaunchKernelGGL(bf_mask_project_kernel, dim3(K.proj_blocks, K.n_masks, F), dim3(256), 0, b->stream, K, (const float *)b->vout.p,
-                       (const float *)b->proj.p, b->mk_uvi.p, b->mk_duvb.p, b->mk_part.p);
+                       (const float *)b->proj.p, b->masks.uvi.p, b->masks.duvb.p, b->masks.part.p);
     if (with_kp) {
         const KpIO Q = kp_io(b, *with_kp, sub);
         hipLaunchKernelGGL(bf_kp_contour_kernel, dim3((K.cmax * 16 + 511) / 512 + 1, K.n_masks, F), dim3(512), kp_smem(Q), b->stream, Q,
                            (const float *)b->jraw.p, (const float *)b->state.p, (const float *)b->proj.p, (const float *)b->keypoints.p,
                            (const int *)b->ndiv.p, (const int *)b->lmk_vid.p, (const float *)b->lmk_w.p, b->ext.p, b->dvout.p, b->terms.p,
-                           K, (const float *)b->mk_uvi.p, b->mk_choice.p, b->mk_cgrad.p, b->mk_part.p, sub ? sub->mesh : b->m->mesh, (const float *)b->vraw.p,
+                           K, (const float *)b->masks.uvi.p, b->masks.choice.p, b->masks.cgrad.p, b->masks.part.p, sub ? sub->mesh : b->m->mesh, (const float *)b->vraw.p,
                            (const float *)b->xpart.p);
     } else
     hipLaunchKernelGGL(bf_mask_contour_kernel, dim3((K.cmax * 16 + 255) / 256, K.n_masks, F), dim3(256), 0, b->stream, K,
-                       (const float *)b->mk_uvi.p, b->mk_choice.p, b->mk_cgrad.p, b->mk_part.p);
+                       (const float *)b->masks.uvi.p, b->masks.choice.p, b->masks.cgrad.p, b->masks.part.p);
     if (!fold_acc)
     hipLaunchKernelGGL(bf_mask_gather_kernel, dim3((K.ns + 63) / 64, K.n_masks, F), dim3(256), 0, b->stream, K, (const float *)b->proj.p,
-                       (const float *)b->mk_uvi.p, (const float *)b->mk_duvb.p, (const int *)b->mk_choice.p,
-                       (const float *)b->mk_cgrad.p, b->mk_gpart.p);
+                       (const float *)b->masks.uvi.p, (const float *)b->masks.duvb.p, (const int *)b->masks.choice.p,
+                       (const float *)b->masks.cgrad.p, b->masks.gpart.p);
     // (sum_views = false: the reverse mesh pass adds the views itself while it loads dL/dvertices)
-    if (sum_views) hipLaunchKernelGGL(bf_mask_gsum_kernel, dim3(K.proj_blocks, F), dim3(256), 0, b->stream, K, (const float *)b->mk_gpart.p, b->dvout.p);
+    if (sum_views) hipLaunchKernelGGL(bf_mask_gsum_kernel, dim3(K.proj_blocks, F), dim3(256), 0, b->stream, K, (const float *)b->masks.gpart.p, b->dvout.p);
     // (the loss VALUE is a serial sum over the partial blocks: only when somebody reads it - the fit loop needs the gradient)
-    if (want_loss) hipLaunchKernelGGL(bf_mask_loss_kernel, dim3(F), dim3(64), 0, b->stream, K, (const float *)b->mk_part.p, b->mk_loss.p);
+    if (want_loss) hipLaunchKernelGGL(bf_mask_loss_kernel, dim3(F), dim3(64), 0, b->stream, K, (const float *)b->masks.part.p, b->masks.loss.p);
     HIP_TRY(hipGetLastError());
     return BF_OK;
 }
@@ -168,7 +168,7 @@ static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, const 
     HIP_TRY(mark(0));
     const MeshTab &Q = o.sub ? o.sub->mesh : m->mesh;
     const int F = b->F, nv = Q.nv, nblk = (nv + 255) / 256;
-    const bool scans = o.late && !b->scans.empty(), masks = o.late && b->has_masks, kp = m->kp_dense;
+    const bool scans = o.late && !b->scans.empty(), masks = o.late && b->masks.on, kp = m->kp_dense;
     const bool acc_mode = fold_acc_on();          // (read once per pass)
     if (masks) BF_TRY(bf_masks_finalize(b));
     if (!o.door) {                     // (with the resident fit launch every state comes from it)
@@ -179,8 +179,8 @@ static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, const 
     }
     MaskProj mp;
     if (masks) {
-        mp.on = 1; mp.K = b->mask; mp.K.weight = o.mask_weight; mp.proj = b->proj.p; mp.uvi = b->mk_uvi.p; mp.duvb = b->mk_duvb.p;
-        mp.K.acc = (acc_mode && !scans) ? b->mk_acc.p : nullptr;      // (zeroed by the projection that precedes the contour scan)
+        mp.on = 1; mp.K = b->masks.io; mp.K.weight = o.mask_weight; mp.proj = b->proj.p; mp.uvi = b->masks.uvi.p; mp.duvb = b->masks.duvb.p;
+        mp.K.acc = (acc_mode && !scans) ? b->masks.acc.p : nullptr;      // (zeroed by the projection that precedes the contour scan)
         if (o.sub) { mp.K.nv = nv; mp.K.sstride = 1; }
     }
     const bool kp_aside = kp && !masks && scans && b->copy_stream;       // (see below)
@@ -254,9 +254,9 @@ static int dense_pass(bf_batch *b, const bf_hyper &h, const HyperDev &hd, const 
     int part_rows = Q.n_tiles;             // (two per tile when the reverse pass splits its tiles: one frame, a small grid)
     {
         MaskFold fold = {};
-        if (fold_acc) { fold.acc = b->mk_acc.p; fold.uvi = b->mk_uvi.p; fold.duvb = b->mk_duvb.p; fold.proj = b->proj.p; fold.view_index = b->mask.view_index; fold.n_views = b->V; }
+        if (fold_acc) { fold.acc = b->masks.acc.p; fold.uvi = b->masks.uvi.p; fold.duvb = b->masks.duvb.p; fold.proj = b->proj.p; fold.view_index = b->masks.io.view_index; fold.n_views = b->V; }
         const int e = bf_mesh_bwd_multi_launch(&Q, o.sub ? o.sub->posedirsT.p : m->posedirsT.p, b->state.p, F, b->dvout.p, b->vposed.p, b->vraw.p, b->ext_part.p,
-                                               b->stream, (fold_views && !fold_acc) ? (const float *)b->mk_gpart.p : nullptr, b->mask.n_masks, b->mask.ns, o.sub ? 1 : 4,
+                                               b->stream, (fold_views && !fold_acc) ? (const float *)b->masks.gpart.p : nullptr, b->masks.io.n_masks, b->masks.io.ns, o.sub ? 1 : 4,
                                                (o.sub && o.sub == &m->sub_kp) ? Q.n_tiles : m->mesh.n_tiles, &part_rows, fold_acc ? &fold : nullptr);      // (keypoint-only sub-model: no tile split - a batch of 8 and its single frames keep the same partial sums)
         if (e) return fail(BF_ERR_HIP, std::string("bf_mesh_bwd_multi_kernel: ") + hipGetErrorString((hipError_t)e));
     }
@@ -369,7 +369,7 @@ static int dense_prepare(bf_batch *b, const bf_hyper &h) {
         for (int f = 0; f < F; ++f) b->h_pc_weight[f] = 5.0f * h.imsize / b->scans[f]->dev.height;
         HIP_TRY(hipMemcpyAsync(b->pc_weight.p, b->h_pc_weight, (size_t)F * sizeof(float), hipMemcpyHostToDevice, b->stream));
     }
-    if (b->has_masks) { b->mask.imsize = h.imsize; b->mask.cdist = h.mask_cdist_form != 0.f; }
+    if (b->masks.on) { b->masks.io.imsize = h.imsize; b->masks.io.cdist = h.mask_cdist_form != 0.f; }
     return bf_ensure_dense_buffers(b);
 }
 
@@ -387,7 +387,7 @@ static void dense_subs(bf_batch *b, const bf_model::Sub *&sub_early, const bf_mo
     // the chaotic end state moved from 1.9 % to 3.9 % of the reference's, outside a band that was 3 x the larger of TWO perturbed
     // reference runs; round 6 measures the reference under ten perturbations (tests/ref_drift.py).
     const bool sub_kp_masks = [] { const char *e = std::getenv("BF_DENSE_SUBMODEL_KP_MASKS"); return !(e && e[0] == '0'); }();
-    sub_early = (sub_ok && sub_kp_ok && m->sub_kp.on && (!b->has_masks || sub_kp_masks)) ? &m->sub_kp : sub_late;
+    sub_early = (sub_ok && sub_kp_ok && m->sub_kp.on && (!b->masks.on || sub_kp_masks)) ? &m->sub_kp : sub_late;
 }
 
 // a call that fails while the fit launch is resident: let everybody through (BF_DOOR_ERR) and wait for the launch, so that it is not
@@ -503,7 +503,7 @@ int bf_dense_iter_eval(bf_batch *b, const bf_hyper &h, const HyperDev &hd, Frame
     const int F = b->F;
     int rc = dense_prepare(b, h);
     if (rc) return rc;
-    const bool scans = late && !b->scans.empty(), masks = late && b->has_masks;
+    const bool scans = late && !b->scans.empty(), masks = late && b->masks.on;
     const bf_model::Sub *sub = nullptr;
     if (use_sub) {
         const bf_model::Sub *sub_early = nullptr, *sub_late = nullptr;
@@ -534,7 +534,7 @@ int bf_dense_iter_eval(bf_batch *b, const bf_hyper &h, const HyperDev &hd, Frame
     if (terms6) {
         std::vector<float> t4((size_t)F * 4), mk(F, 0.f), pc(F, 0.f);
         HIP_TRY(hipMemcpy(t4.data(), b->terms.p, t4.size() * sizeof(float), hipMemcpyDeviceToHost));
-        if (masks) HIP_TRY(hipMemcpy(mk.data(), b->mk_loss.p, (size_t)F * sizeof(float), hipMemcpyDeviceToHost));
+        if (masks) HIP_TRY(hipMemcpy(mk.data(), b->masks.loss.p, (size_t)F * sizeof(float), hipMemcpyDeviceToHost));
         if (scans) HIP_TRY(hipMemcpy(pc.data(), b->pc_loss.p, (size_t)F * sizeof(float), hipMemcpyDeviceToHost));
         for (int f = 0; f < F; ++f) {
             std::copy(t4.begin() + (size_t)f * 4, t4.begin() + (size_t)f * 4 + 4, terms6 + (size_t)f * 6);

@@ -415,3 +415,98 @@ def test_stage_masks_refuses_what_it_cannot_take(dev_model, smpl_model):
     b.fit(6, N.make_hyper(dense_after=3))
     assert np.isfinite(b.get_params()).all()
     b.close()
+
+
+TWO_VIEWS = MASK_FRAMES[:2]
+
+
+def _attached(dev_model, prob, masks, contours=None):
+    """a one-frame, 8-view batch on `prob` with `masks` [1, 2, H, W] attached -> the batch, its view indices and its inputs"""
+    c2w, K, kp, ndiv, betas, pose = N.pack_problem([prob])
+    view_index = [prob["use_frames"].index(f) for f in TWO_VIEWS]
+    b = N.FrameBatch(dev_model, 1, c2w.shape[1])
+    b.set_cameras(c2w, K); b.set_keypoints(kp, ndiv); b.set_init(betas, pose)
+    b.set_masks(masks, view_index, contours)
+    return b, view_index, (kp, ndiv, betas, pose)
+
+
+def _fresh_fit(b, inputs, n_iters=6):
+    from bodyfitting_amd import _lib
+    b.stage_inputs(*inputs)
+    b.fit(n_iters, N.make_hyper(dense_after=3), _lib.FIT_RESET | _lib.FIT_FETCH)
+    return b.get_params().copy()
+
+
+def test_global_planes_inside_a_batch(dev_model, smpl_model):
+    """400 x 1056 masks: their bit planes take 3 * 400 * 33 * 4 = 158,400 bytes, past the 153,600 the contour kernel keeps in LDS, so
+    the batch's own border following (attach and staging) runs on planes in global memory.  Loss and gradient equal, bit for bit,
+    those with the contours of bf_extract_contours handed in; a second set staged under way gives the fit the bits it has with
+    that set attached by bf_batch_set_masks."""
+    from bodyfitting_amd.contours import extract_contours as device_contours
+    shape = (400, 1056)
+    first, second = ((np.stack([_blobs(s, shape) for s in seeds])[None] * 255).astype(np.uint8) for seeds in ((0, 1), (2, 3)))
+    prob = S.make_problem(smpl_model, frame=0, n_views=8)
+    out = []
+    for contours in (None, [device_contours(first[0] > 128)]):
+        b, _, _ = _attached(dev_model, prob, first, contours)
+        out.append(b.mask_loss())
+        b.close()
+    np.testing.assert_array_equal(out[0][0], out[1][0])
+    np.testing.assert_array_equal(out[0][1], out[1][1])
+    assert np.isfinite(out[0][0]).all() and out[0][0][0] > 0
+    fits = []
+    for staged in (True, False):
+        b, view_index, inputs = _attached(dev_model, prob, first)
+        if staged:
+            b.stage_masks(second, view_index)
+        else:
+            b.set_masks(second, view_index, None)
+        fits.append(_fresh_fit(b, inputs))
+        b.close()
+    np.testing.assert_array_equal(fits[0], fits[1])
+    b, _, inputs = _attached(dev_model, prob, first)
+    assert not np.array_equal(_fresh_fit(b, inputs), fits[0])             # (the second set is what that fit saw)
+    b.close()
+
+
+def test_two_stagings_before_one_fit(dev_model, smpl_model):
+    """stage A, stage B, fit: the second staging overwrites the arena that is not the active one, and the fit sees B - the bits of the
+    run that attaches B with bf_batch_set_masks"""
+    probs = [S.make_problem(smpl_model, frame=f, n_views=8, mask_frames=TWO_VIEWS) for f in (0, 1, 2)]
+    m0, mA, mB = (np.array(p["masks"])[None] for p in probs)
+    fits = []
+    for staged in (True, False):
+        b, view_index, inputs = _attached(dev_model, probs[0], m0)
+        if staged:
+            b.stage_masks(mA, view_index)
+            b.stage_masks(mB, view_index)
+        else:
+            b.set_masks(mB, view_index, None)
+        fits.append(_fresh_fit(b, inputs))
+        b.close()
+    np.testing.assert_array_equal(fits[0], fits[1])
+    b, view_index, inputs = _attached(dev_model, probs[0], m0)
+    b.stage_masks(mA, view_index)
+    assert not np.array_equal(_fresh_fit(b, inputs), fits[0])             # (A alone gives another fit: B really replaced it)
+    b.close()
+
+
+def test_destroy_with_a_staged_arena_and_retired_blocks(dev_model, smpl_model):
+    """the comb's border outgrows the slab inside the fit (outgrown blocks retired, not freed), then another set is staged and never
+    fitted: closing the batch returns, and a fresh batch on the same model repeats the first one's bits"""
+    prob = S.make_problem(smpl_model, frame=0, n_views=8, mask_frames=TWO_VIEWS)
+    plain = np.array(prob["masks"])[None]
+    masks = plain.copy()
+    H, W = masks.shape[-2:]
+    masks[0, 1] = 0
+    masks[0, 1, H // 8: 7 * H // 8, W // 8: 7 * W // 8: 2] = 255          # the comb of the tests above
+    masks[0, 1, 7 * H // 8 - 2: 7 * H // 8, W // 8: 7 * W // 8] = 255
+    fits = []
+    for leave_staged in (True, False):
+        b, view_index, inputs = _attached(dev_model, prob, masks)
+        fits.append(_fresh_fit(b, inputs, 9))                   # (the border is read from iteration 5 on)
+        if leave_staged:
+            b.stage_masks(plain, view_index)
+        b.close()
+    np.testing.assert_array_equal(fits[0], fits[1])
+    assert np.isfinite(fits[0]).all()
