@@ -77,6 +77,13 @@ _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int32)
 _DP = C.POINTER(C.c_double)
 _VP = C.c_void_p
+
+
+class NrCameraDev(C.Structure):
+    """bf_nr_camera_dev: K, R, t as device addresses (NULL: that one comes by value)"""
+    _fields_ = [("K", _VP), ("R", _VP), ("t", _VP)]
+
+
 SIGNATURES = {
     "bf_last_error": (C.c_char_p, []),
     "bf_version": (C.c_char_p, []),
@@ -234,6 +241,12 @@ SIGNATURES = {
     "bf_nr_mesh_set_vertices": (C.c_int, [_VP, _FP]),
     "bf_nr_render_taped": (C.c_int, [_VP, _VP, _FP, _FP, _FP, C.c_float, C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.c_int, C.POINTER(_VP)]),
     "bf_nr_tape_vertex_grad": (C.c_int, [_VP, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "bf_nr_render_dev": (C.c_int, [_VP, _VP, _FP, _FP, _FP, C.c_float, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, C.POINTER(_VP), _VP, _VP,
+                                   C.POINTER(NrCameraDev), _VP, C.c_size_t, _VP, _VP]),
+    "bf_nr_tape_texture_grad_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "bf_nr_tape_vertex_grad_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "bf_nr_tape_layout": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_uint64)]),
+    "bf_nr_route_stats": (C.c_int, [C.POINTER(C.c_int64)]),
     "bf_hmr_n_weights": (C.c_int64, []),
     "bf_hmr_create": (C.c_int, [C.c_int, _FP, C.c_int64, _FP, C.c_int, C.POINTER(_VP)]),
     "bf_hmr_destroy": (None, [_VP]),

@@ -159,7 +159,7 @@ hipError_t bf_grow(hipStream_t s, DevBuf<T> &b, size_t count) {
 }
 
 // bf_dev_route_stats: calls of the host entry points a torch loop goes through (bf_smpl_forward, bf_smpl_vjp, bf_smplx_forward[_expr],
-// bf_smplx_vjp[_expr], bf_keypoint_loss, the SMPL+D stage's losses of mesh_loss_api.hip, bf_scan_nearest, bf_silhouette_loss), calls of their *_dev twins, device (re)allocations of workspaces, and calls that had to wait
+// bf_smplx_vjp[_expr], bf_keypoint_loss, the SMPL+D stage's losses of mesh_loss_api.hip, bf_scan_nearest, bf_silhouette_loss, the renderer's bf_nr_render[_taped] and bf_nr_tape_*_grad), calls of their *_dev twins, device (re)allocations of workspaces, and calls that had to wait
 // for their workspace's previous call on another stream.  Process-wide; counted once the arguments have passed.
 struct BfRouteStats { std::atomic<long long> host{0}, dev{0}, allocs{0}, switches{0}; };
 inline BfRouteStats &bf_route_stats() { static BfRouteStats S; return S; }

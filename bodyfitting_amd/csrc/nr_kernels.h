@@ -29,5 +29,7 @@ extern "C" __global__ void bf_nr_unlit_kernel(int is, int nf, const float *pix, 
 extern "C" __global__ void bf_nr_geometry_kernel(NrGeo G, NrLight L, float *grad_frec, float *grad_lrec);
 extern "C" __global__ void bf_nr_fold_kernel(int nv, int nrec, const int *vstart, const int *ventry, const float *grad_frec, const float *grad_lrec,
                                              const float *verts, TexView V, float *grad_verts, float *partial);
-extern "C" __global__ void bf_nr_fold_sum_kernel(int blocks, const float *partial, float *out);
+extern "C" __global__ void bf_nr_fold_view_kernel(int nv, int nrec, const int *vstart, const int *ventry, const float *grad_frec, const float *grad_lrec,
+                                                  const float *verts, const TexView *V, float *grad_verts, float *partial);
+extern "C" __global__ void bf_nr_fold_sum_kernel(int blocks, const float *partial, float *out_R, float *out_t);
 #pragma GCC visibility pop

@@ -200,7 +200,8 @@ bf_nr_backward_large_kernel(int nf, int is, int out, int aa, const float *__rest
 //                           gathered over the record's pixel box; every row of grad_frec / grad_lrec written once, fixed order
 //   bf_nr_fold_kernel       one thread per vertex: its incident (record, corner) rows in table order, then the projection's reverse;
 //                           per block a fixed-order tree of dp and dp (x) v
-//   bf_nr_fold_sum_kernel   the blocks' partial sums in block order -> grad_R[9] | grad_t[3]
+//   bf_nr_fold_view_kernel  the same body with the view read from device memory
+//   bf_nr_fold_sum_kernel   the blocks' partial sums in block order -> grad_R[9], grad_t[3]
 extern "C" __global__ void __launch_bounds__(256)
 bf_nr_unlit_kernel(int is, int nf, const float *__restrict__ pix, const float *__restrict__ frec, const float *__restrict__ textures, int ts,
                    float *__restrict__ unlit) {
@@ -404,11 +405,10 @@ bf_nr_geometry_kernel(NrGeo G, NrLight L, float *__restrict__ grad_frec, float *
 
 // thread = vertex i.  vstart[nv + 1], ventry[]: its (record * 3 + corner) rows, ascending; rows of records >= nrec are not drawn.
 // V.orig < 0 (ndc): grad_verts is the sum itself.  partial[blocks][12]: the block's sums of dp (x) v [9] | dp [3], NULL with ndc.
-extern "C" __global__ void __launch_bounds__(256)
-bf_nr_fold_kernel(int nv, int nrec, const int *__restrict__ vstart, const int *__restrict__ ventry, const float *__restrict__ grad_frec,
-                  const float *__restrict__ grad_lrec, const float *__restrict__ verts, TexView V, float *__restrict__ grad_verts,
-                  float *__restrict__ partial) {
-    __shared__ float s_r[12][256];
+// (the one body of bf_nr_fold_kernel and bf_nr_fold_view_kernel: V by value or through a pointer; s_r: the block's [12][256] floats)
+__device__ __forceinline__ void nr_fold(int nv, int nrec, const int *__restrict__ vstart, const int *__restrict__ ventry, const float *__restrict__ grad_frec,
+                                        const float *__restrict__ grad_lrec, const float *__restrict__ verts, const TexView &V,
+                                        float *__restrict__ grad_verts, float *__restrict__ partial, float (*s_r)[256]) {
     const int i = blockIdx.x * 256 + threadIdx.x, tid = threadIdx.x;
     float gn[3] = {0.f, 0.f, 0.f}, gw[3] = {0.f, 0.f, 0.f}, red[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (i < nv) {
@@ -461,12 +461,31 @@ bf_nr_fold_kernel(int nv, int nrec, const int *__restrict__ vstart, const int *_
     if (tid < 12) partial[(size_t)blockIdx.x * 12 + tid] = s_r[tid][0];
 }
 
-// one block of 64: lane q < 12 adds the blocks' partial sums in block order -> out[12] = grad_R[9] | grad_t[3]
+extern "C" __global__ void __launch_bounds__(256)
+bf_nr_fold_kernel(int nv, int nrec, const int *__restrict__ vstart, const int *__restrict__ ventry, const float *__restrict__ grad_frec,
+                  const float *__restrict__ grad_lrec, const float *__restrict__ verts, TexView V, float *__restrict__ grad_verts,
+                  float *__restrict__ partial) {
+    __shared__ float s_r[12][256];
+    nr_fold(nv, nrec, vstart, ventry, grad_frec, grad_lrec, verts, V, grad_verts, partial, s_r);
+}
+
+// ... with the view where bf_tex_view_pack_kernel wrote it (4-byte aligned)
+extern "C" __global__ void __launch_bounds__(256)
+bf_nr_fold_view_kernel(int nv, int nrec, const int *__restrict__ vstart, const int *__restrict__ ventry, const float *__restrict__ grad_frec,
+                       const float *__restrict__ grad_lrec, const float *__restrict__ verts, const TexView *__restrict__ V,
+                       float *__restrict__ grad_verts, float *__restrict__ partial) {
+    __shared__ float s_r[12][256];
+    nr_fold(nv, nrec, vstart, ventry, grad_frec, grad_lrec, verts, *V, grad_verts, partial, s_r);
+}
+
+// one block of 64: lane q < 12 adds the blocks' partial sums in block order -> out_R[9] = grad_R, out_t[3] = grad_t (each may be NULL)
 extern "C" __global__ void __launch_bounds__(64)
-bf_nr_fold_sum_kernel(int blocks, const float *__restrict__ partial, float *__restrict__ out) {
+bf_nr_fold_sum_kernel(int blocks, const float *__restrict__ partial, float *__restrict__ out_R, float *__restrict__ out_t) {
     const int q = threadIdx.x;
     if (q >= 12) return;
+    float *dst = q < 9 ? (out_R ? out_R + q : nullptr) : (out_t ? out_t + (q - 9) : nullptr);
+    if (!dst) return;
     float s = 0.f;
     for (int b = 0; b < blocks; ++b) s += partial[(size_t)b * 12 + q];
-    out[q] = s;
+    *dst = s;
 }

@@ -7,6 +7,10 @@ struct TexImage { const unsigned char *p; int h, w; };
 
 #pragma GCC visibility push(hidden)       // (a kernel's host-side handle does not follow -fvisibility: see the Makefile)
 extern "C" __global__ void bf_tex_project_kernel(int nv, const float *verts, TexView V, float *pv);
+// the camera of a render in device memory: each of K, R, t from a device pointer (d_*, not NULL) or from `host`'s values; orig from host
+extern "C" __global__ void bf_tex_view_pack_kernel(const float *d_K, const float *d_R, const float *d_t, TexView host, TexView *out);
+// bf_tex_project_kernel with the view read through a pointer (4-byte aligned): the same arithmetic, the same bits
+extern "C" __global__ void bf_tex_project_view_kernel(int nv, const float *verts, const TexView *V, float *pv);
 extern "C" __global__ void bf_tex_face_kernel(int nf, const int *faces, const float *pv, int is, int tiles, float *frec, int *tile_count, int *cursor,
                                               int *tile_list, int pass, int cap);
 extern "C" __global__ void bf_tex_raster_kernel(int is, int tiles, const float *frec, const int *tile_start, const int *tile_list, const float *textures, int ts,

@@ -3,6 +3,7 @@
 // flips on a contracted fma moves a pixel from one face to another).
 //
 //   bf_tex_project_kernel   neural_renderer/projection.py:6-42, zero distortion: world -> (u, v in [-1,1], z)
+//   bf_tex_view_pack_kernel / bf_tex_project_view_kernel   the camera packed into device memory, and the projection reading it there
 //   bf_tex_face_kernel      forward_face_index_map_cuda_kernel_1 (cuda/rasterize_cuda_kernel.cu:24-68): per face the nine projected
 //                           coordinates, the back-face test, the inverted pixel-space triangle; + the 8x8-pixel tiles its bounding
 //                           box touches (count pass / fill pass of the tile lists)
@@ -28,6 +29,25 @@ bf_tex_project_kernel(int nv, const float *__restrict__ verts, TexView V, float 
     if (i >= nv) return;
     const float a = verts[i * 3], b = verts[i * 3 + 1], c = verts[i * 3 + 2];
     tex_project(V, a, b, c, pv + i * 3);
+}
+
+// the view in device memory (bf_nr_render_dev): 22 floats, thread = float.  Plain loads and stores; one block of 64.
+extern "C" __global__ void __launch_bounds__(64)
+bf_tex_view_pack_kernel(const float *__restrict__ d_K, const float *__restrict__ d_R, const float *__restrict__ d_t, TexView host, TexView *__restrict__ out) {
+    const int i = threadIdx.x;
+    float *o = (float *)out;
+    if (i < 9) o[i] = d_R ? d_R[i] : host.R[i];
+    else if (i < 12) o[i] = d_t ? d_t[i - 9] : host.t[i - 9];
+    else if (i < 21) o[i] = d_K ? d_K[i - 12] : host.K[i - 12];
+    else if (i == 21) o[i] = host.orig;
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+bf_tex_project_view_kernel(int nv, const float *__restrict__ verts, const TexView *__restrict__ V, float *__restrict__ pv) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nv) return;
+    const float a = verts[i * 3], b = verts[i * 3 + 1], c = verts[i * 3 + 2];
+    tex_project(*V, a, b, c, pv + i * 3);
 }
 
 // pass 0: the record + count the tiles of the box; pass 1: write the face into their lists (tex_bodies.h: tex_face_record)

@@ -754,6 +754,26 @@ class Silhouette:
 
 
 TAPE_TEXTURES, TAPE_GEOMETRY = 1, 2          # BF_NR_TAPE_*
+# the device route of the renderer (csrc/nr_api.hip)
+NR_DEV_SYMBOLS = ("bf_nr_render_dev", "bf_nr_tape_texture_grad_dev", "bf_nr_tape_vertex_grad_dev", "bf_nr_tape_layout", "bf_nr_route_stats")
+NR_TAPE_SEGMENTS = ("view", "pix", "frec", "light", "verts", "pv", "rgbmap", "unlit")
+
+
+def nr_tape_layout(supersize, nrec, nv, lit, flags, has_rgb, directional):
+    """bf_nr_tape_layout -> dict(offsets, sizes: per NR_TAPE_SEGMENTS name, in floats; total): the float32 storage a tape of
+    NrRenderer.render_dev borrows.  flags 0: a render without a tape"""
+    out = (C.c_uint64 * 17)()
+    _lib.check(_lib.load().bf_nr_tape_layout(int(supersize), int(nrec), int(nv), int(bool(lit)), int(flags), int(bool(has_rgb)),
+                                             int(bool(directional)), out), "bf_nr_tape_layout")
+    v = [int(x) for x in out]
+    return dict(offsets=dict(zip(NR_TAPE_SEGMENTS, v[:8])), sizes=dict(zip(NR_TAPE_SEGMENTS, v[8:16])), total=v[16])
+
+
+def nr_route_stats():
+    """bf_nr_route_stats -> dict(renders, growths, bytes_back): device-route renders, tile lists they grew, bytes they read back"""
+    out = (C.c_int64 * 3)()
+    _lib.check(_lib.load().bf_nr_route_stats(out), "bf_nr_route_stats")
+    return dict(zip(("renders", "growths", "bytes_back"), (int(v) for v in out)))
 
 
 class NrRenderer:
@@ -762,6 +782,7 @@ class NrRenderer:
     def __init__(self, image_size, anti_aliasing=True, near=0.1, far=100.0, background=(0.0, 0.0, 0.0), device=0):
         self._lib = _lib.load()
         self.image_size, self.device = int(image_size), int(device)
+        self.supersize, self.directional = self.image_size * (2 if anti_aliasing else 1), 0.5
         self._h = C.c_void_p()
         _lib.check(self._lib.bf_nr_create(self.device, self.image_size, int(bool(anti_aliasing)), float(near), float(far),
                                           _lib.fptr(_f32(background, (3,))), C.byref(self._h)), "bf_nr_create")
@@ -769,6 +790,43 @@ class NrRenderer:
     def set_light(self, ambient, directional, color_ambient, color_directional, direction):
         _lib.check(self._lib.bf_nr_set_light(self._h, float(ambient), float(directional), _lib.fptr(_f32(color_ambient, (3,))),
                                              _lib.fptr(_f32(color_directional, (3,))), _lib.fptr(_f32(direction, (3,)))), "bf_nr_set_light")
+        self.directional = float(np.float32(directional))
+
+    @classmethod
+    def offers_dev(cls, lib=None):
+        """does the library export the device route's entry points?  One without them: every render takes the host route"""
+        lib = lib or _lib.load()
+        return all(hasattr(lib, name) for name in NR_DEV_SYMBOLS)
+
+    def workspace(self):
+        return _own_workspace(self)
+
+    def tape_floats(self, mesh, fill_back, lit, flags, has_rgb):
+        """how many floats the storage of a tape of this render holds (flags 0: no tape, no storage: 0)"""
+        if not flags:
+            return 0
+        nrec = (2 if fill_back else 1) * mesh.textures_shape[0]
+        return nr_tape_layout(self.supersize, nrec, mesh.n_verts, lit, flags, has_rgb, self.directional != 0.0)["total"]
+
+    def render_dev(self, mesh, stream, verts, textures=0, K=None, R=None, t=None, orig_size=1.0, fill_back=True, lightoff=False, ndc=False,
+                   rgb=0, depth=0, alpha=0, flags=0, storage=0, storage_floats=0):
+        """bf_nr_render_dev: verts / textures / rgb / depth / alpha / storage are device addresses (0: none); each of K, R, t is an
+        array (taken by value) or a device address (an int: read where it lies).  flags 0: no tape -> None, else -> an NrTape that
+        borrows `storage` (the caller keeps it alive)"""
+        host, dev = [], []
+        for x, shape in ((K, (3, 3)), (R, (3, 3)), (t, (3,))):
+            by_address = isinstance(x, int)
+            host.append(None if ndc or by_address else _f32(x, shape))
+            dev.append(x if by_address and not ndc else None)
+        cam = _lib.NrCameraDev(*dev)
+        h = C.c_void_p()
+        ws = self.workspace()
+        with ws.lock:
+            _lib.check(self._lib.bf_nr_render_dev(self._h, mesh._h, _lib.fptr(host[0]), _lib.fptr(host[1]), _lib.fptr(host[2]), float(orig_size),
+                                                  int(bool(fill_back)), int(bool(lightoff)), int(bool(ndc)), rgb or None, depth or None, alpha or None,
+                                                  int(flags), C.byref(h) if flags else None, verts or None, textures or None, C.byref(cam),
+                                                  storage or None, int(storage_floats), ws._h, stream or None), "bf_nr_render_dev")
+        return NrTape(h, mesh.textures_shape, mesh.n_verts, self.image_size, workspace=ws) if flags else None
 
     def render(self, mesh, K=None, R=None, t=None, orig_size=1.0, fill_back=True, lightoff=False, ndc=False, want=("rgb", "depth", "alpha"),
                tape=False):
@@ -800,6 +858,7 @@ class NrRenderer:
 
     def close(self):
         if getattr(self, "_h", None):
+            _close_workspace(self)
             self._lib.bf_nr_destroy(self._h)
             self._h = None
 
@@ -844,9 +903,27 @@ class NrMesh:
 class NrTape:
     """bf_nr_tape: what the texture VJP and (a geometry tape) the vertex / camera VJP need of one render"""
 
-    def __init__(self, handle, textures_shape, n_verts=0, image_size=0):
+    def __init__(self, handle, textures_shape, n_verts=0, image_size=0, workspace=None):
         self._lib, self._h, self.textures_shape = _lib.load(), handle, tuple(textures_shape)
         self.n_verts, self.image_size = int(n_verts), int(image_size)
+        self._workspace = workspace          # a tape of render_dev: its renderer's
+
+    def vertex_grad_dev(self, stream, grad_verts, grad_rgb=0, grad_depth=0, grad_alpha=0, grad_R=0, grad_t=0):
+        """bf_nr_tape_vertex_grad_dev: device addresses all (0: a zero cotangent / a gradient not wanted); grad_verts[NV,3] is written"""
+        if not self._h:
+            raise _lib.BodyfitError("NrTape.vertex_grad_dev: the tape was closed")
+        with self._workspace.lock:
+            _lib.check(self._lib.bf_nr_tape_vertex_grad_dev(self._h, grad_rgb or None, grad_depth or None, grad_alpha or None, grad_verts or None,
+                                                            grad_R or None, grad_t or None, self._workspace._h, stream or None),
+                       "bf_nr_tape_vertex_grad_dev")
+
+    def texture_grad_dev(self, stream, grad_rgb, grad_textures):
+        """bf_nr_tape_texture_grad_dev: grad_rgb[3,is,is] -> grad_textures[NF,ts,ts,ts,3], device addresses"""
+        if not self._h:
+            raise _lib.BodyfitError("NrTape.texture_grad_dev: the tape was closed")
+        with self._workspace.lock:
+            _lib.check(self._lib.bf_nr_tape_texture_grad_dev(self._h, grad_rgb or None, grad_textures or None, self._workspace._h, stream or None),
+                       "bf_nr_tape_texture_grad_dev")
 
     def vertex_grad(self, grad_rgb=None, grad_depth=None, grad_alpha=None, camera=True):
         """cotangents in the outputs' shapes (None: zero) -> (d / d vertices [NV,3], d / d R [3,3], d / d t [3]); camera=False (an

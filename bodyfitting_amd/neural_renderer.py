@@ -21,6 +21,14 @@ Tensors in give float32 tensors out on the vertices' device; arrays in give arra
 (vertices, faces) object and GPU - stamps and a table of _memo.py: a tensor by identity and version, an array by a digest, four at
 a time - and a mesh's textures go up again only when their stamp no longer holds: in the reference's loop the scan's once, the
 fitted ones once per `optimizer.step()`.  torch is imported on first use only.
+
+The DEVICE route: when `vertices` - and `textures`, where the render uses them - are float32 tensors on
+one GPU and `_autograd.route_for` says so, nothing above applies: the kernels read the tensors where they lie and write the images
+and gradients into torch tensors on torch's current stream (bf_nr_render_dev, bf_nr_tape_*_dev); a mesh is remembered by its
+faces, vertex count and GPU only, nothing is sent again, and `K`, `R`, `t` are each read by address (a float32 tensor on that GPU)
+or taken by value (anything else).  DEVICE_ROUTE, read once from BF_NR_DEVICE_ROUTE ("0" = off; the default is
+DEVICE_ROUTE_DEFAULT, on), switches it for this module; BF_TORCH_DEVICE_ROUTE=0 switches it off with every other drop-in's.
+`render_texture` stays on the host route.
 """
 from __future__ import annotations
 
@@ -41,6 +49,9 @@ _NOT_BUILT = ("get_points_from_angles", "lighting", "look", "look_at", "Mesh", "
               "rasterize", "rasterize_silhouettes", "rasterize_depth", "Rasterize", "vertices_to_faces", "cuda")
 _MESH_SLOTS = 4
 GEOMETRY_GRAD = os.environ.get("BF_NR_GEOMETRY_GRAD", "") == "1"
+# on: measured ahead of the parent commit's host route by more than both sides' ranges at the reference's loop size (profiles/nr_device_route.md)
+DEVICE_ROUTE_DEFAULT = "1"
+DEVICE_ROUTE = os.environ.get("BF_NR_DEVICE_ROUTE", DEVICE_ROUTE_DEFAULT).strip() != "0"
 _NO_K_GRAD = ("neural_renderer.Renderer: K is not differentiated (geometry_grad covers `vertices`, `R` and `t`, not the intrinsics); "
               "detach K first")
 _NO_VERTEX_GRAD = ("neural_renderer.Renderer: the soft-edge vertex gradient (backward_pixel_map, backward_depth_map of "
@@ -69,6 +80,11 @@ def _gpu_of(x):
     return x.device.index or 0 if _is_tensor(x) and x.device.type == "cuda" else 0
 
 
+def _readable_on(x, gpu):
+    """can a kernel on GPU `gpu` read `x` where it lies: a float32 tensor there"""
+    return _is_tensor(x) and x.device.type == "cuda" and (x.device.index or 0) == gpu and str(x.dtype) == "torch.float32" and hasattr(x, "data_ptr")
+
+
 def _close_meshes(entry):
     for m in entry["meshes"]:
         m.close()
@@ -95,6 +111,69 @@ class _Tapes:
             self.close()
         except Exception:
             pass
+
+
+class _DeviceTapes(_Tapes):
+    """... of the device route: each tape borrows one float32 tensor, held here and dropped with the tapes - torch's stream-ordered
+    allocator owns its lifetime, so nothing waits"""
+
+    def __init__(self):
+        _Tapes.__init__(self)
+        self.storage = []
+
+    def close(self):
+        _Tapes.close(self)
+        self.storage = []
+
+
+def _sum_in_item_order(rows):
+    """((g0 + g1) + g2) ...: the order numpy's sum(0, dtype=float32) adds the rows of a small array in"""
+    total = rows[0]
+    for g in rows[1:]:
+        total = total + g
+    return total
+
+
+class _DeviceRender:
+    """the `device_route` object of _autograd.apply for one differentiable render: inputs (vertices, textures, R, t) in that order,
+    None where one takes no gradient.  render(v, tex, R, t, flags, held) -> the outputs; it is the Renderer's closure"""
+
+    def __init__(self, device, render, names, flags, ndc):
+        self.device, self.render, self.names, self.flags, self.ndc = device, render, names, flags, ndc
+        self.held = _DeviceTapes()
+
+    def forward(self, tensors, stream):
+        return self.render(tensors, self.flags, self.held, stream)
+
+    def vjp(self, tensors, cotangents, want, stream):
+        import torch
+        tapes = self.held.live()
+        v, tex, R, t = tensors
+        g = dict(zip(self.names, cotangents))
+        like = next(x for x in tensors if x is not None)
+        grads = [None, None, None, None]
+        B = len(tapes)
+        if self.flags & native.TAPE_GEOMETRY and (want[0] or want[2] or want[3]):
+            gv = torch.empty((B, tapes[0].n_verts, 3), dtype=torch.float32, device=like.device)
+            gR = torch.empty((B, 3, 3), dtype=torch.float32, device=like.device) if R is not None else None
+            gt = torch.empty((B, 3), dtype=torch.float32, device=like.device) if t is not None else None
+            for b, tp in enumerate(tapes):
+                cot = [0 if g.get(nm) is None else g[nm][b].data_ptr() for nm in ("rgb", "depth", "alpha")]
+                tp.vertex_grad_dev(stream, gv[b].data_ptr(), cot[0], cot[1], cot[2], 0 if gR is None else gR[b].data_ptr(),
+                                   0 if gt is None else gt[b].data_ptr())
+            grads[0] = gv if v is not None else None
+            for slot, x, each in ((2, R, gR), (3, t, gt)):
+                if x is not None:                            # a camera shared by the batch takes the sum over its items
+                    grads[slot] = each if x.numel() == each.numel() else _sum_in_item_order([each[b] for b in range(B)])
+        if tex is not None and want[1]:
+            if g.get("rgb") is None:
+                grads[1] = torch.zeros_like(tex)
+            else:
+                grads[1] = torch.empty_like(tex)
+                for b, tp in enumerate(tapes):
+                    tp.texture_grad_dev(stream, g["rgb"][b].data_ptr(), grads[1][b].data_ptr())
+        self.held.close()
+        return grads
 
 
 class Renderer:
@@ -197,6 +276,100 @@ class Renderer:
             entry["tex"] = _memo.Stamp(textures)
         return entry["meshes"]
 
+    def _topology_meshes(self, r, gpu, faces, nv, ts, f_host):
+        """the device route's meshes: the topology, texture size and tile lists of these faces - nothing of the vertices or textures,
+        which the kernels read where the caller holds them.  Remembered by the faces' stamp, NV and GPU"""
+        sf = _memo.Stamp(faces)
+        key = (sf.part, int(nv), gpu, "device")
+        entry = _memo.find(self._meshes, key)
+        if entry is not None and not (entry["f"].still(faces) and (not ts or entry["ts"] == ts)):      # (_meshes_for's rule: a render without textures takes the mesh as it is)
+            _memo.drop(self._meshes, key, _close_meshes)
+            entry = None
+        if entry is None:
+            f = f_host()
+            _memo.room(self._meshes, _MESH_SLOTS, key, _close_meshes)
+            blank = np.zeros((int(nv), 3), np.float32)              # (never read: bf_nr_render_dev takes the caller's vertices)
+            entry = {"v": None, "f": sf, "gpu": gpu, "ts": ts, "tex": None, "meshes": [native.NrMesh(r, blank, f[b], ts) for b in range(len(f))]}
+            entry = _memo.store(self._meshes, _MESH_SLOTS, key, (), entry, closed=_close_meshes)
+        return entry["meshes"]
+
+    def _on_device_route(self, r, gpu, vertices, textures, differentiated=()):
+        """_autograd.route_for's answer for this render: a renderer that offers the route, the switches, one HIP runtime, and float32
+        tensors on the renderer's GPU - the vertices, the textures a render uses, and an `R` or `t` that takes a gradient"""
+        offers = getattr(type(r), "offers_dev", None)
+        if not DEVICE_ROUTE or offers is None or not offers():
+            return False
+        present = [x for x in (vertices, textures) if x is not None] + list(differentiated)
+        return _autograd.takes_device_route(gpu, *present)
+
+    def _render_device(self, r, gpu, vertices, faces, textures, K, R, t, orig_size, lightoff, want, fill_back, ndc, geometry, tex_in):
+        """the device route of `_render`: see the module's text.  geometry: [vertices, R, t] that take a gradient (None: not);
+        tex_in: the textures when they do"""
+        import torch
+        B, nv, n = int(vertices.shape[0]), int(vertices.shape[1]), int(self.image_size)
+        ts = 0 if textures is None else int(textures.shape[2])
+        names = [nm for nm in ("rgb", "depth", "alpha") if nm in want]
+        device = vertices.device
+
+        def camera_part(x, shape, nm):
+            """-> (a contiguous [n, *shape] tensor of the GPU, None) to read by address, or (None, a host array) to take by value"""
+            if _readable_on(x, gpu):
+                x = x.detach().reshape((-1,) + shape).contiguous()
+                count = int(x.shape[0])
+            else:
+                x = _host(x).reshape((-1,) + shape)
+                count = len(x)
+            if count not in (1, B):
+                raise ValueError(f"{nm} must have batch size 1 or {B}, not {count}")
+            return (x, None) if _is_tensor(x) else (None, x)
+
+        fixed = None if ndc else [camera_part(K, (3, 3), "K"), camera_part(R, (3, 3), "R"), camera_part(t, (3,), "t")]
+
+        def item(part, b, floats):
+            tensor, array = part
+            if tensor is not None:
+                return tensor.data_ptr() + (b % int(tensor.shape[0])) * floats * 4
+            return array[b % len(array)]
+
+        def render(tensors, flags, held, stream):
+            v, tex, R_in, t_in = tensors
+            v = vertices.detach().contiguous() if v is None else v
+            tex = (None if textures is None else textures.detach().contiguous()) if tex is None else tex
+            cam = fixed
+            if not ndc and (R_in is not None or t_in is not None):
+                cam = list(fixed)
+                if R_in is not None:
+                    cam[1] = (R_in.reshape(-1, 3, 3), None)
+                if t_in is not None:
+                    cam[2] = (t_in.reshape(-1, 3), None)
+            meshes = self._topology_meshes(r, gpu, faces, nv, ts, lambda: _host(faces, np.int32))
+            out = {"rgb": torch.empty((B, 3, n, n), dtype=torch.float32, device=device) if "rgb" in want else None,
+                   "depth": torch.empty((B, n, n), dtype=torch.float32, device=device) if "depth" in want else None,
+                   "alpha": torch.empty((B, n, n), dtype=torch.float32, device=device) if "alpha" in want else None}
+            lit = not lightoff and ("rgb" in want or bool(flags & native.TAPE_TEXTURES))
+            for b, m in enumerate(meshes):
+                args = dict(ndc=True) if ndc else dict(K=item(cam[0], b, 9), R=item(cam[1], b, 9), t=item(cam[2], b, 3), orig_size=float(orig_size))
+                floats = r.tape_floats(m, fill_back, lit, flags, "rgb" in want)
+                storage = torch.empty((floats,), dtype=torch.float32, device=device) if flags else None
+                tp = r.render_dev(m, stream, v[b].data_ptr(), 0 if tex is None else tex[b].data_ptr(), fill_back=fill_back, lightoff=lightoff,
+                                  rgb=0 if out["rgb"] is None else out["rgb"][b].data_ptr(),
+                                  depth=0 if out["depth"] is None else out["depth"][b].data_ptr(),
+                                  alpha=0 if out["alpha"] is None else out["alpha"][b].data_ptr(),
+                                  flags=flags, storage=0 if storage is None else storage.data_ptr(), storage_floats=floats, **args)
+                if flags:
+                    held.tapes.append(tp)
+                    held.storage.append(storage)
+            return tuple(out[nm] for nm in names)
+
+        if any(x is not None for x in geometry):
+            flags = native.TAPE_GEOMETRY | (native.TAPE_TEXTURES if tex_in is not None else 0)
+            route = _DeviceRender(gpu, render, names, flags, ndc)
+            return _autograd.apply(None, None, [geometry[0], tex_in, geometry[1], geometry[2]], device_route=route)
+        if tex_in is not None:
+            route = _DeviceRender(gpu, render, names, native.TAPE_TEXTURES, ndc)
+            return _autograd.apply(None, None, [None, tex_in, None, None], device_route=route)
+        return render([None, None, None, None], 0, None, _autograd.stream_of(vertices))
+
     # ---- the one render path ----
     def _render(self, vertices, faces, textures, K, R, t, dist_coeffs, orig_size, lightoff, want, fill_back=None, ndc=False, like=None):
         self._zero_distortion(dist_coeffs)
@@ -233,17 +406,22 @@ class Renderer:
         else:
             textures = None
         cams = None
+        if not ndc and (K is None or R is None or t is None):
+            raise ValueError("K, R and t are needed (as arguments or from the constructor) with camera_mode='projection'")
+        gpu = _gpu_of(like)
+        r = self._renderer_on(gpu)
+        fill_back = self.fill_back if fill_back is None else fill_back
+        geometry = [x if wants_grad(x) else None for x in (vertices, None if ndc else R, None if ndc else t)] if self.geometry_grad else [None] * 3
+        if like is vertices:
+            if self._on_device_route(r, gpu, vertices, textures, [x for x in geometry[1:] if x is not None]):
+                return self._render_device(r, gpu, vertices, faces, textures, K, R, t, orig_size, lightoff, want, fill_back, ndc, geometry,
+                                           textures if wants_grad(textures) else None)
         if not ndc:
-            if K is None or R is None or t is None:
-                raise ValueError("K, R and t are needed (as arguments or from the constructor) with camera_mode='projection'")
             Kh, Rh, th = _host(K).reshape(-1, 3, 3), _host(R).reshape(-1, 3, 3), _host(t).reshape(-1, 3)
             for nm, a in (("K", Kh), ("R", Rh), ("t", th)):
                 if len(a) not in (1, B):
                     raise ValueError(f"{nm} must have batch size 1 or {B}, not {len(a)}")
             cams = [(Kh[b % len(Kh)], Rh[b % len(Rh)], th[b % len(th)]) for b in range(B)]
-        gpu = _gpu_of(like)
-        r = self._renderer_on(gpu)
-        fill_back = self.fill_back if fill_back is None else fill_back
         tex_ref = textures
 
         def run(tex_host, tape, flags=None):
@@ -260,7 +438,6 @@ class Renderer:
             stacked = tuple(np.stack([o[i] for o in outs]) for i, nm in enumerate(("rgb", "depth", "alpha")) if nm in want)
             return stacked, tapes
 
-        geometry = [x if wants_grad(x) else None for x in (vertices, None if ndc else R, None if ndc else t)] if self.geometry_grad else [None] * 3
         if any(x is not None for x in geometry):
             held = _Tapes()
             tex_in = textures if wants_grad(textures) else None

@@ -301,7 +301,7 @@ int bf_keypoint_loss_dev(bf_workspace *ws, void *stream, const bf_gmm *gmm, cons
  * of another runtime or device).  Never sets bf_last_error and leaves no HIP error behind. */
 int bf_device_pointer_check(int device, const void *p);
 /* test hook, process-wide counts: out[0] calls of the five host entry points named above, of the SMPL+D stage's losses below
- * (bf_vertex_normals, bf_vertex_normals_vjp, bf_normal_laplacian, bf_scan_point_loss, bf_normal_loss), of bf_scan_nearest and of bf_silhouette_loss,
+ * (bf_vertex_normals, bf_vertex_normals_vjp, bf_normal_laplacian, bf_scan_point_loss, bf_normal_loss), of bf_scan_nearest, of bf_silhouette_loss and of bf_nr_render[_taped], bf_nr_tape_texture_grad, bf_nr_tape_vertex_grad,
  * out[1] calls of the *_dev entry points (both counted once the arguments have passed), out[2] device (re)allocations of workspaces, out[3] calls that had to wait
  * for their workspace's previous call on another stream. */
 int bf_dev_route_stats(int64_t out[4]);
@@ -802,6 +802,40 @@ int bf_nr_render_taped(bf_nr *r, bf_nr_mesh *m, const float *K, const float *R, 
 int bf_nr_tape_vertex_grad(bf_nr_tape *tape, const float *grad_rgb, const float *grad_depth, const float *grad_alpha, float *grad_verts, float *grad_R,
                            float *grad_t);
 void bf_nr_tape_destroy(bf_nr_tape *tape);
+
+/* The device route of the three calls above (see bf_workspace): the caller's arrays are read and written where they lie, on
+ * `stream`, and nothing is copied through the host.  Each counts as a *_dev call in bf_dev_route_stats; bf_nr_render[_taped],
+ * bf_nr_tape_texture_grad and bf_nr_tape_vertex_grad count as host calls.  One workspace per renderer.
+ *
+ * bf_nr_render_dev: bf_nr_render_taped's arguments, then verts[n_verts][3] and textures[n_faces][ts][ts][ts][3] of THIS render
+ * as device pointers (the mesh supplies the topology, the texture size and its tile lists; what bf_nr_mesh_create or
+ * bf_nr_mesh_set_* uploaded is not read), rgb / depth / alpha device pointers, and the camera: each of K, R, t EITHER as the host
+ * pointer of bf_nr_render_taped (taken by value) OR as a device pointer in `cam` (taken by address, never read back) - `cam` NULL
+ * or a NULL member: by value.  A tape borrows its storage: tape_storage, a float32 device array of at least the total
+ * bf_nr_tape_layout gives for this render (tape_floats says how many it holds), which must stay alive and unwritten until the last
+ * gradient call of the tape has run on the device; such a tape owns no device memory, bf_nr_tape_destroy of it waits for nothing,
+ * and it takes the *_dev gradient calls only.  Without a tape, tape_storage is not read.
+ * The call returns when its work is queued, with ONE wait inside: the tile lists' total (4 bytes) is read back behind the
+ * projection, the count pass and the scan, through an event recorded there - not the stream's later work - so that lists that
+ * are too short are grown BEFORE the fill pass: a render is never repeated and no output is written from a truncated list.
+ * Neither gradient call waits for anything.  Refusals: the host twins', and BF_ERR_INVALID for no workspace or one of another
+ * device, a NULL vertex pointer, K / R / t given both ways, tape storage that is NULL or too small when a tape is asked for. */
+typedef struct bf_nr_camera_dev { const float *K, *R, *t; } bf_nr_camera_dev;
+int bf_nr_render_dev(bf_nr *r, bf_nr_mesh *m, const float *K, const float *R, const float *t, float orig_size, int fill_back, int lightoff, int ndc,
+                     float *rgb, float *depth, float *alpha, int tape_flags, bf_nr_tape **tape, const float *verts, const float *textures,
+                     const bf_nr_camera_dev *cam, float *tape_storage, size_t tape_floats, bf_workspace *ws, void *stream);
+/* cotangents and gradients as device pointers; grad_textures is fully written, grad_verts too, grad_R[9] / grad_t[3] where given */
+int bf_nr_tape_texture_grad_dev(bf_nr_tape *tape, const float *grad_rgb, float *grad_textures, bf_workspace *ws, void *stream);
+int bf_nr_tape_vertex_grad_dev(bf_nr_tape *tape, const float *grad_rgb, const float *grad_depth, const float *grad_alpha, float *grad_verts, float *grad_R,
+                               float *grad_t, bf_workspace *ws, void *stream);
+/* where a tape's buffers lie in its storage (csrc/nr_tape_layout.h), in floats: out[0..7] the offsets (multiples of 64) and
+ * out[8..15] the sizes (0: absent) of view | pixel map | face records | light rows | vertices | projected vertices | colour map |
+ * unlit samples, out[16] the total.  is: the super-sampled size, nrec: n_faces or 2 n_faces (fill_back), lit: the render is lit,
+ * flags: BF_NR_TAPE_* (0: a render without a tape), has_rgb: it makes rgb, directional: the light's directional term is not 0. */
+int bf_nr_tape_layout(int is, int nrec, int nv, int lit, int flags, int has_rgb, int directional, uint64_t out[17]);
+/* test hook, process-wide: out[0] renders of bf_nr_render_dev, out[1] tile lists it grew, out[2] bytes read back to the host by
+ * the device-route calls */
+int bf_nr_route_stats(int64_t out[3]);
 
 /* ---- HMR initial estimate (smplify/body_fitting.py:17-75, models/hmr.py) ----------------------------------------------------------
  * The reference's run_hmr on the GPU in fp32: cv2.resize to 224 x 224 (INTER_LINEAR, OpenCV's 8-bit fixed-point arithmetic), /255,
